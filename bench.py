@@ -14,8 +14,13 @@ N > 1 (default --scaling strong): the SAME 8192x8192 image over the N GPUs -- ro
        k-means problem over the 8192 x 8192 N image) is measured right after and reported under `extra.weak_scaling_*`.
 N > 1, --scaling weak: only that.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the step's HBM
+roofline).  --full adds everything else: per-kernel HIP-event times, the roofline against a measured copy, the secondary
+configurations under `extra`, N > 1 weak scaling and one-GPU speed-up, and the CPU baseline.  --dump-outputs DIR writes what
+the last timed step computed (see dump_outputs) for output-by-output comparison of two builds.
 
 Prints ONE JSON line on rank 0.
 """
@@ -572,6 +577,44 @@ class _Loop:
         self.backend, self.acc, self.split_labels, self.k = backend, acc, split_labels, int(k)
 
 
+DUMP_LABEL_SAMPLE = 1 << 22              # label-map entries --dump-outputs keeps (16 MiB as float32)
+DUMP_SEED = 0x5EED0D0
+
+
+def dump_outputs(path, centroids, label_maps, bands, n_band, total_pixels, k, gather=None):
+    """What a caller of the timed loop receives after its last step, as float32 / float64 .npy files under `path`:
+    centroids.npy    (k, 4) float32, kmg_group_lloyd_get_centroids
+    label_counts.npy (k,) float64, pixels per label over the whole label map
+    labels_sample_index.npy / labels_sample.npy   (m,) float64 / float32: the label map at m sorted pixel indices drawn with a
+                     fixed seed (every pixel when the image has at most DUMP_LABEL_SAMPLE of them)
+    `label_maps[i]` holds band `bands[i]` (pixels [bands[i] * n_band, + n_band) of the image); `gather` (N > 1 ranks in processes
+    of their own) collects every rank's pieces on rank 0, which alone writes."""
+    import numpy as np
+    import torch
+    if total_pixels <= DUMP_LABEL_SAMPLE:
+        idx = np.arange(total_pixels, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total_pixels, DUMP_LABEL_SAMPLE, dtype=np.int64))
+    pieces, counts = {}, np.zeros(k, np.float64)
+    for band, labels in zip(bands, label_maps):
+        lo, hi = np.searchsorted(idx, [band * n_band, (band + 1) * n_band])
+        at = torch.from_numpy(idx[lo:hi] - band * n_band).to(labels.device)
+        pieces[band] = labels[at].cpu().numpy()
+        counts += torch.bincount(labels.view(-1).long(), minlength=k)[:k].cpu().numpy()
+    if gather is not None:
+        all_pieces, all_counts = gather((pieces, counts))
+        pieces = {b: v for p in all_pieces for b, v in p.items()}
+        counts = sum(all_counts)
+    if centroids is None:
+        return
+    os.makedirs(path, exist_ok=True)
+    sample = np.concatenate([pieces[b] for b in sorted(pieces)]).astype(np.float32)
+    assert sample.shape == idx.shape
+    for name, a in (("centroids", np.asarray(centroids, np.float32)), ("label_counts", counts),
+                    ("labels_sample_index", idx.astype(np.float64)), ("labels_sample", sample)):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -581,10 +624,15 @@ def main():
     ap.add_argument("--rows", type=int, default=None, help="rows per GPU (default 8192; --scaling strong: 8192 / gpus)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None,
                     help="N > 1: strong (default) = the BASELINE 8192x8192 image split over the GPUs; weak = one 8192-row band "
-                         "per GPU (reported under `extra` by the default run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "per GPU (reported under `extra` by a --full run)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel HIP-event times and rooflines, the secondary configurations (`extra`), "
+                         "N > 1 weak scaling and one-GPU speed-up, and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the untimed extra measurements (use under rocprofv3 to keep kernel averages clean)")
+                    help="with --full: skip the untimed extra measurements (use under rocprofv3 to keep kernel averages clean)")
     ap.add_argument("--overlap", action="store_true",
                     help="N > 1: the all-reduce of the sums on a second stream beside the label pass (KMG_GROUP_OVERLAP); default: "
                          "both ways are tried before the timed region and the faster one is measured")
@@ -717,8 +765,11 @@ def main():
         torch.cuda.synchronize()
         s.close()
         return how, time.perf_counter() - t
-    strategy, t_prep_cold = prepared()
-    _, t_prep = prepared()
+    strategy = t_prep_cold = t_prep = None
+    if args.full or world > 1:
+        strategy, t_prep_cold = prepared()                    # (N > 1: the strategy decides which shardings are tried)
+    if args.full:
+        _, t_prep = prepared()
 
     gl = kg.GroupLloyd(group, k)
     fused = world == 1 and not args.force_dist and not args.separate_update
@@ -812,29 +863,42 @@ def main():
     lloyd, strategy = gl.member(0)
     cells = bool(flags & kg.GROUP_CELLS)
 
-    # HIP events around the heavy launches, on the launch stream.  Inside the timed region only the kernel the roofline is
-    # quoted on carries events (every timed launch puts two event records = ~5 us of idle GPU between the kernels); the other
-    # heavy kernel is timed in a short loop of its own right after the timed one.
+    # --full: HIP events around the heavy launches, on the launch stream.  Inside the timed region only the kernel the roofline
+    # is quoted on carries events (every timed launch puts two event records = ~5 us of idle GPU between the kernels); the other
+    # heavy kernel is timed in a short loop of its own right after the timed one.  A plain run times the steps without events.
     timed_kernels = ["k_assign", "k_labels"] if strategy == "table" else ["k_assign"]
-    lloyd.profile(timed_kernels)
+    if args.full:
+        lloyd.profile(timed_kernels)
     elapsed = timed(gl, args.steps)
     fence(gl)
-    prof = lloyd.profile_read()
-    lloyd.profile(False)
-    if strategy == "table":
-        lloyd.profile(["k_cube"])
-        for _ in range(min(args.steps, 10)):
-            gl.step()
-        gl.sync()
-        prof.update(lloyd.profile_read())
+    if args.dump_outputs:
+        # (before anything else steps the loop: what the last timed step left)
+        gather = None
+        if sync_ranks:
+            def gather(obj):
+                objs = [None] * world
+                dist.all_gather_object(objs, obj)
+                return [o[0] for o in objs], [o[1] for o in objs]
+        dump_outputs(args.dump_outputs, gl.get_centroids() if rank == 0 else None, label_maps,
+                     [first_rank + i for i in range(n_here)], n_local, n_local * world, k, gather)
+    prof = {}
+    if args.full:
+        prof = lloyd.profile_read()
         lloyd.profile(False)
+        if strategy == "table":
+            lloyd.profile(["k_cube"])
+            for _ in range(min(args.steps, 10)):
+                gl.step()
+            gl.sync()
+            prof.update(lloyd.profile_read())
+            lloyd.profile(False)
     elapsed = max_over_ranks(elapsed)
 
     # N > 1: (a) the weak-scaling figure of the same loop (one 8192-row band per GPU, one k-means problem over the 8192 x 8192 N
     # image, row bands + the k x 4 all-reduce) -- same bracket, MAX over the ranks; (b) on rank 0 alone, the SAME 8192 x 8192
     # image on one GPU, so that the line carries the speed-up measured in this very run.  Both under `extra`.
     weak, one_gpu_ms = None, None
-    if multi and args.scaling == "strong" and args.rows is None and not args.no_extras:
+    if multi and args.scaling == "strong" and args.rows is None and args.full and not args.no_extras:
         n_w = WIDTH * ROWS_PER_GPU
         bands_w = [synth.uniform_rgba_torch(seed, n_w, first=(first_rank + i) * n_w, device="cuda") for i in range(n_here)]
         labels_w = [torch.empty(n_w, dtype=torch.int32, device="cuda") for _ in range(n_here)]
@@ -872,7 +936,7 @@ def main():
 
     # what a plain device-to-device copy of the same 2 x 4 B/px reaches on THIS box, for the "achievable" column
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         scratch = torch.empty_like(labels)
         for _ in range(2):
             scratch.copy_(labels)
@@ -887,24 +951,7 @@ def main():
     if rank == 0:
         total_pixels = n_local * world
         ms_per_step = elapsed * 1e3 / args.steps
-        kernels = {name: {"ms_per_launch": ms / cnt, "launches": cnt} for name, (ms, cnt) in prof.items()}
-        dominant = max((nm for nm in prof if algorithmic_bytes(nm, n_local, k) is not None),
-                       key=lambda name: prof[name][0])
-        k_ms = kernels[dominant]["ms_per_launch"]
-        abytes = algorithmic_bytes(dominant, n_local, k)
-        achieved = abytes / (k_ms * 1e-3) / 1e9
         step_gbps = ALGORITHMIC_BYTES_PER_PIXEL * total_pixels / (ms_per_step * 1e-3) / 1e9
-        traffic, traffic_source, tj = None, None, {}
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath) and k == K and rows == ROWS_PER_GPU:
-            with open(tpath) as f:
-                tj = json.load(f)
-            traffic = tj.get("bytes_per_launch", {}).get(dominant)
-            traffic_source = tj.get("source", {}).get(dominant, "profiles/traffic.json (rocprofv3 PMC passes, not this run)")
-        flops = total_pixels * (FLOP_PER_PAIR * k + FLOP_PER_PIXEL)
-        design_floor_ms = None
-        if copy_gbps and "k_cube" in kernels and world == 1:
-            design_floor_ms = ALGORITHMIC_BYTES_PER_PIXEL * total_pixels / (copy_gbps * 1e9) * 1e3 + kernels["k_cube"]["ms_per_launch"]
         scaling_note = {}
         if multi:
             shape = "cells" if cells else "bands"
@@ -932,7 +979,8 @@ def main():
                                    + (", all-reduce beside the label pass" if flags & kg.GROUP_OVERLAP else ""),
                        "driver": "kmg_group_lloyd_* of libkmeans_hip (C ABI): one rank per process, collectives inside the library",
                        "collective_backend": collective_backend, "collective_ranks": group.world,
-                       "strategy": strategy, "prepare_ms": t_prep * 1e3, "prepare_cold_ms": t_prep_cold * 1e3,
+                       "strategy": strategy,
+                       **({"prepare_ms": t_prep * 1e3, "prepare_cold_ms": t_prep_cold * 1e3} if args.full else {}),
                        "label_pass": "before the next iteration",
                        "update": ("by the band's label pass, from the all-reduced sums (kmg_lloyd_labels_from_tables_update)" if cells else
                                   "by the last launch of the assign pass (kmg_lloyd_assign_update)") if flags & kg.GROUP_FUSED_UPDATE
@@ -940,70 +988,89 @@ def main():
                        **scaling_note,
                        **({"sharding_choice": picked} if picked else {})},
             # BASELINE.json quotes "% HBM roofline" on the assign+update LOOP: `achieved` / `frac` are the whole iteration's (8 B/px over
-            # ms_per_step: every launch, gap and collective); the dominant kernel's own figures are under kernel_*
+            # ms_per_step: every launch, gap and collective); the dominant kernel's own figures (--full) are under kernel_*
             "roofline": {"bound": "hbm",
                          "scope": "the whole Lloyd iteration (all launches of assign + update): 8 B/px x pixels / ms_per_step",
                          "achieved": step_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": step_gbps / HBM_PEAK_GBPS,
                          "peak_achievable": HBM_ACHIEVABLE_GBPS, "frac_achievable": step_gbps / HBM_ACHIEVABLE_GBPS,
-                         "copy_measured": copy_gbps,      # torch copy_ of the label map on this box, read + write, GB/s
-                         "frac_of_copy": (step_gbps / copy_gbps) if copy_gbps else None,
-                         "algorithmic_bytes_per_step": ALGORITHMIC_BYTES_PER_PIXEL * total_pixels,
-                         # the floor of THIS design: the label pass cannot beat a device copy of the same
-                         # 8 B/px, and the cube pass moves none of them -- copy (measured on this box, above) + k_cube (measured,
-                         # below).  What the step takes beyond it is gather requests, launch boundaries and the tail.
-                         "design_floor_ms": design_floor_ms,
-                         "design_floor_source": "8 B/px / roofline.copy_measured + kernels.k_cube.ms_per_launch, both measured in this run",
-                         "design_floor_frac": (ALGORITHMIC_BYTES_PER_PIXEL * total_pixels / (design_floor_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS)
-                                              if design_floor_ms else None,
-                         "kernel": dominant,
-                         "kernel_bound": "requests" if dominant == "k_labels" else ("valu" if dominant == "k_assign" else "hbm"),
-                         "kernel_bound_note": "k_labels: a device copy plus divergent gather requests that the vector memory pipeline retires "
-                                              "at ~1 lane per 2 clocks per CU, hit or miss (profiles/NOTES.md); the fraction is still taken "
-                                              "against the HBM roof, the metric BASELINE.json names",
-                         "kernel_ms": k_ms, "kernel_algorithmic_bytes_per_launch": abytes,
-                         "kernel_achieved": achieved, "kernel_frac": achieved / HBM_PEAK_GBPS,
-                         "kernel_frac_achievable": achieved / HBM_ACHIEVABLE_GBPS,
-                         "traffic": traffic, "traffic_source": traffic_source, "traffic_age": tj.get("commit"),
-                         "traffic_note": "counter bytes of the dominant kernel per launch (its algorithmic bytes: kernel_algorithmic_bytes_per_launch)",
-                         # SURVEY 8d's second roof, for orientation only: the time the LITERAL per-pixel scan's flops
-                         # (17 k + 50 per pixel) would need at the fp32 vector peak, against the measured step -- a ratio, not a
-                         # utilisation (the colour table does not execute those flops).  What the kernels really issue is in
-                         # kernels_roofline.*.valu
-                         "literal_scan_valu_floor_ms": flops / (FP32_VECTOR_PEAK_TFLOPS * 1e12) * 1e3,
-                         "literal_scan_valu_floor_over_step": flops / (ms_per_step * 1e-3) / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
-                         "valu_peak_tflops": FP32_VECTOR_PEAK_TFLOPS},
-            "kernels": kernels,
-            # every timed kernel against the HBM roof, from its own algorithmic bytes (k_cube: 2^24 counts in, 2^24 labels out)
-            "kernels_roofline": {nm: {"algorithmic_bytes_per_launch": algorithmic_bytes(nm, n_local, k),
-                                      "achieved_GBps": algorithmic_bytes(nm, n_local, k) / (v["ms_per_launch"] * 1e-3) / 1e9,
-                                      "frac": algorithmic_bytes(nm, n_local, k) / (v["ms_per_launch"] * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                                      "traffic": (tj.get("bytes_per_launch", {}).get(nm) if traffic is not None else None)}
-                                 for nm, v in kernels.items() if algorithmic_bytes(nm, n_local, k) is not None},
-            "kernels_note": "HIP events on the launch stream; the dominant kernel inside the timed region, k_cube in a loop of "
-                            "its own right after it (same state, same launches)",
+                         "algorithmic_bytes_per_step": ALGORITHMIC_BYTES_PER_PIXEL * total_pixels},
         }
-        attach_valu_roof(out["kernels_roofline"], {nm: v["ms_per_launch"] for nm, v in kernels.items()}, tj)
-        if world == 1 and rows == ROWS_PER_GPU and not args.no_extras:
-            acc = torch.zeros((k, 4), dtype=torch.int64, device="cuda")
-            out["extra"] = output_pass_timing(proc, rgba, n_local, stream, _Loop(lloyd, acc, strategy == "table", k), prep_ms=t_prep * 1e3)
-            for name in ("find_dither_k64", "find_replace_k64"):          # the output passes of BASELINE config 5, same roof
-                if name + "_ms" in out["extra"]:
-                    ms = out["extra"][name + "_ms"]
-                    out["kernels_roofline"][name] = {
-                        "algorithmic_bytes_per_launch": ALGORITHMIC_BYTES_PER_PIXEL * n_local,
-                        "achieved_GBps": ALGORITHMIC_BYTES_PER_PIXEL * n_local / (ms * 1e-3) / 1e9,
-                        "frac": ALGORITHMIC_BYTES_PER_PIXEL * n_local / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                        "traffic": tj.get("bytes_per_launch", {}).get(name),
-                        "note": "whole kmg_dev_apply call (all its launches), host clock over 3 calls"}
-            c2 = cfg2_roofline(out["extra"], tj)
-            if c2 is not None:
-                out["kernels_roofline"]["cfg2"] = c2
-            attach_valu_roof(out["kernels_roofline"], {nm[:-3]: ms for nm, ms in out["extra"].items() if nm.endswith("_ms")}, tj)
-        if weak is not None:
-            out.setdefault("extra", {}).update(weak)
-        if not args.no_cpu_baseline:                              # (rank 0, beside every N: north_star)
-            out["cpu_baseline"] = cpu_baseline(k, cent, seed)
+        if args.full:
+            kernels = {name: {"ms_per_launch": ms / cnt, "launches": cnt} for name, (ms, cnt) in prof.items()}
+            dominant = max((nm for nm in prof if algorithmic_bytes(nm, n_local, k) is not None),
+                           key=lambda name: prof[name][0])
+            k_ms = kernels[dominant]["ms_per_launch"]
+            abytes = algorithmic_bytes(dominant, n_local, k)
+            achieved = abytes / (k_ms * 1e-3) / 1e9
+            traffic, traffic_source, tj = None, None, {}
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tpath) and k == K and rows == ROWS_PER_GPU:
+                with open(tpath) as f:
+                    tj = json.load(f)
+                traffic = tj.get("bytes_per_launch", {}).get(dominant)
+                traffic_source = tj.get("source", {}).get(dominant, "profiles/traffic.json (rocprofv3 PMC passes, not this run)")
+            flops = total_pixels * (FLOP_PER_PAIR * k + FLOP_PER_PIXEL)
+            design_floor_ms = None
+            if copy_gbps and "k_cube" in kernels and world == 1:
+                design_floor_ms = ALGORITHMIC_BYTES_PER_PIXEL * total_pixels / (copy_gbps * 1e9) * 1e3 + kernels["k_cube"]["ms_per_launch"]
+            out["roofline"].update({
+                "copy_measured": copy_gbps,      # torch copy_ of the label map on this box, read + write, GB/s
+                "frac_of_copy": (step_gbps / copy_gbps) if copy_gbps else None,
+                # the floor of THIS design: the label pass cannot beat a device copy of the same
+                # 8 B/px, and the cube pass moves none of them -- copy (measured on this box, above) + k_cube (measured,
+                # below).  What the step takes beyond it is gather requests, launch boundaries and the tail.
+                "design_floor_ms": design_floor_ms,
+                "design_floor_source": "8 B/px / roofline.copy_measured + kernels.k_cube.ms_per_launch, both measured in this run",
+                "design_floor_frac": (ALGORITHMIC_BYTES_PER_PIXEL * total_pixels / (design_floor_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS)
+                                     if design_floor_ms else None,
+                "kernel": dominant,
+                "kernel_bound": "requests" if dominant == "k_labels" else ("valu" if dominant == "k_assign" else "hbm"),
+                "kernel_bound_note": "k_labels: a device copy plus divergent gather requests that the vector memory pipeline retires "
+                                     "at ~1 lane per 2 clocks per CU, hit or miss (profiles/NOTES.md); the fraction is still taken "
+                                     "against the HBM roof, the metric BASELINE.json names",
+                "kernel_ms": k_ms, "kernel_algorithmic_bytes_per_launch": abytes,
+                "kernel_achieved": achieved, "kernel_frac": achieved / HBM_PEAK_GBPS,
+                "kernel_frac_achievable": achieved / HBM_ACHIEVABLE_GBPS,
+                "traffic": traffic, "traffic_source": traffic_source, "traffic_age": tj.get("commit"),
+                "traffic_note": "counter bytes of the dominant kernel per launch (its algorithmic bytes: kernel_algorithmic_bytes_per_launch)",
+                # SURVEY 8d's second roof, for orientation only: the time the LITERAL per-pixel scan's flops
+                # (17 k + 50 per pixel) would need at the fp32 vector peak, against the measured step -- a ratio, not a
+                # utilisation (the colour table does not execute those flops).  What the kernels really issue is in
+                # kernels_roofline.*.valu
+                "literal_scan_valu_floor_ms": flops / (FP32_VECTOR_PEAK_TFLOPS * 1e12) * 1e3,
+                "literal_scan_valu_floor_over_step": flops / (ms_per_step * 1e-3) / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
+                "valu_peak_tflops": FP32_VECTOR_PEAK_TFLOPS})
+            out["kernels"] = kernels
+            # every timed kernel against the HBM roof, from its own algorithmic bytes (k_cube: 2^24 counts in, 2^24 labels out)
+            out["kernels_roofline"] = {nm: {"algorithmic_bytes_per_launch": algorithmic_bytes(nm, n_local, k),
+                                            "achieved_GBps": algorithmic_bytes(nm, n_local, k) / (v["ms_per_launch"] * 1e-3) / 1e9,
+                                            "frac": algorithmic_bytes(nm, n_local, k) / (v["ms_per_launch"] * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                            "traffic": (tj.get("bytes_per_launch", {}).get(nm) if traffic is not None else None)}
+                                       for nm, v in kernels.items() if algorithmic_bytes(nm, n_local, k) is not None}
+            out["kernels_note"] = ("HIP events on the launch stream; the dominant kernel inside the timed region, k_cube in a loop of "
+                                   "its own right after it (same state, same launches)")
+            attach_valu_roof(out["kernels_roofline"], {nm: v["ms_per_launch"] for nm, v in kernels.items()}, tj)
+            if world == 1 and rows == ROWS_PER_GPU and not args.no_extras:
+                acc = torch.zeros((k, 4), dtype=torch.int64, device="cuda")
+                out["extra"] = output_pass_timing(proc, rgba, n_local, stream, _Loop(lloyd, acc, strategy == "table", k), prep_ms=t_prep * 1e3)
+                for name in ("find_dither_k64", "find_replace_k64"):          # the output passes of BASELINE config 5, same roof
+                    if name + "_ms" in out["extra"]:
+                        ms = out["extra"][name + "_ms"]
+                        out["kernels_roofline"][name] = {
+                            "algorithmic_bytes_per_launch": ALGORITHMIC_BYTES_PER_PIXEL * n_local,
+                            "achieved_GBps": ALGORITHMIC_BYTES_PER_PIXEL * n_local / (ms * 1e-3) / 1e9,
+                            "frac": ALGORITHMIC_BYTES_PER_PIXEL * n_local / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                            "traffic": tj.get("bytes_per_launch", {}).get(name),
+                            "note": "whole kmg_dev_apply call (all its launches), host clock over 3 calls"}
+                c2 = cfg2_roofline(out["extra"], tj)
+                if c2 is not None:
+                    out["kernels_roofline"]["cfg2"] = c2
+                attach_valu_roof(out["kernels_roofline"], {nm[:-3]: ms for nm, ms in out["extra"].items() if nm.endswith("_ms")}, tj)
+            if weak is not None:
+                out.setdefault("extra", {}).update(weak)
+            if not args.no_cpu_baseline:                          # (rank 0, beside every N: north_star)
+                out["cpu_baseline"] = cpu_baseline(k, cent, seed)
         line = json.dumps(out)
     else:
         line = None

@@ -63,7 +63,7 @@ def test_bench_multi_gpu_path_rehearsed_on_one_gpu(torch_cuda):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for name in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(name, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rehearse"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rehearse", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert r.stdout.count("\n") == 1 and r.stdout.startswith("{"), r.stdout[:300]      # stdout carries the JSON line only

@@ -10,7 +10,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-rXX}
 OUT=$ROOT/gpurun_out
-cd $ROOT && python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+cd $ROOT && python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/${TAG}_ks $OUT/${TAG}_pf $OUT/${TAG}_pw
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_ks -- python3 $ROOT/bench.py --no-cpu-baseline --no-extras > $OUT/${TAG}_ks.log 2>&1

@@ -9,7 +9,7 @@ tag = sys.argv[1] if len(sys.argv) > 1 else "strong"
 out = {"workload": "synthetic uniform 8192x8192, k=256, one Lloyd iteration with the label map", "per_rank": {}}
 for strategy in ("table", "scan"):
     for n in (1, 2, 4, 8):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extras", "--steps", "10",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-extras", "--steps", "10",
                "--rows", str(8192 // n), "--strategy", strategy]
         line = subprocess.run(cmd, capture_output=True, text=True).stdout.strip().splitlines()[-1]
         d = json.loads(line)
