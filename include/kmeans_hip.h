@@ -47,8 +47,30 @@ typedef enum kmg_status {
 
 /* core/src/lib.rs:215-219 `enum Algorithm` */
 typedef enum kmg_algorithm { KMG_ALGO_KMEANS = 0, KMG_ALGO_OCTREE = 1 } kmg_algorithm;
-/* core/src/lib.rs:234-239 `enum ReduceMode` */
-typedef enum kmg_reduce_mode { KMG_MODE_REPLACE = 0, KMG_MODE_DITHER = 1, KMG_MODE_MELD = 2 } kmg_reduce_mode;
+/* core/src/lib.rs:234-239 `enum ReduceMode`, and one mode of this library's own:
+ *
+ * KMG_MODE_DIFFUSE -- Floyd-Steinberg error diffusion onto the palette.  Pixels are visited in raster order (rows top to
+ * bottom, each row left to right; no serpentine).  For each pixel (x, y) and each channel ch in {R, G, B}, in int32:
+ *   S   = 7 e(x-1, y) + 3 e(x+1, y-1) + 5 e(x, y-1) + 1 e(x-1, y-1)     (a neighbour outside the image contributes 0)
+ *   v   = 16 src(x, y) + floor((S + 8) / 16)                             (units of 1/16 LSB; floor = arithmetic >> 4)
+ *   t   = clamp(v, 0, 4080)
+ *   c   = (t + 8) >> 4                                                   (0 .. 255)
+ *   lbl = the label KMG_MODE_REPLACE gives an opaque pixel of colour (c_R, c_G, c_B)
+ *   o   = the bytes KMG_MODE_REPLACE writes for lbl
+ *   out(x, y) = (o_R, o_G, o_B, 255)
+ *   e(x, y)   = t - 16 o                                                 (|e| <= 4080, so |S| <= 65 280)
+ * Input alpha is ignored.  kmg_dev_apply diffuses the given rows as an image of their own (zero error above the band);
+ * kmg_apply_plan_run continues the diffusion across consecutive bands (row0 = the rows done so far, 0 first; the width
+ * unchanged; anything else is KMG_ERR_INVALID_ARGUMENT), each band after the previous one whatever its stream.  A pass in
+ * which nothing moves for about half a second gives up and is reported as KMG_ERR_HIP ("diffusion pass timed out"): by
+ * kmg_dev_apply, by later runs of the plan, and by kmg_apply_plan_status.
+ * The kmg_group_* calls reject this mode (KMG_ERR_INVALID_ARGUMENT): diffusion across row-band ranks is serial by nature. */
+typedef enum kmg_reduce_mode {
+    KMG_MODE_REPLACE = 0,
+    KMG_MODE_DITHER = 1,
+    KMG_MODE_MELD = 2,
+    KMG_MODE_DIFFUSE = 3
+} kmg_reduce_mode;
 
 #define KMG_FIX_SHIFT 20
 /* largest k: the kernels keep 48 bytes of LDS per cluster (centroid + int64 sums), 160 KiB per CU */
@@ -359,6 +381,9 @@ KMG_API int kmg_apply_plan_create(kmg_processor *p, const float *centroids4, uin
 KMG_API int kmg_apply_plan_run(kmg_apply_plan *plan, const uint8_t *d_rgba, uint32_t width, uint32_t rows, uint32_t row0,
                                uint8_t *d_out_rgba, void *stream);
 KMG_API void kmg_apply_plan_destroy(kmg_apply_plan *plan, int synchronise);
+/* KMG_MODE_DIFFUSE: waits for the plan's last run and returns KMG_ERR_HIP if any run of the plan timed out (a band that timed
+ * out also fails every later kmg_apply_plan_run issued after it completed); KMG_OK for the other modes.                          */
+KMG_API int kmg_apply_plan_status(kmg_apply_plan *plan);
 
 /* mix_colors.wgsl:53-67: the dither threshold of a centroid table (host helper).             */
 KMG_API int kmg_dither_threshold(const float *centroids4, uint32_t k, float *threshold);

@@ -235,7 +235,7 @@ try {
     if (color_count == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
     if (!out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
     if (algo != KMG_ALGO_KMEANS && algo != KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown algorithm %d", algo);
-    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
+    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_DIFFUSE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
     if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
         return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
     HIP_TRY(hipSetDevice(p->device));

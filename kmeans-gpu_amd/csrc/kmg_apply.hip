@@ -3,6 +3,8 @@
 
 #include "kmg_state.h"
 
+#include <cmath>
+
 // Same model for the replace-mode output pass (no histogram: every cell is labelled; scratch from the processor's
 // blocks).
 static bool replace_table_pays(const kmg_processor *p, uint64_t n, uint32_t k)
@@ -12,6 +14,18 @@ static bool replace_table_pays(const kmg_processor *p, uint64_t n, uint32_t k)
     const double brute = N * (8.1e-12 + 2.45e-13 * k);
     const double table = 9.0e-5 + 1.85e-7 * k + N * (k <= 256 ? 1.8e-12 + 2.0e-15 * k : 6.6e-12);
     return table < brute;
+}
+
+// Error-diffusion output pass (kmg_diffuse.hip): the colour table costs its build (the replace route's model above) and then a
+// few LDS reads per step; the per-lane scan costs ~k key evaluations per step on the critical path, which for a W x H image is
+// W + 2 (H - 1) steps -- about 3 sqrt(n) for the shapes of photographs (an estimate from the step counts; not fitted).
+static bool diffuse_table_pays(const kmg_processor *p, uint64_t n, uint32_t k)
+{
+    if (k < 2) return false;                                // one colour: nothing to look up
+    if (const int f = forced_strategy(p)) return f > 0;
+    const double steps = 3.0 * std::sqrt((double)n);
+    const double table = 9.0e-5 + 1.85e-7 * k;
+    return steps * 6.0e-9 * k > table;
 }
 
 // Dither output pass: per-pixel scan of all k centroids, or of the candidates of the pixel's cell only (k <= 256: byte lists per
@@ -181,7 +195,7 @@ struct kmg_apply_plan {
     int mode = 0;
     bool dither = false;
     float thr = 0.0f;
-    enum Route { kScan, kMeldScan, kMeldMasks, kMeldLists, kReplaceTable, kDitherLists, kDitherMasks } route = kScan;
+    enum Route { kScan, kMeldScan, kMeldMasks, kMeldLists, kReplaceTable, kDitherLists, kDitherMasks, kDiffuseTable, kDiffuseScan } route = kScan;
     ArenaGuard arena;
     std::vector<uint8_t> staged;        // host copy of the tables: lives as long as the asynchronous upload may
     Centroid *d_cent = nullptr;
@@ -190,6 +204,21 @@ struct kmg_apply_plan {
     uint16_t *sub = nullptr;            // kReplaceTable: the label pass's first-level tables
     hipEvent_t ready = nullptr;         // the tables are built (recorded on the creating stream)
     hipStream_t built_on = nullptr;
+    // KMG_MODE_DIFFUSE: the diffusion continues across the bands of consecutive runs
+    // dstate: 2 x width packed error rows, the sticky timeout word (zeroed once), the per-call control block (kmg_diffuse.hip);
+    // stream-ordered from the processor's pool on the first run's stream, given back on `built_on` (every stream is idle by then)
+    void *dstate = nullptr;
+    uint32_t dwidth = 0, drows = 0, dparity = 0;
+    hipEvent_t ddone = nullptr;         // the previous run's pass has completed (the next one waits on it, on any stream)
+    void *h_slot = nullptr;             // page-locked slot of the processor (host_slot_take) for the sticky word's read-back
+    uint32_t h_word = 0;                // (the same in pageable memory when no slot is left)
+    volatile uint32_t *h_timeout = &h_word;
+    ~kmg_apply_plan()
+    {
+        if (dstate) (void)hipFreeAsync(dstate, built_on);
+        if (ddone) (void)hipEventDestroy(ddone);
+        if (h_slot) host_slot_give(p, h_slot);
+    }
 };
 
 extern "C" int kmg_apply_plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, uint64_t n_pixels_hint, void *stream,
@@ -198,7 +227,7 @@ try {
     if (!p || !c4 || !out || k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply_plan arguments");
     *out = nullptr;
     if (k > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", k, KMG_MAX_K);
-    if (mode != KMG_MODE_REPLACE && mode != KMG_MODE_DITHER && mode != KMG_MODE_MELD)
+    if (mode != KMG_MODE_REPLACE && mode != KMG_MODE_DITHER && mode != KMG_MODE_MELD && mode != KMG_MODE_DIFFUSE)
         return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
     HIP_TRY(hipSetDevice(p->device));
     kmg_apply_plan *pl = new (std::nothrow) kmg_apply_plan();
@@ -229,8 +258,9 @@ try {
     // which route (by the number of pixels the plan is made for), and how much scratch it needs: one block per plan
     const uint64_t n_px = n_pixels_hint;
     const bool meld_masks_pay = mode == KMG_MODE_MELD && k >= 2 && meld_pruning_pays(p, n_px, k);
-    const bool replace_table = mode != KMG_MODE_MELD && !dither && replace_table_pays(p, n_px, k);
-    const bool dither_pruned = mode != KMG_MODE_MELD && dither && dither_pruning_pays(p, n_px, k);
+    const bool diffuse = mode == KMG_MODE_DIFFUSE;
+    const bool replace_table = diffuse ? diffuse_table_pays(p, n_px, k) : (mode != KMG_MODE_MELD && !dither && replace_table_pays(p, n_px, k));
+    const bool dither_pruned = mode != KMG_MODE_MELD && !diffuse && dither && dither_pruning_pays(p, n_px, k);
     const size_t tables_bytes = sizeof(Centroid) * k + sizeof(uint32_t) * (k + 1);
     const size_t sub_bytes = sizeof(uint16_t) * (kSubCells + kCells) + sizeof(uint32_t) * kCells;
     const size_t labels_bytes = (size_t)(k <= 256 ? 1 : 2) << 24;
@@ -283,8 +313,10 @@ try {
             void *cwork = arena.take(cube_work_bytes());
             e = launch_cube(nullptr, nullptr, nullptr, nullptr, nullptr, p->d_bounds, p->d_sub_bounds, d_cent, k, p->d_lab_table,
                             m, cwork, colour_labels, sub, nullptr, 0, 0u, nullptr, S(stream), nullptr, affine_for(p, k, S(stream)));
-            pl->aux = colour_labels; pl->sub = sub; pl->route = kmg_apply_plan::kReplaceTable;
+            pl->aux = colour_labels; pl->sub = sub; pl->route = diffuse ? kmg_apply_plan::kDiffuseTable : kmg_apply_plan::kReplaceTable;
         }
+    } else if (diffuse) {
+        pl->route = kmg_apply_plan::kDiffuseScan;
     } else if (dither_pruned) {
         // dither on a large image: candidate lists per cell of a grid over Lab (mask words per (colour cell, Bayer index)
         // above k = 512), then a scan of the pixel's candidates only
@@ -299,12 +331,70 @@ try {
         }
     }
     if (rc != KMG_OK) return rc;
+    if (e == hipSuccess && diffuse) e = hipEventCreateWithFlags(&pl->ddone, hipEventDisableTiming);
+    if (e == hipSuccess && diffuse && (pl->h_slot = host_slot_take(p)) != nullptr) pl->h_timeout = static_cast<uint32_t *>(pl->h_slot);
+    if (e == hipSuccess && diffuse) *pl->h_timeout = 0;
     if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->ready, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventRecord(pl->ready, S(stream));
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP, "apply plan failed: %s", hipGetErrorString(e));
     undo.pl = nullptr;
     *out = pl;
     return KMG_OK;
+}
+KMG_ABI_CATCH
+
+// KMG_MODE_DIFFUSE: one band of the diffusion.  The bands of one plan are consecutive rows of one image (row0 = the rows done
+// so far, the width unchanged); each run waits on the previous run's completion event, so bands issued on several streams still
+// execute in order, and each continues from the error row the previous one left in the plan's scratch.
+static int run_diffuse(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, uint8_t *d_out, hipStream_t st)
+{
+    kmg_processor *p = pl->p;
+    if (w > 0x7FFFFF00u) return fail(KMG_ERR_UNSUPPORTED, "diffusion needs a width below 2^31 - 256");
+    if (row0 != pl->drows) return fail(KMG_ERR_INVALID_ARGUMENT, "diffusion band starts at row %u, the plan has done %u rows", row0, pl->drows);
+    if (pl->drows && w != pl->dwidth) return fail(KMG_ERR_INVALID_ARGUMENT, "diffusion band has width %u, the image has %u", w, pl->dwidth);
+    // an earlier band that timed out (the sticky word; known once a run after it has completed) fails every later run
+    if (pl->drows && hipEventQuery(pl->ddone) == hipSuccess && *pl->h_timeout)
+        return fail(KMG_ERR_HIP, "diffusion pass timed out");
+    const size_t erow_bytes = sizeof(uint32_t) * 2 * 2 * (size_t)w;
+    const size_t sticky_off = (erow_bytes + 255) & ~(size_t)255, ctl_off = sticky_off + 16;
+    const size_t ctl_bytes = (diffuse_ctl_bytes() + 15) & ~(size_t)15;
+    if (!pl->dstate) {
+        HIP_TRY(pool_alloc(p, &pl->dstate, ctl_off + ctl_bytes, st));
+        HIP_TRY(hipMemsetAsync((uint8_t *)pl->dstate + sticky_off, 0, 16, st));
+    }
+    uint8_t *erow = (uint8_t *)pl->dstate, *ctl = erow + ctl_off;
+    uint32_t *sticky = (uint32_t *)(erow + sticky_off);
+    HIP_TRY(hipStreamWaitEvent(st, pl->ready, 0));
+    if (pl->drows) HIP_TRY(hipStreamWaitEvent(st, pl->ddone, 0));
+    else HIP_TRY(hipMemsetAsync(erow + (size_t)pl->dparity * 8u * w, 0, 8u * (size_t)w, st));    // no row above the image
+    HIP_TRY(hipMemsetAsync(ctl, 0, ctl_bytes, st));
+    const bool table = pl->route == kmg_apply_plan::kDiffuseTable;
+    const int route = !table ? kDiffuseScan : (pl->k <= 256 ? kDiffusePairs : kDiffuseCells);
+    hipError_t e = launch_diffuse(route, (const uint32_t *)d_rgba, w, rows, (uint32_t *)d_out, erow, pl->dparity, ctl, sticky, pl->d_cent,
+                                  pl->k, p->d_lut, pl->d_pal, pl->aux, pl->sub, st);
+    if (e == hipSuccess) e = hipMemcpyAsync((void *)pl->h_timeout, sticky, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipEventRecord(pl->ddone, st);
+    if (e != hipSuccess) return fail(KMG_ERR_HIP, "diffusion failed: %s", hipGetErrorString(e));
+    pl->dwidth = w;
+    pl->drows += rows;
+    pl->dparity = (pl->dparity + (rows + 63u) / 64u) & 1u;
+    return KMG_OK;
+}
+
+// kmg_dev_apply and kmg_apply_plan_status: did any diffusion run of the plan time out?  (Read after the last run has completed.)
+static int diffuse_status(kmg_apply_plan *pl)
+{
+    if (pl->mode == KMG_MODE_DIFFUSE && *pl->h_timeout) return fail(KMG_ERR_HIP, "diffusion pass timed out");
+    return KMG_OK;
+}
+
+extern "C" int kmg_apply_plan_status(kmg_apply_plan *pl)
+try {
+    if (!pl) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply_plan_status arguments");
+    if (pl->mode != KMG_MODE_DIFFUSE || !pl->drows) return KMG_OK;
+    HIP_TRY(hipSetDevice(pl->p->device));
+    HIP_TRY(hipEventSynchronize(pl->ddone));                          // (the last run, and with it the read-back of the sticky word)
+    return diffuse_status(pl);
 }
 KMG_ABI_CATCH
 
@@ -316,6 +406,7 @@ try {
     if ((uint64_t)w * rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
     kmg_processor *p = pl->p;
     HIP_TRY(hipSetDevice(p->device));
+    if (pl->mode == KMG_MODE_DIFFUSE) return run_diffuse(pl, d_rgba, w, rows, row0, d_out, S(stream));
     if (S(stream) != pl->built_on) HIP_TRY(hipStreamWaitEvent(S(stream), pl->ready, 0));      // (another stream: after the tables)
     const uint64_t n_px = (uint64_t)w * rows;
     const uint32_t k = pl->k;
@@ -369,8 +460,10 @@ try {
     kmg_apply_plan *pl = nullptr;
     int rc = kmg_apply_plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, &pl);
     if (rc != KMG_OK) return rc;
-    rc = kmg_apply_plan_run(pl, d_rgba, w, rows, row0, d_out, stream);
+    // (diffusion: the band is an image of its own -- the plan is new, so its first run starts from a zero error row)
+    rc = kmg_apply_plan_run(pl, d_rgba, w, rows, mode == KMG_MODE_DIFFUSE ? 0u : row0, d_out, stream);
     const hipError_t e2 = hipStreamSynchronize(S(stream));            // the call returns when the band is written; the block is idle again
+    if (rc == KMG_OK && e2 == hipSuccess) rc = diffuse_status(pl);
     kmg_apply_plan_destroy(pl, 0);
     if (rc != KMG_OK) return rc;
     if (e2 != hipSuccess) return fail(KMG_ERR_HIP, "apply failed: %s", hipGetErrorString(e2));

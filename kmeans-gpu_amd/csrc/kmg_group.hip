@@ -1367,6 +1367,7 @@ extern "C" int kmg_group_reduce_batch(kmg_group *g, uint32_t n_images, const uin
                                       const uint32_t *heights, uint32_t color_count, int algo, int mode, uint8_t *const *out_rgba)
 try {
     if (!g || !rgba || !widths || !heights || !out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "bad group_reduce_batch arguments");
+    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);   // (no diffusion)
     if (g->world != g->n_local) return fail(KMG_ERR_UNSUPPORTED, "the host-buffer calls of a group need all its ranks in one process");
     std::lock_guard<std::mutex> lock(g->call_mu);
     // whole images per device, no exchange of any kind: a failure of one image must not leave the others' ranks waiting

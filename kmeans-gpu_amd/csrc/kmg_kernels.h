@@ -103,4 +103,18 @@ hipError_t launch_encode_check(const float *thr, unsigned long long *bad, hipStr
 hipError_t launch_meld(const uint32_t *rgba, uint64_t n, const Centroid *cent, uint32_t k, const float *lut,
                        const uint64_t *masks, uint32_t *out, hipStream_t st);
 
+// error-diffusion output pass, KMG_MODE_DIFFUSE (kmg_diffuse.hip).  route: how a quantised colour finds its label --
+// kDiffuseScan: per-lane arg-min over cent (LDS); kDiffusePairs (k <= 256) / kDiffuseCells (k > 256): the replace pass's colour
+// table (colour_labels + sub_table of launch_cube without histogram).  erow: 2 x w packed error words, row `parity` = the error of
+// the row above the band (zero for a first band); the band leaves its last row's error in row (parity + chunks) & 1.
+// ctl: diffuse_ctl_bytes() of per-call control words, zero on entry; ctl word 1 != 0 afterwards = the pass timed out.
+// sticky: a word the caller zeroes once; a pass that times out also sets it (so a later pass does not hide the failure).
+enum { kDiffuseScan = 0, kDiffusePairs = 1, kDiffuseCells = 2 };
+constexpr uint32_t kDiffuseRing = 1024;
+size_t diffuse_ctl_bytes();
+uint32_t diffuse_grid(int route, uint32_t rows);
+hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t *out, void *erow, uint32_t parity,
+                          void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
+                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st);
+
 }  // namespace kmg

@@ -31,12 +31,12 @@ struct RGBA8 {                      // rgb::RGBA8 re-export (lib.rs:3)
 static_assert(sizeof(RGBA8) == 4, "RGBA8 must be 4 tightly packed bytes");
 
 enum class Algorithm { Kmeans = KMG_ALGO_KMEANS, Octree = KMG_ALGO_OCTREE };                  // lib.rs:215-219
-enum class ReduceMode { Replace = KMG_MODE_REPLACE, Dither = KMG_MODE_DITHER, Meld = KMG_MODE_MELD };  // lib.rs:234-239
+enum class ReduceMode { Replace = KMG_MODE_REPLACE, Dither = KMG_MODE_DITHER, Meld = KMG_MODE_MELD, Diffuse = KMG_MODE_DIFFUSE };  // lib.rs:234-239
 
 inline const char *to_string(Algorithm a) { return a == Algorithm::Kmeans ? "kmeans" : "octree"; }   // lib.rs:221-232
 inline const char *to_string(ReduceMode m)                                                           // lib.rs:241-253
 {
-    return m == ReduceMode::Replace ? "replace" : m == ReduceMode::Dither ? "dither" : "meld";
+    return m == ReduceMode::Replace ? "replace" : m == ReduceMode::Dither ? "dither" : m == ReduceMode::Meld ? "meld" : "diffuse";
 }
 
 struct Error : std::runtime_error {

@@ -55,10 +55,11 @@ class Algorithm(enum.IntEnum):          # core/src/lib.rs:215-219
     Octree = 1
 
 
-class ReduceMode(enum.IntEnum):         # core/src/lib.rs:234-239
+class ReduceMode(enum.IntEnum):         # core/src/lib.rs:234-239, plus Diffuse (include/kmeans_hip.h KMG_MODE_DIFFUSE)
     Replace = 0
     Dither = 1
     Meld = 2
+    Diffuse = 3                         # Floyd-Steinberg error diffusion (not in the reference; no Group support)
 
 
 class Options(C.Structure):             # include/kmeans_hip.h kmg_options
@@ -137,7 +138,7 @@ SYMBOLS = [
     "kmg_lloyd_unbind_image", "kmg_debug_bound_image", "kmg_lloyd_prepare", "kmg_debug_check_table", "kmg_debug_table_stats", "kmg_debug_check_pairs", "kmg_debug_check_dither_masks", "kmg_debug_check_meld_masks", "kmg_kernel_name",
     "kmg_lloyd_profile", "kmg_lloyd_profile_read",
     "kmg_lloyd_update", "kmg_lloyd_assign_update", "kmg_lloyd_set_cell_share", "kmg_lloyd_labels_from_tables",
-    "kmg_lloyd_table_buffers", "kmg_lloyd_accumulate_into", "kmg_lloyd_labels_from_tables_update", "kmg_lloyd_histogram_buffer", "kmg_lloyd_rebuild_from_histogram", "kmg_debug_block_counts", "kmg_debug_idle_blocks", "kmg_debug_encode_table_check", "kmg_debug_division_check", "kmg_lloyd_converged_count", "kmg_lloyd_iterate", "kmg_lloyd_flush", "kmg_lloyd_run", "kmg_dev_apply", "kmg_apply_plan_create", "kmg_apply_plan_run", "kmg_apply_plan_destroy",
+    "kmg_lloyd_table_buffers", "kmg_lloyd_accumulate_into", "kmg_lloyd_labels_from_tables_update", "kmg_lloyd_histogram_buffer", "kmg_lloyd_rebuild_from_histogram", "kmg_debug_block_counts", "kmg_debug_idle_blocks", "kmg_debug_encode_table_check", "kmg_debug_division_check", "kmg_lloyd_converged_count", "kmg_lloyd_iterate", "kmg_lloyd_flush", "kmg_lloyd_run", "kmg_dev_apply", "kmg_apply_plan_create", "kmg_apply_plan_run", "kmg_apply_plan_destroy", "kmg_apply_plan_status",
     "kmg_dither_threshold",
     "kmg_default_group_options", "kmg_group_create", "kmg_group_unique_id", "kmg_group_create_rank", "kmg_group_destroy",
     "kmg_group_info", "kmg_group_processor", "kmg_group_stream", "kmg_group_palette", "kmg_group_find", "kmg_group_reduce",
@@ -239,6 +240,7 @@ def lib():
     L.kmg_apply_plan_run.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp]
     L.kmg_apply_plan_destroy.argtypes = [vp, C.c_int]
     L.kmg_apply_plan_destroy.restype = None
+    L.kmg_apply_plan_status.argtypes = [vp]
     L.kmg_dither_threshold.argtypes = [f32p, C.c_uint32, C.POINTER(C.c_float)]
     L.kmg_processor_set_strategy.argtypes = [vp, C.c_int]
     L.kmg_default_group_options.argtypes = [C.POINTER(GroupOptions)]
@@ -525,6 +527,10 @@ class ApplyPlan:
 
     def run(self, d_rgba, width, rows, row0, d_out, stream=0):
         _check(lib().kmg_apply_plan_run(self._h, C.c_void_p(d_rgba), width, rows, row0, C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def status(self):
+        """kmg_apply_plan_status: waits for the last run; raises if a diffusion run of the plan timed out"""
+        _check(lib().kmg_apply_plan_status(self._h))
 
     def close(self, synchronise=True):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -1,7 +1,7 @@
 """Command line driver with the reference CLI's sub-commands, flags, validation and output naming
 (cli/src/args.rs:11-216, cli/src/main.rs:46-239), on top of libkmeans_hip.
 
-    python -m kmeans_gpu_amd.cli reduce  -i img.png -c 8 [-a kmeans|octree] [-m replace|dither|meld] [-o out.png]
+    python -m kmeans_gpu_amd.cli reduce  -i img.png -c 8 [-a kmeans|octree] [-m replace|dither|meld|diffuse] [-o out.png]
     python -m kmeans_gpu_amd.cli find    -i img.png -p "#050505,#ffffff,#ff0000"|palette.png [-m ...] [-o out.png]
     python -m kmeans_gpu_amd.cli palette -i img.png -c 8 [-a ...] [-s 40] [-o out.png]
 
@@ -20,7 +20,7 @@ import numpy as np
 from . import Algorithm, Group, ImageProcessor, ReduceMode
 
 _PALETTE_RE = re.compile(r"^#[0-9a-fA-F]{6}(?:,#[0-9a-fA-F]{6})*$")     # args.rs:184
-_MODES = {"replace": ReduceMode.Replace, "dither": ReduceMode.Dither, "meld": ReduceMode.Meld}
+_MODES = {"replace": ReduceMode.Replace, "dither": ReduceMode.Dither, "meld": ReduceMode.Meld, "diffuse": ReduceMode.Diffuse}
 _ALGOS = {"kmeans": Algorithm.Kmeans, "octree": Algorithm.Octree}
 
 

@@ -56,6 +56,7 @@ pub const KMG_ALGO_OCTREE: c_int = 1;
 pub const KMG_MODE_REPLACE: c_int = 0;
 pub const KMG_MODE_DITHER: c_int = 1;
 pub const KMG_MODE_MELD: c_int = 2;
+pub const KMG_MODE_DIFFUSE: c_int = 3;
 
 extern "C" {
     pub fn kmg_last_error() -> *const c_char;

@@ -215,6 +215,8 @@ pub enum ReduceMode {
     Replace,
     Dither,
     Meld,
+    /// Floyd-Steinberg error diffusion (KMG_MODE_DIFFUSE; not in the reference)
+    Diffuse,
 }
 
 impl ReduceMode {
@@ -223,6 +225,7 @@ impl ReduceMode {
             ReduceMode::Replace => ffi::KMG_MODE_REPLACE,
             ReduceMode::Dither => ffi::KMG_MODE_DITHER,
             ReduceMode::Meld => ffi::KMG_MODE_MELD,
+            ReduceMode::Diffuse => ffi::KMG_MODE_DIFFUSE,
         }
     }
 }
@@ -233,6 +236,7 @@ impl Display for ReduceMode {
             ReduceMode::Replace => "replace",
             ReduceMode::Dither => "dither",
             ReduceMode::Meld => "meld",
+            ReduceMode::Diffuse => "diffuse",
         })
     }
 }
