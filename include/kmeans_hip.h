@@ -12,7 +12,8 @@
  *
  * Conventions
  *  - images: tightly packed row-major RGBA8, 4 bytes per pixel, no row padding
- *    (core/src/image.rs:20-48); alpha is ignored on input and 255 on output.
+ *    (core/src/image.rs:20-48); alpha is ignored on input and 255 on output, unless
+ *    kmg_options.alpha_cutoff turns on alpha mode (see there).
  *  - centroid tables: k x 4 floats (L, a, b, 1.0) -- the `vec4<f32>` array of the reference's
  *    CentroidsBuffer (core/src/structures.rs:501-521) without its 16-byte count header.
  *  - accumulators: k x 4 int64 = (sum qL, sum qa, sum qb, count), q = rint(Lab * 2^20).
@@ -59,7 +60,7 @@ typedef enum kmg_algorithm { KMG_ALGO_KMEANS = 0, KMG_ALGO_OCTREE = 1 } kmg_algo
  *   o   = the bytes KMG_MODE_REPLACE writes for lbl
  *   out(x, y) = (o_R, o_G, o_B, 255)
  *   e(x, y)   = t - 16 o                                                 (|e| <= 4080, so |S| <= 65 280)
- * Input alpha is ignored.  kmg_dev_apply diffuses the given rows as an image of their own (zero error above the band);
+ * Input alpha is ignored (alpha mode: see kmg_options.alpha_cutoff).  kmg_dev_apply diffuses the given rows as an image of their own (zero error above the band);
  * kmg_apply_plan_run continues the diffusion across consecutive bands (row0 = the rows done so far, 0 first; the width
  * unchanged; anything else is KMG_ERR_INVALID_ARGUMENT), each band after the previous one whatever its stream.  A pass in
  * which nothing moves for about half a second gives up and is reported as KMG_ERR_HIP ("diffusion pass timed out"): by
@@ -85,7 +86,29 @@ typedef struct kmg_options {
     uint32_t check_period;    /* MAX_ITERATION_BEFORE_CONVERGENCE_CHECK = 8 (modules.rs:766)    */
     float    convergence;     /* ColorSpace::Lab.convergence() = 1.0 (core/src/lib.rs:189-194)  */
     int32_t  strategy;        /* KMG_STRATEGY_*: 0 = the library's cost models pick per call (default)                     */
+    uint32_t alpha_cutoff;    /* 0 = alpha ignored (default); 1..255 = alpha mode, see below                                   */
 } kmg_options;
+
+/* kmg_options.alpha_cutoff / kmg_processor_set_alpha_cutoff -- alpha-aware quantisation.  0 keeps the behaviour described
+ * everywhere else in this header, bit for bit; a value above 255 is KMG_ERR_INVALID_ARGUMENT.  t = 1..255 turns alpha mode on:
+ * a pixel is KEPT if and only if its alpha byte is >= t (t = 1 drops the fully transparent pixels only).
+ *  - Palette (kmg_palette, the palette step of kmg_reduce), KMG_ALGO_KMEANS.  S = the image after the shrink (unchanged: it
+ *    filters alpha with the same bilinear weights as RGB, so colour of transparent neighbours bleeds into edge pixels -- there
+ *    is no premultiplied shrink), K = the kept pixels of S in raster order, n_kept = |K|.  n_kept = |S|: the default call, byte
+ *    for byte.  n_kept = 0: KMG_ERR_INVALID_ARGUMENT ("no pixel reaches alpha_cutoff"), nothing written.  Otherwise the
+ *    centroids are those the default pipeline (initialisation + Lloyd loop, max_iterations / check_period / convergence) gives
+ *    for an image of n_kept x 1 pixels made of K: c_0 = K[floor(n_kept * 0.5625f)], the farthest-point tie rule runs over K's
+ *    indices, the sums run over K only.  Every kept pixel weighs 1, whatever its alpha.
+ *  - Palette, KMG_ALGO_OCTREE: the octree receives the kept pixels of its <= 128 shrink, in raster order.  All kept: the
+ *    default call; none kept: the error above.
+ *  - Output (kmg_find, kmg_reduce, kmg_dev_apply, apply plans), all four modes: out.rgb = what the mode writes for the pixel
+ *    without alpha mode, out.a = the input's alpha byte -- for excluded pixels too (their RGB is invisible anyway).  Exception,
+ *    KMG_MODE_DIFFUSE: a pixel that is not kept takes no part in the diffusion -- its out.rgb is the replace bytes of its own
+ *    unmodified colour and e(x, y) = 0 (it passes no error on; the error that would reach it is dropped).  Kept pixels use the
+ *    formulas of KMG_MODE_DIFFUSE unchanged (excluded neighbours contribute 0); bands of an apply plan continue as without it.
+ *  - Palette entries keep alpha 255.  The kmg_lloyd_* calls count every pixel they are given (callers compact first:
+ *    kmg_dev_alpha_compact); kmg_group_create refuses alpha_cutoff != 0 (KMG_ERR_INVALID_ARGUMENT).
+ * (Options structs of the two previous sizes -- without this field, and without `strategy` -- are accepted and mean 0.)        */
 
 /* kmg_options.strategy / kmg_processor_set_strategy: which of the library's interchangeable strategies a call takes.  Results are
  * IDENTICAL either way (that is what the tests use the switch for); only the time differs.  The low two bits choose between the
@@ -113,6 +136,9 @@ KMG_API void kmg_processor_destroy(kmg_processor *p);
 /* changes kmg_options.strategy of a live processor (tests and tuning: one processor, both strategies); calls that are
  * already running keep the strategy they started with                                                                        */
 KMG_API int kmg_processor_set_strategy(kmg_processor *p, int strategy);
+/* changes kmg_options.alpha_cutoff of a live processor (0 .. 255); calls that are already running keep the value they started
+ * with                                                                                                                         */
+KMG_API int kmg_processor_set_alpha_cutoff(kmg_processor *p, uint32_t alpha_cutoff);
 /* Page-locked host memory for images that cross the boundary often (a frame loop): a result buffer from kmg_host_alloc has
  * its pages resident and is copied to by DMA directly -- kmg_reduce of 8192 x 8192 into a fresh pageable buffer spends 30-50 ms
  * in the caller's page faults, 10 ms into one of these.  Plain memory otherwise; release with kmg_host_free.  (No counterpart
@@ -173,6 +199,12 @@ KMG_API void kmg_resized_dims(uint32_t width, uint32_t height, uint32_t max_size
                               uint32_t *new_width, uint32_t *new_height);
 KMG_API int kmg_dev_resize(kmg_processor *p, const uint8_t *d_rgba, uint32_t width, uint32_t height,
                            uint32_t new_width, uint32_t new_height, uint8_t *d_out_rgba, void *stream);
+
+/* Ordered stream compaction for alpha mode (kmg_options.alpha_cutoff): d_out[0 .. n_kept) = the pixels of d_rgba whose alpha
+ * byte is >= cutoff, in their order; *d_n_kept (a DEVICE word) = n_kept.  d_out has room for n_pixels pixels and does not
+ * overlap d_rgba.  cutoff 0 keeps every pixel; above 255: KMG_ERR_INVALID_ARGUMENT.  Only enqueues work on `stream`.       */
+KMG_API int kmg_dev_alpha_compact(kmg_processor *p, const uint8_t *d_rgba, uint64_t n_pixels, uint32_t cutoff,
+                                  uint8_t *d_out, uint64_t *d_n_kept, void *stream);
 
 /* One Lloyd problem = one image (or one row band of it) with k centroids.
  * ChooseCentroidModule + FindCentroidModule state (core/src/modules.rs:452-761).             */

@@ -23,8 +23,10 @@ int check_image(const kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_
     return KMG_OK;
 }
 
-// operations.rs:15-88 extract_palette_kmeans on a device-resident image -> host centroid table
-int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k,
+// operations.rs:15-88 extract_palette_kmeans on a device-resident image -> host centroid table.  Alpha mode (alpha_cutoff != 0,
+// include/kmeans_hip.h at kmg_options): the kept pixels of the shrunk image, compacted in raster order, are an image of n_kept x 1
+// pixels for the unchanged pipeline -- unless every pixel is kept, which is the default call.
+int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff,
                            hipStream_t st, float *c4)
 {
     int rc;
@@ -37,6 +39,22 @@ int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, 
         HIP_TRY(small.alloc(p, (size_t)sw * sh * 4, st));
         if ((rc = kmg_dev_resize(p, d_rgba, w, h, sw, sh, (uint8_t *)small.ptr, st)) != KMG_OK) return rc;
         src = (const uint8_t *)small.ptr;
+    }
+    StreamBuf kept;
+    if (alpha_cutoff) {
+        const uint64_t n = (uint64_t)sw * sh;
+        HIP_TRY(kept.alloc(p, (size_t)n * 4 + 256, st));               // (the count behind the pixels, 256-byte aligned)
+        uint64_t *d_count = (uint64_t *)((uint8_t *)kept.ptr + pad256((size_t)n * 4));
+        if ((rc = kmg_dev_alpha_compact(p, src, n, alpha_cutoff, (uint8_t *)kept.ptr, d_count, st)) != KMG_OK) return rc;
+        uint64_t n_kept = 0;
+        HIP_TRY(hipMemcpyAsync(&n_kept, d_count, sizeof n_kept, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_kept == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "no pixel reaches alpha_cutoff = %u", alpha_cutoff);
+        if (n_kept < n) {
+            src = (const uint8_t *)kept.ptr;
+            sw = (uint32_t)n_kept;
+            sh = 1;
+        }
     }
     LloydGuard g;
     if ((rc = lloyd_create_impl(p, k, &g.s, st)) != KMG_OK) return rc;
@@ -126,21 +144,22 @@ int upload_image(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, 
 
 // find_colors / dither_colors + OutputTexture::pull_image (structures.rs:441-470)
 int apply_and_download(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, const float *c4,
-                       uint32_t k, int mode, hipStream_t st, uint8_t *out_rgba)
+                       uint32_t k, int mode, uint32_t alpha_cutoff, hipStream_t st, uint8_t *out_rgba)
 {
     int rc;
     StreamBuf out;
     const size_t bytes = (size_t)w * h * 4;
     HIP_TRY(out.alloc(p, bytes, st));
-    if ((rc = kmg_dev_apply(p, d_rgba, w, h, 0, c4, k, mode, (uint8_t *)out.ptr, st)) != KMG_OK) return rc;
+    if ((rc = dev_apply(p, d_rgba, w, h, 0, c4, k, mode, (uint8_t *)out.ptr, st, alpha_cutoff)) != KMG_OK) return rc;
     HIP_TRY(copy_host_image(p, out_rgba, out.ptr, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return KMG_OK;
 }
 
 // octree_palette (lib.rs:288-331) on a device-resident image: shrink to <= 128 on the device, pull
-// the <= 128x128 image, run the reference's CPU octree on it, sort ascending by palette-crate Lab L
-int octree_palette_of(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t color_count,
+// the <= 128x128 image, run the reference's CPU octree on it, sort ascending by palette-crate Lab L.  Alpha mode: the octree gets
+// the kept pixels of the shrunk image, in raster order.
+int octree_palette_of(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t color_count, uint32_t alpha_cutoff,
                       hipStream_t st, std::vector<std::array<uint8_t, 4>> &colors)
 {
     const uint32_t MAX_SIZE = 128;                                     // lib.rs:293
@@ -157,7 +176,15 @@ int octree_palette_of(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint3
     std::vector<uint8_t> host((size_t)sw * sh * 4);
     HIP_TRY(hipMemcpyAsync(host.data(), src, host.size(), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    colors = octree_sorted_palette(host.data(), (uint64_t)sw * sh, color_count);
+    uint64_t n = (uint64_t)sw * sh;
+    if (alpha_cutoff) {
+        uint64_t n_kept = 0;
+        for (uint64_t i = 0; i < n; ++i)
+            if (host[4 * i + 3] >= alpha_cutoff) memmove(&host[4 * n_kept++], &host[4 * i], 4);
+        if (n_kept == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "no pixel reaches alpha_cutoff = %u", alpha_cutoff);
+        n = n_kept;
+    }
+    colors = octree_sorted_palette(host.data(), n, color_count);
     return KMG_OK;
 }
 
@@ -217,13 +244,14 @@ try {
     if (!palette_rgba || n_colors == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "palette is empty");
     if (!out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
     HIP_TRY(hipSetDevice(p->device));
+    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     StreamGuard sg;
     HIP_TRY(sg.acquire(p));
     std::vector<float> c4(4 * (size_t)n_colors);
     if ((rc = kmg_palette_to_centroids(palette_rgba, n_colors, c4.data())) != KMG_OK) return rc;  // lib.rs:86-87
     StreamBuf img;
     if ((rc = upload_image(p, rgba, w, h, sg.st, img)) != KMG_OK) return rc;
-    return apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), n_colors, mode, sg.st, out_rgba);
+    return apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), n_colors, mode, alpha_cutoff, sg.st, out_rgba);
 }
 KMG_ABI_CATCH
 
@@ -239,6 +267,7 @@ try {
     if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
         return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
     HIP_TRY(hipSetDevice(p->device));
+    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     StreamGuard sg;
     HIP_TRY(sg.acquire(p));
     StreamBuf img;
@@ -247,17 +276,17 @@ try {
     const auto t1 = std::chrono::steady_clock::now();
     if (algo == KMG_ALGO_OCTREE) {                                     // lib.rs:133-136
         std::vector<std::array<uint8_t, 4>> colors;
-        if ((rc = octree_palette_of(p, (const uint8_t *)img.ptr, w, h, color_count, sg.st, colors)) != KMG_OK) return rc;
+        if ((rc = octree_palette_of(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, colors)) != KMG_OK) return rc;
         if (colors.empty()) return fail(KMG_ERR_INVALID_ARGUMENT, "the octree returned no colour");
         if (colors.size() > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "the octree returned %zu colours, more than KMG_MAX_K = %u", colors.size(), KMG_MAX_K);
         std::vector<float> oc4(4 * colors.size());
         if ((rc = kmg_palette_to_centroids(colors[0].data(), (uint32_t)colors.size(), oc4.data())) != KMG_OK) return rc;
-        return apply_and_download(p, (const uint8_t *)img.ptr, w, h, oc4.data(), (uint32_t)colors.size(), mode, sg.st, out_rgba);
+        return apply_and_download(p, (const uint8_t *)img.ptr, w, h, oc4.data(), (uint32_t)colors.size(), mode, alpha_cutoff, sg.st, out_rgba);
     }
     std::vector<float> c4(4 * (size_t)color_count);
-    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, sg.st, c4.data())) != KMG_OK) return rc;
+    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data())) != KMG_OK) return rc;
     const auto t2 = std::chrono::steady_clock::now();
-    rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), color_count, mode, sg.st, out_rgba);
+    rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), color_count, mode, alpha_cutoff, sg.st, out_rgba);
     if (log_debug()) {
         const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
             return std::chrono::duration<double, std::milli>(b - a).count();
@@ -280,19 +309,20 @@ try {
     if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
         return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
     HIP_TRY(hipSetDevice(p->device));
+    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     StreamGuard sg;
     HIP_TRY(sg.acquire(p));
     StreamBuf img;
     if ((rc = upload_image(p, rgba, w, h, sg.st, img)) != KMG_OK) return rc;
     if (algo == KMG_ALGO_OCTREE) {                                     // lib.rs:288-331
         std::vector<std::array<uint8_t, 4>> colors;
-        if ((rc = octree_palette_of(p, (const uint8_t *)img.ptr, w, h, color_count, sg.st, colors)) != KMG_OK) return rc;
+        if ((rc = octree_palette_of(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, colors)) != KMG_OK) return rc;
         for (size_t i = 0; i < colors.size(); ++i) memcpy(out_rgba + 4 * i, colors[i].data(), 4);
         *out_count = (uint32_t)colors.size();
         return KMG_OK;
     }
     std::vector<float> c4(4 * (size_t)color_count);
-    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, sg.st, c4.data())) != KMG_OK) return rc;
+    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data())) != KMG_OK) return rc;
     sorted_palette_of(c4.data(), color_count, out_rgba);
     *out_count = color_count;
     return KMG_OK;

@@ -193,6 +193,7 @@ struct kmg_apply_plan {
     kmg_processor *p = nullptr;
     uint32_t k = 0;
     int mode = 0;
+    uint32_t alpha_cutoff = 0;          // kmg_options.alpha_cutoff when the plan was made (0: alpha ignored)
     bool dither = false;
     float thr = 0.0f;
     enum Route { kScan, kMeldScan, kMeldMasks, kMeldLists, kReplaceTable, kDitherLists, kDitherMasks, kDiffuseTable, kDiffuseScan } route = kScan;
@@ -221,9 +222,9 @@ struct kmg_apply_plan {
     }
 };
 
-extern "C" int kmg_apply_plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, uint64_t n_pixels_hint, void *stream,
-                                     kmg_apply_plan **out)
-try {
+static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, uint64_t n_pixels_hint, void *stream,
+                       uint32_t alpha_cutoff, kmg_apply_plan **out)
+{
     if (!p || !c4 || !out || k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply_plan arguments");
     *out = nullptr;
     if (k > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", k, KMG_MAX_K);
@@ -233,7 +234,7 @@ try {
     kmg_apply_plan *pl = new (std::nothrow) kmg_apply_plan();
     if (!pl) return fail(KMG_ERR_OUT_OF_MEMORY, "host allocation failed");
     struct Undo { kmg_apply_plan *pl; ~Undo() { if (pl) { if (pl->ready) (void)hipEventDestroy(pl->ready); (void)hipStreamSynchronize(pl->built_on); delete pl; } } } undo{pl};
-    pl->p = p; pl->k = k; pl->mode = mode; pl->built_on = S(stream);
+    pl->p = p; pl->k = k; pl->mode = mode; pl->alpha_cutoff = alpha_cutoff; pl->built_on = S(stream);
 
     // per-centroid work on the host: (L,a,b,C) table, RGBA8 palette (lab_to_rgb.wgsl), threshold
     std::vector<Centroid> hc(k);
@@ -341,6 +342,13 @@ try {
     *out = pl;
     return KMG_OK;
 }
+
+extern "C" int kmg_apply_plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, uint64_t n_pixels_hint, void *stream,
+                                     kmg_apply_plan **out)
+try {
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply_plan arguments");
+    return plan_create(p, c4, k, mode, n_pixels_hint, stream, p->alpha_cutoff.load(std::memory_order_relaxed), out);
+}
 KMG_ABI_CATCH
 
 // KMG_MODE_DIFFUSE: one band of the diffusion.  The bands of one plan are consecutive rows of one image (row0 = the rows done
@@ -371,7 +379,7 @@ static int run_diffuse(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, ui
     const bool table = pl->route == kmg_apply_plan::kDiffuseTable;
     const int route = !table ? kDiffuseScan : (pl->k <= 256 ? kDiffusePairs : kDiffuseCells);
     hipError_t e = launch_diffuse(route, (const uint32_t *)d_rgba, w, rows, (uint32_t *)d_out, erow, pl->dparity, ctl, sticky, pl->d_cent,
-                                  pl->k, p->d_lut, pl->d_pal, pl->aux, pl->sub, st);
+                                  pl->k, p->d_lut, pl->d_pal, pl->aux, pl->sub, st, pl->alpha_cutoff);
     if (e == hipSuccess) e = hipMemcpyAsync((void *)pl->h_timeout, sticky, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipEventRecord(pl->ddone, st);
     if (e != hipSuccess) return fail(KMG_ERR_HIP, "diffusion failed: %s", hipGetErrorString(e));
@@ -410,29 +418,36 @@ try {
     if (S(stream) != pl->built_on) HIP_TRY(hipStreamWaitEvent(S(stream), pl->ready, 0));      // (another stream: after the tables)
     const uint64_t n_px = (uint64_t)w * rows;
     const uint32_t k = pl->k;
+    // alpha mode: the source's alpha byte over the output's -- inside the kernel (its ALPHA instantiation), or by k_alpha_merge after
+    // the two routes whose kernels live in kmg_table.hip
+    const bool alpha = pl->alpha_cutoff != 0;
     hipError_t e = hipSuccess;
     switch (pl->route) {
     case kmg_apply_plan::kMeldLists:
-        e = launch_meld_lists((const uint32_t *)d_rgba, n_px, pl->d_cent, k, p->d_lut, (const uint8_t *)pl->aux, (uint32_t *)d_out, S(stream));
+        e = launch_meld_lists((const uint32_t *)d_rgba, n_px, pl->d_cent, k, p->d_lut, (const uint8_t *)pl->aux, (uint32_t *)d_out, S(stream),
+                              alpha);
         break;
     case kmg_apply_plan::kMeldMasks:
     case kmg_apply_plan::kMeldScan:
-        e = launch_meld((const uint32_t *)d_rgba, n_px, pl->d_cent, k, p->d_lut, (const uint64_t *)pl->aux, (uint32_t *)d_out, S(stream));
+        e = launch_meld((const uint32_t *)d_rgba, n_px, pl->d_cent, k, p->d_lut, (const uint64_t *)pl->aux, (uint32_t *)d_out, S(stream),
+                        alpha);
         break;
     case kmg_apply_plan::kReplaceTable:
         e = launch_labels((const uint32_t *)d_rgba, n_px, pl->aux, pl->sub, k, pl->d_pal, (uint32_t *)d_out, S(stream));
+        if (e == hipSuccess && alpha) e = launch_alpha_merge((const uint32_t *)d_rgba, (uint32_t *)d_out, n_px, S(stream));
         break;
     case kmg_apply_plan::kDitherLists:
         e = launch_dither_lists((const uint32_t *)d_rgba, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->thr, (const uint8_t *)pl->aux,
-                                (uint32_t *)d_out, S(stream));
+                                (uint32_t *)d_out, S(stream), alpha);
         break;
     case kmg_apply_plan::kDitherMasks:
         e = launch_dither_pruned((const uint32_t *)d_rgba, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->thr, (const uint64_t *)pl->aux,
                                  (uint32_t *)d_out, S(stream));
+        if (e == hipSuccess && alpha) e = launch_alpha_merge((const uint32_t *)d_rgba, (uint32_t *)d_out, n_px, S(stream));
         break;
     default:
         e = launch_apply((const uint32_t *)d_rgba, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->dither, pl->thr, (uint32_t *)d_out,
-                         S(stream));
+                         S(stream), alpha);
     }
     if (e != hipSuccess) return fail(KMG_ERR_HIP, "apply failed: %s", hipGetErrorString(e));
     return KMG_OK;
@@ -451,14 +466,14 @@ try {
 }
 KMG_ABI_CATCH_VOID
 
-extern "C" int kmg_dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0,
-                             const float *c4, uint32_t k, int mode, uint8_t *d_out, void *stream)
-try {
+int kmg::dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, const float *c4, uint32_t k, int mode,
+                   uint8_t *d_out, void *stream, uint32_t alpha_cutoff)
+{
     if (!p || !d_rgba || !d_out || !c4 || !w || !rows || k == 0)
         return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply arguments");
     if ((uint64_t)w * rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
     kmg_apply_plan *pl = nullptr;
-    int rc = kmg_apply_plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, &pl);
+    int rc = plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, alpha_cutoff, &pl);
     if (rc != KMG_OK) return rc;
     // (diffusion: the band is an image of its own -- the plan is new, so its first run starts from a zero error row)
     rc = kmg_apply_plan_run(pl, d_rgba, w, rows, mode == KMG_MODE_DIFFUSE ? 0u : row0, d_out, stream);
@@ -468,6 +483,13 @@ try {
     if (rc != KMG_OK) return rc;
     if (e2 != hipSuccess) return fail(KMG_ERR_HIP, "apply failed: %s", hipGetErrorString(e2));
     return KMG_OK;
+}
+
+extern "C" int kmg_dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0,
+                             const float *c4, uint32_t k, int mode, uint8_t *d_out, void *stream)
+try {
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply arguments");
+    return dev_apply(p, d_rgba, w, rows, row0, c4, k, mode, d_out, stream, p->alpha_cutoff.load(std::memory_order_relaxed));
 }
 KMG_ABI_CATCH
 

@@ -16,6 +16,14 @@ __device__ __forceinline__ void px_to_lab(const float *s_lut, uint32_t px, float
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
+// alpha mode (kmg_options.alpha_cutoff): an output word takes the alpha byte of its source pixel.  A compile-time switch of the
+// output kernels: their instantiations without it are the code of the passes without alpha mode.
+template <bool ALPHA>
+__device__ __forceinline__ uint32_t with_alpha(uint32_t o, uint32_t src)
+{
+    return ALPHA ? (o & 0x00FFFFFFu) | (src & 0xFF000000u) : o;
+}
+
 // streaming (non-temporal) variants: the pixel and label streams are touched once per pass and
 // should not evict the small gather tables from L2
 __device__ __forceinline__ void load4_stream(const uint32_t *rgba, uint64_t i0, uint64_t n, bool aligned,

@@ -150,12 +150,15 @@ __device__ bool wait_progress(DiffCtl *ctl, uint32_t *sticky, uint32_t t, uint32
     return true;
 }
 
-template <int ROUTE>
+// ALPHA (alpha mode, kmg_options.alpha_cutoff = cutoff): a pixel whose alpha byte is below the cutoff takes no part -- S = 0 (its
+// own colour unmodified), e = 0 -- and every output word keeps its pixel's alpha byte
+template <int ROUTE, bool ALPHA>
 __global__ __launch_bounds__(64) void k_diffuse(const uint32_t *__restrict__ rgba, uint32_t w, uint32_t rows,
                                                 uint32_t *__restrict__ out, uint2 *__restrict__ erow, uint32_t parity,
                                                 DiffCtl *__restrict__ ctl, uint32_t *__restrict__ sticky, const Centroid *__restrict__ cent, uint32_t k,
                                                 const float *__restrict__ lut, const uint32_t *__restrict__ pal,
-                                                const void *__restrict__ colour_labels, const uint16_t *__restrict__ sub_table)
+                                                const void *__restrict__ colour_labels, const uint16_t *__restrict__ sub_table,
+                                                uint32_t cutoff)
 {
     constexpr uint32_t kLdsWords = ROUTE == kDiffusePairs ? kPairsLds : ROUTE == kDiffuseCells ? kCellsLds : 4u * 3072u + 256u + 3072u;
     __shared__ __attribute__((aligned(16))) uint32_t s_lds[kLdsWords];
@@ -243,11 +246,12 @@ __global__ __launch_bounds__(64) void k_diffuse(const uint32_t *__restrict__ rgb
                 }
                 const bool act = row_ok && x >= 0 && x < (int)w;
                 const uint32_t src = px[j];
+                const bool keep = !ALPHA || (src >> 24) >= cutoff;
                 int tq[3];
                 uint32_t cpx = 0xFF000000u;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const int S = 7 * eL[c] + 3 * ap1[c] + 5 * a0[c] + am1[c];
+                    const int S = keep ? 7 * eL[c] + 3 * ap1[c] + 5 * a0[c] + am1[c] : 0;
                     const int v = 16 * (int)((src >> (8 * c)) & 255u) + ((S + 8) >> 4);
                     tq[c] = min(max(v, 0), 4080);
                     cpx |= (uint32_t)((tq[c] + 8) >> 4) << (8 * c);
@@ -256,9 +260,9 @@ __global__ __launch_bounds__(64) void k_diffuse(const uint32_t *__restrict__ rgb
                 const uint32_t o = s_pal[act && lbl < k ? lbl : 0u];
                 int e[3];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { e[c] = tq[c] - 16 * (int)((o >> (8 * c)) & 255u); eL[c] = e[c]; }
+                for (int c = 0; c < 3; ++c) { e[c] = keep ? tq[c] - 16 * (int)((o >> (8 * c)) & 255u) : 0; eL[c] = e[c]; }
                 eo = act ? pack_err(e[0], e[1], e[2]) : make_uint2(0u, 0u);
-                ob[j] = o;
+                ob[j] = with_alpha<ALPHA>(o, src);
                 eb[j] = eo;
             }
 #pragma unroll
@@ -307,16 +311,18 @@ uint32_t diffuse_grid(int route, uint32_t rows)
 
 hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t *out, void *erow, uint32_t parity,
                           void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st)
+                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff)
 {
     const uint32_t grid = diffuse_grid(route, rows);
-#define KMG_DIFFUSE(R)                                                                                                          \
-    hipLaunchKernelGGL(k_diffuse<R>, dim3(grid), dim3(64), 0, st, rgba, w, rows, out, (uint2 *)erow, parity, (DiffCtl *)ctl, sticky, \
-                       cent, k, lut, pal, colour_labels, sub_table)
+#define KMG_DIFFUSE_A(R, A)                                                                                                     \
+    hipLaunchKernelGGL((k_diffuse<R, A>), dim3(grid), dim3(64), 0, st, rgba, w, rows, out, (uint2 *)erow, parity, (DiffCtl *)ctl,  \
+                       sticky, cent, k, lut, pal, colour_labels, sub_table, alpha_cutoff)
+#define KMG_DIFFUSE(R) do { if (alpha_cutoff) KMG_DIFFUSE_A(R, true); else KMG_DIFFUSE_A(R, false); } while (0)
     if (route == kDiffusePairs) KMG_DIFFUSE(kDiffusePairs);
     else if (route == kDiffuseCells) KMG_DIFFUSE(kDiffuseCells);
     else KMG_DIFFUSE(kDiffuseScan);
 #undef KMG_DIFFUSE
+#undef KMG_DIFFUSE_A
     return hipGetLastError();
 }
 

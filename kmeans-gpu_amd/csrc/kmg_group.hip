@@ -523,13 +523,17 @@ static int group_create_impl(const kmg_group_options *opt, const uint8_t *id, ui
     kmg_group_options o;
     kmg_default_group_options(&o);
     if (opt) {
-        // (kmg_options, the last member, grew by `strategy` in round 6: a caller compiled against the previous header passes the old size)
+        // (kmg_options, the last member, grew by `strategy` in round 6 and by `alpha_cutoff` after it: a caller compiled against an
+        // earlier header passes its size)
         constexpr uint32_t kOldSize = (uint32_t)(offsetof(kmg_group_options, processor) + offsetof(kmg_options, strategy));
-        if (opt->struct_size != sizeof(kmg_group_options) && opt->struct_size != kOldSize)
+        constexpr uint32_t kNoAlphaSize = (uint32_t)(offsetof(kmg_group_options, processor) + offsetof(kmg_options, alpha_cutoff));
+        if (opt->struct_size != sizeof(kmg_group_options) && opt->struct_size != kNoAlphaSize && opt->struct_size != kOldSize)
             return fail(KMG_ERR_INVALID_ARGUMENT, "kmg_group_options.struct_size mismatch");
         memcpy(&o, opt, opt->struct_size);
         o.struct_size = sizeof(kmg_group_options);
     }
+    // (alpha mode is a feature of the single-device calls: the group layer would have to compact row bands across ranks)
+    if (o.processor.alpha_cutoff != 0) return fail(KMG_ERR_INVALID_ARGUMENT, "kmg_group_options.processor.alpha_cutoff: the kmg_group_* calls have no alpha mode");
     if (o.n_devices > KMG_MAX_DEVICES) return fail(KMG_ERR_INVALID_ARGUMENT, "more than KMG_MAX_DEVICES = %d devices", KMG_MAX_DEVICES);
     int count = 0;
     const hipError_t e = hipGetDeviceCount(&count);

@@ -49,6 +49,10 @@ void sorted_palette_of(const float *centroids4, uint32_t k, uint8_t *out_rgba);
 // lib.rs:288-331 octree_palette on a host image already shrunk to <= 128: the reference's CPU octree, sorted by L
 std::vector<std::array<uint8_t, 4>> octree_sorted_palette(const uint8_t *host_rgba, uint64_t n_pixels, uint32_t color_count);
 
+// kmg_dev_apply with the alpha cutoff given (kmg_apply.hip): the host-buffer calls read the processor's once per call
+int dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, const float *centroids4, uint32_t k,
+              int mode, uint8_t *d_out, void *stream, uint32_t alpha_cutoff);
+
 // An image between a caller's (pageable) buffer and the device, ordered on `st` (kmg_api.hip): small images asynchronously,
 // large ones as synchronous row-range copies on several streams of the processor.
 hipError_t copy_host_image(kmg_processor *p, void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t st);

@@ -86,10 +86,26 @@ hipError_t launch_resize_band(const uint32_t *band, uint32_t w, uint32_t h, uint
                               uint32_t out_row0, uint32_t out_rows, uint32_t *out, hipStream_t st);
 uint32_t resize_source_row(uint32_t gy, uint32_t h, uint32_t nh);
 
+// alpha mode (kmg_alpha.hip): out[0 .. n_kept) = the pixels whose alpha byte is >= cutoff, in order; *n_kept (device) = their
+// number.  counts: alpha_compact_grid(n) words of scratch.  Two launches on st.
+uint32_t alpha_compact_grid(uint64_t n);
+hipError_t launch_alpha_compact(const uint32_t *rgba, uint64_t n, uint32_t cutoff, uint32_t *out, unsigned long long *n_kept,
+                                unsigned long long *counts, hipStream_t st);
+// out[i] = (out[i] & 0x00FFFFFF) | (rgba[i] & 0xFF000000): alpha mode after an output kernel without the compile-time switch
+hipError_t launch_alpha_merge(const uint32_t *rgba, uint32_t *out, uint64_t n, hipStream_t st);
+// the list-based dither and meld passes (kmg_lists.hip) with the alpha switch; kmg_table.h declares them without it (= false)
+hipError_t launch_meld_lists(const uint32_t *rgba, uint64_t n, const Centroid *cent, uint32_t k, const float *lut,
+                             const uint8_t *lists, uint32_t *out, hipStream_t st, bool alpha);
+hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
+                               const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, uint32_t *out,
+                               hipStream_t st, bool alpha);
+
 // replace / dither output pass.  pal: k+1 RGBA8 words (entry k = the converted sentinel).
+// alpha (every output pass, kmg_options.alpha_cutoff != 0): the pixel's own alpha byte over the output's (a separate instantiation
+// of the kernel; alpha = false runs the code of the passes without alpha mode)
 hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0,
                         const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                        bool dither, float threshold, uint32_t *out, hipStream_t st);
+                        bool dither, float threshold, uint32_t *out, hipStream_t st, bool alpha = false);
 
 // thr[256] (device): the linear-channel thresholds of the 256 sRGB8 output bytes (k_meld), made by the device's own encode
 hipError_t launch_encode_thresholds(float *thr, hipStream_t st);
@@ -101,7 +117,7 @@ hipError_t launch_encode_check(const float *thr, unsigned long long *bad, hipStr
 // meld output pass (mix_colors.wgsl main_meld + lab_to_rgb.wgsl); lut: 256 decode entries followed by the 256 thresholds
 // masks: NULL, or per colour cell the candidate centroids of kmg_table.h's launch_meld_candidates
 hipError_t launch_meld(const uint32_t *rgba, uint64_t n, const Centroid *cent, uint32_t k, const float *lut,
-                       const uint64_t *masks, uint32_t *out, hipStream_t st);
+                       const uint64_t *masks, uint32_t *out, hipStream_t st, bool alpha = false);
 
 // error-diffusion output pass, KMG_MODE_DIFFUSE (kmg_diffuse.hip).  route: how a quantised colour finds its label --
 // kDiffuseScan: per-lane arg-min over cent (LDS); kDiffusePairs (k <= 256) / kDiffuseCells (k > 256): the replace pass's colour
@@ -109,12 +125,13 @@ hipError_t launch_meld(const uint32_t *rgba, uint64_t n, const Centroid *cent, u
 // the row above the band (zero for a first band); the band leaves its last row's error in row (parity + chunks) & 1.
 // ctl: diffuse_ctl_bytes() of per-call control words, zero on entry; ctl word 1 != 0 afterwards = the pass timed out.
 // sticky: a word the caller zeroes once; a pass that times out also sets it (so a later pass does not hide the failure).
+// alpha_cutoff != 0: alpha mode -- pixels below the cutoff take no part in the diffusion, every output keeps its pixel's alpha.
 enum { kDiffuseScan = 0, kDiffusePairs = 1, kDiffuseCells = 2 };
 constexpr uint32_t kDiffuseRing = 1024;
 size_t diffuse_ctl_bytes();
 uint32_t diffuse_grid(int route, uint32_t rows);
 hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t *out, void *erow, uint32_t parity,
                           void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st);
+                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff = 0);
 
 }  // namespace kmg

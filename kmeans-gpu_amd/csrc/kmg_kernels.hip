@@ -1072,7 +1072,7 @@ hipError_t launch_resize_band(const uint32_t *band, uint32_t w, uint32_t h, uint
 // ------------------------------------------------------------------------------------------
 __constant__ const float c_bayer[16] = {0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5};
 
-template <int PPT, bool DITHER, bool CHUNKED>
+template <int PPT, bool DITHER, bool CHUNKED, bool ALPHA>
 __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ rgba, uint32_t w,
                                                   uint64_t n, uint32_t row0,
                                                   const Centroid *__restrict__ cent, uint32_t k,
@@ -1103,11 +1103,16 @@ __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ r
         PixelTerms pt[PPT];
         float best[PPT];
         uint32_t idx[PPT];
+        uint32_t src_a[ALPHA ? PPT : 1];                             // alpha mode: the source words' alpha bytes
 #pragma unroll
         for (int g = 0; g < GROUPS; ++g) {
             i0[g] = tile * TILE + (uint64_t)g * (kBlock * 4) + (uint64_t)threadIdx.x * 4;
             uint32_t px[4];
             load4(rgba, i0[g], n, aligned != 0, px);
+            if (ALPHA) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) src_a[g * 4 + q] = px[q];
+            }
             // image coordinates of the group's first pixel (n < 2^32): one 32-bit divide per 4 pixels
             uint32_t gx = 0, gy = 0;
             if (DITHER) {
@@ -1144,7 +1149,7 @@ __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ r
         for (int g = 0; g < GROUPS; ++g) {
             uint32_t o[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = pal[idx[g * 4 + q]];
+            for (int q = 0; q < 4; ++q) o[q] = with_alpha<ALPHA>(pal[idx[g * 4 + q]], src_a[ALPHA ? g * 4 + q : 0]);
             store4(out, i0[g], n, aligned != 0, o);
         }
     }
@@ -1152,7 +1157,7 @@ __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ r
 
 hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0,
                         const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                        bool dither, float threshold, uint32_t *out, hipStream_t st)
+                        bool dither, float threshold, uint32_t *out, hipStream_t st, bool alpha)
 {
     const uint64_t n = (uint64_t)w * rows;
     const uint64_t tiles = (n + (uint64_t)kBlock * kAssignPPT - 1) / ((uint64_t)kBlock * kAssignPPT);
@@ -1162,11 +1167,16 @@ hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_
                          (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
     const bool chunked = k >= 32;
     const size_t lds = sizeof(float4) * kpad + (256 + 16) * sizeof(float);
-#define KMG_APPLY(D, C)                                                                            \
-    hipLaunchKernelGGL((k_apply<kAssignPPT, D, C>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, \
+#define KMG_APPLY(D, C, A)                                                                            \
+    hipLaunchKernelGGL((k_apply<kAssignPPT, D, C, A>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, \
                        row0, cent, k, lut, pal, threshold, out, aligned)
-    if (dither) { if (chunked) KMG_APPLY(true, true); else KMG_APPLY(true, false); }
-    else        { if (chunked) KMG_APPLY(false, true); else KMG_APPLY(false, false); }
+    if (alpha) {
+        if (dither) { if (chunked) KMG_APPLY(true, true, true); else KMG_APPLY(true, false, true); }
+        else        { if (chunked) KMG_APPLY(false, true, true); else KMG_APPLY(false, false, true); }
+    } else {
+        if (dither) { if (chunked) KMG_APPLY(true, true, false); else KMG_APPLY(true, false, false); }
+        else        { if (chunked) KMG_APPLY(false, true, false); else KMG_APPLY(false, false, false); }
+    }
 #undef KMG_APPLY
     return hipGetLastError();
 }
@@ -1251,6 +1261,7 @@ hipError_t launch_division_check(float c, unsigned long long *out, hipStream_t s
 
 // masks != NULL: per colour cell, the centroids that can be among the pixel's two closest (kmg_table.hip,
 // k_meld_candidates); the ordered scan then visits only those -- same two slots, same output
+template <bool ALPHA>
 __global__ __launch_bounds__(kBlock) void k_meld(const uint32_t *__restrict__ rgba, uint64_t n,
                                                  const Centroid *__restrict__ cent, uint32_t k,
                                                  const float *__restrict__ lut, const uint64_t *__restrict__ masks,
@@ -1274,7 +1285,7 @@ __global__ __launch_bounds__(kBlock) void k_meld(const uint32_t *__restrict__ rg
         px_to_lab(s_lut, px, L, a, b);
         if (k == 1) {                                            // mix_colors.wgsl:127-131
             const float4 c = s_cent[0];
-            out[i] = lab_to_rgba8_dev<true>(c.x, c.y, c.z, s_thr);
+            out[i] = with_alpha<ALPHA>(lab_to_rgba8_dev<true>(c.x, c.y, c.z, s_thr), px);
             continue;
         }
         // :30-31 closest = second_closest = vec4(10000.0)
@@ -1322,18 +1333,19 @@ __global__ __launch_bounds__(kBlock) void k_meld(const uint32_t *__restrict__ rg
         const float oL = factor * cL + (1.0f - factor) * sL;
         const float oa = factor * ca + (1.0f - factor) * sa;
         const float ob = factor * cb + (1.0f - factor) * sb;
-        out[i] = lab_to_rgba8_dev<true>(oL, oa, ob, s_thr);
+        out[i] = with_alpha<ALPHA>(lab_to_rgba8_dev<true>(oL, oa, ob, s_thr), px);
     }
 }
 
 hipError_t launch_meld(const uint32_t *rgba, uint64_t n, const Centroid *cent, uint32_t k, const float *lut,
-                       const uint64_t *masks, uint32_t *out, hipStream_t st)
+                       const uint64_t *masks, uint32_t *out, hipStream_t st, bool alpha)
 {
     const uint64_t blocks = (n + kBlock - 1) / kBlock;
     const uint32_t grid = (uint32_t)(blocks < 8192 ? (blocks ? blocks : 1) : 8192);
     const uint32_t kpad = (k + 3u) & ~3u;
     const size_t lds = sizeof(float4) * kpad + (256 + 257) * sizeof(float);
-    hipLaunchKernelGGL(k_meld, dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, masks, out);
+    if (alpha) hipLaunchKernelGGL(k_meld<true>, dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, masks, out);
+    else hipLaunchKernelGGL(k_meld<false>, dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, masks, out);
     return hipGetLastError();
 }
 

@@ -297,7 +297,7 @@ __device__ __forceinline__ void walk_list(const uint8_t *__restrict__ lists, uin
     }
 }
 
-template <int HALVES>
+template <int HALVES, bool ALPHA>
 __global__ __launch_bounds__(kBlock) void k_dither_lists(const uint32_t *__restrict__ rgba, uint32_t w, uint64_t n,
                                                          uint32_t row0, const Centroid *__restrict__ cent, uint32_t k,
                                                          const float *__restrict__ lut, const uint32_t *__restrict__ pal,
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(kBlock) void k_dither_lists(const uint32_t *__restr
                     idx = li;
                 }
             }
-            res[q] = pal[idx];
+            res[q] = with_alpha<ALPHA>(pal[idx], px[q]);
         }
         store4_stream(out, i0, n, aligned != 0, res);
     }
@@ -415,6 +415,13 @@ hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, 
                                const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, uint32_t *out,
                                hipStream_t st)
 {
+    return launch_dither_lists(rgba, w, rows, row0, cent, k, lut, pal, threshold, lists, out, st, false);
+}
+
+hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
+                               const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, uint32_t *out,
+                               hipStream_t st, bool alpha)
+{
     if (k > kLabListMaxK) return hipErrorInvalidValue;
     const uint64_t n = (uint64_t)w * rows;
     const uint64_t tiles = (n + kBlock * 4 - 1) / (kBlock * 4);
@@ -422,12 +429,11 @@ hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, 
     const uint32_t halves = k > 256u ? 2u : 1u;
     const size_t lds = sizeof(float4) * 256 * halves + (256 + 16) * sizeof(float);
     const int aligned = ((reinterpret_cast<uintptr_t>(rgba) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
-    if (halves == 2u)
-        hipLaunchKernelGGL(k_dither_lists<2>, dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut, pal, threshold, lists, out,
-                           aligned);
-    else
-        hipLaunchKernelGGL(k_dither_lists<1>, dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut, pal, threshold, lists, out,
-                           aligned);
+#define KMG_DL(H, A) hipLaunchKernelGGL((k_dither_lists<H, A>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut, pal, \
+                                        threshold, lists, out, aligned)
+    if (halves == 2u) { if (alpha) KMG_DL(2, true); else KMG_DL(2, false); }
+    else { if (alpha) KMG_DL(1, true); else KMG_DL(1, false); }
+#undef KMG_DL
     return hipGetLastError();
 }
 
@@ -536,7 +542,7 @@ __device__ __forceinline__ void walk_list3(const uint8_t *__restrict__ lists, ui
     }
 }
 
-template <int HALVES>
+template <int HALVES, bool ALPHA>
 __global__ __launch_bounds__(kBlock) void k_meld_lists(const uint32_t *__restrict__ rgba, uint64_t n,
                                                        const Centroid *__restrict__ cent, uint32_t k,
                                                        const float *__restrict__ lut, const uint8_t *__restrict__ lists,
@@ -639,7 +645,7 @@ __global__ __launch_bounds__(kBlock) void k_meld_lists(const uint32_t *__restric
             const float oL = factor * cL + (1.0f - factor) * sL;
             const float oa = factor * ca + (1.0f - factor) * sa;
             const float ob = factor * cb + (1.0f - factor) * sb;
-            res[q] = lab_to_rgba8_dev<true>(oL, oa, ob, s_thr);
+            res[q] = with_alpha<ALPHA>(lab_to_rgba8_dev<true>(oL, oa, ob, s_thr), px[q]);
         }
         store4_stream(out, i0, n, aligned != 0, res);
     }
@@ -648,14 +654,22 @@ __global__ __launch_bounds__(kBlock) void k_meld_lists(const uint32_t *__restric
 hipError_t launch_meld_lists(const uint32_t *rgba, uint64_t n, const Centroid *cent, uint32_t k, const float *lut,
                              const uint8_t *lists, uint32_t *out, hipStream_t st)
 {
+    return launch_meld_lists(rgba, n, cent, k, lut, lists, out, st, false);
+}
+
+hipError_t launch_meld_lists(const uint32_t *rgba, uint64_t n, const Centroid *cent, uint32_t k, const float *lut,
+                             const uint8_t *lists, uint32_t *out, hipStream_t st, bool alpha)
+{
     if (k < 2u || k > kLabListMaxK) return hipErrorInvalidValue;
     const uint64_t tiles = (n + kBlock * 4 - 1) / (kBlock * 4);
     const uint32_t grid = (uint32_t)(tiles < 8192 ? (tiles ? tiles : 1) : 8192);
     const uint32_t halves = k > 256u ? 2u : 1u;
     const size_t lds = sizeof(float4) * 256 * halves + (256 + 257) * sizeof(float);
     const int aligned = ((reinterpret_cast<uintptr_t>(rgba) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
-    if (halves == 2u) hipLaunchKernelGGL(k_meld_lists<2>, dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, lists, out, aligned);
-    else hipLaunchKernelGGL(k_meld_lists<1>, dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, lists, out, aligned);
+#define KMG_ML(H, A) hipLaunchKernelGGL((k_meld_lists<H, A>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, lists, out, aligned)
+    if (halves == 2u) { if (alpha) KMG_ML(2, true); else KMG_ML(2, false); }
+    else { if (alpha) KMG_ML(1, true); else KMG_ML(1, false); }
+#undef KMG_ML
     return hipGetLastError();
 }
 

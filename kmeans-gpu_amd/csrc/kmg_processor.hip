@@ -56,6 +56,7 @@ try {
     opt->check_period = 8;       // modules.rs:766
     opt->convergence = 1.0f;     // lib.rs:189-194
     opt->strategy = KMG_STRATEGY_AUTO;
+    opt->alpha_cutoff = 0;
 }
 KMG_ABI_CATCH_VOID
 
@@ -156,13 +157,16 @@ try {
     kmg_options o;
     kmg_default_options(&o);
     if (opt) {
-        // (the struct grew by `strategy` in round 6: a caller compiled against the previous header passes the old size)
+        // (the struct grew by `strategy` in round 6 and by `alpha_cutoff` after it: a caller compiled against an earlier header
+        // passes its size, and the fields it does not know keep their defaults)
         constexpr uint32_t kOldSize = (uint32_t)offsetof(kmg_options, strategy);
-        if (opt->struct_size != sizeof(kmg_options) && opt->struct_size != kOldSize)
+        constexpr uint32_t kNoAlphaSize = (uint32_t)offsetof(kmg_options, alpha_cutoff);
+        if (opt->struct_size != sizeof(kmg_options) && opt->struct_size != kNoAlphaSize && opt->struct_size != kOldSize)
             return fail(KMG_ERR_INVALID_ARGUMENT, "kmg_options.struct_size mismatch");
         memcpy(&o, opt, opt->struct_size);
         o.struct_size = sizeof(kmg_options);
         if ((o.strategy & 3) == 3 || (o.strategy & ~7) != 0) return fail(KMG_ERR_INVALID_ARGUMENT, "kmg_options.strategy: unknown value %d", o.strategy);
+        if (o.alpha_cutoff > 255u) return fail(KMG_ERR_INVALID_ARGUMENT, "kmg_options.alpha_cutoff: %u is above 255", o.alpha_cutoff);
         if (o.max_iterations == 0 || o.check_period == 0)
             return fail(KMG_ERR_INVALID_ARGUMENT, "max_iterations and check_period must be > 0");
     }
@@ -182,6 +186,7 @@ try {
     p->device = dev;
     p->opt = o;
     p->strategy.store(o.strategy);
+    p->alpha_cutoff.store(o.alpha_cutoff);
     p->d_lut = nullptr;
     p->d_bounds = nullptr;
     p->d_sub_bounds = nullptr;
@@ -301,6 +306,15 @@ try {
 }
 KMG_ABI_CATCH
 
+extern "C" int kmg_processor_set_alpha_cutoff(kmg_processor *p, uint32_t alpha_cutoff)
+try {
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
+    if (alpha_cutoff > 255u) return fail(KMG_ERR_INVALID_ARGUMENT, "alpha_cutoff: %u is above 255", alpha_cutoff);
+    p->alpha_cutoff.store(alpha_cutoff);
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
 extern "C" void kmg_processor_destroy(kmg_processor *p)
 try {
     if (!p) return;
@@ -375,6 +389,20 @@ try {
     if (!p || !d_rgba || !d_lab3 || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad rgb_to_lab arguments");
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(launch_rgb_to_lab((const uint32_t *)d_rgba, n, p->d_lut, d_lab3, S(stream)));
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_dev_alpha_compact(kmg_processor *p, const uint8_t *d_rgba, uint64_t n, uint32_t cutoff, uint8_t *d_out,
+                                     uint64_t *d_n_kept, void *stream)
+try {
+    if (!p || !d_rgba || !d_out || !d_n_kept || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad alpha_compact arguments");
+    if (cutoff > 255u) return fail(KMG_ERR_INVALID_ARGUMENT, "alpha cutoff %u is above 255", cutoff);
+    HIP_TRY(hipSetDevice(p->device));
+    StreamBuf counts;                                                  // per-workgroup counts (kmg_alpha.hip)
+    HIP_TRY(counts.alloc(p, sizeof(unsigned long long) * alpha_compact_grid(n), S(stream)));
+    HIP_TRY(launch_alpha_compact((const uint32_t *)d_rgba, n, cutoff, (uint32_t *)d_out, (unsigned long long *)d_n_kept,
+                                 (unsigned long long *)counts.ptr, S(stream)));
     return KMG_OK;
 }
 KMG_ABI_CATCH

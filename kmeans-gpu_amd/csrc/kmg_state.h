@@ -64,6 +64,7 @@ struct kmg_processor {
     int device;
     kmg_options opt;
     std::atomic<int> strategy{0};   // KMG_STRATEGY_* (kmg_options.strategy, kmg_processor_set_strategy)
+    std::atomic<uint32_t> alpha_cutoff{0};   // kmg_options.alpha_cutoff, kmg_processor_set_alpha_cutoff (0 = alpha ignored)
     float *d_lut;            // 256 x f32: sRGB decode * 100, then 256 x f32: thresholds of the sRGB8 encode (k_meld)
     std::mutex mu;           // guards the lazily built static tables below
     CellBounds *d_bounds;    // kCells static cell bounds of the colour-table strategy

@@ -151,6 +151,14 @@ public:
         return out;
     }
 
+    // kmg_options.alpha_cutoff of a single-device processor (0 = alpha ignored, 1..255 = alpha mode; include/kmeans_hip.h).  Set
+    // it at creation through create(opt) or here; a processor over several devices has no alpha mode.
+    void set_alpha_cutoff(uint32_t alpha_cutoff) const
+    {
+        if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "a processor over several devices has no alpha mode");
+        check(kmg_processor_set_alpha_cutoff(p_, alpha_cutoff));
+    }
+
     kmg_processor *handle() const { return g_ ? kmg_group_processor(g_, 0) : p_; }
     kmg_group *group() const { return g_; }
 

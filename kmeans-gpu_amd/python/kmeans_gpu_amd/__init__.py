@@ -65,7 +65,7 @@ class ReduceMode(enum.IntEnum):         # core/src/lib.rs:234-239, plus Diffuse 
 class Options(C.Structure):             # include/kmeans_hip.h kmg_options
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("shrink_max_dim", C.c_uint32),
                 ("max_iterations", C.c_uint32), ("check_period", C.c_uint32), ("convergence", C.c_float),
-                ("strategy", C.c_int32)]
+                ("strategy", C.c_int32), ("alpha_cutoff", C.c_uint32)]
 
 
 # kmg_options.strategy (include/kmeans_hip.h KMG_STRATEGY_*): results are identical either way, only the time differs
@@ -128,9 +128,9 @@ _lib = None
 # every symbol include/kmeans_hip.h declares
 SYMBOLS = [
     "kmg_last_error", "kmg_version", "kmg_host_alloc", "kmg_host_free", "kmg_default_options", "kmg_processor_create",
-    "kmg_processor_create_ex", "kmg_processor_destroy", "kmg_processor_set_strategy", "kmg_palette", "kmg_find", "kmg_reduce",
+    "kmg_processor_create_ex", "kmg_processor_destroy", "kmg_processor_set_strategy", "kmg_processor_set_alpha_cutoff", "kmg_palette", "kmg_find", "kmg_reduce",
     "kmg_palette_to_centroids", "kmg_centroids_to_palette", "kmg_octree_palette", "kmg_dev_rgb_to_lab",
-    "kmg_resized_dims",
+    "kmg_resized_dims", "kmg_dev_alpha_compact",
     "kmg_dev_resize", "kmg_lloyd_create", "kmg_lloyd_destroy", "kmg_lloyd_set_centroids",
     "kmg_lloyd_get_centroids", "kmg_lloyd_init_centroids", "kmg_lloyd_init_step", "kmg_lloyd_init_pick_band",
     "kmg_lloyd_set_centroid_rgba", "kmg_init_first_key", "kmg_lloyd_assign_accumulate",
@@ -243,6 +243,8 @@ def lib():
     L.kmg_apply_plan_status.argtypes = [vp]
     L.kmg_dither_threshold.argtypes = [f32p, C.c_uint32, C.POINTER(C.c_float)]
     L.kmg_processor_set_strategy.argtypes = [vp, C.c_int]
+    L.kmg_processor_set_alpha_cutoff.argtypes = [vp, C.c_uint32]
+    L.kmg_dev_alpha_compact.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, u8p, vp, vp]
     L.kmg_default_group_options.argtypes = [C.POINTER(GroupOptions)]
     L.kmg_default_group_options.restype = None
     L.kmg_group_create.argtypes = [C.POINTER(GroupOptions), C.POINTER(vp)]
@@ -393,7 +395,9 @@ class ImageProcessor:
     """Mirror of `kmeans_color_gpu::ImageProcessor` (core/src/lib.rs:24-165)."""
 
     def __init__(self, device=-1, shrink_max_dim=256, max_iterations=128, check_period=8,
-                 convergence=1.0, strategy=None):
+                 convergence=1.0, strategy=None, alpha_cutoff=0):
+        """alpha_cutoff: 0 = alpha ignored (the reference's behaviour); 1..255 = alpha mode (include/kmeans_hip.h at
+        kmg_options): only pixels whose alpha is >= alpha_cutoff shape the palette, and the outputs keep the input's alpha"""
         self._h = C.c_void_p()
         o = default_options()
         o.device = device
@@ -402,9 +406,15 @@ class ImageProcessor:
         o.check_period = check_period
         o.convergence = convergence
         o.strategy = _default_strategy if strategy is None else _strategy_value(strategy)
+        o.alpha_cutoff = int(alpha_cutoff)
         _check(lib().kmg_processor_create_ex(C.byref(o), C.byref(self._h)))
         self.options = o
         _register(self)
+
+    def set_alpha_cutoff(self, alpha_cutoff):
+        """kmg_processor_set_alpha_cutoff: 0 (alpha ignored) or 1..255 (alpha mode) for the calls that start from now on"""
+        _check(lib().kmg_processor_set_alpha_cutoff(self._h, int(alpha_cutoff)))
+        self.options.alpha_cutoff = int(alpha_cutoff)
 
     def set_strategy(self, strategy):
         """kmg_processor_set_strategy: "auto" | "scan" | "table" [+ "mask_words"] (or the KMG_STRATEGY_* bits)"""
@@ -467,6 +477,11 @@ class ImageProcessor:
     def resize(self, d_rgba, width, height, new_width, new_height, d_out, stream=0):
         _check(lib().kmg_dev_resize(self._h, C.c_void_p(d_rgba), width, height, new_width, new_height,
                                     C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def alpha_compact(self, d_rgba, n_pixels, cutoff, d_out, d_n_kept, stream=0):
+        """kmg_dev_alpha_compact: d_out[0 .. n_kept) = the pixels with alpha >= cutoff, in order; the u64 at d_n_kept (device) = n_kept"""
+        _check(lib().kmg_dev_alpha_compact(self._h, C.c_void_p(d_rgba), int(n_pixels), int(cutoff), C.c_void_p(d_out),
+                                           C.c_void_p(d_n_kept), C.c_void_p(stream)))
 
     def apply(self, d_rgba, width, rows, row0, centroids4, mode, d_out, stream=0):
         c = np.ascontiguousarray(centroids4, np.float32).reshape(-1, 4)

@@ -5,6 +5,9 @@
     python -m kmeans_gpu_amd.cli find    -i img.png -p "#050505,#ffffff,#ff0000"|palette.png [-m ...] [-o out.png]
     python -m kmeans_gpu_amd.cli palette -i img.png -c 8 [-a ...] [-s 40] [-o out.png]
 
+Every sub-command also takes `--alpha-cutoff N` (0..255, default 0 = alpha ignored, as in the reference): with N >= 1 only the
+pixels whose alpha is at least N shape the palette, and the output keeps the input's alpha (include/kmeans_hip.h, kmg_options).
+
 Image decoding/encoding (the `image` crate in the reference) is done with Pillow.  One flag the reference does not have:
 `--devices 0,1,...` (before the sub-command) runs the same operation over several GPUs of the node (kmg_group_*: the image
 tiled in row bands, same bytes).
@@ -105,6 +108,16 @@ def validate_size(s):                                       # args.rs:36-38 valu
     return v
 
 
+def validate_alpha_cutoff(s):
+    try:
+        v = int(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid value '{s}': not an integer")
+    if not 0 <= v <= 255:
+        raise argparse.ArgumentTypeError(f"{v} is not in 0..=255")
+    return v
+
+
 def validate_devices(s):
     try:
         devices = [int(v) for v in s.split(",")]
@@ -137,10 +150,19 @@ def main(argv=None):
     r.add_argument("-o", "--output", type=validate_filename)
     r.add_argument("-a", "--algo", choices=list(_ALGOS), default="kmeans")
     r.add_argument("-m", "--mode", choices=list(_MODES), default="replace")
+    for s in (p, f, r):
+        s.add_argument("--alpha-cutoff", type=validate_alpha_cutoff, default=0,
+                       help="1..255: pixels with a lower alpha do not shape the palette, the output keeps the input's alpha")
     args = ap.parse_args(argv)
+    if args.devices and args.alpha_cutoff:
+        ap.error("--alpha-cutoff is not supported with --devices")
 
     image = _load(args.input)
-    with (Group(devices=args.devices) if args.devices else ImageProcessor()) as proc:
+    if args.devices:
+        proc = Group(devices=args.devices)
+    else:
+        proc = ImageProcessor(alpha_cutoff=args.alpha_cutoff) if args.alpha_cutoff else ImageProcessor()
+    with proc:
         if args.command == "palette":                    # main.rs:46-72
             colors = proc.palette(args.colorcount, image, _ALGOS[args.algo])
             out = np.repeat(np.repeat(colors[None, :, :], args.size, axis=0), args.size, axis=1)   # main.rs:221-239

@@ -23,6 +23,7 @@ pub struct kmg_options {
     pub check_period: u32,
     pub convergence: f32,
     pub strategy: i32,
+    pub alpha_cutoff: u32,
 }
 
 /// `kmg_options.strategy` (KMG_STRATEGY_*): 0 = the library's cost models decide per call; results are identical either way.
@@ -67,6 +68,7 @@ extern "C" {
     pub fn kmg_processor_create_ex(opt: *const kmg_options, out: *mut *mut kmg_processor) -> c_int;
     pub fn kmg_processor_destroy(p: *mut kmg_processor);
     pub fn kmg_processor_set_strategy(p: *mut kmg_processor, strategy: c_int) -> c_int;
+    pub fn kmg_processor_set_alpha_cutoff(p: *mut kmg_processor, alpha_cutoff: u32) -> c_int;
     // ImageProcessor::palette -- lib.rs:67-77
     pub fn kmg_palette(
         p: *mut kmg_processor,

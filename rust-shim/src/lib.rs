@@ -62,6 +62,16 @@ impl ImageProcessor {
         Ok(ImageProcessor { raw: std::ptr::null_mut(), group })
     }
 
+    /// Alpha mode (`kmg_options.alpha_cutoff`, include/kmeans_hip.h): 0 ignores alpha as the reference does; 1..=255 lets
+    /// only pixels whose alpha is at least `alpha_cutoff` shape the palette, and the outputs keep the input's alpha.  No
+    /// counterpart in the reference.  A processor over several devices has no alpha mode.
+    pub fn set_alpha_cutoff(&self, alpha_cutoff: u32) -> Result<()> {
+        if !self.group.is_null() {
+            return Err(anyhow!("a processor over several devices has no alpha mode"));
+        }
+        check(unsafe { ffi::kmg_processor_set_alpha_cutoff(self.raw, alpha_cutoff) })
+    }
+
     /// lib.rs:67-77: `color_count` dominant colours, sorted by Lab lightness (k-means: exactly
     /// `color_count`; octree: at most).
     pub async fn palette<C: Container>(
