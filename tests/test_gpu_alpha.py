@@ -1,7 +1,8 @@
 """Alpha mode (kmg_options.alpha_cutoff) on the device, bit for bit against tests/alpha_ref.py: kmg_dev_alpha_compact against
-numpy, kmg_palette / kmg_reduce (k-means and octree) / kmg_find in all four modes under both strategies, the edge cases of the
+numpy (also with empty trailing workgroups and unaligned input and output), kmg_palette / kmg_reduce (k-means and octree) / kmg_find in all four modes under both strategies, the edge cases of the
 contract (every pixel kept, fewer kept than k, none kept), a diffusion through an apply plan in two bands, an 8192^2 image with
-random alpha, and the Python and CLI layers."""
+random alpha, the Python and CLI layers, and the palette step at full resolution (shrink_max_dim = 0), up to more than 2^24
+kept pixels.  tests/test_gpu_alpha_routes.py runs every output route in alpha mode."""
 import ctypes as C
 import os
 
@@ -52,6 +53,50 @@ def test_compact_matches_numpy(processor, torch_cuda, n, pattern):
     assert n_kept == want.shape[0]
     assert np.array_equal(out[:n_kept], want)
     assert (out[n_kept:] == 0xAB).all()
+
+
+def _edge_alpha(layout, n, t, rng):
+    if layout == "random":                                  # random bytes, half of them t - 1 or t
+        a = rng.integers(0, 256, n).astype(np.uint8)
+        pick = rng.random(n) < 0.5
+        a[pick] = np.array([t - 1, t], np.uint8)[rng.integers(0, 2, int(pick.sum()))]
+        return a
+    a = np.zeros(n, np.uint8)
+    if layout == "runs":                                    # 1024 kept, 4096 not, 1024 kept, ...: whole tiles and chunks empty
+        run = np.arange(n) % 5120
+        a[run < 1024] = 255
+    elif layout == "first":
+        a[0] = 255
+    else:
+        a[-1] = 255
+    return a
+
+
+@pytest.mark.parametrize("n", [2048 * 1024 - 1, 2048 * 1024 + 1, 2049 * 1024 + 3, 3 * 2048 * 1024 + 5])
+@pytest.mark.parametrize("layout", ["random", "runs", "first", "last"])
+def test_compact_at_its_grid_edges(processor, torch_cuda, n, layout):
+    """more tiles (1024 pixels) than the 2048-workgroup cap, unevenly (empty trailing workgroups); the input 1, 2 or 3 pixels into
+    a device buffer (the unaligned loads) and the output 1 pixel into a sentinel-filled one; cutoffs 1, 2, 254, 255"""
+    torch = torch_cuda
+    rng = np.random.default_rng(n + len(layout))
+    st = torch.cuda.current_stream().cuda_stream
+    for i, t in enumerate((1, 2, 254, 255)):
+        off = 1 + i % 3
+        px = rng.integers(0, 256, (n, 4), dtype=np.uint8)
+        px[:, 3] = _edge_alpha(layout, n, t, rng)
+        buf = np.zeros((n + 4, 4), np.uint8)
+        buf[off:off + n] = px
+        d_in = torch.from_numpy(buf).cuda()
+        d_out = torch.full((n + 65, 4), 0xAB, dtype=torch.uint8, device="cuda")
+        d_n = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+        processor.alpha_compact(d_in.data_ptr() + 4 * off, n, t, d_out.data_ptr() + 4, d_n.data_ptr(), st)
+        torch.cuda.synchronize()
+        n_kept = int(d_n.item())
+        out = d_out.cpu().numpy()
+        want = alpha_ref.compact(px, t)
+        assert n_kept == want.shape[0], (t, off)
+        assert np.array_equal(out[1:1 + n_kept], want), (t, off)
+        assert (out[0] == 0xAB).all() and (out[1 + n_kept:] == 0xAB).all(), (t, off)
 
 
 def test_compact_cutoff_zero_copies_and_256_is_refused(processor, torch_cuda):
@@ -108,7 +153,7 @@ def test_reduce_at_cutoff_128_and_large_k(oracle, aproc, images, strategy):
         for mode in (0, 1, 3):
             assert np.array_equal(aproc.reduce(8, img, reduce_mode=mode), alpha_ref.reduce_kmeans(oracle, img, 8, mode, 128))
         cent = alpha_ref.kmeans_centroids(oracle, img, 300, 128)
-        for mode in (0, 1, 2):
+        for mode in (0, 1, 2, 3):
             assert np.array_equal(aproc.reduce(300, img, reduce_mode=mode), alpha_ref.apply(oracle, img, cent, mode, 128))
     finally:
         aproc.set_alpha_cutoff(1)
@@ -234,3 +279,77 @@ def test_group_create_refuses_alpha_mode(torch_cuda):
     o.processor.alpha_cutoff = 1
     h = C.c_void_p()
     assert L.kmg_group_create(C.byref(o), C.byref(h)) == -1 and b"alpha_cutoff" in L.kmg_last_error()
+
+
+# ---- the palette step at full resolution (shrink_max_dim = 0): the kept pixels as one row of n_kept pixels ----------------------
+FULL_T = 128
+_full_refs = {}
+
+
+@pytest.fixture(scope="module")
+def full_disc(tokyo):
+    """the photograph tiled to 1536 x 1024 under a soft disc: about 0.53 M kept pixels, an image of 0.53 M x 1"""
+    return alpha_ref.soft_disc(np.ascontiguousarray(np.tile(tokyo, (2, 2, 1))[:1024, :1536]))
+
+
+@pytest.fixture(scope="module")
+def full_proc(torch_cuda):
+    import kmeans_gpu_amd as kg
+    p = kg.ImageProcessor(shrink_max_dim=0, alpha_cutoff=FULL_T)
+    yield p
+    p.close()
+
+
+def _full_centroids(oracle, img, k):
+    if k not in _full_refs:
+        _full_refs[k] = alpha_ref.kmeans_centroids(oracle, img, k, FULL_T, shrink_max_dim=0)
+    return _full_refs[k]
+
+
+def _palette_of(oracle, cent):
+    pal = np.full((cent.shape[0], 4), 255, np.uint8)
+    for j in range(cent.shape[0]):
+        pal[j, :3] = oracle.palette_lab_to_srgb8(cent[j, :3])
+    return alpha_ref.sorted_by_L(oracle, pal)
+
+
+@pytest.mark.parametrize("strategy", ["scan", "table", "auto"])
+@pytest.mark.parametrize("k", [8, 64])
+def test_full_resolution_palette(oracle, full_proc, full_disc, k, strategy):
+    set_strategy(strategy)
+    assert np.array_equal(full_proc.palette(k, full_disc), _palette_of(oracle, _full_centroids(oracle, full_disc, k)))
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_full_resolution_reduce(oracle, full_proc, full_disc, mode):
+    want = alpha_ref.apply(oracle, full_disc, _full_centroids(oracle, full_disc, 8), mode, FULL_T)
+    assert np.array_equal(full_proc.reduce(8, full_disc, reduce_mode=mode), want)
+
+
+def test_full_resolution_more_than_2_24_kept(oracle, torch_cuda):
+    """n_kept = 17000023 > 2^24: (float)n_kept is rounded, and the first key of the initialisation, pixel
+    (int)((float)width * 0.5625f), is two pixels before floor(9 width / 16)"""
+    import kmeans_gpu_amd as kg
+    w, h, n_kept = 5000, 4000, 17000023
+    assert int(np.float32(n_kept) * np.float32(0.5625)) == n_kept * 9 // 16 + 2
+    rng = np.random.default_rng(24)
+    n = w * h
+    c = rng.integers(0, 256, (40, 3))
+    img = np.empty((n, 4), np.uint8)
+    img[:, :3] = np.clip(c[rng.integers(0, 40, n)] + rng.normal(0, 12, (n, 3)), 0, 255).astype(np.uint8)
+    img[:, 3] = rng.integers(FULL_T, 256, n, dtype=np.uint8)
+    img[rng.permutation(n)[:n - n_kept], 3] = rng.integers(0, FULL_T, n - n_kept, dtype=np.uint8)
+    img = img.reshape(h, w, 4)
+    assert int((img[..., 3] >= FULL_T).sum()) == n_kept
+    with kg.ImageProcessor(shrink_max_dim=0, alpha_cutoff=FULL_T) as p:
+        assert np.array_equal(p.palette(8, img), alpha_ref.palette_kmeans(oracle, img, 8, FULL_T, shrink_max_dim=0))
+
+
+def test_full_resolution_every_pixel_kept_is_the_default_call(torch_cuda, tokyo):
+    import kmeans_gpu_amd as kg
+    img = np.ascontiguousarray(np.tile(tokyo, (2, 2, 1))[:1024, :1536])
+    img[..., 3] = np.random.default_rng(4).integers(FULL_T, 256, img.shape[:2], dtype=np.uint8)
+    with kg.ImageProcessor(shrink_max_dim=0, alpha_cutoff=FULL_T) as pa, kg.ImageProcessor(shrink_max_dim=0) as pd:
+        assert np.array_equal(pa.palette(16, img), pd.palette(16, img))
+        got, ref = pa.reduce(16, img, reduce_mode=kg.ReduceMode.Dither), pd.reduce(16, img, reduce_mode=kg.ReduceMode.Dither)
+        assert np.array_equal(got[..., :3], ref[..., :3]) and np.array_equal(got[..., 3], img[..., 3])

@@ -74,3 +74,15 @@ def test_random_group_calls_equal_the_single_processor(seed):
                        timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "24 cases, 0 mismatching" in r.stdout
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", [1, 2])
+def test_random_alpha_calls_equal_the_references(seed):
+    """tools/fuzz_alpha.py: kmg_reduce / kmg_palette / kmg_find with random alpha_cutoff (0 included), alpha layouts, k, all four
+    modes, both algorithms, every strategy and shrink_max_dim 256 or 0, against tests/alpha_ref.py (t > 0) or the oracle and
+    tests/diffuse_ref.py (t = 0), byte for byte; no kept pixel must be refused with status -1"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_alpha.py"), "30", str(seed)],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "30 cases, 0 mismatching" in r.stdout
