@@ -73,6 +73,28 @@ typedef enum kmg_reduce_mode {
     KMG_MODE_DIFFUSE = 3
 } kmg_reduce_mode;
 
+/* Output format of the output passes (kmg_apply_plan_create_format, kmg_dev_apply_format, kmg_find_indexed, kmg_reduce_indexed).
+ * KMG_FORMAT_RGBA8 is the RGBA8 image every other call writes: the same bytes.  The index formats write one uint8_t / uint16_t
+ * per pixel, tightly packed, row-major: the label i the mode picks for the pixel -- the very label whose palette bytes the RGBA8
+ * call of the same arguments writes, so out_rgba8 = (P[i].rgb, a) with P = the palette of the output pass (lab_to_rgb.wgsl of
+ * centroid i; kmg_reduce_indexed returns it; kmg_centroids_to_palette converts with the palette crate instead and can differ
+ * from it by one LSB where a channel rounds at .5).  For kmg_find_indexed, i is entry i of the caller's palette; the RGBA8
+ * output holds its re-encoded bytes (kmg_palette_to_centroids, then lab_to_rgb.wgsl).
+ *  - Modes: replace, dither and diffuse, each with its per-pixel decision unchanged bit for bit (the Bayer coordinates from
+ *    row0, the diffusion carried across the bands of a plan).  KMG_MODE_MELD blends two colours and has no index:
+ *    KMG_ERR_INVALID_ARGUMENT.
+ *  - Every index is < k.  The dither scan starts from the reference's sentinel (label k, mix_colors.wgsl:73); it cannot win for
+ *    an sRGB8 pixel when every centroid lies in the box L in [-100, 200], a, b in [-300, 300], so the index
+ *    formats refuse (KMG_ERR_INVALID_ARGUMENT) a table with a non-finite component or one outside that box.  Every table
+ *    kmg_palette, kmg_palette_to_centroids or kmg_reduce produces lies inside it.  (KMG_FORMAT_RGBA8 accepts any table, as before.)
+ *  - Alpha mode (kmg_options.alpha_cutoff = t > 0): a pixel with alpha < t is written as index k, the transparent slot; kept
+ *    pixels get their normal index (their partial alpha is not represented).  Diffusion: unchanged, excluded pixels pass no
+ *    error on.
+ *  - Limits: KMG_FORMAT_INDEX8 needs k <= 256 (k <= 255 in alpha mode), KMG_FORMAT_INDEX16 takes any k <= KMG_MAX_K; device
+ *    outputs of KMG_FORMAT_INDEX16 are 2-byte aligned.  Otherwise KMG_ERR_INVALID_ARGUMENT.  The kmg_group_* calls have no
+ *    index output. */
+typedef enum kmg_output_format { KMG_FORMAT_RGBA8 = 0, KMG_FORMAT_INDEX8 = 1, KMG_FORMAT_INDEX16 = 2 } kmg_output_format;
+
 #define KMG_FIX_SHIFT 20
 /* largest k: the kernels keep 48 bytes of LDS per cluster (centroid + int64 sums), 160 KiB per CU */
 #define KMG_MAX_K 3072u
@@ -174,6 +196,16 @@ KMG_API int kmg_find(kmg_processor *p, const uint8_t *rgba, uint32_t width, uint
 /* ---- ImageProcessor::reduce  (core/src/lib.rs:116-164) --------------------------------- */
 KMG_API int kmg_reduce(kmg_processor *p, const uint8_t *rgba, uint32_t width, uint32_t height,
                        uint32_t color_count, int algo, int mode, uint8_t *out_rgba);
+
+/* ---- the same two calls with an output format (kmg_output_format) ------------------------
+ * out_index: width * height pixels of the format (4, 1 or 2 bytes each).  kmg_reduce_indexed also returns the palette in index
+ * order -- the centroid order of the output pass, NOT sorted (k-means: the Lloyd loop's order; octree: kmg_palette's order) --
+ * as the bytes the RGBA8 output writes for each index: out_palette_rgba has room for color_count x 4 bytes, *out_count
+ * receives the number of entries.  KMG_FORMAT_RGBA8 writes exactly what kmg_find / kmg_reduce write.                   */
+KMG_API int kmg_find_indexed(kmg_processor *p, const uint8_t *rgba, uint32_t width, uint32_t height,
+                             const uint8_t *palette_rgba, uint32_t n_colors, int mode, int format, void *out_index);
+KMG_API int kmg_reduce_indexed(kmg_processor *p, const uint8_t *rgba, uint32_t width, uint32_t height, uint32_t color_count,
+                               int algo, int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out_index);
 
 /* ---- host-side colour helpers the reference takes from the `palette` crate -------------
  * CentroidsBuffer::fixed_centroids (core/src/structures.rs:523-553): sRGB8 -> Lab (L,a,b,1)  */
@@ -410,6 +442,13 @@ KMG_API int kmg_dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t widt
  * stream synchronisation + destroy.  (The reference runs the pass on whole textures only: operations.rs:99-155.)              */
 KMG_API int kmg_apply_plan_create(kmg_processor *p, const float *centroids4, uint32_t k, int mode, uint64_t n_pixels_hint,
                                   void *stream, kmg_apply_plan **out);
+/* The same with an output format (kmg_output_format): kmg_apply_plan_run then writes that format into its d_out_rgba (a
+ * uint8_t / uint16_t per pixel for the index formats); kmg_dev_apply_format = kmg_dev_apply with it.  KMG_FORMAT_RGBA8: the
+ * calls above, byte for byte.                                                                                             */
+KMG_API int kmg_apply_plan_create_format(kmg_processor *p, const float *centroids4, uint32_t k, int mode, int format,
+                                         uint64_t n_pixels_hint, void *stream, kmg_apply_plan **out);
+KMG_API int kmg_dev_apply_format(kmg_processor *p, const uint8_t *d_rgba, uint32_t width, uint32_t rows, uint32_t row0,
+                                 const float *centroids4, uint32_t k, int mode, int format, void *d_out, void *stream);
 KMG_API int kmg_apply_plan_run(kmg_apply_plan *plan, const uint8_t *d_rgba, uint32_t width, uint32_t rows, uint32_t row0,
                                uint8_t *d_out_rgba, void *stream);
 KMG_API void kmg_apply_plan_destroy(kmg_apply_plan *plan, int synchronise);

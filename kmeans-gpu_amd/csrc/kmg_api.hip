@@ -143,14 +143,15 @@ int upload_image(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, 
 }
 
 // find_colors / dither_colors + OutputTexture::pull_image (structures.rs:441-470)
+// (format: kmg_output_format; out_rgba then holds 4, 1 or 2 bytes per pixel)
 int apply_and_download(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, const float *c4,
-                       uint32_t k, int mode, uint32_t alpha_cutoff, hipStream_t st, uint8_t *out_rgba)
+                       uint32_t k, int mode, uint32_t alpha_cutoff, hipStream_t st, uint8_t *out_rgba, int format = KMG_FORMAT_RGBA8)
 {
     int rc;
     StreamBuf out;
-    const size_t bytes = (size_t)w * h * 4;
+    const size_t bytes = (size_t)w * h * (format == KMG_FORMAT_INDEX8 ? 1u : format == KMG_FORMAT_INDEX16 ? 2u : 4u);
     HIP_TRY(out.alloc(p, bytes, st));
-    if ((rc = dev_apply(p, d_rgba, w, h, 0, c4, k, mode, (uint8_t *)out.ptr, st, alpha_cutoff)) != KMG_OK) return rc;
+    if ((rc = dev_apply(p, d_rgba, w, h, 0, c4, k, mode, (uint8_t *)out.ptr, st, alpha_cutoff, format)) != KMG_OK) return rc;
     HIP_TRY(copy_host_image(p, out_rgba, out.ptr, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return KMG_OK;
@@ -252,6 +253,67 @@ try {
     StreamBuf img;
     if ((rc = upload_image(p, rgba, w, h, sg.st, img)) != KMG_OK) return rc;
     return apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), n_colors, mode, alpha_cutoff, sg.st, out_rgba);
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_find_indexed(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, const uint8_t *palette_rgba,
+                                uint32_t n_colors, int mode, int format, void *out_index)
+try {
+    int rc;
+    if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
+    if (!palette_rgba || n_colors == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "palette is empty");
+    if (!out_index) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
+    if (format < KMG_FORMAT_RGBA8 || format > KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
+    HIP_TRY(hipSetDevice(p->device));
+    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
+    StreamGuard sg;
+    HIP_TRY(sg.acquire(p));
+    std::vector<float> c4(4 * (size_t)n_colors);
+    if ((rc = kmg_palette_to_centroids(palette_rgba, n_colors, c4.data())) != KMG_OK) return rc;
+    StreamBuf img;
+    if ((rc = upload_image(p, rgba, w, h, sg.st, img)) != KMG_OK) return rc;
+    return apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), n_colors, mode, alpha_cutoff, sg.st, (uint8_t *)out_index, format);
+}
+KMG_ABI_CATCH
+
+// kmg_reduce with an output format; the palette comes back in index order as the bytes the output pass writes (lab_to_rgb.wgsl of
+// each centroid -- kmg_apply.hip's plan palette)
+extern "C" int kmg_reduce_indexed(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t color_count, int algo,
+                                  int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out_index)
+try {
+    int rc;
+    if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
+    if (color_count == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
+    if (!out_index || !out_palette_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
+    if (algo != KMG_ALGO_KMEANS && algo != KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown algorithm %d", algo);
+    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_DIFFUSE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
+    if (format < KMG_FORMAT_RGBA8 || format > KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
+    if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
+        return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
+    HIP_TRY(hipSetDevice(p->device));
+    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
+    StreamGuard sg;
+    HIP_TRY(sg.acquire(p));
+    StreamBuf img;
+    if ((rc = upload_image(p, rgba, w, h, sg.st, img)) != KMG_OK) return rc;
+    std::vector<float> c4;
+    if (algo == KMG_ALGO_OCTREE) {                                     // lib.rs:133-136
+        std::vector<std::array<uint8_t, 4>> colors;
+        if ((rc = octree_palette_of(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, colors)) != KMG_OK) return rc;
+        if (colors.empty()) return fail(KMG_ERR_INVALID_ARGUMENT, "the octree returned no colour");
+        if (colors.size() > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "the octree returned %zu colours, more than KMG_MAX_K = %u", colors.size(), KMG_MAX_K);
+        c4.resize(4 * colors.size());
+        if ((rc = kmg_palette_to_centroids(colors[0].data(), (uint32_t)colors.size(), c4.data())) != KMG_OK) return rc;
+    } else {
+        c4.resize(4 * (size_t)color_count);
+        if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data())) != KMG_OK) return rc;
+    }
+    const uint32_t k = (uint32_t)(c4.size() / 4);
+    if ((rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), k, mode, alpha_cutoff, sg.st, (uint8_t *)out_index, format)) != KMG_OK)
+        return rc;
+    for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], out_palette_rgba + 4 * i);
+    *out_count = k;
+    return KMG_OK;
 }
 KMG_ABI_CATCH
 

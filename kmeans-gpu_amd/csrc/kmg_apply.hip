@@ -193,6 +193,7 @@ struct kmg_apply_plan {
     kmg_processor *p = nullptr;
     uint32_t k = 0;
     int mode = 0;
+    int format = KMG_FORMAT_RGBA8;      // kmg_output_format of what _run writes
     uint32_t alpha_cutoff = 0;          // kmg_options.alpha_cutoff when the plan was made (0: alpha ignored)
     bool dither = false;
     float thr = 0.0f;
@@ -201,6 +202,7 @@ struct kmg_apply_plan {
     std::vector<uint8_t> staged;        // host copy of the tables: lives as long as the asynchronous upload may
     Centroid *d_cent = nullptr;
     uint32_t *d_pal = nullptr;
+    uint32_t *d_ident = nullptr;        // index formats, kDitherMasks: the identity table (entry i = i) its kernels take as palette
     void *aux = nullptr;                // candidate lists / masks, or the per-colour labels (kReplaceTable)
     uint16_t *sub = nullptr;            // kReplaceTable: the label pass's first-level tables
     hipEvent_t ready = nullptr;         // the tables are built (recorded on the creating stream)
@@ -222,19 +224,39 @@ struct kmg_apply_plan {
     }
 };
 
+// The index formats (include/kmeans_hip.h at kmg_output_format): the mode has an index, k fits the format (with the transparent
+// slot in alpha mode), and every centroid lies in the box inside which the dither scan's sentinel never wins.
+static int check_index_format(const float *c4, uint32_t k, int mode, int format, uint32_t alpha_cutoff)
+{
+    if (format != KMG_FORMAT_INDEX8 && format != KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
+    if (mode == KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "meld blends two colours: it has no index output");
+    const uint32_t slots = k + (alpha_cutoff ? 1u : 0u);
+    if (format == KMG_FORMAT_INDEX8 && slots > 256u)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u%s needs INDEX16", k, alpha_cutoff ? " plus the transparent slot" : "");
+    for (uint32_t i = 0; i < k; ++i) {
+        const float L = c4[4 * i], a = c4[4 * i + 1], b = c4[4 * i + 2];
+        if (!(L >= kIndexBoxLmin && L <= kIndexBoxLmax && a >= -kIndexBoxAB && a <= kIndexBoxAB && b >= -kIndexBoxAB && b <= kIndexBoxAB))
+            return fail(KMG_ERR_INVALID_ARGUMENT, "centroid %u (%g, %g, %g) is outside L in [-100, 200], a, b in [-300, 300] (index formats)",
+                        i, (double)L, (double)a, (double)b);
+    }
+    return KMG_OK;
+}
+
 static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, uint64_t n_pixels_hint, void *stream,
-                       uint32_t alpha_cutoff, kmg_apply_plan **out)
+                       uint32_t alpha_cutoff, kmg_apply_plan **out, int format = KMG_FORMAT_RGBA8)
 {
     if (!p || !c4 || !out || k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply_plan arguments");
     *out = nullptr;
     if (k > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", k, KMG_MAX_K);
     if (mode != KMG_MODE_REPLACE && mode != KMG_MODE_DITHER && mode != KMG_MODE_MELD && mode != KMG_MODE_DIFFUSE)
         return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
+    int rc0;
+    if (format != KMG_FORMAT_RGBA8 && (rc0 = check_index_format(c4, k, mode, format, alpha_cutoff)) != KMG_OK) return rc0;
     HIP_TRY(hipSetDevice(p->device));
     kmg_apply_plan *pl = new (std::nothrow) kmg_apply_plan();
     if (!pl) return fail(KMG_ERR_OUT_OF_MEMORY, "host allocation failed");
     struct Undo { kmg_apply_plan *pl; ~Undo() { if (pl) { if (pl->ready) (void)hipEventDestroy(pl->ready); (void)hipStreamSynchronize(pl->built_on); delete pl; } } } undo{pl};
-    pl->p = p; pl->k = k; pl->mode = mode; pl->alpha_cutoff = alpha_cutoff; pl->built_on = S(stream);
+    pl->p = p; pl->k = k; pl->mode = mode; pl->format = format; pl->alpha_cutoff = alpha_cutoff; pl->built_on = S(stream);
 
     // per-centroid work on the host: (L,a,b,C) table, RGBA8 palette (lab_to_rgb.wgsl), threshold
     std::vector<Centroid> hc(k);
@@ -262,7 +284,8 @@ static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, 
     const bool diffuse = mode == KMG_MODE_DIFFUSE;
     const bool replace_table = diffuse ? diffuse_table_pays(p, n_px, k) : (mode != KMG_MODE_MELD && !dither && replace_table_pays(p, n_px, k));
     const bool dither_pruned = mode != KMG_MODE_MELD && !diffuse && dither && dither_pruning_pays(p, n_px, k);
-    const size_t tables_bytes = sizeof(Centroid) * k + sizeof(uint32_t) * (k + 1);
+    const bool ident = format != KMG_FORMAT_RGBA8 && dither_pruned && !dither_takes_lists(p, k);   // index output of kDitherMasks
+    const size_t tables_bytes = sizeof(Centroid) * k + sizeof(uint32_t) * (k + 1) * (ident ? 2u : 1u);
     const size_t sub_bytes = sizeof(uint16_t) * (kSubCells + kCells) + sizeof(uint32_t) * kCells;
     const size_t labels_bytes = (size_t)(k <= 256 ? 1 : 2) << 24;
     const size_t masks_bytes = sizeof(uint64_t) * (size_t)kCells * mask_words(k) * (dither_pruned ? 16u : 1u);
@@ -279,11 +302,16 @@ static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, 
     pl->staged.resize(tables_bytes);
     memcpy(pl->staged.data(), hc.data(), sizeof(Centroid) * k);
     memcpy(pl->staged.data() + sizeof(Centroid) * k, pal.data(), sizeof(uint32_t) * (k + 1));
+    if (ident) {
+        uint32_t *id = (uint32_t *)(pl->staged.data() + sizeof(Centroid) * k + sizeof(uint32_t) * (k + 1));
+        for (uint32_t i = 0; i <= k; ++i) id[i] = i;
+    }
     Centroid *d_cent = nullptr;
     if (e == hipSuccess) {
         d_cent = (Centroid *)arena.take(tables_bytes);
         pl->d_cent = d_cent;
         pl->d_pal = (uint32_t *)((uint8_t *)d_cent + sizeof(Centroid) * k);
+        if (ident) pl->d_ident = pl->d_pal + (k + 1);
         e = hipMemcpyAsync(d_cent, pl->staged.data(), pl->staged.size(), hipMemcpyHostToDevice, S(stream));
     }
     int rc = KMG_OK;
@@ -351,10 +379,18 @@ try {
 }
 KMG_ABI_CATCH
 
+extern "C" int kmg_apply_plan_create_format(kmg_processor *p, const float *c4, uint32_t k, int mode, int format, uint64_t n_pixels_hint,
+                                            void *stream, kmg_apply_plan **out)
+try {
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply_plan arguments");
+    return plan_create(p, c4, k, mode, n_pixels_hint, stream, p->alpha_cutoff.load(std::memory_order_relaxed), out, format);
+}
+KMG_ABI_CATCH
+
 // KMG_MODE_DIFFUSE: one band of the diffusion.  The bands of one plan are consecutive rows of one image (row0 = the rows done
 // so far, the width unchanged); each run waits on the previous run's completion event, so bands issued on several streams still
 // execute in order, and each continues from the error row the previous one left in the plan's scratch.
-static int run_diffuse(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, uint8_t *d_out, hipStream_t st)
+static int run_diffuse(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, void *d_out, hipStream_t st)
 {
     kmg_processor *p = pl->p;
     if (w > 0x7FFFFF00u) return fail(KMG_ERR_UNSUPPORTED, "diffusion needs a width below 2^31 - 256");
@@ -378,8 +414,8 @@ static int run_diffuse(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, ui
     HIP_TRY(hipMemsetAsync(ctl, 0, ctl_bytes, st));
     const bool table = pl->route == kmg_apply_plan::kDiffuseTable;
     const int route = !table ? kDiffuseScan : (pl->k <= 256 ? kDiffusePairs : kDiffuseCells);
-    hipError_t e = launch_diffuse(route, (const uint32_t *)d_rgba, w, rows, (uint32_t *)d_out, erow, pl->dparity, ctl, sticky, pl->d_cent,
-                                  pl->k, p->d_lut, pl->d_pal, pl->aux, pl->sub, st, pl->alpha_cutoff);
+    hipError_t e = launch_diffuse(route, (const uint32_t *)d_rgba, w, rows, d_out, erow, pl->dparity, ctl, sticky, pl->d_cent,
+                                  pl->k, p->d_lut, pl->d_pal, pl->aux, pl->sub, st, pl->alpha_cutoff, pl->format);
     if (e == hipSuccess) e = hipMemcpyAsync((void *)pl->h_timeout, sticky, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipEventRecord(pl->ddone, st);
     if (e != hipSuccess) return fail(KMG_ERR_HIP, "diffusion failed: %s", hipGetErrorString(e));
@@ -406,15 +442,57 @@ try {
 }
 KMG_ABI_CATCH
 
+// Index output (kmg_output_format INDEX8 / INDEX16) of the routes other than diffusion: the index instantiations of the scan and
+// list kernels and the label-table kernel of kmg_index.hip write the label directly; the mask-word dither route runs its
+// unchanged kernel with the identity palette into stream-ordered u32 scratch, then narrows it (k_narrow_index).
+static int run_index(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, void *d_out, hipStream_t st)
+{
+    kmg_processor *p = pl->p;
+    if (st != pl->built_on) HIP_TRY(hipStreamWaitEvent(st, pl->ready, 0));
+    const uint64_t n_px = (uint64_t)w * rows;
+    const uint32_t k = pl->k;
+    const bool wide = pl->format == KMG_FORMAT_INDEX16;
+    const uint32_t *src = (const uint32_t *)d_rgba;
+    hipError_t e = hipSuccess;
+    switch (pl->route) {
+    case kmg_apply_plan::kReplaceTable:
+        e = launch_labels_index(src, n_px, pl->aux, pl->sub, k, d_out, wide, st, pl->alpha_cutoff);
+        break;
+    case kmg_apply_plan::kDitherLists:
+        e = launch_dither_lists_index(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->thr, (const uint8_t *)pl->aux, d_out, wide, st,
+                                      pl->alpha_cutoff);
+        break;
+    case kmg_apply_plan::kDitherMasks: {
+        void *lab = nullptr;
+        HIP_TRY(pool_alloc(p, &lab, sizeof(uint32_t) * n_px, st));
+        e = launch_dither_pruned(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_ident, pl->thr, (const uint64_t *)pl->aux, (uint32_t *)lab, st);
+        if (e == hipSuccess) e = launch_narrow_index(src, (const uint32_t *)lab, n_px, k, d_out, wide, st, pl->alpha_cutoff);
+        const hipError_t e2 = hipFreeAsync(lab, st);
+        if (e == hipSuccess) e = e2;
+        break;
+    }
+    case kmg_apply_plan::kScan:
+        e = launch_apply_index(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->dither, pl->thr, d_out, wide, st, pl->alpha_cutoff);
+        break;
+    default:
+        return fail(KMG_ERR_INVALID_ARGUMENT, "the plan's route has no index output");
+    }
+    if (e != hipSuccess) return fail(KMG_ERR_HIP, "apply failed: %s", hipGetErrorString(e));
+    return KMG_OK;
+}
+
 extern "C" int kmg_apply_plan_run(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, uint8_t *d_out,
                                   void *stream)
 try {
     if (!pl || !d_rgba || !d_out || !w || !rows) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply_plan_run arguments");
     // the output kernels keep the pixel index (and from it the Bayer coordinates) in 32 bits
     if ((uint64_t)w * rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
+    if (pl->format == KMG_FORMAT_INDEX16 && (reinterpret_cast<uintptr_t>(d_out) & 1u))
+        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX16 output must be 2-byte aligned");
     kmg_processor *p = pl->p;
     HIP_TRY(hipSetDevice(p->device));
     if (pl->mode == KMG_MODE_DIFFUSE) return run_diffuse(pl, d_rgba, w, rows, row0, d_out, S(stream));
+    if (pl->format != KMG_FORMAT_RGBA8) return run_index(pl, d_rgba, w, rows, row0, d_out, S(stream));
     if (S(stream) != pl->built_on) HIP_TRY(hipStreamWaitEvent(S(stream), pl->ready, 0));      // (another stream: after the tables)
     const uint64_t n_px = (uint64_t)w * rows;
     const uint32_t k = pl->k;
@@ -467,13 +545,13 @@ try {
 KMG_ABI_CATCH_VOID
 
 int kmg::dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, const float *c4, uint32_t k, int mode,
-                   uint8_t *d_out, void *stream, uint32_t alpha_cutoff)
+                   uint8_t *d_out, void *stream, uint32_t alpha_cutoff, int format)
 {
     if (!p || !d_rgba || !d_out || !c4 || !w || !rows || k == 0)
         return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply arguments");
     if ((uint64_t)w * rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
     kmg_apply_plan *pl = nullptr;
-    int rc = plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, alpha_cutoff, &pl);
+    int rc = plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, alpha_cutoff, &pl, format);
     if (rc != KMG_OK) return rc;
     // (diffusion: the band is an image of its own -- the plan is new, so its first run starts from a zero error row)
     rc = kmg_apply_plan_run(pl, d_rgba, w, rows, mode == KMG_MODE_DIFFUSE ? 0u : row0, d_out, stream);
@@ -493,3 +571,10 @@ try {
 }
 KMG_ABI_CATCH
 
+extern "C" int kmg_dev_apply_format(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, const float *c4,
+                                    uint32_t k, int mode, int format, void *d_out, void *stream)
+try {
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply arguments");
+    return dev_apply(p, d_rgba, w, rows, row0, c4, k, mode, (uint8_t *)d_out, stream, p->alpha_cutoff.load(std::memory_order_relaxed), format);
+}
+KMG_ABI_CATCH

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "kmg_kernels.h"
 #include "kmg_math.h"
 
@@ -76,6 +78,52 @@ __device__ __forceinline__ void store4(uint32_t *out, uint64_t i0, uint64_t n, b
     }
 }
 
+// ---- output formats (kmg_output_format): the output kernels take the type of an output pixel as a template parameter --
+// uint32_t, the RGBA8 word (their instantiations with it are the code of the RGBA8 passes), or uint8_t / uint16_t, the label
+// itself.  An index kernel gets the alpha cutoff in bits 8..15 of its `aligned` argument (bit 0: aligned) where it has no
+// cutoff argument of its own, so that the RGBA8 instantiations keep their signatures.
+template <typename OutT>
+constexpr bool kIndexOut = !std::is_same<OutT, uint32_t>::value;
+
+// the index of a pixel: its label, or k (the transparent slot) when alpha mode drops it
+template <bool ALPHA>
+__device__ __forceinline__ uint32_t index_of(uint32_t label, uint32_t src, uint32_t cutoff, uint32_t k)
+{
+    return (ALPHA && (src >> 24) < cutoff) ? k : label;
+}
+
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// 4 consecutive indices: one dword (u8) or dwordx2 (u16) store when `aligned` (out + i0 then is 4- / 8-byte aligned), else one
+// store per pixel in range.  NT: non-temporal, as the streaming passes store their words.
+template <typename OutT, bool NT>
+__device__ __forceinline__ void store4_index(OutT *out, uint64_t i0, uint64_t n, bool aligned, const uint32_t v[4])
+{
+    static_assert(sizeof(OutT) == 1 || sizeof(OutT) == 2, "index formats are u8 and u16");
+    if (aligned && i0 + 4 <= n) {
+        if (sizeof(OutT) == 1) {
+            const uint32_t q = (v[0] & 255u) | ((v[1] & 255u) << 8) | ((v[2] & 255u) << 16) | (v[3] << 24);
+            uint32_t *d = reinterpret_cast<uint32_t *>(out + i0);
+            if (NT) __builtin_nontemporal_store(q, d); else *d = q;
+        } else {
+            const u32x2 q = {(v[0] & 0xFFFFu) | (v[1] << 16), (v[2] & 0xFFFFu) | (v[3] << 16)};
+            u32x2 *d = reinterpret_cast<u32x2 *>(out + i0);
+            if (NT) __builtin_nontemporal_store(q, d); else *d = q;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (i0 + j < n) out[i0 + j] = (OutT)v[j];
+    }
+}
+
+// what the launchers pass as `aligned` to an output kernel of format OutT: the source 16-byte aligned and the output aligned for
+// its vector store (RGBA8: 16 bytes; u8: 4; u16: 8)
+template <typename OutT>
+inline int output_aligned(const void *src, const void *out)
+{
+    return ((reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & (4u * sizeof(OutT) - 1u)) == 0) ? 1 : 0;
+}
 
 // Centroid table -> LDS as (L, a, b, C) float4, padded to a multiple of 4 with entries no pixel can
 // be closest to (key ~ 1e36, above every sentinel).

@@ -18,6 +18,7 @@
 // its rows and leaves, and every other wave leaves at its next poll.  Ticket, progress, heartbeat and timeout words live in the
 // caller's per-call control block (diffuse_ctl_bytes()), zeroed before every launch.  No grid barrier, no wait on a later ticket.
 
+#include "../../include/kmeans_hip.h"
 #include "kmg_device.h"
 #include "kmg_table.h"
 
@@ -151,10 +152,11 @@ __device__ bool wait_progress(DiffCtl *ctl, uint32_t *sticky, uint32_t t, uint32
 }
 
 // ALPHA (alpha mode, kmg_options.alpha_cutoff = cutoff): a pixel whose alpha byte is below the cutoff takes no part -- S = 0 (its
-// own colour unmodified), e = 0 -- and every output word keeps its pixel's alpha byte
-template <int ROUTE, bool ALPHA>
+// own colour unmodified), e = 0 -- and every output word keeps its pixel's alpha byte.
+// OutT (kmg_device.h): uint32_t writes the RGBA8 word, uint8_t / uint16_t the label (k for a pixel alpha mode drops)
+template <int ROUTE, bool ALPHA, typename OutT>
 __global__ __launch_bounds__(64) void k_diffuse(const uint32_t *__restrict__ rgba, uint32_t w, uint32_t rows,
-                                                uint32_t *__restrict__ out, uint2 *__restrict__ erow, uint32_t parity,
+                                                OutT *__restrict__ out, uint2 *__restrict__ erow, uint32_t parity,
                                                 DiffCtl *__restrict__ ctl, uint32_t *__restrict__ sticky, const Centroid *__restrict__ cent, uint32_t k,
                                                 const float *__restrict__ lut, const uint32_t *__restrict__ pal,
                                                 const void *__restrict__ colour_labels, const uint16_t *__restrict__ sub_table,
@@ -262,14 +264,15 @@ __global__ __launch_bounds__(64) void k_diffuse(const uint32_t *__restrict__ rgb
 #pragma unroll
                 for (int c = 0; c < 3; ++c) { e[c] = keep ? tq[c] - 16 * (int)((o >> (8 * c)) & 255u) : 0; eL[c] = e[c]; }
                 eo = act ? pack_err(e[0], e[1], e[2]) : make_uint2(0u, 0u);
-                ob[j] = with_alpha<ALPHA>(o, src);
+                if constexpr (kIndexOut<OutT>) ob[j] = index_of<ALPHA>(act && lbl < k ? lbl : 0u, src, cutoff, k);
+                else ob[j] = with_alpha<ALPHA>(o, src);
                 eb[j] = eo;
             }
 #pragma unroll
             for (int j = 0; j < kBody; ++j) {
                 const int x = xb + j;
                 if (row_ok && x >= 0 && x < (int)w) {
-                    out[row_base + (uint32_t)x] = ob[j];
+                    out[row_base + (uint32_t)x] = (OutT)ob[j];
                     if (lane == nr - 1u) e_out[x] = eb[j];
                 }
             }
@@ -288,7 +291,7 @@ __global__ __launch_bounds__(64) void k_diffuse(const uint32_t *__restrict__ rgb
         if (abandoned) {
             // the pass failed (the host reports it): no row of this chunk keeps a half-diffused value
             for (uint32_t r = 0; r < nr; ++r)
-                for (uint32_t x = lane; x < w; x += 64) out[(uint64_t)(y0 + r) * w + x] = 0u;
+                for (uint32_t x = lane; x < w; x += 64) out[(uint64_t)(y0 + r) * w + x] = (OutT)0u;
             return;
         }
     }
@@ -309,13 +312,14 @@ uint32_t diffuse_grid(int route, uint32_t rows)
     return g ? g : 1u;
 }
 
-hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t *out, void *erow, uint32_t parity,
-                          void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff)
+template <typename OutT>
+static void launch_diffuse_t(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, OutT *out, void *erow, uint32_t parity,
+                             void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
+                             const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff)
 {
     const uint32_t grid = diffuse_grid(route, rows);
-#define KMG_DIFFUSE_A(R, A)                                                                                                     \
-    hipLaunchKernelGGL((k_diffuse<R, A>), dim3(grid), dim3(64), 0, st, rgba, w, rows, out, (uint2 *)erow, parity, (DiffCtl *)ctl,  \
+#define KMG_DIFFUSE_A(R, A)                                                                                                          \
+    hipLaunchKernelGGL((k_diffuse<R, A, OutT>), dim3(grid), dim3(64), 0, st, rgba, w, rows, out, (uint2 *)erow, parity, (DiffCtl *)ctl,  \
                        sticky, cent, k, lut, pal, colour_labels, sub_table, alpha_cutoff)
 #define KMG_DIFFUSE(R) do { if (alpha_cutoff) KMG_DIFFUSE_A(R, true); else KMG_DIFFUSE_A(R, false); } while (0)
     if (route == kDiffusePairs) KMG_DIFFUSE(kDiffusePairs);
@@ -323,6 +327,18 @@ hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t 
     else KMG_DIFFUSE(kDiffuseScan);
 #undef KMG_DIFFUSE
 #undef KMG_DIFFUSE_A
+}
+
+hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out, void *erow, uint32_t parity,
+                          void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
+                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff, int format)
+{
+    if (format == KMG_FORMAT_INDEX8)
+        launch_diffuse_t(route, rgba, w, rows, (uint8_t *)out, erow, parity, ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, st, alpha_cutoff);
+    else if (format == KMG_FORMAT_INDEX16)
+        launch_diffuse_t(route, rgba, w, rows, (uint16_t *)out, erow, parity, ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, st, alpha_cutoff);
+    else
+        launch_diffuse_t(route, rgba, w, rows, (uint32_t *)out, erow, parity, ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, st, alpha_cutoff);
     return hipGetLastError();
 }
 

@@ -51,7 +51,9 @@ std::vector<std::array<uint8_t, 4>> octree_sorted_palette(const uint8_t *host_rg
 
 // kmg_dev_apply with the alpha cutoff given (kmg_apply.hip): the host-buffer calls read the processor's once per call
 int dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, const float *centroids4, uint32_t k,
-              int mode, uint8_t *d_out, void *stream, uint32_t alpha_cutoff);
+              int mode, uint8_t *d_out, void *stream, uint32_t alpha_cutoff, int format = KMG_FORMAT_RGBA8);
+// the box of the index formats (include/kmeans_hip.h at kmg_output_format)
+constexpr float kIndexBoxLmin = -100.0f, kIndexBoxLmax = 200.0f, kIndexBoxAB = 300.0f;
 
 // An image between a caller's (pageable) buffer and the device, ordered on `st` (kmg_api.hip): small images asynchronously,
 // large ones as synchronous row-range copies on several streams of the processor.

@@ -130,8 +130,26 @@ enum { kDiffuseScan = 0, kDiffusePairs = 1, kDiffuseCells = 2 };
 constexpr uint32_t kDiffuseRing = 1024;
 size_t diffuse_ctl_bytes();
 uint32_t diffuse_grid(int route, uint32_t rows);
-hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t *out, void *erow, uint32_t parity,
+// format (kmg_output_format): out holds RGBA8 words (0), or the labels as u8 (1) / u16 (2) -- k for a pixel alpha mode drops
+hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out, void *erow, uint32_t parity,
                           void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff = 0);
+                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff = 0,
+                          int format = 0);
+
+// ---- index output (kmg_output_format INDEX8 / INDEX16): the label of every pixel as u8 (wide = false) or u16 (wide = true);
+// alpha_cutoff != 0: k where the pixel's alpha is below it.  The same decisions as the RGBA8 launchers above.
+hipError_t launch_apply_index(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
+                              const float *lut, bool dither, float threshold, void *out, bool wide, hipStream_t st, uint32_t alpha_cutoff);
+hipError_t launch_dither_lists_index(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
+                                     const float *lut, float threshold, const uint8_t *lists, void *out, bool wide, hipStream_t st,
+                                     uint32_t alpha_cutoff);
+// kmg_index.hip: the replace pass through the colour cube's label tables (those launch_labels reads: the pair entries and u8
+// per-colour labels for k <= 256, the 8x8x8 / 4x4x4 summaries and u16 per-colour labels above)
+hipError_t launch_labels_index(const uint32_t *rgba, uint64_t n, const void *colour_labels, const uint16_t *sub_table, uint32_t k,
+                               void *out, bool wide, hipStream_t st, uint32_t alpha_cutoff);
+// kmg_index.hip: out[i] = labels[i] (u32 labels of a pass that ran with an identity palette) as u8 / u16, or k where alpha mode drops
+// the pixel
+hipError_t launch_narrow_index(const uint32_t *rgba, const uint32_t *labels, uint64_t n, uint32_t k, void *out, bool wide, hipStream_t st,
+                               uint32_t alpha_cutoff);
 
 }  // namespace kmg

@@ -1072,13 +1072,15 @@ hipError_t launch_resize_band(const uint32_t *band, uint32_t w, uint32_t h, uint
 // ------------------------------------------------------------------------------------------
 __constant__ const float c_bayer[16] = {0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5};
 
-template <int PPT, bool DITHER, bool CHUNKED, bool ALPHA>
+// OutT (kmg_device.h): uint32_t writes pal[label] (RGBA8), uint8_t / uint16_t the index (the alpha cutoff in bits 8..15 of
+// `aligned`)
+template <int PPT, bool DITHER, bool CHUNKED, bool ALPHA, typename OutT>
 __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ rgba, uint32_t w,
                                                   uint64_t n, uint32_t row0,
                                                   const Centroid *__restrict__ cent, uint32_t k,
                                                   const float *__restrict__ lut,
                                                   const uint32_t *__restrict__ pal, float threshold,
-                                                  uint32_t *__restrict__ out, int aligned)
+                                                  OutT *__restrict__ out, int aligned)
 {
     extern __shared__ float4 smem4[];
     const uint32_t kpad = (k + 3u) & ~3u;
@@ -1108,7 +1110,7 @@ __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ r
         for (int g = 0; g < GROUPS; ++g) {
             i0[g] = tile * TILE + (uint64_t)g * (kBlock * 4) + (uint64_t)threadIdx.x * 4;
             uint32_t px[4];
-            load4(rgba, i0[g], n, aligned != 0, px);
+            load4(rgba, i0[g], n, kIndexOut<OutT> ? (aligned & 1) != 0 : aligned != 0, px);
             if (ALPHA) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) src_a[g * 4 + q] = px[q];
@@ -1148,9 +1150,15 @@ __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ r
 #pragma unroll
         for (int g = 0; g < GROUPS; ++g) {
             uint32_t o[4];
+            if constexpr (kIndexOut<OutT>) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = with_alpha<ALPHA>(pal[idx[g * 4 + q]], src_a[ALPHA ? g * 4 + q : 0]);
-            store4(out, i0[g], n, aligned != 0, o);
+                for (int q = 0; q < 4; ++q) o[q] = index_of<ALPHA>(idx[g * 4 + q], src_a[ALPHA ? g * 4 + q : 0], ((uint32_t)aligned >> 8) & 255u, k);
+                store4_index<OutT, false>(out, i0[g], n, (aligned & 1) != 0, o);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) o[q] = with_alpha<ALPHA>(pal[idx[g * 4 + q]], src_a[ALPHA ? g * 4 + q : 0]);
+                store4(out, i0[g], n, aligned != 0, o);
+            }
         }
     }
 }
@@ -1167,8 +1175,8 @@ hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_
                          (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
     const bool chunked = k >= 32;
     const size_t lds = sizeof(float4) * kpad + (256 + 16) * sizeof(float);
-#define KMG_APPLY(D, C, A)                                                                            \
-    hipLaunchKernelGGL((k_apply<kAssignPPT, D, C, A>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, \
+#define KMG_APPLY(D, C, A)                                                                                      \
+    hipLaunchKernelGGL((k_apply<kAssignPPT, D, C, A, uint32_t>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, \
                        row0, cent, k, lut, pal, threshold, out, aligned)
     if (alpha) {
         if (dither) { if (chunked) KMG_APPLY(true, true, true); else KMG_APPLY(true, false, true); }
@@ -1178,6 +1186,38 @@ hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_
         else        { if (chunked) KMG_APPLY(false, true, false); else KMG_APPLY(false, false, false); }
     }
 #undef KMG_APPLY
+    return hipGetLastError();
+}
+
+template <typename OutT>
+static void launch_apply_index_t(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
+                                 const float *lut, bool dither, float threshold, OutT *out, hipStream_t st, uint32_t alpha_cutoff)
+{
+    const uint64_t n = (uint64_t)w * rows;
+    const uint64_t tiles = (n + (uint64_t)kBlock * kAssignPPT - 1) / ((uint64_t)kBlock * kAssignPPT);
+    const uint32_t grid = (uint32_t)(tiles < 2048 ? (tiles ? tiles : 1) : 2048);
+    const uint32_t kpad = (k + 3u) & ~3u;
+    const int flags = output_aligned<OutT>(rgba, out) | (int)((alpha_cutoff & 255u) << 8);
+    const bool chunked = k >= 32;
+    const size_t lds = sizeof(float4) * kpad + (256 + 16) * sizeof(float);
+#define KMG_APPLY(D, C, A)                                                                                  \
+    hipLaunchKernelGGL((k_apply<kAssignPPT, D, C, A, OutT>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, \
+                       row0, cent, k, lut, nullptr, threshold, out, flags)
+    if (alpha_cutoff) {
+        if (dither) { if (chunked) KMG_APPLY(true, true, true); else KMG_APPLY(true, false, true); }
+        else        { if (chunked) KMG_APPLY(false, true, true); else KMG_APPLY(false, false, true); }
+    } else {
+        if (dither) { if (chunked) KMG_APPLY(true, true, false); else KMG_APPLY(true, false, false); }
+        else        { if (chunked) KMG_APPLY(false, true, false); else KMG_APPLY(false, false, false); }
+    }
+#undef KMG_APPLY
+}
+
+hipError_t launch_apply_index(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
+                              const float *lut, bool dither, float threshold, void *out, bool wide, hipStream_t st, uint32_t alpha_cutoff)
+{
+    if (wide) launch_apply_index_t(rgba, w, rows, row0, cent, k, lut, dither, threshold, (uint16_t *)out, st, alpha_cutoff);
+    else launch_apply_index_t(rgba, w, rows, row0, cent, k, lut, dither, threshold, (uint8_t *)out, st, alpha_cutoff);
     return hipGetLastError();
 }
 

@@ -297,12 +297,14 @@ __device__ __forceinline__ void walk_list(const uint8_t *__restrict__ lists, uin
     }
 }
 
-template <int HALVES, bool ALPHA>
+// OutT (kmg_device.h): uint32_t writes pal[label] (RGBA8), uint8_t / uint16_t the index (the alpha cutoff in bits 8..15 of
+// `aligned`)
+template <int HALVES, bool ALPHA, typename OutT>
 __global__ __launch_bounds__(kBlock) void k_dither_lists(const uint32_t *__restrict__ rgba, uint32_t w, uint64_t n,
                                                          uint32_t row0, const Centroid *__restrict__ cent, uint32_t k,
                                                          const float *__restrict__ lut, const uint32_t *__restrict__ pal,
                                                          float threshold, const uint8_t *__restrict__ lists,
-                                                         uint32_t *__restrict__ out, int aligned)
+                                                         OutT *__restrict__ out, int aligned)
 {
     extern __shared__ float4 smem4[];
     constexpr uint32_t kpad = 256u * HALVES;                       // every (half, byte) indexes the table: entries k .. are far away
@@ -328,7 +330,7 @@ __global__ __launch_bounds__(kBlock) void k_dither_lists(const uint32_t *__restr
     for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const uint64_t i0 = tile * TILE + (uint64_t)threadIdx.x * 4;
         uint32_t px[4];
-        load4_stream(rgba, i0, n, aligned != 0, px);
+        load4_stream(rgba, i0, n, kIndexOut<OutT> ? (aligned & 1) != 0 : aligned != 0, px);
         const uint32_t i32 = (uint32_t)i0;                          // n < 2^32
         uint32_t gy = i32 / w, gx = i32 - gy * w;
         gy += row0;
@@ -399,9 +401,11 @@ __global__ __launch_bounds__(kBlock) void k_dither_lists(const uint32_t *__restr
                     idx = li;
                 }
             }
-            res[q] = with_alpha<ALPHA>(pal[idx], px[q]);
+            if constexpr (kIndexOut<OutT>) res[q] = index_of<ALPHA>(idx, px[q], ((uint32_t)aligned >> 8) & 255u, k);
+            else res[q] = with_alpha<ALPHA>(pal[idx], px[q]);
         }
-        store4_stream(out, i0, n, aligned != 0, res);
+        if constexpr (kIndexOut<OutT>) store4_index<OutT, true>(out, i0, n, (aligned & 1) != 0, res);
+        else store4_stream(out, i0, n, aligned != 0, res);
     }
 }
 
@@ -429,11 +433,39 @@ hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, 
     const uint32_t halves = k > 256u ? 2u : 1u;
     const size_t lds = sizeof(float4) * 256 * halves + (256 + 16) * sizeof(float);
     const int aligned = ((reinterpret_cast<uintptr_t>(rgba) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
-#define KMG_DL(H, A) hipLaunchKernelGGL((k_dither_lists<H, A>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut, pal, \
-                                        threshold, lists, out, aligned)
+#define KMG_DL(H, A) hipLaunchKernelGGL((k_dither_lists<H, A, uint32_t>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut, \
+                                        pal, threshold, lists, out, aligned)
     if (halves == 2u) { if (alpha) KMG_DL(2, true); else KMG_DL(2, false); }
     else { if (alpha) KMG_DL(1, true); else KMG_DL(1, false); }
 #undef KMG_DL
+    return hipGetLastError();
+}
+
+template <typename OutT>
+static void launch_dither_lists_index_t(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
+                                        const float *lut, float threshold, const uint8_t *lists, OutT *out, hipStream_t st,
+                                        uint32_t alpha_cutoff)
+{
+    const uint64_t n = (uint64_t)w * rows;
+    const uint64_t tiles = (n + kBlock * 4 - 1) / (kBlock * 4);
+    const uint32_t grid = (uint32_t)(tiles < 8192 ? (tiles ? tiles : 1) : 8192);
+    const uint32_t halves = k > 256u ? 2u : 1u;
+    const size_t lds = sizeof(float4) * 256 * halves + (256 + 16) * sizeof(float);
+    const int flags = output_aligned<OutT>(rgba, out) | (int)((alpha_cutoff & 255u) << 8);
+#define KMG_DL(H, A) hipLaunchKernelGGL((k_dither_lists<H, A, OutT>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut, \
+                                        nullptr, threshold, lists, out, flags)
+    if (halves == 2u) { if (alpha_cutoff) KMG_DL(2, true); else KMG_DL(2, false); }
+    else { if (alpha_cutoff) KMG_DL(1, true); else KMG_DL(1, false); }
+#undef KMG_DL
+}
+
+hipError_t launch_dither_lists_index(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
+                                     const float *lut, float threshold, const uint8_t *lists, void *out, bool wide, hipStream_t st,
+                                     uint32_t alpha_cutoff)
+{
+    if (k > kLabListMaxK) return hipErrorInvalidValue;
+    if (wide) launch_dither_lists_index_t(rgba, w, rows, row0, cent, k, lut, threshold, lists, (uint16_t *)out, st, alpha_cutoff);
+    else launch_dither_lists_index_t(rgba, w, rows, row0, cent, k, lut, threshold, lists, (uint8_t *)out, st, alpha_cutoff);
     return hipGetLastError();
 }
 

@@ -130,6 +130,38 @@ public:
         return out;
     }
 
+    // palette-index output (include/kmeans_hip.h kmg_output_format; single-device processors only): one index per pixel, u8 when
+    // the colours -- and the transparent slot of alpha mode -- fit a byte, else u16
+    struct Indexed {
+        std::pair<uint32_t, uint32_t> dims;
+        int format = KMG_FORMAT_INDEX8;
+        std::vector<uint8_t> index8;              // KMG_FORMAT_INDEX8
+        std::vector<uint16_t> index16;            // KMG_FORMAT_INDEX16
+        std::vector<RGBA8> palette;               // reduce_indexed: the colour of every index, in index order
+        uint32_t at(uint32_t x, uint32_t y) const
+        {
+            const size_t i = (size_t)x + (size_t)y * dims.first;
+            return format == KMG_FORMAT_INDEX8 ? index8[i] : index16[i];
+        }
+    };
+    Indexed find_indexed(const Image &image, const std::vector<RGBA8> &colors, ReduceMode reduce_mode, bool alpha_mode = false) const
+    {
+        Indexed out = indexed_for(image, (uint32_t)colors.size(), alpha_mode);
+        check(kmg_find_indexed(single(), bytes(image), image.dims.first, image.dims.second, reinterpret_cast<const uint8_t *>(colors.data()),
+                               (uint32_t)colors.size(), (int)reduce_mode, out.format, index_data(out)));
+        return out;
+    }
+    Indexed reduce_indexed(uint32_t color_count, const Image &image, Algorithm algo, ReduceMode reduce_mode, bool alpha_mode = false) const
+    {
+        Indexed out = indexed_for(image, color_count, alpha_mode);
+        out.palette.resize(color_count ? color_count : 1);
+        uint32_t n = 0;
+        check(kmg_reduce_indexed(single(), bytes(image), image.dims.first, image.dims.second, color_count, (int)algo, (int)reduce_mode,
+                                 out.format, reinterpret_cast<uint8_t *>(out.palette.data()), &n, index_data(out)));
+        out.palette.resize(n);
+        return out;
+    }
+
     // a batch: whole images per device (a single-device processor takes them one after the other)
     std::vector<Image> reduce_batch(uint32_t color_count, const std::vector<Image> &images, Algorithm algo, ReduceMode reduce_mode) const
     {
@@ -175,6 +207,24 @@ private:
         g_ = nullptr; p_ = nullptr;
     }
     static const uint8_t *bytes(const Image &im) { return reinterpret_cast<const uint8_t *>(im.rgba.data()); }
+    kmg_processor *single() const
+    {
+        if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "index output needs a single-device processor");
+        return p_;
+    }
+    static Indexed indexed_for(const Image &image, uint32_t k, bool alpha_mode)
+    {
+        Indexed out;
+        out.dims = image.dims;
+        out.format = k + (alpha_mode ? 1u : 0u) <= 256u ? KMG_FORMAT_INDEX8 : KMG_FORMAT_INDEX16;
+        if (out.format == KMG_FORMAT_INDEX8) out.index8.resize(image.rgba.size());
+        else out.index16.resize(image.rgba.size());
+        return out;
+    }
+    static void *index_data(Indexed &o)
+    {
+        return o.format == KMG_FORMAT_INDEX8 ? static_cast<void *>(o.index8.data()) : static_cast<void *>(o.index16.data());
+    }
     static void check(int rc)
     {
         if (rc != KMG_OK) throw Error(rc, kmg_last_error());

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -60,6 +60,12 @@ class ReduceMode(enum.IntEnum):         # core/src/lib.rs:234-239, plus Diffuse 
     Dither = 1
     Meld = 2
     Diffuse = 3                         # Floyd-Steinberg error diffusion (not in the reference; no Group support)
+
+
+class OutputFormat(enum.IntEnum):       # include/kmeans_hip.h kmg_output_format
+    RGBA8 = 0
+    Index8 = 1                          # one uint8 palette index per pixel
+    Index16 = 2                         # one uint16 palette index per pixel
 
 
 class Options(C.Structure):             # include/kmeans_hip.h kmg_options
@@ -139,6 +145,7 @@ SYMBOLS = [
     "kmg_lloyd_profile", "kmg_lloyd_profile_read",
     "kmg_lloyd_update", "kmg_lloyd_assign_update", "kmg_lloyd_set_cell_share", "kmg_lloyd_labels_from_tables",
     "kmg_lloyd_table_buffers", "kmg_lloyd_accumulate_into", "kmg_lloyd_labels_from_tables_update", "kmg_lloyd_histogram_buffer", "kmg_lloyd_rebuild_from_histogram", "kmg_debug_block_counts", "kmg_debug_idle_blocks", "kmg_debug_encode_table_check", "kmg_debug_division_check", "kmg_lloyd_converged_count", "kmg_lloyd_iterate", "kmg_lloyd_flush", "kmg_lloyd_run", "kmg_dev_apply", "kmg_apply_plan_create", "kmg_apply_plan_run", "kmg_apply_plan_destroy", "kmg_apply_plan_status",
+    "kmg_find_indexed", "kmg_reduce_indexed", "kmg_apply_plan_create_format", "kmg_dev_apply_format",
     "kmg_dither_threshold",
     "kmg_default_group_options", "kmg_group_create", "kmg_group_unique_id", "kmg_group_create_rank", "kmg_group_destroy",
     "kmg_group_info", "kmg_group_processor", "kmg_group_stream", "kmg_group_palette", "kmg_group_find", "kmg_group_reduce",
@@ -238,6 +245,10 @@ def lib():
     L.kmg_dev_apply.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32, C.c_int, u8p, vp]
     L.kmg_apply_plan_create.argtypes = [vp, f32p, C.c_uint32, C.c_int, C.c_uint64, vp, C.POINTER(vp)]
     L.kmg_apply_plan_run.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp]
+    L.kmg_find_indexed.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, u8p, C.c_uint32, C.c_int, C.c_int, vp]
+    L.kmg_reduce_indexed.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, u8p, C.POINTER(C.c_uint32), vp]
+    L.kmg_apply_plan_create_format.argtypes = [vp, f32p, C.c_uint32, C.c_int, C.c_int, C.c_uint64, vp, C.POINTER(vp)]
+    L.kmg_dev_apply_format.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32, C.c_int, C.c_int, vp, vp]
     L.kmg_apply_plan_destroy.argtypes = [vp, C.c_int]
     L.kmg_apply_plan_destroy.restype = None
     L.kmg_apply_plan_status.argtypes = [vp]
@@ -470,6 +481,36 @@ class ImageProcessor:
         _check(lib().kmg_reduce(self._h, _np_ptr(img), w, h, int(color_count), int(algo), int(reduce_mode), _np_ptr(out)))
         return out
 
+    # ---- palette-index output (include/kmeans_hip.h kmg_output_format) ----------------------
+    def _index_format(self, k):
+        """INDEX8 when the k labels (and, in alpha mode, the transparent slot k) fit a byte, else INDEX16"""
+        return OutputFormat.Index8 if k + (1 if self.options.alpha_cutoff else 0) <= 256 else OutputFormat.Index16
+
+    def find_indexed(self, image, colors, reduce_mode=ReduceMode.Replace):
+        """kmg_find_indexed: (height, width) palette indices into `colors` -- uint8, or uint16 when they do not fit a byte
+        (alpha mode: index len(colors) marks a pixel below the cutoff)"""
+        img = _image(image)
+        h, w = img.shape[:2]
+        pal = np.ascontiguousarray(colors, np.uint8).reshape(-1, 4)
+        fmt = self._index_format(pal.shape[0])
+        out = np.empty((h, w), np.uint8 if fmt == OutputFormat.Index8 else np.uint16)
+        _check(lib().kmg_find_indexed(self._h, _np_ptr(img), w, h, _np_ptr(pal), pal.shape[0], int(reduce_mode), int(fmt),
+                                      out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def reduce_indexed(self, color_count, image, algo=Algorithm.Kmeans, reduce_mode=ReduceMode.Replace):
+        """kmg_reduce_indexed: (palette (n, 4) uint8 in index order, (height, width) indices) -- palette[index] is what reduce
+        writes for the pixel (its alpha aside in alpha mode, where index n marks a pixel below the cutoff)"""
+        img = _image(image)
+        h, w = img.shape[:2]
+        fmt = self._index_format(int(color_count))
+        out = np.empty((h, w), np.uint8 if fmt == OutputFormat.Index8 else np.uint16)
+        pal = np.empty((max(int(color_count), 1), 4), np.uint8)
+        cnt = C.c_uint32()
+        _check(lib().kmg_reduce_indexed(self._h, _np_ptr(img), w, h, int(color_count), int(algo), int(reduce_mode), int(fmt), _np_ptr(pal),
+                                        C.byref(cnt), out.ctypes.data_as(C.c_void_p)))
+        return pal[:cnt.value].copy(), out
+
     # ---- device-pointer helpers (torch tensors supply the memory) -------------------------
     def rgb_to_lab(self, d_rgba, n_pixels, d_lab3, stream=0):
         _check(lib().kmg_dev_rgb_to_lab(self._h, C.c_void_p(d_rgba), n_pixels, C.c_void_p(d_lab3), C.c_void_p(stream)))
@@ -483,14 +524,20 @@ class ImageProcessor:
         _check(lib().kmg_dev_alpha_compact(self._h, C.c_void_p(d_rgba), int(n_pixels), int(cutoff), C.c_void_p(d_out),
                                            C.c_void_p(d_n_kept), C.c_void_p(stream)))
 
-    def apply(self, d_rgba, width, rows, row0, centroids4, mode, d_out, stream=0):
+    def apply(self, d_rgba, width, rows, row0, centroids4, mode, d_out, stream=0, format=None):
+        """format=None: kmg_dev_apply (RGBA8); an OutputFormat: kmg_dev_apply_format (d_out then holds 4, 1 or 2 bytes per pixel)"""
         c = np.ascontiguousarray(centroids4, np.float32).reshape(-1, 4)
-        _check(lib().kmg_dev_apply(self._h, C.c_void_p(d_rgba), width, rows, row0, _np_ptr(c), c.shape[0],
-                                   int(mode), C.c_void_p(d_out), C.c_void_p(stream)))
+        if format is None:
+            _check(lib().kmg_dev_apply(self._h, C.c_void_p(d_rgba), width, rows, row0, _np_ptr(c), c.shape[0],
+                                       int(mode), C.c_void_p(d_out), C.c_void_p(stream)))
+        else:
+            _check(lib().kmg_dev_apply_format(self._h, C.c_void_p(d_rgba), width, rows, row0, _np_ptr(c), c.shape[0],
+                                              int(mode), int(format), C.c_void_p(d_out), C.c_void_p(stream)))
 
-    def apply_plan(self, centroids4, mode, n_pixels_hint, stream=0):
-        """the output pass as a plan (kmg_apply_plan_*): tables built once, then `run` per row band, asynchronously"""
-        return ApplyPlan(self, centroids4, mode, n_pixels_hint, stream)
+    def apply_plan(self, centroids4, mode, n_pixels_hint, stream=0, format=None):
+        """the output pass as a plan (kmg_apply_plan_*): tables built once, then `run` per row band, asynchronously.  format: as
+        for apply()"""
+        return ApplyPlan(self, centroids4, mode, n_pixels_hint, stream, format)
 
     def debug_block_counts(self):
         """(device blocks allocated with hipMalloc so far, blocks handed out again)"""
@@ -534,11 +581,15 @@ class ImageProcessor:
 class ApplyPlan:
     """kmg_apply_plan_*: the output pass for one centroid table, band by band, without host synchronisation"""
 
-    def __init__(self, processor, centroids4, mode, n_pixels_hint, stream=0):
+    def __init__(self, processor, centroids4, mode, n_pixels_hint, stream=0, format=None):
         c = np.ascontiguousarray(centroids4, np.float32).reshape(-1, 4)
         self._h = C.c_void_p()
-        _check(lib().kmg_apply_plan_create(processor.handle, _np_ptr(c), c.shape[0], int(mode), int(n_pixels_hint), C.c_void_p(stream),
-                                           C.byref(self._h)))
+        if format is None:
+            _check(lib().kmg_apply_plan_create(processor.handle, _np_ptr(c), c.shape[0], int(mode), int(n_pixels_hint), C.c_void_p(stream),
+                                               C.byref(self._h)))
+        else:
+            _check(lib().kmg_apply_plan_create_format(processor.handle, _np_ptr(c), c.shape[0], int(mode), int(format), int(n_pixels_hint),
+                                                      C.c_void_p(stream), C.byref(self._h)))
 
     def run(self, d_rgba, width, rows, row0, d_out, stream=0):
         _check(lib().kmg_apply_plan_run(self._h, C.c_void_p(d_rgba), width, rows, row0, C.c_void_p(d_out), C.c_void_p(stream)))

@@ -8,6 +8,10 @@
 Every sub-command also takes `--alpha-cutoff N` (0..255, default 0 = alpha ignored, as in the reference): with N >= 1 only the
 pixels whose alpha is at least N shape the palette, and the output keeps the input's alpha (include/kmeans_hip.h, kmg_options).
 
+`reduce` and `find` also take `--indexed`: the output is a palette-mode PNG (one index per pixel, PLTE = the palette; at most 256
+colours) instead of RGBA.  In alpha mode the pixels below the cutoff take one more, fully transparent entry (tRNS 0), so
+255 colours at most.
+
 Image decoding/encoding (the `image` crate in the reference) is done with Pillow.  One flag the reference does not have:
 `--devices 0,1,...` (before the sub-command) runs the same operation over several GPUs of the node (kmg_group_*: the image
 tiled in row bands, same bytes).
@@ -74,6 +78,24 @@ def _load(path):
 def _save(path, rgba):
     from PIL import Image
     Image.fromarray(rgba, "RGBA").save(path)
+
+
+def save_indexed(path, palette, index, transparent=False):
+    """A palette-mode PNG: `index` (height, width) into `palette` (n, 4); transparent: index n is a fully transparent slot (PLTE
+    entry n black, tRNS 0 for it and 255 for the colours)"""
+    from PIL import Image
+    pal = np.ascontiguousarray(palette, np.uint8).reshape(-1, 4)[:, :3]
+    n = pal.shape[0] + (1 if transparent else 0)
+    if n > 256:
+        raise ValueError(f"a palette PNG holds 256 entries, {n} needed")
+    img = Image.fromarray(np.ascontiguousarray(index, np.uint8), "P")
+    plte = np.zeros((n, 3), np.uint8)
+    plte[:pal.shape[0]] = pal
+    img.putpalette(plte.reshape(-1).tolist(), rawmode="RGB")
+    if transparent:
+        img.save(path, transparency=bytes([255] * pal.shape[0] + [0]))
+    else:
+        img.save(path)
 
 
 def reduce_file_path(k, algo, mode, output, inp):        # main.rs:127-153
@@ -153,9 +175,27 @@ def main(argv=None):
     for s in (p, f, r):
         s.add_argument("--alpha-cutoff", type=validate_alpha_cutoff, default=0,
                        help="1..255: pixels with a lower alpha do not shape the palette, the output keeps the input's alpha")
+    for s in (f, r):
+        s.add_argument("--indexed", action="store_true",
+                       help="write a palette-mode PNG (an index per pixel) instead of RGBA; at most 256 colours, 255 with --alpha-cutoff")
     args = ap.parse_args(argv)
     if args.devices and args.alpha_cutoff:
         ap.error("--alpha-cutoff is not supported with --devices")
+    indexed = getattr(args, "indexed", False)
+    if indexed:
+        n = args.colorcount if args.command == "reduce" else args.palette.shape[0]
+        limit = 255 if args.alpha_cutoff else 256
+        if args.devices:
+            ap.error("--indexed is not supported with --devices")
+        if args.mode == "meld":
+            ap.error("--indexed has no meld mode: meld blends two colours, so a pixel has no palette index")
+        if n > limit:
+            ap.error(f"--indexed writes a palette PNG of at most {limit} colours{' (plus the transparent slot)' if args.alpha_cutoff else ''}; "
+                     f"{n} requested")
+        out_path = (reduce_file_path(args.colorcount, args.algo, args.mode, args.output, args.input) if args.command == "reduce"
+                    else find_file_path(args.mode, args.output, args.input))
+        if not out_path.endswith(".png"):
+            ap.error("--indexed writes a PNG file")
 
     image = _load(args.input)
     if args.devices:
@@ -168,6 +208,12 @@ def main(argv=None):
             out = np.repeat(np.repeat(colors[None, :, :], args.size, axis=0), args.size, axis=1)   # main.rs:221-239
             _save(palette_file_path(args.colorcount, args.input, args.output, args.algo, args.size), out)
             print("Palette: " + ",".join(f"#{c[0]:02X}{c[1]:02X}{c[2]:02X}" for c in colors))
+        elif indexed and args.command == "find":
+            index = proc.find_indexed(image, args.palette, _MODES[args.mode])
+            save_indexed(out_path, args.palette, index, transparent=bool(args.alpha_cutoff))
+        elif indexed:
+            colors, index = proc.reduce_indexed(args.colorcount, image, _ALGOS[args.algo], _MODES[args.mode])
+            save_indexed(out_path, colors, index, transparent=bool(args.alpha_cutoff))
         elif args.command == "find":                     # main.rs:74-98
             out = proc.find(image, args.palette, _MODES[args.mode])
             _save(find_file_path(args.mode, args.output, args.input), out)

@@ -58,6 +58,10 @@ pub const KMG_MODE_REPLACE: c_int = 0;
 pub const KMG_MODE_DITHER: c_int = 1;
 pub const KMG_MODE_MELD: c_int = 2;
 pub const KMG_MODE_DIFFUSE: c_int = 3;
+/// `kmg_output_format`: RGBA8, or one u8 / u16 palette index per pixel (`kmg_find_indexed`, `kmg_reduce_indexed`).
+pub const KMG_FORMAT_RGBA8: c_int = 0;
+pub const KMG_FORMAT_INDEX8: c_int = 1;
+pub const KMG_FORMAT_INDEX16: c_int = 2;
 
 extern "C" {
     pub fn kmg_last_error() -> *const c_char;
@@ -101,6 +105,31 @@ extern "C" {
         algo: c_int,
         mode: c_int,
         out_rgba: *mut u8,
+    ) -> c_int;
+    // find / reduce with an output format: out_index receives 4, 1 or 2 bytes per pixel (a `void *` in the header)
+    pub fn kmg_find_indexed(
+        p: *mut kmg_processor,
+        rgba: *const u8,
+        width: u32,
+        height: u32,
+        palette_rgba: *const u8,
+        n_colors: u32,
+        mode: c_int,
+        format: c_int,
+        out_index: *mut (),
+    ) -> c_int;
+    pub fn kmg_reduce_indexed(
+        p: *mut kmg_processor,
+        rgba: *const u8,
+        width: u32,
+        height: u32,
+        color_count: u32,
+        algo: c_int,
+        mode: c_int,
+        format: c_int,
+        out_palette_rgba: *mut u8,
+        out_count: *mut u32,
+        out_index: *mut (),
     ) -> c_int;
     // ImageProcessor::new over a device list (the reference is single-device: lib.rs:38-65) and the same three calls, the image
     // tiled in row bands over the devices, the k x 4 sums of a sharded Lloyd loop all-reduced by RCCL inside the library
