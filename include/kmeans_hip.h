@@ -281,8 +281,11 @@ KMG_API int kmg_lloyd_assign_accumulate(kmg_lloyd *s, const uint8_t *d_rgba, uin
  * labels, sums and centroids are bit-identical to the per-pixel scan.  kmg_lloyd_run binds by
  * itself when its cost model says it pays (kmg_options.strategy overrides).  The caller
  * must not modify the pixel buffer while it is bound.  kmg_lloyd_init_centroids / _init_step (j = 1)
- * start a new problem: they drop any earlier binding of the buffer (and bind it afresh when the
- * initialisation itself runs over the colour table).                                             */
+ * start a new problem: they drop any earlier binding of the buffer, for every k (and bind it afresh
+ * when the initialisation itself runs over the colour table).  That binding is the library's own: it
+ * serves the kmg_lloyd_run / _prepare of the problem the initialisation started, and
+ * kmg_lloyd_set_centroids ends that problem -- after it, run and prepare read the buffer's current
+ * contents again (the next frame in the same buffer).                                            */
 KMG_API int kmg_lloyd_bind_image(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n_pixels, void *stream);
 KMG_API int kmg_lloyd_unbind_image(kmg_lloyd *s);
 /* Tuning support: what the binding found in the image -- out[0] = occupied cells of the 32^3 grid over the colour cube (the cube

@@ -693,6 +693,9 @@ try {
         h[i].C = chroma(h[i].a, h[i].b);
     }
     s->tab.tables_valid = false;
+    // a caller's table starts another problem than the one the initialisation bound the buffer for: kmg_lloyd_run / _prepare
+    // must not take that binding over (the next frame may have arrived in the same buffer since)
+    s->tab.bound_by_init = false;
     HIP_TRY(hipMemcpyAsync(s->d_cent, h.data(), sizeof(Centroid) * s->k, hipMemcpyHostToDevice, S(stream)));
     HIP_TRY(hipStreamSynchronize(S(stream)));
     return KMG_OK;
@@ -780,6 +783,8 @@ try {
     const uint64_t i0 = (uint64_t)y0 * w + (uint64_t)x0;
     const uint32_t *rgba = (const uint32_t *)d_rgba;
     HIP_TRY(launch_init_first(rgba, i0, s->p->d_lut, s->d_cent, s->d_key, S(stream)));
+    // (k = 1 has no pass that would decide about the binding: the earlier binding of this buffer is dropped here)
+    if (s->k == 1 && s->tab.rgba == d_rgba) s->tab.rgba = nullptr;
     if (s->k > 1) {
         int rc;
         bool colours = false;
