@@ -537,8 +537,13 @@ KMG_API int kmg_group_reduce_batch(kmg_group *g, uint32_t n_images, const uint8_
 
 /* ---- ChooseCentroidModule::compute (core/src/modules.rs:763-840) over row bands that are resident on the group's devices.
  * d_rgba[i] (device memory of local device i) holds image rows [row0[i], row0[i] + rows[i]) of a width x height image,
- * d_labels[i] (optional, may be NULL as a whole) receives that band's u32 label map; rows[i] may be 0.  The bands of all
- * ranks of the world tile the image.  _bind only records the bands (it may be called again for a new image); the calls below
+ * d_labels[i] (optional) receives that band's u32 label map; rows[i] may be 0.  d_labels may be NULL as a whole, and any single
+ * entry may be NULL: that band's label map is then not written, the other bands' are (a band without rows has none either way).
+ * The bands of all ranks of the world tile the image: any split into whole rows, in any owner order (rank 0 may own the bottom
+ * rows); results do not depend on the split.  _bind only records the bands, the image size and the flags, and replaces all three
+ * of an earlier _bind of the same object (another image, other bands, other flags: any change in any direction; call it again too
+ * when new pixels were written into bound bands); the centroids stay.  A refused _bind leaves the earlier one in place.  Argument
+ * errors of every call below are refused on the host before any rank starts: the group stays usable.  The calls below
  * enqueue on the devices' compute streams and return -- only _run, _sync and _get_centroids synchronise.
  *   _init       PlusPlusInitModule::compute (modules.rs:946-1246) sharded: per centroid ONE all-gather of every band's
  *               {64-bit arg-max key, colour of the pixel it names} (kmg_lloyd_init_step / _init_pick_band); the largest key wins
@@ -559,7 +564,20 @@ KMG_API int kmg_group_reduce_batch(kmg_group *g, uint32_t n_images, const uint8_
                                      with rows and label maps): the cube pass adds into the accumulators, the band's label pass
                                      updates from the all-reduced sums and clears them (kmg_lloyd_accumulate_into /
                                      _labels_from_tables_update: two launches per iteration instead of four).  Refused by _run,
-                                     which reads the convergence count between update and re-assignment                       */
+                                     which reads the convergence count between update and re-assignment.
+                                     What _prime + n x _step amount to, from centroids c0 (u = one update, A(c) = the assignment
+                                     under c with its label maps and sums):
+                                       flags                 world                      updates   centroids   label maps describe
+                                       no FUSED_UPDATE       any                        n         c_n         A(c_n): after the last update
+                                       FUSED_UPDATE          one rank, no collectives   n + 1     c_(n+1)     A(c_n): before the last update
+                                        (with or without CELLS, any k: CELLS needs collectives)
+                                       FUSED_UPDATE | CELLS  collectives, k <= 256      n + 1     c_(n+1)     A(c_n): before the last update
+                                       FUSED_UPDATE alone    collectives                n         c_n         A(c_n): the flag is ignored
+                                        (the all-reduce lies between assignment and update: the plain loop)
+                                     FUSED_UPDATE | CELLS with collectives is refused by _bind (KMG_ERR_INVALID_ARGUMENT) when k > 256,
+                                     a local rank has no rows, or a local rank has no label map.  KMG_GROUP_CELLS alone with
+                                     k > 256 is the plain loop.  _step takes its sums from the _prime or _step before it; _prime
+                                     starts over from the current centroids (after _bind, _set_centroids, _init, _run).               */
 KMG_API int kmg_group_lloyd_create(kmg_group *g, uint32_t k, kmg_group_lloyd **out);
 KMG_API void kmg_group_lloyd_destroy(kmg_group_lloyd *gl);
 KMG_API int kmg_group_lloyd_bind(kmg_group_lloyd *gl, const uint8_t *const *d_rgba, const uint32_t *row0, const uint32_t *rows,

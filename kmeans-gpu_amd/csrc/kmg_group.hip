@@ -1015,6 +1015,15 @@ int group_lloyd_bind(kmg_group_lloyd *gl, const uint8_t *const *d_rgba, const ui
             if ((uint64_t)row0[e] + rows[e] > heights[im]) return fail(KMG_ERR_INVALID_ARGUMENT, "band %u of image %u leaves the image", i, im);
         }
     }
+    // KMG_GROUP_FUSED_UPDATE with KMG_GROUP_CELLS in a world with collectives: every band's label pass carries the update.  All of
+    // it is known here, on the host: refused before any rank starts (inside _prime a refusal would abort the communicators)
+    if ((flags & KMG_GROUP_FUSED_UPDATE) && (flags & KMG_GROUP_CELLS) && gl->g->collectives) {
+        if (gl->k > 256u) return fail(KMG_ERR_INVALID_ARGUMENT, "KMG_GROUP_FUSED_UPDATE with KMG_GROUP_CELLS needs k <= 256 (k = %u)", gl->k);
+        for (uint32_t i = 0; i < nl; ++i)
+            if (!rows[i] || !d_labels || !d_labels[i])
+                return fail(KMG_ERR_INVALID_ARGUMENT, "KMG_GROUP_FUSED_UPDATE with KMG_GROUP_CELLS: every rank needs a band with rows and a label map (rank %u has %s)",
+                            gl->g->first_rank + i, rows[i] ? "no label map" : "no rows");
+    }
     gl->flags = flags;
     for (uint32_t im = 0; im < gl->n_images; ++im)
         for (uint32_t i = 0; i < nl; ++i) {

@@ -850,7 +850,7 @@ class Group:
     palette / find / reduce mirror ImageProcessor's and give the same bytes."""
 
     def __init__(self, devices=None, flags=0, unique_id=None, first_rank=0, world=None, shrink_max_dim=256, max_iterations=128,
-                 check_period=8, convergence=1.0, strategy=None):
+                 check_period=8, convergence=1.0, strategy=None, alpha_cutoff=0):
         o = GroupOptions()
         lib().kmg_default_group_options(C.byref(o))
         if devices is not None:
@@ -866,6 +866,7 @@ class Group:
         o.processor.check_period = check_period
         o.processor.convergence = convergence
         o.processor.strategy = _default_strategy if strategy is None else _strategy_value(strategy)
+        o.processor.alpha_cutoff = int(alpha_cutoff)     # (kmg_group_create refuses anything but 0: the group has no alpha mode)
         self._h = C.c_void_p()
         if unique_id is None:
             _check(lib().kmg_group_create(C.byref(o), C.byref(self._h)))

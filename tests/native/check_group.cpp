@@ -229,6 +229,26 @@ int main(int argc, char **argv)
                     CHECK(kmg_group_lloyd_get_centroids(gl, c_group.data()));
                     EXPECT(!memcmp(c_one.data(), c_group.data(), sizeof(float) * 4 * k));
                     EXPECT(kmg_group_lloyd_run(gl, &it_group) == KMG_ERR_INVALID_ARGUMENT && strstr(kmg_last_error(), "FUSED"));
+                    // the fused form's preconditions are argument errors: refused by _bind, before any rank starts (inside _prime the
+                    // refusal would abort the communicators); the earlier binding stays and the group goes on working
+                    EXPECT(kmg_group_lloyd_bind(gl, bands.data(), row0.data(), rows.data(), w, h, nullptr, KMG_GROUP_CELLS | KMG_GROUP_FUSED_UPDATE) == KMG_ERR_INVALID_ARGUMENT);
+                    std::vector<uint32_t *> one_missing = labs;
+                    one_missing[ranks - 1] = nullptr;
+                    EXPECT(kmg_group_lloyd_bind(gl, bands.data(), row0.data(), rows.data(), w, h, one_missing.data(), KMG_GROUP_CELLS | KMG_GROUP_FUSED_UPDATE) == KMG_ERR_INVALID_ARGUMENT);
+                    if (ranks > 1) {
+                        std::vector<uint32_t> r0 = row0, rs = rows;
+                        rs[1] += rs[0]; r0[1] = r0[0]; rs[0] = 0;                                   // rank 0 without rows
+                        std::vector<const uint8_t *> bs = bands;
+                        bs[1] = bands[0];
+                        EXPECT(kmg_group_lloyd_bind(gl, bs.data(), r0.data(), rs.data(), w, h, labs.data(), KMG_GROUP_CELLS | KMG_GROUP_FUSED_UPDATE) == KMG_ERR_INVALID_ARGUMENT
+                               && strstr(kmg_last_error(), "no rows"));
+                    }
+                    CHECK(kmg_group_lloyd_set_centroids(gl, c_init.data()));
+                    CHECK(kmg_group_lloyd_prime(gl));                                               // (still the fused binding made above)
+                    for (uint32_t i = 0; i < it_one; ++i) CHECK(kmg_group_lloyd_step(gl));
+                    CHECK(kmg_group_lloyd_sync(gl));
+                    CHECK(kmg_group_lloyd_get_centroids(gl, c_group.data()));
+                    EXPECT(!memcmp(c_one.data(), c_group.data(), sizeof(float) * 4 * k));
                     CHECK(kmg_group_lloyd_bind(gl, bands.data(), row0.data(), rows.data(), w, h, labs.data(), flags));
                 }
                 if (flags == 0u) {
