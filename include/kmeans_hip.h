@@ -462,6 +462,66 @@ KMG_API int kmg_apply_plan_status(kmg_apply_plan *plan);
 /* mix_colors.wgsl:53-67: the dither threshold of a centroid table (host helper).             */
 KMG_API int kmg_dither_threshold(const float *centroids4, uint32_t k, float *threshold);
 
+/* ======================= quantisation error statistics, quality-targeted colour count =====
+ * How far an output is from its source, as exact integers: every field is a sum or a maximum of integers, so a record does not
+ * depend on tiling, order or stream (the rule of the accumulators above).  No counterpart in the reference.
+ *  - Counted pixels.  alpha_cutoff t = 0 counts every pixel; t = 1..255 counts a pixel iff the SOURCE's alpha byte is >= t.  The
+ *    output's alpha is never read.
+ *  - Output side.  KMG_FORMAT_RGBA8: o = the output's R, G, B bytes.  KMG_FORMAT_INDEX8 / INDEX16 with a HOST palette of k x 4
+ *    bytes: o = palette[index].  Index k, the transparent slot, is legal on uncounted pixels only: a counted pixel whose index is
+ *    >= k adds 1 to `invalid` and nothing to any other field (`pixels` included).
+ *  - Lab terms.  q(c) = (rint(64 L), rint(64 a), rint(64 b)) as int32, (L, a, b) = the Lab kmg_dev_rgb_to_lab gives the sRGB8
+ *    colour c, rint = round half to even (the product by 64 is exact).  Per pixel dq = q(s) - q(o); the term dqL^2 + dqa^2 + dqb^2
+ *    is at most 347 973 309 < 2^29 (from the Lab range of all 2^24 colours), so lab_sse < 2^61 for 2^32 pixels.
+ *    mean dE76^2 = lab_sse / (4096 pixels).  (CIE94 is asymmetric and a float: it has no exact sum.)
+ *  - Combination.  kmg_dev_compare COMBINES into d_stats as it stands -- sums are added, maxima are maxed (the convention of
+ *    kmg_lloyd_accumulate_into) -- so the bands of an image or the frames of a sequence accumulate into one record in any order, on
+ *    any streams; the caller clears the record (112 zero bytes) for a fresh measurement.  The fields of a part (KMG_ERROR_RGB,
+ *    KMG_ERROR_LAB) that `what` does not request are left alone; pixels, changed and invalid are always combined.
+ * The kmg_group_* calls have no error statistics.                                                                            */
+#define KMG_ERROR_RGB 1u
+#define KMG_ERROR_LAB 2u
+typedef struct kmg_error_stats {   /* 14 x uint64_t, no padding */
+    uint64_t pixels;      /* counted pixels (those with an invalid index aside)                                  */
+    uint64_t changed;     /* counted pixels whose R, G or B differs                                              */
+    uint64_t invalid;     /* index formats: counted pixels whose index is >= k (they add nothing else)           */
+    uint64_t sse[3];      /* sum (s_c - o_c)^2, c = R, G, B                     [KMG_ERROR_RGB]                  */
+    uint64_t sad[3];      /* sum |s_c - o_c|                                    [KMG_ERROR_RGB]                  */
+    uint64_t max_abs[3];  /* max |s_c - o_c|                                    [KMG_ERROR_RGB]                  */
+    uint64_t lab_sse;     /* sum (dqL^2 + dqa^2 + dqb^2)                        [KMG_ERROR_LAB]                  */
+    uint64_t lab_max;     /* max of that per-pixel sum                          [KMG_ERROR_LAB]                  */
+} kmg_error_stats;
+
+/* d_src_rgba / d_out: n_pixels (< 2^32) pixels in DEVICE memory (d_out: 4, 1 or 2 bytes per pixel for `format`, INDEX16 2-byte
+ * aligned); palette_rgba: HOST, k x 4 bytes, NULL (and k ignored) for KMG_FORMAT_RGBA8 -- it is read before the call returns;
+ * d_stats: DEVICE, 8-byte aligned.  Only enqueues work on `stream`.  KMG_ERR_INVALID_ARGUMENT: INDEX8 with k > 256 (k > 255 when
+ * alpha_cutoff != 0), k = 0 or k > KMG_MAX_K with an index format, `what` = 0 or with unknown bits, alpha_cutoff > 255.          */
+KMG_API int kmg_dev_compare(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_out, uint64_t n_pixels, int format,
+                            const uint8_t *palette_rgba, uint32_t k, uint32_t alpha_cutoff, uint32_t what, kmg_error_stats *d_stats,
+                            void *stream);
+/* The same on HOST buffers, with the processor's alpha_cutoff: uploads both images, OVERWRITES *stats, synchronises.           */
+KMG_API int kmg_compare(kmg_processor *p, const uint8_t *src_rgba, const void *out, uint32_t width, uint32_t height, int format,
+                        const uint8_t *palette_rgba, uint32_t k, uint32_t what, kmg_error_stats *stats);
+/* kmg_reduce_indexed with the colour count chosen by a quality target: as few colours in [k_min, k_max] as keep the mean squared
+ * Lab error of the palette step's working image at or below `target` (units of 1/4096 dE76^2).  KMG_ALGO_KMEANS only (the octree
+ * is a host algorithm whose colour count is not a monotone knob).
+ *   W    = the working image of the palette step: the image after the shrink (kmg_options.shrink_max_dim), then -- alpha mode -- its
+ *          kept pixels in raster order (include/kmeans_hip.h at kmg_options); made once per call
+ *   C_k  = the centroids the palette pipeline gives W at k (those of kmg_reduce_indexed(k))
+ *   E(k) = lab_sse of W against P[label]: label = the KMG_MODE_REPLACE index of each pixel of W under C_k, P = the palette bytes
+ *          of the output pass (what kmg_reduce_indexed returns); every pixel of W is counted
+ *   k is ACCEPTED iff E(k) <= (uint64_t)target * |W|
+ * The search is fixed: evaluate k_max; not accepted: k* = k_max, *reached = 0.  Otherwise lo = k_min, hi = k_max; while lo < hi:
+ * mid = (lo + hi) / 2, accepted: hi = mid, else lo = mid + 1; k* = hi, *reached = 1.  At most 1 + ceil(log2(k_max - k_min + 1))
+ * palette runs, each a new Lloyd problem on W.  Output (mode, format: the rules of kmg_reduce_indexed, KMG_FORMAT_RGBA8 included;
+ * KMG_FORMAT_INDEX8 is checked against k_max), palette and *out_count are byte for byte what kmg_reduce_indexed(k*) writes for
+ * the image; out_palette_rgba has room for k_max x 4 bytes.  *achieved (optional) = the RGB and Lab statistics of W at k*;
+ * *reached is optional too.  k_min < 1, k_min > k_max or k_max > KMG_MAX_K: KMG_ERR_INVALID_ARGUMENT.
+ * The kmg_group_* calls have no counterpart.                                                                                   */
+KMG_API int kmg_reduce_quality(kmg_processor *p, const uint8_t *rgba, uint32_t width, uint32_t height, uint32_t k_min, uint32_t k_max,
+                               uint32_t target, int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out,
+                               kmg_error_stats *achieved, int *reached);
+
 /* ======================= several GPUs: a group of devices ================================
  * ImageProcessor::new (core/src/lib.rs:38-65) picks ONE adapter; the reference has no multi-device path.  A kmg_group is the
  * same constructor over a device LIST: one kmg_processor, one compute stream and one RCCL communicator rank per device.

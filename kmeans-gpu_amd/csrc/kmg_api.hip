@@ -23,16 +23,21 @@ int check_image(const kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_
     return KMG_OK;
 }
 
-// operations.rs:15-88 extract_palette_kmeans on a device-resident image -> host centroid table.  Alpha mode (alpha_cutoff != 0,
-// include/kmeans_hip.h at kmg_options): the kept pixels of the shrunk image, compacted in raster order, are an image of n_kept x 1
-// pixels for the unchanged pipeline -- unless every pixel is kept, which is the default call.
-int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff,
-                           hipStream_t st, float *c4)
+// The working image of the k-means palette step (operations.rs:15-88 extract_palette_kmeans before its loop): the image after the
+// shrink, then -- alpha mode (alpha_cutoff != 0, include/kmeans_hip.h at kmg_options) -- its kept pixels, compacted in raster order,
+// as an image of n_kept x 1 pixels, unless every pixel is kept.  Made once per call; the buffers live as long as the object.
+struct WorkingImage {
+    StreamBuf small, kept;
+    const uint8_t *src = nullptr;
+    uint32_t sw = 0, sh = 0;
+};
+
+int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t alpha_cutoff, hipStream_t st, WorkingImage &wi)
 {
     int rc;
     const uint8_t *src = d_rgba;
     uint32_t sw = w, sh = h;
-    StreamBuf small;
+    StreamBuf &small = wi.small;
     const uint32_t m = p->opt.shrink_max_dim;
     if (m && (w > m || h > m)) {                                       // structures.rs:67-74
         kmg_resized_dims(w, h, m, &sw, &sh);
@@ -40,7 +45,7 @@ int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, 
         if ((rc = kmg_dev_resize(p, d_rgba, w, h, sw, sh, (uint8_t *)small.ptr, st)) != KMG_OK) return rc;
         src = (const uint8_t *)small.ptr;
     }
-    StreamBuf kept;
+    StreamBuf &kept = wi.kept;
     if (alpha_cutoff) {
         const uint64_t n = (uint64_t)sw * sh;
         HIP_TRY(kept.alloc(p, (size_t)n * 4 + 256, st));               // (the count behind the pixels, 256-byte aligned)
@@ -56,6 +61,20 @@ int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, 
             sh = 1;
         }
     }
+    wi.src = src;
+    wi.sw = sw;
+    wi.sh = sh;
+    return KMG_OK;
+}
+
+// operations.rs:15-88 extract_palette_kmeans on a working image -> host centroid table: a new Lloyd problem of k centroids.
+// d_labels (optional): the u32 label of every pixel of the working image under the final centroids (find_centroid.wgsl:15-44, the
+// label KMG_MODE_REPLACE gives the pixel).
+int palette_of_working(kmg_processor *p, const WorkingImage &wi, uint32_t k, hipStream_t st, float *c4, uint32_t *d_labels = nullptr)
+{
+    int rc;
+    const uint8_t *src = wi.src;
+    const uint32_t sw = wi.sw, sh = wi.sh;
     LloydGuard g;
     if ((rc = lloyd_create_impl(p, k, &g.s, st)) != KMG_OK) return rc;
     if ((rc = kmg_lloyd_init_centroids(g.s, src, sw, sh, st)) != KMG_OK) return rc;   // operations.rs:73
@@ -75,7 +94,17 @@ int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, 
         for (uint32_t i = 0; i < k; ++i)
             fprintf(stderr, "[kmeans_hip] Centroid %u = [%g, %g, %g, %g]\n", i, c4[4 * i], c4[4 * i + 1], c4[4 * i + 2], c4[4 * i + 3]);
     }
+    if (d_labels && (rc = kmg_lloyd_labels(g.s, src, (uint64_t)sw * sh, d_labels, st)) != KMG_OK) return rc;
     return KMG_OK;
+}
+
+int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff,
+                           hipStream_t st, float *c4)
+{
+    int rc;
+    WorkingImage wi;
+    if ((rc = working_image(p, d_rgba, w, h, alpha_cutoff, st, wi)) != KMG_OK) return rc;
+    return palette_of_working(p, wi, k, st, c4);
 }
 
 // An image between a caller's (pageable) buffer and the device.  The calls that use this return when the work is done, so a large
@@ -391,3 +420,186 @@ try {
 }
 KMG_ABI_CATCH
 
+// ---------------------------------------------------------------------------------------------
+// error statistics and the quality-targeted colour count (include/kmeans_hip.h at kmg_error_stats; kernels: kmg_error.hip)
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+void free_host_copy(void *copy) { delete[] static_cast<uint8_t *>(copy); }
+
+// kmg_dev_compare with the output's form given (kmg_kernels.h kErrorRgba8 .. kErrorLabel32).  Enqueues on st: for the index forms
+// the palette's upload from a heap copy of the caller's bytes (released by the stream once the copy has run), the launch that
+// makes its q triples, and the statistics launch; the device scratch goes back to the pool in stream order.
+int dev_compare_form(kmg_processor *p, const uint8_t *d_src, const void *d_out, uint64_t n, int form, const uint8_t *palette_rgba,
+                     uint32_t k, uint32_t alpha_cutoff, uint32_t what, kmg_error_stats *d_stats, hipStream_t st)
+{
+    static_assert(sizeof(kmg_error_stats) == 14 * sizeof(uint64_t), "kmg_error_stats is 14 x uint64_t");
+    // (the refusals that need no device come first)
+    if (what == 0 || (what & ~(KMG_ERROR_RGB | KMG_ERROR_LAB))) return fail(KMG_ERR_INVALID_ARGUMENT, "what = %u: KMG_ERROR_RGB | KMG_ERROR_LAB", what);
+    if (alpha_cutoff > 255u) return fail(KMG_ERR_INVALID_ARGUMENT, "alpha cutoff %u is above 255", alpha_cutoff);
+    if (form != kErrorRgba8) {
+        if (!palette_rgba || k == 0 || k > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "an index format needs a palette of 1 .. %u colours", KMG_MAX_K);
+        if (form == kErrorIndex8 && k + (alpha_cutoff ? 1u : 0u) > 256u)
+            return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u%s needs INDEX16", k, alpha_cutoff ? " plus the transparent slot" : "");
+        if (form == kErrorIndex16 && (reinterpret_cast<uintptr_t>(d_out) & 1u)) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX16 output is not 2-byte aligned");
+    }
+    if (!p || !d_src || !d_out || !d_stats || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad compare arguments");
+    if (n > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "more than 2^32-1 pixels");
+    if (reinterpret_cast<uintptr_t>(d_stats) & 7u) return fail(KMG_ERR_INVALID_ARGUMENT, "the statistics record is not 8-byte aligned");
+    HIP_TRY(hipSetDevice(p->device));
+    unsigned long long *stats = reinterpret_cast<unsigned long long *>(d_stats);
+    if (form == kErrorRgba8) {
+        HIP_TRY(launch_error_stats(form, what, (const uint32_t *)d_src, d_out, n, nullptr, nullptr, 0, alpha_cutoff, p->d_lut, stats, st));
+        return KMG_OK;
+    }
+    StreamBuf tab;                                                     // k (word, qL, qa, qb) entries, then the k palette words
+    const size_t ent_bytes = pad256(error_palette_bytes(k));
+    HIP_TRY(tab.alloc(p, ent_bytes + (size_t)k * 4, st));
+    uint32_t *d_pal = (uint32_t *)((uint8_t *)tab.ptr + ent_bytes);
+    uint8_t *copy = new uint8_t[(size_t)k * 4];
+    memcpy(copy, palette_rgba, (size_t)k * 4);
+    hipError_t e = hipMemcpyAsync(d_pal, copy, (size_t)k * 4, hipMemcpyHostToDevice, st);
+    const hipError_t e2 = hipLaunchHostFunc(st, free_host_copy, copy);
+    if (e2 != hipSuccess) {                                            // (not enqueued: wait for the copy, release here)
+        (void)hipStreamSynchronize(st);
+        delete[] copy;
+    }
+    HIP_TRY(e);
+    HIP_TRY(e2);
+    if (what & KMG_ERROR_LAB) HIP_TRY(launch_error_palette(d_pal, k, p->d_lut, tab.ptr, st));
+    HIP_TRY(launch_error_stats(form, what, (const uint32_t *)d_src, d_out, n, d_pal, tab.ptr, k, alpha_cutoff, p->d_lut, stats, st));
+    return KMG_OK;
+}
+
+int format_form(int format)
+{
+    return format == KMG_FORMAT_RGBA8 ? kErrorRgba8 : format == KMG_FORMAT_INDEX8 ? kErrorIndex8 : format == KMG_FORMAT_INDEX16 ? kErrorIndex16 : -1;
+}
+
+}  // namespace
+
+extern "C" int kmg_dev_compare(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_out, uint64_t n_pixels, int format,
+                               const uint8_t *palette_rgba, uint32_t k, uint32_t alpha_cutoff, uint32_t what, kmg_error_stats *d_stats,
+                               void *stream)
+try {
+    const int form = format_form(format);
+    if (form < 0) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
+    return dev_compare_form(p, d_src_rgba, d_out, n_pixels, form, palette_rgba, k, alpha_cutoff, what, d_stats, S(stream));
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_compare(kmg_processor *p, const uint8_t *src_rgba, const void *out, uint32_t w, uint32_t h, int format,
+                           const uint8_t *palette_rgba, uint32_t k, uint32_t what, kmg_error_stats *stats)
+try {
+    int rc;
+    // (the refusals that need no device come first)
+    const int form = format_form(format);
+    if (form < 0) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
+    if (what == 0 || (what & ~(KMG_ERROR_RGB | KMG_ERROR_LAB))) return fail(KMG_ERR_INVALID_ARGUMENT, "what = %u: KMG_ERROR_RGB | KMG_ERROR_LAB", what);
+    if (form != kErrorRgba8 && (!palette_rgba || k == 0 || k > KMG_MAX_K))
+        return fail(KMG_ERR_INVALID_ARGUMENT, "an index format needs a palette of 1 .. %u colours", KMG_MAX_K);
+    if (form == kErrorIndex8 && k > 256u) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u needs INDEX16", k);
+    if ((rc = check_image(p, src_rgba, w, h)) != KMG_OK) return rc;
+    if (!out || !stats) return fail(KMG_ERR_INVALID_ARGUMENT, "output or statistics pointer is NULL");
+    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
+    if (form == kErrorIndex8 && k + (alpha_cutoff ? 1u : 0u) > 256u)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u%s needs INDEX16", k, alpha_cutoff ? " plus the transparent slot" : "");
+    HIP_TRY(hipSetDevice(p->device));
+    StreamGuard sg;
+    HIP_TRY(sg.acquire(p));
+    const size_t n = (size_t)w * h, out_bytes = n * (form == kErrorIndex8 ? 1u : form == kErrorIndex16 ? 2u : 4u);
+    StreamBuf img, res, rec;
+    if ((rc = upload_image(p, src_rgba, w, h, sg.st, img)) != KMG_OK) return rc;
+    HIP_TRY(res.alloc(p, out_bytes, sg.st));
+    HIP_TRY(copy_host_image(p, res.ptr, out, out_bytes, hipMemcpyHostToDevice, sg.st));
+    HIP_TRY(rec.alloc(p, sizeof(kmg_error_stats), sg.st));
+    HIP_TRY(hipMemsetAsync(rec.ptr, 0, sizeof(kmg_error_stats), sg.st));
+    if ((rc = dev_compare_form(p, (const uint8_t *)img.ptr, res.ptr, n, form, palette_rgba, k, alpha_cutoff, what, (kmg_error_stats *)rec.ptr,
+                               sg.st)) != KMG_OK) {
+        (void)hipStreamSynchronize(sg.st);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(stats, rec.ptr, sizeof(kmg_error_stats), hipMemcpyDeviceToHost, sg.st));
+    HIP_TRY(hipStreamSynchronize(sg.st));
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_reduce_quality(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t k_min, uint32_t k_max,
+                                  uint32_t target, int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out,
+                                  kmg_error_stats *achieved, int *reached)
+try {
+    int rc;
+    // (the refusals that need no device come first)
+    if (k_min < 1 || k_min > k_max || k_max > KMG_MAX_K)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "colour counts [%u, %u]: 1 <= k_min <= k_max <= %u", k_min, k_max, KMG_MAX_K);
+    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_DIFFUSE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
+    if (format < KMG_FORMAT_RGBA8 || format > KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
+    if (format != KMG_FORMAT_RGBA8 && mode == KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "meld blends two colours: it has no index output");
+    if (format == KMG_FORMAT_INDEX8 && k_max > 256u) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k_max = %u needs INDEX16", k_max);
+    if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
+    if (!out || !out_palette_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
+    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
+    if (format == KMG_FORMAT_INDEX8 && k_max + (alpha_cutoff ? 1u : 0u) > 256u)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k_max = %u%s needs INDEX16", k_max, alpha_cutoff ? " plus the transparent slot" : "");
+    HIP_TRY(hipSetDevice(p->device));
+    StreamGuard sg;
+    HIP_TRY(sg.acquire(p));
+    hipStream_t st = sg.st;
+    StreamBuf img;
+    if ((rc = upload_image(p, rgba, w, h, st, img)) != KMG_OK) return rc;
+    WorkingImage wi;                                                   // uploaded, shrunk and compacted once
+    if ((rc = working_image(p, (const uint8_t *)img.ptr, w, h, alpha_cutoff, st, wi)) != KMG_OK) return rc;
+    const uint64_t nw = (uint64_t)wi.sw * wi.sh;
+    StreamBuf labels, rec;
+    HIP_TRY(labels.alloc(p, (size_t)nw * 4, st));
+    HIP_TRY(rec.alloc(p, sizeof(kmg_error_stats), st));
+
+    // one candidate: the palette pipeline on W at k (a new Lloyd problem), the labels of W, the palette bytes, the statistics
+    std::vector<float> c4(4 * (size_t)k_max), best_c4;
+    std::vector<uint8_t> pal(4 * (size_t)k_max);
+    kmg_error_stats cur, best;
+    uint32_t runs = 0;
+    auto evaluate = [&](uint32_t k, bool *accepted) -> int {
+        int r;
+        if ((r = palette_of_working(p, wi, k, st, c4.data(), (uint32_t *)labels.ptr)) != KMG_OK) return r;
+        for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], &pal[4 * i]);
+        HIP_TRY(hipMemsetAsync(rec.ptr, 0, sizeof(kmg_error_stats), st));
+        if ((r = dev_compare_form(p, wi.src, labels.ptr, nw, kErrorLabel32, pal.data(), k, 0, KMG_ERROR_RGB | KMG_ERROR_LAB,
+                                  (kmg_error_stats *)rec.ptr, st)) != KMG_OK) return r;
+        HIP_TRY(hipMemcpyAsync(&cur, rec.ptr, sizeof cur, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        ++runs;
+        *accepted = cur.lab_sse <= (uint64_t)target * nw;
+        if (log_debug())
+            fprintf(stderr, "[kmeans_hip] reduce_quality: k = %u, E = %llu, limit %llu: %s\n", k, (unsigned long long)cur.lab_sse,
+                    (unsigned long long)((uint64_t)target * nw), *accepted ? "accepted" : "not accepted");
+        return KMG_OK;
+    };
+    auto keep = [&](uint32_t k) { best = cur; best_c4.assign(c4.begin(), c4.begin() + 4 * (size_t)k); };
+
+    bool ok = false;
+    uint32_t k_star = k_max;
+    if ((rc = evaluate(k_max, &ok)) != KMG_OK) return rc;
+    keep(k_max);
+    const int did_reach = ok ? 1 : 0;
+    if (ok) {
+        uint32_t lo = k_min, hi = k_max;
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if ((rc = evaluate(mid, &ok)) != KMG_OK) return rc;
+            if (ok) { hi = mid; keep(mid); }
+            else lo = mid + 1;
+        }
+        k_star = hi;
+    }
+    if ((rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, best_c4.data(), k_star, mode, alpha_cutoff, st, (uint8_t *)out, format)) != KMG_OK)
+        return rc;
+    for (uint32_t i = 0; i < k_star; ++i) shader_lab_to_rgba8(&best_c4[4 * i], out_palette_rgba + 4 * i);
+    *out_count = k_star;
+    if (achieved) *achieved = best;
+    if (reached) *reached = did_reach;
+    if (log_debug()) fprintf(stderr, "[kmeans_hip] reduce_quality: k* = %u after %u palette runs\n", k_star, runs);
+    return KMG_OK;
+}
+KMG_ABI_CATCH

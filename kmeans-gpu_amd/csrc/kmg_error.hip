@@ -1,0 +1,258 @@
+// kmg_error.hip -- quantisation error statistics (kmg_error_stats, include/kmeans_hip.h): how far an output is
+// from its source, as exact integer sums and maxima.
+//
+//   k_error_palette  the q triples of a palette, (rint(64 L), rint(64 a), rint(64 b)) of the device's own rgb_to_lab, once per call:
+//                    entry i = (palette word, qL, qa, qb), 16 bytes
+//   k_error_stats    one template over the output's form (RGBA8 words; u8 / u16 indices; u32 labels, the quality search's own) and
+//                    over `what` (the Lab arithmetic is not compiled into the RGB-only instantiations).  At most kErrMaxGrid
+//                    workgroups over contiguous chunks of kErrTile-pixel tiles, as k_alpha_count; a lane takes four consecutive
+//                    pixels per tile -- one 16-byte source load and one 16- / 4- / 8- / 16-byte output load, or one load per pixel
+//                    when the pointers are not aligned for that -- and has the next tile's loads in flight during the current
+//                    tile's arithmetic.  Index forms: the palette (and its q triples) are staged once per workgroup in LDS.
+//                    Accumulators stay in registers (32-bit where a chunk cannot overflow them: see kErrLanePixels), are
+//                    reduced per wave with cross-lane operations, across the waves through LDS, and leave the workgroup as one
+//                    64-bit integer atomicAdd / atomicMax per non-zero field: at most 14 x 2048 integer atomics per launch, no
+//                    float atomics, no waits between workgroups.
+// A pixel that is not counted (out of range, alpha below the cutoff, invalid index) is compared with itself: it adds zero to
+// every sum and maximum without a branch per field.
+
+#include "kmg_device.h"
+#include "kmg_internal.h"
+
+namespace kmg {
+
+namespace {
+
+constexpr uint32_t kErrBlock = 256;                     // 4 waves
+constexpr uint32_t kErrWaves = kErrBlock / 64;
+constexpr uint32_t kErrTile = kErrBlock * 4;            // 4 consecutive pixels per lane
+constexpr uint32_t kErrMaxGrid = 2048;                  // cdna_hip_programming.md Guideline 11
+constexpr uint32_t kErrFields = 14;                     // kmg_error_stats as 14 x u64
+// n < 2^32 pixels are at most 2^22 tiles; a full grid gives a workgroup at most 2^22 / 2048 = 2048 of them, a lane 8192 pixels:
+// its 32-bit sums reach 8192 x 255^2 = 5.3e8 < 2^32.  (The Lab sum, up to 2^29 per pixel, is 64-bit.)
+constexpr uint64_t kErrLanePixels = 8192;
+static_assert(kErrLanePixels * 255u * 255u < 0xFFFFFFFFull, "per-lane 32-bit sums");
+
+enum { fPixels = 0, fChanged = 1, fInvalid = 2, fSse = 3, fSad = 6, fMax = 9, fLabSse = 12, fLabMax = 13 };
+
+__host__ __device__ constexpr bool field_is_max(uint32_t f) { return (f >= fMax && f < fMax + 3) || f == fLabMax; }
+
+// q of an sRGB8 colour: the fixed-point grid of the Lab terms
+__device__ __forceinline__ void px_to_q(const float *s_lut, uint32_t px, int32_t q[3])
+{
+    float L, a, b;
+    px_to_lab(s_lut, px, L, a, b);
+    q[0] = (int32_t)rintf(L * 64.0f);
+    q[1] = (int32_t)rintf(a * 64.0f);
+    q[2] = (int32_t)rintf(b * 64.0f);
+}
+
+__global__ __launch_bounds__(kErrBlock) void k_error_palette(const uint32_t *__restrict__ pal, uint32_t k, const float *__restrict__ lut,
+                                                            int4 *__restrict__ entries)
+{
+    __shared__ float s_lut[256];
+    s_lut[threadIdx.x] = lut[threadIdx.x];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kErrBlock + threadIdx.x;
+    if (i >= k) return;
+    const uint32_t px = pal[i];
+    int32_t q[3];
+    px_to_q(s_lut, px, q);
+    entries[i] = make_int4((int)px, q[0], q[1], q[2]);
+}
+
+// four consecutive output elements as words: RGBA8 words / u32 labels (16-byte load), u8 (4-byte) or u16 (8-byte) indices
+template <int FORM>
+__device__ __forceinline__ void load4_out(const void *out, uint64_t i0, uint64_t n, bool aligned, uint32_t v[4])
+{
+    if (FORM == kErrorRgba8 || FORM == kErrorLabel32) {
+        load4_stream(static_cast<const uint32_t *>(out), i0, n, aligned, v);
+    } else if (FORM == kErrorIndex8) {
+        const uint8_t *o = static_cast<const uint8_t *>(out);
+        if (aligned && i0 + 4 <= n) {
+            const uint32_t w = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(o + i0));
+            v[0] = w & 255u; v[1] = (w >> 8) & 255u; v[2] = (w >> 16) & 255u; v[3] = w >> 24;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (i0 + j < n) ? (uint32_t)o[i0 + j] : 0u;
+        }
+    } else {
+        const uint16_t *o = static_cast<const uint16_t *>(out);
+        if (aligned && i0 + 4 <= n) {
+            const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(o + i0));
+            v[0] = w.x & 0xFFFFu; v[1] = w.x >> 16; v[2] = w.y & 0xFFFFu; v[3] = w.y >> 16;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (i0 + j < n) ? (uint32_t)o[i0 + j] : 0u;
+        }
+    }
+}
+
+// tiles [t0, t1) of this workgroup's chunk
+__device__ __forceinline__ void error_chunk(uint64_t n, uint64_t &t0, uint64_t &t1)
+{
+    const uint64_t tiles = (n + kErrTile - 1) / kErrTile;
+    const uint64_t per = (tiles + gridDim.x - 1) / gridDim.x;
+    t0 = min((uint64_t)blockIdx.x * per, tiles);
+    t1 = min(t0 + per, tiles);
+}
+
+template <int FORM, uint32_t WHAT>
+__global__ __launch_bounds__(kErrBlock) void k_error_stats(const uint32_t *__restrict__ src, const void *__restrict__ out, uint64_t n,
+                                                          const uint32_t *__restrict__ pal, const int4 *__restrict__ entries, uint32_t k,
+                                                          uint32_t cutoff, const float *__restrict__ lut,
+                                                          unsigned long long *__restrict__ stats, int aligned)
+{
+    constexpr bool RGB = (WHAT & KMG_ERROR_RGB) != 0, LAB = (WHAT & KMG_ERROR_LAB) != 0, INDEXED = FORM != kErrorRgba8;
+    extern __shared__ uint4 s_dyn[];                            // index forms: k words, or -- LAB -- k (word, qL, qa, qb) entries
+    __shared__ float s_lut[LAB ? 256 : 1];
+    __shared__ unsigned long long s_part[kErrWaves][kErrFields];
+    const uint32_t *s_pal = reinterpret_cast<const uint32_t *>(s_dyn);
+    const int4 *s_ent = reinterpret_cast<const int4 *>(s_dyn);
+    if (LAB) s_lut[threadIdx.x] = lut[threadIdx.x];
+    if (INDEXED) {
+        if (LAB) for (uint32_t i = threadIdx.x; i < k; i += kErrBlock) reinterpret_cast<int4 *>(s_dyn)[i] = entries[i];
+        else for (uint32_t i = threadIdx.x; i < k; i += kErrBlock) reinterpret_cast<uint32_t *>(s_dyn)[i] = pal[i];
+    }
+    if (LAB || INDEXED) __syncthreads();
+
+    uint32_t pixels = 0, changed = 0, invalid = 0, lab_max = 0;
+    uint32_t sse[3] = {0u, 0u, 0u}, sad[3] = {0u, 0u, 0u}, mx[3] = {0u, 0u, 0u};
+    unsigned long long lab_sse = 0;
+
+    uint64_t t0, t1;
+    error_chunk(n, t0, t1);
+    uint32_t ns[4] = {0u, 0u, 0u, 0u}, no[4] = {0u, 0u, 0u, 0u};
+    if (t0 < t1) {
+        const uint64_t i0 = t0 * kErrTile + (uint64_t)threadIdx.x * 4u;
+        load4_stream(src, i0, n, aligned != 0, ns);
+        load4_out<FORM>(out, i0, n, aligned != 0, no);
+    }
+    for (uint64_t t = t0; t < t1; ++t) {
+        const uint64_t i0 = t * kErrTile + (uint64_t)threadIdx.x * 4u;
+        const uint32_t ps[4] = {ns[0], ns[1], ns[2], ns[3]}, po[4] = {no[0], no[1], no[2], no[3]};
+        if (t + 1 < t1) {                                       // the next tile, in flight meanwhile
+            load4_stream(src, i0 + kErrTile, n, aligned != 0, ns);
+            load4_out<FORM>(out, i0 + kErrTile, n, aligned != 0, no);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t s = ps[q];
+            const bool counted = i0 + (uint64_t)q < n && (s >> 24) >= cutoff;
+            bool valid = true;
+            uint32_t o = po[q];
+            int4 e = make_int4(0, 0, 0, 0);
+            if (INDEXED) {
+                valid = o < k;
+                const uint32_t idx = valid ? o : 0u;
+                if (LAB) { e = s_ent[idx]; o = (uint32_t)e.x; }
+                else o = s_pal[idx];
+            }
+            const bool use = counted && valid;
+            pixels += use ? 1u : 0u;
+            invalid += (counted && !valid) ? 1u : 0u;
+            o = use ? o : s;                                    // a pixel that does not count is compared with itself
+            const bool differs = ((s ^ o) & 0x00FFFFFFu) != 0u;
+            changed += differs ? 1u : 0u;
+            if (RGB) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int d = (int)((s >> (8 * c)) & 255u) - (int)((o >> (8 * c)) & 255u);
+                    const uint32_t ad = (uint32_t)(d < 0 ? -d : d);
+                    sse[c] += ad * ad;
+                    sad[c] += ad;
+                    mx[c] = max(mx[c], ad);
+                }
+            }
+            if (LAB) {
+                if (differs) {                                  // equal colours have equal q: the term is 0
+                    int32_t qs[3], qo[3];
+                    px_to_q(s_lut, s, qs);
+                    if (INDEXED) { qo[0] = e.y; qo[1] = e.z; qo[2] = e.w; }
+                    else px_to_q(s_lut, o, qo);
+                    const int32_t dL = qs[0] - qo[0], da = qs[1] - qo[1], db = qs[2] - qo[2];
+                    const uint32_t term = (uint32_t)(dL * dL) + (uint32_t)(da * da) + (uint32_t)(db * db);   // < 2^29
+                    lab_sse += term;
+                    lab_max = max(lab_max, term);
+                }
+            }
+        }
+    }
+
+    unsigned long long v[kErrFields];
+    v[fPixels] = pixels; v[fChanged] = changed; v[fInvalid] = invalid;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { v[fSse + c] = sse[c]; v[fSad + c] = sad[c]; v[fMax + c] = mx[c]; }
+    v[fLabSse] = lab_sse; v[fLabMax] = lab_max;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t f = 0; f < kErrFields; ++f) {
+        const bool wanted = f < fSse || (f < fLabSse ? RGB : LAB);
+        if (!wanted) continue;
+        unsigned long long x = v[f];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long y = __shfl_xor(x, o);
+            x = field_is_max(f) ? max(x, y) : x + y;
+        }
+        if (lane == 0) s_part[wave][f] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < kErrFields) {
+        const uint32_t f = threadIdx.x;
+        const bool wanted = f < fSse || (f < fLabSse ? RGB : LAB);
+        if (wanted) {
+            unsigned long long x = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < kErrWaves; ++w) x = field_is_max(f) ? max(x, s_part[w][f]) : x + s_part[w][f];
+            if (x != 0) {                                       // (adding 0 or maxing with 0 changes nothing)
+                if (field_is_max(f)) atomicMax(stats + f, x);
+                else atomicAdd(stats + f, x);
+            }
+        }
+    }
+}
+
+template <int FORM>
+hipError_t error_stats_form(uint32_t what, const uint32_t *src, const void *out, uint64_t n, const uint32_t *pal, const void *entries,
+                            uint32_t k, uint32_t cutoff, const float *lut, unsigned long long *stats, hipStream_t st)
+{
+    const uint64_t tiles = (n + kErrTile - 1) / kErrTile;
+    const uint32_t grid = (uint32_t)(tiles < kErrMaxGrid ? (tiles ? tiles : 1) : kErrMaxGrid);
+    // the vector loads: the source 16-byte aligned, the output for its own (RGBA8 words and u32 labels 16, u8 4, u16 8 bytes)
+    const uintptr_t out_mask = FORM == kErrorIndex8 ? 3u : (FORM == kErrorIndex16 ? 7u : 15u);
+    const int aligned = ((reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & out_mask) == 0) ? 1 : 0;
+    const bool lab = (what & KMG_ERROR_LAB) != 0;
+    const size_t lds = FORM == kErrorRgba8 ? 0 : (size_t)k * (lab ? sizeof(int4) : sizeof(uint32_t));
+#define KMG_ES(W) hipLaunchKernelGGL((k_error_stats<FORM, W>), dim3(grid), dim3(kErrBlock), lds, st, src, out, n, pal, \
+                                     static_cast<const int4 *>(entries), k, cutoff, lut, stats, aligned)
+    if (what == KMG_ERROR_RGB) KMG_ES(KMG_ERROR_RGB);
+    else if (what == KMG_ERROR_LAB) KMG_ES(KMG_ERROR_LAB);
+    else KMG_ES(KMG_ERROR_RGB | KMG_ERROR_LAB);
+#undef KMG_ES
+    return hipGetLastError();
+}
+
+}  // namespace
+
+size_t error_palette_bytes(uint32_t k) { return sizeof(int4) * (size_t)k; }
+
+hipError_t launch_error_palette(const uint32_t *pal, uint32_t k, const float *lut, void *entries, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_error_palette, dim3((k + kErrBlock - 1) / kErrBlock), dim3(kErrBlock), 0, st, pal, k, lut, static_cast<int4 *>(entries));
+    return hipGetLastError();
+}
+
+hipError_t launch_error_stats(int form, uint32_t what, const uint32_t *src, const void *out, uint64_t n, const uint32_t *pal,
+                              const void *entries, uint32_t k, uint32_t cutoff, const float *lut, unsigned long long *stats, hipStream_t st)
+{
+    switch (form) {
+    case kErrorRgba8: return error_stats_form<kErrorRgba8>(what, src, out, n, pal, entries, k, cutoff, lut, stats, st);
+    case kErrorIndex8: return error_stats_form<kErrorIndex8>(what, src, out, n, pal, entries, k, cutoff, lut, stats, st);
+    case kErrorIndex16: return error_stats_form<kErrorIndex16>(what, src, out, n, pal, entries, k, cutoff, lut, stats, st);
+    case kErrorLabel32: return error_stats_form<kErrorLabel32>(what, src, out, n, pal, entries, k, cutoff, lut, stats, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace kmg

@@ -152,4 +152,14 @@ hipError_t launch_labels_index(const uint32_t *rgba, uint64_t n, const void *col
 hipError_t launch_narrow_index(const uint32_t *rgba, const uint32_t *labels, uint64_t n, uint32_t k, void *out, bool wide, hipStream_t st,
                                uint32_t alpha_cutoff);
 
+// ---- error statistics (kmg_error.hip; kmg_error_stats of include/kmeans_hip.h): `stats` = 14 u64 the launch COMBINES into (sums
+// added, maxima maxed).  form: what `out` holds per pixel -- an RGBA8 word, a u8 / u16 palette index, or a u32 label (the quality
+// search's own).  Index forms: pal = k palette words, entries = error_palette_bytes(k) written by launch_error_palette from them
+// (both in device memory; entries are read only when `what` has KMG_ERROR_LAB).  n < 2^32.
+enum { kErrorRgba8 = 0, kErrorIndex8 = 1, kErrorIndex16 = 2, kErrorLabel32 = 3 };
+size_t error_palette_bytes(uint32_t k);
+hipError_t launch_error_palette(const uint32_t *pal, uint32_t k, const float *lut, void *entries, hipStream_t st);
+hipError_t launch_error_stats(int form, uint32_t what, const uint32_t *src, const void *out, uint64_t n, const uint32_t *pal,
+                              const void *entries, uint32_t k, uint32_t cutoff, const float *lut, unsigned long long *stats, hipStream_t st);
+
 }  // namespace kmg

@@ -10,10 +10,13 @@
 //   ImageProcessor::create_on({0, 1, ..})      -> the same object over a device LIST (kmg_group_*: one processor + RCCL rank per
 //                                                 device; palette / find / reduce tile the image in row bands, same bytes)
 //   processor.reduce_batch(color_count, images, algo, mode) -> whole images per device, side by side
+//   processor.compare(source, output[, colors])            -> kmg_error_stats: exact error sums of an output against its source
+//   processor.reduce_quality(image, max_delta_e, k_min, k_max, mode) -> the colour count chosen by a quality target
 // `anyhow::Result` errors become kmeans_color_gpu::Error exceptions carrying the kmg_status and the
 // library's message.  Header only; link with -lkmeans_hip.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -162,6 +165,56 @@ public:
         return out;
     }
 
+    // error statistics (include/kmeans_hip.h kmg_error_stats; single-device processors only): exact integer sums and maxima of
+    // an output against its source, over the pixels whose source alpha reaches the processor's alpha_cutoff
+    kmg_error_stats compare(const Image &source, const Image &output, uint32_t what = KMG_ERROR_RGB | KMG_ERROR_LAB) const
+    {
+        if (source.dims != output.dims) throw Error(KMG_ERR_INVALID_ARGUMENT, "compare: the images differ in size");
+        kmg_error_stats s;
+        check(kmg_compare(single(), bytes(source), bytes(output), source.dims.first, source.dims.second, KMG_FORMAT_RGBA8, nullptr, 0, what, &s));
+        return s;
+    }
+    // ... of an index map against its source: `colors` is the palette the indices point into (Indexed::palette of reduce_indexed
+    // and reduce_quality, the caller's palette for find_indexed)
+    kmg_error_stats compare(const Image &source, const Indexed &output, const std::vector<RGBA8> &colors,
+                            uint32_t what = KMG_ERROR_RGB | KMG_ERROR_LAB) const
+    {
+        if (source.dims != output.dims) throw Error(KMG_ERR_INVALID_ARGUMENT, "compare: the images differ in size");
+        kmg_error_stats s;
+        const void *idx = output.format == KMG_FORMAT_INDEX8 ? static_cast<const void *>(output.index8.data())
+                                                             : static_cast<const void *>(output.index16.data());
+        check(kmg_compare(single(), bytes(source), idx, source.dims.first, source.dims.second, output.format,
+                          reinterpret_cast<const uint8_t *>(colors.data()), (uint32_t)colors.size(), what, &s));
+        return s;
+    }
+    static double delta_e_rms(const kmg_error_stats &s) { return s.pixels ? std::sqrt((double)s.lab_sse / (4096.0 * (double)s.pixels)) : 0.0; }
+
+    // kmg_reduce_quality: as few colours in [k_min, k_max] as keep the dE76 RMS of the palette step's working image at or below
+    // max_delta_e (target = floor(4096 max_delta_e^2)); k-means only.  The index map and its palette are those of
+    // reduce_indexed(k) for the k chosen; `achieved` = the statistics of the working image at that k.
+    struct Quality {
+        Indexed indexed;
+        kmg_error_stats achieved;
+        bool reached = false;
+    };
+    Quality reduce_quality(const Image &image, double max_delta_e, uint32_t k_min, uint32_t k_max, ReduceMode reduce_mode,
+                           bool alpha_mode = false) const
+    {
+        Quality q;
+        q.indexed = indexed_for(image, k_max, alpha_mode);
+        q.indexed.palette.resize(k_max ? k_max : 1);
+        const double t = std::floor(4096.0 * max_delta_e * max_delta_e);
+        const uint32_t target = t >= 4294967295.0 ? 0xFFFFFFFFu : (t > 0.0 ? (uint32_t)t : 0u);
+        uint32_t n = 0;
+        int reached = 0;
+        check(kmg_reduce_quality(single(), bytes(image), image.dims.first, image.dims.second, k_min, k_max, target, (int)reduce_mode,
+                                 q.indexed.format, reinterpret_cast<uint8_t *>(q.indexed.palette.data()), &n, index_data(q.indexed), &q.achieved,
+                                 &reached));
+        q.indexed.palette.resize(n);
+        q.reached = reached != 0;
+        return q;
+    }
+
     // a batch: whole images per device (a single-device processor takes them one after the other)
     std::vector<Image> reduce_batch(uint32_t color_count, const std::vector<Image> &images, Algorithm algo, ReduceMode reduce_mode) const
     {
@@ -209,7 +262,7 @@ private:
     static const uint8_t *bytes(const Image &im) { return reinterpret_cast<const uint8_t *>(im.rgba.data()); }
     kmg_processor *single() const
     {
-        if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "index output needs a single-device processor");
+        if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "index output and error statistics need a single-device processor");
         return p_;
     }
     static Indexed indexed_for(const Image &image, uint32_t k, bool alpha_mode)

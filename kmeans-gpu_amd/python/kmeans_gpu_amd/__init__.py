@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -72,6 +72,52 @@ class Options(C.Structure):             # include/kmeans_hip.h kmg_options
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("shrink_max_dim", C.c_uint32),
                 ("max_iterations", C.c_uint32), ("check_period", C.c_uint32), ("convergence", C.c_float),
                 ("strategy", C.c_int32), ("alpha_cutoff", C.c_uint32)]
+
+
+ERROR_RGB, ERROR_LAB = 1, 2             # include/kmeans_hip.h KMG_ERROR_*: the parts of an ErrorStats record
+
+
+class ErrorStats(C.Structure):          # include/kmeans_hip.h kmg_error_stats: 14 x uint64, exact integers
+    _fields_ = [("pixels", C.c_uint64), ("changed", C.c_uint64), ("invalid", C.c_uint64), ("sse", C.c_uint64 * 3),
+                ("sad", C.c_uint64 * 3), ("max_abs", C.c_uint64 * 3), ("lab_sse", C.c_uint64), ("lab_max", C.c_uint64)]
+
+    def as_tuple(self):
+        """the 14 integers in the order of the C struct"""
+        return (int(self.pixels), int(self.changed), int(self.invalid), *map(int, self.sse), *map(int, self.sad),
+                *map(int, self.max_abs), int(self.lab_sse), int(self.lab_max))
+
+    @classmethod
+    def from_array(cls, a):
+        """from 14 uint64 (a record read back from device memory)"""
+        return cls.from_buffer_copy(np.ascontiguousarray(a, np.uint64).reshape(14).tobytes())
+
+    @property
+    def mse(self):
+        """per-channel mean squared error (R, G, B), host floats from the integer sums; nan without counted pixels"""
+        n = int(self.pixels)
+        return tuple(int(v) / n if n else float("nan") for v in self.sse)
+
+    @property
+    def psnr(self):
+        """10 log10(255^2 / mean of the three channel MSEs) in dB; inf for identical images"""
+        n = int(self.pixels)
+        if not n:
+            return float("nan")
+        m = sum(int(v) for v in self.sse) / (3.0 * n)
+        return float("inf") if m == 0 else 10.0 * float(np.log10(65025.0 / m))
+
+    @property
+    def delta_e_rms(self):
+        """root mean square dE76 on the 1/64 grid: sqrt(lab_sse / (4096 pixels))"""
+        n = int(self.pixels)
+        return float(np.sqrt(int(self.lab_sse) / (4096.0 * n))) if n else float("nan")
+
+    @property
+    def delta_e_max(self):
+        return float(np.sqrt(int(self.lab_max) / 4096.0))
+
+    def __repr__(self):
+        return "ErrorStats" + repr(self.as_tuple())
 
 
 # kmg_options.strategy (include/kmeans_hip.h KMG_STRATEGY_*): results are identical either way, only the time differs
@@ -146,7 +192,7 @@ SYMBOLS = [
     "kmg_lloyd_update", "kmg_lloyd_assign_update", "kmg_lloyd_set_cell_share", "kmg_lloyd_labels_from_tables",
     "kmg_lloyd_table_buffers", "kmg_lloyd_accumulate_into", "kmg_lloyd_labels_from_tables_update", "kmg_lloyd_histogram_buffer", "kmg_lloyd_rebuild_from_histogram", "kmg_debug_block_counts", "kmg_debug_idle_blocks", "kmg_debug_encode_table_check", "kmg_debug_division_check", "kmg_lloyd_converged_count", "kmg_lloyd_iterate", "kmg_lloyd_flush", "kmg_lloyd_run", "kmg_dev_apply", "kmg_apply_plan_create", "kmg_apply_plan_run", "kmg_apply_plan_destroy", "kmg_apply_plan_status",
     "kmg_find_indexed", "kmg_reduce_indexed", "kmg_apply_plan_create_format", "kmg_dev_apply_format",
-    "kmg_dither_threshold",
+    "kmg_dither_threshold", "kmg_dev_compare", "kmg_compare", "kmg_reduce_quality",
     "kmg_default_group_options", "kmg_group_create", "kmg_group_unique_id", "kmg_group_create_rank", "kmg_group_destroy",
     "kmg_group_info", "kmg_group_processor", "kmg_group_stream", "kmg_group_palette", "kmg_group_find", "kmg_group_reduce",
     "kmg_group_reduce_batch", "kmg_group_lloyd_create", "kmg_group_lloyd_destroy", "kmg_group_lloyd_bind",
@@ -256,6 +302,10 @@ def lib():
     L.kmg_processor_set_strategy.argtypes = [vp, C.c_int]
     L.kmg_processor_set_alpha_cutoff.argtypes = [vp, C.c_uint32]
     L.kmg_dev_alpha_compact.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, u8p, vp, vp]
+    L.kmg_dev_compare.argtypes = [vp, u8p, vp, C.c_uint64, C.c_int, u8p, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+    L.kmg_compare.argtypes = [vp, u8p, vp, C.c_uint32, C.c_uint32, C.c_int, u8p, C.c_uint32, C.c_uint32, C.POINTER(ErrorStats)]
+    L.kmg_reduce_quality.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, u8p,
+                                     C.POINTER(C.c_uint32), vp, C.POINTER(ErrorStats), C.POINTER(C.c_int)]
     L.kmg_default_group_options.argtypes = [C.POINTER(GroupOptions)]
     L.kmg_default_group_options.restype = None
     L.kmg_group_create.argtypes = [C.POINTER(GroupOptions), C.POINTER(vp)]
@@ -510,6 +560,55 @@ class ImageProcessor:
         _check(lib().kmg_reduce_indexed(self._h, _np_ptr(img), w, h, int(color_count), int(algo), int(reduce_mode), int(fmt), _np_ptr(pal),
                                         C.byref(cnt), out.ctypes.data_as(C.c_void_p)))
         return pal[:cnt.value].copy(), out
+
+    # ---- error statistics and the quality-targeted colour count (include/kmeans_hip.h kmg_error_stats) --------
+    def compare(self, src, out, palette=None, what=ERROR_RGB | ERROR_LAB):
+        """kmg_compare: the ErrorStats of `out` against the image `src`.  out: a (height, width, 4) uint8 image, or -- with
+        `palette` (n, 4) -- a (height, width) uint8 / uint16 index map into it.  Uses the processor's alpha_cutoff: a pixel counts
+        iff the source's alpha reaches it."""
+        img = _image(src)
+        h, w = img.shape[:2]
+        o = np.ascontiguousarray(out)
+        if palette is None:
+            if o.dtype != np.uint8 or o.shape != img.shape:
+                raise ValueError("out must be a uint8 image of the source's shape (or an index map, with palette=)")
+            fmt, pal, k = OutputFormat.RGBA8, None, 0
+        else:
+            if o.shape != (h, w) or o.dtype not in (np.uint8, np.uint16):
+                raise ValueError("out must be a (height, width) uint8 or uint16 index map")
+            pal = np.ascontiguousarray(palette, np.uint8).reshape(-1, 4)
+            fmt, k = (OutputFormat.Index8 if o.dtype == np.uint8 else OutputFormat.Index16), pal.shape[0]
+        stats = ErrorStats()
+        _check(lib().kmg_compare(self._h, _np_ptr(img), _np_ptr(o), w, h, int(fmt), _np_ptr(pal) if pal is not None else None, k,
+                                 int(what), C.byref(stats)))
+        return stats
+
+    def compare_device(self, d_src, d_out, n_pixels, d_stats, format=OutputFormat.RGBA8, palette=None, alpha_cutoff=0,
+                       what=ERROR_RGB | ERROR_LAB, stream=0):
+        """kmg_dev_compare: COMBINES the statistics of n_pixels pixels into the 14 uint64 at d_stats (device; the caller zeroes them
+        for a fresh record).  Only enqueues; palette: host (n, 4) uint8 for the index formats."""
+        pal = None if palette is None else np.ascontiguousarray(palette, np.uint8).reshape(-1, 4)
+        _check(lib().kmg_dev_compare(self._h, C.c_void_p(d_src), C.c_void_p(d_out), int(n_pixels), int(format),
+                                     _np_ptr(pal) if pal is not None else None, pal.shape[0] if pal is not None else 0,
+                                     int(alpha_cutoff), int(what), C.c_void_p(d_stats), C.c_void_p(stream)))
+
+    def reduce_quality(self, image, max_delta_e, k_min=2, k_max=256, reduce_mode=ReduceMode.Replace, indexed=False):
+        """kmg_reduce_quality: as few colours in [k_min, k_max] as keep the dE76 RMS of the palette step's working image at or below
+        max_delta_e (target = floor(4096 max_delta_e^2)).  Returns (k, colors (k, 4) in index order, image or index map, ErrorStats
+        of the working image at k, reached)."""
+        img = _image(image)
+        h, w = img.shape[:2]
+        target = min(int(np.floor(4096.0 * float(max_delta_e) * float(max_delta_e))), 0xFFFFFFFF)
+        if indexed:
+            fmt = self._index_format(int(k_max))
+            out = np.empty((h, w), np.uint8 if fmt == OutputFormat.Index8 else np.uint16)
+        else:
+            fmt, out = OutputFormat.RGBA8, _result(img, None)
+        pal = np.empty((max(int(k_max), 1), 4), np.uint8)
+        cnt, reached, stats = C.c_uint32(), C.c_int(), ErrorStats()
+        _check(lib().kmg_reduce_quality(self._h, _np_ptr(img), w, h, int(k_min), int(k_max), target, int(reduce_mode), int(fmt), _np_ptr(pal),
+                                        C.byref(cnt), out.ctypes.data_as(C.c_void_p), C.byref(stats), C.byref(reached)))
+        return int(cnt.value), pal[:cnt.value].copy(), out, stats, bool(reached.value)
 
     # ---- device-pointer helpers (torch tensors supply the memory) -------------------------
     def rgb_to_lab(self, d_rgba, n_pixels, d_lab3, stream=0):

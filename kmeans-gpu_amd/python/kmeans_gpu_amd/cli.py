@@ -12,6 +12,11 @@ pixels whose alpha is at least N shape the palette, and the output keeps the inp
 colours) instead of RGBA.  In alpha mode the pixels below the cutoff take one more, fully transparent entry (tRNS 0), so
 255 colours at most.
 
+`reduce` and `find` also take `--report`: after the call one line with the error of the output against the input (pixels counted,
+per-channel MSE, PSNR, dE76 RMS and max; kmg_compare).  `reduce --max-error DE [--min-colors A]` picks the colour count itself: as
+few colours between A (default 2) and `-c` as keep the dE76 RMS of the palette step's working image at or below DE
+(kmg_reduce_quality, k-means only); the line then also gives the count chosen and whether the target was reached.
+
 Image decoding/encoding (the `image` crate in the reference) is done with Pillow.  One flag the reference does not have:
 `--devices 0,1,...` (before the sub-command) runs the same operation over several GPUs of the node (kmg_group_*: the image
 tiled in row bands, same bytes).
@@ -140,6 +145,26 @@ def validate_alpha_cutoff(s):
     return v
 
 
+def validate_max_error(s):
+    try:
+        v = float(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid value '{s}': not a number")
+    if not 0.0 <= v <= 1000.0:
+        raise argparse.ArgumentTypeError(f"{v} is not in 0..=1000")
+    return v
+
+
+def report_line(stats, chosen=None, reached=None):
+    """the one line of --report / --max-error (an ErrorStats of the output against the input)"""
+    mse = stats.mse
+    line = (f"Error: pixels={int(stats.pixels)} mse=({mse[0]:.3f},{mse[1]:.3f},{mse[2]:.3f}) psnr={stats.psnr:.2f}dB "
+            f"dE76 rms={stats.delta_e_rms:.3f} max={stats.delta_e_max:.3f}")
+    if chosen is not None:
+        line += f" colors={chosen} target {'reached' if reached else 'not reached'}"
+    return line
+
+
 def validate_devices(s):
     try:
         devices = [int(v) for v in s.split(",")]
@@ -178,9 +203,29 @@ def main(argv=None):
     for s in (f, r):
         s.add_argument("--indexed", action="store_true",
                        help="write a palette-mode PNG (an index per pixel) instead of RGBA; at most 256 colours, 255 with --alpha-cutoff")
+        s.add_argument("--report", action="store_true",
+                       help="print one line with the error of the output against the input: pixels, MSE per channel, PSNR, dE76 RMS and max")
+    r.add_argument("--max-error", type=validate_max_error, default=None, metavar="DE",
+                   help="choose the colour count: as few colours (at most -c) as keep the dE76 RMS of the shrunk image at or below DE; k-means only")
+    r.add_argument("--min-colors", type=validate_k, default=None, metavar="A", help="lower bound of --max-error's search (default 2)")
     args = ap.parse_args(argv)
     if args.devices and args.alpha_cutoff:
         ap.error("--alpha-cutoff is not supported with --devices")
+    report = getattr(args, "report", False)
+    max_error = getattr(args, "max_error", None)
+    if report and args.devices:
+        ap.error("--report is not supported with --devices")
+    if max_error is not None:
+        if args.devices:
+            ap.error("--max-error is not supported with --devices")
+        if args.algo != "kmeans":
+            ap.error("--max-error searches the k-means colour count: -a octree has no such knob")
+        if args.min_colors is None:
+            args.min_colors = min(2, args.colorcount)
+        if args.min_colors > args.colorcount:
+            ap.error(f"--min-colors {args.min_colors} is above -c {args.colorcount}")
+    elif getattr(args, "min_colors", None) is not None:
+        ap.error("--min-colors belongs to --max-error")
     indexed = getattr(args, "indexed", False)
     if indexed:
         n = args.colorcount if args.command == "reduce" else args.palette.shape[0]
@@ -211,15 +256,31 @@ def main(argv=None):
         elif indexed and args.command == "find":
             index = proc.find_indexed(image, args.palette, _MODES[args.mode])
             save_indexed(out_path, args.palette, index, transparent=bool(args.alpha_cutoff))
+            if report:
+                print(report_line(proc.compare(image, index, palette=args.palette)))
+        elif max_error is not None:                      # the colour count from the quality target; -c is the upper bound
+            k, colors, out, _, reached = proc.reduce_quality(image, max_error, args.min_colors, args.colorcount, _MODES[args.mode],
+                                                             indexed=indexed)
+            if indexed:
+                save_indexed(out_path, colors, out, transparent=bool(args.alpha_cutoff))
+            else:
+                _save(reduce_file_path(args.colorcount, args.algo, args.mode, args.output, args.input), out)
+            print(report_line(proc.compare(image, out, palette=colors if indexed else None), chosen=k, reached=reached))
         elif indexed:
             colors, index = proc.reduce_indexed(args.colorcount, image, _ALGOS[args.algo], _MODES[args.mode])
             save_indexed(out_path, colors, index, transparent=bool(args.alpha_cutoff))
+            if report:
+                print(report_line(proc.compare(image, index, palette=colors)))
         elif args.command == "find":                     # main.rs:74-98
             out = proc.find(image, args.palette, _MODES[args.mode])
             _save(find_file_path(args.mode, args.output, args.input), out)
+            if report:
+                print(report_line(proc.compare(image, out)))
         else:                                            # main.rs:100-125
             out = proc.reduce(args.colorcount, image, _ALGOS[args.algo], _MODES[args.mode])
             _save(reduce_file_path(args.colorcount, args.algo, args.mode, args.output, args.input), out)
+            if report:
+                print(report_line(proc.compare(image, out)))
     return 0
 
 

@@ -63,6 +63,24 @@ pub const KMG_FORMAT_RGBA8: c_int = 0;
 pub const KMG_FORMAT_INDEX8: c_int = 1;
 pub const KMG_FORMAT_INDEX16: c_int = 2;
 
+/// `KMG_ERROR_*`: the parts of a `kmg_error_stats` record a comparison computes.
+pub const KMG_ERROR_RGB: u32 = 1;
+pub const KMG_ERROR_LAB: u32 = 2;
+
+/// `kmg_error_stats` (include/kmeans_hip.h): 14 x u64, exact integer sums and maxima of an output against its source.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct kmg_error_stats {
+    pub pixels: u64,
+    pub changed: u64,
+    pub invalid: u64,
+    pub sse: [u64; 3],
+    pub sad: [u64; 3],
+    pub max_abs: [u64; 3],
+    pub lab_sse: u64,
+    pub lab_max: u64,
+}
+
 extern "C" {
     pub fn kmg_last_error() -> *const c_char;
     pub fn kmg_version() -> *const c_char;
@@ -130,6 +148,36 @@ extern "C" {
         out_palette_rgba: *mut u8,
         out_count: *mut u32,
         out_index: *mut (),
+    ) -> c_int;
+    // error statistics of an output against its source (host buffers; `out` holds 4, 1 or 2 bytes per pixel for `format`) and the
+    // colour count chosen by a quality target: no counterpart in the reference
+    pub fn kmg_compare(
+        p: *mut kmg_processor,
+        src_rgba: *const u8,
+        out: *const (),
+        width: u32,
+        height: u32,
+        format: c_int,
+        palette_rgba: *const u8,
+        k: u32,
+        what: u32,
+        stats: *mut kmg_error_stats,
+    ) -> c_int;
+    pub fn kmg_reduce_quality(
+        p: *mut kmg_processor,
+        rgba: *const u8,
+        width: u32,
+        height: u32,
+        k_min: u32,
+        k_max: u32,
+        target: u32,
+        mode: c_int,
+        format: c_int,
+        out_palette_rgba: *mut u8,
+        out_count: *mut u32,
+        out: *mut (),
+        achieved: *mut kmg_error_stats,
+        reached: *mut c_int,
     ) -> c_int;
     // ImageProcessor::new over a device list (the reference is single-device: lib.rs:38-65) and the same three calls, the image
     // tiled in row bands over the devices, the k x 4 sums of a sharded Lloyd loop all-reduced by RCCL inside the library

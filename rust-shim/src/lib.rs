@@ -137,6 +137,106 @@ impl ImageProcessor {
     }
 }
 
+/// `kmg_error_stats`: exact integer error sums of an output against its source (include/kmeans_hip.h).
+pub use ffi::kmg_error_stats as ErrorStats;
+
+impl ErrorStats {
+    /// root mean square dE76 on the 1/64 Lab grid
+    pub fn delta_e_rms(&self) -> f64 {
+        if self.pixels == 0 {
+            return 0.0;
+        }
+        (self.lab_sse as f64 / (4096.0 * self.pixels as f64)).sqrt()
+    }
+
+    /// per-channel mean squared error (R, G, B)
+    pub fn mse(&self) -> [f64; 3] {
+        let n = self.pixels.max(1) as f64;
+        [self.sse[0] as f64 / n, self.sse[1] as f64 / n, self.sse[2] as f64 / n]
+    }
+}
+
+/// What `reduce_quality` returns: the colour count it chose, the palette in index order, the reduced image, the statistics of
+/// the palette step's working image at that count, and whether the target was reached.
+pub struct QualityReduction {
+    pub color_count: u32,
+    pub colors: Vec<RGBA8>,
+    pub image: Image<Vec<RGBA8>>,
+    pub achieved: ErrorStats,
+    pub reached: bool,
+}
+
+impl ImageProcessor {
+    fn single(&self) -> Result<*mut ffi::kmg_processor> {
+        if !self.group.is_null() {
+            return Err(anyhow!("error statistics need a single-device processor"));
+        }
+        Ok(self.raw)
+    }
+
+    /// `kmg_compare` of two RGBA8 images of the same size: RGB and Lab statistics over the pixels whose source alpha reaches the
+    /// processor's alpha cutoff.  No counterpart in the reference.
+    pub fn compare<C: Container, D: Container>(&self, source: &Image<C>, output: &Image<D>) -> Result<ErrorStats> {
+        let (width, height) = source.dimensions();
+        if output.dimensions() != (width, height) {
+            return Err(anyhow!("compare: the images differ in size"));
+        }
+        let mut stats = ErrorStats::default();
+        check(unsafe {
+            ffi::kmg_compare(
+                self.single()?,
+                source.as_bytes().as_ptr(),
+                output.as_bytes().as_ptr() as *const (),
+                width,
+                height,
+                ffi::KMG_FORMAT_RGBA8,
+                std::ptr::null(),
+                0,
+                ffi::KMG_ERROR_RGB | ffi::KMG_ERROR_LAB,
+                &mut stats,
+            )
+        })?;
+        Ok(stats)
+    }
+
+    /// `kmg_reduce_quality`: `reduce` with as few colours in `[k_min, k_max]` as keep the dE76 RMS of the shrunk image at or below
+    /// `max_delta_e` (k-means only).  No counterpart in the reference.
+    pub fn reduce_quality<C: Container>(
+        &self,
+        image: &Image<C>,
+        max_delta_e: f64,
+        k_min: u32,
+        k_max: u32,
+        reduce_mode: &ReduceMode,
+    ) -> Result<QualityReduction> {
+        let (width, height) = image.dimensions();
+        let mut out = vec![RGBA8::default(); width as usize * height as usize];
+        let mut colors = vec![RGBA8::default(); k_max.max(1) as usize];
+        let target = (4096.0 * max_delta_e * max_delta_e).floor().clamp(0.0, u32::MAX as f64) as u32;
+        let (mut count, mut reached, mut achieved) = (0u32, 0 as c_int, ErrorStats::default());
+        check(unsafe {
+            ffi::kmg_reduce_quality(
+                self.single()?,
+                image.as_bytes().as_ptr(),
+                width,
+                height,
+                k_min,
+                k_max,
+                target,
+                reduce_mode.as_c(),
+                ffi::KMG_FORMAT_RGBA8,
+                colors.as_mut_ptr() as *mut u8,
+                &mut count,
+                out.as_mut_ptr() as *mut (),
+                &mut achieved,
+                &mut reached,
+            )
+        })?;
+        colors.truncate(count as usize);
+        Ok(QualityReduction { color_count: count, colors, image: Image::new((width, height), out), achieved, reached: reached != 0 })
+    }
+}
+
 impl Drop for ImageProcessor {
     fn drop(&mut self) {
         unsafe {
