@@ -522,6 +522,86 @@ KMG_API int kmg_reduce_quality(kmg_processor *p, const uint8_t *rgba, uint32_t w
                                uint32_t target, int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out,
                                kmg_error_stats *achieved, int *reached);
 
+/* ======================= frame sequences: a shared palette, delta frames ==================
+ * What an indexed-colour encoder does with many frames (an animation, a sprite sheet, a set of related images): ONE palette for
+ * all of them, and per frame the index map of the pixels that changed.  No counterpart in the reference.
+ *
+ * The working sequence.  For frame i, in the order of the kmg_sequence_add* calls:
+ *   S_i = the frame after the shrink of kmg_options.shrink_max_dim, exactly as kmg_palette shrinks it (frames may differ in size)
+ *   K_i = the kept pixels of S_i in raster order (kmg_options.alpha_cutoff, read when the add starts; 0: all of them)
+ *   W   = K_0 || K_1 || ...
+ * The centroids of a sequence are those the default pipeline (initialisation + Lloyd loop: max_iterations, check_period,
+ * convergence of the processor) gives W as an image of
+ *   (sw, sh) of S_0   when exactly one frame was added and every pixel of it was kept -- kmg_palette / kmg_reduce_indexed of
+ *                     that frame, byte for byte;
+ *   |W| x 1           otherwise (the rule of alpha mode, see kmg_options: c_0 = W[floor(|W| * 0.5625f)], ties over W's indices).
+ * A frame without a kept pixel counts as a frame and adds nothing.  |W| = 0 at _centroids / _palette / _output_begin:
+ * KMG_ERR_INVALID_ARGUMENT ("no pixel reaches alpha_cutoff").  An add that would make |W| >= 2^32 is refused with
+ * KMG_ERR_UNSUPPORTED and leaves the sequence as it was.  KMG_ALGO_KMEANS only.  _centroids returns the Lloyd loop's order, the
+ * one the index maps refer to; _palette converts and sorts as kmg_palette does.  Every call is a new Lloyd problem on W.
+ * _add_device reads the frame from DEVICE memory on `stream`; both adds return when W holds the frame (they synchronise).
+ * _clear empties W and the frame count; _info: out[0] = frames added, out[1] = |W|.
+ *
+ * A kmg_sequence is NOT re-entrant: one thread at a time per sequence, any number of sequences per processor (each has its own
+ * stream and blocks).  The processor outlives its sequences.                                                                   */
+typedef struct kmg_sequence kmg_sequence;
+KMG_API int kmg_sequence_create(kmg_processor *p, kmg_sequence **out);
+KMG_API void kmg_sequence_destroy(kmg_sequence *s);
+KMG_API int kmg_sequence_add(kmg_sequence *s, const uint8_t *rgba, uint32_t width, uint32_t height);
+KMG_API int kmg_sequence_add_device(kmg_sequence *s, const uint8_t *d_rgba, uint32_t width, uint32_t height, void *stream);
+KMG_API int kmg_sequence_clear(kmg_sequence *s);
+KMG_API int kmg_sequence_info(kmg_sequence *s, uint64_t out[2]);
+KMG_API int kmg_sequence_centroids(kmg_sequence *s, uint32_t k, float *centroids4);
+KMG_API int kmg_sequence_palette(kmg_sequence *s, uint32_t k, uint8_t *out_rgba, uint32_t *out_count);
+
+/* The delta pass: an index map against the canvas of what is shown.  For the pixel (x, row0 + r) of the band, c = its index in
+ * d_index, v = its index in d_canvas:
+ *   c == v:   delta = k                 (the transparent slot: "over" blending keeps what is shown)
+ *   c != v:   delta = c, changed += 1, the box takes in (x, row0 + r), and cleared += 1 when c == k
+ *   always:   canvas = c
+ * All integers, no order: the pass COMBINES into *d_info as it stands -- the two sums are added, x0 / y0 are minned, x1 / y1 are
+ * maxed (the convention of kmg_dev_compare) -- so the bands of one frame may run in any order, on any streams, and end in the same
+ * record.  The caller writes the fresh record {0, 0, 0xFFFFFFFF, 0xFFFFFFFF, 0, 0} before a frame; a record that is still fresh
+ * afterwards (changed = 0) has no box.  cleared > 0 means a pixel that showed a colour turns transparent: a delta map cannot
+ * express that under "over" blending, the frame has to be sent in full.
+ * d_index, d_canvas, d_delta: DEVICE, width * rows (< 2^32) elements of `format` each, tightly packed, aligned to their element
+ * only (the 16-byte accesses of the pass need the three pointers at one offset within 16 bytes; otherwise it goes element by
+ * element); d_delta overlaps neither of the others.  d_info: DEVICE, 8-byte aligned.  KMG_FORMAT_INDEX8 needs k <= 255 (slot k
+ * must fit), KMG_FORMAT_INDEX16 takes any k <= KMG_MAX_K; KMG_FORMAT_RGBA8, k = 0, zero width or rows, a NULL pointer:
+ * KMG_ERR_INVALID_ARGUMENT.  Indices above k are compared like any other.  Only enqueues work on `stream`.                      */
+typedef struct kmg_frame_delta {      /* 32 bytes, no padding */
+    uint64_t changed;                 /* pixels whose index differs from the canvas                                */
+    uint64_t cleared;                 /* of those: the frame's index is the transparent slot k                     */
+    uint32_t x0, y0;                  /* min x, min y of the changed pixels   (fresh record: 0xFFFFFFFF)           */
+    uint32_t x1, y1;                  /* max x + 1, max y + 1                 (fresh record: 0)                    */
+} kmg_frame_delta;
+KMG_API int kmg_dev_frame_delta(kmg_processor *p, const void *d_index, void *d_canvas, uint32_t width, uint32_t rows, uint32_t row0,
+                                int format, uint32_t k, void *d_delta, kmg_frame_delta *d_info, void *stream);
+
+/* Frame output with the sequence's palette, on HOST buffers.
+ *   _output_begin   the centroids of W at k (as _centroids); out_palette_rgba (k x 4 bytes) / *out_count: the palette in index
+ *                   order, exactly as kmg_reduce_indexed returns it; one apply plan (kmg_apply_plan_create_format with
+ *                   n_pixels_hint = width * height, the processor's alpha_cutoff as it is now), the frame buffers and a canvas
+ *                   filled with k.  Mode and format: the rules of the index formats (meld has no index; KMG_FORMAT_INDEX8 needs
+ *                   k <= 255 here, alpha mode or not: the canvas uses slot k).  KMG_FORMAT_RGBA8 takes every mode, but no delta.
+ *                   A second _begin ends the first.
+ *   _output_frame   rgba: a frame of width x height.  Without KMG_FRAME_DELTA: out = I_t, the full map -- byte for byte what
+ *                   kmg_dev_apply_format writes for the frame with these centroids; each frame is an image of its own (row0 = 0:
+ *                   Bayer coordinates and diffusion start over); info and is_full are optional (a fresh record, 1); the canvas
+ *                   becomes I_t.  With KMG_FRAME_DELTA: out = the delta map of I_t against the canvas, *info = its record,
+ *                   *is_full = 0 -- unless info->cleared > 0: then out = I_t and *is_full = 1, *info as measured.  The first
+ *                   frame needs no special case: against a canvas of k the delta IS I_0.  Replaying the delta maps with "over"
+ *                   (index k keeps the pixel) and the full maps with "source" reproduces every I_t.
+ *                   No output open, KMG_FRAME_DELTA with KMG_FORMAT_RGBA8 or without info / is_full: KMG_ERR_INVALID_ARGUMENT.
+ *   _output_end     returns the plan and the buffers; so does _destroy.
+ * Frames may be added while an output is open: they do not affect it.                                                         */
+#define KMG_FRAME_DELTA 1u
+KMG_API int kmg_sequence_output_begin(kmg_sequence *s, uint32_t k, int mode, int format, uint32_t width, uint32_t height,
+                                      uint8_t *out_palette_rgba, uint32_t *out_count);
+KMG_API int kmg_sequence_output_frame(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, void *out, kmg_frame_delta *info,
+                                      int *is_full);
+KMG_API int kmg_sequence_output_end(kmg_sequence *s);
+
 /* ======================= several GPUs: a group of devices ================================
  * ImageProcessor::new (core/src/lib.rs:38-65) picks ONE adapter; the reference has no multi-device path.  A kmg_group is the
  * same constructor over a device LIST: one kmg_processor, one compute stream and one RCCL communicator rank per device.

@@ -67,14 +67,15 @@ int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t 
     return KMG_OK;
 }
 
+}  // namespace
+
 // operations.rs:15-88 extract_palette_kmeans on a working image -> host centroid table: a new Lloyd problem of k centroids.
 // d_labels (optional): the u32 label of every pixel of the working image under the final centroids (find_centroid.wgsl:15-44, the
 // label KMG_MODE_REPLACE gives the pixel).
-int palette_of_working(kmg_processor *p, const WorkingImage &wi, uint32_t k, hipStream_t st, float *c4, uint32_t *d_labels = nullptr)
+int kmg::palette_of_working(kmg_processor *p, const uint8_t *src, uint32_t sw, uint32_t sh, uint32_t k, hipStream_t st, float *c4,
+                            uint32_t *d_labels)
 {
     int rc;
-    const uint8_t *src = wi.src;
-    const uint32_t sw = wi.sw, sh = wi.sh;
     LloydGuard g;
     if ((rc = lloyd_create_impl(p, k, &g.s, st)) != KMG_OK) return rc;
     if ((rc = kmg_lloyd_init_centroids(g.s, src, sw, sh, st)) != KMG_OK) return rc;   // operations.rs:73
@@ -96,6 +97,13 @@ int palette_of_working(kmg_processor *p, const WorkingImage &wi, uint32_t k, hip
     }
     if (d_labels && (rc = kmg_lloyd_labels(g.s, src, (uint64_t)sw * sh, d_labels, st)) != KMG_OK) return rc;
     return KMG_OK;
+}
+
+namespace {
+
+int palette_of_working(kmg_processor *p, const WorkingImage &wi, uint32_t k, hipStream_t st, float *c4, uint32_t *d_labels = nullptr)
+{
+    return kmg::palette_of_working(p, wi.src, wi.sw, wi.sh, k, st, c4, d_labels);
 }
 
 int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff,

@@ -425,6 +425,11 @@ static int run_diffuse(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, ui
     return KMG_OK;
 }
 
+void kmg::apply_plan_restart(kmg_apply_plan *pl)
+{
+    if (pl) pl->drows = 0;
+}
+
 // kmg_dev_apply and kmg_apply_plan_status: did any diffusion run of the plan time out?  (Read after the last run has completed.)
 static int diffuse_status(kmg_apply_plan *pl)
 {

@@ -55,6 +55,14 @@ int dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows
 // the box of the index formats (include/kmeans_hip.h at kmg_output_format)
 constexpr float kIndexBoxLmin = -100.0f, kIndexBoxLmax = 200.0f, kIndexBoxAB = 300.0f;
 
+// The k-means palette step on a working image (kmg_api.hip): sw x sh pixels in device memory -> host centroid table, a new Lloyd
+// problem of k centroids (initialisation + loop with the processor's options).  Synchronises `st`.  d_labels: optional label map.
+int palette_of_working(kmg_processor *p, const uint8_t *d_src, uint32_t sw, uint32_t sh, uint32_t k, hipStream_t st, float *centroids4,
+                       uint32_t *d_labels = nullptr);
+// KMG_MODE_DIFFUSE: the plan's next run starts a new image (row0 = 0, zero error above it) instead of continuing the last one
+// (kmg_apply.hip).  The caller has every earlier run of the plan behind it on the stream of the next one.  Other modes: nothing.
+void apply_plan_restart(kmg_apply_plan *plan);
+
 // An image between a caller's (pageable) buffer and the device, ordered on `st` (kmg_api.hip): small images asynchronously,
 // large ones as synchronous row-range copies on several streams of the processor.
 hipError_t copy_host_image(kmg_processor *p, void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t st);

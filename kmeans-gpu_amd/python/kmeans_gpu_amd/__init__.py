@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "Sequence", "FrameDelta", "FRAME_DELTA", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -120,6 +120,37 @@ class ErrorStats(C.Structure):          # include/kmeans_hip.h kmg_error_stats: 
         return "ErrorStats" + repr(self.as_tuple())
 
 
+FRAME_DELTA = 1                         # include/kmeans_hip.h KMG_FRAME_DELTA
+
+
+class FrameDelta(C.Structure):          # include/kmeans_hip.h kmg_frame_delta: 32 bytes
+    _fields_ = [("changed", C.c_uint64), ("cleared", C.c_uint64), ("x0", C.c_uint32), ("y0", C.c_uint32),
+                ("x1", C.c_uint32), ("y1", C.c_uint32)]
+
+    FRESH = (0, 0, 0xFFFFFFFF, 0xFFFFFFFF, 0, 0)        # what the caller writes before a frame
+
+    def as_tuple(self):
+        return (int(self.changed), int(self.cleared), int(self.x0), int(self.y0), int(self.x1), int(self.y1))
+
+    @classmethod
+    def from_array(cls, a):
+        """from the 32 bytes of a record read back from device memory (any dtype)"""
+        return cls.from_buffer_copy(np.ascontiguousarray(a).tobytes()[:32])
+
+    @classmethod
+    def fresh_bytes(cls):
+        """the 32 bytes of the fresh record"""
+        return bytes(cls(*cls.FRESH))
+
+    @property
+    def rect(self):
+        """(x0, y0, x1, y1) of the changed pixels, x1 / y1 exclusive; None when nothing changed"""
+        return None if int(self.changed) == 0 else (int(self.x0), int(self.y0), int(self.x1), int(self.y1))
+
+    def __repr__(self):
+        return "FrameDelta" + repr(self.as_tuple())
+
+
 # kmg_options.strategy (include/kmeans_hip.h KMG_STRATEGY_*): results are identical either way, only the time differs
 STRATEGY_AUTO, STRATEGY_SCAN, STRATEGY_TABLE, STRATEGY_MASK_WORDS = 0, 1, 2, 4
 _STRATEGY_NAMES = {"auto": STRATEGY_AUTO, "scan": STRATEGY_SCAN, "brute": STRATEGY_SCAN, "table": STRATEGY_TABLE}
@@ -193,6 +224,9 @@ SYMBOLS = [
     "kmg_lloyd_table_buffers", "kmg_lloyd_accumulate_into", "kmg_lloyd_labels_from_tables_update", "kmg_lloyd_histogram_buffer", "kmg_lloyd_rebuild_from_histogram", "kmg_debug_block_counts", "kmg_debug_idle_blocks", "kmg_debug_encode_table_check", "kmg_debug_division_check", "kmg_lloyd_converged_count", "kmg_lloyd_iterate", "kmg_lloyd_flush", "kmg_lloyd_run", "kmg_dev_apply", "kmg_apply_plan_create", "kmg_apply_plan_run", "kmg_apply_plan_destroy", "kmg_apply_plan_status",
     "kmg_find_indexed", "kmg_reduce_indexed", "kmg_apply_plan_create_format", "kmg_dev_apply_format",
     "kmg_dither_threshold", "kmg_dev_compare", "kmg_compare", "kmg_reduce_quality",
+    "kmg_sequence_create", "kmg_sequence_destroy", "kmg_sequence_add", "kmg_sequence_add_device", "kmg_sequence_clear",
+    "kmg_sequence_info", "kmg_sequence_centroids", "kmg_sequence_palette", "kmg_dev_frame_delta", "kmg_sequence_output_begin",
+    "kmg_sequence_output_frame", "kmg_sequence_output_end",
     "kmg_default_group_options", "kmg_group_create", "kmg_group_unique_id", "kmg_group_create_rank", "kmg_group_destroy",
     "kmg_group_info", "kmg_group_processor", "kmg_group_stream", "kmg_group_palette", "kmg_group_find", "kmg_group_reduce",
     "kmg_group_reduce_batch", "kmg_group_lloyd_create", "kmg_group_lloyd_destroy", "kmg_group_lloyd_bind",
@@ -306,6 +340,19 @@ def lib():
     L.kmg_compare.argtypes = [vp, u8p, vp, C.c_uint32, C.c_uint32, C.c_int, u8p, C.c_uint32, C.c_uint32, C.POINTER(ErrorStats)]
     L.kmg_reduce_quality.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, u8p,
                                      C.POINTER(C.c_uint32), vp, C.POINTER(ErrorStats), C.POINTER(C.c_int)]
+    L.kmg_sequence_create.argtypes = [vp, C.POINTER(vp)]
+    L.kmg_sequence_destroy.argtypes = [vp]
+    L.kmg_sequence_destroy.restype = None
+    L.kmg_sequence_add.argtypes = [vp, u8p, C.c_uint32, C.c_uint32]
+    L.kmg_sequence_add_device.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, vp]
+    L.kmg_sequence_clear.argtypes = [vp]
+    L.kmg_sequence_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.kmg_sequence_centroids.argtypes = [vp, C.c_uint32, f32p]
+    L.kmg_sequence_palette.argtypes = [vp, C.c_uint32, u8p, C.POINTER(C.c_uint32)]
+    L.kmg_dev_frame_delta.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp]
+    L.kmg_sequence_output_begin.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, u8p, C.POINTER(C.c_uint32)]
+    L.kmg_sequence_output_frame.argtypes = [vp, u8p, C.c_uint32, vp, C.POINTER(FrameDelta), C.POINTER(C.c_int)]
+    L.kmg_sequence_output_end.argtypes = [vp]
     L.kmg_default_group_options.argtypes = [C.POINTER(GroupOptions)]
     L.kmg_default_group_options.restype = None
     L.kmg_group_create.argtypes = [C.POINTER(GroupOptions), C.POINTER(vp)]
@@ -470,6 +517,7 @@ class ImageProcessor:
         o.alpha_cutoff = int(alpha_cutoff)
         _check(lib().kmg_processor_create_ex(C.byref(o), C.byref(self._h)))
         self.options = o
+        self._sequences = None          # weak set of the live Sequence objects: closed with the processor, which they need
         _register(self)
 
     def set_alpha_cutoff(self, alpha_cutoff):
@@ -484,6 +532,8 @@ class ImageProcessor:
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
+            for seq in list(getattr(self, "_sequences", None) or ()):
+                seq.close()
             lib().kmg_processor_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -638,6 +688,23 @@ class ImageProcessor:
         for apply()"""
         return ApplyPlan(self, centroids4, mode, n_pixels_hint, stream, format)
 
+    # ---- frame sequences (include/kmeans_hip.h kmg_sequence) ----------------------------------
+    def sequence(self):
+        """kmg_sequence_create: a Sequence -- one palette for many frames, and their index maps as delta frames"""
+        import weakref
+        seq = Sequence(self)
+        if self._sequences is None:
+            self._sequences = weakref.WeakSet()
+        self._sequences.add(seq)
+        return seq
+
+    def frame_delta(self, d_index, d_canvas, width, rows, row0, format, k, d_delta, d_info, stream=0):
+        """kmg_dev_frame_delta: d_delta = the band's indices where they differ from the canvas, k elsewhere; the canvas takes the
+        indices; COMBINES counts and box into the 32-byte record at d_info (device; the caller writes FrameDelta.FRESH before a
+        frame).  Only enqueues."""
+        _check(lib().kmg_dev_frame_delta(self._h, C.c_void_p(d_index), C.c_void_p(d_canvas), int(width), int(rows), int(row0), int(format),
+                                         int(k), C.c_void_p(d_delta), C.c_void_p(d_info), C.c_void_p(stream)))
+
     def debug_block_counts(self):
         """(device blocks allocated with hipMalloc so far, blocks handed out again)"""
         out = (C.c_uint64 * 2)()
@@ -675,6 +742,100 @@ class ImageProcessor:
         v = C.c_uint64()
         _check(lib().kmg_debug_check_meld_masks(self._h, _np_ptr(c), c.shape[0], C.byref(v), C.c_void_p(stream)))
         return int(v.value)
+
+
+class Sequence:
+    """kmg_sequence_*: the working sequence of the frames added so far (each shrunk and, in alpha mode, compacted as the palette
+    step does), its shared palette, and frame output with that palette as full or delta index maps.  Not re-entrant: one thread
+    at a time."""
+
+    def __init__(self, processor):
+        self._p = processor
+        self._h = C.c_void_p()
+        self._out = None                # (k, format, width, height) of the open output
+        _check(lib().kmg_sequence_create(processor.handle, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().kmg_sequence_destroy(self._h)
+            self._h = C.c_void_p()
+            self._out = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add(self, image):
+        """kmg_sequence_add: one more frame, a (height, width, 4) uint8 host image of any size"""
+        img = _image(image)
+        h, w = img.shape[:2]
+        _check(lib().kmg_sequence_add(self._h, _np_ptr(img), w, h))
+
+    def add_device(self, d_rgba, width, height, stream=0):
+        """kmg_sequence_add_device: the same for a frame in device memory (synchronises `stream`)"""
+        _check(lib().kmg_sequence_add_device(self._h, C.c_void_p(d_rgba), int(width), int(height), C.c_void_p(stream)))
+
+    def clear(self):
+        _check(lib().kmg_sequence_clear(self._h))
+
+    def info(self):
+        """(frames added, pixels of the working sequence)"""
+        out = (C.c_uint64 * 2)()
+        _check(lib().kmg_sequence_info(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def centroids(self, k):
+        """kmg_sequence_centroids: (k, 4) float32 in the Lloyd loop's order -- the order the index maps refer to"""
+        out = np.empty((max(int(k), 1), 4), np.float32)
+        _check(lib().kmg_sequence_centroids(self._h, int(k), _np_ptr(out)))
+        return out
+
+    def palette(self, k):
+        """kmg_sequence_palette: (k, 4) uint8, sorted as ImageProcessor.palette sorts"""
+        out = np.empty((max(int(k), 1), 4), np.uint8)
+        cnt = C.c_uint32()
+        _check(lib().kmg_sequence_palette(self._h, int(k), _np_ptr(out), C.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    def output(self, k, mode=ReduceMode.Replace, format=OutputFormat.Index8, width=0, height=0):
+        """kmg_sequence_output_begin: opens the frame output for frames of width x height; returns the palette (k, 4) in index
+        order.  Index k of the maps is the transparent slot."""
+        pal = np.empty((max(int(k), 1), 4), np.uint8)
+        cnt = C.c_uint32()
+        self._out = None
+        _check(lib().kmg_sequence_output_begin(self._h, int(k), int(mode), int(format), int(width), int(height), _np_ptr(pal), C.byref(cnt)))
+        self._out = (int(k), int(format), int(width), int(height))
+        return pal[:cnt.value].copy()
+
+    def frame(self, image, delta=True):
+        """kmg_sequence_output_frame: (map, FrameDelta, is_full).  delta=True: the delta map against the frames shown so far
+        (index k = unchanged), or -- is_full -- the full map when a shown pixel turns transparent; delta=False: the full map."""
+        if self._out is None:
+            raise KmgError(-1, "no output is open (Sequence.output)")
+        k, fmt, w, h = self._out
+        img = _image(image)
+        if img.shape[:2] != (h, w):
+            raise KmgError(-1, f"the frame is {img.shape[1]} x {img.shape[0]}, the output was opened for {w} x {h}")
+        if fmt == OutputFormat.RGBA8:
+            out = np.empty((h, w, 4), np.uint8)
+        else:
+            out = np.empty((h, w), np.uint8 if fmt == OutputFormat.Index8 else np.uint16)
+        info, full = FrameDelta(*FrameDelta.FRESH), C.c_int(1)
+        _check(lib().kmg_sequence_output_frame(self._h, _np_ptr(img), FRAME_DELTA if delta else 0, out.ctypes.data_as(C.c_void_p),
+                                               C.byref(info), C.byref(full)))
+        return out, info, bool(full.value)
+
+    def end_output(self):
+        self._out = None
+        _check(lib().kmg_sequence_output_end(self._h))
 
 
 class ApplyPlan:

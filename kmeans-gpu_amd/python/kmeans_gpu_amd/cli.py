@@ -17,6 +17,11 @@ per-channel MSE, PSNR, dE76 RMS and max; kmg_compare).  `reduce --max-error DE [
 few colours between A (default 2) and `-c` as keep the dE76 RMS of the palette step's working image at or below DE
 (kmg_reduce_quality, k-means only); the line then also gives the count chosen and whether the target was reached.
 
+`sequence -i A.png B.png ... -c K [-m replace|dither|diffuse] [-o out.png] [--alpha-cutoff T] [--no-delta] [--delay-ms 100]`
+quantises several frames of one size with ONE palette (kmg_sequence_*) and writes a palette-mode APNG (kmeans_gpu_amd/apng.py):
+delta frames -- the rectangle of the pixels that changed, blended "over" -- unless --no-delta asks for full frames.  K <= 255: the
+transparent slot takes the last palette entry.
+
 Image decoding/encoding (the `image` crate in the reference) is done with Pillow.  One flag the reference does not have:
 `--devices 0,1,...` (before the sub-command) runs the same operation over several GPUs of the node (kmg_group_*: the image
 tiled in row bands, same bytes).
@@ -125,6 +130,50 @@ def find_file_path(mode, output, inp):                   # main.rs:184-219
     return os.path.join(os.path.dirname(inp), f"{stem}-find-{mode}-{millis}{ext}")
 
 
+def sequence_file_path(k, mode, output, inp):
+    if output:
+        return output
+    stem = os.path.splitext(os.path.basename(inp))[0]
+    return os.path.join(os.path.dirname(inp), f"{stem}-sequence-c{k}-{mode}.png")
+
+
+def validate_delay(s):
+    try:
+        v = int(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid value '{s}': not an integer")
+    if not 0 <= v <= 65535:
+        raise argparse.ArgumentTypeError(f"{v} is not in 0..=65535")
+    return v
+
+
+def run_sequence(args, ap):
+    """the `sequence` sub-command: one palette over all inputs, then every input as a frame of a palette-mode APNG"""
+    from . import OutputFormat, apng
+    frames = [_load(path) for path in args.input]
+    h, w = frames[0].shape[:2]
+    for path, f in zip(args.input, frames):
+        if f.shape[:2] != (h, w):
+            ap.error(f"every input of `sequence` must have one size: {path} is {f.shape[1]}x{f.shape[0]}, {args.input[0]} is {w}x{h}")
+    out_path = sequence_file_path(args.colorcount, args.mode, args.output, args.input[0])
+    with ImageProcessor(alpha_cutoff=args.alpha_cutoff) as proc, proc.sequence() as seq:
+        for f in frames:
+            seq.add(f)
+        colors = seq.output(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h)
+        coded, n_full, n_changed = [], 0, 0
+        for f in frames:
+            index, info, is_full = seq.frame(f, delta=not args.no_delta)
+            coded.append((index, info.rect, is_full))
+            n_full += 1 if is_full else 0
+            n_changed += int(info.changed)
+        seq.end_output()
+    apng.write(out_path, colors, w, h, coded, delay_ms=args.delay_ms)
+    print("Palette: " + ",".join(f"#{c[0]:02X}{c[1]:02X}{c[2]:02X}" for c in colors))
+    print(f"Sequence: {len(frames)} frames of {w}x{h}, {n_full} written in full"
+          + ("" if args.no_delta else f", {n_changed} changed pixels in the delta frames") + f": {out_path}")
+    return 0
+
+
 def validate_size(s):                                       # args.rs:36-38 value_parser!(u32).range(1..=60)
     try:
         v = int(s)
@@ -197,7 +246,14 @@ def main(argv=None):
     r.add_argument("-o", "--output", type=validate_filename)
     r.add_argument("-a", "--algo", choices=list(_ALGOS), default="kmeans")
     r.add_argument("-m", "--mode", choices=list(_MODES), default="replace")
-    for s in (p, f, r):
+    q = sub.add_parser("sequence", help="Reduce several frames of one size with one shared palette; writes a palette-mode APNG")
+    q.add_argument("-c", "--colorcount", type=validate_k, required=True)
+    q.add_argument("-i", "--input", type=validate_filename, nargs="+", required=True)
+    q.add_argument("-o", "--output", type=validate_filename)
+    q.add_argument("-m", "--mode", choices=["replace", "dither", "diffuse"], default="replace")
+    q.add_argument("--no-delta", action="store_true", help="write every frame in full instead of the rectangle of its changes")
+    q.add_argument("--delay-ms", type=validate_delay, default=100, help="display time of every frame in milliseconds (default 100)")
+    for s in (p, f, r, q):
         s.add_argument("--alpha-cutoff", type=validate_alpha_cutoff, default=0,
                        help="1..255: pixels with a lower alpha do not shape the palette, the output keeps the input's alpha")
     for s in (f, r):
@@ -209,6 +265,15 @@ def main(argv=None):
                    help="choose the colour count: as few colours (at most -c) as keep the dE76 RMS of the shrunk image at or below DE; k-means only")
     r.add_argument("--min-colors", type=validate_k, default=None, metavar="A", help="lower bound of --max-error's search (default 2)")
     args = ap.parse_args(argv)
+    if args.command == "sequence":
+        if args.devices:
+            ap.error("`sequence` is not supported with --devices")
+        if args.colorcount > 255:
+            ap.error(f"`sequence` writes a palette APNG of at most 255 colours plus the transparent slot; {args.colorcount} requested")
+        out_path = sequence_file_path(args.colorcount, args.mode, args.output, args.input[0])
+        if not out_path.endswith(".png"):
+            ap.error("`sequence` writes a PNG file")
+        return run_sequence(args, ap)
     if args.devices and args.alpha_cutoff:
         ap.error("--alpha-cutoff is not supported with --devices")
     report = getattr(args, "report", False)
