@@ -132,6 +132,32 @@ typedef struct kmg_options {
  *    kmg_dev_alpha_compact); kmg_group_create refuses alpha_cutoff != 0 (KMG_ERR_INVALID_ARGUMENT).
  * (Options structs of the two previous sizes -- without this field, and without `strategy` -- are accepted and mean 0.)        */
 
+/* kmg_processor_set_fixed_colors -- fixed palette colours: entries the k-means keeps, exactly, and builds the rest around.  No
+ * counterpart in the reference.  F = a list of f RGBA8 colours set on a processor (alpha ignored, duplicates allowed,
+ * f <= KMG_MAX_K); f = 0, the default, keeps the behaviour described everywhere else in this header, byte for byte.
+ * P_j = kmg_palette_to_centroids(F_j): a pinned entry behaves exactly like an entry of a kmg_find palette.
+ *  - Palette step (kmg_palette, kmg_reduce, kmg_reduce_indexed, every palette run of kmg_reduce_quality, kmg_sequence_centroids /
+ *    _palette / _output_begin), k >= f, on the working image W = the n pixels the default pipeline sees, in its order: after the
+ *    shrink, after alpha mode's compaction, after the concatenation of a sequence.
+ *    Initialisation (the reference's farthest-point loop with the first f picks replaced):  c_j = P_j for j < f;
+ *    dist[i] = 1000000.0f;  for j = 1 .. k - 1:  dist[i] = fminf(dist[i], cie94(pixel_i, c_(j-1)))  (pixel first: CIE94 is
+ *    asymmetric), and, when j >= f, c_j = the pixel the arg-max of dist names under the reference's tie rule (inside each block of
+ *    16 consecutive pixels the earliest maximum, folded from Candidate(0, 0.0); across blocks the last block that attains it).
+ *    With f >= 1 no pixel index derived from width and height enters, so (sw, sh) and |W| x 1 give the same centroids.
+ *    Lloyd loop: the reference's, except that for c < f the update leaves the centroid exactly as it is, whatever its count, and
+ *    counts it as converged: the convergence count is f + the count over c >= f (an empty free cluster: not converged, as ever).
+ *    The check at it > 0 && it % check_period == 0 and max_iterations are unchanged.
+ *  - Outputs take the resulting centroid table and are unchanged.  In index order (kmg_reduce_indexed, kmg_sequence_centroids,
+ *    the index maps) the pinned entries are indices 0 .. f - 1, in the order given; kmg_palette sorts by L as always.  The
+ *    palette bytes of a pinned entry are what the output pass writes for P_j (lab_to_rgb.wgsl) -- the "re-encoded bytes" of
+ *    kmg_find_indexed.  That re-encoding is the identity for every one of the 2^24 colours (counted: DESIGN.md 4.10), so
+ *    pinned colours come back byte-exact: palette entry j of the index-order outputs has the R, G, B of F_j and alpha 255.
+ *  - Alpha mode composes: the pins come first, then the kept pixels as ever.
+ *  - KMG_ERR_INVALID_ARGUMENT, nothing written: color_count < f (kmg_reduce_quality: k_min < f); KMG_ALGO_OCTREE while f > 0;
+ *    n > KMG_MAX_K, or a NULL list with n > 0; kmg_group_palette / _reduce / _reduce_batch when a member processor has fixed
+ *    colours set (the group layer has no pinned path).
+ * The call copies the list; n = 0 clears it.  Calls that are already running keep the list they started with.                   */
+
 /* kmg_options.strategy / kmg_processor_set_strategy: which of the library's interchangeable strategies a call takes.  Results are
  * IDENTICAL either way (that is what the tests use the switch for); only the time differs.  The low two bits choose between the
  * per-pixel scans and the colour-table / candidate-list passes for every decision the cost models otherwise make (Lloyd
@@ -161,6 +187,8 @@ KMG_API int kmg_processor_set_strategy(kmg_processor *p, int strategy);
 /* changes kmg_options.alpha_cutoff of a live processor (0 .. 255); calls that are already running keep the value they started
  * with                                                                                                                         */
 KMG_API int kmg_processor_set_alpha_cutoff(kmg_processor *p, uint32_t alpha_cutoff);
+/* sets (n > 0: copies n x 4 bytes) or clears (n = 0) the processor's fixed colours, see above                                     */
+KMG_API int kmg_processor_set_fixed_colors(kmg_processor *p, const uint8_t *rgba, uint32_t n);
 /* Page-locked host memory for images that cross the boundary often (a frame loop): a result buffer from kmg_host_alloc has
  * its pages resident and is copied to by DMA directly -- kmg_reduce of 8192 x 8192 into a fresh pageable buffer spends 30-50 ms
  * in the caller's page faults, 10 ms into one of these.  Plain memory otherwise; release with kmg_host_free.  (No counterpart
@@ -250,6 +278,22 @@ KMG_API int kmg_lloyd_get_centroids(kmg_lloyd *s, float *centroids4, void *strea
  * kmeans++_calc_diff.wgsl): deterministic farthest-point initialisation on the device.       */
 KMG_API int kmg_lloyd_init_centroids(kmg_lloyd *s, const uint8_t *d_rgba, uint32_t width,
                                      uint32_t height, void *stream);
+
+/* The same initialisation with the first n_seeds centroids GIVEN (seeds4: HOST, n_seeds x 4 floats, (L, a, b, ignored), finite):
+ * the loop described at kmg_processor_set_fixed_colors with arbitrary Lab seeds for P -- the running distances start from all the
+ * seeds, centroids n_seeds .. k - 1 are the farthest-point picks that follow.  n_seeds = 0 is kmg_lloyd_init_centroids, bit for
+ * bit; n_seeds > k: KMG_ERR_INVALID_ARGUMENT.  It starts a new problem exactly as kmg_lloyd_init_centroids does (the binding
+ * rules at kmg_lloyd_bind_image).  Seeding is separate from freezing: without kmg_lloyd_set_fixed the seeds move with the first
+ * update (a warm start from the last frame's palette).  Synchronises `stream`.                                                   */
+KMG_API int kmg_lloyd_init_centroids_seeded(kmg_lloyd *s, const uint8_t *d_rgba, uint32_t width, uint32_t height,
+                                            const float *seeds4, uint32_t n_seeds, void *stream);
+/* Freezes centroids 0 .. n_fixed - 1 (n_fixed <= k; default 0): every update this object performs from now on --
+ * kmg_lloyd_update, _assign_update, _iterate, _run, _labels_from_tables_update -- leaves them exactly as they are and counts them
+ * as converged (kmg_lloyd_converged_count includes them).  Their sums are still accumulated and returned in d_acc4.  The value
+ * has reached the device when the call returns (a small blocking copy): it holds for the updates enqueued after it, on any
+ * stream, not for those enqueued before.  Refused (KMG_ERR_INVALID_ARGUMENT) while a cell share is set, like the updates
+ * themselves.                                                                                                                   */
+KMG_API int kmg_lloyd_set_fixed(kmg_lloyd *s, uint32_t n_fixed);
 
 /* The same initialisation for an image sharded in row bands (one kmg_lloyd per band / GPU).  Step j:
  *   kmg_lloyd_init_step      band-local pass for centroid j-1; *d_key (device u64) = arg-max key of

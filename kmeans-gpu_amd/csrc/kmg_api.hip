@@ -73,12 +73,14 @@ int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t 
 // d_labels (optional): the u32 label of every pixel of the working image under the final centroids (find_centroid.wgsl:15-44, the
 // label KMG_MODE_REPLACE gives the pixel).
 int kmg::palette_of_working(kmg_processor *p, const uint8_t *src, uint32_t sw, uint32_t sh, uint32_t k, hipStream_t st, float *c4,
-                            uint32_t *d_labels)
+                            uint32_t *d_labels, const float *fixed4, uint32_t n_fixed)
 {
     int rc;
     LloydGuard g;
+    if (n_fixed > k) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u is below the %u fixed colours of the processor", k, n_fixed);
     if ((rc = lloyd_create_impl(p, k, &g.s, st)) != KMG_OK) return rc;
-    if ((rc = kmg_lloyd_init_centroids(g.s, src, sw, sh, st)) != KMG_OK) return rc;   // operations.rs:73
+    if ((rc = kmg_lloyd_init_centroids_seeded(g.s, src, sw, sh, fixed4, n_fixed, st)) != KMG_OK) return rc;   // operations.rs:73
+    if ((rc = kmg_lloyd_set_fixed(g.s, n_fixed)) != KMG_OK) return rc;
     if (log_debug()) {
         std::vector<float> c(4 * k);
         if (kmg_lloyd_get_centroids(g.s, c.data(), st) == KMG_OK) {
@@ -101,18 +103,31 @@ int kmg::palette_of_working(kmg_processor *p, const uint8_t *src, uint32_t sw, u
 
 namespace {
 
-int palette_of_working(kmg_processor *p, const WorkingImage &wi, uint32_t k, hipStream_t st, float *c4, uint32_t *d_labels = nullptr)
+typedef std::shared_ptr<const std::vector<float>> FixedList;
+
+int palette_of_working(kmg_processor *p, const WorkingImage &wi, uint32_t k, hipStream_t st, float *c4, const FixedList &fixed,
+                       uint32_t *d_labels = nullptr)
 {
-    return kmg::palette_of_working(p, wi.src, wi.sw, wi.sh, k, st, c4, d_labels);
+    return kmg::palette_of_working(p, wi.src, wi.sw, wi.sh, k, st, c4, d_labels, fixed ? fixed->data() : nullptr, fixed_count(fixed));
 }
 
 int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff,
-                           hipStream_t st, float *c4)
+                           hipStream_t st, float *c4, const FixedList &fixed)
 {
     int rc;
     WorkingImage wi;
     if ((rc = working_image(p, d_rgba, w, h, alpha_cutoff, st, wi)) != KMG_OK) return rc;
-    return palette_of_working(p, wi, k, st, c4);
+    return palette_of_working(p, wi, k, st, c4, fixed);
+}
+
+// the refusals of a palette step while the processor has fixed colours (include/kmeans_hip.h at kmg_processor_set_fixed_colors)
+int check_fixed(const FixedList &fixed, uint32_t k, int algo)
+{
+    const uint32_t f = fixed_count(fixed);
+    if (!f) return KMG_OK;
+    if (algo == KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "the octree has no fixed colours (%u are set on the processor)", f);
+    if (k < f) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u is below the %u fixed colours of the processor", k, f);
+    return KMG_OK;
 }
 
 // An image between a caller's (pageable) buffer and the device.  The calls that use this return when the work is done, so a large
@@ -327,6 +342,8 @@ try {
     if (format < KMG_FORMAT_RGBA8 || format > KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
     if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
         return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
+    const FixedList fixed = fixed_snapshot(p);
+    if ((rc = check_fixed(fixed, color_count, algo)) != KMG_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
     const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     StreamGuard sg;
@@ -343,7 +360,7 @@ try {
         if ((rc = kmg_palette_to_centroids(colors[0].data(), (uint32_t)colors.size(), c4.data())) != KMG_OK) return rc;
     } else {
         c4.resize(4 * (size_t)color_count);
-        if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data())) != KMG_OK) return rc;
+        if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
     }
     const uint32_t k = (uint32_t)(c4.size() / 4);
     if ((rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), k, mode, alpha_cutoff, sg.st, (uint8_t *)out_index, format)) != KMG_OK)
@@ -365,6 +382,8 @@ try {
     if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_DIFFUSE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
     if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
         return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
+    const FixedList fixed = fixed_snapshot(p);
+    if ((rc = check_fixed(fixed, color_count, algo)) != KMG_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
     const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     StreamGuard sg;
@@ -383,7 +402,7 @@ try {
         return apply_and_download(p, (const uint8_t *)img.ptr, w, h, oc4.data(), (uint32_t)colors.size(), mode, alpha_cutoff, sg.st, out_rgba);
     }
     std::vector<float> c4(4 * (size_t)color_count);
-    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data())) != KMG_OK) return rc;
+    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
     const auto t2 = std::chrono::steady_clock::now();
     rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), color_count, mode, alpha_cutoff, sg.st, out_rgba);
     if (log_debug()) {
@@ -407,6 +426,8 @@ try {
     if (algo != KMG_ALGO_KMEANS && algo != KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown algorithm %d", algo);
     if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
         return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
+    const FixedList fixed = fixed_snapshot(p);
+    if ((rc = check_fixed(fixed, color_count, algo)) != KMG_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
     const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     StreamGuard sg;
@@ -421,7 +442,7 @@ try {
         return KMG_OK;
     }
     std::vector<float> c4(4 * (size_t)color_count);
-    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data())) != KMG_OK) return rc;
+    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
     sorted_palette_of(c4.data(), color_count, out_rgba);
     *out_count = color_count;
     return KMG_OK;
@@ -547,6 +568,8 @@ try {
     if (format == KMG_FORMAT_INDEX8 && k_max > 256u) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k_max = %u needs INDEX16", k_max);
     if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
     if (!out || !out_palette_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
+    const FixedList fixed = fixed_snapshot(p);
+    if ((rc = check_fixed(fixed, k_min, KMG_ALGO_KMEANS)) != KMG_OK) return rc;
     const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     if (format == KMG_FORMAT_INDEX8 && k_max + (alpha_cutoff ? 1u : 0u) > 256u)
         return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k_max = %u%s needs INDEX16", k_max, alpha_cutoff ? " plus the transparent slot" : "");
@@ -570,7 +593,7 @@ try {
     uint32_t runs = 0;
     auto evaluate = [&](uint32_t k, bool *accepted) -> int {
         int r;
-        if ((r = palette_of_working(p, wi, k, st, c4.data(), (uint32_t *)labels.ptr)) != KMG_OK) return r;
+        if ((r = palette_of_working(p, wi, k, st, c4.data(), fixed, (uint32_t *)labels.ptr)) != KMG_OK) return r;
         for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], &pal[4 * i]);
         HIP_TRY(hipMemsetAsync(rec.ptr, 0, sizeof(kmg_error_stats), st));
         if ((r = dev_compare_form(p, wi.src, labels.ptr, nw, kErrorLabel32, pal.data(), k, 0, KMG_ERROR_RGB | KMG_ERROR_LAB,

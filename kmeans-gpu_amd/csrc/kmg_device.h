@@ -145,13 +145,18 @@ __device__ __forceinline__ void stage_centroids(float4 *s_cent, const Centroid *
 // choose_centroid.wgsl:180-206 `pick` for all clusters by ONE workgroup of `block` threads (s_count: a word of LDS):
 // centroid <- sum / count where count > 0, *n_converged = number of clusters that moved less than `convergence`
 // (literal CIE94 of the new against the previous centroid); an empty cluster keeps its centroid and counts as not converged.
+// kmg_lloyd_set_fixed: clusters 0 .. n_fixed - 1 keep their centroid whatever their sums and count as converged.  n_fixed is a
+// word of the object's device state, kFixedWord words behind the convergence count (zero unless set): every carrier of the update
+// -- k_update, k_reduce_update, the one-launch loop of small images, the CubeTail of the cube and label passes -- has that
+// pointer, so the freeze needs no argument of its own in any of them (kmg_kernels.h kFixedWord).
 __device__ __forceinline__ void update_centroids(const int64_t *acc, uint32_t k, float convergence, Centroid *cent,
                                                  uint32_t *n_converged, uint32_t *s_count, uint32_t block)
 {
-    if (threadIdx.x == 0) *s_count = 0;
+    const uint32_t n_fixed = n_converged[kFixedWord];
+    if (threadIdx.x == 0) *s_count = n_fixed;
     __syncthreads();
     uint32_t mine = 0;
-    for (uint32_t c = threadIdx.x; c < k; c += block) {
+    for (uint32_t c = n_fixed + threadIdx.x; c < k; c += block) {
         const long long count = acc[4ull * c + 3];
         if (count > 0) {                                         // :185
             float nw[3];

@@ -1325,9 +1325,21 @@ int host_call(kmg_group *g, HostCall &c)
 
 }  // namespace
 
+// (fixed colours are a feature of the single-device calls, like alpha mode: a member processor that has some set makes the group's
+// palette calls refuse, instead of quietly ignoring them)
+static int refuse_fixed(kmg_group *g)
+{
+    if (!g) return KMG_OK;
+    for (uint32_t i = 0; i < g->n_local; ++i)
+        if (g->ranks[i].p && processor_fixed_count(g->ranks[i].p))
+            return fail(KMG_ERR_INVALID_ARGUMENT, "the processor of rank %u has fixed colours set: the kmg_group_* calls have no pinned entries", i);
+    return KMG_OK;
+}
+
 extern "C" int kmg_group_palette(kmg_group *g, const uint8_t *rgba, uint32_t width, uint32_t height, uint32_t color_count, int algo,
                                  uint8_t *out_rgba, uint32_t *out_count)
 try {
+    KMG_TRY(refuse_fixed(g));
     if (color_count == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
     if (!out_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
     if (algo != KMG_ALGO_KMEANS && algo != KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown algorithm %d", algo);
@@ -1364,6 +1376,7 @@ KMG_ABI_CATCH
 extern "C" int kmg_group_reduce(kmg_group *g, const uint8_t *rgba, uint32_t width, uint32_t height, uint32_t color_count, int algo,
                                 int mode, uint8_t *out_rgba)
 try {
+    KMG_TRY(refuse_fixed(g));
     if (color_count == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
     if (!out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
     if (algo != KMG_ALGO_KMEANS && algo != KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown algorithm %d", algo);
@@ -1380,6 +1393,7 @@ extern "C" int kmg_group_reduce_batch(kmg_group *g, uint32_t n_images, const uin
                                       const uint32_t *heights, uint32_t color_count, int algo, int mode, uint8_t *const *out_rgba)
 try {
     if (!g || !rgba || !widths || !heights || !out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "bad group_reduce_batch arguments");
+    KMG_TRY(refuse_fixed(g));
     if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);   // (no diffusion)
     if (g->world != g->n_local) return fail(KMG_ERR_UNSUPPORTED, "the host-buffer calls of a group need all its ranks in one process");
     std::lock_guard<std::mutex> lock(g->call_mu);

@@ -57,8 +57,12 @@ constexpr float kIndexBoxLmin = -100.0f, kIndexBoxLmax = 200.0f, kIndexBoxAB = 3
 
 // The k-means palette step on a working image (kmg_api.hip): sw x sh pixels in device memory -> host centroid table, a new Lloyd
 // problem of k centroids (initialisation + loop with the processor's options).  Synchronises `st`.  d_labels: optional label map.
+// fixed4 / n_fixed (kmg_processor_set_fixed_colors; n_fixed <= k): the Lab of the pinned entries -- centroids 0 .. n_fixed - 1 start
+// there and stay, the rest is initialised and moves around them.
 int palette_of_working(kmg_processor *p, const uint8_t *d_src, uint32_t sw, uint32_t sh, uint32_t k, hipStream_t st, float *centroids4,
-                       uint32_t *d_labels = nullptr);
+                       uint32_t *d_labels = nullptr, const float *fixed4 = nullptr, uint32_t n_fixed = 0);
+// the number of fixed colours set on a processor right now (kmg_processor.hip; kmg_processor_set_fixed_colors)
+uint32_t processor_fixed_count(kmg_processor *p);
 // KMG_MODE_DIFFUSE: the plan's next run starts a new image (row0 = 0, zero error above it) instead of continuing the last one
 // (kmg_apply.hip).  The caller has every earlier run of the plan behind it on the stream of the next one.  Other modes: nothing.
 void apply_plan_restart(kmg_apply_plan *plan);

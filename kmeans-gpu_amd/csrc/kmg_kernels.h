@@ -12,6 +12,11 @@ struct alignas(16) Centroid { float L, a, b, C; };
 
 constexpr int kBlock = 256;          // threads per workgroup (4 waves of 64)
 
+// The state words of a Lloyd object in device memory, which every update receives as `n_converged`: [0] the convergence count,
+// [1 .. 3] the sparsity probe's, [kFixedWord] the number of frozen centroids (kmg_lloyd_set_fixed; update_centroids, kmg_device.h).
+constexpr uint32_t kFixedWord = 8;
+constexpr uint32_t kStateWords = 16;
+
 // What the launchers size grids and LDS requests by, per device ORDINAL: a process may drive several devices (kmg_group's worker
 // threads) and they need not be alike (a partitioned or mixed node).  Of the calling thread's current device; read once per ordinal.
 struct DeviceInfo { uint32_t cus; size_t lds_max; };
@@ -48,6 +53,8 @@ hipError_t launch_assign_loop(const uint32_t *rgba, uint64_t n, const Centroid *
 bool reduce_update_fits(uint32_t rows, uint32_t k);
 hipError_t launch_reduce_update(const int64_t *partials, uint32_t rows, uint32_t k, int64_t *acc, int do_update, float convergence,
                                 Centroid *cent, uint32_t *n_converged, hipStream_t st);
+// (all three updates: n_converged points at the object's state words -- the count, and kFixedWord behind it the number of frozen
+// centroids, kmg_device.h)
 hipError_t launch_update(const int64_t *acc, uint32_t k, float convergence, Centroid *cent,
                          uint32_t *n_converged, hipStream_t st);
 
@@ -61,6 +68,15 @@ hipError_t launch_init_pass(const uint32_t *rgba, uint64_t n, const float *lut,
                             Centroid *cent, uint32_t j, float *dist,
                             unsigned long long *key, uint64_t first_index, hipStream_t st, bool pick = false);
 size_t init_slots_bytes();
+// Seeded initialisation: cent[0 .. n_seeds - 1] are given (1 <= n_seeds <= KMG_MAX_K).  One sweep does what passes 1 .. n_seeds do
+// to the distance map and leaves pass n_seeds's keys in `slots`: launch_init_pass(j = n_seeds + 1, pick = true) continues from there.
+hipError_t launch_init_seed(const uint32_t *rgba, uint64_t n, const float *lut, const Centroid *cent, uint32_t n_seeds, float *dist,
+                            unsigned long long *slots, hipStream_t st);
+// The same over the colours of a bound image (kmg_seed.hip): one sweep over every occupied cell does what launches 1 .. n_seeds of
+// launch_init_pass_cells (kmg_table.h) do to the distance map, the cell records and the slots of init_scratch; that launcher
+// continues from there with j = n_seeds + 1.
+hipError_t launch_init_seed_cells(const uint32_t *tie, const uint8_t *occ_bits, const float4 *lab_table, const Centroid *cent,
+                                  uint32_t n_seeds, float *dist, void *init_scratch, hipStream_t st);
 // Whole image on one device, SEVERAL centroids per launch (kmg_kernels.hip k_init_multi): launch L = 1, 2, ... picks up to four
 // centroids from what launch L - 1 left in `scratch` (init_multi_bytes(n); centroid 0 is there: launch_init_first) and sweeps the
 // running distances against all of them; a launch that finds the table complete does nothing.  *init_multi_count(scratch, n, L)

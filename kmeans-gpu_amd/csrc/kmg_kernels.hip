@@ -227,7 +227,8 @@ __global__ __launch_bounds__(kBlock) void k_assign(const uint32_t *__restrict__ 
         __shared__ uint32_t s_conv;
         const long long *sums = reinterpret_cast<const long long *>(bins);
         for (uint32_t i = threadIdx.x; i < 4 * k; i += kBlock) bins[i] = (unsigned long long)loop.acc_in[i];
-        if (threadIdx.x == 0) s_conv = 0u;
+        const uint32_t n_fixed = loop.n_converged[kFixedWord];       // (kmg_lloyd_set_fixed: kmg_device.h)
+        if (threadIdx.x == 0) s_conv = n_fixed;
         __syncthreads();
         // (update_centroids of kmg_device.h, operation for operation, on the LDS copy)
         uint32_t mine = 0;
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(kBlock) void k_assign(const uint32_t *__restrict__ 
             const float4 prev = s_cent[c];
             float4 now = prev;
             const long long count = sums[4ull * c + 3];
-            if (count > 0) {                                         // choose_centroid.wgsl:185
+            if (count > 0 && c >= n_fixed) {                            // choose_centroid.wgsl:185
                 float nw[3];
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
@@ -687,6 +688,47 @@ __global__ __launch_bounds__(kBlock) void k_init_pick_slots(const uint32_t *__re
     }
 }
 
+// Seeded initialisation (kmg_lloyd_init_centroids_seeded): centroids 0 .. f - 1 are given, so passes 1 .. f have nothing to pick and
+// collapse into ONE sweep -- dist = fminf over 1e6 and cie94(pixel, cent[0 .. f - 1]) in that order, the running minimum pass f
+// leaves -- whose workgroups put their keys where pass f puts them: launch f + 1 of k_init_pass<true> picks centroid f from
+// them and the passes go on unchanged.  The f seeds sit in LDS (16 bytes each, dynamic: at most 48 KiB at KMG_MAX_K).
+__global__ __launch_bounds__(kBlock) void k_init_seed(const uint32_t *__restrict__ rgba, uint64_t n, const float *__restrict__ lut,
+                                                      const Centroid *__restrict__ cent, uint32_t f, float *__restrict__ dist,
+                                                      unsigned long long *__restrict__ key)
+{
+    extern __shared__ float4 s_seed_px[];
+    __shared__ float s_lut[256];
+    __shared__ unsigned long long s_key[kBlock / 64];
+    s_lut[threadIdx.x] = lut[threadIdx.x];
+    for (uint32_t q = threadIdx.x; q < f; q += kBlock) { const Centroid c = cent[q]; s_seed_px[q] = make_float4(c.L, c.a, c.b, c.C); }
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    unsigned long long best = 0ull;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        float L, a, b;
+        px_to_lab(s_lut, rgba[i], L, a, b);
+        float m = 1000000.0f;                                       // kmeans++_calc_diff.wgsl:26-30
+        for (uint32_t q = 0; q < f; ++q) {
+            const float4 c = s_seed_px[q];
+            m = fminf(m, cie94(L, a, b, c.x, c.y, c.z));
+        }
+        dist[i] = m;
+        const unsigned long long kk = ((unsigned long long)float_to_bits(m) << 32) |
+                                      (unsigned long long)(((uint32_t)(i >> 4) << 4) | (15u - (uint32_t)(i & 15u)));
+        best = kk > best ? kk : best;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_down(best, off, 64);
+        best = o > best ? o : best;
+    }
+    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / 64; ++w) best = s_key[w] > best ? s_key[w] : best;
+        key[(f & 1u) * kInitSlots + blockIdx.x] = best;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Several centroids per launch, exactly (whole image on one device; round 5).
 //
@@ -937,6 +979,14 @@ hipError_t launch_init_pick_slots(const uint32_t *rgba, uint64_t n, const float 
                                   uint32_t j, hipStream_t st)
 {
     hipLaunchKernelGGL(k_init_pick_slots, dim3(1), dim3(kBlock), 0, st, rgba, lut, slots, init_pass_grid(n), cent, j);
+    return hipGetLastError();
+}
+
+hipError_t launch_init_seed(const uint32_t *rgba, uint64_t n, const float *lut, const Centroid *cent, uint32_t n_seeds, float *dist,
+                            unsigned long long *slots, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_init_seed, dim3(init_pass_grid(n)), dim3(kBlock), sizeof(float4) * n_seeds, st, rgba, n, lut, cent, n_seeds, dist,
+                       slots);
     return hipGetLastError();
 }
 

@@ -625,7 +625,7 @@ int lloyd_create_impl(kmg_processor *p, uint32_t k, kmg_lloyd **out, hipStream_t
     s->ws = nullptr; s->ws_cap = 0; s->dist_blk_cap = 0;
     s->h_slot = host_slot_take(p);
     // one block from the processor's idle blocks (a warm processor creates a kmg_lloyd without a hipMalloc)
-    const size_t sizes[6] = {sizeof(Centroid) * k, sizeof(int64_t) * 4ull * k * 2048ull, sizeof(int64_t) * 4ull * k, sizeof(uint32_t),
+    const size_t sizes[6] = {sizeof(Centroid) * k, sizeof(int64_t) * 4ull * k * 2048ull, sizeof(int64_t) * 4ull * k, sizeof(uint32_t) * kStateWords,
                              sizeof(unsigned long long), sizeof(int64_t) * 4ull * k};
     size_t need = 0;
     for (size_t b : sizes) need += pad256(b);
@@ -643,7 +643,7 @@ int lloyd_create_impl(kmg_processor *p, uint32_t k, kmg_lloyd **out, hipStream_t
             return s->pooled ? hipMemsetAsync(ptr, 0, bytes, pool_stream) : hipMemset(ptr, 0, bytes);
         };
         e = zero(s->d_cent, sizeof(Centroid) * k);                    // structures.rs:501-521
-        if (e == hipSuccess) e = zero(s->d_nconv, sizeof(uint32_t));
+        if (e == hipSuccess) e = zero(s->d_nconv, sizeof(uint32_t) * kStateWords);   // (the count; no frozen centroid)
     } else {
         s->ws = nullptr; s->ws_cap = 0;
     }
@@ -723,14 +723,15 @@ KMG_ABI_CATCH
 // more for each of the first ~16 passes, which reach every cell) after binding the image (bind_seconds, x 1.5 with the
 // tie keys that come with the partitioned histogram, or another atomic per pixel on small images); MI355X,
 // tools/cfg3_probe.py / tools/init_phases.sh, round 2.
-static bool init_table_pays(const kmg_processor *p, uint64_t n, uint32_t k)
+// (n_seeds > 0, a seeded initialisation: k - n_seeds single-pick launches on either route after one sweep against the seeds)
+static bool init_table_pays(const kmg_processor *p, uint64_t n, uint32_t k, uint32_t n_seeds = 0)
 {
     if (const int f = forced_strategy(p)) return f > 0;
-    const double N = (double)n, passes = (double)(k - 1);
+    const double N = (double)n, passes = (double)(n_seeds ? k - n_seeds + 1u : k - 1u);
     // (k >= 32: k_init_multi picks up to four centroids per launch -- ~0.3 k + 18 launches -- on a grid of at most 256
     // workgroups, four literal distances per pixel and launch: 9 us + 30 ps per pixel; tools/init_crossover.py,
     // profiles/r05_init_crossover.txt)
-    const double pixels = k >= 32u ? (0.3 * k + 18.0) * (9.0e-6 + N * 30.0e-12) : passes * (8.0e-6 + N * 7.0e-12);
+    const double pixels = k >= 32u && !n_seeds ? (0.3 * k + 18.0) * (9.0e-6 + N * 30.0e-12) : passes * (8.0e-6 + N * 7.0e-12);
     // (passes over the colours: 9 us each, the first 16 visit every cell: + 30 us; binding with its tie keys 1.5 x a plain bind,
     // below 2^21 pixels 0.05 ms + 0.2 ns per pixel -- refitted in round 6, tests/test_gpu_costmodel.py prints the rows)
     const double colours = passes * 0.9e-5 + (passes < 16.0 ? passes : 16.0) * 3.0e-5 +
@@ -741,12 +742,12 @@ static bool init_table_pays(const kmg_processor *p, uint64_t n, uint32_t k)
 // decides the init strategy for (d_rgba, n, first_index) and, for the colour strategy, makes sure the
 // image is bound and its tie keys and per-colour distance map exist
 static int init_over_colours(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, uint64_t first_index, bool *colours,
-                             void *stream)
+                             void *stream, uint32_t n_seeds = 0)
 {
     *colours = false;
     // an initialisation starts a new problem: the image is (re)bound from the buffer's current contents,
     // so the loop that follows never works from the histogram of an earlier image in the same buffer
-    if (first_index + n > 0xFFFFFFF0ull || !init_table_pays(s->p, n, s->k)) {
+    if (first_index + n > 0xFFFFFFF0ull || !init_table_pays(s->p, n, s->k, n_seeds)) {
         if (s->tab.rgba == d_rgba) s->tab.rgba = nullptr;
         return KMG_OK;
     }
@@ -855,6 +856,82 @@ try {
         if (!colours)       // the last centroid, from the last pass's slots
             HIP_TRY(launch_init_pick_slots(rgba, n, s->p->d_lut, (const unsigned long long *)s->d_partials, s->d_cent, s->k - 1u, S(stream)));
     }
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+// The initialisation with the first n_seeds centroids given (include/kmeans_hip.h).  One sweep against the seeds stands for
+// passes 1 .. n_seeds (launch_init_seed / launch_init_seed_cells), then the single-pick launches n_seeds + 1 .. continue unchanged
+// on either route: k - n_seeds + 1 launches.  (The multi-pick launches are not resumed: their rows of candidates with Lab are
+// another hand-over format, and what a caller pins is a handful of the k.)
+extern "C" int kmg_lloyd_init_centroids_seeded(kmg_lloyd *s, const uint8_t *d_rgba, uint32_t w, uint32_t h, const float *seeds4,
+                                               uint32_t n_seeds, void *stream)
+try {
+    if (n_seeds == 0) return kmg_lloyd_init_centroids(s, d_rgba, w, h, stream);
+    if (!s || !d_rgba || !w || !h || !seeds4) return fail(KMG_ERR_INVALID_ARGUMENT, "bad init_centroids_seeded arguments");
+    if (n_seeds > s->k) return fail(KMG_ERR_INVALID_ARGUMENT, "init_centroids_seeded: %u seeds for k = %u", n_seeds, s->k);
+    for (uint32_t i = 0; i < 4u * n_seeds; ++i)
+        if ((i & 3u) != 3u && !(seeds4[i] - seeds4[i] == 0.0f)) return fail(KMG_ERR_INVALID_ARGUMENT, "init_centroids_seeded: seed %u is not finite", i / 4u);
+    HIP_TRY(hipSetDevice(s->p->device));
+    const uint64_t n = (uint64_t)w * h;
+    if (n > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
+    s->tab.tables_valid = false;
+    std::vector<Centroid> seeds(n_seeds);
+    for (uint32_t i = 0; i < n_seeds; ++i) {
+        seeds[i].L = seeds4[4 * i]; seeds[i].a = seeds4[4 * i + 1]; seeds[i].b = seeds4[4 * i + 2];
+        seeds[i].C = chroma(seeds[i].a, seeds[i].b);
+    }
+    HIP_TRY(hipMemcpyAsync(s->d_cent, seeds.data(), sizeof(Centroid) * n_seeds, hipMemcpyHostToDevice, S(stream)));
+    HIP_TRY(hipStreamSynchronize(S(stream)));
+    // (every centroid given: no pass decides about the binding, the earlier binding of this buffer is dropped here)
+    if (s->k == n_seeds) {
+        if (s->tab.rgba == d_rgba) s->tab.rgba = nullptr;
+        return KMG_OK;
+    }
+    int rc;
+    bool colours = false;
+    if ((rc = init_over_colours(s, d_rgba, n, 0, &colours, stream, n_seeds)) != KMG_OK) return rc;
+    const uint32_t *rgba = (const uint32_t *)d_rgba;
+    if (colours) {
+        HIP_TRY(launch_init_seed_cells(s->tab.d_tie, s->tab.d_occ, s->p->d_lab_table, s->d_cent, n_seeds, s->tab.d_cdist, s->tab.d_init_cells,
+                                       S(stream)));
+        for (uint32_t j = n_seeds + 1u; j <= s->k; ++j)             // launch j picks centroid j - 1 and runs pass j; launch k only picks
+            HIP_TRY(launch_init_pass_cells(s->tab.d_tie, s->tab.d_occ, s->p->d_lab_table, s->d_cent, j, j < s->k ? 1 : 0, s->tab.d_cdist,
+                                           s->tab.d_init_cells, nullptr, rgba, s->p->d_lut, S(stream)));
+        return KMG_OK;
+    }
+    if (s->dist_cap < n) {
+        if (s->d_dist) {
+            HIP_TRY(hipFree(s->d_dist));                             // (the stream was synchronised above)
+            s->d_dist = nullptr; s->dist_cap = 0; s->dist_blk_cap = 0;
+        }
+        HIP_TRY(block_take(s->p, sizeof(float) * n, (void **)&s->d_dist, &s->dist_blk_cap));
+        s->dist_cap = n;
+    }
+    unsigned long long *slots = (unsigned long long *)s->d_partials;   // (the slab nothing else uses during an initialisation)
+    HIP_TRY(launch_init_seed(rgba, n, s->p->d_lut, s->d_cent, n_seeds, s->d_dist, slots, S(stream)));
+    for (uint32_t j = n_seeds + 1u; j < s->k; ++j)
+        HIP_TRY(launch_init_pass(rgba, n, s->p->d_lut, s->d_cent, j, s->d_dist, slots, 0, S(stream), true));
+    HIP_TRY(launch_init_pick_slots(rgba, n, s->p->d_lut, slots, s->d_cent, s->k - 1u, S(stream)));
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_lloyd_set_fixed(kmg_lloyd *s, uint32_t n_fixed)
+try {
+    if (!s || n_fixed > s->k) return fail(KMG_ERR_INVALID_ARGUMENT, "bad set_fixed arguments");
+    if (s->tab.d_work_share) return fail(KMG_ERR_INVALID_ARGUMENT, "set_fixed: a cell share is set (kmg_lloyd_set_cell_share)");
+    if (n_fixed == s->n_fixed) return KMG_OK;
+    HIP_TRY(hipSetDevice(s->p->device));
+    // the updates read it from the object's state words (kmg_device.h kFixedWord).  The copy has completed when this returns:
+    // updates enqueued afterwards, on any stream, see the new value.  (A per-call object's words are cleared on its own stream.)
+    if (s->pooled) {
+        HIP_TRY(hipMemcpyAsync(s->d_nconv + kFixedWord, &n_fixed, sizeof n_fixed, hipMemcpyHostToDevice, s->pool_stream));
+        HIP_TRY(hipStreamSynchronize(s->pool_stream));
+    } else {
+        HIP_TRY(hipMemcpy(s->d_nconv + kFixedWord, &n_fixed, sizeof n_fixed, hipMemcpyHostToDevice));
+    }
+    s->n_fixed = n_fixed;
     return KMG_OK;
 }
 KMG_ABI_CATCH

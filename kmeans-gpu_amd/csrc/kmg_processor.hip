@@ -315,6 +315,25 @@ try {
 }
 KMG_ABI_CATCH
 
+uint32_t kmg::processor_fixed_count(kmg_processor *p) { return fixed_count(fixed_snapshot(p)); }
+
+extern "C" int kmg_processor_set_fixed_colors(kmg_processor *p, const uint8_t *rgba, uint32_t n)
+try {
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
+    if (n > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "fixed colours: %u is above KMG_MAX_K = %u", n, KMG_MAX_K);
+    if (n && !rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "fixed colours: the list is NULL");
+    std::shared_ptr<std::vector<float>> lab;
+    if (n) {
+        int rc;
+        lab = std::make_shared<std::vector<float>>(4 * (size_t)n);
+        if ((rc = kmg_palette_to_centroids(rgba, n, lab->data())) != KMG_OK) return rc;
+    }
+    std::lock_guard<std::mutex> lock(p->mu);
+    p->fixed = lab;
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
 extern "C" void kmg_processor_destroy(kmg_processor *p)
 try {
     if (!p) return;

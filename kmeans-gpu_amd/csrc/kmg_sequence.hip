@@ -335,9 +335,14 @@ int sequence_centroids(kmg_sequence *s, uint32_t k, float *c4)
     if (k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
     if (k > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", k, KMG_MAX_K);
     if (s->n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "no pixel reaches alpha_cutoff (the working sequence is empty)");
+    // (the processor's fixed colours, as they are when this call starts: kmg_processor_set_fixed_colors)
+    const std::shared_ptr<const std::vector<float>> fixed = fixed_snapshot(s->p);
+    const uint32_t f = fixed_count(fixed);
+    if (k < f) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u is below the %u fixed colours of the processor", k, f);
     HIP_TRY(hipSetDevice(s->p->device));
     const bool as_image = s->frames == 1 && s->first_whole;
-    return palette_of_working(s->p, (const uint8_t *)s->w_blk, as_image ? s->sw0 : (uint32_t)s->n, as_image ? s->sh0 : 1u, k, s->sg.st, c4);
+    return palette_of_working(s->p, (const uint8_t *)s->w_blk, as_image ? s->sw0 : (uint32_t)s->n, as_image ? s->sh0 : 1u, k, s->sg.st, c4,
+                              nullptr, f ? fixed->data() : nullptr, f);
 }
 
 }  // namespace

@@ -15,6 +15,7 @@
 #include <atomic>
 #include <chrono>
 #include <exception>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <new>
@@ -65,6 +66,9 @@ struct kmg_processor {
     kmg_options opt;
     std::atomic<int> strategy{0};   // KMG_STRATEGY_* (kmg_options.strategy, kmg_processor_set_strategy)
     std::atomic<uint32_t> alpha_cutoff{0};   // kmg_options.alpha_cutoff, kmg_processor_set_alpha_cutoff (0 = alpha ignored)
+    // kmg_processor_set_fixed_colors (mu): the pinned palette entries as Lab (kmg_palette_to_centroids of the caller's list, 4 floats
+    // each), or null = none.  A call takes the pointer once when it starts and keeps that list to its end.
+    std::shared_ptr<const std::vector<float>> fixed;
     float *d_lut;            // 256 x f32: sRGB decode * 100, then 256 x f32: thresholds of the sRGB8 encode (k_meld)
     std::mutex mu;           // guards the lazily built static tables below
     CellBounds *d_bounds;    // kCells static cell bounds of the colour-table strategy
@@ -97,6 +101,14 @@ void host_slot_give(kmg_processor *p, void *slot);
 // one / back to the idle list (the caller guarantees that no kernel still uses the block)
 hipError_t block_take(kmg_processor *p, size_t bytes, void **ptr, size_t *cap);
 void block_give(kmg_processor *p, void *ptr, size_t cap);
+
+// the fixed colours a call starts with (empty: none)
+static inline std::shared_ptr<const std::vector<float>> fixed_snapshot(kmg_processor *p)
+{
+    std::lock_guard<std::mutex> lock(p->mu);
+    return p->fixed;
+}
+static inline uint32_t fixed_count(const std::shared_ptr<const std::vector<float>> &f) { return f ? (uint32_t)(f->size() / 4) : 0u; }
 
 static inline size_t pad256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
 
@@ -152,7 +164,7 @@ struct kmg_lloyd {
     int64_t *d_acc_int;          // k x 4: where the cube pass accumulates; ZERO between passes (its last launch hands the sums
                                  // over and clears it, kmg_table.h CubeTail) -- no memset launch per pass
     bool acc_int_dirty;          // a pass was interrupted: clear d_acc_int before the next one
-    uint32_t *d_nconv;           // 1
+    uint32_t *d_nconv;           // kStateWords: the convergence count, the sparsity probe's three words, n_fixed (kmg_device.h)
     void *h_slot = nullptr;      // kHostSlotBytes page-locked bytes for small read-backs (kmg_processor::h_page), or NULL
     unsigned long long *d_key;   // 1 (init arg-max of a sharded image)
     float *d_dist;               // init distance map, grown on demand (a block of its own)
@@ -163,6 +175,8 @@ struct kmg_lloyd {
     uint32_t last_rows;          // rows of d_partials written by the last assign pass
     bool init_colours;           // the running sharded init (kmg_lloyd_init_step) walks colours, not pixels
     uint32_t reserve_cus = 0;    // CUs the label pass leaves free (kmg_lloyd_reserve_cus)
+    uint32_t n_fixed = 0;        // host copy of d_nconv[kFixedWord]: centroids 0 .. n_fixed - 1 are left alone by every update and
+                                 // count as converged (kmg_lloyd_set_fixed)
     bool pooled;                 // workspace came from the stream-ordered pool of `pool_stream` (internal per-call objects)
     hipStream_t pool_stream;
     ColourTable tab;

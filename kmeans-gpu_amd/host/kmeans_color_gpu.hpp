@@ -12,6 +12,7 @@
 //   processor.reduce_batch(color_count, images, algo, mode) -> whole images per device, side by side
 //   processor.compare(source, output[, colors])            -> kmg_error_stats: exact error sums of an output against its source
 //   processor.reduce_quality(image, max_delta_e, k_min, k_max, mode) -> the colour count chosen by a quality target
+//   processor.set_fixed_colors(colors)                     -> palette entries the k-means keeps exactly and builds around
 // `anyhow::Result` errors become kmeans_color_gpu::Error exceptions carrying the kmg_status and the
 // library's message.  Header only; link with -lkmeans_hip.
 #pragma once
@@ -242,6 +243,16 @@ public:
     {
         if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "a processor over several devices has no alpha mode");
         check(kmg_processor_set_alpha_cutoff(p_, alpha_cutoff));
+    }
+
+    // kmg_processor_set_fixed_colors (include/kmeans_hip.h): colours every k-means palette of the calls that start from now on keeps
+    // exactly (alpha ignored), as entries 0 .. colors.size() - 1 in index order; an empty list clears them.  A color_count below
+    // their number and Algorithm::Octree are then errors.  A processor over several devices has no fixed colours.
+    void set_fixed_colors(const std::vector<RGBA8> &colors) const
+    {
+        if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "a processor over several devices has no fixed colours");
+        check(kmg_processor_set_fixed_colors(p_, colors.empty() ? nullptr : reinterpret_cast<const uint8_t *>(colors.data()),
+                                             (uint32_t)colors.size()));
     }
 
     kmg_processor *handle() const { return g_ ? kmg_group_processor(g_, 0) : p_; }

@@ -211,11 +211,11 @@ _lib = None
 # every symbol include/kmeans_hip.h declares
 SYMBOLS = [
     "kmg_last_error", "kmg_version", "kmg_host_alloc", "kmg_host_free", "kmg_default_options", "kmg_processor_create",
-    "kmg_processor_create_ex", "kmg_processor_destroy", "kmg_processor_set_strategy", "kmg_processor_set_alpha_cutoff", "kmg_palette", "kmg_find", "kmg_reduce",
+    "kmg_processor_create_ex", "kmg_processor_destroy", "kmg_processor_set_strategy", "kmg_processor_set_alpha_cutoff", "kmg_processor_set_fixed_colors", "kmg_palette", "kmg_find", "kmg_reduce",
     "kmg_palette_to_centroids", "kmg_centroids_to_palette", "kmg_octree_palette", "kmg_dev_rgb_to_lab",
     "kmg_resized_dims", "kmg_dev_alpha_compact",
     "kmg_dev_resize", "kmg_lloyd_create", "kmg_lloyd_destroy", "kmg_lloyd_set_centroids",
-    "kmg_lloyd_get_centroids", "kmg_lloyd_init_centroids", "kmg_lloyd_init_step", "kmg_lloyd_init_pick_band",
+    "kmg_lloyd_get_centroids", "kmg_lloyd_init_centroids", "kmg_lloyd_init_centroids_seeded", "kmg_lloyd_set_fixed", "kmg_lloyd_init_step", "kmg_lloyd_init_pick_band",
     "kmg_lloyd_set_centroid_rgba", "kmg_init_first_key", "kmg_lloyd_assign_accumulate",
     "kmg_lloyd_assign_partials", "kmg_lloyd_reduce_partials", "kmg_lloyd_labels", "kmg_lloyd_reserve_cus", "kmg_lloyd_bind_image",
     "kmg_lloyd_unbind_image", "kmg_debug_bound_image", "kmg_lloyd_prepare", "kmg_debug_check_table", "kmg_debug_table_stats", "kmg_debug_check_pairs", "kmg_debug_check_dither_masks", "kmg_debug_check_meld_masks", "kmg_kernel_name",
@@ -335,6 +335,9 @@ def lib():
     L.kmg_dither_threshold.argtypes = [f32p, C.c_uint32, C.POINTER(C.c_float)]
     L.kmg_processor_set_strategy.argtypes = [vp, C.c_int]
     L.kmg_processor_set_alpha_cutoff.argtypes = [vp, C.c_uint32]
+    L.kmg_processor_set_fixed_colors.argtypes = [vp, u8p, C.c_uint32]
+    L.kmg_lloyd_init_centroids_seeded.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, f32p, C.c_uint32, vp]
+    L.kmg_lloyd_set_fixed.argtypes = [vp, C.c_uint32]
     L.kmg_dev_alpha_compact.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, u8p, vp, vp]
     L.kmg_dev_compare.argtypes = [vp, u8p, vp, C.c_uint64, C.c_int, u8p, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.kmg_compare.argtypes = [vp, u8p, vp, C.c_uint32, C.c_uint32, C.c_int, u8p, C.c_uint32, C.c_uint32, C.POINTER(ErrorStats)]
@@ -503,9 +506,10 @@ class ImageProcessor:
     """Mirror of `kmeans_color_gpu::ImageProcessor` (core/src/lib.rs:24-165)."""
 
     def __init__(self, device=-1, shrink_max_dim=256, max_iterations=128, check_period=8,
-                 convergence=1.0, strategy=None, alpha_cutoff=0):
+                 convergence=1.0, strategy=None, alpha_cutoff=0, fixed_colors=None):
         """alpha_cutoff: 0 = alpha ignored (the reference's behaviour); 1..255 = alpha mode (include/kmeans_hip.h at
-        kmg_options): only pixels whose alpha is >= alpha_cutoff shape the palette, and the outputs keep the input's alpha"""
+        kmg_options): only pixels whose alpha is >= alpha_cutoff shape the palette, and the outputs keep the input's alpha.
+        fixed_colors: colours every k-means palette of this processor keeps, as its first entries (set_fixed_colors)"""
         self._h = C.c_void_p()
         o = default_options()
         o.device = device
@@ -519,6 +523,20 @@ class ImageProcessor:
         self.options = o
         self._sequences = None          # weak set of the live Sequence objects: closed with the processor, which they need
         _register(self)
+        if fixed_colors is not None:
+            self.set_fixed_colors(fixed_colors)
+
+    def set_fixed_colors(self, colors):
+        """kmg_processor_set_fixed_colors: (n, 3) or (n, 4) uint8 colours (alpha ignored) that the k-means palettes of the
+        calls that start from now on keep exactly, as entries 0 .. n - 1 in index order; None or an empty list clears them"""
+        pal = np.zeros((0, 4), np.uint8)
+        if colors is not None and len(colors):
+            c = np.asarray(colors, dtype=np.uint8)
+            if c.ndim != 2 or c.shape[1] not in (3, 4):
+                raise ValueError("fixed colours: an (n, 3) or (n, 4) uint8 array")
+            pal = np.full((c.shape[0], 4), 255, np.uint8)
+            pal[:, :c.shape[1]] = c
+        _check(lib().kmg_processor_set_fixed_colors(self._h, _np_ptr(pal) if pal.shape[0] else None, pal.shape[0]))
 
     def set_alpha_cutoff(self, alpha_cutoff):
         """kmg_processor_set_alpha_cutoff: 0 (alpha ignored) or 1..255 (alpha mode) for the calls that start from now on"""
@@ -904,6 +922,20 @@ class Lloyd:
         _check(lib().kmg_lloyd_init_centroids(self._h, C.c_void_p(d_rgba), width, height, C.c_void_p(stream)))
 
     # sharded (row band) initialisation steps -- what kmg_group_lloyd_init drives (tests/sharded_harness.py sharded_init)
+    def init_centroids_seeded(self, d_rgba, width, height, seeds4, stream=0):
+        """kmg_lloyd_init_centroids_seeded: centroids 0 .. n - 1 are the (n, 4) or (n, 3) Lab seeds, the others the farthest-point
+        picks that follow them; no seed: init_centroids.  Seeds move with the first update unless set_fixed freezes them."""
+        s = np.asarray(seeds4, np.float32)
+        s = s.reshape(-1, s.shape[-1]) if s.size else np.zeros((0, 4), np.float32)
+        c = np.ones((s.shape[0], 4), np.float32)
+        c[:, :3] = s[:, :3]
+        _check(lib().kmg_lloyd_init_centroids_seeded(self._h, C.c_void_p(d_rgba), int(width), int(height),
+                                                     _np_ptr(c) if c.shape[0] else None, c.shape[0], C.c_void_p(stream)))
+
+    def set_fixed(self, n_fixed):
+        """kmg_lloyd_set_fixed: every update of this object leaves centroids 0 .. n_fixed - 1 alone and counts them as converged"""
+        _check(lib().kmg_lloyd_set_fixed(self._h, int(n_fixed)))
+
     def init_step(self, d_rgba, n_local, first_index, j, d_key, stream=0):
         _check(lib().kmg_lloyd_init_step(self._h, C.c_void_p(d_rgba or None), n_local, first_index, j,
                                          C.c_void_p(d_key), C.c_void_p(stream)))

@@ -22,6 +22,10 @@ quantises several frames of one size with ONE palette (kmg_sequence_*) and write
 delta frames -- the rectangle of the pixels that changed, blended "over" -- unless --no-delta asks for full frames.  K <= 255: the
 transparent slot takes the last palette entry.
 
+`palette`, `reduce` and `sequence` also take `--fixed "#RRGGBB,..."|palette.png` (the palette syntax of `find`): colours the k-means
+palette keeps exactly, as its first entries in index order (the PLTE of `--indexed` and of `sequence`), while the other entries
+are placed around them (kmg_processor_set_fixed_colors).  `-c` counts them; k-means only.
+
 Image decoding/encoding (the `image` crate in the reference) is done with Pillow.  One flag the reference does not have:
 `--devices 0,1,...` (before the sub-command) runs the same operation over several GPUs of the node (kmg_group_*: the image
 tiled in row bands, same bytes).
@@ -156,7 +160,7 @@ def run_sequence(args, ap):
         if f.shape[:2] != (h, w):
             ap.error(f"every input of `sequence` must have one size: {path} is {f.shape[1]}x{f.shape[0]}, {args.input[0]} is {w}x{h}")
     out_path = sequence_file_path(args.colorcount, args.mode, args.output, args.input[0])
-    with ImageProcessor(alpha_cutoff=args.alpha_cutoff) as proc, proc.sequence() as seq:
+    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed) as proc, proc.sequence() as seq:
         for f in frames:
             seq.add(f)
         colors = seq.output(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h)
@@ -256,6 +260,9 @@ def main(argv=None):
     for s in (p, f, r, q):
         s.add_argument("--alpha-cutoff", type=validate_alpha_cutoff, default=0,
                        help="1..255: pixels with a lower alpha do not shape the palette, the output keeps the input's alpha")
+    for s in (p, r, q):
+        s.add_argument("--fixed", type=validate_palette, default=None, metavar="COLORS",
+                       help='"#RRGGBB,..." or a palette image: colours the k-means palette keeps exactly, as its first entries; -c counts them')
     for s in (f, r):
         s.add_argument("--indexed", action="store_true",
                        help="write a palette-mode PNG (an index per pixel) instead of RGBA; at most 256 colours, 255 with --alpha-cutoff")
@@ -265,6 +272,15 @@ def main(argv=None):
                    help="choose the colour count: as few colours (at most -c) as keep the dE76 RMS of the shrunk image at or below DE; k-means only")
     r.add_argument("--min-colors", type=validate_k, default=None, metavar="A", help="lower bound of --max-error's search (default 2)")
     args = ap.parse_args(argv)
+    fixed = getattr(args, "fixed", None)
+    if fixed is not None:
+        if args.devices:
+            ap.error("--fixed is not supported with --devices")
+        if getattr(args, "algo", "kmeans") != "kmeans":
+            ap.error("--fixed pins entries of the k-means palette: -a octree has none")
+        lowest = args.min_colors if getattr(args, "min_colors", None) is not None else args.colorcount
+        if fixed.shape[0] > lowest:
+            ap.error(f"--fixed names {fixed.shape[0]} colours, more than the {lowest} the palette may have")
     if args.command == "sequence":
         if args.devices:
             ap.error("`sequence` is not supported with --devices")
@@ -286,7 +302,7 @@ def main(argv=None):
         if args.algo != "kmeans":
             ap.error("--max-error searches the k-means colour count: -a octree has no such knob")
         if args.min_colors is None:
-            args.min_colors = min(2, args.colorcount)
+            args.min_colors = min(max(2, fixed.shape[0] if fixed is not None else 0), args.colorcount)
         if args.min_colors > args.colorcount:
             ap.error(f"--min-colors {args.min_colors} is above -c {args.colorcount}")
     elif getattr(args, "min_colors", None) is not None:
@@ -311,7 +327,12 @@ def main(argv=None):
     if args.devices:
         proc = Group(devices=args.devices)
     else:
-        proc = ImageProcessor(alpha_cutoff=args.alpha_cutoff) if args.alpha_cutoff else ImageProcessor()
+        options = {}                                     # (only what the command line asks for)
+        if args.alpha_cutoff:
+            options["alpha_cutoff"] = args.alpha_cutoff
+        if fixed is not None:
+            options["fixed_colors"] = fixed
+        proc = ImageProcessor(**options)
     with proc:
         if args.command == "palette":                    # main.rs:46-72
             colors = proc.palette(args.colorcount, image, _ALGOS[args.algo])

@@ -72,6 +72,18 @@ impl ImageProcessor {
         check(unsafe { ffi::kmg_processor_set_alpha_cutoff(self.raw, alpha_cutoff) })
     }
 
+    /// Fixed palette colours (`kmg_processor_set_fixed_colors`, include/kmeans_hip.h): every k-means palette of the calls that
+    /// start from now on keeps `colors` exactly (alpha ignored), as entries `0..colors.len()` in index order, and places the
+    /// others around them; an empty slice clears them.  `color_count` below the number of fixed colours and
+    /// `Algorithm::Octree` are then errors.  No counterpart in the reference.  A processor over several devices has none.
+    pub fn set_fixed_colors(&self, colors: &[RGBA8]) -> Result<()> {
+        if !self.group.is_null() {
+            return Err(anyhow!("a processor over several devices has no fixed colours"));
+        }
+        let list = if colors.is_empty() { std::ptr::null() } else { colors.as_ptr() as *const u8 };
+        check(unsafe { ffi::kmg_processor_set_fixed_colors(self.raw, list, colors.len() as u32) })
+    }
+
     /// lib.rs:67-77: `color_count` dominant colours, sorted by Lab lightness (k-means: exactly
     /// `color_count`; octree: at most).
     pub async fn palette<C: Container>(
