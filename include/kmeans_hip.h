@@ -622,6 +622,41 @@ typedef struct kmg_frame_delta {      /* 32 bytes, no padding */
 KMG_API int kmg_dev_frame_delta(kmg_processor *p, const void *d_index, void *d_canvas, uint32_t width, uint32_t rows, uint32_t row0,
                                 int format, uint32_t k, void *d_delta, kmg_frame_delta *d_info, void *stream);
 
+/* The lossy delta pass: a pixel whose source moved within a tolerance keeps the index it shows.  Real input (sensor noise, video
+ * compression artefacts, dithered or diffused maps) changes nearly every index from frame to frame even when the scene is still;
+ * the exact rule above then sends the whole frame.  A second per-pixel state joins the canvas: the HELD SOURCE h, the RGBA8
+ * source word the pixel had when its canvas index was last written.  It is the anchor of the comparison -- never the previous
+ * frame -- so a slow drift cannot accumulate: once the source has moved more than the tolerance from the anchor, the pixel is sent.
+ *   D(x, y) = dqL^2 + dqa^2 + dqb^2,  dq = q(x) - q(y) over the R, G, B bytes, q = rint(64 Lab): the grid of kmg_error_stats.
+ *             An exact integer, at most 347 973 309, in units of 1/4096 dE76^2 (those of kmg_reduce_quality's target); D = 0 when
+ *             the R, G, B bytes are equal (no conversion is made then).  `tolerance` is in the same unit.
+ * For the pixel (x, row0 + r) of the band, s = its source word, c = its index in d_index, v = its index in d_canvas, h = its held
+ * source:
+ *   hold := v != k  &&  c != k  &&  D(s, h) <= tolerance
+ *   hold:      delta = k; canvas and held source stay; when c != v: held += 1, held_sse += D(s, h)
+ *   not hold:  the exact rule of kmg_dev_frame_delta (c == v: delta = k; c != v: delta = c, changed += 1, the box takes the pixel
+ *              in, cleared += 1 when c == k); canvas = c; held source = s
+ * A pixel that shows nothing (v == k) is never held, nor is one that turns transparent (c == k).  tolerance = 0 holds only where
+ * D = 0.  After any frame every pixel of the canvas either equals this frame's exact index or shows the exact index of an earlier
+ * frame whose source at that pixel is within `tolerance` of this frame's.
+ * The record starts with the fields of kmg_frame_delta (same fresh values, same combination rule); held and held_sse are sums:
+ * fresh 0, combined by addition (held_sse < 2^61 for 2^32 pixels).  Bands may run in any order on any streams, as above.
+ * d_src_rgba, d_held_rgba: DEVICE, width * rows RGBA8 words each, 4-byte aligned; the index buffers as for kmg_dev_frame_delta.
+ * The 16-byte accesses of the pass need the two RGBA8 buffers 16-byte aligned and the three index buffers 4- (INDEX8) or 8-byte
+ * (INDEX16) aligned; otherwise it goes pixel by pixel.  No two buffers overlap.  Refusals: those of kmg_dev_frame_delta, and a NULL
+ * or misaligned source or held pointer.  Only enqueues work on `stream`.                                                        */
+typedef struct kmg_frame_hold {       /* 48 bytes, no padding */
+    uint64_t changed;                 /* as kmg_frame_delta: pixels sent                                            */
+    uint64_t cleared;
+    uint32_t x0, y0;
+    uint32_t x1, y1;
+    uint64_t held;                    /* pixels whose exact index differs from the canvas and that were held        */
+    uint64_t held_sse;                /* sum of D(s, h) over those pixels                                           */
+} kmg_frame_hold;
+KMG_API int kmg_dev_frame_delta_lossy(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_index, void *d_canvas,
+                                      uint8_t *d_held_rgba, uint32_t width, uint32_t rows, uint32_t row0, int format, uint32_t k,
+                                      uint32_t tolerance, void *d_delta, kmg_frame_hold *d_info, void *stream);
+
 /* Frame output with the sequence's palette, on HOST buffers.
  *   _output_begin   the centroids of W at k (as _centroids); out_palette_rgba (k x 4 bytes) / *out_count: the palette in index
  *                   order, exactly as kmg_reduce_indexed returns it; one apply plan (kmg_apply_plan_create_format with
@@ -637,6 +672,12 @@ KMG_API int kmg_dev_frame_delta(kmg_processor *p, const void *d_index, void *d_c
  *                   frame needs no special case: against a canvas of k the delta IS I_0.  Replaying the delta maps with "over"
  *                   (index k keeps the pixel) and the full maps with "source" reproduces every I_t.
  *                   No output open, KMG_FRAME_DELTA with KMG_FORMAT_RGBA8 or without info / is_full: KMG_ERR_INVALID_ARGUMENT.
+ *   _output_frame_lossy   the same with the rule of kmg_dev_frame_delta_lossy at `tolerance`: out = the lossy delta map, *info = its
+ *                   record, *is_full = 0 -- unless info->cleared > 0: then out = I_t, *is_full = 1, *info as measured, and the
+ *                   canvas becomes I_t with the frame as every pixel's held source.  An exact frame (_output_frame, delta or
+ *                   full) leaves the canvas equal to its map everywhere, so its held source is that frame: exact and lossy
+ *                   frames may alternate freely on one open output.  Needs KMG_FRAME_DELTA in flags, an index format, info and
+ *                   is_full: otherwise KMG_ERR_INVALID_ARGUMENT.  Replaying its maps as above reproduces the canvas.
  *   _output_end     returns the plan and the buffers; so does _destroy.
  * Frames may be added while an output is open: they do not affect it.                                                         */
 #define KMG_FRAME_DELTA 1u
@@ -644,6 +685,8 @@ KMG_API int kmg_sequence_output_begin(kmg_sequence *s, uint32_t k, int mode, int
                                       uint8_t *out_palette_rgba, uint32_t *out_count);
 KMG_API int kmg_sequence_output_frame(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, void *out, kmg_frame_delta *info,
                                       int *is_full);
+KMG_API int kmg_sequence_output_frame_lossy(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, uint32_t tolerance, void *out,
+                                            kmg_frame_hold *info, int *is_full);
 KMG_API int kmg_sequence_output_end(kmg_sequence *s);
 
 /* ======================= several GPUs: a group of devices ================================

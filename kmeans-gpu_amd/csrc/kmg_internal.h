@@ -67,6 +67,11 @@ uint32_t processor_fixed_count(kmg_processor *p);
 // (kmg_apply.hip).  The caller has every earlier run of the plan behind it on the stream of the next one.  Other modes: nothing.
 void apply_plan_restart(kmg_apply_plan *plan);
 
+// kmg_dev_frame_delta_lossy on a hipStream_t (kmg_hold.hip): the sequence layer's lossy frames
+int frame_hold_impl(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_index, void *d_canvas, uint8_t *d_held_rgba, uint32_t width,
+                    uint32_t rows, uint32_t row0, int format, uint32_t k, uint32_t tolerance, void *d_delta, kmg_frame_hold *d_info,
+                    hipStream_t st);
+
 // An image between a caller's (pageable) buffer and the device, ordered on `st` (kmg_api.hip): small images asynchronously,
 // large ones as synchronous row-range copies on several streams of the processor.
 hipError_t copy_host_image(kmg_processor *p, void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t st);

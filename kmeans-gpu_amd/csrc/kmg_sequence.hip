@@ -14,7 +14,8 @@
 //                    and box stay in registers, are reduced per wave with cross-lane operations, across the waves through LDS,
 //                    and leave the workgroup as one integer atomicAdd / atomicMin / atomicMax per field that has something to say.
 //   kmg_sequence     host object: the working sequence W (one device block, grown geometrically), the palette step on it, and
-//                    the frame output -- one apply plan, the frame buffers and the canvas in one block.
+//                    the frame output -- one apply plan, the frame buffers, the canvas and its held source (lossy frames:
+//                    kmg_hold.hip) in one block.
 
 #include "kmg_device.h"
 #include "kmg_state.h"
@@ -231,10 +232,13 @@ struct kmg_sequence {
     kmg_apply_plan *plan = nullptr;
     uint32_t k = 0, width = 0, height = 0;
     int mode = 0, format = KMG_FORMAT_RGBA8;
-    void *o_blk = nullptr;           // frame | map | canvas | delta map | record
+    void *o_blk = nullptr;           // frame | map | canvas | delta map | held source | record
     size_t o_cap = 0;
     uint8_t *d_frame = nullptr, *d_map = nullptr, *d_canvas = nullptr, *d_delta = nullptr;
-    kmg_frame_delta *d_info = nullptr;
+    // index formats: the held source of the canvas (kmg_dev_frame_delta_lossy).  After an exact frame it IS that frame, so the two
+    // buffers swap instead of a copy.
+    uint8_t *d_held = nullptr;
+    kmg_frame_hold *d_info = nullptr;    // (an exact frame uses its first 32 bytes: a kmg_frame_delta)
 };
 
 namespace {
@@ -449,12 +453,13 @@ try {
     const size_t n = (size_t)width * height, es = format_bytes(format);
     const bool indexed = format != KMG_FORMAT_RGBA8;
     const size_t frame_b = pad256(n * 4), map_b = pad256(n * es);
-    HIP_TRY(block_take(p, frame_b + map_b * (indexed ? 3u : 1u) + 256, &s->o_blk, &s->o_cap));
+    HIP_TRY(block_take(p, frame_b + map_b * (indexed ? 3u : 1u) + (indexed ? frame_b : 0u) + 256, &s->o_blk, &s->o_cap));
     s->d_frame = (uint8_t *)s->o_blk;
     s->d_map = s->d_frame + frame_b;
     s->d_canvas = indexed ? s->d_map + map_b : nullptr;
     s->d_delta = indexed ? s->d_canvas + map_b : nullptr;
-    s->d_info = (kmg_frame_delta *)(s->d_map + map_b * (indexed ? 3u : 1u));
+    s->d_held = indexed ? s->d_delta + map_b : nullptr;                // (a canvas of k holds nothing: no fill)
+    s->d_info = (kmg_frame_hold *)(s->d_map + map_b * (indexed ? 3u : 1u) + (indexed ? frame_b : 0u));
     if ((rc = kmg_apply_plan_create_format(p, c4.data(), k, mode, format, n, st, &s->plan)) != KMG_OK) {
         s->plan = nullptr;
         output_end(s);
@@ -500,14 +505,17 @@ try {
     if (delta) {
         HIP_TRY(hipMemsetAsync(s->d_info, 0, sizeof(kmg_frame_delta), st));            // the fresh record: zero sums and maxima,
         HIP_TRY(hipMemsetAsync(&s->d_info->x0, 0xFF, 2 * sizeof(uint32_t), st));      // all-ones minima
-        if ((rc = frame_delta_impl(p, s->d_map, s->d_canvas, s->width, s->height, 0, s->format, s->k, s->d_delta, s->d_info, st)) != KMG_OK) {
+        if ((rc = frame_delta_impl(p, s->d_map, s->d_canvas, s->width, s->height, 0, s->format, s->k, s->d_delta,
+                                   reinterpret_cast<kmg_frame_delta *>(s->d_info), st)) != KMG_OK) {
             (void)hipStreamSynchronize(st);
             return rc;
         }
+        std::swap(s->d_frame, s->d_held);                              // the canvas equals this frame's map: its held source is this frame
         HIP_TRY(hipMemcpyAsync(&rec, s->d_info, sizeof rec, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     } else if (s->d_canvas) {
         HIP_TRY(hipMemcpyAsync(s->d_canvas, s->d_map, map_bytes, hipMemcpyDeviceToDevice, st));   // a later delta frame starts from this one
+        std::swap(s->d_frame, s->d_held);
     }
     const bool full = !delta || rec.cleared > 0;                       // "over" cannot show a pixel that turns transparent
     HIP_TRY(copy_host_image(p, out, full ? s->d_map : s->d_delta, map_bytes, hipMemcpyDeviceToHost, st));
@@ -515,6 +523,51 @@ try {
     if ((rc = kmg_apply_plan_status(s->plan)) != KMG_OK) return rc;
     if (info) *info = rec;
     if (is_full) *is_full = full ? 1 : 0;
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_sequence_output_frame_lossy(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, uint32_t tolerance, void *out,
+                                               kmg_frame_hold *info, int *is_full)
+try {
+    int rc;
+    if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
+    if (!s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "no output is open (kmg_sequence_output_begin)");
+    if (!rgba || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame_lossy: a pointer is NULL");
+    if (flags & ~KMG_FRAME_DELTA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
+    if (!(flags & KMG_FRAME_DELTA)) return fail(KMG_ERR_INVALID_ARGUMENT, "a lossy frame is a delta frame: KMG_FRAME_DELTA is required");
+    if (s->format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8");
+    if (!info || !is_full) return fail(KMG_ERR_INVALID_ARGUMENT, "KMG_FRAME_DELTA needs info and is_full");
+    kmg_processor *p = s->p;
+    hipStream_t st = s->sg.st;
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t n = (size_t)s->width * s->height, map_bytes = n * format_bytes(s->format);
+    HIP_TRY(copy_host_image(p, s->d_frame, rgba, n * 4, hipMemcpyHostToDevice, st));
+    if (s->mode == KMG_MODE_DIFFUSE) apply_plan_restart(s->plan);      // every frame is an image of its own
+    if ((rc = kmg_apply_plan_run(s->plan, s->d_frame, s->width, s->height, 0, s->d_map, st)) != KMG_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    kmg_frame_hold rec = {0, 0, kFresh, kFresh, 0, 0, 0, 0};
+    HIP_TRY(hipMemsetAsync(s->d_info, 0, sizeof(kmg_frame_hold), st));                 // the fresh record: zero sums and maxima,
+    HIP_TRY(hipMemsetAsync(&s->d_info->x0, 0xFF, 2 * sizeof(uint32_t), st));          // all-ones minima
+    if ((rc = frame_hold_impl(p, s->d_frame, s->d_map, s->d_canvas, s->d_held, s->width, s->height, 0, s->format, s->k, tolerance, s->d_delta,
+                              s->d_info, st)) != KMG_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(&rec, s->d_info, sizeof rec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const bool full = rec.cleared > 0;                                 // "over" cannot show a pixel that turns transparent
+    if (full) {                                                        // the viewer then shows I_t everywhere: the state of an exact frame
+        HIP_TRY(hipMemcpyAsync(s->d_canvas, s->d_map, map_bytes, hipMemcpyDeviceToDevice, st));
+        std::swap(s->d_frame, s->d_held);
+    }
+    HIP_TRY(copy_host_image(p, out, full ? s->d_map : s->d_delta, map_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = kmg_apply_plan_status(s->plan)) != KMG_OK) return rc;
+    *info = rec;
+    *is_full = full ? 1 : 0;
     return KMG_OK;
 }
 KMG_ABI_CATCH

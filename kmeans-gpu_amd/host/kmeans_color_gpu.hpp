@@ -13,6 +13,8 @@
 //   processor.compare(source, output[, colors])            -> kmg_error_stats: exact error sums of an output against its source
 //   processor.reduce_quality(image, max_delta_e, k_min, k_max, mode) -> the colour count chosen by a quality target
 //   processor.set_fixed_colors(colors)                     -> palette entries the k-means keeps exactly and builds around
+//   Sequence seq(processor); seq.add(frame) ...; seq.output(k, mode, w, h); seq.frame(image) / seq.frame_lossy(image, delta_e)
+//                                                          -> one palette for many frames, exact and lossy delta frames (kmg_sequence_*)
 // `anyhow::Result` errors become kmeans_color_gpu::Error exceptions carrying the kmg_status and the
 // library's message.  Header only; link with -lkmeans_hip.
 #pragma once
@@ -295,6 +297,80 @@ private:
     }
     kmg_processor *p_;
     kmg_group *g_;
+};
+
+// Frame sequences (include/kmeans_hip.h kmg_sequence; single-device processors only, which outlive their sequences): one palette for
+// all frames added, then every frame as an INDEX8 map (k <= 255; index k is the transparent slot) -- a delta map against what is
+// shown, or the full map when a shown pixel turns transparent.  frame_lossy: a pixel whose source stays within max_delta_e (dE76) of
+// the source it was last written for keeps what it shows (kmg_sequence_output_frame_lossy, tolerance = rint(4096 max_delta_e^2)); exact
+// and lossy frames may alternate.  Not re-entrant: one thread at a time per sequence.
+class Sequence {
+public:
+    struct Frame {
+        std::vector<uint8_t> map;     // width x height indices: the delta map, or -- is_full -- the full map
+        kmg_frame_hold info;          // an exact frame leaves held = held_sse = 0
+        bool is_full = false;
+    };
+    explicit Sequence(const ImageProcessor &processor) : s_(nullptr)
+    {
+        if (processor.group()) throw Error(KMG_ERR_INVALID_ARGUMENT, "a sequence needs a single-device processor");
+        check(kmg_sequence_create(processor.handle(), &s_));
+    }
+    ~Sequence() { kmg_sequence_destroy(s_); }
+    Sequence(const Sequence &) = delete;
+    Sequence &operator=(const Sequence &) = delete;
+
+    void add(const Image &image) { check(kmg_sequence_add(s_, reinterpret_cast<const uint8_t *>(image.rgba.data()), image.dims.first, image.dims.second)); }
+    // opens the frame output; returns the palette in index order
+    std::vector<RGBA8> output(uint32_t color_count, ReduceMode reduce_mode, uint32_t width, uint32_t height)
+    {
+        std::vector<RGBA8> palette(color_count ? color_count : 1);
+        uint32_t n = 0;
+        check(kmg_sequence_output_begin(s_, color_count, (int)reduce_mode, KMG_FORMAT_INDEX8, width, height,
+                                        reinterpret_cast<uint8_t *>(palette.data()), &n));
+        palette.resize(n);
+        pixels_ = (size_t)width * height;
+        return palette;
+    }
+    Frame frame(const Image &image, bool delta = true)
+    {
+        Frame f = start(image);
+        kmg_frame_delta rec = {0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0};
+        int full = 1;
+        check(kmg_sequence_output_frame(s_, reinterpret_cast<const uint8_t *>(image.rgba.data()), delta ? KMG_FRAME_DELTA : 0u, f.map.data(), &rec, &full));
+        f.info = kmg_frame_hold{rec.changed, rec.cleared, rec.x0, rec.y0, rec.x1, rec.y1, 0, 0};
+        f.is_full = full != 0;
+        return f;
+    }
+    Frame frame_lossy(const Image &image, double max_delta_e)
+    {
+        const double t = std::nearbyint(4096.0 * max_delta_e * max_delta_e);
+        if (!(max_delta_e >= 0.0) || t > 4294967295.0) throw Error(KMG_ERR_INVALID_ARGUMENT, "frame_lossy: the tolerance does not fit 32 bits");
+        Frame f = start(image);
+        int full = 0;
+        check(kmg_sequence_output_frame_lossy(s_, reinterpret_cast<const uint8_t *>(image.rgba.data()), KMG_FRAME_DELTA, (uint32_t)t, f.map.data(),
+                                              &f.info, &full));
+        f.is_full = full != 0;
+        return f;
+    }
+    void end_output() { pixels_ = 0; check(kmg_sequence_output_end(s_)); }
+    kmg_sequence *handle() const { return s_; }
+
+private:
+    Frame start(const Image &image) const
+    {
+        if (!pixels_) throw Error(KMG_ERR_INVALID_ARGUMENT, "no output is open (Sequence::output)");
+        if (image.rgba.size() != pixels_) throw Error(KMG_ERR_INVALID_ARGUMENT, "the frame does not have the size the output was opened for");
+        Frame f;
+        f.map.resize(pixels_);
+        return f;
+    }
+    static void check(int rc)
+    {
+        if (rc != KMG_OK) throw Error(rc, kmg_last_error());
+    }
+    kmg_sequence *s_;
+    size_t pixels_ = 0;
 };
 
 }  // namespace kmeans_color_gpu

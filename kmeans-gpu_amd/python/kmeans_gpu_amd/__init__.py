@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "Sequence", "FrameDelta", "FRAME_DELTA", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -151,6 +151,54 @@ class FrameDelta(C.Structure):          # include/kmeans_hip.h kmg_frame_delta: 
         return "FrameDelta" + repr(self.as_tuple())
 
 
+MAX_TOLERANCE = 347973309               # the largest D of two sRGB8 colours (include/kmeans_hip.h at kmg_dev_frame_delta_lossy)
+
+
+class FrameHold(C.Structure):           # include/kmeans_hip.h kmg_frame_hold: 48 bytes -- a kmg_frame_delta, then held and held_sse
+    _fields_ = FrameDelta._fields_ + [("held", C.c_uint64), ("held_sse", C.c_uint64)]
+
+    FRESH = FrameDelta.FRESH + (0, 0)                   # what the caller writes before a frame
+
+    def as_tuple(self):
+        return (int(self.changed), int(self.cleared), int(self.x0), int(self.y0), int(self.x1), int(self.y1), int(self.held),
+                int(self.held_sse))
+
+    @classmethod
+    def from_array(cls, a):
+        """from the 48 bytes of a record read back from device memory (any dtype)"""
+        return cls.from_buffer_copy(np.ascontiguousarray(a).tobytes()[:48])
+
+    @classmethod
+    def fresh_bytes(cls):
+        """the 48 bytes of the fresh record"""
+        return bytes(cls(*cls.FRESH))
+
+    @property
+    def rect(self):
+        """(x0, y0, x1, y1) of the pixels sent, x1 / y1 exclusive; None when none was"""
+        return None if int(self.changed) == 0 else (int(self.x0), int(self.y0), int(self.x1), int(self.y1))
+
+    @property
+    def held_delta_e_rms(self):
+        """root mean square dE76 of the held pixels against their anchors: sqrt(held_sse / (4096 held))"""
+        n = int(self.held)
+        return float(np.sqrt(int(self.held_sse) / (4096.0 * n))) if n else 0.0
+
+    def __repr__(self):
+        return "FrameHold" + repr(self.as_tuple())
+
+
+def tolerance_of(delta_e):
+    """a dE76 distance as the `tolerance` of the lossy delta calls: rint(4096 dE^2); ValueError when negative or beyond a uint32"""
+    de = float(delta_e)
+    if not de >= 0.0:
+        raise ValueError(f"a tolerance is a distance >= 0, not {delta_e!r}")
+    t = int(np.rint(4096.0 * de * de)) if de * de < 2.0 ** 40 else 1 << 52
+    if t > 0xFFFFFFFF:
+        raise ValueError(f"dE = {delta_e!r} gives a tolerance beyond 32 bits (every pair of colours is within dE {np.sqrt(MAX_TOLERANCE / 4096.0):.1f})")
+    return t
+
+
 # kmg_options.strategy (include/kmeans_hip.h KMG_STRATEGY_*): results are identical either way, only the time differs
 STRATEGY_AUTO, STRATEGY_SCAN, STRATEGY_TABLE, STRATEGY_MASK_WORDS = 0, 1, 2, 4
 _STRATEGY_NAMES = {"auto": STRATEGY_AUTO, "scan": STRATEGY_SCAN, "brute": STRATEGY_SCAN, "table": STRATEGY_TABLE}
@@ -225,8 +273,8 @@ SYMBOLS = [
     "kmg_find_indexed", "kmg_reduce_indexed", "kmg_apply_plan_create_format", "kmg_dev_apply_format",
     "kmg_dither_threshold", "kmg_dev_compare", "kmg_compare", "kmg_reduce_quality",
     "kmg_sequence_create", "kmg_sequence_destroy", "kmg_sequence_add", "kmg_sequence_add_device", "kmg_sequence_clear",
-    "kmg_sequence_info", "kmg_sequence_centroids", "kmg_sequence_palette", "kmg_dev_frame_delta", "kmg_sequence_output_begin",
-    "kmg_sequence_output_frame", "kmg_sequence_output_end",
+    "kmg_sequence_info", "kmg_sequence_centroids", "kmg_sequence_palette", "kmg_dev_frame_delta", "kmg_dev_frame_delta_lossy",
+    "kmg_sequence_output_begin", "kmg_sequence_output_frame", "kmg_sequence_output_frame_lossy", "kmg_sequence_output_end",
     "kmg_default_group_options", "kmg_group_create", "kmg_group_unique_id", "kmg_group_create_rank", "kmg_group_destroy",
     "kmg_group_info", "kmg_group_processor", "kmg_group_stream", "kmg_group_palette", "kmg_group_find", "kmg_group_reduce",
     "kmg_group_reduce_batch", "kmg_group_lloyd_create", "kmg_group_lloyd_destroy", "kmg_group_lloyd_bind",
@@ -355,6 +403,8 @@ def lib():
     L.kmg_dev_frame_delta.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp]
     L.kmg_sequence_output_begin.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, u8p, C.POINTER(C.c_uint32)]
     L.kmg_sequence_output_frame.argtypes = [vp, u8p, C.c_uint32, vp, C.POINTER(FrameDelta), C.POINTER(C.c_int)]
+    L.kmg_dev_frame_delta_lossy.argtypes = [vp, u8p, vp, vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.kmg_sequence_output_frame_lossy.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, vp, C.POINTER(FrameHold), C.POINTER(C.c_int)]
     L.kmg_sequence_output_end.argtypes = [vp]
     L.kmg_default_group_options.argtypes = [C.POINTER(GroupOptions)]
     L.kmg_default_group_options.restype = None
@@ -723,6 +773,16 @@ class ImageProcessor:
         _check(lib().kmg_dev_frame_delta(self._h, C.c_void_p(d_index), C.c_void_p(d_canvas), int(width), int(rows), int(row0), int(format),
                                          int(k), C.c_void_p(d_delta), C.c_void_p(d_info), C.c_void_p(stream)))
 
+    def frame_delta_lossy(self, d_src_rgba, d_index, d_canvas, d_held_rgba, width, rows, row0, format, k, tolerance, d_delta, d_info,
+                          stream=0):
+        """kmg_dev_frame_delta_lossy: the delta pass with a tolerance -- a pixel that shows a colour, stays opaque and whose source
+        is within `tolerance` (1/4096 dE76^2) of its held source keeps its canvas index; every other pixel follows the exact rule and
+        takes the source as its held source.  COMBINES into the 48-byte record at d_info (device; the caller writes FrameHold.FRESH
+        before a frame).  Only enqueues."""
+        _check(lib().kmg_dev_frame_delta_lossy(self._h, C.c_void_p(d_src_rgba), C.c_void_p(d_index), C.c_void_p(d_canvas),
+                                               C.c_void_p(d_held_rgba), int(width), int(rows), int(row0), int(format), int(k), int(tolerance),
+                                               C.c_void_p(d_delta), C.c_void_p(d_info), C.c_void_p(stream)))
+
     def debug_block_counts(self):
         """(device blocks allocated with hipMalloc so far, blocks handed out again)"""
         out = (C.c_uint64 * 2)()
@@ -833,9 +893,11 @@ class Sequence:
         self._out = (int(k), int(format), int(width), int(height))
         return pal[:cnt.value].copy()
 
-    def frame(self, image, delta=True):
+    def frame(self, image, delta=True, tolerance=None):
         """kmg_sequence_output_frame: (map, FrameDelta, is_full).  delta=True: the delta map against the frames shown so far
-        (index k = unchanged), or -- is_full -- the full map when a shown pixel turns transparent; delta=False: the full map."""
+        (index k = unchanged), or -- is_full -- the full map when a shown pixel turns transparent; delta=False: the full map.
+        tolerance (an integer in 1/4096 dE76^2, see tolerance_of): kmg_sequence_output_frame_lossy -- a pixel whose source stays
+        within it of the source it was last sent for keeps what it shows; the record then is a FrameHold.  Needs delta=True."""
         if self._out is None:
             raise KmgError(-1, "no output is open (Sequence.output)")
         k, fmt, w, h = self._out
@@ -846,6 +908,14 @@ class Sequence:
             out = np.empty((h, w, 4), np.uint8)
         else:
             out = np.empty((h, w), np.uint8 if fmt == OutputFormat.Index8 else np.uint16)
+        if tolerance is not None:
+            tol = int(tolerance)
+            if tol < 0 or tol > 0xFFFFFFFF:
+                raise KmgError(-1, f"tolerance {tolerance!r} is not a uint32")
+            hold, full = FrameHold(*FrameHold.FRESH), C.c_int(1)
+            _check(lib().kmg_sequence_output_frame_lossy(self._h, _np_ptr(img), FRAME_DELTA if delta else 0, tol,
+                                                         out.ctypes.data_as(C.c_void_p), C.byref(hold), C.byref(full)))
+            return out, hold, bool(full.value)
         info, full = FrameDelta(*FrameDelta.FRESH), C.c_int(1)
         _check(lib().kmg_sequence_output_frame(self._h, _np_ptr(img), FRAME_DELTA if delta else 0, out.ctypes.data_as(C.c_void_p),
                                                C.byref(info), C.byref(full)))

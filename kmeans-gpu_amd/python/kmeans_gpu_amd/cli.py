@@ -17,10 +17,13 @@ per-channel MSE, PSNR, dE76 RMS and max; kmg_compare).  `reduce --max-error DE [
 few colours between A (default 2) and `-c` as keep the dE76 RMS of the palette step's working image at or below DE
 (kmg_reduce_quality, k-means only); the line then also gives the count chosen and whether the target was reached.
 
-`sequence -i A.png B.png ... -c K [-m replace|dither|diffuse] [-o out.png] [--alpha-cutoff T] [--no-delta] [--delay-ms 100]`
-quantises several frames of one size with ONE palette (kmg_sequence_*) and writes a palette-mode APNG (kmeans_gpu_amd/apng.py):
-delta frames -- the rectangle of the pixels that changed, blended "over" -- unless --no-delta asks for full frames.  K <= 255: the
-transparent slot takes the last palette entry.
+`sequence -i A.png B.png ... -c K [-m replace|dither|diffuse] [-o out.png] [--alpha-cutoff T] [--no-delta] [--lossy DE] [--report]
+[--delay-ms 100]` quantises several frames of one size with ONE palette (kmg_sequence_*) and writes a palette-mode APNG
+(kmeans_gpu_amd/apng.py): delta frames -- the rectangle of the pixels that changed, blended "over" -- unless --no-delta asks for
+full frames.  K <= 255: the transparent slot takes the last palette entry.  `--lossy DE` (a dE76 distance >= 0) makes the delta
+frames lossy (kmg_sequence_output_frame_lossy with tolerance = rint(4096 DE^2)): a pixel whose source stays within DE of the source it
+was last written for keeps what it shows, so noise and dither flicker no longer fill the delta frames; not with --no-delta.
+`--report` prints the changed (and held) pixels of every frame.
 
 `palette`, `reduce` and `sequence` also take `--fixed "#RRGGBB,..."|palette.png` (the palette syntax of `find`): colours the k-means
 palette keeps exactly, as its first entries in index order (the PLTE of `--indexed` and of `sequence`), while the other entries
@@ -164,17 +167,25 @@ def run_sequence(args, ap):
         for f in frames:
             seq.add(f)
         colors = seq.output(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h)
-        coded, n_full, n_changed = [], 0, 0
-        for f in frames:
-            index, info, is_full = seq.frame(f, delta=not args.no_delta)
+        coded, n_full, n_changed, n_held, lines = [], 0, 0, 0, []
+        for i, f in enumerate(frames):
+            index, info, is_full = seq.frame(f, delta=not args.no_delta, tolerance=args.lossy)
             coded.append((index, info.rect, is_full))
             n_full += 1 if is_full else 0
             n_changed += int(info.changed)
+            line = f"Frame {i}: changed={int(info.changed)}"
+            if args.lossy is not None:
+                n_held += int(info.held)
+                line += f" held={int(info.held)} held dE76 rms={info.held_delta_e_rms:.3f}"
+            lines.append(line + (" (written in full)" if is_full else ""))
         seq.end_output()
     apng.write(out_path, colors, w, h, coded, delay_ms=args.delay_ms)
     print("Palette: " + ",".join(f"#{c[0]:02X}{c[1]:02X}{c[2]:02X}" for c in colors))
     print(f"Sequence: {len(frames)} frames of {w}x{h}, {n_full} written in full"
-          + ("" if args.no_delta else f", {n_changed} changed pixels in the delta frames") + f": {out_path}")
+          + ("" if args.no_delta else f", {n_changed} changed pixels in the delta frames")
+          + ("" if args.lossy is None else f", {n_held} held") + f": {out_path}")
+    if args.report:
+        print("\n".join(lines))
     return 0
 
 
@@ -206,6 +217,15 @@ def validate_max_error(s):
     if not 0.0 <= v <= 1000.0:
         raise argparse.ArgumentTypeError(f"{v} is not in 0..=1000")
     return v
+
+
+def validate_lossy(s):
+    """--lossy DE: a dE76 distance as the tolerance of the lossy delta frames, rint(4096 DE^2) as a uint32"""
+    from . import tolerance_of
+    try:
+        return tolerance_of(float(s))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"invalid value '{s}': {e}")
 
 
 def report_line(stats, chosen=None, reached=None):
@@ -256,6 +276,9 @@ def main(argv=None):
     q.add_argument("-o", "--output", type=validate_filename)
     q.add_argument("-m", "--mode", choices=["replace", "dither", "diffuse"], default="replace")
     q.add_argument("--no-delta", action="store_true", help="write every frame in full instead of the rectangle of its changes")
+    q.add_argument("--lossy", type=validate_lossy, default=None, metavar="DE",
+                   help="lossy delta frames: a pixel whose source stays within dE76 DE of the source it was last written for keeps what it shows")
+    q.add_argument("--report", action="store_true", help="print the changed (and, with --lossy, the held) pixels of every frame")
     q.add_argument("--delay-ms", type=validate_delay, default=100, help="display time of every frame in milliseconds (default 100)")
     for s in (p, f, r, q):
         s.add_argument("--alpha-cutoff", type=validate_alpha_cutoff, default=0,
@@ -284,6 +307,8 @@ def main(argv=None):
     if args.command == "sequence":
         if args.devices:
             ap.error("`sequence` is not supported with --devices")
+        if args.lossy is not None and args.no_delta:
+            ap.error("--lossy makes the delta frames lossy: it cannot be combined with --no-delta")
         if args.colorcount > 255:
             ap.error(f"`sequence` writes a palette APNG of at most 255 colours plus the transparent slot; {args.colorcount} requested")
         out_path = sequence_file_path(args.colorcount, args.mode, args.output, args.input[0])

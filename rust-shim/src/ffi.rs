@@ -81,6 +81,42 @@ pub struct kmg_error_stats {
     pub lab_max: u64,
 }
 
+/// Opaque `kmg_sequence`: one palette for many frames, and their index maps as delta frames (include/kmeans_hip.h).
+#[repr(C)]
+pub struct kmg_sequence {
+    _private: [u8; 0],
+}
+
+/// `kmg_sequence_output_frame*` flags.
+pub const KMG_FRAME_DELTA: u32 = 1;
+
+/// `kmg_frame_delta` (include/kmeans_hip.h): 32 bytes; the fresh record is {0, 0, u32::MAX, u32::MAX, 0, 0}.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct kmg_frame_delta {
+    pub changed: u64,
+    pub cleared: u64,
+    pub x0: u32,
+    pub y0: u32,
+    pub x1: u32,
+    pub y1: u32,
+}
+
+/// `kmg_frame_hold` (include/kmeans_hip.h): 48 bytes -- the fields of `kmg_frame_delta`, then the pixels a lossy delta frame held
+/// and the sum of their distances D (1/4096 dE76^2) to their anchors.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct kmg_frame_hold {
+    pub changed: u64,
+    pub cleared: u64,
+    pub x0: u32,
+    pub y0: u32,
+    pub x1: u32,
+    pub y1: u32,
+    pub held: u64,
+    pub held_sse: u64,
+}
+
 extern "C" {
     pub fn kmg_last_error() -> *const c_char;
     pub fn kmg_version() -> *const c_char;
@@ -180,6 +216,40 @@ extern "C" {
         achieved: *mut kmg_error_stats,
         reached: *mut c_int,
     ) -> c_int;
+    // frame sequences (no counterpart in the reference): a shared palette, then every frame as a full, an exact delta or a lossy
+    // delta index map (`tolerance` in 1/4096 dE76^2; `out` holds 4, 1 or 2 bytes per pixel for the format of `_output_begin`)
+    pub fn kmg_sequence_create(p: *mut kmg_processor, out: *mut *mut kmg_sequence) -> c_int;
+    pub fn kmg_sequence_destroy(s: *mut kmg_sequence);
+    pub fn kmg_sequence_add(s: *mut kmg_sequence, rgba: *const u8, width: u32, height: u32) -> c_int;
+    pub fn kmg_sequence_clear(s: *mut kmg_sequence) -> c_int;
+    pub fn kmg_sequence_output_begin(
+        s: *mut kmg_sequence,
+        k: u32,
+        mode: c_int,
+        format: c_int,
+        width: u32,
+        height: u32,
+        out_palette_rgba: *mut u8,
+        out_count: *mut u32,
+    ) -> c_int;
+    pub fn kmg_sequence_output_frame(
+        s: *mut kmg_sequence,
+        rgba: *const u8,
+        flags: u32,
+        out: *mut (),
+        info: *mut kmg_frame_delta,
+        is_full: *mut c_int,
+    ) -> c_int;
+    pub fn kmg_sequence_output_frame_lossy(
+        s: *mut kmg_sequence,
+        rgba: *const u8,
+        flags: u32,
+        tolerance: u32,
+        out: *mut (),
+        info: *mut kmg_frame_hold,
+        is_full: *mut c_int,
+    ) -> c_int;
+    pub fn kmg_sequence_output_end(s: *mut kmg_sequence) -> c_int;
     // ImageProcessor::new over a device list (the reference is single-device: lib.rs:38-65) and the same three calls, the image
     // tiled in row bands over the devices, the k x 4 sums of a sharded Lloyd loop all-reduced by RCCL inside the library
     pub fn kmg_default_group_options(opt: *mut kmg_group_options);
