@@ -1,0 +1,1586 @@
+"""TEST HARNESS: model-based random call sequences over the surface the lifecycle harness does not know -- alpha mode, index output,
+error statistics and reduce_quality, frame sequences, fixed colours, lossy delta frames -- on ONE long-lived processor
+(tests/test_session_model.py on the CPU, tools/fuzz_session.py and tests/test_gpu_session.py on the device).  A sibling of
+tests/lifecycle_harness.py, from which it takes KgEnv's memory interface, Mismatch, the guard bytes and the generate / Runner /
+replay / run_sequence shape with plain-tuple ops and a printed replay(...) line on failure.
+
+Every call is a pure function of (pixels, switches as they were when the call -- or the object the call belongs to -- started), so
+a stateless model built from tests/oracle_lib.py, alpha_ref, diffuse_ref, fixed_ref, error_ref, sequence_ref and hold_ref predicts
+every byte.  What the model tracks is what the ABI defines as state: the three switches; the cutoff each added frame was compacted
+under; cutoff, k, centroids, mode and format an open output was begun with; canvas and held source of every open output and of
+every caller-owned buffer pair; the running combination of the caller's error record; each Lloyd object's n_fixed.  One sequence
+uses one processor, two Lloyd objects, two Sequence objects and two caller-owned canvas pairs, closed and re-created in each
+other's blocks.
+
+  generate(seed, seq)  -> list of plain tuples (deterministic; a dry Model keeps every op legal or a listed refusal)
+  Runner(env).run(ops) -> executes them on a backend, checks everything the op could have touched, raises Mismatch
+  replay(env, seed, seq, ops) -> the same for a list printed by a failing run
+
+What the generator never emits, because include/kmeans_hip.h leaves it open or because the lifecycle harness owns it:
+  - a pixel buffer that changes while a Lloyd object is bound to it (every image stays resident in a buffer of its own and is
+    never rewritten), cell shares, partial sums, kmg_lloyd_prepare;
+  - a Lloyd pass before the centroids were set, converged_count before an update, set_fixed above k, more seeds than k;
+  - a palette step whose working image is empty, other than the listed refusal on a sequence;
+  - kmg_dev_compare with an INDEX8 map of k = 256 under a cutoff argument, k = 0, `what` = 0;
+  - a frame of another size than the open output's; bands of an apply plan out of order in KMG_MODE_DIFFUSE;
+  - the octree (other than its refusal under fixed colours), meld with an index format (other than its refusal), the group layer;
+  - delta bands that overlap or leave rows out: the bands of a frame tile it exactly once.
+The 1024 x 1024 image enters host calls and kmg_dev_compare only, and only under the forced colour-table strategy.  The images
+are this harness's own (make_images here): frames of one size in families, alpha bytes that fill every cutoff class, a frame above
+the shrink limit -- lifecycle_harness.make_images has none of these.  Every sequence mixes random ops with short directed passages
+(the motif_* functions of generate), so that each way the state could be mishandled is exercised in every few sequences."""
+import collections
+
+import numpy as np
+
+import oracle_lib as O
+import alpha_ref
+import diffuse_ref
+import error_ref
+import fixed_ref
+import hold_ref
+import sequence_ref
+import lifecycle_harness as LH
+from lifecycle_harness import Mismatch, GUARD, PATTERN, MAX_ITERATIONS, CHECK_PERIOD, gamut_centroids, make_centroids, sorted_palette
+
+SHRINK = 256
+K_CLASSES = ((1, 2), (3, 32), (33, 255), (256, 256), (257, 512))
+CUTOFFS = (0, 1, 128, 255)
+STRATEGIES = (0, 1, 2)                               # auto, scan, table
+IMAGE_KINDS = ("odd", "odd_b", "sprite", "sprite_noisy", "sprite_shift", "few", "flat", "clear", "big", "mega", "row", "row_b", "col",
+               "col_b")
+ODD, SPRITE, FEW, FLAT, CLEAR, BIG, MEGA, ROW, COL = 0, 2, 5, 6, 7, 8, 9, 10, 12
+FAMILIES = ((0, 1), (2, 3, 4), (10, 11), (12, 13))   # images of one size: the frames of one output
+ERR_INVALID = -1
+REFUSALS = ("k_below_fixed_palette", "k_below_fixed_reduce", "k_below_fixed_sequence", "octree_fixed", "frame_no_output", "delta_on_rgba8",
+            "lossy_on_rgba8", "lossy_without_delta", "index8_full", "meld_indexed", "empty_sequence")
+TOLERANCES = (0, 40, 4096, 400000)                   # 1/4096 dE76^2: none, under the noise of the still frames, 1 dE, 10 dE
+# the fixed lists of set_fixed_colors: none; one colour; three with a duplicate pair; eight with alpha 0, alpha < 255 and a duplicate
+FIXED = (None,
+         ((200, 30, 40, 255),),
+         ((10, 10, 10, 255), (250, 250, 250, 255), (10, 10, 10, 255)),
+         ((0, 0, 0, 255), (255, 255, 255, 0), (255, 0, 0, 255), (0, 255, 0, 128), (0, 0, 255, 255), (255, 0, 0, 255), (128, 128, 128, 7),
+          (255, 255, 0, 255)))
+
+
+def k_class(k):
+    return next(i for i, (a, b) in enumerate(K_CLASSES) if a <= k <= b)
+
+
+def n_fixed_of(fid):
+    return 0 if FIXED[fid] is None else len(FIXED[fid])
+
+
+# ---- images ---------------------------------------------------------------------------------------------------------
+_images = {}
+
+
+def make_images(seed, seq):
+    """[(kind, (h, w, 4) uint8)] in the order of IMAGE_KINDS.  The smallest shapes at which the kernels branch: an odd-sized noise
+    frame and a still copy of it with noise under TOLERANCES[1]; a sprite with soft alpha edges, a noisy still copy and a shifted
+    one (pixels that showed a colour turn transparent); a few-colour and a flat image; a frame without a kept pixel; one frame
+    above the shrink limit; one of 2^20 pixels; a 1 x N and an N x 1 frame"""
+    if (seed, seq) not in _images:
+        if len(_images) > 2:
+            _images.clear()
+        _images[(seed, seq)] = _make_images(seed, seq)
+    return _images[(seed, seq)]
+
+
+def _blobs(rng, w, h):
+    c = rng.integers(0, 256, (int(rng.integers(4, 20)), 3))
+    a = np.full((h * w, 4), 255, np.uint8)
+    a[:, :3] = np.clip(c[rng.integers(0, c.shape[0], h * w)] + rng.normal(0, rng.uniform(3, 20), (h * w, 3)), 0, 255).astype(np.uint8)
+    return alpha_ref.soft_disc(a.reshape(h, w, 4))
+
+
+def _still(rng, a, amp):
+    b = a.copy()
+    b[..., :3] = np.clip(a[..., :3].astype(np.int64) + rng.integers(-amp, amp + 1, a[..., :3].shape), 0, 255).astype(np.uint8)
+    return b
+
+
+def _alpha(rng, n):
+    """alpha bytes with every cutoff class well filled: a seventh transparent, half opaque, the rest anything"""
+    a = rng.integers(0, 256, n)
+    r = rng.random(n)
+    return np.where(r < 0.15, 0, np.where(r < 0.6, 255, a)).astype(np.uint8)
+
+
+def _make_images(seed, seq):
+    rng = np.random.default_rng([seed, seq, 78])
+    odd = rng.integers(0, 256, (61, 97, 4), dtype=np.uint8)
+    odd[..., 3] = _alpha(rng, 61 * 97).reshape(61, 97)
+    sprite = alpha_ref.sprite(seed=int(rng.integers(1, 1000)))
+    pal = rng.integers(0, 256, (int(rng.integers(5, 10)), 4), dtype=np.uint8)
+    few = pal[rng.integers(0, pal.shape[0], 50 * 80)].reshape(50, 80, 4).copy()
+    few[..., 3] = 255                                             # (every pixel kept under every cutoff, as the flat one)
+    flat = np.tile(rng.integers(0, 256, (1, 1, 4), dtype=np.uint8), (48, 64, 1))
+    flat[..., 3] = 255
+    row = rng.integers(0, 256, (1, 131, 4), dtype=np.uint8)
+    row[..., 3] = rng.choice(np.array([0, 64, 200, 255], np.uint8), (1, 131))
+    col = rng.integers(0, 256, (131, 1, 4), dtype=np.uint8)
+    col[..., 3] = rng.choice(np.array([0, 64, 200, 255], np.uint8), (131, 1))
+    row_b, col_b = _still(rng, row, 1), _still(rng, col, 1)
+    row_b[0, 5:9, 3], col_b[7:11, 0, 3] = 0, 0                    # a few pixels turn transparent
+    out = [odd, _still(rng, odd, 1), sprite, _still(rng, sprite, 1), np.roll(sprite, (5, 9), (0, 1)), few, flat,
+           np.zeros((30, 40, 4), np.uint8), _blobs(rng, 300, 200), _blobs(rng, 1024, 1024), row, row_b, col, col_b]
+    return [(k, np.ascontiguousarray(a)) for k, a in zip(IMAGE_KINDS, out)]
+
+
+# ---- the stateless reference: every answer is a function of its arguments, cached per sequence -----------------------
+_label_tables = collections.OrderedDict()
+
+
+def _label_table(cent):
+    key = cent.tobytes()
+    if key not in _label_tables:
+        if len(_label_tables) > 1:
+            _label_tables.popitem(last=False)
+        _label_tables[key] = np.full(1 << 24, -1, np.int16)
+    return _label_tables[key]
+
+
+def diffuse_index(rgba, cent, t):
+    """(h, w) labels of KMG_MODE_DIFFUSE (include/kmeans_hip.h: lbl = the replace label of the adjusted colour c, o = its bytes),
+    alpha_ref.diffuse with the label kept: an excluded pixel takes no error and passes none on, its label is that of its own colour"""
+    rgba = np.ascontiguousarray(rgba, np.uint8)
+    h, w = rgba.shape[:2]
+    P = O.lab_to_rgba8(np.ascontiguousarray(cent[:, :3]))[:, :3].astype(np.int32)
+    table = _label_table(cent)
+
+    def labels(codes):
+        got = table[codes]
+        if (got < 0).any():
+            new = np.unique(codes[got < 0])
+            px = np.stack([new & 255, (new >> 8) & 255, (new >> 16) & 255, np.full_like(new, 255)], axis=1).astype(np.uint8)
+            table[new] = O.assign(O.rgb_to_lab(px), cent).astype(np.int16)
+            got = table[codes]
+        return got.astype(np.int64)
+
+    src = rgba[..., :3].astype(np.int32)
+    kept = rgba[..., 3] >= t
+    err = np.zeros((h + 1, w + 2, 3), np.int32)
+    out = np.empty((h, w), np.int64)
+    for d in range(w + 2 * (h - 1)):
+        y = np.arange(max(0, (d - w + 2) // 2), min(h - 1, d // 2) + 1)
+        x = d - 2 * y
+        ok = (x >= 0) & (x < w)
+        y, x = y[ok], x[ok]
+        if y.size == 0:
+            continue
+        kp = kept[y, x][:, None]
+        S = np.where(kp, 7 * err[y + 1, x] + 3 * err[y, x + 2] + 5 * err[y, x + 1] + err[y, x], 0)
+        tq = np.clip(16 * src[y, x] + ((S + 8) >> 4), 0, 4080)
+        c = ((tq + 8) >> 4).astype(np.int64)
+        lbl = labels(c[:, 0] | (c[:, 1] << 8) | (c[:, 2] << 16))
+        out[y, x] = lbl
+        err[y + 1, x + 1] = np.where(kp, tq - 16 * P[lbl], 0)
+    return out
+
+
+class Ref:
+    """the expected results, from the reference modules; `cache` is shared by the model and the stand-ins of one sequence"""
+
+    def __init__(self, images, cache=None):
+        self.images = images
+        self.cache = {} if cache is None else cache
+
+    def _memo(self, key, fn):
+        if key not in self.cache:
+            self.cache[key] = fn()
+        return self.cache[key]
+
+    def img(self, i):
+        return self.images[i][1]
+
+    def kept(self, i, t):
+        """K_i: (pixels (n, 4), sw, sh, every pixel kept) of image i after the shrink, under cutoff t"""
+        def make():
+            S = alpha_ref.shrink(O, self.img(i), SHRINK)
+            px = S.reshape(-1, 4)
+            K = px[px[:, 3] >= t] if t else px
+            return np.ascontiguousarray(K), S.shape[1], S.shape[0], K.shape[0] == px.shape[0]
+        return self._memo(("kept", i, t), make)
+
+    def working(self, frames):
+        """W of the frames ((image, cutoff at its add), ...): (pixels, width, height), None when empty"""
+        def make():
+            parts = [self.kept(i, t) for i, t in frames]
+            W = np.ascontiguousarray(np.concatenate([p[0] for p in parts], axis=0)) if parts else np.zeros((0, 4), np.uint8)
+            if W.shape[0] == 0:
+                return None
+            if len(parts) == 1 and parts[0][3]:
+                return W, parts[0][1], parts[0][2]
+            return W, W.shape[0], 1
+        return self._memo(("W", tuple(frames)), make)
+
+    def centroids_px(self, W, w, h, k, fid):
+        """the palette step on the working image W (w x h) with the fixed list `fid`: (k, 4) float32 in the Lloyd loop's order"""
+        def make():
+            if FIXED[fid] is None:
+                lab = O.rgb_to_lab(W)
+                return O.lloyd(lab, O.init_centroids(lab, w, h, k), MAX_ITERATIONS, CHECK_PERIOD)[0]
+            return fixed_ref.palette_centroids(O, W, w, h, k, np.array(FIXED[fid], np.uint8), max_iterations=MAX_ITERATIONS,
+                                               check_period=CHECK_PERIOD)[0]
+        return self._memo(("cent", hash(W.tobytes()), W.shape[0], w, h, k, fid), make)
+
+    def centroids(self, frames, k, fid):
+        W, w, h = self.working(frames)
+        return self.centroids_px(W, w, h, k, fid)
+
+    # -- Lloyd objects: passes over a whole image, every pixel counted
+    def lab(self, i):
+        return self._memo(("lab", i), lambda: O.rgb_to_lab(self.img(i).reshape(-1, 4)))
+
+    def assign(self, i, cent):
+        def make():
+            labels = O.assign(self.lab(i), cent)
+            return labels, O.accumulate(self.lab(i), labels, cent.shape[0])
+        return self._memo(("assign", i, cent.tobytes()), make)
+
+    def run(self, i, cent, f):
+        return self._memo(("run", i, cent.tobytes(), f), lambda: fixed_ref.lloyd(O, self.lab(i), cent, f, MAX_ITERATIONS, CHECK_PERIOD))
+
+    def seeded(self, i, k, f):
+        h, w = self.img(i).shape[:2]
+        seeds = fixed_ref.pins_lab(O, np.array(FIXED[3], np.uint8)[:f])
+        return self._memo(("seeded", i, k, f), lambda: fixed_ref.init_centroids(O, self.lab(i), w, h, k, seeds))
+
+    def rgba(self, rgba, cent, mode, t):
+        """the RGBA8 output of an output pass over a centroid table under cutoff t"""
+        def make():
+            if t:
+                return alpha_ref.apply(O, rgba, cent, mode, t)
+            return diffuse_ref.diffuse(rgba, diffuse_ref.oracle_apply_replace(O, cent)) if mode == 3 else O.apply(rgba, cent, mode)
+        return self._memo(("rgba", rgba.tobytes(), cent.tobytes(), mode, t), make)
+
+    def index(self, rgba, cent, mode, t):
+        """the index map of the same pass: (h, w) int64, k on the pixels below the cutoff"""
+        def make():
+            h, w = rgba.shape[:2]
+            if mode == 3:
+                idx = diffuse_index(rgba, cent, t)
+            else:
+                lab = O.rgb_to_lab(rgba.reshape(-1, 4))
+                idx = (O.assign(lab, cent) if mode == 0 else O.dither(lab, w, h, cent)).astype(np.int64).reshape(h, w)
+            if t:
+                idx = np.where(rgba[..., 3] >= t, idx, cent.shape[0])
+            return idx
+        return self._memo(("index", rgba.tobytes(), cent.tobytes(), mode, t), make)
+
+    def palette_bytes(self, cent):
+        return O.lab_to_rgba8(np.ascontiguousarray(cent[:, :3]))
+
+    def quality(self, i, t, fid, target, k_min, k_max):
+        """(k*, reached, record of W at k*) of kmg_reduce_quality's search"""
+        def make():
+            W, _, _ = self.working(((i, t),))
+            lab = O.rgb_to_lab(W)
+
+            def record(k):
+                cent = self.centroids(((i, t),), k, fid)
+                return error_ref.stats(O, W, O.assign(lab, cent), palette=self.palette_bytes(cent))
+            k, reached, _ = error_ref.bisect(lambda kk: record(kk)[12] <= target * W.shape[0], k_min, k_max)
+            return k, reached, record(k)
+        return self._memo(("quality", i, t, fid, target, k_min, k_max), make)
+
+    def stats(self, src, out, palette, cutoff, what):
+        pal = None if palette is None else np.ascontiguousarray(palette, np.uint8)
+        return self._memo(("stats", src.tobytes(), np.ascontiguousarray(out).tobytes(), None if pal is None else pal.tobytes(), cutoff, what),
+                          lambda: error_ref.stats(O, src, out, palette=pal, cutoff=cutoff, what=what))
+
+    def find_centroids(self, pal):
+        return fixed_ref.pins_lab(O, pal)
+
+    def delta(self, index, canvas, k):
+        return sequence_ref.delta(index, canvas, k)
+
+    def hold(self, src, index, canvas, held, k, tol):
+        return hold_ref.hold(O, src, index, canvas, held, k, tol)
+
+
+def find_palette(seed, k):
+    return gamut_centroids(seed, k)[1]
+
+
+def target_of(max_delta_e):
+    return min(int(np.floor(4096.0 * float(max_delta_e) * float(max_delta_e))), 0xFFFFFFFF)
+
+
+def index_dtype(fmt):
+    return np.uint8 if fmt == 1 else np.uint16
+
+
+def host_format(k, t):
+    """the format ImageProcessor._index_format picks"""
+    return 1 if k + (1 if t else 0) <= 256 else 2
+
+
+def bands_of(h, nb, order_seed):
+    """nb row bands that tile h rows exactly once, in a random order: [(row0, rows), ...]"""
+    nb = max(1, min(nb, h))
+    rng = np.random.default_rng([order_seed, h, nb])
+    cuts = sorted(rng.choice(np.arange(1, h), nb - 1, replace=False).tolist()) if nb > 1 else []
+    edges = [0] + cuts + [h]
+    bands = [(edges[j], edges[j + 1] - edges[j]) for j in range(nb)]
+    return [bands[int(j)] for j in rng.permutation(nb)]
+
+
+# ---- the model: legality state (dry) and, numeric, the expected results -----------------------------------------------
+class LSlot:
+    def __init__(self, k):
+        self.k, self.f = k, 0
+        self.cent = None
+        self.nconv = None
+        self.acc = None
+        self.bind = None          # image index the object may be bound to
+
+
+class SSlot:
+    def __init__(self):
+        self.frames = []          # (image, cutoff at the add)
+        self.out = None           # dict(t, k, cent, mode, fmt, fam, canvas, held, last)
+
+
+class Model:
+    def __init__(self, images, numeric, cache=None):
+        self.images, self.numeric = images, numeric
+        self.ref = Ref(images, cache)
+        self.t, self.fid, self.strategy = 0, 0, 0
+        self.lloyd = [None, None]
+        self.seq = [None, None]
+        self.pairs = [None, None]     # dict(fam, fmt, k, seed, mode, canvas, held, last)
+        self.rec = error_ref.ZERO
+
+    def n_kept(self, i, t):
+        """kept pixels of image i (before the shrink: the large images keep an opaque disc whatever the shrink does to its edge)"""
+        a = self.images[i][1]
+        return int((a[..., 3] >= t).sum()) if t else a.shape[0] * a.shape[1]
+
+    def seq_pixels(self, S):
+        return sum(min(self.n_kept(i, t), 65536) for i, t in self.seq[S].frames)
+
+    def frames_of(self, S):
+        return tuple(self.seq[S].frames)
+
+
+def lloyd_step(s, sums):
+    """one update of a Lloyd object with n_fixed = s.f from `sums`"""
+    s.cent, s.nconv = fixed_ref.step(O, sums, s.cent, s.f)
+
+
+# ---- the generator --------------------------------------------------------------------------------------------------
+def generate(seed, seq, n_ops=150):
+    """one sequence: a list of plain tuples"""
+    rng = np.random.default_rng([seed, seq, 3])
+    images = make_images(seed, seq)
+    m = Model(images, numeric=False)
+    ops = []
+
+    def emit(op):
+        ops.append(op)
+        apply_op(m, op)
+
+    def rint(a, b):
+        return int(rng.integers(a, b))
+
+    def pick(xs, p=None):
+        return xs[int(rng.choice(len(xs), p=p))]
+
+    def st():
+        return rint(0, 2)
+
+    def pick_k(classes=(0, 1, 2, 3, 4), p=(0.15, 0.4, 0.25, 0.1, 0.1), lo=1, hi=512):
+        for _ in range(50):
+            c = pick(list(classes), [x / sum(p[:len(classes)]) for x in p[:len(classes)]])
+            a, b = K_CLASSES[c]
+            k = pick([a, b]) if rng.random() < 0.3 else rint(a, b + 1)
+            if lo <= k <= hi:
+                return k
+        return max(lo, min(hi, 8))
+
+    def cap_k(n):
+        """the largest k the reference answers in reasonable time for a palette step on n pixels under the current fixed list (its
+        seeded initialisation is a Python loop over pixels x centroids)"""
+        if m.fid:
+            return max(200000 // max(n, 1), 1)
+        return 512 if n <= 8000 else 256 if n <= 70000 else 32
+
+    def host_image():
+        """an image for a host call: kept pixels under the current cutoff, the 2^20 one only under the forced colour table"""
+        pool = [ODD, SPRITE, 4, FEW, FLAT, BIG, ROW, COL] + ([MEGA] if m.strategy == 2 else [])
+        for _ in range(20):
+            i = pick(pool)
+            if m.n_kept(i, m.t) > 0:
+                return i
+        return FLAT
+
+    def host_k(i, fmt8=False):
+        f = n_fixed_of(m.fid)
+        hi = min(cap_k(min(m.n_kept(i, m.t), 65536)), 255 + (0 if m.t else 1) if fmt8 else 512)
+        if i == MEGA:
+            hi = min(hi, 32)
+        return None if hi < max(f, 1) else pick_k(lo=max(f, 1), hi=hi)
+
+    def switches():
+        c = rng.random()
+        if c < 0.45:
+            emit(("cutoff", pick([x for x in CUTOFFS if x != m.t])))
+        elif c < 0.8:
+            emit(("fixed", 0 if m.fid and rng.random() < 0.5 else pick([x for x in range(4) if x != m.fid])))
+            if rng.random() < 0.7:                        # the next palette step sees the new list, or none
+                emit(("palette", pick([FEW, FLAT]), n_fixed_of(m.fid) + rint(1, 7)))
+        else:
+            emit(("strategy", pick([x for x in STRATEGIES if x != m.strategy], None)))
+
+    def host():
+        c = rng.random()
+        i = host_image()
+        if c < 0.12:
+            k = host_k(i)
+            if k:
+                emit(("palette", i, k))
+        elif c < 0.27:
+            k = host_k(i)
+            mode = rint(0, 4)
+            if k and (i != MEGA or mode < 2):
+                emit(("reduce", i, k, mode if i not in (BIG,) or mode != 3 else 0))
+        elif c < 0.5:
+            k = host_k(i)
+            mode = pick([0, 1, 3]) if i not in (MEGA, BIG) else pick([0, 1])
+            if k:
+                emit(("reduce_indexed", i, k, mode, int(rng.random() < 0.5)))
+        elif c < 0.6:
+            if i in (MEGA, BIG):
+                i = ODD
+            emit(("find", i, pick_k(hi=300), rint(0, 4), rint(0, 1 << 30)))
+        elif c < 0.75:
+            if i in (MEGA, BIG):
+                i = SPRITE
+            emit(("find_indexed", i, pick_k(), pick([0, 1, 3]), rint(0, 1 << 30)))
+        else:
+            f = n_fixed_of(m.fid)
+            if i == MEGA:
+                i = BIG if m.n_kept(BIG, m.t) else FLAT
+            if cap_k(min(m.n_kept(i, m.t), 65536)) >= max(12, f):
+                k_min = max(pick([1, 2, 3]), f)
+                emit(("quality", i, pick([1.5, 4.0, 9.0, 30.0]), k_min, pick([max(k_min, 6), 12]), pick([0, 1, 3]) if i != BIG else 0,
+                      int(rng.random() < 0.6), int(rng.random() < 0.5)))
+
+    def device():
+        c = rng.random()
+        i = pick([ODD, 1, SPRITE, 3, 4, FEW, FLAT, ROW, COL])
+        if c < 0.3:
+            mode = rint(0, 4)
+            fmt = pick([None, 1, 2]) if mode != 2 else None
+            k = pick_k(hi=255 + (0 if m.t else 1)) if fmt == 1 else pick_k(hi=400)
+            emit(("apply", i, mode, fmt, k, rint(0, 1 << 30), st()))
+        elif c < 0.5:
+            mode = pick([0, 1, 3])
+            fmt = pick([None, 1, 2])
+            t_after = pick([x for x in CUTOFFS if x != m.t])
+            # (the plan keeps the cutoff it was made under: INDEX8 is sized for the cutoff of its creation)
+            k = pick_k(hi=255 + (0 if m.t else 1)) if fmt == 1 else pick_k(hi=400)
+            emit(("apply_plan", i, mode, fmt, k, rint(0, 1 << 30), t_after, st()))
+        elif c < 0.58:
+            emit(("compact", i, pick(list(CUTOFFS)), st()))
+        elif c < 0.8:
+            if m.strategy == 2 and rng.random() < 0.3:
+                i = MEGA
+            fmt = pick([None, 1, 2])
+            cut = pick([m.t, 0, 128])
+            k = pick_k(hi=255) if fmt == 1 else pick_k(hi=32 if i == MEGA else 400)
+            emit(("compare_device", i, pick([0, 1]), fmt, k, rint(0, 1 << 30), rint(1, 4), rint(0, 1 << 30), cut, pick([1, 2, 3, 3]),
+                  int(rng.random() < 0.6), st()))
+        else:
+            P = rint(0, 2)
+            if m.pairs[P] is None or rng.random() < 0.2:
+                fmt = pick([1, 2])
+                emit(("pair_open", P, rint(0, len(FAMILIES)), fmt, pick_k(hi=255) if fmt == 1 else pick_k(hi=400), rint(0, 1 << 30),
+                      pick([0, 1, 3])))
+            pr = m.pairs[P]
+            for _ in range(rint(2, 5)):
+                emit(("pair_frame", P, pick(list(FAMILIES[pr["fam"]])), pick([None] + list(TOLERANCES)), rint(1, 4), rint(0, 1 << 30), st()))
+
+    def lloyd_ops():
+        L = rint(0, 2)
+        s = m.lloyd[L]
+        if s is None:
+            emit(("l_new", L, pick_k()))
+            return
+        c = rng.random()
+        if c < 0.04:
+            emit(("l_close", L))
+            return
+        if c < 0.12 or (s.f and c < 0.3):
+            emit(("l_re", L, pick_k()))
+            if s.f:                                       # nothing is frozen in the new object, whatever its block's last owner froze
+                emit(("l_set", L, "rand", rint(0, 1 << 30), ODD))
+                emit(("l_assign_update", L, pick([ODD, FEW, ROW]), 1, 1, st()))
+            return
+        i = pick([ODD, SPRITE, FEW, FLAT, BIG, ROW])
+        n = images[i][1].shape[0] * images[i][1].shape[1]
+        if s.cent is None or c < 0.24:
+            if n * s.k <= 300000 and rng.random() < 0.7:
+                f = min(pick([0, 1, 3, 8]), s.k)
+                emit(("l_init", L, i, f, st()))
+                if f:
+                    emit(("l_fix", L, pick([f, f, min(f, 1)])))
+            else:
+                emit(("l_set", L, pick(["rand", "dup", "init"]), rint(0, 1 << 30), pick([ODD, FEW])))
+            return
+        if c < 0.34:
+            emit(("l_fix", L, 0 if s.f and rng.random() < 0.6 else pick([min(s.k, 1), min(s.k, 2), min(s.k, 3), min(s.k, 8)])))
+            if rng.random() < 0.6:
+                emit(("l_assign_update", L, pick([ODD, FEW, ROW]), 0, 1, st()))
+            return
+        if c < 0.44:
+            emit(("l_update", L, st()))
+        elif c < 0.58:
+            emit(("l_assign_update", L, i, rint(0, 2), rint(0, 2), st()))
+        elif c < 0.7:
+            if rng.random() < 0.5:
+                emit(("l_bind", L, i, st()))
+            emit(("l_iterate", L, i, rint(1, 4), st()))
+        elif c < 0.82:
+            emit(("l_run", L, i, rint(0, 2), st()))
+        elif c < 0.92 and s.k <= 256:
+            emit(("l_lftu", L, i, st()))
+        else:
+            emit(("l_assign", L, i, st()))
+        if m.lloyd[L].nconv is not None and rng.random() < 0.3:
+            emit(("l_conv", L, st()))
+
+    def seq_k(S, fmt):
+        f = n_fixed_of(m.fid)
+        hi = min(cap_k(m.seq_pixels(S)), 255 if fmt == 1 else 512)
+        return None if hi < max(f, 1) else pick_k(lo=max(f, 1), hi=hi)
+
+    def sequence_ops():
+        S = rint(0, 2)
+        q = m.seq[S]
+        if q is None:
+            emit(("s_new", S))
+            return
+        c = rng.random()
+        if c < 0.04:
+            emit(("s_close", S))
+            return
+        if c < 0.3 or not q.frames:
+            if len(q.frames) >= 5:
+                emit(("s_clear", S))
+            i = pick([ODD, 1, SPRITE, 3, 4, FEW, FLAT, BIG, ROW, COL, CLEAR], None)
+            if i == CLEAR and m.t == 0:
+                i = SPRITE
+            emit(("s_add", S, i, int(i != BIG and rng.random() < 0.4), st()))
+            if rng.random() < 0.4:
+                emit(("s_info", S))
+            return
+        if c < 0.36:
+            emit(("s_clear", S))
+            if rng.random() < 0.4:                        # a first frame that loses pixels, a clear, then one whole frame
+                if m.t == 0:
+                    emit(("cutoff", pick([1, 128, 255])))
+                emit(("s_add", S, SPRITE, 0, 0))
+                emit(("s_clear", S))
+                if m.fid:
+                    emit(("fixed", 0))
+                emit(("s_add", S, FEW, rint(0, 2), st()))
+                emit(("s_centroids", S, rint(3, 7)))
+                return
+            emit(("s_info", S))
+            if rng.random() < 0.7:                        # one whole frame after the clear: an image of its own size again
+                if m.fid and rng.random() < 0.5:
+                    emit(("fixed", 0))                    # (with a fixed colour the size does not enter the initialisation)
+                emit(("s_add", S, pick([FEW, SPRITE, ODD]) if m.t == 0 else FEW, 0, 0))
+                k = seq_k(S, 2)
+                if k:
+                    emit(("s_centroids", S, min(k, 24)))
+            return
+        if m.seq_pixels(S) == 0:
+            emit(("refuse", "empty_sequence", S, 4))
+            emit(("s_add", S, SPRITE if m.n_kept(SPRITE, m.t) else FLAT, 0, 0))
+            return
+        if c < 0.46:
+            k = seq_k(S, 2)
+            if k:
+                emit(("s_centroids" if rng.random() < 0.5 else "s_palette", S, k))
+            return
+        if q.out is None or c < (0.6 if q.out["last"] else 0.5):
+            mode = rint(0, 4)
+            fmt = pick([1, 1, 2]) if mode != 2 else 0
+            if mode != 2 and rng.random() < 0.12:
+                fmt = 0
+            k = seq_k(S, fmt)
+            if k:
+                fam = q.out["fam"] if q.out is not None and rng.random() < 0.6 else rint(0, len(FAMILIES))
+                emit(("s_output", S, k, mode, fmt, fam))
+                if fmt:                                   # against the fresh canvas the first delta is the full map
+                    emit(("s_frame", S, pick(list(FAMILIES[fam])), 1, pick([None, 40])))
+            return
+        if c < 0.64:
+            emit(("s_end", S))
+            return
+        fam = FAMILIES[q.out["fam"]]
+        if q.out["fmt"] and rng.random() < 0.5:           # another frame, the base frame, then its still copy within a tolerance
+            emit(("s_frame", S, fam[-1], 1, None))
+            emit(("s_frame", S, fam[0], rint(0, 2), None))
+            emit(("s_frame", S, fam[1], 1, pick([40, 4096])))
+            if rng.random() < 0.5:
+                emit(("s_frame", S, fam[0], 1, None))
+            return
+        if q.out["fmt"] and rng.random() < 0.4:           # rewritten under a tolerance: the anchor moves with the pixel
+            emit(("s_frame", S, fam[0], 1, None))
+            emit(("s_frame", S, fam[-1], 1, 40))
+            emit(("s_frame", S, fam[1], 1, 4096))
+            return
+        for _ in range(rint(1, 4)):
+            if m.seq[S].out["fmt"] == 0:
+                emit(("s_frame", S, pick(list(fam)), 0, None))
+            else:
+                tol = pick([None, None, None] + list(TOLERANCES))
+                emit(("s_frame", S, pick(list(fam)), 1 if tol is not None or rng.random() < 0.8 else 0, tol))
+
+    def refusal(what=None):
+        what = pick(list(REFUSALS)) if what is None else what
+        f = n_fixed_of(m.fid)
+        if what.startswith("k_below_fixed") or what == "octree_fixed":
+            if f < 2:
+                emit(("fixed", pick([2, 3])))
+                f = n_fixed_of(m.fid)
+            i = SPRITE if m.n_kept(SPRITE, m.t) else FLAT
+            if what == "k_below_fixed_sequence":
+                S = rint(0, 2)
+                if m.seq[S] is None:
+                    emit(("s_new", S))
+                if m.seq_pixels(S) == 0:
+                    emit(("s_add", S, i, 0, 0))
+                if m.seq_pixels(S) > 20000:
+                    return
+                emit(("refuse", what, S, f - 1))
+                emit(("s_palette", S, f + 1))
+            else:
+                emit(("refuse", what, i, f - 1 if what != "octree_fixed" else f + 2))
+                emit(("palette" if what != "k_below_fixed_reduce" else "reduce", i, f + 2) + ((0,) if what == "k_below_fixed_reduce" else ()))
+            return
+        if what == "index8_full":
+            i = pick([ODD, FLAT])
+            emit(("refuse", what, i, 256 if m.t else 257))
+            emit(("apply", i, 0, 1, 255 if m.t else 256, rint(0, 1 << 30), st()))
+            return
+        if what == "meld_indexed":
+            emit(("refuse", what, FLAT, 5))
+            emit(("apply", FLAT, 0, 2, 5, rint(0, 1 << 30), st()))
+            return
+        if what == "empty_sequence":
+            if m.t == 0:
+                emit(("cutoff", pick([1, 128, 255])))
+            S = rint(0, 2)
+            emit(("s_new", S) if m.seq[S] is None else ("s_clear", S))
+            emit(("s_add", S, CLEAR, 0, 0))
+            emit(("refuse", what, S, 4))
+            emit(("s_add", S, FLAT, 0, 0))
+            emit(("s_palette", S, 2 + n_fixed_of(m.fid)))
+            return
+        # the frame refusals
+        S = rint(0, 2)
+        if m.seq[S] is None:
+            emit(("s_new", S))
+        if m.seq_pixels(S) == 0:
+            emit(("s_add", S, SPRITE if m.n_kept(SPRITE, m.t) else FLAT, 0, 0))
+        if cap_k(m.seq_pixels(S)) < max(f, 1) + 1:
+            return
+        k = max(f, 1) + 1
+        if what == "frame_no_output":
+            if m.seq[S].out is not None:
+                emit(("s_end", S))
+            emit(("refuse", what, S, SPRITE))
+            emit(("s_output", S, k, 0, 1, 1))
+            emit(("s_frame", S, SPRITE, 1, None))
+        else:
+            emit(("s_output", S, k, 0, 0 if what != "lossy_without_delta" else 1, 1))
+            emit(("refuse", what, S, 3))
+            emit(("s_frame", S, 3, 0, None))
+
+    # ---- motifs: short directed passages, most of them in every sequence, at random places between the random ops
+    def small_sequence(S):
+        """sequence S with a small working sequence of kept pixels, whatever it held"""
+        emit(("s_new", S) if m.seq[S] is None else ("s_clear", S))
+        emit(("s_add", S, SPRITE if m.n_kept(SPRITE, m.t) else FEW, rint(0, 2), st()))
+
+    def motif_reoutput():
+        """an output with frames, ended, a Lloyd object in the returned block, an output of another k and format: a fresh canvas"""
+        S, f = rint(0, 2), n_fixed_of(m.fid)
+        small_sequence(S)
+        emit(("s_output", S, f + rint(2, 30), pick([0, 1, 3]), 1, 1))
+        for i, tol in ((2, None), (3, 40), (4, 4096), (2, None))[:rint(2, 5)]:
+            emit(("s_frame", S, i, 1, tol))
+        if rng.random() < 0.6:
+            emit(("s_end", S))
+            if m.lloyd[0] is None and rng.random() < 0.7:
+                emit(("l_new", 0, pick_k()))
+                emit(("l_set", 0, "rand", rint(0, 1 << 30), ODD))
+                emit(("l_run", 0, FEW, 1, st()))
+                emit(("l_close", 0))
+        emit(("s_output", S, f + rint(2, 30) if rng.random() < 0.5 else min(f + rint(257, 400), cap_k(m.seq_pixels(S))), pick([0, 1]), 2, 1))
+        emit(("s_frame", S, pick([2, 3]), 1, pick([None, 40])))
+
+    def motif_anchor():
+        """exact and lossy frames alternate: the held source is the frame that wrote the pixel, and moves when the pixel is rewritten"""
+        S, f = rint(0, 2), n_fixed_of(m.fid)
+        small_sequence(S)
+        emit(("s_output", S, f + rint(2, 40), pick([0, 1, 3]), pick([1, 2]), 1))
+        emit(("s_frame", S, 4, 1, None))
+        emit(("s_frame", S, 2, rint(0, 2), None))
+        emit(("s_frame", S, 3, 1, pick([40, 4096])))
+        emit(("s_frame", S, 4, 1, 40))
+        emit(("s_frame", S, 3, 1, 4096))
+        emit(("s_frame", S, 2, 1, None))
+
+    def motif_growth():
+        """a working sequence that outgrows its block several times, frames from both sides"""
+        S = rint(0, 2)
+        emit(("s_new", S) if m.seq[S] is None else ("s_clear", S))
+        for i in (ROW, COL, FEW, BIG if m.fid < 2 else ODD)[:rint(3, 5)]:
+            emit(("s_add", S, i, int(i != BIG and rng.random() < 0.5), st()))
+        emit(("s_info", S))
+        emit(("s_centroids", S, n_fixed_of(m.fid) + rint(2, 6)))
+
+    def motif_first_frame():
+        """a first frame that loses pixels, a clear, then one whole frame: an image of its own size again"""
+        S = rint(0, 2)
+        emit(("s_new", S) if m.seq[S] is None else ("s_clear", S))
+        if m.t == 0:
+            emit(("cutoff", pick([1, 128, 255])))
+        emit(("s_add", S, SPRITE, 0, 0))
+        emit(("s_clear", S))
+        if m.fid:
+            emit(("fixed", 0))                            # (with a fixed colour the size does not enter the initialisation)
+        emit(("s_add", S, FEW, rint(0, 2), st()))
+        emit(("s_centroids", S, rint(3, 7)))
+
+    def motif_freeze():
+        """seeds frozen and run; a new object in the same block, nothing frozen; frozen, unfrozen, updated"""
+        L = rint(0, 2)
+        emit(("l_new" if m.lloyd[L] is None else "l_re", L, rint(4, 40)))
+        emit(("l_init", L, pick([FEW, ROW, SPRITE]), 3, st()))
+        emit(("l_fix", L, 3))
+        for carrier in rng.permutation(5)[:rint(1, 4)]:           # every update carrier leaves the frozen three alone
+            i = pick([FEW, ROW, SPRITE])
+            emit([("l_run", L, i, 1, st()), ("l_update", L, st()), ("l_assign_update", L, i, 1, 1, st()), ("l_iterate", L, i, rint(1, 4), st()),
+                  ("l_lftu", L, i, st())][int(carrier)])
+            if m.lloyd[L].nconv is not None and rng.random() < 0.5:
+                emit(("l_conv", L, st()))
+        emit(("l_re", L, rint(3, 300)))
+        emit(("l_set", L, "rand", rint(0, 1 << 30), ODD))
+        emit(("l_assign_update", L, ODD, 1, 1, st()))
+        emit(("l_fix", L, 2))
+        emit(("l_fix", L, 0))
+        emit(("l_assign_update", L, ODD, 0, 1, st()))
+
+    def motif_pins():
+        """pins set, a quality search, pins cleared, the same search again"""
+        i = FEW
+        emit(("fixed", pick([2, 3])))
+        f = n_fixed_of(m.fid)
+        args = (i, pick([4.0, 9.0]), f, f + 6, 0, rint(0, 2), 0)
+        emit(("quality",) + args)
+        emit(("fixed", 0))
+        emit(("quality",) + args)
+        emit(("palette", i, rint(2, 9)))
+
+    def motif_cutoff():
+        """a plan and an open output made under one cutoff, run under another: each keeps its own"""
+        S, f = rint(0, 2), n_fixed_of(m.fid)
+        if m.t == 0:
+            emit(("cutoff", pick([1, 128, 255])))
+        small_sequence(S)
+        emit(("s_output", S, f + rint(2, 20), pick([0, 1, 3]), pick([1, 2]), pick([0, 1])))
+        i = FAMILIES[m.seq[S].out["fam"]][0]
+        emit(("apply_plan", i, pick([0, 1, 3]), pick([1, 2]), rint(2, 200), rint(0, 1 << 30), 0, st()))
+        emit(("s_frame", S, i, 1, None))
+        emit(("reduce_indexed", i, f + rint(2, 12), pick([0, 1, 3]), 1))
+
+    def motif_mixed():
+        """frames added under different cutoffs: each keeps the pixels its own cutoff kept"""
+        S = rint(0, 2)
+        emit(("s_new", S) if m.seq[S] is None else ("s_clear", S))
+        for i in (SPRITE, ODD, 4):
+            emit(("cutoff", pick([x for x in CUTOFFS if x != m.t])))
+            if m.n_kept(i, m.t):
+                emit(("s_add", S, i, rint(0, 2), st()))
+        emit(("s_info", S))
+        k = seq_k(S, 2)
+        if k:
+            emit(("s_palette" if rng.random() < 0.5 else "s_centroids", S, min(k, 40)))
+
+    def motif_refusals():
+        for j in rng.permutation(len(REFUSALS))[:3]:
+            refusal(REFUSALS[int(j)])
+
+    motifs = [mo for mo in (motif_mixed, motif_refusals, motif_cutoff, motif_reoutput, motif_anchor, motif_growth, motif_first_frame, motif_freeze, motif_pins) if rng.random() < 0.75]
+    at = sorted(rint(3, n_ops - 5) for _ in motifs)
+    motifs = [motifs[int(j)] for j in rng.permutation(len(motifs))]
+    emit(("strategy", pick([2, 0, 1], [0.5, 0.3, 0.2])))
+    while len(ops) < n_ops or motifs:
+        if motifs and len(ops) >= at[0]:
+            at.pop(0)
+            motifs.pop(0)()
+            continue
+        r = rng.random()
+        if r < 0.1:
+            switches()
+        elif r < 0.27:
+            host()
+        elif r < 0.52:
+            device()
+        elif r < 0.74:
+            lloyd_ops()
+        elif r < 0.96:
+            sequence_ops()
+        else:
+            refusal()
+    for L in range(2):
+        if m.lloyd[L] is not None:
+            emit(("l_close", L))
+    for S in range(2):
+        if m.seq[S] is not None:
+            emit(("s_close", S))
+    return ops
+
+
+# ---- one op on the model ----------------------------------------------------------------------------------------------
+def apply_op(m, op):
+    """advances the model by `op`; numeric: returns what the runner compares"""
+    name, num, R = op[0], m.numeric, m.ref
+    exp = {}
+    if name == "cutoff":
+        m.t = op[1]
+    elif name == "fixed":
+        m.fid = op[1]
+    elif name == "strategy":
+        m.strategy = op[1]
+    elif name in ("palette", "reduce", "reduce_indexed"):
+        i, k = op[1], op[2]
+        assert k >= n_fixed_of(m.fid) and m.n_kept(i, m.t) > 0, op
+        if num:
+            cent = R.centroids(((i, m.t),), k, m.fid)
+            if name == "palette":
+                exp["palette"] = sorted_palette(cent)
+            elif name == "reduce":
+                exp["image"] = R.rgba(R.img(i), cent, op[3], m.t)
+            else:
+                exp["palette"] = R.palette_bytes(cent)
+                exp["index"] = R.index(R.img(i), cent, op[3], m.t)
+                exp["image"] = R.rgba(R.img(i), cent, op[3], m.t)
+    elif name in ("find", "find_indexed"):
+        i, k, mode, seed = op[1:5]
+        if num:
+            pal = find_palette(seed, k)
+            if name == "find":
+                exp["image"] = (alpha_ref.find(O, R.img(i), pal, mode, m.t) if m.t else
+                                diffuse_ref.diffuse(R.img(i), diffuse_ref.oracle_find_replace(O, pal)) if mode == 3 else O.find(R.img(i), pal, mode))
+            else:
+                exp["index"] = R.index(R.img(i), R.find_centroids(pal), mode, m.t)
+    elif name == "quality":
+        i, dE, k_min, k_max, mode, indexed = op[1:7]
+        assert k_min >= n_fixed_of(m.fid), op
+        if num:
+            k, reached, rec = R.quality(i, m.t, m.fid, target_of(dE), k_min, k_max)
+            cent = R.centroids(((i, m.t),), k, m.fid)
+            exp.update(k=k, reached=reached, stats=rec, palette=R.palette_bytes(cent))
+            exp["out"] = R.index(R.img(i), cent, mode, m.t) if indexed else R.rgba(R.img(i), cent, mode, m.t)
+    elif name in ("apply", "apply_plan"):
+        i, mode, fmt, k, seed = op[1:6]
+        assert fmt != 1 or k + (1 if m.t else 0) <= 256, op
+        if num:
+            cent, _ = gamut_centroids(seed, k)
+            exp["cent"] = cent
+            exp["out"] = R.rgba(R.img(i), cent, mode, m.t) if fmt is None else R.index(R.img(i), cent, mode, m.t)
+        if name == "apply_plan":
+            m.t = op[6]
+    elif name == "compact":
+        if num:
+            exp["kept"] = alpha_ref.compact(R.img(op[1]), op[2])
+    elif name == "compare_device":
+        i, other, fmt, k, seed, nb, order, cut, what, fresh = op[1:11]
+        if num:
+            cent, _ = gamut_centroids(seed, k)
+            src = R.img(i)
+            exp["cent"] = cent
+            exp["out"] = R.rgba(src, cent, 0, m.t) if fmt is None else R.index(src, cent, 0, m.t)
+            exp["palette"] = None if fmt is None else R.palette_bytes(cent)
+            if fresh:
+                m.rec = error_ref.ZERO
+            m.rec = error_ref.combine(m.rec, R.stats(src, exp["out"], exp["palette"], cut, what))
+            exp["record"] = m.rec
+    elif name == "pair_open":
+        P, fam, fmt, k, seed, mode = op[1:7]
+        assert fmt != 1 or k <= 255, op
+        h, w = m.images[FAMILIES[fam][0]][1].shape[:2]
+        m.pairs[P] = dict(fam=fam, fmt=fmt, k=k, seed=seed, mode=mode, canvas=np.full((h, w), k, np.int64), held=np.zeros((h, w, 4), np.uint8),
+                          last=None)
+    elif name == "pair_frame":
+        P, i, tol = op[1:4]
+        pr = m.pairs[P]
+        assert pr is not None and i in FAMILIES[pr["fam"]], op
+        if num:
+            cent, _ = gamut_centroids(pr["seed"], pr["k"])
+            src = R.img(i)
+            I = R.index(src, cent, pr["mode"], m.t)
+            exp.update(cent=cent, index=I)
+            if tol is None:
+                d, pr["canvas"], rec = R.delta(I, pr["canvas"], pr["k"])
+                pr["held"] = src.copy()                              # (the caller's duty after an exact frame)
+                rec = tuple(rec) + (0, 0)
+            else:
+                d, pr["canvas"], pr["held"], rec = R.hold(src, I, pr["canvas"], pr["held"], pr["k"], tol)
+            exp.update(delta=d, canvas=pr["canvas"], held=pr["held"], record=tuple(rec))
+        pr["last"] = "exact" if tol is None else "lossy"
+    elif name in ("l_new", "l_re"):
+        m.lloyd[op[1]] = LSlot(op[2])
+        if num:
+            m.lloyd[op[1]].acc = np.zeros((op[2], 4), np.int64)
+    elif name == "l_close":
+        m.lloyd[op[1]] = None
+    elif name.startswith("l_"):
+        s = m.lloyd[op[1]]
+        assert s is not None, op
+        if name == "l_set":
+            s.cent = make_centroids(op[2], op[3], s.k, m.images[op[4]][1]) if num else True
+        elif name == "l_init":
+            i, f = op[2], op[3]
+            assert f <= s.k
+            h, w = m.images[i][1].shape[:2]
+            forced = {0: 0, 1: -1, 2: 1}[m.strategy]
+            s.bind = None if (s.k == 1 or forced < 0) else i
+            s.nconv = None
+            s.cent = R.seeded(i, s.k, f) if num else True
+            exp["cent"] = s.cent
+        elif name == "l_fix":
+            assert op[2] <= s.k
+            s.f = op[2]
+        elif name == "l_bind":
+            s.bind = op[2]
+        elif name == "l_conv":
+            assert s.nconv is not None
+            exp["nconv"] = s.nconv
+        else:
+            assert s.cent is not None, op
+            if name == "l_update":
+                if num:
+                    lloyd_step(s, s.acc)
+                    exp["cent"] = s.cent
+                else:
+                    s.nconv = True
+            elif name == "l_assign":
+                if num:
+                    exp["labels"], s.acc = R.assign(op[2], s.cent)
+            elif name == "l_assign_update":
+                if num:
+                    labels, s.acc = R.assign(op[2], s.cent)
+                    if op[3]:
+                        exp["labels"] = labels
+                    if op[4]:
+                        lloyd_step(s, s.acc)
+                    exp["cent"] = s.cent
+                elif op[4]:
+                    s.nconv = True
+            elif name == "l_iterate":
+                if num:
+                    for _ in range(op[3]):
+                        lloyd_step(s, s.acc)
+                        labels, s.acc = R.assign(op[2], s.cent)
+                    exp.update(labels=labels, cent=s.cent)
+                s.nconv = s.nconv if num else True
+            elif name == "l_run":
+                if num:
+                    s.cent, labels, it = R.run(op[2], s.cent, s.f)
+                    exp.update(cent=s.cent, iterations=it)
+                    if op[3]:
+                        exp["labels"] = labels
+                s.nconv = None
+                s.bind = None
+            elif name == "l_lftu":
+                assert s.k <= 256
+                s.bind = op[2]
+                if num:
+                    exp["labels"], sums = R.assign(op[2], s.cent)
+                    lloyd_step(s, sums)
+                    s.acc = np.zeros_like(s.acc)
+                    exp["cent"] = s.cent
+                else:
+                    s.nconv = True
+            else:
+                raise ValueError(op)
+    elif name == "s_new":
+        assert m.seq[op[1]] is None
+        m.seq[op[1]] = SSlot()
+    elif name == "s_close":
+        m.seq[op[1]] = None
+    elif name.startswith("s_"):
+        q = m.seq[op[1]]
+        assert q is not None, op
+        if name == "s_add":
+            q.frames.append((op[2], m.t))
+        elif name == "s_clear":
+            q.frames = []
+        elif name == "s_info":
+            if num:
+                exp["info"] = (len(q.frames), sum(R.kept(i, t)[0].shape[0] for i, t in q.frames))
+        elif name in ("s_centroids", "s_palette"):
+            assert op[2] >= n_fixed_of(m.fid) and m.seq_pixels(op[1]) > 0, op
+            if num:
+                cent = R.centroids(m.frames_of(op[1]), op[2], m.fid)
+                exp["cent" if name == "s_centroids" else "palette"] = cent if name == "s_centroids" else sorted_palette(cent)
+        elif name == "s_output":
+            k, mode, fmt, fam = op[2:6]
+            assert k >= n_fixed_of(m.fid) and m.seq_pixels(op[1]) > 0 and (fmt != 1 or k <= 255) and (fmt == 0 or mode != 2), op
+            h, w = m.images[FAMILIES[fam][0]][1].shape[:2]
+            q.out = dict(t=m.t, k=k, mode=mode, fmt=fmt, fam=fam, cent=None, canvas=np.full((h, w), k, np.int64), held=np.zeros((h, w, 4), np.uint8),
+                         last=None, shape=(h, w))
+            if num:
+                q.out["cent"] = R.centroids(m.frames_of(op[1]), k, m.fid)
+                exp["palette"] = R.palette_bytes(q.out["cent"])
+        elif name == "s_end":
+            q.out = None
+        elif name == "s_frame":
+            i, delta, tol = op[2:5]
+            o = q.out
+            assert o is not None and i in FAMILIES[o["fam"]] and (o["fmt"] != 0 or (not delta and tol is None)) and (tol is None or delta), op
+            kind = "exact" if tol is None else "lossy"
+            exp["transition"] = None if o["last"] in (None, kind) else o["last"] + ">" + kind
+            o["last"] = kind
+            if num:
+                src = R.img(i)
+                if o["fmt"] == 0:
+                    exp.update(map=R.rgba(src, o["cent"], o["mode"], o["t"]), record=sequence_ref.FRESH, full=True)
+                    return exp
+                I = R.index(src, o["cent"], o["mode"], o["t"])
+                if tol is None:
+                    d, canvas, rec = R.delta(I, o["canvas"], o["k"])
+                    held = src.copy()
+                    full = (not delta) or rec[1] > 0
+                    if not delta:
+                        rec = sequence_ref.FRESH
+                else:
+                    d, canvas, held, rec = R.hold(src, I, o["canvas"], o["held"], o["k"], tol)
+                    full = rec[1] > 0
+                    if full:
+                        canvas, held = I.copy(), src.copy()
+                o["canvas"], o["held"] = canvas, held
+                exp.update(map=I if full else d, record=tuple(rec), full=full, fallback=bool(delta and full))
+        else:
+            raise ValueError(op)
+    elif name == "refuse":
+        exp["status"] = ERR_INVALID
+        what = op[1]
+        if what in ("k_below_fixed_palette", "k_below_fixed_reduce", "k_below_fixed_sequence"):
+            assert op[3] < n_fixed_of(m.fid), op
+        elif what == "octree_fixed":
+            assert n_fixed_of(m.fid) > 0, op
+        elif what == "frame_no_output":
+            assert m.seq[op[2]].out is None, op
+        elif what in ("delta_on_rgba8", "lossy_on_rgba8"):
+            assert m.seq[op[2]].out["fmt"] == 0, op
+        elif what == "lossy_without_delta":
+            assert m.seq[op[2]].out["fmt"] != 0, op
+        elif what == "index8_full":
+            assert op[3] + (1 if m.t else 0) == 257, op
+        elif what == "empty_sequence":
+            assert m.seq_pixels(op[2]) == 0 and m.seq[op[2]].frames, op
+    else:
+        raise ValueError(op)
+    return exp
+
+
+# ---- the runner -----------------------------------------------------------------------------------------------------
+def _bits(c):
+    return np.ascontiguousarray(c, np.float32).view(np.uint32)
+
+
+class Runner:
+    """executes ops on a backend and compares with the numeric model after every op"""
+
+    def __init__(self, env, seed, seq, counters=None, proc=None, cache=None):
+        self.env, self.mem = env, env.mem
+        self.images = make_images(seed, seq)
+        self.model = Model(self.images, numeric=True, cache=cache)
+        self.counters = counters if counters is not None else collections.Counter()
+        self.own_proc = proc is None
+        self.proc = env.session_processor() if proc is None else proc
+        for name, v in (("set_alpha_cutoff", 0), ("set_fixed_colors", None), ("set_strategy", 0)):      # (a caller's processor: a known start)
+            getattr(self.proc, name)(v)
+        self.pix = []
+        for _, a in self.images:
+            b = self.mem.alloc(a.size)
+            self.mem.write(b, 0, a.reshape(-1))
+            self.pix.append(b)
+        big = 4 << 20
+        self.out = self.mem.alloc(big + GUARD)
+        self.lab = self.mem.alloc(4 * 60000 + GUARD)
+        self.rec = self.mem.alloc(112 + GUARD)
+        self.mem.fill(self.rec, 0, 112 + GUARD, PATTERN)
+        self.mem.write(self.rec, 0, np.zeros(112, np.uint8))
+        self.count = self.mem.alloc(8)
+        self.acc, self.obj = [None, None], [None, None]
+        self.seqs = [None, None]
+        self.pairs = [None, None]
+        self.n_ops = 0
+
+    def close(self):
+        for o in self.obj + self.seqs:
+            if o is not None:
+                o.close()
+        self.obj, self.seqs = [None, None], [None, None]
+        if self.own_proc:
+            self.proc.close()
+
+    def fail(self, what, got=None, want=None):
+        detail = ""
+        if got is not None and want is not None:
+            got, want = np.asarray(got), np.asarray(want)
+            if got.shape == want.shape:
+                bad = np.flatnonzero(got.reshape(-1) != want.reshape(-1))
+                detail = f": {bad.size} of {got.size} differ, first at {bad[:4].tolist()}: got {got.reshape(-1)[bad[:4]].tolist()} want {want.reshape(-1)[bad[:4]].tolist()}"
+            else:
+                detail = f": shape {got.shape} against {want.shape}"
+        raise Mismatch(what + detail)
+
+    def same(self, what, got, want):
+        got, want = np.asarray(got), np.asarray(want)
+        if got.shape != want.shape or not np.array_equal(got, want):
+            self.fail(what, got, want)
+
+    def arm(self, buf, nbytes):
+        self.mem.fill(buf, 0, nbytes + GUARD, PATTERN)
+
+    def collect(self, buf, nbytes, dtype, what):
+        raw = self.mem.read(buf, 0, nbytes + GUARD)
+        if not (raw[nbytes:] == PATTERN).all():
+            self.fail(f"{what}: written past the end")
+        return raw[:nbytes].view(dtype)
+
+    def expect_status(self, status, fn, *args, **kw):
+        try:
+            fn(*args, **kw)
+        except self.env.Error as e:
+            if e.status != status:
+                self.fail(f"refused with status {e.status}, the header names {status}")
+            return
+        self.fail(f"a call the header refuses with status {status} was accepted")
+
+    def run(self, ops):
+        for i, op in enumerate(ops):
+            try:
+                self.step(op)
+            except Mismatch as e:
+                raise Mismatch(f"op {i} {op!r}: {e}") from None
+            except self.env.Error as e:
+                raise Mismatch(f"op {i} {op!r}: a legal call was refused: {e}") from None
+            self.n_ops += 1
+
+    def fixed_arg(self, fid):
+        return None if FIXED[fid] is None else np.array(FIXED[fid], np.uint8)
+
+    def count_k(self, k, fmt):
+        self.counters[f"k:{k_class(k)}:{ {None: 'rgba8', 0: 'rgba8', 1: 'index8', 2: 'index16'}[fmt] }"] += 1
+
+    def step(self, op):
+        env, m, name, C, proc = self.env, self.model, op[0], self.counters, self.proc
+        C["op:" + name] += 1
+        streams = env.streams
+        before_t = m.t
+        if name.startswith("l_"):
+            return self.step_lloyd(op)
+        if name.startswith("s_"):
+            return self.step_sequence(op)
+        if name == "refuse":
+            return self.step_refuse(op)
+        exp = apply_op(m, op)
+        if name == "cutoff":
+            proc.set_alpha_cutoff(op[1])
+        elif name == "fixed":
+            C[f"fixed:{op[1]}"] += 1
+            proc.set_fixed_colors(self.fixed_arg(op[1]))
+        elif name == "strategy":
+            proc.set_strategy(op[1])
+        elif name == "palette":
+            self.count_k(op[2], None)
+            self.same("palette", proc.palette(op[2], self.images[op[1]][1], 0), exp["palette"])
+        elif name == "reduce":
+            self.count_k(op[2], None)
+            self.same(f"reduce (mode {op[3]})", proc.reduce(op[2], self.images[op[1]][1], 0, op[3]), exp["image"])
+        elif name == "reduce_indexed":
+            i, k, mode, cmp = op[1:5]
+            pal, idx = proc.reduce_indexed(k, self.images[i][1], 0, mode)
+            self.count_k(k, host_format(k, before_t))
+            self.same("palette of reduce_indexed", pal, exp["palette"])
+            if idx.dtype != index_dtype(host_format(k, before_t)):
+                self.fail(f"index type {idx.dtype}")
+            self.same(f"index map of reduce_indexed (mode {mode})", idx.astype(np.int64), exp["index"])
+            if cmp:                                       # the just-produced output against its source: both forms give one record
+                C["compare_host"] += 1
+                src = self.images[i][1]
+                want = m.ref.stats(src, exp["index"], exp["palette"], before_t, 3)
+                self.same("compare of an index map", proc.compare(src, idx, palette=pal).as_tuple(), want)
+                self.same("compare of the image", proc.compare(src, exp["image"]).as_tuple(), want)   # (index k: on uncounted pixels only)
+        elif name == "find":
+            self.same(f"find (mode {op[3]})", proc.find(self.images[op[1]][1], find_palette(op[4], op[2]), op[3]), exp["image"])
+        elif name == "find_indexed":
+            self.count_k(op[2], host_format(op[2], before_t))
+            got = proc.find_indexed(self.images[op[1]][1], find_palette(op[4], op[2]), op[3])
+            self.same(f"find_indexed (mode {op[3]})", got.astype(np.int64), exp["index"])
+        elif name == "quality":
+            i, dE, k_min, k_max, mode, indexed = op[1:7]
+            k, pal, out, stats, reached = proc.reduce_quality(self.images[i][1], dE, k_min, k_max, mode, bool(indexed))
+            if (k, reached) != (exp["k"], exp["reached"]):
+                self.fail(f"reduce_quality chose k = {k}, reached = {reached}; the model k = {exp['k']}, reached = {exp['reached']}")
+            self.same("palette of reduce_quality", pal, exp["palette"])
+            self.same("record of reduce_quality", stats.as_tuple(), exp["stats"])
+            self.same("output of reduce_quality", out.astype(np.int64) if indexed else out, exp["out"])
+            if op[7]:                                     # the switches are as they were: the same call again gives the same answer
+                k2, pal2, out2, _, _ = proc.reduce_quality(self.images[i][1], dE, k_min, k_max, mode, bool(indexed))
+                self.same("reduce_quality, again", out2.astype(np.int64) if indexed else out2, exp["out"])
+        elif name in ("apply", "apply_plan"):
+            self.step_apply(op, exp, before_t)
+        elif name == "compact":
+            i, cut, s = op[1:4]
+            n = self.images[i][1].shape[0] * self.images[i][1].shape[1]
+            self.arm(self.out, 4 * n)
+            proc.alpha_compact(self.pix[i].ptr, n, cut, self.out.ptr, self.count.ptr, streams[s])
+            env.sync()
+            got_n = int(self.mem.read(self.count, 0, 8).view(np.uint64)[0])
+            if got_n != exp["kept"].shape[0]:
+                self.fail(f"alpha_compact kept {got_n}, the model {exp['kept'].shape[0]}")
+            raw = self.collect(self.out, 4 * n, np.uint8, "alpha_compact")
+            self.same("alpha_compact", raw[:4 * got_n].reshape(-1, 4), exp["kept"])
+            if not (raw[4 * got_n:] == PATTERN).all():
+                self.fail("alpha_compact wrote behind the kept pixels")
+        elif name == "compare_device":
+            self.step_compare(op, exp, before_t)
+        elif name == "pair_open":
+            P, fam, fmt, k = op[1:5]
+            self.count_k(k, fmt)
+            pr = m.pairs[P]
+            h, w = pr["canvas"].shape
+            n, size = w * h, fmt
+            C["pair_reopened"] += int(self.pairs[P] is not None)
+            bufs = {"index": self.mem.alloc(size * n + GUARD), "canvas": self.mem.alloc(size * n + GUARD), "delta": self.mem.alloc(size * n + GUARD),
+                    "held": self.mem.alloc(4 * n + GUARD), "rec": self.mem.alloc(48 + GUARD)}
+            for b, nb in (("canvas", size * n), ("held", 4 * n), ("rec", 48)):
+                self.arm(bufs[b], nb)
+            self.mem.write(bufs["canvas"], 0, np.full(n, k, index_dtype(fmt)))
+            self.mem.write(bufs["held"], 0, np.zeros(4 * n, np.uint8))
+            self.pairs[P] = bufs
+        elif name == "pair_frame":
+            self.step_pair_frame(op, exp, before_t)
+        else:
+            raise ValueError(op)
+
+    # -- output passes under the switches
+    def check_output(self, what, fmt, w, h, exp_out):
+        size = {None: 4, 1: 1, 2: 2}[fmt]
+        if fmt is None:
+            self.same(what, self.collect(self.out, 4 * w * h, np.uint8, what).reshape(h, w, 4), exp_out)
+        else:
+            self.same(what, self.collect(self.out, size * w * h, index_dtype(fmt), what).astype(np.int64).reshape(h, w), exp_out)
+
+    def step_apply(self, op, exp, t0):
+        env, proc, C = self.env, self.proc, self.counters
+        i, mode, fmt, k, seed = op[1:6]
+        s = op[-1]
+        self.count_k(k, fmt)
+        img = self.images[i][1]
+        h, w = img.shape[:2]
+        size = {None: 4, 1: 1, 2: 2}[fmt]
+        self.arm(self.out, size * w * h)
+        p = self.pix[i].ptr
+        if op[0] == "apply_plan":
+            C["plan_outlives_cutoff"] += 1
+            pl = proc.apply_plan(exp["cent"], mode, w * h, env.streams[s], format=fmt)
+            try:
+                proc.set_alpha_cutoff(op[6])              # the plan keeps the cutoff it was made under
+                r = 1 + seed % (h - 1) if h > 1 else 1
+                pl.run(p, w, r, 0, self.out.ptr, env.streams[s])
+                if h > r:
+                    pl.run(p + 4 * r * w, w, h - r, r, self.out.ptr + size * r * w, env.streams[1 - s])
+                env.sync()
+                pl.status()
+            finally:
+                pl.close()
+        else:
+            proc.apply(p, w, h, 0, exp["cent"], mode, self.out.ptr, env.streams[s], format=fmt)
+        env.sync()
+        self.check_output(f"{op[0]} (mode {mode}, format {fmt}, cutoff {t0})", fmt, w, h, exp["out"])
+
+    def step_compare(self, op, exp, t0):
+        env, proc, C = self.env, self.proc, self.counters
+        i, other, fmt, k, seed, nb, order, cut, what, fresh, s = op[1:12]
+        self.count_k(k, fmt)
+        img = self.images[i][1]
+        h, w = img.shape[:2]
+        size = {None: 4, 1: 1, 2: 2}[fmt]
+        self.arm(self.out, size * w * h)
+        proc.apply(self.pix[i].ptr, w, h, 0, exp["cent"], 0, self.out.ptr, env.streams[s], format=fmt)
+        env.sync()
+        self.check_output("the output compare_device measures", fmt, w, h, exp["out"])
+        if fresh:
+            self.mem.write(self.rec, 0, np.zeros(112, np.uint8))
+        else:
+            C["record_combined_across_images"] += 1
+        bands = bands_of(h, nb, order)
+        C[f"compare_bands:{len(bands)}"] += 1
+        for j, (r0, rows) in enumerate(bands):
+            proc.compare_device(self.pix[i].ptr + 4 * r0 * w, self.out.ptr + size * r0 * w, rows * w, self.rec.ptr, format=0 if fmt is None else fmt,
+                                palette=exp["palette"], alpha_cutoff=cut, what=what, stream=env.streams[(s + j) % 2])
+        env.sync()
+        got = tuple(int(v) for v in self.collect(self.rec, 112, np.uint64, "error record"))
+        self.same("error record", got, exp["record"])
+
+    def step_pair_frame(self, op, exp, t0):
+        env, proc, C, m = self.env, self.proc, self.counters, self.model
+        P, i, tol, nb, order, s = op[1:7]
+        pr, bufs = m.pairs[P], self.pairs[P]
+        fmt, k = pr["fmt"], pr["k"]
+        img = self.images[i][1]
+        h, w = img.shape[:2]
+        n, size, dt = w * h, fmt, index_dtype(fmt)
+        C["pair_exact" if tol is None else "pair_lossy"] += 1
+        self.arm(bufs["index"], size * n)
+        self.arm(bufs["delta"], size * n)
+        proc.apply(self.pix[i].ptr, w, h, 0, exp["cent"], pr["mode"], bufs["index"].ptr, env.streams[s], format=fmt)
+        env.sync()
+        self.same("index map of the frame", self.collect(bufs["index"], size * n, dt, "index map").astype(np.int64).reshape(h, w), exp["index"])
+        fresh = np.array(hold_ref.FRESH[:2], np.uint64).tobytes() + np.array(hold_ref.FRESH[2:6], np.uint32).tobytes() + \
+            np.array(hold_ref.FRESH[6:], np.uint64).tobytes()
+        self.mem.write(bufs["rec"], 0, np.frombuffer(fresh, np.uint8).copy())
+        bands = bands_of(h, nb, order)
+        C[f"delta_bands:{len(bands)}"] += 1
+        for j, (r0, rows) in enumerate(bands):
+            a, e = 4 * r0 * w, size * r0 * w
+            stj = env.streams[(s + j) % 2]
+            if tol is None:
+                proc.frame_delta(bufs["index"].ptr + e, bufs["canvas"].ptr + e, w, rows, r0, fmt, k, bufs["delta"].ptr + e, bufs["rec"].ptr, stj)
+            else:
+                proc.frame_delta_lossy(self.pix[i].ptr + a, bufs["index"].ptr + e, bufs["canvas"].ptr + e, bufs["held"].ptr + a, w, rows, r0, fmt, k, tol,
+                                       bufs["delta"].ptr + e, bufs["rec"].ptr, stj)
+        env.sync()
+        if tol is None:
+            self.mem.write(bufs["held"], 0, img.reshape(-1))             # the canvas equals the map: the held source is this frame
+        raw = self.collect(bufs["rec"], 48, np.uint8, "frame record")
+        got = tuple(int(v) for v in raw[:16].view(np.uint64)) + tuple(int(v) for v in raw[16:32].view(np.uint32)) + \
+            tuple(int(v) for v in raw[32:48].view(np.uint64))
+        self.same("frame record", got, exp["record"])
+        self.same("delta map", self.collect(bufs["delta"], size * n, dt, "delta map").astype(np.int64).reshape(h, w), exp["delta"])
+        self.same("canvas", self.collect(bufs["canvas"], size * n, dt, "canvas").astype(np.int64).reshape(h, w), exp["canvas"])
+        self.same("held source", self.collect(bufs["held"], 4 * n, np.uint8, "held source").reshape(h, w, 4), exp["held"])
+
+    # -- Lloyd objects
+    def step_lloyd(self, op):
+        env, m, name, C = self.env, self.model, op[0], self.counters
+        L = op[1]
+        o = self.obj[L]
+        if name in ("l_new", "l_re"):
+            if name == "l_re":
+                o.close()
+            C[f"lloyd_k:{k_class(op[2])}"] += 1
+            apply_op(m, op)
+            self.obj[L] = env.lloyd(self.proc, op[2])
+            self.acc[L] = self.mem.alloc(32 * op[2] + GUARD)
+            self.mem.fill(self.acc[L], 32 * op[2], GUARD, PATTERN)
+            self.mem.write(self.acc[L], 0, np.zeros(32 * op[2], np.uint8))
+            return
+        if name == "l_close":
+            apply_op(m, op)
+            o.close()
+            self.obj[L] = None
+            return
+        s = m.lloyd[L]
+        st = env.streams[op[-1]] if name not in ("l_set", "l_fix") else env.streams[0]
+        acc = self.acc[L].ptr
+        img_i = op[2] if name in ("l_init", "l_assign_update", "l_iterate", "l_run", "l_lftu", "l_assign", "l_bind") else None
+        if img_i is not None:
+            if s.bind is not None and s.bind != img_i:
+                o.unbind_image()                              # (whether a pass on other pixels re-binds is the cost model's)
+                s.bind = None
+            h, w = self.images[img_i][1].shape[:2]
+            n, p = w * h, self.pix[img_i].ptr
+        f_before = s.f
+        exp = apply_op(m, op)
+        if f_before and name in ("l_update", "l_assign_update", "l_iterate", "l_run", "l_lftu"):
+            C["update_with_n_fixed:" + name] += 1
+        if name == "l_set":
+            o.set_centroids(s.cent, st)
+        elif name == "l_init":
+            C[f"seeds:{op[3]}"] += 1
+            o.init_centroids_seeded(p, w, h, fixed_ref.pins_lab(O, np.array(FIXED[3], np.uint8)[:op[3]]), st)
+        elif name == "l_fix":
+            C["set_fixed_zero" if op[2] == 0 else "set_fixed"] += 1
+            o.set_fixed(op[2])
+        elif name == "l_bind":
+            o.bind_image(p, n, st)
+        elif name == "l_conv":
+            got = o.converged_count(st)
+            if got != exp["nconv"]:
+                self.fail(f"converged_count {got}, expected {exp['nconv']}")
+        elif name == "l_update":
+            o.update(acc, st)
+        elif name == "l_assign":
+            self.arm(self.lab, 4 * n)
+            o.assign_accumulate(p, n, self.lab.ptr, acc, st)
+        elif name == "l_assign_update":
+            self.arm(self.lab, 4 * n)
+            o.assign_update(p, n, self.lab.ptr if op[3] else 0, acc, bool(op[4]), st)
+        elif name == "l_iterate":
+            self.arm(self.lab, 4 * n)
+            for _ in range(op[3]):
+                o.iterate(p, n, self.lab.ptr, acc, True, st)
+            o.flush(st)
+        elif name == "l_run":
+            self.arm(self.lab, 4 * n)
+            it = o.run(p, n, self.lab.ptr if op[3] else 0, st)
+            if it != exp["iterations"]:
+                self.fail(f"run stopped at iteration {it}, the model at {exp['iterations']}")
+        elif name == "l_lftu":
+            self.arm(self.lab, 4 * n)
+            self.mem.write(self.acc[L], 0, np.zeros(32 * s.k, np.uint8))
+            o.bind_image(p, n, st)
+            o.accumulate_into(p, n, acc, st)
+            o.labels_from_tables_update(p, n, self.lab.ptr, acc, st)
+        env.sync()
+        if "labels" in exp:
+            self.same("labels of " + name, self.collect(self.lab, 4 * n, np.uint32, "labels"), exp["labels"])
+        got = self.collect(self.acc[L], 32 * s.k, np.int64, "accumulators").reshape(s.k, 4)
+        self.same("accumulators", got, s.acc)
+        if exp.get("cent") is not None:
+            got = o.get_centroids(st)
+            if not np.array_equal(_bits(got), _bits(exp["cent"])):
+                self.fail("centroid bits", _bits(got), _bits(exp["cent"]))
+
+    # -- Sequence objects
+    def step_sequence(self, op):
+        env, m, name, C = self.env, self.model, op[0], self.counters
+        S = op[1]
+        q = self.seqs[S]
+        if name == "s_new":
+            apply_op(m, op)
+            self.seqs[S] = self.proc.sequence()
+            return
+        if name == "s_close":
+            C["closed_with_output_open"] += int(m.seq[S].out is not None)
+            apply_op(m, op)
+            q.close()
+            self.seqs[S] = None
+            return
+        if name == "s_output":
+            C["reoutput"] += int(m.seq[S].out is not None)
+            C["mixed_cutoff_sequence"] += int(len({t for _, t in m.seq[S].frames}) > 1)
+            self.count_k(op[2], op[4])
+        exp = apply_op(m, op)
+        if name == "s_add":
+            i = op[2]
+            h, w = self.images[i][1].shape[:2]
+            C["add_shrunk"] += int(max(w, h) > SHRINK)
+            if op[3]:
+                q.add_device(self.pix[i].ptr, w, h, env.streams[op[4]])
+            else:
+                q.add(self.images[i][1])
+        elif name == "s_clear":
+            q.clear()
+        elif name == "s_info":
+            if tuple(q.info()) != exp["info"]:
+                self.fail(f"info {tuple(q.info())}, the model {exp['info']}")
+        elif name == "s_centroids":
+            C["mixed_cutoff_sequence"] += int(len({t for _, t in m.seq[S].frames}) > 1)
+            got = q.centroids(op[2])
+            if not np.array_equal(_bits(got), _bits(exp["cent"])):
+                self.fail("centroid bits of the sequence", _bits(got), _bits(exp["cent"]))
+        elif name == "s_palette":
+            C["mixed_cutoff_sequence"] += int(len({t for _, t in m.seq[S].frames}) > 1)
+            self.same("palette of the sequence", q.palette(op[2]), exp["palette"])
+        elif name == "s_output":
+            o = m.seq[S].out
+            h, w = o["shape"]
+            self.same("palette of the output", q.output(o["k"], o["mode"], o["fmt"], w, h), exp["palette"])
+        elif name == "s_end":
+            q.end_output()
+        elif name == "s_frame":
+            i, delta, tol = op[2:5]
+            C["frame_exact" if tol is None else "frame_lossy"] += 1
+            if exp["transition"]:
+                C["transition:" + exp["transition"]] += 1
+            got, info, full = q.frame(self.images[i][1], delta=bool(delta), tolerance=tol)
+            C["is_full_fallback"] += int(exp.get("fallback", False))
+            C["frame_held_pixels"] += int(tol is not None and exp["record"][6] > 0)
+            if bool(full) != exp["full"]:
+                self.fail(f"is_full {full}, the model {exp['full']}")
+            self.same("frame record", info.as_tuple(), exp["record"])
+            self.same("frame map", got if got.ndim == 3 else got.astype(np.int64), exp["map"])
+        else:
+            raise ValueError(op)
+
+    def step_refuse(self, op):
+        m, proc = self.model, self.proc
+        exp = apply_op(m, op)
+        what = op[1]
+        self.counters["refusal:" + what] += 1
+        st = exp["status"]
+        if what == "k_below_fixed_palette":
+            self.expect_status(st, proc.palette, op[3], self.images[op[2]][1], 0)
+        elif what == "k_below_fixed_reduce":
+            self.expect_status(st, proc.reduce, op[3], self.images[op[2]][1], 0, 0)
+        elif what == "octree_fixed":
+            self.expect_status(st, proc.palette, op[3], self.images[op[2]][1], 1)
+        elif what in ("k_below_fixed_sequence", "empty_sequence"):
+            self.expect_status(st, self.seqs[op[2]].palette, op[3])
+        elif what == "frame_no_output":
+            self.expect_status(st, self.seqs[op[2]].frame, self.images[op[3]][1], delta=True)
+        elif what == "delta_on_rgba8":
+            self.expect_status(st, self.seqs[op[2]].frame, self.images[op[3]][1], delta=True)
+        elif what == "lossy_on_rgba8":
+            self.expect_status(st, self.seqs[op[2]].frame, self.images[op[3]][1], delta=True, tolerance=40)
+        elif what == "lossy_without_delta":
+            self.expect_status(st, self.seqs[op[2]].frame, self.images[op[3]][1], delta=False, tolerance=40)
+        elif what in ("index8_full", "meld_indexed"):
+            i = op[2]
+            h, w = self.images[i][1].shape[:2]
+            cent, _ = gamut_centroids(7, op[3])
+            self.arm(self.out, 2 * w * h)
+            self.expect_status(st, proc.apply, self.pix[i].ptr, w, h, 0, cent, 2 if what == "meld_indexed" else 0, self.out.ptr, self.env.streams[0],
+                               format=1 if what == "index8_full" else 2)
+            self.env.sync()
+            if not (self.collect(self.out, 2 * w * h, np.uint8, "refused call") == PATTERN).all():
+                self.fail("a refused call wrote output")
+        else:
+            raise ValueError(op)
+
+
+def run_sequence(env, seed, seq, ops=None, counters=None, proc=None, cache=None):
+    """one sequence on a fresh processor (or the caller's): (ops run, blocks allocated, blocks re-used); raises Mismatch with the
+    replay text"""
+    ops = generate(seed, seq) if ops is None else ops
+    r = Runner(env, seed, seq, counters, proc, cache)
+    try:
+        before = r.proc.debug_block_counts()
+        r.run(ops)
+        blocks = r.proc.debug_block_counts()
+    except Mismatch as e:
+        raise Mismatch(f"seed {seed} sequence {seq}: {e}\nreplay(env, {seed}, {seq}, {ops[:r.n_ops + 1]!r})") from None
+    finally:
+        r.close()
+    return r.n_ops, blocks[0] - before[0], blocks[1] - before[1]
+
+
+def replay(env, seed, seq, ops, proc=None):
+    """runs a printed op list again: the images are those of (seed, seq)"""
+    return run_sequence(env, seed, seq, ops, proc=proc)
+
+
+# ---- the real binding -----------------------------------------------------------------------------------------------
+class KgEnv(LH.KgEnv):
+    """lifecycle_harness.KgEnv with the processor of this harness: the shrink of the palette step stays on"""
+
+    def session_processor(self):
+        return self.kg.ImageProcessor(shrink_max_dim=SHRINK, max_iterations=MAX_ITERATIONS, check_period=CHECK_PERIOD, strategy="auto")

@@ -1,0 +1,145 @@
+"""Long-lived sessions on the device (tests/session_harness.py): the random sessions of tools/fuzz_session.py on the seeds
+tests/test_session_model.py vouches for, and named scenarios -- each an op list of the harness, run against its stateless model on
+ONE processor that stays alive across all of them (so every scenario works in the blocks the ones before it left).  Everything an
+op could have touched is compared byte for byte after every op."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+import session_harness as H
+from test_session_model import SEEDS, SEQUENCES
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SEED, SEQ = 7, 0                      # the images of the scenarios: H.make_images(SEED, SEQ)
+ODD, ODD_B, SPRITE, NOISY, SHIFT, FEW, FLAT, CLEAR, BIG, MEGA, ROW, COL = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12
+# A seed's run took 7.5 and 7.8 s on an MI355X, process start included (profiles/NOTES.md, "Session harness"); about two thirds of
+# that is the reference on the host's CPUs.  The limit is forty times the measured time: a host with a quarter of the cores, busy
+# with other work, can slow the reference tenfold and still finish; a run that needs longer than that hangs.
+SESSION_SECONDS = 7.8
+TIMEOUT = 40 * SESSION_SECONDS
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_random_sessions_equal_the_model(seed):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_session.py"), str(SEQUENCES), str(seed)],
+                       capture_output=True, text=True, timeout=TIMEOUT)
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    assert re.search(rf"^{SEQUENCES} sequences, \d+ ops, 0 mismatching$", r.stdout, re.M), r.stdout[-2000:]
+    reused = [int(x) for x in re.findall(r"(\d+) blocks re-used", r.stdout)]
+    assert len(reused) == SEQUENCES and all(x > 0 for x in reused), reused     # else nothing ran on recycled memory
+
+
+@pytest.fixture(scope="module")
+def world(torch_cuda):
+    env = H.KgEnv()
+    proc = env.session_processor()
+    yield env, proc
+    proc.close()
+
+
+def _run(world, ops):
+    env, proc = world
+    done = H.run_sequence(env, SEED, SEQ, ops, proc=proc)[0]
+    assert done == len(ops)
+
+
+def _order(h, nb, want):
+    """an order seed for which session_harness.bands_of runs the bands of h rows from the last to the first (want = "reverse")"""
+    for s in range(1000):
+        rows = [r0 for r0, _ in H.bands_of(h, nb, s)]
+        if len(rows) == nb and rows == sorted(rows, reverse=True):
+            return s
+    raise AssertionError(want)
+
+
+def _cutoff_0_128_0_around_palette_reduce_and_a_plan():
+    """the results at cutoff 0 before and after the passage at 128 are those of the default path, and the plan made at 128 still
+    writes index k for the pixels below it after the switch back"""
+    at = [("palette", ODD, 8), ("reduce_indexed", ODD, 8, 0, 1), ("reduce_indexed", SPRITE, 40, 3, 1), ("reduce", ODD, 8, 1)]
+    return ([("strategy", 0), ("cutoff", 0)] + at + [("cutoff", 128)] + at +
+         [("apply_plan", ODD, 0, 1, 40, 11, 0, 0), ("apply_plan", SPRITE, 3, 2, 300, 12, 128, 1), ("apply_plan", ODD, 1, None, 9, 13, 0, 0)] + at)
+
+
+def _frames_added_under_three_cutoffs_then_clear():
+    frames = [(SPRITE, 0), (ODD, 128), (SHIFT, 0)]
+    ops = [("s_new", 0)]
+    for i, t in frames:
+        ops += [("cutoff", t), ("s_add", 0, i, int(i == ODD), 1)]
+    ops += [("s_info", 0), ("s_palette", 0, 12), ("s_centroids", 0, 12), ("cutoff", 255), ("s_centroids", 0, 5), ("s_clear", 0), ("s_info", 0),
+            ("cutoff", 128)]
+    ops += [("s_add", 0, i, 0, 0) for i, _ in frames]
+    return (ops + [("s_info", 0), ("s_palette", 0, 12), ("s_centroids", 0, 12), ("cutoff", 0), ("s_close", 0)])
+
+
+def _an_output_ends_a_lloyd_object_runs_in_its_block_and_the_next_output_starts_fresh():
+    """INDEX8 k = 40, exact / lossy / lossy / exact, end; a Lloyd object created, run and closed in the returned block; INDEX16
+    k = 300 at another size: its first delta is the delta against a canvas of k, that is the full map"""
+    return ([("cutoff", 1), ("s_new", 0), ("s_add", 0, SPRITE, 0, 0), ("s_add", 0, ODD, 1, 0), ("s_output", 0, 40, 0, 1, 1),
+                 ("s_frame", 0, SPRITE, 1, None), ("s_frame", 0, NOISY, 1, 40), ("s_frame", 0, SHIFT, 1, 4096), ("s_frame", 0, SPRITE, 1, None),
+                 ("s_end", 0), ("l_new", 0, 24), ("l_set", 0, "rand", 3, ODD), ("l_run", 0, FEW, 1, 0), ("l_close", 0),
+                 ("s_output", 0, 300, 0, 2, 0), ("s_frame", 0, ODD, 1, None), ("s_frame", 0, ODD_B, 1, 40), ("s_output", 0, 40, 3, 1, 1),
+                 ("s_frame", 0, NOISY, 1, 40), ("s_close", 0), ("cutoff", 0)])
+
+
+def _frozen_seeds_do_not_outlive_their_object():
+    return ([("strategy", 2), ("l_new", 0, 12), ("l_init", 0, FEW, 3, 0), ("l_fix", 0, 3), ("l_run", 0, FEW, 1, 0), ("l_re", 0, 30),
+                 ("l_init", 0, ROW, 0, 1), ("l_run", 0, ROW, 1, 1), ("l_assign_update", 0, ODD, 1, 1, 0), ("l_conv", 0, 0), ("l_fix", 0, 2),
+                 ("l_iterate", 0, ODD, 2, 0), ("l_conv", 0, 0), ("l_lftu", 0, SPRITE, 1), ("l_fix", 0, 0), ("l_assign_update", 0, ODD, 0, 1, 0),
+                 ("l_update", 0, 1), ("l_conv", 0, 1), ("l_close", 0), ("strategy", 0)])
+
+
+def _quality_search_with_and_without_pins_beside_a_bound_object():
+    """the second search equals the unpinned model; the user's Lloyd object stays bound across both, and its next assign is right"""
+    q = ("quality", FEW, 4.0, 8, 14, 0, 1, 1)
+    return ([("strategy", 2), ("l_new", 1, 9), ("l_set", 1, "rand", 5, ODD), ("l_bind", 1, ODD, 0), ("l_assign", 1, ODD, 0), ("fixed", 3), q,
+                 ("l_assign", 1, ODD, 1), ("fixed", 0), q, ("quality", SPRITE, 9.0, 2, 12, 3, 0, 0), ("l_assign_update", 1, ODD, 1, 1, 0),
+                 ("l_close", 1), ("strategy", 0)])
+
+
+def _records_combine_over_bands_in_reverse_on_two_streams():
+    h_odd, h_sprite = 61, 72
+    return ([("cutoff", 128),
+                 ("compare_device", ODD, 0, 1, 40, 21, 3, _order(h_odd, 3, "reverse"), 128, 3, 1, 0),
+                 ("compare_device", SPRITE, 0, 2, 300, 22, 2, _order(h_sprite, 2, "reverse"), 0, 3, 0, 1),      # into the same record
+                 ("compare_device", FEW, 0, None, 9, 23, 3, 5, 0, 1, 1, 0),                                      # a fresh one
+                 ("compare_device", ODD, 0, None, 9, 23, 2, 6, 128, 2, 0, 1),
+                 ("pair_open", 0, 1, 1, 40, 24, 0), ("pair_frame", 0, SPRITE, None, 3, _order(h_sprite, 3, "reverse"), 0),
+                 ("pair_frame", 0, NOISY, 40, 3, _order(h_sprite, 3, "reverse"), 1), ("pair_frame", 0, SHIFT, 4096, 2, 3, 0),
+                 ("pair_frame", 0, SPRITE, 0, 3, 4, 1), ("pair_frame", 0, NOISY, None, 1, 0, 0), ("pair_frame", 0, SPRITE, 400000, 2, 9, 0),
+                 ("pair_open", 1, 0, 2, 300, 25, 1), ("pair_frame", 1, ODD, 40, 3, _order(h_odd, 3, "reverse"), 0),
+                 ("pair_frame", 1, ODD_B, 40, 2, 1, 1), ("cutoff", 0)])
+
+
+def _every_refusal_is_followed_by_the_correct_call():
+    return ([("cutoff", 0), ("fixed", 3), ("refuse", "k_below_fixed_palette", SPRITE, 7), ("palette", SPRITE, 9),
+                 ("refuse", "k_below_fixed_reduce", SPRITE, 3), ("reduce", SPRITE, 10, 0), ("refuse", "octree_fixed", SPRITE, 12),
+                 ("palette", SPRITE, 12), ("s_new", 0), ("s_add", 0, FEW, 0, 0), ("refuse", "k_below_fixed_sequence", 0, 7), ("s_palette", 0, 9),
+                 ("fixed", 0), ("refuse", "frame_no_output", 0, SPRITE), ("s_output", 0, 5, 0, 0, 1), ("refuse", "delta_on_rgba8", 0, NOISY),
+                 ("refuse", "lossy_on_rgba8", 0, NOISY), ("s_frame", 0, NOISY, 0, None), ("s_output", 0, 5, 1, 1, 1),
+                 ("refuse", "lossy_without_delta", 0, NOISY), ("s_frame", 0, NOISY, 1, 40), ("s_end", 0), ("refuse", "frame_no_output", 0, SPRITE),
+                 ("refuse", "index8_full", ODD, 257), ("apply", ODD, 0, 1, 256, 31, 0), ("cutoff", 128), ("refuse", "index8_full", ODD, 256),
+                 ("apply", ODD, 0, 1, 255, 32, 1), ("refuse", "meld_indexed", FLAT, 5), ("apply", FLAT, 2, None, 5, 33, 0), ("s_clear", 0),
+                 ("s_add", 0, CLEAR, 0, 0), ("s_info", 0), ("refuse", "empty_sequence", 0, 4), ("s_add", 0, FLAT, 1, 0), ("s_palette", 0, 4),
+                 ("s_close", 0), ("cutoff", 0)])
+
+
+def _two_sequences_alternate_beside_host_calls_on_the_megapixel_image():
+    """forced colour table on 1024 x 1024: large blocks enter the idle list and the next output picks them up"""
+    return ([("strategy", 2), ("s_new", 0), ("s_new", 1), ("s_add", 0, SPRITE, 0, 0), ("s_add", 1, ODD, 1, 1), ("s_add", 1, BIG, 0, 0),
+                 ("s_output", 0, 16, 0, 1, 1), ("s_output", 1, 20, 1, 2, 0), ("s_frame", 0, SPRITE, 1, None), ("reduce", MEGA, 8, 0),
+                 ("s_frame", 1, ODD, 1, None), ("s_frame", 0, NOISY, 1, 40), ("reduce_indexed", MEGA, 6, 1, 1), ("s_frame", 1, ODD_B, 1, 40),
+                 ("compare_device", MEGA, 0, 1, 12, 41, 3, 2, 0, 3, 1, 0), ("s_end", 0), ("s_output", 0, 30, 0, 2, 1), ("s_frame", 0, SHIFT, 1, None),
+                 ("s_frame", 1, ODD, 0, None), ("s_frame", 0, SPRITE, 1, 4096), ("s_close", 0), ("s_close", 1), ("strategy", 0)])
+
+
+SCENARIOS = {f.__name__[1:]: f for f in (_cutoff_0_128_0_around_palette_reduce_and_a_plan, _frames_added_under_three_cutoffs_then_clear, _an_output_ends_a_lloyd_object_runs_in_its_block_and_the_next_output_starts_fresh, _frozen_seeds_do_not_outlive_their_object, _quality_search_with_and_without_pins_beside_a_bound_object, _records_combine_over_bands_in_reverse_on_two_streams, _every_refusal_is_followed_by_the_correct_call, _two_sequences_alternate_beside_host_calls_on_the_megapixel_image)}
+
+
+@pytest.mark.parametrize("name", list(SCENARIOS))
+def test_scenario(world, name):
+    """(tests/test_session_model.py runs the same lists on its stand-ins: they are legal sequences of the harness)"""
+    _run(world, SCENARIOS[name]())

@@ -1,0 +1,688 @@
+"""tests/session_harness.py shown to be SOUND and SHARP on the CPU, before the device sees it (tests/test_gpu_session.py runs the
+same seeds; the generator is deterministic, so what is covered here is covered there).
+
+Sound: stand-ins of kmeans_gpu_amd.ImageProcessor / Sequence / Lloyd / ApplyPlan over the reference modules, which keep the state
+the library keeps -- the sticky switches and the moment each consumer reads them, the working sequence as compacted pixels in a
+block that grows geometrically, the first-frame record, canvas and held source of an open output in a block that goes back to the
+idle list, n_fixed with the object -- pass every sequence of every committed seed.  Sharp: thirteen faulty variants, one named
+defect each, are each caught by every committed seed.  Coverage: exact counts for the committed seeds, none zero.
+
+Wall time of this file and of tests/test_lifecycle_model.py: profiles/NOTES.md, "session harness"."""
+import collections
+
+import numpy as np
+import pytest
+
+import session_harness as H
+import oracle_lib as O
+import alpha_ref
+import diffuse_ref
+import error_ref
+import fixed_ref
+import hold_ref
+import sequence_ref
+from lifecycle_harness import sorted_palette
+from test_lifecycle_model import FakeError, HostMem, _view
+
+SEEDS = (201, 202)          # the seeds tests/test_gpu_session.py runs
+SEQUENCES = 6               # ... and its sequences per seed
+
+FAULTS = ("cutoff_read_at_palette_time", "plan_follows_cutoff", "fixed_sticks_after_none", "n_fixed_inherited", "set_fixed_zero_ignored",
+          "canvas_survives_end_output", "held_not_reanchored", "held_frame_swap_lost", "record_not_reset", "band_combined_twice",
+          "clear_keeps_first_frame", "w_growth_drops_tail", "quality_leaves_switch")
+
+
+class Record:
+    def __init__(self, values):
+        self.values = tuple(int(v) for v in values)
+
+    def as_tuple(self):
+        return self.values
+
+
+def _record_view(ptr, lossy):
+    """the integers of a kmg_frame_delta / kmg_frame_hold in device memory, and a function that writes them back"""
+    raw = _view(ptr, 48 if lossy else 32, np.uint8)
+    vals = [int(v) for v in raw[:16].view(np.uint64)] + [int(v) for v in raw[16:32].view(np.uint32)]
+    if lossy:
+        vals += [int(v) for v in raw[32:48].view(np.uint64)]
+
+    def put(rec):
+        raw[:16] = np.array(rec[:2], np.uint64).view(np.uint8)
+        raw[16:32] = np.array(rec[2:6], np.uint32).view(np.uint8)
+        if lossy:
+            raw[32:48] = np.array(rec[6:8], np.uint64).view(np.uint8)
+    return tuple(vals), put
+
+
+class FakeProcessor:
+    def __init__(self, fault, images, cache):
+        self.fault = fault
+        self.ref = H.Ref(images, cache)
+        self.by_bytes = {a.tobytes(): i for i, (_, a) in enumerate(images)}
+        self.t, self.fixed, self.strategy = 0, None, 0
+        self.idle = []                 # blocks of closed objects and ended outputs: what their last owner left in them
+        self.allocated = self.reused = 0
+        self.last_compare = error_ref.ZERO
+
+    # -- blocks
+    def take(self):
+        if self.idle:
+            self.reused += 1
+            return self.idle.pop()
+        self.allocated += 1
+        return {}
+
+    def give(self, block):
+        self.idle.append(block)
+
+    def scratch(self):
+        self.give(self.take())
+
+    def debug_block_counts(self):
+        return self.allocated, self.reused
+
+    def close(self):
+        pass
+
+    # -- switches
+    def set_alpha_cutoff(self, t):
+        self.t = int(t)
+
+    def set_fixed_colors(self, colors):
+        if colors is None or len(colors) == 0:
+            if self.fault != "fixed_sticks_after_none":
+                self.fixed = None
+            return
+        self.fixed = tuple(tuple(int(v) for v in c) for c in np.asarray(colors, np.uint8))
+
+    def set_strategy(self, v):
+        self.strategy = int(v)
+
+    def fid(self):
+        return H.FIXED.index(self.fixed)
+
+    def n_fixed(self):
+        return 0 if self.fixed is None else len(self.fixed)
+
+    def image_index(self, a):
+        return self.by_bytes[np.ascontiguousarray(a).tobytes()]
+
+    # -- the palette step of a host call: the switches as they are when it starts
+    def _centroids(self, image, k, algo=0):
+        f = self.n_fixed()
+        if algo == 1 and f:
+            raise FakeError(-1, "the octree has no fixed colours")
+        if k < f:
+            raise FakeError(-1, "k is below the fixed colours")
+        i = self.image_index(image)
+        if self.ref.working(((i, self.t),)) is None:
+            raise FakeError(-1, "no pixel reaches alpha_cutoff")
+        self.scratch()
+        return self.ref.centroids(((i, self.t),), k, self.fid())
+
+    def palette(self, k, image, algo=0):
+        return sorted_palette(self._centroids(image, k, algo))
+
+    def reduce(self, k, image, algo=0, reduce_mode=0):
+        return self.ref.rgba(image, self._centroids(image, k, algo), reduce_mode, self.t)
+
+    def _typed(self, idx, k, t):
+        return idx.astype(H.index_dtype(H.host_format(k, t)))
+
+    def reduce_indexed(self, k, image, algo=0, reduce_mode=0):
+        cent = self._centroids(image, k, algo)
+        return self.ref.palette_bytes(cent), self._typed(self.ref.index(image, cent, reduce_mode, self.t), k, self.t)
+
+    def find(self, image, colors, reduce_mode=0):
+        pal = np.ascontiguousarray(colors, np.uint8).reshape(-1, 4)
+        if self.t:
+            return alpha_ref.find(O, image, pal, reduce_mode, self.t)
+        if reduce_mode == 3:
+            return diffuse_ref.diffuse(image, diffuse_ref.oracle_find_replace(O, pal))
+        return O.find(image, pal, reduce_mode)
+
+    def find_indexed(self, image, colors, reduce_mode=0):
+        pal = np.ascontiguousarray(colors, np.uint8).reshape(-1, 4)
+        return self._typed(self.ref.index(image, self.ref.find_centroids(pal), reduce_mode, self.t), pal.shape[0], self.t)
+
+    def compare(self, src, out, palette=None, what=3):
+        rec = self.ref.stats(src, np.asarray(out).astype(np.int64) if palette is not None else out, palette, self.t, what)
+        if self.fault == "record_not_reset":
+            rec = error_ref.combine(self.last_compare, rec)
+        self.last_compare = rec
+        return Record(rec)
+
+    def reduce_quality(self, image, max_delta_e, k_min=2, k_max=256, reduce_mode=0, indexed=False):
+        if k_min < self.n_fixed():
+            raise FakeError(-1, "k_min is below the fixed colours")
+        i, t = self.image_index(image), self.t
+        self.scratch()
+        k, reached, rec = self.ref.quality(i, t, self.fid(), H.target_of(max_delta_e), k_min, k_max)
+        cent = self.ref.centroids(((i, t),), k, self.fid())
+        out = self._typed(self.ref.index(image, cent, reduce_mode, t), k_max, t) if indexed else self.ref.rgba(image, cent, reduce_mode, t)
+        if self.fault == "quality_leaves_switch":
+            self.t = 0 if t else 255               # the bisection's own setting is left behind
+        return k, self.ref.palette_bytes(cent), out, Record(rec), reached
+
+    # -- device calls
+    def _check_format(self, k, mode, fmt, t):
+        if fmt in (1, 2) and mode == 2:
+            raise FakeError(-1, "meld has no index output")
+        if fmt == 1 and k + (1 if t else 0) > 256:
+            raise FakeError(-1, "INDEX8 holds 256 indices")
+
+    def _pass(self, img, cent, mode, fmt, t):
+        return self.ref.rgba(img, cent, mode, t) if fmt is None else self.ref.index(img, cent, mode, t)
+
+    def _write(self, d_out, a, fmt):
+        a = np.ascontiguousarray(a)
+        _view(d_out, a.size, np.uint8 if fmt is None else H.index_dtype(fmt))[:] = a.reshape(-1)
+
+    def apply(self, d_rgba, width, rows, row0, cent, mode, d_out, stream=0, format=None):
+        cent = np.ascontiguousarray(cent, np.float32).reshape(-1, 4)
+        self._check_format(cent.shape[0], mode, format, self.t)
+        self.scratch()
+        assert row0 == 0
+        img = _view(d_rgba, 4 * width * rows, np.uint8).reshape(rows, width, 4)
+        self._write(d_out, self._pass(img, cent, mode, format, self.t), format)
+
+    def apply_plan(self, cent, mode, n_pixels_hint, stream=0, format=None):
+        proc = self
+        cent = np.ascontiguousarray(cent, np.float32).reshape(-1, 4).copy()
+        self._check_format(cent.shape[0], mode, format, self.t)
+        block = self.take()
+        made_under = self.t
+
+        class Plan:
+            def __init__(self):
+                self.bands = []
+
+            def run(self, d_rgba, width, rows, row0, d_out, stream=0):
+                # (the bands of a sequence tile one image from row 0: Bayer coordinates and the diffusion continue across them)
+                self.bands.append(_view(d_rgba, 4 * width * rows, np.uint8).reshape(rows, width, 4).copy())
+                t = proc.t if proc.fault == "plan_follows_cutoff" else made_under
+                whole = proc._pass(np.ascontiguousarray(np.concatenate(self.bands)), cent, mode, format, t)
+                proc._write(d_out, whole[row0:row0 + rows], format)
+
+            def status(self):
+                pass
+
+            def close(self):
+                proc.give(block)
+        return Plan()
+
+    def alpha_compact(self, d_rgba, n_pixels, cutoff, d_out, d_n_kept, stream=0):
+        kept = alpha_ref.compact(_view(d_rgba, 4 * n_pixels, np.uint8).reshape(-1, 4), cutoff)
+        _view(d_out, kept.size, np.uint8)[:] = kept.reshape(-1)
+        _view(d_n_kept, 1, np.uint64)[0] = kept.shape[0]
+
+    def compare_device(self, d_src, d_out, n_pixels, d_stats, format=0, palette=None, alpha_cutoff=0, what=3, stream=0):
+        if format == 1 and palette is not None and len(palette) + (1 if alpha_cutoff else 0) > 256:
+            raise FakeError(-1, "INDEX8 holds 256 indices")
+        src = _view(d_src, 4 * n_pixels, np.uint8).reshape(-1, 4)
+        out = _view(d_out, 4 * n_pixels, np.uint8).reshape(-1, 4) if format == 0 else _view(d_out, n_pixels, H.index_dtype(format)).astype(np.int64)
+        rec = self.ref.stats(src, out, palette, alpha_cutoff, what)
+        stats = _view(d_stats, 14, np.uint64)
+        for _ in range(2 if self.fault == "band_combined_twice" else 1):
+            stats[:] = np.array(error_ref.combine(tuple(int(v) for v in stats), rec), np.uint64)
+
+    def _band(self, ptr, width, rows, fmt):
+        return _view(ptr, width * rows, H.index_dtype(fmt)).reshape(rows, width)
+
+    def frame_delta(self, d_index, d_canvas, width, rows, row0, format, k, d_delta, d_info, stream=0):
+        index, canvas = self._band(d_index, width, rows, format), self._band(d_canvas, width, rows, format)
+        d, new_canvas, rec = sequence_ref.delta(index.astype(np.int64), canvas.astype(np.int64), k, row0)
+        self._band(d_delta, width, rows, format)[:] = d
+        canvas[:] = new_canvas
+        old, put = _record_view(d_info, False)
+        for _ in range(2 if self.fault == "band_combined_twice" else 1):
+            old = sequence_ref.combine(old, rec)
+        put(old)
+
+    def frame_delta_lossy(self, d_src, d_index, d_canvas, d_held, width, rows, row0, format, k, tolerance, d_delta, d_info, stream=0):
+        index, canvas = self._band(d_index, width, rows, format), self._band(d_canvas, width, rows, format)
+        src = _view(d_src, 4 * width * rows, np.uint8).reshape(rows, width, 4)
+        held = _view(d_held, 4 * width * rows, np.uint8).reshape(rows, width, 4)
+        d, new_canvas, new_held, rec = hold_ref.hold(O, src, index.astype(np.int64), canvas.astype(np.int64), held, k, tolerance, row0)
+        if self.fault == "held_not_reanchored":
+            new_held = np.where((canvas.astype(np.int64) != k)[..., None], held, new_held)
+        self._band(d_delta, width, rows, format)[:] = d
+        canvas[:] = new_canvas
+        held[:] = new_held
+        old, put = _record_view(d_info, True)
+        for _ in range(2 if self.fault == "band_combined_twice" else 1):
+            old = hold_ref.combine(old, rec)
+        put(old)
+
+    def sequence(self):
+        return FakeSequence(self)
+
+
+class FakeSequence:
+    """kmg_sequence_* with the library's kept state spelled out"""
+
+    def __init__(self, proc):
+        self.p, self.fault = proc, proc.fault
+        self.block = None              # W: the compacted pixels of every frame, one array per frame
+        self.cap = 0
+        self.parts = []
+        self.cutoffs = []
+        self.frames = 0
+        self.sw0 = self.sh0 = 0
+        self.first_whole = False
+        self.out = None
+        self.last_record = None
+
+    def close(self):
+        self.end_output()
+        if self.block is not None:
+            self.p.give(self.block)
+        self.block = None
+
+    def _n(self):
+        return sum(p.shape[0] for p in self.parts)
+
+    def _add(self, img):
+        p = self.p
+        t = p.t
+        i = p.image_index(img)
+        K, sw, sh, whole = p.ref.kept(i, t)
+        if self.fault == "cutoff_read_at_palette_time":
+            K = p.ref.kept(i, 0)[0]                    # kept as it came: the compaction is left to the palette step
+        need = 4 * (self._n() + sw * sh)
+        if need > self.cap:                            # a new block of at least twice the size, the old one goes back
+            new = p.take()
+            if self.block is not None:
+                p.give(self.block)
+            if self.fault == "w_growth_drops_tail" and self.parts:
+                self.parts[-1] = np.zeros_like(self.parts[-1])           # the copy stopped one frame short
+            self.block, self.cap = new, max(need, 2 * self.cap)
+        stale = self.fault == "clear_keeps_first_frame" and self.sw0 and not self.first_whole
+        if self.frames == 0 and not stale:
+            self.sw0, self.sh0, self.first_whole = sw, sh, whole
+        self.parts.append(K)
+        self.cutoffs.append(t)
+        self.frames += 1
+
+    def add(self, image):
+        self._add(np.ascontiguousarray(image, np.uint8))
+
+    def add_device(self, d_rgba, width, height, stream=0):
+        self._add(_view(d_rgba, 4 * width * height, np.uint8).reshape(height, width, 4))
+
+    def clear(self):
+        self.parts, self.cutoffs, self.frames = [], [], 0
+        if self.fault != "clear_keeps_first_frame":
+            self.first_whole = False
+            self.sw0 = self.sh0 = 0
+
+    def info(self):
+        return self.frames, self._n()
+
+    def _centroids(self, k):
+        p = self.p
+        parts = self.parts
+        if self.fault == "cutoff_read_at_palette_time":
+            parts = [a[a[:, 3] >= p.t] if p.t else a for a in parts]
+        n = sum(a.shape[0] for a in parts)
+        if n == 0:
+            raise FakeError(-1, "no pixel reaches alpha_cutoff")
+        if k < p.n_fixed():
+            raise FakeError(-1, "k is below the fixed colours")
+        p.scratch()
+        W = np.ascontiguousarray(np.concatenate(parts, axis=0))
+        whole = self.first_whole if self.fault != "cutoff_read_at_palette_time" else n == self.sw0 * self.sh0
+        as_image = self.frames == 1 and whole
+        return p.ref.centroids_px(W, self.sw0 if as_image else n, self.sh0 if as_image else 1, k, p.fid())
+
+    def centroids(self, k):
+        return self._centroids(k)
+
+    def palette(self, k):
+        return sorted_palette(self._centroids(k))
+
+    def output(self, k, mode=0, format=1, width=0, height=0):
+        self.end_output()
+        if format != 0 and mode == 2:
+            raise FakeError(-1, "meld has no index output")
+        if format == 1 and k > 255:
+            raise FakeError(-1, "INDEX8 holds 256 indices")
+        cent = self._centroids(k)
+        p = self.p
+        block = p.take()
+        canvas = np.full((height, width), k, np.int64)
+        left = block.get("canvas")
+        if self.fault == "canvas_survives_end_output" and left is not None and left.shape == canvas.shape:
+            canvas = np.minimum(left, k)                                 # no fresh fill: what the block's last output showed
+        self.out = dict(k=k, mode=mode, fmt=format, t=p.t, cent=cent, canvas=canvas, held=np.zeros((height, width, 4), np.uint8),
+                        frame=np.zeros((height, width, 4), np.uint8), block=block)
+        self.last_record = None
+        return p.ref.palette_bytes(cent)
+
+    def end_output(self):
+        if self.out is not None:
+            self.out["block"]["canvas"] = self.out["canvas"]
+            self.p.give(self.out["block"])
+        self.out = None
+
+    def frame(self, image, delta=True, tolerance=None):
+        o = self.out
+        if o is None:
+            raise FakeError(-1, "no output is open")
+        if (delta or tolerance is not None) and o["fmt"] == 0:
+            raise FakeError(-1, "a delta frame needs an index format")
+        if tolerance is not None and not delta:
+            raise FakeError(-1, "a lossy frame is a delta frame")
+        p = self.p
+        img = np.ascontiguousarray(image, np.uint8)
+        t = p.t if self.fault == "plan_follows_cutoff" else o["t"]
+        if o["fmt"] == 0:
+            return p.ref.rgba(img, o["cent"], o["mode"], t), Record(sequence_ref.FRESH), True
+        I = p.ref.index(img, o["cent"], o["mode"], t)
+        k = o["k"]
+        before = o["frame"]                                              # the frame buffer: what the last call uploaded
+        o["frame"] = img
+        if tolerance is None:
+            d, o["canvas"], rec = sequence_ref.delta(I, o["canvas"], k)
+            o["held"] = before if self.fault == "held_frame_swap_lost" else img   # the buffers swap: the held source is this frame
+            full = (not delta) or rec[1] > 0
+            if not delta:
+                rec = sequence_ref.FRESH
+            combine = sequence_ref.combine
+        else:
+            was_shown = o["canvas"] != k
+            d, o["canvas"], held, rec = hold_ref.hold(O, img, I, o["canvas"], o["held"], k, tolerance)
+            if self.fault == "held_not_reanchored":
+                held = np.where(was_shown[..., None], o["held"], held)
+            o["held"] = held
+            full = rec[1] > 0
+            if full:
+                o["canvas"], o["held"] = I.copy(), (before if self.fault == "held_frame_swap_lost" else img)
+            combine = hold_ref.combine
+        if self.fault == "record_not_reset" and self.last_record is not None and len(self.last_record) == len(rec) and delta:
+            rec = combine(self.last_record, rec)
+        self.last_record = tuple(rec)
+        return (I if full else d).astype(H.index_dtype(o["fmt"])), Record(rec), full
+
+
+class FakeLloyd:
+    """the part of kmg_lloyd_* the session harness drives: per-pixel passes over whole images, n_fixed with the object"""
+
+    def __init__(self, proc, k, fault=None):
+        self.p, self.k, self.fault = proc, int(k), fault
+        self.cent = np.zeros((self.k, 4), np.float32)
+        self.nconv = 0
+        self.block = proc.take()
+        self.f = min(self.block.get("n_fixed", 0), self.k) if fault == "n_fixed_inherited" else 0   # the device word of the block's last owner
+        self.bound = None
+
+    def close(self):
+        self.block["n_fixed"] = self.f
+        self.p.give(self.block)
+
+    def _image(self, ptr, n):
+        return self.p.image_index(_view(ptr, 4 * n, np.uint8))
+
+    def _step(self, sums):
+        self.cent, self.nconv = fixed_ref.step(O, np.ascontiguousarray(sums), self.cent, self.f)
+
+    def _acc(self, d_acc):
+        return _view(d_acc, 4 * self.k, np.int64).reshape(self.k, 4)
+
+    def set_centroids(self, c, stream=0):
+        self.cent = np.ascontiguousarray(c, np.float32).reshape(self.k, 4).copy()
+
+    def get_centroids(self, stream=0):
+        out = self.cent.copy()
+        out[:, 3] = 1.0
+        return out
+
+    def init_centroids_seeded(self, d_rgba, w, h, seeds4, stream=0):
+        f = np.asarray(seeds4).reshape(-1, 4).shape[0]
+        if f > self.k:
+            raise FakeError(-1, "more seeds than centroids")
+        self.cent = self.p.ref.seeded(self._image(d_rgba, w * h), self.k, f)
+
+    def set_fixed(self, n_fixed):
+        if n_fixed > self.k:
+            raise FakeError(-1, "n_fixed > k")
+        if n_fixed == 0 and self.fault == "set_fixed_zero_ignored":
+            return
+        self.f = int(n_fixed)
+
+    def bind_image(self, d_rgba, n, stream=0):
+        self.bound = (d_rgba, n)
+
+    def unbind_image(self):
+        self.bound = None
+
+    def converged_count(self, stream=0):
+        return self.nconv
+
+    def update(self, d_acc, stream=0):
+        self._step(self._acc(d_acc).copy())
+
+    def assign_accumulate(self, d_rgba, n, d_labels, d_acc, stream=0):
+        labels, sums = self.p.ref.assign(self._image(d_rgba, n), self.cent)
+        if d_labels:
+            _view(d_labels, n, np.uint32)[:] = labels
+        if d_acc:
+            self._acc(d_acc)[:] = sums
+
+    def assign_update(self, d_rgba, n, d_labels, d_acc, do_update=True, stream=0):
+        self.assign_accumulate(d_rgba, n, d_labels, d_acc)
+        if do_update:
+            self.update(d_acc)
+
+    def iterate(self, d_rgba, n, d_labels, d_acc, update_first=True, stream=0):
+        if update_first:
+            self.update(d_acc)
+        self.assign_accumulate(d_rgba, n, d_labels, d_acc)
+
+    def flush(self, stream=0):
+        pass
+
+    def run(self, d_rgba, n, d_labels=0, stream=0):
+        self.cent, labels, it = self.p.ref.run(self._image(d_rgba, n), self.cent, self.f)
+        self.nconv = 0
+        if d_labels:
+            _view(d_labels, n, np.uint32)[:] = labels
+        return it
+
+    def accumulate_into(self, d_rgba, n, d_acc, stream=0):
+        if self.bound != (d_rgba, n):
+            raise FakeError(-1, "the image is not bound")
+        self._acc(d_acc)[:] += self.p.ref.assign(self._image(d_rgba, n), self.cent)[1]
+
+    def labels_from_tables_update(self, d_rgba, n, d_labels, d_acc, stream=0):
+        if self.bound is None:
+            raise FakeError(-1, "no bound image")
+        if self.k > 256:
+            raise FakeError(-5, "k <= 256")
+        _view(d_labels, n, np.uint32)[:] = self.p.ref.assign(self._image(d_rgba, n), self.cent)[0]
+        acc = self._acc(d_acc)
+        self._step(acc.copy())
+        acc[:] = 0
+
+
+class FakeEnv:
+    Error = FakeError
+
+    def __init__(self, images, cache, fault=None):
+        self.fault, self.images, self.cache = fault, images, cache
+        self.mem = HostMem()
+        self.streams = [0, 0]
+
+    def sync(self):
+        pass
+
+    def session_processor(self):
+        return FakeProcessor(self.fault, self.images, self.cache)
+
+    def lloyd(self, proc, k):
+        return FakeLloyd(proc, k, self.fault)
+
+
+def _env(seed, seq, cache, fault=None):
+    return FakeEnv(H.make_images(seed, seq), cache, fault)
+
+
+@pytest.fixture(scope="module")
+def campaign():
+    """every committed (seed, sequence) on the faithful stand-in and on each faulty one that seed has not caught yet"""
+    O.lib()
+    counters = collections.Counter()
+    caught = {seed: {} for seed in SEEDS}
+    failures, reused, n_ops = [], {}, 0
+    for seed in SEEDS:
+        reused[seed] = []
+        for seq in range(SEQUENCES):
+            answers = {}                          # the reference's answers: the same for every stand-in of this sequence
+            ops = H.generate(seed, seq)
+            try:
+                done, _, again = H.run_sequence(_env(seed, seq, answers), seed, seq, ops, counters, cache=answers)
+                reused[seed].append(again)
+                n_ops += done
+            except H.Mismatch as e:
+                failures.append(str(e)[:3000])
+            for fault in FAULTS:
+                if fault in caught[seed]:
+                    continue
+                try:
+                    H.run_sequence(_env(seed, seq, answers, fault), seed, seq, ops, cache=answers)
+                except H.Mismatch as e:
+                    caught[seed][fault] = (seq, str(e).split("\n")[0][:200])
+    return {"counters": counters, "caught": caught, "failures": failures, "reused": reused, "ops": n_ops}
+
+
+def test_generator_is_deterministic():
+    assert H.generate(SEEDS[0], 1) == H.generate(SEEDS[0], 1)
+    assert H.generate(SEEDS[0], 1) != H.generate(SEEDS[1], 1)
+    ops = H.generate(SEEDS[0], 0)
+    assert eval(repr(ops)) == ops                      # a sequence is a list of plain tuples: the printed list replays
+    a, b = H.make_images(SEEDS[0], 1), H._make_images(SEEDS[0], 1)
+    assert all(np.array_equal(x[1], y[1]) for x, y in zip(a, b))
+
+
+def test_faithful_stand_in_passes_every_sequence(campaign):
+    assert not campaign["failures"], "\n\n".join(campaign["failures"])
+    assert all(n > 0 for seed in SEEDS for n in campaign["reused"][seed]) and all(len(campaign["reused"][s]) == SEQUENCES for s in SEEDS), \
+        campaign["reused"]
+
+
+@pytest.mark.parametrize("fault", FAULTS)
+def test_every_seed_catches_the_faulty_stand_in(campaign, fault):
+    for seed in SEEDS:
+        assert fault in campaign["caught"][seed], f"seed {seed} does not catch {fault} in {SEQUENCES} sequences"
+
+
+def test_a_mismatch_prints_a_list_that_replays(campaign):
+    seq, _ = campaign["caught"][SEEDS[0]]["plan_follows_cutoff"]
+    with pytest.raises(H.Mismatch) as e:
+        H.run_sequence(_env(SEEDS[0], seq, {}, "plan_follows_cutoff"), SEEDS[0], seq)
+    text = str(e.value)
+    assert f"seed {SEEDS[0]} sequence {seq}: op " in text
+    ops = eval(text[text.index("replay(env, "):].split(", ", 3)[3][:-1])
+    with pytest.raises(H.Mismatch):
+        H.replay(_env(SEEDS[0], seq, {}, "plan_follows_cutoff"), SEEDS[0], seq, ops)
+    assert H.replay(_env(SEEDS[0], seq, {}), SEEDS[0], seq, ops)[0] == len(ops)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_vectorised_references_equal_their_loop_forms(seed):
+    """the model uses hold_ref.hold and the anti-diagonal diffusion; once per seed they are held against the literal per-pixel
+    loops (hold_ref.hold_loop, alpha_ref.diffuse_serial), and the index diffusion against the RGBA8 one"""
+    images = H.make_images(seed, 0)
+    rng = np.random.default_rng(seed)
+    for t in (0, 128):
+        img = np.ascontiguousarray(images[H.COL][1] if t else images[H.ROW][1])
+        crop = np.ascontiguousarray(images[H.SPRITE][1][20:44, 30:60])
+        cent, _ = H.gamut_centroids(seed, 9)
+        P = O.lab_to_rgba8(cent[:, :3])
+        for a in (img, crop):
+            idx = H.diffuse_index(a, cent, t)
+            want = alpha_ref.diffuse_serial(a, diffuse_ref.oracle_apply_replace(O, cent), t)
+            assert np.array_equal(P[idx][..., :3], want[..., :3])
+            assert np.array_equal(alpha_ref.diffuse(a, diffuse_ref.oracle_apply_replace(O, cent), t), want)
+    src, nxt = images[H.SPRITE][1][10:40, 20:60], images[3][1][10:40, 20:60]
+    index = rng.integers(0, 6, src.shape[:2])
+    canvas = np.where(rng.random(src.shape[:2]) < 0.3, 5, rng.integers(0, 6, src.shape[:2]))
+    for tol in (0, 40, 4096):
+        got = hold_ref.hold(O, nxt, index, canvas, src, 5, tol, row0=3)
+        want = hold_ref.hold_loop(O, nxt, index, canvas, src, 5, tol, row0=3)
+        assert all(np.array_equal(g, w) for g, w in zip(got[:3], want[:3])) and tuple(got[3]) == tuple(want[3])
+
+
+def _scenarios():
+    import test_gpu_session as G
+    return G
+
+
+@pytest.mark.parametrize("name", ["cutoff_0_128_0_around_palette_reduce_and_a_plan", "frames_added_under_three_cutoffs_then_clear",
+                                  "an_output_ends_a_lloyd_object_runs_in_its_block_and_the_next_output_starts_fresh",
+                                  "frozen_seeds_do_not_outlive_their_object", "quality_search_with_and_without_pins_beside_a_bound_object",
+                                  "records_combine_over_bands_in_reverse_on_two_streams", "every_refusal_is_followed_by_the_correct_call",
+                                  "two_sequences_alternate_beside_host_calls_on_the_megapixel_image"])
+def test_the_named_scenarios_of_the_device_are_legal_sequences(name):
+    """the op lists tests/test_gpu_session.py runs on the device, on the faithful stand-in (one processor per list here)"""
+    G = _scenarios()
+    assert set(G.SCENARIOS) >= {name}
+    ops = G.SCENARIOS[name]()
+    answers = {}
+    assert H.run_sequence(_env(G.SEED, G.SEQ, answers), G.SEED, G.SEQ, ops, cache=answers)[0] == len(ops)
+
+
+def test_every_scenario_of_the_device_is_checked_here():
+    G = _scenarios()
+    names = test_the_named_scenarios_of_the_device_are_legal_sequences.pytestmark[0].args[1]
+    assert sorted(G.SCENARIOS) == sorted(names)
+
+
+# what the committed seeds give (SEEDS x SEQUENCES), exactly: the generator is deterministic.  None may be zero.
+EXACT = {
+    'op:cutoff': 82, 'op:fixed': 68, 'op:strategy': 25, 'op:palette': 62, 'op:reduce': 26, 'op:reduce_indexed': 32, 'op:find':
+    12, 'op:find_indexed': 22, 'op:quality': 47, 'op:apply': 80, 'op:apply_plan': 38, 'op:compact': 16, 'op:compare_device': 36,
+    'op:pair_open': 24, 'op:pair_frame': 108, 'op:l_new': 29, 'op:l_re': 38, 'op:l_close': 29, 'op:l_set': 37, 'op:l_init': 30,
+    'op:l_fix': 52, 'op:l_bind': 4, 'op:l_conv': 21, 'op:l_update': 18, 'op:l_assign': 11, 'op:l_assign_update': 48,
+    'op:l_iterate': 10, 'op:l_run': 15, 'op:l_lftu': 13, 'op:s_new': 31, 'op:s_close': 31, 'op:s_add': 178, 'op:s_clear': 75,
+    'op:s_info': 39, 'op:s_centroids': 32, 'op:s_palette': 15, 'op:s_output': 98, 'op:s_end': 18, 'op:s_frame': 245,
+    'op:refuse': 67, 'refusal:k_below_fixed_palette': 8, 'refusal:k_below_fixed_reduce': 7, 'refusal:k_below_fixed_sequence': 1,
+    'refusal:octree_fixed': 9, 'refusal:frame_no_output': 5, 'refusal:delta_on_rgba8': 4, 'refusal:lossy_on_rgba8': 8,
+    'refusal:lossy_without_delta': 8, 'refusal:index8_full': 4, 'refusal:meld_indexed': 10, 'refusal:empty_sequence': 3,
+    'k:0:rgba8': 20, 'k:0:index8': 22, 'k:0:index16': 10, 'k:1:rgba8': 112, 'k:1:index8': 91, 'k:1:index16': 52, 'k:2:rgba8':
+    21, 'k:2:index8': 42, 'k:2:index16': 17, 'k:3:rgba8': 11, 'k:3:index8': 3, 'k:3:index16': 3, 'k:4:rgba8': 2, 'k:4:index16':
+    12, 'transition:exact>lossy': 46, 'transition:lossy>exact': 30, 'is_full_fallback': 46, 'frame_held_pixels': 21,
+    'mixed_cutoff_sequence': 28, 'plan_outlives_cutoff': 38, 'reoutput': 53, 'add_shrunk': 8, 'compare_host': 20,
+    'record_combined_across_images': 14, 'set_fixed_zero': 10, 'set_fixed': 42, 'pair_exact': 20, 'pair_lossy': 88,
+    'frame_exact': 159, 'frame_lossy': 86, 'update_with_n_fixed:l_update': 9, 'update_with_n_fixed:l_assign_update': 10,
+    'update_with_n_fixed:l_iterate': 5, 'update_with_n_fixed:l_run': 6, 'update_with_n_fixed:l_lftu': 6, 'compare_bands:1': 21,
+    'compare_bands:2': 9, 'compare_bands:3': 6, 'delta_bands:1': 50, 'delta_bands:2': 29, 'delta_bands:3': 29, 'fixed:0': 26,
+    'fixed:1': 3, 'fixed:2': 17, 'fixed:3': 22,
+}
+
+
+def coverage_names():
+    formats = {0: ("rgba8", "index8", "index16"), 1: ("rgba8", "index8", "index16"), 2: ("rgba8", "index8", "index16"),
+               3: ("rgba8", "index8", "index16"), 4: ("rgba8", "index16")}
+    return ["op:" + o for o in ("cutoff", "fixed", "strategy", "palette", "reduce", "reduce_indexed", "find", "find_indexed", "quality", "apply",
+                                "apply_plan", "compact", "compare_device", "pair_open", "pair_frame", "l_new", "l_re", "l_close", "l_set", "l_init",
+                                "l_fix", "l_bind", "l_conv", "l_update", "l_assign", "l_assign_update", "l_iterate", "l_run", "l_lftu", "s_new",
+                                "s_close", "s_add", "s_clear", "s_info", "s_centroids", "s_palette", "s_output", "s_end", "s_frame", "refuse")] + \
+           ["refusal:" + r for r in H.REFUSALS] + [f"k:{cls}:{f}" for cls, fs in formats.items() for f in fs] + \
+           ["transition:exact>lossy", "transition:lossy>exact", "is_full_fallback", "frame_held_pixels", "mixed_cutoff_sequence",
+            "plan_outlives_cutoff", "reoutput", "add_shrunk", "compare_host", "record_combined_across_images", "set_fixed_zero", "set_fixed",
+            "pair_exact", "pair_lossy", "frame_exact", "frame_lossy"] + \
+           ["update_with_n_fixed:" + n for n in ("l_update", "l_assign_update", "l_iterate", "l_run", "l_lftu")] + \
+           [f"compare_bands:{n}" for n in (1, 2, 3)] + [f"delta_bands:{n}" for n in (1, 2, 3)] + [f"fixed:{i}" for i in range(4)]
+
+
+def test_coverage_of_the_committed_seeds(campaign):
+    c = campaign["counters"]
+    print(dict(sorted(c.items())), campaign["ops"])
+    assert not campaign["failures"]
+    need = coverage_names()
+    assert set(need) == set(EXACT), sorted(set(need) ^ set(EXACT))
+    wrong = {name: (c[name], EXACT[name]) for name in need if c[name] != EXACT[name] or EXACT[name] < 1}
+    assert not wrong, wrong
+    assert all(n > 0 for seed in SEEDS for n in campaign["reused"][seed])          # blocks re-used, in every sequence

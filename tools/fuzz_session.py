@@ -1,0 +1,28 @@
+#!/usr/bin/env python3
+"""Random sessions on ONE long-lived processor against the stateless model (tests/session_harness.py): the sticky switches (alpha
+cutoff, fixed colours, strategy), host calls, output passes and plans, error records combined over bands, caller-owned delta
+canvases, two Lloyd objects with seeds and n_fixed, two Sequence objects with their outputs -- all closed and re-created in each
+other's blocks, every result compared byte for byte after every call, every refused call with the status include/kmeans_hip.h
+names.  A mismatch prints the op list (replay() of the harness runs it) and ends the run: nothing more is started on the device.
+usage: fuzz_session.py [sequences] [seed]"""
+import os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "kmeans-gpu_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import session_harness as H
+
+sequences = int(sys.argv[1]) if len(sys.argv) > 1 else 6
+seed = int(sys.argv[2]) if len(sys.argv) > 2 else 201
+env = H.KgEnv()
+ops_total, t0 = 0, time.time()
+for seq in range(sequences):
+    try:
+        n_ops, allocated, reused = H.run_sequence(env, seed, seq)
+    except H.Mismatch as e:
+        print(f"MISMATCH {e}", flush=True)
+        print(f"{seq + 1} sequences, {ops_total} ops, 1 mismatching")
+        sys.exit(1)
+    ops_total += n_ops
+    print(f"sequence {seq}: {n_ops} ops, {allocated} blocks allocated, {reused} blocks re-used", flush=True)
+print(f"{time.time() - t0:.1f} s")
+print(f"{sequences} sequences, {ops_total} ops, 0 mismatching")
