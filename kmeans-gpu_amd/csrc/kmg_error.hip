@@ -4,29 +4,21 @@
 //   k_error_palette  the q triples of a palette, (rint(64 L), rint(64 a), rint(64 b)) of the device's own rgb_to_lab, once per call:
 //                    entry i = (palette word, qL, qa, qb), 16 bytes
 //   k_error_stats    one template over the output's form (RGBA8 words; u8 / u16 indices; u32 labels, the quality search's own) and
-//                    over `what` (the Lab arithmetic is not compiled into the RGB-only instantiations).  At most kErrMaxGrid
-//                    workgroups over contiguous chunks of kErrTile-pixel tiles, as k_alpha_count; a lane takes four consecutive
-//                    pixels per tile -- one 16-byte source load and one 16- / 4- / 8- / 16-byte output load, or one load per pixel
-//                    when the pointers are not aligned for that -- and has the next tile's loads in flight during the current
-//                    tile's arithmetic.  Index forms: the palette (and its q triples) are staged once per workgroup in LDS.
-//                    Accumulators stay in registers (32-bit where a chunk cannot overflow them: see kErrLanePixels), are
-//                    reduced per wave with cross-lane operations, across the waves through LDS, and leave the workgroup as one
-//                    64-bit integer atomicAdd / atomicMax per non-zero field: at most 14 x 2048 integer atomics per launch, no
-//                    float atomics, no waits between workgroups.
+//                    over `what` (the Lab arithmetic is not compiled into the RGB-only instantiations), on the skeleton of
+//                    kmg_pass.h.  A lane takes four consecutive pixels per tile: one 16-byte source load and one 16- / 4- / 8- /
+//                    16-byte output load.  Index forms: the palette (and its q triples) are staged once per workgroup in LDS.
+//                    Accumulators are 32-bit where a run cannot overflow them (see kErrLanePixels) and leave the workgroup as
+//                    64-bit atomics: at most 14 x 2048 per launch.
 // A pixel that is not counted (out of range, alpha below the cutoff, invalid index) is compared with itself: it adds zero to
 // every sum and maximum without a branch per field.
 
-#include "kmg_device.h"
 #include "kmg_internal.h"
+#include "kmg_pass.h"
 
 namespace kmg {
 
 namespace {
 
-constexpr uint32_t kErrBlock = 256;                     // 4 waves
-constexpr uint32_t kErrWaves = kErrBlock / 64;
-constexpr uint32_t kErrTile = kErrBlock * 4;            // 4 consecutive pixels per lane
-constexpr uint32_t kErrMaxGrid = 2048;                  // cdna_hip_programming.md Guideline 11
 constexpr uint32_t kErrFields = 14;                     // kmg_error_stats as 14 x u64
 // n < 2^32 pixels are at most 2^22 tiles; a full grid gives a workgroup at most 2^22 / 2048 = 2048 of them, a lane 8192 pixels:
 // its 32-bit sums reach 8192 x 255^2 = 5.3e8 < 2^32.  (The Lab sum, up to 2^29 per pixel, is 64-bit.)
@@ -37,23 +29,13 @@ enum { fPixels = 0, fChanged = 1, fInvalid = 2, fSse = 3, fSad = 6, fMax = 9, fL
 
 __host__ __device__ constexpr bool field_is_max(uint32_t f) { return (f >= fMax && f < fMax + 3) || f == fLabMax; }
 
-// q of an sRGB8 colour: the fixed-point grid of the Lab terms
-__device__ __forceinline__ void px_to_q(const float *s_lut, uint32_t px, int32_t q[3])
-{
-    float L, a, b;
-    px_to_lab(s_lut, px, L, a, b);
-    q[0] = (int32_t)rintf(L * 64.0f);
-    q[1] = (int32_t)rintf(a * 64.0f);
-    q[2] = (int32_t)rintf(b * 64.0f);
-}
-
-__global__ __launch_bounds__(kErrBlock) void k_error_palette(const uint32_t *__restrict__ pal, uint32_t k, const float *__restrict__ lut,
+__global__ __launch_bounds__(kPassBlock) void k_error_palette(const uint32_t *__restrict__ pal, uint32_t k, const float *__restrict__ lut,
                                                             int4 *__restrict__ entries)
 {
     __shared__ float s_lut[256];
     s_lut[threadIdx.x] = lut[threadIdx.x];
     __syncthreads();
-    const uint32_t i = blockIdx.x * kErrBlock + threadIdx.x;
+    const uint32_t i = blockIdx.x * kPassBlock + threadIdx.x;
     if (i >= k) return;
     const uint32_t px = pal[i];
     int32_t q[3];
@@ -65,40 +47,13 @@ __global__ __launch_bounds__(kErrBlock) void k_error_palette(const uint32_t *__r
 template <int FORM>
 __device__ __forceinline__ void load4_out(const void *out, uint64_t i0, uint64_t n, bool aligned, uint32_t v[4])
 {
-    if (FORM == kErrorRgba8 || FORM == kErrorLabel32) {
-        load4_stream(static_cast<const uint32_t *>(out), i0, n, aligned, v);
-    } else if (FORM == kErrorIndex8) {
-        const uint8_t *o = static_cast<const uint8_t *>(out);
-        if (aligned && i0 + 4 <= n) {
-            const uint32_t w = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(o + i0));
-            v[0] = w & 255u; v[1] = (w >> 8) & 255u; v[2] = (w >> 16) & 255u; v[3] = w >> 24;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = (i0 + j < n) ? (uint32_t)o[i0 + j] : 0u;
-        }
-    } else {
-        const uint16_t *o = static_cast<const uint16_t *>(out);
-        if (aligned && i0 + 4 <= n) {
-            const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(o + i0));
-            v[0] = w.x & 0xFFFFu; v[1] = w.x >> 16; v[2] = w.y & 0xFFFFu; v[3] = w.y >> 16;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = (i0 + j < n) ? (uint32_t)o[i0 + j] : 0u;
-        }
-    }
-}
-
-// tiles [t0, t1) of this workgroup's chunk
-__device__ __forceinline__ void error_chunk(uint64_t n, uint64_t &t0, uint64_t &t1)
-{
-    const uint64_t tiles = (n + kErrTile - 1) / kErrTile;
-    const uint64_t per = (tiles + gridDim.x - 1) / gridDim.x;
-    t0 = min((uint64_t)blockIdx.x * per, tiles);
-    t1 = min(t0 + per, tiles);
+    if (FORM == kErrorIndex8) load4_index<uint8_t, true>(static_cast<const uint8_t *>(out), i0, n, aligned, v);
+    else if (FORM == kErrorIndex16) load4_index<uint16_t, true>(static_cast<const uint16_t *>(out), i0, n, aligned, v);
+    else load4_stream(static_cast<const uint32_t *>(out), i0, n, aligned, v);
 }
 
 template <int FORM, uint32_t WHAT>
-__global__ __launch_bounds__(kErrBlock) void k_error_stats(const uint32_t *__restrict__ src, const void *__restrict__ out, uint64_t n,
+__global__ __launch_bounds__(kPassBlock) void k_error_stats(const uint32_t *__restrict__ src, const void *__restrict__ out, uint64_t n,
                                                           const uint32_t *__restrict__ pal, const int4 *__restrict__ entries, uint32_t k,
                                                           uint32_t cutoff, const float *__restrict__ lut,
                                                           unsigned long long *__restrict__ stats, int aligned)
@@ -106,13 +61,13 @@ __global__ __launch_bounds__(kErrBlock) void k_error_stats(const uint32_t *__res
     constexpr bool RGB = (WHAT & KMG_ERROR_RGB) != 0, LAB = (WHAT & KMG_ERROR_LAB) != 0, INDEXED = FORM != kErrorRgba8;
     extern __shared__ uint4 s_dyn[];                            // index forms: k words, or -- LAB -- k (word, qL, qa, qb) entries
     __shared__ float s_lut[LAB ? 256 : 1];
-    __shared__ unsigned long long s_part[kErrWaves][kErrFields];
+    __shared__ unsigned long long s_part[kPassWaves][kErrFields];
     const uint32_t *s_pal = reinterpret_cast<const uint32_t *>(s_dyn);
     const int4 *s_ent = reinterpret_cast<const int4 *>(s_dyn);
     if (LAB) s_lut[threadIdx.x] = lut[threadIdx.x];
     if (INDEXED) {
-        if (LAB) for (uint32_t i = threadIdx.x; i < k; i += kErrBlock) reinterpret_cast<int4 *>(s_dyn)[i] = entries[i];
-        else for (uint32_t i = threadIdx.x; i < k; i += kErrBlock) reinterpret_cast<uint32_t *>(s_dyn)[i] = pal[i];
+        if (LAB) for (uint32_t i = threadIdx.x; i < k; i += kPassBlock) reinterpret_cast<int4 *>(s_dyn)[i] = entries[i];
+        else for (uint32_t i = threadIdx.x; i < k; i += kPassBlock) reinterpret_cast<uint32_t *>(s_dyn)[i] = pal[i];
     }
     if (LAB || INDEXED) __syncthreads();
 
@@ -121,19 +76,19 @@ __global__ __launch_bounds__(kErrBlock) void k_error_stats(const uint32_t *__res
     unsigned long long lab_sse = 0;
 
     uint64_t t0, t1;
-    error_chunk(n, t0, t1);
+    tile_run((n + kPassTile - 1) / kPassTile, t0, t1);
     uint32_t ns[4] = {0u, 0u, 0u, 0u}, no[4] = {0u, 0u, 0u, 0u};
     if (t0 < t1) {
-        const uint64_t i0 = t0 * kErrTile + (uint64_t)threadIdx.x * 4u;
+        const uint64_t i0 = t0 * kPassTile + (uint64_t)threadIdx.x * 4u;
         load4_stream(src, i0, n, aligned != 0, ns);
         load4_out<FORM>(out, i0, n, aligned != 0, no);
     }
     for (uint64_t t = t0; t < t1; ++t) {
-        const uint64_t i0 = t * kErrTile + (uint64_t)threadIdx.x * 4u;
+        const uint64_t i0 = t * kPassTile + (uint64_t)threadIdx.x * 4u;
         const uint32_t ps[4] = {ns[0], ns[1], ns[2], ns[3]}, po[4] = {no[0], no[1], no[2], no[3]};
         if (t + 1 < t1) {                                       // the next tile, in flight meanwhile
-            load4_stream(src, i0 + kErrTile, n, aligned != 0, ns);
-            load4_out<FORM>(out, i0 + kErrTile, n, aligned != 0, no);
+            load4_stream(src, i0 + kPassTile, n, aligned != 0, ns);
+            load4_out<FORM>(out, i0 + kPassTile, n, aligned != 0, no);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -204,7 +159,7 @@ __global__ __launch_bounds__(kErrBlock) void k_error_stats(const uint32_t *__res
         if (wanted) {
             unsigned long long x = 0;
 #pragma unroll
-            for (uint32_t w = 0; w < kErrWaves; ++w) x = field_is_max(f) ? max(x, s_part[w][f]) : x + s_part[w][f];
+            for (uint32_t w = 0; w < kPassWaves; ++w) x = field_is_max(f) ? max(x, s_part[w][f]) : x + s_part[w][f];
             if (x != 0) {                                       // (adding 0 or maxing with 0 changes nothing)
                 if (field_is_max(f)) atomicMax(stats + f, x);
                 else atomicAdd(stats + f, x);
@@ -217,14 +172,13 @@ template <int FORM>
 hipError_t error_stats_form(uint32_t what, const uint32_t *src, const void *out, uint64_t n, const uint32_t *pal, const void *entries,
                             uint32_t k, uint32_t cutoff, const float *lut, unsigned long long *stats, hipStream_t st)
 {
-    const uint64_t tiles = (n + kErrTile - 1) / kErrTile;
-    const uint32_t grid = (uint32_t)(tiles < kErrMaxGrid ? (tiles ? tiles : 1) : kErrMaxGrid);
+    const uint32_t grid = pass_grid((n + kPassTile - 1) / kPassTile);
     // the vector loads: the source 16-byte aligned, the output for its own (RGBA8 words and u32 labels 16, u8 4, u16 8 bytes)
     const uintptr_t out_mask = FORM == kErrorIndex8 ? 3u : (FORM == kErrorIndex16 ? 7u : 15u);
     const int aligned = ((reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & out_mask) == 0) ? 1 : 0;
     const bool lab = (what & KMG_ERROR_LAB) != 0;
     const size_t lds = FORM == kErrorRgba8 ? 0 : (size_t)k * (lab ? sizeof(int4) : sizeof(uint32_t));
-#define KMG_ES(W) hipLaunchKernelGGL((k_error_stats<FORM, W>), dim3(grid), dim3(kErrBlock), lds, st, src, out, n, pal, \
+#define KMG_ES(W) hipLaunchKernelGGL((k_error_stats<FORM, W>), dim3(grid), dim3(kPassBlock), lds, st, src, out, n, pal, \
                                      static_cast<const int4 *>(entries), k, cutoff, lut, stats, aligned)
     if (what == KMG_ERROR_RGB) KMG_ES(KMG_ERROR_RGB);
     else if (what == KMG_ERROR_LAB) KMG_ES(KMG_ERROR_LAB);
@@ -239,7 +193,7 @@ size_t error_palette_bytes(uint32_t k) { return sizeof(int4) * (size_t)k; }
 
 hipError_t launch_error_palette(const uint32_t *pal, uint32_t k, const float *lut, void *entries, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_error_palette, dim3((k + kErrBlock - 1) / kErrBlock), dim3(kErrBlock), 0, st, pal, k, lut, static_cast<int4 *>(entries));
+    hipLaunchKernelGGL(k_error_palette, dim3((k + kPassBlock - 1) / kPassBlock), dim3(kPassBlock), 0, st, pal, k, lut, static_cast<int4 *>(entries));
     return hipGetLastError();
 }
 

@@ -1,65 +1,26 @@
 // kmg_hold.hip -- lossy delta frames (kmg_dev_frame_delta_lossy, include/kmeans_hip.h): the delta pass of
 // kmg_sequence.hip with a second per-pixel state, the held source, and a tolerance on the integer Lab grid of kmg_error.hip.
 //
-//   k_frame_hold     one template over the index type (u8 / u16).  At most kHoldMaxGrid workgroups over contiguous runs of
-//                    kHoldTile-pixel tiles (k_error_stats); a lane takes four consecutive pixels per tile -- one 16-byte
-//                    non-temporal load of the source, one 16-byte load of the held source, one 4- / 8-byte load of the frame's
-//                    indices and of the canvas, or one load per pixel with bounds when the pointers are not aligned for that -- and
-//                    has the next tile's loads in flight during the current tile's arithmetic.  The decode table is staged once
-//                    per workgroup in LDS.  A pixel whose R, G, B bytes equal its held word's has D = 0 without a conversion; a
-//                    pixel that cannot be held (slot k on either side) needs no D at all.  The delta map is stored for every
-//                    group of four, the canvas and the held source only where a pixel of the group changes them.  Coordinates:
-//                    one division per lane and launch, every further tile adds the tile's (columns, rows) step (k_frame_delta).
-//                    Counts, box and sums stay in registers, are reduced per wave with cross-lane operations, across the waves
-//                    through LDS, and leave the workgroup as one integer atomicAdd / atomicMin / atomicMax per field that has
-//                    something to say: at most 8 x 2048 integer atomics per launch, no float atomics, no waits between workgroups.
+//   k_frame_hold     one template over the index type (u8 / u16), on the skeleton of kmg_pass.h.  A lane takes four consecutive
+//                    pixels per tile: one 16-byte non-temporal load of the source, one 16-byte load of the held source, one 4- /
+//                    8-byte load of the frame's indices and of the canvas.  The decode table is staged once per workgroup in LDS.
+//                    A pixel whose R, G, B bytes equal its held word's has D = 0 without a conversion; a pixel that cannot be
+//                    held (slot k on either side) needs no D at all.  The delta map is stored for every group of four, the
+//                    canvas and the held source only where a pixel of the group changes them.  Coordinates: one division per lane
+//                    and launch, every further tile adds the tile's (columns, rows) step (k_frame_delta).  Seven u32 fields and
+//                    the u64 held_sse are reduced as kmg_pass.h says: at most 8 x 2048 atomics per launch.
 // An element outside the band reads as 0 in all four buffers: held with D = 0 and equal indices, it adds nothing anywhere.
 
-#include "kmg_device.h"
+#include "kmg_pass.h"
 #include "kmg_state.h"
 
 namespace kmg {
 
 namespace {
 
-constexpr uint32_t kHoldBlock = 256;                    // 4 waves
-constexpr uint32_t kHoldWaves = kHoldBlock / 64;
-constexpr uint32_t kHoldTile = kHoldBlock * 4;          // 4 consecutive pixels per lane
-constexpr uint32_t kHoldMaxGrid = 2048;                 // cdna_hip_programming.md Guideline 11
-constexpr uint32_t kHoldFresh = 0xFFFFFFFFu;
 // n < 2^32 pixels are at most 2^22 tiles; a full grid gives a workgroup at most 2048 of them, a lane 8192 pixels: the counts are
 // 32-bit, held_sse (up to 347 973 309 per pixel) is 64-bit throughout.
 enum { hChanged = 0, hCleared = 1, hX0 = 2, hY0 = 3, hX1 = 4, hY1 = 5, hHeld = 6, hFields = 7 };
-
-// q of an sRGB8 colour: the fixed-point grid of kmg_error_stats (kmg_error.hip px_to_q, operation by operation)
-__device__ __forceinline__ void hold_q(const float *s_lut, uint32_t px, int32_t q[3])
-{
-    float L, a, b;
-    px_to_lab(s_lut, px, L, a, b);
-    q[0] = (int32_t)rintf(L * 64.0f);
-    q[1] = (int32_t)rintf(a * 64.0f);
-    q[2] = (int32_t)rintf(b * 64.0f);
-}
-
-// four consecutive indices as words: one 4-byte (u8) or 8-byte (u16) load, or one load per index in range
-template <typename T, bool NT>
-__device__ __forceinline__ void load4_index(const T *p, uint64_t i0, uint64_t n, bool aligned, uint32_t v[4])
-{
-    if (aligned && i0 + 4 <= n) {
-        if (sizeof(T) == 1) {
-            const uint32_t *q = reinterpret_cast<const uint32_t *>(p + i0);
-            const uint32_t w = NT ? __builtin_nontemporal_load(q) : *q;
-            v[0] = w & 255u; v[1] = (w >> 8) & 255u; v[2] = (w >> 16) & 255u; v[3] = w >> 24;
-        } else {
-            const u32x2 *q = reinterpret_cast<const u32x2 *>(p + i0);
-            const u32x2 w = NT ? __builtin_nontemporal_load(q) : *q;
-            v[0] = w.x & 0xFFFFu; v[1] = w.x >> 16; v[2] = w.y & 0xFFFFu; v[3] = w.y >> 16;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (i0 + j < n) ? (uint32_t)p[i0 + j] : 0u;
-    }
-}
 
 // one lane's four pixels of a tile: source, held source, frame index, canvas index
 struct HoldGroup { uint32_t s[4], h[4], c[4], v[4]; };
@@ -75,32 +36,32 @@ __device__ __forceinline__ void hold_load(const uint32_t *src, const uint32_t *h
 }
 
 template <typename T>
-__global__ __launch_bounds__(kHoldBlock) void k_frame_hold(const uint32_t *src, const T *index, T *canvas, uint32_t *held,
+__global__ __launch_bounds__(kPassBlock) void k_frame_hold(const uint32_t *src, const T *index, T *canvas, uint32_t *held,
                                                            T *__restrict__ delta, uint64_t n, uint32_t width, uint32_t row0, uint32_t k,
                                                            uint32_t tolerance, const float *__restrict__ lut, int aligned, uint32_t step_x,
                                                            uint32_t step_y, unsigned long long *__restrict__ info)
 {
     __shared__ float s_lut[256];
-    __shared__ uint32_t s_part[kHoldWaves][hFields];
-    __shared__ unsigned long long s_sse[kHoldWaves];
+    __shared__ uint32_t s_part[kPassWaves][hFields];
+    __shared__ unsigned long long s_sse[kPassWaves];
     s_lut[threadIdx.x] = lut[threadIdx.x];
     __syncthreads();
 
-    const uint64_t tiles = (n + kHoldTile - 1) / kHoldTile;
-    const uint64_t per = (tiles + gridDim.x - 1) / gridDim.x;
-    const uint64_t t0 = min((uint64_t)blockIdx.x * per, tiles), t1 = min(t0 + per, tiles);
+    uint64_t t0, t1;
+    tile_run((n + kPassTile - 1) / kPassTile, t0, t1);
 
-    uint32_t changed = 0, cleared = 0, n_held = 0, bx0 = kHoldFresh, by0 = kHoldFresh, bx1 = 0, by1 = 0;
+    uint32_t changed = 0, cleared = 0, n_held = 0;
+    uint32_t bx0 = kFresh, by0 = kFresh, bx1 = 0, by1 = 0;
     unsigned long long held_sse = 0;
     if (t0 < t1) {
-        uint64_t i0 = t0 * kHoldTile + (uint64_t)threadIdx.x * 4u;
+        uint64_t i0 = t0 * kPassTile + (uint64_t)threadIdx.x * 4u;
         // (x, y) of pixel i0: the one division of this lane
         uint32_t y = (uint32_t)(i0 / width), x = (uint32_t)(i0 - (uint64_t)y * width);
         HoldGroup nx;
         hold_load<T>(src, held, index, canvas, i0, n, aligned != 0, nx);
         for (uint64_t t = t0; t < t1; ++t) {
             const HoldGroup g = nx;
-            if (t + 1 < t1) hold_load<T>(src, held, index, canvas, i0 + kHoldTile, n, aligned != 0, nx);   // the next tile, in flight meanwhile
+            if (t + 1 < t1) hold_load<T>(src, held, index, canvas, i0 + kPassTile, n, aligned != 0, nx);   // the next tile, in flight meanwhile
             uint32_t out_d[4], out_c[4], out_h[4], ch_mask = 0;
             bool put_canvas = false, put_held = false;
 #pragma unroll
@@ -110,8 +71,8 @@ __global__ __launch_bounds__(kHoldBlock) void k_frame_hold(const uint32_t *src, 
                 uint32_t D = 0;
                 if (holdable && ((s ^ h) & 0x00FFFFFFu) != 0u) {    // equal bytes have equal q: D = 0 without a conversion
                     int32_t qs[3], qh[3];
-                    hold_q(s_lut, s, qs);
-                    hold_q(s_lut, h, qh);
+                    px_to_q(s_lut, s, qs);
+                    px_to_q(s_lut, h, qh);
                     const int32_t dL = qs[0] - qh[0], da = qs[1] - qh[1], db = qs[2] - qh[2];
                     D = (uint32_t)(dL * dL) + (uint32_t)(da * da) + (uint32_t)(db * db);                   // < 2^29
                 }
@@ -145,7 +106,7 @@ __global__ __launch_bounds__(kHoldBlock) void k_frame_hold(const uint32_t *src, 
                 }
             }
             // the same lane's pixels of the next tile
-            i0 += kHoldTile;
+            i0 += kPassTile;
             const uint64_t xs = (uint64_t)x + step_x;
             y += step_y;
             if (xs >= width) { x = (uint32_t)(xs - width); ++y; } else x = (uint32_t)xs;
@@ -175,15 +136,15 @@ __global__ __launch_bounds__(kHoldBlock) void k_frame_hold(const uint32_t *src, 
         const bool is_min = f == hX0 || f == hY0, is_max = f == hX1 || f == hY1;
         uint32_t a = s_part[0][f];
 #pragma unroll
-        for (uint32_t w = 1; w < kHoldWaves; ++w) a = is_min ? min(a, s_part[w][f]) : (is_max ? max(a, s_part[w][f]) : a + s_part[w][f]);
+        for (uint32_t w = 1; w < kPassWaves; ++w) a = is_min ? min(a, s_part[w][f]) : (is_max ? max(a, s_part[w][f]) : a + s_part[w][f]);
         uint32_t *box = reinterpret_cast<uint32_t *>(info + 2);
-        if (is_min) { if (a != kHoldFresh) atomicMin(box + (f - hX0), a); }
+        if (is_min) { if (a != kFresh) atomicMin(box + (f - hX0), a); }
         else if (is_max) { if (a) atomicMax(box + (f - hX0), a); }
         else if (a) atomicAdd(info + (f == hHeld ? 4u : f), (unsigned long long)a);
     } else if (threadIdx.x == hFields) {
         unsigned long long a = s_sse[0];
 #pragma unroll
-        for (uint32_t w = 1; w < kHoldWaves; ++w) a += s_sse[w];
+        for (uint32_t w = 1; w < kPassWaves; ++w) a += s_sse[w];
         if (a) atomicAdd(info + 5, a);
     }
 }
@@ -192,16 +153,15 @@ template <typename T>
 hipError_t frame_hold_typed(const void *src, const void *index, void *canvas, void *held, void *delta, uint64_t n, uint32_t width,
                             uint32_t row0, uint32_t k, uint32_t tolerance, const float *lut, unsigned long long *info, hipStream_t st)
 {
-    const uint64_t tiles = (n + kHoldTile - 1) / kHoldTile;
-    const uint32_t grid = (uint32_t)(tiles < kHoldMaxGrid ? (tiles ? tiles : 1) : kHoldMaxGrid);
+    const uint32_t grid = pass_grid((n + kPassTile - 1) / kPassTile);
     // the vector accesses: the two RGBA8 streams 16-byte aligned, the three index streams for their own (u8: 4, u16: 8 bytes)
     const uintptr_t im = 4u * sizeof(T) - 1u;
     const uintptr_t words = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(held);
     const uintptr_t idx = reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(canvas) | reinterpret_cast<uintptr_t>(delta);
     const int aligned = ((words & 15u) == 0 && (idx & im) == 0) ? 1 : 0;
-    hipLaunchKernelGGL((k_frame_hold<T>), dim3(grid), dim3(kHoldBlock), 0, st, static_cast<const uint32_t *>(src), static_cast<const T *>(index),
+    hipLaunchKernelGGL((k_frame_hold<T>), dim3(grid), dim3(kPassBlock), 0, st, static_cast<const uint32_t *>(src), static_cast<const T *>(index),
                        static_cast<T *>(canvas), static_cast<uint32_t *>(held), static_cast<T *>(delta), n, width, row0, k, tolerance, lut,
-                       aligned, kHoldTile % width, kHoldTile / width, info);
+                       aligned, kPassTile % width, kPassTile / width, info);
     return hipGetLastError();
 }
 
@@ -212,22 +172,10 @@ int frame_hold_impl(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_i
                     hipStream_t st)
 {
     static_assert(sizeof(kmg_frame_hold) == 48, "kmg_frame_hold is 48 bytes");
-    if (format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8");
-    if (format != KMG_FORMAT_INDEX8 && format != KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
-    if (k == 0 || k > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u: 1 .. %u", k, KMG_MAX_K);
-    if (format == KMG_FORMAT_INDEX8 && k > 255u) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u plus the transparent slot needs INDEX16", k);
-    if (!p || !d_src_rgba || !d_index || !d_canvas || !d_held_rgba || !d_delta || !d_info)
-        return fail(KMG_ERR_INVALID_ARGUMENT, "frame_delta_lossy: a pointer is NULL");
-    if (width == 0 || rows == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "frame_delta_lossy: the band has zero width or no rows");
+    const int rc = check_index_band("frame_delta_lossy", true, p, d_index, d_canvas, d_delta, d_src_rgba, d_held_rgba, d_info, width, rows, row0,
+                                    format, k);
+    if (rc != KMG_OK) return rc;
     const uint64_t n = (uint64_t)width * rows;
-    if (n > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
-    if ((uint64_t)row0 + rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "row0 + rows exceeds 2^32-1");
-    if (format == KMG_FORMAT_INDEX16 &&
-        ((reinterpret_cast<uintptr_t>(d_index) | reinterpret_cast<uintptr_t>(d_canvas) | reinterpret_cast<uintptr_t>(d_delta)) & 1u))
-        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX16 buffers must be 2-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_src_rgba) | reinterpret_cast<uintptr_t>(d_held_rgba)) & 3u)
-        return fail(KMG_ERR_INVALID_ARGUMENT, "the source and the held source must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_info) & 7u) return fail(KMG_ERR_INVALID_ARGUMENT, "the hold record is not 8-byte aligned");
     HIP_TRY(hipSetDevice(p->device));
     unsigned long long *info = reinterpret_cast<unsigned long long *>(d_info);
     if (format == KMG_FORMAT_INDEX8)

@@ -67,6 +67,11 @@ uint32_t processor_fixed_count(kmg_processor *p);
 // (kmg_apply.hip).  The caller has every earlier run of the plan behind it on the stream of the next one.  Other modes: nothing.
 void apply_plan_restart(kmg_apply_plan *plan);
 
+// The argument checks of the two delta passes, in one order (kmg_sequence.hip): `name` prefixes the messages; lossy: the call has
+// the two RGBA8 buffers d_src / d_held and a hold record (exact: both NULL, a delta record).
+int check_index_band(const char *name, bool lossy, const kmg_processor *p, const void *d_index, const void *d_canvas, const void *d_delta,
+                     const void *d_src, const void *d_held, const void *d_info, uint32_t width, uint32_t rows, uint32_t row0, int format,
+                     uint32_t k);
 // kmg_dev_frame_delta_lossy on a hipStream_t (kmg_hold.hip): the sequence layer's lossy frames
 int frame_hold_impl(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_index, void *d_canvas, uint8_t *d_held_rgba, uint32_t width,
                     uint32_t rows, uint32_t row0, int format, uint32_t k, uint32_t tolerance, void *d_delta, kmg_frame_hold *d_info,

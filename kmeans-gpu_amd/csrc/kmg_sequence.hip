@@ -1,33 +1,32 @@
 // kmg_sequence.hip -- frame sequences (include/kmeans_hip.h at kmg_sequence): one palette for many frames, and
 // index maps as delta frames.
 //
-//   k_frame_delta    one template over the index type (u8 / u16).  The band is one flat run of width x rows elements in each of
-//                    its three buffers.  A lane takes 16 bytes of each per tile -- 16 or 8 consecutive elements: one 16-byte load
-//                    of the frame's indices and of the canvas, one 16-byte store of the delta map and, where the chunk changed at
-//                    all, of the canvas -- and has the next tile's loads in flight during the current tile's arithmetic.  The
-//                    chunks are laid out from the 16-byte boundary below the pointers, so the first and the last chunk of a band
-//                    may be partial: those go element by element, as every chunk does when the three pointers do not share one
-//                    offset within 16 bytes.  At most kDeltaMaxGrid workgroups over contiguous runs of tiles (k_error_stats,
-//                    k_alpha_count).  Coordinates: one division per lane and launch gives (x, y) of its first chunk, every
-//                    further tile adds the tile's (columns, rows) step; a changed chunk that lies within one row gets its box
-//                    from the first and last set bit of its change mask, one that crosses a row end walks its elements.  Counts
-//                    and box stay in registers, are reduced per wave with cross-lane operations, across the waves through LDS,
-//                    and leave the workgroup as one integer atomicAdd / atomicMin / atomicMax per field that has something to say.
+//   k_frame_delta    one template over the index type (u8 / u16), on the skeleton of kmg_pass.h.  The band is one flat run of
+//                    width x rows elements in each of its three buffers.  A lane takes 16 bytes of each per tile -- 16 or 8
+//                    consecutive elements: one 16-byte load of the frame's indices and of the canvas, one 16-byte store of the
+//                    delta map and, where the chunk changed at all, of the canvas.  The chunks are laid out from the 16-byte
+//                    boundary below the pointers, so the first and the last chunk of a band may be partial: those go element by
+//                    element, as every chunk does when the three pointers do not share one offset within 16 bytes.  A changed
+//                    chunk that lies within one row gets its box from the first and last set bit of its change mask, one that
+//                    crosses a row end walks its elements; (x, y) costs one division per lane and launch, every further tile adds
+//                    the tile's (columns, rows) step.  Six u32 fields are reduced as kmg_pass.h says.
 //   kmg_sequence     host object: the working sequence W (one device block, grown geometrically), the palette step on it, and
 //                    the frame output -- one apply plan, the frame buffers, the canvas and its held source (lossy frames:
 //                    kmg_hold.hip) in one block.
 
-#include "kmg_device.h"
+#include "kmg_pass.h"
 #include "kmg_state.h"
 
 namespace kmg {
 
 namespace {
 
-constexpr uint32_t kDeltaBlock = 256;                   // 4 waves
-constexpr uint32_t kDeltaWaves = kDeltaBlock / 64;
-constexpr uint32_t kDeltaMaxGrid = 2048;                // cdna_hip_programming.md Guideline 11
-constexpr uint32_t kFresh = 0xFFFFFFFFu;
+// tiles of kPassBlock 16-byte chunks that cover the flat elements [-shift, n)
+template <typename T>
+__host__ __device__ constexpr uint64_t delta_tiles(uint64_t n, uint32_t shift)
+{
+    return ((n + shift + 16 / sizeof(T) - 1) / (16 / sizeof(T)) + kPassBlock - 1) / kPassBlock;
+}
 
 // one lane's 16 bytes of the frame's indices and of the canvas
 struct DeltaChunk { uint32_t c[4], v[4]; };
@@ -58,23 +57,21 @@ __device__ __forceinline__ void delta_load(const T *index, const T *canvas, int6
 }
 
 template <typename T>
-__global__ __launch_bounds__(kDeltaBlock) void k_frame_delta(const T *index, T *canvas, T *__restrict__ delta, uint64_t n, uint32_t width,
+__global__ __launch_bounds__(kPassBlock) void k_frame_delta(const T *index, T *canvas, T *__restrict__ delta, uint64_t n, uint32_t width,
                                                             uint32_t row0, uint32_t k, uint32_t shift, int vec, uint32_t step_x,
                                                             uint32_t step_y, unsigned long long *__restrict__ info)
 {
     constexpr int E = 16 / sizeof(T), EPW = 4 / sizeof(T), BITS = 8 * sizeof(T);
     constexpr uint32_t MASK = (1u << BITS) - 1u;
-    __shared__ uint32_t s_part[kDeltaWaves][6];
+    __shared__ uint32_t s_part[kPassWaves][6];
 
-    // chunk c covers the flat elements [c E - shift, (c + 1) E - shift); tiles of kDeltaBlock chunks; this workgroup's run of tiles
-    const uint64_t chunks = (n + shift + E - 1) / E;
-    const uint64_t tiles = (chunks + kDeltaBlock - 1) / kDeltaBlock;
-    const uint64_t per = (tiles + gridDim.x - 1) / gridDim.x;
-    const uint64_t t0 = min((uint64_t)blockIdx.x * per, tiles), t1 = min(t0 + per, tiles);
+    // chunk c covers the flat elements [c E - shift, (c + 1) E - shift); tiles of kPassBlock chunks
+    uint64_t t0, t1;
+    tile_run(delta_tiles<T>(n, shift), t0, t1);
 
     uint32_t changed = 0, cleared = 0, bx0 = kFresh, by0 = kFresh, bx1 = 0, by1 = 0;
     if (t0 < t1) {
-        int64_t lo = (int64_t)((t0 * kDeltaBlock + threadIdx.x) * E) - (int64_t)shift;
+        int64_t lo = (int64_t)((t0 * kPassBlock + threadIdx.x) * E) - (int64_t)shift;
         // (x, y) of element `lo`: the one division of this lane (lo < 0, the partial first chunk, lies in the rows above the band)
         int64_t y = lo >= 0 ? (int64_t)((uint64_t)lo / width) : -(int64_t)(((uint64_t)(-lo) + width - 1) / width);
         uint32_t x = (uint32_t)(lo - y * (int64_t)width);
@@ -82,7 +79,7 @@ __global__ __launch_bounds__(kDeltaBlock) void k_frame_delta(const T *index, T *
         delta_load<T>(index, canvas, lo, n, vec != 0, nx);
         for (uint64_t t = t0; t < t1; ++t) {
             const DeltaChunk d = nx;
-            if (t + 1 < t1) delta_load<T>(index, canvas, lo + (int64_t)kDeltaBlock * E, n, vec != 0, nx);   // the next tile, in flight meanwhile
+            if (t + 1 < t1) delta_load<T>(index, canvas, lo + (int64_t)kPassBlock * E, n, vec != 0, nx);   // the next tile, in flight meanwhile
             uint32_t out[4] = {0u, 0u, 0u, 0u}, mask = 0, ncl = 0;
 #pragma unroll
             for (int j = 0; j < E; ++j) {
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(kDeltaBlock) void k_frame_delta(const T *index, T *
                 }
             }
             // the same lane's chunk of the next tile
-            lo += (int64_t)kDeltaBlock * E;
+            lo += (int64_t)kPassBlock * E;
             const uint64_t xs = (uint64_t)x + step_x;
             y += step_y;
             if (xs >= width) { x = (uint32_t)(xs - width); ++y; } else x = (uint32_t)xs;
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(kDeltaBlock) void k_frame_delta(const T *index, T *
         const uint32_t f = threadIdx.x;
         uint32_t a = s_part[0][f];
 #pragma unroll
-        for (uint32_t w = 1; w < kDeltaWaves; ++w) a = f < 2 ? a + s_part[w][f] : (f < 4 ? min(a, s_part[w][f]) : max(a, s_part[w][f]));
+        for (uint32_t w = 1; w < kPassWaves; ++w) a = f < 2 ? a + s_part[w][f] : (f < 4 ? min(a, s_part[w][f]) : max(a, s_part[w][f]));
         // kmg_frame_delta: two u64 sums, then x0, y0 (minima), x1, y1 (maxima) as u32; a field this workgroup cannot move is left alone
         uint32_t *box = reinterpret_cast<uint32_t *>(info + 2);
         if (f < 2) { if (a) atomicAdd(info + f, (unsigned long long)a); }
@@ -171,11 +168,8 @@ hipError_t frame_delta_typed(const void *index, void *canvas, void *delta, uint6
     const uintptr_t a = reinterpret_cast<uintptr_t>(index) & 15u;
     const int vec = (a == (reinterpret_cast<uintptr_t>(canvas) & 15u) && a == (reinterpret_cast<uintptr_t>(delta) & 15u)) ? 1 : 0;
     const uint32_t shift = vec ? (uint32_t)(a / sizeof(T)) : 0u;
-    const uint64_t chunks = (n + shift + E - 1) / E;
-    const uint64_t tiles = (chunks + kDeltaBlock - 1) / kDeltaBlock;
-    const uint32_t grid = (uint32_t)(tiles < kDeltaMaxGrid ? (tiles ? tiles : 1) : kDeltaMaxGrid);
-    const uint32_t tile_elems = kDeltaBlock * E;
-    hipLaunchKernelGGL((k_frame_delta<T>), dim3(grid), dim3(kDeltaBlock), 0, st, static_cast<const T *>(index), static_cast<T *>(canvas),
+    const uint32_t grid = pass_grid(delta_tiles<T>(n, shift)), tile_elems = kPassBlock * E;
+    hipLaunchKernelGGL((k_frame_delta<T>), dim3(grid), dim3(kPassBlock), 0, st, static_cast<const T *>(index), static_cast<T *>(canvas),
                        static_cast<T *>(delta), n, width, row0, k, shift, vec, tile_elems % width, tile_elems / width, info);
     return hipGetLastError();
 }
@@ -184,19 +178,9 @@ int frame_delta_impl(kmg_processor *p, const void *d_index, void *d_canvas, uint
                      uint32_t k, void *d_delta, kmg_frame_delta *d_info, hipStream_t st)
 {
     static_assert(sizeof(kmg_frame_delta) == 32, "kmg_frame_delta is 32 bytes");
-    if (format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8");
-    if (format != KMG_FORMAT_INDEX8 && format != KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
-    if (k == 0 || k > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u: 1 .. %u", k, KMG_MAX_K);
-    if (format == KMG_FORMAT_INDEX8 && k > 255u) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u plus the transparent slot needs INDEX16", k);
-    if (!p || !d_index || !d_canvas || !d_delta || !d_info) return fail(KMG_ERR_INVALID_ARGUMENT, "frame_delta: a pointer is NULL");
-    if (width == 0 || rows == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "frame_delta: the band has zero width or no rows");
+    const int rc = check_index_band("frame_delta", false, p, d_index, d_canvas, d_delta, nullptr, nullptr, d_info, width, rows, row0, format, k);
+    if (rc != KMG_OK) return rc;
     const uint64_t n = (uint64_t)width * rows;
-    if (n > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
-    if ((uint64_t)row0 + rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "row0 + rows exceeds 2^32-1");
-    if (format == KMG_FORMAT_INDEX16 &&
-        ((reinterpret_cast<uintptr_t>(d_index) | reinterpret_cast<uintptr_t>(d_canvas) | reinterpret_cast<uintptr_t>(d_delta)) & 1u))
-        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX16 buffers must be 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_info) & 7u) return fail(KMG_ERR_INVALID_ARGUMENT, "the delta record is not 8-byte aligned");
     HIP_TRY(hipSetDevice(p->device));
     unsigned long long *info = reinterpret_cast<unsigned long long *>(d_info);
     if (format == KMG_FORMAT_INDEX8) HIP_TRY(frame_delta_typed<uint8_t>(d_index, d_canvas, d_delta, n, width, row0, k, info, st));
@@ -205,6 +189,28 @@ int frame_delta_impl(kmg_processor *p, const void *d_index, void *d_canvas, uint
 }
 
 }  // namespace
+
+int check_index_band(const char *name, bool lossy, const kmg_processor *p, const void *d_index, const void *d_canvas, const void *d_delta,
+                     const void *d_src, const void *d_held, const void *d_info, uint32_t width, uint32_t rows, uint32_t row0, int format,
+                     uint32_t k)
+{
+    if (format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8");
+    if (format != KMG_FORMAT_INDEX8 && format != KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
+    if (k == 0 || k > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u: 1 .. %u", k, KMG_MAX_K);
+    if (format == KMG_FORMAT_INDEX8 && k > 255u) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u plus the transparent slot needs INDEX16", k);
+    if (!p || !d_index || !d_canvas || !d_delta || !d_info || (lossy && (!d_src || !d_held)))
+        return fail(KMG_ERR_INVALID_ARGUMENT, "%s: a pointer is NULL", name);
+    if (width == 0 || rows == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "%s: the band has zero width or no rows", name);
+    if ((uint64_t)width * rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
+    if ((uint64_t)row0 + rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "row0 + rows exceeds 2^32-1");
+    if (format == KMG_FORMAT_INDEX16 &&
+        ((reinterpret_cast<uintptr_t>(d_index) | reinterpret_cast<uintptr_t>(d_canvas) | reinterpret_cast<uintptr_t>(d_delta)) & 1u))
+        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX16 buffers must be 2-byte aligned");
+    if (lossy && ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_held)) & 3u))
+        return fail(KMG_ERR_INVALID_ARGUMENT, "the source and the held source must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_info) & 7u) return fail(KMG_ERR_INVALID_ARGUMENT, "the %s record is not 8-byte aligned", lossy ? "hold" : "delta");
+    return KMG_OK;
+}
 
 }  // namespace kmg
 
@@ -480,19 +486,23 @@ try {
 }
 KMG_ABI_CATCH
 
-extern "C" int kmg_sequence_output_frame(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, void *out, kmg_frame_delta *info,
-                                         int *is_full)
-try {
+namespace {
+
+// the fresh record on the device: zero sums and maxima, all-ones minima
+hipError_t fresh_record(kmg_frame_hold *d_info, size_t bytes, hipStream_t st)
+{
+    const hipError_t e = hipMemsetAsync(d_info, 0, bytes, st);
+    return e != hipSuccess ? e : hipMemsetAsync(&d_info->x0, 0xFF, 2 * sizeof(uint32_t), st);
+}
+
+// One frame through the open output (the callers have checked their arguments): upload, plan run, then -- delta -- the exact pass
+// (tolerance == NULL) or the lossy one on a fresh record, its read-back, and the download of the full map or the delta map.
+int output_frame(kmg_sequence *s, const uint8_t *rgba, bool delta, const uint32_t *tolerance, void *out, kmg_frame_hold *rec, bool *is_full)
+{
     int rc;
-    if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
-    if (!s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "no output is open (kmg_sequence_output_begin)");
-    if (!rgba || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame: a pointer is NULL");
-    if (flags & ~KMG_FRAME_DELTA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
-    const bool delta = (flags & KMG_FRAME_DELTA) != 0;
-    if (delta && s->format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8");
-    if (delta && (!info || !is_full)) return fail(KMG_ERR_INVALID_ARGUMENT, "KMG_FRAME_DELTA needs info and is_full");
     kmg_processor *p = s->p;
     hipStream_t st = s->sg.st;
+    const bool lossy = tolerance != nullptr;
     HIP_TRY(hipSetDevice(p->device));
     const size_t n = (size_t)s->width * s->height, map_bytes = n * format_bytes(s->format);
     HIP_TRY(copy_host_image(p, s->d_frame, rgba, n * 4, hipMemcpyHostToDevice, st));
@@ -501,27 +511,54 @@ try {
         (void)hipStreamSynchronize(st);
         return rc;
     }
-    kmg_frame_delta rec = {0, 0, kFresh, kFresh, 0, 0};
+    *rec = kmg_frame_hold{0, 0, kFresh, kFresh, 0, 0, 0, 0};
+    const size_t rec_bytes = lossy ? sizeof(kmg_frame_hold) : sizeof(kmg_frame_delta);     // (the exact record is the first 32 bytes)
     if (delta) {
-        HIP_TRY(hipMemsetAsync(s->d_info, 0, sizeof(kmg_frame_delta), st));            // the fresh record: zero sums and maxima,
-        HIP_TRY(hipMemsetAsync(&s->d_info->x0, 0xFF, 2 * sizeof(uint32_t), st));      // all-ones minima
-        if ((rc = frame_delta_impl(p, s->d_map, s->d_canvas, s->width, s->height, 0, s->format, s->k, s->d_delta,
-                                   reinterpret_cast<kmg_frame_delta *>(s->d_info), st)) != KMG_OK) {
+        HIP_TRY(fresh_record(s->d_info, rec_bytes, st));
+        if (lossy) rc = frame_hold_impl(p, s->d_frame, s->d_map, s->d_canvas, s->d_held, s->width, s->height, 0, s->format, s->k, *tolerance,
+                                        s->d_delta, s->d_info, st);
+        else rc = frame_delta_impl(p, s->d_map, s->d_canvas, s->width, s->height, 0, s->format, s->k, s->d_delta,
+                                   reinterpret_cast<kmg_frame_delta *>(s->d_info), st);
+        if (rc != KMG_OK) {
             (void)hipStreamSynchronize(st);
             return rc;
         }
-        std::swap(s->d_frame, s->d_held);                              // the canvas equals this frame's map: its held source is this frame
-        HIP_TRY(hipMemcpyAsync(&rec, s->d_info, sizeof rec, hipMemcpyDeviceToHost, st));
+        if (!lossy) std::swap(s->d_frame, s->d_held);                 // the canvas equals this frame's map: its held source is this frame
+        HIP_TRY(hipMemcpyAsync(rec, s->d_info, rec_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-    } else if (s->d_canvas) {
-        HIP_TRY(hipMemcpyAsync(s->d_canvas, s->d_map, map_bytes, hipMemcpyDeviceToDevice, st));   // a later delta frame starts from this one
+    }
+    const bool full = !delta || rec->cleared > 0;                      // "over" cannot show a pixel that turns transparent
+    // Index formats.  The canvas is made this frame's map where no pass did that: a frame without delta (a later delta frame starts
+    // from it), and a lossy frame that is sent in full (the viewer then shows I_t everywhere: the state of an exact frame).  Its held
+    // source then IS this frame: the two buffers swap instead of a copy.
+    if (s->d_canvas && (lossy ? full : !delta)) {
+        HIP_TRY(hipMemcpyAsync(s->d_canvas, s->d_map, map_bytes, hipMemcpyDeviceToDevice, st));
         std::swap(s->d_frame, s->d_held);
     }
-    const bool full = !delta || rec.cleared > 0;                       // "over" cannot show a pixel that turns transparent
     HIP_TRY(copy_host_image(p, out, full ? s->d_map : s->d_delta, map_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if ((rc = kmg_apply_plan_status(s->plan)) != KMG_OK) return rc;
-    if (info) *info = rec;
+    *is_full = full;
+    return KMG_OK;
+}
+
+}  // namespace
+
+extern "C" int kmg_sequence_output_frame(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, void *out, kmg_frame_delta *info,
+                                         int *is_full)
+try {
+    if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
+    if (!s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "no output is open (kmg_sequence_output_begin)");
+    if (!rgba || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame: a pointer is NULL");
+    if (flags & ~KMG_FRAME_DELTA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
+    const bool delta = (flags & KMG_FRAME_DELTA) != 0;
+    if (delta && s->format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8");
+    if (delta && (!info || !is_full)) return fail(KMG_ERR_INVALID_ARGUMENT, "KMG_FRAME_DELTA needs info and is_full");
+    kmg_frame_hold rec;
+    bool full;
+    const int rc = output_frame(s, rgba, delta, nullptr, out, &rec, &full);
+    if (rc != KMG_OK) return rc;
+    if (info) *info = kmg_frame_delta{rec.changed, rec.cleared, rec.x0, rec.y0, rec.x1, rec.y1};
     if (is_full) *is_full = full ? 1 : 0;
     return KMG_OK;
 }
@@ -530,7 +567,6 @@ KMG_ABI_CATCH
 extern "C" int kmg_sequence_output_frame_lossy(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, uint32_t tolerance, void *out,
                                                kmg_frame_hold *info, int *is_full)
 try {
-    int rc;
     if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
     if (!s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "no output is open (kmg_sequence_output_begin)");
     if (!rgba || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame_lossy: a pointer is NULL");
@@ -538,34 +574,10 @@ try {
     if (!(flags & KMG_FRAME_DELTA)) return fail(KMG_ERR_INVALID_ARGUMENT, "a lossy frame is a delta frame: KMG_FRAME_DELTA is required");
     if (s->format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8");
     if (!info || !is_full) return fail(KMG_ERR_INVALID_ARGUMENT, "KMG_FRAME_DELTA needs info and is_full");
-    kmg_processor *p = s->p;
-    hipStream_t st = s->sg.st;
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t n = (size_t)s->width * s->height, map_bytes = n * format_bytes(s->format);
-    HIP_TRY(copy_host_image(p, s->d_frame, rgba, n * 4, hipMemcpyHostToDevice, st));
-    if (s->mode == KMG_MODE_DIFFUSE) apply_plan_restart(s->plan);      // every frame is an image of its own
-    if ((rc = kmg_apply_plan_run(s->plan, s->d_frame, s->width, s->height, 0, s->d_map, st)) != KMG_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    kmg_frame_hold rec = {0, 0, kFresh, kFresh, 0, 0, 0, 0};
-    HIP_TRY(hipMemsetAsync(s->d_info, 0, sizeof(kmg_frame_hold), st));                 // the fresh record: zero sums and maxima,
-    HIP_TRY(hipMemsetAsync(&s->d_info->x0, 0xFF, 2 * sizeof(uint32_t), st));          // all-ones minima
-    if ((rc = frame_hold_impl(p, s->d_frame, s->d_map, s->d_canvas, s->d_held, s->width, s->height, 0, s->format, s->k, tolerance, s->d_delta,
-                              s->d_info, st)) != KMG_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(&rec, s->d_info, sizeof rec, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const bool full = rec.cleared > 0;                                 // "over" cannot show a pixel that turns transparent
-    if (full) {                                                        // the viewer then shows I_t everywhere: the state of an exact frame
-        HIP_TRY(hipMemcpyAsync(s->d_canvas, s->d_map, map_bytes, hipMemcpyDeviceToDevice, st));
-        std::swap(s->d_frame, s->d_held);
-    }
-    HIP_TRY(copy_host_image(p, out, full ? s->d_map : s->d_delta, map_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if ((rc = kmg_apply_plan_status(s->plan)) != KMG_OK) return rc;
+    kmg_frame_hold rec;
+    bool full;
+    const int rc = output_frame(s, rgba, true, &tolerance, out, &rec, &full);
+    if (rc != KMG_OK) return rc;
     *info = rec;
     *is_full = full ? 1 : 0;
     return KMG_OK;

@@ -150,6 +150,18 @@ def test_compare_device_4096_squared(oracle, torch_cuda, procs, fmt, k, cutoff):
     assert want[0] > 1 << 22 and want[12] > 1 << 40
 
 
+@pytest.mark.parametrize("n", [2048 * 1024 - 1, 2048 * 1024 + 1, 2049 * 1024 + 3])
+def test_compare_device_at_its_grid_edges(oracle, torch_cuda, procs, n):
+    """the partition of the tiles into the workgroups' runs where it is uneven: 2048 tiles with a ragged last one (one each); 2049
+    tiles (two per workgroup: 1024 full runs, one of a single ragged tile, 1023 empty ones); 2050 tiles, the last one ragged"""
+    rng = np.random.default_rng(n)
+    src, out, pal = _case(rng, n, INDEX8, 255, 128)
+    want = R.stats(oracle, src, out, palette=pal, cutoff=128)
+    got = _dev(torch_cuda, procs[0], src, out, INDEX8, pal, 128, R.RGB | R.LAB)
+    assert got == want, dict(zip(R.FIELDS, zip(got, want)))
+    assert want[0] > n // 4 and want[2] > 0
+
+
 def test_refusals_on_the_device(torch_cuda, procs):
     import kmeans_gpu_amd as kg
     torch = torch_cuda
