@@ -689,6 +689,85 @@ KMG_API int kmg_sequence_output_frame_lossy(kmg_sequence *s, const uint8_t *rgba
                                             kmg_frame_hold *info, int *is_full);
 KMG_API int kmg_sequence_output_end(kmg_sequence *s);
 
+/* ======================= index-map optimisation: usage counts, palette pruning, packed maps ===
+ * The last step before a PNG8 / GIF / APNG writer: which palette entries a map uses, a palette without the unused ones in the
+ * order a writer wants, and the map rewritten for it at 1, 2, 4, 8 or 16 bits per pixel.  All integers.  No counterpart in the
+ * reference.  Three building blocks -- count (device), plan (host), rewrite (device) -- and host-buffer calls over them.
+ *
+ * The usage record of a map with k colours is k + 2 uint64_t:
+ *   usage[i], i < k   pixels with index i
+ *   usage[k]          pixels with index k: the transparent slot of alpha mode, the "keep what is shown" value of delta maps
+ *   usage[k + 1]      pixels with an index above k (the `invalid` of kmg_error_stats)
+ * kmg_dev_index_usage COMBINES (adds) into d_usage as it stands -- the convention of kmg_dev_compare -- so the bands of a frame and
+ * the frames of a sequence, in any order, on any streams, end in the same record; the caller zeroes a fresh record.  d_index:
+ * DEVICE, n_pixels (< 2^32) elements of `format`, aligned to its element (a 4-element-aligned pointer allows the vector loads);
+ * d_usage: DEVICE, k + 2 entries, 8-byte aligned.  KMG_FORMAT_INDEX8 takes k <= 256 -- at k = 256 no byte can be slot k or above:
+ * usage[256] and usage[257] stay as they were -- KMG_FORMAT_INDEX16 any k <= KMG_MAX_K.  KMG_ERR_INVALID_ARGUMENT, nothing
+ * enqueued: KMG_FORMAT_RGBA8, k = 0 or above the format's limit, n_pixels = 0, a NULL pointer, a misaligned INDEX16 map or
+ * record.  Only enqueues work on `stream`.                                                                                  */
+KMG_API int kmg_dev_index_usage(kmg_processor *p, const void *d_index, uint64_t n_pixels, int format, uint32_t k, uint64_t *d_usage,
+                                void *stream);
+
+/* The plan: host arithmetic on a usage record and the palette it counts, no processor, no device.
+ *   kept colours   the entries i < k with usage[i] > 0; with KMG_INDEX_KEEP_UNUSED every i < k
+ *   their order    the low two bits of `flags`: KMG_INDEX_ORDER_KEEP ascending old index (fixed colours keep their relative
+ *                  order); _USAGE descending usage; _LUMA ascending 2126 R + 7152 G + 722 B of the palette bytes; ties by
+ *                  ascending old index
+ *   the slot       the transparent slot is present iff usage[k] > 0 or KMG_INDEX_KEEP_TRANSPARENT is set.  With
+ *                  KMG_INDEX_TRANSPARENT_FIRST it is new index 0 and the colours follow from 1 (a PNG tRNS chunk is then one
+ *                  byte); otherwise it is new index n_colors.  info->transparent = its new index, -1 when absent
+ *   n_slots        n_colors + (present ? 1 : 0); bits = the smallest of 1, 2, 4, 8, 16 with 2^bits >= n_slots
+ *   remap[old]     old = 0 .. k: the new index, 0xFFFF for a dropped entry
+ *   out_palette    [new] = the four palette bytes of the colour, (0, 0, 0, 0) for the transparent slot: n_slots x 4 bytes are
+ *                  written (PLTE + tRNS material as it stands); room for (k + 1) x 4; it may be `palette_rgba` itself
+ * ORDER_KEEP | KEEP_UNUSED | KEEP_TRANSPARENT without TRANSPARENT_FIRST is the identity: remap[i] = i for i <= k.
+ * KMG_ERR_INVALID_ARGUMENT, nothing written: usage[k + 1] != 0 ("the map holds indices above k"); n_slots = 0 (an all-zero
+ * record without the keep flags); unknown flag bits or order value 3; k = 0 or k > KMG_MAX_K; a NULL pointer.                */
+#define KMG_INDEX_ORDER_KEEP        0u
+#define KMG_INDEX_ORDER_USAGE       1u
+#define KMG_INDEX_ORDER_LUMA        2u
+#define KMG_INDEX_KEEP_UNUSED       4u
+#define KMG_INDEX_KEEP_TRANSPARENT  8u
+#define KMG_INDEX_TRANSPARENT_FIRST 16u
+typedef struct kmg_index_plan_info {  /* 16 bytes, no padding */
+    uint32_t n_colors;                /* kept colours                                                              */
+    uint32_t n_slots;                 /* n_colors, plus 1 when the transparent slot is present                     */
+    int32_t transparent;              /* the slot's new index, -1 when absent                                      */
+    uint32_t bits;                    /* 1, 2, 4, 8 or 16: what an index of n_slots needs                          */
+} kmg_index_plan_info;
+KMG_API int kmg_index_plan(const uint64_t *usage, const uint8_t *palette_rgba, uint32_t k, uint32_t flags, uint16_t *remap,
+                           uint8_t *out_palette_rgba, kmg_index_plan_info *info);
+
+/* Rewrite and pack: d_out = remap[d_in] at out_bits per pixel.
+ *   out_bits 8, 16     one uint8_t / uint16_t per pixel, rows contiguous: the layouts of KMG_FORMAT_INDEX8 / INDEX16; narrowing
+ *                      16 -> 8 and widening 8 -> 16 are both allowed
+ *   out_bits 1, 2, 4   packed rows as PNG stores them (a filter-0 scanline without its filter byte): every row starts on a byte,
+ *                      the stride is ceil(width * out_bits / 8), the leftmost pixel sits in the high bits, the padding bits of a
+ *                      row's last byte are zero
+ * A pixel is BAD if its index is above k, its remap entry is 0xFFFF, or its new index does not fit out_bits: it is written as 0
+ * and counted; the pass COMBINES (adds) the count into *d_bad.  d_in: DEVICE, width * rows (< 2^32) elements of in_format;
+ * remap: HOST, k + 1 entries, read before the call returns; d_out: DEVICE, 2-byte aligned for out_bits = 16; d_bad: DEVICE,
+ * 8-byte aligned.  d_out == d_in is allowed when out_bits equals the input's own width; otherwise the buffers must not overlap.
+ * Refusals: those of kmg_dev_index_usage, and out_bits outside {1, 2, 4, 8, 16}, zero width, zero rows.  Only enqueues work on
+ * `stream`.                                                                                                                 */
+KMG_API int kmg_dev_index_remap(kmg_processor *p, const void *d_in, int in_format, uint32_t width, uint32_t rows, uint32_t k,
+                                const uint16_t *remap, uint32_t out_bits, void *d_out, uint64_t *d_bad, void *stream);
+
+/* The same on HOST buffers; each uploads, runs and synchronises.
+ *   kmg_index_usage     COMBINES into the host record `usage` (k + 2 entries) as it stands
+ *   kmg_index_remap     out: ceil(width * out_bits / 8) * height bytes (1, 2 or width * height elements for 8 / 16);
+ *                       *bad (optional) = the number of bad pixels (overwritten)
+ *   kmg_index_optimize  one upload, usage, plan with `flags`, remap, download.  out_bits = 0 takes the plan's bits; a non-zero
+ *                       out_bits below them, and bits (given or the plan's) above the input map's own width, are
+ *                       KMG_ERR_INVALID_ARGUMENT, so out_map needs no more room than the input map.  out_palette_rgba: room for
+ *                       (k + 1) x 4 bytes, n_slots x 4 written; *info: the plan's; the refusals of kmg_index_plan apply.          */
+KMG_API int kmg_index_usage(kmg_processor *p, const void *index, int format, uint64_t n_pixels, uint32_t k, uint64_t *usage);
+KMG_API int kmg_index_remap(kmg_processor *p, const void *in, int in_format, uint32_t width, uint32_t height, uint32_t k,
+                            const uint16_t *remap, uint32_t out_bits, void *out, uint64_t *bad);
+KMG_API int kmg_index_optimize(kmg_processor *p, const void *index, int format, uint32_t width, uint32_t height,
+                               const uint8_t *palette_rgba, uint32_t k, uint32_t flags, uint32_t out_bits, uint8_t *out_palette_rgba,
+                               kmg_index_plan_info *info, void *out_map);
+
 /* ======================= several GPUs: a group of devices ================================
  * ImageProcessor::new (core/src/lib.rs:38-65) picks ONE adapter; the reference has no multi-device path.  A kmg_group is the
  * same constructor over a device LIST: one kmg_processor, one compute stream and one RCCL communicator rank per device.

@@ -178,4 +178,12 @@ hipError_t launch_error_palette(const uint32_t *pal, uint32_t k, const float *lu
 hipError_t launch_error_stats(int form, uint32_t what, const uint32_t *src, const void *out, uint64_t n, const uint32_t *pal,
                               const void *entries, uint32_t k, uint32_t cutoff, const float *lut, unsigned long long *stats, hipStream_t st);
 
+// ---- index-map optimisation (kmg_usage.hip; kmg_dev_index_usage / kmg_dev_index_remap of include/kmeans_hip.h).  wide: the map
+// holds u16 (else u8).  usage: k + 2 u64 the launch ADDS to (bin k: the transparent slot, bin k + 1: indices above k).  n < 2^32.
+hipError_t launch_index_usage(const void *index, bool wide, uint64_t n, uint32_t k, unsigned long long *usage, hipStream_t st);
+// out = map[in] at out_bits (8 / 16: one element per pixel; 1 / 2 / 4: packed rows, each starting on a byte); map: k + 1 u16 in
+// device memory, 0xFFFF = dropped; *bad += the pixels written as 0 because they have no new index that fits.  width * rows < 2^32.
+hipError_t launch_index_remap(const void *in, bool wide, uint32_t width, uint32_t rows, uint32_t k, const uint16_t *map, uint32_t out_bits,
+                              void *out, unsigned long long *bad, hipStream_t st);
+
 }  // namespace kmg

@@ -12,6 +12,7 @@
 //   processor.reduce_batch(color_count, images, algo, mode) -> whole images per device, side by side
 //   processor.compare(source, output[, colors])            -> kmg_error_stats: exact error sums of an output against its source
 //   processor.reduce_quality(image, max_delta_e, k_min, k_max, mode) -> the colour count chosen by a quality target
+//   processor.optimize_indexed(indexed[, flags, bits])     -> the palette without unused entries, ordered, and the map packed for it
 //   processor.set_fixed_colors(colors)                     -> palette entries the k-means keeps exactly and builds around
 //   Sequence seq(processor); seq.add(frame) ...; seq.output(k, mode, w, h); seq.frame(image) / seq.frame_lossy(image, delta_e)
 //                                                          -> one palette for many frames, exact and lossy delta frames (kmg_sequence_*)
@@ -216,6 +217,37 @@ public:
         q.indexed.palette.resize(n);
         q.reached = reached != 0;
         return q;
+    }
+
+    // kmg_index_optimize (single-device processors only): the palette of an index map without the entries no pixel uses, in the
+    // order `flags` asks for (KMG_INDEX_*), and the map rewritten for it -- packed rows of info.bits (or `bits`) per pixel, every row
+    // starting on a byte, as a PNG of colour type 3 stores them.  palette[info.transparent] is (0, 0, 0, 0) when the slot is there.
+    struct Optimized {
+        std::pair<uint32_t, uint32_t> dims;
+        kmg_index_plan_info info;
+        uint32_t bits = 0;                        // bits per pixel of `rows`
+        size_t stride = 0;                        // bytes per row: ceil(width * bits / 8)
+        std::vector<uint8_t> rows;                // stride * height bytes (bits = 16: uint16_t values in host order)
+        std::vector<RGBA8> palette;               // info.n_slots entries in the new index order
+    };
+    Optimized optimize_indexed(const Indexed &indexed, uint32_t flags = KMG_INDEX_ORDER_USAGE | KMG_INDEX_TRANSPARENT_FIRST,
+                               uint32_t bits = 0) const
+    {
+        Optimized out;
+        out.dims = indexed.dims;
+        const size_t n = (size_t)indexed.dims.first * indexed.dims.second;
+        const void *idx = indexed.format == KMG_FORMAT_INDEX8 ? static_cast<const void *>(indexed.index8.data())
+                                                              : static_cast<const void *>(indexed.index16.data());
+        out.rows.resize(n * (indexed.format == KMG_FORMAT_INDEX8 ? 1u : 2u));
+        out.palette.resize(indexed.palette.size() + 1);
+        check(kmg_index_optimize(single(), idx, indexed.format, indexed.dims.first, indexed.dims.second,
+                                 reinterpret_cast<const uint8_t *>(indexed.palette.data()), (uint32_t)indexed.palette.size(), flags, bits,
+                                 reinterpret_cast<uint8_t *>(out.palette.data()), &out.info, out.rows.data()));
+        out.bits = bits ? bits : out.info.bits;
+        out.stride = ((size_t)indexed.dims.first * out.bits + 7u) / 8u;
+        out.rows.resize(out.stride * indexed.dims.second);
+        out.palette.resize(out.info.n_slots);
+        return out;
     }
 
     // a batch: whole images per device (a single-device processor takes them one after the other)

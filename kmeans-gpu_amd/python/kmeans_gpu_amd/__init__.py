@@ -188,6 +188,81 @@ class FrameHold(C.Structure):           # include/kmeans_hip.h kmg_frame_hold: 4
         return "FrameHold" + repr(self.as_tuple())
 
 
+# include/kmeans_hip.h KMG_INDEX_*: the flags of kmg_index_plan (the low two bits are the order)
+INDEX_ORDER_KEEP, INDEX_ORDER_USAGE, INDEX_ORDER_LUMA = 0, 1, 2
+INDEX_KEEP_UNUSED, INDEX_KEEP_TRANSPARENT, INDEX_TRANSPARENT_FIRST = 4, 8, 16
+INDEX_DROPPED = 0xFFFF                  # remap entry of a palette entry the plan drops
+
+
+class IndexPlanInfo(C.Structure):       # include/kmeans_hip.h kmg_index_plan_info: 16 bytes
+    _fields_ = [("n_colors", C.c_uint32), ("n_slots", C.c_uint32), ("transparent", C.c_int32), ("bits", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.n_colors, self.n_slots, self.transparent, self.bits)
+
+    def __repr__(self):
+        return f"IndexPlanInfo(n_colors={self.n_colors}, n_slots={self.n_slots}, transparent={self.transparent}, bits={self.bits})"
+
+
+def index_plan(usage, palette, flags=INDEX_ORDER_USAGE | INDEX_TRANSPARENT_FIRST):
+    """kmg_index_plan (host arithmetic, no device): usage = the k + 2 counts of a map, palette (k, 4) uint8.  Returns (remap (k + 1,)
+    uint16 with INDEX_DROPPED for dropped entries, palette_out (n_slots, 4) uint8 with (0, 0, 0, 0) at the transparent slot,
+    IndexPlanInfo)."""
+    pal = np.ascontiguousarray(palette, np.uint8).reshape(-1, 4)
+    k = pal.shape[0]
+    use = np.ascontiguousarray(usage, np.uint64).reshape(-1)
+    if use.shape[0] != k + 2:
+        raise ValueError("usage must hold k + 2 counts for a palette of k colours")
+    remap = np.empty(k + 1, np.uint16)
+    out = np.empty((k + 1, 4), np.uint8)
+    info = IndexPlanInfo()
+    _check(lib().kmg_index_plan(_np_ptr(use), _np_ptr(pal), k, int(flags), _np_ptr(remap), _np_ptr(out), C.byref(info)))
+    return remap, out[:info.n_slots].copy(), info
+
+
+def packed_stride(width, bits):
+    """bytes of one row of `width` indices at `bits` per pixel (rows start on a byte)"""
+    return (int(width) * int(bits) + 7) // 8
+
+
+def pack_indices(index, bits):
+    """a (height, width) index map as PNG stores it at bits = 1, 2 or 4: (height, ceil(width * bits / 8)) uint8, the leftmost
+    pixel in the high bits, padding bits zero; bits = 8 / 16: the map as uint8 / uint16.  Every index must fit."""
+    a = np.asarray(index)
+    if a.ndim != 2:
+        raise ValueError("index map must be (height, width)")
+    if bits not in (1, 2, 4, 8, 16):
+        raise ValueError("bits must be 1, 2, 4, 8 or 16")
+    if a.size and int(a.max()) >= (1 << bits):
+        raise ValueError(f"an index does not fit {bits} bits")
+    if bits >= 8:
+        return np.ascontiguousarray(a, np.uint8 if bits == 8 else np.uint16)
+    h, w = a.shape
+    per = 8 // bits
+    stride = packed_stride(w, bits)
+    wide = np.zeros((h, stride * per), np.uint8)
+    wide[:, :w] = a
+    out = np.zeros((h, stride), np.uint8)
+    for s in range(per):
+        out |= wide[:, s::per] << np.uint8(8 - bits * (s + 1))
+    return out
+
+
+def unpack_indices(packed, width, bits):
+    """the inverse of pack_indices: packed rows -> (height, width) uint8 (uint16 at bits = 16)"""
+    if bits not in (1, 2, 4, 8, 16):
+        raise ValueError("bits must be 1, 2, 4, 8 or 16")
+    if bits >= 8:
+        return np.ascontiguousarray(packed, np.uint8 if bits == 8 else np.uint16).reshape(-1, int(width))
+    stride = packed_stride(width, bits)
+    a = np.ascontiguousarray(packed, np.uint8).reshape(-1, stride)
+    per = 8 // bits
+    out = np.empty((a.shape[0], stride * per), np.uint8)
+    for s in range(per):
+        out[:, s::per] = (a >> np.uint8(8 - bits * (s + 1))) & np.uint8((1 << bits) - 1)
+    return np.ascontiguousarray(out[:, :int(width)])
+
+
 def tolerance_of(delta_e):
     """a dE76 distance as the `tolerance` of the lossy delta calls: rint(4096 dE^2); ValueError when negative or beyond a uint32"""
     de = float(delta_e)
@@ -275,6 +350,7 @@ SYMBOLS = [
     "kmg_sequence_create", "kmg_sequence_destroy", "kmg_sequence_add", "kmg_sequence_add_device", "kmg_sequence_clear",
     "kmg_sequence_info", "kmg_sequence_centroids", "kmg_sequence_palette", "kmg_dev_frame_delta", "kmg_dev_frame_delta_lossy",
     "kmg_sequence_output_begin", "kmg_sequence_output_frame", "kmg_sequence_output_frame_lossy", "kmg_sequence_output_end",
+    "kmg_dev_index_usage", "kmg_index_plan", "kmg_dev_index_remap", "kmg_index_usage", "kmg_index_remap", "kmg_index_optimize",
     "kmg_default_group_options", "kmg_group_create", "kmg_group_unique_id", "kmg_group_create_rank", "kmg_group_destroy",
     "kmg_group_info", "kmg_group_processor", "kmg_group_stream", "kmg_group_palette", "kmg_group_find", "kmg_group_reduce",
     "kmg_group_reduce_batch", "kmg_group_lloyd_create", "kmg_group_lloyd_destroy", "kmg_group_lloyd_bind",
@@ -406,6 +482,13 @@ def lib():
     L.kmg_dev_frame_delta_lossy.argtypes = [vp, u8p, vp, vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.kmg_sequence_output_frame_lossy.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, vp, C.POINTER(FrameHold), C.POINTER(C.c_int)]
     L.kmg_sequence_output_end.argtypes = [vp]
+    L.kmg_dev_index_usage.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, vp, vp]
+    L.kmg_index_plan.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, vp, u8p, C.POINTER(IndexPlanInfo)]
+    L.kmg_dev_index_remap.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
+    L.kmg_index_usage.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint32, vp]
+    L.kmg_index_remap.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(C.c_uint64)]
+    L.kmg_index_optimize.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u8p, C.c_uint32, C.c_uint32, C.c_uint32, u8p,
+                                     C.POINTER(IndexPlanInfo), vp]
     L.kmg_default_group_options.argtypes = [C.POINTER(GroupOptions)]
     L.kmg_default_group_options.restype = None
     L.kmg_group_create.argtypes = [C.POINTER(GroupOptions), C.POINTER(vp)]
@@ -709,6 +792,75 @@ class ImageProcessor:
         _check(lib().kmg_dev_compare(self._h, C.c_void_p(d_src), C.c_void_p(d_out), int(n_pixels), int(format),
                                      _np_ptr(pal) if pal is not None else None, pal.shape[0] if pal is not None else 0,
                                      int(alpha_cutoff), int(what), C.c_void_p(d_stats), C.c_void_p(stream)))
+
+    # ---- index-map optimisation (include/kmeans_hip.h kmg_index_plan) --------------------------------------
+    def index_usage_device(self, d_index, n_pixels, format, k, d_usage, stream=0):
+        """kmg_dev_index_usage: ADDS the counts of n_pixels indices to the k + 2 uint64 at d_usage (device; the caller zeroes a
+        fresh record): [i] pixels with index i, [k] the transparent slot, [k + 1] indices above k.  Only enqueues."""
+        _check(lib().kmg_dev_index_usage(self._h, C.c_void_p(d_index), int(n_pixels), int(format), int(k), C.c_void_p(d_usage),
+                                         C.c_void_p(stream)))
+
+    def index_remap_device(self, d_in, in_format, width, rows, k, remap, out_bits, d_out, d_bad, stream=0):
+        """kmg_dev_index_remap: d_out = remap[d_in] at out_bits per pixel (1 / 2 / 4: packed rows); remap: host (k + 1,) uint16;
+        ADDS the bad pixels (written as 0) to the uint64 at d_bad (device).  Only enqueues."""
+        r = np.ascontiguousarray(remap, np.uint16).reshape(-1)
+        if r.shape[0] != int(k) + 1:
+            raise ValueError("remap must hold k + 1 entries")
+        _check(lib().kmg_dev_index_remap(self._h, C.c_void_p(d_in), int(in_format), int(width), int(rows), int(k), _np_ptr(r), int(out_bits),
+                                         C.c_void_p(d_out), C.c_void_p(d_bad), C.c_void_p(stream)))
+
+    @staticmethod
+    def _index_map(index):
+        a = np.ascontiguousarray(index)
+        if a.ndim != 2 or a.dtype not in (np.uint8, np.uint16):
+            raise ValueError("index map must be a (height, width) uint8 or uint16 array")
+        return a, (OutputFormat.Index8 if a.dtype == np.uint8 else OutputFormat.Index16)
+
+    def index_usage(self, index, k, usage=None):
+        """kmg_index_usage: the k + 2 counts of a (height, width) uint8 / uint16 map, ADDED to `usage` when given (frames of a
+        sequence accumulate into one record)"""
+        a, fmt = self._index_map(index)
+        use = np.zeros(int(k) + 2, np.uint64) if usage is None else usage
+        if use.dtype != np.uint64 or use.shape != (int(k) + 2,) or not use.flags.c_contiguous:
+            raise ValueError("usage must be a contiguous (k + 2,) uint64 array")
+        _check(lib().kmg_index_usage(self._h, _np_ptr(a), int(fmt), a.size, int(k), _np_ptr(use)))
+        return use
+
+    def index_remap(self, index, k, remap, bits):
+        """kmg_index_remap: (remap[index] at `bits` per pixel -- (height, stride) uint8 packed rows for 1 / 2 / 4, a (height, width)
+        uint8 / uint16 map for 8 / 16 --, the number of bad pixels, written as 0)"""
+        a, fmt = self._index_map(index)
+        h, w = a.shape
+        r = np.ascontiguousarray(remap, np.uint16).reshape(-1)
+        if r.shape[0] != int(k) + 1:
+            raise ValueError("remap must hold k + 1 entries")
+        if bits not in (1, 2, 4, 8, 16):
+            raise ValueError("bits must be 1, 2, 4, 8 or 16")
+        out = np.empty((h, w), np.uint16) if bits == 16 else np.empty((h, packed_stride(w, bits)), np.uint8)
+        bad = C.c_uint64()
+        _check(lib().kmg_index_remap(self._h, _np_ptr(a), int(fmt), w, h, int(k), _np_ptr(r), int(bits), _np_ptr(out), C.byref(bad)))
+        return out, int(bad.value)
+
+    def optimize_indexed(self, index, palette, flags=INDEX_ORDER_USAGE | INDEX_TRANSPARENT_FIRST, bits=None):
+        """kmg_index_optimize: prune and order the palette of a (height, width) index map and rewrite the map for it.  Returns
+        (palette_out (n_slots, 4) uint8 -- (0, 0, 0, 0) at info.transparent --, the map at info.bits (bits=None) or `bits` per pixel:
+        packed rows (height, stride) uint8 for 1 / 2 / 4, (height, width) uint8 / uint16 for 8 / 16, IndexPlanInfo)."""
+        a, fmt = self._index_map(index)
+        h, w = a.shape
+        pal = np.ascontiguousarray(palette, np.uint8).reshape(-1, 4)
+        k = pal.shape[0]
+        out_pal = np.empty((k + 1, 4), np.uint8)
+        out = np.empty(a.nbytes, np.uint8)
+        info = IndexPlanInfo()
+        _check(lib().kmg_index_optimize(self._h, _np_ptr(a), int(fmt), w, h, _np_ptr(pal), k, int(flags), int(bits or 0), _np_ptr(out_pal),
+                                        C.byref(info), _np_ptr(out)))
+        b = int(bits or info.bits)
+        if b == 16:
+            m = out[:h * w * 2].view(np.uint16).reshape(h, w).copy()
+        else:
+            stride = packed_stride(w, b)
+            m = out[:h * stride].reshape(h, stride).copy()
+        return out_pal[:info.n_slots].copy(), m, info
 
     def reduce_quality(self, image, max_delta_e, k_min=2, k_max=256, reduce_mode=ReduceMode.Replace, indexed=False):
         """kmg_reduce_quality: as few colours in [k_min, k_max] as keep the dE76 RMS of the palette step's working image at or below

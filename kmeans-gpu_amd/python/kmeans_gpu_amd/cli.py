@@ -17,6 +17,12 @@ per-channel MSE, PSNR, dE76 RMS and max; kmg_compare).  `reduce --max-error DE [
 few colours between A (default 2) and `-c` as keep the dE76 RMS of the palette step's working image at or below DE
 (kmg_reduce_quality, k-means only); the line then also gives the count chosen and whether the target was reached.
 
+`reduce` and `find` with `--indexed` also take `--optimize [usage|luma|keep]` (kmg_index_optimize): the palette loses the entries
+no pixel uses, is ordered by descending use (the default), ascending luma or as it was, the transparent slot of alpha mode comes
+first (tRNS is then one byte), and the PNG is written at the bit depth the entries left need: 1, 2, 4 or 8 (kmeans_gpu_amd/png8.py).
+`--report` compares before the rewrite.  `sequence --optimize` counts the use of every entry over all frames, drops the unused
+ones, orders the rest by use (the transparent slot stays last, where the APNG wants it) and rewrites every map at 8 bits.
+
 `sequence -i A.png B.png ... -c K [-m replace|dither|diffuse] [-o out.png] [--alpha-cutoff T] [--no-delta] [--lossy DE] [--report]
 [--delay-ms 100]` quantises several frames of one size with ONE palette (kmg_sequence_*) and writes a palette-mode APNG
 (kmeans_gpu_amd/apng.py): delta frames -- the rectangle of the pixels that changed, blended "over" -- unless --no-delta asks for
@@ -115,6 +121,19 @@ def save_indexed(path, palette, index, transparent=False):
         img.save(path)
 
 
+_ORDERS = {"usage": 1, "luma": 2, "keep": 0}                 # KMG_INDEX_ORDER_*
+
+
+def save_optimized(proc, path, palette, index, order):
+    """--indexed --optimize: the palette pruned and ordered, the transparent slot first, the PNG at the plan's bit depth"""
+    from . import INDEX_TRANSPARENT_FIRST, png8
+    colors, rows, info = proc.optimize_indexed(index, palette, _ORDERS[order] | INDEX_TRANSPARENT_FIRST)
+    h, w = np.asarray(index).shape
+    png8.write(path, colors, w, h, rows, info.bits, transparent_first=info.transparent == 0)
+    print(f"Optimized: {info.n_colors} of {np.asarray(palette).reshape(-1, 4).shape[0]} colours used"
+          + (", transparent slot first" if info.transparent == 0 else "") + f", {info.bits} bits per pixel")
+
+
 def reduce_file_path(k, algo, mode, output, inp):        # main.rs:127-153
     if output:
         return output
@@ -179,6 +198,16 @@ def run_sequence(args, ap):
                 line += f" held={int(info.held)} held dE76 rms={info.held_delta_e_rms:.3f}"
             lines.append(line + (" (written in full)" if is_full else ""))
         seq.end_output()
+        if args.optimize:                                    # one plan over every frame's map; the slot stays last (apng.encode)
+            from . import INDEX_KEEP_TRANSPARENT, INDEX_ORDER_USAGE, index_plan
+            k = colors.shape[0]
+            use = np.zeros(k + 2, np.uint64)
+            for index, _, _ in coded:
+                proc.index_usage(index, k, usage=use)
+            remap, pruned, info = index_plan(use, colors, INDEX_ORDER_USAGE | INDEX_KEEP_TRANSPARENT)
+            coded = [(proc.index_remap(index, k, remap, 8)[0], rect, is_full) for index, rect, is_full in coded]
+            colors = pruned[:info.n_colors]
+            print(f"Optimized: {info.n_colors} of {k} colours used")
     apng.write(out_path, colors, w, h, coded, delay_ms=args.delay_ms)
     print("Palette: " + ",".join(f"#{c[0]:02X}{c[1]:02X}{c[2]:02X}" for c in colors))
     print(f"Sequence: {len(frames)} frames of {w}x{h}, {n_full} written in full"
@@ -278,6 +307,8 @@ def main(argv=None):
     q.add_argument("--no-delta", action="store_true", help="write every frame in full instead of the rectangle of its changes")
     q.add_argument("--lossy", type=validate_lossy, default=None, metavar="DE",
                    help="lossy delta frames: a pixel whose source stays within dE76 DE of the source it was last written for keeps what it shows")
+    q.add_argument("--optimize", action="store_true",
+                   help="drop the palette entries no frame uses and order the rest by use (the transparent slot stays last)")
     q.add_argument("--report", action="store_true", help="print the changed (and, with --lossy, the held) pixels of every frame")
     q.add_argument("--delay-ms", type=validate_delay, default=100, help="display time of every frame in milliseconds (default 100)")
     for s in (p, f, r, q):
@@ -289,6 +320,9 @@ def main(argv=None):
     for s in (f, r):
         s.add_argument("--indexed", action="store_true",
                        help="write a palette-mode PNG (an index per pixel) instead of RGBA; at most 256 colours, 255 with --alpha-cutoff")
+        s.add_argument("--optimize", nargs="?", const="usage", default=None, choices=list(_ORDERS), metavar="ORDER",
+                       help="with --indexed: drop unused palette entries, order the rest (usage, the default; luma; keep), put the "
+                            "transparent slot first and write the PNG at 1, 2, 4 or 8 bits per pixel")
         s.add_argument("--report", action="store_true",
                        help="print one line with the error of the output against the input: pixels, MSE per channel, PSNR, dE76 RMS and max")
     r.add_argument("--max-error", type=validate_max_error, default=None, metavar="DE",
@@ -333,6 +367,9 @@ def main(argv=None):
     elif getattr(args, "min_colors", None) is not None:
         ap.error("--min-colors belongs to --max-error")
     indexed = getattr(args, "indexed", False)
+    optimize = getattr(args, "optimize", None)
+    if optimize is not None and not indexed:
+        ap.error("--optimize rewrites an index map: it needs --indexed")
     if indexed:
         n = args.colorcount if args.command == "reduce" else args.palette.shape[0]
         limit = 255 if args.alpha_cutoff else 256
@@ -366,20 +403,28 @@ def main(argv=None):
             print("Palette: " + ",".join(f"#{c[0]:02X}{c[1]:02X}{c[2]:02X}" for c in colors))
         elif indexed and args.command == "find":
             index = proc.find_indexed(image, args.palette, _MODES[args.mode])
-            save_indexed(out_path, args.palette, index, transparent=bool(args.alpha_cutoff))
+            if optimize is not None:
+                save_optimized(proc, out_path, args.palette, index, optimize)
+            else:
+                save_indexed(out_path, args.palette, index, transparent=bool(args.alpha_cutoff))
             if report:
                 print(report_line(proc.compare(image, index, palette=args.palette)))
         elif max_error is not None:                      # the colour count from the quality target; -c is the upper bound
             k, colors, out, _, reached = proc.reduce_quality(image, max_error, args.min_colors, args.colorcount, _MODES[args.mode],
                                                              indexed=indexed)
-            if indexed:
+            if indexed and optimize is not None:
+                save_optimized(proc, out_path, colors, out, optimize)
+            elif indexed:
                 save_indexed(out_path, colors, out, transparent=bool(args.alpha_cutoff))
             else:
                 _save(reduce_file_path(args.colorcount, args.algo, args.mode, args.output, args.input), out)
             print(report_line(proc.compare(image, out, palette=colors if indexed else None), chosen=k, reached=reached))
         elif indexed:
             colors, index = proc.reduce_indexed(args.colorcount, image, _ALGOS[args.algo], _MODES[args.mode])
-            save_indexed(out_path, colors, index, transparent=bool(args.alpha_cutoff))
+            if optimize is not None:
+                save_optimized(proc, out_path, colors, index, optimize)
+            else:
+                save_indexed(out_path, colors, index, transparent=bool(args.alpha_cutoff))
             if report:
                 print(report_line(proc.compare(image, index, palette=colors)))
         elif args.command == "find":                     # main.rs:74-98
