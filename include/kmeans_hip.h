@@ -689,6 +689,78 @@ KMG_API int kmg_sequence_output_frame_lossy(kmg_sequence *s, const uint8_t *rgba
                                             kmg_frame_hold *info, int *is_full);
 KMG_API int kmg_sequence_output_end(kmg_sequence *s);
 
+/* ======================= per-frame palettes: colour-keyed delta frames =====================
+ * One palette for all frames is what limits a 256-entry format on a clip whose content changes (a cut, a pan, a fade); GIF has
+ * local colour tables for that.  Once entry 7 of frame t is another colour than entry 7 of frame t - 1, comparing indices means
+ * nothing: the canvas has to hold what is SHOWN, and the comparison goes through the frame's palette.  No counterpart in the
+ * reference.
+ *
+ * The colour-keyed delta pass.  State per pixel: shown, an RGBA8 word -- what the viewer shows; the word 0 means nothing is shown
+ * -- and, in the lossy form, the held source of kmg_dev_frame_delta_lossy.  For the pixel (x, row0 + r) of the band:
+ *   c = its index in d_index;  p = P[c] as a 32-bit word when c < k, else 0 (an index >= k shows nothing; indices above k are
+ *   treated as k);  v = its word in d_shown.
+ * Exact rule:
+ *   p == v:   delta = k
+ *   p != v:   delta = c (k when c > k), changed += 1, the box takes the pixel in, cleared += 1 when p == 0
+ *   always:   shown = p
+ * Lossy rule, s = the source word, h = the held source, D and `tolerance` exactly as at kmg_dev_frame_delta_lossy:
+ *   hold := v != 0  &&  p != 0  &&  D(s, h) <= tolerance
+ *   hold:      delta = k; shown and held stay; when p != v: held += 1, held_sse += D(s, h)
+ *   not hold:  the exact rule; shown = p; held = s
+ * The records are kmg_frame_delta (exact) and kmg_frame_hold (lossy), unchanged: same fresh values, same combination rule (sums
+ * added, minima minned, maxima maxed), so the bands of a frame may run in any order on any streams.
+ * Two consequences:
+ *   same palette       with one palette whose entries are distinct and non-zero, and indices <= k, the exact pass writes the delta
+ *                      map and the record of kmg_dev_frame_delta (the lossy one those of kmg_dev_frame_delta_lossy); afterwards
+ *                      shown == P'[canvas] with P'[k] = 0.
+ *   duplicate entries  a pixel whose index changes between two entries with equal bytes is NOT sent (the index pass would send it).
+ * d_palette_rgba: DEVICE, k words, 4-byte aligned, read when the pass runs.  d_shown_rgba (and d_src_rgba, d_held_rgba): DEVICE,
+ * width * rows RGBA8 words, 4-byte aligned.  d_index, d_delta, formats and refusals: those of kmg_dev_frame_delta / _lossy
+ * (KMG_FORMAT_INDEX8 needs k <= 255, KMG_FORMAT_INDEX16 takes k <= KMG_MAX_K); a NULL or misaligned palette or shown pointer is
+ * refused as well.  The pass takes its vector route -- 16-byte accesses of the RGBA8 buffers, 4- / 8-byte accesses of the index
+ * buffers -- when d_shown_rgba (lossy: also d_src_rgba and d_held_rgba) is 16-byte aligned and d_index and d_delta are 4- (INDEX8)
+ * or 8-byte (INDEX16) aligned; otherwise it goes pixel by pixel, correct but not fast.  No two buffers overlap.  Both only enqueue
+ * work on `stream`.                                                                                                            */
+KMG_API int kmg_dev_frame_delta_colour(kmg_processor *p, const void *d_index, const uint8_t *d_palette_rgba, uint8_t *d_shown_rgba,
+                                       uint32_t width, uint32_t rows, uint32_t row0, int format, uint32_t k, void *d_delta,
+                                       kmg_frame_delta *d_info, void *stream);
+KMG_API int kmg_dev_frame_delta_colour_lossy(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_index,
+                                             const uint8_t *d_palette_rgba, uint8_t *d_shown_rgba, uint8_t *d_held_rgba, uint32_t width,
+                                             uint32_t rows, uint32_t row0, int format, uint32_t k, uint32_t tolerance, void *d_delta,
+                                             kmg_frame_hold *d_info, void *stream);
+
+/* Frame output with a palette per frame, on HOST buffers.
+ *   _output_begin_local   needs no added frame (W is not used).  Takes the frame buffers, a shown canvas filled with 0, the held
+ *                   source, the palette and the record.  Mode and format: the rules of _output_begin for delta frames -- index
+ *                   formats only, no meld, KMG_FORMAT_INDEX8 needs k <= 255.  flags: 0 or KMG_LOCAL_WARM.  A second begin of
+ *                   either kind ends the first; _output_end and _destroy end either kind.  _output_frame / _output_frame_lossy
+ *                   on a local output, and _output_frame_local on a shared one, are refused with KMG_ERR_INVALID_ARGUMENT; the
+ *                   output stays open.
+ *   _output_frame_local   rgba: a frame of width x height.  Its centroids C_t:
+ *                     cold   (flags of the begin 0; the first frame; the frame after one that failed)  C_t, the palette bytes in
+ *                            index order and the full map I_t are those of kmg_reduce_indexed(frame, k, KMG_ALGO_KMEANS, mode)
+ *                            byte for byte; alpha cutoff and fixed colours are read when the call starts.
+ *                     warm   (KMG_LOCAL_WARM, every later frame)  the processor's Lloyd loop on the frame's working image -- the
+ *                            one cold would use -- started from all k of C_{t-1} (kmg_lloyd_init_centroids_seeded with
+ *                            n_seeds = k: no farthest-point pick); palette bytes and I_t from the usual output pass with C_t.  A
+ *                            frame of a warm output while the processor has fixed colours: KMG_ERR_UNSUPPORTED.
+ *                   A frame that fails (for example "no pixel reaches alpha_cutoff") returns that status and leaves shown and held
+ *                   as they were; the next frame is cold.
+ *                   out_palette_rgba (k x 4 bytes) / *out_count: P_t.  Without KMG_FRAME_DELTA in `flags`: out = I_t,
+ *                   *is_full = 1, *info fresh.  With it: out = the delta map of (I_t, P_t) against shown -- the exact rule when
+ *                   `tolerance` is NULL, else the lossy rule at *tolerance -- and *is_full = 0; unless info->cleared > 0: then
+ *                   out = I_t, *is_full = 1, *info as measured.  After every full frame shown = P_t[I_t] and every pixel's held
+ *                   source is this frame; exact and lossy frames alternate freely.  The exact form fills the first 32 bytes of
+ *                   *info and leaves held = held_sse = 0.  A tolerance without KMG_FRAME_DELTA, unknown flags, a NULL pointer
+ *                   other than `tolerance`: KMG_ERR_INVALID_ARGUMENT.
+ * Replay: decode each coded frame through ITS OWN palette, compose delta maps "over" (index k keeps the pixel) and full maps as
+ * "source".  For exact frames this gives P_t[I_t]; for lossy frames it gives the shown canvas.                                  */
+#define KMG_LOCAL_WARM 1u
+KMG_API int kmg_sequence_output_begin_local(kmg_sequence *s, uint32_t k, int mode, int format, uint32_t width, uint32_t height,
+                                            uint32_t flags);
+KMG_API int kmg_sequence_output_frame_local(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, const uint32_t *tolerance, void *out,
+                                            uint8_t *out_palette_rgba, uint32_t *out_count, kmg_frame_hold *info, int *is_full);
+
 /* ======================= index-map optimisation: usage counts, palette pruning, packed maps ===
  * The last step before a PNG8 / GIF / APNG writer: which palette entries a map uses, a palette without the unused ones in the
  * order a writer wants, and the map rewritten for it at 1, 2, 4, 8 or 16 bits per pixel.  All integers.  No counterpart in the

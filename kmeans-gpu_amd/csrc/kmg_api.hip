@@ -120,6 +120,24 @@ int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, 
     return palette_of_working(p, wi, k, st, c4, fixed);
 }
 
+}  // namespace
+
+int kmg::local_frame_centroids(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff,
+                               hipStream_t st, float *c4, const float *fixed4, uint32_t n_fixed, const float *warm4)
+{
+    int rc;
+    WorkingImage wi;
+    if ((rc = working_image(p, d_rgba, w, h, alpha_cutoff, st, wi)) != KMG_OK) return rc;
+    if (!warm4) return kmg::palette_of_working(p, wi.src, wi.sw, wi.sh, k, st, c4, nullptr, fixed4, n_fixed);
+    LloydGuard g;
+    if ((rc = lloyd_create_impl(p, k, &g.s, st)) != KMG_OK) return rc;
+    if ((rc = kmg_lloyd_init_centroids_seeded(g.s, wi.src, wi.sw, wi.sh, warm4, k, st)) != KMG_OK) return rc;
+    if ((rc = kmg_lloyd_run(g.s, wi.src, (uint64_t)wi.sw * wi.sh, nullptr, nullptr, st)) != KMG_OK) return rc;
+    return kmg_lloyd_get_centroids(g.s, c4, st);
+}
+
+namespace {
+
 // the refusals of a palette step while the processor has fixed colours (include/kmeans_hip.h at kmg_processor_set_fixed_colors)
 int check_fixed(const FixedList &fixed, uint32_t k, int algo)
 {

@@ -77,6 +77,17 @@ int frame_hold_impl(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_i
                     uint32_t rows, uint32_t row0, int format, uint32_t k, uint32_t tolerance, void *d_delta, kmg_frame_hold *d_info,
                     hipStream_t st);
 
+// kmg_dev_frame_delta_colour / _colour_lossy on a hipStream_t (kmg_local.hip): the frames of an output with per-frame palettes.
+// lossy: d_src_rgba, d_held_rgba and a hold record; exact: both NULL and a delta record
+int frame_local_impl(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_index, const uint8_t *d_palette_rgba, uint8_t *d_shown_rgba,
+                     uint8_t *d_held_rgba, uint32_t width, uint32_t rows, uint32_t row0, int format, uint32_t k, bool lossy, uint32_t tolerance,
+                     void *d_delta, void *d_info, hipStream_t st);
+// The centroids of one frame of such an output (kmg_api.hip): the working image of kmg_reduce_indexed's k-means step for the frame in
+// device memory, then -- warm4 == NULL -- that step itself with the fixed colours given, or -- warm4: k x 4 -- the Lloyd loop from
+// those k centroids (a seeded initialisation with every centroid given: no pick).  Synchronises `st`.
+int local_frame_centroids(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff, hipStream_t st,
+                          float *centroids4, const float *fixed4, uint32_t n_fixed, const float *warm4);
+
 // An image between a caller's (pageable) buffer and the device, ordered on `st` (kmg_api.hip): small images asynchronously,
 // large ones as synchronous row-range copies on several streams of the processor.
 hipError_t copy_host_image(kmg_processor *p, void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t st);

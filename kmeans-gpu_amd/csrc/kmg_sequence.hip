@@ -245,6 +245,12 @@ struct kmg_sequence {
     // buffers swap instead of a copy.
     uint8_t *d_held = nullptr;
     kmg_frame_hold *d_info = nullptr;    // (an exact frame uses its first 32 bytes: a kmg_frame_delta)
+    // an output with per-frame palettes (kmg_sequence_output_begin_local): no plan; the block is frame | map | delta map | shown |
+    // held source | palette | record, and the canvas is what is SHOWN, an RGBA8 word per pixel (kmg_local.hip)
+    bool local = false, have_prev = false;
+    uint32_t local_flags = 0;
+    uint8_t *d_shown = nullptr, *d_pal = nullptr;
+    std::vector<float> prev_c4;      // C_{t-1}: where a warm frame's Lloyd loop starts
 };
 
 namespace {
@@ -262,6 +268,7 @@ void output_end(kmg_sequence *s)
     block_give(s->p, s->o_blk, s->o_cap);
     s->o_blk = nullptr;
     s->o_cap = 0;
+    s->local = s->have_prev = false;
 }
 
 // room for `extra` more pixels behind W: a new block of at least twice the size, then a device-to-device copy of what is there
@@ -548,6 +555,7 @@ extern "C" int kmg_sequence_output_frame(kmg_sequence *s, const uint8_t *rgba, u
                                          int *is_full)
 try {
     if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
+    if (s->local) return fail(KMG_ERR_INVALID_ARGUMENT, "the open output has per-frame palettes: its frames go through kmg_sequence_output_frame_local");
     if (!s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "no output is open (kmg_sequence_output_begin)");
     if (!rgba || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame: a pointer is NULL");
     if (flags & ~KMG_FRAME_DELTA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
@@ -568,6 +576,7 @@ extern "C" int kmg_sequence_output_frame_lossy(kmg_sequence *s, const uint8_t *r
                                                kmg_frame_hold *info, int *is_full)
 try {
     if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
+    if (s->local) return fail(KMG_ERR_INVALID_ARGUMENT, "the open output has per-frame palettes: its frames go through kmg_sequence_output_frame_local");
     if (!s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "no output is open (kmg_sequence_output_begin)");
     if (!rgba || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame_lossy: a pointer is NULL");
     if (flags & ~KMG_FRAME_DELTA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
@@ -588,6 +597,142 @@ extern "C" int kmg_sequence_output_end(kmg_sequence *s)
 try {
     if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
     output_end(s);
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// per-frame palettes (include/kmeans_hip.h at kmg_sequence_output_begin_local)
+// ---------------------------------------------------------------------------------------------
+extern "C" int kmg_sequence_output_begin_local(kmg_sequence *s, uint32_t k, int mode, int format, uint32_t width, uint32_t height,
+                                               uint32_t flags)
+try {
+    if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
+    output_end(s);                                                     // a second begin of either kind ends the first
+    if (width == 0 || height == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "image has zero width or height");
+    if ((uint64_t)width * height > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
+    if (flags & ~KMG_LOCAL_WARM) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
+    if (k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
+    if (k > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", k, KMG_MAX_K);
+    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_DIFFUSE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
+    if (format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "per-frame palettes need an index format (INDEX8 / INDEX16), not RGBA8");
+    if (format != KMG_FORMAT_INDEX8 && format != KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
+    if (mode == KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "meld blends two colours: it has no index output");
+    if (format == KMG_FORMAT_INDEX8 && k > 255u)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u plus the transparent slot needs INDEX16", k);
+    kmg_processor *p = s->p;
+    hipStream_t st = s->sg.st;
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t n = (size_t)width * height, es = format_bytes(format);
+    const size_t frame_b = pad256(n * 4), map_b = pad256(n * es), pal_b = pad256(((size_t)k + 1u) * 4);
+    HIP_TRY(block_take(p, 3 * frame_b + 2 * map_b + pal_b + 256, &s->o_blk, &s->o_cap));
+    s->d_frame = (uint8_t *)s->o_blk;
+    s->d_map = s->d_frame + frame_b;
+    s->d_delta = s->d_map + map_b;
+    s->d_shown = s->d_delta + map_b;
+    s->d_held = s->d_shown + frame_b;
+    s->d_pal = s->d_held + frame_b;
+    s->d_info = (kmg_frame_hold *)(s->d_pal + pal_b);
+    s->d_canvas = nullptr;
+    hipError_t e = hipMemsetAsync(s->d_shown, 0, n * 4, st);           // nothing is shown (and nothing is held: no fill)
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        output_end(s);
+        return fail(KMG_ERR_HIP, "filling the canvas failed: %s", hipGetErrorString(e));
+    }
+    s->k = k; s->mode = mode; s->format = format; s->width = width; s->height = height;
+    s->local = true; s->have_prev = false; s->local_flags = flags;
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+// HIP_TRY for a call that has copies in flight to or from its own locals: the stream is drained before the early return
+#define HIP_TRY_DRAIN(st_, expr)                                                               \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess) {                                                                \
+            (void)hipStreamSynchronize(st_);                                                   \
+            return fail(e_ == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP,       \
+                        "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+        }                                                                                      \
+    } while (0)
+
+extern "C" int kmg_sequence_output_frame_local(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, const uint32_t *tolerance, void *out,
+                                               uint8_t *out_palette_rgba, uint32_t *out_count, kmg_frame_hold *info, int *is_full)
+try {
+    int rc;
+    if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
+    if (!s->local) {
+        if (s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "the open output has one shared palette: its frames go through kmg_sequence_output_frame");
+        return fail(KMG_ERR_INVALID_ARGUMENT, "no output is open (kmg_sequence_output_begin_local)");
+    }
+    if (!rgba || !out || !out_palette_rgba || !out_count || !info || !is_full)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame_local: a pointer is NULL");
+    if (flags & ~KMG_FRAME_DELTA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
+    const bool delta = (flags & KMG_FRAME_DELTA) != 0, lossy = tolerance != nullptr;
+    if (lossy && !delta) return fail(KMG_ERR_INVALID_ARGUMENT, "a lossy frame is a delta frame: KMG_FRAME_DELTA is required");
+    kmg_processor *p = s->p;
+    hipStream_t st = s->sg.st;
+    const uint32_t k = s->k;
+    // alpha cutoff and fixed colours: as they are when this call starts
+    const uint32_t cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
+    const std::shared_ptr<const std::vector<float>> fixed = fixed_snapshot(p);
+    const uint32_t f = fixed_count(fixed);
+    const bool warm_output = (s->local_flags & KMG_LOCAL_WARM) != 0;
+    if (warm_output && f) return fail(KMG_ERR_UNSUPPORTED, "a warm start moves every centroid: it has no fixed colours (%u are set on the processor)", f);
+    if (k < f) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u is below the %u fixed colours of the processor", k, f);
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t n = (size_t)s->width * s->height, map_bytes = n * format_bytes(s->format);
+    // the frame and its centroids: nothing below touches shown or held before the palette step has succeeded
+    const bool warm = warm_output && s->have_prev;
+    s->have_prev = false;                                              // (the frame after one that failed starts cold)
+    HIP_TRY(copy_host_image(p, s->d_frame, rgba, n * 4, hipMemcpyHostToDevice, st));
+    std::vector<float> c4(4 * (size_t)k);
+    if ((rc = local_frame_centroids(p, s->d_frame, s->width, s->height, k, cutoff, st, c4.data(), f ? fixed->data() : nullptr, f,
+                                    warm ? s->prev_c4.data() : nullptr)) != KMG_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if ((rc = dev_apply(p, s->d_frame, s->width, s->height, 0, c4.data(), k, s->mode, s->d_map, st, cutoff, s->format)) != KMG_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    // P_t: the bytes the output pass writes for each centroid, to the caller and -- one small stream-ordered copy -- to the device
+    std::vector<uint8_t> pal(4 * (size_t)k);
+    for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], &pal[4 * i]);
+    HIP_TRY_DRAIN(st, hipMemcpyAsync(s->d_pal, pal.data(), pal.size(), hipMemcpyHostToDevice, st));
+    kmg_frame_hold rec{0, 0, kFresh, kFresh, 0, 0, 0, 0};
+    const size_t rec_bytes = lossy ? sizeof(kmg_frame_hold) : sizeof(kmg_frame_delta);     // (the exact record is the first 32 bytes)
+    HIP_TRY_DRAIN(st, fresh_record(s->d_info, rec_bytes, st));
+    // without KMG_FRAME_DELTA the exact pass still runs: it leaves shown = P_t[I_t] everywhere; its delta map and record are not used
+    rc = frame_local_impl(p, lossy ? s->d_frame : nullptr, s->d_map, s->d_pal, s->d_shown, lossy ? s->d_held : nullptr, s->width, s->height, 0,
+                          s->format, k, lossy, lossy ? *tolerance : 0u, s->d_delta, s->d_info, st);
+    if (rc != KMG_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (delta) HIP_TRY_DRAIN(st, hipMemcpyAsync(&rec, s->d_info, rec_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY_DRAIN(st, hipStreamSynchronize(st));
+    const bool full = !delta || rec.cleared > 0;                       // "over" cannot show a pixel that turns transparent
+    // a lossy frame that is sent in full: the viewer then shows P_t[I_t] everywhere -- the exact pass makes the canvas that
+    if (lossy && full) {
+        HIP_TRY_DRAIN(st, fresh_record(s->d_info, sizeof(kmg_frame_delta), st));
+        if ((rc = frame_local_impl(p, nullptr, s->d_map, s->d_pal, s->d_shown, nullptr, s->width, s->height, 0, s->format, k, false, 0u, s->d_delta,
+                                   s->d_info, st)) != KMG_OK) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+    }
+    // after an exact frame or a full one every pixel's held source IS this frame: the two buffers swap instead of a copy
+    if (!lossy || full) std::swap(s->d_frame, s->d_held);
+    HIP_TRY_DRAIN(st, copy_host_image(p, out, full ? s->d_map : s->d_delta, map_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY_DRAIN(st, hipStreamSynchronize(st));
+    memcpy(out_palette_rgba, pal.data(), pal.size());
+    *out_count = k;
+    *info = rec;
+    *is_full = full ? 1 : 0;
+    s->prev_c4.swap(c4);
+    s->have_prev = true;
     return KMG_OK;
 }
 KMG_ABI_CATCH

@@ -16,6 +16,7 @@
 //   processor.set_fixed_colors(colors)                     -> palette entries the k-means keeps exactly and builds around
 //   Sequence seq(processor); seq.add(frame) ...; seq.output(k, mode, w, h); seq.frame(image) / seq.frame_lossy(image, delta_e)
 //                                                          -> one palette for many frames, exact and lossy delta frames (kmg_sequence_*)
+//   seq.begin_local(k, mode, w, h, warm); seq.frame_local(image) -> a palette per frame, colour-keyed delta frames
 // `anyhow::Result` errors become kmeans_color_gpu::Error exceptions carrying the kmg_status and the
 // library's message.  Header only; link with -lkmeans_hip.
 #pragma once
@@ -385,6 +386,36 @@ public:
         f.is_full = full != 0;
         return f;
     }
+    // Per-frame palettes (kmg_sequence_output_begin_local): no frame needs to be added.  warm: the k-means of every frame after the
+    // first starts from the previous frame's centroids.  frame_local: the frame's own palette in index order and its map -- a delta
+    // map against what is shown (exact, or lossy within max_delta_e when that is >= 0), or the full map.
+    struct LocalFrame : Frame {
+        std::vector<RGBA8> palette;
+    };
+    void begin_local(uint32_t color_count, ReduceMode reduce_mode, uint32_t width, uint32_t height, bool warm = false)
+    {
+        pixels_ = 0;
+        check(kmg_sequence_output_begin_local(s_, color_count, (int)reduce_mode, KMG_FORMAT_INDEX8, width, height, warm ? KMG_LOCAL_WARM : 0u));
+        pixels_ = (size_t)width * height;
+        colors_ = color_count;
+    }
+    LocalFrame frame_local(const Image &image, bool delta = true, double max_delta_e = -1.0)
+    {
+        const bool lossy = max_delta_e >= 0.0;
+        const double t = lossy ? std::nearbyint(4096.0 * max_delta_e * max_delta_e) : 0.0;
+        if (max_delta_e != max_delta_e || t > 4294967295.0) throw Error(KMG_ERR_INVALID_ARGUMENT, "frame_local: the tolerance does not fit 32 bits");
+        LocalFrame f;
+        static_cast<Frame &>(f) = start(image);
+        f.palette.resize(colors_);
+        const uint32_t tol = (uint32_t)t;
+        uint32_t n = 0;
+        int full = 1;
+        check(kmg_sequence_output_frame_local(s_, reinterpret_cast<const uint8_t *>(image.rgba.data()), delta ? KMG_FRAME_DELTA : 0u,
+                                              lossy ? &tol : nullptr, f.map.data(), reinterpret_cast<uint8_t *>(f.palette.data()), &n, &f.info, &full));
+        f.palette.resize(n);
+        f.is_full = full != 0;
+        return f;
+    }
     void end_output() { pixels_ = 0; check(kmg_sequence_output_end(s_)); }
     kmg_sequence *handle() const { return s_; }
 
@@ -403,6 +434,7 @@ private:
     }
     kmg_sequence *s_;
     size_t pixels_ = 0;
+    uint32_t colors_ = 0;
 };
 
 }  // namespace kmeans_color_gpu

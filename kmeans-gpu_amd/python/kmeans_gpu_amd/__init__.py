@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -121,6 +121,7 @@ class ErrorStats(C.Structure):          # include/kmeans_hip.h kmg_error_stats: 
 
 
 FRAME_DELTA = 1                         # include/kmeans_hip.h KMG_FRAME_DELTA
+LOCAL_WARM = 1                          # include/kmeans_hip.h KMG_LOCAL_WARM
 
 
 class FrameDelta(C.Structure):          # include/kmeans_hip.h kmg_frame_delta: 32 bytes
@@ -350,6 +351,7 @@ SYMBOLS = [
     "kmg_sequence_create", "kmg_sequence_destroy", "kmg_sequence_add", "kmg_sequence_add_device", "kmg_sequence_clear",
     "kmg_sequence_info", "kmg_sequence_centroids", "kmg_sequence_palette", "kmg_dev_frame_delta", "kmg_dev_frame_delta_lossy",
     "kmg_sequence_output_begin", "kmg_sequence_output_frame", "kmg_sequence_output_frame_lossy", "kmg_sequence_output_end",
+    "kmg_dev_frame_delta_colour", "kmg_dev_frame_delta_colour_lossy", "kmg_sequence_output_begin_local", "kmg_sequence_output_frame_local",
     "kmg_dev_index_usage", "kmg_index_plan", "kmg_dev_index_remap", "kmg_index_usage", "kmg_index_remap", "kmg_index_optimize",
     "kmg_default_group_options", "kmg_group_create", "kmg_group_unique_id", "kmg_group_create_rank", "kmg_group_destroy",
     "kmg_group_info", "kmg_group_processor", "kmg_group_stream", "kmg_group_palette", "kmg_group_find", "kmg_group_reduce",
@@ -482,6 +484,12 @@ def lib():
     L.kmg_dev_frame_delta_lossy.argtypes = [vp, u8p, vp, vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.kmg_sequence_output_frame_lossy.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, vp, C.POINTER(FrameHold), C.POINTER(C.c_int)]
     L.kmg_sequence_output_end.argtypes = [vp]
+    L.kmg_dev_frame_delta_colour.argtypes = [vp, vp, u8p, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp]
+    L.kmg_dev_frame_delta_colour_lossy.argtypes = [vp, u8p, vp, u8p, u8p, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                                   vp, vp, vp]
+    L.kmg_sequence_output_begin_local.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.kmg_sequence_output_frame_local.argtypes = [vp, u8p, C.c_uint32, C.POINTER(C.c_uint32), vp, u8p, C.POINTER(C.c_uint32), C.POINTER(FrameHold),
+                                                  C.POINTER(C.c_int)]
     L.kmg_dev_index_usage.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, vp, vp]
     L.kmg_index_plan.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, vp, u8p, C.POINTER(IndexPlanInfo)]
     L.kmg_dev_index_remap.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
@@ -935,6 +943,24 @@ class ImageProcessor:
                                                C.c_void_p(d_held_rgba), int(width), int(rows), int(row0), int(format), int(k), int(tolerance),
                                                C.c_void_p(d_delta), C.c_void_p(d_info), C.c_void_p(stream)))
 
+    def frame_delta_colour(self, d_index, d_palette_rgba, d_shown_rgba, width, rows, row0, format, k, d_delta, d_info, stream=0):
+        """kmg_dev_frame_delta_colour: the delta pass for frames with a palette of their own -- the canvas d_shown_rgba holds the RGBA8
+        word each pixel shows (0: nothing), a pixel is sent when palette[index] differs from it.  COMBINES into the 32-byte record at
+        d_info (device; the caller writes FrameDelta.FRESH before a frame).  Only enqueues."""
+        _check(lib().kmg_dev_frame_delta_colour(self._h, C.c_void_p(d_index), C.c_void_p(d_palette_rgba), C.c_void_p(d_shown_rgba), int(width),
+                                                int(rows), int(row0), int(format), int(k), C.c_void_p(d_delta), C.c_void_p(d_info),
+                                                C.c_void_p(stream)))
+
+    def frame_delta_colour_lossy(self, d_src_rgba, d_index, d_palette_rgba, d_shown_rgba, d_held_rgba, width, rows, row0, format, k, tolerance,
+                                 d_delta, d_info, stream=0):
+        """kmg_dev_frame_delta_colour_lossy: the same with the hold rule of frame_delta_lossy -- a pixel that shows a colour, stays
+        opaque and whose source is within `tolerance` of its held source keeps what it shows.  COMBINES into the 48-byte record at
+        d_info (device; FrameHold.FRESH before a frame).  Only enqueues."""
+        _check(lib().kmg_dev_frame_delta_colour_lossy(self._h, C.c_void_p(d_src_rgba), C.c_void_p(d_index), C.c_void_p(d_palette_rgba),
+                                                      C.c_void_p(d_shown_rgba), C.c_void_p(d_held_rgba), int(width), int(rows), int(row0),
+                                                      int(format), int(k), int(tolerance), C.c_void_p(d_delta), C.c_void_p(d_info),
+                                                      C.c_void_p(stream)))
+
     def debug_block_counts(self):
         """(device blocks allocated with hipMalloc so far, blocks handed out again)"""
         out = (C.c_uint64 * 2)()
@@ -1040,7 +1066,7 @@ class Sequence:
         order.  Index k of the maps is the transparent slot."""
         pal = np.empty((max(int(k), 1), 4), np.uint8)
         cnt = C.c_uint32()
-        self._out = None
+        self._out = self._local = None
         _check(lib().kmg_sequence_output_begin(self._h, int(k), int(mode), int(format), int(width), int(height), _np_ptr(pal), C.byref(cnt)))
         self._out = (int(k), int(format), int(width), int(height))
         return pal[:cnt.value].copy()
@@ -1073,8 +1099,38 @@ class Sequence:
                                                C.byref(info), C.byref(full)))
         return out, info, bool(full.value)
 
+    def output_local(self, k, mode=ReduceMode.Replace, format=OutputFormat.Index8, width=0, height=0, warm=False):
+        """kmg_sequence_output_begin_local: opens a frame output in which every frame gets a palette of its own (no frame needs to
+        have been added).  warm: the Lloyd loop of every frame after the first starts from the previous frame's centroids."""
+        self._out = self._local = None
+        _check(lib().kmg_sequence_output_begin_local(self._h, int(k), int(mode), int(format), int(width), int(height), LOCAL_WARM if warm else 0))
+        self._local = (int(k), int(format), int(width), int(height))
+
+    def frame_local(self, image, delta=True, tolerance=None):
+        """kmg_sequence_output_frame_local: (map, palette (k, 4) in index order, FrameHold, is_full).  delta=True: the delta map of
+        the frame's own map and palette against what is shown (index k = unchanged) -- exact, or with `tolerance` the lossy rule of
+        Sequence.frame -- or, is_full, the full map when a shown pixel turns transparent; delta=False: the full map.  An exact frame
+        leaves held = held_sse = 0 in the record."""
+        if getattr(self, "_local", None) is None:
+            raise KmgError(-1, "no output with per-frame palettes is open (Sequence.output_local)")
+        k, fmt, w, h = self._local
+        img = _image(image)
+        if img.shape[:2] != (h, w):
+            raise KmgError(-1, f"the frame is {img.shape[1]} x {img.shape[0]}, the output was opened for {w} x {h}")
+        tol = None
+        if tolerance is not None:
+            if int(tolerance) < 0 or int(tolerance) > 0xFFFFFFFF:
+                raise KmgError(-1, f"tolerance {tolerance!r} is not a uint32")
+            tol = C.byref(C.c_uint32(int(tolerance)))
+        out = np.empty((h, w), np.uint8 if fmt == OutputFormat.Index8 else np.uint16)
+        pal, cnt = np.empty((k, 4), np.uint8), C.c_uint32()
+        hold, full = FrameHold(*FrameHold.FRESH), C.c_int(1)
+        _check(lib().kmg_sequence_output_frame_local(self._h, _np_ptr(img), FRAME_DELTA if delta else 0, tol, out.ctypes.data_as(C.c_void_p),
+                                                     _np_ptr(pal), C.byref(cnt), C.byref(hold), C.byref(full)))
+        return out, pal[:cnt.value].copy(), hold, bool(full.value)
+
     def end_output(self):
-        self._out = None
+        self._out = self._local = None
         _check(lib().kmg_sequence_output_end(self._h))
 
 

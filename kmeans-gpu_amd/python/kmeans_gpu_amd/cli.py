@@ -29,7 +29,11 @@ ones, orders the rest by use (the transparent slot stays last, where the APNG wa
 full frames.  K <= 255: the transparent slot takes the last palette entry.  `--lossy DE` (a dE76 distance >= 0) makes the delta
 frames lossy (kmg_sequence_output_frame_lossy with tolerance = rint(4096 DE^2)): a pixel whose source stays within DE of the source it
 was last written for keeps what it shows, so noise and dither flicker no longer fill the delta frames; not with --no-delta.
-`--report` prints the changed (and held) pixels of every frame.
+`--report` prints the changed (and held) pixels of every frame.  `--local` gives every frame a palette of its own
+(Sequence.frame_local) and writes a GIF with local colour tables (kmeans_gpu_amd/gif.py) instead; `--warm` starts each frame's k-means
+from the previous frame's centroids.  It composes with --lossy, --report, --no-delta and --fixed (--fixed not with --warm), not with
+--optimize; with --alpha-cutoff every frame is written in full with disposal 2 (a full frame holds nothing: --lossy then has no
+effect).
 
 `palette`, `reduce` and `sequence` also take `--fixed "#RRGGBB,..."|palette.png` (the palette syntax of `find`): colours the k-means
 palette keeps exactly, as its first entries in index order (the PLTE of `--indexed` and of `sequence`), while the other entries
@@ -68,6 +72,13 @@ def validate_filename(s):                                # args.rs:173-179
     if len(s) > 4 and (s.endswith(".png") or s.endswith(".jpg")):
         return s
     raise argparse.ArgumentTypeError("Only support png or jpg files.")
+
+
+def validate_sequence_output(s):
+    """`sequence -o`: what validate_filename takes, and a .gif for --local (which of them fits is checked once --local is known)"""
+    if len(s) > 4 and s.endswith(".gif"):
+        return s
+    return validate_filename(s)
 
 
 def parse_colors(s):                                     # args.rs:218-231
@@ -156,11 +167,11 @@ def find_file_path(mode, output, inp):                   # main.rs:184-219
     return os.path.join(os.path.dirname(inp), f"{stem}-find-{mode}-{millis}{ext}")
 
 
-def sequence_file_path(k, mode, output, inp):
+def sequence_file_path(k, mode, output, inp, ext=".png"):
     if output:
         return output
     stem = os.path.splitext(os.path.basename(inp))[0]
-    return os.path.join(os.path.dirname(inp), f"{stem}-sequence-c{k}-{mode}.png")
+    return os.path.join(os.path.dirname(inp), f"{stem}-sequence-c{k}-{mode}{ext}")
 
 
 def validate_delay(s):
@@ -173,6 +184,38 @@ def validate_delay(s):
     return v
 
 
+def run_sequence_local(args, frames, w, h, out_path):
+    """`sequence --local`: every input gets a palette of its own (Sequence.frame_local); a GIF with local colour tables"""
+    from . import OutputFormat, gif
+    delay = (args.delay_ms + 5) // 10
+    coded, n_full, n_changed, n_held, lines = [], 0, 0, 0, []
+    # alpha mode: GIF cannot clear the whole canvas from a small rectangle, so every frame is written in full, disposal 2 -- and a
+    # frame that is not a delta frame holds nothing: --lossy then has no effect
+    delta = not (args.no_delta or args.alpha_cutoff)
+    lossy = args.lossy if delta else None
+    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed) as proc, proc.sequence() as seq:
+        seq.output_local(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h, warm=args.warm)
+        for i, f in enumerate(frames):
+            index, colors, info, is_full = seq.frame_local(f, delta=delta, tolerance=lossy)
+            rect = None if is_full else (info.rect or (0, 0, 1, 1))           # (nothing changed: one transparent pixel)
+            coded.append({"indices": index, "palette": colors, "rect": rect, "delay": delay, "disposal": 2 if args.alpha_cutoff else 1})
+            n_full += 1 if is_full else 0
+            n_changed += int(info.changed)
+            line = f"Frame {i}: changed={int(info.changed)}"
+            if lossy is not None:
+                n_held += int(info.held)
+                line += f" held={int(info.held)} held dE76 rms={info.held_delta_e_rms:.3f}"
+            lines.append(line + (" (written in full)" if is_full else ""))
+        seq.end_output()
+    gif.write(out_path, w, h, coded)
+    print(f"Sequence: {len(frames)} frames of {w}x{h} with a palette each, {n_full} written in full"
+          + (f", {n_changed} changed pixels in the delta frames" if delta else "")
+          + ("" if lossy is None else f", {n_held} held") + f": {out_path}")
+    if args.report:
+        print("\n".join(lines))
+    return 0
+
+
 def run_sequence(args, ap):
     """the `sequence` sub-command: one palette over all inputs, then every input as a frame of a palette-mode APNG"""
     from . import OutputFormat, apng
@@ -181,7 +224,9 @@ def run_sequence(args, ap):
     for path, f in zip(args.input, frames):
         if f.shape[:2] != (h, w):
             ap.error(f"every input of `sequence` must have one size: {path} is {f.shape[1]}x{f.shape[0]}, {args.input[0]} is {w}x{h}")
-    out_path = sequence_file_path(args.colorcount, args.mode, args.output, args.input[0])
+    out_path = sequence_file_path(args.colorcount, args.mode, args.output, args.input[0], ".gif" if args.local else ".png")
+    if args.local:
+        return run_sequence_local(args, frames, w, h, out_path)
     with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed) as proc, proc.sequence() as seq:
         for f in frames:
             seq.add(f)
@@ -302,7 +347,7 @@ def main(argv=None):
     q = sub.add_parser("sequence", help="Reduce several frames of one size with one shared palette; writes a palette-mode APNG")
     q.add_argument("-c", "--colorcount", type=validate_k, required=True)
     q.add_argument("-i", "--input", type=validate_filename, nargs="+", required=True)
-    q.add_argument("-o", "--output", type=validate_filename)
+    q.add_argument("-o", "--output", type=validate_sequence_output)
     q.add_argument("-m", "--mode", choices=["replace", "dither", "diffuse"], default="replace")
     q.add_argument("--no-delta", action="store_true", help="write every frame in full instead of the rectangle of its changes")
     q.add_argument("--lossy", type=validate_lossy, default=None, metavar="DE",
@@ -310,6 +355,10 @@ def main(argv=None):
     q.add_argument("--optimize", action="store_true",
                    help="drop the palette entries no frame uses and order the rest by use (the transparent slot stays last)")
     q.add_argument("--report", action="store_true", help="print the changed (and, with --lossy, the held) pixels of every frame")
+    q.add_argument("--local", action="store_true",
+                   help="a palette per frame instead of one for all: writes a GIF with local colour tables (not with --optimize)")
+    q.add_argument("--warm", action="store_true",
+                   help="with --local: every frame's k-means starts from the previous frame's centroids (not with --fixed)")
     q.add_argument("--delay-ms", type=validate_delay, default=100, help="display time of every frame in milliseconds (default 100)")
     for s in (p, f, r, q):
         s.add_argument("--alpha-cutoff", type=validate_alpha_cutoff, default=0,
@@ -345,8 +394,18 @@ def main(argv=None):
             ap.error("--lossy makes the delta frames lossy: it cannot be combined with --no-delta")
         if args.colorcount > 255:
             ap.error(f"`sequence` writes a palette APNG of at most 255 colours plus the transparent slot; {args.colorcount} requested")
-        out_path = sequence_file_path(args.colorcount, args.mode, args.output, args.input[0])
-        if not out_path.endswith(".png"):
+        if args.warm and not args.local:
+            ap.error("--warm starts a frame's palette from the previous frame's: it needs --local")
+        if args.local and args.optimize:
+            ap.error("--local writes every frame's own palette: it cannot be combined with --optimize")
+        if args.warm and fixed is not None:
+            ap.error("--warm moves every centroid: it cannot be combined with --fixed")
+        out_path = sequence_file_path(args.colorcount, args.mode, args.output, args.input[0], ".gif" if args.local else ".png")
+        if args.local and not out_path.endswith(".gif"):
+            ap.error("`sequence --local` writes a GIF file")
+        if not args.local and out_path.endswith(".gif"):
+            ap.error("argument -o/--output: Only support png or jpg files.")
+        if not args.local and not out_path.endswith(".png"):
             ap.error("`sequence` writes a PNG file")
         return run_sequence(args, ap)
     if args.devices and args.alpha_cutoff:

@@ -89,6 +89,8 @@ pub struct kmg_sequence {
 
 /// `kmg_sequence_output_frame*` flags.
 pub const KMG_FRAME_DELTA: u32 = 1;
+/// `kmg_sequence_output_begin_local` flags.
+pub const KMG_LOCAL_WARM: u32 = 1;
 
 /// `kmg_frame_delta` (include/kmeans_hip.h): 32 bytes; the fresh record is {0, 0, u32::MAX, u32::MAX, 0, 0}.
 #[repr(C)]
@@ -250,6 +252,59 @@ extern "C" {
         is_full: *mut c_int,
     ) -> c_int;
     pub fn kmg_sequence_output_end(s: *mut kmg_sequence) -> c_int;
+    // per-frame palettes: the colour-keyed delta passes on device buffers (the canvas holds RGBA8 words, 0 = nothing shown), and a
+    // frame output in which every frame gets its own palette (`tolerance` NULL: an exact frame; `flags` of the begin: KMG_LOCAL_WARM)
+    pub fn kmg_dev_frame_delta_colour(
+        p: *mut kmg_processor,
+        d_index: *const (),
+        d_palette_rgba: *const u8,
+        d_shown_rgba: *mut u8,
+        width: u32,
+        rows: u32,
+        row0: u32,
+        format: c_int,
+        k: u32,
+        d_delta: *mut (),
+        d_info: *mut kmg_frame_delta,
+        stream: *mut (),
+    ) -> c_int;
+    pub fn kmg_dev_frame_delta_colour_lossy(
+        p: *mut kmg_processor,
+        d_src_rgba: *const u8,
+        d_index: *const (),
+        d_palette_rgba: *const u8,
+        d_shown_rgba: *mut u8,
+        d_held_rgba: *mut u8,
+        width: u32,
+        rows: u32,
+        row0: u32,
+        format: c_int,
+        k: u32,
+        tolerance: u32,
+        d_delta: *mut (),
+        d_info: *mut kmg_frame_hold,
+        stream: *mut (),
+    ) -> c_int;
+    pub fn kmg_sequence_output_begin_local(
+        s: *mut kmg_sequence,
+        k: u32,
+        mode: c_int,
+        format: c_int,
+        width: u32,
+        height: u32,
+        flags: u32,
+    ) -> c_int;
+    pub fn kmg_sequence_output_frame_local(
+        s: *mut kmg_sequence,
+        rgba: *const u8,
+        flags: u32,
+        tolerance: *const u32,
+        out: *mut (),
+        out_palette_rgba: *mut u8,
+        out_count: *mut u32,
+        info: *mut kmg_frame_hold,
+        is_full: *mut c_int,
+    ) -> c_int;
     // ImageProcessor::new over a device list (the reference is single-device: lib.rs:38-65) and the same three calls, the image
     // tiled in row bands over the devices, the k x 4 sums of a sharded Lloyd loop all-reduced by RCCL inside the library
     pub fn kmg_default_group_options(opt: *mut kmg_group_options);
