@@ -737,15 +737,17 @@ KMG_API int kmg_dev_frame_delta_colour_lossy(kmg_processor *p, const uint8_t *d_
  *                   on a local output, and _output_frame_local on a shared one, are refused with KMG_ERR_INVALID_ARGUMENT; the
  *                   output stays open.
  *   _output_frame_local   rgba: a frame of width x height.  Its centroids C_t:
- *                     cold   (flags of the begin 0; the first frame; the frame after one that failed)  C_t, the palette bytes in
- *                            index order and the full map I_t are those of kmg_reduce_indexed(frame, k, KMG_ALGO_KMEANS, mode)
+ *                     cold   (flags of the begin 0; the first frame; the frame after one whose palette step failed)  C_t, the palette
+ *                            bytes in index order and the full map I_t are those of kmg_reduce_indexed(frame, k, KMG_ALGO_KMEANS, mode)
  *                            byte for byte; alpha cutoff and fixed colours are read when the call starts.
  *                     warm   (KMG_LOCAL_WARM, every later frame)  the processor's Lloyd loop on the frame's working image -- the
  *                            one cold would use -- started from all k of C_{t-1} (kmg_lloyd_init_centroids_seeded with
  *                            n_seeds = k: no farthest-point pick); palette bytes and I_t from the usual output pass with C_t.  A
  *                            frame of a warm output while the processor has fixed colours: KMG_ERR_UNSUPPORTED.
- *                   A frame that fails (for example "no pixel reaches alpha_cutoff") returns that status and leaves shown and held
- *                   as they were; the next frame is cold.
+ *                   A call refused before any work is enqueued changes nothing, not even whether the next frame is warm.  Such
+ *                   calls are: bad arguments, fixed colours on a warm output, k below the fixed colours.  A frame that fails in
+ *                   its palette step (for example "no pixel reaches alpha_cutoff") returns that status, leaves shown and held as
+ *                   they were and makes the next frame cold.
  *                   out_palette_rgba (k x 4 bytes) / *out_count: P_t.  Without KMG_FRAME_DELTA in `flags`: out = I_t,
  *                   *is_full = 1, *info fresh.  With it: out = the delta map of (I_t, P_t) against shown -- the exact rule when
  *                   `tolerance` is NULL, else the lossy rule at *tolerance -- and *is_full = 0; unless info->cleared > 0: then

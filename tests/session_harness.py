@@ -12,6 +12,15 @@ every caller-owned buffer pair; the running combination of the caller's error re
 uses one processor, two Lloyd objects, two Sequence objects and two caller-owned canvas pairs, closed and re-created in each
 other's blocks.
 
+Surface 2 (generate(..., surface=2), seeds of its own; the lists of surface 1 are pinned by hash) adds, on the same Sequence
+objects, switches and blocks: outputs with per-frame palettes (local_ref: cold frames as reduce_indexed, warm frames from the last
+frame's centroids on the working image of the cutoff read at the call, shown and held source carried in the model, every coded frame
+since the begin replayed after every frame; a call refused before any work is enqueued leaves a warm output warm, a frame that fails
+in its palette step makes the next one cold); colour-keyed canvases of the caller's at element offsets that pick the vector or the
+per-pixel route, a new palette with repeated entries and a zero word per frame; the index-map optimisation (index_ref): two usage
+records and the bad-pixel count, which COMBINE across bands, images and the frames of a sequence, two plan slots, remaps at every
+width, kmg_index_optimize between the other calls.
+
   generate(seed, seq)  -> list of plain tuples (deterministic; a dry Model keeps every op legal or a listed refusal)
   Runner(env).run(ops) -> executes them on a backend, checks everything the op could have touched, raises Mismatch
   replay(env, seed, seq, ops) -> the same for a list printed by a failing run
@@ -24,7 +33,13 @@ What the generator never emits, because include/kmeans_hip.h leaves it open or b
   - kmg_dev_compare with an INDEX8 map of k = 256 under a cutoff argument, k = 0, `what` = 0;
   - a frame of another size than the open output's; bands of an apply plan out of order in KMG_MODE_DIFFUSE;
   - the octree (other than its refusal under fixed colours), meld with an index format (other than its refusal), the group layer;
-  - delta bands that overlap or leave rows out: the bands of a frame tile it exactly once.
+  - delta bands that overlap or leave rows out: the bands of a frame tile it exactly once;
+  - (surface 2) a local frame from the 300 x 200 or the 1024 x 1024 image; an RGBA8 or meld local output, INDEX8 with k = 256 (other
+    than their refusals); a usage record combined across maps of different k, or read before it was zeroed; a plan from a record
+    with indices above k or without a count (other than the refusals); a remap in place at another width than the map's own, a
+    remap whose buffers overlap otherwise; kmg_index_optimize with bits below the plan's (other than the refusal) or above the map's
+    width; the colour-keyed passes on buffers that overlap; a palette step whose working image is empty other than the frame of a
+    local output at the size of the image without a kept pixel.
 The 1024 x 1024 image enters host calls and kmg_dev_compare only, and only under the forced colour-table strategy.  The images
 are this harness's own (make_images here): frames of one size in families, alpha bytes that fill every cutoff class, a frame above
 the shrink limit -- lifecycle_harness.make_images has none of these.  Every sequence mixes random ops with short directed passages
@@ -39,6 +54,8 @@ import diffuse_ref
 import error_ref
 import fixed_ref
 import hold_ref
+import index_ref
+import local_ref
 import sequence_ref
 import lifecycle_harness as LH
 from lifecycle_harness import Mismatch, GUARD, PATTERN, MAX_ITERATIONS, CHECK_PERIOD, gamut_centroids, make_centroids, sorted_palette
@@ -52,8 +69,17 @@ IMAGE_KINDS = ("odd", "odd_b", "sprite", "sprite_noisy", "sprite_shift", "few", 
 ODD, SPRITE, FEW, FLAT, CLEAR, BIG, MEGA, ROW, COL = 0, 2, 5, 6, 7, 8, 9, 10, 12
 FAMILIES = ((0, 1), (2, 3, 4), (10, 11), (12, 13))   # images of one size: the frames of one output
 ERR_INVALID = -1
-REFUSALS = ("k_below_fixed_palette", "k_below_fixed_reduce", "k_below_fixed_sequence", "octree_fixed", "frame_no_output", "delta_on_rgba8",
-            "lossy_on_rgba8", "lossy_without_delta", "index8_full", "meld_indexed", "empty_sequence")
+REFUSALS_1 = ("k_below_fixed_palette", "k_below_fixed_reduce", "k_below_fixed_sequence", "octree_fixed", "frame_no_output", "delta_on_rgba8",
+              "lossy_on_rgba8", "lossy_without_delta", "index8_full", "meld_indexed", "empty_sequence")
+# surface 2: per-frame palettes and the index-map optimisation
+REFUSALS_2 = ("shared_frame_on_local", "local_frame_on_shared", "local_frame_no_output", "warm_with_fixed", "local_tolerance_without_delta",
+              "local_meld", "local_index8_k256", "plan_indices_above_k", "plan_empty_record", "optimize_bits_too_narrow", "remap_bad_bits")
+REFUSALS = REFUSALS_1 + REFUSALS_2
+ERR_UNSUPPORTED = -5
+LOCAL_FAMILIES = FAMILIES + ((7,),)                  # a local output needs no added frame: also at the size of the frame without a kept pixel
+BITS = (1, 2, 4, 8, 16)
+CPAIR_OFFSETS = (0, 4, 1)                            # elements into the allocations: the vector route twice, the per-pixel route
+FAILED_KINDS = ("fixed_on_warm", "k_below_fixed", "empty")
 TOLERANCES = (0, 40, 4096, 400000)                   # 1/4096 dE76^2: none, under the noise of the still frames, 1 dE, 10 dE
 # the fixed lists of set_fixed_colors: none; one colour; three with a duplicate pair; eight with alpha 0, alpha < 255 and a duplicate
 FIXED = (None,
@@ -61,6 +87,9 @@ FIXED = (None,
          ((10, 10, 10, 255), (250, 250, 250, 255), (10, 10, 10, 255)),
          ((0, 0, 0, 255), (255, 255, 255, 0), (255, 0, 0, 255), (0, 255, 0, 128), (0, 0, 255, 255), (255, 0, 0, 255), (128, 128, 128, 7),
           (255, 255, 0, 255)))
+
+
+SURFACE_2_OPS = 120
 
 
 def k_class(k):
@@ -293,6 +322,11 @@ class Ref:
     def find_centroids(self, pal):
         return fixed_ref.pins_lab(O, pal)
 
+    def warm(self, i, t, prev):
+        """C_t of a warm frame: the Lloyd loop on the working image of image i under cutoff t, from all k of `prev`"""
+        return self._memo(("warm", i, t, prev.tobytes()),
+                          lambda: local_ref.warm_centroids(O, self.kept(i, t)[0], prev, MAX_ITERATIONS, CHECK_PERIOD)[0])
+
     def delta(self, index, canvas, k):
         return sequence_ref.delta(index, canvas, k)
 
@@ -352,6 +386,10 @@ class Model:
         self.seq = [None, None]
         self.pairs = [None, None]     # dict(fam, fmt, k, seed, mode, canvas, held, last)
         self.rec = error_ref.ZERO
+        self.cpairs = [None, None]    # dict(fam, fmt, k, offs, pseed, shown, held)
+        self.urec = [None, None]      # dict(k, counts, palette): the caller's usage records
+        self.tables = [None, None]    # dict(k, remap, palette, info): the plans kept
+        self.bad = 0                  # the running bad-pixel count of kmg_dev_index_remap
 
     def n_kept(self, i, t):
         """kept pixels of image i (before the shrink: the large images keep an opaque disc whatever the shrink does to its edge)"""
@@ -371,9 +409,13 @@ def lloyd_step(s, sums):
 
 
 # ---- the generator --------------------------------------------------------------------------------------------------
-def generate(seed, seq, n_ops=150):
-    """one sequence: a list of plain tuples"""
-    rng = np.random.default_rng([seed, seq, 3])
+def generate(seed, seq, n_ops=None, surface=1):
+    """one sequence: a list of plain tuples.  surface 1: the calls up to the lossy delta frames, 150 ops; surface 2: those plus
+    per-frame palettes, colour-keyed canvases and the index-map optimisation (SURFACE_2_OPS ops).  A surface-1 list never changes:
+    tests/test_session_model.py pins its hash"""
+    n_ops = (150 if surface == 1 else SURFACE_2_OPS) if n_ops is None else n_ops
+    refusals = REFUSALS_1 if surface == 1 else REFUSALS
+    rng = np.random.default_rng([seed, seq, 3] if surface == 1 else [seed, seq, 3, surface])
     images = make_images(seed, seq)
     m = Model(images, numeric=False)
     ops = []
@@ -607,7 +649,7 @@ def generate(seed, seq, n_ops=150):
             if k:
                 emit(("s_centroids" if rng.random() < 0.5 else "s_palette", S, k))
             return
-        if q.out is None or c < (0.6 if q.out["last"] else 0.5):
+        if q.out is None or q.out.get("local") or c < (0.6 if q.out["last"] else 0.5):
             mode = rint(0, 4)
             fmt = pick([1, 1, 2]) if mode != 2 else 0
             if mode != 2 and rng.random() < 0.12:
@@ -643,7 +685,9 @@ def generate(seed, seq, n_ops=150):
                 emit(("s_frame", S, pick(list(fam)), 1 if tol is not None or rng.random() < 0.8 else 0, tol))
 
     def refusal(what=None):
-        what = pick(list(REFUSALS)) if what is None else what
+        what = pick(list(refusals)) if what is None else what
+        if what in REFUSALS_2:
+            return refusal_2(what)
         f = n_fixed_of(m.fid)
         if what.startswith("k_below_fixed") or what == "octree_fixed":
             if f < 2:
@@ -816,10 +860,343 @@ def generate(seed, seq, n_ops=150):
             emit(("s_palette" if rng.random() < 0.5 else "s_centroids", S, min(k, 40)))
 
     def motif_refusals():
-        for j in rng.permutation(len(REFUSALS))[:3]:
-            refusal(REFUSALS[int(j)])
+        for j in rng.permutation(len(REFUSALS_1))[:3]:
+            refusal(REFUSALS_1[int(j)])
+        if surface == 2:
+            for j in rng.permutation(len(REFUSALS_2))[:4]:
+                refusal(REFUSALS_2[int(j)])
+
+
+    # ---- surface 2: per-frame palettes, colour-keyed canvases, index-map optimisation -------------------------------------
+    def fam_pixels(fam):
+        a = images[LOCAL_FAMILIES[fam][0]][1]
+        return a.shape[0] * a.shape[1]
+
+    def local_k(fam, fmt):
+        f = n_fixed_of(m.fid)
+        hi = min(cap_k(fam_pixels(fam)), 255 if fmt == 1 else 512)
+        return None if hi < max(f, 1) else pick_k(p=(0.15, 0.42, 0.25, 0.1, 0.08), lo=max(f, 1), hi=hi)
+
+    def need_seq(S):
+        if m.seq[S] is None:
+            emit(("s_new", S))
+
+    def open_local(S, fam=None, k=None, fmt=None, warm=None, mode=None):
+        need_seq(S)
+        fam = rint(0, len(FAMILIES)) if fam is None else fam
+        warm = int(rng.random() < 0.5) if warm is None else warm
+        if warm and m.fid:
+            emit(("fixed", 0))
+        fmt = pick([1, 1, 2]) if fmt is None else fmt
+        k = local_k(fam, fmt) if k is None else k
+        if k is None or k < n_fixed_of(m.fid) or (m.fid and k > cap_k(fam_pixels(fam))):
+            emit(("fixed", 0))
+            k = rint(2, 24) if k is None else k
+        emit(("s_output_local", S, k, pick([0, 1, 3]) if mode is None else mode, fmt, fam, warm))
+
+    def frame_local(S, i, delta=1, tol=None):
+        o = m.seq[S].out
+        if m.fid and not o["warm"] and o["k"] >= n_fixed_of(m.fid) and o["k"] > cap_k(fam_pixels(o["fam"])):
+            emit(("fixed", 0))                                # (the seeded initialisation of the reference is a Python loop)
+        emit(("s_frame_local", S, i, delta, tol))
+
+    def local_ops():
+        S = rint(0, 2)
+        q = m.seq[S]
+        if q is None or q.out is None or not q.out.get("local") or rng.random() < 0.2:
+            open_local(S)
+        o = m.seq[S].out
+        fam = LOCAL_FAMILIES[o["fam"]]
+        for _ in range(rint(1, 4)):
+            tol = pick([None, None] + list(TOLERANCES))
+            frame_local(S, pick(list(fam)), 1 if tol is not None or rng.random() < 0.8 else 0, tol)
+        if rng.random() < 0.25:
+            s_index_ops(S)
+
+    def cpair_ops(P=None, n=None):
+        P = rint(0, 2) if P is None else P
+        if m.cpairs[P] is None or rng.random() < 0.2:
+            fmt = pick([1, 2])
+            emit(("cpair_open", P, rint(0, len(FAMILIES)), fmt, pick_k(hi=255) if fmt == 1 else pick_k(p=(0.15, 0.42, 0.25, 0.1, 0.08), hi=400),
+                  pick(list(CPAIR_OFFSETS))))
+        pr = m.cpairs[P]
+        for _ in range(rint(2, 5) if n is None else n):
+            pseed = pr["pseed"] if pr["pseed"] is not None and rng.random() < 0.45 else rint(0, 1 << 30)
+            emit(("cpair_frame", P, pick(list(FAMILIES[pr["fam"]])), pseed, pick([None, None] + list(TOLERANCES)), rint(1, 4), rint(0, 1 << 30), st()))
+
+    def small_image():
+        return pick([ODD, 1, SPRITE, 3, 4, FEW, FLAT, ROW, COL])
+
+    def usage_op(i=None, rec=None, fresh=None, fmt=None, k=None, nb=None):
+        i = small_image() if i is None else i
+        rec = rint(0, 2) if rec is None else rec
+        u = m.urec[rec]
+        fresh = int(u is None or rng.random() < 0.5) if fresh is None else fresh
+        fmt = pick([1, 2]) if fmt is None else fmt
+        if not fresh:
+            k = u["k"]
+        elif k is None:
+            k = pick_k(hi=256 - (1 if m.t else 0)) if fmt == 1 else pick_k(p=(0.15, 0.42, 0.25, 0.1, 0.08), hi=512)
+        if fmt == 1 and k + (1 if m.t else 0) > 256:
+            fmt = 2
+        emit(("usage_device", i, pick([0, 1, 3]), fmt, k, rint(0, 1 << 30), rec, rint(1, 4) if nb is None else nb, rint(0, 1 << 30), st(), fresh))
+
+    def plan_op(rec=None, slot=None, flags=None):
+        rec = pick([r for r in range(2) if m.urec[r] is not None]) if rec is None else rec
+        flags = pick([0, 1, 2]) | (4 if rng.random() < 0.4 else 0) | (8 if rng.random() < 0.4 else 0) | (16 if rng.random() < 0.4 else 0) \
+            if flags is None else flags
+        emit(("plan", rec, rint(0, 2) if slot is None else slot, flags))
+
+    def remap_op(i=None, table=None, bits=None, bad_fresh=None):
+        i = small_image() if i is None else i
+        bits = pick(list(BITS)) if bits is None else bits
+        slots = [t for t in range(2) if m.tables[t] is not None]
+        if table is None:
+            table = pick(slots) if slots and rng.random() < 0.5 else ("rand", rint(0, 1 << 30))
+        fmt = pick([1, 2])
+        if isinstance(table, int):
+            k = m.tables[table]["k"]
+        else:
+            k = pick_k(hi=256 - (1 if m.t else 0)) if fmt == 1 else pick_k(p=(0.15, 0.42, 0.25, 0.1, 0.08), hi=512)
+        if fmt == 1 and k + (1 if m.t else 0) > 256:
+            fmt = 2
+        in_place = int(bits == 8 * fmt and rng.random() < 0.6)
+        emit(("remap_device", i, pick([0, 1, 3]), fmt, k, rint(0, 1 << 30), table, bits, in_place,
+              int(rng.random() < 0.4) if bad_fresh is None else bad_fresh, st()))
+
+    def optimize_op(i=None, flags=None):
+        for _ in range(20):
+            i = pick([ODD, SPRITE, 4, FEW, FLAT, ROW, COL]) if i is None else i
+            if m.n_kept(i, m.t) > 0:
+                break
+            i = None
+        if i is None:
+            i = FLAT
+        k = host_k(i)
+        if not k:
+            return
+        flags = pick([0, 1, 2]) | (4 if rng.random() < 0.3 else 0) | (8 if rng.random() < 0.4 else 0) | (16 if rng.random() < 0.4 else 0) \
+            if flags is None else flags
+        emit(("optimize", i, k, pick([0, 1, 3]), flags, pick([0, 8 * host_format(k, m.t)])))
+
+    def s_index_ops(S):
+        """the host calls on a map a frame of S returned"""
+        o = m.seq[S].out
+        if o is None or not o["coded"]:
+            return
+        rec = rint(0, 2)
+        u = m.urec[rec]
+        emit(("s_usage", S, rec, int(u is None or u["k"] != o["k"] or rng.random() < 0.4), rint(0, len(o["coded"]))))
+        if rng.random() < 0.7:
+            slot = rint(0, 2)
+            emit(("plan", rec, slot, pick([0, 1, 2]) | (8 if rng.random() < 0.5 else 0) | (16 if rng.random() < 0.3 else 0)))
+            emit(("s_remap", S, slot, pick([8, 16] if o["k"] > 15 else [4, 8, 16]), rint(0, len(o["coded"])), 0))
+
+    def index_ops():
+        c = rng.random()
+        if c < 0.3 or (m.urec[0] is None and m.urec[1] is None):
+            usage_op()
+        elif c < 0.45:
+            plan_op()
+        elif c < 0.7:
+            remap_op()
+        elif c < 0.85:
+            optimize_op()
+        else:
+            S = rint(0, 2)
+            if m.seq[S] is not None:
+                s_index_ops(S)
+
+    def surface_2_ops():
+        c = rng.random()
+        if c < 0.4:
+            local_ops()
+        elif c < 0.6:
+            cpair_ops()
+        else:
+            index_ops()
+
+    def refusal_2(what):
+        S = rint(0, 2)
+        if what in ("shared_frame_on_local", "local_tolerance_without_delta", "warm_with_fixed"):
+            open_local(S, fam=pick([0, 1]), k=rint(2, 20), warm=int(what == "warm_with_fixed"))
+            i = LOCAL_FAMILIES[m.seq[S].out["fam"]][0]
+            if what == "warm_with_fixed":
+                frame_local(S, i)
+                emit(("fixed", pick([1, 2, 3])))
+            emit(("refuse", what, S, i))
+            if what == "warm_with_fixed":
+                emit(("fixed", 0))
+            frame_local(S, LOCAL_FAMILIES[m.seq[S].out["fam"]][1], int(what != "local_tolerance_without_delta"), None)
+        elif what == "local_frame_on_shared":
+            small_sequence(S)
+            emit(("s_output", S, n_fixed_of(m.fid) + rint(2, 12), pick([0, 1]), 1, 1))
+            emit(("refuse", what, S, SPRITE))
+            emit(("s_frame", S, SPRITE, 1, None))
+        elif what == "local_frame_no_output":
+            need_seq(S)
+            if m.seq[S].out is not None:
+                emit(("s_end", S))
+            emit(("refuse", what, S, ODD))
+            open_local(S, fam=0, k=rint(2, 20))
+            frame_local(S, ODD)
+        elif what in ("local_meld", "local_index8_k256"):
+            need_seq(S)
+            emit(("refuse", what, S, 256 if what == "local_index8_k256" else 5))       # (the refused begin has ended what was open)
+            open_local(S, fam=1, k=255 if what == "local_index8_k256" and not m.fid else rint(2, 20), fmt=1)
+            frame_local(S, SPRITE)
+        elif what in ("plan_indices_above_k", "plan_empty_record"):
+            rec = rint(0, 2)
+            if m.urec[rec] is None:
+                usage_op(rec=rec, fresh=1)
+            emit(("refuse", what, rec, 0))
+            plan_op(rec=rec)
+        elif what == "optimize_bits_too_narrow":
+            i = FEW if m.n_kept(FEW, m.t) else FLAT
+            k = max(n_fixed_of(m.fid), 3) + rint(0, 6)
+            emit(("refuse", what, i, k))
+            emit(("optimize", i, k, 0, 4, 0))
+        else:
+            assert what == "remap_bad_bits", what
+            emit(("refuse", what, FLAT, pick([0, 3, 5, 32])))
+            remap_op(i=FLAT)
+
+    def restore_cutoff(t):
+        if m.t != t:
+            emit(("cutoff", t))
+
+    def motif_warm_cutoff():
+        """a warm output across a cutoff switch and back: each frame's working image is that of the cutoff read at its call"""
+        S, t0 = rint(0, 2), m.t
+        fam = pick([0, 1])
+        open_local(S, fam=fam, k=rint(3, 24), warm=1)
+        F = LOCAL_FAMILIES[fam]
+        frame_local(S, F[0])
+        frame_local(S, F[1], 1, pick([None, 40]))
+        emit(("cutoff", pick([x for x in CUTOFFS if x != m.t])))
+        frame_local(S, F[-1])
+        emit(("cutoff", t0))
+        frame_local(S, F[0], 1, pick([None, 4096]))
+
+    def motif_refused_warm():
+        """frame / refused frame / frame on a warm output: the refusal changes nothing, the frame after it is warm; a frame that
+        fails in its palette step makes the next one cold"""
+        S, t0 = rint(0, 2), m.t
+        open_local(S, fam=1, k=rint(3, 16), warm=1, mode=pick([0, 1]))
+        frame_local(S, SPRITE)
+        emit(("fixed", pick([1, 2, 3])))
+        emit(("s_frame_local", S, 3, 1, None))               # -5: fixed colours on a warm output
+        emit(("fixed", 0))
+        frame_local(S, 3)
+        open_local(S, fam=0, k=2, warm=0, fmt=1)
+        frame_local(S, ODD)
+        emit(("fixed", 3))
+        emit(("s_frame_local", S, 1, 1, None))               # -1: k below the fixed colours
+        emit(("fixed", 0))
+        frame_local(S, 1, 1, 40)
+        restore_cutoff(0)
+        open_local(S, fam=len(FAMILIES), k=rint(2, 5), warm=1, fmt=1)
+        frame_local(S, CLEAR)
+        emit(("cutoff", pick([1, 128, 255])))
+        emit(("s_frame_local", S, CLEAR, 1, None))           # -1: no pixel reaches the cutoff
+        emit(("cutoff", 0))
+        frame_local(S, CLEAR)
+        emit(("s_end", S))
+        restore_cutoff(t0)
+
+    def motif_used_block():
+        """a shared output ended, a Lloyd object run and closed, a local output of a smaller k in the block that came back, a lossy
+        first frame: shown is filled at the begin, the held source is not and must not be read"""
+        S, f = rint(0, 2), n_fixed_of(m.fid)
+        small_sequence(S)
+        emit(("s_output", S, f + rint(20, 30), pick([0, 1]), pick([1, 2]), 1))
+        emit(("s_frame", S, SPRITE, 1, None))
+        emit(("s_frame", S, 3, 1, 40))
+        emit(("s_end", S))
+        if m.lloyd[0] is None:
+            emit(("l_new", 0, pick_k(hi=64)))
+            emit(("l_set", 0, "rand", rint(0, 1 << 30), ODD))
+            emit(("l_run", 0, FEW, 1, st()))
+            emit(("l_close", 0))
+        open_local(S, fam=1, k=max(f, 1) + rint(1, 8), fmt=1)
+        frame_local(S, SPRITE, 1, 40)
+        frame_local(S, 3, 1, 4096)
+        frame_local(S, 4, 1, None)
+        # ... and a second begin on the same sequence: nothing shown, nothing to start warm from
+        open_local(S, fam=1, k=m.seq[S].out["k"], fmt=1, warm=m.seq[S].out["warm"], mode=m.seq[S].out["mode"])
+        frame_local(S, 3, 1, 40)
+        frame_local(S, SPRITE)
+
+    def motif_lossy_full():
+        """a lossy frame whose sprite shifted comes back in full; an exact delta frame and a lossy frame after it"""
+        S, t0 = rint(0, 2), m.t
+        if m.t == 0:
+            emit(("cutoff", pick([1, 128, 255])))
+        open_local(S, fam=1, k=rint(3, 24))
+        frame_local(S, SPRITE)
+        frame_local(S, 4, 1, pick([40, 4096]))
+        frame_local(S, 3, 1, None)
+        frame_local(S, SPRITE, 1, 4096)
+        frame_local(S, 4, 1, 400000)
+        frame_local(S, 3, 1, 40)
+        restore_cutoff(t0)
+
+    def motif_local_shared_local():
+        """local / shared / local on one Sequence, with the two cross refusals, which leave the output open"""
+        S = rint(0, 2)
+        small_sequence(S)
+        open_local(S, fam=1, k=rint(3, 16))
+        frame_local(S, SPRITE)
+        emit(("refuse", "shared_frame_on_local", S, 3))
+        frame_local(S, 3)
+        emit(("s_output", S, n_fixed_of(m.fid) + rint(2, 12), pick([0, 1]), pick([1, 2]), 1))
+        emit(("s_frame", S, SPRITE, 1, None))
+        emit(("refuse", "local_frame_on_shared", S, 3))
+        emit(("s_frame", S, 3, 1, pick([None, 40])))
+        open_local(S, fam=1, k=rint(3, 16))
+        frame_local(S, 4)
+        frame_local(S, 3, 1, 40)
+
+    def motif_optimize_path():
+        """what `sequence --optimize` does: one usage record over the coded frames, one plan, every frame remapped"""
+        S, rec, slot = rint(0, 2), rint(0, 2), rint(0, 2)
+        small_sequence(S)
+        emit(("s_output", S, n_fixed_of(m.fid) + rint(4, 40), pick([0, 1, 3]), 1, 1))
+        for j, i in enumerate((SPRITE, 3, 4)):
+            emit(("s_frame", S, i, 1, None))
+            emit(("s_usage", S, rec, int(j == 0), j))
+        emit(("plan", rec, slot, index_ref.ORDER_USAGE | index_ref.KEEP_TRANSPARENT))
+        for j in range(3):
+            emit(("s_remap", S, slot, 8, j, 1))
+
+    def motif_records():
+        """records that outlive their map: usage of A, an optimize of B, usage of C into the same record; the bad count across two
+        remaps; INDEX8 at k = 256; two optimize calls in a row"""
+        rec, slot = rint(0, 2), rint(0, 2)
+        usage_op(i=ODD, rec=rec, fresh=1, nb=pick([2, 3]))
+        optimize_op(flags=pick([1, 1 | 16]))
+        usage_op(i=1, rec=rec, fresh=0, nb=pick([2, 3]))
+        optimize_op(flags=pick([1, 1 | 8]))
+        plan_op(rec=rec, slot=slot)
+        remap_op(i=ODD, table=slot, bits=pick([8, 16]), bad_fresh=1)
+        remap_op(i=ODD, table=("rand", rint(0, 1 << 30)), bits=pick([1, 2, 4]), bad_fresh=1)
+        remap_op(i=ROW, table=("rand", rint(0, 1 << 30)), bits=pick([1, 2, 4]), bad_fresh=0)
+        t0 = m.t
+        restore_cutoff(0)
+        usage_op(i=ODD, rec=1 - rec, fresh=1, fmt=1, k=256, nb=2)
+        restore_cutoff(t0)
+
+    def motif_cpair():
+        """a colour-keyed canvas of the caller's on the per-pixel route and on the vector route, palettes kept and changed"""
+        for P, offs in ((0, 1), (1, pick([0, 4]))):
+            fmt = pick([1, 2])
+            emit(("cpair_open", P, 1, fmt, rint(5, 40), offs))
+            cpair_ops(P, 4)
 
     motifs = [mo for mo in (motif_mixed, motif_refusals, motif_cutoff, motif_reoutput, motif_anchor, motif_growth, motif_first_frame, motif_freeze, motif_pins) if rng.random() < 0.75]
+    if surface == 2:
+        motifs += [mo for mo in (motif_warm_cutoff, motif_refused_warm, motif_used_block, motif_lossy_full, motif_local_shared_local,
+                                 motif_optimize_path, motif_records, motif_cpair) if rng.random() < 0.8]
     at = sorted(rint(3, n_ops - 5) for _ in motifs)
     motifs = [motifs[int(j)] for j in rng.permutation(len(motifs))]
     emit(("strategy", pick([2, 0, 1], [0.5, 0.3, 0.2])))
@@ -827,6 +1204,9 @@ def generate(seed, seq, n_ops=150):
         if motifs and len(ops) >= at[0]:
             at.pop(0)
             motifs.pop(0)()
+            continue
+        if surface == 2 and rng.random() < 0.4:
+            surface_2_ops()
             continue
         r = rng.random()
         if r < 0.1:
@@ -1039,7 +1419,7 @@ def apply_op(m, op):
             assert k >= n_fixed_of(m.fid) and m.seq_pixels(op[1]) > 0 and (fmt != 1 or k <= 255) and (fmt == 0 or mode != 2), op
             h, w = m.images[FAMILIES[fam][0]][1].shape[:2]
             q.out = dict(t=m.t, k=k, mode=mode, fmt=fmt, fam=fam, cent=None, canvas=np.full((h, w), k, np.int64), held=np.zeros((h, w, 4), np.uint8),
-                         last=None, shape=(h, w))
+                         last=None, shape=(h, w), coded=[])
             if num:
                 q.out["cent"] = R.centroids(m.frames_of(op[1]), k, m.fid)
                 exp["palette"] = R.palette_bytes(q.out["cent"])
@@ -1048,7 +1428,10 @@ def apply_op(m, op):
         elif name == "s_frame":
             i, delta, tol = op[2:5]
             o = q.out
-            assert o is not None and i in FAMILIES[o["fam"]] and (o["fmt"] != 0 or (not delta and tol is None)) and (tol is None or delta), op
+            assert o is not None and not o.get("local") and i in FAMILIES[o["fam"]] and (o["fmt"] != 0 or (not delta and tol is None)) and \
+                (tol is None or delta), op
+            if o["fmt"] and not num:
+                o["coded"].append(None)
             kind = "exact" if tol is None else "lossy"
             exp["transition"] = None if o["last"] in (None, kind) else o["last"] + ">" + kind
             o["last"] = kind
@@ -1071,11 +1454,44 @@ def apply_op(m, op):
                         canvas, held = I.copy(), src.copy()
                 o["canvas"], o["held"] = canvas, held
                 exp.update(map=I if full else d, record=tuple(rec), full=full, fallback=bool(delta and full))
+                o["coded"].append((exp["map"], None, full))
+        elif name == "s_output_local":
+            k, mode, fmt, fam, warm = op[2:7]
+            assert fmt in (1, 2) and (fmt != 1 or k <= 255) and mode in (0, 1, 3), op
+            h, w = m.images[LOCAL_FAMILIES[fam][0]][1].shape[:2]
+            q.out = dict(local=True, k=k, mode=mode, fmt=fmt, fam=fam, warm=warm, shape=(h, w), prev=None, failed=None, last=None, coded=[],
+                         shown=np.zeros((h, w), np.uint32), held=np.zeros((h, w, 4), np.uint8))
+        elif name == "s_frame_local":
+            exp.update(local_frame(m, q.out, op[2], op[3], op[4]))
+        elif name in ("s_usage", "s_remap"):
+            o = q.out
+            assert o is not None and o["coded"] and 0 <= op[4] < len(o["coded"]), op
+            k = o["k"]
+            if name == "s_usage":
+                rec, fresh = op[2], op[3]
+                assert fresh or (m.urec[rec] is not None and m.urec[rec]["k"] == k), op
+                if num:
+                    I, pal, _ = o["coded"][op[4]]
+                    old = np.zeros(k + 2, np.uint64) if fresh else m.urec[rec]["counts"]
+                    m.urec[rec] = dict(k=k, counts=old + index_ref.usage(I, k), palette=R.palette_bytes(o["cent"]) if pal is None else pal)
+                    exp["counts"] = m.urec[rec]["counts"]
+                else:
+                    m.urec[rec] = dict(k=k)
+            else:
+                tb = m.tables[op[2]]
+                assert tb is not None and tb["k"] == k and op[3] in BITS, op
+                if num:
+                    new, bad = index_ref.remap_fast(o["coded"][op[4]][0], k, tb["remap"], op[3])
+                    exp.update(out=index_ref.pack_fast(new, op[3]), bad=bad, new=new)
         else:
             raise ValueError(op)
+    elif name in ("cpair_open", "cpair_frame", "usage_device", "plan", "remap_device", "optimize"):
+        apply_op_2(m, op, exp)
     elif name == "refuse":
         exp["status"] = ERR_INVALID
         what = op[1]
+        if what in REFUSALS_2:
+            refuse_2(m, op, exp)
         if what in ("k_below_fixed_palette", "k_below_fixed_reduce", "k_below_fixed_sequence"):
             assert op[3] < n_fixed_of(m.fid), op
         elif what == "octree_fixed":
@@ -1093,6 +1509,174 @@ def apply_op(m, op):
     else:
         raise ValueError(op)
     return exp
+
+
+# ---- surface 2 on the model -------------------------------------------------------------------------------------------
+def local_frame(m, o, i, delta, tol):
+    """kmg_sequence_output_frame_local on the open local output o: cutoff and fixed colours as they are at THIS call.  A call
+    refused before any work is enqueued (fixed colours on a warm output, k below the fixed colours) changes nothing, not even
+    whether the next frame is warm; a frame that fails in its palette step leaves shown and held and makes the next frame cold"""
+    assert o is not None and o.get("local") and i in LOCAL_FAMILIES[o["fam"]] and (tol is None or delta), (i, delta, tol)
+    R, k, f = m.ref, o["k"], n_fixed_of(m.fid)
+    kind = "fixed_on_warm" if o["warm"] and f else "k_below_fixed" if k < f else "empty" if m.n_kept(i, m.t) == 0 else None
+    exp = {"after": o["failed"], "failed": kind}
+    o["failed"] = kind
+    if kind:
+        exp["status"] = ERR_UNSUPPORTED if kind == "fixed_on_warm" else ERR_INVALID
+        if kind == "empty":
+            o["prev"] = None
+        return exp
+    exp["warm"] = bool(o["warm"] and o["prev"] is not None)
+    exp["first_lossy"] = tol is not None and not o["coded"]
+    if not m.numeric:
+        o["prev"] = True
+        o["coded"].append(None)
+        return exp
+    src = R.img(i)
+    cent = R.warm(i, m.t, o["prev"]) if exp["warm"] else R.centroids(((i, m.t),), k, m.fid)
+    I, P = R.index(src, cent, o["mode"], m.t), R.palette_bytes(cent)
+    if not delta:
+        d, rec, full = None, local_ref.FRESH8, True
+        shown, held = local_ref.lookup(I, P, k)[1], src.copy()
+    elif tol is None:
+        d, shown, rec = local_ref.colour(I, o["shown"], P, k)
+        rec, held, full = tuple(rec) + (0, 0), src.copy(), rec[1] > 0
+    else:
+        d, shown, held, rec = local_ref.lossy(O, src, I, o["shown"], o["held"], P, k, tol)
+        full = rec[1] > 0
+        if full:                                              # the viewer then shows P_t[I_t] everywhere
+            shown, held = local_ref.lookup(I, P, k)[1], src.copy()
+        exp["lossy_full"] = full
+    o.update(shown=shown, held=held, prev=cent)
+    out = I if full else d
+    o["coded"].append((out, P, full))
+    exp.update(map=out, palette=P, record=tuple(int(v) for v in rec), full=full, shown=shown, held_pixels=tol is not None and rec[6] > 0)
+    return exp
+
+
+def cpair_palette(pseed, k):
+    """(the k colours the map is made for, the palette the canvas is keyed by): in the second some entries repeat an earlier one's
+    bytes and one word is zero, as _palette of tests/test_gpu_local.py makes them"""
+    base = find_palette(pseed, k)
+    pal = base.copy()
+    rng = np.random.default_rng([pseed, k, 5])
+    if k >= 2:
+        for j in rng.integers(1, k, max(1, k // 5)):
+            pal[j] = pal[rng.integers(0, j)]
+        pal[rng.integers(0, k)] = 0
+    return base, np.ascontiguousarray(pal)
+
+
+def random_table(tseed, k, bits):
+    """a remap table nobody planned: new indices that fit, dropped entries, entries too wide for `bits`"""
+    rng = np.random.default_rng([tseed, k, bits])
+    t = rng.integers(0, min(1 << bits, 0xFFFF), k + 1).astype(np.uint16)
+    r = rng.random(k + 1)
+    t[r < 0.12] = index_ref.DROPPED
+    if bits < 16:
+        t[r > 0.92] = (1 << bits) + rng.integers(0, 3)
+    return t
+
+
+def usage_source(m, op):
+    """(centroids, index map) of the map usage_device and remap_device make on the device: op[1:6] = image, mode, format, k, seed"""
+    i, mode, fmt, k, seed = op[1:6]
+    cent, _ = gamut_centroids(seed, k)
+    return cent, m.ref.index(m.ref.img(i), cent, mode, m.t)
+
+
+def apply_op_2(m, op, exp):
+    name, num, R = op[0], m.numeric, m.ref
+    if name == "cpair_open":
+        P, fam, fmt, k, offs = op[1:6]
+        assert (fmt != 1 or k <= 255) and offs in CPAIR_OFFSETS, op
+        h, w = m.images[FAMILIES[fam][0]][1].shape[:2]
+        m.cpairs[P] = dict(fam=fam, fmt=fmt, k=k, offs=offs, pseed=None, shown=np.zeros((h, w), np.uint32), held=np.zeros((h, w, 4), np.uint8))
+    elif name == "cpair_frame":
+        P, i, pseed, tol = op[1:5]
+        pr = m.cpairs[P]
+        assert pr is not None and i in FAMILIES[pr["fam"]], op
+        pr["pseed"] = pseed
+        if num:
+            k = pr["k"]
+            base, pal = cpair_palette(pseed, k)
+            src = R.img(i)
+            I = R.index(src, R.find_centroids(base), pseed % 2, m.t)
+            if tol is None:
+                d, pr["shown"], rec = local_ref.colour(I, pr["shown"], pal, k)
+                pr["held"] = src.copy()                              # (the caller's duty after an exact frame)
+                rec = tuple(rec) + (0, 0)
+            else:
+                d, pr["shown"], pr["held"], rec = local_ref.lossy(O, src, I, pr["shown"], pr["held"], pal, k, tol)
+            exp.update(base=base, palette=pal, index=I, delta=d, shown=pr["shown"], held=pr["held"], record=tuple(int(v) for v in rec))
+    elif name == "usage_device":
+        i, mode, fmt, k, seed, rec = op[1:7]
+        fresh = op[10]
+        assert (fmt != 1 or k + (1 if m.t else 0) <= 256) and (fresh or (m.urec[rec] is not None and m.urec[rec]["k"] == k)), op
+        if num:
+            cent, I = usage_source(m, op)
+            old = np.zeros(k + 2, np.uint64) if fresh else m.urec[rec]["counts"]
+            m.urec[rec] = dict(k=k, counts=old + index_ref.usage(I, k), palette=R.palette_bytes(cent))
+            exp.update(cent=cent, index=I, counts=m.urec[rec]["counts"])
+        else:
+            m.urec[rec] = dict(k=k)
+    elif name == "plan":
+        rec, slot, flags = op[1:4]
+        u = m.urec[rec]
+        assert u is not None and (flags & 3) != 3 and not flags & ~index_ref.ALL_FLAGS, op
+        if num:
+            remap, pal, info = index_ref.plan(u["counts"], u["palette"], flags)         # (a record of maps counted here is never empty)
+            m.tables[slot] = dict(k=u["k"], remap=remap, palette=pal, info=info)
+            exp.update(counts=u["counts"], source=u["palette"], remap=remap, palette=pal, info=info)
+        else:
+            m.tables[slot] = dict(k=u["k"])
+    elif name == "remap_device":
+        i, mode, fmt, k, seed, table, bits, in_place, bad_fresh = op[1:10]
+        assert (fmt != 1 or k + (1 if m.t else 0) <= 256) and bits in BITS and (not in_place or bits == 8 * fmt), op
+        assert not isinstance(table, int) or (m.tables[table] is not None and m.tables[table]["k"] == k), op
+        if num:
+            cent, I = usage_source(m, op)
+            tb = m.tables[table]["remap"] if isinstance(table, int) else random_table(table[1], k, bits)
+            new, bad = index_ref.remap_fast(I, k, tb, bits)
+            m.bad = (0 if bad_fresh else m.bad) + bad
+            exp.update(cent=cent, index=I, table=tb, out=index_ref.pack_fast(new, bits), bad=m.bad)
+    elif name == "optimize":
+        i, k, mode, flags, bits = op[1:6]
+        assert k >= n_fixed_of(m.fid) and m.n_kept(i, m.t) > 0 and bits in (0, 8 * host_format(k, m.t)), op
+        if num:
+            cent = R.centroids(((i, m.t),), k, m.fid)
+            pal, I = R.palette_bytes(cent), R.index(R.img(i), cent, mode, m.t)
+            remap, out_pal, info = index_ref.plan(index_ref.usage(I, k), pal, flags)
+            b = bits or info[3]
+            new, bad = index_ref.remap_fast(I, k, remap, b)
+            assert bad == 0
+            exp.update(source=pal, index=I, palette=out_pal, info=info, bits=b, out=index_ref.pack_fast(new, b))
+    else:
+        raise ValueError(op)
+
+
+def refuse_2(m, op, exp):
+    what = op[1]
+    if what in ("shared_frame_on_local", "local_tolerance_without_delta", "warm_with_fixed"):
+        o = m.seq[op[2]].out
+        assert o is not None and o.get("local"), op
+        if what == "warm_with_fixed":
+            assert o["warm"] and n_fixed_of(m.fid) > 0, op
+            exp["status"] = ERR_UNSUPPORTED
+            exp["after"], o["failed"] = o["failed"], "fixed_on_warm"
+    elif what == "local_frame_on_shared":
+        o = m.seq[op[2]].out
+        assert o is not None and not o.get("local"), op
+    elif what == "local_frame_no_output":
+        assert m.seq[op[2]].out is None, op
+    elif what in ("local_meld", "local_index8_k256"):
+        m.seq[op[2]].out = None                               # a begin ends what was open before it checks its arguments
+    elif what in ("plan_indices_above_k", "plan_empty_record"):
+        assert m.urec[op[2]] is not None, op
+    elif what == "optimize_bits_too_narrow":
+        assert op[3] >= max(n_fixed_of(m.fid), 3) and m.n_kept(op[2], m.t) > 0, op
+    else:
+        assert what == "remap_bad_bits" and op[3] not in BITS, op
 
 
 # ---- the runner -----------------------------------------------------------------------------------------------------
@@ -1127,6 +1711,14 @@ class Runner:
         self.acc, self.obj = [None, None], [None, None]
         self.seqs = [None, None]
         self.pairs = [None, None]
+        self.cpairs = [None, None]
+        self.urec = [None, None]                              # device usage records: k + 2 uint64 and the guard
+        self.out2 = self.mem.alloc((1 << 16) + GUARD)
+        self.bad = self.mem.alloc(8 + GUARD)
+        self.mem.fill(self.bad, 0, 8 + GUARD, PATTERN)
+        self.mem.write(self.bad, 0, np.zeros(8, np.uint8))
+        self.coded = [[], []]                                 # what the frames of each Sequence's open output returned
+        self.remapped = [{}, {}]
         self.n_ops = 0
 
     def close(self):
@@ -1276,6 +1868,10 @@ class Runner:
             self.pairs[P] = bufs
         elif name == "pair_frame":
             self.step_pair_frame(op, exp, before_t)
+        elif name in ("cpair_open", "cpair_frame"):
+            self.step_cpair(op, exp)
+        elif name in ("usage_device", "plan", "remap_device", "optimize"):
+            self.step_index(op, exp, before_t)
         else:
             raise ValueError(op)
 
@@ -1464,6 +2060,8 @@ class Runner:
         env, m, name, C = self.env, self.model, op[0], self.counters
         S = op[1]
         q = self.seqs[S]
+        if name in ("s_new", "s_close", "s_output", "s_output_local", "s_end"):
+            self.coded[S], self.remapped[S] = [], {}
         if name == "s_new":
             apply_op(m, op)
             self.seqs[S] = self.proc.sequence()
@@ -1518,8 +2116,90 @@ class Runner:
                 self.fail(f"is_full {full}, the model {exp['full']}")
             self.same("frame record", info.as_tuple(), exp["record"])
             self.same("frame map", got if got.ndim == 3 else got.astype(np.int64), exp["map"])
+            if got.ndim == 2:
+                self.coded[S].append((got, None, bool(full)))
+        elif name == "s_output_local":
+            k, mode, fmt, fam, warm = op[2:7]
+            self.count_k(k, fmt)
+            C["local_begin_warm" if warm else "local_begin_cold"] += 1
+            h, w = m.seq[S].out["shape"]
+            q.output_local(k, mode, fmt, w, h, warm=bool(warm))
+        elif name == "s_frame_local":
+            self.step_frame_local(op, exp)
+        elif name == "s_usage":
+            rec, fresh, j = op[2:5]
+            k = m.seq[S].out["k"]
+            C["s_usage_fresh" if fresh else "s_usage_combined"] += 1
+            self.same("usage record (host)", self.host_usage(rec, fresh, k, lambda use: self.proc.index_usage(self.coded[S][j][0], k, use)), exp["counts"])
+        elif name == "s_remap":
+            slot, bits, j, sure = op[2:6]
+            k, tb = m.seq[S].out["k"], m.tables[slot]
+            C[f"remap_bits:{bits}"] += 1
+            out, bad = self.proc.index_remap(self.coded[S][j][0], k, tb["remap"], bits)
+            self.same("remapped map (host)", out, exp["out"])
+            if bad != exp["bad"] or (sure and bad):
+                self.fail(f"index_remap counted {bad} bad pixels, the model {exp['bad']}" +
+                          (", the plan of these maps' own counts drops no used entry" if sure else ""))
+            self.remapped[S][j] = (exp["new"], slot)
+            coded = self.coded[S]
+            if sure and m.seq[S].out.get("cent") is not None and all(self.remapped[S].get(x, (None, None))[1] == slot for x in range(len(coded))):
+                # the remapped maps through the pruned palette show what the originals show through the original one
+                C["optimize_path_replayed"] += 1
+                pal = m.ref.palette_bytes(m.seq[S].out["cent"])
+                n_colors, _, transparent, _ = tb["info"]
+                if transparent != n_colors:
+                    self.fail("the passage plans without TRANSPARENT_FIRST")
+                a = local_ref.replay_colour([(mp, pal, full) for mp, _, full in coded], k)
+                b = local_ref.replay_colour([(self.remapped[S][x][0], tb["palette"][:n_colors], coded[x][2]) for x in range(len(coded))], n_colors)
+                for x in range(len(coded)):
+                    self.same(f"canvas after frame {x}, remapped against original", b[x], a[x])
         else:
             raise ValueError(op)
+
+    def host_usage(self, rec, fresh, k, call):
+        """a host call that COMBINES into the caller's record `rec`, which lives on the device between the calls"""
+        if fresh:
+            self.new_record(rec, k)
+        use = self.mem.read(self.urec[rec], 0, 8 * (k + 2)).view(np.uint64).copy()
+        call(use)
+        self.mem.write(self.urec[rec], 0, use)
+        return self.read_record(rec, k)
+
+    def new_record(self, rec, k):
+        self.urec[rec] = self.mem.alloc(8 * (k + 2) + GUARD)
+        self.mem.fill(self.urec[rec], 0, 8 * (k + 2) + GUARD, PATTERN)
+        self.mem.write(self.urec[rec], 0, np.zeros(k + 2, np.uint64))
+
+    def read_record(self, rec, k):
+        return self.collect(self.urec[rec], 8 * (k + 2), np.uint64, "usage record")
+
+    def step_frame_local(self, op, exp):
+        m, C = self.model, self.counters
+        S, i, delta, tol = op[1:5]
+        q, o = self.seqs[S], m.seq[S].out
+        img = self.images[i][1]
+        if exp["failed"]:
+            C["failed_frame:" + exp["failed"]] += 1
+            self.expect_status(exp["status"], q.frame_local, img, delta=bool(delta), tolerance=tol)
+            return
+        if exp["after"]:
+            C["frame_after_failed:" + exp["after"]] += 1
+        C["local_warm" if exp["warm"] else "local_cold"] += 1
+        C["local_exact" if tol is None else "local_lossy"] += 1
+        C["local_first_frame_lossy"] += int(exp["first_lossy"])
+        C["local_lossy_full"] += int(exp.get("lossy_full", False))
+        C["local_held_pixels"] += int(exp["held_pixels"])
+        C["local_cutoff_differs_from_last_frame"] += int(o.get("t_last") not in (None, m.t))
+        o["t_last"] = m.t
+        got, pal, info, full = q.frame_local(img, delta=bool(delta), tolerance=tol)
+        what = f"local frame ({'warm' if exp['warm'] else 'cold'}, cutoff {m.t})"
+        self.same("palette of the " + what, pal, exp["palette"])
+        if bool(full) != exp["full"]:
+            self.fail(f"is_full {full}, the model {exp['full']}")
+        self.same("record of the " + what, info.as_tuple(), exp["record"])
+        self.same("map of the " + what, got.astype(np.int64), exp["map"])
+        self.coded[S].append((got, pal, bool(full)))
+        self.same("replay of the coded frames since the begin", local_ref.replay_colour(self.coded[S], o["k"])[-1], exp["shown"])
 
     def step_refuse(self, op):
         m, proc = self.model, self.proc
@@ -1527,6 +2207,8 @@ class Runner:
         what = op[1]
         self.counters["refusal:" + what] += 1
         st = exp["status"]
+        if what in REFUSALS_2:
+            return self.step_refuse_2(op, st)
         if what == "k_below_fixed_palette":
             self.expect_status(st, proc.palette, op[3], self.images[op[2]][1], 0)
         elif what == "k_below_fixed_reduce":
@@ -1557,10 +2239,184 @@ class Runner:
             raise ValueError(op)
 
 
-def run_sequence(env, seed, seq, ops=None, counters=None, proc=None, cache=None):
+    # -- surface 2
+    def step_refuse_2(self, op, st):
+        m, proc, env, what = self.model, self.proc, self.env, op[1]
+        if what in ("shared_frame_on_local", "local_frame_on_shared", "local_frame_no_output", "local_tolerance_without_delta", "warm_with_fixed"):
+            q, img = self.seqs[op[2]], self.images[op[3]][1]
+            if what == "shared_frame_on_local":
+                self.expect_status(st, q.frame, img, delta=True)
+            elif what == "local_tolerance_without_delta":
+                self.expect_status(st, q.frame_local, img, delta=False, tolerance=40)
+            else:
+                self.counters["failed_frame:fixed_on_warm"] += int(what == "warm_with_fixed")
+                self.expect_status(st, q.frame_local, img, delta=True)
+        elif what in ("local_meld", "local_index8_k256"):
+            self.coded[op[2]], self.remapped[op[2]] = [], {}
+            self.expect_status(st, self.seqs[op[2]].output_local, op[3], 2 if what == "local_meld" else 0, 1, 96, 72)
+        elif what in ("plan_indices_above_k", "plan_empty_record"):
+            u = m.urec[op[2]]
+            use = np.zeros(u["k"] + 2, np.uint64)
+            if what == "plan_indices_above_k":
+                use[:] = u["counts"]
+                use[-1] += 1
+            self.expect_status(st, env.index_plan, use, u["palette"], 0)
+        elif what == "optimize_bits_too_narrow":
+            pal, idx = proc.reduce_indexed(op[3], self.images[op[2]][1], 0, 0)
+            self.expect_status(st, proc.optimize_indexed, idx, pal, index_ref.KEEP_UNUSED, 1)
+        elif what == "remap_bad_bits":
+            h, w = self.images[op[2]][1].shape[:2]
+            self.arm(self.out2, 2 * w * h)
+            self.expect_status(st, proc.index_remap_device, self.pix[op[2]].ptr, 1, w, h, 5, np.zeros(6, np.uint16), op[3], self.out2.ptr, self.bad.ptr,
+                               env.streams[0])
+            env.sync()
+            if not (self.collect(self.out2, 2 * w * h, np.uint8, "refused call") == PATTERN).all():
+                self.fail("a refused call wrote output")
+        else:
+            raise ValueError(op)
+
+    def step_cpair(self, op, exp):
+        env, proc, C, m = self.env, self.proc, self.counters, self.model
+        P = op[1]
+        pr = m.cpairs[P]
+        fmt, k, offs = pr["fmt"], pr["k"], pr["offs"]
+        h, w = pr["shown"].shape
+        n, dt = w * h, index_dtype(fmt)
+        sizes = {"index": fmt * n, "delta": fmt * n, "palette": 4 * k, "shown": 4 * n, "held": 4 * n}
+        if op[0] == "cpair_open":
+            self.count_k(k, fmt)
+            # every buffer `offs` elements into a sentinel-filled allocation: offsets 0 and 4 allow the vector route, 1 does not
+            bufs = {b: self.mem.alloc(offs * (fmt if b in ("index", "delta") else 4) + nb + GUARD) for b, nb in sizes.items()}
+            bufs["rec"] = self.mem.alloc(48 + GUARD)
+            self.mem.fill(bufs["rec"], 0, 48 + GUARD, PATTERN)
+            for b, nb in sizes.items():
+                self.mem.fill(bufs[b], 0, offs * (fmt if b in ("index", "delta") else 4) + nb + GUARD, PATTERN)
+            for b in ("shown", "held"):
+                self.mem.write(bufs[b], 4 * offs, np.zeros(4 * n, np.uint8))
+            self.cpairs[P] = bufs
+            return
+        i, pseed, tol, nb, order, s = op[2:8]
+        bufs = self.cpairs[P]
+        off = {b: offs * (fmt if b in ("index", "delta") else 4) for b in sizes}
+        ptr = {b: bufs[b].ptr + off[b] for b in sizes}
+        C["cpair_exact" if tol is None else "cpair_lossy"] += 1
+        C["route:per_pixel" if offs % 4 else "route:vector"] += 1
+        self.arm(self.out, fmt * n)
+        proc.apply(self.pix[i].ptr, w, h, 0, m.ref.find_centroids(exp["base"]), pseed % 2, self.out.ptr, env.streams[s], format=fmt)
+        env.sync()
+        index = self.collect(self.out, fmt * n, dt, "index map")
+        self.same("index map of the frame", index.astype(np.int64).reshape(h, w), exp["index"])
+        self.mem.write(bufs["index"], off["index"], index)
+        self.mem.write(bufs["palette"], off["palette"], exp["palette"].reshape(-1))
+        self.mem.fill(bufs["delta"], off["delta"], fmt * n, PATTERN)
+        self.mem.write(bufs["rec"], 0, np.frombuffer(env.fresh_hold(), np.uint8).copy())
+        bands = bands_of(h, nb, order)
+        C[f"cdelta_bands:{len(bands)}"] += 1
+        for j, (r0, rows) in enumerate(bands):
+            a, e = 4 * r0 * w, fmt * r0 * w
+            stj = env.streams[(s + j) % 2]
+            if tol is None:
+                proc.frame_delta_colour(ptr["index"] + e, ptr["palette"], ptr["shown"] + a, w, rows, r0, fmt, k, ptr["delta"] + e, bufs["rec"].ptr, stj)
+            else:
+                proc.frame_delta_colour_lossy(self.pix[i].ptr + a, ptr["index"] + e, ptr["palette"], ptr["shown"] + a, ptr["held"] + a, w, rows, r0, fmt, k,
+                                              tol, ptr["delta"] + e, bufs["rec"].ptr, stj)
+        env.sync()
+        if tol is None:
+            self.mem.write(bufs["held"], off["held"], self.images[i][1].reshape(-1))     # the caller's duty after an exact frame
+        raw = self.collect(bufs["rec"], 48, np.uint8, "frame record")
+        got = tuple(int(v) for v in raw[:16].view(np.uint64)) + tuple(int(v) for v in raw[16:32].view(np.uint32)) + \
+            tuple(int(v) for v in raw[32:48].view(np.uint64))
+        self.same("record of the colour-keyed frame", got, exp["record"])
+        data = {}
+        for b, nbytes in sizes.items():
+            raw = self.mem.read(bufs[b], 0, off[b] + nbytes + GUARD)
+            if not ((raw[:off[b]] == PATTERN).all() and (raw[off[b] + nbytes:] == PATTERN).all()):
+                self.fail(f"{b}: written outside the buffer")
+            data[b] = raw[off[b]:off[b] + nbytes].copy()
+        self.same("delta map (colour-keyed)", data["delta"].view(dt).astype(np.int64).reshape(h, w), exp["delta"])
+        self.same("shown canvas", data["shown"].view(np.uint32).reshape(h, w), exp["shown"])
+        self.same("held source (colour-keyed)", data["held"].reshape(h, w, 4), exp["held"])
+        self.same("index map after the pass", data["index"].view(dt), index)
+        self.same("palette after the pass", data["palette"], exp["palette"].reshape(-1))
+
+    def device_map(self, op, exp, t0):
+        """the map of usage_device / remap_device, made on the device by the output pass into self.out"""
+        env = self.env
+        i, mode, fmt, k = op[1:5]
+        h, w = self.images[i][1].shape[:2]
+        self.arm(self.out, fmt * w * h)
+        self.proc.apply(self.pix[i].ptr, w, h, 0, exp["cent"], mode, self.out.ptr, env.streams[op[-2] if op[0] == "usage_device" else op[-1]], format=fmt)
+        env.sync()
+        self.check_output(f"the map {op[0]} works on (mode {mode}, format {fmt}, cutoff {t0})", fmt, w, h, exp["index"])
+        return w, h
+
+    def step_index(self, op, exp, t0):
+        env, proc, C, m, name = self.env, self.proc, self.counters, self.model, op[0]
+        if name == "usage_device":
+            fmt, k, rec, nb, order, s, fresh = op[3], op[4], op[6], op[7], op[8], op[9], op[10]
+            C[f"usage:{ {1: 'index8', 2: 'index16'}[fmt] }:{k_class(k)}"] += 1
+            C["usage_fresh" if fresh else "usage_combined_across_images"] += 1
+            w, h = self.device_map(op, exp, t0)
+            if fresh:
+                self.new_record(rec, k)
+            bands = bands_of(h, nb, order)
+            C[f"usage_bands:{len(bands)}"] += 1
+            for j, (r0, rows) in enumerate(bands):
+                proc.index_usage_device(self.out.ptr + fmt * r0 * w, rows * w, fmt, k, self.urec[rec].ptr, env.streams[(s + j) % 2])
+            env.sync()
+            self.same("usage record", self.read_record(rec, k), exp["counts"])
+        elif name == "plan":
+            rec, slot, flags = op[1:4]
+            C[f"plan_order:{flags & 3}"] += 1
+            for bit in (4, 8, 16):
+                C[f"plan_flag:{bit}"] += int(bool(flags & bit))
+            k = m.urec[rec]["k"]
+            use = self.read_record(rec, k)
+            self.same("the record the plan is made from", use, exp["counts"])
+            remap, pal, info = env.index_plan(use, exp["source"], flags)
+            self.same("remap table of the plan", remap, exp["remap"])
+            self.same("palette of the plan", pal, exp["palette"])
+            self.same("info of the plan", tuple(info), exp["info"])
+        elif name == "remap_device":
+            fmt, k, table, bits, in_place, bad_fresh, s = op[3], op[4], op[6], op[7], op[8], op[9], op[10]
+            C[f"remap_bits:{bits}"] += 1
+            C["remap_planned_table" if isinstance(table, int) else "remap_random_table"] += 1
+            C["remap_in_place"] += int(in_place)
+            C["bad_count_combined"] += int(not bad_fresh)
+            w, h = self.device_map(op, exp, t0)
+            nbytes = exp["out"].nbytes
+            dst = self.out if in_place else self.out2
+            if not in_place:
+                self.arm(self.out2, nbytes)
+            if bad_fresh:
+                self.mem.write(self.bad, 0, np.zeros(8, np.uint8))
+            proc.index_remap_device(self.out.ptr, fmt, w, h, k, exp["table"], bits, dst.ptr, self.bad.ptr, env.streams[s])
+            env.sync()
+            self.same(f"remapped map at {bits} bits", self.collect(dst, nbytes, exp["out"].dtype, "remapped map").reshape(exp["out"].shape), exp["out"])
+            got = int(self.collect(self.bad, 8, np.uint64, "bad count")[0])
+            if got != exp["bad"]:
+                self.fail(f"bad-pixel count {got}, the model {exp['bad']}")
+            if not in_place:
+                self.check_output("the input map after the remap", fmt, w, h, exp["index"])
+        elif name == "optimize":
+            i, k, mode, flags, bits = op[1:6]
+            self.count_k(k, host_format(k, t0))
+            C["optimize_plan_bits" if bits == 0 else "optimize_given_bits"] += 1
+            pal, idx = proc.reduce_indexed(k, self.images[i][1], 0, mode)
+            self.same("palette of reduce_indexed", pal, exp["source"])
+            self.same("index map of reduce_indexed", idx.astype(np.int64), exp["index"])
+            out_pal, out, info = proc.optimize_indexed(idx, pal, flags, bits or None)
+            self.same("info of optimize", tuple(info.as_tuple()), exp["info"])
+            self.same("palette of optimize", out_pal, exp["palette"])
+            self.same(f"map of optimize at {exp['bits']} bits", out, exp["out"])
+        else:
+            raise ValueError(op)
+
+
+def run_sequence(env, seed, seq, ops=None, counters=None, proc=None, cache=None, surface=1):
     """one sequence on a fresh processor (or the caller's): (ops run, blocks allocated, blocks re-used); raises Mismatch with the
     replay text"""
-    ops = generate(seed, seq) if ops is None else ops
+    ops = generate(seed, seq, surface=surface) if ops is None else ops
     r = Runner(env, seed, seq, counters, proc, cache)
     try:
         before = r.proc.debug_block_counts()
@@ -1584,3 +2440,10 @@ class KgEnv(LH.KgEnv):
 
     def session_processor(self):
         return self.kg.ImageProcessor(shrink_max_dim=SHRINK, max_iterations=MAX_ITERATIONS, check_period=CHECK_PERIOD, strategy="auto")
+
+    def index_plan(self, usage, palette, flags):
+        remap, pal, info = self.kg.index_plan(usage, palette, flags)
+        return remap, pal, info.as_tuple()
+
+    def fresh_hold(self):
+        return self.kg.FrameHold.fresh_bytes()

@@ -1,6 +1,7 @@
 """Long-lived sessions on the device (tests/session_harness.py): the random sessions of tools/fuzz_session.py on the seeds
 tests/test_session_model.py vouches for, and named scenarios -- each an op list of the harness, run against its stateless model on
-ONE processor that stays alive across all of them (so every scenario works in the blocks the ones before it left).  Everything an
+ONE processor that stays alive across all of them (so every scenario works in the blocks the ones before it left): the eight of the
+first surface, then the directed passages of surface 2 (local outputs, colour-keyed canvases, the index-map optimisation).  Everything an
 op could have touched is compared byte for byte after every op."""
 import os
 import re
@@ -10,7 +11,7 @@ import sys
 import pytest
 
 import session_harness as H
-from test_session_model import SEEDS, SEQUENCES
+from test_session_model import SEEDS, SEEDS_2, SEQUENCES
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,10 +24,26 @@ SESSION_SECONDS = 7.8
 TIMEOUT = 40 * SESSION_SECONDS
 
 
+# The seeds of surface 2 (per-frame palettes, colour-keyed canvases, index-map optimisation) took 5.2 and 4.8 s in the visit in which
+# a seed-201 run took 7.7 s (profiles/NOTES.md): the same rule, forty times the slower of the two.
+SESSION_2_SECONDS = 5.2
+TIMEOUT_2 = 40 * SESSION_2_SECONDS
+
+
 @pytest.mark.parametrize("seed", SEEDS)
 def test_random_sessions_equal_the_model(seed):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_session.py"), str(SEQUENCES), str(seed)],
                        capture_output=True, text=True, timeout=TIMEOUT)
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    assert re.search(rf"^{SEQUENCES} sequences, \d+ ops, 0 mismatching$", r.stdout, re.M), r.stdout[-2000:]
+    reused = [int(x) for x in re.findall(r"(\d+) blocks re-used", r.stdout)]
+    assert len(reused) == SEQUENCES and all(x > 0 for x in reused), reused     # else nothing ran on recycled memory
+
+
+@pytest.mark.parametrize("seed", SEEDS_2)
+def test_random_sessions_of_surface_2_equal_the_model(seed):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_session.py"), str(SEQUENCES), str(seed), "2"],
+                       capture_output=True, text=True, timeout=TIMEOUT_2)
     assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
     assert re.search(rf"^{SEQUENCES} sequences, \d+ ops, 0 mismatching$", r.stdout, re.M), r.stdout[-2000:]
     reused = [int(x) for x in re.findall(r"(\d+) blocks re-used", r.stdout)]
@@ -136,7 +153,87 @@ def _two_sequences_alternate_beside_host_calls_on_the_megapixel_image():
                  ("s_frame", 1, ODD, 0, None), ("s_frame", 0, SPRITE, 1, 4096), ("s_close", 0), ("s_close", 1), ("strategy", 0)])
 
 
-SCENARIOS = {f.__name__[1:]: f for f in (_cutoff_0_128_0_around_palette_reduce_and_a_plan, _frames_added_under_three_cutoffs_then_clear, _an_output_ends_a_lloyd_object_runs_in_its_block_and_the_next_output_starts_fresh, _frozen_seeds_do_not_outlive_their_object, _quality_search_with_and_without_pins_beside_a_bound_object, _records_combine_over_bands_in_reverse_on_two_streams, _every_refusal_is_followed_by_the_correct_call, _two_sequences_alternate_beside_host_calls_on_the_megapixel_image)}
+def _a_warm_output_across_a_cutoff_switch_and_back():
+    """each warm frame runs on the working image of the cutoff read at its own call, from the centroids of the frame before"""
+    return [("cutoff", 0), ("fixed", 0), ("s_new", 0), ("s_output_local", 0, 12, 1, 1, 1, 1), ("s_frame_local", 0, SPRITE, 1, None),
+            ("s_frame_local", 0, NOISY, 1, 40), ("cutoff", 128), ("s_frame_local", 0, SHIFT, 1, None), ("cutoff", 0),
+            ("s_frame_local", 0, SPRITE, 1, 4096), ("s_frame_local", 0, NOISY, 0, None), ("s_close", 0)]
+
+
+def _a_refused_frame_leaves_a_warm_output_warm_and_a_failed_palette_step_makes_it_cold():
+    """frame / refused frame / frame: status -5 for fixed colours on a warm output, -1 for k below the fixed colours, and the
+    frame without a kept pixel, after which the next frame is cold"""
+    return [("cutoff", 0), ("fixed", 0), ("s_new", 0), ("s_output_local", 0, 9, 0, 1, 1, 1), ("s_frame_local", 0, SPRITE, 1, None), ("fixed", 2),
+            ("s_frame_local", 0, NOISY, 1, None), ("fixed", 0), ("s_frame_local", 0, NOISY, 1, None), ("fixed", 1),
+            ("refuse", "warm_with_fixed", 0, SHIFT), ("fixed", 0), ("s_frame_local", 0, SHIFT, 1, 40),
+            ("s_output_local", 0, 2, 0, 1, 0, 0), ("s_frame_local", 0, ODD, 1, None), ("fixed", 3), ("s_frame_local", 0, ODD_B, 1, None), ("fixed", 0),
+            ("s_frame_local", 0, ODD_B, 1, 40),
+            ("s_output_local", 0, 3, 0, 1, 4, 1), ("s_frame_local", 0, CLEAR, 1, None), ("cutoff", 128), ("s_frame_local", 0, CLEAR, 1, None),
+            ("cutoff", 0), ("s_frame_local", 0, CLEAR, 1, None), ("s_close", 0)]
+
+
+def _a_local_output_begins_in_a_used_block_with_a_lossy_first_frame():
+    """a shared output ended, a Lloyd object run and closed, then begin_local with a smaller k in the block that came back: shown is
+    filled, the held source is not and the lossy first frame must not read it; a second begin_local starts from nothing again"""
+    return [("cutoff", 1), ("s_new", 0), ("s_add", 0, SPRITE, 0, 0), ("s_output", 0, 40, 0, 1, 1), ("s_frame", 0, SPRITE, 1, None),
+            ("s_frame", 0, NOISY, 1, 40), ("s_end", 0), ("l_new", 0, 24), ("l_set", 0, "rand", 3, ODD), ("l_run", 0, FEW, 1, 0), ("l_close", 0),
+            ("s_output_local", 0, 7, 1, 1, 1, 0), ("s_frame_local", 0, SPRITE, 1, 40), ("s_frame_local", 0, NOISY, 1, 4096),
+            ("s_frame_local", 0, SHIFT, 1, None), ("s_output_local", 0, 7, 1, 1, 1, 1), ("s_frame_local", 0, NOISY, 1, 40),
+            ("s_frame_local", 0, SPRITE, 1, None), ("s_close", 0), ("cutoff", 0)]
+
+
+def _a_lossy_frame_comes_back_in_full_then_an_exact_and_a_lossy_frame():
+    return [("cutoff", 128), ("s_new", 1), ("s_output_local", 1, 16, 0, 2, 1, 0), ("s_frame_local", 1, SPRITE, 1, None),
+            ("s_frame_local", 1, SHIFT, 1, 4096), ("s_frame_local", 1, NOISY, 1, None), ("s_frame_local", 1, SPRITE, 1, 4096),
+            ("s_frame_local", 1, SHIFT, 1, 400000), ("s_frame_local", 1, NOISY, 1, 40), ("s_close", 1), ("cutoff", 0)]
+
+
+def _local_shared_local_on_one_sequence_with_the_refusals_between():
+    return [("cutoff", 0), ("s_new", 0), ("s_add", 0, SPRITE, 0, 0), ("s_output_local", 0, 8, 0, 1, 1, 0), ("s_frame_local", 0, SPRITE, 1, None),
+            ("refuse", "shared_frame_on_local", 0, NOISY), ("s_frame_local", 0, NOISY, 1, None), ("s_output", 0, 8, 0, 1, 1),
+            ("s_frame", 0, SPRITE, 1, None), ("refuse", "local_frame_on_shared", 0, NOISY), ("s_frame", 0, NOISY, 1, 40),
+            ("s_output_local", 0, 8, 1, 2, 1, 1), ("s_frame_local", 0, SHIFT, 1, None), ("s_frame_local", 0, NOISY, 1, 40), ("s_end", 0),
+            ("refuse", "local_frame_no_output", 0, ODD), ("refuse", "local_meld", 0, 5), ("refuse", "local_index8_k256", 0, 256),
+            ("s_output_local", 0, 255, 0, 1, 1, 0), ("s_frame_local", 0, SPRITE, 1, None), ("refuse", "local_tolerance_without_delta", 0, NOISY),
+            ("s_frame_local", 0, NOISY, 0, None), ("s_close", 0)]
+
+
+def _the_sequence_optimize_path_counts_plans_remaps_and_replays():
+    """one record over the coded frames, one plan by usage with the transparent slot kept, every frame remapped at 8 bits: no bad
+    pixel, and the remapped maps through the pruned palette show what the originals show"""
+    ops = [("cutoff", 128), ("s_new", 0), ("s_add", 0, SPRITE, 0, 0), ("s_output", 0, 24, 1, 1, 1)]
+    for j, i in enumerate((SPRITE, NOISY, SHIFT)):
+        ops += [("s_frame", 0, i, 1, None), ("s_usage", 0, 0, int(j == 0), j)]
+    return ops + [("plan", 0, 0, 1 | 8)] + [("s_remap", 0, 0, 8, j, 1) for j in range(3)] + [("s_close", 0), ("cutoff", 0)]
+
+
+def _usage_records_outlive_their_maps_and_the_bad_count_combines():
+    return [("cutoff", 0), ("usage_device", ODD, 0, 1, 40, 51, 0, 3, _order(61, 3, "reverse"), 0, 1), ("optimize", SPRITE, 12, 1, 1 | 16, 0),
+            ("usage_device", ODD_B, 1, 2, 40, 52, 0, 2, 5, 1, 0), ("optimize", FEW, 6, 0, 1 | 8, 8), ("plan", 0, 0, 2 | 4 | 16),
+            ("remap_device", ODD, 0, 1, 40, 53, 0, 8, 1, 1, 0), ("remap_device", ODD, 3, 2, 40, 54, ("rand", 9), 4, 0, 1, 1),
+            ("remap_device", ROW, 0, 1, 40, 55, ("rand", 10), 1, 0, 0, 0), ("remap_device", COL, 1, 2, 300, 58, ("rand", 11), 2, 0, 0, 1),
+            ("usage_device", ODD, 0, 1, 256, 56, 1, 2, 3, 0, 1), ("refuse", "plan_indices_above_k", 1, 0), ("refuse", "plan_empty_record", 1, 0),
+            ("plan", 1, 1, 0), ("refuse", "optimize_bits_too_narrow", FEW, 5), ("optimize", FEW, 5, 0, 4, 0), ("refuse", "remap_bad_bits", FLAT, 3),
+            ("usage_device", SPRITE, 0, 2, 300, 57, 0, 2, 4, 1, 1), ("plan", 0, 0, 1), ("remap_device", SPRITE, 0, 2, 300, 57, 0, 16, 1, 0, 0)]
+
+
+def _a_colour_keyed_canvas_of_the_caller_on_both_routes():
+    return [("cutoff", 128), ("cpair_open", 0, 1, 1, 40, 1), ("cpair_frame", 0, SPRITE, 61, None, 3, _order(72, 3, "reverse"), 0),
+            ("cpair_frame", 0, NOISY, 61, 40, 3, _order(72, 3, "reverse"), 1), ("cpair_frame", 0, SHIFT, 62, 4096, 2, 3, 0),
+            ("cpair_frame", 0, SPRITE, 62, None, 1, 0, 0), ("cpair_open", 1, 0, 2, 300, 4), ("cpair_frame", 1, ODD, 63, 40, 3, _order(61, 3, "reverse"), 0),
+            ("cpair_frame", 1, ODD_B, 63, 40, 2, 1, 1), ("cpair_frame", 1, ODD, 64, None, 2, 2, 0), ("cutoff", 0)]
+
+
+SCENARIOS = {f.__name__[1:]: f for f in (_cutoff_0_128_0_around_palette_reduce_and_a_plan, _frames_added_under_three_cutoffs_then_clear, _an_output_ends_a_lloyd_object_runs_in_its_block_and_the_next_output_starts_fresh, _frozen_seeds_do_not_outlive_their_object, _quality_search_with_and_without_pins_beside_a_bound_object, _records_combine_over_bands_in_reverse_on_two_streams, _every_refusal_is_followed_by_the_correct_call, _two_sequences_alternate_beside_host_calls_on_the_megapixel_image,
+                                         # surface 2, on the same long-lived processor after the eight above
+                                         _a_warm_output_across_a_cutoff_switch_and_back,
+                                         _a_refused_frame_leaves_a_warm_output_warm_and_a_failed_palette_step_makes_it_cold,
+                                         _a_local_output_begins_in_a_used_block_with_a_lossy_first_frame,
+                                         _a_lossy_frame_comes_back_in_full_then_an_exact_and_a_lossy_frame,
+                                         _local_shared_local_on_one_sequence_with_the_refusals_between,
+                                         _the_sequence_optimize_path_counts_plans_remaps_and_replays,
+                                         _usage_records_outlive_their_maps_and_the_bad_count_combines,
+                                         _a_colour_keyed_canvas_of_the_caller_on_both_routes)}
 
 
 @pytest.mark.parametrize("name", list(SCENARIOS))

@@ -7,8 +7,15 @@ block that grows geometrically, the first-frame record, canvas and held source o
 idle list, n_fixed with the object -- pass every sequence of every committed seed.  Sharp: thirteen faulty variants, one named
 defect each, are each caught by every committed seed.  Coverage: exact counts for the committed seeds, none zero.
 
+Surface 2 (per-frame palettes, colour-keyed canvases, index-map optimisation) has seeds of its own, SEEDS_2, whose sequences also
+run the old ops: the stand-ins keep shown, held source and the last centroids of a local output where the library keeps them (shown
+filled at the begin, the held source not; the centroids in the sequence), usage records and the bad count combine; thirteen more
+faulty variants, and the thirteen old ones, are each caught by each of SEEDS_2; a second exact table, EXACT_2.  The op lists of the
+old seeds are pinned by hash: surface 2 must not move them.
+
 Wall time of this file and of tests/test_lifecycle_model.py: profiles/NOTES.md, "session harness"."""
 import collections
+import hashlib
 
 import numpy as np
 import pytest
@@ -20,6 +27,8 @@ import diffuse_ref
 import error_ref
 import fixed_ref
 import hold_ref
+import index_ref
+import local_ref
 import sequence_ref
 from lifecycle_harness import sorted_palette
 from test_lifecycle_model import FakeError, HostMem, _view
@@ -30,6 +39,17 @@ SEQUENCES = 6               # ... and its sequences per seed
 FAULTS = ("cutoff_read_at_palette_time", "plan_follows_cutoff", "fixed_sticks_after_none", "n_fixed_inherited", "set_fixed_zero_ignored",
           "canvas_survives_end_output", "held_not_reanchored", "held_frame_swap_lost", "record_not_reset", "band_combined_twice",
           "clear_keeps_first_frame", "w_growth_drops_tail", "quality_leaves_switch")
+
+
+# surface 2 (per-frame palettes, colour-keyed canvases, index-map optimisation): its own seeds, which also run every old op
+SEEDS_2 = (314, 315)
+FAULTS_2 = ("warm_after_failed_frame", "warm_survives_begin", "shown_survives_begin", "failed_frame_touches_shown",
+            "local_switches_read_at_begin", "held_not_reanchored_local", "lossy_full_keeps_lossy_canvas", "duplicate_entries_sent",
+            "usage_overwrites", "usage_index8_256_touches_tail", "bad_count_overwrites", "optimize_counts_leak", "remap_padding_dirty")
+
+
+NEW_OPS = ("s_output_local", "s_frame_local", "cpair_open", "cpair_frame", "usage_device", "plan", "remap_device", "optimize", "s_usage",
+           "s_remap")
 
 
 class Record:
@@ -64,6 +84,7 @@ class FakeProcessor:
         self.idle = []                 # blocks of closed objects and ended outputs: what their last owner left in them
         self.allocated = self.reused = 0
         self.last_compare = error_ref.ZERO
+        self.opt_counts = None
 
     # -- blocks
     def take(self):
@@ -255,6 +276,97 @@ class FakeProcessor:
             old = hold_ref.combine(old, rec)
         put(old)
 
+    # -- colour-keyed delta passes on the caller's canvas
+    def _colour_band(self, d_index, d_palette, d_shown, width, rows, format, k):
+        return (self._band(d_index, width, rows, format).astype(np.int64), _view(d_palette, 4 * k, np.uint8).reshape(k, 4),
+                _view(d_shown, width * rows, np.uint32).reshape(rows, width))
+
+    def frame_delta_colour(self, d_index, d_palette, d_shown, width, rows, row0, format, k, d_delta, d_info, stream=0):
+        index, pal, shown = self._colour_band(d_index, d_palette, d_shown, width, rows, format, k)
+        d, new_shown, rec = local_ref.colour(index, shown, pal, k, row0)
+        if self.fault == "duplicate_entries_sent":                       # entries are told apart by index: a repeat of an earlier entry is "another colour"
+            c, p = local_ref.lookup(index, pal, k)
+            table = np.concatenate([local_ref.words(pal), np.zeros(1, np.uint32)])
+            first = np.array([int(np.flatnonzero(table == w)[0]) for w in table])
+            ch = (p != shown) | (first[c] != c)
+            d, rec = np.where(ch, c, k), local_ref._record(ch, p, row0)
+        self._band(d_delta, width, rows, format)[:] = d
+        shown[:] = new_shown
+        old, put = _record_view(d_info, False)
+        put(local_ref.combine(old, rec))
+
+    def frame_delta_colour_lossy(self, d_src, d_index, d_palette, d_shown, d_held, width, rows, row0, format, k, tolerance, d_delta, d_info,
+                                 stream=0):
+        index, pal, shown = self._colour_band(d_index, d_palette, d_shown, width, rows, format, k)
+        src = _view(d_src, 4 * width * rows, np.uint8).reshape(rows, width, 4)
+        held = _view(d_held, 4 * width * rows, np.uint8).reshape(rows, width, 4)
+        d, new_shown, new_held, rec = local_ref.lossy(O, src, index, shown, held, pal, k, tolerance, row0)
+        self._band(d_delta, width, rows, format)[:] = d
+        shown[:] = new_shown
+        held[:] = new_held
+        old, put = _record_view(d_info, True)
+        put(local_ref.combine(old, rec))
+
+    # -- index-map optimisation
+    def _check_index(self, format, k, n):
+        if format not in (1, 2) or k == 0 or k > index_ref.MAX_K or (format == 1 and k > 256) or n == 0:
+            raise FakeError(-1, "index format, k or size")
+
+    def _count(self, index, k, use, format):
+        counts = index_ref.usage(index, k)
+        if self.fault == "usage_index8_256_touches_tail" and format == 1 and k == 256:
+            counts[256] = counts[0]                                      # the byte 0 taken for slot 256
+        use[:] = counts if self.fault == "usage_overwrites" else use + counts
+
+    def index_usage_device(self, d_index, n_pixels, format, k, d_usage, stream=0):
+        self._check_index(format, k, n_pixels)
+        self._count(_view(d_index, n_pixels, H.index_dtype(format)), k, _view(d_usage, k + 2, np.uint64), format)
+
+    def _remap(self, a, k, remap, bits):
+        new, bad = index_ref.remap_fast(a, k, remap, bits)
+        out = index_ref.pack_fast(new, bits)
+        if self.fault == "remap_padding_dirty" and bits < 8 and (a.shape[1] * bits) % 8:
+            out[:, -1] |= 1
+        return out, bad
+
+    def index_remap_device(self, d_in, in_format, width, rows, k, remap, out_bits, d_out, d_bad, stream=0):
+        self._check_index(in_format, k, width * rows)
+        if out_bits not in H.BITS:
+            raise FakeError(-1, "out_bits")
+        out, bad = self._remap(_view(d_in, width * rows, H.index_dtype(in_format)).reshape(rows, width).copy(), k, remap, out_bits)
+        _view(d_out, out.size, out.dtype)[:] = out.reshape(-1)
+        count = _view(d_bad, 1, np.uint64)
+        count[0] = bad if self.fault == "bad_count_overwrites" else int(count[0]) + bad
+
+    def index_usage(self, index, k, usage=None):
+        a = np.ascontiguousarray(index)
+        use = np.zeros(k + 2, np.uint64) if usage is None else usage
+        self._check_index(1 if a.dtype == np.uint8 else 2, k, a.size)
+        self._count(a, k, use, 1 if a.dtype == np.uint8 else 2)
+        return use
+
+    def index_remap(self, index, k, remap, bits):
+        a = np.ascontiguousarray(index)
+        self._check_index(1 if a.dtype == np.uint8 else 2, k, a.size)
+        return self._remap(a, k, remap, bits)
+
+    def optimize_indexed(self, index, palette, flags=17, bits=None):
+        a = np.ascontiguousarray(index)
+        pal = np.ascontiguousarray(palette, np.uint8).reshape(-1, 4)
+        k = pal.shape[0]
+        counts = index_ref.usage(a, k)
+        if self.fault == "optimize_counts_leak" and self.opt_counts is not None:     # the call's device record is not zeroed
+            counts[:k + 1] += np.resize(self.opt_counts, k + 1)
+        self.opt_counts = counts
+        planned = index_ref.plan(counts, pal, flags)
+        if planned is None:
+            raise FakeError(-1, "the plan refuses")
+        remap, out_pal, info = planned
+        b = bits or info[3]
+        if b < info[3] or b > 8 * a.dtype.itemsize:
+            raise FakeError(-1, "out_bits")
+        return out_pal, self._remap(a, k, remap, b)[0], Record(info)
+
     def sequence(self):
         return FakeSequence(self)
 
@@ -273,6 +385,7 @@ class FakeSequence:
         self.first_whole = False
         self.out = None
         self.last_record = None
+        self.prev = None               # the centroids of the last local frame: they live in the sequence, not in the output
 
     def close(self):
         self.end_output()
@@ -362,12 +475,81 @@ class FakeSequence:
 
     def end_output(self):
         if self.out is not None:
-            self.out["block"]["canvas"] = self.out["canvas"]
+            for name in ("canvas", "shown", "held"):
+                if name in self.out:
+                    self.out["block"][name] = self.out[name]
             self.p.give(self.out["block"])
         self.out = None
 
+    def output_local(self, k, mode=0, format=1, width=0, height=0, warm=False):
+        self.end_output()                                                # a begin ends what was open before it checks its arguments
+        if format not in (1, 2):
+            raise FakeError(-1, "per-frame palettes need an index format")
+        if mode == 2:
+            raise FakeError(-1, "meld has no index output")
+        if format == 1 and k > 255:
+            raise FakeError(-1, "INDEX8 holds 256 indices")
+        block = self.p.take()
+        shown = np.zeros((height, width), np.uint32)                     # filled; the held source is not: what the block held
+        left = block.get("shown")
+        if self.fault == "shown_survives_begin" and left is not None and left.shape == shown.shape:
+            shown = left.copy()
+        held = block.get("held")
+        if held is None or held.shape != (height, width, 4):
+            held = np.full((height, width, 4), 0xCD, np.uint8)
+        have_prev = self.fault == "warm_survives_begin" and self.prev is not None and self.prev.shape[0] == k
+        self.out = dict(local=True, k=k, mode=mode, fmt=format, warm=bool(warm), t=self.p.t, shown=shown, held=held, have_prev=have_prev,
+                        block=block)
+
+    def frame_local(self, image, delta=True, tolerance=None):
+        o = self.out
+        if o is None or not o.get("local"):
+            raise FakeError(-1, "no output with per-frame palettes is open")
+        if tolerance is not None and not delta:
+            raise FakeError(-1, "a lossy frame is a delta frame")
+        p, k = self.p, o["k"]
+        t = o["t"] if self.fault == "local_switches_read_at_begin" else p.t      # the switches: as they are when this call starts
+        swapped = self.fault == "warm_after_failed_frame"                # which kind of failure forgets the last centroids
+        if (o["warm"] and p.n_fixed()) or k < p.n_fixed():
+            if swapped:
+                o["have_prev"] = False
+            raise FakeError(-5 if o["warm"] and p.n_fixed() else -1, "fixed colours")
+        warm = o["warm"] and o["have_prev"]
+        if not swapped:
+            o["have_prev"] = False                                       # (the frame after one that failed in its palette step starts cold)
+        img = np.ascontiguousarray(image, np.uint8)
+        i = p.image_index(img)
+        if p.ref.working(((i, t),)) is None:
+            if self.fault == "failed_frame_touches_shown":
+                o["shown"] = np.zeros_like(o["shown"])
+            raise FakeError(-1, "no pixel reaches alpha_cutoff")
+        p.scratch()
+        cent = p.ref.warm(i, t, self.prev) if warm else p.ref.centroids(((i, t),), k, p.fid())
+        I, P = p.ref.index(img, cent, o["mode"], t), p.ref.palette_bytes(cent)
+        if tolerance is None:                                            # without delta the exact pass still runs: shown = P[I]
+            d, o["shown"], rec = local_ref.colour(I, o["shown"], P, k)
+            rec, full = tuple(rec) + (0, 0), (not delta) or rec[1] > 0
+            if not delta:
+                rec = local_ref.FRESH8
+            o["held"] = img                                              # the frame buffer and the held source swap
+        else:
+            was_shown = o["shown"] != 0
+            d, shown, held, rec = local_ref.lossy(O, img, I, o["shown"], o["held"], P, k, tolerance)
+            if self.fault == "held_not_reanchored_local":
+                held = np.where(was_shown[..., None], o["held"], held)
+            full = rec[1] > 0
+            if full:                                                     # the exact pass over the same canvas, and the swap
+                if self.fault != "lossy_full_keeps_lossy_canvas":
+                    shown = local_ref.lookup(I, P, k)[1]
+                held = img
+            o["shown"], o["held"] = shown, held
+        self.prev, o["have_prev"] = cent, True
+        return (I if full else d).astype(H.index_dtype(o["fmt"])), P, Record(rec), full
+
     def frame(self, image, delta=True, tolerance=None):
         o = self.out
+        if o is not None and o.get("local"):
+            raise FakeError(-1, "the open output has per-frame palettes")
         if o is None:
             raise FakeError(-1, "no output is open")
         if (delta or tolerance is not None) and o["fmt"] == 0:
@@ -523,30 +705,39 @@ class FakeEnv:
     def lloyd(self, proc, k):
         return FakeLloyd(proc, k, self.fault)
 
+    def index_plan(self, usage, palette, flags):
+        planned = index_ref.plan(usage, palette, flags)
+        if planned is None:
+            raise FakeError(-1, "the plan refuses")
+        return planned
+
+    def fresh_hold(self):
+        return np.array(hold_ref.FRESH[:2], np.uint64).tobytes() + np.array(hold_ref.FRESH[2:6], np.uint32).tobytes() + \
+            np.array(hold_ref.FRESH[6:], np.uint64).tobytes()
+
 
 def _env(seed, seq, cache, fault=None):
     return FakeEnv(H.make_images(seed, seq), cache, fault)
 
 
-@pytest.fixture(scope="module")
-def campaign():
+def _campaign(seeds, faults, surface):
     """every committed (seed, sequence) on the faithful stand-in and on each faulty one that seed has not caught yet"""
     O.lib()
     counters = collections.Counter()
-    caught = {seed: {} for seed in SEEDS}
+    caught = {seed: {} for seed in seeds}
     failures, reused, n_ops = [], {}, 0
-    for seed in SEEDS:
+    for seed in seeds:
         reused[seed] = []
         for seq in range(SEQUENCES):
             answers = {}                          # the reference's answers: the same for every stand-in of this sequence
-            ops = H.generate(seed, seq)
+            ops = H.generate(seed, seq, surface=surface)
             try:
                 done, _, again = H.run_sequence(_env(seed, seq, answers), seed, seq, ops, counters, cache=answers)
                 reused[seed].append(again)
                 n_ops += done
             except H.Mismatch as e:
                 failures.append(str(e)[:3000])
-            for fault in FAULTS:
+            for fault in faults:
                 if fault in caught[seed]:
                     continue
                 try:
@@ -554,6 +745,16 @@ def campaign():
                 except H.Mismatch as e:
                     caught[seed][fault] = (seq, str(e).split("\n")[0][:200])
     return {"counters": counters, "caught": caught, "failures": failures, "reused": reused, "ops": n_ops}
+
+
+@pytest.fixture(scope="module")
+def campaign():
+    return _campaign(SEEDS, FAULTS, 1)
+
+
+@pytest.fixture(scope="module")
+def campaign_2():
+    return _campaign(SEEDS_2, FAULTS + FAULTS_2, 2)
 
 
 def test_generator_is_deterministic():
@@ -571,22 +772,63 @@ def test_faithful_stand_in_passes_every_sequence(campaign):
         campaign["reused"]
 
 
+def test_faithful_stand_in_passes_every_sequence_of_surface_2(campaign_2):
+    assert not campaign_2["failures"], "\n\n".join(campaign_2["failures"])
+    reused = campaign_2["reused"]
+    assert all(n > 0 for seed in SEEDS_2 for n in reused[seed]) and all(len(reused[s]) == SEQUENCES for s in SEEDS_2), reused
+
+
+# sha256 of repr(generate(seed, seq)) on the commit before surface 2 existed: the sessions of the old seeds never change
+PINNED = {
+    201: ("9583056de68e9607bd6dc48e57fac0e98ea9ef1e700e99f80ff67861f48a5309", "a9220eb11068dd3887b9e29b693f33ad6198d868f915388d85772889113eec54",
+          "e258aeb19305343aed8cdf3b7ca1f860acf23702a782312c43c4233bfdf9ea9b", "54b695d69c1eb3d23db5c8db72bb3c9b45ae19d97435c6f2dfe9fd541a3e4470",
+          "b87c37e3a40f5d685370ab682c6eea800065861e14c76396875ea2f456c72bd1", "4c0a60228005c39d972e225bbc420b10ef493a101460781c7e77b47644a64b78"),
+    202: ("656bc1cc05998d6ddb2399629ad7e7f02a49db17fc31df209875cab3a7df1207", "7ef1e222f1dc1559c410fa6e9b4f24f962b3ce6db7cd112d5d51d0bebea006cb",
+          "dbf61297a835f5e39a63bc7e2bad3825078a126864306ab9d4a0e069362965c2", "b39ddf06b2c417efa46d86c40bfbefbcb610e29e724ef21da68d1356ae84dbe2",
+          "3035460b8c40bd9e7d23d242ccead673b1132903efde7f233640f793cbfc5975", "f8737bebd5eb4efddea290d3d1cac4ddb4b02a765c588e693adedb78adc352b0"),
+}
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_the_committed_sessions_are_as_they_were(seed):
+    assert len(PINNED[seed]) == SEQUENCES
+    for seq in range(SEQUENCES):
+        ops = H.generate(seed, seq)
+        assert hashlib.sha256(repr(ops).encode()).hexdigest() == PINNED[seed][seq], (seed, seq)
+        assert ops == H.generate(seed, seq, surface=1) and ops != H.generate(seed, seq, surface=2)
+        assert not {op[0] for op in ops} & set(NEW_OPS) and not {op[1] for op in ops if op[0] == "refuse"} & set(H.REFUSALS_2)
+
+
 @pytest.mark.parametrize("fault", FAULTS)
 def test_every_seed_catches_the_faulty_stand_in(campaign, fault):
     for seed in SEEDS:
         assert fault in campaign["caught"][seed], f"seed {seed} does not catch {fault} in {SEQUENCES} sequences"
 
 
-def test_a_mismatch_prints_a_list_that_replays(campaign):
-    seq, _ = campaign["caught"][SEEDS[0]]["plan_follows_cutoff"]
+@pytest.mark.parametrize("fault", FAULTS + FAULTS_2)
+def test_every_seed_of_surface_2_catches_the_faulty_stand_in(campaign_2, fault):
+    for seed in SEEDS_2:
+        assert fault in campaign_2["caught"][seed], f"seed {seed} does not catch {fault} in {SEQUENCES} sequences"
+
+
+def _replays(caught, seed, fault, surface):
+    """the replay(...) line a failing run prints runs again: it fails on the faulty stand-in and passes on the faithful one"""
+    seq, _ = caught[seed][fault]
     with pytest.raises(H.Mismatch) as e:
-        H.run_sequence(_env(SEEDS[0], seq, {}, "plan_follows_cutoff"), SEEDS[0], seq)
+        H.run_sequence(_env(seed, seq, {}, fault), seed, seq, surface=surface)
     text = str(e.value)
-    assert f"seed {SEEDS[0]} sequence {seq}: op " in text
+    assert f"seed {seed} sequence {seq}: op " in text
     ops = eval(text[text.index("replay(env, "):].split(", ", 3)[3][:-1])
     with pytest.raises(H.Mismatch):
-        H.replay(_env(SEEDS[0], seq, {}, "plan_follows_cutoff"), SEEDS[0], seq, ops)
-    assert H.replay(_env(SEEDS[0], seq, {}), SEEDS[0], seq, ops)[0] == len(ops)
+        H.replay(_env(seed, seq, {}, fault), seed, seq, ops)
+    assert H.replay(_env(seed, seq, {}), seed, seq, ops)[0] == len(ops)
+    return ops
+
+
+def test_a_mismatch_prints_a_list_that_replays(campaign, campaign_2):
+    _replays(campaign["caught"], SEEDS[0], "plan_follows_cutoff", 1)
+    ops = _replays(campaign_2["caught"], SEEDS_2[0], "lossy_full_keeps_lossy_canvas", 2)        # a printed list of surface 2
+    assert {op[0] for op in ops} & set(NEW_OPS)
 
 
 @pytest.mark.parametrize("seed", SEEDS)
@@ -623,7 +865,15 @@ def _scenarios():
                                   "an_output_ends_a_lloyd_object_runs_in_its_block_and_the_next_output_starts_fresh",
                                   "frozen_seeds_do_not_outlive_their_object", "quality_search_with_and_without_pins_beside_a_bound_object",
                                   "records_combine_over_bands_in_reverse_on_two_streams", "every_refusal_is_followed_by_the_correct_call",
-                                  "two_sequences_alternate_beside_host_calls_on_the_megapixel_image"])
+                                  "two_sequences_alternate_beside_host_calls_on_the_megapixel_image",
+                                  "a_warm_output_across_a_cutoff_switch_and_back",
+                                  "a_refused_frame_leaves_a_warm_output_warm_and_a_failed_palette_step_makes_it_cold",
+                                  "a_local_output_begins_in_a_used_block_with_a_lossy_first_frame",
+                                  "a_lossy_frame_comes_back_in_full_then_an_exact_and_a_lossy_frame",
+                                  "local_shared_local_on_one_sequence_with_the_refusals_between",
+                                  "the_sequence_optimize_path_counts_plans_remaps_and_replays",
+                                  "usage_records_outlive_their_maps_and_the_bad_count_combines",
+                                  "a_colour_keyed_canvas_of_the_caller_on_both_routes"])
 def test_the_named_scenarios_of_the_device_are_legal_sequences(name):
     """the op lists tests/test_gpu_session.py runs on the device, on the faithful stand-in (one processor per list here)"""
     G = _scenarios()
@@ -669,7 +919,7 @@ def coverage_names():
                                 "apply_plan", "compact", "compare_device", "pair_open", "pair_frame", "l_new", "l_re", "l_close", "l_set", "l_init",
                                 "l_fix", "l_bind", "l_conv", "l_update", "l_assign", "l_assign_update", "l_iterate", "l_run", "l_lftu", "s_new",
                                 "s_close", "s_add", "s_clear", "s_info", "s_centroids", "s_palette", "s_output", "s_end", "s_frame", "refuse")] + \
-           ["refusal:" + r for r in H.REFUSALS] + [f"k:{cls}:{f}" for cls, fs in formats.items() for f in fs] + \
+           ["refusal:" + r for r in H.REFUSALS_1] + [f"k:{cls}:{f}" for cls, fs in formats.items() for f in fs] + \
            ["transition:exact>lossy", "transition:lossy>exact", "is_full_fallback", "frame_held_pixels", "mixed_cutoff_sequence",
             "plan_outlives_cutoff", "reoutput", "add_shrunk", "compare_host", "record_combined_across_images", "set_fixed_zero", "set_fixed",
             "pair_exact", "pair_lossy", "frame_exact", "frame_lossy"] + \
@@ -686,3 +936,51 @@ def test_coverage_of_the_committed_seeds(campaign):
     wrong = {name: (c[name], EXACT[name]) for name in need if c[name] != EXACT[name] or EXACT[name] < 1}
     assert not wrong, wrong
     assert all(n > 0 for seed in SEEDS for n in campaign["reused"][seed])          # blocks re-used, in every sequence
+
+
+# what the committed seeds of surface 2 give (SEEDS_2 x SEQUENCES), exactly, for what surface 2 adds.  None may be zero.
+EXACT_2 = {
+    'op:s_output_local': 117, 'op:s_frame_local': 328, 'op:cpair_open': 26, 'op:cpair_frame': 93, 'op:usage_device': 46,
+    'op:plan': 29, 'op:remap_device': 40, 'op:optimize': 25, 'op:s_usage': 32, 'op:s_remap': 29,
+    'refusal:shared_frame_on_local': 12, 'refusal:local_frame_on_shared': 14, 'refusal:local_frame_no_output': 3,
+    'refusal:warm_with_fixed': 2, 'refusal:local_tolerance_without_delta': 4, 'refusal:local_meld': 2,
+    'refusal:local_index8_k256': 1, 'refusal:plan_indices_above_k': 4, 'refusal:plan_empty_record': 3,
+    'refusal:optimize_bits_too_narrow': 2, 'refusal:remap_bad_bits': 3, 'local_warm': 108, 'local_cold': 190, 'local_exact':
+    175, 'local_lossy': 123, 'local_begin_warm': 70, 'local_begin_cold': 47, 'local_first_frame_lossy': 29, 'local_lossy_full':
+    41, 'local_held_pixels': 64, 'local_cutoff_differs_from_last_frame': 16, 'failed_frame:fixed_on_warm': 12,
+    'failed_frame:k_below_fixed': 10, 'failed_frame:empty': 10, 'frame_after_failed:fixed_on_warm': 12,
+    'frame_after_failed:k_below_fixed': 10, 'frame_after_failed:empty': 10, 'cpair_exact': 39, 'cpair_lossy': 54,
+    'route:vector': 51, 'route:per_pixel': 42, 'cdelta_bands:1': 49, 'cdelta_bands:2': 10, 'cdelta_bands:3': 34, 'remap_bits:1':
+    11, 'remap_bits:2': 12, 'remap_bits:4': 2, 'remap_bits:8': 36, 'remap_bits:16': 8, 'plan_order:0': 6, 'plan_order:1': 14,
+    'plan_order:2': 9, 'plan_flag:4': 8, 'plan_flag:8': 14, 'plan_flag:16': 7, 'usage:index8:0': 6, 'usage:index8:1': 4,
+    'usage:index8:2': 5, 'usage:index8:3': 12, 'usage:index16:0': 3, 'usage:index16:1': 10, 'usage:index16:2': 3,
+    'usage:index16:3': 1, 'usage:index16:4': 2, 'usage_fresh': 34, 'usage_combined_across_images': 12, 'usage_bands:1': 6,
+    'usage_bands:2': 22, 'usage_bands:3': 18, 's_usage_fresh': 14, 's_usage_combined': 18, 'remap_in_place': 7,
+    'remap_planned_table': 14, 'remap_random_table': 26, 'bad_count_combined': 18, 'optimize_plan_bits': 8,
+    'optimize_given_bits': 17, 'optimize_path_replayed': 9,
+}
+
+
+def coverage_names_2():
+    """what surface 2 adds (the old names are EXACT's and are counted there on the old seeds)"""
+    return ["op:" + o for o in NEW_OPS] + ["refusal:" + r for r in H.REFUSALS_2] + \
+           ["local_warm", "local_cold", "local_exact", "local_lossy", "local_begin_warm", "local_begin_cold", "local_first_frame_lossy",
+            "local_lossy_full", "local_held_pixels", "local_cutoff_differs_from_last_frame"] + \
+           ["failed_frame:" + k for k in H.FAILED_KINDS] + ["frame_after_failed:" + k for k in H.FAILED_KINDS] + \
+           ["cpair_exact", "cpair_lossy", "route:vector", "route:per_pixel"] + [f"cdelta_bands:{n}" for n in (1, 2, 3)] + \
+           [f"remap_bits:{b}" for b in H.BITS] + [f"plan_order:{o}" for o in (0, 1, 2)] + [f"plan_flag:{b}" for b in (4, 8, 16)] + \
+           [f"usage:index8:{c}" for c in range(4)] + [f"usage:index16:{c}" for c in range(5)] + \
+           ["usage_fresh", "usage_combined_across_images"] + [f"usage_bands:{n}" for n in (1, 2, 3)] + \
+           ["s_usage_fresh", "s_usage_combined", "remap_in_place", "remap_planned_table", "remap_random_table", "bad_count_combined",
+            "optimize_plan_bits", "optimize_given_bits", "optimize_path_replayed"]
+
+
+def test_coverage_of_the_committed_seeds_of_surface_2(campaign_2):
+    c = campaign_2["counters"]
+    print({name: c[name] for name in coverage_names_2()}, campaign_2["ops"])
+    assert not campaign_2["failures"]
+    need = coverage_names_2()
+    assert set(need) == set(EXACT_2), sorted(set(need) ^ set(EXACT_2))
+    wrong = {name: (c[name], EXACT_2[name]) for name in need if c[name] != EXACT_2[name] or EXACT_2[name] < 1}
+    assert not wrong, wrong
+    assert all(n > 0 for seed in SEEDS_2 for n in campaign_2["reused"][seed])      # blocks re-used, in every sequence

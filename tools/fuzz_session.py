@@ -3,8 +3,10 @@
 cutoff, fixed colours, strategy), host calls, output passes and plans, error records combined over bands, caller-owned delta
 canvases, two Lloyd objects with seeds and n_fixed, two Sequence objects with their outputs -- all closed and re-created in each
 other's blocks, every result compared byte for byte after every call, every refused call with the status include/kmeans_hip.h
-names.  A mismatch prints the op list (replay() of the harness runs it) and ends the run: nothing more is started on the device.
-usage: fuzz_session.py [sequences] [seed]"""
+names.  Surface 2 adds outputs with per-frame palettes (cold and warm), colour-keyed canvases of the caller's and the index-map
+optimisation (usage records, plans, remaps, kmg_index_optimize) to the same objects, switches and blocks.  A mismatch prints the op
+list (replay() of the harness runs it) and ends the run: nothing more is started on the device.
+usage: fuzz_session.py [sequences] [seed] [surface]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "kmeans-gpu_amd", "python"))
@@ -13,11 +15,13 @@ import session_harness as H
 
 sequences = int(sys.argv[1]) if len(sys.argv) > 1 else 6
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 201
+surface = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+extra = {} if surface == 1 else {"surface": surface}     # (surface 1 is the call as it always was)
 env = H.KgEnv()
 ops_total, t0 = 0, time.time()
 for seq in range(sequences):
     try:
-        n_ops, allocated, reused = H.run_sequence(env, seed, seq)
+        n_ops, allocated, reused = H.run_sequence(env, seed, seq, **extra)
     except H.Mismatch as e:
         print(f"MISMATCH {e}", flush=True)
         print(f"{seq + 1} sequences, {ops_total} ops, 1 mismatching")
