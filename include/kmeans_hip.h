@@ -120,7 +120,7 @@ typedef struct kmg_options {
  *    for byte.  n_kept = 0: KMG_ERR_INVALID_ARGUMENT ("no pixel reaches alpha_cutoff"), nothing written.  Otherwise the
  *    centroids are those the default pipeline (initialisation + Lloyd loop, max_iterations / check_period / convergence) gives
  *    for an image of n_kept x 1 pixels made of K: c_0 = K[floor(n_kept * 0.5625f)], the farthest-point tie rule runs over K's
- *    indices, the sums run over K only.  Every kept pixel weighs 1, whatever its alpha.
+ *    indices, the sums run over K only.  Every kept pixel weighs 1, whatever its alpha (kmg_processor_set_weighting changes that).
  *  - Palette, KMG_ALGO_OCTREE: the octree receives the kept pixels of its <= 128 shrink, in raster order.  All kept: the
  *    default call; none kept: the error above.
  *  - Output (kmg_find, kmg_reduce, kmg_dev_apply, apply plans), all four modes: out.rgb = what the mode writes for the pixel
@@ -131,6 +131,46 @@ typedef struct kmg_options {
  *  - Palette entries keep alpha 255.  The kmg_lloyd_* calls count every pixel they are given (callers compact first:
  *    kmg_dev_alpha_compact); kmg_group_create refuses alpha_cutoff != 0 (KMG_ERR_INVALID_ARGUMENT).
  * (Options structs of the two previous sizes -- without this field, and without `strategy` -- are accepted and mean 0.)        */
+
+/* kmg_processor_set_weighting -- alpha-weighted k-means: a pixel shapes the palette by how much of it is seen.  No counterpart in the
+ * reference.  KMG_WEIGHT_NONE, the default, keeps the behaviour described everywhere else in this header, byte for byte;
+ * KMG_WEIGHT_ALPHA turns weighting on; any other value is KMG_ERR_INVALID_ARGUMENT.  The setter is sticky, like
+ * kmg_processor_set_fixed_colors (kmg_options has no field for it); calls that are already running keep the value they started
+ * with.  With KMG_WEIGHT_ALPHA on a processor whose alpha_cutoff is t:
+ *  - Weight.  The weight of a pixel of the working image is its alpha byte a, 0 .. 255 -- the alpha after the shrink, which filters
+ *    alpha with the bilinear weights of RGB.  (An importance map for an opaque image is therefore an alpha channel, at t = 0.)
+ *  - Kept pixels.  A pixel is kept iff a >= max(t, 1).  The working image W is alpha mode's compaction at that cutoff (the whole
+ *    pixel is copied, alpha included); when every pixel is kept the image itself is W; when none is, the KMG_ERR_INVALID_ARGUMENT
+ *    of alpha mode comes back.
+ *  - Initialisation: unweighted and unchanged -- the farthest-point loop over the kept pixels, the fixed colours first when set,
+ *    exactly what alpha mode at cutoff max(t, 1) runs.
+ *  - Lloyd loop: the accumulators are (sum a qL, sum a qa, sum a qb, sum a) instead of (sum qL, sum qa, sum qb, count) --
+ *    equivalently, the default loop on the pixel list in which pixel i appears a_i times.  Update, convergence count,
+ *    check_period, max_iterations and the fixed colours are unchanged and read those sums; a cluster whose members all weigh 0 is
+ *    an empty cluster.  Labels do not depend on the weights.  Integer sums: every route returns identical bits, as ever.
+ *  - NO identity with the unweighted result is promised, not even for uniform weights: (double)(255 S) / (double)(255 n) can
+ *    round differently from (double)S / (double)n once a sum passes 2^53.
+ *  - Outputs (kmg_find, the output step of kmg_reduce, apply plans, index maps, delta frames, error records) are unchanged: with
+ *    t = 0 the output alpha is 255 as ever, in alpha mode the input's alpha is kept (and the cutoff of the OUTPUT stays t).
+ *  - Bound: |q| < 2^27 and a < 2^8, so a working image of up to 2^28 pixels cannot overflow the int64 sums; a larger one is
+ *    KMG_ERR_UNSUPPORTED, found on the host before any pass of the loop is enqueued.
+ *  - Applies to kmg_palette, kmg_reduce, kmg_reduce_indexed; every palette run of kmg_reduce_quality (whose error measure stays
+ *    the UNWEIGHTED record it is without weighting: a pixel of alpha 1 counts as much as one of 255 there); kmg_sequence_* -- the
+ *    weighting in force at an add decides that frame's cutoff, as alpha_cutoff is read there, and the weighting in force at
+ *    _centroids, _palette, _output_begin or _output_begin_local decides whether the loop is weighted (pixels of weight 0 already
+ *    in W add nothing); the cold and warm per-frame palettes of _output_frame_local.
+ *  - The sums are always those of the per-pixel passes, whatever kmg_options.strategy says: the colour table's histogram counts
+ *    pixels.  (The initialisation may still run over the colour table.)
+ *  - KMG_ERR_INVALID_ARGUMENT, nothing written: KMG_ALGO_OCTREE while weighting is on; kmg_group_palette / _reduce /
+ *    _reduce_batch when a member processor has it on.
+ * kmg_lloyd_set_weighting(s, KMG_WEIGHT_ALPHA) is the device building block: every later sum of that object -- _assign_accumulate,
+ * _assign_partials + _reduce_partials, _assign_update, _iterate, _run -- weighs each pixel it is given by its alpha byte (at most
+ * 2^28 pixels per pass: KMG_ERR_UNSUPPORTED above); kmg_lloyd_prepare answers strategy 0, and kmg_lloyd_run drops a binding the
+ * initialisation left instead of inheriting it.  Refused with KMG_ERR_INVALID_ARGUMENT on such an object: kmg_lloyd_bind_image,
+ * _set_cell_share, _accumulate_into, _labels_from_tables_update; and kmg_lloyd_set_weighting itself while the caller holds a
+ * binding (kmg_lloyd_bind_image / _prepare).  The kmg_lloyd_* calls still count every pixel they are given: callers compact.     */
+#define KMG_WEIGHT_NONE  0
+#define KMG_WEIGHT_ALPHA 1
 
 /* kmg_processor_set_fixed_colors -- fixed palette colours: entries the k-means keeps, exactly, and builds the rest around.  No
  * counterpart in the reference.  F = a list of f RGBA8 colours set on a processor (alpha ignored, duplicates allowed,
@@ -187,6 +227,8 @@ KMG_API int kmg_processor_set_strategy(kmg_processor *p, int strategy);
 /* changes kmg_options.alpha_cutoff of a live processor (0 .. 255); calls that are already running keep the value they started
  * with                                                                                                                         */
 KMG_API int kmg_processor_set_alpha_cutoff(kmg_processor *p, uint32_t alpha_cutoff);
+/* KMG_WEIGHT_*: whether the palette step weighs a pixel by its alpha byte, see above                                              */
+KMG_API int kmg_processor_set_weighting(kmg_processor *p, int weighting);
 /* sets (n > 0: copies n x 4 bytes) or clears (n = 0) the processor's fixed colours, see above                                     */
 KMG_API int kmg_processor_set_fixed_colors(kmg_processor *p, const uint8_t *rgba, uint32_t n);
 /* Page-locked host memory for images that cross the boundary often (a frame loop): a result buffer from kmg_host_alloc has
@@ -294,6 +336,8 @@ KMG_API int kmg_lloyd_init_centroids_seeded(kmg_lloyd *s, const uint8_t *d_rgba,
  * stream, not for those enqueued before.  Refused (KMG_ERR_INVALID_ARGUMENT) while a cell share is set, like the updates
  * themselves.                                                                                                                   */
 KMG_API int kmg_lloyd_set_fixed(kmg_lloyd *s, uint32_t n_fixed);
+/* KMG_WEIGHT_*: whether the sums of this object weigh a pixel by its alpha byte (at kmg_processor_set_weighting above)            */
+KMG_API int kmg_lloyd_set_weighting(kmg_lloyd *s, int weighting);
 
 /* The same initialisation for an image sharded in row bands (one kmg_lloyd per band / GPU).  Step j:
  *   kmg_lloyd_init_step      band-local pass for centroid j-1; *d_key (device u64) = arg-max key of

@@ -26,15 +26,21 @@ int check_image(const kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_
 // The working image of the k-means palette step (operations.rs:15-88 extract_palette_kmeans before its loop): the image after the
 // shrink, then -- alpha mode (alpha_cutoff != 0, include/kmeans_hip.h at kmg_options) -- its kept pixels, compacted in raster order,
 // as an image of n_kept x 1 pixels, unless every pixel is kept.  Made once per call; the buffers live as long as the object.
+// Alpha weighting (kmg_processor_set_weighting) composes here: the cutoff becomes max(alpha_cutoff, 1) -- a pixel of weight 0 is
+// not kept -- and the compaction copies whole pixels, so the weights ride in the working image's alpha bytes.
 struct WorkingImage {
     StreamBuf small, kept;
     const uint8_t *src = nullptr;
     uint32_t sw = 0, sh = 0;
+    int weighting = KMG_WEIGHT_NONE;
 };
 
-int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t alpha_cutoff, hipStream_t st, WorkingImage &wi)
+int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t alpha_cutoff, int weighting, hipStream_t st,
+                  WorkingImage &wi)
 {
     int rc;
+    alpha_cutoff = working_cutoff(alpha_cutoff, weighting);
+    wi.weighting = weighting;
     const uint8_t *src = d_rgba;
     uint32_t sw = w, sh = h;
     StreamBuf &small = wi.small;
@@ -61,6 +67,8 @@ int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t 
             sh = 1;
         }
     }
+    if (weighting && (uint64_t)sw * sh > kMaxWeightedPixels)
+        return fail(KMG_ERR_UNSUPPORTED, "alpha weighting: the working image has %llu pixels, more than 2^28", (unsigned long long)((uint64_t)sw * sh));
     wi.src = src;
     wi.sw = sw;
     wi.sh = sh;
@@ -73,14 +81,18 @@ int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t 
 // d_labels (optional): the u32 label of every pixel of the working image under the final centroids (find_centroid.wgsl:15-44, the
 // label KMG_MODE_REPLACE gives the pixel).
 int kmg::palette_of_working(kmg_processor *p, const uint8_t *src, uint32_t sw, uint32_t sh, uint32_t k, hipStream_t st, float *c4,
-                            uint32_t *d_labels, const float *fixed4, uint32_t n_fixed)
+                            uint32_t *d_labels, const float *fixed4, uint32_t n_fixed, int weighting)
 {
     int rc;
     LloydGuard g;
+    if (weighting && (uint64_t)sw * sh > kMaxWeightedPixels)
+        return fail(KMG_ERR_UNSUPPORTED, "alpha weighting: the working image has %llu pixels, more than 2^28", (unsigned long long)((uint64_t)sw * sh));
     if (n_fixed > k) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u is below the %u fixed colours of the processor", k, n_fixed);
     if ((rc = lloyd_create_impl(p, k, &g.s, st)) != KMG_OK) return rc;
     if ((rc = kmg_lloyd_init_centroids_seeded(g.s, src, sw, sh, fixed4, n_fixed, st)) != KMG_OK) return rc;   // operations.rs:73
     if ((rc = kmg_lloyd_set_fixed(g.s, n_fixed)) != KMG_OK) return rc;
+    // (after the initialisation, which is unweighted and may have bound the image: a weighted loop drops that binding)
+    if ((rc = kmg_lloyd_set_weighting(g.s, weighting)) != KMG_OK) return rc;
     if (log_debug()) {
         std::vector<float> c(4 * k);
         if (kmg_lloyd_get_centroids(g.s, c.data(), st) == KMG_OK) {
@@ -108,39 +120,43 @@ typedef std::shared_ptr<const std::vector<float>> FixedList;
 int palette_of_working(kmg_processor *p, const WorkingImage &wi, uint32_t k, hipStream_t st, float *c4, const FixedList &fixed,
                        uint32_t *d_labels = nullptr)
 {
-    return kmg::palette_of_working(p, wi.src, wi.sw, wi.sh, k, st, c4, d_labels, fixed ? fixed->data() : nullptr, fixed_count(fixed));
+    return kmg::palette_of_working(p, wi.src, wi.sw, wi.sh, k, st, c4, d_labels, fixed ? fixed->data() : nullptr, fixed_count(fixed),
+                                   wi.weighting);
 }
 
 int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff,
-                           hipStream_t st, float *c4, const FixedList &fixed)
+                           int weighting, hipStream_t st, float *c4, const FixedList &fixed)
 {
     int rc;
     WorkingImage wi;
-    if ((rc = working_image(p, d_rgba, w, h, alpha_cutoff, st, wi)) != KMG_OK) return rc;
+    if ((rc = working_image(p, d_rgba, w, h, alpha_cutoff, weighting, st, wi)) != KMG_OK) return rc;
     return palette_of_working(p, wi, k, st, c4, fixed);
 }
 
 }  // namespace
 
 int kmg::local_frame_centroids(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff,
-                               hipStream_t st, float *c4, const float *fixed4, uint32_t n_fixed, const float *warm4)
+                               hipStream_t st, float *c4, const float *fixed4, uint32_t n_fixed, const float *warm4, int weighting)
 {
     int rc;
     WorkingImage wi;
-    if ((rc = working_image(p, d_rgba, w, h, alpha_cutoff, st, wi)) != KMG_OK) return rc;
-    if (!warm4) return kmg::palette_of_working(p, wi.src, wi.sw, wi.sh, k, st, c4, nullptr, fixed4, n_fixed);
+    if ((rc = working_image(p, d_rgba, w, h, alpha_cutoff, weighting, st, wi)) != KMG_OK) return rc;
+    if (!warm4) return kmg::palette_of_working(p, wi.src, wi.sw, wi.sh, k, st, c4, nullptr, fixed4, n_fixed, weighting);
     LloydGuard g;
     if ((rc = lloyd_create_impl(p, k, &g.s, st)) != KMG_OK) return rc;
     if ((rc = kmg_lloyd_init_centroids_seeded(g.s, wi.src, wi.sw, wi.sh, warm4, k, st)) != KMG_OK) return rc;
+    if ((rc = kmg_lloyd_set_weighting(g.s, weighting)) != KMG_OK) return rc;
     if ((rc = kmg_lloyd_run(g.s, wi.src, (uint64_t)wi.sw * wi.sh, nullptr, nullptr, st)) != KMG_OK) return rc;
     return kmg_lloyd_get_centroids(g.s, c4, st);
 }
 
 namespace {
 
-// the refusals of a palette step while the processor has fixed colours (include/kmeans_hip.h at kmg_processor_set_fixed_colors)
-int check_fixed(const FixedList &fixed, uint32_t k, int algo)
+// the refusals of a palette step while the processor has fixed colours (include/kmeans_hip.h at kmg_processor_set_fixed_colors) or
+// alpha weighting (at kmg_processor_set_weighting)
+int check_fixed(const FixedList &fixed, uint32_t k, int algo, int weighting)
 {
+    if (weighting && algo == KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "the octree has no alpha weighting (it is on for the processor)");
     const uint32_t f = fixed_count(fixed);
     if (!f) return KMG_OK;
     if (algo == KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "the octree has no fixed colours (%u are set on the processor)", f);
@@ -361,7 +377,8 @@ try {
     if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
         return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
     const FixedList fixed = fixed_snapshot(p);
-    if ((rc = check_fixed(fixed, color_count, algo)) != KMG_OK) return rc;
+    const int weighting = p->weighting.load(std::memory_order_relaxed);
+    if ((rc = check_fixed(fixed, color_count, algo, weighting)) != KMG_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
     const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     StreamGuard sg;
@@ -378,7 +395,7 @@ try {
         if ((rc = kmg_palette_to_centroids(colors[0].data(), (uint32_t)colors.size(), c4.data())) != KMG_OK) return rc;
     } else {
         c4.resize(4 * (size_t)color_count);
-        if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
+        if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, weighting, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
     }
     const uint32_t k = (uint32_t)(c4.size() / 4);
     if ((rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), k, mode, alpha_cutoff, sg.st, (uint8_t *)out_index, format)) != KMG_OK)
@@ -401,7 +418,8 @@ try {
     if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
         return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
     const FixedList fixed = fixed_snapshot(p);
-    if ((rc = check_fixed(fixed, color_count, algo)) != KMG_OK) return rc;
+    const int weighting = p->weighting.load(std::memory_order_relaxed);
+    if ((rc = check_fixed(fixed, color_count, algo, weighting)) != KMG_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
     const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     StreamGuard sg;
@@ -420,7 +438,7 @@ try {
         return apply_and_download(p, (const uint8_t *)img.ptr, w, h, oc4.data(), (uint32_t)colors.size(), mode, alpha_cutoff, sg.st, out_rgba);
     }
     std::vector<float> c4(4 * (size_t)color_count);
-    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
+    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, weighting, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
     const auto t2 = std::chrono::steady_clock::now();
     rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), color_count, mode, alpha_cutoff, sg.st, out_rgba);
     if (log_debug()) {
@@ -445,7 +463,8 @@ try {
     if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
         return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
     const FixedList fixed = fixed_snapshot(p);
-    if ((rc = check_fixed(fixed, color_count, algo)) != KMG_OK) return rc;
+    const int weighting = p->weighting.load(std::memory_order_relaxed);
+    if ((rc = check_fixed(fixed, color_count, algo, weighting)) != KMG_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
     const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     StreamGuard sg;
@@ -460,7 +479,7 @@ try {
         return KMG_OK;
     }
     std::vector<float> c4(4 * (size_t)color_count);
-    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
+    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, weighting, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
     sorted_palette_of(c4.data(), color_count, out_rgba);
     *out_count = color_count;
     return KMG_OK;
@@ -587,7 +606,8 @@ try {
     if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
     if (!out || !out_palette_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
     const FixedList fixed = fixed_snapshot(p);
-    if ((rc = check_fixed(fixed, k_min, KMG_ALGO_KMEANS)) != KMG_OK) return rc;
+    const int weighting = p->weighting.load(std::memory_order_relaxed);
+    if ((rc = check_fixed(fixed, k_min, KMG_ALGO_KMEANS, weighting)) != KMG_OK) return rc;
     const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
     if (format == KMG_FORMAT_INDEX8 && k_max + (alpha_cutoff ? 1u : 0u) > 256u)
         return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k_max = %u%s needs INDEX16", k_max, alpha_cutoff ? " plus the transparent slot" : "");
@@ -598,7 +618,7 @@ try {
     StreamBuf img;
     if ((rc = upload_image(p, rgba, w, h, st, img)) != KMG_OK) return rc;
     WorkingImage wi;                                                   // uploaded, shrunk and compacted once
-    if ((rc = working_image(p, (const uint8_t *)img.ptr, w, h, alpha_cutoff, st, wi)) != KMG_OK) return rc;
+    if ((rc = working_image(p, (const uint8_t *)img.ptr, w, h, alpha_cutoff, weighting, st, wi)) != KMG_OK) return rc;
     const uint64_t nw = (uint64_t)wi.sw * wi.sh;
     StreamBuf labels, rec;
     HIP_TRY(labels.alloc(p, (size_t)nw * 4, st));

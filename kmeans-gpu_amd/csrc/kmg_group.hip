@@ -1325,14 +1325,17 @@ int host_call(kmg_group *g, HostCall &c)
 
 }  // namespace
 
-// (fixed colours are a feature of the single-device calls, like alpha mode: a member processor that has some set makes the group's
-// palette calls refuse, instead of quietly ignoring them)
+// (fixed colours and alpha weighting are features of the single-device calls, like alpha mode: a member processor that has either
+// set makes the group's palette calls refuse, instead of quietly ignoring them)
 static int refuse_fixed(kmg_group *g)
 {
     if (!g) return KMG_OK;
     for (uint32_t i = 0; i < g->n_local; ++i)
         if (g->ranks[i].p && processor_fixed_count(g->ranks[i].p))
             return fail(KMG_ERR_INVALID_ARGUMENT, "the processor of rank %u has fixed colours set: the kmg_group_* calls have no pinned entries", i);
+    for (uint32_t i = 0; i < g->n_local; ++i)
+        if (g->ranks[i].p && processor_weighting(g->ranks[i].p))
+            return fail(KMG_ERR_INVALID_ARGUMENT, "the processor of rank %u has alpha weighting on: the kmg_group_* calls have no weighted sums", i);
     return KMG_OK;
 }
 

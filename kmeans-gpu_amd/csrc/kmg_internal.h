@@ -58,9 +58,12 @@ constexpr float kIndexBoxLmin = -100.0f, kIndexBoxLmax = 200.0f, kIndexBoxAB = 3
 // The k-means palette step on a working image (kmg_api.hip): sw x sh pixels in device memory -> host centroid table, a new Lloyd
 // problem of k centroids (initialisation + loop with the processor's options).  Synchronises `st`.  d_labels: optional label map.
 // fixed4 / n_fixed (kmg_processor_set_fixed_colors; n_fixed <= k): the Lab of the pinned entries -- centroids 0 .. n_fixed - 1 start
-// there and stay, the rest is initialised and moves around them.
+// there and stay, the rest is initialised and moves around them.  weighting (KMG_WEIGHT_*): the loop's sums weigh each pixel by its
+// alpha byte; the initialisation does not.
 int palette_of_working(kmg_processor *p, const uint8_t *d_src, uint32_t sw, uint32_t sh, uint32_t k, hipStream_t st, float *centroids4,
-                       uint32_t *d_labels = nullptr, const float *fixed4 = nullptr, uint32_t n_fixed = 0);
+                       uint32_t *d_labels = nullptr, const float *fixed4 = nullptr, uint32_t n_fixed = 0, int weighting = KMG_WEIGHT_NONE);
+// the weighting set on a processor right now (kmg_processor.hip; kmg_processor_set_weighting)
+int processor_weighting(kmg_processor *p);
 // the number of fixed colours set on a processor right now (kmg_processor.hip; kmg_processor_set_fixed_colors)
 uint32_t processor_fixed_count(kmg_processor *p);
 // KMG_MODE_DIFFUSE: the plan's next run starts a new image (row0 = 0, zero error above it) instead of continuing the last one
@@ -84,9 +87,10 @@ int frame_local_impl(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_
                      void *d_delta, void *d_info, hipStream_t st);
 // The centroids of one frame of such an output (kmg_api.hip): the working image of kmg_reduce_indexed's k-means step for the frame in
 // device memory, then -- warm4 == NULL -- that step itself with the fixed colours given, or -- warm4: k x 4 -- the Lloyd loop from
-// those k centroids (a seeded initialisation with every centroid given: no pick).  Synchronises `st`.
+// those k centroids (a seeded initialisation with every centroid given: no pick).  Synchronises `st`.  weighting: KMG_WEIGHT_* (the
+// working image is then cut at max(alpha_cutoff, 1) and both loops are weighted).
 int local_frame_centroids(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff, hipStream_t st,
-                          float *centroids4, const float *fixed4, uint32_t n_fixed, const float *warm4);
+                          float *centroids4, const float *fixed4, uint32_t n_fixed, const float *warm4, int weighting = KMG_WEIGHT_NONE);
 
 // An image between a caller's (pageable) buffer and the device, ordered on `st` (kmg_api.hip): small images asynchronously,
 // large ones as synchronous row-range copies on several streams of the processor.

@@ -32,8 +32,9 @@ hipError_t launch_rgb_to_lab(const uint32_t *rgba, uint64_t n, const float *lut,
                              hipStream_t st);
 
 // labels and/or partial sums.  partials: [assign_grid(n)][k][4] int64, fully overwritten.
+// weighted (kmg_lloyd_set_weighting; it changes the sums only): every pixel adds its alpha byte times (qL, qa, qb, 1); n <= 2^28.
 hipError_t launch_assign(const uint32_t *rgba, uint64_t n, const Centroid *cent, uint32_t k,
-                         const float *lut, uint32_t *labels, int64_t *partials, hipStream_t st);
+                         const float *lut, uint32_t *labels, int64_t *partials, hipStream_t st, bool weighted = false);
 
 // acc[k][4] = sum over rows of partials
 hipError_t launch_reduce_partials(const int64_t *partials, uint32_t rows, uint32_t k,
@@ -48,7 +49,7 @@ bool assign_loop_fits(uint64_t n_pixels);
 size_t assign_loop_scratch_bytes(uint32_t k);
 hipError_t launch_assign_loop(const uint32_t *rgba, uint64_t n, const Centroid *cent, Centroid *cent_out, uint32_t k, const float *lut,
                               uint32_t *labels, const int64_t *acc_in, int64_t *acc_out, int64_t *acc_clear, int do_update,
-                              float convergence, uint32_t *n_converged, hipStream_t st);
+                              float convergence, uint32_t *n_converged, hipStream_t st, bool weighted = false);
 // rows x k x 4 values small enough (reduce_update_fits): reduction and -- do_update -- the update in one launch of one workgroup
 bool reduce_update_fits(uint32_t rows, uint32_t k);
 hipError_t launch_reduce_update(const int64_t *partials, uint32_t rows, uint32_t k, int64_t *acc, int do_update, float convergence,

@@ -208,7 +208,11 @@ struct AssignLoop {
     int do_update = 0;
 };
 
-template <int PPT, bool ACCUM, bool CHUNKED, bool LOOP = false>
+// WEIGHTED (kmg_lloyd_set_weighting, KMG_WEIGHT_ALPHA): a pixel adds w (q, 1) to its cluster's sums, w = its alpha byte -- the word's
+// top byte, which the unweighted instantiations load and ignore.  |q| < 2^27 and w < 2^8: the run registers and the bins hold
+// 2^28 such pixels in int64.  Labels, bins, flush and the LOOP update are the same code; a compile-time switch, so that the
+// unweighted instantiations keep theirs.
+template <int PPT, bool ACCUM, bool CHUNKED, bool LOOP = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(kBlock) void k_assign(const uint32_t *__restrict__ rgba, uint64_t n,
                                                    const Centroid *__restrict__ cent, uint32_t k,
                                                    const float *__restrict__ lut,
@@ -266,6 +270,7 @@ __global__ __launch_bounds__(kBlock) void k_assign(const uint32_t *__restrict__ 
     for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         uint64_t i0[GROUPS];
         float L[PPT], A[PPT], B[PPT];
+        uint32_t wgt[WEIGHTED ? PPT : 1];                              // WEIGHTED: the pixels' alpha bytes
         PixelTerms pt[PPT];
 #pragma unroll
         for (int g = 0; g < GROUPS; ++g) {
@@ -282,6 +287,7 @@ __global__ __launch_bounds__(kBlock) void k_assign(const uint32_t *__restrict__ 
                 const int p = g * G + q;
                 px_to_lab(s_lut, px[q], L[p], A[p], B[p]);
                 pt[p] = pixel_terms(L[p], A[p], B[p]);
+                if (WEIGHTED) wgt[p] = px[q] >> 24;
             }
         }
 
@@ -322,10 +328,18 @@ __global__ __launch_bounds__(kBlock) void k_assign(const uint32_t *__restrict__ 
                             cur = idx[p];
                             rs[0] = rs[1] = rs[2] = rs[3] = 0;
                         }
-                        rs[0] += (long long)lab_fix(L[p]);
-                        rs[1] += (long long)lab_fix(A[p]);
-                        rs[2] += (long long)lab_fix(B[p]);
-                        rs[3] += 1;
+                        if (WEIGHTED) {
+                            const long long w = (long long)wgt[p];
+                            rs[0] += w * (long long)lab_fix(L[p]);
+                            rs[1] += w * (long long)lab_fix(A[p]);
+                            rs[2] += w * (long long)lab_fix(B[p]);
+                            rs[3] += w;
+                        } else {
+                            rs[0] += (long long)lab_fix(L[p]);
+                            rs[1] += (long long)lab_fix(A[p]);
+                            rs[2] += (long long)lab_fix(B[p]);
+                            rs[3] += 1;
+                        }
                     }
                 }
                 if (cur != 0xFFFFFFFFu) {
@@ -388,7 +402,7 @@ uint32_t assign_grid(uint64_t n)
 }
 
 hipError_t launch_assign(const uint32_t *rgba, uint64_t n, const Centroid *cent, uint32_t k,
-                         const float *lut, uint32_t *labels, int64_t *partials, hipStream_t st)
+                         const float *lut, uint32_t *labels, int64_t *partials, hipStream_t st, bool weighted)
 {
     const uint32_t grid = assign_grid(n);
     const uint32_t kpad = (k + 3u) & ~3u;
@@ -400,9 +414,12 @@ hipError_t launch_assign(const uint32_t *rgba, uint64_t n, const Centroid *cent,
     if (partials) lds += sizeof(unsigned long long) * 4ull * k;
 #define KMG_ASSIGN(P, A, C)                                                                                    \
     hipLaunchKernelGGL((k_assign<P, A, C>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, partials, aligned, AssignLoop())
+#define KMG_ASSIGN_W(P, C)                                                                                     \
+    hipLaunchKernelGGL((k_assign<P, true, C, false, true>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, partials, aligned, AssignLoop())
 #define KMG_ASSIGN_P(P)                                                                                        \
     do {                                                                                                       \
-        if (partials) { if (chunked) KMG_ASSIGN(P, true, true); else KMG_ASSIGN(P, true, false); }             \
+        if (partials && weighted) { if (chunked) KMG_ASSIGN_W(P, true); else KMG_ASSIGN_W(P, false); }         \
+        else if (partials) { if (chunked) KMG_ASSIGN(P, true, true); else KMG_ASSIGN(P, true, false); }        \
         else          { if (chunked) KMG_ASSIGN(P, false, true); else KMG_ASSIGN(P, false, false); }           \
     } while (0)
     switch (assign_ppt(n)) {
@@ -412,6 +429,7 @@ hipError_t launch_assign(const uint32_t *rgba, uint64_t n, const Centroid *cent,
     default: KMG_ASSIGN_P(kAssignPPT); break;
     }
 #undef KMG_ASSIGN_P
+#undef KMG_ASSIGN_W
 #undef KMG_ASSIGN
     return hipGetLastError();
 }
@@ -422,7 +440,7 @@ size_t assign_loop_scratch_bytes(uint32_t k) { return sizeof(int64_t) * 12ull * 
 
 hipError_t launch_assign_loop(const uint32_t *rgba, uint64_t n, const Centroid *cent, Centroid *cent_out, uint32_t k, const float *lut,
                               uint32_t *labels, const int64_t *acc_in, int64_t *acc_out, int64_t *acc_clear, int do_update,
-                              float convergence, uint32_t *n_converged, hipStream_t st)
+                              float convergence, uint32_t *n_converged, hipStream_t st, bool weighted)
 {
     const uint64_t tiles = (n + kBlock - 1) / kBlock;
     const uint32_t grid = (uint32_t)(tiles < 2048 ? (tiles ? tiles : 1) : 2048);
@@ -433,7 +451,11 @@ hipError_t launch_assign_loop(const uint32_t *rgba, uint64_t n, const Centroid *
     loop.acc_in = acc_in; loop.acc_out = acc_out; loop.acc_clear = acc_clear; loop.cent_out = cent_out;
     loop.n_converged = n_converged; loop.convergence = convergence; loop.do_update = do_update;
     int64_t *no_partials = nullptr;
-    if (k >= 32)
+    if (weighted && k >= 32)
+        hipLaunchKernelGGL((k_assign<1, true, true, true, true>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, no_partials, aligned, loop);
+    else if (weighted)
+        hipLaunchKernelGGL((k_assign<1, true, false, true, true>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, no_partials, aligned, loop);
+    else if (k >= 32)
         hipLaunchKernelGGL((k_assign<1, true, true, true>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, no_partials, aligned, loop);
     else
         hipLaunchKernelGGL((k_assign<1, true, false, true>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, no_partials, aligned, loop);

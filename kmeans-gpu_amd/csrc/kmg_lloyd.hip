@@ -236,6 +236,7 @@ static int bind_image_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, void
 
 extern "C" int kmg_lloyd_bind_image(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, void *stream)
 try {
+    if (s && s->weighted) return fail(KMG_ERR_INVALID_ARGUMENT, "bind_image: the object's sums are weighted (kmg_lloyd_set_weighting): the colour table counts pixels");
     const int rc = bind_image_impl(s, d_rgba, n, stream, false, 0);
     if (rc == KMG_OK) s->tab.bound_by_caller = true;
     return rc;
@@ -247,6 +248,13 @@ KMG_ABI_CATCH
 static int prepare_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, int want_labels, int *strategy, void *stream, bool caller)
 {
     if (!s || !d_rgba || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad prepare arguments");
+    if (s->weighted) {
+        // weighted sums always take the per-pixel routes: a binding the initialisation left on this buffer is dropped, not inherited
+        if (s->tab.rgba == d_rgba) { s->tab.rgba = nullptr; s->tab.tables_valid = false; }
+        s->tab.bound_by_init = false;
+        if (strategy) *strategy = 0;
+        return KMG_OK;
+    }
     int chosen = 0;
     // the initialisation of this problem may have bound the image a moment ago: that binding is kept, and its facts are known
     const bool fresh = s->tab.rgba == d_rgba && s->tab.n == n && s->tab.bound_by_init;
@@ -508,6 +516,7 @@ static int side_flush(kmg_lloyd *s, hipStream_t st)
 
 static bool table_bound(const kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n)
 {
+    if (s->weighted) return false;   // (the initialisation of a weighted object may have bound the image: its passes do not use that)
     return s->tab.rgba != nullptr && s->tab.rgba == d_rgba && s->tab.n == n;
 }
 
@@ -917,6 +926,26 @@ try {
 }
 KMG_ABI_CATCH
 
+// KMG_WEIGHT_* for every later sum of the object (include/kmeans_hip.h).  A binding the library made itself -- the initialisation's
+// -- ends here in both directions: a weighted object has no use for it, and an unweighted one must not meet, later, the
+// histogram of whatever the buffer held when the object was weighted.
+extern "C" int kmg_lloyd_set_weighting(kmg_lloyd *s, int weighting)
+try {
+    if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "lloyd object is NULL");
+    if (weighting != KMG_WEIGHT_NONE && weighting != KMG_WEIGHT_ALPHA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown weighting %d", weighting);
+    if (s->tab.rgba && s->tab.bound_by_caller)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "set_weighting: an image is bound (kmg_lloyd_unbind_image first): the colour table counts pixels");
+    const bool weighted = weighting == KMG_WEIGHT_ALPHA;
+    if (weighted != s->weighted) {
+        s->tab.rgba = nullptr;
+        s->tab.tables_valid = false;
+        s->tab.bound_by_init = false;
+    }
+    s->weighted = weighted;
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
 extern "C" int kmg_lloyd_set_fixed(kmg_lloyd *s, uint32_t n_fixed)
 try {
     if (!s || n_fixed > s->k) return fail(KMG_ERR_INVALID_ARGUMENT, "bad set_fixed arguments");
@@ -1019,11 +1048,13 @@ static int assign_pass(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, uint32_t
         return table_assign(s, d_rgba, n, d_labels, s->d_partials, kMergeRows, st);
     }
     // a label pass kmg_lloyd_iterate left on the side stream may still be writing d_labels
+    if (sums && s->weighted && n > kMaxWeightedPixels)
+        return fail(KMG_ERR_UNSUPPORTED, "weighted sums take at most 2^28 pixels (%llu given)", (unsigned long long)n);
     int rc_;
     if ((rc_ = side_flush(s, st)) != KMG_OK) return rc_;
     s->last_rows = assign_grid(n);
     PROF_LAUNCH(s, KMG_K_ASSIGN, st, launch_assign((const uint32_t *)d_rgba, n, s->d_cent, s->k, s->p->d_lut, d_labels,
-                                                  sums ? s->d_partials : nullptr, st));
+                                                  sums ? s->d_partials : nullptr, st, s->weighted));
     return KMG_OK;
 }
 
@@ -1045,6 +1076,7 @@ KMG_ABI_CATCH
 extern "C" int kmg_lloyd_accumulate_into(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, int64_t *d_acc4, void *stream)
 try {
     if (!s || !d_rgba || !d_acc4 || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad accumulate_into arguments");
+    if (s->weighted) return fail(KMG_ERR_INVALID_ARGUMENT, "accumulate_into: the object's sums are weighted (kmg_lloyd_set_weighting): the colour table counts pixels");
     HIP_TRY(hipSetDevice(s->p->device));
     if (!table_bound(s, d_rgba, n)) return fail(KMG_ERR_INVALID_ARGUMENT, "accumulate_into: the image is not bound (kmg_lloyd_bind_image / _prepare)");
     return table_assign(s, d_rgba, n, nullptr, d_acc4, 1u, S(stream), false, false, true);
@@ -1090,6 +1122,7 @@ KMG_ABI_CATCH
 extern "C" int kmg_lloyd_set_cell_share(kmg_lloyd *s, uint32_t part, uint32_t parts, void *stream)
 try {
     if (!s || parts == 0 || part >= parts) return fail(KMG_ERR_INVALID_ARGUMENT, "bad set_cell_share arguments");
+    if (s->weighted) return fail(KMG_ERR_INVALID_ARGUMENT, "set_cell_share: the object's sums are weighted (kmg_lloyd_set_weighting): the colour table counts pixels");
     if (!s->tab.rgba || !s->tab.d_hist) return fail(KMG_ERR_INVALID_ARGUMENT, "set_cell_share: no bound image");
     HIP_TRY(hipSetDevice(s->p->device));
     ColourTable &t = s->tab;
@@ -1120,6 +1153,7 @@ extern "C" int kmg_lloyd_labels_from_tables_update(kmg_lloyd *s, const uint8_t *
                                                    void *stream)
 try {
     if (!s || !d_rgba || !d_labels || !d_acc4 || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad labels_from_tables_update arguments");
+    if (s->weighted) return fail(KMG_ERR_INVALID_ARGUMENT, "labels_from_tables_update: the object's sums are weighted (kmg_lloyd_set_weighting): the colour table counts pixels");
     if (!s->tab.rgba || !s->tab.d_hist) return fail(KMG_ERR_INVALID_ARGUMENT, "labels_from_tables_update: no bound image");
     if (s->k > 256u) return fail(KMG_ERR_UNSUPPORTED, "labels_from_tables_update: k <= 256 (the label pass that carries a tail)");
     HIP_TRY(hipSetDevice(s->p->device));
@@ -1380,6 +1414,8 @@ extern "C" int kmg_lloyd_run(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, ui
                              uint32_t *iterations, void *stream)
 try {
     if (!s || !d_rgba || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad lloyd_run arguments");
+    if (s->weighted && n > kMaxWeightedPixels)
+        return fail(KMG_ERR_UNSUPPORTED, "weighted sums take at most 2^28 pixels (%llu given)", (unsigned long long)n);
     if (s->tab.d_work_share && table_bound(s, d_rgba, n))
         return fail(KMG_ERR_INVALID_ARGUMENT, "lloyd_run: a cell share is set (kmg_lloyd_set_cell_share): the loop would update from one share's sums");
     const kmg_options &o = s->p->opt;
@@ -1414,12 +1450,12 @@ try {
         s->tab.tables_valid = false;
         // operations.rs:75-83: the initial assignment
         PROF_LAUNCH(s, KMG_K_ASSIGN, st, launch_assign_loop(px, n, cur, alt, s->k, s->p->d_lut, d_labels, nullptr, acc3[0], acc3[1], 0,
-                                                          o.convergence, s->d_nconv, st));
+                                                          o.convergence, s->d_nconv, st, s->weighted));
         uint32_t it = 0;
         for (it = 0; it < o.max_iterations; ++it) {                   // modules.rs:769: update (:773-788), re-assign (:793-800)
             const uint32_t l = it + 1u;
             PROF_LAUNCH(s, KMG_K_ASSIGN, st, launch_assign_loop(px, n, cur, alt, s->k, s->p->d_lut, d_labels, acc3[(l + 2u) % 3u], acc3[l % 3u],
-                                                              acc3[(l + 1u) % 3u], 1, o.convergence, s->d_nconv, st));
+                                                              acc3[(l + 1u) % 3u], 1, o.convergence, s->d_nconv, st, s->weighted));
             std::swap(cur, alt);
             if (checked(it)) {                                       // :802
                 uint32_t conv = 0;

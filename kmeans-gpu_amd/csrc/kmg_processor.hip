@@ -315,6 +315,17 @@ try {
 }
 KMG_ABI_CATCH
 
+extern "C" int kmg_processor_set_weighting(kmg_processor *p, int weighting)
+try {
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
+    if (weighting != KMG_WEIGHT_NONE && weighting != KMG_WEIGHT_ALPHA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown weighting %d", weighting);
+    p->weighting.store(weighting);
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+int kmg::processor_weighting(kmg_processor *p) { return p->weighting.load(std::memory_order_relaxed); }
+
 uint32_t kmg::processor_fixed_count(kmg_processor *p) { return fixed_count(fixed_snapshot(p)); }
 
 extern "C" int kmg_processor_set_fixed_colors(kmg_processor *p, const uint8_t *rgba, uint32_t n)

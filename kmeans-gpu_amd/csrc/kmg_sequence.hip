@@ -304,7 +304,8 @@ int add_frame(kmg_sequence *s, const uint8_t *rgba, bool on_host, uint32_t w, ui
     if (w == 0 || h == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "image has zero width or height");
     if ((uint64_t)w * h > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
     HIP_TRY(hipSetDevice(p->device));
-    const uint32_t cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
+    // (alpha weighting, as it is now, cuts this frame's working pixels at max(alpha_cutoff, 1): kmg_processor_set_weighting)
+    const uint32_t cutoff = working_cutoff(p->alpha_cutoff.load(std::memory_order_relaxed), processor_weighting(p));
     uint32_t sw = w, sh = h;
     const uint32_t m = p->opt.shrink_max_dim;
     const bool shrink = m && (w > m || h > m);                         // structures.rs:67-74
@@ -356,10 +357,11 @@ int sequence_centroids(kmg_sequence *s, uint32_t k, float *c4)
     const std::shared_ptr<const std::vector<float>> fixed = fixed_snapshot(s->p);
     const uint32_t f = fixed_count(fixed);
     if (k < f) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u is below the %u fixed colours of the processor", k, f);
+    const int weighting = processor_weighting(s->p);                   // (as it is when this call starts)
     HIP_TRY(hipSetDevice(s->p->device));
     const bool as_image = s->frames == 1 && s->first_whole;
     return palette_of_working(s->p, (const uint8_t *)s->w_blk, as_image ? s->sw0 : (uint32_t)s->n, as_image ? s->sh0 : 1u, k, s->sg.st, c4,
-                              nullptr, f ? fixed->data() : nullptr, f);
+                              nullptr, f ? fixed->data() : nullptr, f, weighting);
 }
 
 }  // namespace
@@ -676,6 +678,7 @@ try {
     const uint32_t k = s->k;
     // alpha cutoff and fixed colours: as they are when this call starts
     const uint32_t cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
+    const int weighting = processor_weighting(p);
     const std::shared_ptr<const std::vector<float>> fixed = fixed_snapshot(p);
     const uint32_t f = fixed_count(fixed);
     const bool warm_output = (s->local_flags & KMG_LOCAL_WARM) != 0;
@@ -689,7 +692,7 @@ try {
     HIP_TRY(copy_host_image(p, s->d_frame, rgba, n * 4, hipMemcpyHostToDevice, st));
     std::vector<float> c4(4 * (size_t)k);
     if ((rc = local_frame_centroids(p, s->d_frame, s->width, s->height, k, cutoff, st, c4.data(), f ? fixed->data() : nullptr, f,
-                                    warm ? s->prev_c4.data() : nullptr)) != KMG_OK) {
+                                    warm ? s->prev_c4.data() : nullptr, weighting)) != KMG_OK) {
         (void)hipStreamSynchronize(st);
         return rc;
     }

@@ -66,6 +66,7 @@ struct kmg_processor {
     kmg_options opt;
     std::atomic<int> strategy{0};   // KMG_STRATEGY_* (kmg_options.strategy, kmg_processor_set_strategy)
     std::atomic<uint32_t> alpha_cutoff{0};   // kmg_options.alpha_cutoff, kmg_processor_set_alpha_cutoff (0 = alpha ignored)
+    std::atomic<int> weighting{0};  // KMG_WEIGHT_* (kmg_processor_set_weighting): the palette step's sums weigh a pixel by its alpha
     // kmg_processor_set_fixed_colors (mu): the pinned palette entries as Lab (kmg_palette_to_centroids of the caller's list, 4 floats
     // each), or null = none.  A call takes the pointer once when it starts and keeps that list to its end.
     std::shared_ptr<const std::vector<float>> fixed;
@@ -109,6 +110,11 @@ static inline std::shared_ptr<const std::vector<float>> fixed_snapshot(kmg_proce
     return p->fixed;
 }
 static inline uint32_t fixed_count(const std::shared_ptr<const std::vector<float>> &f) { return f ? (uint32_t)(f->size() / 4) : 0u; }
+
+// Alpha weighting (include/kmeans_hip.h at kmg_processor_set_weighting): the cutoff of the working image -- a pixel of weight 0
+// is never kept -- and the largest working image whose weighted int64 sums cannot overflow (|q| < 2^27, a < 2^8)
+static inline uint32_t working_cutoff(uint32_t alpha_cutoff, int weighting) { return weighting && alpha_cutoff == 0 ? 1u : alpha_cutoff; }
+constexpr uint64_t kMaxWeightedPixels = 1ull << 28;
 
 static inline size_t pad256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
 
@@ -175,6 +181,8 @@ struct kmg_lloyd {
     uint32_t last_rows;          // rows of d_partials written by the last assign pass
     bool init_colours;           // the running sharded init (kmg_lloyd_init_step) walks colours, not pixels
     uint32_t reserve_cus = 0;    // CUs the label pass leaves free (kmg_lloyd_reserve_cus)
+    bool weighted = false;       // kmg_lloyd_set_weighting(KMG_WEIGHT_ALPHA): every sum of this object weighs a pixel by its alpha byte;
+                                 // such an object never takes the colour-table route (its histogram counts pixels)
     uint32_t n_fixed = 0;        // host copy of d_nconv[kFixedWord]: centroids 0 .. n_fixed - 1 are left alone by every update and
                                  // count as converged (kmg_lloyd_set_fixed)
     bool pooled;                 // workspace came from the stream-ordered pool of `pool_stream` (internal per-call objects)

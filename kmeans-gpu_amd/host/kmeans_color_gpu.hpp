@@ -14,6 +14,7 @@
 //   processor.reduce_quality(image, max_delta_e, k_min, k_max, mode) -> the colour count chosen by a quality target
 //   processor.optimize_indexed(indexed[, flags, bits])     -> the palette without unused entries, ordered, and the map packed for it
 //   processor.set_fixed_colors(colors)                     -> palette entries the k-means keeps exactly and builds around
+//   processor.set_alpha_weight(on)                         -> the k-means palette weighs every pixel by its alpha byte
 //   Sequence seq(processor); seq.add(frame) ...; seq.output(k, mode, w, h); seq.frame(image) / seq.frame_lossy(image, delta_e)
 //                                                          -> one palette for many frames, exact and lossy delta frames (kmg_sequence_*)
 //   seq.begin_local(k, mode, w, h, warm); seq.frame_local(image) -> a palette per frame, colour-keyed delta frames
@@ -288,6 +289,15 @@ public:
         if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "a processor over several devices has no fixed colours");
         check(kmg_processor_set_fixed_colors(p_, colors.empty() ? nullptr : reinterpret_cast<const uint8_t *>(colors.data()),
                                              (uint32_t)colors.size()));
+    }
+
+    // kmg_processor_set_weighting (include/kmeans_hip.h): on = the k-means palette steps of the calls that start from now on weigh every
+    // pixel by its alpha byte (KMG_WEIGHT_ALPHA) and keep the pixels with alpha >= max(alpha_cutoff, 1); Algorithm::Octree is then an
+    // error.  off = every kept pixel weighs 1 (KMG_WEIGHT_NONE, the default).  A processor over several devices has no weighting.
+    void set_alpha_weight(bool on) const
+    {
+        if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "a processor over several devices has no alpha weighting");
+        check(kmg_processor_set_weighting(p_, on ? KMG_WEIGHT_ALPHA : KMG_WEIGHT_NONE));
     }
 
     kmg_processor *handle() const { return g_ ? kmg_group_processor(g_, 0) : p_; }

@@ -335,11 +335,11 @@ _lib = None
 # every symbol include/kmeans_hip.h declares
 SYMBOLS = [
     "kmg_last_error", "kmg_version", "kmg_host_alloc", "kmg_host_free", "kmg_default_options", "kmg_processor_create",
-    "kmg_processor_create_ex", "kmg_processor_destroy", "kmg_processor_set_strategy", "kmg_processor_set_alpha_cutoff", "kmg_processor_set_fixed_colors", "kmg_palette", "kmg_find", "kmg_reduce",
+    "kmg_processor_create_ex", "kmg_processor_destroy", "kmg_processor_set_strategy", "kmg_processor_set_alpha_cutoff", "kmg_processor_set_weighting", "kmg_processor_set_fixed_colors", "kmg_palette", "kmg_find", "kmg_reduce",
     "kmg_palette_to_centroids", "kmg_centroids_to_palette", "kmg_octree_palette", "kmg_dev_rgb_to_lab",
     "kmg_resized_dims", "kmg_dev_alpha_compact",
     "kmg_dev_resize", "kmg_lloyd_create", "kmg_lloyd_destroy", "kmg_lloyd_set_centroids",
-    "kmg_lloyd_get_centroids", "kmg_lloyd_init_centroids", "kmg_lloyd_init_centroids_seeded", "kmg_lloyd_set_fixed", "kmg_lloyd_init_step", "kmg_lloyd_init_pick_band",
+    "kmg_lloyd_get_centroids", "kmg_lloyd_init_centroids", "kmg_lloyd_init_centroids_seeded", "kmg_lloyd_set_fixed", "kmg_lloyd_set_weighting", "kmg_lloyd_init_step", "kmg_lloyd_init_pick_band",
     "kmg_lloyd_set_centroid_rgba", "kmg_init_first_key", "kmg_lloyd_assign_accumulate",
     "kmg_lloyd_assign_partials", "kmg_lloyd_reduce_partials", "kmg_lloyd_labels", "kmg_lloyd_reserve_cus", "kmg_lloyd_bind_image",
     "kmg_lloyd_unbind_image", "kmg_debug_bound_image", "kmg_lloyd_prepare", "kmg_debug_check_table", "kmg_debug_table_stats", "kmg_debug_check_pairs", "kmg_debug_check_dither_masks", "kmg_debug_check_meld_masks", "kmg_kernel_name",
@@ -464,6 +464,8 @@ def lib():
     L.kmg_processor_set_fixed_colors.argtypes = [vp, u8p, C.c_uint32]
     L.kmg_lloyd_init_centroids_seeded.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, f32p, C.c_uint32, vp]
     L.kmg_lloyd_set_fixed.argtypes = [vp, C.c_uint32]
+    L.kmg_processor_set_weighting.argtypes = [vp, C.c_int]
+    L.kmg_lloyd_set_weighting.argtypes = [vp, C.c_int]
     L.kmg_dev_alpha_compact.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, u8p, vp, vp]
     L.kmg_dev_compare.argtypes = [vp, u8p, vp, C.c_uint64, C.c_int, u8p, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.kmg_compare.argtypes = [vp, u8p, vp, C.c_uint32, C.c_uint32, C.c_int, u8p, C.c_uint32, C.c_uint32, C.POINTER(ErrorStats)]
@@ -590,6 +592,24 @@ def dither_threshold(centroids4):
     return t.value
 
 
+WEIGHT_NONE, WEIGHT_ALPHA = 0, 1        # include/kmeans_hip.h KMG_WEIGHT_*
+
+
+def with_weights(image, weights):
+    """A copy of `image` ((height, width, 4) uint8) whose alpha byte is `weights`, a (height, width) uint8 map: the importance-map
+    route of alpha weighting for opaque images -- ImageProcessor(alpha_weight=True) at alpha_cutoff = 0 then weighs every pixel by
+    its entry (0: the pixel does not shape the palette at all) and still writes alpha 255."""
+    img = _image(image)
+    w = np.asarray(weights)
+    if w.dtype != np.uint8:
+        raise ValueError("weights must be a uint8 map")
+    if w.shape != img.shape[:2]:
+        raise ValueError(f"weights of shape {w.shape} do not match the image's {img.shape[:2]}")
+    out = img.copy()
+    out[:, :, 3] = w
+    return out
+
+
 def _image(image):
     a = np.ascontiguousarray(image, dtype=np.uint8)
     if a.ndim != 3 or a.shape[2] != 4:
@@ -647,10 +667,11 @@ class ImageProcessor:
     """Mirror of `kmeans_color_gpu::ImageProcessor` (core/src/lib.rs:24-165)."""
 
     def __init__(self, device=-1, shrink_max_dim=256, max_iterations=128, check_period=8,
-                 convergence=1.0, strategy=None, alpha_cutoff=0, fixed_colors=None):
+                 convergence=1.0, strategy=None, alpha_cutoff=0, fixed_colors=None, alpha_weight=False):
         """alpha_cutoff: 0 = alpha ignored (the reference's behaviour); 1..255 = alpha mode (include/kmeans_hip.h at
         kmg_options): only pixels whose alpha is >= alpha_cutoff shape the palette, and the outputs keep the input's alpha.
-        fixed_colors: colours every k-means palette of this processor keeps, as its first entries (set_fixed_colors)"""
+        fixed_colors: colours every k-means palette of this processor keeps, as its first entries (set_fixed_colors)
+        alpha_weight: the k-means palettes weigh every pixel by its alpha byte (set_alpha_weight)"""
         self._h = C.c_void_p()
         o = default_options()
         o.device = device
@@ -664,8 +685,18 @@ class ImageProcessor:
         self.options = o
         self._sequences = None          # weak set of the live Sequence objects: closed with the processor, which they need
         _register(self)
+        self.alpha_weight = False
         if fixed_colors is not None:
             self.set_fixed_colors(fixed_colors)
+        if alpha_weight:
+            self.set_alpha_weight(True)
+
+    def set_alpha_weight(self, on):
+        """kmg_processor_set_weighting: True = the k-means palette steps of the calls that start from now on weigh every pixel by
+        its alpha byte and keep the pixels with alpha >= max(alpha_cutoff, 1) (include/kmeans_hip.h; with_weights makes an
+        importance map of an opaque image); False = every kept pixel weighs 1, the default"""
+        _check(lib().kmg_processor_set_weighting(self._h, WEIGHT_ALPHA if on else WEIGHT_NONE))
+        self.alpha_weight = bool(on)
 
     def set_fixed_colors(self, colors):
         """kmg_processor_set_fixed_colors: (n, 3) or (n, 4) uint8 colours (alpha ignored) that the k-means palettes of the
@@ -1213,6 +1244,10 @@ class Lloyd:
     def set_fixed(self, n_fixed):
         """kmg_lloyd_set_fixed: every update of this object leaves centroids 0 .. n_fixed - 1 alone and counts them as converged"""
         _check(lib().kmg_lloyd_set_fixed(self._h, int(n_fixed)))
+
+    def set_weighting(self, weighting):
+        """kmg_lloyd_set_weighting: WEIGHT_ALPHA (or True) = every later sum of this object weighs a pixel by its alpha byte"""
+        _check(lib().kmg_lloyd_set_weighting(self._h, int(weighting)))
 
     def init_step(self, d_rgba, n_local, first_index, j, d_key, stream=0):
         _check(lib().kmg_lloyd_init_step(self._h, C.c_void_p(d_rgba or None), n_local, first_index, j,

@@ -39,6 +39,13 @@ effect).
 palette keeps exactly, as its first entries in index order (the PLTE of `--indexed` and of `sequence`), while the other entries
 are placed around them (kmg_processor_set_fixed_colors).  `-c` counts them; k-means only.
 
+`palette`, `reduce` and `sequence` also take `--alpha-weight`: the k-means palette weighs every pixel by its alpha byte, so an
+anti-aliased edge at alpha 20 pulls a colour a twelfth as hard as a solid pixel, and pixels of alpha 0 not at all
+(kmg_processor_set_weighting; k-means only, not with --devices).  `--weights MAP.png` gives the weights as a greyscale image of the
+input's size instead -- an importance map for an opaque image: 255 where the colours matter most, 0 where they do not matter at
+all.  It implies --alpha-weight, replaces the input's alpha (the output is opaque) and is therefore refused together with a
+non-zero --alpha-cutoff; `sequence` applies the one map to every frame.
+
 Image decoding/encoding (the `image` crate in the reference) is done with Pillow.  One flag the reference does not have:
 `--devices 0,1,...` (before the sub-command) runs the same operation over several GPUs of the node (kmg_group_*: the image
 tiled in row bands, same bytes).
@@ -107,6 +114,15 @@ def validate_palette(s):                                 # args.rs:181-195
 def _load(path):
     from PIL import Image
     return np.array(Image.open(path).convert("RGBA"))      # image::open(..).to_rgba8()
+
+
+def _load_weights(path, width, height, ap):
+    """`--weights`: a greyscale map of the input's size as (height, width) uint8; anything else ends the command"""
+    from PIL import Image
+    w = np.array(Image.open(path).convert("L"))
+    if w.shape != (height, width):
+        ap.error(f"--weights: {path} is {w.shape[1]}x{w.shape[0]}, the input is {width}x{height}")
+    return w
 
 
 def _save(path, rgba):
@@ -193,7 +209,7 @@ def run_sequence_local(args, frames, w, h, out_path):
     # frame that is not a delta frame holds nothing: --lossy then has no effect
     delta = not (args.no_delta or args.alpha_cutoff)
     lossy = args.lossy if delta else None
-    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed) as proc, proc.sequence() as seq:
+    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed, alpha_weight=args.alpha_weight) as proc, proc.sequence() as seq:
         seq.output_local(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h, warm=args.warm)
         for i, f in enumerate(frames):
             index, colors, info, is_full = seq.frame_local(f, delta=delta, tolerance=lossy)
@@ -225,9 +241,13 @@ def run_sequence(args, ap):
         if f.shape[:2] != (h, w):
             ap.error(f"every input of `sequence` must have one size: {path} is {f.shape[1]}x{f.shape[0]}, {args.input[0]} is {w}x{h}")
     out_path = sequence_file_path(args.colorcount, args.mode, args.output, args.input[0], ".gif" if args.local else ".png")
+    if args.weights is not None:
+        from . import with_weights
+        weights = _load_weights(args.weights, w, h, ap)
+        frames = [with_weights(f, weights) for f in frames]
     if args.local:
         return run_sequence_local(args, frames, w, h, out_path)
-    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed) as proc, proc.sequence() as seq:
+    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed, alpha_weight=args.alpha_weight) as proc, proc.sequence() as seq:
         for f in frames:
             seq.add(f)
         colors = seq.output(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h)
@@ -366,6 +386,12 @@ def main(argv=None):
     for s in (p, r, q):
         s.add_argument("--fixed", type=validate_palette, default=None, metavar="COLORS",
                        help='"#RRGGBB,..." or a palette image: colours the k-means palette keeps exactly, as its first entries; -c counts them')
+    for s in (p, r, q):
+        s.add_argument("--alpha-weight", action="store_true",
+                       help="the k-means palette weighs every pixel by its alpha byte (pixels of alpha 0 do not shape it at all)")
+        s.add_argument("--weights", type=validate_filename, default=None, metavar="MAP",
+                       help="a greyscale image of the input's size: the weight of every pixel, in place of its alpha; implies "
+                            "--alpha-weight, not with a non-zero --alpha-cutoff")
     for s in (f, r):
         s.add_argument("--indexed", action="store_true",
                        help="write a palette-mode PNG (an index per pixel) instead of RGBA; at most 256 colours, 255 with --alpha-cutoff")
@@ -378,6 +404,15 @@ def main(argv=None):
                    help="choose the colour count: as few colours (at most -c) as keep the dE76 RMS of the shrunk image at or below DE; k-means only")
     r.add_argument("--min-colors", type=validate_k, default=None, metavar="A", help="lower bound of --max-error's search (default 2)")
     args = ap.parse_args(argv)
+    if getattr(args, "weights", None) is not None:
+        if args.alpha_cutoff:
+            ap.error("--weights replaces the input's alpha with the map: it cannot be combined with a non-zero --alpha-cutoff")
+        args.alpha_weight = True
+    if getattr(args, "alpha_weight", False):
+        if args.devices:
+            ap.error("--alpha-weight is not supported with --devices")
+        if getattr(args, "algo", "kmeans") != "kmeans":
+            ap.error("--alpha-weight weighs the sums of the k-means palette: -a octree has none")
     fixed = getattr(args, "fixed", None)
     if fixed is not None:
         if args.devices:
@@ -445,6 +480,9 @@ def main(argv=None):
             ap.error("--indexed writes a PNG file")
 
     image = _load(args.input)
+    if getattr(args, "weights", None) is not None:
+        from . import with_weights
+        image = with_weights(image, _load_weights(args.weights, image.shape[1], image.shape[0], ap))
     if args.devices:
         proc = Group(devices=args.devices)
     else:
@@ -453,6 +491,8 @@ def main(argv=None):
             options["alpha_cutoff"] = args.alpha_cutoff
         if fixed is not None:
             options["fixed_colors"] = fixed
+        if getattr(args, "alpha_weight", False):
+            options["alpha_weight"] = True
         proc = ImageProcessor(**options)
     with proc:
         if args.command == "palette":                    # main.rs:46-72

@@ -130,6 +130,7 @@ extern "C" {
     pub fn kmg_processor_set_strategy(p: *mut kmg_processor, strategy: c_int) -> c_int;
     pub fn kmg_processor_set_alpha_cutoff(p: *mut kmg_processor, alpha_cutoff: u32) -> c_int;
     pub fn kmg_processor_set_fixed_colors(p: *mut kmg_processor, rgba: *const u8, n: u32) -> c_int;
+    pub fn kmg_processor_set_weighting(p: *mut kmg_processor, weighting: c_int) -> c_int;
     // ImageProcessor::palette -- lib.rs:67-77
     pub fn kmg_palette(
         p: *mut kmg_processor,

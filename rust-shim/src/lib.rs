@@ -72,6 +72,17 @@ impl ImageProcessor {
         check(unsafe { ffi::kmg_processor_set_alpha_cutoff(self.raw, alpha_cutoff) })
     }
 
+    /// Alpha weighting (`kmg_processor_set_weighting`, include/kmeans_hip.h): `true` lets every k-means palette of the calls that
+    /// start from now on weigh a pixel by its alpha byte (pixels of alpha 0 do not shape it at all); `Algorithm::Octree` is then
+    /// an error.  `false`, the default, weighs every kept pixel 1.  No counterpart in the reference.  A processor over several
+    /// devices has none.
+    pub fn set_alpha_weight(&self, on: bool) -> Result<()> {
+        if !self.group.is_null() {
+            return Err(anyhow!("a processor over several devices has no alpha weighting"));
+        }
+        check(unsafe { ffi::kmg_processor_set_weighting(self.raw, if on { 1 } else { 0 }) })
+    }
+
     /// Fixed palette colours (`kmg_processor_set_fixed_colors`, include/kmeans_hip.h): every k-means palette of the calls that
     /// start from now on keeps `colors` exactly (alpha ignored), as entries `0..colors.len()` in index order, and places the
     /// others around them; an empty slice clears them.  `color_count` below the number of fixed colours and
