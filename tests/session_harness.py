@@ -21,6 +21,16 @@ per-pixel route, a new palette with repeated entries and a zero word per frame; 
 records and the bad-pixel count, which COMBINE across bands, images and the frames of a sequence, two plan slots, remaps at every
 width, kmg_index_optimize between the other calls.
 
+Surface 3 (generate(..., surface=3), seeds of its own; the lists of surfaces 1 and 2 are pinned by hash) adds alpha weighting, the
+one sticky switch with the most cross-talk: ("weight", 0|1) on the processor between all the calls above -- it moves the cutoff of
+a working image to max(t, 1) where the image is MADE (a host call, an add, a local frame, cold or warm), decides whether a loop is
+weighted where the loop STARTS (the palette call of a sequence, not its adds), and leaves every output's cutoff, the error record
+of reduce_quality and the initialisation alone; find, apply, compare, the canvases, usage, remap never look at it, and neither does
+the model there.  ("l_weight", L, 0|1) on a Lloyd object: weighted sums (weight_ref.accumulate on the alpha bytes of the image
+given), the same labels; the model tracks WHO holds the object's binding -- nobody, the initialisation (under the forced colour
+table), the caller -- because the setter drops the initialisation's and is refused under the caller's ("l_unbind" where the model
+cannot rule a caller's binding out).  One more image, the importance map: 53 x 67, every alpha in 1 .. 255.
+
   generate(seed, seq)  -> list of plain tuples (deterministic; a dry Model keeps every op legal or a listed refusal)
   Runner(env).run(ops) -> executes them on a backend, checks everything the op could have touched, raises Mismatch
   replay(env, seed, seq, ops) -> the same for a list printed by a failing run
@@ -39,7 +49,9 @@ What the generator never emits, because include/kmeans_hip.h leaves it open or b
     with indices above k or without a count (other than the refusals); a remap in place at another width than the map's own, a
     remap whose buffers overlap otherwise; kmg_index_optimize with bits below the plan's (other than the refusal) or above the map's
     width; the colour-keyed passes on buffers that overlap; a palette step whose working image is empty other than the frame of a
-    local output at the size of the image without a kept pixel.
+    local output at the size of the image without a kept pixel;
+  - (surface 3) kmg_lloyd_set_weighting where the model cannot tell whose binding the object holds (it unbinds first), a weighted
+    pass of more than 2^28 pixels (tests/test_gpu_weight.py), the group layer's refusal (the harness owns no group).
 The 1024 x 1024 image enters host calls and kmg_dev_compare only, and only under the forced colour-table strategy.  The images
 are this harness's own (make_images here): frames of one size in families, alpha bytes that fill every cutoff class, a frame above
 the shrink limit -- lifecycle_harness.make_images has none of these.  Every sequence mixes random ops with short directed passages
@@ -57,6 +69,7 @@ import hold_ref
 import index_ref
 import local_ref
 import sequence_ref
+import weight_ref
 import lifecycle_harness as LH
 from lifecycle_harness import Mismatch, GUARD, PATTERN, MAX_ITERATIONS, CHECK_PERIOD, gamut_centroids, make_centroids, sorted_palette
 
@@ -65,8 +78,8 @@ K_CLASSES = ((1, 2), (3, 32), (33, 255), (256, 256), (257, 512))
 CUTOFFS = (0, 1, 128, 255)
 STRATEGIES = (0, 1, 2)                               # auto, scan, table
 IMAGE_KINDS = ("odd", "odd_b", "sprite", "sprite_noisy", "sprite_shift", "few", "flat", "clear", "big", "mega", "row", "row_b", "col",
-               "col_b")
-ODD, SPRITE, FEW, FLAT, CLEAR, BIG, MEGA, ROW, COL = 0, 2, 5, 6, 7, 8, 9, 10, 12
+               "col_b", "map")
+ODD, SPRITE, FEW, FLAT, CLEAR, BIG, MEGA, ROW, COL, MAP = 0, 2, 5, 6, 7, 8, 9, 10, 12, 14
 FAMILIES = ((0, 1), (2, 3, 4), (10, 11), (12, 13))   # images of one size: the frames of one output
 ERR_INVALID = -1
 REFUSALS_1 = ("k_below_fixed_palette", "k_below_fixed_reduce", "k_below_fixed_sequence", "octree_fixed", "frame_no_output", "delta_on_rgba8",
@@ -75,6 +88,11 @@ REFUSALS_1 = ("k_below_fixed_palette", "k_below_fixed_reduce", "k_below_fixed_se
 REFUSALS_2 = ("shared_frame_on_local", "local_frame_on_shared", "local_frame_no_output", "warm_with_fixed", "local_tolerance_without_delta",
               "local_meld", "local_index8_k256", "plan_indices_above_k", "plan_empty_record", "optimize_bits_too_narrow", "remap_bad_bits")
 REFUSALS = REFUSALS_1 + REFUSALS_2
+# surface 3: alpha weighting (kmg_processor_set_weighting, kmg_lloyd_set_weighting)
+REFUSALS_3 = ("weight_bad_value", "l_weight_bad_value", "octree_weighted", "l_weight_under_caller_binding", "weighted_bind", "weighted_lftu",
+              "weighted_accumulate_into", "weighted_no_kept_pixel")
+MOTIFS_3 = ("weight_cutoff", "weight_adds", "weight_warm", "weight_binding", "weight_blocks", "weight_fixed", "weight_quality")
+LLOYD_IMAGE_OPS = ("l_init", "l_assign_update", "l_iterate", "l_run", "l_lftu", "l_assign", "l_bind")
 ERR_UNSUPPORTED = -5
 LOCAL_FAMILIES = FAMILIES + ((7,),)                  # a local output needs no added frame: also at the size of the frame without a kept pixel
 BITS = (1, 2, 4, 8, 16)
@@ -90,6 +108,7 @@ FIXED = (None,
 
 
 SURFACE_2_OPS = 120
+SURFACE_3_OPS = 70
 
 
 def k_class(k):
@@ -154,6 +173,12 @@ def _make_images(seed, seq):
     row_b[0, 5:9, 3], col_b[7:11, 0, 3] = 0, 0                    # a few pixels turn transparent
     out = [odd, _still(rng, odd, 1), sprite, _still(rng, sprite, 1), np.roll(sprite, (5, 9), (0, 1)), few, flat,
            np.zeros((30, 40, 4), np.uint8), _blobs(rng, 300, 200), _blobs(rng, 1024, 1024), row, row_b, col, col_b]
+    # an importance map (surface 3), from a stream of its own: 53 x 67 noise, every alpha byte in 1 .. 255 -- every pixel is kept at
+    # t <= 1, so the working image keeps its 2-D shape; the images above give the compacted, the uniform and the shrunk weights
+    rng3 = np.random.default_rng([seed, seq, 79])
+    wmap = rng3.integers(0, 256, (67, 53, 4), dtype=np.uint8)
+    wmap[..., 3] = rng3.integers(1, 256, (67, 53))
+    out.append(wmap)
     return [(k, np.ascontiguousarray(a)) for k, a in zip(IMAGE_KINDS, out)]
 
 
@@ -244,31 +269,47 @@ class Ref:
             return W, W.shape[0], 1
         return self._memo(("W", tuple(frames)), make)
 
-    def centroids_px(self, W, w, h, k, fid):
-        """the palette step on the working image W (w x h) with the fixed list `fid`: (k, 4) float32 in the Lloyd loop's order"""
+    def centroids_px(self, W, w, h, k, fid, wt=0):
+        """the palette step on the working image W (w x h) with the fixed list `fid`: (k, 4) float32 in the Lloyd loop's order;
+        wt: the loop is weighted by W's alpha bytes (weight_ref), the initialisation is not"""
         def make():
+            if wt:
+                return weight_ref.centroids_of_working(O, W, w, h, k, () if FIXED[fid] is None else np.array(FIXED[fid], np.uint8),
+                                                       max_iterations=MAX_ITERATIONS, check_period=CHECK_PERIOD)[0]
             if FIXED[fid] is None:
                 lab = O.rgb_to_lab(W)
                 return O.lloyd(lab, O.init_centroids(lab, w, h, k), MAX_ITERATIONS, CHECK_PERIOD)[0]
             return fixed_ref.palette_centroids(O, W, w, h, k, np.array(FIXED[fid], np.uint8), max_iterations=MAX_ITERATIONS,
                                                check_period=CHECK_PERIOD)[0]
-        return self._memo(("cent", hash(W.tobytes()), W.shape[0], w, h, k, fid), make)
+        return self._memo(("cent", hash(W.tobytes()), W.shape[0], w, h, k, fid) + (("weighted",) if wt else ()), make)
 
-    def centroids(self, frames, k, fid):
+    def centroids(self, frames, k, fid, wt=0):
         W, w, h = self.working(frames)
-        return self.centroids_px(W, w, h, k, fid)
+        return self.centroids_px(W, w, h, k, fid, wt)
 
     # -- Lloyd objects: passes over a whole image, every pixel counted
     def lab(self, i):
         return self._memo(("lab", i), lambda: O.rgb_to_lab(self.img(i).reshape(-1, 4)))
 
-    def assign(self, i, cent):
+    def q(self, i):
+        return self._memo(("q", i), lambda: weight_ref.pixel_q(O, self.lab(i)))
+
+    def alpha(self, i):
+        return self.img(i).reshape(-1, 4)[:, 3]
+
+    def assign(self, i, cent, wt=0):
+        """(labels, sums) of one pass over image i; wt: the sums weigh every pixel by its alpha byte, the labels are the same"""
         def make():
             labels = O.assign(self.lab(i), cent)
+            if wt:
+                return labels, weight_ref.accumulate(self.q(i), self.alpha(i), labels, cent.shape[0])
             return labels, O.accumulate(self.lab(i), labels, cent.shape[0])
-        return self._memo(("assign", i, cent.tobytes()), make)
+        return self._memo(("assign", i, cent.tobytes()) + (("weighted",) if wt else ()), make)
 
-    def run(self, i, cent, f):
+    def run(self, i, cent, f, wt=0):
+        if wt:
+            return self._memo(("run", i, cent.tobytes(), f, "weighted"),
+                              lambda: weight_ref.lloyd(O, self.lab(i), self.alpha(i), cent, f, MAX_ITERATIONS, CHECK_PERIOD))
         return self._memo(("run", i, cent.tobytes(), f), lambda: fixed_ref.lloyd(O, self.lab(i), cent, f, MAX_ITERATIONS, CHECK_PERIOD))
 
     def seeded(self, i, k, f):
@@ -301,18 +342,19 @@ class Ref:
     def palette_bytes(self, cent):
         return O.lab_to_rgba8(np.ascontiguousarray(cent[:, :3]))
 
-    def quality(self, i, t, fid, target, k_min, k_max):
-        """(k*, reached, record of W at k*) of kmg_reduce_quality's search"""
+    def quality(self, i, t, fid, target, k_min, k_max, wt=0):
+        """(k*, reached, record of W at k*) of kmg_reduce_quality's search; t: the cutoff of the working image; wt: the palettes
+        are weighted, the record is the unweighted one as ever"""
         def make():
             W, _, _ = self.working(((i, t),))
             lab = O.rgb_to_lab(W)
 
             def record(k):
-                cent = self.centroids(((i, t),), k, fid)
+                cent = self.centroids(((i, t),), k, fid, wt)
                 return error_ref.stats(O, W, O.assign(lab, cent), palette=self.palette_bytes(cent))
             k, reached, _ = error_ref.bisect(lambda kk: record(kk)[12] <= target * W.shape[0], k_min, k_max)
             return k, reached, record(k)
-        return self._memo(("quality", i, t, fid, target, k_min, k_max), make)
+        return self._memo(("quality", i, t, fid, target, k_min, k_max) + (("weighted",) if wt else ()), make)
 
     def stats(self, src, out, palette, cutoff, what):
         pal = None if palette is None else np.ascontiguousarray(palette, np.uint8)
@@ -322,8 +364,15 @@ class Ref:
     def find_centroids(self, pal):
         return fixed_ref.pins_lab(O, pal)
 
-    def warm(self, i, t, prev):
+    def warm(self, i, t, prev, wt=0):
         """C_t of a warm frame: the Lloyd loop on the working image of image i under cutoff t, from all k of `prev`"""
+        if wt:
+            def make():
+                warm4 = np.ones((prev.shape[0], 4), np.float32)
+                warm4[:, :3] = np.asarray(prev, np.float32)[:, :3]
+                return weight_ref.centroids_of_working(O, self.kept(i, t)[0], 0, 0, prev.shape[0], warm4=warm4, max_iterations=MAX_ITERATIONS,
+                                                       check_period=CHECK_PERIOD)[0]
+            return self._memo(("warm", i, t, prev.tobytes(), "weighted"), make)
         return self._memo(("warm", i, t, prev.tobytes()),
                           lambda: local_ref.warm_centroids(O, self.kept(i, t)[0], prev, MAX_ITERATIONS, CHECK_PERIOD)[0])
 
@@ -369,11 +418,16 @@ class LSlot:
         self.nconv = None
         self.acc = None
         self.bind = None          # image index the object may be bound to
+        self.w = 0                # kmg_lloyd_set_weighting
+        # who holds the binding, where the model knows: None (nobody, or the library at most), "init" (the initialisation, under the
+        # forced colour table), "caller" (kmg_lloyd_bind_image), "unsure" (the caller's, unless a later call of the library re-bound)
+        self.owner = None
 
 
 class SSlot:
     def __init__(self):
-        self.frames = []          # (image, cutoff at the add)
+        self.frames = []          # (image, cutoff at the add): max(t, 1) when weighting was on at the add
+        self.wadd = []            # the weighting at each add (coverage only: the cutoff above is all an add keeps of it)
         self.out = None           # dict(t, k, cent, mode, fmt, fam, canvas, held, last)
 
 
@@ -382,6 +436,7 @@ class Model:
         self.images, self.numeric = images, numeric
         self.ref = Ref(images, cache)
         self.t, self.fid, self.strategy = 0, 0, 0
+        self.w = 0                    # kmg_processor_set_weighting
         self.lloyd = [None, None]
         self.seq = [None, None]
         self.pairs = [None, None]     # dict(fam, fmt, k, seed, mode, canvas, held, last)
@@ -395,6 +450,10 @@ class Model:
         """kept pixels of image i (before the shrink: the large images keep an opaque disc whatever the shrink does to its edge)"""
         a = self.images[i][1]
         return int((a[..., 3] >= t).sum()) if t else a.shape[0] * a.shape[1]
+
+    def wc(self):
+        """the cutoff of a working image made now: a pixel of weight 0 is never kept"""
+        return max(self.t, 1) if self.w else self.t
 
     def seq_pixels(self, S):
         return sum(min(self.n_kept(i, t), 65536) for i, t in self.seq[S].frames)
@@ -411,10 +470,11 @@ def lloyd_step(s, sums):
 # ---- the generator --------------------------------------------------------------------------------------------------
 def generate(seed, seq, n_ops=None, surface=1):
     """one sequence: a list of plain tuples.  surface 1: the calls up to the lossy delta frames, 150 ops; surface 2: those plus
-    per-frame palettes, colour-keyed canvases and the index-map optimisation (SURFACE_2_OPS ops).  A surface-1 list never changes:
-    tests/test_session_model.py pins its hash"""
-    n_ops = (150 if surface == 1 else SURFACE_2_OPS) if n_ops is None else n_ops
-    refusals = REFUSALS_1 if surface == 1 else REFUSALS
+    per-frame palettes, colour-keyed canvases and the index-map optimisation (SURFACE_2_OPS ops); surface 3: those plus alpha
+    weighting on the processor and on the Lloyd objects (SURFACE_3_OPS random ops, then the motifs).  The lists of surfaces 1 and 2
+    never change: tests/test_session_model.py pins their hashes"""
+    n_ops = {1: 150, 2: SURFACE_2_OPS, 3: SURFACE_3_OPS}[surface] if n_ops is None else n_ops
+    refusals = {1: REFUSALS_1, 2: REFUSALS, 3: REFUSALS + REFUSALS_3}[surface]
     rng = np.random.default_rng([seed, seq, 3] if surface == 1 else [seed, seq, 3, surface])
     images = make_images(seed, seq)
     m = Model(images, numeric=False)
@@ -451,10 +511,10 @@ def generate(seed, seq, n_ops=None, surface=1):
 
     def host_image():
         """an image for a host call: kept pixels under the current cutoff, the 2^20 one only under the forced colour table"""
-        pool = [ODD, SPRITE, 4, FEW, FLAT, BIG, ROW, COL] + ([MEGA] if m.strategy == 2 else [])
+        pool = [ODD, SPRITE, 4, FEW, FLAT, BIG, ROW, COL] + ([MEGA] if m.strategy == 2 else []) + ([MAP, MAP] if surface == 3 else [])
         for _ in range(20):
             i = pick(pool)
-            if m.n_kept(i, m.t) > 0:
+            if m.n_kept(i, m.wc()) > 0:
                 return i
         return FLAT
 
@@ -466,6 +526,11 @@ def generate(seed, seq, n_ops=None, surface=1):
         return None if hi < max(f, 1) else pick_k(lo=max(f, 1), hi=hi)
 
     def switches():
+        if surface == 3 and rng.random() < 0.35:          # the weighting, and a palette step that sees it
+            emit(("weight", 1 - m.w))
+            if rng.random() < 0.6:
+                emit(("palette", pick([SPRITE, MAP, ODD]), n_fixed_of(m.fid) + rint(1, 7)))
+            return
         c = rng.random()
         if c < 0.45:
             emit(("cutoff", pick([x for x in CUTOFFS if x != m.t])))
@@ -551,6 +616,8 @@ def generate(seed, seq, n_ops=None, surface=1):
         if s is None:
             emit(("l_new", L, pick_k()))
             return
+        if surface == 3 and rng.random() < 0.22:
+            return l_weight_ops(L)
         c = rng.random()
         if c < 0.04:
             emit(("l_close", L))
@@ -561,7 +628,7 @@ def generate(seed, seq, n_ops=None, surface=1):
                 emit(("l_set", L, "rand", rint(0, 1 << 30), ODD))
                 emit(("l_assign_update", L, pick([ODD, FEW, ROW]), 1, 1, st()))
             return
-        i = pick([ODD, SPRITE, FEW, FLAT, BIG, ROW])
+        i = pick([ODD, SPRITE, FEW, FLAT, BIG, ROW] + ([MAP] if surface == 3 else []))
         n = images[i][1].shape[0] * images[i][1].shape[1]
         if s.cent is None or c < 0.24:
             if n * s.k <= 300000 and rng.random() < 0.7:
@@ -583,12 +650,19 @@ def generate(seed, seq, n_ops=None, surface=1):
             emit(("l_assign_update", L, i, rint(0, 2), rint(0, 2), st()))
         elif c < 0.7:
             if rng.random() < 0.5:
-                emit(("l_bind", L, i, st()))
+                if not s.w:
+                    emit(("l_bind", L, i, st()))
+                elif s.k <= 256:
+                    emit(("refuse", "weighted_bind", L, i))
             emit(("l_iterate", L, i, rint(1, 4), st()))
         elif c < 0.82:
             emit(("l_run", L, i, rint(0, 2), st()))
         elif c < 0.92 and s.k <= 256:
-            emit(("l_lftu", L, i, st()))
+            if s.w:                                       # a weighted object has no colour-table route
+                emit(("refuse", pick(["weighted_lftu", "weighted_accumulate_into"]), L, i))
+                emit(("l_assign", L, i, st()))
+            else:
+                emit(("l_lftu", L, i, st()))
         else:
             emit(("l_assign", L, i, st()))
         if m.lloyd[L].nconv is not None and rng.random() < 0.3:
@@ -688,6 +762,8 @@ def generate(seed, seq, n_ops=None, surface=1):
         what = pick(list(refusals)) if what is None else what
         if what in REFUSALS_2:
             return refusal_2(what)
+        if what in REFUSALS_3:
+            return refusal_3(what)
         f = n_fixed_of(m.fid)
         if what.startswith("k_below_fixed") or what == "octree_fixed":
             if f < 2:
@@ -862,9 +938,12 @@ def generate(seed, seq, n_ops=None, surface=1):
     def motif_refusals():
         for j in rng.permutation(len(REFUSALS_1))[:3]:
             refusal(REFUSALS_1[int(j)])
-        if surface == 2:
+        if surface >= 2:
             for j in rng.permutation(len(REFUSALS_2))[:4]:
                 refusal(REFUSALS_2[int(j)])
+        if surface == 3:
+            for j in rng.permutation(len(REFUSALS_3))[:4]:
+                refusal(REFUSALS_3[int(j)])
 
 
     # ---- surface 2: per-frame palettes, colour-keyed canvases, index-map optimisation -------------------------------------
@@ -1193,10 +1272,252 @@ def generate(seed, seq, n_ops=None, surface=1):
             emit(("cpair_open", P, 1, fmt, rint(5, 40), offs))
             cpair_ops(P, 4)
 
+    # ---- surface 3: alpha weighting -----------------------------------------------------------------------------------------
+    def set_weight(v):
+        if m.w != v:
+            emit(("weight", v))
+
+    def need_lloyd(hi=64):
+        """a Lloyd slot whose object exists and has centroids"""
+        L = rint(0, 2)
+        if m.lloyd[L] is None:
+            emit(("l_new", L, pick_k(hi=hi)))
+        if m.lloyd[L].cent is None:
+            emit(("l_set", L, "rand", rint(0, 1 << 30), ODD))
+        return L
+
+    def make_settable(L):
+        """the setter is refused under a caller's binding: unbind first where the model knows of one or cannot rule it out"""
+        if m.lloyd[L].owner in ("caller", "unsure"):
+            emit(("l_unbind", L))
+
+    def l_weight_ops(L):
+        s = m.lloyd[L]
+        if s.owner == "caller" and rng.random() < 0.5:
+            emit(("refuse", "l_weight_under_caller_binding", L, rint(0, 2)))
+        make_settable(L)
+        emit(("l_weight", L, 1 - s.w if rng.random() < 0.8 else s.w))
+        if s.cent is not None:
+            i = pick([ODD, SPRITE, FEW, ROW, MAP, MAP])
+            emit(pick([("l_assign_update", L, i, rint(0, 2), rint(0, 2), st()), ("l_run", L, i, rint(0, 2), st()), ("l_iterate", L, i, rint(1, 3), st()),
+                       ("l_assign", L, i, st())]))
+
+    def refusal_3(what):
+        f = n_fixed_of(m.fid)
+        if what == "weight_bad_value":                        # the old value stays in force: mostly weighting on, which a reset would show
+            if rng.random() < 0.7:
+                set_weight(1)
+            emit(("refuse", what, pick([2, -1, 255])))
+            emit(("palette", pick([SPRITE, MAP]), f + rint(2, 6)))
+        elif what == "octree_weighted":                       # no fixed colours: the weighting is the only cause (octree_fixed is the other)
+            if m.fid:
+                emit(("fixed", 0))
+            set_weight(1)
+            k = rint(2, 12)
+            for variant in rng.permutation(3):                # palette, reduce (nothing written), reduce_indexed
+                emit(("refuse", what, SPRITE, k, int(variant)))
+            emit(("palette", SPRITE, rint(2, 6)))
+        elif what == "weighted_no_kept_pixel":                # no fixed colours either: k below them is refused before the image is looked at
+            t0 = m.t
+            if m.fid:
+                emit(("fixed", 0))
+            restore_cutoff(0)
+            set_weight(1)
+            for variant in rng.permutation(3):
+                emit(("refuse", what, int(variant)))
+            emit(("palette", FLAT, 2))
+            restore_cutoff(t0)
+        elif what == "l_weight_bad_value":
+            L = need_lloyd()
+            emit(("refuse", what, L, pick([2, -1])))
+            emit(("l_assign", L, pick([ODD, MAP]), st()))
+        elif what == "l_weight_under_caller_binding":
+            L = need_lloyd()
+            if m.lloyd[L].w:
+                emit(("l_weight", L, 0))
+            emit(("l_bind", L, ODD, st()))
+            emit(("refuse", what, L, rint(0, 2)))
+            emit(("l_assign", L, ODD, st()))                  # still unweighted, still bound
+        else:
+            L = need_lloyd(hi=64)
+            if m.lloyd[L].k > 256:
+                emit(("l_re", L, pick_k(hi=64)))
+                emit(("l_set", L, "rand", rint(0, 1 << 30), ODD))
+            if not m.lloyd[L].w:
+                make_settable(L)
+                emit(("l_weight", L, 1))
+            i = pick([ODD, MAP])
+            emit(("refuse", what, L, i))
+            emit(("l_assign_update", L, i, 1, 1, st()))
+
+    def motif_weight_cutoff():
+        """weight on / cutoff 0 -> 128 -> 0 / weight off around the same palette + reduce_indexed + reduce: the first and the last
+        results are the default path's; INDEX8 at k = 256 is legal at t = 0 under weighting"""
+        emit(("motif", "weight_cutoff"))
+        t0, w0 = m.t, m.w
+        if m.fid:
+            emit(("fixed", 0))
+        i, k = pick([ODD, SPRITE]), rint(2, 10)
+        at = [("palette", i, k), ("reduce_indexed", i, k, pick([0, 1, 3]), 1), ("reduce", i, k, rint(0, 4))]
+        restore_cutoff(0)
+        set_weight(0)
+        for op in at:
+            emit(op)
+        emit(("weight", 1))
+        for t in (0, 128, 0):
+            restore_cutoff(t)
+            for op in at:
+                emit(op)
+        emit(("reduce_indexed", FEW, 256, 0, 0))
+        emit(("weight", 0))
+        for op in at:
+            emit(op)
+        restore_cutoff(t0)
+        set_weight(w0)
+
+    def motif_weight_adds():
+        """two frames added with the switch differing between the adds, the palette taken with the switch both ways"""
+        emit(("motif", "weight_adds"))
+        S, t0, w0 = rint(0, 2), m.t, m.w
+        if m.fid == 3:
+            emit(("fixed", 0))
+        emit(("s_new", S) if m.seq[S] is None else ("s_clear", S))
+        restore_cutoff(0)
+        first = rint(0, 2)
+        set_weight(first)
+        emit(("s_add", S, pick([SPRITE, ODD]), rint(0, 2), st()))
+        emit(("weight", 1 - first))
+        emit(("s_add", S, pick([4, 1, MAP]), rint(0, 2), st()))
+        emit(("s_info", S))
+        k = n_fixed_of(m.fid) + rint(2, 8)
+        emit(("s_centroids", S, k))
+        emit(("weight", first))
+        emit(("s_palette", S, k))
+        emit(("s_centroids", S, k))
+        restore_cutoff(t0)
+        set_weight(w0)
+
+    def motif_weight_warm():
+        """a warm local output whose frames alternate weighted and unweighted, across a cutoff switch"""
+        emit(("motif", "weight_warm"))
+        S, t0, w0 = rint(0, 2), m.t, m.w
+        fam = pick([0, 1])
+        F = LOCAL_FAMILIES[fam]
+        open_local(S, fam=fam, k=rint(3, 16), warm=1)
+        set_weight(1)
+        frame_local(S, F[0])
+        emit(("weight", 0))
+        frame_local(S, F[1], 1, pick([None, 40]))
+        emit(("cutoff", pick([x for x in CUTOFFS if x != m.t])))
+        emit(("weight", 1))
+        frame_local(S, F[-1])
+        emit(("weight", 0))
+        frame_local(S, F[0], 1, pick([None, 4096]))
+        emit(("weight", 1))
+        frame_local(S, F[1])
+        restore_cutoff(t0)
+        set_weight(w0)
+
+    def motif_weight_binding():
+        """an initialisation under the forced colour table leaves its binding; weight 1, run, weight 0, assign_update: the last call
+        is unweighted and right.  Then the same with the caller's binding in between, and the setter's refusal"""
+        emit(("motif", "weight_binding"))
+        L, s0 = rint(0, 2), m.strategy
+        if m.strategy != 2:
+            emit(("strategy", 2))
+        emit(("l_new" if m.lloyd[L] is None else "l_re", L, rint(4, 13)))
+        i = pick([ODD, SPRITE, MAP])
+        emit(("l_init", L, i, 0, st()))
+        emit(("l_weight", L, 1))
+        emit(("l_run", L, i, 1, st()))
+        emit(("l_weight", L, 0))
+        emit(("l_assign_update", L, i, 1, 1, st()))
+        emit(("l_init", L, i, pick([0, 1]), st()))
+        emit(("l_weight", L, 1))                              # (the binding of the initialisation: dropped by the setter)
+        emit(("l_assign", L, i, st()))
+        emit(("l_weight", L, 0))
+        emit(("l_init", L, i, 0, st()))
+        emit(("l_weight", L, 0))                              # (no change: the binding of the initialisation stays)
+        emit(("l_assign", L, i, st()))
+        emit(("l_bind", L, i, st()))
+        emit(("refuse", "l_weight_under_caller_binding", L, 1))
+        emit(("l_assign", L, i, st()))
+        emit(("refuse", "l_weight_under_caller_binding", L, 0))
+        emit(("l_unbind", L))
+        emit(("l_weight", L, 1))
+        emit(("refuse", "weighted_bind", L, i))
+        emit(("l_run", L, i, 1, st()))
+        emit(("l_weight", L, 0))
+        emit(("l_assign_update", L, i, 1, 1, st()))
+        if m.strategy != s0:
+            emit(("strategy", s0))
+
+    def motif_weight_blocks():
+        """a weighted Lloyd object closed and an unweighted one created in its block, and the reverse, beside host calls under the
+        opposite processor weighting: neither the object's nor the library's own object leaks its weighting"""
+        emit(("motif", "weight_blocks"))
+        w0 = m.w
+        for first in (1, 0):
+            L = rint(0, 2)
+            emit(("l_new" if m.lloyd[L] is None else "l_re", L, rint(3, 40)))
+            emit(("l_set", L, "rand", rint(0, 1 << 30), ODD))
+            emit(("l_weight", L, first))
+            emit(("l_assign_update", L, pick([ODD, MAP]), 1, 1, st()))
+            set_weight(1 - first)
+            emit(("palette", SPRITE, n_fixed_of(m.fid) + rint(2, 8)))
+            emit(("l_close", L))
+            emit(("l_new", L, rint(3, 40)))
+            emit(("l_set", L, "rand", rint(0, 1 << 30), ODD))
+            if not first:
+                emit(("l_weight", L, 1))
+            emit(("l_assign_update", L, pick([ODD, MAP]), 1, 1, st()))
+            emit(("reduce_indexed", pick([SPRITE, MAP]), n_fixed_of(m.fid) + rint(2, 8), 0, 0))
+        set_weight(w0)
+
+    def motif_weight_fixed():
+        """fixed colours and weighting: a pinned entry stays put whatever its members weigh and counts as converged; a free cluster
+        of total weight 0 is an empty cluster"""
+        emit(("motif", "weight_fixed"))
+        w0 = m.w
+        emit(("fixed", pick([2, 3])))
+        f = n_fixed_of(m.fid)
+        set_weight(1)
+        emit(("palette", SPRITE, f + rint(1, 5)))
+        if m.n_kept(ROW, m.wc()):
+            emit(("reduce_indexed", ROW, f + rint(1, 4), 0, 0))
+        L = rint(0, 2)
+        emit(("l_new" if m.lloyd[L] is None else "l_re", L, rint(40, 80)))
+        emit(("l_init", L, ROW, 3, st()))
+        emit(("l_fix", L, 3))
+        emit(("l_weight", L, 1))
+        emit(("l_assign_update", L, ROW, 1, 1, st()))
+        emit(("l_conv", L, st()))
+        emit(("l_run", L, COL, 1, st()))
+        emit(("l_iterate", L, ROW, 2, st()))
+        emit(("l_conv", L, st()))
+        emit(("fixed", 0))
+        set_weight(w0)
+
+    def motif_weight_quality():
+        """the quality search with weighting on, then off, on the sprite: both records unweighted, the palettes differ"""
+        emit(("motif", "weight_quality"))
+        w0 = m.w
+        if m.fid:
+            emit(("fixed", 0))
+        args = (SPRITE, pick([4.0, 9.0]), 2, 12, pick([0, 1, 3]), rint(0, 2), 0)
+        set_weight(1)
+        emit(("quality",) + args)
+        emit(("weight", 0))
+        emit(("quality",) + args)
+        set_weight(w0)
+
     motifs = [mo for mo in (motif_mixed, motif_refusals, motif_cutoff, motif_reoutput, motif_anchor, motif_growth, motif_first_frame, motif_freeze, motif_pins) if rng.random() < 0.75]
-    if surface == 2:
+    if surface >= 2:
         motifs += [mo for mo in (motif_warm_cutoff, motif_refused_warm, motif_used_block, motif_lossy_full, motif_local_shared_local,
                                  motif_optimize_path, motif_records, motif_cpair) if rng.random() < 0.8]
+    if surface == 3:
+        motifs += [mo for mo in (motif_weight_cutoff, motif_weight_adds, motif_weight_warm, motif_weight_binding, motif_weight_blocks,
+                                 motif_weight_fixed, motif_weight_quality) if rng.random() < 0.8]
     at = sorted(rint(3, n_ops - 5) for _ in motifs)
     motifs = [motifs[int(j)] for j in rng.permutation(len(motifs))]
     emit(("strategy", pick([2, 0, 1], [0.5, 0.3, 0.2])))
@@ -1205,7 +1526,7 @@ def generate(seed, seq, n_ops=None, surface=1):
             at.pop(0)
             motifs.pop(0)()
             continue
-        if surface == 2 and rng.random() < 0.4:
+        if surface >= 2 and rng.random() < 0.4:
             surface_2_ops()
             continue
         r = rng.random()
@@ -1227,6 +1548,8 @@ def generate(seed, seq, n_ops=None, surface=1):
     for S in range(2):
         if m.seq[S] is not None:
             emit(("s_close", S))
+    if m.w:
+        emit(("weight", 0))
     return ops
 
 
@@ -1241,11 +1564,16 @@ def apply_op(m, op):
         m.fid = op[1]
     elif name == "strategy":
         m.strategy = op[1]
+    elif name == "weight":
+        assert op[1] in (0, 1), op
+        m.w = op[1]
+    elif name == "motif":
+        assert op[1] in MOTIFS_3, op
     elif name in ("palette", "reduce", "reduce_indexed"):
         i, k = op[1], op[2]
-        assert k >= n_fixed_of(m.fid) and m.n_kept(i, m.t) > 0, op
+        assert k >= n_fixed_of(m.fid) and m.n_kept(i, m.wc()) > 0, op
         if num:
-            cent = R.centroids(((i, m.t),), k, m.fid)
+            cent = R.centroids(((i, m.wc()),), k, m.fid, m.w)               # (the outputs below: their cutoff stays t)
             if name == "palette":
                 exp["palette"] = sorted_palette(cent)
             elif name == "reduce":
@@ -1267,8 +1595,8 @@ def apply_op(m, op):
         i, dE, k_min, k_max, mode, indexed = op[1:7]
         assert k_min >= n_fixed_of(m.fid), op
         if num:
-            k, reached, rec = R.quality(i, m.t, m.fid, target_of(dE), k_min, k_max)
-            cent = R.centroids(((i, m.t),), k, m.fid)
+            k, reached, rec = R.quality(i, m.wc(), m.fid, target_of(dE), k_min, k_max, m.w)
+            cent = R.centroids(((i, m.wc()),), k, m.fid, m.w)
             exp.update(k=k, reached=reached, stats=rec, palette=R.palette_bytes(cent))
             exp["out"] = R.index(R.img(i), cent, mode, m.t) if indexed else R.rgba(R.img(i), cent, mode, m.t)
     elif name in ("apply", "apply_plan"):
@@ -1319,7 +1647,7 @@ def apply_op(m, op):
             exp.update(delta=d, canvas=pr["canvas"], held=pr["held"], record=tuple(rec))
         pr["last"] = "exact" if tol is None else "lossy"
     elif name in ("l_new", "l_re"):
-        m.lloyd[op[1]] = LSlot(op[2])
+        m.lloyd[op[1]] = LSlot(op[2])                         # (unweighted and unbound, whatever its block's last owner was)
         if num:
             m.lloyd[op[1]].acc = np.zeros((op[2], 4), np.int64)
     elif name == "l_close":
@@ -1327,6 +1655,9 @@ def apply_op(m, op):
     elif name.startswith("l_"):
         s = m.lloyd[op[1]]
         assert s is not None, op
+        if name in LLOYD_IMAGE_OPS and s.bind is not None and s.bind != op[2]:
+            exp["unbind"] = True                              # (whether a pass on other pixels re-binds is the cost model's)
+            s.bind = s.owner = None
         if name == "l_set":
             s.cent = make_centroids(op[2], op[3], s.k, m.images[op[4]][1]) if num else True
         elif name == "l_init":
@@ -1335,6 +1666,7 @@ def apply_op(m, op):
             h, w = m.images[i][1].shape[:2]
             forced = {0: 0, 1: -1, 2: 1}[m.strategy]
             s.bind = None if (s.k == 1 or forced < 0) else i
+            s.owner = "init" if forced > 0 and s.k > 1 else "unsure" if s.owner in ("caller", "unsure") else None
             s.nconv = None
             s.cent = R.seeded(i, s.k, f) if num else True
             exp["cent"] = s.cent
@@ -1342,7 +1674,16 @@ def apply_op(m, op):
             assert op[2] <= s.k
             s.f = op[2]
         elif name == "l_bind":
-            s.bind = op[2]
+            assert not s.w, op
+            s.bind, s.owner = op[2], "caller"
+        elif name == "l_unbind":
+            s.bind = s.owner = None
+        elif name == "l_weight":
+            assert op[2] in (0, 1) and s.owner in (None, "init"), op
+            exp["owner"] = s.owner
+            if op[2] != s.w:                                  # a binding the initialisation left ends here, in both directions
+                s.bind = s.owner = None
+            s.w = op[2]
         elif name == "l_conv":
             assert s.nconv is not None
             exp["nconv"] = s.nconv
@@ -1356,10 +1697,12 @@ def apply_op(m, op):
                     s.nconv = True
             elif name == "l_assign":
                 if num:
-                    exp["labels"], s.acc = R.assign(op[2], s.cent)
+                    exp["cent_before"] = s.cent
+                    exp["labels"], s.acc = R.assign(op[2], s.cent, s.w)
             elif name == "l_assign_update":
                 if num:
-                    labels, s.acc = R.assign(op[2], s.cent)
+                    exp["cent_before"] = s.cent
+                    labels, s.acc = R.assign(op[2], s.cent, s.w)
                     if op[3]:
                         exp["labels"] = labels
                     if op[4]:
@@ -1371,20 +1714,22 @@ def apply_op(m, op):
                 if num:
                     for _ in range(op[3]):
                         lloyd_step(s, s.acc)
-                        labels, s.acc = R.assign(op[2], s.cent)
+                        labels, s.acc = R.assign(op[2], s.cent, s.w)
                     exp.update(labels=labels, cent=s.cent)
                 s.nconv = s.nconv if num else True
             elif name == "l_run":
                 if num:
-                    s.cent, labels, it = R.run(op[2], s.cent, s.f)
+                    s.cent, labels, it = R.run(op[2], s.cent, s.f, s.w)
                     exp.update(cent=s.cent, iterations=it)
                     if op[3]:
                         exp["labels"] = labels
                 s.nconv = None
+                # a caller's binding of these pixels is trusted and stays; any other one is (re)made and dropped by the run
+                s.owner = "caller" if s.owner == "caller" and s.bind == op[2] else "unsure" if s.owner in ("caller", "unsure") else None
                 s.bind = None
             elif name == "l_lftu":
-                assert s.k <= 256
-                s.bind = op[2]
+                assert s.k <= 256 and not s.w, op
+                s.bind, s.owner = op[2], "caller"
                 if num:
                     exp["labels"], sums = R.assign(op[2], s.cent)
                     lloyd_step(s, sums)
@@ -1403,16 +1748,17 @@ def apply_op(m, op):
         q = m.seq[op[1]]
         assert q is not None, op
         if name == "s_add":
-            q.frames.append((op[2], m.t))
+            q.frames.append((op[2], m.wc()))
+            q.wadd.append(m.w)
         elif name == "s_clear":
-            q.frames = []
+            q.frames, q.wadd = [], []
         elif name == "s_info":
             if num:
                 exp["info"] = (len(q.frames), sum(R.kept(i, t)[0].shape[0] for i, t in q.frames))
         elif name in ("s_centroids", "s_palette"):
             assert op[2] >= n_fixed_of(m.fid) and m.seq_pixels(op[1]) > 0, op
             if num:
-                cent = R.centroids(m.frames_of(op[1]), op[2], m.fid)
+                cent = R.centroids(m.frames_of(op[1]), op[2], m.fid, m.w)
                 exp["cent" if name == "s_centroids" else "palette"] = cent if name == "s_centroids" else sorted_palette(cent)
         elif name == "s_output":
             k, mode, fmt, fam = op[2:6]
@@ -1421,7 +1767,7 @@ def apply_op(m, op):
             q.out = dict(t=m.t, k=k, mode=mode, fmt=fmt, fam=fam, cent=None, canvas=np.full((h, w), k, np.int64), held=np.zeros((h, w, 4), np.uint8),
                          last=None, shape=(h, w), coded=[])
             if num:
-                q.out["cent"] = R.centroids(m.frames_of(op[1]), k, m.fid)
+                q.out["cent"] = R.centroids(m.frames_of(op[1]), k, m.fid, m.w)
                 exp["palette"] = R.palette_bytes(q.out["cent"])
         elif name == "s_end":
             q.out = None
@@ -1492,6 +1838,8 @@ def apply_op(m, op):
         what = op[1]
         if what in REFUSALS_2:
             refuse_2(m, op, exp)
+        if what in REFUSALS_3:
+            refuse_3(m, op, exp)
         if what in ("k_below_fixed_palette", "k_below_fixed_reduce", "k_below_fixed_sequence"):
             assert op[3] < n_fixed_of(m.fid), op
         elif what == "octree_fixed":
@@ -1518,7 +1866,8 @@ def local_frame(m, o, i, delta, tol):
     whether the next frame is warm; a frame that fails in its palette step leaves shown and held and makes the next frame cold"""
     assert o is not None and o.get("local") and i in LOCAL_FAMILIES[o["fam"]] and (tol is None or delta), (i, delta, tol)
     R, k, f = m.ref, o["k"], n_fixed_of(m.fid)
-    kind = "fixed_on_warm" if o["warm"] and f else "k_below_fixed" if k < f else "empty" if m.n_kept(i, m.t) == 0 else None
+    wc = m.wc()                                               # (the weighting, as the cutoff, is read at THIS call: cold and warm)
+    kind = "fixed_on_warm" if o["warm"] and f else "k_below_fixed" if k < f else "empty" if m.n_kept(i, wc) == 0 else None
     exp = {"after": o["failed"], "failed": kind}
     o["failed"] = kind
     if kind:
@@ -1533,7 +1882,7 @@ def local_frame(m, o, i, delta, tol):
         o["coded"].append(None)
         return exp
     src = R.img(i)
-    cent = R.warm(i, m.t, o["prev"]) if exp["warm"] else R.centroids(((i, m.t),), k, m.fid)
+    cent = R.warm(i, wc, o["prev"], m.w) if exp["warm"] else R.centroids(((i, wc),), k, m.fid, m.w)
     I, P = R.index(src, cent, o["mode"], m.t), R.palette_bytes(cent)
     if not delta:
         d, rec, full = None, local_ref.FRESH8, True
@@ -1642,9 +1991,9 @@ def apply_op_2(m, op, exp):
             exp.update(cent=cent, index=I, table=tb, out=index_ref.pack_fast(new, bits), bad=m.bad)
     elif name == "optimize":
         i, k, mode, flags, bits = op[1:6]
-        assert k >= n_fixed_of(m.fid) and m.n_kept(i, m.t) > 0 and bits in (0, 8 * host_format(k, m.t)), op
+        assert k >= n_fixed_of(m.fid) and m.n_kept(i, m.wc()) > 0 and bits in (0, 8 * host_format(k, m.t)), op
         if num:
-            cent = R.centroids(((i, m.t),), k, m.fid)
+            cent = R.centroids(((i, m.wc()),), k, m.fid, m.w)
             pal, I = R.palette_bytes(cent), R.index(R.img(i), cent, mode, m.t)
             remap, out_pal, info = index_ref.plan(index_ref.usage(I, k), pal, flags)
             b = bits or info[3]
@@ -1679,6 +2028,28 @@ def refuse_2(m, op, exp):
         assert what == "remap_bad_bits" and op[3] not in BITS, op
 
 
+def refuse_3(m, op, exp):
+    """the refusals of alpha weighting: all KMG_ERR_INVALID_ARGUMENT, none changes anything"""
+    what = op[1]
+    if what == "weight_bad_value":
+        assert op[2] not in (0, 1), op
+    elif what == "l_weight_bad_value":
+        assert m.lloyd[op[2]] is not None and op[3] not in (0, 1), op
+    elif what == "octree_weighted":                           # no other cause applies: the octree under fixed colours is refused too
+        assert m.w == 1 and n_fixed_of(m.fid) == 0 and op[4] in (0, 1, 2), op
+    elif what == "weighted_no_kept_pixel":                    # alpha mode's error although the cutoff is 0; no k below fixed colours
+        assert m.w == 1 and m.t == 0 and n_fixed_of(m.fid) == 0 and op[2] in (0, 1, 2), op
+    elif what == "l_weight_under_caller_binding":
+        s = m.lloyd[op[2]]
+        assert s is not None and s.owner == "caller" and not s.w and op[3] in (0, 1), op
+    else:
+        # weighted_lftu and weighted_accumulate_into cannot tell two causes apart: a weighted object never holds a binding, so both
+        # calls would also be refused as "not bound", with the same status.  They are listed because the header lists them; what
+        # they do show is that the refused call writes neither labels nor sums and leaves the object weighted and usable.
+        s = m.lloyd[op[2]]
+        assert what in ("weighted_bind", "weighted_lftu", "weighted_accumulate_into") and s is not None and s.w and s.k <= 256, op
+
+
 # ---- the runner -----------------------------------------------------------------------------------------------------
 def _bits(c):
     return np.ascontiguousarray(c, np.float32).view(np.uint32)
@@ -1694,8 +2065,10 @@ class Runner:
         self.counters = counters if counters is not None else collections.Counter()
         self.own_proc = proc is None
         self.proc = env.session_processor() if proc is None else proc
-        for name, v in (("set_alpha_cutoff", 0), ("set_fixed_colors", None), ("set_strategy", 0)):      # (a caller's processor: a known start)
-            getattr(self.proc, name)(v)
+        for name, v in (("set_alpha_cutoff", 0), ("set_fixed_colors", None), ("set_strategy", 0), ("set_alpha_weight", False)):
+            getattr(self.proc, name)(v)                       # (a caller's processor: a known start)
+        self.weighted_closed = False                          # the last Lloyd call closed a weighted object: its block is the idle list's newest
+        self.last_quality = None
         self.pix = []
         for _, a in self.images:
             b = self.mem.alloc(a.size)
@@ -1784,15 +2157,26 @@ class Runner:
         C["op:" + name] += 1
         streams = env.streams
         before_t = m.t
+        if name not in ("l_new", "l_re", "l_close"):
+            self.weighted_closed = False
         if name.startswith("l_"):
             return self.step_lloyd(op)
         if name.startswith("s_"):
             return self.step_sequence(op)
         if name == "refuse":
             return self.step_refuse(op)
+        if m.w and name in ("palette", "reduce", "reduce_indexed", "quality", "optimize"):
+            C["weighted_host:" + name] += 1
+            C["weighted_host_at_cutoff_0"] += int(m.t == 0)
+        if name in ("palette", "reduce", "reduce_indexed", "quality") and op[1] == MAP:
+            C["host_call_on_the_map"] += 1
         exp = apply_op(m, op)
         if name == "cutoff":
             proc.set_alpha_cutoff(op[1])
+        elif name == "weight":
+            proc.set_alpha_weight(bool(op[1]))
+        elif name == "motif":
+            C["motif:" + op[1]] += 1
         elif name == "fixed":
             C[f"fixed:{op[1]}"] += 1
             proc.set_fixed_colors(self.fixed_arg(op[1]))
@@ -1832,6 +2216,9 @@ class Runner:
             self.same("palette of reduce_quality", pal, exp["palette"])
             self.same("record of reduce_quality", stats.as_tuple(), exp["stats"])
             self.same("output of reduce_quality", out.astype(np.int64) if indexed else out, exp["out"])
+            if self.last_quality is not None and self.last_quality[0] == op[1:] and self.last_quality[1] != m.w:
+                C["quality_weighting_changes_the_palette"] += int(not np.array_equal(self.last_quality[2], exp["palette"]))
+            self.last_quality = (op[1:], m.w, exp["palette"])
             if op[7]:                                     # the switches are as they were: the same call again gives the same answer
                 k2, pal2, out2, _, _ = proc.reduce_quality(self.images[i][1], dE, k_min, k_max, mode, bool(indexed))
                 self.same("reduce_quality, again", out2.astype(np.int64) if indexed else out2, exp["out"])
@@ -1982,6 +2369,10 @@ class Runner:
             if name == "l_re":
                 o.close()
             C[f"lloyd_k:{k_class(op[2])}"] += 1
+            if name == "l_re":
+                self.weighted_closed = bool(m.lloyd[L].w)
+            C["lloyd_object_created_right_after_a_weighted_one_closed"] += int(self.weighted_closed)    # (no call between the two)
+            self.weighted_closed = False
             apply_op(m, op)
             self.obj[L] = env.lloyd(self.proc, op[2])
             self.acc[L] = self.mem.alloc(32 * op[2] + GUARD)
@@ -1989,6 +2380,7 @@ class Runner:
             self.mem.write(self.acc[L], 0, np.zeros(32 * op[2], np.uint8))
             return
         if name == "l_close":
+            self.weighted_closed = bool(m.lloyd[L].w)
             apply_op(m, op)
             o.close()
             self.obj[L] = None
@@ -1996,15 +2388,17 @@ class Runner:
         s = m.lloyd[L]
         st = env.streams[op[-1]] if name not in ("l_set", "l_fix") else env.streams[0]
         acc = self.acc[L].ptr
-        img_i = op[2] if name in ("l_init", "l_assign_update", "l_iterate", "l_run", "l_lftu", "l_assign", "l_bind") else None
+        img_i = op[2] if name in LLOYD_IMAGE_OPS else None
         if img_i is not None:
-            if s.bind is not None and s.bind != img_i:
-                o.unbind_image()                              # (whether a pass on other pixels re-binds is the cost model's)
-                s.bind = None
             h, w = self.images[img_i][1].shape[:2]
             n, p = w * h, self.pix[img_i].ptr
         f_before = s.f
         exp = apply_op(m, op)
+        if exp.get("unbind"):
+            o.unbind_image()                                  # (whether a pass on other pixels re-binds is the cost model's)
+        if name in ("l_assign", "l_assign_update", "l_iterate", "l_run"):
+            C[f"pass:{name}:{'weighted' if s.w else 'unweighted'}"] += 1
+            C["lloyd_pass_on_the_map"] += int(img_i == MAP)
         if f_before and name in ("l_update", "l_assign_update", "l_iterate", "l_run", "l_lftu"):
             C["update_with_n_fixed:" + name] += 1
         if name == "l_set":
@@ -2017,6 +2411,11 @@ class Runner:
             o.set_fixed(op[2])
         elif name == "l_bind":
             o.bind_image(p, n, st)
+        elif name == "l_unbind":
+            o.unbind_image()
+        elif name == "l_weight":
+            C[f"l_weight:{op[2]}:owner_{exp['owner'] or 'nobody'}"] += 1
+            o.set_weighting(op[2])
         elif name == "l_conv":
             got = o.converged_count(st)
             if got != exp["nconv"]:
@@ -2050,6 +2449,11 @@ class Runner:
             self.same("labels of " + name, self.collect(self.lab, 4 * n, np.uint32, "labels"), exp["labels"])
         got = self.collect(self.acc[L], 32 * s.k, np.int64, "accumulators").reshape(s.k, 4)
         self.same("accumulators", got, s.acc)
+        if s.w and name in ("l_assign", "l_assign_update", "l_iterate"):
+            pixels = m.ref.assign(img_i, exp["cent_before"], 0)[1][:, 3] if "cent_before" in exp else None
+            if pixels is not None:
+                C["free_cluster_of_weight_0_with_pixels"] += int(((s.acc[s.f:, 3] == 0) & (pixels[s.f:] > 0)).any())
+                C["pinned_cluster_of_weight_0_with_pixels"] += int(((s.acc[:s.f, 3] == 0) & (pixels[:s.f] > 0)).any())
         if exp.get("cent") is not None:
             got = o.get_centroids(st)
             if not np.array_equal(_bits(got), _bits(exp["cent"])):
@@ -2072,6 +2476,9 @@ class Runner:
             q.close()
             self.seqs[S] = None
             return
+        if name in ("s_centroids", "s_palette", "s_output"):
+            C["sequence_loop_weighted" if m.w else "sequence_loop_unweighted"] += 1
+            C["sequence_loop_weighting_differs_from_an_add"] += int(any(w != m.w for w in m.seq[S].wadd))
         if name == "s_output":
             C["reoutput"] += int(m.seq[S].out is not None)
             C["mixed_cutoff_sequence"] += int(len({t for _, t in m.seq[S].frames}) > 1)
@@ -2081,6 +2488,8 @@ class Runner:
             i = op[2]
             h, w = self.images[i][1].shape[:2]
             C["add_shrunk"] += int(max(w, h) > SHRINK)
+            C["add_under_weighting"] += int(m.w)
+            C["add_under_weighting_loses_weight_0_pixels"] += int(m.w and m.t == 0 and m.n_kept(i, 1) < w * h)
             if op[3]:
                 q.add_device(self.pix[i].ptr, w, h, env.streams[op[4]])
             else:
@@ -2191,6 +2600,10 @@ class Runner:
         C["local_held_pixels"] += int(exp["held_pixels"])
         C["local_cutoff_differs_from_last_frame"] += int(o.get("t_last") not in (None, m.t))
         o["t_last"] = m.t
+        if m.w:
+            C["local_warm_weighted" if exp["warm"] else "local_cold_weighted"] += 1
+        C["local_warm_weighting_differs_from_last_frame"] += int(exp["warm"] and o.get("w_last") not in (None, m.w))
+        o["w_last"] = m.w
         got, pal, info, full = q.frame_local(img, delta=bool(delta), tolerance=tol)
         what = f"local frame ({'warm' if exp['warm'] else 'cold'}, cutoff {m.t})"
         self.same("palette of the " + what, pal, exp["palette"])
@@ -2209,6 +2622,8 @@ class Runner:
         st = exp["status"]
         if what in REFUSALS_2:
             return self.step_refuse_2(op, st)
+        if what in REFUSALS_3:
+            return self.step_refuse_3(op, st)
         if what == "k_below_fixed_palette":
             self.expect_status(st, proc.palette, op[3], self.images[op[2]][1], 0)
         elif what == "k_below_fixed_reduce":
@@ -2238,6 +2653,45 @@ class Runner:
         else:
             raise ValueError(op)
 
+
+    # -- surface 3
+    def step_refuse_3(self, op, st):
+        m, proc, env, what = self.model, self.proc, self.env, op[1]
+        if what == "weight_bad_value":
+            self.expect_status(st, env.set_weighting, proc, op[2])
+        elif what in ("octree_weighted", "weighted_no_kept_pixel"):
+            img, k, algo, variant = (self.images[op[2]][1], op[3], 1, op[4]) if what == "octree_weighted" else (self.images[CLEAR][1], 4, 0, op[2])
+            self.counters[f"{what}:{('palette', 'reduce', 'reduce_indexed')[variant]}"] += 1
+            if variant == 0:
+                self.expect_status(st, proc.palette, k, img, algo)
+            elif variant == 1:
+                out = np.full(img.shape, PATTERN, np.uint8)
+                self.expect_status(st, proc.reduce, k, img, algo, 0, out=out)
+                if not (out == PATTERN).all():
+                    self.fail("a refused call wrote output")
+            else:
+                self.expect_status(st, proc.reduce_indexed, k, img, algo, 0)
+        else:
+            L = op[2]
+            o, s = self.obj[L], m.lloyd[L]
+            if what in ("l_weight_bad_value", "l_weight_under_caller_binding"):
+                if what == "l_weight_under_caller_binding":
+                    self.counters[f"l_weight:{op[3]}:owner_caller"] += 1
+                self.expect_status(st, o.set_weighting, op[3])
+            else:
+                h, w = self.images[op[3]][1].shape[:2]
+                n, p, stream = w * h, self.pix[op[3]].ptr, env.streams[0]
+                self.arm(self.lab, 4 * n)
+                if what == "weighted_bind":
+                    self.expect_status(st, o.bind_image, p, n, stream)
+                elif what == "weighted_accumulate_into":
+                    self.expect_status(st, o.accumulate_into, p, n, self.acc[L].ptr, stream)
+                else:
+                    self.expect_status(st, o.labels_from_tables_update, p, n, self.lab.ptr, self.acc[L].ptr, stream)
+                env.sync()
+                if not (self.collect(self.lab, 4 * n, np.uint8, "refused call") == PATTERN).all():
+                    self.fail("a refused call wrote labels")
+            self.same("accumulators after a refused call", self.collect(self.acc[L], 32 * s.k, np.int64, "accumulators").reshape(s.k, 4), s.acc)
 
     # -- surface 2
     def step_refuse_2(self, op, st):
@@ -2444,6 +2898,10 @@ class KgEnv(LH.KgEnv):
     def index_plan(self, usage, palette, flags):
         remap, pal, info = self.kg.index_plan(usage, palette, flags)
         return remap, pal, info.as_tuple()
+
+    def set_weighting(self, proc, value):
+        """kmg_processor_set_weighting with any value (ImageProcessor.set_alpha_weight passes the two legal ones only)"""
+        self.kg._check(self.kg.lib().kmg_processor_set_weighting(proc.handle, int(value)))
 
     def fresh_hold(self):
         return self.kg.FrameHold.fresh_bytes()

@@ -1,8 +1,9 @@
 """Long-lived sessions on the device (tests/session_harness.py): the random sessions of tools/fuzz_session.py on the seeds
 tests/test_session_model.py vouches for, and named scenarios -- each an op list of the harness, run against its stateless model on
 ONE processor that stays alive across all of them (so every scenario works in the blocks the ones before it left): the eight of the
-first surface, then the directed passages of surface 2 (local outputs, colour-keyed canvases, the index-map optimisation).  Everything an
-op could have touched is compared byte for byte after every op."""
+first surface, then the directed passages of surface 2 (local outputs, colour-keyed canvases, the index-map optimisation), then
+the seven of surface 3 (alpha weighting turned on and off between the other calls of that processor and of its Lloyd objects).
+Everything an op could have touched is compared byte for byte after every op."""
 import os
 import re
 import subprocess
@@ -11,12 +12,12 @@ import sys
 import pytest
 
 import session_harness as H
-from test_session_model import SEEDS, SEEDS_2, SEQUENCES
+from test_session_model import SEEDS, SEEDS_2, SEEDS_3, SEQUENCES
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED, SEQ = 7, 0                      # the images of the scenarios: H.make_images(SEED, SEQ)
-ODD, ODD_B, SPRITE, NOISY, SHIFT, FEW, FLAT, CLEAR, BIG, MEGA, ROW, COL = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12
+ODD, ODD_B, SPRITE, NOISY, SHIFT, FEW, FLAT, CLEAR, BIG, MEGA, ROW, COL, MAP = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14
 # A seed's run took 7.5 and 7.8 s on an MI355X, process start included (profiles/NOTES.md, "Session harness"); about two thirds of
 # that is the reference on the host's CPUs.  The limit is forty times the measured time: a host with a quarter of the cores, busy
 # with other work, can slow the reference tenfold and still finish; a run that needs longer than that hangs.
@@ -44,6 +45,22 @@ def test_random_sessions_equal_the_model(seed):
 def test_random_sessions_of_surface_2_equal_the_model(seed):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_session.py"), str(SEQUENCES), str(seed), "2"],
                        capture_output=True, text=True, timeout=TIMEOUT_2)
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    assert re.search(rf"^{SEQUENCES} sequences, \d+ ops, 0 mismatching$", r.stdout, re.M), r.stdout[-2000:]
+    reused = [int(x) for x in re.findall(r"(\d+) blocks re-used", r.stdout)]
+    assert len(reused) == SEQUENCES and all(x > 0 for x in reused), reused     # else nothing ran on recycled memory
+
+
+# The seeds of surface 3 (alpha weighting) took 5.5 and 5.5 s in the visit in which a seed-314 run took 5.3 s (profiles/NOTES.md):
+# the same rule, forty times the slower of the two.
+SESSION_3_SECONDS = 5.5
+TIMEOUT_3 = 40 * SESSION_3_SECONDS
+
+
+@pytest.mark.parametrize("seed", SEEDS_3)
+def test_random_sessions_of_surface_3_equal_the_model(seed):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_session.py"), str(SEQUENCES), str(seed), "3"],
+                       capture_output=True, text=True, timeout=TIMEOUT_3)
     assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
     assert re.search(rf"^{SEQUENCES} sequences, \d+ ops, 0 mismatching$", r.stdout, re.M), r.stdout[-2000:]
     reused = [int(x) for x in re.findall(r"(\d+) blocks re-used", r.stdout)]
@@ -224,6 +241,81 @@ def _a_colour_keyed_canvas_of_the_caller_on_both_routes():
             ("cpair_frame", 1, ODD_B, 63, 40, 2, 1, 1), ("cpair_frame", 1, ODD, 64, None, 2, 2, 0), ("cutoff", 0)]
 
 
+# ---- surface 3: alpha weighting ---------------------------------------------------------------------------------------------------
+def _weight_on_cutoff_0_128_0_weight_off_around_the_same_calls():
+    """the first and the last results are the default path's; under weighting the working image is cut at max(t, 1) and the outputs
+    at t; INDEX8 at k = 256 is legal at t = 0 under weighting"""
+    at = [("palette", SPRITE, 8), ("reduce_indexed", SPRITE, 8, 0, 1), ("reduce_indexed", ODD, 40, 3, 1), ("reduce", ODD, 8, 1), ("reduce", MAP, 5, 3)]
+    return ([("strategy", 0), ("fixed", 0), ("cutoff", 0), ("weight", 0)] + at + [("weight", 1)] + at + [("cutoff", 128)] + at + [("cutoff", 0)] + at +
+            [("reduce_indexed", FEW, 256, 0, 0), ("find", ODD, 9, 0, 71), ("apply", SPRITE, 1, 1, 256, 72, 0), ("weight", 0)] + at)
+
+
+def _two_frames_added_under_different_weightings_and_the_palette_both_ways():
+    """the weighting at an add decides that frame's cutoff (s_info: the frame added under it at t = 0 loses its pixels of alpha 0),
+    the weighting at the palette call whether the loop is weighted"""
+    ops = [("cutoff", 0), ("fixed", 0), ("s_new", 0)]
+    for first in (0, 1):
+        ops += [("s_clear", 0), ("weight", first), ("s_add", 0, SPRITE, 0, 0), ("weight", 1 - first), ("s_add", 0, ODD, 1, 1), ("s_info", 0),
+                ("s_centroids", 0, 7), ("s_palette", 0, 7), ("weight", first), ("s_centroids", 0, 7), ("s_palette", 0, 7),
+                ("s_output", 0, 7, 0, 1, 1), ("s_frame", 0, SPRITE, 1, None), ("s_frame", 0, NOISY, 1, 40), ("s_end", 0)]
+    return ops + [("fixed", 2), ("weight", 1), ("s_add", 0, MAP, 0, 0), ("s_info", 0), ("s_centroids", 0, 6), ("fixed", 0), ("weight", 0),
+                  ("s_centroids", 0, 6), ("s_close", 0)]
+
+
+def _a_warm_output_alternates_weighted_and_unweighted_frames_across_a_cutoff_switch():
+    """a warm frame reads the weighting at its own call, as it reads the cutoff"""
+    return [("cutoff", 0), ("fixed", 0), ("weight", 1), ("s_new", 1), ("s_output_local", 1, 12, 0, 1, 1, 1), ("s_frame_local", 1, SPRITE, 1, None),
+            ("weight", 0), ("s_frame_local", 1, NOISY, 1, 40), ("cutoff", 128), ("weight", 1), ("s_frame_local", 1, SHIFT, 1, None), ("weight", 0),
+            ("s_frame_local", 1, SPRITE, 1, 4096), ("cutoff", 0), ("weight", 1), ("s_frame_local", 1, NOISY, 1, None),
+            ("s_output_local", 1, 5, 1, 2, 0, 0), ("s_frame_local", 1, ODD, 1, None), ("weight", 0), ("s_frame_local", 1, ODD_B, 1, 40),
+            ("s_output_local", 1, 3, 0, 1, 4, 1), ("s_frame_local", 1, CLEAR, 1, None), ("weight", 1), ("s_frame_local", 1, CLEAR, 1, None),
+            ("weight", 0), ("s_frame_local", 1, CLEAR, 1, None), ("s_close", 1)]
+
+
+def _the_binding_of_an_initialisation_and_of_the_caller_around_the_lloyd_weighting():
+    """forced colour table, so that the initialisation leaves a binding: the weighted run drops it, and so does the setter, in both
+    directions; the setter is refused under the caller's binding, bind_image on a weighted object"""
+    return [("strategy", 2), ("l_new", 0, 9), ("l_init", 0, ODD, 0, 0), ("l_weight", 0, 1), ("l_run", 0, ODD, 1, 0), ("l_weight", 0, 0),
+            ("l_assign_update", 0, ODD, 1, 1, 0), ("l_init", 0, ODD, 1, 1), ("l_weight", 0, 1), ("l_assign", 0, ODD, 1), ("l_weight", 0, 0),
+            ("l_assign", 0, ODD, 0), ("l_init", 0, MAP, 0, 0), ("l_weight", 0, 0), ("l_assign", 0, MAP, 0), ("l_bind", 0, MAP, 0),
+            ("refuse", "l_weight_under_caller_binding", 0, 1), ("l_assign", 0, MAP, 1), ("l_run", 0, MAP, 1, 0),
+            ("refuse", "l_weight_under_caller_binding", 0, 0), ("refuse", "l_weight_bad_value", 0, 2), ("l_unbind", 0), ("l_weight", 0, 1),
+            ("refuse", "weighted_bind", 0, MAP), ("refuse", "weighted_lftu", 0, MAP), ("refuse", "weighted_accumulate_into", 0, MAP),
+            ("l_run", 0, MAP, 1, 1), ("l_iterate", 0, SPRITE, 2, 0), ("l_conv", 0, 0), ("refuse", "l_weight_bad_value", 0, -1), ("l_assign", 0, SPRITE, 0),
+            ("l_weight", 0, 0), ("l_assign_update", 0, SPRITE, 1, 1, 1), ("l_lftu", 0, SPRITE, 0), ("l_close", 0), ("strategy", 0)]
+
+
+def _weighted_and_unweighted_lloyd_objects_in_each_others_blocks_beside_weighted_host_calls():
+    """neither a Lloyd object of the caller's nor the library's own one leaks its weighting into the block's next owner"""
+    return [("cutoff", 0), ("fixed", 0), ("l_new", 0, 12), ("l_set", 0, "rand", 81, ODD), ("l_weight", 0, 1), ("l_assign_update", 0, ODD, 1, 1, 0),
+            ("weight", 0), ("palette", SPRITE, 6), ("l_close", 0), ("l_new", 0, 12), ("l_set", 0, "rand", 81, ODD), ("l_assign_update", 0, ODD, 1, 1, 0),
+            ("weight", 1), ("reduce_indexed", SPRITE, 6, 0, 0), ("l_new", 1, 40), ("l_set", 1, "rand", 82, ODD), ("l_assign_update", 1, MAP, 1, 1, 1),
+            ("l_close", 1), ("l_close", 0), ("l_new", 1, 40), ("l_set", 1, "rand", 82, ODD), ("l_weight", 1, 1), ("l_assign_update", 1, MAP, 1, 1, 0),
+            ("weight", 0), ("reduce_indexed", SPRITE, 6, 0, 0), ("palette", MAP, 300), ("l_re", 1, 5), ("l_set", 1, "dup", 83, ODD),
+            ("l_run", 1, FEW, 1, 0), ("l_close", 1)]
+
+
+def _fixed_colours_and_weighting_with_clusters_of_weight_0():
+    """a pinned entry stays put whatever its members weigh and counts as converged; a free cluster whose members all weigh 0 is an
+    empty cluster (60 centroids on the 131 pixels of the row, a quarter of which weigh 0)"""
+    return [("cutoff", 0), ("fixed", 3), ("weight", 1), ("palette", SPRITE, 11), ("reduce_indexed", ROW, 12, 0, 0), ("reduce", COL, 9, 1),
+            ("refuse", "weight_bad_value", 2), ("refuse", "weight_bad_value", -1), ("palette", SPRITE, 11),
+            ("l_new", 0, 60), ("l_init", 0, ROW, 3, 0), ("l_fix", 0, 3), ("l_weight", 0, 1), ("l_assign_update", 0, ROW, 1, 1, 0), ("l_conv", 0, 0),
+            ("l_run", 0, COL, 1, 1), ("l_iterate", 0, ROW, 2, 0), ("l_conv", 0, 1), ("l_update", 0, 0), ("l_conv", 0, 0), ("l_close", 0),
+            # the refusals of weighting once no colour is fixed, so that nothing else refuses them: the octree in its three calls
+            # (reduce: nothing written), and the image without a kept pixel at t = 0
+            ("fixed", 0), ("refuse", "octree_weighted", SPRITE, 12, 0), ("refuse", "octree_weighted", SPRITE, 12, 1),
+            ("refuse", "octree_weighted", FEW, 6, 2), ("refuse", "weighted_no_kept_pixel", 0), ("refuse", "weighted_no_kept_pixel", 1),
+            ("refuse", "weighted_no_kept_pixel", 2), ("palette", SPRITE, 5), ("weight", 0)]
+
+
+def _the_quality_search_weighted_then_unweighted():
+    """weighted palettes, the unweighted record, on the working image cut at max(t, 1); then the same call without weighting"""
+    q = ("quality", SPRITE, 4.0, 2, 12, 0, 1, 1)
+    return [("cutoff", 0), ("fixed", 0), ("weight", 1), q, ("quality", MAP, 9.0, 2, 10, 3, 0, 0), ("cutoff", 128), q, ("cutoff", 0), ("weight", 0), q,
+            ("fixed", 2), ("weight", 1), ("quality", SPRITE, 9.0, 3, 9, 1, 1, 0), ("fixed", 0), ("weight", 0)]
+
+
 SCENARIOS = {f.__name__[1:]: f for f in (_cutoff_0_128_0_around_palette_reduce_and_a_plan, _frames_added_under_three_cutoffs_then_clear, _an_output_ends_a_lloyd_object_runs_in_its_block_and_the_next_output_starts_fresh, _frozen_seeds_do_not_outlive_their_object, _quality_search_with_and_without_pins_beside_a_bound_object, _records_combine_over_bands_in_reverse_on_two_streams, _every_refusal_is_followed_by_the_correct_call, _two_sequences_alternate_beside_host_calls_on_the_megapixel_image,
                                          # surface 2, on the same long-lived processor after the eight above
                                          _a_warm_output_across_a_cutoff_switch_and_back,
@@ -233,7 +325,15 @@ SCENARIOS = {f.__name__[1:]: f for f in (_cutoff_0_128_0_around_palette_reduce_a
                                          _local_shared_local_on_one_sequence_with_the_refusals_between,
                                          _the_sequence_optimize_path_counts_plans_remaps_and_replays,
                                          _usage_records_outlive_their_maps_and_the_bad_count_combines,
-                                         _a_colour_keyed_canvas_of_the_caller_on_both_routes)}
+                                         _a_colour_keyed_canvas_of_the_caller_on_both_routes,
+                                         # surface 3, after the sixteen above: the processor ends with weighting off
+                                         _weight_on_cutoff_0_128_0_weight_off_around_the_same_calls,
+                                         _two_frames_added_under_different_weightings_and_the_palette_both_ways,
+                                         _a_warm_output_alternates_weighted_and_unweighted_frames_across_a_cutoff_switch,
+                                         _the_binding_of_an_initialisation_and_of_the_caller_around_the_lloyd_weighting,
+                                         _weighted_and_unweighted_lloyd_objects_in_each_others_blocks_beside_weighted_host_calls,
+                                         _fixed_colours_and_weighting_with_clusters_of_weight_0,
+                                         _the_quality_search_weighted_then_unweighted)}
 
 
 @pytest.mark.parametrize("name", list(SCENARIOS))

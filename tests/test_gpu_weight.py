@@ -6,7 +6,8 @@ against tests/weight_ref.py:
      initialisation that bound the image;
   3. the host-buffer calls against the model: palette, reduce, reduce_indexed at t = 0 and 128, fixed colours, sequences,
      per-frame palettes cold and warm, the quality search, and the default bytes after the weighting is taken back;
-  4. the refusals, with the objects usable afterwards."""
+  4. the refusals, with the objects usable afterwards;
+  5. the sums at the bound: 2^28 pixels made on the device, sums between 2^62 and 2^63 against exact integer arithmetic."""
 import numpy as np
 import pytest
 
@@ -447,5 +448,138 @@ def test_lloyd_refusals(torch_cuda, processor, oracle):
         d.acc.zero_()
         s.assign_accumulate(d.ptr, n, 0, d.acc.data_ptr(), d.st)
         assert np.array_equal(d.sums(), oracle.accumulate(lab, labels, k))
+    finally:
+        s.close()
+
+
+# ---- the sums at the bound ----------------------------------------------------------------------------------------------------------
+N_BOUND = 1 << 28
+TILE = 4093                                                          # prime: every repetition meets the 4-pixel groups at another phase
+
+
+def _bound_problem(oracle):
+    """the host side of test_sums_at_the_pixel_bound, no device needed: 64 RGBA words, a tile of TILE indices into them in runs of
+    1 .. 5, and -- the image being the tile repeated, cut at N_BOUND -- the per-colour counts in closed form:
+    count_c = (N_BOUND // TILE) (occurrences of c in the tile) + (occurrences in its first N_BOUND % TILE entries).
+    About 70 % of the pixels are opaque near-whites, 25 % opaque pure green (what is left of 72 % and 24 % of the runs once
+    neighbours must differ), the rest 55 random colours with alpha bytes that
+    include 0, 1, 2, 127, 128, 254 and 255."""
+    rng = np.random.default_rng(228)
+    pal = rng.integers(0, 256, (64, 4), dtype=np.uint8)
+    pal[:8, :3] = 255 - rng.integers(0, 3, (8, 3))
+    pal[0, :3] = 255
+    pal[:9, 3] = 255
+    pal[8, :3] = (0, 255, 0)
+    pal[9:16, 3] = (0, 1, 2, 127, 128, 254, 255)
+    runs = rng.integers(1, 6, TILE)
+    colour, other = [], 0
+    for r in rng.random(TILE):
+        while True:                                                  # (neighbours differ, so that no two runs make a longer one)
+            c = int(rng.integers(0, 8)) if r < 0.72 else 8 if r < 0.96 else 9 + other % 55
+            if not colour or c != colour[-1]:
+                break
+            r = rng.random()
+        other += c > 8                                               # the 55 others in turn: each of them is there
+        colour.append(c)
+    tile = np.repeat(colour, runs)[:TILE].astype(np.int64)
+    reps, tail = divmod(N_BOUND, TILE)
+    counts = reps * np.bincount(tile, minlength=64).astype(object) + np.bincount(tile[:tail], minlength=64).astype(object)
+    assert sum(counts) == N_BOUND
+    lab = oracle.rgb_to_lab(pal)
+    q = W.pixel_q(oracle, lab)
+    problem = dict(pal=pal, tile=tile, counts=counts, lab=lab)
+    for k, rows in ((8, [0, 8, 9, 10, 11, 12, 13, 14]), (40, list(range(40)))):
+        cent = oracle.centroids4(lab[rows])
+        labels = oracle.assign(lab, cent)
+        sums = [[0, 0, 0, 0] for _ in range(k)]                      # exact Python integers
+        for c in range(64):
+            a = int(pal[c, 3])
+            for j in range(3):
+                sums[labels[c]][j] += int(counts[c]) * a * int(q[c, j])
+            sums[labels[c]][3] += int(counts[c]) * a
+        problem[k] = (cent, labels, sums)
+    return problem
+
+
+def _bound_feasible(P):
+    """what the palette of _bound_problem must give, asserted on the expected values before any launch (and, without a device, by
+    tests/test_weight_contract.py): a sum of a qL of at least 2^62, a sum of a qa or a qb of at most -2^60, every |sum| below 2^63,
+    weights 0, 1 and 255 present"""
+    sums = P[8][2]
+    flat = [v for row in sums for v in row]
+    print("largest sum 2^%.3f, lowest -2^%.3f" % (np.log2(float(max(flat))), np.log2(float(-min(flat)))))
+    assert max(row[0] for row in sums) >= 1 << 62
+    assert min(min(row[1], row[2]) for row in sums) <= -(1 << 60)
+    assert all(abs(v) < (1 << 63) for v in flat) and all(abs(v) < (1 << 63) for row in P[40][2] for v in row)
+    assert {0, 1, 255} <= set(P["pal"][np.unique(P["tile"]), 3].tolist())
+
+
+def test_sums_at_the_pixel_bound(torch_cuda, processor, oracle):
+    """2^28 pixels exactly, the most a weighted pass takes: sums between 2^62 and 2^63 and below -2^60 through the int64 run
+    registers, the unsigned 64-bit LDS bins, the partial slabs and the double division of the update, bit for bit against exact
+    integer arithmetic; one pixel more is KMG_ERR_UNSUPPORTED and touches nothing.  The pixels are made on the device (a tile
+    broadcast into the buffer); the counts are in closed form (_bound_problem).  1 GiB of pixels, 1 GiB of labels."""
+    import kmeans_gpu_amd as kg
+    torch = torch_cuda
+    P = _bound_problem(oracle)
+    n, pal, tile = N_BOUND, P["pal"], P["tile"]
+    cent, labels_of, sums = P[8]
+    _bound_feasible(P)
+    want = np.array(sums, np.int64)
+    want_cent, want_conv = oracle.finalize(want, cent)
+
+    st = torch.cuda.current_stream().cuda_stream
+    words = torch.from_numpy(np.ascontiguousarray(pal).view(np.uint32).reshape(-1).astype(np.int64)).cuda().to(torch.int32)
+    tile_words = words[torch.from_numpy(tile).cuda()]
+    reps, tail = divmod(n, TILE)
+    buf = torch.empty(n + 1, dtype=torch.int32, device="cuda")      # one pixel more than the bound, for the refusal
+    buf[:reps * TILE].view(reps, TILE).copy_(tile_words.expand(reps, TILE))
+    buf[reps * TILE:n] = tile_words[:tail]
+    buf[n] = words[0]                                                # opaque white: a pass that read it would show in every sum
+    labels = torch.zeros(n, dtype=torch.int32, device="cuda")
+    acc = torch.zeros((8, 4), dtype=torch.int64, device="cuda")
+    tile_labels = torch.from_numpy(labels_of.astype(np.int64)).cuda().to(torch.int32)[torch.from_numpy(tile).cuda()]
+
+    def got():
+        torch.cuda.synchronize()
+        return acc.cpu().numpy()
+
+    s = kg.Lloyd(processor, 8)
+    try:
+        s.set_weighting(kg.WEIGHT_ALPHA)
+        s.set_centroids(cent, st)
+        s.assign_accumulate(buf.data_ptr(), n, 0, acc.data_ptr(), st)
+        assert np.array_equal(got(), want)
+        # one pixel more: refused before anything is enqueued, the sums buffer untouched, the object usable
+        acc.fill_(0x5A5A5A5A5A5A5A5A)
+        for call in (lambda: s.assign_accumulate(buf.data_ptr(), n + 1, 0, acc.data_ptr(), st), lambda: s.run(buf.data_ptr(), n + 1, 0, st)):
+            with pytest.raises(kg.KmgError) as e:
+                call()
+            assert e.value.status == -5
+        assert (got() == 0x5A5A5A5A5A5A5A5A).all()
+        assert np.array_equal(_bits(s.get_centroids(st)), _bits(cent))
+        # the two halves, with the label map
+        acc.zero_()
+        s.assign_partials(buf.data_ptr(), n, labels.data_ptr(), st)
+        s.reduce_partials(n, acc.data_ptr(), st)
+        assert np.array_equal(got(), want)
+        assert bool((labels[:reps * TILE].view(reps, TILE) == tile_labels).all()) and bool((labels[reps * TILE:] == tile_labels[:tail]).all())
+        # the fused update: the double division of sums far above 2^53
+        acc.zero_()
+        s.assign_update(buf.data_ptr(), n, 0, acc.data_ptr(), True, st)
+        assert np.array_equal(got(), want)
+        assert np.array_equal(_bits(s.get_centroids(st)[:, :3]), _bits(want_cent[:, :3]))
+        assert s.converged_count(st) == want_conv
+    finally:
+        s.close()
+    # the chunked scan: sums only
+    cent40, _, sums40 = P[40]
+    acc = torch.zeros((40, 4), dtype=torch.int64, device="cuda")
+    s = kg.Lloyd(processor, 40)
+    try:
+        s.set_weighting(kg.WEIGHT_ALPHA)
+        s.set_centroids(cent40, st)
+        s.assign_accumulate(buf.data_ptr(), n, 0, acc.data_ptr(), st)
+        assert np.array_equal(got(), np.array(sums40, np.int64))
     finally:
         s.close()

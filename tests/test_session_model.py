@@ -13,6 +13,11 @@ filled at the begin, the held source not; the centroids in the sequence), usage 
 faulty variants, and the thirteen old ones, are each caught by each of SEEDS_2; a second exact table, EXACT_2.  The op lists of the
 old seeds are pinned by hash: surface 2 must not move them.
 
+Surface 3 (alpha weighting on the processor and on the Lloyd objects) has SEEDS_3: the stand-ins keep the processor's switch, read
+it where the library reads it (the cutoff of a working image where the image is made, the loop where it starts), keep a Lloyd
+object's weighting and both kinds of binding; twelve more faulty variants, and the twenty-six old ones, are each caught by each of
+SEEDS_3; a third exact table, EXACT_3.  The op lists of SEEDS_2 and the fourteen old images are pinned by hash as well.
+
 Wall time of this file and of tests/test_lifecycle_model.py: profiles/NOTES.md, "session harness"."""
 import collections
 import hashlib
@@ -30,6 +35,7 @@ import hold_ref
 import index_ref
 import local_ref
 import sequence_ref
+import weight_ref
 from lifecycle_harness import sorted_palette
 from test_lifecycle_model import FakeError, HostMem, _view
 
@@ -46,6 +52,17 @@ SEEDS_2 = (314, 315)
 FAULTS_2 = ("warm_after_failed_frame", "warm_survives_begin", "shown_survives_begin", "failed_frame_touches_shown",
             "local_switches_read_at_begin", "held_not_reanchored_local", "lossy_full_keeps_lossy_canvas", "duplicate_entries_sent",
             "usage_overwrites", "usage_index8_256_touches_tail", "bad_count_overwrites", "optimize_counts_leak", "remap_padding_dirty")
+
+
+# surface 3 (alpha weighting on the processor and on the Lloyd objects): its own seeds, which also run every op of surfaces 1 and 2
+SEEDS_3 = (421, 422)
+# weight_set_under_binding can be caught only through the refusal l_weight_under_caller_binding: the deviation is that a call the
+# header refuses is accepted, and the generator never emits that call but as a listed refusal (warm_after_failed_frame is the
+# precedent: there the refusal is what moves the state).
+FAULTS_3 = ("weight_read_at_add", "add_cutoff_ignores_weight", "output_cutoff_follows_weight", "weight_off_ignored", "bad_value_clears_weight",
+            "lloyd_weight_inherited", "weighted_object_uses_binding", "weight_set_under_binding", "warm_frame_unweighted", "init_weighted",
+            "quality_record_weighted", "zero_weight_cluster_counts_pixels")
+NEW_OPS_3 = ("weight", "l_weight", "l_unbind", "motif")
 
 
 NEW_OPS = ("s_output_local", "s_frame_local", "cpair_open", "cpair_frame", "usage_device", "plan", "remap_device", "optimize", "s_usage",
@@ -81,6 +98,7 @@ class FakeProcessor:
         self.ref = H.Ref(images, cache)
         self.by_bytes = {a.tobytes(): i for i, (_, a) in enumerate(images)}
         self.t, self.fixed, self.strategy = 0, None, 0
+        self.w = 0                     # kmg_processor_set_weighting
         self.idle = []                 # blocks of closed objects and ended outputs: what their last owner left in them
         self.allocated = self.reused = 0
         self.last_compare = error_ref.ZERO
@@ -120,6 +138,26 @@ class FakeProcessor:
     def set_strategy(self, v):
         self.strategy = int(v)
 
+    def set_weighting(self, v):
+        if v not in (0, 1):
+            if self.fault == "bad_value_clears_weight":
+                self.w = 0
+            raise FakeError(-1, "unknown weighting")
+        if v == 0 and self.fault == "weight_off_ignored":
+            return
+        self.w = int(v)
+
+    def set_alpha_weight(self, on):
+        self.set_weighting(1 if on else 0)
+
+    def wc(self):
+        """the cutoff of a working image made now"""
+        return max(self.t, 1) if self.w else self.t
+
+    def out_t(self):
+        """the cutoff of an output made now: t, whatever the weighting"""
+        return 1 if self.fault == "output_cutoff_follows_weight" and self.w and self.t == 0 else self.t
+
     def fid(self):
         return H.FIXED.index(self.fixed)
 
@@ -132,28 +170,38 @@ class FakeProcessor:
     # -- the palette step of a host call: the switches as they are when it starts
     def _centroids(self, image, k, algo=0):
         f = self.n_fixed()
-        if algo == 1 and f:
-            raise FakeError(-1, "the octree has no fixed colours")
+        if algo == 1 and (f or self.w):
+            raise FakeError(-1, "the octree has no fixed colours and no weighting")
         if k < f:
             raise FakeError(-1, "k is below the fixed colours")
         i = self.image_index(image)
-        if self.ref.working(((i, self.t),)) is None:
+        if self.ref.working(((i, self.wc()),)) is None:
             raise FakeError(-1, "no pixel reaches alpha_cutoff")
         self.scratch()
-        return self.ref.centroids(((i, self.t),), k, self.fid())
+        if self.fault == "init_weighted" and self.w and self.t == 0:
+            # the initialisation on the pixels kept at t, the weighted loop on those kept at max(t, 1)
+            W0, w0, h0 = self.ref.working(((i, 0),))
+            W1 = self.ref.working(((i, 1),))[0]
+            pins = fixed_ref.pins_lab(O, () if self.fixed is None else np.array(self.fixed, np.uint8))
+            cent0 = fixed_ref.init_centroids(O, O.rgb_to_lab(W0), w0, h0, k, pins) if f else O.init_centroids(O.rgb_to_lab(W0), w0, h0, k)
+            return weight_ref.lloyd(O, O.rgb_to_lab(W1), W1[:, 3], cent0, f, H.MAX_ITERATIONS, H.CHECK_PERIOD)[0]
+        return self.ref.centroids(((i, self.wc()),), k, self.fid(), self.w)
 
     def palette(self, k, image, algo=0):
         return sorted_palette(self._centroids(image, k, algo))
 
-    def reduce(self, k, image, algo=0, reduce_mode=0):
-        return self.ref.rgba(image, self._centroids(image, k, algo), reduce_mode, self.t)
+    def reduce(self, k, image, algo=0, reduce_mode=0, out=None):
+        res = self.ref.rgba(image, self._centroids(image, k, algo), reduce_mode, self.out_t())
+        if out is not None:
+            out[:] = res
+        return res
 
     def _typed(self, idx, k, t):
         return idx.astype(H.index_dtype(H.host_format(k, t)))
 
     def reduce_indexed(self, k, image, algo=0, reduce_mode=0):
         cent = self._centroids(image, k, algo)
-        return self.ref.palette_bytes(cent), self._typed(self.ref.index(image, cent, reduce_mode, self.t), k, self.t)
+        return self.ref.palette_bytes(cent), self._typed(self.ref.index(image, cent, reduce_mode, self.out_t()), k, self.t)
 
     def find(self, image, colors, reduce_mode=0):
         pal = np.ascontiguousarray(colors, np.uint8).reshape(-1, 4)
@@ -179,8 +227,12 @@ class FakeProcessor:
             raise FakeError(-1, "k_min is below the fixed colours")
         i, t = self.image_index(image), self.t
         self.scratch()
-        k, reached, rec = self.ref.quality(i, t, self.fid(), H.target_of(max_delta_e), k_min, k_max)
-        cent = self.ref.centroids(((i, t),), k, self.fid())
+        k, reached, rec = self.ref.quality(i, self.wc(), self.fid(), H.target_of(max_delta_e), k_min, k_max, self.w)
+        cent = self.ref.centroids(((i, self.wc()),), k, self.fid(), self.w)
+        if self.fault == "quality_record_weighted" and self.w:       # the record of the list in which pixel i appears a_i times
+            W = self.ref.working(((i, self.wc()),))[0]
+            rep = np.ascontiguousarray(np.repeat(W, W[:, 3].astype(np.int64), axis=0))
+            rec = error_ref.stats(O, rep, O.assign(O.rgb_to_lab(rep), cent), palette=self.ref.palette_bytes(cent))
         out = self._typed(self.ref.index(image, cent, reduce_mode, t), k_max, t) if indexed else self.ref.rgba(image, cent, reduce_mode, t)
         if self.fault == "quality_leaves_switch":
             self.t = 0 if t else 255               # the bisection's own setting is left behind
@@ -386,6 +438,7 @@ class FakeSequence:
         self.out = None
         self.last_record = None
         self.prev = None               # the centroids of the last local frame: they live in the sequence, not in the output
+        self.wadd = 0                  # the weighting at the last add
 
     def close(self):
         self.end_output()
@@ -398,9 +451,10 @@ class FakeSequence:
 
     def _add(self, img):
         p = self.p
-        t = p.t
+        t = p.t if self.fault == "add_cutoff_ignores_weight" else p.wc()
         i = p.image_index(img)
         K, sw, sh, whole = p.ref.kept(i, t)
+        self.wadd = p.w
         if self.fault == "cutoff_read_at_palette_time":
             K = p.ref.kept(i, 0)[0]                    # kept as it came: the compaction is left to the palette step
         need = 4 * (self._n() + sw * sh)
@@ -447,7 +501,8 @@ class FakeSequence:
         W = np.ascontiguousarray(np.concatenate(parts, axis=0))
         whole = self.first_whole if self.fault != "cutoff_read_at_palette_time" else n == self.sw0 * self.sh0
         as_image = self.frames == 1 and whole
-        return p.ref.centroids_px(W, self.sw0 if as_image else n, self.sh0 if as_image else 1, k, p.fid())
+        wt = self.wadd if self.fault == "weight_read_at_add" else p.w        # the weighting: as it is at the palette call
+        return p.ref.centroids_px(W, self.sw0 if as_image else n, self.sh0 if as_image else 1, k, p.fid(), wt)
 
     def centroids(self, k):
         return self._centroids(k)
@@ -468,7 +523,7 @@ class FakeSequence:
         left = block.get("canvas")
         if self.fault == "canvas_survives_end_output" and left is not None and left.shape == canvas.shape:
             canvas = np.minimum(left, k)                                 # no fresh fill: what the block's last output showed
-        self.out = dict(k=k, mode=mode, fmt=format, t=p.t, cent=cent, canvas=canvas, held=np.zeros((height, width, 4), np.uint8),
+        self.out = dict(k=k, mode=mode, fmt=format, t=p.out_t(), cent=cent, canvas=canvas, held=np.zeros((height, width, 4), np.uint8),
                         frame=np.zeros((height, width, 4), np.uint8), block=block)
         self.last_record = None
         return p.ref.palette_bytes(cent)
@@ -519,12 +574,16 @@ class FakeSequence:
             o["have_prev"] = False                                       # (the frame after one that failed in its palette step starts cold)
         img = np.ascontiguousarray(image, np.uint8)
         i = p.image_index(img)
-        if p.ref.working(((i, t),)) is None:
+        wt = 0 if self.fault == "warm_frame_unweighted" and warm else p.w    # the weighting, as the cutoff: read at this call
+        tw = max(t, 1) if wt else t
+        if p.ref.working(((i, tw),)) is None:
             if self.fault == "failed_frame_touches_shown":
                 o["shown"] = np.zeros_like(o["shown"])
             raise FakeError(-1, "no pixel reaches alpha_cutoff")
         p.scratch()
-        cent = p.ref.warm(i, t, self.prev) if warm else p.ref.centroids(((i, t),), k, p.fid())
+        cent = p.ref.warm(i, tw, self.prev, wt) if warm else p.ref.centroids(((i, tw),), k, p.fid(), wt)
+        if self.fault == "output_cutoff_follows_weight" and p.w and t == 0:
+            t = 1
         I, P = p.ref.index(img, cent, o["mode"], t), p.ref.palette_bytes(cent)
         if tolerance is None:                                            # without delta the exact pass still runs: shown = P[I]
             d, o["shown"], rec = local_ref.colour(I, o["shown"], P, k)
@@ -597,11 +656,30 @@ class FakeLloyd:
         self.nconv = 0
         self.block = proc.take()
         self.f = min(self.block.get("n_fixed", 0), self.k) if fault == "n_fixed_inherited" else 0   # the device word of the block's last owner
-        self.bound = None
+        self.bound = None              # the caller's binding
+        self.init_bound = None         # the binding the initialisation left (forced colour table)
+        self.w = self.block.get("weighted", 0) if fault == "lloyd_weight_inherited" else 0
+        self.plain = None              # the pixel counts of the last weighted pass
 
     def close(self):
         self.block["n_fixed"] = self.f
+        self.block["weighted"] = self.w
         self.p.give(self.block)
+
+    def set_weighting(self, v):
+        if v not in (0, 1):
+            raise FakeError(-1, "unknown weighting")
+        if self.bound is not None and self.fault != "weight_set_under_binding":
+            raise FakeError(-1, "an image is bound")
+        if v != self.w and self.fault != "weighted_object_uses_binding":
+            self.init_bound = None                                       # ends in both directions
+        self.w = int(v)
+
+    def _wt(self, d_rgba, n):
+        """are the sums of a pass over these pixels weighted?"""
+        if self.fault == "weighted_object_uses_binding" and self.init_bound == (d_rgba, n):
+            return 0
+        return self.w
 
     def _image(self, ptr, n):
         return self.p.image_index(_view(ptr, 4 * n, np.uint8))
@@ -625,6 +703,8 @@ class FakeLloyd:
         if f > self.k:
             raise FakeError(-1, "more seeds than centroids")
         self.cent = self.p.ref.seeded(self._image(d_rgba, w * h), self.k, f)
+        if self.p.strategy == 2 and self.k > 1:                          # over the colour table: the image stays bound, by the library
+            self.init_bound, self.bound = (d_rgba, w * h), None
 
     def set_fixed(self, n_fixed):
         if n_fixed > self.k:
@@ -634,19 +714,27 @@ class FakeLloyd:
         self.f = int(n_fixed)
 
     def bind_image(self, d_rgba, n, stream=0):
-        self.bound = (d_rgba, n)
+        if self.w:
+            raise FakeError(-1, "the object's sums are weighted")
+        self.bound, self.init_bound = (d_rgba, n), None
 
     def unbind_image(self):
-        self.bound = None
+        self.bound = self.init_bound = None
 
     def converged_count(self, stream=0):
         return self.nconv
 
     def update(self, d_acc, stream=0):
-        self._step(self._acc(d_acc).copy())
+        sums = self._acc(d_acc).copy()
+        if self.fault == "zero_weight_cluster_counts_pixels" and self.w and self.plain is not None and self.plain.shape == sums.shape:
+            rows = (sums[:, 3] == 0) & (self.plain[:, 3] > 0)            # "not empty": it has pixels
+            sums[rows] = self.plain[rows]
+        self._step(sums)
 
     def assign_accumulate(self, d_rgba, n, d_labels, d_acc, stream=0):
-        labels, sums = self.p.ref.assign(self._image(d_rgba, n), self.cent)
+        i, wt = self._image(d_rgba, n), self._wt(d_rgba, n)
+        labels, sums = self.p.ref.assign(i, self.cent, wt)
+        self.plain = self.p.ref.assign(i, self.cent, 0)[1] if wt else None
         if d_labels:
             _view(d_labels, n, np.uint32)[:] = labels
         if d_acc:
@@ -666,18 +754,23 @@ class FakeLloyd:
         pass
 
     def run(self, d_rgba, n, d_labels=0, stream=0):
-        self.cent, labels, it = self.p.ref.run(self._image(d_rgba, n), self.cent, self.f)
+        self.cent, labels, it = self.p.ref.run(self._image(d_rgba, n), self.cent, self.f, self._wt(d_rgba, n))
+        self.init_bound = None                                           # made or taken over for this run, dropped before it returns
         self.nconv = 0
         if d_labels:
             _view(d_labels, n, np.uint32)[:] = labels
         return it
 
     def accumulate_into(self, d_rgba, n, d_acc, stream=0):
+        if self.w:
+            raise FakeError(-1, "the object's sums are weighted")
         if self.bound != (d_rgba, n):
             raise FakeError(-1, "the image is not bound")
         self._acc(d_acc)[:] += self.p.ref.assign(self._image(d_rgba, n), self.cent)[1]
 
     def labels_from_tables_update(self, d_rgba, n, d_labels, d_acc, stream=0):
+        if self.w:
+            raise FakeError(-1, "the object's sums are weighted")
         if self.bound is None:
             raise FakeError(-1, "no bound image")
         if self.k > 256:
@@ -704,6 +797,9 @@ class FakeEnv:
 
     def lloyd(self, proc, k):
         return FakeLloyd(proc, k, self.fault)
+
+    def set_weighting(self, proc, value):
+        proc.set_weighting(value)
 
     def index_plan(self, usage, palette, flags):
         planned = index_ref.plan(usage, palette, flags)
@@ -757,6 +853,11 @@ def campaign_2():
     return _campaign(SEEDS_2, FAULTS + FAULTS_2, 2)
 
 
+@pytest.fixture(scope="module")
+def campaign_3():
+    return _campaign(SEEDS_3, FAULTS + FAULTS_2 + FAULTS_3, 3)
+
+
 def test_generator_is_deterministic():
     assert H.generate(SEEDS[0], 1) == H.generate(SEEDS[0], 1)
     assert H.generate(SEEDS[0], 1) != H.generate(SEEDS[1], 1)
@@ -778,6 +879,12 @@ def test_faithful_stand_in_passes_every_sequence_of_surface_2(campaign_2):
     assert all(n > 0 for seed in SEEDS_2 for n in reused[seed]) and all(len(reused[s]) == SEQUENCES for s in SEEDS_2), reused
 
 
+def test_faithful_stand_in_passes_every_sequence_of_surface_3(campaign_3):
+    assert not campaign_3["failures"], "\n\n".join(campaign_3["failures"])
+    reused = campaign_3["reused"]
+    assert all(n > 0 for seed in SEEDS_3 for n in reused[seed]) and all(len(reused[s]) == SEQUENCES for s in SEEDS_3), reused
+
+
 # sha256 of repr(generate(seed, seq)) on the commit before surface 2 existed: the sessions of the old seeds never change
 PINNED = {
     201: ("9583056de68e9607bd6dc48e57fac0e98ea9ef1e700e99f80ff67861f48a5309", "a9220eb11068dd3887b9e29b693f33ad6198d868f915388d85772889113eec54",
@@ -787,6 +894,40 @@ PINNED = {
           "dbf61297a835f5e39a63bc7e2bad3825078a126864306ab9d4a0e069362965c2", "b39ddf06b2c417efa46d86c40bfbefbcb610e29e724ef21da68d1356ae84dbe2",
           "3035460b8c40bd9e7d23d242ccead673b1132903efde7f233640f793cbfc5975", "f8737bebd5eb4efddea290d3d1cac4ddb4b02a765c588e693adedb78adc352b0"),
 }
+
+
+# ... and of repr(generate(seed, seq, surface=2)) on the commit before surface 3 existed
+PINNED_2 = {
+    314: ("49309b4d407ca09b47f663d4c30ed2b2b0c5a53e1fec61e22009f921cfd97609", "201513196dab6bb60bfc7e09fa09350b16a174619006d6be3fae7dca730190c7",
+          "55d9f5daff0eaeb6e48cb0580a2498033d3aa4fa2641a2898141851a757c6695", "76c916704ac61e08ad3de1bb040da159f5e57e2d202c92bf0589cbe5cfef71ae",
+          "88aa550a65ed86108bdc714bc8108dcb447991a2c9b419a245d46b122f3911e0", "ccdd01752634f5d2dc2a45280daaf73d2eb028050e469a65d51905d3bf395ee5"),
+    315: ("6e11c95f09439fdc1f5f528b02f38ce7b040f2373a6d9a0d83ab9269f04ebcef", "0b8ec27d1b6ff7e3bd7b7ef8735d4c8eaa15ebecd93526ed04d6cc340249f7c5",
+          "9765e08acd84064eb4f7d38b1d92fe5edeba024442b3deaac34b3d7c191198a6", "fcd694726c11c0c0ffa60c474b7bc7a11a6799ee6e35ee7d695db959344443d8",
+          "8699f6627162b8a739234f6d14431033426a04862b568d272d4f826ba1d1fd24", "0a951a1aac38858d12d3c6dad528548e0cdd9a929358253aa53c80a920b41331"),
+}
+# sha256 over the bytes of the fourteen images of make_images(seed, 0) that existed before the importance map was appended
+PINNED_IMAGES = {201: "851b8715dfdba15b", 314: "791765901562b45a", 7: "cfdc31856e48d6fc"}
+
+
+@pytest.mark.parametrize("seed", SEEDS_2)
+def test_the_committed_sessions_of_surface_2_are_as_they_were(seed):
+    assert len(PINNED_2[seed]) == SEQUENCES
+    for seq in range(SEQUENCES):
+        ops = H.generate(seed, seq, surface=2)
+        assert hashlib.sha256(repr(ops).encode()).hexdigest() == PINNED_2[seed][seq], (seed, seq)
+        assert ops != H.generate(seed, seq, surface=3)
+        assert not {op[0] for op in ops} & set(NEW_OPS_3) and not {op[1] for op in ops if op[0] == "refuse"} & set(H.REFUSALS_3)
+        assert not any(op[1] == H.MAP for op in ops if op[0] in ("palette", "reduce", "reduce_indexed", "quality")) and \
+            not any(op[2] == H.MAP for op in ops if op[0] == "s_add")
+
+
+@pytest.mark.parametrize("seed", sorted(PINNED_IMAGES))
+def test_the_images_are_as_they_were(seed):
+    images = H.make_images(seed, 0)
+    assert [k for k, _ in images] == list(H.IMAGE_KINDS) and H.IMAGE_KINDS[H.MAP] == "map"
+    assert hashlib.sha256(b"".join(a.tobytes() for _, a in images[:14])).hexdigest()[:16] == PINNED_IMAGES[seed]
+    wmap = images[H.MAP][1]
+    assert wmap.shape == (67, 53, 4) and wmap[..., 3].min() >= 1            # every pixel kept at t <= 1: the working image is 2-D
 
 
 @pytest.mark.parametrize("seed", SEEDS)
@@ -811,6 +952,12 @@ def test_every_seed_of_surface_2_catches_the_faulty_stand_in(campaign_2, fault):
         assert fault in campaign_2["caught"][seed], f"seed {seed} does not catch {fault} in {SEQUENCES} sequences"
 
 
+@pytest.mark.parametrize("fault", FAULTS + FAULTS_2 + FAULTS_3)
+def test_every_seed_of_surface_3_catches_the_faulty_stand_in(campaign_3, fault):
+    for seed in SEEDS_3:
+        assert fault in campaign_3["caught"][seed], f"seed {seed} does not catch {fault} in {SEQUENCES} sequences"
+
+
 def _replays(caught, seed, fault, surface):
     """the replay(...) line a failing run prints runs again: it fails on the faulty stand-in and passes on the faithful one"""
     seq, _ = caught[seed][fault]
@@ -825,10 +972,12 @@ def _replays(caught, seed, fault, surface):
     return ops
 
 
-def test_a_mismatch_prints_a_list_that_replays(campaign, campaign_2):
+def test_a_mismatch_prints_a_list_that_replays(campaign, campaign_2, campaign_3):
     _replays(campaign["caught"], SEEDS[0], "plan_follows_cutoff", 1)
     ops = _replays(campaign_2["caught"], SEEDS_2[0], "lossy_full_keeps_lossy_canvas", 2)        # a printed list of surface 2
     assert {op[0] for op in ops} & set(NEW_OPS)
+    ops = _replays(campaign_3["caught"], SEEDS_3[0], "weight_read_at_add", 3)                   # ... and of surface 3
+    assert {op[0] for op in ops} & set(NEW_OPS_3)
 
 
 @pytest.mark.parametrize("seed", SEEDS)
@@ -873,7 +1022,14 @@ def _scenarios():
                                   "local_shared_local_on_one_sequence_with_the_refusals_between",
                                   "the_sequence_optimize_path_counts_plans_remaps_and_replays",
                                   "usage_records_outlive_their_maps_and_the_bad_count_combines",
-                                  "a_colour_keyed_canvas_of_the_caller_on_both_routes"])
+                                  "a_colour_keyed_canvas_of_the_caller_on_both_routes",
+                                  "weight_on_cutoff_0_128_0_weight_off_around_the_same_calls",
+                                  "two_frames_added_under_different_weightings_and_the_palette_both_ways",
+                                  "a_warm_output_alternates_weighted_and_unweighted_frames_across_a_cutoff_switch",
+                                  "the_binding_of_an_initialisation_and_of_the_caller_around_the_lloyd_weighting",
+                                  "weighted_and_unweighted_lloyd_objects_in_each_others_blocks_beside_weighted_host_calls",
+                                  "fixed_colours_and_weighting_with_clusters_of_weight_0",
+                                  "the_quality_search_weighted_then_unweighted"])
 def test_the_named_scenarios_of_the_device_are_legal_sequences(name):
     """the op lists tests/test_gpu_session.py runs on the device, on the faithful stand-in (one processor per list here)"""
     G = _scenarios()
@@ -984,3 +1140,53 @@ def test_coverage_of_the_committed_seeds_of_surface_2(campaign_2):
     wrong = {name: (c[name], EXACT_2[name]) for name in need if c[name] != EXACT_2[name] or EXACT_2[name] < 1}
     assert not wrong, wrong
     assert all(n > 0 for seed in SEEDS_2 for n in campaign_2["reused"][seed])      # blocks re-used, in every sequence
+
+
+# what the committed seeds of surface 3 give (SEEDS_3 x SEQUENCES), exactly, for what surface 3 adds.  None may be zero.
+EXACT_3 = {
+    'op:weight': 190, 'op:l_weight': 137, 'op:l_unbind': 12, 'op:motif': 73, 'refusal:weight_bad_value': 6,
+    'refusal:l_weight_bad_value': 8, 'refusal:octree_weighted': 12, 'refusal:l_weight_under_caller_binding': 30,
+    'refusal:weighted_bind': 18, 'refusal:weighted_lftu': 2, 'refusal:weighted_accumulate_into': 3,
+    'refusal:weighted_no_kept_pixel': 15, 'motif:weight_cutoff': 11, 'motif:weight_adds': 12, 'motif:weight_warm': 11,
+    'motif:weight_binding': 12, 'motif:weight_blocks': 11, 'motif:weight_fixed': 9, 'motif:weight_quality': 7,
+    'l_weight:0:owner_nobody': 48, 'l_weight:0:owner_init': 12, 'l_weight:0:owner_caller': 14, 'l_weight:1:owner_nobody': 47,
+    'l_weight:1:owner_init': 30, 'l_weight:1:owner_caller': 16, 'pass:l_assign:weighted': 16, 'pass:l_assign:unweighted': 34,
+    'pass:l_assign_update:weighted': 42, 'pass:l_assign_update:unweighted': 68, 'pass:l_iterate:weighted': 9,
+    'pass:l_iterate:unweighted': 3, 'pass:l_run:weighted': 33, 'pass:l_run:unweighted': 9, 'weighted_host:palette': 69,
+    'weighted_host:reduce': 33, 'weighted_host:reduce_indexed': 68, 'weighted_host:quality': 13, 'weighted_host:optimize': 5,
+    'octree_weighted:palette': 4, 'octree_weighted:reduce': 4, 'octree_weighted:reduce_indexed': 4,
+    'weighted_no_kept_pixel:palette': 5, 'weighted_no_kept_pixel:reduce': 5, 'weighted_no_kept_pixel:reduce_indexed': 5,
+    'weighted_host_at_cutoff_0': 105, 'host_call_on_the_map': 21, 'lloyd_pass_on_the_map': 74,
+    'lloyd_object_created_right_after_a_weighted_one_closed': 31, 'free_cluster_of_weight_0_with_pixels': 12,
+    'pinned_cluster_of_weight_0_with_pixels': 2, 'add_under_weighting': 50, 'add_under_weighting_loses_weight_0_pixels': 18,
+    'sequence_loop_weighted': 49, 'sequence_loop_unweighted': 108, 'sequence_loop_weighting_differs_from_an_add': 37,
+    'local_warm_weighted': 57, 'local_cold_weighted': 44, 'local_warm_weighting_differs_from_last_frame': 44,
+    'quality_weighting_changes_the_palette': 6,
+}
+
+
+def coverage_names_3():
+    """what surface 3 adds: every new op, refusal and motif; both binding owners crossed with both values of the Lloyd setter (under
+    the caller's binding the call is the listed refusal); every pass of a Lloyd object and every palette call of the processor under
+    weighting; the moments at which the switch is read"""
+    return ["op:" + o for o in NEW_OPS_3] + ["refusal:" + r for r in H.REFUSALS_3] + ["motif:" + mo for mo in H.MOTIFS_3] + \
+           [f"l_weight:{v}:owner_{who}" for v in (0, 1) for who in ("nobody", "init", "caller")] + \
+           [f"pass:{p}:{w}" for p in ("l_assign", "l_assign_update", "l_iterate", "l_run") for w in ("weighted", "unweighted")] + \
+           ["weighted_host:" + n for n in ("palette", "reduce", "reduce_indexed", "quality", "optimize")] + \
+           [f"{r}:{call}" for r in ("octree_weighted", "weighted_no_kept_pixel") for call in ("palette", "reduce", "reduce_indexed")] + \
+           ["weighted_host_at_cutoff_0", "host_call_on_the_map", "lloyd_pass_on_the_map", "lloyd_object_created_right_after_a_weighted_one_closed",
+            "free_cluster_of_weight_0_with_pixels", "pinned_cluster_of_weight_0_with_pixels", "add_under_weighting",
+            "add_under_weighting_loses_weight_0_pixels", "sequence_loop_weighted", "sequence_loop_unweighted",
+            "sequence_loop_weighting_differs_from_an_add", "local_warm_weighted", "local_cold_weighted",
+            "local_warm_weighting_differs_from_last_frame", "quality_weighting_changes_the_palette"]
+
+
+def test_coverage_of_the_committed_seeds_of_surface_3(campaign_3):
+    c = campaign_3["counters"]
+    print({name: c[name] for name in coverage_names_3()}, campaign_3["ops"])
+    assert not campaign_3["failures"]
+    need = coverage_names_3()
+    assert set(need) == set(EXACT_3), sorted(set(need) ^ set(EXACT_3))
+    wrong = {name: (c[name], EXACT_3[name]) for name in need if c[name] != EXACT_3[name] or EXACT_3[name] < 1}
+    assert not wrong, wrong
+    assert all(n > 0 for seed in SEEDS_3 for n in campaign_3["reused"][seed])      # blocks re-used, in every sequence

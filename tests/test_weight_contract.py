@@ -156,3 +156,18 @@ def test_surface_is_declared_everywhere():
     assert "kmg_processor_set_weighting" in open(os.path.join(ROOT, "kmeans-gpu_amd", "host", "kmeans_color_gpu.hpp")).read()
     assert "pub fn kmg_processor_set_weighting" in open(os.path.join(ROOT, "rust-shim", "src", "ffi.rs")).read()
     assert "pub fn set_alpha_weight" in open(os.path.join(ROOT, "rust-shim", "src", "lib.rs")).read()
+
+
+def test_the_problem_of_the_pixel_bound_is_feasible(oracle):
+    """the host side of tests/test_gpu_weight.py::test_sums_at_the_pixel_bound needs no device: 2^28 pixels in closed form, runs of
+    1 .. 5, and expected sums that reach 2^62 and -2^60 and stay below 2^63"""
+    import test_gpu_weight as G
+    P = G._bound_problem(oracle)
+    G._bound_feasible(P)
+    assert sum(P["counts"]) == G.N_BOUND == 1 << 28
+    tile = P["tile"]
+    runs = np.diff(np.flatnonzero(np.r_[True, tile[1:] != tile[:-1], True]))
+    assert runs.min() == 1 and runs.max() == 5 and G.TILE % 4 != 0          # runs straddle the 4-pixel groups
+    # the counts of the closed form against a count of the whole pattern, one repetition at a time
+    reps, tail = divmod(G.N_BOUND, G.TILE)
+    assert list(P["counts"]) == [int(reps * (tile == c).sum() + (tile[:tail] == c).sum()) for c in range(64)]

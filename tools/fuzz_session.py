@@ -4,7 +4,9 @@ cutoff, fixed colours, strategy), host calls, output passes and plans, error rec
 canvases, two Lloyd objects with seeds and n_fixed, two Sequence objects with their outputs -- all closed and re-created in each
 other's blocks, every result compared byte for byte after every call, every refused call with the status include/kmeans_hip.h
 names.  Surface 2 adds outputs with per-frame palettes (cold and warm), colour-keyed canvases of the caller's and the index-map
-optimisation (usage records, plans, remaps, kmg_index_optimize) to the same objects, switches and blocks.  A mismatch prints the op
+optimisation (usage records, plans, remaps, kmg_index_optimize) to the same objects, switches and blocks.  Surface 3 adds alpha
+weighting: kmg_processor_set_weighting turned on and off between all of those calls, kmg_lloyd_set_weighting on the two Lloyd
+objects, with the bindings of the initialisation and of the caller around it, and the refusals of both.  A mismatch prints the op
 list (replay() of the harness runs it) and ends the run: nothing more is started on the device.
 usage: fuzz_session.py [sequences] [seed] [surface]"""
 import os, sys, time
