@@ -1,6 +1,7 @@
 // kmg_api.hip -- the host-buffer calls of the C ABI (include/kmeans_hip.h): ImageProcessor::{palette, find, reduce}
-// (core/src/lib.rs:67-164) -- argument checking, upload, the host sequencing of operations.rs on top of kmg_lloyd_* / kmg_dev_apply,
-// download.  There is no CPU data path in this file: every per-pixel step is a kernel launch.
+// (core/src/lib.rs:67-164) -- argument checking (the shared checks: kmg_checks.h), upload, the host sequencing of operations.rs on
+// top of kmg_lloyd_* / kmg_dev_apply, download.  A call starts with a CallStart; kmg_find / kmg_find_indexed and kmg_reduce /
+// kmg_reduce_indexed are one body each.  There is no CPU data path in this file: every per-pixel step is a kernel launch.
 
 #include "kmg_state.h"
 
@@ -17,10 +18,7 @@ struct LloydGuard {
 int check_image(const kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h)
 {
     if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
-    if (!rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "image pointer is NULL");
-    if (w == 0 || h == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "image has zero width or height");
-    if ((uint64_t)w * h > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
-    return KMG_OK;
+    return check_image_buffer(rgba, w, h);
 }
 
 // The working image of the k-means palette step (operations.rs:15-88 extract_palette_kmeans before its loop): the image after the
@@ -38,7 +36,6 @@ struct WorkingImage {
 int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t alpha_cutoff, int weighting, hipStream_t st,
                   WorkingImage &wi)
 {
-    int rc;
     alpha_cutoff = working_cutoff(alpha_cutoff, weighting);
     wi.weighting = weighting;
     const uint8_t *src = d_rgba;
@@ -48,7 +45,7 @@ int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t 
     if (m && (w > m || h > m)) {                                       // structures.rs:67-74
         kmg_resized_dims(w, h, m, &sw, &sh);
         HIP_TRY(small.alloc(p, (size_t)sw * sh * 4, st));
-        if ((rc = kmg_dev_resize(p, d_rgba, w, h, sw, sh, (uint8_t *)small.ptr, st)) != KMG_OK) return rc;
+        KMG_TRY(kmg_dev_resize(p, d_rgba, w, h, sw, sh, (uint8_t *)small.ptr, st));
         src = (const uint8_t *)small.ptr;
     }
     StreamBuf &kept = wi.kept;
@@ -56,7 +53,7 @@ int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t 
         const uint64_t n = (uint64_t)sw * sh;
         HIP_TRY(kept.alloc(p, (size_t)n * 4 + 256, st));               // (the count behind the pixels, 256-byte aligned)
         uint64_t *d_count = (uint64_t *)((uint8_t *)kept.ptr + pad256((size_t)n * 4));
-        if ((rc = kmg_dev_alpha_compact(p, src, n, alpha_cutoff, (uint8_t *)kept.ptr, d_count, st)) != KMG_OK) return rc;
+        KMG_TRY(kmg_dev_alpha_compact(p, src, n, alpha_cutoff, (uint8_t *)kept.ptr, d_count, st));
         uint64_t n_kept = 0;
         HIP_TRY(hipMemcpyAsync(&n_kept, d_count, sizeof n_kept, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -83,16 +80,15 @@ int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t 
 int kmg::palette_of_working(kmg_processor *p, const uint8_t *src, uint32_t sw, uint32_t sh, uint32_t k, hipStream_t st, float *c4,
                             uint32_t *d_labels, const float *fixed4, uint32_t n_fixed, int weighting)
 {
-    int rc;
     LloydGuard g;
     if (weighting && (uint64_t)sw * sh > kMaxWeightedPixels)
         return fail(KMG_ERR_UNSUPPORTED, "alpha weighting: the working image has %llu pixels, more than 2^28", (unsigned long long)((uint64_t)sw * sh));
     if (n_fixed > k) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u is below the %u fixed colours of the processor", k, n_fixed);
-    if ((rc = lloyd_create_impl(p, k, &g.s, st)) != KMG_OK) return rc;
-    if ((rc = kmg_lloyd_init_centroids_seeded(g.s, src, sw, sh, fixed4, n_fixed, st)) != KMG_OK) return rc;   // operations.rs:73
-    if ((rc = kmg_lloyd_set_fixed(g.s, n_fixed)) != KMG_OK) return rc;
+    KMG_TRY(lloyd_create_impl(p, k, &g.s, st));
+    KMG_TRY(kmg_lloyd_init_centroids_seeded(g.s, src, sw, sh, fixed4, n_fixed, st));   // operations.rs:73
+    KMG_TRY(kmg_lloyd_set_fixed(g.s, n_fixed));
     // (after the initialisation, which is unweighted and may have bound the image: a weighted loop drops that binding)
-    if ((rc = kmg_lloyd_set_weighting(g.s, weighting)) != KMG_OK) return rc;
+    KMG_TRY(kmg_lloyd_set_weighting(g.s, weighting));
     if (log_debug()) {
         std::vector<float> c(4 * k);
         if (kmg_lloyd_get_centroids(g.s, c.data(), st) == KMG_OK) {
@@ -102,15 +98,14 @@ int kmg::palette_of_working(kmg_processor *p, const uint8_t *src, uint32_t sw, u
         }
     }
     uint32_t it = 0;
-    if ((rc = kmg_lloyd_run(g.s, src, (uint64_t)sw * sh, nullptr, &it, st)) != KMG_OK) return rc;  // operations.rs:85
-    if ((rc = kmg_lloyd_get_centroids(g.s, c4, st)) != KMG_OK) return rc;
+    KMG_TRY(kmg_lloyd_run(g.s, src, (uint64_t)sw * sh, nullptr, &it, st));  // operations.rs:85
+    KMG_TRY(kmg_lloyd_get_centroids(g.s, c4, st));
     if (log_debug()) {
         fprintf(stderr, "[kmeans_hip] == Final centroids at iteration %u: ==\n", it);
         for (uint32_t i = 0; i < k; ++i)
             fprintf(stderr, "[kmeans_hip] Centroid %u = [%g, %g, %g, %g]\n", i, c4[4 * i], c4[4 * i + 1], c4[4 * i + 2], c4[4 * i + 3]);
     }
-    if (d_labels && (rc = kmg_lloyd_labels(g.s, src, (uint64_t)sw * sh, d_labels, st)) != KMG_OK) return rc;
-    return KMG_OK;
+    return d_labels ? kmg_lloyd_labels(g.s, src, (uint64_t)sw * sh, d_labels, st) : KMG_OK;
 }
 
 namespace {
@@ -127,9 +122,8 @@ int palette_of_working(kmg_processor *p, const WorkingImage &wi, uint32_t k, hip
 int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff,
                            int weighting, hipStream_t st, float *c4, const FixedList &fixed)
 {
-    int rc;
     WorkingImage wi;
-    if ((rc = working_image(p, d_rgba, w, h, alpha_cutoff, weighting, st, wi)) != KMG_OK) return rc;
+    KMG_TRY(working_image(p, d_rgba, w, h, alpha_cutoff, weighting, st, wi));
     return palette_of_working(p, wi, k, st, c4, fixed);
 }
 
@@ -138,15 +132,14 @@ int extract_palette_kmeans(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, 
 int kmg::local_frame_centroids(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t k, uint32_t alpha_cutoff,
                                hipStream_t st, float *c4, const float *fixed4, uint32_t n_fixed, const float *warm4, int weighting)
 {
-    int rc;
     WorkingImage wi;
-    if ((rc = working_image(p, d_rgba, w, h, alpha_cutoff, weighting, st, wi)) != KMG_OK) return rc;
+    KMG_TRY(working_image(p, d_rgba, w, h, alpha_cutoff, weighting, st, wi));
     if (!warm4) return kmg::palette_of_working(p, wi.src, wi.sw, wi.sh, k, st, c4, nullptr, fixed4, n_fixed, weighting);
     LloydGuard g;
-    if ((rc = lloyd_create_impl(p, k, &g.s, st)) != KMG_OK) return rc;
-    if ((rc = kmg_lloyd_init_centroids_seeded(g.s, wi.src, wi.sw, wi.sh, warm4, k, st)) != KMG_OK) return rc;
-    if ((rc = kmg_lloyd_set_weighting(g.s, weighting)) != KMG_OK) return rc;
-    if ((rc = kmg_lloyd_run(g.s, wi.src, (uint64_t)wi.sw * wi.sh, nullptr, nullptr, st)) != KMG_OK) return rc;
+    KMG_TRY(lloyd_create_impl(p, k, &g.s, st));
+    KMG_TRY(kmg_lloyd_init_centroids_seeded(g.s, wi.src, wi.sw, wi.sh, warm4, k, st));
+    KMG_TRY(kmg_lloyd_set_weighting(g.s, weighting));
+    KMG_TRY(kmg_lloyd_run(g.s, wi.src, (uint64_t)wi.sw * wi.sh, nullptr, nullptr, st));
     return kmg_lloyd_get_centroids(g.s, c4, st);
 }
 
@@ -231,13 +224,12 @@ int upload_image(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, 
 // find_colors / dither_colors + OutputTexture::pull_image (structures.rs:441-470)
 // (format: kmg_output_format; out_rgba then holds 4, 1 or 2 bytes per pixel)
 int apply_and_download(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, const float *c4,
-                       uint32_t k, int mode, uint32_t alpha_cutoff, hipStream_t st, uint8_t *out_rgba, int format = KMG_FORMAT_RGBA8)
+                       uint32_t k, int mode, uint32_t alpha_cutoff, hipStream_t st, uint8_t *out_rgba, int format)
 {
-    int rc;
     StreamBuf out;
     const size_t bytes = (size_t)w * h * (format == KMG_FORMAT_INDEX8 ? 1u : format == KMG_FORMAT_INDEX16 ? 2u : 4u);
     HIP_TRY(out.alloc(p, bytes, st));
-    if ((rc = dev_apply(p, d_rgba, w, h, 0, c4, k, mode, (uint8_t *)out.ptr, st, alpha_cutoff, format)) != KMG_OK) return rc;
+    KMG_TRY(dev_apply(p, d_rgba, w, h, 0, c4, k, mode, (uint8_t *)out.ptr, st, alpha_cutoff, format));
     HIP_TRY(copy_host_image(p, out_rgba, out.ptr, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return KMG_OK;
@@ -250,14 +242,13 @@ int octree_palette_of(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint3
                       hipStream_t st, std::vector<std::array<uint8_t, 4>> &colors)
 {
     const uint32_t MAX_SIZE = 128;                                     // lib.rs:293
-    int rc;
     uint32_t sw = w, sh = h;
     const uint8_t *src = d_rgba;
     StreamBuf small;
     if (w > MAX_SIZE || h > MAX_SIZE) {
         kmg_resized_dims(w, h, MAX_SIZE, &sw, &sh);
         HIP_TRY(small.alloc(p, (size_t)sw * sh * 4, st));
-        if ((rc = kmg_dev_resize(p, d_rgba, w, h, sw, sh, (uint8_t *)small.ptr, st)) != KMG_OK) return rc;
+        KMG_TRY(kmg_dev_resize(p, d_rgba, w, h, sw, sh, (uint8_t *)small.ptr, st));
         src = (const uint8_t *)small.ptr;
     }
     std::vector<uint8_t> host((size_t)sw * sh * 4);
@@ -323,163 +314,152 @@ try {
 }
 KMG_ABI_CATCH
 
+namespace {
+
+// What every host-buffer call on a processor takes at its start.  snapshot(): the processor's settings as they are now -- the
+// call keeps them to its end -- taken before any device work, so that the refusals that need no device come first.  begin(): the
+// device part -- the call's own stream and the image on the device.
+struct CallStart {
+    FixedList fixed;
+    int weighting = KMG_WEIGHT_NONE;
+    uint32_t alpha_cutoff = 0;
+    StreamGuard sg;
+    StreamBuf img;
+    void snapshot(kmg_processor *p)
+    {
+        fixed = fixed_snapshot(p);
+        weighting = p->weighting.load(std::memory_order_relaxed);
+        alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
+    }
+    int begin(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h)
+    {
+        HIP_TRY(hipSetDevice(p->device));
+        HIP_TRY(sg.acquire(p));
+        return upload_image(p, rgba, w, h, sg.st, img);
+    }
+    const uint8_t *d_rgba() const { return (const uint8_t *)img.ptr; }
+};
+
+double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b)
+{
+    return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
+// kmg_find / kmg_find_indexed
+int find_call(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, const uint8_t *palette_rgba, uint32_t n_colors, int mode,
+              int format, uint8_t *out)
+{
+    KMG_TRY(check_image(p, rgba, w, h));
+    if (!palette_rgba || n_colors == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "palette is empty");
+    if (!out) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
+    KMG_TRY(check_format(format));
+    CallStart c;
+    c.snapshot(p);
+    std::vector<float> c4(4 * (size_t)n_colors);
+    KMG_TRY(kmg_palette_to_centroids(palette_rgba, n_colors, c4.data()));   // lib.rs:86-87
+    KMG_TRY(c.begin(p, rgba, w, h));
+    return apply_and_download(p, c.d_rgba(), w, h, c4.data(), n_colors, mode, c.alpha_cutoff, c.sg.st, out, format);
+}
+
+// kmg_reduce (no palette outputs) / kmg_reduce_indexed (palette_out: the palette comes back in index order as the bytes the
+// output pass writes -- lab_to_rgb.wgsl of each centroid, kmg_apply.hip's plan palette)
+int reduce_call(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t color_count, int algo, int mode, int format,
+                bool palette_out, uint8_t *out_palette_rgba, uint32_t *out_count, uint8_t *out)
+{
+    KMG_TRY(check_image(p, rgba, w, h));
+    KMG_TRY(check_k_nonzero(color_count));
+    if (!out || (palette_out && (!out_palette_rgba || !out_count))) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
+    KMG_TRY(check_algo(algo));
+    KMG_TRY(check_mode(mode));
+    KMG_TRY(check_format(format));
+    if (algo == KMG_ALGO_KMEANS) KMG_TRY(check_k_limit(color_count));
+    CallStart c;
+    c.snapshot(p);
+    KMG_TRY(check_fixed(c.fixed, color_count, algo, c.weighting));
+    const auto t0 = std::chrono::steady_clock::now();
+    KMG_TRY(c.begin(p, rgba, w, h));
+    const auto t1 = std::chrono::steady_clock::now();
+    std::vector<float> c4;
+    if (algo == KMG_ALGO_OCTREE) {                                     // lib.rs:133-136
+        std::vector<std::array<uint8_t, 4>> colors;
+        KMG_TRY(octree_palette_of(p, c.d_rgba(), w, h, color_count, c.alpha_cutoff, c.sg.st, colors));
+        KMG_TRY(octree_centroids(colors, c4));
+    } else {
+        c4.resize(4 * (size_t)color_count);
+        KMG_TRY(extract_palette_kmeans(p, c.d_rgba(), w, h, color_count, c.alpha_cutoff, c.weighting, c.sg.st, c4.data(), c.fixed));
+    }
+    const auto t2 = std::chrono::steady_clock::now();
+    const uint32_t k = (uint32_t)(c4.size() / 4);
+    KMG_TRY(apply_and_download(p, c.d_rgba(), w, h, c4.data(), k, mode, c.alpha_cutoff, c.sg.st, out, format));
+    if (log_debug())
+        fprintf(stderr, "[kmeans_hip] reduce %ux%u k=%u: upload %.2f ms, palette %.2f ms, output pass + download %.2f ms\n", w, h, k,
+                ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, std::chrono::steady_clock::now()));
+    if (palette_out) {
+        for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], out_palette_rgba + 4 * i);
+        *out_count = k;
+    }
+    return KMG_OK;
+}
+
+}  // namespace
+
+int kmg::octree_centroids(const std::vector<std::array<uint8_t, 4>> &colors, std::vector<float> &c4)
+{
+    if (colors.empty()) return fail(KMG_ERR_INVALID_ARGUMENT, "the octree returned no colour");
+    if (colors.size() > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "the octree returned %zu colours, more than KMG_MAX_K = %u", colors.size(), KMG_MAX_K);
+    c4.resize(4 * colors.size());
+    return kmg_palette_to_centroids(colors[0].data(), (uint32_t)colors.size(), c4.data());
+}
+
 extern "C" int kmg_find(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, const uint8_t *palette_rgba,
                         uint32_t n_colors, int mode, uint8_t *out_rgba)
 try {
-    int rc;
-    if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
-    if (!palette_rgba || n_colors == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "palette is empty");
-    if (!out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-    HIP_TRY(hipSetDevice(p->device));
-    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
-    StreamGuard sg;
-    HIP_TRY(sg.acquire(p));
-    std::vector<float> c4(4 * (size_t)n_colors);
-    if ((rc = kmg_palette_to_centroids(palette_rgba, n_colors, c4.data())) != KMG_OK) return rc;  // lib.rs:86-87
-    StreamBuf img;
-    if ((rc = upload_image(p, rgba, w, h, sg.st, img)) != KMG_OK) return rc;
-    return apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), n_colors, mode, alpha_cutoff, sg.st, out_rgba);
+    return find_call(p, rgba, w, h, palette_rgba, n_colors, mode, KMG_FORMAT_RGBA8, out_rgba);
 }
 KMG_ABI_CATCH
 
 extern "C" int kmg_find_indexed(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, const uint8_t *palette_rgba,
                                 uint32_t n_colors, int mode, int format, void *out_index)
 try {
-    int rc;
-    if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
-    if (!palette_rgba || n_colors == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "palette is empty");
-    if (!out_index) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-    if (format < KMG_FORMAT_RGBA8 || format > KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
-    HIP_TRY(hipSetDevice(p->device));
-    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
-    StreamGuard sg;
-    HIP_TRY(sg.acquire(p));
-    std::vector<float> c4(4 * (size_t)n_colors);
-    if ((rc = kmg_palette_to_centroids(palette_rgba, n_colors, c4.data())) != KMG_OK) return rc;
-    StreamBuf img;
-    if ((rc = upload_image(p, rgba, w, h, sg.st, img)) != KMG_OK) return rc;
-    return apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), n_colors, mode, alpha_cutoff, sg.st, (uint8_t *)out_index, format);
+    return find_call(p, rgba, w, h, palette_rgba, n_colors, mode, format, (uint8_t *)out_index);
 }
 KMG_ABI_CATCH
 
-// kmg_reduce with an output format; the palette comes back in index order as the bytes the output pass writes (lab_to_rgb.wgsl of
-// each centroid -- kmg_apply.hip's plan palette)
 extern "C" int kmg_reduce_indexed(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t color_count, int algo,
                                   int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out_index)
 try {
-    int rc;
-    if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
-    if (color_count == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
-    if (!out_index || !out_palette_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-    if (algo != KMG_ALGO_KMEANS && algo != KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown algorithm %d", algo);
-    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_DIFFUSE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
-    if (format < KMG_FORMAT_RGBA8 || format > KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
-    if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
-        return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
-    const FixedList fixed = fixed_snapshot(p);
-    const int weighting = p->weighting.load(std::memory_order_relaxed);
-    if ((rc = check_fixed(fixed, color_count, algo, weighting)) != KMG_OK) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
-    StreamGuard sg;
-    HIP_TRY(sg.acquire(p));
-    StreamBuf img;
-    if ((rc = upload_image(p, rgba, w, h, sg.st, img)) != KMG_OK) return rc;
-    std::vector<float> c4;
-    if (algo == KMG_ALGO_OCTREE) {                                     // lib.rs:133-136
-        std::vector<std::array<uint8_t, 4>> colors;
-        if ((rc = octree_palette_of(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, colors)) != KMG_OK) return rc;
-        if (colors.empty()) return fail(KMG_ERR_INVALID_ARGUMENT, "the octree returned no colour");
-        if (colors.size() > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "the octree returned %zu colours, more than KMG_MAX_K = %u", colors.size(), KMG_MAX_K);
-        c4.resize(4 * colors.size());
-        if ((rc = kmg_palette_to_centroids(colors[0].data(), (uint32_t)colors.size(), c4.data())) != KMG_OK) return rc;
-    } else {
-        c4.resize(4 * (size_t)color_count);
-        if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, weighting, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
-    }
-    const uint32_t k = (uint32_t)(c4.size() / 4);
-    if ((rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), k, mode, alpha_cutoff, sg.st, (uint8_t *)out_index, format)) != KMG_OK)
-        return rc;
-    for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], out_palette_rgba + 4 * i);
-    *out_count = k;
-    return KMG_OK;
+    return reduce_call(p, rgba, w, h, color_count, algo, mode, format, true, out_palette_rgba, out_count, (uint8_t *)out_index);
 }
 KMG_ABI_CATCH
 
 extern "C" int kmg_reduce(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t color_count,
                           int algo, int mode, uint8_t *out_rgba)
 try {
-    int rc;
-    if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
-    if (color_count == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
-    if (!out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-    if (algo != KMG_ALGO_KMEANS && algo != KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown algorithm %d", algo);
-    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_DIFFUSE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
-    if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
-        return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
-    const FixedList fixed = fixed_snapshot(p);
-    const int weighting = p->weighting.load(std::memory_order_relaxed);
-    if ((rc = check_fixed(fixed, color_count, algo, weighting)) != KMG_OK) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
-    StreamGuard sg;
-    HIP_TRY(sg.acquire(p));
-    StreamBuf img;
-    const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = upload_image(p, rgba, w, h, sg.st, img)) != KMG_OK) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
-    if (algo == KMG_ALGO_OCTREE) {                                     // lib.rs:133-136
-        std::vector<std::array<uint8_t, 4>> colors;
-        if ((rc = octree_palette_of(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, colors)) != KMG_OK) return rc;
-        if (colors.empty()) return fail(KMG_ERR_INVALID_ARGUMENT, "the octree returned no colour");
-        if (colors.size() > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "the octree returned %zu colours, more than KMG_MAX_K = %u", colors.size(), KMG_MAX_K);
-        std::vector<float> oc4(4 * colors.size());
-        if ((rc = kmg_palette_to_centroids(colors[0].data(), (uint32_t)colors.size(), oc4.data())) != KMG_OK) return rc;
-        return apply_and_download(p, (const uint8_t *)img.ptr, w, h, oc4.data(), (uint32_t)colors.size(), mode, alpha_cutoff, sg.st, out_rgba);
-    }
-    std::vector<float> c4(4 * (size_t)color_count);
-    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, weighting, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
-    const auto t2 = std::chrono::steady_clock::now();
-    rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, c4.data(), color_count, mode, alpha_cutoff, sg.st, out_rgba);
-    if (log_debug()) {
-        const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-            return std::chrono::duration<double, std::milli>(b - a).count();
-        };
-        fprintf(stderr, "[kmeans_hip] reduce %ux%u k=%u: upload %.2f ms, palette %.2f ms, output pass + download %.2f ms\n", w, h,
-                color_count, ms(t0, t1), ms(t1, t2), ms(t2, std::chrono::steady_clock::now()));
-    }
-    return rc;
+    return reduce_call(p, rgba, w, h, color_count, algo, mode, KMG_FORMAT_RGBA8, false, nullptr, nullptr, out_rgba);
 }
 KMG_ABI_CATCH
 
 extern "C" int kmg_palette(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t color_count,
                            int algo, uint8_t *out_rgba, uint32_t *out_count)
 try {
-    int rc;
-    if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
-    if (color_count == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
+    KMG_TRY(check_image(p, rgba, w, h));
+    KMG_TRY(check_k_nonzero(color_count));
     if (!out_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-    if (algo != KMG_ALGO_KMEANS && algo != KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown algorithm %d", algo);
-    if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K)
-        return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
-    const FixedList fixed = fixed_snapshot(p);
-    const int weighting = p->weighting.load(std::memory_order_relaxed);
-    if ((rc = check_fixed(fixed, color_count, algo, weighting)) != KMG_OK) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
-    StreamGuard sg;
-    HIP_TRY(sg.acquire(p));
-    StreamBuf img;
-    if ((rc = upload_image(p, rgba, w, h, sg.st, img)) != KMG_OK) return rc;
+    KMG_TRY(check_algo(algo));
+    if (algo == KMG_ALGO_KMEANS) KMG_TRY(check_k_limit(color_count));
+    CallStart c;
+    c.snapshot(p);
+    KMG_TRY(check_fixed(c.fixed, color_count, algo, c.weighting));
+    KMG_TRY(c.begin(p, rgba, w, h));
     if (algo == KMG_ALGO_OCTREE) {                                     // lib.rs:288-331
         std::vector<std::array<uint8_t, 4>> colors;
-        if ((rc = octree_palette_of(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, sg.st, colors)) != KMG_OK) return rc;
+        KMG_TRY(octree_palette_of(p, c.d_rgba(), w, h, color_count, c.alpha_cutoff, c.sg.st, colors));
         for (size_t i = 0; i < colors.size(); ++i) memcpy(out_rgba + 4 * i, colors[i].data(), 4);
         *out_count = (uint32_t)colors.size();
         return KMG_OK;
     }
     std::vector<float> c4(4 * (size_t)color_count);
-    if ((rc = extract_palette_kmeans(p, (const uint8_t *)img.ptr, w, h, color_count, alpha_cutoff, weighting, sg.st, c4.data(), fixed)) != KMG_OK) return rc;
+    KMG_TRY(extract_palette_kmeans(p, c.d_rgba(), w, h, color_count, c.alpha_cutoff, c.weighting, c.sg.st, c4.data(), c.fixed));
     sorted_palette_of(c4.data(), color_count, out_rgba);
     *out_count = color_count;
     return KMG_OK;
@@ -490,8 +470,6 @@ KMG_ABI_CATCH
 // error statistics and the quality-targeted colour count (include/kmeans_hip.h at kmg_error_stats; kernels: kmg_error.hip)
 // ---------------------------------------------------------------------------------------------
 namespace {
-
-void free_host_copy(void *copy) { delete[] static_cast<uint8_t *>(copy); }
 
 // kmg_dev_compare with the output's form given (kmg_kernels.h kErrorRgba8 .. kErrorLabel32).  Enqueues on st: for the index forms
 // the palette's upload from a heap copy of the caller's bytes (released by the stream once the copy has run), the launch that
@@ -505,8 +483,7 @@ int dev_compare_form(kmg_processor *p, const uint8_t *d_src, const void *d_out, 
     if (alpha_cutoff > 255u) return fail(KMG_ERR_INVALID_ARGUMENT, "alpha cutoff %u is above 255", alpha_cutoff);
     if (form != kErrorRgba8) {
         if (!palette_rgba || k == 0 || k > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "an index format needs a palette of 1 .. %u colours", KMG_MAX_K);
-        if (form == kErrorIndex8 && k + (alpha_cutoff ? 1u : 0u) > 256u)
-            return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u%s needs INDEX16", k, alpha_cutoff ? " plus the transparent slot" : "");
+        KMG_TRY(check_index8_room(form == kErrorIndex8, "k", k, alpha_cutoff != 0));
         if (form == kErrorIndex16 && (reinterpret_cast<uintptr_t>(d_out) & 1u)) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX16 output is not 2-byte aligned");
     }
     if (!p || !d_src || !d_out || !d_stats || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad compare arguments");
@@ -522,16 +499,7 @@ int dev_compare_form(kmg_processor *p, const uint8_t *d_src, const void *d_out, 
     const size_t ent_bytes = pad256(error_palette_bytes(k));
     HIP_TRY(tab.alloc(p, ent_bytes + (size_t)k * 4, st));
     uint32_t *d_pal = (uint32_t *)((uint8_t *)tab.ptr + ent_bytes);
-    uint8_t *copy = new uint8_t[(size_t)k * 4];
-    memcpy(copy, palette_rgba, (size_t)k * 4);
-    hipError_t e = hipMemcpyAsync(d_pal, copy, (size_t)k * 4, hipMemcpyHostToDevice, st);
-    const hipError_t e2 = hipLaunchHostFunc(st, free_host_copy, copy);
-    if (e2 != hipSuccess) {                                            // (not enqueued: wait for the copy, release here)
-        (void)hipStreamSynchronize(st);
-        delete[] copy;
-    }
-    HIP_TRY(e);
-    HIP_TRY(e2);
+    HIP_TRY(upload_host_copy(d_pal, palette_rgba, (size_t)k * 4, st));
     if (what & KMG_ERROR_LAB) HIP_TRY(launch_error_palette(d_pal, k, p->d_lut, tab.ptr, st));
     HIP_TRY(launch_error_stats(form, what, (const uint32_t *)d_src, d_out, n, d_pal, tab.ptr, k, alpha_cutoff, p->d_lut, stats, st));
     return KMG_OK;
@@ -548,45 +516,37 @@ extern "C" int kmg_dev_compare(kmg_processor *p, const uint8_t *d_src_rgba, cons
                                const uint8_t *palette_rgba, uint32_t k, uint32_t alpha_cutoff, uint32_t what, kmg_error_stats *d_stats,
                                void *stream)
 try {
-    const int form = format_form(format);
-    if (form < 0) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
-    return dev_compare_form(p, d_src_rgba, d_out, n_pixels, form, palette_rgba, k, alpha_cutoff, what, d_stats, S(stream));
+    KMG_TRY(check_format(format));
+    return dev_compare_form(p, d_src_rgba, d_out, n_pixels, format_form(format), palette_rgba, k, alpha_cutoff, what, d_stats, S(stream));
 }
 KMG_ABI_CATCH
 
 extern "C" int kmg_compare(kmg_processor *p, const uint8_t *src_rgba, const void *out, uint32_t w, uint32_t h, int format,
                            const uint8_t *palette_rgba, uint32_t k, uint32_t what, kmg_error_stats *stats)
 try {
-    int rc;
     // (the refusals that need no device come first)
+    KMG_TRY(check_format(format));
     const int form = format_form(format);
-    if (form < 0) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
     if (what == 0 || (what & ~(KMG_ERROR_RGB | KMG_ERROR_LAB))) return fail(KMG_ERR_INVALID_ARGUMENT, "what = %u: KMG_ERROR_RGB | KMG_ERROR_LAB", what);
     if (form != kErrorRgba8 && (!palette_rgba || k == 0 || k > KMG_MAX_K))
         return fail(KMG_ERR_INVALID_ARGUMENT, "an index format needs a palette of 1 .. %u colours", KMG_MAX_K);
-    if (form == kErrorIndex8 && k > 256u) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u needs INDEX16", k);
-    if ((rc = check_image(p, src_rgba, w, h)) != KMG_OK) return rc;
+    KMG_TRY(check_index8_room(form == kErrorIndex8, "k", k, false));
+    KMG_TRY(check_image(p, src_rgba, w, h));
     if (!out || !stats) return fail(KMG_ERR_INVALID_ARGUMENT, "output or statistics pointer is NULL");
-    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
-    if (form == kErrorIndex8 && k + (alpha_cutoff ? 1u : 0u) > 256u)
-        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u%s needs INDEX16", k, alpha_cutoff ? " plus the transparent slot" : "");
-    HIP_TRY(hipSetDevice(p->device));
-    StreamGuard sg;
-    HIP_TRY(sg.acquire(p));
+    CallStart c;
+    c.snapshot(p);
+    KMG_TRY(check_index8_room(form == kErrorIndex8, "k", k, c.alpha_cutoff != 0));
+    KMG_TRY(c.begin(p, src_rgba, w, h));
+    hipStream_t st = c.sg.st;
     const size_t n = (size_t)w * h, out_bytes = n * (form == kErrorIndex8 ? 1u : form == kErrorIndex16 ? 2u : 4u);
-    StreamBuf img, res, rec;
-    if ((rc = upload_image(p, src_rgba, w, h, sg.st, img)) != KMG_OK) return rc;
-    HIP_TRY(res.alloc(p, out_bytes, sg.st));
-    HIP_TRY(copy_host_image(p, res.ptr, out, out_bytes, hipMemcpyHostToDevice, sg.st));
-    HIP_TRY(rec.alloc(p, sizeof(kmg_error_stats), sg.st));
-    HIP_TRY(hipMemsetAsync(rec.ptr, 0, sizeof(kmg_error_stats), sg.st));
-    if ((rc = dev_compare_form(p, (const uint8_t *)img.ptr, res.ptr, n, form, palette_rgba, k, alpha_cutoff, what, (kmg_error_stats *)rec.ptr,
-                               sg.st)) != KMG_OK) {
-        (void)hipStreamSynchronize(sg.st);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(stats, rec.ptr, sizeof(kmg_error_stats), hipMemcpyDeviceToHost, sg.st));
-    HIP_TRY(hipStreamSynchronize(sg.st));
+    StreamBuf res, rec;
+    HIP_TRY(res.alloc(p, out_bytes, st));
+    HIP_TRY(copy_host_image(p, res.ptr, out, out_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(rec.alloc(p, sizeof(kmg_error_stats), st));
+    HIP_TRY(hipMemsetAsync(rec.ptr, 0, sizeof(kmg_error_stats), st));
+    KMG_TRY_DRAIN(st, dev_compare_form(p, c.d_rgba(), res.ptr, n, form, palette_rgba, k, c.alpha_cutoff, what, (kmg_error_stats *)rec.ptr, st));
+    HIP_TRY(hipMemcpyAsync(stats, rec.ptr, sizeof(kmg_error_stats), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return KMG_OK;
 }
 KMG_ABI_CATCH
@@ -595,30 +555,24 @@ extern "C" int kmg_reduce_quality(kmg_processor *p, const uint8_t *rgba, uint32_
                                   uint32_t target, int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out,
                                   kmg_error_stats *achieved, int *reached)
 try {
-    int rc;
     // (the refusals that need no device come first)
     if (k_min < 1 || k_min > k_max || k_max > KMG_MAX_K)
         return fail(KMG_ERR_INVALID_ARGUMENT, "colour counts [%u, %u]: 1 <= k_min <= k_max <= %u", k_min, k_max, KMG_MAX_K);
-    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_DIFFUSE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
-    if (format < KMG_FORMAT_RGBA8 || format > KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
-    if (format != KMG_FORMAT_RGBA8 && mode == KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "meld blends two colours: it has no index output");
-    if (format == KMG_FORMAT_INDEX8 && k_max > 256u) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k_max = %u needs INDEX16", k_max);
-    if ((rc = check_image(p, rgba, w, h)) != KMG_OK) return rc;
+    KMG_TRY(check_mode(mode));
+    KMG_TRY(check_format(format));
+    KMG_TRY(check_meld_format(mode, format));
+    KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k_max", k_max, false));
+    KMG_TRY(check_image(p, rgba, w, h));
     if (!out || !out_palette_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-    const FixedList fixed = fixed_snapshot(p);
-    const int weighting = p->weighting.load(std::memory_order_relaxed);
-    if ((rc = check_fixed(fixed, k_min, KMG_ALGO_KMEANS, weighting)) != KMG_OK) return rc;
-    const uint32_t alpha_cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
-    if (format == KMG_FORMAT_INDEX8 && k_max + (alpha_cutoff ? 1u : 0u) > 256u)
-        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k_max = %u%s needs INDEX16", k_max, alpha_cutoff ? " plus the transparent slot" : "");
-    HIP_TRY(hipSetDevice(p->device));
-    StreamGuard sg;
-    HIP_TRY(sg.acquire(p));
-    hipStream_t st = sg.st;
-    StreamBuf img;
-    if ((rc = upload_image(p, rgba, w, h, st, img)) != KMG_OK) return rc;
+    CallStart c;
+    c.snapshot(p);
+    KMG_TRY(check_fixed(c.fixed, k_min, KMG_ALGO_KMEANS, c.weighting));
+    KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k_max", k_max, c.alpha_cutoff != 0));
+    KMG_TRY(c.begin(p, rgba, w, h));
+    hipStream_t st = c.sg.st;
+    const FixedList &fixed = c.fixed;
     WorkingImage wi;                                                   // uploaded, shrunk and compacted once
-    if ((rc = working_image(p, (const uint8_t *)img.ptr, w, h, alpha_cutoff, weighting, st, wi)) != KMG_OK) return rc;
+    KMG_TRY(working_image(p, c.d_rgba(), w, h, c.alpha_cutoff, c.weighting, st, wi));
     const uint64_t nw = (uint64_t)wi.sw * wi.sh;
     StreamBuf labels, rec;
     HIP_TRY(labels.alloc(p, (size_t)nw * 4, st));
@@ -630,12 +584,11 @@ try {
     kmg_error_stats cur, best;
     uint32_t runs = 0;
     auto evaluate = [&](uint32_t k, bool *accepted) -> int {
-        int r;
-        if ((r = palette_of_working(p, wi, k, st, c4.data(), fixed, (uint32_t *)labels.ptr)) != KMG_OK) return r;
+        KMG_TRY(palette_of_working(p, wi, k, st, c4.data(), fixed, (uint32_t *)labels.ptr));
         for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], &pal[4 * i]);
         HIP_TRY(hipMemsetAsync(rec.ptr, 0, sizeof(kmg_error_stats), st));
-        if ((r = dev_compare_form(p, wi.src, labels.ptr, nw, kErrorLabel32, pal.data(), k, 0, KMG_ERROR_RGB | KMG_ERROR_LAB,
-                                  (kmg_error_stats *)rec.ptr, st)) != KMG_OK) return r;
+        KMG_TRY(dev_compare_form(p, wi.src, labels.ptr, nw, kErrorLabel32, pal.data(), k, 0, KMG_ERROR_RGB | KMG_ERROR_LAB,
+                                 (kmg_error_stats *)rec.ptr, st));
         HIP_TRY(hipMemcpyAsync(&cur, rec.ptr, sizeof cur, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         ++runs;
@@ -649,21 +602,20 @@ try {
 
     bool ok = false;
     uint32_t k_star = k_max;
-    if ((rc = evaluate(k_max, &ok)) != KMG_OK) return rc;
+    KMG_TRY(evaluate(k_max, &ok));
     keep(k_max);
     const int did_reach = ok ? 1 : 0;
     if (ok) {
         uint32_t lo = k_min, hi = k_max;
         while (lo < hi) {
             const uint32_t mid = lo + (hi - lo) / 2;
-            if ((rc = evaluate(mid, &ok)) != KMG_OK) return rc;
+            KMG_TRY(evaluate(mid, &ok));
             if (ok) { hi = mid; keep(mid); }
             else lo = mid + 1;
         }
         k_star = hi;
     }
-    if ((rc = apply_and_download(p, (const uint8_t *)img.ptr, w, h, best_c4.data(), k_star, mode, alpha_cutoff, st, (uint8_t *)out, format)) != KMG_OK)
-        return rc;
+    KMG_TRY(apply_and_download(p, c.d_rgba(), w, h, best_c4.data(), k_star, mode, c.alpha_cutoff, st, (uint8_t *)out, format));
     for (uint32_t i = 0; i < k_star; ++i) shader_lab_to_rgba8(&best_c4[4 * i], out_palette_rgba + 4 * i);
     *out_count = k_star;
     if (achieved) *achieved = best;

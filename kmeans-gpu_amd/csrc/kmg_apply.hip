@@ -228,11 +228,9 @@ struct kmg_apply_plan {
 // slot in alpha mode), and every centroid lies in the box inside which the dither scan's sentinel never wins.
 static int check_index_format(const float *c4, uint32_t k, int mode, int format, uint32_t alpha_cutoff)
 {
-    if (format != KMG_FORMAT_INDEX8 && format != KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
-    if (mode == KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "meld blends two colours: it has no index output");
-    const uint32_t slots = k + (alpha_cutoff ? 1u : 0u);
-    if (format == KMG_FORMAT_INDEX8 && slots > 256u)
-        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u%s needs INDEX16", k, alpha_cutoff ? " plus the transparent slot" : "");
+    KMG_TRY(check_format(format));                                     // (the caller has dealt with KMG_FORMAT_RGBA8)
+    KMG_TRY(check_meld_format(mode, format));
+    KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k", k, alpha_cutoff != 0));
     for (uint32_t i = 0; i < k; ++i) {
         const float L = c4[4 * i], a = c4[4 * i + 1], b = c4[4 * i + 2];
         if (!(L >= kIndexBoxLmin && L <= kIndexBoxLmax && a >= -kIndexBoxAB && a <= kIndexBoxAB && b >= -kIndexBoxAB && b <= kIndexBoxAB))
@@ -247,9 +245,8 @@ static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, 
 {
     if (!p || !c4 || !out || k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply_plan arguments");
     *out = nullptr;
-    if (k > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", k, KMG_MAX_K);
-    if (mode != KMG_MODE_REPLACE && mode != KMG_MODE_DITHER && mode != KMG_MODE_MELD && mode != KMG_MODE_DIFFUSE)
-        return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
+    KMG_TRY(check_k_limit(k));
+    KMG_TRY(check_mode(mode));
     int rc0;
     if (format != KMG_FORMAT_RGBA8 && (rc0 = check_index_format(c4, k, mode, format, alpha_cutoff)) != KMG_OK) return rc0;
     HIP_TRY(hipSetDevice(p->device));

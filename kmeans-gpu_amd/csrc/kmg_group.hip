@@ -26,25 +26,12 @@
 #include <thread>
 #include <vector>
 
+#include "kmg_checks.h"
 #include "kmg_internal.h"
 #include "kmg_kernels.h"
 #include "kmg_table.h"
 
 using namespace kmg;
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP,       \
-                        "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-#define KMG_TRY(expr)                                                                          \
-    do {                                                                                       \
-        const int rc_ = (expr);                                                                \
-        if (rc_ != KMG_OK) return rc_;                                                         \
-    } while (0)
 
 namespace {
 
@@ -713,7 +700,7 @@ int rank_prepare(kmg_group_lloyd *gl, GroupRank &r, uint32_t image)
     if (q.cells) {
         // once per image: the band's histogram, all-reduced into the image's; this rank's share of the colour cube
         const uint64_t n_total = (uint64_t)q.width * q.height;
-        if (n_total > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
+        KMG_TRY(check_pixel_count(n_total));
         // (a rank without rows still takes its share of the cube: the table of ONE dummy pixel, its count taken out again)
         const uint8_t *dummy = (const uint8_t *)gl->blocks[r.idx].d_dummy;
         if (q.n_local) KMG_TRY(kmg_lloyd_bind_image(q.s, q.band, q.n_local, r.st));
@@ -1197,19 +1184,6 @@ struct HostCall {
     kmg_group_lloyd *gl = nullptr;       // sharded full-resolution k-means
 };
 
-// k-means of a small device-resident image on one device (operations.rs:15-88 without the shrink)
-int kmeans_small(kmg_processor *p, const uint8_t *d_img, uint32_t w, uint32_t h, uint32_t k, hipStream_t st, float *c4)
-{
-    kmg_lloyd *s = nullptr;
-    KMG_TRY(kmg_lloyd_create(p, k, &s));
-    int rc = kmg_lloyd_init_centroids(s, d_img, w, h, st);                      // operations.rs:73
-    uint32_t it = 0;
-    if (rc == KMG_OK) rc = kmg_lloyd_run(s, d_img, (uint64_t)w * h, nullptr, &it, st);   // operations.rs:85
-    if (rc == KMG_OK) rc = kmg_lloyd_get_centroids(s, c4, st);
-    kmg_lloyd_destroy(s);
-    return rc;
-}
-
 int host_call_rank(kmg_group *g, HostCall &c, GroupRank &r)
 {
     uint32_t r0, r1;
@@ -1253,11 +1227,8 @@ int host_call_rank(kmg_group *g, HostCall &c, GroupRank &r)
             const uint8_t *host_img = c.shrink ? c.shrunk.data() : c.rgba;
             if (c.algo == KMG_ALGO_OCTREE) {
                 c.colors = octree_sorted_palette(host_img, (uint64_t)c.sw * c.sh, c.k);            // lib.rs:288-331
-                if (c.colors.empty()) return fail(KMG_ERR_INVALID_ARGUMENT, "the octree returned no colour");
-                if (c.colors.size() > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "the octree returned %zu colours, more than KMG_MAX_K = %u", c.colors.size(), KMG_MAX_K);
+                KMG_TRY(octree_centroids(c.colors, c.c4));
                 c.k = (uint32_t)c.colors.size();
-                c.c4.resize(4u * (size_t)c.k);
-                KMG_TRY(kmg_palette_to_centroids(c.colors[0].data(), c.k, c.c4.data()));
             } else {
                 const uint8_t *d_img = (const uint8_t *)r.d_in;          // a group of one holds the whole image already
                 if (c.shrink || g->n_local > 1) {
@@ -1266,7 +1237,8 @@ int host_call_rank(kmg_group *g, HostCall &c, GroupRank &r)
                     HIP_TRY(hipMemcpyAsync(r.d_small, host_img, bytes, hipMemcpyHostToDevice, r.st));
                     d_img = (const uint8_t *)r.d_small;
                 }
-                KMG_TRY(kmeans_small(r.p, d_img, c.sw, c.sh, c.k, r.st, c.c4.data()));
+                // k-means of a small device-resident image on one device (operations.rs:15-88 without the shrink)
+                KMG_TRY(palette_of_working(r.p, d_img, c.sw, c.sh, c.k, r.st, c.c4.data()));
             }
         }
         KMG_TRY(meet());
@@ -1284,9 +1256,7 @@ int host_call_rank(kmg_group *g, HostCall &c, GroupRank &r)
 int host_call(kmg_group *g, HostCall &c)
 {
     if (!g) return fail(KMG_ERR_INVALID_ARGUMENT, "group is NULL");
-    if (!c.rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "image pointer is NULL");
-    if (c.w == 0 || c.h == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "image has zero width or height");
-    if ((uint64_t)c.w * c.h > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
+    KMG_TRY(check_image_buffer(c.rgba, c.w, c.h));
     if (g->world != g->n_local) return fail(KMG_ERR_UNSUPPORTED, "the host-buffer calls of a group need all its ranks in one process");
     std::lock_guard<std::mutex> lock(g->call_mu);
     const kmg_options &o = g->opt.processor;
@@ -1343,10 +1313,10 @@ extern "C" int kmg_group_palette(kmg_group *g, const uint8_t *rgba, uint32_t wid
                                  uint8_t *out_rgba, uint32_t *out_count)
 try {
     KMG_TRY(refuse_fixed(g));
-    if (color_count == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
+    KMG_TRY(check_k_nonzero(color_count));
     if (!out_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-    if (algo != KMG_ALGO_KMEANS && algo != KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown algorithm %d", algo);
-    if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
+    KMG_TRY(check_algo(algo));
+    if (algo == KMG_ALGO_KMEANS) KMG_TRY(check_k_limit(color_count));
     HostCall c;
     c.rgba = rgba; c.w = width; c.h = height; c.k = color_count; c.algo = algo; c.want_palette = true;
     KMG_TRY(host_call(g, c));
@@ -1366,8 +1336,8 @@ extern "C" int kmg_group_find(kmg_group *g, const uint8_t *rgba, uint32_t width,
 try {
     if (!palette_rgba || n_colors == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "palette is empty");
     if (!out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
-    if (n_colors > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", n_colors, KMG_MAX_K);
+    KMG_TRY(check_mode(mode, KMG_MODE_MELD));
+    KMG_TRY(check_k_limit(n_colors));
     HostCall c;
     c.rgba = rgba; c.w = width; c.h = height; c.k = n_colors; c.mode = mode; c.want_output = true; c.out = out_rgba;
     c.c4.resize(4u * (size_t)n_colors);
@@ -1380,11 +1350,11 @@ extern "C" int kmg_group_reduce(kmg_group *g, const uint8_t *rgba, uint32_t widt
                                 int mode, uint8_t *out_rgba)
 try {
     KMG_TRY(refuse_fixed(g));
-    if (color_count == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
+    KMG_TRY(check_k_nonzero(color_count));
     if (!out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-    if (algo != KMG_ALGO_KMEANS && algo != KMG_ALGO_OCTREE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown algorithm %d", algo);
-    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
-    if (algo == KMG_ALGO_KMEANS && color_count > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", color_count, KMG_MAX_K);
+    KMG_TRY(check_algo(algo));
+    KMG_TRY(check_mode(mode, KMG_MODE_MELD));
+    if (algo == KMG_ALGO_KMEANS) KMG_TRY(check_k_limit(color_count));
     HostCall c;
     c.rgba = rgba; c.w = width; c.h = height; c.k = color_count; c.algo = algo; c.mode = mode;
     c.want_palette = true; c.want_output = true; c.out = out_rgba;
@@ -1397,7 +1367,7 @@ extern "C" int kmg_group_reduce_batch(kmg_group *g, uint32_t n_images, const uin
 try {
     if (!g || !rgba || !widths || !heights || !out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "bad group_reduce_batch arguments");
     KMG_TRY(refuse_fixed(g));
-    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);   // (no diffusion)
+    KMG_TRY(check_mode(mode, KMG_MODE_MELD));                          // (no diffusion)
     if (g->world != g->n_local) return fail(KMG_ERR_UNSUPPORTED, "the host-buffer calls of a group need all its ranks in one process");
     std::lock_guard<std::mutex> lock(g->call_mu);
     // whole images per device, no exchange of any kind: a failure of one image must not leave the others' ranks waiting

@@ -43,11 +43,29 @@ int abi_trap() noexcept;
 #define KMG_ABI_CATCH_VOID catch (...) { (void)kmg::abi_trap(); }
 #define KMG_ABI_CATCH_NULL catch (...) { (void)kmg::abi_trap(); return nullptr; }
 
+// early return from a function that returns a status: a HIP call that failed (the message names it), a library call that failed
+// (it has set the message itself)
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return fail(e_ == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP,       \
+                        "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+#define KMG_TRY(expr)                                                                          \
+    do {                                                                                       \
+        const int rc_ = (expr);                                                                \
+        if (rc_ != KMG_OK) return rc_;                                                         \
+    } while (0)
+
 // lib.rs:255-286 kmeans_palette: CentroidsBuffer::pull_values (palette-crate Lab -> sRGB8) of a k-means centroid table, then
 // sorted ascending by the palette-crate Lab L of the 8-bit colour.  out_rgba: k x 4 bytes.
 void sorted_palette_of(const float *centroids4, uint32_t k, uint8_t *out_rgba);
 // lib.rs:288-331 octree_palette on a host image already shrunk to <= 128: the reference's CPU octree, sorted by L
 std::vector<std::array<uint8_t, 4>> octree_sorted_palette(const uint8_t *host_rgba, uint64_t n_pixels, uint32_t color_count);
+// an octree's colour list -> centroid table, 4 floats per colour (kmg_api.hip): refuses an empty list and one of more than KMG_MAX_K
+int octree_centroids(const std::vector<std::array<uint8_t, 4>> &colors, std::vector<float> &centroids4);
 
 // kmg_dev_apply with the alpha cutoff given (kmg_apply.hip): the host-buffer calls read the processor's once per call
 int dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, const float *centroids4, uint32_t k,

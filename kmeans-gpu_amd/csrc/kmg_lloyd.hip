@@ -161,7 +161,7 @@ static int bind_image_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, void
     if (s->side) HIP_TRY(hipStreamSynchronize(s->side));             // label passes of the previous binding
     s->lab_pending[0] = s->lab_pending[1] = false;
     // the histogram counts, partition totals and prefix sums are u32 (kmg_table.hip)
-    if (n > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
+    KMG_TRY(check_pixel_count(n));
     HIP_TRY(hipSetDevice(s->p->device));
     int rc;
     if ((rc = ensure_bounds(s->p, S(stream))) != KMG_OK) return rc;
@@ -618,8 +618,7 @@ int lloyd_create_impl(kmg_processor *p, uint32_t k, kmg_lloyd **out, hipStream_t
 {
     if (!p || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "bad lloyd_create arguments");
     *out = nullptr;
-    if (k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");  // args.rs:160-171
-    if (k > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", k, KMG_MAX_K);
+    KMG_TRY(check_k(k));
     HIP_TRY(hipSetDevice(p->device));
     kmg_lloyd *s = new (std::nothrow) kmg_lloyd();
     if (!s) return fail(KMG_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -785,7 +784,7 @@ try {
     if (!s || !d_rgba || !w || !h) return fail(KMG_ERR_INVALID_ARGUMENT, "bad init_centroids arguments");
     HIP_TRY(hipSetDevice(s->p->device));
     const uint64_t n = (uint64_t)w * h;
-    if (n > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
+    KMG_TRY(check_pixel_count(n));
     s->tab.tables_valid = false;
     // plus_plus_init.wgsl:161-168: rand(42) = 0.5625, rand(12) = 0.93359375 in IEEE binary32
     const int32_t x0 = (int32_t)((float)w * 0.5625f);
@@ -883,7 +882,7 @@ try {
         if ((i & 3u) != 3u && !(seeds4[i] - seeds4[i] == 0.0f)) return fail(KMG_ERR_INVALID_ARGUMENT, "init_centroids_seeded: seed %u is not finite", i / 4u);
     HIP_TRY(hipSetDevice(s->p->device));
     const uint64_t n = (uint64_t)w * h;
-    if (n > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
+    KMG_TRY(check_pixel_count(n));
     s->tab.tables_valid = false;
     std::vector<Centroid> seeds(n_seeds);
     for (uint32_t i = 0; i < n_seeds; ++i) {
@@ -975,7 +974,7 @@ extern "C" int kmg_lloyd_init_step(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t
 try {
     if (!s || !d_key || j == 0 || j >= s->k || (n_local && !d_rgba))
         return fail(KMG_ERR_INVALID_ARGUMENT, "bad init_step arguments");
-    if (first_index + n_local > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
+    KMG_TRY(check_pixel_count(first_index + n_local));
     HIP_TRY(hipSetDevice(s->p->device));
     s->tab.tables_valid = false;
     HIP_TRY(hipMemsetAsync(d_key, 0, sizeof(uint64_t), S(stream)));

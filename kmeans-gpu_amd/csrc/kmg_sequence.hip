@@ -14,6 +14,9 @@
 //                    the frame output -- one apply plan, the frame buffers, the canvas and its held source (lossy frames:
 //                    kmg_hold.hip) in one block.
 
+#include <initializer_list>
+#include <utility>
+
 #include "kmg_pass.h"
 #include "kmg_state.h"
 
@@ -174,12 +177,13 @@ hipError_t frame_delta_typed(const void *index, void *canvas, void *delta, uint6
     return hipGetLastError();
 }
 
+int delta_needs_index() { return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8"); }
+
 int frame_delta_impl(kmg_processor *p, const void *d_index, void *d_canvas, uint32_t width, uint32_t rows, uint32_t row0, int format,
                      uint32_t k, void *d_delta, kmg_frame_delta *d_info, hipStream_t st)
 {
     static_assert(sizeof(kmg_frame_delta) == 32, "kmg_frame_delta is 32 bytes");
-    const int rc = check_index_band("frame_delta", false, p, d_index, d_canvas, d_delta, nullptr, nullptr, d_info, width, rows, row0, format, k);
-    if (rc != KMG_OK) return rc;
+    KMG_TRY(check_index_band("frame_delta", false, p, d_index, d_canvas, d_delta, nullptr, nullptr, d_info, width, rows, row0, format, k));
     const uint64_t n = (uint64_t)width * rows;
     HIP_TRY(hipSetDevice(p->device));
     unsigned long long *info = reinterpret_cast<unsigned long long *>(d_info);
@@ -194,10 +198,10 @@ int check_index_band(const char *name, bool lossy, const kmg_processor *p, const
                      const void *d_src, const void *d_held, const void *d_info, uint32_t width, uint32_t rows, uint32_t row0, int format,
                      uint32_t k)
 {
-    if (format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8");
-    if (format != KMG_FORMAT_INDEX8 && format != KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
+    if (format == KMG_FORMAT_RGBA8) return delta_needs_index();
+    KMG_TRY(check_format(format));
     if (k == 0 || k > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "k = %u: 1 .. %u", k, KMG_MAX_K);
-    if (format == KMG_FORMAT_INDEX8 && k > 255u) return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u plus the transparent slot needs INDEX16", k);
+    KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k", k, true));
     if (!p || !d_index || !d_canvas || !d_delta || !d_info || (lossy && (!d_src || !d_held)))
         return fail(KMG_ERR_INVALID_ARGUMENT, "%s: a pointer is NULL", name);
     if (width == 0 || rows == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "%s: the band has zero width or no rows", name);
@@ -298,11 +302,8 @@ int reserve(kmg_sequence *s, uint64_t extra, hipStream_t st)
 // mode -- the kept pixels in raster order.  Returns with `st` drained, so W is complete whatever stream the next call uses.
 int add_frame(kmg_sequence *s, const uint8_t *rgba, bool on_host, uint32_t w, uint32_t h, hipStream_t st)
 {
-    int rc;
     kmg_processor *p = s->p;
-    if (!rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "image pointer is NULL");
-    if (w == 0 || h == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "image has zero width or height");
-    if ((uint64_t)w * h > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
+    KMG_TRY(check_image_buffer(rgba, w, h));
     HIP_TRY(hipSetDevice(p->device));
     // (alpha weighting, as it is now, cuts this frame's working pixels at max(alpha_cutoff, 1): kmg_processor_set_weighting)
     const uint32_t cutoff = working_cutoff(p->alpha_cutoff.load(std::memory_order_relaxed), processor_weighting(p));
@@ -312,7 +313,7 @@ int add_frame(kmg_sequence *s, const uint8_t *rgba, bool on_host, uint32_t w, ui
     if (shrink) kmg_resized_dims(w, h, m, &sw, &sh);
     const uint64_t ns = (uint64_t)sw * sh;
     if (!cutoff && s->n + ns > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "the working sequence would reach 2^32 pixels");
-    if ((rc = reserve(s, ns, st)) != KMG_OK) return rc;
+    KMG_TRY(reserve(s, ns, st));
     uint8_t *tail = (uint8_t *)s->w_blk + (size_t)s->n * 4;
     const size_t bytes = (size_t)w * h * 4;
 
@@ -328,13 +329,13 @@ int add_frame(kmg_sequence *s, const uint8_t *rgba, bool on_host, uint32_t w, ui
     if (shrink) {
         uint8_t *dst = tail;
         if (cutoff) { HIP_TRY(small.alloc(p, (size_t)ns * 4, st)); dst = (uint8_t *)small.ptr; }
-        if ((rc = kmg_dev_resize(p, src, w, h, sw, sh, dst, st)) != KMG_OK) return rc;
+        KMG_TRY(kmg_dev_resize(p, src, w, h, sw, sh, dst, st));
         src = dst;
     }
     uint64_t n_kept = ns;
     if (cutoff) {
         HIP_TRY(count.alloc(p, 256, st));
-        if ((rc = kmg_dev_alpha_compact(p, src, ns, cutoff, tail, (uint64_t *)count.ptr, st)) != KMG_OK) return rc;
+        KMG_TRY(kmg_dev_alpha_compact(p, src, ns, cutoff, tail, (uint64_t *)count.ptr, st));
         HIP_TRY(hipMemcpyAsync(&n_kept, count.ptr, sizeof n_kept, hipMemcpyDeviceToHost, st));
     } else if (src != tail) {
         HIP_TRY(hipMemcpyAsync(tail, src, (size_t)ns * 4, hipMemcpyDeviceToDevice, st));
@@ -350,8 +351,7 @@ int add_frame(kmg_sequence *s, const uint8_t *rgba, bool on_host, uint32_t w, ui
 // the palette step on W: a new Lloyd problem of k centroids
 int sequence_centroids(kmg_sequence *s, uint32_t k, float *c4)
 {
-    if (k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
-    if (k > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", k, KMG_MAX_K);
+    KMG_TRY(check_k(k));
     if (s->n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "no pixel reaches alpha_cutoff (the working sequence is empty)");
     // (the processor's fixed colours, as they are when this call starts: kmg_processor_set_fixed_colors)
     const std::shared_ptr<const std::vector<float>> fixed = fixed_snapshot(s->p);
@@ -436,46 +436,75 @@ KMG_ABI_CATCH
 
 extern "C" int kmg_sequence_palette(kmg_sequence *s, uint32_t k, uint8_t *out_rgba, uint32_t *out_count)
 try {
-    int rc;
     if (!s || !out_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_palette: a pointer is NULL");
-    if (k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
-    if (k > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", k, KMG_MAX_K);
+    KMG_TRY(check_k(k));
     std::vector<float> c4(4 * (size_t)k);
-    if ((rc = sequence_centroids(s, k, c4.data())) != KMG_OK) return rc;
+    KMG_TRY(sequence_centroids(s, k, c4.data()));
     sorted_palette_of(c4.data(), k, out_rgba);
     *out_count = k;
     return KMG_OK;
 }
 KMG_ABI_CATCH
 
+namespace {
+
+// what both kinds of output ask of the mode, the format and the colour count they are opened with (index_only: per-frame palettes)
+int check_output_form(uint32_t k, int mode, int format, bool index_only)
+{
+    KMG_TRY(check_mode(mode));
+    if (index_only && format == KMG_FORMAT_RGBA8)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "per-frame palettes need an index format (INDEX8 / INDEX16), not RGBA8");
+    KMG_TRY(check_format(format));
+    KMG_TRY(check_meld_format(mode, format));
+    return check_index8_room(format == KMG_FORMAT_INDEX8, "k", k, true);
+}
+
+// The output block: one sub-buffer per entry of `parts` (where its pointer goes, its bytes), each padded to 256 bytes, one behind
+// the other, then the record.
+int output_block(kmg_sequence *s, std::initializer_list<std::pair<uint8_t **, size_t>> parts)
+{
+    size_t total = 256;
+    for (const auto &part : parts) total += pad256(part.second);
+    HIP_TRY(block_take(s->p, total, &s->o_blk, &s->o_cap));
+    uint8_t *at = (uint8_t *)s->o_blk;
+    for (const auto &part : parts) {
+        *part.first = at;
+        at += pad256(part.second);
+    }
+    s->d_info = (kmg_frame_hold *)at;
+    return KMG_OK;
+}
+
+// the last step of a begin: the canvas fill `e`, enqueued on the sequence's stream, has run; the output is open
+int output_opened(kmg_sequence *s, hipError_t e, uint32_t k, int mode, int format, uint32_t width, uint32_t height)
+{
+    if (e == hipSuccess) e = hipStreamSynchronize(s->sg.st);
+    if (e != hipSuccess) {
+        output_end(s);
+        return fail(KMG_ERR_HIP, "filling the canvas failed: %s", hipGetErrorString(e));
+    }
+    s->k = k; s->mode = mode; s->format = format; s->width = width; s->height = height;
+    return KMG_OK;
+}
+
+}  // namespace
+
 extern "C" int kmg_sequence_output_begin(kmg_sequence *s, uint32_t k, int mode, int format, uint32_t width, uint32_t height,
                                          uint8_t *out_palette_rgba, uint32_t *out_count)
 try {
-    int rc;
     if (!s || !out_palette_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_begin: a pointer is NULL");
     output_end(s);                                                     // a second begin ends the first
-    if (width == 0 || height == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "image has zero width or height");
-    if ((uint64_t)width * height > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
-    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_DIFFUSE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
-    if (format < KMG_FORMAT_RGBA8 || format > KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
-    if (format != KMG_FORMAT_RGBA8 && mode == KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "meld blends two colours: it has no index output");
-    if (format == KMG_FORMAT_INDEX8 && k > 255u)
-        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u plus the transparent slot needs INDEX16", k);
+    KMG_TRY(check_image_size(width, height));
+    KMG_TRY(check_output_form(k, mode, format, false));
     std::vector<float> c4(4 * (size_t)std::max(k, 1u));
-    if ((rc = sequence_centroids(s, k, c4.data())) != KMG_OK) return rc;
-    kmg_processor *p = s->p;
+    KMG_TRY(sequence_centroids(s, k, c4.data()));
     hipStream_t st = s->sg.st;
     const size_t n = (size_t)width * height, es = format_bytes(format);
-    const bool indexed = format != KMG_FORMAT_RGBA8;
-    const size_t frame_b = pad256(n * 4), map_b = pad256(n * es);
-    HIP_TRY(block_take(p, frame_b + map_b * (indexed ? 3u : 1u) + (indexed ? frame_b : 0u) + 256, &s->o_blk, &s->o_cap));
-    s->d_frame = (uint8_t *)s->o_blk;
-    s->d_map = s->d_frame + frame_b;
-    s->d_canvas = indexed ? s->d_map + map_b : nullptr;
-    s->d_delta = indexed ? s->d_canvas + map_b : nullptr;
-    s->d_held = indexed ? s->d_delta + map_b : nullptr;                // (a canvas of k holds nothing: no fill)
-    s->d_info = (kmg_frame_hold *)(s->d_map + map_b * (indexed ? 3u : 1u) + (indexed ? frame_b : 0u));
-    if ((rc = kmg_apply_plan_create_format(p, c4.data(), k, mode, format, n, st, &s->plan)) != KMG_OK) {
+    s->d_canvas = s->d_delta = s->d_held = nullptr;                    // (a canvas of k holds nothing: no fill of the held source)
+    if (format == KMG_FORMAT_RGBA8) KMG_TRY(output_block(s, {{&s->d_frame, n * 4}, {&s->d_map, n * es}}));
+    else KMG_TRY(output_block(s, {{&s->d_frame, n * 4}, {&s->d_map, n * es}, {&s->d_canvas, n * es}, {&s->d_delta, n * es}, {&s->d_held, n * 4}}));
+    const int rc = kmg_apply_plan_create_format(s->p, c4.data(), k, mode, format, n, st, &s->plan);
+    if (rc != KMG_OK) {
         s->plan = nullptr;
         output_end(s);
         return rc;
@@ -483,12 +512,7 @@ try {
     hipError_t e = hipSuccess;
     if (format == KMG_FORMAT_INDEX8) e = hipMemsetD8Async((hipDeviceptr_t)s->d_canvas, (unsigned char)k, n, st);
     else if (format == KMG_FORMAT_INDEX16) e = hipMemsetD16Async((hipDeviceptr_t)s->d_canvas, (unsigned short)k, n, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        output_end(s);
-        return fail(KMG_ERR_HIP, "filling the canvas failed: %s", hipGetErrorString(e));
-    }
-    s->k = k; s->mode = mode; s->format = format; s->width = width; s->height = height;
+    KMG_TRY(output_opened(s, e, k, mode, format, width, height));
     for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], out_palette_rgba + 4 * i);
     *out_count = k;
     return KMG_OK;
@@ -504,11 +528,32 @@ hipError_t fresh_record(kmg_frame_hold *d_info, size_t bytes, hipStream_t st)
     return e != hipSuccess ? e : hipMemsetAsync(&d_info->x0, 0xFF, 2 * sizeof(uint32_t), st);
 }
 
+// the flags of a frame call (lossy: the call holds pixels within a tolerance)
+int check_frame_flags(uint32_t flags, bool lossy)
+{
+    if (flags & ~KMG_FRAME_DELTA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
+    if (lossy && !(flags & KMG_FRAME_DELTA)) return fail(KMG_ERR_INVALID_ARGUMENT, "a lossy frame is a delta frame: KMG_FRAME_DELTA is required");
+    return KMG_OK;
+}
+
+// what kmg_sequence_output_frame and _lossy ask of the open output and of their arguments
+int check_shared_frame(const kmg_sequence *s, bool lossy, const void *rgba, uint32_t flags, const void *out, const void *info, const void *is_full)
+{
+    if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
+    if (s->local) return fail(KMG_ERR_INVALID_ARGUMENT, "the open output has per-frame palettes: its frames go through kmg_sequence_output_frame_local");
+    if (!s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "no output is open (kmg_sequence_output_begin)");
+    if (!rgba || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame%s: a pointer is NULL", lossy ? "_lossy" : "");
+    KMG_TRY(check_frame_flags(flags, lossy));
+    if (!(flags & KMG_FRAME_DELTA)) return KMG_OK;
+    if (s->format == KMG_FORMAT_RGBA8) return delta_needs_index();
+    if (!info || !is_full) return fail(KMG_ERR_INVALID_ARGUMENT, "KMG_FRAME_DELTA needs info and is_full");
+    return KMG_OK;
+}
+
 // One frame through the open output (the callers have checked their arguments): upload, plan run, then -- delta -- the exact pass
 // (tolerance == NULL) or the lossy one on a fresh record, its read-back, and the download of the full map or the delta map.
 int output_frame(kmg_sequence *s, const uint8_t *rgba, bool delta, const uint32_t *tolerance, void *out, kmg_frame_hold *rec, bool *is_full)
 {
-    int rc;
     kmg_processor *p = s->p;
     hipStream_t st = s->sg.st;
     const bool lossy = tolerance != nullptr;
@@ -516,22 +561,15 @@ int output_frame(kmg_sequence *s, const uint8_t *rgba, bool delta, const uint32_
     const size_t n = (size_t)s->width * s->height, map_bytes = n * format_bytes(s->format);
     HIP_TRY(copy_host_image(p, s->d_frame, rgba, n * 4, hipMemcpyHostToDevice, st));
     if (s->mode == KMG_MODE_DIFFUSE) apply_plan_restart(s->plan);      // every frame is an image of its own
-    if ((rc = kmg_apply_plan_run(s->plan, s->d_frame, s->width, s->height, 0, s->d_map, st)) != KMG_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    KMG_TRY_DRAIN(st, kmg_apply_plan_run(s->plan, s->d_frame, s->width, s->height, 0, s->d_map, st));
     *rec = kmg_frame_hold{0, 0, kFresh, kFresh, 0, 0, 0, 0};
     const size_t rec_bytes = lossy ? sizeof(kmg_frame_hold) : sizeof(kmg_frame_delta);     // (the exact record is the first 32 bytes)
     if (delta) {
         HIP_TRY(fresh_record(s->d_info, rec_bytes, st));
-        if (lossy) rc = frame_hold_impl(p, s->d_frame, s->d_map, s->d_canvas, s->d_held, s->width, s->height, 0, s->format, s->k, *tolerance,
-                                        s->d_delta, s->d_info, st);
-        else rc = frame_delta_impl(p, s->d_map, s->d_canvas, s->width, s->height, 0, s->format, s->k, s->d_delta,
-                                   reinterpret_cast<kmg_frame_delta *>(s->d_info), st);
-        if (rc != KMG_OK) {
-            (void)hipStreamSynchronize(st);
-            return rc;
-        }
+        KMG_TRY_DRAIN(st, lossy ? frame_hold_impl(p, s->d_frame, s->d_map, s->d_canvas, s->d_held, s->width, s->height, 0, s->format, s->k,
+                                                  *tolerance, s->d_delta, s->d_info, st)
+                                : frame_delta_impl(p, s->d_map, s->d_canvas, s->width, s->height, 0, s->format, s->k, s->d_delta,
+                                                   reinterpret_cast<kmg_frame_delta *>(s->d_info), st));
         if (!lossy) std::swap(s->d_frame, s->d_held);                 // the canvas equals this frame's map: its held source is this frame
         HIP_TRY(hipMemcpyAsync(rec, s->d_info, rec_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -546,7 +584,7 @@ int output_frame(kmg_sequence *s, const uint8_t *rgba, bool delta, const uint32_
     }
     HIP_TRY(copy_host_image(p, out, full ? s->d_map : s->d_delta, map_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if ((rc = kmg_apply_plan_status(s->plan)) != KMG_OK) return rc;
+    KMG_TRY(kmg_apply_plan_status(s->plan));
     *is_full = full;
     return KMG_OK;
 }
@@ -556,18 +594,10 @@ int output_frame(kmg_sequence *s, const uint8_t *rgba, bool delta, const uint32_
 extern "C" int kmg_sequence_output_frame(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, void *out, kmg_frame_delta *info,
                                          int *is_full)
 try {
-    if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
-    if (s->local) return fail(KMG_ERR_INVALID_ARGUMENT, "the open output has per-frame palettes: its frames go through kmg_sequence_output_frame_local");
-    if (!s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "no output is open (kmg_sequence_output_begin)");
-    if (!rgba || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame: a pointer is NULL");
-    if (flags & ~KMG_FRAME_DELTA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
-    const bool delta = (flags & KMG_FRAME_DELTA) != 0;
-    if (delta && s->format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8");
-    if (delta && (!info || !is_full)) return fail(KMG_ERR_INVALID_ARGUMENT, "KMG_FRAME_DELTA needs info and is_full");
+    KMG_TRY(check_shared_frame(s, false, rgba, flags, out, info, is_full));
     kmg_frame_hold rec;
     bool full;
-    const int rc = output_frame(s, rgba, delta, nullptr, out, &rec, &full);
-    if (rc != KMG_OK) return rc;
+    KMG_TRY(output_frame(s, rgba, (flags & KMG_FRAME_DELTA) != 0, nullptr, out, &rec, &full));
     if (info) *info = kmg_frame_delta{rec.changed, rec.cleared, rec.x0, rec.y0, rec.x1, rec.y1};
     if (is_full) *is_full = full ? 1 : 0;
     return KMG_OK;
@@ -577,18 +607,10 @@ KMG_ABI_CATCH
 extern "C" int kmg_sequence_output_frame_lossy(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, uint32_t tolerance, void *out,
                                                kmg_frame_hold *info, int *is_full)
 try {
-    if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
-    if (s->local) return fail(KMG_ERR_INVALID_ARGUMENT, "the open output has per-frame palettes: its frames go through kmg_sequence_output_frame_local");
-    if (!s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "no output is open (kmg_sequence_output_begin)");
-    if (!rgba || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame_lossy: a pointer is NULL");
-    if (flags & ~KMG_FRAME_DELTA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
-    if (!(flags & KMG_FRAME_DELTA)) return fail(KMG_ERR_INVALID_ARGUMENT, "a lossy frame is a delta frame: KMG_FRAME_DELTA is required");
-    if (s->format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "a delta frame needs an index format (INDEX8 / INDEX16), not RGBA8");
-    if (!info || !is_full) return fail(KMG_ERR_INVALID_ARGUMENT, "KMG_FRAME_DELTA needs info and is_full");
+    KMG_TRY(check_shared_frame(s, true, rgba, flags, out, info, is_full));
     kmg_frame_hold rec;
     bool full;
-    const int rc = output_frame(s, rgba, true, &tolerance, out, &rec, &full);
-    if (rc != KMG_OK) return rc;
+    KMG_TRY(output_frame(s, rgba, true, &tolerance, out, &rec, &full));
     *info = rec;
     *is_full = full ? 1 : 0;
     return KMG_OK;
@@ -611,58 +633,25 @@ extern "C" int kmg_sequence_output_begin_local(kmg_sequence *s, uint32_t k, int 
 try {
     if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
     output_end(s);                                                     // a second begin of either kind ends the first
-    if (width == 0 || height == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "image has zero width or height");
-    if ((uint64_t)width * height > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "image has more than 2^32-1 pixels");
+    KMG_TRY(check_image_size(width, height));
     if (flags & ~KMG_LOCAL_WARM) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
-    if (k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "k must be an integer higher than 0");
-    if (k > KMG_MAX_K) return fail(KMG_ERR_UNSUPPORTED, "k = %u exceeds KMG_MAX_K = %u", k, KMG_MAX_K);
-    if (mode < KMG_MODE_REPLACE || mode > KMG_MODE_DIFFUSE) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
-    if (format == KMG_FORMAT_RGBA8) return fail(KMG_ERR_INVALID_ARGUMENT, "per-frame palettes need an index format (INDEX8 / INDEX16), not RGBA8");
-    if (format != KMG_FORMAT_INDEX8 && format != KMG_FORMAT_INDEX16) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown output format %d", format);
-    if (mode == KMG_MODE_MELD) return fail(KMG_ERR_INVALID_ARGUMENT, "meld blends two colours: it has no index output");
-    if (format == KMG_FORMAT_INDEX8 && k > 255u)
-        return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX8 holds 256 indices; k = %u plus the transparent slot needs INDEX16", k);
-    kmg_processor *p = s->p;
-    hipStream_t st = s->sg.st;
-    HIP_TRY(hipSetDevice(p->device));
+    KMG_TRY(check_k(k));
+    KMG_TRY(check_output_form(k, mode, format, true));
+    HIP_TRY(hipSetDevice(s->p->device));
     const size_t n = (size_t)width * height, es = format_bytes(format);
-    const size_t frame_b = pad256(n * 4), map_b = pad256(n * es), pal_b = pad256(((size_t)k + 1u) * 4);
-    HIP_TRY(block_take(p, 3 * frame_b + 2 * map_b + pal_b + 256, &s->o_blk, &s->o_cap));
-    s->d_frame = (uint8_t *)s->o_blk;
-    s->d_map = s->d_frame + frame_b;
-    s->d_delta = s->d_map + map_b;
-    s->d_shown = s->d_delta + map_b;
-    s->d_held = s->d_shown + frame_b;
-    s->d_pal = s->d_held + frame_b;
-    s->d_info = (kmg_frame_hold *)(s->d_pal + pal_b);
     s->d_canvas = nullptr;
-    hipError_t e = hipMemsetAsync(s->d_shown, 0, n * 4, st);           // nothing is shown (and nothing is held: no fill)
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        output_end(s);
-        return fail(KMG_ERR_HIP, "filling the canvas failed: %s", hipGetErrorString(e));
-    }
-    s->k = k; s->mode = mode; s->format = format; s->width = width; s->height = height;
+    KMG_TRY(output_block(s, {{&s->d_frame, n * 4}, {&s->d_map, n * es}, {&s->d_delta, n * es}, {&s->d_shown, n * 4}, {&s->d_held, n * 4},
+                             {&s->d_pal, ((size_t)k + 1u) * 4}}));
+    // nothing is shown (and nothing is held: no fill)
+    KMG_TRY(output_opened(s, hipMemsetAsync(s->d_shown, 0, n * 4, s->sg.st), k, mode, format, width, height));
     s->local = true; s->have_prev = false; s->local_flags = flags;
     return KMG_OK;
 }
 KMG_ABI_CATCH
 
-// HIP_TRY for a call that has copies in flight to or from its own locals: the stream is drained before the early return
-#define HIP_TRY_DRAIN(st_, expr)                                                               \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (void)hipStreamSynchronize(st_);                                                   \
-            return fail(e_ == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP,       \
-                        "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-        }                                                                                      \
-    } while (0)
-
 extern "C" int kmg_sequence_output_frame_local(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, const uint32_t *tolerance, void *out,
                                                uint8_t *out_palette_rgba, uint32_t *out_count, kmg_frame_hold *info, int *is_full)
 try {
-    int rc;
     if (!s) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence is NULL");
     if (!s->local) {
         if (s->plan) return fail(KMG_ERR_INVALID_ARGUMENT, "the open output has one shared palette: its frames go through kmg_sequence_output_frame");
@@ -670,9 +659,8 @@ try {
     }
     if (!rgba || !out || !out_palette_rgba || !out_count || !info || !is_full)
         return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frame_local: a pointer is NULL");
-    if (flags & ~KMG_FRAME_DELTA) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown flags %u", flags);
     const bool delta = (flags & KMG_FRAME_DELTA) != 0, lossy = tolerance != nullptr;
-    if (lossy && !delta) return fail(KMG_ERR_INVALID_ARGUMENT, "a lossy frame is a delta frame: KMG_FRAME_DELTA is required");
+    KMG_TRY(check_frame_flags(flags, lossy));
     kmg_processor *p = s->p;
     hipStream_t st = s->sg.st;
     const uint32_t k = s->k;
@@ -691,15 +679,9 @@ try {
     s->have_prev = false;                                              // (the frame after one that failed starts cold)
     HIP_TRY(copy_host_image(p, s->d_frame, rgba, n * 4, hipMemcpyHostToDevice, st));
     std::vector<float> c4(4 * (size_t)k);
-    if ((rc = local_frame_centroids(p, s->d_frame, s->width, s->height, k, cutoff, st, c4.data(), f ? fixed->data() : nullptr, f,
-                                    warm ? s->prev_c4.data() : nullptr, weighting)) != KMG_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    if ((rc = dev_apply(p, s->d_frame, s->width, s->height, 0, c4.data(), k, s->mode, s->d_map, st, cutoff, s->format)) != KMG_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    KMG_TRY_DRAIN(st, local_frame_centroids(p, s->d_frame, s->width, s->height, k, cutoff, st, c4.data(), f ? fixed->data() : nullptr, f,
+                                            warm ? s->prev_c4.data() : nullptr, weighting));
+    KMG_TRY_DRAIN(st, dev_apply(p, s->d_frame, s->width, s->height, 0, c4.data(), k, s->mode, s->d_map, st, cutoff, s->format));
     // P_t: the bytes the output pass writes for each centroid, to the caller and -- one small stream-ordered copy -- to the device
     std::vector<uint8_t> pal(4 * (size_t)k);
     for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], &pal[4 * i]);
@@ -708,23 +690,16 @@ try {
     const size_t rec_bytes = lossy ? sizeof(kmg_frame_hold) : sizeof(kmg_frame_delta);     // (the exact record is the first 32 bytes)
     HIP_TRY_DRAIN(st, fresh_record(s->d_info, rec_bytes, st));
     // without KMG_FRAME_DELTA the exact pass still runs: it leaves shown = P_t[I_t] everywhere; its delta map and record are not used
-    rc = frame_local_impl(p, lossy ? s->d_frame : nullptr, s->d_map, s->d_pal, s->d_shown, lossy ? s->d_held : nullptr, s->width, s->height, 0,
-                          s->format, k, lossy, lossy ? *tolerance : 0u, s->d_delta, s->d_info, st);
-    if (rc != KMG_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    KMG_TRY_DRAIN(st, frame_local_impl(p, lossy ? s->d_frame : nullptr, s->d_map, s->d_pal, s->d_shown, lossy ? s->d_held : nullptr, s->width,
+                                       s->height, 0, s->format, k, lossy, lossy ? *tolerance : 0u, s->d_delta, s->d_info, st));
     if (delta) HIP_TRY_DRAIN(st, hipMemcpyAsync(&rec, s->d_info, rec_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY_DRAIN(st, hipStreamSynchronize(st));
     const bool full = !delta || rec.cleared > 0;                       // "over" cannot show a pixel that turns transparent
     // a lossy frame that is sent in full: the viewer then shows P_t[I_t] everywhere -- the exact pass makes the canvas that
     if (lossy && full) {
         HIP_TRY_DRAIN(st, fresh_record(s->d_info, sizeof(kmg_frame_delta), st));
-        if ((rc = frame_local_impl(p, nullptr, s->d_map, s->d_pal, s->d_shown, nullptr, s->width, s->height, 0, s->format, k, false, 0u, s->d_delta,
-                                   s->d_info, st)) != KMG_OK) {
-            (void)hipStreamSynchronize(st);
-            return rc;
-        }
+        KMG_TRY_DRAIN(st, frame_local_impl(p, nullptr, s->d_map, s->d_pal, s->d_shown, nullptr, s->width, s->height, 0, s->format, k, false, 0u,
+                                           s->d_delta, s->d_info, st));
     }
     // after an exact frame or a full one every pixel's held source IS this frame: the two buffers swap instead of a copy
     if (!lossy || full) std::swap(s->d_frame, s->d_held);

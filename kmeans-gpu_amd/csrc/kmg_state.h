@@ -1,7 +1,8 @@
 // kmg_state.h -- the objects behind the opaque handles of include/kmeans_hip.h (kmg_processor, kmg_lloyd) and what the
 // translation units of the C ABI share: kmg_processor.hip (processor, device blocks, host helpers), kmg_lloyd.hip (one Lloyd
 // problem: colour table, initialisation, passes, loop), kmg_apply.hip (output passes), kmg_api.hip (the host-buffer calls of
-// ImageProcessor::{palette, find, reduce}), kmg_group.hip (several devices).  Internal: nothing here is exported.
+// ImageProcessor::{palette, find, reduce}), kmg_group.hip (several devices).  Internal: nothing here is exported.  The argument
+// checks these units share are in kmg_checks.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include <new>
 #include <vector>
 
+#include "kmg_checks.h"
 #include "kmg_color.h"
 #include "kmg_internal.h"
 #include "kmg_kernels.h"
@@ -29,12 +31,25 @@
 
 using namespace kmg;
 
-#define HIP_TRY(expr)                                                                          \
+// HIP_TRY / KMG_TRY for a call that has work in flight on st_ that reads or writes its own locals, or buffers it is about to
+// give back: the stream is drained before the early return
+#define HIP_TRY_DRAIN(st_, expr)                                                               \
     do {                                                                                       \
         hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
+        if (e_ != hipSuccess) {                                                                \
+            (void)hipStreamSynchronize(st_);                                                   \
             return fail(e_ == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP,       \
                         "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+        }                                                                                      \
+    } while (0)
+
+#define KMG_TRY_DRAIN(st_, expr)                                                               \
+    do {                                                                                       \
+        const int rc_ = (expr);                                                                \
+        if (rc_ != KMG_OK) {                                                                   \
+            (void)hipStreamSynchronize(st_);                                                   \
+            return rc_;                                                                        \
+        }                                                                                      \
     } while (0)
 
 // launch wrapper: when profiling is on, bracket the launch with HIP events on its own stream
@@ -257,6 +272,23 @@ struct ArenaGuard {
     }
     ~ArenaGuard() { if (base) block_give(p, base, cap); }
 };
+
+// A small table from the caller's memory to the device, enqueued on st: the bytes travel from a heap copy that the stream
+// releases once the copy has run, so the caller's table may change as soon as this returns.
+static void free_host_copy(void *copy) { delete[] static_cast<uint8_t *>(copy); }
+
+static hipError_t upload_host_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
+{
+    uint8_t *copy = new uint8_t[bytes];
+    memcpy(copy, src, bytes);
+    const hipError_t e = hipMemcpyAsync(dst, copy, bytes, hipMemcpyHostToDevice, st);
+    const hipError_t e2 = hipLaunchHostFunc(st, free_host_copy, copy);
+    if (e2 != hipSuccess) {                                            // (not enqueued: wait for the copy, release here)
+        (void)hipStreamSynchronize(st);
+        delete[] copy;
+    }
+    return e != hipSuccess ? e : e2;
+}
 
 // the private stream of one host-buffer call (every call has its own, so calls on one processor run
 // concurrently, examples/parallel.rs); taken from / returned to the processor's idle list

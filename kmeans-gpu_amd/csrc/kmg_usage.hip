@@ -280,8 +280,7 @@ int check_index_map(const char *name, const void *map, int format, uint32_t k)
 
 int check_usage_args(const kmg_processor *p, const void *index, uint64_t n, int format, uint32_t k, const uint64_t *usage)
 {
-    const int rc = check_index_map("index_usage", index, format, k);
-    if (rc != KMG_OK) return rc;
+    KMG_TRY(check_index_map("index_usage", index, format, k));
     if (!p || !usage) return fail(KMG_ERR_INVALID_ARGUMENT, "index_usage: the processor or the record is NULL");
     if (n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "index_usage: no pixels");
     if (n > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "index_usage: more than 2^32-1 pixels");
@@ -292,8 +291,7 @@ int check_usage_args(const kmg_processor *p, const void *index, uint64_t n, int 
 int check_remap_args(const kmg_processor *p, const void *in, int format, uint32_t width, uint32_t rows, uint32_t k, const uint16_t *remap,
                      uint32_t out_bits, const void *out)
 {
-    const int rc = check_index_map("index_remap", in, format, k);
-    if (rc != KMG_OK) return rc;
+    KMG_TRY(check_index_map("index_remap", in, format, k));
     if (!bits_ok(out_bits)) return fail(KMG_ERR_INVALID_ARGUMENT, "index_remap: out_bits = %u is not 1, 2, 4, 8 or 16", out_bits);
     if (!p || !remap || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "index_remap: the processor, the table or the output is NULL");
     if (width == 0 || rows == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "index_remap: zero width or rows");
@@ -304,38 +302,25 @@ int check_remap_args(const kmg_processor *p, const void *in, int format, uint32_
 
 int dev_usage(kmg_processor *p, const void *d_index, uint64_t n, int format, uint32_t k, uint64_t *d_usage, hipStream_t st)
 {
-    const int rc = check_usage_args(p, d_index, n, format, k, d_usage);
-    if (rc != KMG_OK) return rc;
+    KMG_TRY(check_usage_args(p, d_index, n, format, k, d_usage));
     HIP_TRY(hipSetDevice(p->device));
     unsigned long long *usage = reinterpret_cast<unsigned long long *>(d_usage);
     HIP_TRY(launch_index_usage(d_index, format == KMG_FORMAT_INDEX16, n, k, usage, st));
     return KMG_OK;
 }
 
-void free_table_copy(void *copy) { delete[] static_cast<uint16_t *>(copy); }
-
 // Enqueues on st: the table's upload from a heap copy of the caller's entries (released by the stream once the copy has run)
 // and the launch; the device copy of the table goes back to the pool in stream order.
 int dev_remap(kmg_processor *p, const void *d_in, int format, uint32_t width, uint32_t rows, uint32_t k, const uint16_t *remap,
               uint32_t out_bits, void *d_out, uint64_t *d_bad, hipStream_t st)
 {
-    const int rc = check_remap_args(p, d_in, format, width, rows, k, remap, out_bits, d_out);
-    if (rc != KMG_OK) return rc;
+    KMG_TRY(check_remap_args(p, d_in, format, width, rows, k, remap, out_bits, d_out));
     if (!d_bad || (reinterpret_cast<uintptr_t>(d_bad) & 7u)) return fail(KMG_ERR_INVALID_ARGUMENT, "index_remap: the bad-pixel count is NULL or not 8-byte aligned");
     HIP_TRY(hipSetDevice(p->device));
     const size_t bytes = ((size_t)k + 1u) * sizeof(uint16_t);
     StreamBuf tab;
     HIP_TRY(tab.alloc(p, bytes, st));
-    uint16_t *copy = new uint16_t[(size_t)k + 1u];
-    memcpy(copy, remap, bytes);
-    const hipError_t e = hipMemcpyAsync(tab.ptr, copy, bytes, hipMemcpyHostToDevice, st);
-    const hipError_t e2 = hipLaunchHostFunc(st, free_table_copy, copy);
-    if (e2 != hipSuccess) {                                            // (not enqueued: wait for the copy, release here)
-        (void)hipStreamSynchronize(st);
-        delete[] copy;
-    }
-    HIP_TRY(e);
-    HIP_TRY(e2);
+    HIP_TRY(upload_host_copy(tab.ptr, remap, bytes, st));
     unsigned long long *bad = reinterpret_cast<unsigned long long *>(d_bad);
     const uint16_t *map = static_cast<const uint16_t *>(tab.ptr);
     HIP_TRY(launch_index_remap(d_in, format == KMG_FORMAT_INDEX16, width, rows, k, map, out_bits, d_out, bad, st));
@@ -395,9 +380,8 @@ KMG_ABI_CATCH
 
 extern "C" int kmg_index_usage(kmg_processor *p, const void *index, int format, uint64_t n_pixels, uint32_t k, uint64_t *usage)
 try {
-    int rc;
     // (the refusals that need no device come first)
-    if ((rc = check_usage_args(p, index, n_pixels, format, k, usage)) != KMG_OK) return rc;
+    KMG_TRY(check_usage_args(p, index, n_pixels, format, k, usage));
     HIP_TRY(hipSetDevice(p->device));
     StreamGuard sg;
     HIP_TRY(sg.acquire(p));
@@ -407,10 +391,7 @@ try {
     HIP_TRY(copy_host_image(p, map.ptr, index, bytes, hipMemcpyHostToDevice, sg.st));
     HIP_TRY(rec.alloc(p, rec_bytes, sg.st));
     HIP_TRY(hipMemsetAsync(rec.ptr, 0, rec_bytes, sg.st));
-    if ((rc = dev_usage(p, map.ptr, n_pixels, format, k, static_cast<uint64_t *>(rec.ptr), sg.st)) != KMG_OK) {
-        (void)hipStreamSynchronize(sg.st);
-        return rc;
-    }
+    KMG_TRY_DRAIN(sg.st, dev_usage(p, map.ptr, n_pixels, format, k, static_cast<uint64_t *>(rec.ptr), sg.st));
     std::vector<uint64_t> got((size_t)k + 2u);
     HIP_TRY(hipMemcpyAsync(got.data(), rec.ptr, rec_bytes, hipMemcpyDeviceToHost, sg.st));
     HIP_TRY(hipStreamSynchronize(sg.st));
@@ -422,9 +403,8 @@ KMG_ABI_CATCH
 extern "C" int kmg_index_remap(kmg_processor *p, const void *in, int in_format, uint32_t width, uint32_t height, uint32_t k,
                                const uint16_t *remap, uint32_t out_bits, void *out, uint64_t *bad)
 try {
-    int rc;
     // (the refusals that need no device come first)
-    if ((rc = check_remap_args(p, in, in_format, width, height, k, remap, out_bits, out)) != KMG_OK) return rc;
+    KMG_TRY(check_remap_args(p, in, in_format, width, height, k, remap, out_bits, out));
     HIP_TRY(hipSetDevice(p->device));
     StreamGuard sg;
     HIP_TRY(sg.acquire(p));
@@ -435,10 +415,7 @@ try {
     HIP_TRY(dst.alloc(p, out_bytes, sg.st));
     HIP_TRY(cnt.alloc(p, sizeof(uint64_t), sg.st));
     HIP_TRY(hipMemsetAsync(cnt.ptr, 0, sizeof(uint64_t), sg.st));
-    if ((rc = dev_remap(p, src.ptr, in_format, width, height, k, remap, out_bits, dst.ptr, static_cast<uint64_t *>(cnt.ptr), sg.st)) != KMG_OK) {
-        (void)hipStreamSynchronize(sg.st);
-        return rc;
-    }
+    KMG_TRY_DRAIN(sg.st, dev_remap(p, src.ptr, in_format, width, height, k, remap, out_bits, dst.ptr, static_cast<uint64_t *>(cnt.ptr), sg.st));
     uint64_t n_bad = 0;
     HIP_TRY(copy_host_image(p, out, dst.ptr, out_bytes, hipMemcpyDeviceToHost, sg.st));
     HIP_TRY(hipMemcpyAsync(&n_bad, cnt.ptr, sizeof(uint64_t), hipMemcpyDeviceToHost, sg.st));
@@ -452,9 +429,8 @@ extern "C" int kmg_index_optimize(kmg_processor *p, const void *index, int forma
                                   const uint8_t *palette_rgba, uint32_t k, uint32_t flags, uint32_t out_bits, uint8_t *out_palette_rgba,
                                   kmg_index_plan_info *info, void *out_map)
 try {
-    int rc;
     // (the refusals that need no device come first)
-    if ((rc = check_index_map("index_optimize", index, format, k)) != KMG_OK) return rc;
+    KMG_TRY(check_index_map("index_optimize", index, format, k));
     if (!p || !palette_rgba || !out_palette_rgba || !info || !out_map) return fail(KMG_ERR_INVALID_ARGUMENT, "index_optimize: a pointer is NULL");
     if (width == 0 || height == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "index_optimize: zero width or height");
     const uint64_t n = (uint64_t)width * height;
@@ -472,27 +448,21 @@ try {
     HIP_TRY(copy_host_image(p, src.ptr, index, in_bytes, hipMemcpyHostToDevice, sg.st));
     HIP_TRY(rec.alloc(p, rec_bytes + sizeof(uint64_t), sg.st));
     HIP_TRY(hipMemsetAsync(rec.ptr, 0, rec_bytes + sizeof(uint64_t), sg.st));
-    if ((rc = dev_usage(p, src.ptr, n, format, k, static_cast<uint64_t *>(rec.ptr), sg.st)) != KMG_OK) {
-        (void)hipStreamSynchronize(sg.st);
-        return rc;
-    }
+    KMG_TRY_DRAIN(sg.st, dev_usage(p, src.ptr, n, format, k, static_cast<uint64_t *>(rec.ptr), sg.st));
     std::vector<uint64_t> usage((size_t)k + 2u);
     HIP_TRY(hipMemcpyAsync(usage.data(), rec.ptr, rec_bytes, hipMemcpyDeviceToHost, sg.st));
     HIP_TRY(hipStreamSynchronize(sg.st));                              // (the plan is host arithmetic on the counts)
     std::vector<uint16_t> remap((size_t)k + 1u);
     std::vector<uint8_t> pal(((size_t)k + 1u) * 4u);
     kmg_index_plan_info pi;
-    if ((rc = plan_of(usage.data(), palette_rgba, k, flags, remap.data(), pal.data(), &pi)) != KMG_OK) return rc;
+    KMG_TRY(plan_of(usage.data(), palette_rgba, k, flags, remap.data(), pal.data(), &pi));
     const uint32_t bits = out_bits ? out_bits : pi.bits;
     if (bits < pi.bits) return fail(KMG_ERR_INVALID_ARGUMENT, "index_optimize: %u slots need %u bits, out_bits = %u", pi.n_slots, pi.bits, out_bits);
     if (bits > in_bits) return fail(KMG_ERR_INVALID_ARGUMENT, "index_optimize: %u slots need %u bits, more than the input map's %u", pi.n_slots, bits, in_bits);
     const size_t out_bytes = packed_bytes(width, height, bits);
     HIP_TRY(dst.alloc(p, out_bytes, sg.st));
     uint64_t *d_bad = static_cast<uint64_t *>(rec.ptr) + (k + 2u);
-    if ((rc = dev_remap(p, src.ptr, format, width, height, k, remap.data(), bits, dst.ptr, d_bad, sg.st)) != KMG_OK) {
-        (void)hipStreamSynchronize(sg.st);
-        return rc;
-    }
+    KMG_TRY_DRAIN(sg.st, dev_remap(p, src.ptr, format, width, height, k, remap.data(), bits, dst.ptr, d_bad, sg.st));
     uint64_t n_bad = 0;
     HIP_TRY(copy_host_image(p, out_map, dst.ptr, out_bytes, hipMemcpyDeviceToHost, sg.st));
     HIP_TRY(hipMemcpyAsync(&n_bad, d_bad, sizeof(uint64_t), hipMemcpyDeviceToHost, sg.st));
