@@ -362,7 +362,7 @@ static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, 
     if (e == hipSuccess && diffuse) *pl->h_timeout = 0;
     if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->ready, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventRecord(pl->ready, S(stream));
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP, "apply plan failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail_hip(e, "apply plan");
     undo.pl = nullptr;
     *out = pl;
     return KMG_OK;

@@ -32,6 +32,12 @@ namespace kmg {
 // sets the calling thread's kmg_last_error() message and returns `code`
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 bool log_debug();
+// a HIP call that failed where HIP_TRY does not fit (the caller has something to release first): "<what> failed: <HIP's words>",
+// out of memory told apart from every other error
+static inline int fail_hip(hipError_t e, const char *what)
+{
+    return fail(e == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+}
 
 // No C++ exception leaves the library: the callers of this ABI are C, Rust (rust-shim/) and ctypes, for which an exception that
 // unwinds through an extern "C" frame is undefined behaviour, where the reference returns anyhow::Result (core/src/lib.rs:38).

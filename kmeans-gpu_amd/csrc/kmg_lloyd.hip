@@ -1,19 +1,141 @@
-// kmg_lloyd.hip -- one Lloyd problem of the C ABI (kmg_lloyd_*, include/kmeans_hip.h): binding an image to its colour table
-// (kmg_table.h), the strategy choice, the farthest-point initialisation (modules.rs:946-1246), the assign / accumulate / update
-// passes and the loop of ChooseCentroidModule::compute (modules.rs:763-840), with their test and statistics support.  Every
-// per-pixel and per-colour step is a kernel launch.
+// kmg_lloyd.hip -- one Lloyd problem of the C ABI (kmg_lloyd_*, include/kmeans_hip.h).  Host code only: every per-pixel and
+// per-colour step is a kernel launch.  In this order, so that nothing needs a forward declaration: what the sections share (events,
+// side_flush, table_bound, ensure_entries, next_balance, the ONE cube launch, label launch and CubeTail, the refusals several calls
+// repeat); the colour-table strategy (cost model, binding an image to its colour table of kmg_table.h, the choice, test and statistics
+// support); the object; the farthest-point initialisation (modules.rs:946-1246); the assign / accumulate / label passes; profiling,
+// the update and the loop of ChooseCentroidModule::compute (modules.rs:763-840).
 
 #include <math.h>
 
 #include "kmg_state.h"
 
-// ---------------------------------------------------------------------------------------------
-// colour-table strategy (kmg_table.h): binding an image, strategy choice
-// ---------------------------------------------------------------------------------------------
-static void drop_events(kmg_lloyd *s);
-static void destroy_events(kmg_lloyd *s);
-static int debug_refresh(kmg_lloyd *s, hipStream_t st, unsigned long long stage[8]);
-static int side_flush(kmg_lloyd *s, hipStream_t st);
+// ---- what the sections share ----
+static void drop_events(kmg_lloyd *s)
+{
+    for (ProfEvent &e : s->events) { s->pool.push_back(e.e0); s->pool.push_back(e.e1); }
+    s->events.clear();
+}
+
+static void destroy_events(kmg_lloyd *s)
+{
+    drop_events(s);
+    for (hipEvent_t e : s->pool) (void)hipEventDestroy(e);
+    s->pool.clear();
+}
+
+// label passes that kmg_lloyd_iterate left running on the side stream: `st` waits for them (no host sync)
+static int side_flush(kmg_lloyd *s, hipStream_t st)
+{
+    for (int i = 0; i < 2; ++i)
+        if (s->lab_pending[i]) {
+            HIP_TRY(hipStreamWaitEvent(st, s->ev_lab[i], 0));
+            s->lab_pending[i] = false;
+        }
+    return KMG_OK;
+}
+
+static bool table_bound(const kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n)
+{
+    if (s->weighted) return false;   // (the initialisation of a weighted object may have bound the image: its passes do not use that)
+    return s->tab.rgba != nullptr && s->tab.rgba == d_rgba && s->tab.n == n;
+}
+
+// "drop the binding of this buffer": the tables and blocks stay with the object, the next image may want them.  True: it was bound.
+static bool drop_binding_of(kmg_lloyd *s, const uint8_t *d_rgba)
+{
+    const bool bound = s->tab.rgba == d_rgba;
+    if (bound) s->tab.rgba = nullptr;
+    return bound;
+}
+
+// the work list a pass walks (this rank's cell share, if one is set), the flag and the list of the bound image's hot cells
+static const uint32_t *share_or_work(const ColourTable &t) { return t.d_work_share ? t.d_work_share : t.d_work; }
+static uint32_t hot_flag(const ColourTable &t) { return t.n_hot ? kCubeHot : 0u; }
+static const uint32_t *hot_list(const ColourTable &t) { return t.n_hot ? t.d_work + kCells + 1 : nullptr; }
+
+// the label pass's first-level tables (pair entries / cell summaries) of the current per-colour labels, if a pass deferred them
+static int ensure_entries(kmg_lloyd *s, hipStream_t st)
+{
+    ColourTable &t = s->tab;
+    if (t.entries_valid) return KMG_OK;
+    HIP_TRY(launch_cube_entries(share_or_work(t), t.d_occ, t.d_colour_labels, t.d_sub, s->k, st));
+    t.entries_valid = true;
+    return KMG_OK;
+}
+
+// The balancing state of the next cube pass of a loop (kmg_table.h CubeBalance): the passes count on as long as the same work list is
+// walked -- the image's, or one share of it; a new list (another binding, another share) starts over.
+static CubeBalance next_balance(ColourTable &t, const uint32_t *work)
+{
+    if (t.balance_work != work) { t.balance_work = work; t.balance_pass = 0; }
+    CubeBalance b;
+    b.state = t.d_balance;
+    b.pass = t.balance_pass++;
+    return b;
+}
+
+// The cube pass of the bound image for the current centroids (kmg_table.h).  What varies between its callers: where the sums go
+// (`rows` shared rows of d_sums), whether the cell share or the whole work list is walked, whether the pass continues the loop's
+// load balance, flags on top of kCubeHot, the tail of the last launch and the statistics' stage counters.
+static hipError_t cube_pass(kmg_lloyd *s, hipStream_t st, int64_t *d_sums, uint32_t rows, bool share, bool balance, uint32_t flags = 0u,
+                            const CubeTail *tail = nullptr, unsigned long long *d_stage = nullptr)
+{
+    ColourTable &t = s->tab;
+    const uint32_t *work = share ? share_or_work(t) : t.d_work;
+    CubeBalance bal;
+    if (balance) bal = next_balance(t, work);
+    return launch_cube(t.d_hist, t.d_agg, t.d_sub_agg, t.d_occ, work, s->p->d_bounds, s->p->d_sub_bounds, s->d_cent, s->k, s->p->d_lab_table,
+                       t.d_masks, t.d_cell_work, t.d_colour_labels, t.d_sub, d_sums, rows, flags | hot_flag(t), d_stage, st, tail,
+                       affine_for(s->p, s->k, st), balance ? &bal : nullptr);
+}
+
+// The label pass: the per-pixel label map from the current label tables.  tail / acc: the pass's last workgroup also runs a CubeTail
+// on the sums in acc (k <= 256)
+static int label_pass(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, uint32_t *d_labels, hipStream_t st, const CubeTail *tail = nullptr,
+                      int64_t *acc = nullptr)
+{
+    const ColourTable &t = s->tab;
+    PROF_LAUNCH(s, KMG_K_LABELS, st, launch_labels((const uint32_t *)d_rgba, n, t.d_colour_labels, t.d_sub, s->k, nullptr, d_labels, st,
+                                                   s->reserve_cus, hot_list(t), tail, acc));
+    return KMG_OK;
+}
+
+// hand the sums over to acc_out and -- do_update -- update the object's centroids from them (kmg_table.h CubeTail)
+static CubeTail make_tail(const kmg_lloyd *s, int64_t *acc_out, bool do_update)
+{
+    return CubeTail{acc_out, do_update ? 1 : 0, s->p->opt.convergence, s->d_cent, s->d_nconv};
+}
+
+// The refusals that several calls repeat, each once (the pattern of kmg_checks.h: KMG_OK or the status of fail(); a call makes
+// the checks it needs in the order it refuses).  call: the name the message starts with.
+static int check_unweighted(const kmg_lloyd *s, const char *call)
+{
+    if (s->weighted)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "%s: the object's sums are weighted (kmg_lloyd_set_weighting): the colour table counts pixels", call);
+    return KMG_OK;
+}
+
+// image = false: the tables are enough (they outlive the image's binding: kmg_lloyd_run drops the image, not the tables)
+static int check_bound(const kmg_lloyd *s, const char *call, bool image = true)
+{
+    if (!s || !s->tab.d_hist || (image && !s->tab.rgba)) return fail(KMG_ERR_INVALID_ARGUMENT, "%s: no bound image", call);
+    return KMG_OK;
+}
+
+static int check_no_share(const kmg_lloyd *s, const char *call, const char *why = "")
+{
+    if (s->tab.d_work_share) return fail(KMG_ERR_INVALID_ARGUMENT, "%s: a cell share is set (kmg_lloyd_set_cell_share)%s", call, why);
+    return KMG_OK;
+}
+
+// the largest image whose weighted int64 sums cannot overflow (kmg_state.h kMaxWeightedPixels)
+static int check_weighted_count(const kmg_lloyd *s, uint64_t n)
+{
+    if (s->weighted && n > kMaxWeightedPixels)
+        return fail(KMG_ERR_UNSUPPORTED, "weighted sums take at most 2^28 pixels (%llu given)", (unsigned long long)n);
+    return KMG_OK;
+}
+
 // The table's blocks go back to the processor for the next image.  The caller has made sure that no kernel still uses them.
 static void free_table(kmg_processor *p, ColourTable &t)
 {
@@ -23,7 +145,6 @@ static void free_table(kmg_processor *p, ColourTable &t)
     t = ColourTable();
 }
 
-
 // carve `bytes` (256-byte granules) off a block
 static inline void *carve(void *base, size_t &off, size_t bytes)
 {
@@ -32,6 +153,7 @@ static inline void *carve(void *base, size_t &off, size_t bytes)
     return r;
 }
 
+// ---- colour-table strategy (kmg_table.h): binding an image, strategy choice ----
 // Cost model of one Lloyd iteration (seconds on MI355X), refitted in round 6 to tools/costmodel_sweep.py
 // (profiles/r06_costmodel_sweep.txt: noise, Gaussian blobs and the tiled photograph, 2^18 .. 2^24 pixels, k = 8 .. 256, the
 // one-launch cube pass).  It is asked TWICE: before anything is known about the image (`facts` = NULL) it answers with the
@@ -78,14 +200,19 @@ static double cube_seconds(uint32_t k, const ImageFacts *facts)
     return facts->hot ? three_launches : one_launch;
 }
 
+// the label pass of an iteration, if the caller wants a label map
+static double label_seconds(uint64_t n, uint32_t k, bool labels)
+{
+    const double N = (double)n;
+    const double N22 = (double)(1u << 22);
+    return !labels ? 0.0 : (k > 256u ? N * 6.7e-12 : (N <= N22 ? 3.0e-6 + N * 4.4e-12 : 2.15e-5 + (N - N22) * 2.2e-12));
+}
+
 // facts == NULL: before a binding (its cost counts); else: the image is bound (its cost is spent)
 static bool table_pays(const kmg_processor *p, uint64_t n, uint32_t k, bool labels, const ImageFacts *facts)
 {
     if (const int f = forced_strategy(p)) return f > 0;
-    const double N = (double)n;
-    const double N22 = (double)(1u << 22);
-    const double label_pass = !labels ? 0.0 : (k > 256u ? N * 6.7e-12 : (N <= N22 ? 3.0e-6 + N * 4.4e-12 : 2.15e-5 + (N - N22) * 2.2e-12));
-    const double table = cube_seconds(k, facts) + label_pass + (facts ? 0.0 : bind_seconds(n) / 16.0);
+    const double table = cube_seconds(k, facts) + label_seconds(n, k, labels) + (facts ? 0.0 : bind_seconds(n) / 16.0);
     // (blind: the scan at its dearest -- an image with hot cells -- against the table at its cheapest)
     const double scan = scan_seconds(n, k, facts ? facts->hot != 0u : true);
     return table < scan;
@@ -106,7 +233,7 @@ int ensure_bounds(kmg_processor *p, hipStream_t st)
         (void)hipFree(b);
         if (sb) (void)hipFree(sb);
         if (lab) (void)hipFree(lab);
-        return fail(e == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP, "colour tables failed: %s", hipGetErrorString(e));
+        return fail_hip(e, "colour tables");
     }
     p->d_lab_table = lab;
     p->d_sub_bounds = sb;
@@ -163,8 +290,7 @@ static int bind_image_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, void
     // the histogram counts, partition totals and prefix sums are u32 (kmg_table.hip)
     KMG_TRY(check_pixel_count(n));
     HIP_TRY(hipSetDevice(s->p->device));
-    int rc;
-    if ((rc = ensure_bounds(s->p, S(stream))) != KMG_OK) return rc;
+    KMG_TRY(ensure_bounds(s->p, S(stream)));
     ColourTable &t = s->tab;
     if (!t.d_hist) {
         // one block for all tables, from the processor's idle blocks when one fits (no hipMalloc on a warm processor)
@@ -177,8 +303,7 @@ static int bind_image_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, void
         const hipError_t e = block_take(s->p, need, &t.blk, &t.blk_cap);
         if (e != hipSuccess) {
             t.blk = nullptr; t.blk_cap = 0;
-            return fail(e == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP,
-                        "colour table allocation failed: %s", hipGetErrorString(e));
+            return fail_hip(e, "colour table allocation");
         }
         size_t off = 0;
         t.d_hist = (uint32_t *)carve(t.blk, off, sizes[0]);
@@ -212,8 +337,7 @@ static int bind_image_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, void
         if (e == hipSuccess)
             e = launch_partitioned_histogram((const uint32_t *)d_rgba, n, first_index, (uint32_t *)small.ptr, (uint16_t *)elems.ptr,
                                              (uint32_t *)keys.ptr, t.d_hist, t.d_tie, S(stream));
-        if (e != hipSuccess)
-            return fail(e == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP, "histogram failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail_hip(e, "histogram");
     } else {
         HIP_TRY(hipMemsetAsync(t.d_hist, 0, sizeof(uint32_t) << 24, S(stream)));
         HIP_TRY(launch_histogram((const uint32_t *)d_rgba, n, t.d_hist, S(stream)));
@@ -226,8 +350,7 @@ static int bind_image_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, void
         t.tie_valid = true;
         t.tie_first = first_index;
     }
-    int rc_agg;
-    if ((rc_agg = tables_from_histogram(s, n, S(stream))) != KMG_OK) return rc_agg;
+    KMG_TRY(tables_from_histogram(s, n, S(stream)));
     if (want_tie) HIP_TRY(launch_init_records(t.d_work, s->p->d_bounds, t.d_init_cells, S(stream)));   // an initialisation follows
     t.rgba = d_rgba;
     t.n = n;
@@ -236,10 +359,10 @@ static int bind_image_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, void
 
 extern "C" int kmg_lloyd_bind_image(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, void *stream)
 try {
-    if (s && s->weighted) return fail(KMG_ERR_INVALID_ARGUMENT, "bind_image: the object's sums are weighted (kmg_lloyd_set_weighting): the colour table counts pixels");
-    const int rc = bind_image_impl(s, d_rgba, n, stream, false, 0);
-    if (rc == KMG_OK) s->tab.bound_by_caller = true;
-    return rc;
+    if (s) KMG_TRY(check_unweighted(s, "bind_image"));               // (before the NULL image: the order the call has always had)
+    KMG_TRY(bind_image_impl(s, d_rgba, n, stream, false, 0));
+    s->tab.bound_by_caller = true;
+    return KMG_OK;
 }
 KMG_ABI_CATCH
 
@@ -250,7 +373,7 @@ static int prepare_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, int wan
     if (!s || !d_rgba || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad prepare arguments");
     if (s->weighted) {
         // weighted sums always take the per-pixel routes: a binding the initialisation left on this buffer is dropped, not inherited
-        if (s->tab.rgba == d_rgba) { s->tab.rgba = nullptr; s->tab.tables_valid = false; }
+        if (drop_binding_of(s, d_rgba)) s->tab.tables_valid = false;
         s->tab.bound_by_init = false;
         if (strategy) *strategy = 0;
         return KMG_OK;
@@ -265,10 +388,9 @@ static int prepare_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, int wan
     bool try_table = n <= 0xFFFFFFFFull && table_pays(s->p, n, s->k, want_labels != 0, fresh ? &before : nullptr);
     if (try_table && !fresh && forced_strategy(s->p) == 0) {
         const ImageFacts dense = {kCells, 0u};
-        const double N = (double)n, N22 = (double)(1u << 22);
         // (the dearest table of this size: every cell occupied, no hot cells to make the scan dearer -- with the binding on top)
-        const double label_pass = !want_labels ? 0.0 : (s->k > 256u ? N * 6.7e-12 : (N <= N22 ? 3.0e-6 + N * 4.4e-12 : 2.15e-5 + (N - N22) * 2.2e-12));
-        const bool sure = cube_seconds(s->k, &dense) + label_pass + bind_seconds(n) / 16.0 < scan_seconds(n, s->k, false);
+        const double label_pass_s = label_seconds(n, s->k, want_labels != 0);
+        const bool sure = cube_seconds(s->k, &dense) + label_pass_s + bind_seconds(n) / 16.0 < scan_seconds(n, s->k, false);
         if (!sure) {
             uint32_t *d_probe = reinterpret_cast<uint32_t *>(s->d_nconv) + 1;     // (three words behind the convergence count)
             uint32_t h[3] = {0u, 0u, 1u};
@@ -279,17 +401,14 @@ static int prepare_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, int wan
             double M = (double)h[0];
             for (int it = 0; it < 8 && h[0] < h[2]; ++it) M = (double)h[0] / (1.0 - exp(-(double)h[2] / (M > 1.0 ? M : 1.0)));
             const ImageFacts guess = {(uint32_t)(M < (double)kCells ? M : (double)kCells), h[1] * 10u >= h[2] ? 1u : 0u};
-            const double table = cube_seconds(s->k, &guess) + label_pass + bind_seconds(n) / 16.0;
+            const double table = cube_seconds(s->k, &guess) + label_pass_s + bind_seconds(n) / 16.0;
             try_table = table < scan_seconds(n, s->k, guess.hot != 0u);
             if (log_debug()) fprintf(stderr, "[kmeans_hip] prepare: %u of %u samples' cells, %u in crowded cells -> ~%u occupied%s: %s\n", h[0], h[2], h[1],
                                      guess.occupied, guess.hot ? ", hot" : "", try_table ? "bind" : "per-pixel scan");
         }
     }
     if (try_table) {
-        if (!fresh) {
-            int rc = bind_image_impl(s, d_rgba, n, stream, false, 0);
-            if (rc != KMG_OK) return rc;
-        }
+        if (!fresh) KMG_TRY(bind_image_impl(s, d_rgba, n, stream, false, 0));
         // now the histogram has been seen: occupied cells, hot cells -- the model answers for THIS image
         const ImageFacts facts = {s->tab.n_occ, s->tab.n_hot};
         if (fresh || table_pays(s->p, n, s->k, want_labels != 0, &facts)) {
@@ -299,8 +418,8 @@ static int prepare_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, int wan
             s->tab.rgba = nullptr;   // (the blocks stay with the object: the next image may want them)
             if (log_debug()) fprintf(stderr, "[kmeans_hip] prepare: %u occupied cells, %u hot cells -- the per-pixel scan after all\n", facts.occupied, facts.hot);
         }
-    } else if (s->tab.rgba == d_rgba) {
-        s->tab.rgba = nullptr;   // the cost model prefers the per-pixel scan for this problem
+    } else {
+        drop_binding_of(s, d_rgba);   // the cost model prefers the per-pixel scan for this problem
     }
     if (strategy) *strategy = chosen;
     return KMG_OK;
@@ -342,8 +461,7 @@ extern "C" int kmg_debug_check_table(kmg_lloyd *s, uint64_t out[3], void *stream
 try {
     if (!s || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "bad check_table arguments");
     HIP_TRY(hipSetDevice(s->p->device));
-    int rc;
-    if ((rc = ensure_bounds(s->p, S(stream))) != KMG_OK) return rc;
+    KMG_TRY(ensure_bounds(s->p, S(stream)));
     DevBuf masks, viol, labels, sub, cwork;
     HIP_TRY(masks.alloc(cube_masks_bytes(s->k)));
     HIP_TRY(cwork.alloc(cube_work_bytes()));
@@ -351,6 +469,7 @@ try {
     HIP_TRY(labels.alloc((size_t)(s->k <= 256 ? 1 : 2) << 24));
     HIP_TRY(sub.alloc(sizeof(uint16_t) * (kSubCells + kCells) + sizeof(uint32_t) * kCells));
     HIP_TRY(hipMemsetAsync(viol.ptr, 0, 3 * sizeof(unsigned long long), S(stream)));
+    // (no image, buffers of its own: the one cube launch that is not cube_pass)
     HIP_TRY(launch_cube(nullptr, nullptr, nullptr, nullptr, nullptr, s->p->d_bounds, s->p->d_sub_bounds, s->d_cent, s->k,
                         s->p->d_lab_table, (uint64_t *)masks.ptr, cwork.ptr, labels.ptr, (uint16_t *)sub.ptr, nullptr, 0, 1u, nullptr,
                         S(stream), nullptr, affine_for(s->p, s->k, S(stream))));
@@ -363,6 +482,23 @@ try {
     return KMG_OK;
 }
 KMG_ABI_CATCH
+
+// statistics / checks read the cell masks and the per-colour labels of EVERY cell, which the normal pass does
+// not store: repeat the cube pass of the bound image for the current centroids with both switched on
+static int debug_refresh(kmg_lloyd *s, hipStream_t st, unsigned long long stage[8] = nullptr)
+{
+    ColourTable &t = s->tab;
+    if (t.d_work_share) return fail(KMG_ERR_INVALID_ARGUMENT, "statistics / checks of a bound image need the whole cube: a cell share is set");
+    KMG_TRY(side_flush(s, st));
+    // d_partials is scratch here: the sums of this repeat pass and, behind them, the stage counters
+    unsigned long long *d_stage = reinterpret_cast<unsigned long long *>(s->d_partials) + 4ull * s->k;
+    HIP_TRY(hipMemsetAsync(s->d_partials, 0, sizeof(int64_t) * (4ull * s->k + 8ull), st));
+    HIP_TRY(cube_pass(s, st, s->d_partials, 1u, false, false, 1u, nullptr, d_stage));
+    t.entries_valid = true;
+    if (stage) HIP_TRY(hipMemcpyAsync(stage, d_stage, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return KMG_OK;
+}
 
 // test / tuning support: statistics of the last colour-table pass of the bound image.
 // out[0] occupied cells, [1] sum of candidate counts over occupied cells, [2] occupied cells with one
@@ -377,9 +513,8 @@ try {
     if (!s->tab.rgba || !s->tab.tables_valid) return fail(KMG_ERR_INVALID_ARGUMENT, "no current colour table");
     HIP_TRY(hipSetDevice(s->p->device));
     HIP_TRY(hipStreamSynchronize(S(stream)));
-    int rc_;
     unsigned long long stage[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if ((rc_ = debug_refresh(s, S(stream), stage)) != KMG_OK) return rc_;
+    KMG_TRY(debug_refresh(s, S(stream), stage));
     const uint32_t words = mask_words(s->k);
     std::vector<uint64_t> masks((size_t)kCells * words);
     std::vector<int64_t> agg(4ull * kCells);
@@ -436,8 +571,7 @@ try {
     if (s->k > 256) return fail(KMG_ERR_INVALID_ARGUMENT, "pair entries exist for k <= 256 only");
     HIP_TRY(hipSetDevice(s->p->device));
     HIP_TRY(hipStreamSynchronize(S(stream)));
-    int rc_;
-    if ((rc_ = debug_refresh(s, S(stream), nullptr)) != KMG_OK) return rc_;
+    KMG_TRY(debug_refresh(s, S(stream), nullptr));
     std::vector<uint32_t> hist(1u << 24), pairs(kCells);
     std::vector<uint8_t> labels(1u << 24);
     HIP_TRY(hipMemcpy(hist.data(), s->tab.d_hist, hist.size() * 4, hipMemcpyDeviceToHost));
@@ -472,146 +606,7 @@ try {
 }
 KMG_ABI_CATCH
 
-// statistics / checks read the cell masks and the per-colour labels of EVERY cell, which the normal pass does
-// not store: repeat the cube pass of the bound image for the current centroids with both switched on
-// The balancing state of the next cube pass of a loop (kmg_table.h CubeBalance): the passes count on as long as the same work list is
-// walked -- the image's, or one share of it; a new list (another binding, another share) starts over.
-static CubeBalance next_balance(ColourTable &t, const uint32_t *work)
-{
-    if (t.balance_work != work) { t.balance_work = work; t.balance_pass = 0; }
-    CubeBalance b;
-    b.state = t.d_balance;
-    b.pass = t.balance_pass++;
-    return b;
-}
-
-static int debug_refresh(kmg_lloyd *s, hipStream_t st, unsigned long long stage[8] = nullptr)
-{
-    ColourTable &t = s->tab;
-    int rc_;
-    if (t.d_work_share) return fail(KMG_ERR_INVALID_ARGUMENT, "statistics / checks of a bound image need the whole cube: a cell share is set");
-    if ((rc_ = side_flush(s, st)) != KMG_OK) return rc_;
-    // d_partials is scratch here: the sums of this repeat pass and, behind them, the stage counters
-    unsigned long long *d_stage = reinterpret_cast<unsigned long long *>(s->d_partials) + 4ull * s->k;
-    HIP_TRY(hipMemsetAsync(s->d_partials, 0, sizeof(int64_t) * (4ull * s->k + 8ull), st));
-    HIP_TRY(launch_cube(t.d_hist, t.d_agg, t.d_sub_agg, t.d_occ, t.d_work, s->p->d_bounds, s->p->d_sub_bounds, s->d_cent, s->k,
-                        s->p->d_lab_table, t.d_masks, t.d_cell_work, t.d_colour_labels, t.d_sub, s->d_partials, 1u, 1u | (t.n_hot ? kCubeHot : 0u), d_stage, st,
-                        nullptr, affine_for(s->p, s->k, st)));
-    t.entries_valid = true;
-    if (stage) HIP_TRY(hipMemcpyAsync(stage, d_stage, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return KMG_OK;
-}
-
-// label passes that kmg_lloyd_iterate left running on the side stream: `st` waits for them (no host sync)
-static int side_flush(kmg_lloyd *s, hipStream_t st)
-{
-    for (int i = 0; i < 2; ++i)
-        if (s->lab_pending[i]) {
-            HIP_TRY(hipStreamWaitEvent(st, s->ev_lab[i], 0));
-            s->lab_pending[i] = false;
-        }
-    return KMG_OK;
-}
-
-static bool table_bound(const kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n)
-{
-    if (s->weighted) return false;   // (the initialisation of a weighted object may have bound the image: its passes do not use that)
-    return s->tab.rgba != nullptr && s->tab.rgba == d_rgba && s->tab.n == n;
-}
-
-// labels (optional) + sums through the colour table.  The cube workgroups add their sums into `rows` shared
-// rows of `d_sums` (k x 4 int64 each): the caller's accumulators directly (rows = 1, no reduction pass), or
-// the partial slab for the two-step entry points.
-// the label pass's first-level tables (pair entries / cell summaries) of the current per-colour labels, if a pass deferred them
-static int ensure_entries(kmg_lloyd *s, hipStream_t st)
-{
-    ColourTable &t = s->tab;
-    if (t.entries_valid) return KMG_OK;
-    HIP_TRY(launch_cube_entries(t.d_work_share ? t.d_work_share : t.d_work, t.d_occ, t.d_colour_labels, t.d_sub, s->k, st));
-    t.entries_valid = true;
-    return KMG_OK;
-}
-
-static int table_assign(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, uint32_t *d_labels, int64_t *d_sums,
-                        uint32_t rows, hipStream_t st, bool update_after = false, bool defer_entries = false, bool add_in_place = false)
-{
-    if (d_labels) defer_entries = false;
-    ColourTable &t = s->tab;
-    if (add_in_place) {
-        // the cube pass ADDS its sums to d_sums as it stands (the caller keeps it zero between passes, or carries other sums in
-        // it): no hand-over, no clearing -- no tail launch (kmg_lloyd_accumulate_into)
-        if (d_labels || update_after || rows != 1u) return fail(KMG_ERR_INVALID_ARGUMENT, "table_assign: in-place sums are sums only");
-        t.bound_by_init = false;
-        int rc2;
-        if ((rc2 = side_flush(s, st)) != KMG_OK) return rc2;
-        const CubeBalance bal = next_balance(t, t.d_work_share ? t.d_work_share : t.d_work);
-        PROF_LAUNCH(s, KMG_K_CUBE, st, launch_cube(t.d_hist, t.d_agg, t.d_sub_agg, t.d_occ, t.d_work_share ? t.d_work_share : t.d_work,
-                                                   s->p->d_bounds, s->p->d_sub_bounds, s->d_cent, s->k, s->p->d_lab_table, t.d_masks, t.d_cell_work,
-                                                   t.d_colour_labels, t.d_sub, d_sums, 1u, t.n_hot ? kCubeHot : 0u, nullptr, st, nullptr,
-                                                   affine_for(s->p, s->k, st), &bal));
-        t.entries_valid = true;
-        t.tables_valid = t.d_work_share == nullptr;
-        return KMG_OK;
-    }
-    // With a cell share set (kmg_lloyd_set_cell_share) a pass labels one share of the cube and returns ITS sums: the label
-    // tables are complete only after the caller's all-gather, the sums only after its all-reduce.  A label map, a centroid
-    // update or the two-step partial sums from such a pass would silently be those of a fraction of the image.
-    if (t.d_work_share && (d_labels || update_after || rows != 1u))
-        return fail(KMG_ERR_INVALID_ARGUMENT, "a cell share is set: this pass returns one share's sums only -- no label map, no "
-                    "update, no partial rows (all-reduce the sums, all-gather the tables, then kmg_lloyd_labels_from_tables)");
-    t.bound_by_init = false;      // only a prepare() that directly follows the initialisation may reuse its binding
-    int rc_;
-    if ((rc_ = side_flush(s, st)) != KMG_OK) return rc_;
-    if (rows == 1u) {
-        // the sums accumulate in the state's own buffer, which is zero between passes: the last launch of the cube pass
-        // hands them over to d_sums, clears the buffer again and -- update_after -- updates the centroids from them
-        // (CubeTail): neither a memset nor a k_update launch
-        if (s->acc_int_dirty) HIP_TRY(hipMemsetAsync(s->d_acc_int, 0, sizeof(int64_t) * 4ull * s->k, st));
-        s->acc_int_dirty = true;
-        CubeTail tail;
-        tail.acc_out = d_sums;
-        tail.do_update = update_after ? 1 : 0;
-        tail.convergence = s->p->opt.convergence;
-        tail.cent = s->d_cent;
-        tail.n_converged = s->d_nconv;
-        // (k <= 32, and 32 < k <= 256 without hot cells: the cube pass is one launch, and when a label pass follows, its tail rides on that one)
-        static const bool tail_rides = tools_env_int(KMG_TOOLS_ENV("KMG_TAIL_ON_LABELS"), 1) != 0;   // (tools build: 0 = a launch of its own)
-        const bool tail_on_labels = tail_rides && d_labels != nullptr && s->k <= 256u && cube_single_launch(s->k, t.n_hot ? kCubeHot : 0u);
-        const CubeBalance bal = next_balance(t, t.d_work_share ? t.d_work_share : t.d_work);
-        PROF_LAUNCH(s, KMG_K_CUBE, st, launch_cube(t.d_hist, t.d_agg, t.d_sub_agg, t.d_occ, t.d_work_share ? t.d_work_share : t.d_work,
-                                                   s->p->d_bounds, s->p->d_sub_bounds,
-                                                   s->d_cent, s->k, s->p->d_lab_table, t.d_masks, t.d_cell_work, t.d_colour_labels, t.d_sub,
-                                                   s->d_acc_int, 1u, (defer_entries ? kCubeNoEntries : 0u) | (t.n_hot ? kCubeHot : 0u), nullptr, st,
-                                                   tail_on_labels ? nullptr : &tail, affine_for(s->p, s->k, st), &bal));
-        t.entries_valid = !defer_entries;
-        if (tail_on_labels) {
-            t.tables_valid = true;
-            PROF_LAUNCH(s, KMG_K_LABELS, st, launch_labels((const uint32_t *)d_rgba, n, t.d_colour_labels, t.d_sub, s->k, nullptr, d_labels, st,
-                                                           s->reserve_cus, t.n_hot ? t.d_work + kCells + 1 : nullptr, &tail, s->d_acc_int));
-            s->acc_int_dirty = false;
-            if (update_after) t.tables_valid = false;
-            return KMG_OK;
-        }
-        s->acc_int_dirty = false;
-    } else {
-        if (update_after) return fail(KMG_ERR_INVALID_ARGUMENT, "table_assign: update_after needs the final sums");
-        HIP_TRY(hipMemsetAsync(d_sums, 0, sizeof(int64_t) * 4ull * s->k * rows, st));
-        PROF_LAUNCH(s, KMG_K_CUBE, st, launch_cube(t.d_hist, t.d_agg, t.d_sub_agg, t.d_occ, t.d_work, s->p->d_bounds, s->p->d_sub_bounds,
-                                                   s->d_cent, s->k, s->p->d_lab_table, t.d_masks, t.d_cell_work, t.d_colour_labels, t.d_sub,
-                                                   d_sums, rows, t.n_hot ? kCubeHot : 0u, nullptr, st, nullptr, affine_for(s->p, s->k, st)));
-        t.entries_valid = true;
-    }
-    // (a share's pass leaves the tables current for ITS cells only: kmg_lloyd_labels refuses them, _labels_from_tables -- after
-    // the caller's all-gather -- takes them as they stand)
-    t.tables_valid = t.d_work_share == nullptr;
-    if (d_labels)
-        PROF_LAUNCH(s, KMG_K_LABELS, st, launch_labels((const uint32_t *)d_rgba, n, t.d_colour_labels, t.d_sub, s->k, nullptr, d_labels, st, s->reserve_cus, t.n_hot ? t.d_work + kCells + 1 : nullptr));
-    // (after an update the tables still describe the assignment just made, not the new centroids)
-    if (update_after) t.tables_valid = false;
-    return KMG_OK;
-}
-
+// ---- the object: create / destroy, centroids in and out ----
 // pool_stream != NULL: the small workspace buffers are stream-ordered allocations on that stream (the
 // per-call objects of the host-buffer API, which would otherwise pay ~6 hipMalloc + hipFree per call)
 int lloyd_create_impl(kmg_processor *p, uint32_t k, kmg_lloyd **out, hipStream_t pool_stream)
@@ -620,17 +615,12 @@ int lloyd_create_impl(kmg_processor *p, uint32_t k, kmg_lloyd **out, hipStream_t
     *out = nullptr;
     KMG_TRY(check_k(k));
     HIP_TRY(hipSetDevice(p->device));
-    kmg_lloyd *s = new (std::nothrow) kmg_lloyd();
+    kmg_lloyd *s = new (std::nothrow) kmg_lloyd();                    // (every member has its default: kmg_state.h)
     if (!s) return fail(KMG_ERR_OUT_OF_MEMORY, "host allocation failed");
     s->p = p;
     s->k = k;
-    s->d_cent = nullptr; s->d_partials = nullptr; s->d_acc = nullptr; s->d_nconv = nullptr;
-    s->d_key = nullptr; s->d_dist = nullptr; s->dist_cap = 0; s->last_rows = 0; s->prof = 0; s->init_colours = false;
-    s->side = nullptr; s->ev_cube = nullptr; s->ev_lab[0] = s->ev_lab[1] = nullptr;
-    s->lab_pending[0] = s->lab_pending[1] = false; s->set = 0;
     s->pooled = pool_stream != nullptr;
     s->pool_stream = pool_stream;
-    s->ws = nullptr; s->ws_cap = 0; s->dist_blk_cap = 0;
     s->h_slot = host_slot_take(p);
     // one block from the processor's idle blocks (a warm processor creates a kmg_lloyd without a hipMalloc)
     const size_t sizes[6] = {sizeof(Centroid) * k, sizeof(int64_t) * 4ull * k * 2048ull, sizeof(int64_t) * 4ull * k, sizeof(uint32_t) * kStateWords,
@@ -645,8 +635,7 @@ int lloyd_create_impl(kmg_processor *p, uint32_t k, kmg_lloyd **out, hipStream_t
         s->d_acc = (int64_t *)carve(s->ws, off, sizes[2]);
         s->d_nconv = (uint32_t *)carve(s->ws, off, sizes[3]);
         s->d_key = (unsigned long long *)carve(s->ws, off, sizes[4]);
-        s->d_acc_int = (int64_t *)carve(s->ws, off, sizes[5]);
-        s->acc_int_dirty = true;                                      // cleared in stream order by the first pass
+        s->d_acc_int = (int64_t *)carve(s->ws, off, sizes[5]);        // (acc_int_dirty: cleared in stream order by the first pass)
         auto zero = [&](void *ptr, size_t bytes) {
             return s->pooled ? hipMemsetAsync(ptr, 0, bytes, pool_stream) : hipMemset(ptr, 0, bytes);
         };
@@ -657,8 +646,7 @@ int lloyd_create_impl(kmg_processor *p, uint32_t k, kmg_lloyd **out, hipStream_t
     }
     if (e != hipSuccess) {
         kmg_lloyd_destroy(s);
-        return fail(e == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP,
-                    "lloyd workspace allocation failed: %s", hipGetErrorString(e));
+        return fail_hip(e, "lloyd workspace allocation");
     }
     *out = s;
     return KMG_OK;
@@ -691,15 +679,21 @@ try {
 }
 KMG_ABI_CATCH_VOID
 
+// a caller's (L, a, b, unused) as a centroid of the device table
+static Centroid centroid_of(const float *c4)
+{
+    Centroid c;
+    c.L = c4[0]; c.a = c4[1]; c.b = c4[2];
+    c.C = chroma(c.a, c.b);
+    return c;
+}
+
 extern "C" int kmg_lloyd_set_centroids(kmg_lloyd *s, const float *c4, void *stream)
 try {
     if (!s || !c4) return fail(KMG_ERR_INVALID_ARGUMENT, "bad set_centroids arguments");
     HIP_TRY(hipSetDevice(s->p->device));
     std::vector<Centroid> h(s->k);
-    for (uint32_t i = 0; i < s->k; ++i) {
-        h[i].L = c4[4 * i]; h[i].a = c4[4 * i + 1]; h[i].b = c4[4 * i + 2];
-        h[i].C = chroma(h[i].a, h[i].b);
-    }
+    for (uint32_t i = 0; i < s->k; ++i) h[i] = centroid_of(c4 + 4 * i);
     s->tab.tables_valid = false;
     // a caller's table starts another problem than the one the initialisation bound the buffer for: kmg_lloyd_run / _prepare
     // must not take that binding over (the next frame may have arrived in the same buffer since)
@@ -726,6 +720,7 @@ try {
 }
 KMG_ABI_CATCH
 
+// ---- initialisation ----
 // Farthest-point init: k - 1 passes over the pixels (two launches, ~8e-6 s, + n * 7.0e-12 s each: sRGB->Lab + literal
 // CIE94 per pixel) or over the image's colours (one launch per pass: ~1.05e-5 s once most cells are skipped, ~3e-5 s
 // more for each of the first ~16 passes, which reach every cell) after binding the image (bind_seconds, x 1.5 with the
@@ -756,7 +751,7 @@ static int init_over_colours(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, ui
     // an initialisation starts a new problem: the image is (re)bound from the buffer's current contents,
     // so the loop that follows never works from the histogram of an earlier image in the same buffer
     if (first_index + n > 0xFFFFFFF0ull || !init_table_pays(s->p, n, s->k, n_seeds)) {
-        if (s->tab.rgba == d_rgba) s->tab.rgba = nullptr;
+        drop_binding_of(s, d_rgba);
         return KMG_OK;
     }
     ColourTable &t = s->tab;
@@ -765,17 +760,81 @@ static int init_over_colours(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, ui
         const hipError_t e = block_take(s->p, need, &t.blk_init, &t.blk_init_cap);
         if (e != hipSuccess) {
             t.blk_init = nullptr; t.blk_init_cap = 0;
-            return fail(e == hipErrorOutOfMemory ? KMG_ERR_OUT_OF_MEMORY : KMG_ERR_HIP, "init tables allocation failed: %s", hipGetErrorString(e));
+            return fail_hip(e, "init tables allocation");
         }
         size_t off = 0;
         t.d_tie = (uint32_t *)carve(t.blk_init, off, sizeof(uint32_t) << 24);
         t.d_cdist = (float *)carve(t.blk_init, off, sizeof(float) << 24);
         t.d_init_cells = carve(t.blk_init, off, init_scratch_bytes());
     }
-    int rc;
-    if ((rc = bind_image_impl(s, d_rgba, n, stream, true, first_index)) != KMG_OK) return rc;
+    KMG_TRY(bind_image_impl(s, d_rgba, n, stream, true, first_index));
     t.bound_by_init = true;
     *colours = true;
+    return KMG_OK;
+}
+
+// The distance map of a per-pixel initialisation, n floats at least: the one way it grows.  A map that is too small is freed, not
+// parked -- a distance map serves nothing else -- once the stream's work on it is through.
+static int ensure_dist(kmg_lloyd *s, uint64_t n, hipStream_t st)
+{
+    if (s->dist_cap >= n) return KMG_OK;
+    if (s->d_dist) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipFree(s->d_dist));
+        s->d_dist = nullptr; s->dist_cap = 0; s->dist_blk_cap = 0;
+    }
+    HIP_TRY(block_take(s->p, sizeof(float) * n, (void **)&s->d_dist, &s->dist_blk_cap));
+    s->dist_cap = n;
+    return KMG_OK;
+}
+
+// plus_plus_init.wgsl:161-168 `initial`: pixel (floor(w rand(42)), floor(h rand(12))); rand(42) = 0.5625, rand(12) = 0.93359375 in
+// IEEE binary32
+static uint64_t first_pixel(uint32_t w, uint32_t h)
+{
+    const int32_t x0 = (int32_t)((float)w * 0.5625f);
+    const int32_t y0 = (int32_t)((float)h * 0.93359375f);
+    return (uint64_t)y0 * w + (uint64_t)x0;
+}
+
+// The multi-pick launches of an initialisation with k >= 32, over the pixels or over the colours.  Launches go out in chunks -- the
+// reference submits its passes 32 at a time and polls, modules.rs:949,1211-1246 -- and the number of centroids chosen so far comes
+// back in between (a launch picks one to four; one that finds the table complete does nothing).  launch_no(i): enqueue launch i;
+// count_of(i): where launch i leaves the count; route: what the debug line calls the route.
+template <class Launch, class Count>
+static int init_multi_loop(kmg_lloyd *s, hipStream_t st, const char *route, Launch launch_no, Count count_of)
+{
+    uint32_t have = 1u, launch = 1u, launches = 0u;
+    while (have < s->k) {
+        // (launch 1 only sweeps; early launches pick ~1.3 centroids each over the pixels, ~2 over the colours, late ones 3 .. 3.6 of at
+        // most 4: a third of what is missing, then look)
+        const uint32_t chunk = (launch == 1u ? 1u : 0u) + (s->k - have + 2u) / 3u;
+        for (uint32_t q = 0; q < chunk; ++q, ++launch) HIP_TRY(launch_no(launch));
+        launches += chunk;
+        uint32_t *h = s->h_slot ? static_cast<uint32_t *>(s->h_slot) : &have;
+        HIP_TRY(hipMemcpyAsync(h, count_of(launch - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        have = *static_cast<volatile uint32_t *>(h);
+        if (have == 0u || have > s->k) return fail(KMG_ERR_HIP, "initialisation: centroid count %u out of range", have);
+    }
+    if (log_debug()) fprintf(stderr, "[kmeans_hip] initialisation%s: %u centroids in %u launches\n", route, s->k, launches);
+    return KMG_OK;
+}
+
+// The single-pick launches first_j .. of either route (modules.rs:1211-1246): launch j picks centroid j - 1 and runs pass j
+static int init_single_picks(kmg_lloyd *s, const uint32_t *rgba, uint64_t n, uint32_t first_j, bool colours, hipStream_t st)
+{
+    if (colours) {
+        for (uint32_t j = first_j; j <= s->k; ++j)                  // (launch k only picks)
+            HIP_TRY(launch_init_pass_cells(s->tab.d_tie, s->tab.d_occ, s->p->d_lab_table, s->d_cent, j, j < s->k ? 1 : 0, s->tab.d_cdist,
+                                           s->tab.d_init_cells, nullptr, rgba, s->p->d_lut, st));
+        return KMG_OK;
+    }
+    // (launch 1 picks nothing.)  The workgroups' keys travel through two slot sets in the partial-sum slab, which nothing else uses
+    // during the initialisation (kmg_kernels.h); the last centroid comes from the last pass's slots
+    unsigned long long *slots = (unsigned long long *)s->d_partials;
+    for (uint32_t j = first_j; j < s->k; ++j) HIP_TRY(launch_init_pass(rgba, n, s->p->d_lut, s->d_cent, j, s->d_dist, slots, 0, st, true));
+    HIP_TRY(launch_init_pick_slots(rgba, n, s->p->d_lut, slots, s->d_cent, s->k - 1u, st));
     return KMG_OK;
 }
 
@@ -786,85 +845,26 @@ try {
     const uint64_t n = (uint64_t)w * h;
     KMG_TRY(check_pixel_count(n));
     s->tab.tables_valid = false;
-    // plus_plus_init.wgsl:161-168: rand(42) = 0.5625, rand(12) = 0.93359375 in IEEE binary32
-    const int32_t x0 = (int32_t)((float)w * 0.5625f);
-    const int32_t y0 = (int32_t)((float)h * 0.93359375f);
-    const uint64_t i0 = (uint64_t)y0 * w + (uint64_t)x0;
     const uint32_t *rgba = (const uint32_t *)d_rgba;
-    HIP_TRY(launch_init_first(rgba, i0, s->p->d_lut, s->d_cent, s->d_key, S(stream)));
+    hipStream_t st = S(stream);
+    HIP_TRY(launch_init_first(rgba, first_pixel(w, h), s->p->d_lut, s->d_cent, s->d_key, st));
     // (k = 1 has no pass that would decide about the binding: the earlier binding of this buffer is dropped here)
-    if (s->k == 1 && s->tab.rgba == d_rgba) s->tab.rgba = nullptr;
-    if (s->k > 1) {
-        int rc;
-        bool colours = false;
-        if ((rc = init_over_colours(s, d_rgba, n, 0, &colours, stream)) != KMG_OK) return rc;
-        if (!colours && s->dist_cap < n) {
-            if (s->d_dist) {
-                // (too small for this image: freed, not parked -- a distance map serves nothing else)
-                HIP_TRY(hipStreamSynchronize(S(stream)));
-                HIP_TRY(hipFree(s->d_dist));
-                s->d_dist = nullptr; s->dist_cap = 0; s->dist_blk_cap = 0;
-            }
-            HIP_TRY(block_take(s->p, sizeof(float) * n, (void **)&s->d_dist, &s->dist_blk_cap));
-            s->dist_cap = n;
-        }
-        // Per-pixel passes of a whole image, k >= 32: several centroids per launch (kmg_kernels.h
-        // launch_init_multi).  Launches go out in chunks -- the reference submits its passes 32 at a time and polls,
-        // modules.rs:949,1211-1246 -- and the number of centroids chosen so far comes back in between (a launch picks one to
-        // four; one that finds the table complete does nothing).
-        if (!colours && s->k >= 32u && init_multi_bytes(n) <= sizeof(int64_t) * 4ull * s->k * 2048ull) {
-            uint32_t have = 1u, launch = 1u, launches = 0u;
-            while (have < s->k) {
-                // (launch 1 only sweeps; early launches pick ~1.3 centroids each, late ones ~3: a third of what is missing, then look)
-                const uint32_t chunk = (launch == 1u ? 1u : 0u) + (s->k - have + 2u) / 3u;
-                for (uint32_t q = 0; q < chunk; ++q, ++launch)
-                    HIP_TRY(launch_init_multi(rgba, n, s->p->d_lut, s->d_cent, s->k, launch, s->d_dist, s->d_partials, S(stream)));
-                launches += chunk;
-                uint32_t *h = s->h_slot ? static_cast<uint32_t *>(s->h_slot) : &have;
-                HIP_TRY(hipMemcpyAsync(h, init_multi_count(s->d_partials, n, launch - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, S(stream)));
-                HIP_TRY(hipStreamSynchronize(S(stream)));
-                have = *static_cast<volatile uint32_t *>(h);
-                if (have == 0u || have > s->k) return fail(KMG_ERR_HIP, "initialisation: centroid count %u out of range", have);
-            }
-            if (log_debug()) fprintf(stderr, "[kmeans_hip] initialisation: %u centroids in %u launches\n", s->k, launches);
-            return KMG_OK;
-        }
-        // Passes over the colours, k >= 32: several centroids per launch as well (kmg_table.h launch_init_cells_multi; early
-        // launches pick ~2, late ones ~3.6 of at most 4: a third of what is missing, then look)
-        if (colours && s->k >= 32u) {
-            uint32_t have = 1u, launch = 1u, launches = 0u;
-            while (have < s->k) {
-                const uint32_t chunk = (launch == 1u ? 1u : 0u) + (s->k - have + 2u) / 3u;
-                for (uint32_t q = 0; q < chunk; ++q, ++launch)
-                    HIP_TRY(launch_init_cells_multi(s->tab.d_tie, s->tab.d_occ, s->p->d_lab_table, s->d_cent, s->k, launch, s->tab.d_cdist,
-                                                    s->tab.d_init_cells, rgba, s->p->d_lut, S(stream)));
-                launches += chunk;
-                uint32_t *h = s->h_slot ? static_cast<uint32_t *>(s->h_slot) : &have;
-                HIP_TRY(hipMemcpyAsync(h, init_cells_multi_count(s->tab.d_init_cells, launch - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                       S(stream)));
-                HIP_TRY(hipStreamSynchronize(S(stream)));
-                have = *static_cast<volatile uint32_t *>(h);
-                if (have == 0u || have > s->k) return fail(KMG_ERR_HIP, "initialisation: centroid count %u out of range", have);
-            }
-            if (log_debug()) fprintf(stderr, "[kmeans_hip] initialisation over the colours: %u centroids in %u launches\n", s->k, launches);
-            return KMG_OK;
-        }
-        for (uint32_t j = 1; j < s->k + (colours ? 1u : 0u); ++j) {   // modules.rs:1211-1246
-            if (colours) {
-                // launch j picks centroid j - 1 and runs pass j; launch k only picks
-                HIP_TRY(launch_init_pass_cells(s->tab.d_tie, s->tab.d_occ, s->p->d_lab_table, s->d_cent, j,
-                                               j < s->k ? 1 : 0, s->tab.d_cdist, s->tab.d_init_cells, nullptr, rgba, s->p->d_lut,
-                                               S(stream)));
-            } else {
-                // launch j picks centroid j - 1 (j >= 2) and runs pass j; the workgroups' keys travel through two slot sets
-                // in the partial-sum slab, which nothing else uses during the initialisation (kmg_kernels.h)
-                HIP_TRY(launch_init_pass(rgba, n, s->p->d_lut, s->d_cent, j, s->d_dist, (unsigned long long *)s->d_partials, 0, S(stream), true));
-            }
-        }
-        if (!colours)       // the last centroid, from the last pass's slots
-            HIP_TRY(launch_init_pick_slots(rgba, n, s->p->d_lut, (const unsigned long long *)s->d_partials, s->d_cent, s->k - 1u, S(stream)));
-    }
-    return KMG_OK;
+    if (s->k == 1) { drop_binding_of(s, d_rgba); return KMG_OK; }
+    bool colours = false;
+    KMG_TRY(init_over_colours(s, d_rgba, n, 0, &colours, stream));
+    if (!colours) KMG_TRY(ensure_dist(s, n, st));
+    // Per-pixel passes of a whole image, k >= 32: several centroids per launch (kmg_kernels.h launch_init_multi)
+    if (!colours && s->k >= 32u && init_multi_bytes(n) <= sizeof(int64_t) * 4ull * s->k * 2048ull)
+        return init_multi_loop(s, st, "",
+            [&](uint32_t i) { return launch_init_multi(rgba, n, s->p->d_lut, s->d_cent, s->k, i, s->d_dist, s->d_partials, st); },
+            [&](uint32_t i) { return init_multi_count(s->d_partials, n, i); });
+    // Passes over the colours, k >= 32: several centroids per launch as well (kmg_table.h launch_init_cells_multi)
+    if (colours && s->k >= 32u)
+        return init_multi_loop(s, st, " over the colours",
+            [&](uint32_t i) { return launch_init_cells_multi(s->tab.d_tie, s->tab.d_occ, s->p->d_lab_table, s->d_cent, s->k, i, s->tab.d_cdist,
+                                                             s->tab.d_init_cells, rgba, s->p->d_lut, st); },
+            [&](uint32_t i) { return init_cells_multi_count(s->tab.d_init_cells, i); });
+    return init_single_picks(s, rgba, n, 1u, colours, st);
 }
 KMG_ABI_CATCH
 
@@ -885,43 +885,25 @@ try {
     KMG_TRY(check_pixel_count(n));
     s->tab.tables_valid = false;
     std::vector<Centroid> seeds(n_seeds);
-    for (uint32_t i = 0; i < n_seeds; ++i) {
-        seeds[i].L = seeds4[4 * i]; seeds[i].a = seeds4[4 * i + 1]; seeds[i].b = seeds4[4 * i + 2];
-        seeds[i].C = chroma(seeds[i].a, seeds[i].b);
-    }
+    for (uint32_t i = 0; i < n_seeds; ++i) seeds[i] = centroid_of(seeds4 + 4 * i);
     HIP_TRY(hipMemcpyAsync(s->d_cent, seeds.data(), sizeof(Centroid) * n_seeds, hipMemcpyHostToDevice, S(stream)));
     HIP_TRY(hipStreamSynchronize(S(stream)));
     // (every centroid given: no pass decides about the binding, the earlier binding of this buffer is dropped here)
     if (s->k == n_seeds) {
-        if (s->tab.rgba == d_rgba) s->tab.rgba = nullptr;
+        drop_binding_of(s, d_rgba);
         return KMG_OK;
     }
-    int rc;
     bool colours = false;
-    if ((rc = init_over_colours(s, d_rgba, n, 0, &colours, stream, n_seeds)) != KMG_OK) return rc;
+    KMG_TRY(init_over_colours(s, d_rgba, n, 0, &colours, stream, n_seeds));
     const uint32_t *rgba = (const uint32_t *)d_rgba;
     if (colours) {
         HIP_TRY(launch_init_seed_cells(s->tab.d_tie, s->tab.d_occ, s->p->d_lab_table, s->d_cent, n_seeds, s->tab.d_cdist, s->tab.d_init_cells,
                                        S(stream)));
-        for (uint32_t j = n_seeds + 1u; j <= s->k; ++j)             // launch j picks centroid j - 1 and runs pass j; launch k only picks
-            HIP_TRY(launch_init_pass_cells(s->tab.d_tie, s->tab.d_occ, s->p->d_lab_table, s->d_cent, j, j < s->k ? 1 : 0, s->tab.d_cdist,
-                                           s->tab.d_init_cells, nullptr, rgba, s->p->d_lut, S(stream)));
-        return KMG_OK;
+    } else {
+        KMG_TRY(ensure_dist(s, n, S(stream)));
+        HIP_TRY(launch_init_seed(rgba, n, s->p->d_lut, s->d_cent, n_seeds, s->d_dist, (unsigned long long *)s->d_partials, S(stream)));
     }
-    if (s->dist_cap < n) {
-        if (s->d_dist) {
-            HIP_TRY(hipFree(s->d_dist));                             // (the stream was synchronised above)
-            s->d_dist = nullptr; s->dist_cap = 0; s->dist_blk_cap = 0;
-        }
-        HIP_TRY(block_take(s->p, sizeof(float) * n, (void **)&s->d_dist, &s->dist_blk_cap));
-        s->dist_cap = n;
-    }
-    unsigned long long *slots = (unsigned long long *)s->d_partials;   // (the slab nothing else uses during an initialisation)
-    HIP_TRY(launch_init_seed(rgba, n, s->p->d_lut, s->d_cent, n_seeds, s->d_dist, slots, S(stream)));
-    for (uint32_t j = n_seeds + 1u; j < s->k; ++j)
-        HIP_TRY(launch_init_pass(rgba, n, s->p->d_lut, s->d_cent, j, s->d_dist, slots, 0, S(stream), true));
-    HIP_TRY(launch_init_pick_slots(rgba, n, s->p->d_lut, slots, s->d_cent, s->k - 1u, S(stream)));
-    return KMG_OK;
+    return init_single_picks(s, rgba, n, n_seeds + 1u, colours, S(stream));
 }
 KMG_ABI_CATCH
 
@@ -948,7 +930,7 @@ KMG_ABI_CATCH
 extern "C" int kmg_lloyd_set_fixed(kmg_lloyd *s, uint32_t n_fixed)
 try {
     if (!s || n_fixed > s->k) return fail(KMG_ERR_INVALID_ARGUMENT, "bad set_fixed arguments");
-    if (s->tab.d_work_share) return fail(KMG_ERR_INVALID_ARGUMENT, "set_fixed: a cell share is set (kmg_lloyd_set_cell_share)");
+    KMG_TRY(check_no_share(s, "set_fixed"));
     if (n_fixed == s->n_fixed) return KMG_OK;
     HIP_TRY(hipSetDevice(s->p->device));
     // the updates read it from the object's state words (kmg_device.h kFixedWord).  The copy has completed when this returns:
@@ -979,10 +961,7 @@ try {
     s->tab.tables_valid = false;
     HIP_TRY(hipMemsetAsync(d_key, 0, sizeof(uint64_t), S(stream)));
     if (n_local == 0) return KMG_OK;
-    if (j == 1) {
-        int rc;
-        if ((rc = init_over_colours(s, d_rgba, n_local, first_index, &s->init_colours, stream)) != KMG_OK) return rc;
-    }
+    if (j == 1) KMG_TRY(init_over_colours(s, d_rgba, n_local, first_index, &s->init_colours, stream));
     if (s->init_colours) {
         const ColourTable &t = s->tab;
         if (t.rgba != d_rgba || t.n != n_local || !t.tie_valid || t.tie_first != first_index)
@@ -991,16 +970,9 @@ try {
                                        t.d_init_cells, (unsigned long long *)d_key, nullptr, nullptr, S(stream)));
         return KMG_OK;
     }
-    if (s->dist_cap < n_local) {
-        if (j != 1) return fail(KMG_ERR_INVALID_ARGUMENT, "init_step: the distance map of this band was never started (j = 1)");
-        if (s->d_dist) {
-            HIP_TRY(hipStreamSynchronize(S(stream)));
-            HIP_TRY(hipFree(s->d_dist));
-            s->d_dist = nullptr; s->dist_cap = 0; s->dist_blk_cap = 0;
-        }
-        HIP_TRY(block_take(s->p, sizeof(float) * n_local, (void **)&s->d_dist, &s->dist_blk_cap));
-        s->dist_cap = n_local;
-    }
+    if (s->dist_cap < n_local && j != 1)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "init_step: the distance map of this band was never started (j = 1)");
+    KMG_TRY(ensure_dist(s, n_local, S(stream)));
     HIP_TRY(launch_init_pass((const uint32_t *)d_rgba, n_local, s->p->d_lut, s->d_cent, j, s->d_dist,
                              (unsigned long long *)d_key, first_index, S(stream)));
     return KMG_OK;
@@ -1030,11 +1002,73 @@ KMG_ABI_CATCH
 
 extern "C" uint64_t kmg_init_first_key(uint32_t width, uint32_t height)
 {
-    // plus_plus_init.wgsl:161-168 `initial`: the key that names pixel (floor(w rand(42)), floor(h rand(12)))
-    const int32_t x0 = (int32_t)((float)width * 0.5625f);
-    const int32_t y0 = (int32_t)((float)height * 0.93359375f);
-    const uint64_t i0 = (uint64_t)y0 * width + (uint64_t)x0;
+    // the key that names the first pixel (first_pixel)
+    const uint64_t i0 = first_pixel(width, height);
     return (1ull << 32) | (uint64_t)((((uint32_t)(i0 >> 4)) << 4) | (15u - (uint32_t)(i0 & 15u)));
+}
+
+// ---- passes ----
+// labels (optional) + sums through the colour table.  The cube workgroups add their sums into `rows` shared
+// rows of `d_sums` (k x 4 int64 each): the caller's accumulators directly (rows = 1, no reduction pass), or
+// the partial slab for the two-step entry points.
+static int table_assign(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, uint32_t *d_labels, int64_t *d_sums,
+                        uint32_t rows, hipStream_t st, bool update_after = false, bool defer_entries = false, bool add_in_place = false)
+{
+    if (d_labels) defer_entries = false;
+    ColourTable &t = s->tab;
+    if (add_in_place) {
+        // the cube pass ADDS its sums to d_sums as it stands (the caller keeps it zero between passes, or carries other sums in
+        // it): no hand-over, no clearing -- no tail launch (kmg_lloyd_accumulate_into)
+        if (d_labels || update_after || rows != 1u) return fail(KMG_ERR_INVALID_ARGUMENT, "table_assign: in-place sums are sums only");
+        t.bound_by_init = false;
+        KMG_TRY(side_flush(s, st));
+        PROF_LAUNCH(s, KMG_K_CUBE, st, cube_pass(s, st, d_sums, 1u, true, true));
+        t.entries_valid = true;
+        t.tables_valid = t.d_work_share == nullptr;
+        return KMG_OK;
+    }
+    // With a cell share set (kmg_lloyd_set_cell_share) a pass labels one share of the cube and returns ITS sums: the label
+    // tables are complete only after the caller's all-gather, the sums only after its all-reduce.  A label map, a centroid
+    // update or the two-step partial sums from such a pass would silently be those of a fraction of the image.
+    if (t.d_work_share && (d_labels || update_after || rows != 1u))
+        return fail(KMG_ERR_INVALID_ARGUMENT, "a cell share is set: this pass returns one share's sums only -- no label map, no "
+                    "update, no partial rows (all-reduce the sums, all-gather the tables, then kmg_lloyd_labels_from_tables)");
+    t.bound_by_init = false;      // only a prepare() that directly follows the initialisation may reuse its binding
+    KMG_TRY(side_flush(s, st));
+    if (rows == 1u) {
+        // the sums accumulate in the state's own buffer, which is zero between passes: the last launch of the cube pass
+        // hands them over to d_sums, clears the buffer again and -- update_after -- updates the centroids from them
+        // (CubeTail): neither a memset nor a k_update launch
+        if (s->acc_int_dirty) HIP_TRY(hipMemsetAsync(s->d_acc_int, 0, sizeof(int64_t) * 4ull * s->k, st));
+        s->acc_int_dirty = true;
+        const CubeTail tail = make_tail(s, d_sums, update_after);
+        // (k <= 32, and 32 < k <= 256 without hot cells: the cube pass is one launch, and when a label pass follows, its tail rides on that one)
+        static const bool tail_rides = tools_env_int(KMG_TOOLS_ENV("KMG_TAIL_ON_LABELS"), 1) != 0;   // (tools build: 0 = a launch of its own)
+        const bool tail_on_labels = tail_rides && d_labels != nullptr && s->k <= 256u && cube_single_launch(s->k, hot_flag(t));
+        PROF_LAUNCH(s, KMG_K_CUBE, st, cube_pass(s, st, s->d_acc_int, 1u, true, true, defer_entries ? kCubeNoEntries : 0u,
+                                                 tail_on_labels ? nullptr : &tail));
+        t.entries_valid = !defer_entries;
+        if (tail_on_labels) {
+            t.tables_valid = true;
+            KMG_TRY(label_pass(s, d_rgba, n, d_labels, st, &tail, s->d_acc_int));
+            s->acc_int_dirty = false;
+            if (update_after) t.tables_valid = false;
+            return KMG_OK;
+        }
+        s->acc_int_dirty = false;
+    } else {
+        if (update_after) return fail(KMG_ERR_INVALID_ARGUMENT, "table_assign: update_after needs the final sums");
+        HIP_TRY(hipMemsetAsync(d_sums, 0, sizeof(int64_t) * 4ull * s->k * rows, st));
+        PROF_LAUNCH(s, KMG_K_CUBE, st, cube_pass(s, st, d_sums, rows, false, false));
+        t.entries_valid = true;
+    }
+    // (a share's pass leaves the tables current for ITS cells only: kmg_lloyd_labels refuses them, _labels_from_tables -- after
+    // the caller's all-gather -- takes them as they stand)
+    t.tables_valid = t.d_work_share == nullptr;
+    if (d_labels) KMG_TRY(label_pass(s, d_rgba, n, d_labels, st));
+    // (after an update the tables still describe the assignment just made, not the new centroids)
+    if (update_after) t.tables_valid = false;
+    return KMG_OK;
 }
 
 // One pass: labels and/or the partial sums of the current centroid table.  Uses the colour table
@@ -1046,11 +1080,9 @@ static int assign_pass(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, uint32_t
         s->last_rows = kMergeRows;
         return table_assign(s, d_rgba, n, d_labels, s->d_partials, kMergeRows, st);
     }
+    if (sums) KMG_TRY(check_weighted_count(s, n));
     // a label pass kmg_lloyd_iterate left on the side stream may still be writing d_labels
-    if (sums && s->weighted && n > kMaxWeightedPixels)
-        return fail(KMG_ERR_UNSUPPORTED, "weighted sums take at most 2^28 pixels (%llu given)", (unsigned long long)n);
-    int rc_;
-    if ((rc_ = side_flush(s, st)) != KMG_OK) return rc_;
+    KMG_TRY(side_flush(s, st));
     s->last_rows = assign_grid(n);
     PROF_LAUNCH(s, KMG_K_ASSIGN, st, launch_assign((const uint32_t *)d_rgba, n, s->d_cent, s->k, s->p->d_lut, d_labels,
                                                   sums ? s->d_partials : nullptr, st, s->weighted));
@@ -1065,8 +1097,7 @@ try {
     HIP_TRY(hipSetDevice(s->p->device));
     if (d_acc4 && table_bound(s, d_rgba, n))        // the cube pass adds straight into d_acc4: no reduction pass
         return table_assign(s, d_rgba, n, d_labels, d_acc4, 1u, S(stream));
-    int rc;
-    if ((rc = assign_pass(s, d_rgba, n, d_labels, d_acc4 != nullptr, S(stream))) != KMG_OK) return rc;
+    KMG_TRY(assign_pass(s, d_rgba, n, d_labels, d_acc4 != nullptr, S(stream)));
     if (d_acc4) PROF_LAUNCH(s, KMG_K_REDUCE, S(stream), launch_reduce_partials(s->d_partials, s->last_rows, s->k, d_acc4, S(stream)));
     return KMG_OK;
 }
@@ -1075,7 +1106,7 @@ KMG_ABI_CATCH
 extern "C" int kmg_lloyd_accumulate_into(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, int64_t *d_acc4, void *stream)
 try {
     if (!s || !d_rgba || !d_acc4 || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad accumulate_into arguments");
-    if (s->weighted) return fail(KMG_ERR_INVALID_ARGUMENT, "accumulate_into: the object's sums are weighted (kmg_lloyd_set_weighting): the colour table counts pixels");
+    KMG_TRY(check_unweighted(s, "accumulate_into"));
     HIP_TRY(hipSetDevice(s->p->device));
     if (!table_bound(s, d_rgba, n)) return fail(KMG_ERR_INVALID_ARGUMENT, "accumulate_into: the image is not bound (kmg_lloyd_bind_image / _prepare)");
     return table_assign(s, d_rgba, n, nullptr, d_acc4, 1u, S(stream), false, false, true);
@@ -1102,14 +1133,10 @@ extern "C" int kmg_lloyd_labels(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n,
 try {
     if (!s || !d_rgba || !d_labels || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad labels arguments");
     HIP_TRY(hipSetDevice(s->p->device));
-    int rc_;
-    if ((rc_ = side_flush(s, S(stream))) != KMG_OK) return rc_;      // both branches write d_labels
+    KMG_TRY(side_flush(s, S(stream)));                               // both branches write d_labels
     if (table_bound(s, d_rgba, n) && s->tab.tables_valid) {
-        if ((rc_ = ensure_entries(s, S(stream))) != KMG_OK) return rc_;
-        PROF_LAUNCH(s, KMG_K_LABELS, S(stream), launch_labels((const uint32_t *)d_rgba, n, s->tab.d_colour_labels,
-                                                              s->tab.d_sub, s->k, nullptr, d_labels, S(stream), s->reserve_cus,
-                                                              s->tab.n_hot ? s->tab.d_work + kCells + 1 : nullptr));
-        return KMG_OK;
+        KMG_TRY(ensure_entries(s, S(stream)));
+        return label_pass(s, d_rgba, n, d_labels, S(stream));
     }
     PROF_LAUNCH(s, KMG_K_ASSIGN, S(stream), launch_assign((const uint32_t *)d_rgba, n, s->d_cent, s->k, s->p->d_lut,
                                                           d_labels, nullptr, S(stream)));
@@ -1121,8 +1148,8 @@ KMG_ABI_CATCH
 extern "C" int kmg_lloyd_set_cell_share(kmg_lloyd *s, uint32_t part, uint32_t parts, void *stream)
 try {
     if (!s || parts == 0 || part >= parts) return fail(KMG_ERR_INVALID_ARGUMENT, "bad set_cell_share arguments");
-    if (s->weighted) return fail(KMG_ERR_INVALID_ARGUMENT, "set_cell_share: the object's sums are weighted (kmg_lloyd_set_weighting): the colour table counts pixels");
-    if (!s->tab.rgba || !s->tab.d_hist) return fail(KMG_ERR_INVALID_ARGUMENT, "set_cell_share: no bound image");
+    KMG_TRY(check_unweighted(s, "set_cell_share"));
+    KMG_TRY(check_bound(s, "set_cell_share"));
     HIP_TRY(hipSetDevice(s->p->device));
     ColourTable &t = s->tab;
     t.balance_work = nullptr;                                        // (the share buffer is reused: the same pointer, another list)
@@ -1136,15 +1163,11 @@ KMG_ABI_CATCH
 extern "C" int kmg_lloyd_labels_from_tables(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, uint32_t *d_labels, void *stream)
 try {
     if (!s || !d_rgba || !d_labels || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad labels_from_tables arguments");
-    if (!s->tab.rgba || !s->tab.d_hist) return fail(KMG_ERR_INVALID_ARGUMENT, "labels_from_tables: no bound image");
+    KMG_TRY(check_bound(s, "labels_from_tables"));
     HIP_TRY(hipSetDevice(s->p->device));
-    int rc_;
-    if ((rc_ = side_flush(s, S(stream))) != KMG_OK) return rc_;
-    if ((rc_ = ensure_entries(s, S(stream))) != KMG_OK) return rc_;
-    PROF_LAUNCH(s, KMG_K_LABELS, S(stream), launch_labels((const uint32_t *)d_rgba, n, s->tab.d_colour_labels, s->tab.d_sub, s->k,
-                                                          nullptr, d_labels, S(stream), s->reserve_cus,
-                                                          s->tab.n_hot ? s->tab.d_work + kCells + 1 : nullptr));
-    return KMG_OK;
+    KMG_TRY(side_flush(s, S(stream)));
+    KMG_TRY(ensure_entries(s, S(stream)));
+    return label_pass(s, d_rgba, n, d_labels, S(stream));
 }
 KMG_ABI_CATCH
 
@@ -1152,24 +1175,16 @@ extern "C" int kmg_lloyd_labels_from_tables_update(kmg_lloyd *s, const uint8_t *
                                                    void *stream)
 try {
     if (!s || !d_rgba || !d_labels || !d_acc4 || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad labels_from_tables_update arguments");
-    if (s->weighted) return fail(KMG_ERR_INVALID_ARGUMENT, "labels_from_tables_update: the object's sums are weighted (kmg_lloyd_set_weighting): the colour table counts pixels");
-    if (!s->tab.rgba || !s->tab.d_hist) return fail(KMG_ERR_INVALID_ARGUMENT, "labels_from_tables_update: no bound image");
+    KMG_TRY(check_unweighted(s, "labels_from_tables_update"));
+    KMG_TRY(check_bound(s, "labels_from_tables_update"));
     if (s->k > 256u) return fail(KMG_ERR_UNSUPPORTED, "labels_from_tables_update: k <= 256 (the label pass that carries a tail)");
     HIP_TRY(hipSetDevice(s->p->device));
-    int rc_;
-    if ((rc_ = side_flush(s, S(stream))) != KMG_OK) return rc_;
-    if ((rc_ = ensure_entries(s, S(stream))) != KMG_OK) return rc_;
+    KMG_TRY(side_flush(s, S(stream)));
+    KMG_TRY(ensure_entries(s, S(stream)));
     // the label pass's last workgroup copies the sums to the object's own k x 4 buffer, updates the centroids from them
     // (choose_centroid.wgsl:180-206) and clears d_acc4 (kmg_table.h CubeTail)
-    CubeTail tail;
-    tail.acc_out = s->d_acc;
-    tail.do_update = 1;
-    tail.convergence = s->p->opt.convergence;
-    tail.cent = s->d_cent;
-    tail.n_converged = s->d_nconv;
-    PROF_LAUNCH(s, KMG_K_LABELS, S(stream), launch_labels((const uint32_t *)d_rgba, n, s->tab.d_colour_labels, s->tab.d_sub, s->k,
-                                                          nullptr, d_labels, S(stream), s->reserve_cus,
-                                                          s->tab.n_hot ? s->tab.d_work + kCells + 1 : nullptr, &tail, d_acc4));
+    const CubeTail tail = make_tail(s, s->d_acc, true);
+    KMG_TRY(label_pass(s, d_rgba, n, d_labels, S(stream), &tail, d_acc4));
     s->tab.tables_valid = false;                                 // (the tables describe the assignment just made, not the new centroids)
     return KMG_OK;
 }
@@ -1177,7 +1192,7 @@ KMG_ABI_CATCH
 
 extern "C" int kmg_lloyd_histogram_buffer(kmg_lloyd *s, void **hist, uint64_t *bytes)
 try {
-    if (!s || !s->tab.d_hist || !s->tab.rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "histogram_buffer: no bound image");
+    KMG_TRY(check_bound(s, "histogram_buffer"));                     // (a NULL object, too, is answered with "no bound image")
     if (hist) *hist = s->tab.d_hist;
     if (bytes) *bytes = sizeof(uint32_t) << 24;
     return KMG_OK;
@@ -1189,8 +1204,7 @@ try {
     if (!s || !s->tab.d_hist || !s->tab.rgba || n_pixels == 0 || n_pixels > 0xFFFFFFFFull)
         return fail(KMG_ERR_INVALID_ARGUMENT, "bad rebuild_from_histogram arguments");
     HIP_TRY(hipSetDevice(s->p->device));
-    int rc_;
-    if ((rc_ = side_flush(s, S(stream))) != KMG_OK) return rc_;
+    KMG_TRY(side_flush(s, S(stream)));
     s->tab.tables_valid = false;
     s->tab.tie_valid = false;                                        // the init's tie keys belong to the band's own histogram
     return tables_from_histogram(s, n_pixels, S(stream));
@@ -1200,7 +1214,7 @@ KMG_ABI_CATCH
 extern "C" int kmg_lloyd_table_buffers(kmg_lloyd *s, void **colour_labels, uint64_t *colour_label_bytes, void **entries,
                                        uint64_t *entry_bytes)
 try {
-    if (!s || !s->tab.d_hist) return fail(KMG_ERR_INVALID_ARGUMENT, "table_buffers: no bound image");
+    KMG_TRY(check_bound(s, "table_buffers", false));
     if (colour_labels) *colour_labels = s->tab.d_colour_labels;
     if (colour_label_bytes) *colour_label_bytes = (uint64_t)(s->k <= 256 ? 1 : 2) << 24;
     if (entries) *entries = s->tab.d_sub;
@@ -1219,19 +1233,7 @@ try {
 }
 KMG_ABI_CATCH
 
-static void drop_events(kmg_lloyd *s)
-{
-    for (ProfEvent &e : s->events) { s->pool.push_back(e.e0); s->pool.push_back(e.e1); }
-    s->events.clear();
-}
-
-static void destroy_events(kmg_lloyd *s)
-{
-    drop_events(s);
-    for (hipEvent_t e : s->pool) (void)hipEventDestroy(e);
-    s->pool.clear();
-}
-
+// ---- profiling, update, loop ----
 extern "C" const char *kmg_kernel_name(int id)
 {
     static const char *names[KMG_K_COUNT] = {"k_assign", "k_reduce_partials", "k_update", "k_cell_candidates", "k_cube", "k_labels"};
@@ -1288,9 +1290,8 @@ static int assign_update_impl(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, u
     if (!s || !d_rgba || n == 0 || !d_acc4) return fail(KMG_ERR_INVALID_ARGUMENT, "bad assign_update arguments");
     HIP_TRY(hipSetDevice(s->p->device));
     if (table_bound(s, d_rgba, n)) return table_assign(s, d_rgba, n, d_labels, d_acc4, 1u, S(stream), do_update != 0, defer_entries);
-    int rc;
     // (a small slab of partial sums: reduction and update are one launch -- kmg_kernels.h reduce_update_fits)
-    if ((rc = assign_pass(s, d_rgba, n, d_labels, true, S(stream))) != KMG_OK) return rc;
+    KMG_TRY(assign_pass(s, d_rgba, n, d_labels, true, S(stream)));
     if (reduce_update_fits(s->last_rows, s->k)) {
         if (do_update) s->tab.tables_valid = false;
         PROF_LAUNCH(s, KMG_K_REDUCE, S(stream), launch_reduce_update(s->d_partials, s->last_rows, s->k, d_acc4, do_update, s->p->opt.convergence,
@@ -1319,15 +1320,14 @@ extern "C" int kmg_lloyd_iterate(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n
 try {
     if (!s || !d_rgba || n == 0 || !d_acc4) return fail(KMG_ERR_INVALID_ARGUMENT, "bad iterate arguments");
     HIP_TRY(hipSetDevice(s->p->device));
-    int rc;
     if (!table_bound(s, d_rgba, n) || !d_labels) {
         // per-pixel scan (labels and sums come out of one kernel) or no label map wanted: nothing to overlap
-        if (update_first && (rc = kmg_lloyd_update(s, d_acc4, stream)) != KMG_OK) return rc;
+        if (update_first) KMG_TRY(kmg_lloyd_update(s, d_acc4, stream));
         return kmg_lloyd_assign_accumulate(s, d_rgba, n, d_labels, d_acc4, stream);
     }
     hipStream_t st = S(stream);
     ColourTable &t = s->tab;
-    if (t.d_work_share) return fail(KMG_ERR_INVALID_ARGUMENT, "iterate: a cell share is set (kmg_lloyd_set_cell_share)");
+    KMG_TRY(check_no_share(s, "iterate"));
     if (!s->side) {
         int least = 0, greatest = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -1361,13 +1361,11 @@ try {
         if (update_first)
             PROF_LAUNCH(s, KMG_K_UPDATE, st, launch_update(d_acc4, s->k, s->p->opt.convergence, s->d_cent, s->d_nconv, st));
         HIP_TRY(hipMemsetAsync(d_acc4, 0, sizeof(int64_t) * 4ull * s->k, st));
-        const CubeBalance bal = next_balance(t, t.d_work);
-        PROF_LAUNCH(s, KMG_K_CUBE, st, launch_cube(t.d_hist, t.d_agg, t.d_sub_agg, t.d_occ, t.d_work, s->p->d_bounds, s->p->d_sub_bounds,
-                                                   s->d_cent, s->k, s->p->d_lab_table, t.d_masks, t.d_cell_work, t.d_colour_labels, t.d_sub,
-                                                   d_acc4, 1u, t.n_hot ? kCubeHot : 0u, nullptr, st, nullptr, affine_for(s->p, s->k, st), &bal));
+        PROF_LAUNCH(s, KMG_K_CUBE, st, cube_pass(s, st, d_acc4, 1u, false, true));
         return KMG_OK;
     };
-    if ((rc = issue()) != KMG_OK) {
+    const int rc = issue();
+    if (rc != KMG_OK) {
         std::swap(t.d_colour_labels, t.d_colour_labels_alt);
         std::swap(t.d_sub, t.d_sub_alt);
         s->set ^= 1;
@@ -1377,8 +1375,7 @@ try {
     t.entries_valid = true;
     HIP_TRY(hipEventRecord(s->ev_cube, st));
     HIP_TRY(hipStreamWaitEvent(s->side, s->ev_cube, 0));
-    PROF_LAUNCH(s, KMG_K_LABELS, s->side, launch_labels((const uint32_t *)d_rgba, n, t.d_colour_labels, t.d_sub, s->k, nullptr,
-                                                        d_labels, s->side, s->reserve_cus, t.n_hot ? t.d_work + kCells + 1 : nullptr));
+    KMG_TRY(label_pass(s, d_rgba, n, d_labels, s->side));
     HIP_TRY(hipEventRecord(s->ev_lab[s->set], s->side));
     s->lab_pending[s->set] = true;
     return KMG_OK;
@@ -1397,14 +1394,10 @@ extern "C" int kmg_lloyd_converged_count(kmg_lloyd *s, uint32_t *count, void *st
 try {
     if (!s || !count) return fail(KMG_ERR_INVALID_ARGUMENT, "bad converged_count arguments");
     HIP_TRY(hipSetDevice(s->p->device));
-    if (s->h_slot) {
-        HIP_TRY(hipMemcpyAsync(s->h_slot, s->d_nconv, sizeof(uint32_t), hipMemcpyDeviceToHost, S(stream)));
-        HIP_TRY(hipStreamSynchronize(S(stream)));
-        *count = *static_cast<const volatile uint32_t *>(s->h_slot);
-        return KMG_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(count, s->d_nconv, sizeof(uint32_t), hipMemcpyDeviceToHost, S(stream)));
+    uint32_t *h = s->h_slot ? static_cast<uint32_t *>(s->h_slot) : count;   // (page-locked where the object has a slot)
+    HIP_TRY(hipMemcpyAsync(h, s->d_nconv, sizeof(uint32_t), hipMemcpyDeviceToHost, S(stream)));
     HIP_TRY(hipStreamSynchronize(S(stream)));
+    *count = *static_cast<const volatile uint32_t *>(h);
     return KMG_OK;
 }
 KMG_ABI_CATCH
@@ -1413,12 +1406,9 @@ extern "C" int kmg_lloyd_run(kmg_lloyd *s, const uint8_t *d_rgba, uint64_t n, ui
                              uint32_t *iterations, void *stream)
 try {
     if (!s || !d_rgba || n == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad lloyd_run arguments");
-    if (s->weighted && n > kMaxWeightedPixels)
-        return fail(KMG_ERR_UNSUPPORTED, "weighted sums take at most 2^28 pixels (%llu given)", (unsigned long long)n);
-    if (s->tab.d_work_share && table_bound(s, d_rgba, n))
-        return fail(KMG_ERR_INVALID_ARGUMENT, "lloyd_run: a cell share is set (kmg_lloyd_set_cell_share): the loop would update from one share's sums");
+    KMG_TRY(check_weighted_count(s, n));
+    if (table_bound(s, d_rgba, n)) KMG_TRY(check_no_share(s, "lloyd_run", ": the loop would update from one share's sums"));
     const kmg_options &o = s->p->opt;
-    int rc;
     // large problems iterate over the image's colour table instead of its pixels (same results);
     // the loop itself only needs the sums, so with the table the per-pixel label map is written
     // once, after the last iteration (the per-pixel scan writes it in the same pass for free)
@@ -1427,8 +1417,7 @@ try {
     // binding over (prepare keeps it) -- and dropped before returning: a later run on the same buffer with
     // new pixels must not meet the histogram of the old ones.
     const bool callers = table_bound(s, d_rgba, n) && s->tab.bound_by_caller;
-    if (!callers)
-        if ((rc = prepare_impl(s, d_rgba, n, 0, nullptr, stream, false)) != KMG_OK) return rc;
+    if (!callers) KMG_TRY(prepare_impl(s, d_rgba, n, 0, nullptr, stream, false));
     const bool table = table_bound(s, d_rgba, n);
     uint32_t *loop_labels = table ? nullptr : d_labels;
     // operations.rs:75-83 initial assignment (fused with the sums the first update needs), then modules.rs:769-800:
@@ -1437,11 +1426,24 @@ try {
     // in between -- i.e. unless that pass is the one a convergence check follows: after the last update nothing but the
     // re-assignment may happen.
     auto checked = [&](uint32_t it) { return it > 0 && it % o.check_period == 0; };
+    // modules.rs:802-831: the check after iteration `it`, where one is due; stop = every centroid has converged
+    auto check = [&](uint32_t it, bool &stop) -> int {
+        stop = false;
+        if (!checked(it)) return KMG_OK;                             // :802
+        uint32_t conv = 0;
+        KMG_TRY(kmg_lloyd_converged_count(s, &conv, stream));
+        if (conv >= s->k) {                                          // :826-831
+            if (log_debug()) fprintf(stderr, "[kmeans_hip] We have convergence, checked at iteration %u\n", it);
+            stop = true;
+        }
+        return KMG_OK;
+    };
+    bool stop = false;
     if (!table && assign_loop_fits(n) && assign_loop_scratch_bytes(s->k) <= sizeof(int64_t) * 4ull * s->k * 2048ull) {
         // Small image (the reference's default working size): one launch per iteration (kmg_kernels.h launch_assign_loop).
         // The partial-sum slab, unused by this loop, holds its three sum buffers and the second centroid buffer.
         hipStream_t st = S(stream);
-        if ((rc = side_flush(s, st)) != KMG_OK) return rc;
+        KMG_TRY(side_flush(s, st));
         int64_t *acc3[3] = {s->d_partials, s->d_partials + 4ull * s->k, s->d_partials + 8ull * s->k};
         Centroid *cur = s->d_cent, *alt = reinterpret_cast<Centroid *>(s->d_partials + 12ull * s->k);
         HIP_TRY(hipMemsetAsync(s->d_partials, 0, sizeof(int64_t) * 12ull * s->k, st));
@@ -1456,14 +1458,8 @@ try {
             PROF_LAUNCH(s, KMG_K_ASSIGN, st, launch_assign_loop(px, n, cur, alt, s->k, s->p->d_lut, d_labels, acc3[(l + 2u) % 3u], acc3[l % 3u],
                                                               acc3[(l + 1u) % 3u], 1, o.convergence, s->d_nconv, st, s->weighted));
             std::swap(cur, alt);
-            if (checked(it)) {                                       // :802
-                uint32_t conv = 0;
-                if ((rc = kmg_lloyd_converged_count(s, &conv, stream)) != KMG_OK) return rc;
-                if (conv >= s->k) {                                  // :826-831
-                    if (log_debug()) fprintf(stderr, "[kmeans_hip] We have convergence, checked at iteration %u\n", it);
-                    break;
-                }
-            }
+            KMG_TRY(check(it, stop));
+            if (stop) break;
         }
         if (cur != s->d_cent) HIP_TRY(hipMemcpyAsync(s->d_cent, cur, sizeof(Centroid) * s->k, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -1479,31 +1475,23 @@ try {
         // final label pass -- 19 us per iteration at k = 256)
         return assign_update_impl(s, d_rgba, n, loop_labels, s->d_acc, fuse ? 1 : 0, stream, true);
     };
-    if ((rc = pass(-1)) != KMG_OK) return rc;
+    KMG_TRY(pass(-1));
     uint32_t it = 0;
     for (it = 0; it < o.max_iterations; ++it) {                       // modules.rs:769
         // the update of this iteration: already done by the previous pass unless that pass was followed by a check
         const bool fused_before = !(it >= 1 && checked(it - 1));
-        if (!fused_before && (rc = kmg_lloyd_update(s, s->d_acc, stream)) != KMG_OK) return rc;   // :773-788
-        if ((rc = pass((long)it)) != KMG_OK) return rc;                                            // :793-800
-        if (checked(it)) {                                           // :802
-            uint32_t conv = 0;
-            if ((rc = kmg_lloyd_converged_count(s, &conv, stream)) != KMG_OK) return rc;
-            if (conv >= s->k) {                                      // :826-831
-                if (log_debug()) fprintf(stderr, "[kmeans_hip] We have convergence, checked at iteration %u\n", it);
-                break;
-            }
-        }
+        if (!fused_before) KMG_TRY(kmg_lloyd_update(s, s->d_acc, stream));   // :773-788
+        KMG_TRY(pass((long)it));                                             // :793-800
+        KMG_TRY(check(it, stop));
+        if (stop) break;
     }
-    if (table && d_labels && (rc = ensure_entries(s, S(stream))) != KMG_OK) return rc;
-    if (table && d_labels)   // the label tables of the last pass belong to the final centroids
-        PROF_LAUNCH(s, KMG_K_LABELS, S(stream), launch_labels((const uint32_t *)d_rgba, n, s->tab.d_colour_labels,
-                                                              s->tab.d_sub, s->k, nullptr, d_labels, S(stream), s->reserve_cus,
-                                                              s->tab.n_hot ? s->tab.d_work + kCells + 1 : nullptr));
+    if (table && d_labels) {   // the label tables of the last pass belong to the final centroids
+        KMG_TRY(ensure_entries(s, S(stream)));
+        KMG_TRY(label_pass(s, d_rgba, n, d_labels, S(stream)));
+    }
     HIP_TRY(hipStreamSynchronize(S(stream)));
     if (table && !callers) { s->tab.rgba = nullptr; s->tab.tables_valid = false; }
     if (iterations) *iterations = it < o.max_iterations ? it : o.max_iterations - 1;
     return KMG_OK;
 }
 KMG_ABI_CATCH
-

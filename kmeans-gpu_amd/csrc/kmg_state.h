@@ -176,42 +176,42 @@ struct ColourTable {
 };
 
 struct kmg_lloyd {
-    kmg_processor *p;
-    uint32_t k;
-    Centroid *d_cent;            // k
-    int64_t *d_partials;         // 2048 x k x 4: partial sums of the per-pixel scan; between passes also scratch of whoever runs --
-                                 // the key slots of a per-pixel initialisation, the sum / centroid rotation of the small-image loop
-    int64_t *d_acc;              // k x 4 (used by kmg_lloyd_run)
-    int64_t *d_acc_int;          // k x 4: where the cube pass accumulates; ZERO between passes (its last launch hands the sums
-                                 // over and clears it, kmg_table.h CubeTail) -- no memset launch per pass
-    bool acc_int_dirty;          // a pass was interrupted: clear d_acc_int before the next one
-    uint32_t *d_nconv;           // kStateWords: the convergence count, the sparsity probe's three words, n_fixed (kmg_device.h)
-    void *h_slot = nullptr;      // kHostSlotBytes page-locked bytes for small read-backs (kmg_processor::h_page), or NULL
-    unsigned long long *d_key;   // 1 (init arg-max of a sharded image)
-    float *d_dist;               // init distance map, grown on demand (a block of its own)
-    uint64_t dist_cap;
-    size_t dist_blk_cap;
-    void *ws;                    // the block d_cent .. d_key are carved from (kmg_processor::idle_arenas)
-    size_t ws_cap;
-    uint32_t last_rows;          // rows of d_partials written by the last assign pass
-    bool init_colours;           // the running sharded init (kmg_lloyd_init_step) walks colours, not pixels
-    uint32_t reserve_cus = 0;    // CUs the label pass leaves free (kmg_lloyd_reserve_cus)
-    bool weighted = false;       // kmg_lloyd_set_weighting(KMG_WEIGHT_ALPHA): every sum of this object weighs a pixel by its alpha byte;
-                                 // such an object never takes the colour-table route (its histogram counts pixels)
-    uint32_t n_fixed = 0;        // host copy of d_nconv[kFixedWord]: centroids 0 .. n_fixed - 1 are left alone by every update and
-                                 // count as converged (kmg_lloyd_set_fixed)
-    bool pooled;                 // workspace came from the stream-ordered pool of `pool_stream` (internal per-call objects)
-    hipStream_t pool_stream;
+    kmg_processor *p = nullptr;
+    uint32_t k = 0;
+    Centroid *d_cent = nullptr;             // k
+    int64_t *d_partials = nullptr;          // 2048 x k x 4: partial sums of the per-pixel scan; between passes also scratch of whoever runs --
+                                            // the key slots of a per-pixel initialisation, the sum / centroid rotation of the small-image loop
+    int64_t *d_acc = nullptr;               // k x 4 (used by kmg_lloyd_run)
+    int64_t *d_acc_int = nullptr;           // k x 4: where the cube pass accumulates; ZERO between passes (its last launch hands the sums
+                                            // over and clears it, kmg_table.h CubeTail) -- no memset launch per pass
+    bool acc_int_dirty = true;              // no pass has run yet, or one was interrupted: clear d_acc_int (in stream order) before the next one
+    uint32_t *d_nconv = nullptr;            // kStateWords: the convergence count, the sparsity probe's three words, n_fixed (kmg_device.h)
+    void *h_slot = nullptr;                 // kHostSlotBytes page-locked bytes for small read-backs (kmg_processor::h_page), or NULL
+    unsigned long long *d_key = nullptr;    // 1 (init arg-max of a sharded image)
+    float *d_dist = nullptr;                // init distance map, grown on demand (a block of its own)
+    uint64_t dist_cap = 0;
+    size_t dist_blk_cap = 0;
+    void *ws = nullptr;                     // the block d_cent .. d_key are carved from (kmg_processor::idle_arenas)
+    size_t ws_cap = 0;
+    uint32_t last_rows = 0;                 // rows of d_partials written by the last assign pass
+    bool init_colours = false;              // the running sharded init (kmg_lloyd_init_step) walks colours, not pixels
+    uint32_t reserve_cus = 0;               // CUs the label pass leaves free (kmg_lloyd_reserve_cus)
+    bool weighted = false;                  // kmg_lloyd_set_weighting(KMG_WEIGHT_ALPHA): every sum of this object weighs a pixel by its alpha byte;
+                                            // such an object never takes the colour-table route (its histogram counts pixels)
+    uint32_t n_fixed = 0;                   // host copy of d_nconv[kFixedWord]: centroids 0 .. n_fixed - 1 are left alone by every update and
+                                            // count as converged (kmg_lloyd_set_fixed)
+    bool pooled = false;                    // workspace came from the stream-ordered pool of `pool_stream` (internal per-call objects)
+    hipStream_t pool_stream = nullptr;
     ColourTable tab;
     // kmg_lloyd_iterate: label passes run on a stream of their own, beside the next iteration's cube pass
-    hipStream_t side;            // high-priority stream of the label passes (created on first use)
-    hipEvent_t ev_cube;          // cube pass of the current iteration done (main stream -> side stream)
-    hipEvent_t ev_lab[2];        // label pass reading table set i done (side stream -> main stream)
-    bool lab_pending[2];
-    int set;                     // event slot of the table set written last
-    uint32_t prof;               // per-launch HIP-event timing: bit i = time kernel id i (kmg_lloyd_profile)
+    hipStream_t side = nullptr;             // high-priority stream of the label passes (created on first use)
+    hipEvent_t ev_cube = nullptr;           // cube pass of the current iteration done (main stream -> side stream)
+    hipEvent_t ev_lab[2] = {nullptr, nullptr}; // label pass reading table set i done (side stream -> main stream)
+    bool lab_pending[2] = {false, false};
+    int set = 0;                            // event slot of the table set written last
+    uint32_t prof = 0;                      // per-launch HIP-event timing: bit i = time kernel id i (kmg_lloyd_profile)
     std::vector<ProfEvent> events;
-    std::vector<hipEvent_t> pool; // recycled timing events
+    std::vector<hipEvent_t> pool;           // recycled timing events
 };
 
 static inline hipStream_t S(void *s) { return (hipStream_t)s; }
