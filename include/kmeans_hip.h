@@ -277,6 +277,65 @@ KMG_API int kmg_find_indexed(kmg_processor *p, const uint8_t *rgba, uint32_t wid
 KMG_API int kmg_reduce_indexed(kmg_processor *p, const uint8_t *rgba, uint32_t width, uint32_t height, uint32_t color_count,
                                int algo, int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out_index);
 
+/* ---- batches: many small images per launch on one device ---------------------------------
+ * No counterpart in the reference, which quantises image after image.  The default call works on an image shrunk to at most
+ * 256 x 256: a few hundred workgroups on 256 CUs and a chain of launches whose length does not depend on the image.  A batch runs
+ * that chain ONCE for all its images: launch j of the initialisation is pass j of every image, a launch of the loop is one Lloyd
+ * iteration of every image that is still running (kmg_batch.hip).
+ *
+ * Equivalence.  kmg_palette_batch / kmg_reduce_batch write for image i exactly the bytes (and out_counts[i]) that kmg_palette /
+ * kmg_reduce of image i alone write on the same processor; kmg_dev_palette_batch gives the centroids and the iteration count that
+ * kmg_lloyd_init_centroids + kmg_lloyd_run + kmg_lloyd_get_centroids give for image i.  Images may differ in size, an image may
+ * appear twice, and neither the order of the batch nor max_resident_bytes changes any image's result.  An image stops where
+ * kmg_lloyd_run stops it -- at the check after iteration `it` (it > 0, it % check_period == 0) with every centroid converged, or at
+ * max_iterations; later launches leave it alone.  kmg_options.strategy changes nothing: the batch is the per-pixel route.
+ *
+ * Per-image steps.  The shrink and alpha mode's compaction are the existing ones (kmg_dev_resize, kmg_dev_alpha_compact), enqueued
+ * per image; the kept-pixel counts of a sub-batch come back in one copy.  A working image of 2^19 pixels or more (shrink off or
+ * shrink_max_dim large) takes the per-image path inside the call and counts in `fallback`.  KMG_ALGO_OCTREE runs the host
+ * algorithm per image (the report stays 0 apart from sub_batches).  kmg_reduce_batch's output step is the per-image output pass at
+ * full size with that image's centroids; the sources stay on the device between their shrink and their output pass.
+ *
+ * max_resident_bytes (0 = 1 GiB) bounds what a call keeps on the device at once: the batch is cut into consecutive sub-batches
+ * whose images' resident bytes fit (an image that does not fit alone forms a sub-batch of its own).  An image counts with
+ * 4 * width * height bytes for its source -- kmg_palette_batch: only where the image is not shrunk, a shrunk source is released as
+ * soon as its shrink is enqueued -- plus 4 bytes per pixel of its shrunk copy where it has one, plus the same again in alpha mode
+ * for the compacted copy.  (The batched state itself, ~ 12 bytes per working pixel + 128 k bytes per image, rides on top.)
+ *
+ * Refusals, KMG_ERR_INVALID_ARGUMENT, checked for the whole batch before anything is uploaded, in this order: a NULL processor;
+ * n_images == 0; a NULL array; then per image in order a NULL entry or a zero dimension; color_count == 0; an algorithm or mode out
+ * of range; (color_count > KMG_MAX_K with k-means: KMG_ERR_UNSUPPORTED;) fixed colours set on the processor; alpha weighting on --
+ * there is no seeded or weighted batched path yet, the group calls refuse both for the same reason.  Alpha mode: an image that
+ * keeps no pixel refuses the call, the message names its index; this is found on the device after the shrinks, still before
+ * any output is written (with several sub-batches the call shrinks everything once more up front to find it).  Any other failure
+ * returns the first error; which outputs were written by then is unspecified.
+ *
+ * report (may be NULL): what the call did.                                                                                         */
+typedef struct kmg_batch_report {   /* 16 bytes, no padding */
+    uint32_t launches;      /* kernel launches of the batched initialisation + loop (not shrink, compaction, the final gather, output) */
+    uint32_t iterations;    /* largest iteration count of any image                                                                      */
+    uint32_t sub_batches;   /* how many pieces max_resident_bytes cut the batch into                                                     */
+    uint32_t fallback;      /* images that took the per-image path (working image >= 2^19 pixels)                                        */
+} kmg_batch_report;
+
+/* device building block: working images already on the device (d_rgba: a HOST array of n_images device pointers), centroids in
+ * index order as (L, a, b, 1).  centroids4: host, n_images * k * 4 floats; iterations: host, n_images, may be NULL.  The
+ * initialisation takes k launches, the loop 1 + its iterations, whatever n_images is (up to 2^20 tiles of 256 pixels in all; a
+ * larger batch runs as several such chains, one after the other).  The state of the batch is carved from the
+ * processor's idle blocks (no hipMalloc on a warm processor).  Ignores the processor's alpha cutoff, fixed colours and weighting,
+ * as the kmg_lloyd_* calls do.  Synchronises `stream`.                                                                          */
+KMG_API int kmg_dev_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths,
+                                  const uint32_t *heights, uint32_t k, float *centroids4, uint32_t *iterations,
+                                  kmg_batch_report *report, void *stream);
+/* host buffers, as kmg_palette / kmg_reduce per image: rgba, widths, heights, out_rgba (and out_counts) are arrays of n_images
+ * entries; out_rgba[i] has room for color_count * 4 bytes (palette) or widths[i] * heights[i] * 4 bytes (reduce)                */
+KMG_API int kmg_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths,
+                              const uint32_t *heights, uint32_t color_count, int algo, uint64_t max_resident_bytes,
+                              uint8_t *const *out_rgba, uint32_t *out_counts, kmg_batch_report *report);
+KMG_API int kmg_reduce_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths,
+                             const uint32_t *heights, uint32_t color_count, int algo, int mode, uint64_t max_resident_bytes,
+                             uint8_t *const *out_rgba, kmg_batch_report *report);
+
 /* ---- host-side colour helpers the reference takes from the `palette` crate -------------
  * CentroidsBuffer::fixed_centroids (core/src/structures.rs:523-553): sRGB8 -> Lab (L,a,b,1)  */
 KMG_API int kmg_palette_to_centroids(const uint8_t *palette_rgba, uint32_t n_colors, float *centroids4);

@@ -467,6 +467,226 @@ try {
 KMG_ABI_CATCH
 
 // ---------------------------------------------------------------------------------------------
+// batches (include/kmeans_hip.h at kmg_batch_report; the kernels and kmg_dev_palette_batch: kmg_batch.hip)
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// The smallest sub-batch that goes through the batched kernels; a smaller one -- a single image -- runs the per-image palette step
+// inside the call (the same results).  The batched initialisation is the single pick, k launches, where the per-image route picks
+// several centroids per launch from k = 32 on (~ 0.3 k + 18 launches): one image alone would pay for that, two images already
+// do not -- the `kernels` rows of profiles/r09_batch_time.txt (tools/batch_probe.py) at N = 1, i.e. two images: 0.89, 0.61 and
+// 0.77 of the per-image calls at k = 8, 64 and 256.
+constexpr uint32_t kBatchMinImages = 2;
+
+// One image of a sub-batch on the device: its source, its shrunk copy, alpha mode's compacted copy, and which of them is the
+// working image (what working_image makes, but only enqueued: the kept-pixel counts of a sub-batch are read back together).
+struct BatchStage {
+    StreamBuf src, small, kept;
+    const uint8_t *work = nullptr;
+    uint32_t sw = 0, sh = 0;
+};
+
+// what image (w, h) keeps on the device while its sub-batch runs (include/kmeans_hip.h at max_resident_bytes)
+uint64_t batch_resident_bytes(const kmg_processor *p, uint32_t w, uint32_t h, uint32_t alpha_cutoff, bool keep_source)
+{
+    uint32_t sw = w, sh = h;
+    const uint32_t m = p->opt.shrink_max_dim;
+    const bool shrunk = m && (w > m || h > m);
+    if (shrunk) kmg_resized_dims(w, h, m, &sw, &sh);
+    uint64_t bytes = shrunk ? 4ull * sw * sh : 0ull;
+    if (keep_source || !shrunk) bytes += 4ull * w * h;
+    if (alpha_cutoff) bytes += 4ull * sw * sh;
+    return bytes;
+}
+
+// Uploads images [a, b) and makes their working images; one synchronisation for the kept-pixel counts of all of them.
+// keep_source = false: a source that was shrunk is released as soon as its shrink is enqueued.
+int batch_stage(kmg_processor *p, const uint8_t *const *rgba, const uint32_t *widths, const uint32_t *heights, uint32_t a, uint32_t b,
+                uint32_t alpha_cutoff, bool keep_source, hipStream_t st, BatchStage *stage)
+{
+    const uint32_t count = b - a, m = p->opt.shrink_max_dim;
+    StreamBuf counts;
+    if (alpha_cutoff) HIP_TRY(counts.alloc(p, sizeof(uint64_t) * count, st));
+    for (uint32_t i = a; i < b; ++i) {
+        BatchStage &s = stage[i - a];
+        const uint32_t w = widths[i], h = heights[i];
+        KMG_TRY(upload_image(p, rgba[i], w, h, st, s.src));
+        s.work = (const uint8_t *)s.src.ptr;
+        s.sw = w;
+        s.sh = h;
+        if (m && (w > m || h > m)) {                                   // structures.rs:67-74
+            kmg_resized_dims(w, h, m, &s.sw, &s.sh);
+            HIP_TRY(s.small.alloc(p, (size_t)s.sw * s.sh * 4, st));
+            KMG_TRY(kmg_dev_resize(p, s.work, w, h, s.sw, s.sh, (uint8_t *)s.small.ptr, st));
+            s.work = (const uint8_t *)s.small.ptr;
+            if (!keep_source) {
+                HIP_TRY(hipFreeAsync(s.src.ptr, st));
+                s.src.ptr = nullptr;
+            }
+        }
+        if (alpha_cutoff) {
+            const uint64_t n = (uint64_t)s.sw * s.sh;
+            HIP_TRY(s.kept.alloc(p, (size_t)n * 4, st));
+            KMG_TRY(kmg_dev_alpha_compact(p, s.work, n, alpha_cutoff, (uint8_t *)s.kept.ptr, (uint64_t *)counts.ptr + (i - a), st));
+        }
+    }
+    if (!alpha_cutoff) return KMG_OK;
+    std::vector<uint64_t> n_kept(count);
+    HIP_TRY(hipMemcpyAsync(n_kept.data(), counts.ptr, sizeof(uint64_t) * count, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t i = a; i < b; ++i) {
+        BatchStage &s = stage[i - a];
+        if (n_kept[i - a] == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: no pixel reaches alpha_cutoff = %u", i, alpha_cutoff);
+        if (n_kept[i - a] < (uint64_t)s.sw * s.sh) {
+            s.work = (const uint8_t *)s.kept.ptr;
+            s.sw = (uint32_t)n_kept[i - a];
+            s.sh = 1;
+        }
+    }
+    return KMG_OK;
+}
+
+// kmg_palette_batch (reduce = false) / kmg_reduce_batch
+int batch_call(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths, const uint32_t *heights,
+               uint32_t color_count, int algo, int mode, bool reduce, uint64_t max_resident_bytes, uint8_t *const *out_rgba,
+               uint32_t *out_counts, kmg_batch_report *report)
+{
+    // the refusals, for the whole batch, before any device work (the order is part of the contract: include/kmeans_hip.h)
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
+    if (n_images == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "the batch is empty");
+    if (!rgba || !widths || !heights || !out_rgba || (!reduce && !out_counts)) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch array is NULL");
+    for (uint32_t i = 0; i < n_images; ++i) {
+        if (!rgba[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: image pointer is NULL", i);
+        if (!out_rgba[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: output pointer is NULL", i);
+        if (!widths[i] || !heights[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u has zero width or height", i);
+        KMG_TRY(check_pixel_count((uint64_t)widths[i] * heights[i]));
+    }
+    KMG_TRY(check_k_nonzero(color_count));
+    KMG_TRY(check_algo(algo));
+    if (reduce) KMG_TRY(check_mode(mode));
+    if (algo == KMG_ALGO_KMEANS) KMG_TRY(check_k_limit(color_count));
+    CallStart c;
+    c.snapshot(p);
+    if (const uint32_t f = fixed_count(c.fixed))
+        return fail(KMG_ERR_INVALID_ARGUMENT, "a batch has no fixed colours (%u are set on the processor)", f);
+    if (c.weighting) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch has no alpha weighting (it is on for the processor)");
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(c.sg.acquire(p));
+    hipStream_t st = c.sg.st;
+    const uint32_t cutoff = c.alpha_cutoff;
+    const bool octree = algo == KMG_ALGO_OCTREE;
+
+    // consecutive sub-batches whose resident bytes fit the bound: images [cuts[s], cuts[s + 1])
+    const uint64_t bound = max_resident_bytes ? max_resident_bytes : (1ull << 30);
+    std::vector<uint32_t> cuts(1, 0u);
+    uint64_t held = 0;
+    for (uint32_t i = 0; i < n_images; ++i) {
+        const uint64_t bytes = octree ? 4ull * widths[i] * heights[i] : batch_resident_bytes(p, widths[i], heights[i], cutoff, reduce);
+        if (i > cuts.back() && held + bytes > bound) { cuts.push_back(i); held = 0; }
+        held += bytes;
+    }
+    cuts.push_back(n_images);
+    const size_t n_sub = cuts.size() - 1;
+    kmg_batch_report rep = {0u, 0u, (uint32_t)n_sub, 0u};
+
+    std::vector<std::vector<std::array<uint8_t, 4>>> colors(octree ? n_images : 0);
+    auto octree_of = [&](uint32_t i, const uint8_t *d_src) -> int {   // lib.rs:288-331
+        const int rc = octree_palette_of(p, d_src, widths[i], heights[i], color_count, cutoff, st, colors[i]);
+        if (rc == KMG_ERR_INVALID_ARGUMENT && cutoff) return fail(rc, "image %u: no pixel reaches alpha_cutoff = %u", i, cutoff);
+        return rc;
+    };
+    // Alpha mode, several sub-batches: an image that keeps no pixel has to refuse the call before the first sub-batch writes its
+    // outputs -- everything is uploaded and shrunk once up front for that alone (the octree's palettes are kept)
+    const bool up_front = cutoff && n_sub > 1;
+    if (up_front)
+        for (size_t s = 0; s < n_sub; ++s) {
+            const uint32_t a = cuts[s], b = cuts[s + 1];
+            if (octree) {
+                for (uint32_t i = a; i < b; ++i) {
+                    StreamBuf src;
+                    KMG_TRY(upload_image(p, rgba[i], widths[i], heights[i], st, src));
+                    KMG_TRY(octree_of(i, (const uint8_t *)src.ptr));
+                }
+            } else {
+                std::unique_ptr<BatchStage[]> stage(new BatchStage[b - a]);
+                KMG_TRY(batch_stage(p, rgba, widths, heights, a, b, cutoff, false, st, stage.get()));
+            }
+        }
+
+    std::vector<float> c4;
+    for (size_t s = 0; s < n_sub; ++s) {
+        const uint32_t a = cuts[s], b = cuts[s + 1], count = b - a;
+        std::unique_ptr<BatchStage[]> stage(new BatchStage[count]);
+        if (octree) {
+            // the host algorithm per image; the palettes of the sub-batch before its first output
+            for (uint32_t i = a; i < b; ++i) {
+                KMG_TRY(upload_image(p, rgba[i], widths[i], heights[i], st, stage[i - a].src));
+                if (!up_front) KMG_TRY(octree_of(i, (const uint8_t *)stage[i - a].src.ptr));
+            }
+            for (uint32_t i = a; i < b; ++i) {
+                if (!reduce) {
+                    for (size_t q = 0; q < colors[i].size(); ++q) memcpy(out_rgba[i] + 4 * q, colors[i][q].data(), 4);
+                    out_counts[i] = (uint32_t)colors[i].size();
+                    continue;
+                }
+                KMG_TRY(octree_centroids(colors[i], c4));
+                KMG_TRY(apply_and_download(p, (const uint8_t *)stage[i - a].src.ptr, widths[i], heights[i], c4.data(), (uint32_t)(c4.size() / 4), mode,
+                                           cutoff, st, out_rgba[i], KMG_FORMAT_RGBA8));
+            }
+            continue;
+        }
+        KMG_TRY(batch_stage(p, rgba, widths, heights, a, b, cutoff, reduce, st, stage.get()));
+        c4.resize(4ull * color_count * count);
+        if (count < kBatchMinImages) {
+            // (too few images for the batched kernels to pay: the per-image palette step, image after image)
+            for (uint32_t q = 0; q < count; ++q)
+                KMG_TRY(kmg::palette_of_working(p, stage[q].work, stage[q].sw, stage[q].sh, color_count, st, &c4[4ull * color_count * q]));
+        } else {
+            std::vector<const uint8_t *> work(count);
+            std::vector<uint32_t> sw(count), sh(count);
+            for (uint32_t q = 0; q < count; ++q) { work[q] = stage[q].work; sw[q] = stage[q].sw; sh[q] = stage[q].sh; }
+            kmg_batch_report r;
+            KMG_TRY_DRAIN(st, dev_palette_batch(p, count, work.data(), sw.data(), sh.data(), color_count, c4.data(), nullptr, &r, st));
+            rep.launches += r.launches;
+            rep.iterations = std::max(rep.iterations, r.iterations);
+            rep.fallback += r.fallback;
+        }
+        for (uint32_t i = a; i < b; ++i) {
+            const float *mine = &c4[4ull * color_count * (i - a)];
+            if (!reduce) {
+                sorted_palette_of(mine, color_count, out_rgba[i]);     // lib.rs:255-286
+                out_counts[i] = color_count;
+                continue;
+            }
+            KMG_TRY(apply_and_download(p, (const uint8_t *)stage[i - a].src.ptr, widths[i], heights[i], mine, color_count, mode, cutoff, st,
+                                       out_rgba[i], KMG_FORMAT_RGBA8));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (report) *report = rep;
+    return KMG_OK;
+}
+
+}  // namespace
+
+extern "C" int kmg_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths,
+                                 const uint32_t *heights, uint32_t color_count, int algo, uint64_t max_resident_bytes,
+                                 uint8_t *const *out_rgba, uint32_t *out_counts, kmg_batch_report *report)
+try {
+    return batch_call(p, n_images, rgba, widths, heights, color_count, algo, KMG_MODE_REPLACE, false, max_resident_bytes, out_rgba, out_counts,
+                      report);
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_reduce_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths,
+                                const uint32_t *heights, uint32_t color_count, int algo, int mode, uint64_t max_resident_bytes,
+                                uint8_t *const *out_rgba, kmg_batch_report *report)
+try {
+    return batch_call(p, n_images, rgba, widths, heights, color_count, algo, mode, true, max_resident_bytes, out_rgba, nullptr, report);
+}
+KMG_ABI_CATCH
+
+// ---------------------------------------------------------------------------------------------
 // error statistics and the quality-targeted colour count (include/kmeans_hip.h at kmg_error_stats; kernels: kmg_error.hip)
 // ---------------------------------------------------------------------------------------------
 namespace {

@@ -86,6 +86,10 @@ constexpr float kIndexBoxLmin = -100.0f, kIndexBoxLmax = 200.0f, kIndexBoxAB = 3
 // alpha byte; the initialisation does not.
 int palette_of_working(kmg_processor *p, const uint8_t *d_src, uint32_t sw, uint32_t sh, uint32_t k, hipStream_t st, float *centroids4,
                        uint32_t *d_labels = nullptr, const float *fixed4 = nullptr, uint32_t n_fixed = 0, int weighting = KMG_WEIGHT_NONE);
+// kmg_dev_palette_batch on a hipStream_t (kmg_batch.hip): the k-means palette step of many working images in device memory, the
+// small ones through the batched kernels.  Synchronises `st`.
+int dev_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths, const uint32_t *heights,
+                      uint32_t k, float *centroids4, uint32_t *iterations, kmg_batch_report *report, hipStream_t st);
 // the weighting set on a processor right now (kmg_processor.hip; kmg_processor_set_weighting)
 int processor_weighting(kmg_processor *p);
 // the number of fixed colours set on a processor right now (kmg_processor.hip; kmg_processor_set_fixed_colors)

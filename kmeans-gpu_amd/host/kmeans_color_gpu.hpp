@@ -10,7 +10,9 @@
 //   ImageProcessor::create_on({0, 1, ..})      -> the same object over a device LIST (kmg_group_*: one processor + RCCL rank per
 //                                                 device; palette / find / reduce tile the image in row bands, same bytes)
 //   processor.reduce_batch(color_count, images, algo, mode) -> whole images per device, side by side
-//   processor.compare(source, output[, colors])            -> kmg_error_stats: exact error sums of an output against its source
+//   processor.palette_batch(color_count, images, algo) / reduce_batch(color_count, images, algo, mode, max_resident_bytes)
+//                                                          -> many small images per launch on one device (kmg_*_batch)
+//   processor.compare(source, output[, colors])         -> kmg_error_stats: exact error sums of an output against its source
 //   processor.reduce_quality(image, max_delta_e, k_min, k_max, mode) -> the colour count chosen by a quality target
 //   processor.optimize_indexed(indexed[, flags, bits])     -> the palette without unused entries, ordered, and the map packed for it
 //   processor.set_fixed_colors(colors)                     -> palette entries the k-means keeps exactly and builds around
@@ -270,6 +272,43 @@ public:
         }
         check(kmg_group_reduce_batch(g_, (uint32_t)images.size(), src.data(), ws.data(), hs.data(), color_count, (int)algo, (int)reduce_mode,
                                      dst.data()));
+        return out;
+    }
+
+    // Many small images per launch on a single-device processor (kmg_palette_batch / kmg_reduce_batch, include/kmeans_hip.h): the
+    // palettes / results that palette() / reduce() give image by image, from one launch chain for all of them.  max_resident_bytes
+    // bounds what the call keeps on the device at once (0 = 1 GiB); report: what the call did.  The batch must not be empty.
+    std::vector<std::vector<RGBA8>> palette_batch(uint32_t color_count, const std::vector<Image> &images, Algorithm algo,
+                                                  uint64_t max_resident_bytes = 0, kmg_batch_report *report = nullptr) const
+    {
+        std::vector<std::vector<RGBA8>> out(images.size(), std::vector<RGBA8>(color_count ? color_count : 1));
+        std::vector<const uint8_t *> src;
+        std::vector<uint8_t *> dst;
+        std::vector<uint32_t> ws, hs, counts(images.size() ? images.size() : 1);
+        for (size_t i = 0; i < images.size(); ++i) {
+            src.push_back(bytes(images[i])); dst.push_back(reinterpret_cast<uint8_t *>(out[i].data()));
+            ws.push_back(images[i].dims.first); hs.push_back(images[i].dims.second);
+        }
+        check(kmg_palette_batch(single(), (uint32_t)images.size(), src.data(), ws.data(), hs.data(), color_count, (int)algo, max_resident_bytes,
+                                dst.data(), counts.data(), report));
+        for (size_t i = 0; i < images.size(); ++i) out[i].resize(counts[i]);
+        return out;
+    }
+
+    std::vector<Image> reduce_batch(uint32_t color_count, const std::vector<Image> &images, Algorithm algo, ReduceMode reduce_mode,
+                                    uint64_t max_resident_bytes, kmg_batch_report *report = nullptr) const
+    {
+        std::vector<Image> out;
+        std::vector<const uint8_t *> src;
+        std::vector<uint8_t *> dst;
+        std::vector<uint32_t> ws, hs;
+        for (const Image &im : images) out.emplace_back(im.dims, std::vector<RGBA8>(im.rgba.size()));
+        for (size_t i = 0; i < images.size(); ++i) {
+            src.push_back(bytes(images[i])); dst.push_back(reinterpret_cast<uint8_t *>(out[i].rgba.data()));
+            ws.push_back(images[i].dims.first); hs.push_back(images[i].dims.second);
+        }
+        check(kmg_reduce_batch(single(), (uint32_t)images.size(), src.data(), ws.data(), hs.data(), color_count, (int)algo, (int)reduce_mode,
+                               max_resident_bytes, dst.data(), report));
         return out;
     }
 

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "BatchReport","Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -195,6 +195,17 @@ INDEX_KEEP_UNUSED, INDEX_KEEP_TRANSPARENT, INDEX_TRANSPARENT_FIRST = 4, 8, 16
 INDEX_DROPPED = 0xFFFF                  # remap entry of a palette entry the plan drops
 
 
+class BatchReport(C.Structure):         # include/kmeans_hip.h kmg_batch_report: 16 bytes
+    _fields_ = [("launches", C.c_uint32), ("iterations", C.c_uint32), ("sub_batches", C.c_uint32), ("fallback", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.launches, self.iterations, self.sub_batches, self.fallback)
+
+    def __repr__(self):
+        return (f"BatchReport(launches={self.launches}, iterations={self.iterations}, sub_batches={self.sub_batches}, "
+                f"fallback={self.fallback})")
+
+
 class IndexPlanInfo(C.Structure):       # include/kmeans_hip.h kmg_index_plan_info: 16 bytes
     _fields_ = [("n_colors", C.c_uint32), ("n_slots", C.c_uint32), ("transparent", C.c_int32), ("bits", C.c_uint32)]
 
@@ -347,6 +358,7 @@ SYMBOLS = [
     "kmg_lloyd_update", "kmg_lloyd_assign_update", "kmg_lloyd_set_cell_share", "kmg_lloyd_labels_from_tables",
     "kmg_lloyd_table_buffers", "kmg_lloyd_accumulate_into", "kmg_lloyd_labels_from_tables_update", "kmg_lloyd_histogram_buffer", "kmg_lloyd_rebuild_from_histogram", "kmg_debug_block_counts", "kmg_debug_idle_blocks", "kmg_debug_encode_table_check", "kmg_debug_division_check", "kmg_lloyd_converged_count", "kmg_lloyd_iterate", "kmg_lloyd_flush", "kmg_lloyd_run", "kmg_dev_apply", "kmg_apply_plan_create", "kmg_apply_plan_run", "kmg_apply_plan_destroy", "kmg_apply_plan_status",
     "kmg_find_indexed", "kmg_reduce_indexed", "kmg_apply_plan_create_format", "kmg_dev_apply_format",
+    "kmg_dev_palette_batch", "kmg_palette_batch", "kmg_reduce_batch",
     "kmg_dither_threshold", "kmg_dev_compare", "kmg_compare", "kmg_reduce_quality",
     "kmg_sequence_create", "kmg_sequence_destroy", "kmg_sequence_add", "kmg_sequence_add_device", "kmg_sequence_clear",
     "kmg_sequence_info", "kmg_sequence_centroids", "kmg_sequence_palette", "kmg_dev_frame_delta", "kmg_dev_frame_delta_lossy",
@@ -516,6 +528,12 @@ def lib():
     L.kmg_group_reduce.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, u8p]
     L.kmg_group_reduce_batch.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32,
                                          C.c_int, C.c_int, C.POINTER(vp)]
+    L.kmg_dev_palette_batch.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, f32p,
+                                        u32p, C.POINTER(BatchReport), vp]
+    L.kmg_palette_batch.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_int,
+                                    C.c_uint64, C.POINTER(vp), u32p, C.POINTER(BatchReport)]
+    L.kmg_reduce_batch.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_int,
+                                   C.c_int, C.c_uint64, C.POINTER(vp), C.POINTER(BatchReport)]
     L.kmg_group_lloyd_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
     L.kmg_group_lloyd_destroy.argtypes = [vp]
     L.kmg_group_lloyd_destroy.restype = None
@@ -686,6 +704,7 @@ class ImageProcessor:
         self._sequences = None          # weak set of the live Sequence objects: closed with the processor, which they need
         _register(self)
         self.alpha_weight = False
+        self.last_batch_report = None   # BatchReport of the last palette_batch / reduce_batch / palette_batch_device
         if fixed_colors is not None:
             self.set_fixed_colors(fixed_colors)
         if alpha_weight:
@@ -770,6 +789,59 @@ class ImageProcessor:
         out = _result(img, out)
         _check(lib().kmg_reduce(self._h, _np_ptr(img), w, h, int(color_count), int(algo), int(reduce_mode), _np_ptr(out)))
         return out
+
+    # ---- batches: many small images per launch (include/kmeans_hip.h kmg_batch_report) --------
+    @staticmethod
+    def _batch_arrays(imgs):
+        n = len(imgs)
+        return ((C.c_void_p * n)(*[im.ctypes.data for im in imgs]), (C.c_uint32 * n)(*[im.shape[1] for im in imgs]),
+                (C.c_uint32 * n)(*[im.shape[0] for im in imgs]))
+
+    def palette_batch(self, color_count, images, algo=Algorithm.Kmeans, max_resident_bytes=0):
+        """kmg_palette_batch: the palettes of many images, one launch chain for all of them; returns the list of palettes, each
+        what palette() returns for that image.  The report of the call: last_batch_report"""
+        imgs = [_image(im) for im in images]
+        n = len(imgs)
+        outs = [np.empty((max(int(color_count), 1), 4), np.uint8) for _ in imgs]
+        src, ws, hs = self._batch_arrays(imgs)
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        counts = np.zeros(max(n, 1), np.uint32)
+        rep = BatchReport()
+        _check(lib().kmg_palette_batch(self._h, n, src, ws, hs, int(color_count), int(algo), int(max_resident_bytes), dst, _np_ptr(counts),
+                                       C.byref(rep)))
+        self.last_batch_report = rep
+        return [o[:int(c)].copy() for o, c in zip(outs, counts)]
+
+    def reduce_batch(self, color_count, images, algo=Algorithm.Kmeans, reduce_mode=ReduceMode.Replace, max_resident_bytes=0, out=None):
+        """kmg_reduce_batch: reduce() of many images with one launch chain for their palettes; returns the list of results (it
+        mirrors Group.reduce_batch).  out: optional list of arrays that receive the results, as reduce(out=) takes one.  The
+        report of the call: last_batch_report"""
+        imgs = [_image(im) for im in images]
+        n = len(imgs)
+        if out is not None and len(out) != n:
+            raise ValueError("out must hold one array per image")
+        outs = [_result(im, None if out is None else out[i]) for i, im in enumerate(imgs)]
+        src, ws, hs = self._batch_arrays(imgs)
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        rep = BatchReport()
+        _check(lib().kmg_reduce_batch(self._h, n, src, ws, hs, int(color_count), int(algo), int(reduce_mode), int(max_resident_bytes), dst,
+                                      C.byref(rep)))
+        self.last_batch_report = rep
+        return outs
+
+    def palette_batch_device(self, d_images, widths, heights, k, stream=0):
+        """kmg_dev_palette_batch: working images in device memory (d_images: their addresses) -> (centroids (n, k, 4) float32 in
+        index order, iterations (n,) uint32).  The report of the call: last_batch_report"""
+        n = len(d_images)
+        src = (C.c_void_p * n)(*[int(d) for d in d_images])
+        ws = (C.c_uint32 * n)(*[int(w) for w in widths])
+        hs = (C.c_uint32 * n)(*[int(h) for h in heights])
+        cent = np.empty((n, int(k), 4), np.float32)
+        its = np.zeros(max(n, 1), np.uint32)
+        rep = BatchReport()
+        _check(lib().kmg_dev_palette_batch(self._h, n, src, ws, hs, int(k), _np_ptr(cent), _np_ptr(its), C.byref(rep), C.c_void_p(stream)))
+        self.last_batch_report = rep
+        return cent, its[:n]
 
     # ---- palette-index output (include/kmeans_hip.h kmg_output_format) ----------------------
     def _index_format(self, k):

@@ -4,6 +4,7 @@
     python -m kmeans_gpu_amd.cli reduce  -i img.png -c 8 [-a kmeans|octree] [-m replace|dither|meld|diffuse] [-o out.png]
     python -m kmeans_gpu_amd.cli find    -i img.png -p "#050505,#ffffff,#ff0000"|palette.png [-m ...] [-o out.png]
     python -m kmeans_gpu_amd.cli palette -i img.png -c 8 [-a ...] [-s 40] [-o out.png]
+    python -m kmeans_gpu_amd.cli batch   -i A.png B.png ... -c 8 [-a ...] [-m ...] -o DIR | --palette
 
 Every sub-command also takes `--alpha-cutoff N` (0..255, default 0 = alpha ignored, as in the reference): with N >= 1 only the
 pixels whose alpha is at least N shape the palette, and the output keeps the input's alpha (include/kmeans_hip.h, kmg_options).
@@ -45,6 +46,10 @@ anti-aliased edge at alpha 20 pulls a colour a twelfth as hard as a solid pixel,
 input's size instead -- an importance map for an opaque image: 255 where the colours matter most, 0 where they do not matter at
 all.  It implies --alpha-weight, replaces the input's alpha (the output is opaque) and is therefore refused together with a
 non-zero --alpha-cutoff; `sequence` applies the one map to every frame.
+
+`batch` reduces many images in one call (kmg_reduce_batch: one launch chain for the palettes of all of them, the results of
+`reduce` image by image) and writes DIR/<name>-reduce-c<K>-<algo>-<mode>.png for every input; `--palette` prints their palettes
+instead (kmg_palette_batch).  It takes --alpha-cutoff; not --fixed, --alpha-weight or --devices.
 
 Image decoding/encoding (the `image` crate in the reference) is done with Pillow.  One flag the reference does not have:
 `--devices 0,1,...` (before the sub-command) runs the same operation over several GPUs of the node (kmg_group_*: the image
@@ -342,7 +347,8 @@ def validate_devices(s):
     return devices
 
 
-def main(argv=None):
+def build_parser():
+    """the argument parser of every sub-command"""
     ap = argparse.ArgumentParser(prog="kmeans-hip", description="k-means colour quantisation on MI355X")
     ap.add_argument("--devices", type=validate_devices, default=None,
                     help="HIP device ordinals, e.g. 0,1,2,3: tile the image over several GPUs (no counterpart in the reference)")
@@ -380,7 +386,14 @@ def main(argv=None):
     q.add_argument("--warm", action="store_true",
                    help="with --local: every frame's k-means starts from the previous frame's centroids (not with --fixed)")
     q.add_argument("--delay-ms", type=validate_delay, default=100, help="display time of every frame in milliseconds (default 100)")
-    for s in (p, f, r, q):
+    b = sub.add_parser("batch", help="Reduce many images with one launch chain for their palettes; one output per input")
+    b.add_argument("-c", "--colorcount", type=validate_k, required=True)
+    b.add_argument("-i", "--input", nargs="+", required=True)
+    b.add_argument("-o", "--output", metavar="DIR", help="directory of the outputs (created if missing)")
+    b.add_argument("-a", "--algo", choices=list(_ALGOS), default="kmeans")
+    b.add_argument("-m", "--mode", choices=list(_MODES), default="replace")
+    b.add_argument("--palette", action="store_true", help="print the palette of every input instead of writing reduced images")
+    for s in (p, f, r, q, b):
         s.add_argument("--alpha-cutoff", type=validate_alpha_cutoff, default=0,
                        help="1..255: pixels with a lower alpha do not shape the palette, the output keeps the input's alpha")
     for s in (p, r, q):
@@ -403,7 +416,37 @@ def main(argv=None):
     r.add_argument("--max-error", type=validate_max_error, default=None, metavar="DE",
                    help="choose the colour count: as few colours (at most -c) as keep the dE76 RMS of the shrunk image at or below DE; k-means only")
     r.add_argument("--min-colors", type=validate_k, default=None, metavar="A", help="lower bound of --max-error's search (default 2)")
+    return ap
+
+
+def run_batch(args, ap):
+    """the `batch` sub-command: every input through one kmg_reduce_batch (or, --palette, kmg_palette_batch) call"""
+    if args.devices:
+        ap.error("`batch` is not supported with --devices")
+    if not args.palette and not args.output:
+        ap.error("`batch` writes one output per input: it needs -o DIR (or --palette)")
+    images = [_load(path) for path in args.input]
+    with ImageProcessor(alpha_cutoff=args.alpha_cutoff) as proc:
+        if args.palette:
+            for path, colors in zip(args.input, proc.palette_batch(args.colorcount, images, _ALGOS[args.algo])):
+                print(f"Palette {path}: " + ",".join(f"#{c[0]:02X}{c[1]:02X}{c[2]:02X}" for c in colors))
+        else:
+            os.makedirs(args.output, exist_ok=True)
+            outs = proc.reduce_batch(args.colorcount, images, _ALGOS[args.algo], _MODES[args.mode])
+            for path, out in zip(args.input, outs):
+                name = os.path.basename(reduce_file_path(args.colorcount, args.algo, args.mode, None, path))
+                _save(os.path.join(args.output, name), out)
+        rep = proc.last_batch_report
+        print(f"Batch: {len(images)} images, {rep.launches} launches, {rep.iterations} iterations at most, {rep.sub_batches} sub-batches, "
+              f"{rep.fallback} on the per-image path")
+    return 0
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if args.command == "batch":
+        return run_batch(args, ap)
     if getattr(args, "weights", None) is not None:
         if args.alpha_cutoff:
             ap.error("--weights replaces the input's alpha with the map: it cannot be combined with a non-zero --alpha-cutoff")

@@ -119,6 +119,16 @@ pub struct kmg_frame_hold {
     pub held_sse: u64,
 }
 
+/// `kmg_batch_report` (include/kmeans_hip.h): 16 bytes, what a batch call did.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct kmg_batch_report {
+    pub launches: u32,
+    pub iterations: u32,
+    pub sub_batches: u32,
+    pub fallback: u32,
+}
+
 extern "C" {
     pub fn kmg_last_error() -> *const c_char;
     pub fn kmg_version() -> *const c_char;
@@ -188,6 +198,48 @@ extern "C" {
         out_palette_rgba: *mut u8,
         out_count: *mut u32,
         out_index: *mut (),
+    ) -> c_int;
+    // batches (no counterpart in the reference): many small images per launch on one device.  `rgba`, `widths`, `heights`,
+    // `out_rgba` (and `out_counts`) are arrays of `n_images` entries; `d_rgba` holds device pointers.  (The pointer arrays are
+    // written the way tests/test_rust_shim.py derives a `T *const *` from the header; the library reads the arrays and writes
+    // through the entries of `out_rgba` only.)
+    pub fn kmg_dev_palette_batch(
+        p: *mut kmg_processor,
+        n_images: u32,
+        d_rgba: *mut *const u8,
+        widths: *const u32,
+        heights: *const u32,
+        k: u32,
+        centroids4: *mut f32,
+        iterations: *mut u32,
+        report: *mut kmg_batch_report,
+        stream: *mut (),
+    ) -> c_int;
+    pub fn kmg_palette_batch(
+        p: *mut kmg_processor,
+        n_images: u32,
+        rgba: *mut *const u8,
+        widths: *const u32,
+        heights: *const u32,
+        color_count: u32,
+        algo: c_int,
+        max_resident_bytes: u64,
+        out_rgba: *mut *const u8,
+        out_counts: *mut u32,
+        report: *mut kmg_batch_report,
+    ) -> c_int;
+    pub fn kmg_reduce_batch(
+        p: *mut kmg_processor,
+        n_images: u32,
+        rgba: *mut *const u8,
+        widths: *const u32,
+        heights: *const u32,
+        color_count: u32,
+        algo: c_int,
+        mode: c_int,
+        max_resident_bytes: u64,
+        out_rgba: *mut *const u8,
+        report: *mut kmg_batch_report,
     ) -> c_int;
     // error statistics of an output against its source (host buffers; `out` holds 4, 1 or 2 bytes per pixel for `format`) and the
     // colour count chosen by a quality target: no counterpart in the reference
