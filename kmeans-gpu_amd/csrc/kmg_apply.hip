@@ -1,98 +1,66 @@
 // kmg_apply.hip -- the output passes of the C ABI (find_colors / dither_colors / meld_colors, core/src/operations.rs:99-155,
-// 215-271): kmg_apply_plan_*, kmg_dev_apply, their cost models and the exhaustive checks of their candidate masks / lists.
+// 215-271): kmg_apply_plan_*, kmg_dev_apply and the exhaustive checks of their candidate masks / lists.  Which route a plan takes
+// is decided by apply_route (kmg_apply_route.h, with the cost models); here a route is named in three places only: the list of its
+// scratch parts, the switch that builds them and the switch that runs a band.
 
 #include "kmg_state.h"
+#include "kmg_apply_route.h"
 
-#include <cmath>
+static_assert(kRouteListMaxK == kLabListMaxK && kRouteModeDither == KMG_MODE_DITHER && kRouteModeMeld == KMG_MODE_MELD &&
+              kRouteModeDiffuse == KMG_MODE_DIFFUSE, "kmg_apply_route.h repeats these constants");
 
-// Same model for the replace-mode output pass (no histogram: every cell is labelled; scratch from the processor's
-// blocks).
-static bool replace_table_pays(const kmg_processor *p, uint64_t n, uint32_t k)
+// a HIP call inside a function that returns hipError_t
+#define HIP_PASS(expr)                                                                         \
+    do {                                                                                       \
+        const hipError_t e_ = (expr);                                                          \
+        if (e_ != hipSuccess) return e_;                                                       \
+    } while (0)
+
+// the (L, a, b, chroma) table of a caller's k x 4 floats
+static std::vector<Centroid> centroids_of(const float *c4, uint32_t k)
 {
-    if (const int f = forced_strategy(p)) return f > 0;
-    const double N = (double)n;
-    const double brute = N * (8.1e-12 + 2.45e-13 * k);
-    const double table = 9.0e-5 + 1.85e-7 * k + N * (k <= 256 ? 1.8e-12 + 2.0e-15 * k : 6.6e-12);
-    return table < brute;
-}
-
-// Error-diffusion output pass (kmg_diffuse.hip): the colour table costs its build (the replace route's model above) and then a
-// few LDS reads per step; the per-lane scan costs ~k key evaluations per step on the critical path, which for a W x H image is
-// W + 2 (H - 1) steps -- about 3 sqrt(n) for the shapes of photographs (an estimate from the step counts; not fitted).
-static bool diffuse_table_pays(const kmg_processor *p, uint64_t n, uint32_t k)
-{
-    if (k < 2) return false;                                // one colour: nothing to look up
-    if (const int f = forced_strategy(p)) return f > 0;
-    const double steps = 3.0 * std::sqrt((double)n);
-    const double table = 9.0e-5 + 1.85e-7 * k;
-    return steps * 6.0e-9 * k > table;
-}
-
-// Dither output pass: per-pixel scan of all k centroids, or of the candidates of the pixel's cell only (k <= 256: byte lists per
-// cell of a grid over Lab, kmg_lists.hip; above: mask words per (RGB cell, Bayer index)).  Measured on MI355X, noise images,
-// random palettes (tools/dither_crossover.py -> profiles/r03_dither_crossover.txt): the scan costs 6.5 + 0.275 k ps per pixel,
-// the list pass 6.8 + 0.02 k ps per pixel after ~45 us for the lists and their launch; with k >= 128 the scan's own latency
-// (one wave walks all k) makes the lists win on any image.
-static bool dither_pruning_pays(const kmg_processor *p, uint64_t n, uint32_t k)
-{
-    if (const int f = forced_strategy(p)) return f > 0;
-    if (k > kLabListMaxK) return n >= 4000000ull;          // mask words: 0.55 ms of masks at k = 512
-    if (k >= 128u) return n >= 16384ull;
-    return (double)n * (0.255 * k - 0.3) > 45.0e6;          // ps saved per pixel x pixels > 45 us
-}
-
-// Meld output pass: ordered scan of all k centroids per pixel, or of the candidates of the pixel's colour
-// cell only (k_meld_candidates: ~0.03 ms per 64 centroids; tools/dither_probe.py).
-static bool meld_pruning_pays(const kmg_processor *p, uint64_t n, uint32_t k)
-{
-    if (const int f = forced_strategy(p)) return f > 0;
-    return k >= 16 && n >= (1ull << 20);
-}
-
-// test support: exhaustive validation of the dither candidate masks (kmg_table.hip) for a centroid
-// table: over all 2^24 colours x 16 Bayer offsets, the arg-min over the candidates must equal the
-// brute-force arg-min.  *violations must come back 0.
-// Which pruned dither / meld pass?  k <= 512: byte lists per cell of a grid over Lab (kmg_lists.hip); larger k: mask words per (RGB
-// cell, Bayer index) (kmg_table.hip).  KMG_STRATEGY_MASK_WORDS (kmg_options.strategy) sends every k to the mask words.
-static bool dither_takes_lists(const kmg_processor *p, uint32_t k)
-{
-    return !(p->strategy.load(std::memory_order_relaxed) & KMG_STRATEGY_MASK_WORDS) && k <= kLabListMaxK;
-}
-
-extern "C" int kmg_debug_check_dither_masks(kmg_processor *p, const float *c4, uint32_t k, uint64_t *violations, void *stream)
-try {
-    if (!p || !c4 || !violations || k < 2 || k > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "bad check_dither_masks arguments");
-    HIP_TRY(hipSetDevice(p->device));
-    int rc;
-    if ((rc = ensure_bounds(p, S(stream))) != KMG_OK) return rc;
     std::vector<Centroid> hc(k);
-    for (uint32_t i = 0; i < k; ++i) {
-        hc[i].L = c4[4 * i]; hc[i].a = c4[4 * i + 1]; hc[i].b = c4[4 * i + 2];
-        hc[i].C = chroma(hc[i].a, hc[i].b);
-    }
-    const float thr = dither_threshold(c4, k);
-    DevBuf cent, masks, viol;
+    for (uint32_t i = 0; i < k; ++i) hc[i] = {c4[4 * i], c4[4 * i + 1], c4[4 * i + 2], chroma(c4[4 * i + 1], c4[4 * i + 2])};
+    return hc;
+}
+
+// test support: exhaustive validation of the candidate masks (kmg_table.hip) and, for k <= kLabListMaxK, of the byte lists over Lab
+// cells (kmg_lists.hip, same counter) for a centroid table.  *violations must come back 0.
+//   dither: over all 2^24 colours x 16 Bayer offsets, the arg-min over the candidates must equal the brute-force arg-min;
+//   meld (k >= 2): over all 2^24 colours the two closest centroids found among the cell's candidates must be those of the full scan.
+static int check_candidates(kmg_processor *p, const float *c4, uint32_t k, bool dither, uint64_t *violations, hipStream_t st)
+{
+    HIP_TRY(hipSetDevice(p->device));
+    KMG_TRY(ensure_bounds(p, st));
+    const std::vector<Centroid> hc = centroids_of(c4, k);
+    const float thr = dither ? dither_threshold(c4, k) : 0.0f;
+    DevBuf cent, masks, viol, lists;
     HIP_TRY(cent.alloc(sizeof(Centroid) * k));
-    HIP_TRY(masks.alloc(sizeof(uint64_t) * (size_t)kCells * 16u * mask_words(k)));
+    HIP_TRY(masks.alloc(sizeof(uint64_t) * (size_t)kCells * (dither ? 16u : 1u) * mask_words(k)));
     HIP_TRY(viol.alloc(sizeof(unsigned long long)));
-    HIP_TRY(hipMemcpyAsync(cent.ptr, hc.data(), sizeof(Centroid) * k, hipMemcpyHostToDevice, S(stream)));
-    HIP_TRY(hipMemsetAsync(viol.ptr, 0, sizeof(unsigned long long), S(stream)));
-    HIP_TRY(launch_offset_candidates(p->d_bounds, (const Centroid *)cent.ptr, k, thr, (uint64_t *)masks.ptr, S(stream)));
-    HIP_TRY(launch_check_offset_masks((const Centroid *)cent.ptr, k, (const uint64_t *)masks.ptr, p->d_lut, thr,
-                                      (unsigned long long *)viol.ptr, S(stream)));
-    if (k <= kLabListMaxK) {                                // the byte lists over Lab cells (kmg_lists.hip), same counter
-        DevBuf lists;
+    HIP_TRY(hipMemcpyAsync(cent.ptr, hc.data(), sizeof(Centroid) * k, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(viol.ptr, 0, sizeof(unsigned long long), st));
+    const Centroid *d_cent = (const Centroid *)cent.ptr;
+    uint64_t *d_masks = (uint64_t *)masks.ptr;
+    unsigned long long *d_viol = (unsigned long long *)viol.ptr;
+    if (dither) {
+        HIP_TRY(launch_offset_candidates(p->d_bounds, d_cent, k, thr, d_masks, st));
+        HIP_TRY(launch_check_offset_masks(d_cent, k, d_masks, p->d_lut, thr, d_viol, st));
+    } else {
+        HIP_TRY(launch_meld_candidates(p->d_bounds, d_cent, k, d_masks, st));
+        HIP_TRY(launch_check_meld_masks(d_cent, k, d_masks, p->d_lut, d_viol, st));
+    }
+    if (k <= kLabListMaxK) {
         HIP_TRY(lists.alloc(lab_list_bytes(k)));
-        HIP_TRY(launch_lab_candidates((const Centroid *)cent.ptr, k, thr, false, (uint8_t *)lists.ptr, S(stream)));
-        HIP_TRY(launch_check_lab_lists((const Centroid *)cent.ptr, k, (const uint8_t *)lists.ptr, p->d_lut, thr,
-                                       (unsigned long long *)viol.ptr, S(stream)));
-        HIP_TRY(hipStreamSynchronize(S(stream)));
+        HIP_TRY(launch_lab_candidates(d_cent, k, thr, !dither, (uint8_t *)lists.ptr, st));
+        HIP_TRY(dither ? launch_check_lab_lists(d_cent, k, (const uint8_t *)lists.ptr, p->d_lut, thr, d_viol, st)
+                       : launch_check_lab_lists_two(d_cent, k, (const uint8_t *)lists.ptr, p->d_lut, d_viol, st));
     }
     unsigned long long h = 0;
-    HIP_TRY(hipMemcpyAsync(&h, viol.ptr, sizeof h, hipMemcpyDeviceToHost, S(stream)));
-    HIP_TRY(hipStreamSynchronize(S(stream)));
+    HIP_TRY(hipMemcpyAsync(&h, viol.ptr, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *violations = h;
-    if (KMG_TOOLS_ENV("KMG_DITHER_STATS")) {
+    if (dither && KMG_TOOLS_ENV("KMG_DITHER_STATS")) {
         // distribution of the candidate counts: per (cell, Bayer index) slot, and per cell over its 16 slots together
         const uint32_t words = mask_words(k);
         std::vector<uint64_t> hm((size_t)kCells * 16u * words);
@@ -117,6 +85,19 @@ try {
     }
     return KMG_OK;
 }
+
+extern "C" int kmg_debug_check_dither_masks(kmg_processor *p, const float *c4, uint32_t k, uint64_t *violations, void *stream)
+try {
+    if (!p || !c4 || !violations || k < 2 || k > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "bad check_dither_masks arguments");
+    return check_candidates(p, c4, k, true, violations, S(stream));
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_debug_check_meld_masks(kmg_processor *p, const float *c4, uint32_t k, uint64_t *violations, void *stream)
+try {
+    if (!p || !c4 || !violations || k < 2 || k > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "bad check_meld_masks arguments");
+    return check_candidates(p, c4, k, false, violations, S(stream));
+}
 KMG_ABI_CATCH
 
 #ifdef KMG_TOOLS
@@ -130,8 +111,7 @@ extern "C" KMG_API int kmg_tools_dither_list_stats(kmg_processor *p, const uint8
 try {
     if (!p || !d_rgba || !c4 || !out68 || k < 2 || k > 256) return fail(KMG_ERR_INVALID_ARGUMENT, "bad dither_list_stats arguments");
     HIP_TRY(hipSetDevice(p->device));
-    std::vector<Centroid> hc(k);
-    for (uint32_t i = 0; i < k; ++i) hc[i] = {c4[4 * i], c4[4 * i + 1], c4[4 * i + 2], chroma(c4[4 * i + 1], c4[4 * i + 2])};
+    const std::vector<Centroid> hc = centroids_of(c4, k);
     const float thr = dither_threshold(c4, k);
     DevBuf cent, lists, acc;
     HIP_TRY(cent.alloc(sizeof(Centroid) * k));
@@ -147,43 +127,6 @@ try {
 KMG_ABI_CATCH
 #endif
 
-// test support: exhaustive validation of the meld candidate masks for a centroid table (k >= 2): over all
-// 2^24 colours the two closest centroids found among the cell's candidates must be those of the full scan.
-extern "C" int kmg_debug_check_meld_masks(kmg_processor *p, const float *c4, uint32_t k, uint64_t *violations, void *stream)
-try {
-    if (!p || !c4 || !violations || k < 2 || k > KMG_MAX_K) return fail(KMG_ERR_INVALID_ARGUMENT, "bad check_meld_masks arguments");
-    HIP_TRY(hipSetDevice(p->device));
-    int rc;
-    if ((rc = ensure_bounds(p, S(stream))) != KMG_OK) return rc;
-    std::vector<Centroid> hc(k);
-    for (uint32_t i = 0; i < k; ++i) {
-        hc[i].L = c4[4 * i]; hc[i].a = c4[4 * i + 1]; hc[i].b = c4[4 * i + 2];
-        hc[i].C = chroma(hc[i].a, hc[i].b);
-    }
-    DevBuf cent, masks, viol;
-    HIP_TRY(cent.alloc(sizeof(Centroid) * k));
-    HIP_TRY(masks.alloc(sizeof(uint64_t) * (size_t)kCells * mask_words(k)));
-    HIP_TRY(viol.alloc(sizeof(unsigned long long)));
-    HIP_TRY(hipMemcpyAsync(cent.ptr, hc.data(), sizeof(Centroid) * k, hipMemcpyHostToDevice, S(stream)));
-    HIP_TRY(hipMemsetAsync(viol.ptr, 0, sizeof(unsigned long long), S(stream)));
-    HIP_TRY(launch_meld_candidates(p->d_bounds, (const Centroid *)cent.ptr, k, (uint64_t *)masks.ptr, S(stream)));
-    HIP_TRY(launch_check_meld_masks((const Centroid *)cent.ptr, k, (const uint64_t *)masks.ptr, p->d_lut,
-                                    (unsigned long long *)viol.ptr, S(stream)));
-    DevBuf lists;
-    if (k <= kLabListMaxK) {                                // the byte lists over Lab cells (kmg_lists.hip), same counter
-        HIP_TRY(lists.alloc(lab_list_bytes(k)));
-        HIP_TRY(launch_lab_candidates((const Centroid *)cent.ptr, k, 0.0f, true, (uint8_t *)lists.ptr, S(stream)));
-        HIP_TRY(launch_check_lab_lists_two((const Centroid *)cent.ptr, k, (const uint8_t *)lists.ptr, p->d_lut,
-                                           (unsigned long long *)viol.ptr, S(stream)));
-    }
-    unsigned long long h = 0;
-    HIP_TRY(hipMemcpyAsync(&h, viol.ptr, sizeof h, hipMemcpyDeviceToHost, S(stream)));
-    HIP_TRY(hipStreamSynchronize(S(stream)));
-    *violations = h;
-    return KMG_OK;
-}
-KMG_ABI_CATCH
-
 // ---- the output pass as a PLAN: everything that depends on the centroid table only -- the device copy of centroids and palette,
 // the threshold, the candidate lists / masks or the label tables of the colour cube -- is built once (asynchronously on the
 // creating call's stream); kmg_apply_plan_run then launches the per-pixel kernel for any band of rows on any stream, without a
@@ -197,7 +140,7 @@ struct kmg_apply_plan {
     uint32_t alpha_cutoff = 0;          // kmg_options.alpha_cutoff when the plan was made (0: alpha ignored)
     bool dither = false;
     float thr = 0.0f;
-    enum Route { kScan, kMeldScan, kMeldMasks, kMeldLists, kReplaceTable, kDitherLists, kDitherMasks, kDiffuseTable, kDiffuseScan } route = kScan;
+    Route route = Route::kScan;
     ArenaGuard arena;
     std::vector<uint8_t> staged;        // host copy of the tables: lives as long as the asynchronous upload may
     Centroid *d_cent = nullptr;
@@ -240,6 +183,35 @@ static int check_index_format(const float *c4, uint32_t k, int mode, int format,
     return KMG_OK;
 }
 
+// What a route keeps in the plan's scratch block behind the centroid table and the palette: the parts in the order the build (the
+// switch of plan_create) takes them, and whether the identity table rides behind the palette.  Sizing and building both read this.
+struct RouteScratch {
+    bool ident = false;
+    std::vector<size_t> parts;
+};
+
+static RouteScratch route_scratch(Route route, uint32_t k, bool index_format)
+{
+    const size_t masks_bytes = sizeof(uint64_t) * (size_t)kCells * mask_words(k);
+    switch (route) {
+    case Route::kScan:
+    case Route::kMeldScan:
+    case Route::kDiffuseScan:
+        return {};
+    case Route::kMeldLists:
+    case Route::kDitherLists:
+        return {false, {lab_list_bytes(k)}};
+    case Route::kMeldMasks:
+        return {false, {masks_bytes}};
+    case Route::kDitherMasks:                                          // (index output: its kernel writes pal[label] with pal = the identity)
+        return {index_format, {16u * masks_bytes}};
+    case Route::kReplaceTable:
+    case Route::kDiffuseTable:                                         // per-colour labels, first-level tables, the cube pass's scratch
+        return {false, {(size_t)(k <= 256 ? 1 : 2) << 24, sub_table_bytes(), cube_masks_bytes(k), cube_work_bytes()}};
+    }
+    return {};
+}
+
 static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, uint64_t n_pixels_hint, void *stream,
                        uint32_t alpha_cutoff, kmg_apply_plan **out, int format = KMG_FORMAT_RGBA8)
 {
@@ -247,122 +219,91 @@ static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, 
     *out = nullptr;
     KMG_TRY(check_k_limit(k));
     KMG_TRY(check_mode(mode));
-    int rc0;
-    if (format != KMG_FORMAT_RGBA8 && (rc0 = check_index_format(c4, k, mode, format, alpha_cutoff)) != KMG_OK) return rc0;
+    if (format != KMG_FORMAT_RGBA8) KMG_TRY(check_index_format(c4, k, mode, format, alpha_cutoff));
     HIP_TRY(hipSetDevice(p->device));
+    const hipStream_t st = S(stream);
     kmg_apply_plan *pl = new (std::nothrow) kmg_apply_plan();
     if (!pl) return fail(KMG_ERR_OUT_OF_MEMORY, "host allocation failed");
     struct Undo { kmg_apply_plan *pl; ~Undo() { if (pl) { if (pl->ready) (void)hipEventDestroy(pl->ready); (void)hipStreamSynchronize(pl->built_on); delete pl; } } } undo{pl};
-    pl->p = p; pl->k = k; pl->mode = mode; pl->format = format; pl->alpha_cutoff = alpha_cutoff; pl->built_on = S(stream);
+    pl->p = p; pl->k = k; pl->mode = mode; pl->format = format; pl->alpha_cutoff = alpha_cutoff; pl->built_on = st;
 
-    // per-centroid work on the host: (L,a,b,C) table, RGBA8 palette (lab_to_rgb.wgsl), threshold
-    std::vector<Centroid> hc(k);
+    // per-centroid work on the host: (L,a,b,C) table, RGBA8 palette (lab_to_rgb.wgsl) with the sentinel's entry behind it
+    // (mix_colors.wgsl:73), threshold
+    const std::vector<Centroid> hc = centroids_of(c4, k);
     std::vector<uint32_t> pal(k + 1);
-    for (uint32_t i = 0; i < k; ++i) {
-        hc[i].L = c4[4 * i]; hc[i].a = c4[4 * i + 1]; hc[i].b = c4[4 * i + 2];
-        hc[i].C = chroma(hc[i].a, hc[i].b);
+    const float sentinel[3] = {10000.0f, 10000.0f, 10000.0f};
+    for (uint32_t i = 0; i <= k; ++i) {
         uint8_t px[4];
-        shader_lab_to_rgba8(c4 + 4 * i, px);
+        shader_lab_to_rgba8(i < k ? c4 + 4 * i : sentinel, px);
         memcpy(&pal[i], px, 4);
     }
-    {
-        const float sentinel[3] = {10000.0f, 10000.0f, 10000.0f};     // mix_colors.wgsl:73
-        uint8_t px[4];
-        shader_lab_to_rgba8(sentinel, px);
-        memcpy(&pal[k], px, 4);
-    }
-    const bool dither = (mode == KMG_MODE_DITHER) && k > 1;           // mix_colors.wgsl:104-108
-    const float thr = dither ? dither_threshold(c4, k) : 0.0f;
-    pl->dither = dither; pl->thr = thr;
+    pl->dither = (mode == KMG_MODE_DITHER) && k > 1;                   // mix_colors.wgsl:104-108
+    pl->thr = pl->dither ? dither_threshold(c4, k) : 0.0f;
 
-    // which route (by the number of pixels the plan is made for), and how much scratch it needs: one block per plan
-    const uint64_t n_px = n_pixels_hint;
-    const bool meld_masks_pay = mode == KMG_MODE_MELD && k >= 2 && meld_pruning_pays(p, n_px, k);
-    const bool diffuse = mode == KMG_MODE_DIFFUSE;
-    const bool replace_table = diffuse ? diffuse_table_pays(p, n_px, k) : (mode != KMG_MODE_MELD && !dither && replace_table_pays(p, n_px, k));
-    const bool dither_pruned = mode != KMG_MODE_MELD && !diffuse && dither && dither_pruning_pays(p, n_px, k);
-    const bool ident = format != KMG_FORMAT_RGBA8 && dither_pruned && !dither_takes_lists(p, k);   // index output of kDitherMasks
-    const size_t tables_bytes = sizeof(Centroid) * k + sizeof(uint32_t) * (k + 1) * (ident ? 2u : 1u);
-    const size_t sub_bytes = sizeof(uint16_t) * (kSubCells + kCells) + sizeof(uint32_t) * kCells;
-    const size_t labels_bytes = (size_t)(k <= 256 ? 1 : 2) << 24;
-    const size_t masks_bytes = sizeof(uint64_t) * (size_t)kCells * mask_words(k) * (dither_pruned ? 16u : 1u);
+    // which route (by the number of pixels the plan is made for), and the scratch it needs: one block per plan
+    const bool mask_words_only = (p->strategy.load(std::memory_order_relaxed) & KMG_STRATEGY_MASK_WORDS) != 0;
+    pl->route = apply_route(mode, k, n_pixels_hint, forced_strategy(p), mask_words_only);
+    const RouteScratch scratch = route_scratch(pl->route, k, format != KMG_FORMAT_RGBA8);
+    const size_t cent_bytes = sizeof(Centroid) * k, pal_bytes = sizeof(uint32_t) * (k + 1);
+    const size_t tables_bytes = cent_bytes + pal_bytes * (scratch.ident ? 2u : 1u);
     size_t need = ArenaGuard::padded(tables_bytes);
-    const bool dither_lists = dither_pruned && dither_takes_lists(p, k);      // byte lists over Lab cells instead of mask words
-    const bool meld_lists = meld_masks_pay && dither_takes_lists(p, k);       // the same for the meld pass's two closest
-    if ((meld_masks_pay && !meld_lists) || (dither_pruned && !dither_lists)) need += ArenaGuard::padded(masks_bytes);
-    if (dither_lists || meld_lists) need += ArenaGuard::padded(lab_list_bytes(k));
-    if (replace_table) need += ArenaGuard::padded(labels_bytes) + ArenaGuard::padded(sub_bytes) + ArenaGuard::padded(cube_masks_bytes(k)) +
-                               ArenaGuard::padded(cube_work_bytes());
+    for (const size_t bytes : scratch.parts) need += ArenaGuard::padded(bytes);
     ArenaGuard &arena = pl->arena;
-    hipError_t e = arena.acquire(p, need);
+    HIP_TRY(arena.acquire(p, need));
     // centroid table and palette travel in one block (one copy)
     pl->staged.resize(tables_bytes);
-    memcpy(pl->staged.data(), hc.data(), sizeof(Centroid) * k);
-    memcpy(pl->staged.data() + sizeof(Centroid) * k, pal.data(), sizeof(uint32_t) * (k + 1));
-    if (ident) {
-        uint32_t *id = (uint32_t *)(pl->staged.data() + sizeof(Centroid) * k + sizeof(uint32_t) * (k + 1));
+    memcpy(pl->staged.data(), hc.data(), cent_bytes);
+    memcpy(pl->staged.data() + cent_bytes, pal.data(), pal_bytes);
+    if (scratch.ident) {
+        uint32_t *id = (uint32_t *)(pl->staged.data() + cent_bytes + pal_bytes);
         for (uint32_t i = 0; i <= k; ++i) id[i] = i;
     }
-    Centroid *d_cent = nullptr;
-    if (e == hipSuccess) {
-        d_cent = (Centroid *)arena.take(tables_bytes);
-        pl->d_cent = d_cent;
-        pl->d_pal = (uint32_t *)((uint8_t *)d_cent + sizeof(Centroid) * k);
-        if (ident) pl->d_ident = pl->d_pal + (k + 1);
-        e = hipMemcpyAsync(d_cent, pl->staged.data(), pl->staged.size(), hipMemcpyHostToDevice, S(stream));
-    }
-    int rc = KMG_OK;
-    if (e != hipSuccess) {
-        // fall through to the error report
-    } else if (mode == KMG_MODE_MELD) {
-        pl->route = kmg_apply_plan::kMeldScan;
-        if (meld_lists) {
-            uint8_t *lst = (uint8_t *)arena.take(lab_list_bytes(k));
-            e = launch_lab_candidates(d_cent, k, 0.0f, true, lst, S(stream));
-            pl->aux = lst; pl->route = kmg_apply_plan::kMeldLists;
-        } else if (meld_masks_pay) {
-            // large image: per colour cell, the centroids that can be one of a pixel's two closest
-            if ((rc = ensure_bounds(p, S(stream))) == KMG_OK) {
-                uint64_t *m = (uint64_t *)arena.take(masks_bytes);
-                e = launch_meld_candidates(p->d_bounds, d_cent, k, m, S(stream));
-                pl->aux = m; pl->route = kmg_apply_plan::kMeldMasks;
-            }
-        }
-    } else if (replace_table) {
+    Centroid *d_cent = pl->d_cent = (Centroid *)arena.take(tables_bytes);
+    pl->d_pal = (uint32_t *)((uint8_t *)d_cent + cent_bytes);
+    if (scratch.ident) pl->d_ident = pl->d_pal + (k + 1);
+    void *part[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (size_t i = 0; i < scratch.parts.size(); ++i) part[i] = arena.take(scratch.parts[i]);
+    pl->aux = part[0];
+    HIP_TRY(hipMemcpyAsync(d_cent, pl->staged.data(), pl->staged.size(), hipMemcpyHostToDevice, st));
+
+    switch (pl->route) {
+    case Route::kScan:
+    case Route::kMeldScan:
+    case Route::kDiffuseScan:                                          // every pixel scans all centroids: nothing to build
+        break;
+    case Route::kMeldLists:
+    case Route::kDitherLists:
+        // candidate lists per cell of a grid over Lab, then a scan of the pixel's candidates only (meld: whatever can be one of the
+        // two closest; its threshold is 0)
+        HIP_TRY(launch_lab_candidates(d_cent, k, pl->thr, mode == KMG_MODE_MELD, (uint8_t *)part[0], st));
+        break;
+    case Route::kMeldMasks:
+        // large image: per colour cell, the centroids that can be one of a pixel's two closest
+        KMG_TRY(ensure_bounds(p, st));
+        HIP_TRY(launch_meld_candidates(p->d_bounds, d_cent, k, (uint64_t *)part[0], st));
+        break;
+    case Route::kDitherMasks:
+        // dither on a large image above k = 512: mask words per (colour cell, Bayer index)
+        KMG_TRY(ensure_bounds(p, st));
+        HIP_TRY(launch_offset_candidates(p->d_bounds, d_cent, k, pl->thr, (uint64_t *)part[0], st));
+        break;
+    case Route::kReplaceTable:
+    case Route::kDiffuseTable:
         // replace mode on a large image: the label of a pixel depends on its colour only, so label the
         // colour cube once (candidate masks + cube pass without sums) and emit pal[label] through the
         // label tables -- the same bit-exact machinery as the Lloyd label pass
-        if ((rc = ensure_bounds(p, S(stream))) == KMG_OK) {
-            void *colour_labels = arena.take(labels_bytes);
-            uint16_t *sub = (uint16_t *)arena.take(sub_bytes);
-            uint64_t *m = (uint64_t *)arena.take(cube_masks_bytes(k));
-            void *cwork = arena.take(cube_work_bytes());
-            e = launch_cube(nullptr, nullptr, nullptr, nullptr, nullptr, p->d_bounds, p->d_sub_bounds, d_cent, k, p->d_lab_table,
-                            m, cwork, colour_labels, sub, nullptr, 0, 0u, nullptr, S(stream), nullptr, affine_for(p, k, S(stream)));
-            pl->aux = colour_labels; pl->sub = sub; pl->route = diffuse ? kmg_apply_plan::kDiffuseTable : kmg_apply_plan::kReplaceTable;
-        }
-    } else if (diffuse) {
-        pl->route = kmg_apply_plan::kDiffuseScan;
-    } else if (dither_pruned) {
-        // dither on a large image: candidate lists per cell of a grid over Lab (mask words per (colour cell, Bayer index)
-        // above k = 512), then a scan of the pixel's candidates only
-        if (dither_lists) {
-            uint8_t *lst = (uint8_t *)arena.take(lab_list_bytes(k));
-            e = launch_lab_candidates(d_cent, k, thr, false, lst, S(stream));
-            pl->aux = lst; pl->route = kmg_apply_plan::kDitherLists;
-        } else if ((rc = ensure_bounds(p, S(stream))) == KMG_OK) {
-            uint64_t *m = (uint64_t *)arena.take(masks_bytes);
-            e = launch_offset_candidates(p->d_bounds, d_cent, k, thr, m, S(stream));
-            pl->aux = m; pl->route = kmg_apply_plan::kDitherMasks;
-        }
+        KMG_TRY(ensure_bounds(p, st));
+        pl->sub = (uint16_t *)part[1];
+        HIP_TRY(launch_cube(labels_only_pass(p, d_cent, k, st, (uint64_t *)part[2], part[3], part[0], pl->sub), st));
+        break;
     }
-    if (rc != KMG_OK) return rc;
-    if (e == hipSuccess && diffuse) e = hipEventCreateWithFlags(&pl->ddone, hipEventDisableTiming);
-    if (e == hipSuccess && diffuse && (pl->h_slot = host_slot_take(p)) != nullptr) pl->h_timeout = static_cast<uint32_t *>(pl->h_slot);
-    if (e == hipSuccess && diffuse) *pl->h_timeout = 0;
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->ready, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(pl->ready, S(stream));
-    if (e != hipSuccess) return fail_hip(e, "apply plan");
+    if (mode == KMG_MODE_DIFFUSE) {
+        HIP_TRY(hipEventCreateWithFlags(&pl->ddone, hipEventDisableTiming));
+        if ((pl->h_slot = host_slot_take(p)) != nullptr) pl->h_timeout = static_cast<uint32_t *>(pl->h_slot);
+        *pl->h_timeout = 0;
+    }
+    HIP_TRY(hipEventCreateWithFlags(&pl->ready, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(pl->ready, st));
     undo.pl = nullptr;
     *out = pl;
     return KMG_OK;
@@ -387,39 +328,41 @@ KMG_ABI_CATCH
 // KMG_MODE_DIFFUSE: one band of the diffusion.  The bands of one plan are consecutive rows of one image (row0 = the rows done
 // so far, the width unchanged); each run waits on the previous run's completion event, so bands issued on several streams still
 // execute in order, and each continues from the error row the previous one left in the plan's scratch.
-static int run_diffuse(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, void *d_out, hipStream_t st)
+static int check_diffuse_band(kmg_apply_plan *pl, uint32_t w, uint32_t row0)
 {
-    kmg_processor *p = pl->p;
     if (w > 0x7FFFFF00u) return fail(KMG_ERR_UNSUPPORTED, "diffusion needs a width below 2^31 - 256");
     if (row0 != pl->drows) return fail(KMG_ERR_INVALID_ARGUMENT, "diffusion band starts at row %u, the plan has done %u rows", row0, pl->drows);
     if (pl->drows && w != pl->dwidth) return fail(KMG_ERR_INVALID_ARGUMENT, "diffusion band has width %u, the image has %u", w, pl->dwidth);
     // an earlier band that timed out (the sticky word; known once a run after it has completed) fails every later run
     if (pl->drows && hipEventQuery(pl->ddone) == hipSuccess && *pl->h_timeout)
         return fail(KMG_ERR_HIP, "diffusion pass timed out");
+    return KMG_OK;
+}
+
+static hipError_t run_diffuse(kmg_apply_plan *pl, const uint32_t *src, uint32_t w, uint32_t rows, void *d_out, hipStream_t st)
+{
+    kmg_processor *p = pl->p;
     const size_t erow_bytes = sizeof(uint32_t) * 2 * 2 * (size_t)w;
-    const size_t sticky_off = (erow_bytes + 255) & ~(size_t)255, ctl_off = sticky_off + 16;
+    const size_t sticky_off = pad256(erow_bytes), ctl_off = sticky_off + 16;
     const size_t ctl_bytes = (diffuse_ctl_bytes() + 15) & ~(size_t)15;
     if (!pl->dstate) {
-        HIP_TRY(pool_alloc(p, &pl->dstate, ctl_off + ctl_bytes, st));
-        HIP_TRY(hipMemsetAsync((uint8_t *)pl->dstate + sticky_off, 0, 16, st));
+        HIP_PASS(pool_alloc(p, &pl->dstate, ctl_off + ctl_bytes, st));
+        HIP_PASS(hipMemsetAsync((uint8_t *)pl->dstate + sticky_off, 0, 16, st));
     }
     uint8_t *erow = (uint8_t *)pl->dstate, *ctl = erow + ctl_off;
     uint32_t *sticky = (uint32_t *)(erow + sticky_off);
-    HIP_TRY(hipStreamWaitEvent(st, pl->ready, 0));
-    if (pl->drows) HIP_TRY(hipStreamWaitEvent(st, pl->ddone, 0));
-    else HIP_TRY(hipMemsetAsync(erow + (size_t)pl->dparity * 8u * w, 0, 8u * (size_t)w, st));    // no row above the image
-    HIP_TRY(hipMemsetAsync(ctl, 0, ctl_bytes, st));
-    const bool table = pl->route == kmg_apply_plan::kDiffuseTable;
-    const int route = !table ? kDiffuseScan : (pl->k <= 256 ? kDiffusePairs : kDiffuseCells);
-    hipError_t e = launch_diffuse(route, (const uint32_t *)d_rgba, w, rows, d_out, erow, pl->dparity, ctl, sticky, pl->d_cent,
-                                  pl->k, p->d_lut, pl->d_pal, pl->aux, pl->sub, st, pl->alpha_cutoff, pl->format);
-    if (e == hipSuccess) e = hipMemcpyAsync((void *)pl->h_timeout, sticky, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipEventRecord(pl->ddone, st);
-    if (e != hipSuccess) return fail(KMG_ERR_HIP, "diffusion failed: %s", hipGetErrorString(e));
+    if (pl->drows) HIP_PASS(hipStreamWaitEvent(st, pl->ddone, 0));
+    else HIP_PASS(hipMemsetAsync(erow + (size_t)pl->dparity * 8u * w, 0, 8u * (size_t)w, st));    // no row above the image
+    HIP_PASS(hipMemsetAsync(ctl, 0, ctl_bytes, st));
+    const int kernel = pl->route != Route::kDiffuseTable ? kDiffuseScan : (pl->k <= 256 ? kDiffusePairs : kDiffuseCells);
+    HIP_PASS(launch_diffuse(kernel, src, w, rows, d_out, erow, pl->dparity, ctl, sticky, pl->d_cent, pl->k, p->d_lut, pl->d_pal, pl->aux,
+                            pl->sub, st, pl->alpha_cutoff, pl->format));
+    HIP_PASS(hipMemcpyAsync((void *)pl->h_timeout, sticky, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_PASS(hipEventRecord(pl->ddone, st));
     pl->dwidth = w;
     pl->drows += rows;
     pl->dparity = (pl->dparity + (rows + 63u) / 64u) & 1u;
-    return KMG_OK;
+    return hipSuccess;
 }
 
 void kmg::apply_plan_restart(kmg_apply_plan *pl)
@@ -444,43 +387,66 @@ try {
 }
 KMG_ABI_CATCH
 
-// Index output (kmg_output_format INDEX8 / INDEX16) of the routes other than diffusion: the index instantiations of the scan and
-// list kernels and the label-table kernel of kmg_index.hip write the label directly; the mask-word dither route runs its
-// unchanged kernel with the identity palette into stream-ordered u32 scratch, then narrows it (k_narrow_index).
-static int run_index(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, void *d_out, hipStream_t st)
+// The mask-word dither route.  RGBA8: its kernel lives in kmg_table.hip and knows no alpha, so k_alpha_merge follows in alpha mode
+// (DESIGN.md 4.6).  Index output: the unchanged kernel with the identity palette into stream-ordered u32 scratch, then narrowed
+// (k_narrow_index).
+static hipError_t run_dither_masks(kmg_apply_plan *pl, const uint32_t *src, uint32_t w, uint32_t rows, uint32_t row0, void *d_out, hipStream_t st)
 {
     kmg_processor *p = pl->p;
-    if (st != pl->built_on) HIP_TRY(hipStreamWaitEvent(st, pl->ready, 0));
     const uint64_t n_px = (uint64_t)w * rows;
-    const uint32_t k = pl->k;
-    const bool wide = pl->format == KMG_FORMAT_INDEX16;
-    const uint32_t *src = (const uint32_t *)d_rgba;
+    const uint64_t *masks = (const uint64_t *)pl->aux;
+    if (pl->format == KMG_FORMAT_RGBA8) {
+        HIP_PASS(launch_dither_pruned(src, w, rows, row0, pl->d_cent, pl->k, p->d_lut, pl->d_pal, pl->thr, masks, (uint32_t *)d_out, st));
+        return pl->alpha_cutoff ? launch_alpha_merge(src, (uint32_t *)d_out, n_px, st) : hipSuccess;
+    }
+    StreamBuf lab;                                                    // (freed in stream order when this returns)
+    HIP_PASS(lab.alloc(p, sizeof(uint32_t) * n_px, st));
+    HIP_PASS(launch_dither_pruned(src, w, rows, row0, pl->d_cent, pl->k, p->d_lut, pl->d_ident, pl->thr, masks, (uint32_t *)lab.ptr, st));
+    return launch_narrow_index(src, (const uint32_t *)lab.ptr, n_px, pl->k, d_out, pl->format == KMG_FORMAT_INDEX16, st, pl->alpha_cutoff);
+}
+
+// One band by the plan's route.  RGBA8 in alpha mode: the source's alpha byte over the output's -- inside the kernel (its ALPHA
+// instantiation), or by k_alpha_merge after the two routes whose kernels live in kmg_table.hip.  Index output
+// (kmg_output_format INDEX8 / INDEX16): the index instantiations of the scan and list kernels and the label-table kernel of
+// kmg_index.hip write the label directly.
+static int run_band(kmg_apply_plan *pl, const uint32_t *src, uint32_t w, uint32_t rows, uint32_t row0, void *d_out, hipStream_t st)
+{
+    kmg_processor *p = pl->p;
+    const uint64_t n_px = (uint64_t)w * rows;
+    const uint32_t k = pl->k, cutoff = pl->alpha_cutoff;
+    const bool index = pl->format != KMG_FORMAT_RGBA8, wide = pl->format == KMG_FORMAT_INDEX16, alpha = cutoff != 0;
+    uint32_t *out = (uint32_t *)d_out;                                // (RGBA8)
     hipError_t e = hipSuccess;
     switch (pl->route) {
-    case kmg_apply_plan::kReplaceTable:
-        e = launch_labels_index(src, n_px, pl->aux, pl->sub, k, d_out, wide, st, pl->alpha_cutoff);
+    case Route::kScan:
+        e = index ? launch_apply_index(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->dither, pl->thr, d_out, wide, st, cutoff)
+                  : launch_apply(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->dither, pl->thr, out, st, alpha);
         break;
-    case kmg_apply_plan::kDitherLists:
-        e = launch_dither_lists_index(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->thr, (const uint8_t *)pl->aux, d_out, wide, st,
-                                      pl->alpha_cutoff);
+    case Route::kReplaceTable:
+        if (index) e = launch_labels_index(src, n_px, pl->aux, pl->sub, k, d_out, wide, st, cutoff);
+        else if ((e = launch_labels(src, n_px, pl->aux, pl->sub, k, pl->d_pal, out, st)) == hipSuccess && alpha)
+            e = launch_alpha_merge(src, out, n_px, st);
         break;
-    case kmg_apply_plan::kDitherMasks: {
-        void *lab = nullptr;
-        HIP_TRY(pool_alloc(p, &lab, sizeof(uint32_t) * n_px, st));
-        e = launch_dither_pruned(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_ident, pl->thr, (const uint64_t *)pl->aux, (uint32_t *)lab, st);
-        if (e == hipSuccess) e = launch_narrow_index(src, (const uint32_t *)lab, n_px, k, d_out, wide, st, pl->alpha_cutoff);
-        const hipError_t e2 = hipFreeAsync(lab, st);
-        if (e == hipSuccess) e = e2;
+    case Route::kDitherLists:
+        e = index ? launch_dither_lists_index(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->thr, (const uint8_t *)pl->aux, d_out, wide, st, cutoff)
+                  : launch_dither_lists(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->thr, (const uint8_t *)pl->aux, out, st, alpha);
+        break;
+    case Route::kDitherMasks:
+        e = run_dither_masks(pl, src, w, rows, row0, d_out, st);
+        break;
+    case Route::kMeldLists:
+    case Route::kMeldMasks:
+    case Route::kMeldScan:
+        if (index) return fail(KMG_ERR_INVALID_ARGUMENT, "the plan's route has no index output");   // (meld: refused at create)
+        e = pl->route == Route::kMeldLists ? launch_meld_lists(src, n_px, pl->d_cent, k, p->d_lut, (const uint8_t *)pl->aux, out, st, alpha)
+                                           : launch_meld(src, n_px, pl->d_cent, k, p->d_lut, (const uint64_t *)pl->aux, out, st, alpha);
+        break;
+    case Route::kDiffuseTable:
+    case Route::kDiffuseScan:
+        e = run_diffuse(pl, src, w, rows, d_out, st);
         break;
     }
-    case kmg_apply_plan::kScan:
-        e = launch_apply_index(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->dither, pl->thr, d_out, wide, st, pl->alpha_cutoff);
-        break;
-    default:
-        return fail(KMG_ERR_INVALID_ARGUMENT, "the plan's route has no index output");
-    }
-    if (e != hipSuccess) return fail(KMG_ERR_HIP, "apply failed: %s", hipGetErrorString(e));
-    return KMG_OK;
+    return e == hipSuccess ? KMG_OK : fail_hip(e, "apply");
 }
 
 extern "C" int kmg_apply_plan_run(kmg_apply_plan *pl, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, uint8_t *d_out,
@@ -491,46 +457,12 @@ try {
     if ((uint64_t)w * rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
     if (pl->format == KMG_FORMAT_INDEX16 && (reinterpret_cast<uintptr_t>(d_out) & 1u))
         return fail(KMG_ERR_INVALID_ARGUMENT, "INDEX16 output must be 2-byte aligned");
-    kmg_processor *p = pl->p;
-    HIP_TRY(hipSetDevice(p->device));
-    if (pl->mode == KMG_MODE_DIFFUSE) return run_diffuse(pl, d_rgba, w, rows, row0, d_out, S(stream));
-    if (pl->format != KMG_FORMAT_RGBA8) return run_index(pl, d_rgba, w, rows, row0, d_out, S(stream));
-    if (S(stream) != pl->built_on) HIP_TRY(hipStreamWaitEvent(S(stream), pl->ready, 0));      // (another stream: after the tables)
-    const uint64_t n_px = (uint64_t)w * rows;
-    const uint32_t k = pl->k;
-    // alpha mode: the source's alpha byte over the output's -- inside the kernel (its ALPHA instantiation), or by k_alpha_merge after
-    // the two routes whose kernels live in kmg_table.hip
-    const bool alpha = pl->alpha_cutoff != 0;
-    hipError_t e = hipSuccess;
-    switch (pl->route) {
-    case kmg_apply_plan::kMeldLists:
-        e = launch_meld_lists((const uint32_t *)d_rgba, n_px, pl->d_cent, k, p->d_lut, (const uint8_t *)pl->aux, (uint32_t *)d_out, S(stream),
-                              alpha);
-        break;
-    case kmg_apply_plan::kMeldMasks:
-    case kmg_apply_plan::kMeldScan:
-        e = launch_meld((const uint32_t *)d_rgba, n_px, pl->d_cent, k, p->d_lut, (const uint64_t *)pl->aux, (uint32_t *)d_out, S(stream),
-                        alpha);
-        break;
-    case kmg_apply_plan::kReplaceTable:
-        e = launch_labels((const uint32_t *)d_rgba, n_px, pl->aux, pl->sub, k, pl->d_pal, (uint32_t *)d_out, S(stream));
-        if (e == hipSuccess && alpha) e = launch_alpha_merge((const uint32_t *)d_rgba, (uint32_t *)d_out, n_px, S(stream));
-        break;
-    case kmg_apply_plan::kDitherLists:
-        e = launch_dither_lists((const uint32_t *)d_rgba, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->thr, (const uint8_t *)pl->aux,
-                                (uint32_t *)d_out, S(stream), alpha);
-        break;
-    case kmg_apply_plan::kDitherMasks:
-        e = launch_dither_pruned((const uint32_t *)d_rgba, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->thr, (const uint64_t *)pl->aux,
-                                 (uint32_t *)d_out, S(stream));
-        if (e == hipSuccess && alpha) e = launch_alpha_merge((const uint32_t *)d_rgba, (uint32_t *)d_out, n_px, S(stream));
-        break;
-    default:
-        e = launch_apply((const uint32_t *)d_rgba, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->dither, pl->thr, (uint32_t *)d_out,
-                         S(stream), alpha);
-    }
-    if (e != hipSuccess) return fail(KMG_ERR_HIP, "apply failed: %s", hipGetErrorString(e));
-    return KMG_OK;
+    HIP_TRY(hipSetDevice(pl->p->device));
+    const bool diffuse = pl->mode == KMG_MODE_DIFFUSE;
+    if (diffuse) KMG_TRY(check_diffuse_band(pl, w, row0));
+    // after the tables: diffusion always waits, the others only on another stream than the one that builds them
+    if (diffuse || S(stream) != pl->built_on) HIP_TRY(hipStreamWaitEvent(S(stream), pl->ready, 0));
+    return run_band(pl, (const uint32_t *)d_rgba, w, rows, row0, d_out, S(stream));
 }
 KMG_ABI_CATCH
 
@@ -553,16 +485,14 @@ int kmg::dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t
         return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply arguments");
     if ((uint64_t)w * rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
     kmg_apply_plan *pl = nullptr;
-    int rc = plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, alpha_cutoff, &pl, format);
-    if (rc != KMG_OK) return rc;
+    KMG_TRY(plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, alpha_cutoff, &pl, format));
     // (diffusion: the band is an image of its own -- the plan is new, so its first run starts from a zero error row)
-    rc = kmg_apply_plan_run(pl, d_rgba, w, rows, mode == KMG_MODE_DIFFUSE ? 0u : row0, d_out, stream);
+    int rc = kmg_apply_plan_run(pl, d_rgba, w, rows, mode == KMG_MODE_DIFFUSE ? 0u : row0, d_out, stream);
     const hipError_t e2 = hipStreamSynchronize(S(stream));            // the call returns when the band is written; the block is idle again
     if (rc == KMG_OK && e2 == hipSuccess) rc = diffuse_status(pl);
     kmg_apply_plan_destroy(pl, 0);
     if (rc != KMG_OK) return rc;
-    if (e2 != hipSuccess) return fail(KMG_ERR_HIP, "apply failed: %s", hipGetErrorString(e2));
-    return KMG_OK;
+    return e2 == hipSuccess ? KMG_OK : fail_hip(e2, "apply");
 }
 
 extern "C" int kmg_dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0,

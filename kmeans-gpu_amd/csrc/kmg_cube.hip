@@ -2179,15 +2179,14 @@ bool cube_single_launch(uint32_t k, uint32_t flags)
     return k <= kSmallMaxK || (k <= 256u && !(flags & kCubeHot));
 }
 
-hipError_t launch_cube(const uint32_t *hist, const int64_t *agg, const int64_t *sub_agg, const uint8_t *occ_bits,
-                       const uint32_t *work, const CellBounds *bounds, const CellBounds *sub_bounds, const Centroid *cent,
-                       uint32_t k, const float4 *lab_table, uint64_t *masks, void *cell_work, void *colour_labels,
-                       uint16_t *sub_table, int64_t *sums, uint32_t n_rows, uint32_t flags, unsigned long long *stats,
-                       hipStream_t st, const CubeTail *tail, const float *sub_affine, const CubeBalance *balance)
+hipError_t launch_cube(const CubePass &c, hipStream_t st)
 {
-    const CubeTail tl = (tail && hist && n_rows <= 1u) ? *tail : CubeTail();
+    const uint32_t k = c.k;
+    uint32_t n_rows = c.n_rows, flags = c.flags;                      // (0 rows count as one; kCubeSplitLong is added below)
+    const CubeBalance *balance = c.balance;
+    const CubeTail tl = (c.tail && c.hist && n_rows <= 1u) ? *c.tail : CubeTail();
     const uint32_t kpad = (k + 63u) & ~63u;
-    const bool with_sums = hist != nullptr;
+    const bool with_sums = c.hist != nullptr;
     const uint32_t repl = with_sums ? cube_replicas(k) : 1u;
     const size_t lds_stage = sizeof(float4) * kpad + (with_sums ? sizeof(unsigned long long) * 4ull * k : 0) +
                              sizeof(uint32_t) * (kBlock / 64) * kMaxListed + sizeof(unsigned long long) * (kBlock / 64) * (kpad / 64u) +
@@ -2213,9 +2212,9 @@ hipError_t launch_cube(const uint32_t *hist, const int64_t *agg, const int64_t *
         static const bool split = tools_env_int(KMG_TOOLS_ENV("KMG_CUBE_SMALL"), 1) == 2;
         const uint32_t sflags = (flags & ~0x100u) | (split ? kSmallEmit : 0u);
 #define KMG_SMALL(KP, S)                                                                                                    \
-        hipLaunchKernelGGL((k_cube_small<KP, S>), dim3(g_small), dim3(kSmallBlock), lds, st, hist, agg, sub_agg, occ_bits,   \
-                           work, bounds, sub_bounds, sub_affine, cent, k, lab_table, masks, (CellWork *)cell_work,            \
-                           (uint8_t *)colour_labels, sub_table, sums, n_rows, sflags, stats)
+        hipLaunchKernelGGL((k_cube_small<KP, S>), dim3(g_small), dim3(kSmallBlock), lds, st, c.hist, c.agg, c.sub_agg,       \
+                           c.occ_bits, c.work, c.bounds, c.sub_bounds, c.sub_affine, c.cent, k, c.lab_table, c.masks,       \
+                           (CellWork *)c.cell_work, (uint8_t *)c.colour_labels, c.sub_table, c.sums, n_rows, sflags, c.stats)
         if (with_sums) { if (kp == 8u) KMG_SMALL(8, true); else if (kp == 16u) KMG_SMALL(16, true); else KMG_SMALL(32, true); }
         else           { if (kp == 8u) KMG_SMALL(8, false); else if (kp == 16u) KMG_SMALL(16, false); else KMG_SMALL(32, false); }
 #undef KMG_SMALL
@@ -2225,18 +2224,18 @@ hipError_t launch_cube(const uint32_t *hist, const int64_t *agg, const int64_t *
             const size_t lds_scan2 = sizeof(float4) * kpad2 + (with_sums ? sizeof(unsigned long long) * (4ull * k + 4ull) * repl2 : 0) +
                                      sizeof(float4) * (kScanBlock / 64) * kMaxListed + (kScanBlock / 64) * kCellColours;
             if (with_sums)
-                hipLaunchKernelGGL((k_cube_scan<uint8_t, true>), dim3(g_scan2), dim3(kScanBlock), lds_scan2, st, hist, sub_agg, work, cent, k,
-                                   lab_table, masks, (const CellWork *)cell_work, (uint8_t *)colour_labels, sub_table, sums, n_rows, repl2, flags);
+                hipLaunchKernelGGL((k_cube_scan<uint8_t, true>), dim3(g_scan2), dim3(kScanBlock), lds_scan2, st, c.hist, c.sub_agg, c.work, c.cent, k,
+                                   c.lab_table, c.masks, (const CellWork *)c.cell_work, (uint8_t *)c.colour_labels, c.sub_table, c.sums, n_rows, repl2, flags);
             else
-                hipLaunchKernelGGL((k_cube_scan<uint8_t, false>), dim3(g_scan2), dim3(kScanBlock), lds_scan2, st, hist, sub_agg, work, cent, k,
-                                   lab_table, masks, (const CellWork *)cell_work, (uint8_t *)colour_labels, sub_table, sums, n_rows, repl2, flags);
-            hipLaunchKernelGGL((k_cube_pairs<uint8_t>), dim3((flags & kCubeNoEntries) ? 1u : g_pairs2), dim3(kBlock), 0, st, work,
-                               with_sums ? 1 : 0, occ_bits, (const uint8_t *)colour_labels, sub_table, flags, sums, k, tl);
+                hipLaunchKernelGGL((k_cube_scan<uint8_t, false>), dim3(g_scan2), dim3(kScanBlock), lds_scan2, st, c.hist, c.sub_agg, c.work, c.cent, k,
+                                   c.lab_table, c.masks, (const CellWork *)c.cell_work, (uint8_t *)c.colour_labels, c.sub_table, c.sums, n_rows, repl2, flags);
+            hipLaunchKernelGGL((k_cube_pairs<uint8_t>), dim3((flags & kCubeNoEntries) ? 1u : g_pairs2), dim3(kBlock), 0, st, c.work,
+                               with_sums ? 1 : 0, c.occ_bits, (const uint8_t *)c.colour_labels, c.sub_table, flags, c.sums, k, tl);
             return hipGetLastError();
         }
         if (tl.acc_out)
-            hipLaunchKernelGGL((k_cube_pairs<uint8_t>), dim3(1), dim3(kBlock), 0, st, work, 1, occ_bits,
-                               (const uint8_t *)colour_labels, sub_table, flags | kCubeNoEntries, sums, k, tl);
+            hipLaunchKernelGGL((k_cube_pairs<uint8_t>), dim3(1), dim3(kBlock), 0, st, c.work, 1, c.occ_bits,
+                               (const uint8_t *)c.colour_labels, c.sub_table, flags | kCubeNoEntries, c.sums, k, tl);
         return hipGetLastError();
     }
     // 32 < k <= 256 without hot cells: the whole pass in one launch (k_cube_one) + the tail workgroup
@@ -2248,39 +2247,41 @@ hipError_t launch_cube(const uint32_t *hist, const int64_t *agg, const int64_t *
         static const bool balance_on = tools_env_int(KMG_TOOLS_ENV("KMG_BALANCE"), 1) != 0;      // (tools build: 0 = the fixed deal)
         if (!balance_on) balance = nullptr;
         if (with_sums)
-            hipLaunchKernelGGL((k_cube_one<true>), dim3(kCells / kOneCells), dim3(kOneBlock), lds, st, hist, agg, sub_agg, occ_bits, work, bounds,
-                               sub_bounds, sub_affine, cent, k, lab_table, masks, (uint8_t *)colour_labels, sub_table, sums, n_rows, flags, stats,
+            hipLaunchKernelGGL((k_cube_one<true>), dim3(kCells / kOneCells), dim3(kOneBlock), lds, st, c.hist, c.agg, c.sub_agg, c.occ_bits, c.work, c.bounds,
+                               c.sub_bounds, c.sub_affine, c.cent, k, c.lab_table, c.masks, (uint8_t *)c.colour_labels, c.sub_table, c.sums, n_rows, flags, c.stats,
                                balance ? balance->state : nullptr, balance ? balance->pass : 0u);
         else
-            hipLaunchKernelGGL((k_cube_one<false>), dim3(kCells / kOneCells), dim3(kOneBlock), lds, st, hist, agg, sub_agg, occ_bits, work, bounds,
-                               sub_bounds, sub_affine, cent, k, lab_table, masks, (uint8_t *)colour_labels, sub_table, sums, n_rows, flags, stats,
+            hipLaunchKernelGGL((k_cube_one<false>), dim3(kCells / kOneCells), dim3(kOneBlock), lds, st, c.hist, c.agg, c.sub_agg, c.occ_bits, c.work, c.bounds,
+                               c.sub_bounds, c.sub_affine, c.cent, k, c.lab_table, c.masks, (uint8_t *)c.colour_labels, c.sub_table, c.sums, n_rows, flags, c.stats,
                                (uint16_t *)nullptr, 0u);
         if (tl.acc_out)
-            hipLaunchKernelGGL((k_cube_pairs<uint8_t>), dim3(1), dim3(kBlock), 0, st, work, 1, occ_bits,
-                               (const uint8_t *)colour_labels, sub_table, flags | kCubeNoEntries, sums, k, tl);
+            hipLaunchKernelGGL((k_cube_pairs<uint8_t>), dim3(1), dim3(kBlock), 0, st, c.work, 1, c.occ_bits,
+                               (const uint8_t *)c.colour_labels, c.sub_table, flags | kCubeNoEntries, c.sums, k, tl);
         return hipGetLastError();
     }
     // (the scan kernel's cells differ a lot in cost: finer hand-out, 2 cells per wave, measured 83 -> 75 us)
     // (stage: 1536 workgroups = one full round at its 6 waves per SIMD: 33 -> 30-31 us against 2048, round 3)
     static const uint32_t g_stage = env_grid("KMG_CUBE_GRID", 1536u), g_scan = env_grid("KMG_SCAN_GRID", kCubeGrid),
                           g_pairs = env_grid("KMG_PAIRS_GRID", kCubeGrid);
-    CellWork *cw = (CellWork *)cell_work;
+    CellWork *cw = (CellWork *)c.cell_work;
     if (!n_rows) n_rows = 1u;
     if (k <= 256u && tools_env_int(KMG_TOOLS_ENV("KMG_SPLIT_LONG"), 1) != 0) {
         // (the stage kernel's workgroups append to the list of long-list cells as they meet them: its counters are cleared ahead of
         // the launch, not by one of its workgroups)
         flags |= kCubeSplitLong;
-        hipError_t e = hipMemsetAsync(reinterpret_cast<uint32_t *>((CellWork *)cell_work + kCells) + kLongCount, 0, sizeof(uint32_t) * kLongSegs, st);
+        hipError_t e = hipMemsetAsync(reinterpret_cast<uint32_t *>((CellWork *)c.cell_work + kCells) + kLongCount, 0, sizeof(uint32_t) * kLongSegs, st);
         if (e != hipSuccess) return e;
     }
 #define KMG_CUBE(T, S)                                                                                                      \
     do {                                                                                                                    \
-        hipLaunchKernelGGL((k_cube_stage<T, S>), dim3(g_stage), dim3(kBlock), lds_stage, st, agg, sub_agg, work, bounds,     \
-                           sub_bounds, cent, k, masks, cw, (T *)colour_labels, sub_table, sums, n_rows, flags, stats);      \
-        hipLaunchKernelGGL((k_cube_scan<T, S>), dim3(g_scan), dim3(kScanBlock), lds_scan, st, hist, sub_agg, work, cent, k,   \
-                           lab_table, masks, cw, (T *)colour_labels, sub_table, sums, n_rows, repl, flags);                 \
-        hipLaunchKernelGGL((k_cube_pairs<T>), dim3((flags & kCubeNoEntries) ? 1u : g_pairs), dim3(kBlock), 0, st, work,   \
-                           S ? 1 : 0, occ_bits, (const T *)colour_labels, sub_table, flags, sums, k, tl);                   \
+        hipLaunchKernelGGL((k_cube_stage<T, S>), dim3(g_stage), dim3(kBlock), lds_stage, st, c.agg, c.sub_agg, c.work,      \
+                           c.bounds, c.sub_bounds, c.cent, k, c.masks, cw, (T *)c.colour_labels, c.sub_table, c.sums,       \
+                           n_rows, flags, c.stats);                                                                         \
+        hipLaunchKernelGGL((k_cube_scan<T, S>), dim3(g_scan), dim3(kScanBlock), lds_scan, st, c.hist, c.sub_agg, c.work,    \
+                           c.cent, k, c.lab_table, c.masks, cw, (T *)c.colour_labels, c.sub_table, c.sums, n_rows, repl,    \
+                           flags);                                                                                          \
+        hipLaunchKernelGGL((k_cube_pairs<T>), dim3((flags & kCubeNoEntries) ? 1u : g_pairs), dim3(kBlock), 0, st, c.work,   \
+                           S ? 1 : 0, c.occ_bits, (const T *)c.colour_labels, c.sub_table, flags, c.sums, k, tl);           \
     } while (0)
     if (k <= 256) { if (with_sums) KMG_CUBE(uint8_t, true); else KMG_CUBE(uint8_t, false); }
     else          { if (with_sums) KMG_CUBE(uint16_t, true); else KMG_CUBE(uint16_t, false); }

@@ -84,9 +84,15 @@ static hipError_t cube_pass(kmg_lloyd *s, hipStream_t st, int64_t *d_sums, uint3
     const uint32_t *work = share ? share_or_work(t) : t.d_work;
     CubeBalance bal;
     if (balance) bal = next_balance(t, work);
-    return launch_cube(t.d_hist, t.d_agg, t.d_sub_agg, t.d_occ, work, s->p->d_bounds, s->p->d_sub_bounds, s->d_cent, s->k, s->p->d_lab_table,
-                       t.d_masks, t.d_cell_work, t.d_colour_labels, t.d_sub, d_sums, rows, flags | hot_flag(t), d_stage, st, tail,
-                       affine_for(s->p, s->k, st), balance ? &bal : nullptr);
+    CubePass c;
+    c.hist = t.d_hist; c.agg = t.d_agg; c.sub_agg = t.d_sub_agg; c.occ_bits = t.d_occ; c.work = work;
+    c.bounds = s->p->d_bounds; c.sub_bounds = s->p->d_sub_bounds; c.lab_table = s->p->d_lab_table;
+    c.cent = s->d_cent; c.k = s->k;
+    c.masks = t.d_masks; c.cell_work = t.d_cell_work; c.colour_labels = t.d_colour_labels; c.sub_table = t.d_sub;
+    c.sums = d_sums; c.n_rows = rows; c.flags = flags | hot_flag(t); c.stats = d_stage; c.tail = tail;
+    c.sub_affine = affine_for(s->p, s->k, st);
+    c.balance = balance ? &bal : nullptr;
+    return launch_cube(c, st);
 }
 
 // The label pass: the per-pixel label map from the current label tables.  tail / acc: the pass's last workgroup also runs a CubeTail
@@ -467,12 +473,11 @@ try {
     HIP_TRY(cwork.alloc(cube_work_bytes()));
     HIP_TRY(viol.alloc(3 * sizeof(unsigned long long)));
     HIP_TRY(labels.alloc((size_t)(s->k <= 256 ? 1 : 2) << 24));
-    HIP_TRY(sub.alloc(sizeof(uint16_t) * (kSubCells + kCells) + sizeof(uint32_t) * kCells));
+    HIP_TRY(sub.alloc(sub_table_bytes()));
     HIP_TRY(hipMemsetAsync(viol.ptr, 0, 3 * sizeof(unsigned long long), S(stream)));
-    // (no image, buffers of its own: the one cube launch that is not cube_pass)
-    HIP_TRY(launch_cube(nullptr, nullptr, nullptr, nullptr, nullptr, s->p->d_bounds, s->p->d_sub_bounds, s->d_cent, s->k,
-                        s->p->d_lab_table, (uint64_t *)masks.ptr, cwork.ptr, labels.ptr, (uint16_t *)sub.ptr, nullptr, 0, 1u, nullptr,
-                        S(stream), nullptr, affine_for(s->p, s->k, S(stream))));
+    // (no image, buffers of its own: the one cube launch that is not cube_pass; flag 1: the labels of single-candidate cells too)
+    HIP_TRY(launch_cube(labels_only_pass(s->p, s->d_cent, s->k, S(stream), (uint64_t *)masks.ptr, cwork.ptr, labels.ptr, (uint16_t *)sub.ptr, 1u),
+                        S(stream)));
     HIP_TRY(launch_check_bounds(s->p->d_bounds, s->p->d_sub_bounds, s->d_cent, s->k, (const uint64_t *)masks.ptr, labels.ptr,
                                 s->p->d_lut, (unsigned long long *)viol.ptr, S(stream)));
     unsigned long long h[3];

@@ -319,3 +319,17 @@ int ensure_bounds(kmg_processor *p, hipStream_t st);
 const float *affine_for(kmg_processor *p, uint32_t k, hipStream_t st);
 int lloyd_create_impl(kmg_processor *p, uint32_t k, kmg_lloyd **out, hipStream_t pool_stream);
 static inline size_t sub_table_bytes() { return sizeof(uint16_t) * (kSubCells + kCells) + sizeof(uint32_t) * kCells; }
+
+// The cube pass without an image (kmg_table.h CubePass): the per-colour labels (2^24 x u8 for k <= 256, else u16) and the first-level
+// tables (sub_table_bytes()) of a centroid table over all 2^24 colours, no sums.  After ensure_bounds; masks: cube_masks_bytes(k),
+// cell_work: cube_work_bytes().
+static inline CubePass labels_only_pass(kmg_processor *p, const Centroid *cent, uint32_t k, hipStream_t st, uint64_t *masks, void *cell_work,
+                                        void *colour_labels, uint16_t *sub_table, uint32_t flags = 0u)
+{
+    CubePass c;
+    c.bounds = p->d_bounds; c.sub_bounds = p->d_sub_bounds; c.lab_table = p->d_lab_table; c.sub_affine = affine_for(p, k, st);
+    c.cent = cent; c.k = k;
+    c.masks = masks; c.cell_work = cell_work; c.colour_labels = colour_labels; c.sub_table = sub_table;
+    c.flags = flags;
+    return c;
+}

@@ -187,17 +187,8 @@ hipError_t launch_init_cells_multi(const uint32_t *tie, const uint8_t *occ_bits,
                                    hipStream_t st);
 const uint32_t *init_cells_multi_count(const void *init_scratch, uint32_t launch);
 // per iteration (kmg_cube.hip): candidates + sub-cell stage, dominance tests, colour scan, pair entries -- ONE launch for k <= 256
-// on images without hot cells (k_cube_small, k_cube_one), three otherwise (k_cube_stage, k_cube_scan, k_cube_pairs).
-// work: [0] = number of occupied cells of the bound image, [1..] = their indices (built at bind time).
-// masks: the cell candidate masks, mask_words(k) u64 per cell; cell_work: cube_work_bytes() of scratch (the
-// stage kernel's records for the scan kernel and, behind them, its list of cells with long candidate lists).
-// Every workgroup adds the sums of the clusters it met into row (workgroup % n_rows) of `sums` (k x 4 int64
-// per row, zero on entry; n_rows = 1: the final sums).  hist == NULL: output pass of replace mode -- every
-// colour of every cell is labelled, nothing is accumulated (agg, sub_agg, occ_bits, work, sums unused).
-// flags bit 0: also write the per-colour labels of single-candidate cells (the label passes never read them).
-// stats (optional, 8 x u64, zero on entry): single-candidate cells, other cells, sub-cells decided by their
-// bounds, sub-cells scanned, candidates summed over the scanned sub-cells, cells beyond the listing limit, candidates the
-// dominance phase removed, scanned sub-cells it left with one candidate.
+// on images without hot cells (k_cube_small, k_cube_one), three otherwise (k_cube_stage, k_cube_scan, k_cube_pairs).  What a pass
+// takes: struct CubePass below.
 size_t cube_work_bytes();
 // flags bit 16: the pass leaves the cells' pair entries / summaries (what the LABEL pass reads first) to a later
 // launch_cube_entries -- a loop that only needs the sums (kmg_lloyd_run) pays for them once, after its last iteration
@@ -232,12 +223,37 @@ struct CubeBalance {
     uint32_t pass = 0;
 };
 size_t cube_balance_bytes();
-hipError_t launch_cube(const uint32_t *hist, const int64_t *agg, const int64_t *sub_agg, const uint8_t *occ_bits,
-                       const uint32_t *work, const CellBounds *bounds, const CellBounds *sub_bounds, const Centroid *cent,
-                       uint32_t k, const float4 *lab_table, uint64_t *masks, void *cell_work, void *colour_labels,
-                       uint16_t *sub_table, int64_t *sums, uint32_t n_rows, uint32_t flags, unsigned long long *stats,
-                       hipStream_t st, const CubeTail *tail = nullptr, const float *sub_affine = nullptr,
-                       const CubeBalance *balance = nullptr);
+// One cube pass by its arguments' names.  A bound image's pass fills all of it (cube_pass of kmg_lloyd.hip); a pass without an image
+// -- hist == NULL: the output pass of replace mode, every colour of every cell is labelled, nothing is accumulated -- leaves agg,
+// sub_agg, occ_bits, work and sums NULL (labels_only_pass of kmg_state.h).
+struct CubePass {
+    const uint32_t *hist = nullptr;          // 2^24 counts of the bound image, or NULL: no image, no sums
+    const int64_t *agg = nullptr;            // kCells x 4 per-cell sums of the image
+    const int64_t *sub_agg = nullptr;        // kSubCells x 4 per-sub-cell sums of the image
+    const uint8_t *occ_bits = nullptr;       // 2^24 bits: colours the image has pixels of
+    const uint32_t *work = nullptr;          // [0] = number of occupied cells of the bound image, [1..] = their indices (built at bind time)
+    const CellBounds *bounds = nullptr;      // kCells static cell bounds (once per processor)
+    const CellBounds *sub_bounds = nullptr;  // kSubCells static bounds of the 4x4x4 sub-cells
+    const Centroid *cent = nullptr;          // k centroids
+    uint32_t k = 0;
+    const float4 *lab_table = nullptr;       // 2^24 x (L, a, b, C): Lab of every colour
+    uint64_t *masks = nullptr;               // cube_masks_bytes(k): the cell candidate masks, mask_words(k) u64 per cell
+    void *cell_work = nullptr;               // cube_work_bytes() of scratch: the stage kernel's records for the scan kernel and, behind
+                                             // them, its list of cells with long candidate lists
+    void *colour_labels = nullptr;           // out: 2^24 x u8 (k <= 256) or u16
+    uint16_t *sub_table = nullptr;           // out: the label pass's first-level tables (sub_table_bytes() of kmg_state.h)
+    int64_t *sums = nullptr;                 // every workgroup adds the sums of the clusters it met into row (workgroup % n_rows) of
+    uint32_t n_rows = 0;                     // `sums` (k x 4 int64 per row, zero on entry; n_rows = 1: the final sums)
+    uint32_t flags = 0;                      // bit 0: also write the per-colour labels of single-candidate cells (the label passes never
+                                             // read them); kCubeNoEntries, kCubeHot above
+    unsigned long long *stats = nullptr;     // optional, 8 x u64, zero on entry: single-candidate cells, other cells, sub-cells decided by
+                                             // their bounds, sub-cells scanned, candidates summed over the scanned sub-cells, cells beyond the
+                                             // listing limit, candidates the dominance phase removed, scanned sub-cells it left with one candidate
+    const CubeTail *tail = nullptr;          // what the pass's last launch does on top (hist != NULL, n_rows <= 1)
+    const float *sub_affine = nullptr;       // optional, below
+    const CubeBalance *balance = nullptr;    // optional: the one-launch pass continues a loop's load balance
+};
+hipError_t launch_cube(const CubePass &pass, hipStream_t st);
 // sub_affine (optional, once per processor, sub_affine_bytes() = 24 MiB, image independent; k_cube_small and k_cube_one use it):
 // per sub-cell affine models (binary16) of the seven per-colour features the difference of two keys is linear in, with exact
 // residual ranges -- the dominance test that removes, from a sub-cell's candidates, those another candidate beats on every

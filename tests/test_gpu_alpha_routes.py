@@ -1,16 +1,17 @@
 """Alpha mode (kmg_options.alpha_cutoff) on every route of the output pass, bit for bit against tests/alpha_ref.py.
 
-With a forced strategy the route follows from (strategy, k, mode) alone: `forced_strategy` short-circuits every `*_pays` cost model
-of csrc/kmg_apply.hip (except `diffuse_table_pays`, which answers false for k < 2 before it looks at the strategy), and
-`dither_takes_lists` is `!(strategy & KMG_STRATEGY_MASK_WORDS) && k <= kLabListMaxK (512)`.  From `plan_create`:
+With a forced strategy the route follows from (strategy, k, mode) alone: a `forced` of -1 or +1 (`forced_strategy` of the
+processor) short-circuits every `*_pays` cost model of csrc/kmg_apply_route.h (except `diffuse_table_pays`, which answers false for
+k < 2 before it looks at `forced`), and `dither_takes_lists` is `!mask_words && k <= kRouteListMaxK (512)` with `mask_words` =
+`strategy & KMG_STRATEGY_MASK_WORDS`.  From `apply_route`:
 
     dither         = mode == DITHER && k > 1
-    meld_masks_pay = mode == MELD && k >= 2 && meld_pruning_pays          -> kMeldLists if dither_takes_lists, else kMeldMasks
-    replace_table  = DIFFUSE ? diffuse_table_pays : mode != MELD && !dither && replace_table_pays  -> kReplaceTable / kDiffuseTable
-    dither_pruned  = mode != MELD && !DIFFUSE && dither && dither_pruning_pays -> kDitherLists if dither_takes_lists, else kDitherMasks
-    otherwise        kMeldScan (meld), kDiffuseScan (diffuse), the default k_apply route (replace, dither)
+    meld           : k >= 2 && meld_pruning_pays                          -> kMeldLists if dither_takes_lists, else kMeldMasks
+    colour table   : DIFFUSE ? diffuse_table_pays : !dither && replace_table_pays          -> kDiffuseTable / kReplaceTable
+    pruned dither  : dither && dither_pruning_pays                        -> kDitherLists if dither_takes_lists, else kDitherMasks
+    otherwise        kMeldScan (meld), kDiffuseScan (diffuse), kScan: the default k_apply route (replace, dither)
 
-and from `kmg_apply_plan_run` / `run_diffuse` / the launchers: k_apply is chunked for k >= 32; the label tables are u8 for k <= 256,
+and from `run_band` / `run_diffuse` of csrc/kmg_apply.hip and the launchers: k_apply is chunked for k >= 32; the label tables are u8 for k <= 256,
 u16 above, and kReplaceTable / kDitherMasks are followed by k_alpha_merge in alpha mode; the Lab lists have two halves for k > 256;
 kDitherMasks launches k_dither_sorted for one mask word (k <= 64), else k_dither_pruned<W> with W = 1, 2, 4 words or 0 (any other
 count); kDiffuseTable runs kDiffusePairs for k <= 256 and kDiffuseCells above.

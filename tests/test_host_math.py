@@ -46,3 +46,15 @@ def test_colour_index_equals_its_plain_form_for_every_colour(tmp_path):
                     os.path.join(ROOT, "tests", "native", "check_colour_index.cpp"), "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and "colour_index_mismatches 0" in r.stdout and "inverse_mismatches 0" in r.stdout, r.stdout
+
+
+def test_apply_route_equals_the_recorded_decisions(tmp_path):
+    """csrc/kmg_apply_route.h apply_route gives the route recorded in tests/native/apply_route_table.txt for every (mode, k, n, forced,
+    mask_words) of the table: k and n on both sides of every constant the cost models compare with, and 1 % to either side of the
+    floating-point models' crossovers (tests/native/check_apply_route.cpp, host build of the same header)."""
+    exe = str(tmp_path / "check_apply_route")
+    native = os.path.join(ROOT, "tests", "native")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I", os.path.join(ROOT, "kmeans-gpu_amd", "csrc"),
+                    os.path.join(native, "check_apply_route.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe, os.path.join(native, "apply_route_table.txt")], capture_output=True, text=True)
+    assert r.returncode == 0 and "rows 264 " in r.stdout and "route_mismatches 0" in r.stdout, r.stdout + r.stderr
