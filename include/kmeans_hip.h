@@ -336,6 +336,63 @@ KMG_API int kmg_reduce_batch(kmg_processor *p, uint32_t n_images, const uint8_t 
                              const uint32_t *heights, uint32_t color_count, int algo, int mode, uint64_t max_resident_bytes,
                              uint8_t *const *out_rgba, kmg_batch_report *report);
 
+/* ---- batched output: find and indexed reduce for many small images ------------------------
+ * The output step of a batch in ONE launch for all its images (kmg_batch_apply.hip): a workgroup finds the image
+ * its tile belongs to and runs the per-pixel output pass on it with that image's width, threshold and tables.  kmg_palette_batch,
+ * kmg_reduce_batch and every per-image call keep their code paths and their bytes.
+ *
+ * Equivalence.  Image i receives exactly the bytes the per-image call writes for image i alone on the same processor:
+ * kmg_find_batch those of kmg_find_indexed, kmg_reduce_indexed_batch those of kmg_reduce_indexed (also the palette in index order
+ * and out_counts[i]), kmg_dev_apply_batch those of kmg_dev_apply_format; KMG_FORMAT_RGBA8 means the bytes of kmg_find / kmg_reduce.
+ * Neither the order of the batch, an image appearing twice, max_resident_bytes nor kmg_options.strategy changes any image's bytes.
+ *
+ * Which images join the launch.  Image i joins when the mode is KMG_MODE_REPLACE or KMG_MODE_DITHER and its own output plan would
+ * scan all centroids per pixel (the route kmg_dev_apply takes for a small image); in a batch of two images or more also a dither
+ * image with 128 .. 512 colours that a plan of its own sends to the candidate lists only for the latency of one image's scan
+ * (DESIGN.md 4.17).  Every other image -- KMG_MODE_MELD,
+ * KMG_MODE_DIFFUSE, an image large enough for the colour table, the candidate lists or the mask words, a forced
+ * KMG_STRATEGY_TABLE -- takes its own output pass inside the call and counts in `per_image`.  KMG_ALGO_OCTREE runs the host
+ * algorithm and the per-image output pass, as in kmg_reduce_batch (palette sizes differ per image): every image is `per_image`.
+ *
+ * max_resident_bytes: as for kmg_reduce_batch -- the source stays on the device until its output -- plus the bytes of the image's
+ * output (4, 1 or 2 per pixel); kmg_find_batch counts the source and the output.
+ *
+ * Refusals, KMG_ERR_INVALID_ARGUMENT unless stated, checked for the whole batch before anything is uploaded, in this order (the
+ * order of kmg_reduce_batch, continued): a NULL processor; n_images == 0; a NULL array; then per image in order a NULL entry or a
+ * zero dimension; k == 0 (color_count, n_colors or a NULL palette); an algorithm, mode or format out of range; k > KMG_MAX_K
+ * (KMG_ERR_UNSUPPORTED; kmg_reduce_indexed_batch: with k-means); the rules of the index formats -- KMG_MODE_MELD has no index,
+ * KMG_FORMAT_INDEX8 needs k <= 256 (k <= 255 in alpha mode), a palette entry outside the box of the index formats; fixed colours or
+ * alpha weighting on the processor (kmg_reduce_indexed_batch only; kmg_find_batch ignores both, as kmg_find does); n_tables other
+ * than 1 or n_images, then an INDEX16 output that is not 2-byte aligned (kmg_dev_apply_batch).  Alpha mode's "image keeps no
+ * pixel" refusal of kmg_reduce_indexed_batch is that of kmg_reduce_batch.  Any other failure returns the first error; which
+ * outputs were written by then is unspecified.                                                                                  */
+typedef struct kmg_batch_apply_report {   /* 16 bytes, no padding */
+    uint32_t launches;     /* launches of the batched output kernel                 */
+    uint32_t batched;      /* images written by them                                */
+    uint32_t per_image;    /* images that took their own output pass                */
+    uint32_t sub_batches;  /* how many pieces max_resident_bytes cut the batch into */
+} kmg_batch_apply_report;
+
+/* device building block, as kmg_dev_palette_batch: d_rgba and d_out are HOST arrays of n_images device pointers (images of
+ * widths[i] x heights[i] pixels; outputs of 4, 1 or 2 bytes per pixel); centroids4: HOST, n_tables tables of k x 4 floats in index
+ * order -- n_tables = 1: one table for all images, n_tables = n_images: table i for image i.  The alpha cutoff is the
+ * processor's, read as kmg_dev_apply_format reads it.  report (may be NULL): sub_batches = 1.  Synchronises `stream`.          */
+KMG_API int kmg_dev_apply_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths,
+                                const uint32_t *heights, const float *centroids4, uint32_t n_tables, uint32_t k, int mode, int format,
+                                void *const *d_out, kmg_batch_apply_report *report, void *stream);
+/* host buffers, as kmg_find_indexed per image with ONE palette for all images: out[i] has room for widths[i] * heights[i]
+ * outputs of `format`                                                                                                           */
+KMG_API int kmg_find_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths,
+                           const uint32_t *heights, const uint8_t *palette_rgba, uint32_t n_colors, int mode, int format,
+                           uint64_t max_resident_bytes, void *const *out, kmg_batch_apply_report *report);
+/* host buffers, as kmg_reduce_indexed per image: out_palette_rgba[i] has room for color_count * 4 bytes, out_counts[i] receives
+ * the number of entries, out_index[i] has room for widths[i] * heights[i] outputs of `format`.  batch_report: what
+ * kmg_reduce_batch reports for the palettes; apply_report: the output step (both may be NULL)                                   */
+KMG_API int kmg_reduce_indexed_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths,
+                                     const uint32_t *heights, uint32_t color_count, int algo, int mode, int format,
+                                     uint64_t max_resident_bytes, uint8_t *const *out_palette_rgba, uint32_t *out_counts,
+                                     void *const *out_index, kmg_batch_report *batch_report, kmg_batch_apply_report *apply_report);
+
 /* ---- host-side colour helpers the reference takes from the `palette` crate -------------
  * CentroidsBuffer::fixed_centroids (core/src/structures.rs:523-553): sRGB8 -> Lab (L,a,b,1)  */
 KMG_API int kmg_palette_to_centroids(const uint8_t *palette_rgba, uint32_t n_colors, float *centroids4);

@@ -4,6 +4,7 @@
 // kmg_reduce_indexed are one body each.  There is no CPU data path in this file: every per-pixel step is a kernel launch.
 
 #include "kmg_state.h"
+#include "kmg_batch_layout.h"
 
 // ---------------------------------------------------------------------------------------------
 // host-buffer API (ImageProcessor::{palette, find, reduce})
@@ -546,27 +547,44 @@ int batch_stage(kmg_processor *p, const uint8_t *const *rgba, const uint32_t *wi
     return KMG_OK;
 }
 
-// kmg_palette_batch (reduce = false) / kmg_reduce_batch
+// What kmg_reduce_indexed_batch adds to kmg_reduce_batch: the output's format, the palettes in index order (with out_counts), and
+// the output step of a sub-batch in one launch (apply_batch_download, kmg_batch_apply.hip) instead of image after image.
+struct IndexedBatch {
+    int format;
+    uint8_t *const *palettes;
+    kmg_batch_apply_report rep;
+};
+
+uint32_t format_bytes(int format) { return format == KMG_FORMAT_INDEX8 ? 1u : format == KMG_FORMAT_INDEX16 ? 2u : 4u; }
+
+// kmg_palette_batch (reduce = false) / kmg_reduce_batch / kmg_reduce_indexed_batch (reduce = true, ix)
 int batch_call(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths, const uint32_t *heights,
                uint32_t color_count, int algo, int mode, bool reduce, uint64_t max_resident_bytes, uint8_t *const *out_rgba,
-               uint32_t *out_counts, kmg_batch_report *report)
+               uint32_t *out_counts, kmg_batch_report *report, IndexedBatch *ix = nullptr)
 {
     // the refusals, for the whole batch, before any device work (the order is part of the contract: include/kmeans_hip.h)
     if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
     if (n_images == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "the batch is empty");
-    if (!rgba || !widths || !heights || !out_rgba || (!reduce && !out_counts)) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch array is NULL");
+    if (!rgba || !widths || !heights || !out_rgba || ((!reduce || ix) && !out_counts) || (ix && !ix->palettes))
+        return fail(KMG_ERR_INVALID_ARGUMENT, "a batch array is NULL");
     for (uint32_t i = 0; i < n_images; ++i) {
         if (!rgba[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: image pointer is NULL", i);
-        if (!out_rgba[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: output pointer is NULL", i);
+        if (!out_rgba[i] || (ix && !ix->palettes[i])) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: output pointer is NULL", i);
         if (!widths[i] || !heights[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u has zero width or height", i);
         KMG_TRY(check_pixel_count((uint64_t)widths[i] * heights[i]));
     }
     KMG_TRY(check_k_nonzero(color_count));
     KMG_TRY(check_algo(algo));
     if (reduce) KMG_TRY(check_mode(mode));
+    if (ix) KMG_TRY(check_format(ix->format));
     if (algo == KMG_ALGO_KMEANS) KMG_TRY(check_k_limit(color_count));
     CallStart c;
     c.snapshot(p);
+    const int format = ix ? ix->format : KMG_FORMAT_RGBA8;
+    if (format != KMG_FORMAT_RGBA8) {                                  // (the centroids' box: once a sub-batch has its palettes)
+        KMG_TRY(check_meld_format(mode, format));
+        KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k", color_count, c.alpha_cutoff != 0));
+    }
     if (const uint32_t f = fixed_count(c.fixed))
         return fail(KMG_ERR_INVALID_ARGUMENT, "a batch has no fixed colours (%u are set on the processor)", f);
     if (c.weighting) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch has no alpha weighting (it is on for the processor)");
@@ -581,13 +599,20 @@ int batch_call(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, 
     std::vector<uint32_t> cuts(1, 0u);
     uint64_t held = 0;
     for (uint32_t i = 0; i < n_images; ++i) {
-        const uint64_t bytes = octree ? 4ull * widths[i] * heights[i] : batch_resident_bytes(p, widths[i], heights[i], cutoff, reduce);
+        const uint64_t bytes = (octree ? 4ull * widths[i] * heights[i] : batch_resident_bytes(p, widths[i], heights[i], cutoff, reduce)) +
+                               (ix ? (uint64_t)format_bytes(format) * widths[i] * heights[i] : 0ull);
         if (i > cuts.back() && held + bytes > bound) { cuts.push_back(i); held = 0; }
         held += bytes;
     }
     cuts.push_back(n_images);
     const size_t n_sub = cuts.size() - 1;
     kmg_batch_report rep = {0u, 0u, (uint32_t)n_sub, 0u};
+    if (ix) ix->rep = {0u, 0u, 0u, (uint32_t)n_sub};
+    // kmg_reduce_indexed_batch: the palette in index order, as the bytes the output pass writes (reduce_call)
+    auto palette_out = [&](uint32_t i, const float *mine, uint32_t k) {
+        for (uint32_t q = 0; q < k; ++q) shader_lab_to_rgba8(mine + 4 * q, ix->palettes[i] + 4 * q);
+        out_counts[i] = k;
+    };
 
     std::vector<std::vector<std::array<uint8_t, 4>>> colors(octree ? n_images : 0);
     auto octree_of = [&](uint32_t i, const uint8_t *d_src) -> int {   // lib.rs:288-331
@@ -631,7 +656,11 @@ int batch_call(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, 
                 }
                 KMG_TRY(octree_centroids(colors[i], c4));
                 KMG_TRY(apply_and_download(p, (const uint8_t *)stage[i - a].src.ptr, widths[i], heights[i], c4.data(), (uint32_t)(c4.size() / 4), mode,
-                                           cutoff, st, out_rgba[i], KMG_FORMAT_RGBA8));
+                                           cutoff, st, out_rgba[i], format));
+                if (ix) {
+                    palette_out(i, c4.data(), (uint32_t)(c4.size() / 4));
+                    ++ix->rep.per_image;
+                }
             }
             continue;
         }
@@ -650,6 +679,17 @@ int batch_call(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, 
             rep.launches += r.launches;
             rep.iterations = std::max(rep.iterations, r.iterations);
             rep.fallback += r.fallback;
+        }
+        if (ix) {
+            // the output step of the whole sub-batch: one launch for the images that join it, one download each
+            std::vector<const uint8_t *> src(count);
+            for (uint32_t q = 0; q < count; ++q) src[q] = (const uint8_t *)stage[q].src.ptr;
+            if (format != KMG_FORMAT_RGBA8)
+                for (uint32_t q = 0; q < count; ++q) KMG_TRY(check_index_format(&c4[4ull * color_count * q], color_count, mode, format, cutoff));
+            KMG_TRY(apply_batch_download(p, count, src.data(), widths + a, heights + a, c4.data(), count, color_count, mode, format, cutoff,
+                                         out_rgba + a, &ix->rep, st));
+            for (uint32_t i = a; i < b; ++i) palette_out(i, &c4[4ull * color_count * (i - a)], color_count);
+            continue;
         }
         for (uint32_t i = a; i < b; ++i) {
             const float *mine = &c4[4ull * color_count * (i - a)];
@@ -683,6 +723,93 @@ extern "C" int kmg_reduce_batch(kmg_processor *p, uint32_t n_images, const uint8
                                 uint8_t *const *out_rgba, kmg_batch_report *report)
 try {
     return batch_call(p, n_images, rgba, widths, heights, color_count, algo, mode, true, max_resident_bytes, out_rgba, nullptr, report);
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_reduce_indexed_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths,
+                                        const uint32_t *heights, uint32_t color_count, int algo, int mode, int format,
+                                        uint64_t max_resident_bytes, uint8_t *const *out_palette_rgba, uint32_t *out_counts,
+                                        void *const *out_index, kmg_batch_report *batch_report, kmg_batch_apply_report *apply_report)
+try {
+    IndexedBatch ix = {format, out_palette_rgba, {0u, 0u, 0u, 0u}};
+    KMG_TRY(batch_call(p, n_images, rgba, widths, heights, color_count, algo, mode, true, max_resident_bytes, (uint8_t *const *)out_index,
+                       out_counts, batch_report, &ix));
+    if (apply_report) *apply_report = ix.rep;
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+namespace {
+
+// kmg_find_batch: kmg_find_indexed of every image with one palette; the sources of a sub-batch in one stream-ordered block
+// (kmg_batch_layout.h), its output step in one launch (apply_batch_download)
+int find_batch_call(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths, const uint32_t *heights,
+                    const uint8_t *palette_rgba, uint32_t n_colors, int mode, int format, uint64_t max_resident_bytes, uint8_t *const *out,
+                    kmg_batch_apply_report *report)
+{
+    // the refusals, for the whole batch, before any device work (the order is part of the contract: include/kmeans_hip.h)
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
+    if (n_images == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "the batch is empty");
+    if (!rgba || !widths || !heights || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch array is NULL");
+    for (uint32_t i = 0; i < n_images; ++i) {
+        if (!rgba[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: image pointer is NULL", i);
+        if (!out[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: output pointer is NULL", i);
+        if (!widths[i] || !heights[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u has zero width or height", i);
+        KMG_TRY(check_pixel_count((uint64_t)widths[i] * heights[i]));
+    }
+    if (!palette_rgba || n_colors == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "palette is empty");
+    KMG_TRY(check_mode(mode));
+    KMG_TRY(check_format(format));
+    KMG_TRY(check_k_limit(n_colors));
+    CallStart c;
+    c.snapshot(p);
+    const uint32_t cutoff = c.alpha_cutoff, bpp = format_bytes(format);
+    std::vector<float> c4(4 * (size_t)n_colors);
+    KMG_TRY(kmg_palette_to_centroids(palette_rgba, n_colors, c4.data()));   // lib.rs:86-87
+    if (format != KMG_FORMAT_RGBA8) KMG_TRY(check_index_format(c4.data(), n_colors, mode, format, cutoff));
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(c.sg.acquire(p));
+    hipStream_t st = c.sg.st;
+
+    // consecutive sub-batches whose resident bytes (source and output) fit the bound: images [a, b)
+    const uint64_t bound = max_resident_bytes ? max_resident_bytes : (1ull << 30);
+    kmg_batch_apply_report rep = {0u, 0u, 0u, 0u};
+    std::vector<uint64_t> pixels(n_images), offset;
+    for (uint32_t i = 0; i < n_images; ++i) pixels[i] = (uint64_t)widths[i] * heights[i];
+    for (uint32_t a = 0, b; a < n_images; a = b) {
+        uint64_t held = 0;
+        for (b = a; b < n_images; ++b) {
+            const uint64_t bytes = (4ull + bpp) * pixels[b];
+            if (b > a && held + bytes > bound) break;
+            held += bytes;
+        }
+        const uint32_t count = b - a;
+        uint64_t total = 0;
+        if (!batch_offsets(&pixels[a], count, 4u, offset, &total, (uint64_t)SIZE_MAX / 2))
+            return fail(KMG_ERR_OUT_OF_MEMORY, "the sources of the sub-batch do not fit one block");
+        StreamBuf block;
+        HIP_TRY(block.alloc(p, (size_t)total, st));
+        std::vector<const uint8_t *> src(count);
+        for (uint32_t q = 0; q < count; ++q) {
+            src[q] = (const uint8_t *)block.ptr + offset[q];
+            HIP_TRY_DRAIN(st, copy_host_image(p, (void *)src[q], rgba[a + q], (size_t)pixels[a + q] * 4, hipMemcpyHostToDevice, st));   // structures.rs:31-65
+        }
+        KMG_TRY_DRAIN(st, apply_batch_download(p, count, src.data(), widths + a, heights + a, c4.data(), 1u, n_colors, mode, format, cutoff,
+                                               out + a, &rep, st));
+        ++rep.sub_batches;
+    }
+    if (report) *report = rep;
+    return KMG_OK;
+}
+
+}  // namespace
+
+extern "C" int kmg_find_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths,
+                              const uint32_t *heights, const uint8_t *palette_rgba, uint32_t n_colors, int mode, int format,
+                              uint64_t max_resident_bytes, void *const *out, kmg_batch_apply_report *report)
+try {
+    return find_batch_call(p, n_images, rgba, widths, heights, palette_rgba, n_colors, mode, format, max_resident_bytes, (uint8_t *const *)out,
+                           report);
 }
 KMG_ABI_CATCH
 

@@ -169,7 +169,7 @@ struct kmg_apply_plan {
 
 // The index formats (include/kmeans_hip.h at kmg_output_format): the mode has an index, k fits the format (with the transparent
 // slot in alpha mode), and every centroid lies in the box inside which the dither scan's sentinel never wins.
-static int check_index_format(const float *c4, uint32_t k, int mode, int format, uint32_t alpha_cutoff)
+int kmg::check_index_format(const float *c4, uint32_t k, int mode, int format, uint32_t alpha_cutoff)
 {
     KMG_TRY(check_format(format));                                     // (the caller has dealt with KMG_FORMAT_RGBA8)
     KMG_TRY(check_meld_format(mode, format));

@@ -85,4 +85,24 @@ inline Route apply_route(int mode, uint32_t k, uint64_t n_pixels_hint, int force
     return Route::kScan;
 }
 
+// Which images of a batch join the batched output launch (kmg_batch_apply.hip): replace or dither, and the image's
+// own plan would scan all centroids per pixel -- the batched launch then does the same work with one launch and no plan build.
+// Every other image (meld, diffusion, a table, lists or mask-word route, a forced KMG_STRATEGY_TABLE) keeps its per-image pass.
+// All routes write identical bytes: the rule changes time only.
+// Widened by one case (profiles/r10_batch_apply_time.txt, the `pruned` rows): with 128 <= k <= 512 a plan takes the candidate
+// lists from 16384 pixels on because ONE image's scan is bound by the latency of a wave that walks all k, not by throughput
+// (dither_pruning_pays).  In a batched launch that latency is paid once for all images, so in a batch of two images or more such
+// an image joins while the throughput model alone -- the line dither_pruning_pays applies below k = 128 -- says that the lists do
+// not pay for it: at k = 256 the joined launch takes 0.23 - 0.37 of the images' own passes from 7 such images on; one such image
+// alone takes 1.30 of its own pass and keeps it.
+inline bool batch_apply_joins(int mode, uint32_t k, uint64_t n_pixels, int forced, bool mask_words, uint32_t n_images)
+{
+    if (mode == kRouteModeMeld || mode == kRouteModeDiffuse) return false;
+    const Route route = apply_route(mode, k, n_pixels, forced, mask_words);
+    if (route == Route::kScan) return true;
+    if (n_images >= 2u && forced == 0 && (route == Route::kDitherLists || route == Route::kDitherMasks) && k >= 128u && k <= kRouteListMaxK)
+        return !((double)n_pixels * (0.255 * k - 0.3) > 45.0e6);
+    return false;
+}
+
 }  // namespace kmg

@@ -17,6 +17,7 @@
 
 #include "kmg_state.h"
 
+#include "kmg_batch_layout.h"    // kBatchMaxGrid
 #include "kmg_device.h"
 #include "kmg_lloyd_dev.h"       // argmin_scan, init_key_index, init_max_slot
 
@@ -37,16 +38,7 @@ struct alignas(16) BatchImage {
 };
 static_assert(sizeof(BatchImage) == 64, "BatchImage layout");
 
-// the image workgroup `wg` belongs to: the last record whose first workgroup is <= wg (records are in grid order; at most 32 steps)
-__device__ __forceinline__ uint32_t batch_image_of(const BatchImage *__restrict__ img, uint32_t n_images, uint32_t wg)
-{
-    uint32_t lo = 0, hi = n_images;
-    for (uint32_t step = 0; step < 32u && hi - lo > 1u; ++step) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (img[mid].first_wg <= wg) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+// (the image a workgroup belongs to: batch_image_of, kmg_device.h)
 
 __device__ __forceinline__ Centroid centroid_of_pixel(const float *__restrict__ lut, uint32_t px)
 {
@@ -235,8 +227,7 @@ struct LloydGuard {
 
 // the batch takes working images below this many pixels: the PPT = 1 tiling of the small-image route (kmg_kernels.hip assign_ppt)
 constexpr uint64_t kBatchMaxPixels = 1ull << 19;
-// workgroups of one batched launch at most; a larger batch runs as several pieces, one after the other
-constexpr uint64_t kBatchMaxGrid = 1ull << 20;
+// (workgroups of one batched launch at most: kBatchMaxGrid, kmg_batch_layout.h)
 
 // plus_plus_init.wgsl:161-168 `initial`: the pixel that kmg_init_first_key(w, h) names
 uint32_t first_pixel_of(uint32_t w, uint32_t h)

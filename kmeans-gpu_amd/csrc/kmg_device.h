@@ -142,6 +142,20 @@ __device__ __forceinline__ void stage_centroids(float4 *s_cent, const Centroid *
     }
 }
 
+// Batched launches (kmg_batch.hip, kmg_batch_apply.hip): a device table of one record per image, in grid order, each with the
+// index of the image's first workgroup in `first_wg`.  The image workgroup `wg` belongs to: the last record whose first workgroup
+// is <= wg (at most 32 steps).
+template <typename Record>
+__device__ __forceinline__ uint32_t batch_image_of(const Record *__restrict__ img, uint32_t n_images, uint32_t wg)
+{
+    uint32_t lo = 0, hi = n_images;
+    for (uint32_t step = 0; step < 32u && hi - lo > 1u; ++step) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (img[mid].first_wg <= wg) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // choose_centroid.wgsl:180-206 `pick` for all clusters by ONE workgroup of `block` threads (s_count: a word of LDS):
 // centroid <- sum / count where count > 0, *n_converged = number of clusters that moved less than `convergence`
 // (literal CIE94 of the new against the previous centroid); an empty cluster keeps its centroid and counts as not converged.

@@ -78,6 +78,21 @@ int dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows
               int mode, uint8_t *d_out, void *stream, uint32_t alpha_cutoff, int format = KMG_FORMAT_RGBA8);
 // the box of the index formats (include/kmeans_hip.h at kmg_output_format)
 constexpr float kIndexBoxLmin = -100.0f, kIndexBoxLmax = 200.0f, kIndexBoxAB = 300.0f;
+// the rules of the index formats for a centroid table (kmg_apply.hip): the mode has an index, k fits the format, every centroid lies
+// in the box
+int check_index_format(const float *centroids4, uint32_t k, int mode, int format, uint32_t alpha_cutoff);
+// The output pass of many images in device memory (kmg_batch_apply.hip; include/kmeans_hip.h at kmg_batch_apply_report), arguments
+// already checked: the images that join (batch_apply_joins, kmg_apply_route.h) through the batched launch, the others through
+// dev_apply one by one.  centroids4: n_tables (1 or n_images) tables of k.  ADDS to report's launches, batched and per_image.
+// Synchronises `st`.
+int apply_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
+                const float *centroids4, uint32_t n_tables, uint32_t k, int mode, int format, uint32_t alpha_cutoff, void *const *d_out,
+                kmg_batch_apply_report *report, hipStream_t st);
+// apply_batch into one stream-ordered block (kmg_batch_layout.h: every image at a 16-byte aligned offset), then the images'
+// outputs to the host buffers out[i].  Synchronises `st`.
+int apply_batch_download(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
+                         const float *centroids4, uint32_t n_tables, uint32_t k, int mode, int format, uint32_t alpha_cutoff,
+                         uint8_t *const *out, kmg_batch_apply_report *report, hipStream_t st);
 
 // The k-means palette step on a working image (kmg_api.hip): sw x sh pixels in device memory -> host centroid table, a new Lloyd
 // problem of k centroids (initialisation + loop with the processor's options).  Synchronises `st`.  d_labels: optional label map.

@@ -12,6 +12,8 @@
 //   processor.reduce_batch(color_count, images, algo, mode) -> whole images per device, side by side
 //   processor.palette_batch(color_count, images, algo) / reduce_batch(color_count, images, algo, mode, max_resident_bytes)
 //                                                          -> many small images per launch on one device (kmg_*_batch)
+//   processor.find_batch(images, colors, mode) / reduce_indexed_batch(color_count, images, algo, mode)
+//                                                          -> their index maps, the output passes in one launch
 //   processor.compare(source, output[, colors])         -> kmg_error_stats: exact error sums of an output against its source
 //   processor.reduce_quality(image, max_delta_e, k_min, k_max, mode) -> the colour count chosen by a quality target
 //   processor.optimize_indexed(indexed[, flags, bits])     -> the palette without unused entries, ordered, and the map packed for it
@@ -309,6 +311,52 @@ public:
         }
         check(kmg_reduce_batch(single(), (uint32_t)images.size(), src.data(), ws.data(), hs.data(), color_count, (int)algo, (int)reduce_mode,
                                max_resident_bytes, dst.data(), report));
+        return out;
+    }
+
+    // Batched output on a single-device processor (kmg_find_batch / kmg_reduce_indexed_batch, include/kmeans_hip.h): what
+    // find_indexed() / reduce_indexed() give image by image, the output passes of the images in one launch.  apply_report (and
+    // batch_report, the palettes' chain): what the call did.  The batch must not be empty.
+    std::vector<Indexed> find_batch(const std::vector<Image> &images, const std::vector<RGBA8> &colors, ReduceMode reduce_mode,
+                                    bool alpha_mode = false, uint64_t max_resident_bytes = 0, kmg_batch_apply_report *apply_report = nullptr) const
+    {
+        std::vector<Indexed> out;
+        std::vector<const uint8_t *> src;
+        std::vector<void *> dst;
+        std::vector<uint32_t> ws, hs;
+        for (const Image &im : images) out.push_back(indexed_for(im, (uint32_t)colors.size(), alpha_mode));
+        for (size_t i = 0; i < images.size(); ++i) {
+            src.push_back(bytes(images[i])); dst.push_back(index_data(out[i]));
+            ws.push_back(images[i].dims.first); hs.push_back(images[i].dims.second);
+        }
+        const int format = images.empty() ? KMG_FORMAT_INDEX8 : out[0].format;
+        check(kmg_find_batch(single(), (uint32_t)images.size(), src.data(), ws.data(), hs.data(), reinterpret_cast<const uint8_t *>(colors.data()),
+                             (uint32_t)colors.size(), (int)reduce_mode, format, max_resident_bytes, dst.data(), apply_report));
+        return out;
+    }
+
+    std::vector<Indexed> reduce_indexed_batch(uint32_t color_count, const std::vector<Image> &images, Algorithm algo, ReduceMode reduce_mode,
+                                              bool alpha_mode = false, uint64_t max_resident_bytes = 0, kmg_batch_report *batch_report = nullptr,
+                                              kmg_batch_apply_report *apply_report = nullptr) const
+    {
+        std::vector<Indexed> out;
+        std::vector<const uint8_t *> src;
+        std::vector<void *> dst;
+        std::vector<uint8_t *> pals;
+        std::vector<uint32_t> ws, hs, counts(images.size() ? images.size() : 1);
+        for (const Image &im : images) {
+            out.push_back(indexed_for(im, color_count, alpha_mode));
+            out.back().palette.resize(color_count ? color_count : 1);
+        }
+        for (size_t i = 0; i < images.size(); ++i) {
+            src.push_back(bytes(images[i])); dst.push_back(index_data(out[i]));
+            pals.push_back(reinterpret_cast<uint8_t *>(out[i].palette.data()));
+            ws.push_back(images[i].dims.first); hs.push_back(images[i].dims.second);
+        }
+        const int format = images.empty() ? KMG_FORMAT_INDEX8 : out[0].format;
+        check(kmg_reduce_indexed_batch(single(), (uint32_t)images.size(), src.data(), ws.data(), hs.data(), color_count, (int)algo, (int)reduce_mode,
+                                       format, max_resident_bytes, pals.data(), counts.data(), dst.data(), batch_report, apply_report));
+        for (size_t i = 0; i < images.size(); ++i) out[i].palette.resize(counts[i]);
         return out;
     }
 

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "BatchReport","Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "BatchReport", "BatchApplyReport", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -206,6 +206,17 @@ class BatchReport(C.Structure):         # include/kmeans_hip.h kmg_batch_report:
                 f"fallback={self.fallback})")
 
 
+class BatchApplyReport(C.Structure):    # include/kmeans_hip.h kmg_batch_apply_report: 16 bytes
+    _fields_ = [("launches", C.c_uint32), ("batched", C.c_uint32), ("per_image", C.c_uint32), ("sub_batches", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.launches, self.batched, self.per_image, self.sub_batches)
+
+    def __repr__(self):
+        return (f"BatchApplyReport(launches={self.launches}, batched={self.batched}, per_image={self.per_image}, "
+                f"sub_batches={self.sub_batches})")
+
+
 class IndexPlanInfo(C.Structure):       # include/kmeans_hip.h kmg_index_plan_info: 16 bytes
     _fields_ = [("n_colors", C.c_uint32), ("n_slots", C.c_uint32), ("transparent", C.c_int32), ("bits", C.c_uint32)]
 
@@ -359,6 +370,7 @@ SYMBOLS = [
     "kmg_lloyd_table_buffers", "kmg_lloyd_accumulate_into", "kmg_lloyd_labels_from_tables_update", "kmg_lloyd_histogram_buffer", "kmg_lloyd_rebuild_from_histogram", "kmg_debug_block_counts", "kmg_debug_idle_blocks", "kmg_debug_encode_table_check", "kmg_debug_division_check", "kmg_lloyd_converged_count", "kmg_lloyd_iterate", "kmg_lloyd_flush", "kmg_lloyd_run", "kmg_dev_apply", "kmg_apply_plan_create", "kmg_apply_plan_run", "kmg_apply_plan_destroy", "kmg_apply_plan_status",
     "kmg_find_indexed", "kmg_reduce_indexed", "kmg_apply_plan_create_format", "kmg_dev_apply_format",
     "kmg_dev_palette_batch", "kmg_palette_batch", "kmg_reduce_batch",
+    "kmg_dev_apply_batch", "kmg_find_batch", "kmg_reduce_indexed_batch",
     "kmg_dither_threshold", "kmg_dev_compare", "kmg_compare", "kmg_reduce_quality",
     "kmg_sequence_create", "kmg_sequence_destroy", "kmg_sequence_add", "kmg_sequence_add_device", "kmg_sequence_clear",
     "kmg_sequence_info", "kmg_sequence_centroids", "kmg_sequence_palette", "kmg_dev_frame_delta", "kmg_dev_frame_delta_lossy",
@@ -534,6 +546,13 @@ def lib():
                                     C.c_uint64, C.POINTER(vp), u32p, C.POINTER(BatchReport)]
     L.kmg_reduce_batch.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_int,
                                    C.c_int, C.c_uint64, C.POINTER(vp), C.POINTER(BatchReport)]
+    L.kmg_dev_apply_batch.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), f32p, C.c_uint32,
+                                      C.c_uint32, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(BatchApplyReport), vp]
+    L.kmg_find_batch.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u8p, C.c_uint32, C.c_int,
+                                 C.c_int, C.c_uint64, C.POINTER(vp), C.POINTER(BatchApplyReport)]
+    L.kmg_reduce_indexed_batch.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_int,
+                                           C.c_int, C.c_int, C.c_uint64, C.POINTER(vp), u32p, C.POINTER(vp), C.POINTER(BatchReport),
+                                           C.POINTER(BatchApplyReport)]
     L.kmg_group_lloyd_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
     L.kmg_group_lloyd_destroy.argtypes = [vp]
     L.kmg_group_lloyd_destroy.restype = None
@@ -704,7 +723,8 @@ class ImageProcessor:
         self._sequences = None          # weak set of the live Sequence objects: closed with the processor, which they need
         _register(self)
         self.alpha_weight = False
-        self.last_batch_report = None   # BatchReport of the last palette_batch / reduce_batch / palette_batch_device
+        self.last_batch_report = None   # BatchReport of the last palette_batch / reduce_batch / palette_batch_device / reduce_indexed_batch
+        self.last_batch_apply_report = None   # BatchApplyReport of the last find_batch / reduce_indexed_batch / apply_batch_device
         if fixed_colors is not None:
             self.set_fixed_colors(fixed_colors)
         if alpha_weight:
@@ -842,6 +862,78 @@ class ImageProcessor:
         _check(lib().kmg_dev_palette_batch(self._h, n, src, ws, hs, int(k), _np_ptr(cent), _np_ptr(its), C.byref(rep), C.c_void_p(stream)))
         self.last_batch_report = rep
         return cent, its[:n]
+
+    # ---- batched output (include/kmeans_hip.h kmg_batch_apply_report) ---------------------------
+    def _batch_format(self, k, format):
+        """the output format of a batch and the dtype of its arrays: `format`, or what find_indexed / reduce_indexed choose for k"""
+        fmt = self._index_format(k) if format is None else OutputFormat(format)
+        return fmt, {OutputFormat.RGBA8: np.uint8, OutputFormat.Index8: np.uint8, OutputFormat.Index16: np.uint16}[fmt]
+
+    @staticmethod
+    def _batch_outputs(imgs, fmt, dtype, out):
+        """the result arrays of a batch: new ones, or the caller's `out` (one C-contiguous array of the right shape per image)"""
+        shapes = [im.shape if fmt == OutputFormat.RGBA8 else im.shape[:2] for im in imgs]
+        if out is None:
+            return [np.empty(s, dtype) for s in shapes]
+        if len(out) != len(imgs) or any(o.shape != s or o.dtype != dtype or not o.flags.c_contiguous for o, s in zip(out, shapes)):
+            raise ValueError("out must hold one C-contiguous array of the output's shape and type per image")
+        return list(out)
+
+    def find_batch(self, images, colors, reduce_mode=ReduceMode.Replace, format=None, max_resident_bytes=0, out=None):
+        """kmg_find_batch: find_indexed() of many images onto ONE palette, their output passes in one launch; returns the list of
+        index maps, each what find_indexed returns for that image (format=OutputFormat.RGBA8: what find returns).  The report of
+        the call: last_batch_apply_report.  out: optional list of arrays that receive the results"""
+        imgs = [_image(im) for im in images]
+        n = len(imgs)
+        pal = np.ascontiguousarray(colors, np.uint8).reshape(-1, 4)
+        fmt, dtype = self._batch_format(pal.shape[0], format)
+        outs = self._batch_outputs(imgs, fmt, dtype, out)
+        src, ws, hs = self._batch_arrays(imgs)
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        rep = BatchApplyReport()
+        _check(lib().kmg_find_batch(self._h, n, src, ws, hs, _np_ptr(pal), pal.shape[0], int(reduce_mode), int(fmt), int(max_resident_bytes),
+                                    dst, C.byref(rep)))
+        self.last_batch_apply_report = rep
+        return outs
+
+    def reduce_indexed_batch(self, color_count, images, algo=Algorithm.Kmeans, reduce_mode=ReduceMode.Replace, format=None,
+                             max_resident_bytes=0, out=None):
+        """kmg_reduce_indexed_batch: reduce_indexed() of many images -- one launch chain for their palettes, one launch for their
+        output passes; returns the list of (palette, index_map), each what reduce_indexed returns for that image
+        (format=OutputFormat.RGBA8: the image reduce returns in place of the map).  The reports of the call: last_batch_report and
+        last_batch_apply_report.  out: optional list of arrays that receive the maps"""
+        imgs = [_image(im) for im in images]
+        n = len(imgs)
+        fmt, dtype = self._batch_format(int(color_count), format)
+        outs = self._batch_outputs(imgs, fmt, dtype, out)
+        pals = [np.empty((max(int(color_count), 1), 4), np.uint8) for _ in imgs]
+        src, ws, hs = self._batch_arrays(imgs)
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        pdst = (C.c_void_p * n)(*[q.ctypes.data for q in pals])
+        counts = np.zeros(max(n, 1), np.uint32)
+        rep, arep = BatchReport(), BatchApplyReport()
+        _check(lib().kmg_reduce_indexed_batch(self._h, n, src, ws, hs, int(color_count), int(algo), int(reduce_mode), int(fmt),
+                                              int(max_resident_bytes), pdst, _np_ptr(counts), dst, C.byref(rep), C.byref(arep)))
+        self.last_batch_report, self.last_batch_apply_report = rep, arep
+        return [(q[:int(c)].copy(), o) for q, c, o in zip(pals, counts, outs)]
+
+    def apply_batch_device(self, d_images, widths, heights, centroids4, reduce_mode, format, d_outs, stream=0):
+        """kmg_dev_apply_batch: the output pass of images in device memory (d_images, d_outs: their addresses) in one launch;
+        centroids4: (k, 4) float32 -- one table for all images -- or (n, k, 4), table i for image i.  Synchronises the stream.
+        The report of the call: last_batch_apply_report"""
+        n = len(d_images)
+        c4 = np.ascontiguousarray(centroids4, np.float32)
+        n_tables = 1 if c4.ndim == 2 else c4.shape[0]
+        k = c4.shape[-2]
+        src = (C.c_void_p * n)(*[int(d) for d in d_images])
+        dst = (C.c_void_p * n)(*[int(d) for d in d_outs])
+        ws = (C.c_uint32 * n)(*[int(w) for w in widths])
+        hs = (C.c_uint32 * n)(*[int(h) for h in heights])
+        rep = BatchApplyReport()
+        _check(lib().kmg_dev_apply_batch(self._h, n, src, ws, hs, _np_ptr(c4), n_tables, k, int(reduce_mode), int(format), dst,
+                                         C.byref(rep), C.c_void_p(stream)))
+        self.last_batch_apply_report = rep
+        return rep
 
     # ---- palette-index output (include/kmeans_hip.h kmg_output_format) ----------------------
     def _index_format(self, k):

@@ -4,7 +4,7 @@
     python -m kmeans_gpu_amd.cli reduce  -i img.png -c 8 [-a kmeans|octree] [-m replace|dither|meld|diffuse] [-o out.png]
     python -m kmeans_gpu_amd.cli find    -i img.png -p "#050505,#ffffff,#ff0000"|palette.png [-m ...] [-o out.png]
     python -m kmeans_gpu_amd.cli palette -i img.png -c 8 [-a ...] [-s 40] [-o out.png]
-    python -m kmeans_gpu_amd.cli batch   -i A.png B.png ... -c 8 [-a ...] [-m ...] -o DIR | --palette
+    python -m kmeans_gpu_amd.cli batch   -i A.png B.png ... -c 8 [-a ...] [-m ...] -o DIR [--indexed] | --palette
 
 Every sub-command also takes `--alpha-cutoff N` (0..255, default 0 = alpha ignored, as in the reference): with N >= 1 only the
 pixels whose alpha is at least N shape the palette, and the output keeps the input's alpha (include/kmeans_hip.h, kmg_options).
@@ -50,6 +50,8 @@ non-zero --alpha-cutoff; `sequence` applies the one map to every frame.
 `batch` reduces many images in one call (kmg_reduce_batch: one launch chain for the palettes of all of them, the results of
 `reduce` image by image) and writes DIR/<name>-reduce-c<K>-<algo>-<mode>.png for every input; `--palette` prints their palettes
 instead (kmg_palette_batch).  It takes --alpha-cutoff; not --fixed, --alpha-weight or --devices.
+`batch --indexed` writes one palette-mode PNG per input instead (kmg_reduce_indexed_batch: the output passes of the images in one
+launch as well; kmeans_gpu_amd/png8.py, 8 bits per pixel, the transparent slot of --alpha-cutoff as entry 0) and prints both reports.
 
 Image decoding/encoding (the `image` crate in the reference) is done with Pillow.  One flag the reference does not have:
 `--devices 0,1,...` (before the sub-command) runs the same operation over several GPUs of the node (kmg_group_*: the image
@@ -393,6 +395,8 @@ def build_parser():
     b.add_argument("-a", "--algo", choices=list(_ALGOS), default="kmeans")
     b.add_argument("-m", "--mode", choices=list(_MODES), default="replace")
     b.add_argument("--palette", action="store_true", help="print the palette of every input instead of writing reduced images")
+    b.add_argument("--indexed", action="store_true",
+                   help="write a palette-mode PNG (an index per pixel) per input instead of RGBA; at most 256 colours, 255 with --alpha-cutoff")
     for s in (p, f, r, q, b):
         s.add_argument("--alpha-cutoff", type=validate_alpha_cutoff, default=0,
                        help="1..255: pixels with a lower alpha do not shape the palette, the output keeps the input's alpha")
@@ -420,16 +424,41 @@ def build_parser():
 
 
 def run_batch(args, ap):
-    """the `batch` sub-command: every input through one kmg_reduce_batch (or, --palette, kmg_palette_batch) call"""
+    """the `batch` sub-command: every input through one kmg_reduce_batch (or, --palette, kmg_palette_batch; --indexed,
+    kmg_reduce_indexed_batch) call"""
     if args.devices:
         ap.error("`batch` is not supported with --devices")
     if not args.palette and not args.output:
         ap.error("`batch` writes one output per input: it needs -o DIR (or --palette)")
+    if args.indexed:
+        limit = 255 if args.alpha_cutoff else 256
+        if args.palette:
+            ap.error("--indexed writes images: not with --palette")
+        if args.mode == "meld":
+            ap.error("--indexed has no meld mode: meld blends two colours, so a pixel has no palette index")
+        if args.colorcount > limit:
+            ap.error(f"--indexed writes a palette PNG of at most {limit} colours{' (plus the transparent slot)' if args.alpha_cutoff else ''}; "
+                     f"{args.colorcount} requested")
     images = [_load(path) for path in args.input]
     with ImageProcessor(alpha_cutoff=args.alpha_cutoff) as proc:
         if args.palette:
             for path, colors in zip(args.input, proc.palette_batch(args.colorcount, images, _ALGOS[args.algo])):
                 print(f"Palette {path}: " + ",".join(f"#{c[0]:02X}{c[1]:02X}{c[2]:02X}" for c in colors))
+        elif args.indexed:
+            from . import png8
+            os.makedirs(args.output, exist_ok=True)
+            pairs = proc.reduce_indexed_batch(args.colorcount, images, _ALGOS[args.algo], _MODES[args.mode])
+            for path, (colors, index) in zip(args.input, pairs):
+                name = os.path.splitext(os.path.basename(reduce_file_path(args.colorcount, args.algo, args.mode, None, path)))[0] + ".png"
+                if args.alpha_cutoff:
+                    # the transparent slot (index len(colors)) becomes entry 0, which is where png8 writes its one tRNS byte
+                    colors = np.concatenate([np.zeros((1, 4), np.uint8), colors])
+                    index = ((index.astype(np.uint16) + 1) % len(colors)).astype(np.uint8)
+                png8.write(os.path.join(args.output, name), colors, index.shape[1], index.shape[0], index, 8,
+                           transparent_first=bool(args.alpha_cutoff))
+            arep = proc.last_batch_apply_report
+            print(f"Batch output: {arep.launches} launches for {arep.batched} images, {arep.per_image} on the per-image pass, "
+                  f"{arep.sub_batches} sub-batches")
         else:
             os.makedirs(args.output, exist_ok=True)
             outs = proc.reduce_batch(args.colorcount, images, _ALGOS[args.algo], _MODES[args.mode])

@@ -129,6 +129,16 @@ pub struct kmg_batch_report {
     pub fallback: u32,
 }
 
+/// `kmg_batch_apply_report` (include/kmeans_hip.h): 16 bytes, what the output step of a batch call did.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct kmg_batch_apply_report {
+    pub launches: u32,
+    pub batched: u32,
+    pub per_image: u32,
+    pub sub_batches: u32,
+}
+
 extern "C" {
     pub fn kmg_last_error() -> *const c_char;
     pub fn kmg_version() -> *const c_char;
@@ -240,6 +250,54 @@ extern "C" {
         max_resident_bytes: u64,
         out_rgba: *mut *const u8,
         report: *mut kmg_batch_report,
+    ) -> c_int;
+    // batched output: the output passes of many small images in one launch.  `d_out`, `out`, `out_index` and `out_palette_rgba`
+    // are arrays of `n_images` pointers the library writes through; `centroids4` holds `n_tables` (1 or `n_images`) tables.
+    pub fn kmg_dev_apply_batch(
+        p: *mut kmg_processor,
+        n_images: u32,
+        d_rgba: *mut *const u8,
+        widths: *const u32,
+        heights: *const u32,
+        centroids4: *const f32,
+        n_tables: u32,
+        k: u32,
+        mode: c_int,
+        format: c_int,
+        d_out: *mut *const (),
+        report: *mut kmg_batch_apply_report,
+        stream: *mut (),
+    ) -> c_int;
+    pub fn kmg_find_batch(
+        p: *mut kmg_processor,
+        n_images: u32,
+        rgba: *mut *const u8,
+        widths: *const u32,
+        heights: *const u32,
+        palette_rgba: *const u8,
+        n_colors: u32,
+        mode: c_int,
+        format: c_int,
+        max_resident_bytes: u64,
+        out: *mut *const (),
+        report: *mut kmg_batch_apply_report,
+    ) -> c_int;
+    pub fn kmg_reduce_indexed_batch(
+        p: *mut kmg_processor,
+        n_images: u32,
+        rgba: *mut *const u8,
+        widths: *const u32,
+        heights: *const u32,
+        color_count: u32,
+        algo: c_int,
+        mode: c_int,
+        format: c_int,
+        max_resident_bytes: u64,
+        out_palette_rgba: *mut *const u8,
+        out_counts: *mut u32,
+        out_index: *mut *const (),
+        batch_report: *mut kmg_batch_report,
+        apply_report: *mut kmg_batch_apply_report,
     ) -> c_int;
     // error statistics of an output against its source (host buffers; `out` holds 4, 1 or 2 bytes per pixel for `format`) and the
     // colour count chosen by a quality target: no counterpart in the reference

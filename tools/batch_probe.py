@@ -7,7 +7,18 @@
   kernels : kmg_dev_palette_batch -- always the batched kernels -- against the per-image kmg_lloyd_init_centroids + kmg_lloyd_run +
             kmg_lloyd_get_centroids on the working images, resident on the device: where the batched chain itself starts to pay;
             `init` = the same batched call with max_iterations = 1, i.e. the k launches of the single-pick initialisation + 2
-    python tools/batch_probe.py [largest N] > profiles/r09_batch_time.txt"""
+    python tools/batch_probe.py [largest N] > profiles/r09_batch_time.txt
+
+`apply`: the batched output pass (kmg_batch_apply.hip) on the same batches, 2 N in {2, 8, 32, 128, 512}, replace and
+dither, the same protocol (warm processor, result arrays allocated once, batch and baseline taking turns, minimum of five):
+  bound   : kmg_reduce_indexed_batch(RGBA8) against kmg_reduce_batch -- the same bytes; no point above 1.10
+  index8  : kmg_reduce_indexed_batch(INDEX8) against kmg_reduce_batch
+  find    : kmg_find_batch(INDEX8) against kmg_find_indexed image after image
+  device  : kmg_dev_apply_batch against kmg_dev_apply_format image after image, images and outputs resident on the device
+  pruned  : (dither, k = 256, the images a plan of their own sends to the candidate lists) kmg_dev_apply_batch with the strategy
+            "scan" -- they join the launch -- against "table" -- they take their own pass inside the call
+  ppt     : (tools build only: KMG_LIBRARY=lib/libkmeans_hip_tools.so) kmg_dev_apply_batch with 4 against 8 pixels per thread
+    python tools/batch_probe.py apply [largest N] > profiles/r10_batch_apply_time.txt"""
 import os
 import sys
 import time
@@ -19,7 +30,9 @@ import torch
 import kmeans_gpu_amd as kg
 from PIL import Image
 
-largest = int(sys.argv[1]) if len(sys.argv) > 1 else 256
+APPLY = len(sys.argv) > 1 and sys.argv[1] == "apply"
+args = sys.argv[2:] if APPLY else sys.argv[1:]
+largest = int(args[0]) if args else 256
 NS = [n for n in (1, 2, 4, 8, 16, 64, 256) if n <= largest]
 KS = (8, 64, 256)
 RUNS = 5
@@ -55,6 +68,90 @@ def best(*fns):
     print("   samples ms: " + " | ".join(" ".join(f"{v * 1e3:.2f}" for v in ti) for ti in t), file=sys.stderr)
     return [min(ti) * 1e3 for ti in t]
 
+
+def apply_probe():
+    import ctypes as C
+    L = kg.lib()
+    tools = "tools" in os.path.basename(os.environ.get("KMG_LIBRARY", ""))
+    proc = kg.ImageProcessor()
+    st = torch.cuda.current_stream().cuda_stream
+    rows = [f"tokyo.png {tokyo.shape[1]}x{tokyo.shape[0]} x N + N synthetic images of {len(SIZES)} sizes (2 N images per batch); wall ms, warm, minimum of {RUNS}",
+            "batch = the new call; base = what it is measured against (tools/batch_probe.py apply)",
+            f"{'':8} {'mode':>8} {'k':>4} {'2N':>4} {'batch':>10} {'base':>10} {'batch/base':>10} {'launches':>9} {'batched':>8} {'per_image':>9}"]
+    worst = {}
+
+    def row(name, mode, k, n2, t_b, t_s, rep):
+        rows.append(f"{name:8} {mode.name.lower():>8} {k:4d} {n2:4d} {t_b:10.3f} {t_s:10.3f} {t_b / t_s:10.3f} {rep.launches:9d} {rep.batched:8d} {rep.per_image:9d}")
+        print(rows[-1], file=sys.stderr, flush=True)
+
+    for k in KS:
+        pal = rng.integers(0, 256, (k, 4), dtype=np.uint8)
+        pal[:, 3] = 255
+        c4 = kg.palette_to_centroids(pal)
+        for n in [n for n in (1, 4, 16, 64, 256) if n <= largest]:
+            images = [tokyo] * n + [synthetic(i) for i in range(n)]
+            ws, hs = [im.shape[1] for im in images], [im.shape[0] for im in images]
+            rgba = [np.empty_like(im) for im in images]
+            rgba2 = [np.empty_like(im) for im in images]
+            maps = [np.empty(im.shape[:2], np.uint8) for im in images]
+            maps2 = [np.empty(im.shape[:2], np.uint8) for im in images]
+            d_imgs = [torch.from_numpy(im).cuda() for im in images]
+            d_outs = [torch.empty(im.shape[:2], dtype=torch.uint8, device="cuda") for im in images]
+            src, dst = [d.data_ptr() for d in d_imgs], [d.data_ptr() for d in d_outs]
+
+            def find_each():
+                for im, o in zip(images, maps2):
+                    L.kmg_find_indexed(proc.handle, C.c_void_p(im.ctypes.data), im.shape[1], im.shape[0], C.c_void_p(pal.ctypes.data), k, int(mode),
+                                       int(kg.OutputFormat.Index8), C.c_void_p(o.ctypes.data))
+
+            def apply_each():
+                for s, w, h, d in zip(src, ws, hs, dst):
+                    proc.apply(s, w, h, 0, c4, mode, d, st, format=kg.OutputFormat.Index8)
+
+            for mode in (kg.ReduceMode.Replace, kg.ReduceMode.Dither):
+                if tools:
+                    def with_ppt(ppt):
+                        os.environ["KMG_BATCH_APPLY_PPT"] = str(ppt)
+                        proc.apply_batch_device(src, ws, hs, c4, mode, kg.OutputFormat.Index8, dst, st)
+                    t_b, t_s = best(lambda: with_ppt(4), lambda: with_ppt(8))
+                    row("ppt 4/8", mode, k, 2 * n, t_b, t_s, proc.last_batch_apply_report)
+                    worst[(mode.name, k, 2 * n)] = 0.0
+                    continue
+                t_b, t_s = best(lambda: proc.reduce_indexed_batch(k, images, reduce_mode=mode, format=kg.OutputFormat.RGBA8, out=rgba),
+                                lambda: proc.reduce_batch(k, images, reduce_mode=mode, out=rgba2))
+                assert all(np.array_equal(a, b) for a, b in zip(rgba, rgba2))
+                row("bound", mode, k, 2 * n, t_b, t_s, proc.last_batch_apply_report)
+                worst[(mode.name, k, 2 * n)] = t_b / t_s
+                t_b, t_s = best(lambda: proc.reduce_indexed_batch(k, images, reduce_mode=mode, format=kg.OutputFormat.Index8, out=maps),
+                                lambda: proc.reduce_batch(k, images, reduce_mode=mode, out=rgba2))
+                row("index8", mode, k, 2 * n, t_b, t_s, proc.last_batch_apply_report)
+                t_b, t_s = best(lambda: proc.find_batch(images, pal, reduce_mode=mode, format=kg.OutputFormat.Index8, out=maps), find_each)
+                assert all(np.array_equal(a, b) for a, b in zip(maps, maps2))
+                row("find", mode, k, 2 * n, t_b, t_s, proc.last_batch_apply_report)
+                t_b, t_s = best(lambda: proc.apply_batch_device(src, ws, hs, c4, mode, kg.OutputFormat.Index8, dst, st), apply_each)
+                row("device", mode, k, 2 * n, t_b, t_s, proc.last_batch_apply_report)
+                if k == 256 and mode == kg.ReduceMode.Dither:
+                    # the images of this batch whose own plan prunes (k >= 128: from 16384 pixels on)
+                    big = [i for i in range(len(images)) if ws[i] * hs[i] >= 16384]
+                    pick = lambda v: [v[i] for i in big]
+
+                    def under(strategy):
+                        proc.set_strategy(strategy)
+                        proc.apply_batch_device(pick(src), pick(ws), pick(hs), c4, mode, kg.OutputFormat.Index8, pick(dst), st)
+                        proc.set_strategy("auto")
+                    t_b, t_s = best(lambda: under("scan"), lambda: under("table"))
+                    under("scan")
+                    row("pruned", mode, k, len(big), t_b, t_s, proc.last_batch_apply_report)
+    bad = {key: v for key, v in worst.items() if v > 1.10}
+    rows.append(f"largest batch / base over the bound rows: {max(worst.values()):.3f}" +
+                ("" if not bad else "; above 1.10: " + ", ".join(f"{a} k={b} 2N={c}: {v:.3f}" for (a, b, c), v in sorted(bad.items()))))
+    print("\n".join(rows))
+    proc.close()
+
+
+if APPLY:
+    apply_probe()
+    sys.exit(0)
 
 proc = kg.ImageProcessor()
 proc_init = kg.ImageProcessor(max_iterations=1)
