@@ -1,7 +1,9 @@
 // kmg_api.hip -- the host-buffer calls of the C ABI (include/kmeans_hip.h): ImageProcessor::{palette, find, reduce}
 // (core/src/lib.rs:67-164) -- argument checking (the shared checks: kmg_checks.h), upload, the host sequencing of operations.rs on
 // top of kmg_lloyd_* / kmg_dev_apply, download.  A call starts with a CallStart; kmg_find / kmg_find_indexed and kmg_reduce /
-// kmg_reduce_indexed are one body each.  There is no CPU data path in this file: every per-pixel step is a kernel launch.
+// kmg_reduce_indexed are one body each; the palette / reduce batches are one BatchCall, a function per step (their cut rule and
+// kmg_find_batch's: batch_cuts, kmg_batch_layout.h); the working image has one rule (working_enqueue, working_resolve).  There
+// is no CPU data path in this file: every per-pixel step is a kernel launch.
 
 #include "kmg_state.h"
 #include "kmg_batch_layout.h"
@@ -10,11 +12,6 @@
 // host-buffer API (ImageProcessor::{palette, find, reduce})
 // ---------------------------------------------------------------------------------------------
 namespace {
-
-struct LloydGuard {
-    kmg_lloyd *s = nullptr;
-    ~LloydGuard() { kmg_lloyd_destroy(s); }
-};
 
 int check_image(const kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h)
 {
@@ -27,49 +24,66 @@ int check_image(const kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_
 // as an image of n_kept x 1 pixels, unless every pixel is kept.  Made once per call; the buffers live as long as the object.
 // Alpha weighting (kmg_processor_set_weighting) composes here: the cutoff becomes max(alpha_cutoff, 1) -- a pixel of weight 0 is
 // not kept -- and the compaction copies whole pixels, so the weights ride in the working image's alpha bytes.
+// Made in two halves, so that a sub-batch reads the kept counts of its images back at once (BatchCall::stage_images):
+// working_enqueue, then -- cutoff != 0, with the count read back from d_count -- working_resolve.
 struct WorkingImage {
     StreamBuf small, kept;
     const uint8_t *src = nullptr;
     uint32_t sw = 0, sh = 0;
     int weighting = KMG_WEIGHT_NONE;
+    uint32_t cutoff = 0;                 // the cutoff the compaction ran with; 0 = none ran, nothing to resolve
+    uint64_t *d_count = nullptr;         // where the compaction leaves the number of kept pixels
 };
+
+// The enqueue half: the shrink (structures.rs:67-74) and the compaction on st, no synchronisation.  d_count: the device slot for
+// the kept count, or NULL = one behind the kept pixels (256-byte aligned).  spent: the buffer of d_rgba where the caller needs it
+// no longer once it is shrunk -- released as soon as the shrink is enqueued -- or NULL.
+int working_enqueue(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t alpha_cutoff, int weighting, hipStream_t st,
+                    WorkingImage &wi, uint64_t *d_count = nullptr, StreamBuf *spent = nullptr)
+{
+    wi.cutoff = working_cutoff(alpha_cutoff, weighting); wi.weighting = weighting;
+    wi.src = d_rgba; wi.sw = w; wi.sh = h;
+    const uint32_t m = p->opt.shrink_max_dim;
+    if (m && (w > m || h > m)) {
+        kmg_resized_dims(w, h, m, &wi.sw, &wi.sh);
+        HIP_TRY(wi.small.alloc(p, (size_t)wi.sw * wi.sh * 4, st));
+        KMG_TRY(kmg_dev_resize(p, d_rgba, w, h, wi.sw, wi.sh, (uint8_t *)wi.small.ptr, st));
+        wi.src = (const uint8_t *)wi.small.ptr;
+        if (spent) {
+            HIP_TRY(hipFreeAsync(spent->ptr, st));
+            spent->ptr = nullptr;
+        }
+    }
+    if (!wi.cutoff) return KMG_OK;
+    const uint64_t n = (uint64_t)wi.sw * wi.sh;
+    HIP_TRY(wi.kept.alloc(p, (size_t)n * 4 + (d_count ? 0u : 256u), st));
+    wi.d_count = d_count ? d_count : (uint64_t *)((uint8_t *)wi.kept.ptr + pad256((size_t)n * 4));
+    return kmg_dev_alpha_compact(p, wi.src, n, wi.cutoff, (uint8_t *)wi.kept.ptr, wi.d_count, st);
+}
+
+// The resolve half: with n_kept pixels kept, which buffer is the working image, and its shape.  false: the image is empty -- the
+// caller refuses it in its own words.
+bool working_resolve(WorkingImage &wi, uint64_t n_kept)
+{
+    if (n_kept && n_kept < (uint64_t)wi.sw * wi.sh) {
+        wi.src = (const uint8_t *)wi.kept.ptr;
+        wi.sw = (uint32_t)n_kept; wi.sh = 1;
+    }
+    return n_kept != 0;
+}
 
 int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t alpha_cutoff, int weighting, hipStream_t st,
                   WorkingImage &wi)
 {
-    alpha_cutoff = working_cutoff(alpha_cutoff, weighting);
-    wi.weighting = weighting;
-    const uint8_t *src = d_rgba;
-    uint32_t sw = w, sh = h;
-    StreamBuf &small = wi.small;
-    const uint32_t m = p->opt.shrink_max_dim;
-    if (m && (w > m || h > m)) {                                       // structures.rs:67-74
-        kmg_resized_dims(w, h, m, &sw, &sh);
-        HIP_TRY(small.alloc(p, (size_t)sw * sh * 4, st));
-        KMG_TRY(kmg_dev_resize(p, d_rgba, w, h, sw, sh, (uint8_t *)small.ptr, st));
-        src = (const uint8_t *)small.ptr;
-    }
-    StreamBuf &kept = wi.kept;
-    if (alpha_cutoff) {
-        const uint64_t n = (uint64_t)sw * sh;
-        HIP_TRY(kept.alloc(p, (size_t)n * 4 + 256, st));               // (the count behind the pixels, 256-byte aligned)
-        uint64_t *d_count = (uint64_t *)((uint8_t *)kept.ptr + pad256((size_t)n * 4));
-        KMG_TRY(kmg_dev_alpha_compact(p, src, n, alpha_cutoff, (uint8_t *)kept.ptr, d_count, st));
+    KMG_TRY(working_enqueue(p, d_rgba, w, h, alpha_cutoff, weighting, st, wi));
+    if (wi.cutoff) {
         uint64_t n_kept = 0;
-        HIP_TRY(hipMemcpyAsync(&n_kept, d_count, sizeof n_kept, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&n_kept, wi.d_count, sizeof n_kept, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        if (n_kept == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "no pixel reaches alpha_cutoff = %u", alpha_cutoff);
-        if (n_kept < n) {
-            src = (const uint8_t *)kept.ptr;
-            sw = (uint32_t)n_kept;
-            sh = 1;
-        }
+        if (!working_resolve(wi, n_kept)) return fail(KMG_ERR_INVALID_ARGUMENT, "no pixel reaches alpha_cutoff = %u", wi.cutoff);
     }
-    if (weighting && (uint64_t)sw * sh > kMaxWeightedPixels)
-        return fail(KMG_ERR_UNSUPPORTED, "alpha weighting: the working image has %llu pixels, more than 2^28", (unsigned long long)((uint64_t)sw * sh));
-    wi.src = src;
-    wi.sw = sw;
-    wi.sh = sh;
+    if (weighting && (uint64_t)wi.sw * wi.sh > kMaxWeightedPixels)
+        return fail(KMG_ERR_UNSUPPORTED, "alpha weighting: the working image has %llu pixels, more than 2^28", (unsigned long long)((uint64_t)wi.sw * wi.sh));
     return KMG_OK;
 }
 
@@ -228,7 +242,7 @@ int apply_and_download(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint
                        uint32_t k, int mode, uint32_t alpha_cutoff, hipStream_t st, uint8_t *out_rgba, int format)
 {
     StreamBuf out;
-    const size_t bytes = (size_t)w * h * (format == KMG_FORMAT_INDEX8 ? 1u : format == KMG_FORMAT_INDEX16 ? 2u : 4u);
+    const size_t bytes = (size_t)w * h * format_bytes(format);
     HIP_TRY(out.alloc(p, bytes, st));
     KMG_TRY(dev_apply(p, d_rgba, w, h, 0, c4, k, mode, (uint8_t *)out.ptr, st, alpha_cutoff, format));
     HIP_TRY(copy_host_image(p, out_rgba, out.ptr, bytes, hipMemcpyDeviceToHost, st));
@@ -238,9 +252,9 @@ int apply_and_download(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint
 
 // octree_palette (lib.rs:288-331) on a device-resident image: shrink to <= 128 on the device, pull
 // the <= 128x128 image, run the reference's CPU octree on it, sort ascending by palette-crate Lab L.  Alpha mode: the octree gets
-// the kept pixels of the shrunk image, in raster order.
+// the kept pixels of the shrunk image, in raster order (image: the index by which a batch names an image without one, or -1).
 int octree_palette_of(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, uint32_t color_count, uint32_t alpha_cutoff,
-                      hipStream_t st, std::vector<std::array<uint8_t, 4>> &colors)
+                      hipStream_t st, std::vector<std::array<uint8_t, 4>> &colors, int64_t image = -1)
 {
     const uint32_t MAX_SIZE = 128;                                     // lib.rs:293
     uint32_t sw = w, sh = h;
@@ -260,6 +274,7 @@ int octree_palette_of(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint3
         uint64_t n_kept = 0;
         for (uint64_t i = 0; i < n; ++i)
             if (host[4 * i + 3] >= alpha_cutoff) memmove(&host[4 * n_kept++], &host[4 * i], 4);
+        if (n_kept == 0 && image >= 0) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: no pixel reaches alpha_cutoff = %u", (uint32_t)image, alpha_cutoff);
         if (n_kept == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "no pixel reaches alpha_cutoff = %u", alpha_cutoff);
         n = n_kept;
     }
@@ -479,233 +494,214 @@ namespace {
 // 0.77 of the per-image calls at k = 8, 64 and 256.
 constexpr uint32_t kBatchMinImages = 2;
 
-// One image of a sub-batch on the device: its source, its shrunk copy, alpha mode's compacted copy, and which of them is the
-// working image (what working_image makes, but only enqueued: the kept-pixel counts of a sub-batch are read back together).
-struct BatchStage {
-    StreamBuf src, small, kept;
-    const uint8_t *work = nullptr;
-    uint32_t sw = 0, sh = 0;
-};
+enum class BatchKind { kPalette, kReduce, kReduceIndexed };   // kmg_palette_batch, kmg_reduce_batch, kmg_reduce_indexed_batch
 
-// what image (w, h) keeps on the device while its sub-batch runs (include/kmeans_hip.h at max_resident_bytes)
-uint64_t batch_resident_bytes(const kmg_processor *p, uint32_t w, uint32_t h, uint32_t alpha_cutoff, bool keep_source)
+// One image of a sub-batch on the device: its source and its working image (the octree has the source only)
+struct BatchStage { StreamBuf src; WorkingImage wi; };
+
+// What image (w, h) keeps on the device while its sub-batch runs (include/kmeans_hip.h at max_resident_bytes): the source -- a palette
+// call releases one that was shrunk --, the shrunk and the compacted copy, an indexed call's output.  The octree holds the source only.
+uint64_t batch_resident_bytes(const kmg_processor *p, uint32_t w, uint32_t h, uint32_t alpha_cutoff, BatchKind kind, int algo, int format)
 {
+    const uint64_t n = (uint64_t)w * h, out = kind == BatchKind::kReduceIndexed ? format_bytes(format) * n : 0ull;
+    if (algo == KMG_ALGO_OCTREE) return 4 * n + out;
     uint32_t sw = w, sh = h;
     const uint32_t m = p->opt.shrink_max_dim;
     const bool shrunk = m && (w > m || h > m);
     if (shrunk) kmg_resized_dims(w, h, m, &sw, &sh);
-    uint64_t bytes = shrunk ? 4ull * sw * sh : 0ull;
-    if (keep_source || !shrunk) bytes += 4ull * w * h;
-    if (alpha_cutoff) bytes += 4ull * sw * sh;
-    return bytes;
+    return (shrunk ? 4ull * sw * sh : 0ull) + (kind != BatchKind::kPalette || !shrunk ? 4 * n : 0ull) + (alpha_cutoff ? 4ull * sw * sh : 0ull) + out;
 }
 
-// Uploads images [a, b) and makes their working images; one synchronisation for the kept-pixel counts of all of them.
-// keep_source = false: a source that was shrunk is released as soon as its shrink is enqueued.
-int batch_stage(kmg_processor *p, const uint8_t *const *rgba, const uint32_t *widths, const uint32_t *heights, uint32_t a, uint32_t b,
-                uint32_t alpha_cutoff, bool keep_source, hipStream_t st, BatchStage *stage)
-{
-    const uint32_t count = b - a, m = p->opt.shrink_max_dim;
-    StreamBuf counts;
-    if (alpha_cutoff) HIP_TRY(counts.alloc(p, sizeof(uint64_t) * count, st));
-    for (uint32_t i = a; i < b; ++i) {
-        BatchStage &s = stage[i - a];
-        const uint32_t w = widths[i], h = heights[i];
-        KMG_TRY(upload_image(p, rgba[i], w, h, st, s.src));
-        s.work = (const uint8_t *)s.src.ptr;
-        s.sw = w;
-        s.sh = h;
-        if (m && (w > m || h > m)) {                                   // structures.rs:67-74
-            kmg_resized_dims(w, h, m, &s.sw, &s.sh);
-            HIP_TRY(s.small.alloc(p, (size_t)s.sw * s.sh * 4, st));
-            KMG_TRY(kmg_dev_resize(p, s.work, w, h, s.sw, s.sh, (uint8_t *)s.small.ptr, st));
-            s.work = (const uint8_t *)s.small.ptr;
-            if (!keep_source) {
-                HIP_TRY(hipFreeAsync(s.src.ptr, st));
-                s.src.ptr = nullptr;
-            }
-        }
-        if (alpha_cutoff) {
-            const uint64_t n = (uint64_t)s.sw * s.sh;
-            HIP_TRY(s.kept.alloc(p, (size_t)n * 4, st));
-            KMG_TRY(kmg_dev_alpha_compact(p, s.work, n, alpha_cutoff, (uint8_t *)s.kept.ptr, (uint64_t *)counts.ptr + (i - a), st));
-        }
-    }
-    if (!alpha_cutoff) return KMG_OK;
-    std::vector<uint64_t> n_kept(count);
-    HIP_TRY(hipMemcpyAsync(n_kept.data(), counts.ptr, sizeof(uint64_t) * count, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (uint32_t i = a; i < b; ++i) {
-        BatchStage &s = stage[i - a];
-        if (n_kept[i - a] == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: no pixel reaches alpha_cutoff = %u", i, alpha_cutoff);
-        if (n_kept[i - a] < (uint64_t)s.sw * s.sh) {
-            s.work = (const uint8_t *)s.kept.ptr;
-            s.sw = (uint32_t)n_kept[i - a];
-            s.sh = 1;
-        }
-    }
-    return KMG_OK;
-}
-
-// What kmg_reduce_indexed_batch adds to kmg_reduce_batch: the output's format, the palettes in index order (with out_counts), and
-// the output step of a sub-batch in one launch (apply_batch_download, kmg_batch_apply.hip) instead of image after image.
-struct IndexedBatch {
-    int format;
-    uint8_t *const *palettes;
-    kmg_batch_apply_report rep;
-};
-
-uint32_t format_bytes(int format) { return format == KMG_FORMAT_INDEX8 ? 1u : format == KMG_FORMAT_INDEX16 ? 2u : 4u; }
-
-// kmg_palette_batch (reduce = false) / kmg_reduce_batch / kmg_reduce_indexed_batch (reduce = true, ix)
-int batch_call(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths, const uint32_t *heights,
-               uint32_t color_count, int algo, int mode, bool reduce, uint64_t max_resident_bytes, uint8_t *const *out_rgba,
-               uint32_t *out_counts, kmg_batch_report *report, IndexedBatch *ix = nullptr)
-{
-    // the refusals, for the whole batch, before any device work (the order is part of the contract: include/kmeans_hip.h)
-    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
-    if (n_images == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "the batch is empty");
-    if (!rgba || !widths || !heights || !out_rgba || ((!reduce || ix) && !out_counts) || (ix && !ix->palettes))
-        return fail(KMG_ERR_INVALID_ARGUMENT, "a batch array is NULL");
-    for (uint32_t i = 0; i < n_images; ++i) {
-        if (!rgba[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: image pointer is NULL", i);
-        if (!out_rgba[i] || (ix && !ix->palettes[i])) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: output pointer is NULL", i);
-        if (!widths[i] || !heights[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u has zero width or height", i);
-        KMG_TRY(check_pixel_count((uint64_t)widths[i] * heights[i]));
-    }
-    KMG_TRY(check_k_nonzero(color_count));
-    KMG_TRY(check_algo(algo));
-    if (reduce) KMG_TRY(check_mode(mode));
-    if (ix) KMG_TRY(check_format(ix->format));
-    if (algo == KMG_ALGO_KMEANS) KMG_TRY(check_k_limit(color_count));
+// One call of kmg_palette_batch / kmg_reduce_batch / kmg_reduce_indexed_batch by steps: run() is the refusals, the cuts, alpha
+// mode's up-front pass, then per sub-batch a palette step (by algorithm) and an output step (by kind), and one drain at the end.
+// First the arguments.  format: KMG_FORMAT_RGBA8 unless kReduceIndexed; out: per image the palette (kPalette) or the output;
+// palettes: kReduceIndexed's palettes in index order, else NULL; out_counts: NULL for kReduce.
+struct BatchCall {
+    BatchKind kind; kmg_processor *p; uint32_t n_images;
+    const uint8_t *const *rgba; const uint32_t *widths, *heights;
+    uint32_t color_count; int algo, mode, format; uint64_t max_resident_bytes;
+    uint8_t *const *out, *const *palettes; uint32_t *out_counts;
     CallStart c;
-    c.snapshot(p);
-    const int format = ix ? ix->format : KMG_FORMAT_RGBA8;
-    if (format != KMG_FORMAT_RGBA8) {                                  // (the centroids' box: once a sub-batch has its palettes)
-        KMG_TRY(check_meld_format(mode, format));
-        KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k", color_count, c.alpha_cutoff != 0));
-    }
-    if (const uint32_t f = fixed_count(c.fixed))
-        return fail(KMG_ERR_INVALID_ARGUMENT, "a batch has no fixed colours (%u are set on the processor)", f);
-    if (c.weighting) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch has no alpha weighting (it is on for the processor)");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(c.sg.acquire(p));
-    hipStream_t st = c.sg.st;
-    const uint32_t cutoff = c.alpha_cutoff;
-    const bool octree = algo == KMG_ALGO_OCTREE;
+    hipStream_t st = nullptr;
+    std::vector<uint32_t> cuts;      // sub-batch s: images [cuts[s], cuts[s + 1])
+    std::vector<std::vector<std::array<uint8_t, 4>>> colors;   // the octree's palette of every image
+    // what the palette step of a sub-batch leaves: the centroid table of its image q has ks[q] colours and starts at c4[at[q]]
+    std::vector<float> c4; std::vector<uint32_t> ks; std::vector<size_t> at;
+    kmg_batch_report rep = {0u, 0u, 0u, 0u}; kmg_batch_apply_report arep = {0u, 0u, 0u, 0u};
+    bool octree() const { return algo == KMG_ALGO_OCTREE; }
+    bool up_front() const { return c.alpha_cutoff && cuts.size() > 2; }   // alpha mode, several sub-batches: alpha_up_front runs
+    const float *table(uint32_t q) const { return &c4[at[q]]; }
 
-    // consecutive sub-batches whose resident bytes fit the bound: images [cuts[s], cuts[s + 1])
-    const uint64_t bound = max_resident_bytes ? max_resident_bytes : (1ull << 30);
-    std::vector<uint32_t> cuts(1, 0u);
-    uint64_t held = 0;
-    for (uint32_t i = 0; i < n_images; ++i) {
-        const uint64_t bytes = (octree ? 4ull * widths[i] * heights[i] : batch_resident_bytes(p, widths[i], heights[i], cutoff, reduce)) +
-                               (ix ? (uint64_t)format_bytes(format) * widths[i] * heights[i] : 0ull);
-        if (i > cuts.back() && held + bytes > bound) { cuts.push_back(i); held = 0; }
-        held += bytes;
+    // the refusals, for the whole batch, before any device work (the order is part of the contract: include/kmeans_hip.h)
+    int refusals()
+    {
+        const bool indexed = kind == BatchKind::kReduceIndexed;
+        const bool array_null = !rgba || !widths || !heights || !out || (kind != BatchKind::kReduce && !out_counts) || (indexed && !palettes);
+        KMG_TRY(check_batch_prefix(p, n_images, array_null, "a batch array is NULL", rgba, widths, heights, out, palettes));
+        KMG_TRY(check_k_nonzero(color_count));
+        KMG_TRY(check_algo(algo));
+        if (kind != BatchKind::kPalette) KMG_TRY(check_mode(mode));
+        if (indexed) KMG_TRY(check_format(format));
+        if (!octree()) KMG_TRY(check_k_limit(color_count));
+        c.snapshot(p);
+        if (format != KMG_FORMAT_RGBA8) {                              // (the centroids' box: once a sub-batch has its palettes)
+            KMG_TRY(check_meld_format(mode, format));
+            KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k", color_count, c.alpha_cutoff != 0));
+        }
+        if (const uint32_t f = fixed_count(c.fixed)) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch has no fixed colours (%u are set on the processor)", f);
+        if (c.weighting) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch has no alpha weighting (it is on for the processor)");
+        return KMG_OK;
     }
-    cuts.push_back(n_images);
-    const size_t n_sub = cuts.size() - 1;
-    kmg_batch_report rep = {0u, 0u, (uint32_t)n_sub, 0u};
-    if (ix) ix->rep = {0u, 0u, 0u, (uint32_t)n_sub};
-    // kmg_reduce_indexed_batch: the palette in index order, as the bytes the output pass writes (reduce_call)
-    auto palette_out = [&](uint32_t i, const float *mine, uint32_t k) {
-        for (uint32_t q = 0; q < k; ++q) shader_lab_to_rgba8(mine + 4 * q, ix->palettes[i] + 4 * q);
-        out_counts[i] = k;
-    };
-
-    std::vector<std::vector<std::array<uint8_t, 4>>> colors(octree ? n_images : 0);
-    auto octree_of = [&](uint32_t i, const uint8_t *d_src) -> int {   // lib.rs:288-331
-        const int rc = octree_palette_of(p, d_src, widths[i], heights[i], color_count, cutoff, st, colors[i]);
-        if (rc == KMG_ERR_INVALID_ARGUMENT && cutoff) return fail(rc, "image %u: no pixel reaches alpha_cutoff = %u", i, cutoff);
-        return rc;
-    };
-    // Alpha mode, several sub-batches: an image that keeps no pixel has to refuse the call before the first sub-batch writes its
-    // outputs -- everything is uploaded and shrunk once up front for that alone (the octree's palettes are kept)
-    const bool up_front = cutoff && n_sub > 1;
-    if (up_front)
-        for (size_t s = 0; s < n_sub; ++s) {
-            const uint32_t a = cuts[s], b = cuts[s + 1];
-            if (octree) {
-                for (uint32_t i = a; i < b; ++i) {
-                    StreamBuf src;
-                    KMG_TRY(upload_image(p, rgba[i], widths[i], heights[i], st, src));
-                    KMG_TRY(octree_of(i, (const uint8_t *)src.ptr));
-                }
-            } else {
-                std::unique_ptr<BatchStage[]> stage(new BatchStage[b - a]);
-                KMG_TRY(batch_stage(p, rgba, widths, heights, a, b, cutoff, false, st, stage.get()));
+    // the cuts: batch_cuts over batch_resident_bytes
+    void plan()
+    {
+        std::vector<uint64_t> bytes(n_images);
+        for (uint32_t i = 0; i < n_images; ++i) bytes[i] = batch_resident_bytes(p, widths[i], heights[i], c.alpha_cutoff, kind, algo, format);
+        cuts = batch_cuts(bytes.data(), n_images, max_resident_bytes);
+        rep.sub_batches = arep.sub_batches = (uint32_t)cuts.size() - 1u;
+        colors.resize(octree() ? n_images : 0);
+    }
+    // Uploads images [a, e) and makes their working images: working_enqueue for each, one read-back and one synchronisation for the
+    // kept-pixel counts of all of them, working_resolve.  keep_source = false: a source that was shrunk is released at once.
+    int stage_images(uint32_t a, uint32_t e, bool keep_source, BatchStage *stage)
+    {
+        const uint32_t cutoff = c.alpha_cutoff;
+        StreamBuf counts;
+        if (cutoff) HIP_TRY(counts.alloc(p, sizeof(uint64_t) * (e - a), st));
+        for (uint32_t i = a; i < e; ++i) {
+            BatchStage &s = stage[i - a];
+            KMG_TRY(upload_image(p, rgba[i], widths[i], heights[i], st, s.src));
+            KMG_TRY(working_enqueue(p, (const uint8_t *)s.src.ptr, widths[i], heights[i], cutoff, KMG_WEIGHT_NONE, st, s.wi,
+                                    cutoff ? (uint64_t *)counts.ptr + (i - a) : nullptr, keep_source ? nullptr : &s.src));
+        }
+        if (!cutoff) return KMG_OK;
+        std::vector<uint64_t> n_kept(e - a);
+        HIP_TRY(hipMemcpyAsync(n_kept.data(), counts.ptr, sizeof(uint64_t) * (e - a), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t i = a; i < e; ++i)
+            if (!working_resolve(stage[i - a].wi, n_kept[i - a]))
+                return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: no pixel reaches alpha_cutoff = %u", i, cutoff);
+        return KMG_OK;
+    }
+    // An image that keeps no pixel has to refuse the call before the first sub-batch writes its outputs -- everything is uploaded and
+    // shrunk once up front for that alone.  The octree's palettes are kept, so it still runs once per image; the k-means route keeps
+    // nothing and stages every image a second time in its sub-batch.
+    int alpha_up_front()
+    {
+        for (size_t s = 0; s + 1 < cuts.size(); ++s) {
+            const uint32_t a = cuts[s], e = cuts[s + 1];
+            std::unique_ptr<BatchStage[]> stage(new BatchStage[octree() ? 0 : e - a]);
+            if (!octree()) KMG_TRY(stage_images(a, e, false, stage.get()));
+            for (uint32_t i = a; octree() && i < e; ++i) {
+                StreamBuf src;
+                KMG_TRY(upload_image(p, rgba[i], widths[i], heights[i], st, src));
+                KMG_TRY(octree_palette_of(p, (const uint8_t *)src.ptr, widths[i], heights[i], color_count, c.alpha_cutoff, st, colors[i], i));
             }
         }
-
-    std::vector<float> c4;
-    for (size_t s = 0; s < n_sub; ++s) {
-        const uint32_t a = cuts[s], b = cuts[s + 1], count = b - a;
-        std::unique_ptr<BatchStage[]> stage(new BatchStage[count]);
-        if (octree) {
-            // the host algorithm per image; the palettes of the sub-batch before its first output
-            for (uint32_t i = a; i < b; ++i) {
-                KMG_TRY(upload_image(p, rgba[i], widths[i], heights[i], st, stage[i - a].src));
-                if (!up_front) KMG_TRY(octree_of(i, (const uint8_t *)stage[i - a].src.ptr));
+        return KMG_OK;
+    }
+    // The palette step of sub-batch [a, e), octree: per image the source on the device, the host algorithm (unless it ran up front)
+    // and the centroid table.  (A palette call returns the octree's own bytes: no tables, none of octree_centroids' refusals.)
+    int palettes_octree(uint32_t a, uint32_t e, BatchStage *stage)
+    {
+        std::vector<float> mine;
+        for (uint32_t i = a; i < e; ++i) {
+            StreamBuf &src = stage[i - a].src;
+            KMG_TRY(upload_image(p, rgba[i], widths[i], heights[i], st, src));
+            if (!up_front())
+                KMG_TRY(octree_palette_of(p, (const uint8_t *)src.ptr, widths[i], heights[i], color_count, c.alpha_cutoff, st, colors[i], i));
+            if (kind != BatchKind::kPalette) {
+                KMG_TRY(octree_centroids(colors[i], mine));
+                at.push_back(c4.size()); ks.push_back((uint32_t)(mine.size() / 4));
+                c4.insert(c4.end(), mine.begin(), mine.end());
             }
-            for (uint32_t i = a; i < b; ++i) {
-                if (!reduce) {
-                    for (size_t q = 0; q < colors[i].size(); ++q) memcpy(out_rgba[i] + 4 * q, colors[i][q].data(), 4);
-                    out_counts[i] = (uint32_t)colors[i].size();
-                    continue;
-                }
-                KMG_TRY(octree_centroids(colors[i], c4));
-                KMG_TRY(apply_and_download(p, (const uint8_t *)stage[i - a].src.ptr, widths[i], heights[i], c4.data(), (uint32_t)(c4.size() / 4), mode,
-                                           cutoff, st, out_rgba[i], format));
-                if (ix) {
-                    palette_out(i, c4.data(), (uint32_t)(c4.size() / 4));
-                    ++ix->rep.per_image;
-                }
-            }
-            continue;
         }
-        KMG_TRY(batch_stage(p, rgba, widths, heights, a, b, cutoff, reduce, st, stage.get()));
-        c4.resize(4ull * color_count * count);
+        return KMG_OK;
+    }
+    // The palette step of sub-batch [a, e), k-means: the working images, then the batched kernels -- or, below kBatchMinImages, the
+    // per-image palette step, image after image.  Every table has color_count colours.
+    int palettes_kmeans(uint32_t a, uint32_t e, BatchStage *stage)
+    {
+        const uint32_t count = e - a, k = color_count;
+        KMG_TRY(stage_images(a, e, kind != BatchKind::kPalette, stage));
+        c4.resize(4ull * k * count); ks.assign(count, k);
+        std::vector<const uint8_t *> work(count); std::vector<uint32_t> sw(count), sh(count);
+        for (uint32_t q = 0; q < count; ++q) {
+            at.push_back(4ull * k * q);
+            work[q] = stage[q].wi.src; sw[q] = stage[q].wi.sw; sh[q] = stage[q].wi.sh;
+        }
         if (count < kBatchMinImages) {
-            // (too few images for the batched kernels to pay: the per-image palette step, image after image)
-            for (uint32_t q = 0; q < count; ++q)
-                KMG_TRY(kmg::palette_of_working(p, stage[q].work, stage[q].sw, stage[q].sh, color_count, st, &c4[4ull * color_count * q]));
-        } else {
-            std::vector<const uint8_t *> work(count);
-            std::vector<uint32_t> sw(count), sh(count);
-            for (uint32_t q = 0; q < count; ++q) { work[q] = stage[q].work; sw[q] = stage[q].sw; sh[q] = stage[q].sh; }
-            kmg_batch_report r;
-            KMG_TRY_DRAIN(st, dev_palette_batch(p, count, work.data(), sw.data(), sh.data(), color_count, c4.data(), nullptr, &r, st));
-            rep.launches += r.launches;
-            rep.iterations = std::max(rep.iterations, r.iterations);
-            rep.fallback += r.fallback;
+            for (uint32_t q = 0; q < count; ++q) KMG_TRY(kmg::palette_of_working(p, work[q], sw[q], sh[q], k, st, &c4[at[q]]));
+            return KMG_OK;
         }
-        if (ix) {
-            // the output step of the whole sub-batch: one launch for the images that join it, one download each
-            std::vector<const uint8_t *> src(count);
-            for (uint32_t q = 0; q < count; ++q) src[q] = (const uint8_t *)stage[q].src.ptr;
-            if (format != KMG_FORMAT_RGBA8)
-                for (uint32_t q = 0; q < count; ++q) KMG_TRY(check_index_format(&c4[4ull * color_count * q], color_count, mode, format, cutoff));
-            KMG_TRY(apply_batch_download(p, count, src.data(), widths + a, heights + a, c4.data(), count, color_count, mode, format, cutoff,
-                                         out_rgba + a, &ix->rep, st));
-            for (uint32_t i = a; i < b; ++i) palette_out(i, &c4[4ull * color_count * (i - a)], color_count);
-            continue;
-        }
-        for (uint32_t i = a; i < b; ++i) {
-            const float *mine = &c4[4ull * color_count * (i - a)];
-            if (!reduce) {
-                sorted_palette_of(mine, color_count, out_rgba[i]);     // lib.rs:255-286
-                out_counts[i] = color_count;
-                continue;
-            }
-            KMG_TRY(apply_and_download(p, (const uint8_t *)stage[i - a].src.ptr, widths[i], heights[i], mine, color_count, mode, cutoff, st,
-                                       out_rgba[i], KMG_FORMAT_RGBA8));
+        kmg_batch_report r;
+        KMG_TRY_DRAIN(st, dev_palette_batch(p, count, work.data(), sw.data(), sh.data(), k, c4.data(), nullptr, &r, st));
+        rep.launches += r.launches; rep.fallback += r.fallback;
+        rep.iterations = std::max(rep.iterations, r.iterations);
+        return KMG_OK;
+    }
+    // the output step of kmg_palette_batch: the octree's colours as they are, the k-means centroids as the sorted palette (lib.rs:255-286)
+    void output_palette(uint32_t a, uint32_t e)
+    {
+        for (uint32_t i = a; i < e; ++i) {
+            if (!octree()) sorted_palette_of(table(i - a), color_count, out[i]);
+            for (size_t q = 0; octree() && q < colors[i].size(); ++q) memcpy(out[i] + 4 * q, colors[i][q].data(), 4);
+            out_counts[i] = octree() ? (uint32_t)colors[i].size() : color_count;
         }
     }
-    HIP_TRY(hipStreamSynchronize(st));
-    if (report) *report = rep;
-    return KMG_OK;
-}
+    // kmg_reduce_indexed_batch: the palette of image a + q in index order, as the bytes the output pass writes (reduce_call)
+    void palette_out(uint32_t a, uint32_t q)
+    {
+        for (uint32_t j = 0; j < ks[q]; ++j) shader_lab_to_rgba8(table(q) + 4 * j, palettes[a + q] + 4 * j);
+        out_counts[a + q] = ks[q];
+    }
+    // the output step of kmg_reduce_batch, and of kmg_reduce_indexed_batch after the octree (palette sizes differ): the per-image output pass
+    int output_each(uint32_t a, uint32_t e, const BatchStage *stage)
+    {
+        for (uint32_t q = 0; q < e - a; ++q) {
+            KMG_TRY(apply_and_download(p, (const uint8_t *)stage[q].src.ptr, widths[a + q], heights[a + q], table(q), ks[q], mode, c.alpha_cutoff, st,
+                                       out[a + q], format));
+            if (kind == BatchKind::kReduceIndexed) palette_out(a, q);
+        }
+        if (kind == BatchKind::kReduceIndexed) arep.per_image += e - a;
+        return KMG_OK;
+    }
+    // the output step of kmg_reduce_indexed_batch after k-means: one launch for the images that join it, one download each (kmg_batch_apply.hip)
+    int output_joined(uint32_t a, uint32_t e, const BatchStage *stage)
+    {
+        const uint32_t count = e - a, k = color_count;
+        std::vector<const uint8_t *> src(count);
+        for (uint32_t q = 0; q < count; ++q) src[q] = (const uint8_t *)stage[q].src.ptr;
+        if (format != KMG_FORMAT_RGBA8)
+            for (uint32_t q = 0; q < count; ++q) KMG_TRY(check_index_format(table(q), k, mode, format, c.alpha_cutoff));
+        KMG_TRY(apply_batch_download(p, count, src.data(), widths + a, heights + a, c4.data(), count, k, mode, format, c.alpha_cutoff, out + a, &arep,
+                                     st));
+        for (uint32_t q = 0; q < count; ++q) palette_out(a, q);
+        return KMG_OK;
+    }
+    int run(kmg_batch_report *report, kmg_batch_apply_report *apply_report = nullptr)
+    {
+        KMG_TRY(refusals());
+        HIP_TRY(hipSetDevice(p->device));
+        HIP_TRY(c.sg.acquire(p));
+        st = c.sg.st;
+        plan();
+        if (up_front()) KMG_TRY(alpha_up_front());
+        for (size_t s = 0; s + 1 < cuts.size(); ++s) {
+            const uint32_t a = cuts[s], e = cuts[s + 1];
+            std::unique_ptr<BatchStage[]> stage(new BatchStage[e - a]);
+            c4.clear(); ks.clear(); at.clear();
+            KMG_TRY(octree() ? palettes_octree(a, e, stage.get()) : palettes_kmeans(a, e, stage.get()));
+            if (kind == BatchKind::kPalette) output_palette(a, e);
+            else if (kind == BatchKind::kReduce || octree()) KMG_TRY(output_each(a, e, stage.get()));
+            else KMG_TRY(output_joined(a, e, stage.get()));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        if (report) *report = rep;
+        if (apply_report) *apply_report = arep;
+        return KMG_OK;
+    }
+};
 
 }  // namespace
 
@@ -713,8 +709,8 @@ extern "C" int kmg_palette_batch(kmg_processor *p, uint32_t n_images, const uint
                                  const uint32_t *heights, uint32_t color_count, int algo, uint64_t max_resident_bytes,
                                  uint8_t *const *out_rgba, uint32_t *out_counts, kmg_batch_report *report)
 try {
-    return batch_call(p, n_images, rgba, widths, heights, color_count, algo, KMG_MODE_REPLACE, false, max_resident_bytes, out_rgba, out_counts,
-                      report);
+    return BatchCall{BatchKind::kPalette, p, n_images, rgba, widths, heights, color_count, algo, KMG_MODE_REPLACE, KMG_FORMAT_RGBA8,
+                     max_resident_bytes, out_rgba, nullptr, out_counts}.run(report);
 }
 KMG_ABI_CATCH
 
@@ -722,7 +718,8 @@ extern "C" int kmg_reduce_batch(kmg_processor *p, uint32_t n_images, const uint8
                                 const uint32_t *heights, uint32_t color_count, int algo, int mode, uint64_t max_resident_bytes,
                                 uint8_t *const *out_rgba, kmg_batch_report *report)
 try {
-    return batch_call(p, n_images, rgba, widths, heights, color_count, algo, mode, true, max_resident_bytes, out_rgba, nullptr, report);
+    return BatchCall{BatchKind::kReduce, p, n_images, rgba, widths, heights, color_count, algo, mode, KMG_FORMAT_RGBA8,
+                     max_resident_bytes, out_rgba, nullptr, nullptr}.run(report);
 }
 KMG_ABI_CATCH
 
@@ -731,11 +728,8 @@ extern "C" int kmg_reduce_indexed_batch(kmg_processor *p, uint32_t n_images, con
                                         uint64_t max_resident_bytes, uint8_t *const *out_palette_rgba, uint32_t *out_counts,
                                         void *const *out_index, kmg_batch_report *batch_report, kmg_batch_apply_report *apply_report)
 try {
-    IndexedBatch ix = {format, out_palette_rgba, {0u, 0u, 0u, 0u}};
-    KMG_TRY(batch_call(p, n_images, rgba, widths, heights, color_count, algo, mode, true, max_resident_bytes, (uint8_t *const *)out_index,
-                       out_counts, batch_report, &ix));
-    if (apply_report) *apply_report = ix.rep;
-    return KMG_OK;
+    return BatchCall{BatchKind::kReduceIndexed, p, n_images, rgba, widths, heights, color_count, algo, mode, format,
+                     max_resident_bytes, (uint8_t *const *)out_index, out_palette_rgba, out_counts}.run(batch_report, apply_report);
 }
 KMG_ABI_CATCH
 
@@ -748,15 +742,7 @@ int find_batch_call(kmg_processor *p, uint32_t n_images, const uint8_t *const *r
                     kmg_batch_apply_report *report)
 {
     // the refusals, for the whole batch, before any device work (the order is part of the contract: include/kmeans_hip.h)
-    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
-    if (n_images == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "the batch is empty");
-    if (!rgba || !widths || !heights || !out) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch array is NULL");
-    for (uint32_t i = 0; i < n_images; ++i) {
-        if (!rgba[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: image pointer is NULL", i);
-        if (!out[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: output pointer is NULL", i);
-        if (!widths[i] || !heights[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u has zero width or height", i);
-        KMG_TRY(check_pixel_count((uint64_t)widths[i] * heights[i]));
-    }
+    KMG_TRY(check_batch_prefix(p, n_images, !rgba || !widths || !heights || !out, "a batch array is NULL", rgba, widths, heights, out));
     if (!palette_rgba || n_colors == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "palette is empty");
     KMG_TRY(check_mode(mode));
     KMG_TRY(check_format(format));
@@ -771,19 +757,13 @@ int find_batch_call(kmg_processor *p, uint32_t n_images, const uint8_t *const *r
     HIP_TRY(c.sg.acquire(p));
     hipStream_t st = c.sg.st;
 
-    // consecutive sub-batches whose resident bytes (source and output) fit the bound: images [a, b)
-    const uint64_t bound = max_resident_bytes ? max_resident_bytes : (1ull << 30);
+    // consecutive sub-batches whose resident bytes (source and output) fit the bound: images [a, a + count)
     kmg_batch_apply_report rep = {0u, 0u, 0u, 0u};
-    std::vector<uint64_t> pixels(n_images), offset;
-    for (uint32_t i = 0; i < n_images; ++i) pixels[i] = (uint64_t)widths[i] * heights[i];
-    for (uint32_t a = 0, b; a < n_images; a = b) {
-        uint64_t held = 0;
-        for (b = a; b < n_images; ++b) {
-            const uint64_t bytes = (4ull + bpp) * pixels[b];
-            if (b > a && held + bytes > bound) break;
-            held += bytes;
-        }
-        const uint32_t count = b - a;
+    std::vector<uint64_t> pixels(n_images), bytes(n_images), offset;
+    for (uint32_t i = 0; i < n_images; ++i) { pixels[i] = (uint64_t)widths[i] * heights[i]; bytes[i] = (4ull + bpp) * pixels[i]; }
+    const std::vector<uint32_t> cuts = batch_cuts(bytes.data(), n_images, max_resident_bytes);
+    for (size_t s = 0; s + 1 < cuts.size(); ++s) {
+        const uint32_t a = cuts[s], count = cuts[s + 1] - a;
         uint64_t total = 0;
         if (!batch_offsets(&pixels[a], count, 4u, offset, &total, (uint64_t)SIZE_MAX / 2))
             return fail(KMG_ERR_OUT_OF_MEMORY, "the sources of the sub-batch do not fit one block");
@@ -885,7 +865,7 @@ try {
     KMG_TRY(check_index8_room(form == kErrorIndex8, "k", k, c.alpha_cutoff != 0));
     KMG_TRY(c.begin(p, src_rgba, w, h));
     hipStream_t st = c.sg.st;
-    const size_t n = (size_t)w * h, out_bytes = n * (form == kErrorIndex8 ? 1u : form == kErrorIndex16 ? 2u : 4u);
+    const size_t n = (size_t)w * h, out_bytes = n * format_bytes(format);
     StreamBuf res, rec;
     HIP_TRY(res.alloc(p, out_bytes, st));
     HIP_TRY(copy_host_image(p, res.ptr, out, out_bytes, hipMemcpyHostToDevice, st));

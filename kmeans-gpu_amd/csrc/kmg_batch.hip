@@ -220,11 +220,6 @@ __global__ __launch_bounds__(kBlock) void k_batch_gather(const BatchImage *__res
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-struct LloydGuard {
-    kmg_lloyd *s = nullptr;
-    ~LloydGuard() { kmg_lloyd_destroy(s); }
-};
-
 // the batch takes working images below this many pixels: the PPT = 1 tiling of the small-image route (kmg_kernels.hip assign_ppt)
 constexpr uint64_t kBatchMaxPixels = 1ull << 19;
 // (workgroups of one batched launch at most: kBatchMaxGrid, kmg_batch_layout.h)
@@ -354,14 +349,7 @@ int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *
 int kmg::dev_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths, const uint32_t *heights,
                            uint32_t k, float *centroids4, uint32_t *iterations, kmg_batch_report *report, hipStream_t st)
 {
-    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
-    if (n_images == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "the batch is empty");
-    if (!d_rgba || !widths || !heights || !centroids4) return fail(KMG_ERR_INVALID_ARGUMENT, "bad palette_batch arguments");
-    for (uint32_t i = 0; i < n_images; ++i) {
-        if (!d_rgba[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: image pointer is NULL", i);
-        if (!widths[i] || !heights[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u has zero width or height", i);
-        KMG_TRY(check_pixel_count((uint64_t)widths[i] * heights[i]));
-    }
+    KMG_TRY(check_batch_prefix(p, n_images, !d_rgba || !widths || !heights || !centroids4, "bad palette_batch arguments", d_rgba, widths, heights));
     KMG_TRY(check_k(k));
     HIP_TRY(hipSetDevice(p->device));
     kmg_batch_report rep = {0u, 0u, 1u, 0u};

@@ -207,7 +207,7 @@ int kmg::apply_batch_download(kmg_processor *p, uint32_t n_images, const uint8_t
                               const uint32_t *heights, const float *c4, uint32_t n_tables, uint32_t k, int mode, int format, uint32_t cutoff,
                               uint8_t *const *out, kmg_batch_apply_report *report, hipStream_t st)
 {
-    const uint32_t bpp = format == KMG_FORMAT_INDEX8 ? 1u : format == KMG_FORMAT_INDEX16 ? 2u : 4u;
+    const uint32_t bpp = format_bytes(format);
     std::vector<uint64_t> pixels(n_images), offset;
     for (uint32_t i = 0; i < n_images; ++i) pixels[i] = (uint64_t)widths[i] * heights[i];
     uint64_t total = 0;
@@ -229,15 +229,7 @@ extern "C" int kmg_dev_apply_batch(kmg_processor *p, uint32_t n_images, const ui
                                    void *const *d_out, kmg_batch_apply_report *report, void *stream)
 try {
     // the refusals, for the whole batch, before any device work (the order is part of the contract: include/kmeans_hip.h)
-    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
-    if (n_images == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "the batch is empty");
-    if (!d_rgba || !widths || !heights || !centroids4 || !d_out) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch array is NULL");
-    for (uint32_t i = 0; i < n_images; ++i) {
-        if (!d_rgba[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: image pointer is NULL", i);
-        if (!d_out[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: output pointer is NULL", i);
-        if (!widths[i] || !heights[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u has zero width or height", i);
-        KMG_TRY(check_pixel_count((uint64_t)widths[i] * heights[i]));
-    }
+    KMG_TRY(check_batch_prefix(p, n_images, !d_rgba || !widths || !heights || !centroids4 || !d_out, "a batch array is NULL", d_rgba, widths, heights, d_out));
     KMG_TRY(check_k_nonzero(k));
     KMG_TRY(check_mode(mode));
     KMG_TRY(check_format(format));

@@ -16,6 +16,24 @@ constexpr uint64_t kBatchMaxGrid = 1ull << 20;
 // (the vector paths are taken for four pixels in range only)
 constexpr uint64_t kBatchAlign = 16;
 
+constexpr uint64_t kBatchDefaultResident = 1ull << 30;   // what max_resident_bytes = 0 stands for (include/kmeans_hip.h)
+
+// The sub-batches of n >= 1 images that keep bytes[i] on the device each: consecutive images [c[s], c[s + 1]), 0 = c[0] < ... < c[m] = n,
+// filled greedily -- image i opens a new one when it is not the first of its own and the bytes held plus its own exceed the bound
+// (0 = kBatchDefaultResident); an image larger than the bound is alone.  No sum wraps: a sub-batch that has an image grows within the bound.
+inline std::vector<uint32_t> batch_cuts(const uint64_t *bytes, uint32_t n, uint64_t bound)
+{
+    if (!bound) bound = kBatchDefaultResident;
+    std::vector<uint32_t> cuts(1, 0u);
+    uint64_t held = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (i > cuts.back() && (held > bound || bytes[i] > bound - held)) { cuts.push_back(i); held = 0; }
+        held += bytes[i];
+    }
+    cuts.push_back(n);
+    return cuts;
+}
+
 // Packed block: offset[i] = the byte offset of image i (pixels[i] pixels of bytes_per_pixel bytes), *total = the bytes of the block.
 // false: a size does not fit 64 bits or the block would exceed `limit` bytes; nothing is to be allocated then.
 inline bool batch_offsets(const uint64_t *pixels, uint32_t m, uint32_t bytes_per_pixel, std::vector<uint64_t> &offset, uint64_t *total,

@@ -26,6 +26,25 @@ static inline int check_image_buffer(const void *rgba, uint32_t w, uint32_t h)
     return check_image_size(w, h);
 }
 
+// The refusals every batch call starts with, in the order that is part of the contract (include/kmeans_hip.h at kmg_batch_report):
+// processor, empty batch, the call's arrays (array_null: one of them is NULL; array_message: how the call words that), then image by
+// image a NULL image, a NULL entry of a per-image output array (out_a, out_b: NULL = the call has none), a zero side, 2^32-1 pixels.
+template <typename Image, typename OutA = void, typename OutB = void>
+static inline int check_batch_prefix(const void *p, uint32_t n_images, bool array_null, const char *array_message, Image *const *images,
+                                     const uint32_t *widths, const uint32_t *heights, OutA *const *out_a = nullptr, OutB *const *out_b = nullptr)
+{
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
+    if (n_images == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "the batch is empty");
+    if (array_null) return fail(KMG_ERR_INVALID_ARGUMENT, "%s", array_message);
+    for (uint32_t i = 0; i < n_images; ++i) {
+        if (!images[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: image pointer is NULL", i);
+        if ((out_a && !out_a[i]) || (out_b && !out_b[i])) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: output pointer is NULL", i);
+        if (!widths[i] || !heights[i]) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u has zero width or height", i);
+        KMG_TRY(check_pixel_count((uint64_t)widths[i] * heights[i]));
+    }
+    return KMG_OK;
+}
+
 // the colour count (args.rs:160-171), its two halves for the calls that refuse something else in between
 static inline int check_k_nonzero(uint32_t k)
 {

@@ -259,8 +259,6 @@ struct kmg_sequence {
 
 namespace {
 
-size_t format_bytes(int format) { return format == KMG_FORMAT_INDEX8 ? 1u : format == KMG_FORMAT_INDEX16 ? 2u : 4u; }
-
 // ends the open output: the plan and the frame block go back to the processor (the sequence's stream is drained first)
 void output_end(kmg_sequence *s)
 {

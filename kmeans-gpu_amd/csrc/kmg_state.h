@@ -132,6 +132,8 @@ static inline uint32_t working_cutoff(uint32_t alpha_cutoff, int weighting) { re
 constexpr uint64_t kMaxWeightedPixels = 1ull << 28;
 
 static inline size_t pad256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
+// bytes per pixel of an output in `format` (kmg_output_format)
+static inline uint32_t format_bytes(int format) { return format == KMG_FORMAT_INDEX8 ? 1u : format == KMG_FORMAT_INDEX16 ? 2u : 4u; }
 
 struct ProfEvent { int id; hipEvent_t e0, e1; };
 
@@ -234,6 +236,9 @@ struct DevBuf {
     ~DevBuf() { if (ptr) (void)hipFree(ptr); }
     hipError_t alloc(size_t bytes) { return hipMalloc(&ptr, bytes); }
 };
+
+// a Lloyd problem that lives for one call
+struct LloydGuard { kmg_lloyd *s = nullptr; ~LloydGuard() { kmg_lloyd_destroy(s); } };
 
 // scratch that lives for one call on one stream: stream-ordered allocation from the device's memory
 // pool (a reused block after the first call instead of a ~0.1 ms hipMalloc + hipFree pair)

@@ -1,5 +1,5 @@
-// check_batch_layout.cpp -- the host arithmetic of the batched output pass: the packed blocks, the grid and its cuts into launches
-// (csrc/kmg_batch_layout.h) and the rule for which images join the launch (csrc/kmg_apply_route.h batch_apply_joins), the latter over
+// check_batch_layout.cpp -- the host arithmetic of the batches: the packed blocks, the grid and its cuts into launches, the cuts of a
+// batch into sub-batches (csrc/kmg_batch_layout.h) and the rule for which images join the launch (csrc/kmg_apply_route.h batch_apply_joins), the latter over
 // the grid of (mode, k, n, forced, mask_words) of apply_route_table.txt, which check_apply_route.cpp walks.  Stops at the first
 // difference.  Host code only: built plain and with -fsanitize=address,undefined by tests/test_batch_layout.py.
 #include <cinttypes>
@@ -79,6 +79,63 @@ static int check_layout()
     return 0;
 }
 
+// the greedy rule of the sub-batches, written out once more (sums that cannot wrap here: the callers keep them small)
+static std::vector<uint32_t> expected_cuts(const std::vector<uint64_t> &bytes, uint64_t bound)
+{
+    std::vector<uint32_t> cuts(1, 0u);
+    uint64_t held = 0;
+    for (uint32_t i = 0; i < bytes.size(); ++i) {
+        if (i > cuts.back() && held + bytes[i] > bound) { cuts.push_back(i); held = 0; }
+        held += bytes[i];
+    }
+    cuts.push_back((uint32_t)bytes.size());
+    return cuts;
+}
+
+static int check_cuts()
+{
+    using namespace kmg;
+    std::vector<uint64_t> bytes;
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < 40; ++i) { bytes.push_back(1 + (i * 17) % 40); sum += bytes.back(); }
+    const uint32_t n = (uint32_t)bytes.size();
+    // everything fits: one sub-batch; a bound below every image: one image each
+    CHECK((batch_cuts(bytes.data(), n, sum) == std::vector<uint32_t>{0, n}));
+    CHECK((batch_cuts(bytes.data(), n, UINT64_MAX) == std::vector<uint32_t>{0, n}));
+    const std::vector<uint64_t> big(5, 7);
+    const std::vector<uint32_t> each = batch_cuts(big.data(), 5, 6);
+    CHECK((each == std::vector<uint32_t>{0, 1, 2, 3, 4, 5}));
+    // pixel counts 1 .. 40 in mixed order over a range of bounds: the greedy loop; [0, n) once and in order; no sub-batch of two
+    // images or more above the bound, and none that the next image would still have fitted
+    for (uint64_t bound = 1; bound <= sum + 1; ++bound) {
+        const std::vector<uint32_t> cuts = batch_cuts(bytes.data(), n, bound);
+        CHECK(cuts == expected_cuts(bytes, bound));
+        CHECK(cuts.size() >= 2 && cuts.front() == 0 && cuts.back() == n);
+        for (size_t s = 0; s + 1 < cuts.size(); ++s) {
+            CHECK(cuts[s] < cuts[s + 1]);
+            uint64_t held = 0;
+            for (uint32_t i = cuts[s]; i < cuts[s + 1]; ++i) held += bytes[i];
+            CHECK(held <= bound || cuts[s + 1] - cuts[s] == 1);
+            CHECK(cuts[s + 1] == n || held + bytes[cuts[s + 1]] > bound);
+        }
+    }
+    // bound == 0 is 2^30
+    const uint64_t gib[4] = {1ull << 29, 1ull << 29, 1, (1ull << 30) + 5};
+    CHECK(kBatchDefaultResident == 1ull << 30);
+    CHECK((batch_cuts(gib, 4, 0) == std::vector<uint32_t>{0, 2, 3, 4}));
+    CHECK(batch_cuts(gib, 4, 0) == batch_cuts(gib, 4, 1ull << 30));
+    CHECK((batch_cuts(gib, 2, 0) == std::vector<uint32_t>{0, 2}));
+    // sizes of 2^63 and above: held + bytes would wrap to a small number and join what does not fit
+    const uint64_t huge[5] = {1ull << 63, 1ull << 63, 3, UINT64_MAX, 2};
+    CHECK((batch_cuts(huge, 5, UINT64_MAX) == std::vector<uint32_t>{0, 1, 3, 4, 5}));
+    CHECK((batch_cuts(huge, 5, 1ull << 63) == std::vector<uint32_t>{0, 1, 2, 3, 4, 5}));
+    CHECK((batch_cuts(huge, 5, 10) == std::vector<uint32_t>{0, 1, 2, 3, 4, 5}));
+    const uint64_t tail[3] = {4, UINT64_MAX - 4, 1};
+    CHECK((batch_cuts(tail, 3, UINT64_MAX) == std::vector<uint32_t>{0, 2, 3}));
+    CHECK((batch_cuts(tail, 3, UINT64_MAX - 1) == std::vector<uint32_t>{0, 1, 3}));
+    return 0;
+}
+
 // the rule, written out once more: what its own plan would scan joins, and -- a batch of two images or more, forced == 0,
 // 128 <= k <= 512 -- a dither image that a plan prunes only for the latency of one image's scan (n (0.255 k - 0.3) <= 45e6 ps);
 // never meld or diffusion
@@ -93,7 +150,7 @@ static bool expected_join(int mode, uint32_t k, uint64_t n, int forced, int rout
 int main(int argc, char **argv)
 {
     if (argc != 2) { fprintf(stderr, "usage: check_batch_layout apply_route_table.txt\n"); return 2; }
-    if (check_layout()) return 1;
+    if (check_layout() || check_cuts()) return 1;
     FILE *f = fopen(argv[1], "r");
     if (!f) { perror(argv[1]); return 2; }
     static char line[1 << 16];
@@ -130,6 +187,6 @@ int main(int argc, char **argv)
         }
     }
     fclose(f);
-    printf("layout ok; rows %lu points %lu joined %lu scan %lu widened %lu join_mismatches 0\n", rows, points, joined, scan, widened);
+    printf("layout ok; cuts ok; rows %lu points %lu joined %lu scan %lu widened %lu join_mismatches 0\n", rows, points, joined, scan, widened);
     return rows == 4 * 11 * 3 * 2 && joined == scan + widened && scan > 0 ? 0 : 1;
 }

@@ -534,3 +534,47 @@ def test_cli_batch_indexed_writes_palette_pngs(torch_cuda, tmp_path, capsys, cut
             kept = im[..., 3] >= cutoff
             assert np.array_equal(got[kept][:, :3], want[kept][:, :3]) and np.all(got[kept][:, 3] == 255), i
             assert np.all(got[~kept][:, 3] == 0), i
+
+
+# ---- 10. sub-batches: the cuts of kmg_find_batch, the up-front alpha pass, the octree image by image --------------------------------
+@pytest.mark.parametrize("fmt", [RGBA8, INDEX8, INDEX16])
+def test_find_batch_in_several_sub_batches(processor, fmt):
+    """six images of one size: a cut after every second image (the bound two images' source and output), then one after every image"""
+    same = [_noise(90 + i, 30, 40) for i in range(6)]
+    pal = _palette(8, 8)
+    want = [find_one(processor, im, pal, DITHER, fmt) for im in same]
+    got, rep = find_batch(processor, same, pal, DITHER, fmt, bound=2 * 1200 * (4 + BPP[fmt]))
+    assert (rep.sub_batches, rep.batched, rep.per_image) == (3, 6, 0), rep
+    assert all(np.array_equal(g, w) for g, w in zip(got, want))
+    got, rep = find_batch(processor, same, pal, DITHER, fmt, bound=1)
+    assert rep.sub_batches == 6 and rep.batched + rep.per_image == 6, rep
+    assert all(np.array_equal(g, w) for g, w in zip(got, want))
+
+
+@pytest.mark.parametrize("algo", [0, 1], ids=["kmeans", "octree"])
+def test_reduce_indexed_batch_image_without_a_kept_pixel(torch_cuda, algo):
+    """an image that keeps no pixel refuses the whole call before any output is written, in one sub-batch and in one per image (the
+    up-front alpha pass); without it, a sub-batch per image gives the bytes of kmg_reduce_indexed"""
+    import kmeans_gpu_amd as kg
+    images = _alpha_images()
+    empty = _noise(26, 30, 41)
+    empty[..., 3] = 127
+    k = 8
+    with kg.ImageProcessor(alpha_cutoff=128) as proc:
+        for bound in (0, 1):
+            rc, pals, counts, bufs, _, msg = raw_reduce_batch(proc, images[:3] + [empty] + images[3:], k, DITHER, INDEX8, algo=algo, bound=bound)
+            assert rc == INVALID and "image 3" in msg, (bound, rc, msg)
+            assert all(b.untouched() for b in bufs + pals) and np.all(counts == 0xA5A5A5A5), bound
+        got, (brep, arep) = reduce_batch(proc, images, k, DITHER, INDEX8, algo=algo, bound=1)
+        assert (brep.sub_batches, arep.sub_batches) == (len(images), len(images))
+        assert _same_pairs(got, [reduce_one(proc, im, k, DITHER, INDEX8, algo=algo) for im in images])
+
+
+def test_octree_reduce_indexed_batch_image_by_image(processor, edge_images):
+    """the octree at a sub-batch per image: the host algorithm and the per-image output pass, nothing batched"""
+    images = edge_images[3:9] + edge_images[-1:]
+    n = len(images)
+    got, (brep, arep) = reduce_batch(processor, images, 8, DITHER, INDEX8, algo=1, bound=1)
+    assert (arep.per_image, arep.batched, arep.launches, arep.sub_batches) == (n, 0, 0, n), arep
+    assert (brep.sub_batches, brep.launches) == (n, 0), brep
+    assert _same_pairs(got, [reduce_one(processor, im, 8, DITHER, INDEX8, algo=1) for im in images])
