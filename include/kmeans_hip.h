@@ -293,7 +293,9 @@ KMG_API int kmg_reduce_indexed(kmg_processor *p, const uint8_t *rgba, uint32_t w
  * Per-image steps.  The shrink and alpha mode's compaction are the existing ones (kmg_dev_resize, kmg_dev_alpha_compact), enqueued
  * per image; the kept-pixel counts of a sub-batch come back in one copy.  A working image of 2^19 pixels or more (shrink off or
  * shrink_max_dim large) takes the per-image path inside the call and counts in `fallback`.  KMG_ALGO_OCTREE runs the host
- * algorithm per image (the report stays 0 apart from sub_batches).  kmg_reduce_batch's output step is the per-image output pass at
+ * algorithm per image (the report stays 0 apart from sub_batches).  A sub-batch of ONE image (a batch of one, or max_resident_bytes
+ * cutting an image off alone) takes the per-image palette step of kmg_palette: no batched launch, so `launches` counts none for it;
+ * `iterations` covers it all the same.  kmg_reduce_batch's output step is the per-image output pass at
  * full size with that image's centroids; the sources stay on the device between their shrink and their output pass.
  *
  * max_resident_bytes (0 = 1 GiB) bounds what a call keeps on the device at once: the batch is cut into consecutive sub-batches

@@ -93,7 +93,7 @@ int working_image(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t 
 // d_labels (optional): the u32 label of every pixel of the working image under the final centroids (find_centroid.wgsl:15-44, the
 // label KMG_MODE_REPLACE gives the pixel).
 int kmg::palette_of_working(kmg_processor *p, const uint8_t *src, uint32_t sw, uint32_t sh, uint32_t k, hipStream_t st, float *c4,
-                            uint32_t *d_labels, const float *fixed4, uint32_t n_fixed, int weighting)
+                            uint32_t *d_labels, const float *fixed4, uint32_t n_fixed, int weighting, uint32_t *iterations)
 {
     LloydGuard g;
     if (weighting && (uint64_t)sw * sh > kMaxWeightedPixels)
@@ -115,6 +115,7 @@ int kmg::palette_of_working(kmg_processor *p, const uint8_t *src, uint32_t sw, u
     uint32_t it = 0;
     KMG_TRY(kmg_lloyd_run(g.s, src, (uint64_t)sw * sh, nullptr, &it, st));  // operations.rs:85
     KMG_TRY(kmg_lloyd_get_centroids(g.s, c4, st));
+    if (iterations) *iterations = it;
     if (log_debug()) {
         fprintf(stderr, "[kmeans_hip] == Final centroids at iteration %u: ==\n", it);
         for (uint32_t i = 0; i < k; ++i)
@@ -631,7 +632,11 @@ struct BatchCall {
             work[q] = stage[q].wi.src; sw[q] = stage[q].wi.sw; sh[q] = stage[q].wi.sh;
         }
         if (count < kBatchMinImages) {
-            for (uint32_t q = 0; q < count; ++q) KMG_TRY(kmg::palette_of_working(p, work[q], sw[q], sh[q], k, st, &c4[at[q]]));
+            for (uint32_t q = 0; q < count; ++q) {                   // (no batched launch; the report's iterations cover the image all the same)
+                uint32_t it = 0;
+                KMG_TRY(kmg::palette_of_working(p, work[q], sw[q], sh[q], k, st, &c4[at[q]], nullptr, nullptr, 0, KMG_WEIGHT_NONE, &it));
+                rep.iterations = std::max(rep.iterations, it);
+            }
             return KMG_OK;
         }
         kmg_batch_report r;

@@ -98,9 +98,10 @@ int apply_batch_download(kmg_processor *p, uint32_t n_images, const uint8_t *con
 // problem of k centroids (initialisation + loop with the processor's options).  Synchronises `st`.  d_labels: optional label map.
 // fixed4 / n_fixed (kmg_processor_set_fixed_colors; n_fixed <= k): the Lab of the pinned entries -- centroids 0 .. n_fixed - 1 start
 // there and stay, the rest is initialised and moves around them.  weighting (KMG_WEIGHT_*): the loop's sums weigh each pixel by its
-// alpha byte; the initialisation does not.
+// alpha byte; the initialisation does not.  iterations (may be NULL): where kmg_lloyd_run stopped.
 int palette_of_working(kmg_processor *p, const uint8_t *d_src, uint32_t sw, uint32_t sh, uint32_t k, hipStream_t st, float *centroids4,
-                       uint32_t *d_labels = nullptr, const float *fixed4 = nullptr, uint32_t n_fixed = 0, int weighting = KMG_WEIGHT_NONE);
+                       uint32_t *d_labels = nullptr, const float *fixed4 = nullptr, uint32_t n_fixed = 0, int weighting = KMG_WEIGHT_NONE,
+                       uint32_t *iterations = nullptr);
 // kmg_dev_palette_batch on a hipStream_t (kmg_batch.hip): the k-means palette step of many working images in device memory, the
 // small ones through the batched kernels.  Synchronises `st`.
 int dev_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths, const uint32_t *heights,

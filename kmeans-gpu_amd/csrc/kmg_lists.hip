@@ -376,7 +376,9 @@ __global__ __launch_bounds__(kBlock) void k_dither_lists(const uint32_t *__restr
                 best = min(best, best1);
             }
             const float thr = tie_threshold(__uint_as_float(best));
-            const bool near = __uint_as_float(second) <= thr || best >= kSentinelFloor || !(pt.L < 9000.0f);
+            // (two halves: the runner-up without its index byte.  At a key of exactly 0 -- the pixel lies on two equal centroids, one
+            // in each half -- the threshold is 0 too and the index bytes alone would order the pair, the second half's low byte first)
+            const bool near = __uint_as_float(HALVES == 2 ? second & ~255u : second) <= thr || best >= kSentinelFloor || !(pt.L < 9000.0f);
             if (__ballot(near)) {
                 // near-tie (kmg_math.h): mix_colors.wgsl:73-80 with the literal distance, the sentinel first, same order.  Rare:
                 // the lists are read again, byte by byte
@@ -634,6 +636,8 @@ __global__ __launch_bounds__(kBlock) void k_meld_lists(const uint32_t *__restric
                 const uint32_t m1 = min(k1, c1), m2 = min(min(k2, c2), max(k1, c1));
                 const uint32_t m3 = min(min(k3, c3), min(max(k2, c1), max(k1, c2)));
                 // (keys of the two halves that are EQUAL are a near-tie: the literal scan below decides, whatever these say)
+                // (at a key of exactly 0 the tie threshold is 0 and the index bytes alone order equal centroids of the two halves, as
+                // they did in k_dither_lists; here it cannot show: the pass writes colours, and equal centroids blend to equal colours)
                 i1 = c1 < k1 ? 256u + (c1 & 255u) : (k1 & 255u);
                 i2 = (m2 == c1 || m2 == c2) ? 256u + (m2 & 255u) : (m2 & 255u);
                 k1 = m1; k2 = m2; k3 = m3;

@@ -31,6 +31,22 @@ given), the same labels; the model tracks WHO holds the object's binding -- nobo
 table), the caller -- because the setter drops the initialisation's and is refused under the caller's ("l_unbind" where the model
 cannot rule a caller's binding out).  One more image, the importance map: 53 x 67, every alpha in 1 .. 255.
 
+Surface 4 (generate(..., surface=4), seeds of its own; the lists of surfaces 1 to 3 are pinned by hash) adds the batched calls, on
+the same processor, switches, Lloyd and Sequence objects and blocks: ("b_palette", images, k, algo, bound), ("b_reduce", images, k,
+algo, mode, bound), ("b_reduce_indexed", images, k, algo, mode, format, bound), ("b_find", images, k, palette seed, mode, format,
+bound) on host buffers, ("b_palette_device", images, k) and ("b_apply_device", images, k, centroid seed, shared, mode, format,
+offset) on the resident device copies.  `images` is a list of image indices of length 1, 2 or 3 .. 9, in a random order, an image
+may appear twice; `bound` is max_resident_bytes: 0, 1 (a sub-batch per image) or the bytes of two neighbours, which cuts after
+every second image.  The model stays stateless: what a batched call gives for image i is what the per-image call gives for image i
+under the switches as they stand -- palette, reduce, reduce_indexed, find / find_indexed, apply, and init_centroids + run +
+get_centroids for the device call.  The reports are predicted from include/kmeans_hip.h alone: sub_batches by the greedy cut over
+the resident bytes the header lists (batch_resident, batch_cut: the model's own few lines), fallback 0 (no working image has 2^19
+pixels), iterations the largest count, launches the sum over the k-means sub-batches of two images or more of k + 2 + their largest
+count (a sub-batch of one image takes the per-image palette step), and for the output step batched + per_image = n with per_image
+= n for meld, diffusion, the octree and the forced table strategy.  After every op: every output, palette and out_counts entry,
+the guard bytes, the resident sources of a device call; after a refusal that nothing at all was written -- outputs, counts,
+reports -- and that status and message are the header's.
+
   generate(seed, seq)  -> list of plain tuples (deterministic; a dry Model keeps every op legal or a listed refusal)
   Runner(env).run(ops) -> executes them on a backend, checks everything the op could have touched, raises Mismatch
   replay(env, seed, seq, ops) -> the same for a list printed by a failing run
@@ -52,6 +68,12 @@ What the generator never emits, because include/kmeans_hip.h leaves it open or b
     local output at the size of the image without a kept pixel;
   - (surface 3) kmg_lloyd_set_weighting where the model cannot tell whose binding the object holds (it unbinds first), a weighted
     pass of more than 2^28 pixels (tests/test_gpu_weight.py), the group layer's refusal (the harness owns no group).
+  - (surface 4) a batch with the 1024 x 1024 image; a dither of 128 colours or more on an image of 16384 pixels or more in a
+    batched output step (b_reduce_indexed, b_find, b_apply_device: include/kmeans_hip.h leaves whether it joins the launch to a
+    measured rule); diffusion of the 300 x 200 image; the octree under a cutoff above 0, on an image above the shrink limit, in
+    b_reduce_indexed, or on the noise images (the reference needs seconds for each); a batch with a palette step on an image
+    without a kept pixel, under fixed colours or under weighting (other than the refusals); a NULL array or entry, a zero
+    dimension, k = 0 or above KMG_MAX_K, an INDEX16 output at an odd address (tests/test_gpu_batch.py and _apply.py own those).
 The 1024 x 1024 image enters host calls and kmg_dev_compare only, and only under the forced colour-table strategy.  The images
 are this harness's own (make_images here): frames of one size in families, alpha bytes that fill every cutoff class, a frame above
 the shrink limit -- lifecycle_harness.make_images has none of these.  Every sequence mixes random ops with short directed passages
@@ -109,6 +131,19 @@ FIXED = (None,
 
 SURFACE_2_OPS = 120
 SURFACE_3_OPS = 70
+# surface 4: the batched calls (kmg_palette_batch, kmg_reduce_batch, kmg_reduce_indexed_batch, kmg_find_batch, kmg_dev_palette_batch,
+# kmg_dev_apply_batch) on the same processor, switches, objects and blocks
+SURFACE_4_OPS = 130
+BATCH_OPS = ("b_palette", "b_reduce", "b_reduce_indexed", "b_find", "b_palette_device", "b_apply_device")
+REFUSALS_4 = ("batch_fixed", "batch_weighted", "batch_no_kept_pixel", "batch_index8_full", "batch_meld_indexed", "batch_bad_tables", "batch_empty")
+MOTIFS_4 = ("batch_shrinking", "batch_device_blocks", "batch_cutoff", "batch_switches", "batch_no_kept_pixel", "batch_beside_objects",
+            "batch_octree")
+BATCH_POOL = (0, 1, 2, 3, 4, 5, 6, 8, 10, 11, 12, 13, 14)     # every image but the one without a kept pixel and the one of 2^20 pixels
+BATCH_PALETTE_CALLS = ("b_palette", "b_reduce", "b_reduce_indexed")
+# the words of kmg_last_error a refused batch is recognised by
+BATCH_NEEDLES = {"batch_fixed": ("fixed colours",), "batch_weighted": ("alpha weighting",), "batch_no_kept_pixel": ("alpha_cutoff",),
+                 "batch_index8_full": ("INDEX8",), "batch_meld_indexed": ("no index output",), "batch_bad_tables": ("n_tables",),
+                 "batch_empty": ("empty",)}
 
 
 def k_class(k):
@@ -361,6 +396,25 @@ class Ref:
         return self._memo(("stats", src.tobytes(), np.ascontiguousarray(out).tobytes(), None if pal is None else pal.tobytes(), cutoff, what),
                           lambda: error_ref.stats(O, src, out, palette=pal, cutoff=cutoff, what=what))
 
+    def palette_step(self, i, t, k):
+        """(centroids, iteration count) of the default palette step on the working image of image i under cutoff t: no fixed
+        colour, no weighting -- what a batched call runs for each of its images"""
+        def make():
+            W, w, h = self.working(((i, t),))
+            lab = O.rgb_to_lab(W)
+            cent, _, it = O.lloyd(lab, O.init_centroids(lab, w, h, k), MAX_ITERATIONS, CHECK_PERIOD)
+            return cent, it
+        return self._memo(("step", i, t, k), make)
+
+    def lloyd_triple(self, i, k):
+        """(centroids as (L, a, b, 1), iteration count) of init_centroids + run + get_centroids on the whole image i"""
+        def make():
+            h, w = self.img(i).shape[:2]
+            cent, _, it = O.lloyd(self.lab(i), O.init_centroids(self.lab(i), w, h, k), MAX_ITERATIONS, CHECK_PERIOD)
+            cent[:, 3] = 1.0
+            return cent, it
+        return self._memo(("triple", i, k), make)
+
     def find_centroids(self, pal):
         return fixed_ref.pins_lab(O, pal)
 
@@ -471,10 +525,12 @@ def lloyd_step(s, sums):
 def generate(seed, seq, n_ops=None, surface=1):
     """one sequence: a list of plain tuples.  surface 1: the calls up to the lossy delta frames, 150 ops; surface 2: those plus
     per-frame palettes, colour-keyed canvases and the index-map optimisation (SURFACE_2_OPS ops); surface 3: those plus alpha
-    weighting on the processor and on the Lloyd objects (SURFACE_3_OPS random ops, then the motifs).  The lists of surfaces 1 and 2
-    never change: tests/test_session_model.py pins their hashes"""
-    n_ops = {1: 150, 2: SURFACE_2_OPS, 3: SURFACE_3_OPS}[surface] if n_ops is None else n_ops
-    refusals = {1: REFUSALS_1, 2: REFUSALS, 3: REFUSALS + REFUSALS_3}[surface]
+    weighting on the processor and on the Lloyd objects (SURFACE_3_OPS random ops, then the motifs); surface 4: those plus the
+    batched calls (fewer of the older motifs, the seven of the batches, and random draws -- nearly half of them batches -- until
+    the list has SURFACE_4_OPS ops: the motifs' ops count, as on every surface, so most of a sequence is directed).  The
+    lists of surfaces 1 to 3 never change: tests/test_session_model.py pins their hashes"""
+    n_ops = {1: 150, 2: SURFACE_2_OPS, 3: SURFACE_3_OPS, 4: SURFACE_4_OPS}[surface] if n_ops is None else n_ops
+    refusals = {1: REFUSALS_1, 2: REFUSALS, 3: REFUSALS + REFUSALS_3, 4: REFUSALS + REFUSALS_3 + REFUSALS_4}[surface]
     rng = np.random.default_rng([seed, seq, 3] if surface == 1 else [seed, seq, 3, surface])
     images = make_images(seed, seq)
     m = Model(images, numeric=False)
@@ -511,7 +567,7 @@ def generate(seed, seq, n_ops=None, surface=1):
 
     def host_image():
         """an image for a host call: kept pixels under the current cutoff, the 2^20 one only under the forced colour table"""
-        pool = [ODD, SPRITE, 4, FEW, FLAT, BIG, ROW, COL] + ([MEGA] if m.strategy == 2 else []) + ([MAP, MAP] if surface == 3 else [])
+        pool = [ODD, SPRITE, 4, FEW, FLAT, BIG, ROW, COL] + ([MEGA] if m.strategy == 2 else []) + ([MAP, MAP] if surface >= 3 else [])
         for _ in range(20):
             i = pick(pool)
             if m.n_kept(i, m.wc()) > 0:
@@ -526,7 +582,7 @@ def generate(seed, seq, n_ops=None, surface=1):
         return None if hi < max(f, 1) else pick_k(lo=max(f, 1), hi=hi)
 
     def switches():
-        if surface == 3 and rng.random() < 0.35:          # the weighting, and a palette step that sees it
+        if surface >= 3 and rng.random() < 0.35:          # the weighting, and a palette step that sees it
             emit(("weight", 1 - m.w))
             if rng.random() < 0.6:
                 emit(("palette", pick([SPRITE, MAP, ODD]), n_fixed_of(m.fid) + rint(1, 7)))
@@ -616,7 +672,7 @@ def generate(seed, seq, n_ops=None, surface=1):
         if s is None:
             emit(("l_new", L, pick_k()))
             return
-        if surface == 3 and rng.random() < 0.22:
+        if surface >= 3 and rng.random() < 0.22:
             return l_weight_ops(L)
         c = rng.random()
         if c < 0.04:
@@ -628,7 +684,7 @@ def generate(seed, seq, n_ops=None, surface=1):
                 emit(("l_set", L, "rand", rint(0, 1 << 30), ODD))
                 emit(("l_assign_update", L, pick([ODD, FEW, ROW]), 1, 1, st()))
             return
-        i = pick([ODD, SPRITE, FEW, FLAT, BIG, ROW] + ([MAP] if surface == 3 else []))
+        i = pick([ODD, SPRITE, FEW, FLAT, BIG, ROW] + ([MAP] if surface >= 3 else []))
         n = images[i][1].shape[0] * images[i][1].shape[1]
         if s.cent is None or c < 0.24:
             if n * s.k <= 300000 and rng.random() < 0.7:
@@ -764,6 +820,8 @@ def generate(seed, seq, n_ops=None, surface=1):
             return refusal_2(what)
         if what in REFUSALS_3:
             return refusal_3(what)
+        if what in REFUSALS_4:
+            return refusal_4(what)
         f = n_fixed_of(m.fid)
         if what.startswith("k_below_fixed") or what == "octree_fixed":
             if f < 2:
@@ -941,9 +999,12 @@ def generate(seed, seq, n_ops=None, surface=1):
         if surface >= 2:
             for j in rng.permutation(len(REFUSALS_2))[:4]:
                 refusal(REFUSALS_2[int(j)])
-        if surface == 3:
+        if surface >= 3:
             for j in rng.permutation(len(REFUSALS_3))[:4]:
                 refusal(REFUSALS_3[int(j)])
+        if surface >= 4:
+            for j in rng.permutation(len(REFUSALS_4))[:4]:
+                refusal(REFUSALS_4[int(j)])
 
 
     # ---- surface 2: per-frame palettes, colour-keyed canvases, index-map optimisation -------------------------------------
@@ -1511,13 +1572,314 @@ def generate(seed, seq, n_ops=None, surface=1):
         emit(("quality",) + args)
         set_weight(w0)
 
-    motifs = [mo for mo in (motif_mixed, motif_refusals, motif_cutoff, motif_reoutput, motif_anchor, motif_growth, motif_first_frame, motif_freeze, motif_pins) if rng.random() < 0.75]
+    # ---- surface 4: the batched calls -----------------------------------------------------------------------------------------
+    def shape_of(i):
+        return images[i][1].shape[:2]
+
+    def batch_list(pool, n=None):
+        """image indices drawn with replacement (an image may appear twice), in a random order: lengths 1, 2 and 3 .. 9"""
+        if n is None:
+            c = rng.random()
+            n = 1 if c < 0.15 else 2 if c < 0.35 else rint(3, 10)
+        return tuple(pick(list(pool)) for _ in range(n))
+
+    def kept_pool():
+        return [i for i in BATCH_POOL if m.n_kept(i, m.t) > 0]
+
+    def swap(imgs, old, new):
+        return tuple(new if i == old else i for i in imgs)
+
+    def pairs_bound(call, imgs, fmt):
+        """the bytes two neighbours keep resident, where that bound cuts the list after every second image; else None"""
+        sizes = [batch_resident(shape_of(i), m.t, call, fmt) for i in imgs]
+        B = max(sum(sizes[j:j + 2]) for j in range(0, len(sizes), 2))
+        return B if [len(p) for p in batch_cut(sizes, B)] == [2] * (len(imgs) // 2) + [1] * (len(imgs) % 2) else None
+
+    def batch_bound(call, imgs, fmt, pool):
+        """(images, max_resident_bytes): 0; 1, a sub-batch per image; or a bound that cuts after every second image -- where the
+        drawn list has none, images of one size (a family) take its place"""
+        c = rint(0, 3)
+        if c < 2:
+            return imgs, c
+        B = pairs_bound(call, imgs, fmt)
+        if B is None:
+            fam = pick([f for f in FAMILIES if all(i in pool for i in f)])
+            imgs = tuple(pick(list(fam)) for _ in imgs)
+            B = pairs_bound(call, imgs, fmt)
+        assert B is not None, (call, imgs, fmt)                   # (images of one size keep the same bytes: two fit, three do not)
+        return imgs, B
+
+    def batch_k(imgs, fmt=0):
+        cap = min(cap_k(min(m.n_kept(i, m.t), 65536)) for i in imgs)
+        return pick_k(hi=min(cap, 255 + (0 if m.t else 1) if fmt == 1 else 512))
+
+    def plain_switches(refuse=True):
+        """the three calls with a palette step refuse fixed colours and weighting: both off, now and then after the refusal"""
+        if m.fid:
+            if refuse and rng.random() < 0.4:
+                emit(("refuse", "batch_fixed", pick(list(BATCH_PALETTE_CALLS)), batch_list(kept_pool(), rint(1, 4)), rint(8, 20)))
+            emit(("fixed", 0))
+        if m.w:
+            if refuse and rng.random() < 0.4:
+                emit(("refuse", "batch_weighted", pick(list(BATCH_PALETTE_CALLS)), batch_list(kept_pool(), rint(1, 4)), rint(2, 20)))
+            emit(("weight", 0))
+
+    def output_args(fmt=None, mode=None):
+        fmt = pick([0, 1, 2]) if fmt is None else fmt
+        if mode is None:
+            mode = pick([0, 0, 1, 1, 3]) if fmt else pick([0, 0, 1, 1, 2, 3])
+        return fmt, mode
+
+    def small_enough(imgs, mode, k, output_step=True):
+        """no diffusion of the 300 x 200 image (the reference's is a Python loop), and in a batched output step no dither of it with
+        128 colours or more (include/kmeans_hip.h leaves whether it joins the launch to a measured rule)"""
+        if mode == 3 or (output_step and mode == 1 and k >= 128):
+            return swap(imgs, BIG, ODD)
+        return imgs
+
+    def host_batch(call, imgs=None, k=None, algo=0, mode=None, fmt=None, bound=None):
+        plain_switches()
+        pool = kept_pool()
+        imgs = batch_list(pool) if imgs is None else imgs
+        if call == "b_palette":
+            fmt, mode = 0, 0
+        else:
+            fmt, mode = output_args(0 if call == "b_reduce" else fmt, mode)
+        k = batch_k(imgs, fmt) if k is None else k
+        imgs = small_enough(imgs, mode, k, call == "b_reduce_indexed")
+        if bound is None:
+            imgs, bound = batch_bound(call, imgs, fmt, pool)
+        emit({"b_palette": ("b_palette", imgs, k, algo, bound), "b_reduce": ("b_reduce", imgs, k, algo, mode, bound),
+              "b_reduce_indexed": ("b_reduce_indexed", imgs, k, algo, mode, fmt, bound)}[call])
+
+    def find_batch(imgs=None, k=None, mode=None, fmt=None, bound=None):
+        pool = list(BATCH_POOL) + [CLEAR]
+        imgs = batch_list(pool) if imgs is None else imgs
+        fmt, mode = output_args(fmt, mode)
+        k = pick_k(hi=255 + (0 if m.t else 1) if fmt == 1 else 300) if k is None else k
+        imgs = small_enough(imgs, mode, k)
+        if bound is None:
+            imgs, bound = batch_bound("b_find", imgs, fmt, pool)
+        emit(("b_find", imgs, k, rint(0, 1 << 30), mode, fmt, bound))
+
+    def palette_device(imgs=None, k=None):
+        imgs = batch_list(list(BATCH_POOL) + [CLEAR]) if imgs is None else imgs
+        n = max(shape_of(i)[0] * shape_of(i)[1] for i in imgs)
+        emit(("b_palette_device", imgs, pick_k(hi=512 if n <= 8000 else 256) if k is None else k))
+
+    def apply_device(imgs=None, k=None, shared=None, mode=None, fmt=None):
+        imgs = batch_list(list(BATCH_POOL) + [CLEAR]) if imgs is None else imgs
+        fmt, mode = output_args(fmt, mode)
+        k = pick_k(hi=255 + (0 if m.t else 1) if fmt == 1 else 400) if k is None else k
+        imgs = small_enough(imgs, mode, k)
+        emit(("b_apply_device", imgs, k, rint(0, 1 << 30), rint(0, 2) if shared is None else shared, mode, fmt, pick(list(CPAIR_OFFSETS))))
+
+    def family_pairs():
+        """five to nine images of one size at the bound of two of them, in a call with a palette step and in the find call: the
+        list is cut after every second image, three or four times"""
+        fam = pick([f for f in FAMILIES if all(m.n_kept(i, m.t) > 0 for i in f)])
+        imgs = tuple(pick(list(fam)) for _ in range(rint(5, 10)))
+        call, mode, k = pick(list(BATCH_PALETTE_CALLS)), pick([0, 1]), rint(2, 40)
+        fmt = 1 if call == "b_reduce_indexed" else 0
+        host_batch(call, imgs, k, mode=mode, fmt=fmt, bound=pairs_bound(call, imgs, fmt))
+        fmt = pick([0, 1, 2])
+        find_batch(imgs, k, mode, fmt, pairs_bound("b_find", imgs, fmt))
+
+    def batch_ops():
+        c = rng.random()
+        if c < 0.6:
+            host_batch(pick(list(BATCH_PALETTE_CALLS)))
+        elif c < 0.75:
+            find_batch()
+        elif c < 0.87:
+            palette_device()
+        else:
+            apply_device()
+
+    def refusal_4(what):
+        small = [i for i in (ODD, SPRITE, FEW, FLAT, ROW, MAP) if m.n_kept(i, m.t) > 0]
+        if what in ("batch_fixed", "batch_weighted"):
+            call, imgs, k = pick(list(BATCH_PALETTE_CALLS)), batch_list(small, rint(1, 5)), rint(8, 20)
+            if what == "batch_fixed" and not m.fid:
+                emit(("fixed", pick([1, 2, 3])))
+            if what == "batch_weighted":
+                if m.fid:
+                    emit(("fixed", 0))
+                set_weight(1)
+            emit(("refuse", what, call, imgs, k))
+            plain_switches(refuse=False)
+            host_batch(call, imgs, k, bound=pick([0, 1]))
+        elif what == "batch_no_kept_pixel":
+            t0 = m.t
+            plain_switches(refuse=False)
+            if m.t == 0:
+                emit(("cutoff", pick([1, 128, 255])))
+            call, k = pick(list(BATCH_PALETTE_CALLS)), rint(2, 12)
+            imgs = list(batch_list([i for i in (ODD, SPRITE, FEW, FLAT, MAP) if m.n_kept(i, m.t) > 0], rint(1, 5)))
+            imgs.insert(rint(0, len(imgs) + 1), CLEAR)
+            emit(("refuse", what, call, tuple(imgs), k, pick([0, 1])))
+            host_batch(call, tuple(i for i in imgs if i != CLEAR), k, bound=1)
+            restore_cutoff(t0)
+        elif what in ("batch_index8_full", "batch_meld_indexed"):
+            call, imgs = pick(["b_find", "b_reduce_indexed", "b_apply_device"]), batch_list(small, rint(1, 4))
+            if what == "batch_index8_full":
+                k = 256 if m.t else 257
+                emit(("refuse", what, call, imgs, k))
+                good = dict(k=k - 1, mode=0, fmt=1)
+            else:
+                emit(("refuse", what, call, imgs, 5, pick([1, 2])))
+                good = dict(k=5, mode=2, fmt=0)
+            if call == "b_find":
+                find_batch(imgs, bound=0, **good)
+            elif call == "b_apply_device":
+                apply_device(imgs, **good)
+            else:
+                plain_switches(refuse=False)
+                host_batch(call, imgs, bound=0, **good)
+        elif what == "batch_bad_tables":
+            imgs = batch_list(small, rint(3, 6))
+            emit(("refuse", what, imgs, rint(2, 40), pick([0, 2, len(imgs) + 1])))
+            apply_device(imgs, shared=0)
+        else:
+            assert what == "batch_empty", what
+            emit(("refuse", what, pick(list(BATCH_OPS))))
+
+    def motif_batch_shrinking():
+        """nine images at k = 300, two others at k = 3, one at k = 33, through the host call, the indexed call and the device call:
+        n, k and the sizes shrink, so every word a recycled block still holds differs from the one the next batch needs"""
+        emit(("motif", "batch_shrinking"))
+        t0 = m.t
+        plain_switches(refuse=False)
+        nine = (ODD, 1, SPRITE, 3, 4, FEW, FLAT, ROW, COL)
+        if not all(m.n_kept(i, m.t) for i in nine + (11, 13)):
+            restore_cutoff(0)
+        nine = tuple(nine[int(j)] for j in rng.permutation(9))
+        steps = ((nine, 300), (pick([(11, 13), (MAP, BIG), (13, MAP)]), 3), ((pick([ODD, MAP, FEW]),), 33))
+        for imgs, k in steps:
+            emit(("b_palette", imgs, k, 0, 0))
+        mode = pick([0, 1])
+        for imgs, k in steps:
+            emit(("b_reduce_indexed", imgs, k, 0, mode, 2 if k > 255 else 1, 0))
+        for imgs, k in steps:
+            emit(("b_palette_device", imgs, k))
+        family_pairs()
+        restore_cutoff(t0)
+
+    def motif_batch_device_blocks():
+        """kmg_dev_palette_batch twice with different images, a Lloyd object created, run and closed in the block between them"""
+        emit(("motif", "batch_device_blocks"))
+        L = rint(0, 2)
+        palette_device((SPRITE, FEW, ODD, FLAT, MAP)[:rint(3, 6)], rint(4, 40))
+        if m.lloyd[L] is not None:
+            emit(("l_close", L))
+        emit(("l_new", L, pick_k(hi=64)))
+        emit(("l_set", L, "rand", rint(0, 1 << 30), ODD))
+        emit(("l_run", L, FEW, 1, st()))
+        emit(("l_close", L))
+        palette_device((COL, 1, FEW)[:rint(2, 4)], rint(2, 12))
+
+    def motif_batch_cutoff():
+        """cutoff 0 -> 128 -> 0 around the indexed call and the find call, then the device output call at each cutoff with one
+        shared and one table per image: every batched call reads the cutoff when it starts"""
+        emit(("motif", "batch_cutoff"))
+        t0 = m.t
+        plain_switches(refuse=False)
+        imgs, k, seed = batch_list([SPRITE, ODD, 3, ROW, MAP, 1], rint(2, 6)), rint(3, 40), rint(0, 1 << 30)
+        mode, bound = pick([0, 1]), pick([0, 1])
+        for t in (0, 128, 0):
+            restore_cutoff(t)
+            emit(("b_reduce_indexed", imgs, k, 0, mode, pick([1, 2]), bound))
+            emit(("b_find", imgs + (CLEAR,), k, seed, mode, 1, bound))
+        for t in (128, 0):
+            restore_cutoff(t)
+            emit(("b_apply_device", imgs, k, seed, 1, mode, pick([1, 2]), pick(list(CPAIR_OFFSETS))))
+            emit(("b_apply_device", imgs, k, seed, 0, pick([0, 1, 3]), 0, pick(list(CPAIR_OFFSETS))))
+        restore_cutoff(t0)
+
+    def motif_batch_switches():
+        """fixed colours on: the find call works and equals the unpinned model, the three calls with a palette step refuse; off: the
+        same calls work.  Then the same with alpha weighting"""
+        emit(("motif", "batch_switches"))
+        w0 = m.w
+        imgs = batch_list([i for i in (ODD, SPRITE, FEW, MAP, ROW) if m.n_kept(i, m.t) > 0], rint(2, 5))
+        k, seed, mode = rint(8, 24), rint(0, 1 << 30), pick([0, 1])
+        calls = [("b_reduce_indexed", imgs, k, 0, mode, 1, 0), ("b_palette", imgs, k, 0, 0), ("b_reduce", imgs, k, 0, mode, pick([0, 1]))]
+        set_weight(0)
+        for what in ("batch_fixed", "batch_weighted"):
+            if what == "batch_fixed":
+                emit(("fixed", pick([1, 2, 3])))
+            else:
+                emit(("weight", 1))
+            emit(("b_find", imgs, k, seed, mode, 1, 0))
+            for op in calls:
+                emit(("refuse", what, op[0], imgs, k))
+            emit(("fixed", 0) if what == "batch_fixed" else ("weight", 0))
+            emit(("b_find", imgs, k, seed, mode, 1, 0))
+            for op in calls:
+                emit(op)
+        set_weight(w0)
+
+    def motif_batch_no_kept_pixel():
+        """the image without a kept pixel last in the list, at bound 0 and at bound 1 (the up-front pass); then the same list without
+        it at bound 1 and at bound 0, in the blocks the refused calls gave back"""
+        emit(("motif", "batch_no_kept_pixel"))
+        t0 = m.t
+        plain_switches(refuse=False)
+        if m.t == 0:
+            emit(("cutoff", pick([1, 128, 255])))
+        imgs = batch_list([i for i in (ODD, SPRITE, FEW, FLAT, MAP) if m.n_kept(i, m.t) > 0], rint(2, 5))
+        call, k = pick(list(BATCH_PALETTE_CALLS)), rint(2, 12)
+        for bound in (0, 1):
+            emit(("refuse", "batch_no_kept_pixel", call, imgs + (CLEAR,), k, bound))
+        for bound in (1, 0):
+            host_batch(call, imgs, k, mode=pick([0, 1]), fmt=1 if call == "b_reduce_indexed" else 0, bound=bound)
+        restore_cutoff(t0)
+
+    def motif_batch_beside_objects():
+        """batched calls between the frames of an open output and beside a bound Lloyd object: the next frame and the next assign
+        are still right"""
+        emit(("motif", "batch_beside_objects"))
+        S, L = rint(0, 2), rint(0, 2)
+        plain_switches(refuse=False)
+        small_sequence(S)
+        emit(("s_output", S, rint(2, 30), pick([0, 1, 3]), 1, 1))
+        emit(("s_frame", S, SPRITE, 1, None))
+        emit(("l_new" if m.lloyd[L] is None else "l_re", L, rint(4, 13)))
+        emit(("l_set", L, "rand", rint(0, 1 << 30), ODD))
+        emit(("l_bind", L, ODD, st()))
+        emit(("l_assign", L, ODD, st()))
+        host_batch("b_reduce_indexed", bound=0)
+        emit(("s_frame", S, 3, 1, pick([None, 40])))
+        emit(("l_assign", L, ODD, st()))
+        palette_device()
+        apply_device()
+        emit(("s_frame", S, 4, 1, None))
+        emit(("l_assign_update", L, ODD, 1, 1, st()))
+
+    def motif_batch_octree():
+        """octree batches (the host algorithm per image, no batched launch) alternate with k-means batches"""
+        emit(("motif", "batch_octree"))
+        t0 = m.t
+        plain_switches(refuse=False)
+        restore_cutoff(0)
+        imgs, k = batch_list([SPRITE, 3, 4, FEW, ROW, 11, COL, 13], rint(2, 6)), rint(2, 40)   # (the noise images cost the reference seconds each)
+        for algo in (1, 0, 1):
+            emit(("b_palette", imgs, k, algo, pick([0, 1])))
+            emit(("b_reduce", imgs, k, 1 - algo, pick([0, 1]), 0))
+        family_pairs()
+        restore_cutoff(t0)
+
+    older = 0.3       # surface 4: fewer of the older passages in a sequence, so that a seed costs what the other surfaces' seeds cost
+    motifs = [mo for mo in (motif_mixed, motif_refusals, motif_cutoff, motif_reoutput, motif_anchor, motif_growth, motif_first_frame, motif_freeze, motif_pins) if rng.random() < (0.75 if surface < 4 else older)]
     if surface >= 2:
         motifs += [mo for mo in (motif_warm_cutoff, motif_refused_warm, motif_used_block, motif_lossy_full, motif_local_shared_local,
-                                 motif_optimize_path, motif_records, motif_cpair) if rng.random() < 0.8]
-    if surface == 3:
+                                 motif_optimize_path, motif_records, motif_cpair) if rng.random() < (0.8 if surface < 4 else older)]
+    if surface >= 3:
         motifs += [mo for mo in (motif_weight_cutoff, motif_weight_adds, motif_weight_warm, motif_weight_binding, motif_weight_blocks,
-                                 motif_weight_fixed, motif_weight_quality) if rng.random() < 0.8]
+                                 motif_weight_fixed, motif_weight_quality) if rng.random() < (0.8 if surface < 4 else older)]
+    if surface >= 4:
+        motifs += [mo for mo in (motif_batch_shrinking, motif_batch_device_blocks, motif_batch_cutoff, motif_batch_switches,
+                                 motif_batch_no_kept_pixel, motif_batch_beside_objects, motif_batch_octree) if rng.random() < 0.8]
     at = sorted(rint(3, n_ops - 5) for _ in motifs)
     motifs = [motifs[int(j)] for j in rng.permutation(len(motifs))]
     emit(("strategy", pick([2, 0, 1], [0.5, 0.3, 0.2])))
@@ -1525,6 +1887,9 @@ def generate(seed, seq, n_ops=None, surface=1):
         if motifs and len(ops) >= at[0]:
             at.pop(0)
             motifs.pop(0)()
+            continue
+        if surface >= 4 and rng.random() < 0.45:
+            batch_ops()
             continue
         if surface >= 2 and rng.random() < 0.4:
             surface_2_ops()
@@ -1568,7 +1933,9 @@ def apply_op(m, op):
         assert op[1] in (0, 1), op
         m.w = op[1]
     elif name == "motif":
-        assert op[1] in MOTIFS_3, op
+        assert op[1] in MOTIFS_3 + MOTIFS_4, op
+    elif name in BATCH_OPS:
+        apply_op_4(m, op, exp)
     elif name in ("palette", "reduce", "reduce_indexed"):
         i, k = op[1], op[2]
         assert k >= n_fixed_of(m.fid) and m.n_kept(i, m.wc()) > 0, op
@@ -1840,6 +2207,8 @@ def apply_op(m, op):
             refuse_2(m, op, exp)
         if what in REFUSALS_3:
             refuse_3(m, op, exp)
+        if what in REFUSALS_4:
+            refuse_4(m, op, exp)
         if what in ("k_below_fixed_palette", "k_below_fixed_reduce", "k_below_fixed_sequence"):
             assert op[3] < n_fixed_of(m.fid), op
         elif what == "octree_fixed":
@@ -2048,6 +2417,142 @@ def refuse_3(m, op, exp):
         # they do show is that the refused call writes neither labels nor sums and leaves the object weighted and usable.
         s = m.lloyd[op[2]]
         assert what in ("weighted_bind", "weighted_lftu", "weighted_accumulate_into") and s is not None and s.w and s.k <= 256, op
+
+
+# ---- surface 4 on the model: a batched call is the per-image call, image by image -------------------------------------
+def fmt_bytes(fmt):
+    return {None: 4, 0: 4, 1: 1, 2: 2}[fmt]
+
+
+def batch_resident(shape, t, call, fmt=0):
+    """the bytes an image of `shape` keeps on the device while its sub-batch runs, as include/kmeans_hip.h lists them at
+    max_resident_bytes: the source (kmg_palette_batch: only where the image is not shrunk), the shrunk copy where it has one, the
+    same again under a cutoff for the compacted copy, the output of an indexed call; kmg_find_batch: the source and the output"""
+    h, w = shape
+    if call == "b_find":
+        return (4 + fmt_bytes(fmt)) * w * h
+    shrunk = max(w, h) > SHRINK
+    sw, sh = O.resized_dims(w, h, SHRINK) if shrunk else (w, h)
+    return (4 * sw * sh if shrunk else 0) + (0 if call == "b_palette" and shrunk else 4 * w * h) + (4 * sw * sh if t else 0) + \
+        (fmt_bytes(fmt) * w * h if call == "b_reduce_indexed" else 0)
+
+
+def batch_cut(sizes, bound):
+    """the sub-batches of images that keep sizes[i] bytes each: consecutive, filled while the bytes fit `bound` (0 = 1 GiB); an
+    image that does not fit alone forms one of its own"""
+    bound = bound or 1 << 30
+    pieces, held = [], 0
+    for i, b in enumerate(sizes):
+        if not pieces or held + b > bound:
+            pieces.append([])
+            held = 0
+        pieces[-1].append(i)
+        held += b
+    return pieces
+
+
+def batch_output_report(m, n, mode, algo=0):
+    """(batched, per_image) of the output step: meld, diffusion, the octree and a forced table strategy keep the per-image pass;
+    replace and dither join the launch on this harness's images (the generator leaves the one measured rule out)"""
+    per_image = n if mode in (2, 3) or algo == 1 or m.strategy == 2 else 0
+    return n - per_image, per_image
+
+
+def batch_tables(seed, k, n, shared):
+    return [gamut_centroids(seed + (0 if shared else j), k)[0] for j in range(1 if shared else n)]
+
+
+def find_rgba(R, i, pal, mode, t):
+    img = R.img(i)
+    return R._memo(("find", i, pal.tobytes(), mode, t), lambda: alpha_ref.find(O, img, pal, mode, t) if t else
+                   diffuse_ref.diffuse(img, diffuse_ref.oracle_find_replace(O, pal)) if mode == 3 else O.find(img, pal, mode))
+
+
+def apply_op_4(m, op, exp):
+    name, num, R = op[0], m.numeric, m.ref
+    imgs = op[1]
+    n = len(imgs)
+    shapes = [m.images[i][1].shape[:2] for i in imgs]
+    assert n >= 1, op
+    if name in BATCH_PALETTE_CALLS:
+        k, algo, bound = op[2], op[3], op[-1]
+        mode = 0 if name == "b_palette" else op[4]
+        fmt = op[5] if name == "b_reduce_indexed" else 0
+        assert m.fid == 0 and m.w == 0 and all(m.n_kept(i, m.t) > 0 for i in imgs), op
+        assert algo == 0 or (algo == 1 and m.t == 0 and name != "b_reduce_indexed" and mode in (0, 1) and all(max(s) <= SHRINK for s in shapes)), op
+        assert (fmt != 1 or k + (1 if m.t else 0) <= 256) and (fmt == 0 or mode != 2), op
+        assert not (name == "b_reduce_indexed" and mode == 1 and k >= 128 and any(h * w >= 16384 for h, w in shapes)), op
+        pieces = batch_cut([batch_resident(s, m.t, name, fmt) for s in shapes], bound)
+        exp["pieces"] = pieces
+        if name == "b_reduce_indexed":
+            exp["areport"] = batch_output_report(m, n, mode, algo) + (len(pieces),)
+        if not num:
+            return
+        if algo == 1:
+            exp["report"] = (0, 0, len(pieces), 0)
+            if name == "b_palette":
+                exp["palettes"] = [R._memo(("octree", i, k), lambda i=i: O.palette_octree(R.img(i), k)) for i in imgs]
+            else:
+                exp["outputs"] = [R._memo(("octree", i, k, mode), lambda i=i: O.reduce_octree(R.img(i), k, mode)) for i in imgs]
+            return
+        steps = [R.palette_step(i, m.t, k) for i in imgs]
+        its = [it for _, it in steps]
+        # the chain of a sub-batch: k launches of the initialisation, the initial assignment, one launch per iteration up to its
+        # slowest image; a sub-batch of one image takes the per-image palette step and launches none
+        exp["report"] = (sum(k + 2 + max(its[q] for q in p) for p in pieces if len(p) >= 2), max(its), len(pieces), 0)
+        if name == "b_palette":
+            exp["palettes"] = [R._memo(("sorted", i, m.t, k), lambda c=c: sorted_palette(c)) for i, (c, _) in zip(imgs, steps)]
+        elif name == "b_reduce":
+            exp["outputs"] = [R.rgba(R.img(i), c, mode, m.t) for i, (c, _) in zip(imgs, steps)]
+        else:
+            exp["palettes"] = [R.palette_bytes(c) for c, _ in steps]
+            exp["outputs"] = [R.rgba(R.img(i), c, mode, m.t) if fmt == 0 else R.index(R.img(i), c, mode, m.t) for i, (c, _) in zip(imgs, steps)]
+    elif name == "b_find":
+        k, seed, mode, fmt, bound = op[2:7]
+        assert (fmt != 1 or k + (1 if m.t else 0) <= 256) and (fmt == 0 or mode != 2), op
+        assert not (mode == 1 and k >= 128 and any(h * w >= 16384 for h, w in shapes)), op
+        pieces = batch_cut([batch_resident(s, m.t, name, fmt) for s in shapes], bound)
+        exp["pieces"] = pieces
+        exp["areport"] = batch_output_report(m, n, mode) + (len(pieces),)
+        if num:
+            pal = find_palette(seed, k)
+            exp["outputs"] = [find_rgba(R, i, pal, mode, m.t) if fmt == 0 else R.index(R.img(i), R.find_centroids(pal), mode, m.t) for i in imgs]
+    elif name == "b_palette_device":
+        k = op[2]
+        assert all(h * w < 1 << 19 for h, w in shapes), op
+        if num:
+            steps = [R.lloyd_triple(i, k) for i in imgs]
+            its = [it for _, it in steps]
+            exp.update(cent=[c for c, _ in steps], its=its, report=(k + 2 + max(its), max(its), 1, 0))
+    else:
+        k, seed, shared, mode, fmt, offs = op[2:8]
+        assert name == "b_apply_device" and (fmt != 1 or k + (1 if m.t else 0) <= 256) and (fmt == 0 or mode != 2) and offs in CPAIR_OFFSETS, op
+        assert not (mode == 1 and k >= 128 and any(h * w >= 16384 for h, w in shapes)), op
+        exp["areport"] = batch_output_report(m, n, mode) + (1,)
+        if num:
+            tables = batch_tables(seed, k, n, shared)
+            exp["tables"] = tables
+            exp["outputs"] = [R.rgba(R.img(i), tables[0 if shared else j], mode, m.t) if fmt == 0 else
+                              R.index(R.img(i), tables[0 if shared else j], mode, m.t) for j, i in enumerate(imgs)]
+
+
+def refuse_4(m, op, exp):
+    """the refusals of the batched calls: all KMG_ERR_INVALID_ARGUMENT, checked for the whole batch before any output is written"""
+    what = op[1]
+    if what in ("batch_fixed", "batch_weighted"):
+        assert op[2] in BATCH_PALETTE_CALLS and (n_fixed_of(m.fid) > 0 if what == "batch_fixed" else (m.fid == 0 and m.w == 1)), op
+    elif what == "batch_no_kept_pixel":
+        gone = [j for j, i in enumerate(op[3]) if m.n_kept(i, m.t) == 0]
+        assert op[2] in BATCH_PALETTE_CALLS and m.t > 0 and m.fid == 0 and m.w == 0 and gone, op
+        exp["needle"] = f"image {gone[0]}:"
+    elif what == "batch_index8_full":
+        assert op[2] in ("b_find", "b_reduce_indexed", "b_apply_device") and op[4] + (1 if m.t else 0) == 257, op
+    elif what == "batch_meld_indexed":
+        assert op[2] in ("b_find", "b_reduce_indexed", "b_apply_device") and op[5] in (1, 2), op
+    elif what == "batch_bad_tables":
+        assert op[4] not in (1, len(op[2])), op
+    else:
+        assert what == "batch_empty" and op[2] in BATCH_OPS, op
 
 
 # ---- the runner -----------------------------------------------------------------------------------------------------
@@ -2259,6 +2764,8 @@ class Runner:
             self.step_cpair(op, exp)
         elif name in ("usage_device", "plan", "remap_device", "optimize"):
             self.step_index(op, exp, before_t)
+        elif name in BATCH_OPS:
+            self.step_batch(op, exp)
         else:
             raise ValueError(op)
 
@@ -2624,6 +3131,8 @@ class Runner:
             return self.step_refuse_2(op, st)
         if what in REFUSALS_3:
             return self.step_refuse_3(op, st)
+        if what in REFUSALS_4:
+            return self.step_refuse_4(op, exp)
         if what == "k_below_fixed_palette":
             self.expect_status(st, proc.palette, op[3], self.images[op[2]][1], 0)
         elif what == "k_below_fixed_reduce":
@@ -2692,6 +3201,186 @@ class Runner:
                 if not (self.collect(self.lab, 4 * n, np.uint8, "refused call") == PATTERN).all():
                     self.fail("a refused call wrote labels")
             self.same("accumulators after a refused call", self.collect(self.acc[L], 32 * s.k, np.int64, "accumulators").reshape(s.k, 4), s.acc)
+
+    # -- surface 4: the batched calls
+    ARMED32 = 0xA5A5A5A5
+
+    def batch_args(self, call, imgs, k, algo=0, mode=0, fmt=0, bound=0, seed=7, shared=1, offs=0, n_images=None, n_tables=None):
+        """the arguments of one batched call, every output armed: host outputs are arrays with guard bytes behind them, device
+        outputs lie `offs` elements into sentinel-filled allocations, counts and reports hold a pattern"""
+        n = len(imgs)
+        shapes = [self.images[i][1].shape[:2] for i in imgs]
+        size = fmt_bytes(fmt)
+        a = dict(call=call, n=n if n_images is None else n_images, k=k, algo=algo, mode=mode, fmt=fmt, bound=bound, stream=self.env.streams[0],
+                 ws=[w for _, w in shapes], hs=[h for h, _ in shapes], rep=np.full(4, self.ARMED32, np.uint32),
+                 arep=np.full(4, self.ARMED32, np.uint32), offs=offs * size)
+        if call in ("b_palette_device", "b_apply_device"):
+            a["src"] = [self.pix[i].ptr for i in imgs]
+        else:
+            a["src"] = [self.images[i][1].ctypes.data for i in imgs]
+            a["room"] = [4 * k if call == "b_palette" else size * w * h for h, w in shapes]
+            a["out_bufs"] = [np.full(nb + GUARD, PATTERN, np.uint8) for nb in a["room"]]
+            a["out"] = [b.ctypes.data for b in a["out_bufs"]]
+        if call in ("b_palette", "b_reduce_indexed"):
+            a["counts"] = np.full(n, self.ARMED32, np.uint32)
+        if call == "b_reduce_indexed":
+            a["pal_bufs"] = [np.full(4 * k + GUARD, PATTERN, np.uint8) for _ in imgs]
+            a["pal_out"] = [b.ctypes.data for b in a["pal_bufs"]]
+        if call == "b_find":
+            a["palette"] = np.ascontiguousarray(find_palette(seed, k), np.uint8)
+        if call == "b_palette_device":
+            a["cent"], a["its"] = np.full((n, k, 4), -7.25, np.float32), np.full(n, self.ARMED32, np.uint32)
+        if call == "b_apply_device":
+            a["c4"] = np.ascontiguousarray(np.stack(batch_tables(seed, k, n, shared)), np.float32)
+            a["n_tables"] = a["c4"].shape[0] if n_tables is None else n_tables
+            a["room"] = [size * w * h for h, w in shapes]
+            a["dev_bufs"] = [self.mem.alloc(a["offs"] + nb + GUARD) for nb in a["room"]]
+            for b, nb in zip(a["dev_bufs"], a["room"]):
+                self.mem.fill(b, 0, a["offs"] + nb + GUARD, PATTERN)
+            a["out"] = [b.ptr + a["offs"] for b in a["dev_bufs"]]
+        return a
+
+    def batch_bodies(self, a):
+        """the bodies of the outputs of a batched call, after the bytes around them were seen to be untouched"""
+        bodies = []
+        for j, nb in enumerate(a["room"]):
+            if "dev_bufs" in a:
+                raw = self.mem.read(a["dev_bufs"][j], 0, a["offs"] + nb + GUARD)
+            else:
+                raw = a["out_bufs"][j]
+            off = a["offs"] if "dev_bufs" in a else 0
+            if not ((raw[:off] == PATTERN).all() and (raw[off + nb:] == PATTERN).all()):
+                self.fail(f"output {j} of the batch: written outside the buffer")
+            bodies.append(raw[off:off + nb])
+        return bodies
+
+    def batch_untouched(self, a):
+        """after a refusal: no output, count, palette, centroid or report was written"""
+        if "room" in a and not all((b == PATTERN).all() for b in self.batch_bodies(a)):
+            self.fail("a refused batch wrote output")
+        for name in ("counts", "its", "rep", "arep"):
+            if name in a and not (a[name] == self.ARMED32).all():
+                self.fail(f"a refused batch wrote {name}")
+        if "pal_bufs" in a and not all((b == PATTERN).all() for b in a["pal_bufs"]):
+            self.fail("a refused batch wrote a palette")
+        if "cent" in a and not (a["cent"] == -7.25).all():
+            self.fail("a refused batch wrote centroids")
+
+    def sources_intact(self, imgs):
+        """the resident images a device batch read: the neighbouring device buffers of its state and outputs"""
+        for i in set(imgs):
+            a = self.images[i][1]
+            if not np.array_equal(self.mem.read(self.pix[i], 0, a.size), a.reshape(-1)):
+                self.fail(f"the resident image {i} changed under a device batch")
+
+    def typed(self, body, shape, fmt):
+        h, w = shape
+        return body.reshape(h, w, 4) if fmt == 0 else body.view(index_dtype(fmt)).astype(np.int64).reshape(h, w)
+
+    def step_batch(self, op, exp):
+        env, C, m, call = self.env, self.counters, self.model, op[0]
+        imgs = op[1]
+        n = len(imgs)
+        shapes = [self.images[i][1].shape[:2] for i in imgs]
+        C[f"batch_len:{n if n < 3 else '3+'}"] += 1
+        C["batch_repeated_image"] += int(len(set(imgs)) < n)
+        C["batch_under_cutoff"] += int(m.t > 0)
+        C["batch_under_forced_table"] += int(m.strategy == 2)
+        if call in BATCH_PALETTE_CALLS or call == "b_find":
+            bound = op[-1]
+            C[f"bound:{'0' if bound == 0 else '1' if bound == 1 else 'pairs'}"] += 1
+            C["bound_cuts"] += int(len(exp["pieces"]) > 1)
+            C["bound_pairs_cuts_twice"] += int(bound > 1 and len(exp["pieces"]) >= 3)
+        if call in BATCH_PALETTE_CALLS:
+            C["batch_octree" if op[3] else "batch_kmeans"] += 1
+            C[f"batch_k:{k_class(op[2])}"] += 1
+        if call == "b_palette":
+            a = self.batch_args(call, imgs, op[2], algo=op[3], bound=op[4])
+        elif call == "b_reduce":
+            a = self.batch_args(call, imgs, op[2], algo=op[3], mode=op[4], bound=op[5])
+        elif call == "b_reduce_indexed":
+            a = self.batch_args(call, imgs, op[2], algo=op[3], mode=op[4], fmt=op[5], bound=op[6])
+        elif call == "b_find":
+            a = self.batch_args(call, imgs, op[2], seed=op[3], mode=op[4], fmt=op[5], bound=op[6])
+        elif call == "b_palette_device":
+            a = self.batch_args(call, imgs, op[2])
+        else:
+            a = self.batch_args(call, imgs, op[2], seed=op[3], shared=op[4], mode=op[5], fmt=op[6], offs=op[7])
+            C["tables:shared" if op[4] else "tables:per_image"] += 1
+            C[f"batch_offset:{op[7]}"] += 1
+        if call in ("b_reduce_indexed", "b_find", "b_apply_device"):
+            C[f"batch_output:{('rgba8', 'index8', 'index16')[a['fmt']]}:{('replace', 'dither', 'meld', 'diffuse')[a['mode']]}"] += 1
+        status, message = env.batch(self.proc, a)
+        env.sync()
+        if status != 0:
+            self.fail(f"a legal batched call was refused with status {status}: {message}")
+        if "report" in exp:
+            if tuple(int(v) for v in a["rep"]) != exp["report"]:
+                self.fail(f"batch report {tuple(int(v) for v in a['rep'])}, the model {exp['report']} (launches, iterations, sub_batches, fallback)")
+            C["batch_iterations_differ"] += int("its" in exp and len(set(exp["its"])) > 1)
+        if "areport" in exp:
+            launches, batched, per_image, subs = (int(v) for v in a["arep"])
+            if (batched, per_image, subs) != exp["areport"] or (launches > 0) != (batched > 0):
+                self.fail(f"output report {(launches, batched, per_image, subs)}, the model (launches, batched, per_image, sub_batches) = "
+                          f"({'> 0' if exp['areport'][0] else 0}, {exp['areport'][0]}, {exp['areport'][1]}, {exp['areport'][2]})")
+        if call == "b_palette_device":
+            self.same("iteration counts of the device batch", a["its"].astype(np.int64), np.array(exp["its"], np.int64))
+            for j in range(n):
+                if not np.array_equal(_bits(a["cent"][j]), _bits(exp["cent"][j])):
+                    self.fail(f"centroid bits of image {j} of the device batch", _bits(a["cent"][j]), _bits(exp["cent"][j]))
+            return self.sources_intact(imgs)
+        bodies = self.batch_bodies(a)
+        if call == "b_palette":
+            self.same("out_counts of the batch", a["counts"].astype(np.int64), np.array([p.shape[0] for p in exp["palettes"]], np.int64))
+            for j, want in enumerate(exp["palettes"]):
+                self.same(f"palette of image {j} of the batch", bodies[j][:want.size].reshape(-1, 4), want)
+                if not (bodies[j][want.size:] == PATTERN).all():
+                    self.fail(f"palette of image {j} of the batch: written behind its out_counts entries")
+            return
+        if call == "b_reduce_indexed":
+            self.same("out_counts of the batch", a["counts"].astype(np.int64), np.full(n, op[2], np.int64))
+            for j, want in enumerate(exp["palettes"]):
+                if not (a["pal_bufs"][j][4 * op[2]:] == PATTERN).all():
+                    self.fail(f"palette of image {j} of the batch: written past the end")
+                self.same(f"palette of image {j} of the batch", a["pal_bufs"][j][:4 * op[2]].reshape(-1, 4), want)
+        for j, want in enumerate(exp["outputs"]):
+            self.same(f"output of image {j} of {call} (mode {a['mode']}, format {a['fmt']}, cutoff {m.t})", self.typed(bodies[j], shapes[j], a["fmt"]), want)
+        if call == "b_apply_device":
+            self.sources_intact(imgs)
+
+    def step_refuse_4(self, op, exp):
+        env, m, what = self.env, self.model, op[1]
+        if what == "batch_bad_tables":
+            call, a = "b_apply_device", self.batch_args("b_apply_device", op[2], op[3], fmt=2, n_tables=op[4],
+                                                         shared=int(op[4] <= 1 or op[4] > len(op[2])))
+            if op[4] > 1:                                         # (tables enough for the count that is passed)
+                a["c4"] = np.ascontiguousarray(np.stack(batch_tables(7, op[3], op[4], 0)), np.float32)
+        elif what == "batch_empty":
+            call = op[2]
+            a = self.batch_args(call, (FLAT,), 4, fmt=int(call in ("b_reduce_indexed", "b_find", "b_apply_device")), n_images=0)
+        else:
+            call, imgs, k = op[2:5]
+            kw = {}
+            if what == "batch_no_kept_pixel":
+                kw["bound"] = op[5]
+                self.counters[f"batch_no_kept_pixel:bound_{op[5]}"] += 1
+            if call != "b_palette_device" and call != "b_palette":
+                kw["fmt"] = 1 if what == "batch_index8_full" else op[5] if what == "batch_meld_indexed" else 0
+                kw["mode"] = 2 if what == "batch_meld_indexed" else 0
+                if call == "b_reduce":
+                    kw["fmt"] = 0
+            self.counters[f"{what}:{call}"] += 1
+            a = self.batch_args(call, imgs, k, **kw)
+        status, message = env.batch(self.proc, a)
+        env.sync()
+        if status == 0:
+            self.fail(f"a batched call the header refuses with status {exp['status']} was accepted")
+        if status != exp["status"]:
+            self.fail(f"refused with status {status}, the header names {exp['status']}")
+        for needle in BATCH_NEEDLES[what] + ((exp["needle"],) if "needle" in exp else ()):
+            if needle not in message:
+                self.fail(f"the message of the refusal does not say {needle!r}: {message!r}")
+        self.batch_untouched(a)
 
     # -- surface 2
     def step_refuse_2(self, op, st):
@@ -2905,3 +3594,32 @@ class KgEnv(LH.KgEnv):
 
     def fresh_hold(self):
         return self.kg.FrameHold.fresh_bytes()
+
+    def batch(self, proc, a):
+        """one batched call of the C ABI on the arguments Runner.batch_args made: (status, message of kmg_last_error)"""
+        import ctypes as C
+        kg, L, n = self.kg, self.kg.lib(), len(a["src"])
+        vp, u32 = C.c_void_p, C.c_uint32
+        src, ws, hs = (vp * n)(*a["src"]), (u32 * n)(*a["ws"]), (u32 * n)(*a["hs"])
+        out = (vp * n)(*a["out"]) if "out" in a else None
+        rep = C.cast(a["rep"].ctypes.data, C.POINTER(kg.BatchReport))
+        arep = C.cast(a["arep"].ctypes.data, C.POINTER(kg.BatchApplyReport))
+
+        def ptr(name, ctype):
+            return a[name].ctypes.data_as(C.POINTER(ctype))
+        call, h = a["call"], proc.handle
+        if call == "b_palette":
+            rc = L.kmg_palette_batch(h, a["n"], src, ws, hs, a["k"], a["algo"], a["bound"], out, ptr("counts", u32), rep)
+        elif call == "b_reduce":
+            rc = L.kmg_reduce_batch(h, a["n"], src, ws, hs, a["k"], a["algo"], a["mode"], a["bound"], out, rep)
+        elif call == "b_reduce_indexed":
+            rc = L.kmg_reduce_indexed_batch(h, a["n"], src, ws, hs, a["k"], a["algo"], a["mode"], a["fmt"], a["bound"], (vp * n)(*a["pal_out"]),
+                                            ptr("counts", u32), out, rep, arep)
+        elif call == "b_find":
+            rc = L.kmg_find_batch(h, a["n"], src, ws, hs, ptr("palette", C.c_uint8), a["k"], a["mode"], a["fmt"], a["bound"], out, arep)
+        elif call == "b_palette_device":
+            rc = L.kmg_dev_palette_batch(h, a["n"], src, ws, hs, a["k"], ptr("cent", C.c_float), ptr("its", u32), rep, vp(a["stream"]))
+        else:
+            rc = L.kmg_dev_apply_batch(h, a["n"], src, ws, hs, ptr("c4", C.c_float), a["n_tables"], a["k"], a["mode"], a["fmt"], out, arep,
+                                       vp(a["stream"]))
+        return rc, L.kmg_last_error().decode() if rc else ""

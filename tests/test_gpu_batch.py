@@ -382,3 +382,200 @@ def test_warm_processor_reuses_its_blocks(torch_cuda, edge_images, five_images):
         assert proc.debug_block_counts()[0] == mallocs_r
         for a, b in zip(red_1, red_2):
             assert np.array_equal(a, b)
+
+
+# ---- 11. a warm processor whose blocks hold other batches' words ---------------------------------------------------------
+def test_warm_processor_runs_each_batch_in_another_batchs_blocks(torch_cuda, edge_images, five_images):
+    """nine images at k = 300, then two others at k = 3, then those two reversed plus one at k = 33, on one processor: n, k and the
+    sizes shrink and change, so every word a recycled block still holds (stop, slots, dist, centroids, records, gather buffer,
+    tables) differs from the one the next batch needs.  Every result against the per-image calls of a FRESH processor; a second
+    round of the three batches allocates nothing"""
+    import kmeans_gpu_amd as kg
+    a = list(edge_images) + [five_images[0]]
+    b = [five_images[1], five_images[3]]
+    c = [b[1], b[0], five_images[4]]
+    batches = [(a, 300), (b, 3), (c, 33)]
+    assert len(a) == 9
+    dither = kg.ReduceMode.Dither
+    with kg.ImageProcessor() as fresh:
+        want = []
+        for images, k in batches:
+            pals = [fresh.palette(k, im) for im in images]
+            reds = [fresh.reduce_indexed(k, im, reduce_mode=dither) for im in images]
+            finds = [fresh.find_indexed(im, reds[0][0], reduce_mode=dither) for im in images]
+            want.append((pals, reds, finds))
+    with kg.ImageProcessor() as proc:
+        def one_round(tag):
+            for (images, k), (pals, reds, finds) in zip(batches, want):
+                got = proc.palette_batch(k, images)
+                assert proc.last_batch_report.launches > 0 and proc.last_batch_report.fallback == 0
+                for i in range(len(images)):
+                    assert got[i].shape == pals[i].shape and np.array_equal(got[i], pals[i]), (tag, k, i, "palette_batch")
+                got = proc.reduce_indexed_batch(k, images, reduce_mode=dither)
+                for i in range(len(images)):
+                    assert got[i][1].dtype == (np.uint8 if k <= 256 else np.uint16) == reds[i][1].dtype
+                    assert np.array_equal(got[i][0], reds[i][0]), (tag, k, i, "palette of reduce_indexed_batch")
+                    assert np.array_equal(got[i][1], reds[i][1]), (tag, k, i, "map of reduce_indexed_batch")
+                got = proc.find_batch(images, reds[0][0], reduce_mode=dither)
+                for i in range(len(images)):
+                    assert got[i].dtype == finds[i].dtype and np.array_equal(got[i], finds[i]), (tag, k, i, "find_batch")
+        one_round("first")
+        mallocs = proc.debug_block_counts()[0]
+        one_round("second")
+        assert proc.debug_block_counts()[0] == mallocs                 # no hipMalloc in the second round
+
+
+# ---- 12. more tiles than one chain of launches takes -------------------------------------------------------------------
+BATCH_MAX_TILES = 1 << 20          # include/kmeans_hip.h at kmg_dev_palette_batch: "up to 2^20 tiles of 256 pixels in all"
+
+
+def _chains(pixel_counts):
+    """the pieces the documented limit cuts a device batch into: consecutive entries whose tiles of 256 pixels sum to 2^20 at most"""
+    pieces, held = [[]], 0
+    for i, n in enumerate(pixel_counts):
+        tiles = (n + 255) // 256
+        if pieces[-1] and held + tiles > BATCH_MAX_TILES:
+            pieces.append([])
+            held = 0
+        pieces[-1].append(i)
+        held += tiles
+    return pieces
+
+
+def test_more_tiles_than_one_chain_takes(torch_cuda):
+    """4 100 device views of ONE resident 256 x 256 image (256 tiles each: 2^20 tiles after 4 096 views), k = 2: the batch runs as two
+    chains, and the second chain's results go back through its own index list.  The last entry of the first chain, the first of
+    the second and the last of the batch are three OTHER images (two colours each: they stop at the first check, the noise runs to
+    the cap), so a result stored at an index counted from 0, or one piece's results in the other's place, shows.
+    Batched state by the header's figure (12 bytes per working pixel + 128 k per view): 4 096 x (12 x 65 536 + 256) = 3 222 274 048
+    bytes = 3.0 GiB for the first chain, 3 146 752 bytes for the second; under 4 GiB."""
+    import kmeans_gpu_amd as kg
+    k, side, n_views = 2, 256, 4100
+    state_bytes = 4096 * (12 * side * side + 128 * k)
+    assert state_bytes == 3222274048 and state_bytes < 4 << 30
+    base = _noise(51, side, side)
+
+    def two_colours(seed, lo, hi):
+        m = np.random.default_rng(seed).random((side, side, 1)) < 0.4
+        return _rgba(np.where(m, np.uint8(lo), np.uint8(hi)) * np.ones((side, side, 3), np.uint8))
+    odd = [two_colours(52, 30, 220), two_colours(53, 90, 160), two_colours(54, 5, 120)]
+    pieces = _chains([side * side] * n_views)
+    assert [len(p) for p in pieces] == [4096, 4] and sum(256 * len(p) for p in pieces) > BATCH_MAX_TILES
+    where = {pieces[0][-1]: 0, pieces[1][0]: 1, pieces[1][-1]: 2}       # entry -> which odd image
+    assert sorted(where) == [4095, 4096, 4099]
+    with kg.ImageProcessor(max_iterations=3, check_period=1) as proc:
+        d_base, d_odd = _on_device(torch_cuda, [base])[0], _on_device(torch_cuda, odd)
+        want_base = _per_image(torch_cuda, proc, d_base, base, k)
+        want_odd = [_per_image(torch_cuda, proc, d, im, k) for d, im in zip(d_odd, odd)]
+        assert len({want_base[1]} | {it for _, it in want_odd}) > 1, (want_base[1], [it for _, it in want_odd])
+        d_imgs = [d_odd[where[i]] if i in where else d_base for i in range(n_views)]
+        images = [odd[where[i]] if i in where else base for i in range(n_views)]
+        want = [want_odd[where[i]] if i in where else want_base for i in range(n_views)]
+        cent, its, rep = _device_batch(torch_cuda, proc, d_imgs, images, k)
+        assert rep.fallback == 0
+        # two chains, each k launches of the initialisation, the initial assignment and one launch per iteration up to its slowest
+        assert rep.launches == sum(k + 2 + max(want[i][1] for i in p) for p in pieces), (rep, [max(want[i][1] for i in p) for p in pieces])
+        assert rep.iterations == max(it for _, it in want)
+        for i in sorted(where) + [0, 1, 2048, 4097, 4098]:             # the three odd entries; 0, 1 and one in the middle of each piece
+            assert int(its[i]) == want[i][1], (i, int(its[i]), want[i][1])
+            assert _same_bits(cent[i], want[i][0]), i
+
+
+# ---- 13. the loop's options at their edges --------------------------------------------------------------------------------
+EVERYTHING_CONVERGES = 1.0e6       # far above every CIE94 distance: every centroid with a pixel counts as converged at once
+OPTION_EDGES = [(1, 1, None), (1, 8, None), (2, 1, None), (5, 1, None), (20, 4, EVERYTHING_CONVERGES), (9, 2, 0.0)]
+_oracle_counts = {}
+
+
+def _oracle_lloyd(oracle, im, k, max_iterations, check_period, convergence):
+    h, w = im.shape[:2]
+    lab = oracle.rgb_to_lab(im)
+    cent, _, it = oracle.lloyd(lab, oracle.init_centroids(lab, w, h, k), max_iterations=max_iterations, check_period=check_period,
+                               convergence=1.0 if convergence is None else convergence)
+    return cent, it
+
+
+def _oracle_count_table(oracle, images, max_iterations, check_period, convergence):
+    """{k: iteration counts of the images} by the oracle, for the three k of the test; computed once per row of OPTION_EDGES"""
+    key = (max_iterations, check_period, convergence)
+    if key not in _oracle_counts:
+        _oracle_counts[key] = {k: [_oracle_lloyd(oracle, im, k, *key)[1] for im in images] for k in (1, 8, 33)}
+    return _oracle_counts[key]
+
+
+@pytest.fixture(scope="module")
+def edge_and_early_images(edge_images):
+    """edge_images, which all run to the cap under (max_iterations 5, check_period 1) at k = 8 and 33, and three images that stop
+    earlier there (the test asserts it with the oracle): forty colours with a little noise, twice, and three grey levels with noise"""
+    def forty(seed):
+        r = np.random.default_rng(seed)
+        pal = r.integers(0, 256, (40, 3), dtype=np.uint8)
+        return _rgba(np.clip(pal[r.integers(0, 40, (30, 30))].astype(int) + r.integers(-2, 3, (30, 30, 3)), 0, 255).astype(np.uint8))
+    r = np.random.default_rng(5)
+    levels = _rgba((r.integers(0, 3, (32, 32, 1)) * 83 + r.integers(0, 20, (32, 32, 3))).astype(np.uint8))
+    return list(edge_images) + [forty(0), levels, forty(5)]
+
+
+@pytest.mark.parametrize("k", [1, 8, 33])
+@pytest.mark.parametrize("max_iterations,check_period,convergence", OPTION_EDGES)
+def test_options_at_their_edges(torch_cuda, oracle, edge_and_early_images, max_iterations, check_period, convergence, k):
+    """max_iterations = 1 never reaches a check (its = max_iterations - 1 through stop = max_iterations + 1); check_period = 1 checks
+    after every iteration but the first; a threshold above every distance stops an image at the first check (iteration 4), unless
+    it has fewer colours than k -- an empty cluster never counts as converged, so that image runs to the cap; threshold 0.0: no
+    centroid ever counts, every image runs to the cap.  Not vacuous, by the oracle, for every batch: the counts of ITS images take
+    at least two values -- (5, 1): 1, 2 and 4 at k = 8 and at k = 33; the large threshold: 4 and 19 -- unless the options
+    force one: max_iterations 1 and 2, threshold 0.0, and k = 1 in every row (one centroid with a pixel has converged at the
+    first check, whatever the image)."""
+    import kmeans_gpu_amd as kg
+    edge_images = edge_and_early_images
+    table = _oracle_count_table(oracle, edge_images, max_iterations, check_period, convergence)
+    spread = sorted(set(table[k]))
+    forced = {(1, 1): [0], (1, 8): [0], (2, 1): [1], (9, 2): [8]}.get((max_iterations, check_period))
+    if forced is None and k == 1:
+        forced = [1 if check_period == 1 else check_period]
+    if forced is not None:
+        assert spread == forced, spread
+    else:
+        assert len(spread) >= 2, spread
+        if (max_iterations, check_period) == (5, 1):
+            assert min(spread) < 3 and max(spread) == 4, spread          # (an early stop, a later one and the cap in one batch)
+    if convergence == EVERYTHING_CONVERGES:
+        for im, it in zip(edge_images, table[k]):
+            colours = len(np.unique(im.reshape(-1, 4), axis=0))
+            assert it == (4 if colours >= k else max_iterations - 1), (k, im.shape, it, colours)
+    opts = {} if convergence is None else {"convergence": convergence}
+    with kg.ImageProcessor(max_iterations=max_iterations, check_period=check_period, **opts) as proc:
+        d_imgs = _on_device(torch_cuda, edge_images)
+        cent, its, rep = _device_batch(torch_cuda, proc, d_imgs, edge_images, k)
+        assert rep.fallback == 0 and rep.sub_batches == 1
+        for i, (d, im) in enumerate(zip(d_imgs, edge_images)):
+            want_c, want_it = _per_image(torch_cuda, proc, d, im, k)
+            assert int(its[i]) == want_it, (i, im.shape, int(its[i]), want_it)
+            assert _same_bits(cent[i], want_c), (i, im.shape)
+        assert rep.iterations == int(its.max())
+        assert rep.launches == k + 2 + int(its.max())
+        if k == 8:
+            for i in (5, 6, 7):                                          # 73 x 7 (three colours), 27 x 19, 256 x 171
+                want_c, want_it = _oracle_lloyd(oracle, edge_images[i], k, max_iterations, check_period, convergence)
+                assert int(its[i]) == want_it == table[8][i], (i, int(its[i]), want_it)
+                assert _same_bits(cent[i][:, :3], want_c[:, :3]), i
+
+
+# ---- 14. a sub-batch of one image -----------------------------------------------------------------------------------------
+def test_a_sub_batch_of_one_image_reports_its_iterations(torch_cuda, processor, edge_images):
+    """include/kmeans_hip.h: a sub-batch of ONE image takes the per-image palette step -- no batched launch -- and `iterations`
+    covers it all the same (it was 0 for such a sub-batch: the per-image step dropped the count)"""
+    images = [edge_images[7], edge_images[5], edge_images[6]]        # 256 x 171, 73 x 7 (runs to the cap), 27 x 19: none is shrunk
+    k = 8
+    want = [_per_image(torch_cuda, processor, d, im, k)[1] for d, im in zip(_on_device(torch_cuda, images), images)]
+    assert max(want) not in (want[0], want[-1]), want                 # (neither the first nor the last image's count is the answer)
+    for i, im in enumerate(images):
+        got = processor.palette_batch(k, [im])
+        assert np.array_equal(got[0], processor.palette(k, im))
+        assert processor.last_batch_report.as_tuple() == (0, want[i], 1, 0), (i, processor.last_batch_report)
+    got = processor.palette_batch(k, images, max_resident_bytes=1)
+    assert processor.last_batch_report.as_tuple() == (0, max(want), 3, 0), processor.last_batch_report
+    whole = processor.palette_batch(k, images)
+    assert processor.last_batch_report.as_tuple() == (k + 2 + max(want), max(want), 1, 0), processor.last_batch_report
+    for a, b in zip(got, whole):
+        assert np.array_equal(a, b)

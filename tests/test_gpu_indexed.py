@@ -242,3 +242,31 @@ def test_errors(torch_cuda, processor, oracle):
             p.apply(d_in.data_ptr(), 8, 8, 0, _centroids(oracle, 256), 0, out.data_ptr(), st, format=FMT8)
         p.apply(d_in.data_ptr(), 8, 8, 0, _centroids(oracle, 256), 0, out.data_ptr(), st, format=FMT16)
     torch.cuda.synchronize()
+
+
+def test_dither_lists_with_equal_centroids_in_both_halves(oracle, procs):
+    """A palette step with more centroids than the image has colours leaves equal centroids, and with k = 300 some pairs lie in
+    different halves of the Lab lists (indices below and from 256).  A pixel whose dithered colour is exactly such a centroid has
+    key 0 for both: the scan takes the first, and so must the list pass -- its packed keys then differ in the index byte alone,
+    which orders the second half's index 256 (byte 0) first, and the tie threshold of a key of 0 is 0.  Found by the random sessions
+    (tests/session_harness.py, surface 4: a batch of nine images at k = 300 under the forced table strategy)."""
+    import kmeans_gpu_amd as kg
+    rng = np.random.default_rng(11)
+    pal = rng.integers(0, 256, (7, 4), dtype=np.uint8)
+    img = np.ascontiguousarray(pal[rng.integers(0, 7, 50 * 80)].reshape(50, 80, 4))
+    img[..., 3] = 255
+    k = 300
+    cent, _ = oracle.extract_palette_kmeans(img, k)
+    want = oracle.dither(oracle.rgb_to_lab(img), 80, 50, cent).reshape(50, 80)
+    pairs = [m for m in range(256) if (cent[256:] == cent[m]).all(axis=1).any()]
+    on_a_pair = np.isin(want, pairs)
+    assert pairs and on_a_pair.any() and want.max() < 256        # (not vacuous: the scan labels pixels with the first of such a pair)
+    got = {}
+    for strategy in ("scan", "table"):
+        set_strategy(strategy)
+        p, idx = procs[0].reduce_indexed(k, img, reduce_mode=kg.ReduceMode.Dither)
+        assert idx.dtype == np.uint16 and p.shape == (k, 4)
+        got[strategy] = idx
+    assert np.array_equal(got["scan"], want)
+    bad = np.flatnonzero(got["table"].reshape(-1) != want.reshape(-1))
+    assert bad.size == 0, (bad.size, bad[:4], got["table"].reshape(-1)[bad[:4]], want.reshape(-1)[bad[:4]])

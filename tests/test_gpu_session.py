@@ -2,7 +2,8 @@
 tests/test_session_model.py vouches for, and named scenarios -- each an op list of the harness, run against its stateless model on
 ONE processor that stays alive across all of them (so every scenario works in the blocks the ones before it left): the eight of the
 first surface, then the directed passages of surface 2 (local outputs, colour-keyed canvases, the index-map optimisation), then
-the seven of surface 3 (alpha weighting turned on and off between the other calls of that processor and of its Lloyd objects).
+the seven of surface 3 (alpha weighting turned on and off between the other calls of that processor and of its Lloyd objects), then
+the seven of surface 4 (the batched calls, each in the blocks that larger batches, refused batches and other objects gave back).
 Everything an op could have touched is compared byte for byte after every op."""
 import os
 import re
@@ -12,12 +13,13 @@ import sys
 import pytest
 
 import session_harness as H
-from test_session_model import SEEDS, SEEDS_2, SEEDS_3, SEQUENCES
+from test_session_model import SEEDS, SEEDS_2, SEEDS_3, SEEDS_4, SEQUENCES
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED, SEQ = 7, 0                      # the images of the scenarios: H.make_images(SEED, SEQ)
 ODD, ODD_B, SPRITE, NOISY, SHIFT, FEW, FLAT, CLEAR, BIG, MEGA, ROW, COL, MAP = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14
+ROW_B, COL_B = 11, 13
 # A seed's run took 7.5 and 7.8 s on an MI355X, process start included (profiles/NOTES.md, "Session harness"); about two thirds of
 # that is the reference on the host's CPUs.  The limit is forty times the measured time: a host with a quarter of the cores, busy
 # with other work, can slow the reference tenfold and still finish; a run that needs longer than that hangs.
@@ -65,6 +67,22 @@ def test_random_sessions_of_surface_3_equal_the_model(seed):
     assert re.search(rf"^{SEQUENCES} sequences, \d+ ops, 0 mismatching$", r.stdout, re.M), r.stdout[-2000:]
     reused = [int(x) for x in re.findall(r"(\d+) blocks re-used", r.stdout)]
     assert len(reused) == SEQUENCES and all(x > 0 for x in reused), reused     # else nothing ran on recycled memory
+
+
+# The seeds of surface 4 (the batched calls) took 6.7 and 6.3 s in the visit in which a seed-421 run took 5.6 s (profiles/NOTES.md):
+# the same rule, forty times the slower of the two.
+SESSION_4_SECONDS = 6.7
+TIMEOUT_4 = 40 * SESSION_4_SECONDS
+
+
+@pytest.mark.parametrize("seed", SEEDS_4)
+def test_random_sessions_of_surface_4_equal_the_model(seed):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_session.py"), str(SEQUENCES), str(seed), "4"],
+                       capture_output=True, text=True, timeout=TIMEOUT_4)
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    assert re.search(rf"^{SEQUENCES} sequences, \d+ ops, 0 mismatching$", r.stdout, re.M), r.stdout[-2000:]
+    reused = [int(x) for x in re.findall(r"(\d+) blocks re-used", r.stdout)]
+    assert len(reused) == SEQUENCES and all(x > 0 for x in reused), reused     # else no batch ran in a recycled block
 
 
 @pytest.fixture(scope="module")
@@ -316,6 +334,84 @@ def _the_quality_search_weighted_then_unweighted():
             ("fixed", 2), ("weight", 1), ("quality", SPRITE, 9.0, 3, 9, 1, 1, 0), ("fixed", 0), ("weight", 0)]
 
 
+# ---- surface 4: the batched calls ---------------------------------------------------------------------------------------------------
+def _batches_of_nine_two_and_one_image_at_k_300_3_and_33():
+    """n, k and the sizes shrink from batch to batch, through the palette, the indexed, the find and the device call: every word a
+    recycled block still holds -- stop, slots, distances, centroids, records, gather buffer, tables -- differs from the needed one"""
+    nine = (ODD, ROW, SPRITE, FLAT, SHIFT, FEW, NOISY, ODD_B, COL)
+    steps = ((nine, 300), ((ROW_B, COL_B), 3), ((MAP,), 33))
+    ops = [("strategy", 0), ("cutoff", 0), ("fixed", 0), ("weight", 0)]
+    ops += [("b_palette", imgs, k, 0, 0) for imgs, k in steps]
+    ops += [("b_reduce_indexed", imgs, k, 0, 1, 2 if k > 255 else 1, 0) for imgs, k in steps]
+    ops += [("b_find", imgs, k, 91, 1, 2 if k > 255 else 1, 0) for imgs, k in steps]
+    ops += [("b_palette_device", imgs, k) for imgs, k in steps]
+    return ops + [("b_reduce", (MAP, BIG), 3, 0, 1, 0), ("b_palette", (BIG,), 33, 0, 0)]
+
+
+def _two_device_batches_with_a_lloyd_object_in_the_block_between():
+    return [("b_palette_device", (SPRITE, FEW, ODD, FLAT, MAP), 24), ("l_new", 0, 12), ("l_set", 0, "rand", 3, ODD), ("l_run", 0, FEW, 1, 0),
+            ("l_close", 0), ("b_palette_device", (COL, ODD_B, FEW), 5), ("l_new", 1, 300), ("l_set", 1, "rand", 4, ODD), ("l_run", 1, ROW, 1, 1),
+            ("l_close", 1), ("b_palette_device", (BIG, ROW, CLEAR), 40), ("b_palette_device", (FLAT,), 1)]
+
+
+def _cutoff_0_128_0_around_the_indexed_and_the_find_batch_then_device_output_batches():
+    """every batched call reads the cutoff when it starts: index k below it, INDEX8 sized for it; the device output call at each
+    cutoff with one shared table and with a table per image, at the aligned and the unaligned element offsets"""
+    imgs = (SPRITE, ODD, NOISY, ROW, MAP)
+    ops = [("fixed", 0), ("weight", 0)]
+    for t in (0, 128, 0):
+        ops += [("cutoff", t), ("b_reduce_indexed", imgs, 24, 0, 1, 1, 0), ("b_reduce_indexed", imgs, 24, 0, 0, 2, 1),
+                ("b_find", imgs + (CLEAR,), 24, 92, 1, 1, 0), ("b_find", imgs, 300, 93, 0, 2, 1)]
+    for t in (128, 0):
+        ops += [("cutoff", t), ("b_apply_device", imgs, 24, 94, 1, 1, 1, 1), ("b_apply_device", imgs, 24, 94, 0, 0, 2, 4),
+                ("b_apply_device", imgs + (CLEAR,), 9, 95, 0, 3, 0, 0), ("b_apply_device", imgs, 255, 96, 0, 1, 1, 1)]
+    return ops + [("refuse", "batch_index8_full", "b_apply_device", imgs, 257), ("refuse", "batch_index8_full", "b_find", imgs, 257),
+                  ("b_apply_device", imgs, 256, 97, 1, 0, 1, 0)]
+
+
+def _fixed_colours_and_weighting_around_the_batches():
+    """the find batch ignores both switches and equals the unpinned model; the three calls with a palette step refuse; with the
+    switch off again the same calls work"""
+    imgs, k = (ODD, SPRITE, MAP, FEW), 12
+    calls = [("b_reduce_indexed", imgs, k, 0, 1, 1, 0), ("b_palette", imgs, k, 0, 0), ("b_reduce", imgs, k, 0, 0, 1)]
+    ops = [("cutoff", 0), ("weight", 0)]
+    for what, on, off in (("batch_fixed", ("fixed", 3), ("fixed", 0)), ("batch_weighted", ("weight", 1), ("weight", 0))):
+        ops += [on, ("b_find", imgs, k, 98, 1, 1, 0)] + [("refuse", what, c[0], imgs, k) for c in calls] + [off, ("b_find", imgs, k, 98, 1, 1, 0)] + calls
+    return ops
+
+
+def _a_batch_refused_for_an_image_without_a_kept_pixel_then_the_same_list_without_it():
+    """refused at bound 0 after the shrinks and at bound 1 in the up-front pass, no output written; the same list without the image
+    at bound 1 and at bound 0, in the blocks the refused calls gave back"""
+    imgs, k = (ODD, SPRITE, FEW, MAP), 7
+    ops = [("fixed", 0), ("weight", 0), ("cutoff", 128)]
+    for call in ("b_reduce_indexed", "b_palette", "b_reduce"):
+        ops += [("refuse", "batch_no_kept_pixel", call, imgs + (CLEAR,), k, bound) for bound in (0, 1)]
+        ops += [{"b_palette": ("b_palette", imgs, k, 0, bound), "b_reduce": ("b_reduce", imgs, k, 0, 1, bound),
+                 "b_reduce_indexed": ("b_reduce_indexed", imgs, k, 0, 1, 1, bound)}[call] for bound in (1, 0)]
+    return ops + [("refuse", "batch_no_kept_pixel", "b_palette", (CLEAR, ODD), k, 1), ("refuse", "batch_empty", "b_palette"),
+                  ("refuse", "batch_empty", "b_apply_device"), ("refuse", "batch_meld_indexed", "b_reduce_indexed", imgs, 5, 1),
+                  ("refuse", "batch_bad_tables", imgs, 9, 2), ("refuse", "batch_bad_tables", imgs, 9, 5), ("b_palette", imgs, k, 0, 0), ("cutoff", 0)]
+
+
+def _batches_between_the_frames_of_an_open_output_and_beside_a_bound_lloyd_object():
+    return [("cutoff", 0), ("fixed", 0), ("weight", 0), ("s_new", 0), ("s_add", 0, SPRITE, 0, 0), ("s_output", 0, 16, 1, 1, 1),
+            ("s_frame", 0, SPRITE, 1, None), ("l_new", 0, 9), ("l_set", 0, "rand", 5, ODD), ("l_bind", 0, ODD, 0), ("l_assign", 0, ODD, 0),
+            ("b_reduce_indexed", (ODD, FEW, SPRITE, ROW), 40, 0, 1, 1, 0), ("s_frame", 0, NOISY, 1, 40), ("l_assign", 0, ODD, 1),
+            ("b_palette_device", (MAP, FLAT, COL), 33), ("b_apply_device", (NOISY, ODD), 40, 99, 0, 1, 2, 1), ("s_frame", 0, SHIFT, 1, None),
+            ("l_assign_update", 0, ODD, 1, 1, 0), ("b_palette", (SPRITE, SPRITE, ODD), 8, 0, 1), ("s_frame", 0, SPRITE, 1, 4096), ("l_close", 0),
+            ("s_close", 0)]
+
+
+def _octree_batches_alternate_with_k_means_batches():
+    """the octree is the host algorithm per image: no batched launch, palettes of their own sizes"""
+    imgs, k = (SPRITE, FEW, ROW, NOISY, COL_B), 13
+    ops = [("cutoff", 0), ("fixed", 0), ("weight", 0)]
+    for algo in (1, 0, 1):
+        ops += [("b_palette", imgs, k, algo, int(algo)), ("b_reduce", imgs, k, 1 - algo, 1, 0)]
+    return ops
+
+
 SCENARIOS = {f.__name__[1:]: f for f in (_cutoff_0_128_0_around_palette_reduce_and_a_plan, _frames_added_under_three_cutoffs_then_clear, _an_output_ends_a_lloyd_object_runs_in_its_block_and_the_next_output_starts_fresh, _frozen_seeds_do_not_outlive_their_object, _quality_search_with_and_without_pins_beside_a_bound_object, _records_combine_over_bands_in_reverse_on_two_streams, _every_refusal_is_followed_by_the_correct_call, _two_sequences_alternate_beside_host_calls_on_the_megapixel_image,
                                          # surface 2, on the same long-lived processor after the eight above
                                          _a_warm_output_across_a_cutoff_switch_and_back,
@@ -333,7 +429,15 @@ SCENARIOS = {f.__name__[1:]: f for f in (_cutoff_0_128_0_around_palette_reduce_a
                                          _the_binding_of_an_initialisation_and_of_the_caller_around_the_lloyd_weighting,
                                          _weighted_and_unweighted_lloyd_objects_in_each_others_blocks_beside_weighted_host_calls,
                                          _fixed_colours_and_weighting_with_clusters_of_weight_0,
-                                         _the_quality_search_weighted_then_unweighted)}
+                                         _the_quality_search_weighted_then_unweighted,
+                                         # surface 4, after the twenty-three above: the switches end as they began
+                                         _batches_of_nine_two_and_one_image_at_k_300_3_and_33,
+                                         _two_device_batches_with_a_lloyd_object_in_the_block_between,
+                                         _cutoff_0_128_0_around_the_indexed_and_the_find_batch_then_device_output_batches,
+                                         _fixed_colours_and_weighting_around_the_batches,
+                                         _a_batch_refused_for_an_image_without_a_kept_pixel_then_the_same_list_without_it,
+                                         _batches_between_the_frames_of_an_open_output_and_beside_a_bound_lloyd_object,
+                                         _octree_batches_alternate_with_k_means_batches)}
 
 
 @pytest.mark.parametrize("name", list(SCENARIOS))

@@ -18,6 +18,13 @@ it where the library reads it (the cutoff of a working image where the image is 
 object's weighting and both kinds of binding; twelve more faulty variants, and the twenty-six old ones, are each caught by each of
 SEEDS_3; a third exact table, EXACT_3.  The op lists of SEEDS_2 and the fourteen old images are pinned by hash as well.
 
+Surface 4 (the batched calls) has SEEDS_4: the stand-ins gain the six batched calls, built from the per-image stand-ins -- what a
+batch adds is where a result goes (its index in the caller's arrays, through the sub-batches), when the switches are read (at the
+call), what is refused before anything is written, and the state of a chain of batched launches in a block of the idle list (the
+results come back by slot).  Nine faulty variants, FAULTS_4, are each caught by each of SEEDS_4; a fourth exact table, EXACT_4.  The
+sequences of surface 4 hold fewer of the older directed passages (so that a seed costs what the other seeds cost), so the older
+faulty variants stay with the campaigns of their own surfaces.  The op lists of SEEDS_3, and those of SEEDS_4, are pinned by hash.
+
 Wall time of this file and of tests/test_lifecycle_model.py: profiles/NOTES.md, "session harness"."""
 import collections
 import hashlib
@@ -65,6 +72,14 @@ FAULTS_3 = ("weight_read_at_add", "add_cutoff_ignores_weight", "output_cutoff_fo
 NEW_OPS_3 = ("weight", "l_weight", "l_unbind", "motif")
 
 
+# surface 4 (the batched calls): its own seeds, which also run every op of surfaces 1 to 3
+SEEDS_4 = (533, 534)
+FAULTS_4 = ("stale_stop_word", "second_sub_batch_indexes_from_0", "per_image_tables_read_table_0", "batch_cutoff_read_once",
+            "find_batch_refuses_fixed", "batch_weight_refusal_sticks", "refused_batch_writes_first_sub_batch", "out_counts_unwritten",
+            "iterations_of_last_image")
+NEW_OPS_4 = H.BATCH_OPS
+
+
 NEW_OPS = ("s_output_local", "s_frame_local", "cpair_open", "cpair_frame", "usage_device", "plan", "remap_device", "optimize", "s_usage",
            "s_remap")
 
@@ -103,6 +118,8 @@ class FakeProcessor:
         self.allocated = self.reused = 0
         self.last_compare = error_ref.ZERO
         self.opt_counts = None
+        self.batch_t = None            # (a faulty variant's: the cutoff of the first batched call)
+        self.weight_refused = False    # (a faulty variant's: a batch was refused for the weighting)
 
     # -- blocks
     def take(self):
@@ -418,6 +435,171 @@ class FakeProcessor:
         if b < info[3] or b > 8 * a.dtype.itemsize:
             raise FakeError(-1, "out_bits")
         return out_pal, self._remap(a, k, remap, b)[0], Record(info)
+
+    # -- the batched calls, from the per-image stand-ins: what a batch adds is where a result goes, when the switches are read, and
+    # the state of a chain in a block of the idle list
+    def _batch_images(self, a):
+        if a["n"] == 0:
+            raise FakeError(-1, "the batch is empty")
+        return [_view(p, 4 * w * h, np.uint8).reshape(h, w, 4) for p, w, h in zip(a["src"], a["ws"], a["hs"])][:a["n"]]
+
+    def _batch_t(self):
+        """the cutoff of a batched call: the processor's, as it is when the call starts"""
+        if self.fault == "batch_cutoff_read_once":
+            self.batch_t = self.t if self.batch_t is None else self.batch_t
+            return self.batch_t
+        return self.t
+
+    def _batch_refusals(self, a, t, palette_step):
+        k, mode, fmt = a["k"], a["mode"], a["fmt"]
+        if fmt in (1, 2) and mode == 2:
+            raise FakeError(-1, "meld blends two colours: it has no index output")
+        if fmt == 1 and k + (1 if t else 0) > 256:
+            raise FakeError(-1, "INDEX8 holds 256 indices")
+        if palette_step:
+            if self.n_fixed():
+                raise FakeError(-1, "a batch has no fixed colours")
+            if self.w or (self.fault == "batch_weight_refusal_sticks" and self.weight_refused):
+                self.weight_refused = True
+                raise FakeError(-1, "a batch has no alpha weighting")
+
+    def _put(self, a, at, data):
+        """the bytes of a result into output `at`, as far as that output has room"""
+        raw = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        nb = min(raw.size, a["room"][at])
+        _view(a["out"][at], nb, np.uint8)[:] = raw[:nb]
+
+    def _chain(self, results, k):
+        """the batched kernels on one piece: its state lives in a block of the idle list, the results come back by slot"""
+        block = self.take()
+        stale = block.get("batch_cent")
+        block["batch_cent"] = [c for c, _ in results]
+        self.give(block)
+        if self.fault == "stale_stop_word" and stale is not None and len(stale) > len(results):
+            # the stop words of the block's last batch still stand: the slot's old centroid buffer is gathered
+            out = []
+            for q, (_, it) in enumerate(results):
+                c = np.resize(stale[q], (k, 4)).astype(np.float32)
+                c[:, 3] = 1.0
+                out.append((c, it))
+            return out
+        return results
+
+    def _find_rgba(self, img, pal, mode, t):
+        if t:
+            return alpha_ref.find(O, img, pal, mode, t)
+        if mode == 3:
+            return diffuse_ref.diffuse(img, diffuse_ref.oracle_find_replace(O, pal))
+        return O.find(img, pal, mode)
+
+    def _indexed(self, idx, fmt):
+        return idx.astype(H.index_dtype(fmt))
+
+    def _output_report(self, a, n, pieces, mode, algo=0):
+        batched, per_image = H.batch_output_report(self, n, mode, algo)
+        a["arep"][:] = (len(pieces) if batched else 0, batched, per_image, len(pieces))
+
+    def _batch_host(self, a, call):
+        imgs = self._batch_images(a)
+        k, algo, mode, fmt = a["k"], a["algo"], a["mode"], a["fmt"]
+        t = self._batch_t()
+        self._batch_refusals(a, t, True)
+        idx = [self.image_index(im) for im in imgs]
+        pieces = H.batch_cut([H.batch_resident(im.shape[:2], t, call, fmt) for im in imgs], a["bound"])
+        gone = [j for j, i in enumerate(idx) if self.ref.working(((i, t),)) is None]
+        if gone and self.fault != "refused_batch_writes_first_sub_batch":
+            raise FakeError(-1, f"image {gone[0]}: no pixel reaches alpha_cutoff = {t}")
+        rep, its = [0, 0, len(pieces), 0], []
+        for s, piece in enumerate(pieces):
+            if set(piece) & set(gone):
+                raise FakeError(-1, f"image {min(set(piece) & set(gone))}: no pixel reaches alpha_cutoff = {t}")
+            if algo == 0:
+                results = [self.ref.palette_step(idx[j], t, k) for j in piece]
+                if len(piece) >= 2:
+                    rep[0] += k + 2 + max(it for _, it in results)
+                    results = self._chain(results, k)
+                else:
+                    self.scratch()                                   # a sub-batch of one image: the per-image palette step
+                its += [it for _, it in results]
+            for q, j in enumerate(piece):
+                at = q if self.fault == "second_sub_batch_indexes_from_0" and s > 0 else j
+                img = imgs[j]
+                if algo == 1:
+                    res = self.ref._memo(("octree", idx[j], k) + ((mode,) if call != "b_palette" else ()),
+                                         lambda: O.palette_octree(img, k) if call == "b_palette" else O.reduce_octree(img, k, mode))
+                    self._put(a, at, res)
+                    count = res.shape[0]
+                else:
+                    cent, count = results[q][0], k
+                    if call == "b_palette":
+                        self._put(a, at, sorted_palette(cent))
+                    elif call == "b_reduce" or fmt == 0:
+                        self._put(a, at, self.ref.rgba(img, cent, mode, t))
+                    else:
+                        self._put(a, at, self._indexed(self.ref.index(img, cent, mode, t), fmt))
+                    if call == "b_reduce_indexed":
+                        _view(a["pal_out"][at], 4 * k, np.uint8)[:] = self.ref.palette_bytes(cent).reshape(-1)
+                if call != "b_reduce" and self.fault != "out_counts_unwritten":
+                    a["counts"][at] = count
+            if call != "b_palette":
+                self.scratch()                                       # the records and tables of the output step
+        if its:
+            rep[1] = its[-1] if self.fault == "iterations_of_last_image" else max(its)
+        a["rep"][:] = rep
+        if call == "b_reduce_indexed":
+            self._output_report(a, len(imgs), pieces, mode, algo)
+
+    def batch_palette(self, a):
+        self._batch_host(a, "b_palette")
+
+    def batch_reduce(self, a):
+        self._batch_host(a, "b_reduce")
+
+    def batch_reduce_indexed(self, a):
+        self._batch_host(a, "b_reduce_indexed")
+
+    def batch_find(self, a):
+        imgs = self._batch_images(a)
+        mode, fmt, pal = a["mode"], a["fmt"], a["palette"]
+        t = self._batch_t()
+        self._batch_refusals(a, t, False)
+        if self.fault == "find_batch_refuses_fixed" and self.n_fixed():
+            raise FakeError(-1, "a batch has no fixed colours")
+        pieces = H.batch_cut([H.batch_resident(im.shape[:2], t, "b_find", fmt) for im in imgs], a["bound"])
+        for s, piece in enumerate(pieces):
+            self.scratch()
+            for q, j in enumerate(piece):
+                at = q if self.fault == "second_sub_batch_indexes_from_0" and s > 0 else j
+                if fmt == 0:
+                    self._put(a, at, self._find_rgba(imgs[j], pal, mode, t))
+                else:
+                    self._put(a, at, self._indexed(self.ref.index(imgs[j], self.ref.find_centroids(pal), mode, t), fmt))
+        self._output_report(a, len(imgs), pieces, mode)
+
+    def batch_palette_device(self, a):
+        imgs = self._batch_images(a)
+        k = a["k"]
+        true = [self.ref.lloyd_triple(self.image_index(im), k) for im in imgs]
+        results = self._chain(true, k)
+        for j, (cent, it) in enumerate(results):
+            a["cent"][j] = cent
+            a["its"][j] = it
+        its = [it for _, it in true]
+        a["rep"][:] = (k + 2 + max(its), its[-1] if self.fault == "iterations_of_last_image" else max(its), 1, 0)
+
+    def batch_apply_device(self, a):
+        imgs = self._batch_images(a)
+        mode, fmt, c4 = a["mode"], a["fmt"], a["c4"]
+        t = self._batch_t()
+        self._batch_refusals(a, t, False)
+        if a["n_tables"] not in (1, len(imgs)):
+            raise FakeError(-1, f"n_tables = {a['n_tables']}: 1 or n_images")
+        self.scratch()
+        for j, img in enumerate(imgs):
+            cent = c4[0] if a["n_tables"] == 1 or self.fault == "per_image_tables_read_table_0" else c4[j]
+            res = self._pass(img, cent, mode, fmt or None, t)
+            self._put(a, j, res if fmt == 0 else self._indexed(res, fmt))
+        self._output_report(a, len(imgs), [list(range(len(imgs)))], mode)
 
     def sequence(self):
         return FakeSequence(self)
@@ -807,6 +989,13 @@ class FakeEnv:
             raise FakeError(-1, "the plan refuses")
         return planned
 
+    def batch(self, proc, a):
+        try:
+            getattr(proc, "batch_" + a["call"][2:])(a)
+        except FakeError as e:
+            return e.status, str(e)
+        return 0, ""
+
     def fresh_hold(self):
         return np.array(hold_ref.FRESH[:2], np.uint64).tobytes() + np.array(hold_ref.FRESH[2:6], np.uint32).tobytes() + \
             np.array(hold_ref.FRESH[6:], np.uint64).tobytes()
@@ -858,6 +1047,11 @@ def campaign_3():
     return _campaign(SEEDS_3, FAULTS + FAULTS_2 + FAULTS_3, 3)
 
 
+@pytest.fixture(scope="module")
+def campaign_4():
+    return _campaign(SEEDS_4, FAULTS_4, 4)
+
+
 def test_generator_is_deterministic():
     assert H.generate(SEEDS[0], 1) == H.generate(SEEDS[0], 1)
     assert H.generate(SEEDS[0], 1) != H.generate(SEEDS[1], 1)
@@ -885,6 +1079,12 @@ def test_faithful_stand_in_passes_every_sequence_of_surface_3(campaign_3):
     assert all(n > 0 for seed in SEEDS_3 for n in reused[seed]) and all(len(reused[s]) == SEQUENCES for s in SEEDS_3), reused
 
 
+def test_faithful_stand_in_passes_every_sequence_of_surface_4(campaign_4):
+    assert not campaign_4["failures"], "\n\n".join(campaign_4["failures"])
+    reused = campaign_4["reused"]
+    assert all(n > 0 for seed in SEEDS_4 for n in reused[seed]) and all(len(reused[s]) == SEQUENCES for s in SEEDS_4), reused
+
+
 # sha256 of repr(generate(seed, seq)) on the commit before surface 2 existed: the sessions of the old seeds never change
 PINNED = {
     201: ("9583056de68e9607bd6dc48e57fac0e98ea9ef1e700e99f80ff67861f48a5309", "a9220eb11068dd3887b9e29b693f33ad6198d868f915388d85772889113eec54",
@@ -905,6 +1105,24 @@ PINNED_2 = {
           "9765e08acd84064eb4f7d38b1d92fe5edeba024442b3deaac34b3d7c191198a6", "fcd694726c11c0c0ffa60c474b7bc7a11a6799ee6e35ee7d695db959344443d8",
           "8699f6627162b8a739234f6d14431033426a04862b568d272d4f826ba1d1fd24", "0a951a1aac38858d12d3c6dad528548e0cdd9a929358253aa53c80a920b41331"),
 }
+# ... of repr(generate(seed, seq, surface=3)) on the commit before surface 4 existed
+PINNED_3 = {
+    421: ("ea72033d6d80006f4d9029e3dea242728a8c739d462be243c0c9c8c39faf417b", "dd00d5cf53402dfbb3c15bfe3e4fff4d4dc21ffd9c739677c61b26ba20908fbc",
+          "bdfc865d99626729996bb4993db34ef18c603355ca9d8b0e1d8c69291f840273", "d41facc2e879d7b809ad5128cd4b04f46d9ca9a382aaf567d66d2ec0da6252ef",
+          "a928e98364454e1190fc00bb4b5f819b8763e5306011c50ee7e14bd9dc366a5d", "066921f160d7e9ef055799076c5b07902b609d2f116bb46197a0d3441e1913a6"),
+    422: ("9c0d84e0d648d5617cf1629380e172c7db4dfd10e1a6db78af84159febbbeade", "6393f1ac88529fed21e2163ed9233777f7102d59675142dc8d2849157a27f02c",
+          "6196c5b3c953cb2dc79f5f6e6dade51eb91268f38c4b1c4cb52f369d3a5c3c03", "a840107b70aff802cd20d67f7f88b0efcca0ef754b01f2e89d037dc8a86538cd",
+          "5530ca1e74ea34dd71566a7e165c9f39a754e80b3d0a4f8fc6c686d15e075bfd", "b9e704f483873327f7d303e483181ac38f7e8a1ddbe64507d59419fe327bdfb3"),
+}
+# ... and of repr(generate(seed, seq, surface=4)): the sessions tests/test_gpu_session.py runs and the counts of EXACT_4
+PINNED_4 = {
+    533: ("ad497ddd08dbc0a50e987338cf21904db926f718a0d0088798c0cfe53830f505", "8351a62d49201a4c566c3d49d0ea8776389653bd2af294f56c7dcc9c7874e6aa",
+          "fca5d5ee0ac741a48d54b8f44180d3625585754d55db345e1895e7434cbd70b7", "876020a91bd90588af4e7d68c47e43e5733a46819c73a4371fa74a27f4d885cf",
+          "92fd0e42c68f4c93ad387b6e5d25b19c52df1576f5ad0652c31eb3cbae295729", "14525f7e8b1b8a4f9f370364fd374939b779398534e0a897b424f81e77525c6b"),
+    534: ("d541c3ad00b085730dd3e8d33a0f06bad3c7d5fedc63799d8edd8803089ed999", "b2c7dd932a2a97bf31fc3e09e38d40acf352b61c5e60697b38f0225033f0f440",
+          "32751133cb3a7dc3fa9e00d5e5d66dc5750063a8e96ff5145fdf26c1cab0bf29", "1ed0f78b32c4a31ca27c894306f74e4a8bbd9362950f9a8756390f2612f2c0a2",
+          "ac3f70a7c2ed089af65589eed00e16fa061d2c0890f96e166976c52d0c556a9a", "0abbd29da2924a72cca7f5cbf15d69546cd954099720acf7277fd9aef29bc047"),
+}
 # sha256 over the bytes of the fourteen images of make_images(seed, 0) that existed before the importance map was appended
 PINNED_IMAGES = {201: "851b8715dfdba15b", 314: "791765901562b45a", 7: "cfdc31856e48d6fc"}
 
@@ -919,6 +1137,26 @@ def test_the_committed_sessions_of_surface_2_are_as_they_were(seed):
         assert not {op[0] for op in ops} & set(NEW_OPS_3) and not {op[1] for op in ops if op[0] == "refuse"} & set(H.REFUSALS_3)
         assert not any(op[1] == H.MAP for op in ops if op[0] in ("palette", "reduce", "reduce_indexed", "quality")) and \
             not any(op[2] == H.MAP for op in ops if op[0] == "s_add")
+
+
+@pytest.mark.parametrize("seed", SEEDS_3)
+def test_the_committed_sessions_of_surface_3_are_as_they_were(seed):
+    assert len(PINNED_3[seed]) == SEQUENCES
+    for seq in range(SEQUENCES):
+        ops = H.generate(seed, seq, surface=3)
+        assert hashlib.sha256(repr(ops).encode()).hexdigest() == PINNED_3[seed][seq], (seed, seq)
+        assert ops != H.generate(seed, seq, surface=4)
+        assert not {op[0] for op in ops} & set(NEW_OPS_4) and not {op[1] for op in ops if op[0] == "refuse"} & set(H.REFUSALS_4)
+        assert not {op[1] for op in ops if op[0] == "motif"} & set(H.MOTIFS_4)
+
+
+@pytest.mark.parametrize("seed", SEEDS_4)
+def test_the_committed_sessions_of_surface_4_are_pinned(seed):
+    assert len(PINNED_4[seed]) == SEQUENCES
+    for seq in range(SEQUENCES):
+        ops = H.generate(seed, seq, surface=4)
+        assert hashlib.sha256(repr(ops).encode()).hexdigest() == PINNED_4[seed][seq], (seed, seq)
+        assert eval(repr(ops)) == ops
 
 
 @pytest.mark.parametrize("seed", sorted(PINNED_IMAGES))
@@ -958,6 +1196,12 @@ def test_every_seed_of_surface_3_catches_the_faulty_stand_in(campaign_3, fault):
         assert fault in campaign_3["caught"][seed], f"seed {seed} does not catch {fault} in {SEQUENCES} sequences"
 
 
+@pytest.mark.parametrize("fault", FAULTS_4)
+def test_every_seed_of_surface_4_catches_the_faulty_stand_in(campaign_4, fault):
+    for seed in SEEDS_4:
+        assert fault in campaign_4["caught"][seed], f"seed {seed} does not catch {fault} in {SEQUENCES} sequences"
+
+
 def _replays(caught, seed, fault, surface):
     """the replay(...) line a failing run prints runs again: it fails on the faulty stand-in and passes on the faithful one"""
     seq, _ = caught[seed][fault]
@@ -972,12 +1216,16 @@ def _replays(caught, seed, fault, surface):
     return ops
 
 
-def test_a_mismatch_prints_a_list_that_replays(campaign, campaign_2, campaign_3):
+def test_a_mismatch_prints_a_list_that_replays(campaign, campaign_2, campaign_3, campaign_4):
     _replays(campaign["caught"], SEEDS[0], "plan_follows_cutoff", 1)
     ops = _replays(campaign_2["caught"], SEEDS_2[0], "lossy_full_keeps_lossy_canvas", 2)        # a printed list of surface 2
     assert {op[0] for op in ops} & set(NEW_OPS)
     ops = _replays(campaign_3["caught"], SEEDS_3[0], "weight_read_at_add", 3)                   # ... and of surface 3
     assert {op[0] for op in ops} & set(NEW_OPS_3)
+    ops = _replays(campaign_4["caught"], SEEDS_4[0], "stale_stop_word", 4)                      # ... and of surface 4
+    assert {op[0] for op in ops} & set(NEW_OPS_4)
+    ops = _replays(campaign_4["caught"], SEEDS_4[1], "refused_batch_writes_first_sub_batch", 4)
+    assert ops[-1][:2] == ("refuse", "batch_no_kept_pixel")
 
 
 @pytest.mark.parametrize("seed", SEEDS)
@@ -1029,7 +1277,14 @@ def _scenarios():
                                   "the_binding_of_an_initialisation_and_of_the_caller_around_the_lloyd_weighting",
                                   "weighted_and_unweighted_lloyd_objects_in_each_others_blocks_beside_weighted_host_calls",
                                   "fixed_colours_and_weighting_with_clusters_of_weight_0",
-                                  "the_quality_search_weighted_then_unweighted"])
+                                  "the_quality_search_weighted_then_unweighted",
+                                  "batches_of_nine_two_and_one_image_at_k_300_3_and_33",
+                                  "two_device_batches_with_a_lloyd_object_in_the_block_between",
+                                  "cutoff_0_128_0_around_the_indexed_and_the_find_batch_then_device_output_batches",
+                                  "fixed_colours_and_weighting_around_the_batches",
+                                  "a_batch_refused_for_an_image_without_a_kept_pixel_then_the_same_list_without_it",
+                                  "batches_between_the_frames_of_an_open_output_and_beside_a_bound_lloyd_object",
+                                  "octree_batches_alternate_with_k_means_batches"])
 def test_the_named_scenarios_of_the_device_are_legal_sequences(name):
     """the op lists tests/test_gpu_session.py runs on the device, on the faithful stand-in (one processor per list here)"""
     G = _scenarios()
@@ -1190,3 +1445,49 @@ def test_coverage_of_the_committed_seeds_of_surface_3(campaign_3):
     wrong = {name: (c[name], EXACT_3[name]) for name in need if c[name] != EXACT_3[name] or EXACT_3[name] < 1}
     assert not wrong, wrong
     assert all(n > 0 for seed in SEEDS_3 for n in campaign_3["reused"][seed])      # blocks re-used, in every sequence
+
+
+# what the committed seeds of surface 4 give (SEEDS_4 x SEQUENCES), exactly, for what surface 4 adds.  None may be zero.
+EXACT_4 = {
+    'op:b_palette': 101, 'op:b_reduce': 76, 'op:b_reduce_indexed': 124, 'op:b_find': 98, 'op:b_palette_device': 65,
+    'op:b_apply_device': 74, 'refusal:batch_fixed': 30, 'refusal:batch_weighted': 28, 'refusal:batch_no_kept_pixel': 22,
+    'refusal:batch_index8_full': 3, 'refusal:batch_meld_indexed': 3, 'refusal:batch_bad_tables': 3, 'refusal:batch_empty': 3,
+    'motif:batch_shrinking': 9, 'motif:batch_device_blocks': 11, 'motif:batch_cutoff': 12, 'motif:batch_switches': 9,
+    'motif:batch_no_kept_pixel': 10, 'motif:batch_beside_objects': 10, 'motif:batch_octree': 9, 'bound:0': 254, 'bound:1': 89,
+    'bound:pairs': 56, 'bound_cuts': 134, 'bound_pairs_cuts_twice': 44, 'batch_len:1': 42, 'batch_len:2': 132, 'batch_len:3+':
+    364, 'batch_repeated_image': 226, 'batch_output:rgba8:replace': 17, 'batch_output:rgba8:dither': 25,
+    'batch_output:index8:replace': 48, 'batch_output:index8:dither': 122, 'batch_output:index16:replace': 16,
+    'batch_output:index16:dither': 43, 'batch_fixed:b_palette': 9, 'batch_fixed:b_reduce': 9, 'batch_fixed:b_reduce_indexed':
+    12, 'batch_weighted:b_palette': 10, 'batch_weighted:b_reduce': 9, 'batch_weighted:b_reduce_indexed': 9,
+    'batch_no_kept_pixel:b_palette': 8, 'batch_no_kept_pixel:b_reduce': 9, 'batch_no_kept_pixel:b_reduce_indexed': 5,
+    'batch_no_kept_pixel:bound_0': 11, 'batch_no_kept_pixel:bound_1': 11, 'batch_octree': 27, 'batch_kmeans': 274,
+    'batch_under_cutoff': 188, 'batch_under_forced_table': 327, 'tables:shared': 33, 'tables:per_image': 41,
+    'batch_iterations_differ': 34, 'batch_offset:0': 24, 'batch_offset:4': 22, 'batch_offset:1': 28, 'batch_k:0': 9,
+    'batch_k:1': 206, 'batch_k:2': 60, 'batch_k:3': 5, 'batch_k:4': 21,
+}
+
+
+def coverage_names_4():
+    """what surface 4 adds: every batched op, refusal and motif; every class of max_resident_bytes, and that the computed bound did
+    cut; every output format with replace and with dither; lists of one, two and more images and an image twice in a list; the
+    refusals by call; k-means and octree batches, under a cutoff and under the forced table strategy; shared and per-image tables
+    at every element offset; every class of k; batches whose images stop at different iterations"""
+    return ["op:" + o for o in NEW_OPS_4] + ["refusal:" + r for r in H.REFUSALS_4] + ["motif:" + mo for mo in H.MOTIFS_4] + \
+           ["bound:0", "bound:1", "bound:pairs", "bound_cuts", "bound_pairs_cuts_twice", "batch_len:1", "batch_len:2", "batch_len:3+", "batch_repeated_image"] + \
+           [f"batch_output:{f}:{mo}" for f in ("rgba8", "index8", "index16") for mo in ("replace", "dither")] + \
+           [f"{r}:{call}" for r in ("batch_fixed", "batch_weighted", "batch_no_kept_pixel") for call in H.BATCH_PALETTE_CALLS] + \
+           ["batch_no_kept_pixel:bound_0", "batch_no_kept_pixel:bound_1", "batch_octree", "batch_kmeans", "batch_under_cutoff",
+            "batch_under_forced_table", "tables:shared", "tables:per_image", "batch_iterations_differ"] + \
+           [f"batch_offset:{o}" for o in H.CPAIR_OFFSETS] + [f"batch_k:{c}" for c in range(5)]
+
+
+def test_coverage_of_the_committed_seeds_of_surface_4(campaign_4):
+    c = campaign_4["counters"]
+    print({name: c[name] for name in coverage_names_4()}, campaign_4["ops"])
+    assert not campaign_4["failures"]
+    need = coverage_names_4()
+    assert set(need) == set(EXACT_4), sorted(set(need) ^ set(EXACT_4))
+    wrong = {name: (c[name], EXACT_4[name]) for name in need if c[name] != EXACT_4[name] or EXACT_4[name] < 1}
+    assert not wrong, wrong
+    assert EXACT_4["bound_pairs_cuts_twice"] >= 12                                 # the computed bound cuts a list in three pieces or more: often
+    assert all(n > 0 for seed in SEEDS_4 for n in campaign_4["reused"][seed])      # blocks re-used, in every sequence

@@ -6,7 +6,9 @@ other's blocks, every result compared byte for byte after every call, every refu
 names.  Surface 2 adds outputs with per-frame palettes (cold and warm), colour-keyed canvases of the caller's and the index-map
 optimisation (usage records, plans, remaps, kmg_index_optimize) to the same objects, switches and blocks.  Surface 3 adds alpha
 weighting: kmg_processor_set_weighting turned on and off between all of those calls, kmg_lloyd_set_weighting on the two Lloyd
-objects, with the bindings of the initialisation and of the caller around it, and the refusals of both.  A mismatch prints the op
+objects, with the bindings of the initialisation and of the caller around it, and the refusals of both.  Surface 4 adds the batched
+calls -- kmg_palette_batch, kmg_reduce_batch, kmg_reduce_indexed_batch, kmg_find_batch, kmg_dev_palette_batch, kmg_dev_apply_batch
+-- with lists of 1 to 9 images, three classes of max_resident_bytes, their reports and their refusals.  A mismatch prints the op
 list (replay() of the harness runs it) and ends the run: nothing more is started on the device.
 usage: fuzz_session.py [sequences] [seed] [surface]"""
 import os, sys, time
