@@ -728,6 +728,79 @@ KMG_API int kmg_reduce_quality(kmg_processor *p, const uint8_t *rgba, uint32_t w
                                uint32_t target, int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out,
                                kmg_error_stats *achieved, int *reached);
 
+/* ---- batched quality targets: a colour count per image in one launch chain -----------------
+ * kmg_reduce_quality for many small images (kmg_batch.hip, kmg_batch_apply.hip, kmg_batch_error.hip).  The
+ * batched kernels take a colour count PER IMAGE, so one round of every image's search is ONE launch chain: all images that
+ * still search, each at its own count.
+ *
+ * Equivalence.  kmg_reduce_quality_batch gives image i exactly what kmg_reduce_quality of image i alone gives on the same
+ * processor: out[i], the palette, out_counts[i], achieved[i], reached[i].  The order of the batch, an image appearing twice,
+ * max_resident_bytes and kmg_options.strategy change nothing.  The device calls: kmg_dev_palette_batch_counts gives image i the
+ * centroid bits and the iteration count of kmg_lloyd_init_centroids + kmg_lloyd_run + kmg_lloyd_get_centroids at ks[i];
+ * kmg_dev_apply_batch_counts the bytes of kmg_dev_apply_format at ks[i]; kmg_dev_compare_batch the record of kmg_dev_compare.
+ *
+ * The search is kmg_reduce_quality's fixed bisection in lock step (kmg_quality_search.h): round 0 evaluates k_max for every
+ * image, round r every image that still searches at its own mid-point; a finished image is in no later launch.  One round: the
+ * palette chain with a count per image on the working images W (resident for the whole sub-batch), the labels of W under the
+ * resulting tables (the batched output pass: replace, KMG_FORMAT_INDEX16, no cutoff -- W is compacted already), one batched
+ * record; acceptance is lab_sse <= (uint64_t)target * |W| per image, on the host.  The final output is the batched output pass
+ * at every image's own k* on the full-size sources (meld and diffusion: the per-image pass).  k-means only.
+ *
+ * Per-image paths inside the call: a working image of 2^19 pixels or more takes kmg_reduce_quality's own search (`fallback`), and
+ * so do the images of a sub-batch with fewer than two smaller ones (a batch of one, or max_resident_bytes cutting an image off).
+ * max_resident_bytes: as for kmg_reduce_indexed_batch, plus 2 bytes per working pixel for the labels.
+ *
+ * Refusals, KMG_ERR_INVALID_ARGUMENT, checked for the whole batch before anything is uploaded, in this order: a NULL processor;
+ * n_images == 0; a NULL array (achieved and reached may be NULL); then per image in order a NULL entry or a zero side (more than
+ * 2^32-1 pixels: KMG_ERR_UNSUPPORTED); k_min < 1, k_min > k_max or k_max > KMG_MAX_K; an unknown mode; an unknown format;
+ * KMG_MODE_MELD with an index format; KMG_FORMAT_INDEX8 without room for k_max colours (alpha mode: plus the transparent slot);
+ * fixed colours on the processor; alpha weighting on the processor; then, after the shrinks, alpha mode's "image i: no pixel
+ * reaches alpha_cutoff", before any output is written.
+ * kmg_dev_palette_batch_counts: those of kmg_dev_palette_batch, then per image in order ks[i] == 0 or ks[i] > KMG_MAX_K
+ * (KMG_ERR_UNSUPPORTED).  kmg_dev_apply_batch_counts: those of kmg_dev_apply_batch with each image's own count -- a NULL
+ * processor, n_images == 0, a NULL array, per image a NULL entry or a zero side; a zero entry of ks; mode; format; an entry of ks
+ * above KMG_MAX_K (KMG_ERR_UNSUPPORTED); the rules of the index formats table by table; an INDEX16 output that is not 2-byte
+ * aligned.  kmg_dev_compare_batch: a NULL processor; n_images == 0; a NULL array; format; what; alpha_cutoff above 255; an index
+ * format without palettes or counts; then per image in order a NULL entry, no pixel, more than 2^32-1 pixels (KMG_ERR_UNSUPPORTED),
+ * and for the index formats a count outside 1 .. KMG_MAX_K, no room in INDEX8, an INDEX16 map that is not 2-byte aligned; records
+ * that are not 8-byte aligned.                                                                                                    */
+typedef struct kmg_batch_quality_report {   /* 32 bytes, no padding */
+    uint32_t rounds;            /* rounds of the lock-step search: the most evaluations of any image of a batched search            */
+    uint32_t palette_runs;      /* palette chains run, summed over images (the per-image searches included)                         */
+    uint32_t launches;          /* kernel launches of the batched palette chains (kmg_batch_report.launches, summed over rounds)    */
+    uint32_t measure_launches;  /* launches of the batched error record                                                             */
+    uint32_t batched;           /* final output: images written by the batched output launches                                      */
+    uint32_t per_image;         /* final output: images written by a per-image output pass                                          */
+    uint32_t sub_batches;       /* how many pieces max_resident_bytes cut the batch into                                            */
+    uint32_t fallback;          /* working images of 2^19 pixels or more: the per-image search                                      */
+} kmg_batch_quality_report;
+
+/* kmg_dev_palette_batch with a colour count per image: ks is a HOST array of n_images counts; centroids4 (HOST) is concatenated,
+ * image i's table of ks[i] x 4 floats starts at 4 * (ks[0] + ... + ks[i - 1]) floats.  kmg_dev_palette_batch is the case where all
+ * counts are equal.  report->launches: per piece the largest count + 2 + the most iterations.                                    */
+KMG_API int kmg_dev_palette_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths,
+                                         const uint32_t *heights, const uint32_t *ks, float *centroids4, uint32_t *iterations,
+                                         kmg_batch_report *report, void *stream);
+/* kmg_dev_apply_batch with a table per image of its own size: centroids4 concatenated as above.  The images that join go out as
+ * at most two chains of launches (those with k < 32 and the others: the chunked scan is a launch's).                            */
+KMG_API int kmg_dev_apply_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths,
+                                       const uint32_t *heights, const float *centroids4, const uint32_t *ks, int mode, int format,
+                                       void *const *d_out, kmg_batch_apply_report *report, void *stream);
+/* kmg_dev_compare for n_images images in one launch: d_src_rgba and d_out are HOST arrays of device pointers, n_pixels a HOST array;
+ * palettes_rgba (HOST; index formats) is concatenated, image i's ks[i] x 4 bytes start at 4 * (ks[0] + ... + ks[i - 1]); d_stats:
+ * n_images records in device memory.  COMBINES into record i exactly what kmg_dev_compare combines for image i alone (all fields,
+ * every `what`, the invalid-index rule).  Enqueues on `stream`; does not synchronise.                                              */
+KMG_API int kmg_dev_compare_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src_rgba, const void *const *d_out,
+                                  const uint64_t *n_pixels, int format, const uint8_t *palettes_rgba, const uint32_t *ks,
+                                  uint32_t alpha_cutoff, uint32_t what, kmg_error_stats *d_stats, void *stream);
+/* host buffers, as kmg_reduce_quality per image: out_palette_rgba[i] has room for k_max * 4 bytes, out_counts[i] receives k*,
+ * out[i] has room for widths[i] * heights[i] outputs of `format`; achieved and reached (n_images entries each) may be NULL, and
+ * so may report.                                                                                                                  */
+KMG_API int kmg_reduce_quality_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths,
+                                     const uint32_t *heights, uint32_t k_min, uint32_t k_max, uint32_t target, int mode, int format,
+                                     uint64_t max_resident_bytes, uint8_t *const *out_palette_rgba, uint32_t *out_counts,
+                                     void *const *out, kmg_error_stats *achieved, int *reached, kmg_batch_quality_report *report);
+
 /* ======================= frame sequences: a shared palette, delta frames ==================
  * What an indexed-colour encoder does with many frames (an animation, a sprite sheet, a set of related images): ONE palette for
  * all of them, and per frame the index map of the pixels that changed.  No counterpart in the reference.

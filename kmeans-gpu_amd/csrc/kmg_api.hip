@@ -7,6 +7,7 @@
 
 #include "kmg_state.h"
 #include "kmg_batch_layout.h"
+#include "kmg_quality_search.h"
 
 // ---------------------------------------------------------------------------------------------
 // host-buffer API (ImageProcessor::{palette, find, reduce})
@@ -56,7 +57,9 @@ int working_enqueue(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_
     }
     if (!wi.cutoff) return KMG_OK;
     const uint64_t n = (uint64_t)wi.sw * wi.sh;
-    HIP_TRY(wi.kept.alloc(p, (size_t)n * 4 + (d_count ? 0u : 256u), st));
+    // (a count slot of the call's own lies behind the pixels, 256-byte aligned: room up to that boundary and for the slot --
+    // n * 4 + 256 bytes ended 4 bytes inside the slot where n = 1 mod 64)
+    HIP_TRY(wi.kept.alloc(p, d_count ? (size_t)n * 4 : pad256((size_t)n * 4) + 256u, st));
     wi.d_count = d_count ? d_count : (uint64_t *)((uint8_t *)wi.kept.ptr + pad256((size_t)n * 4));
     return kmg_dev_alpha_compact(p, wi.src, n, wi.cutoff, (uint8_t *)wi.kept.ptr, wi.d_count, st);
 }
@@ -495,33 +498,44 @@ namespace {
 // 0.77 of the per-image calls at k = 8, 64 and 256.
 constexpr uint32_t kBatchMinImages = 2;
 
-enum class BatchKind { kPalette, kReduce, kReduceIndexed };   // kmg_palette_batch, kmg_reduce_batch, kmg_reduce_indexed_batch
+// kmg_palette_batch, kmg_reduce_batch, kmg_reduce_indexed_batch, kmg_reduce_quality_batch
+enum class BatchKind { kPalette, kReduce, kReduceIndexed, kQuality };
+
+// kmg_reduce_quality from its working image on (defined with it, below): the search, the output, the results.  runs: ADDS the palette runs.
+int quality_of_working(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, const WorkingImage &wi, uint32_t k_min, uint32_t k_max,
+                       uint32_t target, int mode, int format, uint32_t alpha_cutoff, const FixedList &fixed, hipStream_t st,
+                       uint8_t *out_palette_rgba, uint32_t *out_count, void *out, kmg_error_stats *achieved, int *reached, uint32_t *runs);
 
 // One image of a sub-batch on the device: its source and its working image (the octree has the source only)
 struct BatchStage { StreamBuf src; WorkingImage wi; };
 
 // What image (w, h) keeps on the device while its sub-batch runs (include/kmeans_hip.h at max_resident_bytes): the source -- a palette
-// call releases one that was shrunk --, the shrunk and the compacted copy, an indexed call's output.  The octree holds the source only.
+// call releases one that was shrunk --, the shrunk and the compacted copy, an indexed or quality call's output, a quality call's
+// labels of the working image (2 bytes each).  The octree holds the source only.
 uint64_t batch_resident_bytes(const kmg_processor *p, uint32_t w, uint32_t h, uint32_t alpha_cutoff, BatchKind kind, int algo, int format)
 {
-    const uint64_t n = (uint64_t)w * h, out = kind == BatchKind::kReduceIndexed ? format_bytes(format) * n : 0ull;
+    const bool quality = kind == BatchKind::kQuality;
+    const uint64_t n = (uint64_t)w * h, out = kind == BatchKind::kReduceIndexed || quality ? format_bytes(format) * n : 0ull;
     if (algo == KMG_ALGO_OCTREE) return 4 * n + out;
     uint32_t sw = w, sh = h;
     const uint32_t m = p->opt.shrink_max_dim;
     const bool shrunk = m && (w > m || h > m);
     if (shrunk) kmg_resized_dims(w, h, m, &sw, &sh);
-    return (shrunk ? 4ull * sw * sh : 0ull) + (kind != BatchKind::kPalette || !shrunk ? 4 * n : 0ull) + (alpha_cutoff ? 4ull * sw * sh : 0ull) + out;
+    return (quality ? 2ull * sw * sh : 0ull) + (shrunk ? 4ull * sw * sh : 0ull) + (kind != BatchKind::kPalette || !shrunk ? 4 * n : 0ull) + (alpha_cutoff ? 4ull * sw * sh : 0ull) + out;
 }
 
 // One call of kmg_palette_batch / kmg_reduce_batch / kmg_reduce_indexed_batch by steps: run() is the refusals, the cuts, alpha
 // mode's up-front pass, then per sub-batch a palette step (by algorithm) and an output step (by kind), and one drain at the end.
 // First the arguments.  format: KMG_FORMAT_RGBA8 unless kReduceIndexed; out: per image the palette (kPalette) or the output;
-// palettes: kReduceIndexed's palettes in index order, else NULL; out_counts: NULL for kReduce.
+// palettes: kReduceIndexed's and kQuality's palettes in index order, else NULL; out_counts: NULL for kReduce.  kQuality:
+// color_count is k_max, and the call has k_min, target, achieved and reached (the last two may be NULL).
 struct BatchCall {
     BatchKind kind; kmg_processor *p; uint32_t n_images;
     const uint8_t *const *rgba; const uint32_t *widths, *heights;
     uint32_t color_count; int algo, mode, format; uint64_t max_resident_bytes;
     uint8_t *const *out, *const *palettes; uint32_t *out_counts;
+    uint32_t k_min = 0, target = 0; kmg_error_stats *achieved = nullptr; int *reached = nullptr;
+    kmg_batch_quality_report qrep = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     CallStart c;
     hipStream_t st = nullptr;
     std::vector<uint32_t> cuts;      // sub-batch s: images [cuts[s], cuts[s + 1])
@@ -536,9 +550,21 @@ struct BatchCall {
     // the refusals, for the whole batch, before any device work (the order is part of the contract: include/kmeans_hip.h)
     int refusals()
     {
-        const bool indexed = kind == BatchKind::kReduceIndexed;
-        const bool array_null = !rgba || !widths || !heights || !out || (kind != BatchKind::kReduce && !out_counts) || (indexed && !palettes);
+        const bool quality = kind == BatchKind::kQuality, indexed = kind == BatchKind::kReduceIndexed;
+        const bool array_null = !rgba || !widths || !heights || !out || (kind != BatchKind::kReduce && !out_counts) || ((indexed || quality) && !palettes);
         KMG_TRY(check_batch_prefix(p, n_images, array_null, "a batch array is NULL", rgba, widths, heights, out, palettes));
+        if (quality) {                                                 // the list of kmg_reduce_quality, then the batches' two
+            if (k_min < 1 || k_min > color_count || color_count > KMG_MAX_K)
+                return fail(KMG_ERR_INVALID_ARGUMENT, "colour counts [%u, %u]: 1 <= k_min <= k_max <= %u", k_min, color_count, KMG_MAX_K);
+            KMG_TRY(check_mode(mode));
+            KMG_TRY(check_format(format));
+            KMG_TRY(check_meld_format(mode, format));
+            c.snapshot(p);
+            KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k_max", color_count, c.alpha_cutoff != 0));
+            if (const uint32_t f = fixed_count(c.fixed)) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch has no fixed colours (%u are set on the processor)", f);
+            if (c.weighting) return fail(KMG_ERR_INVALID_ARGUMENT, "a batch has no alpha weighting (it is on for the processor)");
+            return KMG_OK;
+        }
         KMG_TRY(check_k_nonzero(color_count));
         KMG_TRY(check_algo(algo));
         if (kind != BatchKind::kPalette) KMG_TRY(check_mode(mode));
@@ -559,7 +585,7 @@ struct BatchCall {
         std::vector<uint64_t> bytes(n_images);
         for (uint32_t i = 0; i < n_images; ++i) bytes[i] = batch_resident_bytes(p, widths[i], heights[i], c.alpha_cutoff, kind, algo, format);
         cuts = batch_cuts(bytes.data(), n_images, max_resident_bytes);
-        rep.sub_batches = arep.sub_batches = (uint32_t)cuts.size() - 1u;
+        rep.sub_batches = arep.sub_batches = qrep.sub_batches = (uint32_t)cuts.size() - 1u;
         colors.resize(octree() ? n_images : 0);
     }
     // Uploads images [a, e) and makes their working images: working_enqueue for each, one read-back and one synchronisation for the
@@ -684,6 +710,112 @@ struct BatchCall {
         for (uint32_t q = 0; q < count; ++q) palette_out(a, q);
         return KMG_OK;
     }
+    // kmg_reduce_quality's own search for image a + q of a sub-batch, from its staged working image on
+    int quality_each(uint32_t a, uint32_t q, const BatchStage *stage)
+    {
+        const uint32_t i = a + q;
+        ++qrep.per_image;
+        return quality_of_working(p, (const uint8_t *)stage[q].src.ptr, widths[i], heights[i], stage[q].wi, k_min, color_count, target, mode, format,
+                                  c.alpha_cutoff, c.fixed, st, palettes[i], &out_counts[i], out[i], achieved ? &achieved[i] : nullptr,
+                                  reached ? &reached[i] : nullptr, &qrep.palette_runs);
+    }
+    // Sub-batch [a, e) of kmg_reduce_quality_batch: the working images; the per-image search for a working image of kBatchMaxWorking
+    // pixels or more and for fewer than kBatchMinImages smaller ones; for the others the search in lock step (kmg_quality_search.h)
+    // -- per round one palette chain, one label pass, one record, each with the images' own counts -- and the output at every k*.
+    int quality_batch(uint32_t a, uint32_t e, BatchStage *stage)
+    {
+        constexpr uint64_t kBatchMaxWorking = 1ull << 19;              // (what kmg_dev_palette_batch takes through the batched kernels)
+        KMG_TRY(stage_images(a, e, true, stage));
+        std::vector<uint32_t> small;
+        for (uint32_t q = 0; q < e - a; ++q) {
+            if ((uint64_t)stage[q].wi.sw * stage[q].wi.sh < kBatchMaxWorking) { small.push_back(q); continue; }
+            ++qrep.fallback;
+            KMG_TRY(quality_each(a, q, stage));
+        }
+        if (small.size() < kBatchMinImages) {
+            for (const uint32_t q : small) KMG_TRY(quality_each(a, q, stage));
+            return KMG_OK;
+        }
+        const uint32_t m = (uint32_t)small.size();
+        // W and its labels (one block, kmg_batch_layout.h), the records
+        std::vector<const uint8_t *> work(m); std::vector<uint32_t> sw(m), sh(m); std::vector<uint64_t> nw(m), offset;
+        for (uint32_t j = 0; j < m; ++j) {
+            const WorkingImage &wi = stage[small[j]].wi;
+            work[j] = wi.src; sw[j] = wi.sw; sh[j] = wi.sh; nw[j] = (uint64_t)wi.sw * wi.sh;
+        }
+        uint64_t total = 0;
+        if (!batch_offsets(nw.data(), m, 2u, offset, &total, (uint64_t)SIZE_MAX / 2))
+            return fail(KMG_ERR_OUT_OF_MEMORY, "the labels of the sub-batch do not fit one block");
+        StreamBuf labels, records;
+        HIP_TRY(labels.alloc(p, (size_t)total, st));
+        HIP_TRY(records.alloc(p, sizeof(kmg_error_stats) * m, st));
+        std::vector<QualitySearch> search(m, QualitySearch(k_min, color_count));
+        std::vector<std::vector<float>> best_c4(m);
+        std::vector<kmg_error_stats> best(m), cur(m);
+        // the rounds: the images that still search, each at its own count
+        std::vector<uint32_t> act, ks_r, sw_r, sh_r; std::vector<const uint8_t *> work_r; std::vector<void *> lab_r; std::vector<uint64_t> nw_r;
+        std::vector<size_t> at_r; std::vector<float> c4_r; std::vector<uint8_t> pal_r;
+        for (uint32_t round = 0;; ++round) {
+            act.clear(); ks_r.clear(); sw_r.clear(); sh_r.clear(); work_r.clear(); lab_r.clear(); nw_r.clear(); at_r.clear();
+            size_t k_sum = 0;
+            for (uint32_t j = 0; j < m; ++j) {
+                if (search[j].done()) continue;
+                act.push_back(j); ks_r.push_back(search[j].next()); sw_r.push_back(sw[j]); sh_r.push_back(sh[j]); work_r.push_back(work[j]);
+                lab_r.push_back((uint8_t *)labels.ptr + offset[j]); nw_r.push_back(nw[j]); at_r.push_back(4 * k_sum);
+                k_sum += ks_r.back();
+            }
+            if (act.empty()) break;
+            qrep.rounds = std::max(qrep.rounds, round + 1u);
+            const uint32_t r = (uint32_t)act.size();
+            c4_r.resize(4 * k_sum); pal_r.resize(4 * k_sum);
+            kmg_batch_report prep;
+            KMG_TRY_DRAIN(st, dev_palette_batch_counts(p, r, work_r.data(), sw_r.data(), sh_r.data(), ks_r.data(), c4_r.data(), nullptr, &prep, st));
+            qrep.launches += prep.launches; qrep.palette_runs += r;
+            kmg_batch_apply_report lrep = {0u, 0u, 0u, 0u};
+            KMG_TRY_DRAIN(st, apply_batch_counts(p, r, work_r.data(), sw_r.data(), sh_r.data(), c4_r.data(), at_r.data(), ks_r.data(), false,
+                                                 KMG_MODE_REPLACE, KMG_FORMAT_INDEX16, 0u, lab_r.data(), &lrep, st));
+            for (size_t t = 0; t < k_sum; ++t) shader_lab_to_rgba8(&c4_r[4 * t], &pal_r[4 * t]);
+            HIP_TRY_DRAIN(st, hipMemsetAsync(records.ptr, 0, sizeof(kmg_error_stats) * r, st));
+            KMG_TRY_DRAIN(st, dev_compare_batch(p, r, work_r.data(), lab_r.data(), nw_r.data(), KMG_FORMAT_INDEX16, pal_r.data(), ks_r.data(), 0u,
+                                                KMG_ERROR_RGB | KMG_ERROR_LAB, (kmg_error_stats *)records.ptr, st, &qrep.measure_launches));
+            HIP_TRY_DRAIN(st, hipMemcpyAsync(cur.data(), records.ptr, sizeof(kmg_error_stats) * r, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (uint32_t t = 0; t < r; ++t) {
+                const uint32_t j = act[t];
+                const bool accepted = cur[t].lab_sse <= (uint64_t)target * nw[j];
+                if (log_debug())
+                    fprintf(stderr, "[kmeans_hip] reduce_quality_batch: image %u, k = %u, E = %llu, limit %llu: %s\n", a + small[j], ks_r[t],
+                            (unsigned long long)cur[t].lab_sse, (unsigned long long)((uint64_t)target * nw[j]), accepted ? "accepted" : "not accepted");
+                if (search[j].take(accepted)) {
+                    best[j] = cur[t];
+                    best_c4[j].assign(c4_r.begin() + at_r[t], c4_r.begin() + at_r[t] + 4 * (size_t)ks_r[t]);
+                }
+            }
+        }
+        // the output: every image at its own k*, on the full-size sources
+        std::vector<const uint8_t *> src(m); std::vector<uint32_t> w_o(m), h_o(m), ks_o(m); std::vector<size_t> at_o(m); std::vector<uint8_t *> out_o(m);
+        std::vector<float> c4_o;
+        for (uint32_t j = 0; j < m; ++j) {
+            const uint32_t i = a + small[j];
+            src[j] = (const uint8_t *)stage[small[j]].src.ptr; w_o[j] = widths[i]; h_o[j] = heights[i]; out_o[j] = out[i];
+            ks_o[j] = search[j].k_star(); at_o[j] = c4_o.size();
+            c4_o.insert(c4_o.end(), best_c4[j].begin(), best_c4[j].end());
+        }
+        if (format != KMG_FORMAT_RGBA8)
+            for (uint32_t j = 0; j < m; ++j) KMG_TRY(check_index_format(&c4_o[at_o[j]], ks_o[j], mode, format, c.alpha_cutoff));
+        kmg_batch_apply_report orep = {0u, 0u, 0u, 0u};
+        KMG_TRY(apply_batch_counts_download(p, m, src.data(), w_o.data(), h_o.data(), c4_o.data(), at_o.data(), ks_o.data(), mode, format, c.alpha_cutoff,
+                                            out_o.data(), &orep, st));
+        qrep.batched += orep.batched; qrep.per_image += orep.per_image;
+        for (uint32_t j = 0; j < m; ++j) {
+            const uint32_t i = a + small[j];
+            for (uint32_t t = 0; t < ks_o[j]; ++t) shader_lab_to_rgba8(&c4_o[at_o[j] + 4 * t], palettes[i] + 4 * t);
+            out_counts[i] = ks_o[j];
+            if (achieved) achieved[i] = best[j];
+            if (reached) reached[i] = search[j].reached ? 1 : 0;
+        }
+        return KMG_OK;
+    }
     int run(kmg_batch_report *report, kmg_batch_apply_report *apply_report = nullptr)
     {
         KMG_TRY(refusals());
@@ -696,6 +828,7 @@ struct BatchCall {
             const uint32_t a = cuts[s], e = cuts[s + 1];
             std::unique_ptr<BatchStage[]> stage(new BatchStage[e - a]);
             c4.clear(); ks.clear(); at.clear();
+            if (kind == BatchKind::kQuality) { KMG_TRY(quality_batch(a, e, stage.get())); continue; }
             KMG_TRY(octree() ? palettes_octree(a, e, stage.get()) : palettes_kmeans(a, e, stage.get()));
             if (kind == BatchKind::kPalette) output_palette(a, e);
             else if (kind == BatchKind::kReduce || octree()) KMG_TRY(output_each(a, e, stage.get()));
@@ -883,28 +1016,12 @@ try {
 }
 KMG_ABI_CATCH
 
-extern "C" int kmg_reduce_quality(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t k_min, uint32_t k_max,
-                                  uint32_t target, int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out,
-                                  kmg_error_stats *achieved, int *reached)
-try {
-    // (the refusals that need no device come first)
-    if (k_min < 1 || k_min > k_max || k_max > KMG_MAX_K)
-        return fail(KMG_ERR_INVALID_ARGUMENT, "colour counts [%u, %u]: 1 <= k_min <= k_max <= %u", k_min, k_max, KMG_MAX_K);
-    KMG_TRY(check_mode(mode));
-    KMG_TRY(check_format(format));
-    KMG_TRY(check_meld_format(mode, format));
-    KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k_max", k_max, false));
-    KMG_TRY(check_image(p, rgba, w, h));
-    if (!out || !out_palette_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
-    CallStart c;
-    c.snapshot(p);
-    KMG_TRY(check_fixed(c.fixed, k_min, KMG_ALGO_KMEANS, c.weighting));
-    KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k_max", k_max, c.alpha_cutoff != 0));
-    KMG_TRY(c.begin(p, rgba, w, h));
-    hipStream_t st = c.sg.st;
-    const FixedList &fixed = c.fixed;
-    WorkingImage wi;                                                   // uploaded, shrunk and compacted once
-    KMG_TRY(working_image(p, c.d_rgba(), w, h, c.alpha_cutoff, c.weighting, st, wi));
+namespace {
+
+int quality_of_working(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t h, const WorkingImage &wi, uint32_t k_min, uint32_t k_max,
+                       uint32_t target, int mode, int format, uint32_t alpha_cutoff, const FixedList &fixed, hipStream_t st,
+                       uint8_t *out_palette_rgba, uint32_t *out_count, void *out, kmg_error_stats *achieved, int *reached, uint32_t *total_runs)
+{
     const uint64_t nw = (uint64_t)wi.sw * wi.sh;
     StreamBuf labels, rec;
     HIP_TRY(labels.alloc(p, (size_t)nw * 4, st));
@@ -947,12 +1064,53 @@ try {
         }
         k_star = hi;
     }
-    KMG_TRY(apply_and_download(p, c.d_rgba(), w, h, best_c4.data(), k_star, mode, c.alpha_cutoff, st, (uint8_t *)out, format));
+    KMG_TRY(apply_and_download(p, d_rgba, w, h, best_c4.data(), k_star, mode, alpha_cutoff, st, (uint8_t *)out, format));
     for (uint32_t i = 0; i < k_star; ++i) shader_lab_to_rgba8(&best_c4[4 * i], out_palette_rgba + 4 * i);
     *out_count = k_star;
     if (achieved) *achieved = best;
     if (reached) *reached = did_reach;
+    if (total_runs) *total_runs += runs;
     if (log_debug()) fprintf(stderr, "[kmeans_hip] reduce_quality: k* = %u after %u palette runs\n", k_star, runs);
+    return KMG_OK;
+}
+
+}  // namespace
+
+extern "C" int kmg_reduce_quality(kmg_processor *p, const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t k_min, uint32_t k_max,
+                                  uint32_t target, int mode, int format, uint8_t *out_palette_rgba, uint32_t *out_count, void *out,
+                                  kmg_error_stats *achieved, int *reached)
+try {
+    // (the refusals that need no device come first)
+    if (k_min < 1 || k_min > k_max || k_max > KMG_MAX_K)
+        return fail(KMG_ERR_INVALID_ARGUMENT, "colour counts [%u, %u]: 1 <= k_min <= k_max <= %u", k_min, k_max, KMG_MAX_K);
+    KMG_TRY(check_mode(mode));
+    KMG_TRY(check_format(format));
+    KMG_TRY(check_meld_format(mode, format));
+    KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k_max", k_max, false));
+    KMG_TRY(check_image(p, rgba, w, h));
+    if (!out || !out_palette_rgba || !out_count) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
+    CallStart c;
+    c.snapshot(p);
+    KMG_TRY(check_fixed(c.fixed, k_min, KMG_ALGO_KMEANS, c.weighting));
+    KMG_TRY(check_index8_room(format == KMG_FORMAT_INDEX8, "k_max", k_max, c.alpha_cutoff != 0));
+    KMG_TRY(c.begin(p, rgba, w, h));
+    hipStream_t st = c.sg.st;
+    WorkingImage wi;                                                   // uploaded, shrunk and compacted once
+    KMG_TRY(working_image(p, c.d_rgba(), w, h, c.alpha_cutoff, c.weighting, st, wi));
+    return quality_of_working(p, c.d_rgba(), w, h, wi, k_min, k_max, target, mode, format, c.alpha_cutoff, c.fixed, st, out_palette_rgba, out_count,
+                              out, achieved, reached, nullptr);
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_reduce_quality_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *rgba, const uint32_t *widths,
+                                        const uint32_t *heights, uint32_t k_min, uint32_t k_max, uint32_t target, int mode, int format,
+                                        uint64_t max_resident_bytes, uint8_t *const *out_palette_rgba, uint32_t *out_counts,
+                                        void *const *out, kmg_error_stats *achieved, int *reached, kmg_batch_quality_report *report)
+try {
+    BatchCall call{BatchKind::kQuality, p, n_images, rgba, widths, heights, k_max, KMG_ALGO_KMEANS, mode, format, max_resident_bytes,
+                   (uint8_t *const *)out, out_palette_rgba, out_counts, k_min, target, achieved, reached};
+    KMG_TRY(call.run(nullptr));
+    if (report) *report = call.qrep;
     return KMG_OK;
 }
 KMG_ABI_CATCH

@@ -1,6 +1,7 @@
 // kmg_batch.hip -- many small images per launch on one device: the segmented versions of the small-image route (single-pick
 // initialisation k_init_first / k_init_pass<PICK> / k_init_pick_slots and the one-launch Lloyd step k_assign<1, true, CHUNKED, LOOP>
-// of kmg_kernels.hip) and kmg_dev_palette_batch on top of them (include/kmeans_hip.h).
+// of kmg_kernels.hip) and kmg_dev_palette_batch / kmg_dev_palette_batch_counts on top of them (include/kmeans_hip.h; DESIGN.md 4.16,
+// and 4.18 for the colour count per image).
 //
 // A batch is a table of BatchImage records in device memory, one per image.  The grid of a pass is the sum of the images' tiles
 // (256 pixels each, at most 2048 per image: the batch takes working images below 2^19 pixels); a workgroup finds its image by a
@@ -34,7 +35,7 @@ struct alignas(16) BatchImage {
     uint32_t n;                    // pixels, < 2^19
     uint32_t first_wg;             // index of the image's first workgroup in the grid
     uint32_t first_pixel;          // plus_plus_init.wgsl:161-168 `initial` of this image's width and height
-    uint32_t pad;
+    uint32_t k;                    // the image's own colour count: the size of its cent / acc tables, what its loop converges to
 };
 static_assert(sizeof(BatchImage) == 64, "BatchImage layout");
 
@@ -50,8 +51,9 @@ __device__ __forceinline__ Centroid centroid_of_pixel(const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------
-// Batched initialisation: pass j (1 <= j < k) of EVERY image in one launch -- k_init_pass<true> per image with one tile per
-// workgroup.  Every workgroup first derives centroid j - 1 of its image itself: the image's first pixel (j = 1: k_init_first) or the
+// Batched initialisation: pass j (1 <= j < the largest k of the piece) of EVERY image with j < its own k in one launch --
+// k_init_pass<true> per image with one tile per workgroup.  The workgroups of an image whose k is reached return at once: its slot
+// set of parity (k - 1) & 1 -- the one its last pass wrote -- then stays as it is until k_batch_init_pick reads it.  Every workgroup first derives centroid j - 1 of its image itself: the image's first pixel (j = 1: k_init_first) or the
 // pixel named by the largest slot of pass j - 1; the image's first workgroup also writes it to the table.  Then the pass: the
 // running distances against that centroid, the workgroup's largest key into the slot set of parity j & 1.
 // ------------------------------------------------------------------------------------------
@@ -62,6 +64,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_init_pass(const BatchImage *__
     __shared__ unsigned long long s_key[kBlock / 64];
     __shared__ Centroid s_c;
     const BatchImage im = img[batch_image_of(img, n_images, blockIdx.x)];
+    if (j >= im.k) return;                                           // (the whole workgroup: the image is uniform)
     const uint32_t wg = blockIdx.x - im.first_wg, tiles = (im.n + kBlock - 1u) / kBlock;
     s_lut[threadIdx.x] = lut[threadIdx.x];
     // (this thread's pixel and its running distance do not depend on the new centroid: requested before the pick)
@@ -102,12 +105,13 @@ __global__ __launch_bounds__(kBlock) void k_batch_init_pass(const BatchImage *__
     }
 }
 
-// The last centroid of every image, one workgroup per image: centroid j from the slots of pass j (k_init_pick_slots), or --
-// j = 0, a batch with k = 1 -- the image's first pixel (k_init_first).
-__global__ __launch_bounds__(kBlock) void k_batch_init_pick(const BatchImage *__restrict__ img, const float *__restrict__ lut, uint32_t j)
+// The last centroid of every image, one workgroup per image: centroid j = k - 1 of the image's own k from the slots of its pass j
+// (k_init_pick_slots), or -- j = 0, an image with k = 1 -- the image's first pixel (k_init_first).
+__global__ __launch_bounds__(kBlock) void k_batch_init_pick(const BatchImage *__restrict__ img, const float *__restrict__ lut)
 {
     __shared__ unsigned long long s_key[kBlock / 64];
     const BatchImage im = img[blockIdx.x];
+    const uint32_t j = im.k - 1u;
     const uint32_t tiles = (im.n + kBlock - 1u) / kBlock;
     unsigned long long kk = 0ull;
     if (j >= 1u) kk = init_max_slot(im.slots + (j & 1u) * tiles, tiles, s_key);
@@ -120,18 +124,24 @@ __global__ __launch_bounds__(kBlock) void k_batch_init_pick(const BatchImage *__
 // previous launch left (the image's first workgroup writes the centroids to the other buffer and the convergence count to the
 // image's state); then the assign, and the workgroup's bins are added to the image's sum buffer of this launch.  The buffers
 // rotate with the launch number, the same for every image; stop[i] != 0 (host-written between launches): image i has stopped.
-// LDS: [centroids kpad x 16 B][bins k x 32 B][sRGB table 1 KiB]
+// LDS: [centroids kpad x 16 B][bins k x 32 B][sRGB table 1 KiB], laid out by the image's own k; the launch is sized for the
+// largest k of the piece.
+// SCAN: the form of argmin_scan (kmg_lloyd_dev.h) -- kScanPlain / kScanChunked: the one form for every image of the piece (all k
+// below 32 / all from 32 on); kScanByImage: a piece with counts on both sides, each workgroup takes the form of its image's k by
+// a branch that is uniform over the workgroup.  Either way an image is scanned by the form k_assign takes at its k.
 // ------------------------------------------------------------------------------------------
-template <bool CHUNKED>
+enum { kScanPlain = 0, kScanChunked = 1, kScanByImage = 2 };
+
+template <int SCAN>
 __global__ __launch_bounds__(kBlock) void k_batch_assign(const BatchImage *__restrict__ img, uint32_t n_images,
-                                                         const uint32_t *__restrict__ stop, uint32_t k,
+                                                         const uint32_t *__restrict__ stop,
                                                          const float *__restrict__ lut, uint32_t launch, float convergence)
 {
     extern __shared__ float4 smem4[];
     const uint32_t which = batch_image_of(img, n_images, blockIdx.x);
     if (stop[which]) return;                                         // (the whole workgroup: `which` is uniform)
     const BatchImage im = img[which];
-    const uint32_t wg = blockIdx.x - im.first_wg;
+    const uint32_t wg = blockIdx.x - im.first_wg, k = im.k;
     const uint32_t kpad = (k + 3u) & ~3u;
     float4 *s_cent = smem4;
     unsigned long long *bins = reinterpret_cast<unsigned long long *>(smem4 + kpad);
@@ -188,7 +198,8 @@ __global__ __launch_bounds__(kBlock) void k_batch_assign(const BatchImage *__res
     // find_centroid.wgsl:29-41: min_distance = 100000.0 (squared here), found_index = 0, strict '<': the first minimum wins
     float best[1] = {1.0e10f};
     uint32_t idx[1] = {0u};
-    argmin_scan<1, CHUNKED, false>(pt, best, idx, s_cent, k, kpad);
+    if (SCAN == kScanChunked || (SCAN == kScanByImage && k >= 32u)) argmin_scan<1, true, false>(pt, best, idx, s_cent, k, kpad);
+    else argmin_scan<1, false, false>(pt, best, idx, s_cent, k, kpad);
     if (i < im.n) {
         unsigned long long *bin = bins + 4ull * idx[0];
         atomicAdd(bin + 0, (unsigned long long)(long long)lab_fix(L[0]));
@@ -204,13 +215,17 @@ __global__ __launch_bounds__(kBlock) void k_batch_assign(const BatchImage *__res
     }
 }
 
-// out[image][0 .. k) = the image's final centroids: the buffer its last launch wrote, stop[image] - 1 being that launch
-__global__ __launch_bounds__(kBlock) void k_batch_gather(const BatchImage *__restrict__ img, const uint32_t *__restrict__ stop, uint32_t k,
-                                                         Centroid *__restrict__ out)
+// The images' final centroids, concatenated: the buffer an image's last launch wrote, stop[image] - 1 being that launch.  cent0:
+// the first image's centroid buffers -- the images' pairs of buffers lie one behind the other, so an image whose pair starts 2 s
+// centroids behind cent0 has s centroids of earlier images before its own in `out`.
+__global__ __launch_bounds__(kBlock) void k_batch_gather(const BatchImage *__restrict__ img, const uint32_t *__restrict__ stop,
+                                                         const Centroid *__restrict__ cent0, Centroid *__restrict__ out)
 {
     const BatchImage im = img[blockIdx.x];
+    const uint32_t k = im.k;
     const Centroid *from = im.cent + (size_t)((stop[blockIdx.x] - 1u) & 1u) * k;
-    for (uint32_t c = threadIdx.x; c < k; c += kBlock) out[(size_t)blockIdx.x * k + c] = from[c];
+    Centroid *to = out + (size_t)(im.cent - cent0) / 2u;
+    for (uint32_t c = threadIdx.x; c < k; c += kBlock) to[c] = from[c];
 }
 
 }  // namespace kmg
@@ -231,12 +246,22 @@ uint32_t first_pixel_of(uint32_t w, uint32_t h)
     return (low & ~15u) | (15u - (low & 15u));
 }
 
-// One piece of a batch through the batched kernels: images idx[0 .. m) of the caller's arrays, each below kBatchMaxPixels.
-// Returns with the stream drained and the piece's state back with the processor.
+// One piece of a batch through the batched kernels: images idx[0 .. m) of the caller's arrays, each below kBatchMaxPixels; image
+// i has ks[i] colours and its table starts at centroids4[at[i]].  Returns with the stream drained and the piece's state back with
+// the processor.
 int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *const *d_rgba, const uint32_t *widths, const uint32_t *heights,
-              uint32_t k, float *centroids4, uint32_t *iterations, uint32_t *launches, hipStream_t st)
+              const uint32_t *ks, const size_t *at, float *centroids4, uint32_t *iterations, uint32_t *launches, hipStream_t st)
 {
     const kmg_options &o = p->opt;
+    // the piece's counts: before[q] = the colours of its images before q; k = the largest, k_low = the smallest
+    std::vector<size_t> before(m + 1u, 0);
+    uint32_t k = 0, k_low = 0xFFFFFFFFu;
+    for (uint32_t q = 0; q < m; ++q) {
+        const uint32_t kq = ks[idx[q]];
+        before[q + 1u] = before[q] + kq;
+        k = std::max(k, kq); k_low = std::min(k_low, kq);
+    }
+    const size_t k_sum = before[m];
     // the layout of the piece's block
     std::vector<BatchImage> rec(m);
     size_t off = 0;
@@ -244,10 +269,10 @@ int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *
     const size_t at_rec = room(sizeof(BatchImage) * m);
     const size_t at_stop = room(sizeof(uint32_t) * m);               // stop, state and sums: one memset
     const size_t at_state = room(sizeof(uint32_t) * kStateWords * m);
-    const size_t at_acc = room(sizeof(int64_t) * 12ull * k * m);
+    const size_t at_acc = room(sizeof(int64_t) * 12ull * k_sum);
     const size_t zero_bytes = off - at_stop;
-    const size_t at_cent = room(sizeof(Centroid) * 2ull * k * m);
-    const size_t at_out = room(sizeof(Centroid) * (size_t)k * m);
+    const size_t at_cent = room(sizeof(Centroid) * 2ull * k_sum);
+    const size_t at_out = room(sizeof(Centroid) * k_sum);
     std::vector<size_t> at_slots(m), at_dist(m);
     uint64_t grid = 0;
     for (uint32_t q = 0; q < m; ++q) {
@@ -257,7 +282,7 @@ int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *
         rec[q].n = (uint32_t)n;
         rec[q].first_wg = (uint32_t)grid;
         rec[q].first_pixel = first_pixel_of(widths[idx[q]], heights[idx[q]]);
-        rec[q].pad = 0u;
+        rec[q].k = ks[idx[q]];
         grid += tiles;
     }
     ArenaGuard blk;
@@ -270,8 +295,8 @@ int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *
         rec[q].rgba = (const uint32_t *)d_rgba[idx[q]];
         rec[q].dist = (float *)(base + at_dist[q]);
         rec[q].slots = (unsigned long long *)(base + at_slots[q]);
-        rec[q].cent = (Centroid *)(base + at_cent) + 2ull * k * q;
-        rec[q].acc = (int64_t *)(base + at_acc) + 12ull * k * q;
+        rec[q].cent = (Centroid *)(base + at_cent) + 2ull * before[q];
+        rec[q].acc = (int64_t *)(base + at_acc) + 12ull * before[q];
         rec[q].state = (uint32_t *)(base + at_state) + (size_t)kStateWords * q;
     }
     const BatchImage *d_rec = (const BatchImage *)(base + at_rec);
@@ -282,13 +307,13 @@ int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *
     HIP_TRY_DRAIN(st, upload_host_copy(base + at_rec, rec.data(), sizeof(BatchImage) * m, st));
     HIP_TRY_DRAIN(st, hipMemsetAsync(d_stop, 0, zero_bytes, st));
 
-    // initialisation: passes 1 .. k - 1 of every image, then the last centroid -- k launches whatever m is
+    // initialisation: passes 1 .. k - 1 of every image that has them, then the last centroid -- k launches whatever m is
     uint32_t n_launches = 0;
     for (uint32_t j = 1; j < k; ++j, ++n_launches) {
         hipLaunchKernelGGL(k_batch_init_pass, dim3((uint32_t)grid), dim3(kBlock), 0, st, d_rec, m, p->d_lut, j);
         HIP_TRY_DRAIN(st, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_batch_init_pick, dim3(m), dim3(kBlock), 0, st, d_rec, p->d_lut, k - 1u);
+    hipLaunchKernelGGL(k_batch_init_pick, dim3(m), dim3(kBlock), 0, st, d_rec, p->d_lut);
     HIP_TRY_DRAIN(st, hipGetLastError());
     ++n_launches;
 
@@ -296,8 +321,12 @@ int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *
     const uint32_t kpad = (k + 3u) & ~3u;
     const size_t lds = sizeof(float4) * kpad + 256 * sizeof(float) + sizeof(unsigned long long) * 4ull * k;
     auto step = [&](uint32_t l) {
-        if (k >= 32u) hipLaunchKernelGGL((k_batch_assign<true>), dim3((uint32_t)grid), dim3(kBlock), lds, st, d_rec, m, d_stop, k, p->d_lut, l, o.convergence);
-        else hipLaunchKernelGGL((k_batch_assign<false>), dim3((uint32_t)grid), dim3(kBlock), lds, st, d_rec, m, d_stop, k, p->d_lut, l, o.convergence);
+#define KMG_BATCH_ASSIGN(SCAN) \
+    hipLaunchKernelGGL((k_batch_assign<SCAN>), dim3((uint32_t)grid), dim3(kBlock), lds, st, d_rec, m, d_stop, p->d_lut, l, o.convergence)
+        if (k_low >= 32u) KMG_BATCH_ASSIGN(kScanChunked);
+        else if (k < 32u) KMG_BATCH_ASSIGN(kScanPlain);
+        else KMG_BATCH_ASSIGN(kScanByImage);
+#undef KMG_BATCH_ASSIGN
         ++n_launches;
         return hipGetLastError();
     };
@@ -312,7 +341,7 @@ int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *
         HIP_TRY(hipStreamSynchronize(st));
         bool stopped = false;
         for (uint32_t q = 0; q < m; ++q)
-            if (!stop[q] && state[(size_t)kStateWords * q] >= k) {   // :826-831
+            if (!stop[q] && state[(size_t)kStateWords * q] >= rec[q].k) {   // :826-831
                 stop[q] = l + 1u;
                 its[q] = it;
                 --running;
@@ -326,16 +355,16 @@ int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *
             stop[q] = o.max_iterations + 1u;
             its[q] = o.max_iterations - 1u;
         }
-    std::vector<Centroid> cent((size_t)k * m);
+    std::vector<Centroid> cent(k_sum);
     HIP_TRY_DRAIN(st, upload_host_copy(d_stop, stop.data(), sizeof(uint32_t) * m, st));
-    hipLaunchKernelGGL(k_batch_gather, dim3(m), dim3(kBlock), 0, st, d_rec, d_stop, k, d_out);
+    hipLaunchKernelGGL(k_batch_gather, dim3(m), dim3(kBlock), 0, st, d_rec, d_stop, (const Centroid *)(base + at_cent), d_out);
     HIP_TRY_DRAIN(st, hipGetLastError());
     HIP_TRY_DRAIN(st, hipMemcpyAsync(cent.data(), d_out, sizeof(Centroid) * cent.size(), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t q = 0; q < m; ++q) {
-        float *c4 = centroids4 + 4ull * k * idx[q];
-        for (uint32_t c = 0; c < k; ++c) {
-            const Centroid &v = cent[(size_t)k * q + c];
+        float *c4 = centroids4 + at[idx[q]];
+        for (uint32_t c = 0; c < rec[q].k; ++c) {
+            const Centroid &v = cent[before[q] + c];
             c4[4 * c] = v.L; c4[4 * c + 1] = v.a; c4[4 * c + 2] = v.b; c4[4 * c + 3] = 1.0f;
         }
         if (iterations) iterations[idx[q]] = its[q];
@@ -346,18 +375,19 @@ int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *
 
 }  // namespace
 
-int kmg::dev_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths, const uint32_t *heights,
-                           uint32_t k, float *centroids4, uint32_t *iterations, kmg_batch_report *report, hipStream_t st)
+int kmg::dev_palette_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths,
+                                  const uint32_t *heights, const uint32_t *ks, float *centroids4, uint32_t *iterations,
+                                  kmg_batch_report *report, hipStream_t st)
 {
-    KMG_TRY(check_batch_prefix(p, n_images, !d_rgba || !widths || !heights || !centroids4, "bad palette_batch arguments", d_rgba, widths, heights));
-    KMG_TRY(check_k(k));
     HIP_TRY(hipSetDevice(p->device));
     kmg_batch_report rep = {0u, 0u, 1u, 0u};
     std::vector<uint32_t> its(n_images, 0u), piece;
+    std::vector<size_t> at(n_images, 0);
+    for (uint32_t i = 1; i < n_images; ++i) at[i] = at[i - 1] + 4ull * ks[i - 1];
     uint64_t grid = 0;
     auto flush = [&]() -> int {
         if (piece.empty()) return KMG_OK;
-        KMG_TRY(batch_run(p, piece.data(), (uint32_t)piece.size(), d_rgba, widths, heights, k, centroids4, its.data(), &rep.launches, st));
+        KMG_TRY(batch_run(p, piece.data(), (uint32_t)piece.size(), d_rgba, widths, heights, ks, at.data(), centroids4, its.data(), &rep.launches, st));
         piece.clear();
         grid = 0;
         return KMG_OK;
@@ -367,10 +397,10 @@ int kmg::dev_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *c
         if (n >= kBatchMaxPixels) {
             // a large working image: the per-image path (its own choice of route; the same results by the library's guarantee)
             LloydGuard g;
-            KMG_TRY(lloyd_create_impl(p, k, &g.s, st));
+            KMG_TRY(lloyd_create_impl(p, ks[i], &g.s, st));
             KMG_TRY(kmg_lloyd_init_centroids(g.s, d_rgba[i], widths[i], heights[i], st));
             KMG_TRY(kmg_lloyd_run(g.s, d_rgba[i], n, nullptr, &its[i], st));
-            KMG_TRY(kmg_lloyd_get_centroids(g.s, centroids4 + 4ull * k * i, st));
+            KMG_TRY(kmg_lloyd_get_centroids(g.s, centroids4 + at[i], st));
             ++rep.fallback;
             continue;
         }
@@ -388,10 +418,30 @@ int kmg::dev_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *c
     return KMG_OK;
 }
 
+// (the case where every image has k colours)
+int kmg::dev_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths, const uint32_t *heights,
+                           uint32_t k, float *centroids4, uint32_t *iterations, kmg_batch_report *report, hipStream_t st)
+{
+    KMG_TRY(check_batch_prefix(p, n_images, !d_rgba || !widths || !heights || !centroids4, "bad palette_batch arguments", d_rgba, widths, heights));
+    KMG_TRY(check_k(k));
+    const std::vector<uint32_t> ks(n_images, k);
+    return dev_palette_batch_counts(p, n_images, d_rgba, widths, heights, ks.data(), centroids4, iterations, report, st);
+}
+
 extern "C" int kmg_dev_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths,
                                      const uint32_t *heights, uint32_t k, float *centroids4, uint32_t *iterations,
                                      kmg_batch_report *report, void *stream)
 try {
     return dev_palette_batch(p, n_images, d_rgba, widths, heights, k, centroids4, iterations, report, S(stream));
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_dev_palette_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths,
+                                            const uint32_t *heights, const uint32_t *ks, float *centroids4, uint32_t *iterations,
+                                            kmg_batch_report *report, void *stream)
+try {
+    KMG_TRY(check_batch_prefix(p, n_images, !d_rgba || !widths || !heights || !ks || !centroids4, "bad palette_batch arguments", d_rgba, widths, heights));
+    for (uint32_t i = 0; i < n_images; ++i) KMG_TRY(check_k(ks[i]));
+    return dev_palette_batch_counts(p, n_images, d_rgba, widths, heights, ks, centroids4, iterations, report, S(stream));
 }
 KMG_ABI_CATCH

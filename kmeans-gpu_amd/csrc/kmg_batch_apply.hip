@@ -15,6 +15,8 @@
 
 #include "kmg_state.h"
 
+#include <functional>
+
 #include "kmg_apply_dev.h"
 #include "kmg_apply_route.h"
 #include "kmg_batch_layout.h"
@@ -23,7 +25,8 @@ namespace kmg {
 
 // One image of a batched output launch.  cent / pal: the image's centroid table and palette words (k + 1: the dither sentinel's
 // behind them), shared by all images or one per image.  aligned: what k_apply takes as `aligned` for this image's pointers (bit 0;
-// index formats: the alpha cutoff in bits 8..15).  k, mode_format (mode | format << 8) and alpha_cutoff are common to the launch.
+// index formats: the alpha cutoff in bits 8..15).  k: the image's own colour count (kmg_dev_apply_batch_counts; the other calls
+// fill in the same for every image).  mode_format (mode | format << 8) and alpha_cutoff are common to the launch.
 struct alignas(16) BatchApplyImage {
     const uint32_t *rgba;          // n pixels
     void *out;                     // n outputs of the launch's format
@@ -40,13 +43,21 @@ struct alignas(16) BatchApplyImage {
 };
 static_assert(sizeof(BatchApplyImage) == 64, "BatchApplyImage layout");
 
-// workgroup wg0 + blockIdx.x of the batch's grid: one tile of its image
-template <int PPT, bool DITHER, bool CHUNKED, bool ALPHA, typename OutT>
+// workgroup wg0 + blockIdx.x of the batch's grid: one tile of its image.  ONE (a dither launch whose images have counts of their
+// own, one of them k = 1): such an image is not dithered (mix_colors.wgsl:104-108) -- its workgroups, uniformly, take the replace pass.
+template <int PPT, bool DITHER, bool CHUNKED, bool ALPHA, typename OutT, bool ONE = false>
 __global__ __launch_bounds__(kBlock) void k_batch_apply(const BatchApplyImage *__restrict__ img, uint32_t n_images, uint32_t wg0,
                                                         const float *__restrict__ lut)
 {
+    static_assert(!ONE || (DITHER && !CHUNKED), "ONE: a dither launch below k = 32");
     const uint32_t wg = wg0 + blockIdx.x;
     const BatchApplyImage im = img[batch_image_of(img, n_images, wg)];
+    if (ONE && im.k == 1u) {
+        apply_tiles<PPT, false, false, ALPHA, OutT>(im.rgba, im.w, (uint64_t)im.n, 0u, im.cent, im.k, lut, im.pal, im.threshold,
+                                                    static_cast<OutT *>(im.out), (int)im.aligned, (uint64_t)(wg - im.first_wg),
+                                                    0x100000000ull);
+        return;
+    }
     // (one tile: the stride leaves the image)
     apply_tiles<PPT, DITHER, CHUNKED, ALPHA, OutT>(im.rgba, im.w, (uint64_t)im.n, 0u, im.cent, im.k, lut, im.pal, im.threshold,
                                                    static_cast<OutT *>(im.out), (int)im.aligned, (uint64_t)(wg - im.first_wg),
@@ -68,13 +79,19 @@ int batch_apply_ppt()
     return ppt == 4 || ppt == 8 ? ppt : kBatchApplyPPT;
 }
 
+// k: the largest count of the launch's images (all below 32, or all from 32 on); one: dither, and an image of the launch has k = 1
 template <int PPT, typename OutT>
 void launch_batch_apply_t(const BatchApplyImage *rec, uint32_t m, kmg::BatchLaunch cut, uint32_t k, const float *lut, bool dither, bool alpha,
-                          hipStream_t st)
+                          bool one, hipStream_t st)
 {
     const uint32_t kpad = (k + 3u) & ~3u;
     const bool chunked = k >= 32;
     const size_t lds = sizeof(float4) * kpad + (256 + 16) * sizeof(float);
+    if (one) {
+        if (alpha) hipLaunchKernelGGL((k_batch_apply<PPT, true, false, true, OutT, true>), dim3(cut.count), dim3(kBlock), lds, st, rec, m, cut.first, lut);
+        else hipLaunchKernelGGL((k_batch_apply<PPT, true, false, false, OutT, true>), dim3(cut.count), dim3(kBlock), lds, st, rec, m, cut.first, lut);
+        return;
+    }
 #define KMG_BATCH_APPLY(D, C, A) \
     hipLaunchKernelGGL((k_batch_apply<PPT, D, C, A, OutT>), dim3(cut.count), dim3(kBlock), lds, st, rec, m, cut.first, lut)
     if (alpha) {
@@ -89,11 +106,11 @@ void launch_batch_apply_t(const BatchApplyImage *rec, uint32_t m, kmg::BatchLaun
 
 template <int PPT>
 hipError_t launch_batch_apply(const BatchApplyImage *rec, uint32_t m, kmg::BatchLaunch cut, uint32_t k, const float *lut, bool dither,
-                              bool alpha, int format, hipStream_t st)
+                              bool alpha, bool one, int format, hipStream_t st)
 {
-    if (format == KMG_FORMAT_INDEX8) launch_batch_apply_t<PPT, uint8_t>(rec, m, cut, k, lut, dither, alpha, st);
-    else if (format == KMG_FORMAT_INDEX16) launch_batch_apply_t<PPT, uint16_t>(rec, m, cut, k, lut, dither, alpha, st);
-    else launch_batch_apply_t<PPT, uint32_t>(rec, m, cut, k, lut, dither, alpha, st);
+    if (format == KMG_FORMAT_INDEX8) launch_batch_apply_t<PPT, uint8_t>(rec, m, cut, k, lut, dither, alpha, one, st);
+    else if (format == KMG_FORMAT_INDEX16) launch_batch_apply_t<PPT, uint16_t>(rec, m, cut, k, lut, dither, alpha, one, st);
+    else launch_batch_apply_t<PPT, uint32_t>(rec, m, cut, k, lut, dither, alpha, one, st);
     return hipGetLastError();
 }
 
@@ -105,14 +122,14 @@ uint32_t aligned_word(const void *src, const void *out, int format, uint32_t cut
     return (uint32_t)output_aligned<uint32_t>(src, out);
 }
 
-// The joined images idx[0 .. m) of the caller's arrays through the batched kernel: records and tables in one block of the
-// processor, one upload, the launches.  Only enqueues; *blk holds the block until the caller has drained the stream.
+// Images idx[0 .. m) of the caller's arrays through ONE chain of the batched kernel (their counts all below 32, or all from 32
+// on): records and tables in one block of the processor, one upload, the launches.  Image i has ks[i] colours and the table at
+// c4[at[i]]; shared: one table for all (that of idx[0]).  Only enqueues; *blk holds the block until the caller has drained the stream.
 int batch_apply_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *const *d_src, const uint32_t *widths,
-                    const uint32_t *heights, const float *c4, uint32_t n_tables, uint32_t k, int mode, int format, uint32_t cutoff,
-                    void *const *d_out, uint32_t *launches, ArenaGuard *blk, hipStream_t st)
+                    const uint32_t *heights, const float *c4, const size_t *at, const uint32_t *ks, bool shared, int mode, int format,
+                    uint32_t cutoff, void *const *d_out, uint32_t *launches, ArenaGuard *blk, hipStream_t st)
 {
     const int ppt = batch_apply_ppt();
-    const bool dither = mode == KMG_MODE_DITHER && k > 1;              // mix_colors.wgsl:104-108
     std::vector<uint64_t> pixels(m);
     for (uint32_t q = 0; q < m; ++q) pixels[q] = (uint64_t)widths[idx[q]] * heights[idx[q]];
     std::vector<uint32_t> first_wg;
@@ -120,11 +137,20 @@ int batch_apply_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uin
     if (!batch_grid(pixels.data(), m, (uint64_t)kBlock * ppt, first_wg, &grid))
         return fail(KMG_ERR_UNSUPPORTED, "the batch has more than 2^32-1 tiles");
 
-    // the block: [records][table 0: k centroids, k + 1 palette words][table 1] ...
-    const uint32_t tables = n_tables == 1 ? 1u : m;
+    // the block: [records][table 0: k centroids, k + 1 palette words][table 1] ... -- each table by its own k
+    const uint32_t tables = shared ? 1u : m;
     const size_t rec_bytes = pad256(sizeof(BatchApplyImage) * (size_t)m);
-    const size_t cent_bytes = sizeof(Centroid) * (size_t)k, table_bytes = pad256(cent_bytes + sizeof(uint32_t) * ((size_t)k + 1));
-    const size_t bytes = rec_bytes + table_bytes * tables;
+    std::vector<size_t> table_at(tables + 1u, rec_bytes);
+    uint32_t k = 0;                                                    // the largest count: the launch's LDS
+    bool dither = false, one = false;                                  // mix_colors.wgsl:104-108: an image with k = 1 is not dithered
+    for (uint32_t q = 0; q < m; ++q) {
+        const uint32_t kq = ks[idx[q]];
+        if (q < tables) table_at[q + 1u] = table_at[q] + pad256(sizeof(Centroid) * (size_t)kq + sizeof(uint32_t) * ((size_t)kq + 1));
+        k = std::max(k, kq);
+        if (mode == KMG_MODE_DITHER) (kq > 1 ? dither : one) = true;
+    }
+    one = one && dither;
+    const size_t bytes = table_at[tables];
     {
         const hipError_t e = blk->acquire(p, bytes);
         if (e != hipSuccess) { blk->base = nullptr; return fail_hip(e, "batch output tables allocation"); }
@@ -135,27 +161,28 @@ int batch_apply_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uin
     const float sentinel[3] = {10000.0f, 10000.0f, 10000.0f};
     for (uint32_t t = 0; t < tables; ++t) {
         // per-centroid work on the host, as a plan does it (kmg_apply.hip plan_create)
-        const float *mine = c4 + (n_tables == 1 ? 0 : 4ull * k * idx[t]);
-        Centroid *hc = (Centroid *)(host.data() + rec_bytes + table_bytes * t);
-        uint8_t *pal = (uint8_t *)hc + cent_bytes;
-        for (uint32_t i = 0; i < k; ++i) hc[i] = {mine[4 * i], mine[4 * i + 1], mine[4 * i + 2], chroma(mine[4 * i + 1], mine[4 * i + 2])};
-        for (uint32_t i = 0; i <= k; ++i) shader_lab_to_rgba8(i < k ? mine + 4 * i : sentinel, pal + 4 * i);
-        thr[t] = dither ? dither_threshold(mine, k) : 0.0f;
+        const uint32_t kt = ks[idx[t]];
+        const float *mine = c4 + at[idx[t]];
+        Centroid *hc = (Centroid *)(host.data() + table_at[t]);
+        uint8_t *pal = (uint8_t *)hc + sizeof(Centroid) * (size_t)kt;
+        for (uint32_t i = 0; i < kt; ++i) hc[i] = {mine[4 * i], mine[4 * i + 1], mine[4 * i + 2], chroma(mine[4 * i + 1], mine[4 * i + 2])};
+        for (uint32_t i = 0; i <= kt; ++i) shader_lab_to_rgba8(i < kt ? mine + 4 * i : sentinel, pal + 4 * i);
+        thr[t] = mode == KMG_MODE_DITHER && kt > 1 ? dither_threshold(mine, kt) : 0.0f;
     }
     BatchApplyImage *rec = (BatchApplyImage *)host.data();
     for (uint32_t q = 0; q < m; ++q) {
-        const uint32_t t = n_tables == 1 ? 0u : q;
+        const uint32_t t = shared ? 0u : q;
         BatchApplyImage &r = rec[q];
         r.rgba = (const uint32_t *)d_src[idx[q]];
         r.out = d_out[idx[q]];
-        r.cent = (const Centroid *)(base + rec_bytes + table_bytes * t);
-        r.pal = (const uint32_t *)((const uint8_t *)r.cent + cent_bytes);
+        r.cent = (const Centroid *)(base + table_at[t]);
+        r.pal = (const uint32_t *)((const uint8_t *)r.cent + sizeof(Centroid) * (size_t)ks[idx[q]]);
         r.n = (uint32_t)pixels[q];
         r.w = widths[idx[q]];
         r.first_wg = first_wg[q];
         r.threshold = thr[t];
         r.aligned = aligned_word(r.rgba, r.out, format, cutoff);
-        r.k = k;
+        r.k = ks[idx[q]];
         r.mode_format = (uint32_t)mode | ((uint32_t)format << 8);
         r.alpha_cutoff = cutoff;
     }
@@ -163,12 +190,12 @@ int batch_apply_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uin
     for (const BatchLaunch &cut : batch_launches(grid)) {
 #ifdef KMG_TOOLS
         if (ppt != kBatchApplyPPT) {
-            HIP_TRY(launch_batch_apply<12 - kBatchApplyPPT>((const BatchApplyImage *)base, m, cut, k, p->d_lut, dither, cutoff != 0, format, st));
+            HIP_TRY(launch_batch_apply<12 - kBatchApplyPPT>((const BatchApplyImage *)base, m, cut, k, p->d_lut, dither, cutoff != 0, one, format, st));
             ++*launches;
             continue;
         }
 #endif
-        HIP_TRY(launch_batch_apply<kBatchApplyPPT>((const BatchApplyImage *)base, m, cut, k, p->d_lut, dither, cutoff != 0, format, st));
+        HIP_TRY(launch_batch_apply<kBatchApplyPPT>((const BatchApplyImage *)base, m, cut, k, p->d_lut, dither, cutoff != 0, one, format, st));
         ++*launches;
     }
     return KMG_OK;
@@ -176,36 +203,52 @@ int batch_apply_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uin
 
 }  // namespace
 
-int kmg::apply_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
-                     const float *c4, uint32_t n_tables, uint32_t k, int mode, int format, uint32_t cutoff, void *const *d_out,
-                     kmg_batch_apply_report *report, hipStream_t st)
+int kmg::apply_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
+                            const float *c4, const size_t *at, const uint32_t *ks, bool shared, int mode, int format, uint32_t cutoff,
+                            void *const *d_out, kmg_batch_apply_report *report, hipStream_t st)
 {
-    // which images join the launch (kmg_apply_route.h): the others take their own output pass, after the launch is on its way
+    // which images join a launch (kmg_apply_route.h), each asked with its own k: the others take their own output pass, after the
+    // launches are on their way.  The chunked scan is a launch's: the joined images below k = 32 go out as one chain, the others
+    // as a second.
     const int forced = forced_strategy(p);
     const bool mask_words_only = (p->strategy.load(std::memory_order_relaxed) & KMG_STRATEGY_MASK_WORDS) != 0;
-    std::vector<uint32_t> joined, alone;
+    std::vector<uint32_t> joined[2], alone;
     for (uint32_t i = 0; i < n_images; ++i)
-        (batch_apply_joins(mode, k, (uint64_t)widths[i] * heights[i], forced, mask_words_only, n_images) ? joined : alone).push_back(i);
-    ArenaGuard blk;
+        (batch_apply_joins(mode, ks[i], (uint64_t)widths[i] * heights[i], forced, mask_words_only, n_images) ? joined[ks[i] >= 32u ? 1 : 0] : alone)
+            .push_back(i);
+    ArenaGuard blk[2];
     uint32_t launches = 0;
-    if (!joined.empty())
-        KMG_TRY_DRAIN(st, batch_apply_run(p, joined.data(), (uint32_t)joined.size(), d_src, widths, heights, c4, n_tables, k, mode, format, cutoff,
-                                          d_out, &launches, &blk, st));
+    for (int c = 0; c < 2; ++c)
+        if (!joined[c].empty())
+            KMG_TRY_DRAIN(st, batch_apply_run(p, joined[c].data(), (uint32_t)joined[c].size(), d_src, widths, heights, c4, at, ks, shared, mode,
+                                              format, cutoff, d_out, &launches, &blk[c], st));
     for (const uint32_t i : alone)
-        KMG_TRY_DRAIN(st, dev_apply(p, d_src[i], widths[i], heights[i], 0, c4 + (n_tables == 1 ? 0 : 4ull * k * i), k, mode, (uint8_t *)d_out[i], st,
-                                    cutoff, format));
-    HIP_TRY(hipStreamSynchronize(st));                                 // (the block is idle again)
+        KMG_TRY_DRAIN(st, dev_apply(p, d_src[i], widths[i], heights[i], 0, c4 + at[i], ks[i], mode, (uint8_t *)d_out[i], st, cutoff, format));
+    HIP_TRY(hipStreamSynchronize(st));                                 // (the blocks are idle again)
     if (report) {
         report->launches += launches;
-        report->batched += (uint32_t)joined.size();
+        report->batched += (uint32_t)(joined[0].size() + joined[1].size());
         report->per_image += (uint32_t)alone.size();
     }
     return KMG_OK;
 }
 
-int kmg::apply_batch_download(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths,
-                              const uint32_t *heights, const float *c4, uint32_t n_tables, uint32_t k, int mode, int format, uint32_t cutoff,
-                              uint8_t *const *out, kmg_batch_apply_report *report, hipStream_t st)
+// (the case where every table has k colours: n_tables = 1, one table for all images, or one per image)
+int kmg::apply_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
+                     const float *c4, uint32_t n_tables, uint32_t k, int mode, int format, uint32_t cutoff, void *const *d_out,
+                     kmg_batch_apply_report *report, hipStream_t st)
+{
+    const std::vector<uint32_t> ks(n_images, k);
+    std::vector<size_t> at(n_images, 0);
+    for (uint32_t i = 0; n_tables != 1 && i < n_images; ++i) at[i] = 4ull * k * i;
+    return apply_batch_counts(p, n_images, d_src, widths, heights, c4, at.data(), ks.data(), n_tables == 1, mode, format, cutoff, d_out, report, st);
+}
+
+// The outputs of apply_batch / apply_batch_counts in one stream-ordered block, then to the host
+namespace {
+
+int batch_download(kmg_processor *p, uint32_t n_images, const uint32_t *widths, const uint32_t *heights, int format, uint8_t *const *out,
+                   hipStream_t st, const std::function<int(void *const *)> &apply)
 {
     const uint32_t bpp = format_bytes(format);
     std::vector<uint64_t> pixels(n_images), offset;
@@ -217,11 +260,31 @@ int kmg::apply_batch_download(kmg_processor *p, uint32_t n_images, const uint8_t
     HIP_TRY(block.alloc(p, (size_t)total, st));
     std::vector<void *> d_out(n_images);
     for (uint32_t i = 0; i < n_images; ++i) d_out[i] = (uint8_t *)block.ptr + offset[i];
-    KMG_TRY(apply_batch(p, n_images, d_src, widths, heights, c4, n_tables, k, mode, format, cutoff, d_out.data(), report, st));
+    KMG_TRY(apply(d_out.data()));
     for (uint32_t i = 0; i < n_images; ++i)
         HIP_TRY_DRAIN(st, copy_host_image(p, out[i], d_out[i], (size_t)pixels[i] * bpp, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return KMG_OK;
+}
+
+}  // namespace
+
+int kmg::apply_batch_download(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths,
+                              const uint32_t *heights, const float *c4, uint32_t n_tables, uint32_t k, int mode, int format, uint32_t cutoff,
+                              uint8_t *const *out, kmg_batch_apply_report *report, hipStream_t st)
+{
+    return batch_download(p, n_images, widths, heights, format, out, st, [&](void *const *d_out) {
+        return apply_batch(p, n_images, d_src, widths, heights, c4, n_tables, k, mode, format, cutoff, d_out, report, st);
+    });
+}
+
+int kmg::apply_batch_counts_download(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths,
+                                     const uint32_t *heights, const float *c4, const size_t *at, const uint32_t *ks, int mode, int format,
+                                     uint32_t cutoff, uint8_t *const *out, kmg_batch_apply_report *report, hipStream_t st)
+{
+    return batch_download(p, n_images, widths, heights, format, out, st, [&](void *const *d_out) {
+        return apply_batch_counts(p, n_images, d_src, widths, heights, c4, at, ks, false, mode, format, cutoff, d_out, report, st);
+    });
 }
 
 extern "C" int kmg_dev_apply_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths,
@@ -247,6 +310,33 @@ try {
     HIP_TRY(hipSetDevice(p->device));
     kmg_batch_apply_report rep = {0u, 0u, 0u, 1u};
     KMG_TRY(apply_batch(p, n_images, d_rgba, widths, heights, centroids4, n_tables, k, mode, format, cutoff, d_out, &rep, S(stream)));
+    if (report) *report = rep;
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_dev_apply_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths,
+                                          const uint32_t *heights, const float *centroids4, const uint32_t *ks, int mode, int format,
+                                          void *const *d_out, kmg_batch_apply_report *report, void *stream)
+try {
+    // the refusals of kmg_dev_apply_batch, image by image with its own count
+    KMG_TRY(check_batch_prefix(p, n_images, !d_rgba || !widths || !heights || !centroids4 || !ks || !d_out, "a batch array is NULL", d_rgba, widths,
+                               heights, d_out));
+    for (uint32_t i = 0; i < n_images; ++i) KMG_TRY(check_k_nonzero(ks[i]));
+    KMG_TRY(check_mode(mode));
+    KMG_TRY(check_format(format));
+    for (uint32_t i = 0; i < n_images; ++i) KMG_TRY(check_k_limit(ks[i]));
+    const uint32_t cutoff = p->alpha_cutoff.load(std::memory_order_relaxed);
+    std::vector<size_t> at(n_images, 0);
+    for (uint32_t i = 1; i < n_images; ++i) at[i] = at[i - 1] + 4ull * ks[i - 1];
+    if (format != KMG_FORMAT_RGBA8)
+        for (uint32_t i = 0; i < n_images; ++i) KMG_TRY(check_index_format(centroids4 + at[i], ks[i], mode, format, cutoff));
+    if (format == KMG_FORMAT_INDEX16)
+        for (uint32_t i = 0; i < n_images; ++i)
+            if (reinterpret_cast<uintptr_t>(d_out[i]) & 1u) return fail(KMG_ERR_INVALID_ARGUMENT, "image %u: INDEX16 output must be 2-byte aligned", i);
+    HIP_TRY(hipSetDevice(p->device));
+    kmg_batch_apply_report rep = {0u, 0u, 0u, 1u};
+    KMG_TRY(apply_batch_counts(p, n_images, d_rgba, widths, heights, centroids4, at.data(), ks, false, mode, format, cutoff, d_out, &rep, S(stream)));
     if (report) *report = rep;
     return KMG_OK;
 }

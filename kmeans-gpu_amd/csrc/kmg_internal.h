@@ -106,6 +106,23 @@ int palette_of_working(kmg_processor *p, const uint8_t *d_src, uint32_t sw, uint
 // small ones through the batched kernels.  Synchronises `st`.
 int dev_palette_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths, const uint32_t *heights,
                       uint32_t k, float *centroids4, uint32_t *iterations, kmg_batch_report *report, hipStream_t st);
+// kmg_dev_palette_batch_counts, arguments already checked: image i has ks[i] colours, its table starts at centroids4[4 * (ks[0] + ... +
+// ks[i - 1])].  launches: the largest count + 2 + the most iterations, per piece.
+int dev_palette_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_rgba, const uint32_t *widths, const uint32_t *heights,
+                             const uint32_t *ks, float *centroids4, uint32_t *iterations, kmg_batch_report *report, hipStream_t st);
+// apply_batch with a count per image: image i has ks[i] colours and the table at centroids4[at[i]] (shared: every image the table
+// of the first, all ks equal).  The joined images go out as at most two chains of launches, those below k = 32 and the others.
+int apply_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
+                       const float *centroids4, const size_t *at, const uint32_t *ks, bool shared, int mode, int format, uint32_t alpha_cutoff,
+                       void *const *d_out, kmg_batch_apply_report *report, hipStream_t st);
+int apply_batch_counts_download(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
+                                const float *centroids4, const size_t *at, const uint32_t *ks, int mode, int format, uint32_t alpha_cutoff,
+                                uint8_t *const *out, kmg_batch_apply_report *report, hipStream_t st);
+// kmg_dev_compare_batch on a hipStream_t, arguments already checked (kmg_batch_error.hip): COMBINES into the n_images records at
+// d_stats.  Only enqueues; its scratch goes back to the pool in stream order.  launches (may be NULL): ADDS the statistics launches.
+int dev_compare_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const void *const *d_out, const uint64_t *n_pixels,
+                      int format, const uint8_t *palettes_rgba, const uint32_t *ks, uint32_t alpha_cutoff, uint32_t what,
+                      kmg_error_stats *d_stats, hipStream_t st, uint32_t *launches);
 // the weighting set on a processor right now (kmg_processor.hip; kmg_processor_set_weighting)
 int processor_weighting(kmg_processor *p);
 // the number of fixed colours set on a processor right now (kmg_processor.hip; kmg_processor_set_fixed_colors)

@@ -12,6 +12,7 @@
 //   processor.reduce_batch(color_count, images, algo, mode) -> whole images per device, side by side
 //   processor.palette_batch(color_count, images, algo) / reduce_batch(color_count, images, algo, mode, max_resident_bytes)
 //                                                          -> many small images per launch on one device (kmg_*_batch)
+//   processor.reduce_quality_batch(images, max_delta_e, k_min, k_max, mode) -> reduce_quality of many small images, searched in lock step
 //   processor.find_batch(images, colors, mode) / reduce_indexed_batch(color_count, images, algo, mode)
 //                                                          -> their index maps, the output passes in one launch
 //   processor.compare(source, output[, colors])         -> kmg_error_stats: exact error sums of an output against its source
@@ -357,6 +358,40 @@ public:
         check(kmg_reduce_indexed_batch(single(), (uint32_t)images.size(), src.data(), ws.data(), hs.data(), color_count, (int)algo, (int)reduce_mode,
                                        format, max_resident_bytes, pals.data(), counts.data(), dst.data(), batch_report, apply_report));
         for (size_t i = 0; i < images.size(); ++i) out[i].palette.resize(counts[i]);
+        return out;
+    }
+
+    // kmg_reduce_quality_batch (include/kmeans_hip.h): reduce_quality() of many small images on a single-device processor, every
+    // round of their searches one launch chain -- image by image what reduce_quality gives.  report: what the call did.  The batch
+    // must not be empty.
+    std::vector<Quality> reduce_quality_batch(const std::vector<Image> &images, double max_delta_e, uint32_t k_min, uint32_t k_max,
+                                              ReduceMode reduce_mode, bool alpha_mode = false, uint64_t max_resident_bytes = 0,
+                                              kmg_batch_quality_report *report = nullptr) const
+    {
+        std::vector<Quality> out(images.size());
+        std::vector<const uint8_t *> src;
+        std::vector<void *> dst;
+        std::vector<uint8_t *> pals;
+        std::vector<uint32_t> ws, hs, counts(images.size() ? images.size() : 1);
+        std::vector<kmg_error_stats> achieved(images.size() ? images.size() : 1);
+        std::vector<int> reached(images.size() ? images.size() : 1, 0);
+        for (size_t i = 0; i < images.size(); ++i) {
+            out[i].indexed = indexed_for(images[i], k_max, alpha_mode);
+            out[i].indexed.palette.resize(k_max ? k_max : 1);
+            src.push_back(bytes(images[i])); dst.push_back(index_data(out[i].indexed));
+            pals.push_back(reinterpret_cast<uint8_t *>(out[i].indexed.palette.data()));
+            ws.push_back(images[i].dims.first); hs.push_back(images[i].dims.second);
+        }
+        const double t = std::floor(4096.0 * max_delta_e * max_delta_e);
+        const uint32_t target = t >= 4294967295.0 ? 0xFFFFFFFFu : (t > 0.0 ? (uint32_t)t : 0u);
+        const int format = images.empty() ? KMG_FORMAT_INDEX8 : out[0].indexed.format;
+        check(kmg_reduce_quality_batch(single(), (uint32_t)images.size(), src.data(), ws.data(), hs.data(), k_min, k_max, target, (int)reduce_mode,
+                                       format, max_resident_bytes, pals.data(), counts.data(), dst.data(), achieved.data(), reached.data(), report));
+        for (size_t i = 0; i < images.size(); ++i) {
+            out[i].indexed.palette.resize(counts[i]);
+            out[i].achieved = achieved[i];
+            out[i].reached = reached[i] != 0;
+        }
         return out;
     }
 

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "BatchReport", "BatchApplyReport", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "BatchReport", "BatchApplyReport", "BatchQualityReport", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -206,6 +206,14 @@ class BatchReport(C.Structure):         # include/kmeans_hip.h kmg_batch_report:
                 f"fallback={self.fallback})")
 
 
+class BatchQualityReport(C.Structure):  # include/kmeans_hip.h kmg_batch_quality_report: 32 bytes
+    _fields_ = [("rounds", C.c_uint32), ("palette_runs", C.c_uint32), ("launches", C.c_uint32), ("measure_launches", C.c_uint32),
+                ("batched", C.c_uint32), ("per_image", C.c_uint32), ("sub_batches", C.c_uint32), ("fallback", C.c_uint32)]
+
+    def __repr__(self):
+        return ("BatchQualityReport(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")")
+
+
 class BatchApplyReport(C.Structure):    # include/kmeans_hip.h kmg_batch_apply_report: 16 bytes
     _fields_ = [("launches", C.c_uint32), ("batched", C.c_uint32), ("per_image", C.c_uint32), ("sub_batches", C.c_uint32)]
 
@@ -371,6 +379,7 @@ SYMBOLS = [
     "kmg_find_indexed", "kmg_reduce_indexed", "kmg_apply_plan_create_format", "kmg_dev_apply_format",
     "kmg_dev_palette_batch", "kmg_palette_batch", "kmg_reduce_batch",
     "kmg_dev_apply_batch", "kmg_find_batch", "kmg_reduce_indexed_batch",
+    "kmg_dev_palette_batch_counts", "kmg_dev_apply_batch_counts", "kmg_dev_compare_batch", "kmg_reduce_quality_batch",
     "kmg_dither_threshold", "kmg_dev_compare", "kmg_compare", "kmg_reduce_quality",
     "kmg_sequence_create", "kmg_sequence_destroy", "kmg_sequence_add", "kmg_sequence_add_device", "kmg_sequence_clear",
     "kmg_sequence_info", "kmg_sequence_centroids", "kmg_sequence_palette", "kmg_dev_frame_delta", "kmg_dev_frame_delta_lossy",
@@ -565,6 +574,15 @@ def lib():
     L.kmg_group_lloyd_run.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.kmg_group_lloyd_member.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int)]
     L.kmg_group_lloyd_member.restype = vp
+    L.kmg_dev_palette_batch_counts.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u32p, f32p, u32p,
+                                               C.POINTER(BatchReport), vp]
+    L.kmg_dev_apply_batch_counts.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), f32p, u32p, C.c_int,
+                                             C.c_int, C.POINTER(vp), C.POINTER(BatchApplyReport), vp]
+    L.kmg_dev_compare_batch.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64), C.c_int, u8p, u32p, C.c_uint32,
+                                        C.c_uint32, vp, vp]
+    L.kmg_reduce_quality_batch.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.POINTER(vp), u32p, C.POINTER(vp), C.POINTER(ErrorStats),
+                                           C.POINTER(C.c_int), C.POINTER(BatchQualityReport)]
     L.kmg_group_lloyd_create_batch.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
     L.kmg_group_lloyd_bind_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_uint32), C.POINTER(vp), C.c_uint32]
@@ -724,6 +742,7 @@ class ImageProcessor:
         _register(self)
         self.alpha_weight = False
         self.last_batch_report = None   # BatchReport of the last palette_batch / reduce_batch / palette_batch_device / reduce_indexed_batch
+        self.last_quality_report = None   # BatchQualityReport of the last reduce_quality_batch
         self.last_batch_apply_report = None   # BatchApplyReport of the last find_batch / reduce_indexed_batch / apply_batch_device
         if fixed_colors is not None:
             self.set_fixed_colors(fixed_colors)
@@ -934,6 +953,82 @@ class ImageProcessor:
                                          C.byref(rep), C.c_void_p(stream)))
         self.last_batch_apply_report = rep
         return rep
+
+    # ---- batched quality targets (include/kmeans_hip.h kmg_batch_quality_report) ----------------
+    def palette_batch_counts_device(self, d_images, widths, heights, ks, stream=0):
+        """kmg_dev_palette_batch_counts: palette_batch_device with a colour count per image -> (list of centroid tables, table i
+        (ks[i], 4) float32 in index order, iterations (n,) uint32).  The report of the call: last_batch_report"""
+        n = len(d_images)
+        src = (C.c_void_p * n)(*[int(d) for d in d_images])
+        ws = (C.c_uint32 * n)(*[int(w) for w in widths])
+        hs = (C.c_uint32 * n)(*[int(h) for h in heights])
+        counts = np.ascontiguousarray(ks, np.uint32).reshape(-1)
+        cent = np.empty((max(int(counts.sum()), 1), 4), np.float32)
+        its = np.zeros(max(n, 1), np.uint32)
+        rep = BatchReport()
+        _check(lib().kmg_dev_palette_batch_counts(self._h, n, src, ws, hs, _np_ptr(counts), _np_ptr(cent), _np_ptr(its), C.byref(rep),
+                                                  C.c_void_p(stream)))
+        self.last_batch_report = rep
+        ends = np.cumsum(counts)
+        return [cent[e - k:e].copy() for e, k in zip(ends, counts)], its[:n]
+
+    def apply_batch_counts_device(self, d_images, widths, heights, tables, reduce_mode, format, d_outs, stream=0):
+        """kmg_dev_apply_batch_counts: apply_batch_device with a table per image of its own size; tables: one (k_i, 4) float32
+        array per image.  Synchronises the stream.  The report of the call: last_batch_apply_report"""
+        n = len(d_images)
+        tabs = [np.ascontiguousarray(t, np.float32).reshape(-1, 4) for t in tables]
+        counts = np.array([t.shape[0] for t in tabs], np.uint32)
+        c4 = np.ascontiguousarray(np.concatenate(tabs) if tabs else np.zeros((1, 4)), np.float32)
+        src = (C.c_void_p * n)(*[int(d) for d in d_images])
+        dst = (C.c_void_p * n)(*[int(d) for d in d_outs])
+        ws = (C.c_uint32 * n)(*[int(w) for w in widths])
+        hs = (C.c_uint32 * n)(*[int(h) for h in heights])
+        rep = BatchApplyReport()
+        _check(lib().kmg_dev_apply_batch_counts(self._h, n, src, ws, hs, _np_ptr(c4), _np_ptr(counts), int(reduce_mode), int(format), dst,
+                                                C.byref(rep), C.c_void_p(stream)))
+        self.last_batch_apply_report = rep
+        return rep
+
+    def compare_batch_device(self, d_srcs, d_outs, n_pixels, format, palettes, alpha_cutoff, what, d_stats, stream=0):
+        """kmg_dev_compare_batch: COMBINES the error record of every image into the n records at d_stats (device memory, 112 bytes
+        each).  palettes: one (k_i, 4) uint8 array per image (index formats), or None.  Enqueues on the stream only."""
+        n = len(d_srcs)
+        src = (C.c_void_p * n)(*[int(d) for d in d_srcs])
+        dst = (C.c_void_p * n)(*[int(d) for d in d_outs])
+        npx = (C.c_uint64 * n)(*[int(v) for v in n_pixels])
+        if palettes is None:
+            pal, counts = None, None
+        else:
+            pals = [np.ascontiguousarray(q, np.uint8).reshape(-1, 4) for q in palettes]
+            counts = np.array([q.shape[0] for q in pals], np.uint32)
+            pal = np.ascontiguousarray(np.concatenate(pals))
+        _check(lib().kmg_dev_compare_batch(self._h, n, src, dst, npx, int(format), None if pal is None else _np_ptr(pal),
+                                           None if counts is None else _np_ptr(counts), int(alpha_cutoff), int(what), C.c_void_p(d_stats),
+                                           C.c_void_p(stream)))
+
+    def reduce_quality_batch(self, images, max_delta_e, k_min=2, k_max=256, reduce_mode=ReduceMode.Replace, indexed=False, format=None,
+                             max_resident_bytes=0):
+        """kmg_reduce_quality_batch: reduce_quality() of many images, every round of their searches one launch chain; returns the
+        list of (k, colors, image or index map, ErrorStats, reached), each what reduce_quality returns for that image.  format:
+        the output format, or None = what reduce_quality chooses (indexed).  The report of the call: last_quality_report"""
+        imgs = [_image(im) for im in images]
+        n = len(imgs)
+        target = min(int(np.floor(4096.0 * float(max_delta_e) * float(max_delta_e))), 0xFFFFFFFF)
+        fmt = OutputFormat(format) if format is not None else (self._index_format(int(k_max)) if indexed else OutputFormat.RGBA8)
+        dtype = np.uint16 if fmt == OutputFormat.Index16 else np.uint8
+        outs = self._batch_outputs(imgs, fmt, dtype, None)
+        pals = [np.empty((max(int(k_max), 1), 4), np.uint8) for _ in imgs]
+        src, ws, hs = self._batch_arrays(imgs)
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        pdst = (C.c_void_p * n)(*[q.ctypes.data for q in pals])
+        counts = np.zeros(max(n, 1), np.uint32)
+        stats = (ErrorStats * max(n, 1))()
+        reached = (C.c_int * max(n, 1))()
+        rep = BatchQualityReport()
+        _check(lib().kmg_reduce_quality_batch(self._h, n, src, ws, hs, int(k_min), int(k_max), target, int(reduce_mode), int(fmt),
+                                              int(max_resident_bytes), pdst, _np_ptr(counts), dst, stats, reached, C.byref(rep)))
+        self.last_quality_report = rep
+        return [(int(counts[i]), pals[i][:int(counts[i])].copy(), outs[i], stats[i], bool(reached[i])) for i in range(n)]
 
     # ---- palette-index output (include/kmeans_hip.h kmg_output_format) ----------------------
     def _index_format(self, k):

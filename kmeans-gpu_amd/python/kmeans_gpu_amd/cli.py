@@ -17,6 +17,7 @@ colours) instead of RGBA.  In alpha mode the pixels below the cutoff take one mo
 per-channel MSE, PSNR, dE76 RMS and max; kmg_compare).  `reduce --max-error DE [--min-colors A]` picks the colour count itself: as
 few colours between A (default 2) and `-c` as keep the dE76 RMS of the palette step's working image at or below DE
 (kmg_reduce_quality, k-means only); the line then also gives the count chosen and whether the target was reached.
+`batch --max-error DE [--min-colors A]` does the same for every input of a batch in one call (kmg_reduce_quality_batch).
 
 `reduce` and `find` with `--indexed` also take `--optimize [usage|luma|keep]` (kmg_index_optimize): the palette loses the entries
 no pixel uses, is ordered by descending use (the default), ascending luma or as it was, the transparent slot of alpha mode comes
@@ -397,6 +398,10 @@ def build_parser():
     b.add_argument("--palette", action="store_true", help="print the palette of every input instead of writing reduced images")
     b.add_argument("--indexed", action="store_true",
                    help="write a palette-mode PNG (an index per pixel) per input instead of RGBA; at most 256 colours, 255 with --alpha-cutoff")
+    b.add_argument("--max-error", type=validate_max_error, default=None, metavar="DE",
+                   help="choose every image's colour count: as few colours (at most -c) as keep the dE76 RMS of its shrunk image at or "
+                        "below DE; k-means only (kmg_reduce_quality_batch)")
+    b.add_argument("--min-colors", type=validate_k, default=None, metavar="A", help="lower bound of --max-error's search (default 2)")
     for s in (p, f, r, q, b):
         s.add_argument("--alpha-cutoff", type=validate_alpha_cutoff, default=0,
                        help="1..255: pixels with a lower alpha do not shape the palette, the output keeps the input's alpha")
@@ -425,9 +430,20 @@ def build_parser():
 
 def run_batch(args, ap):
     """the `batch` sub-command: every input through one kmg_reduce_batch (or, --palette, kmg_palette_batch; --indexed,
-    kmg_reduce_indexed_batch) call"""
+    kmg_reduce_indexed_batch; --max-error, kmg_reduce_quality_batch) call"""
     if args.devices:
         ap.error("`batch` is not supported with --devices")
+    if args.max_error is not None:
+        if args.algo != "kmeans":
+            ap.error("--max-error searches the k-means colour count: -a octree has no such knob")
+        if args.palette:
+            ap.error("--max-error writes images: not with --palette")
+        if args.min_colors is None:
+            args.min_colors = min(2, args.colorcount)
+        if args.min_colors > args.colorcount:
+            ap.error(f"--min-colors {args.min_colors} is above -c {args.colorcount}")
+    elif args.min_colors is not None:
+        ap.error("--min-colors belongs to --max-error")
     if not args.palette and not args.output:
         ap.error("`batch` writes one output per input: it needs -o DIR (or --palette)")
     if args.indexed:
@@ -441,6 +457,21 @@ def run_batch(args, ap):
                      f"{args.colorcount} requested")
     images = [_load(path) for path in args.input]
     with ImageProcessor(alpha_cutoff=args.alpha_cutoff) as proc:
+        if args.max_error is not None:                   # every image's colour count from the quality target; -c is the upper bound
+            os.makedirs(args.output, exist_ok=True)
+            results = proc.reduce_quality_batch(images, args.max_error, args.min_colors, args.colorcount, _MODES[args.mode], indexed=args.indexed)
+            for path, (k, colors, out, _, reached) in zip(args.input, results):
+                name = os.path.basename(reduce_file_path(args.colorcount, args.algo, args.mode, None, path))
+                if args.indexed:
+                    save_indexed(os.path.join(args.output, os.path.splitext(name)[0] + ".png"), colors, out, transparent=bool(args.alpha_cutoff))
+                else:
+                    _save(os.path.join(args.output, name), out)
+                print(f"Quality {path}: {k} colours, target {'reached' if reached else 'not reached'}")
+            qrep = proc.last_quality_report
+            print(f"Batch quality: {len(images)} images, {qrep.rounds} rounds, {qrep.palette_runs} palette runs, {qrep.launches} + "
+                  f"{qrep.measure_launches} launches, output {qrep.batched} batched and {qrep.per_image} per image, {qrep.sub_batches} sub-batches, "
+                  f"{qrep.fallback} on the per-image path")
+            return 0
         if args.palette:
             for path, colors in zip(args.input, proc.palette_batch(args.colorcount, images, _ALGOS[args.algo])):
                 print(f"Palette {path}: " + ",".join(f"#{c[0]:02X}{c[1]:02X}{c[2]:02X}" for c in colors))

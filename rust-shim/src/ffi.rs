@@ -139,6 +139,20 @@ pub struct kmg_batch_apply_report {
     pub sub_batches: u32,
 }
 
+/// `kmg_batch_quality_report` (include/kmeans_hip.h): 32 bytes, what kmg_reduce_quality_batch did.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct kmg_batch_quality_report {
+    pub rounds: u32,
+    pub palette_runs: u32,
+    pub launches: u32,
+    pub measure_launches: u32,
+    pub batched: u32,
+    pub per_image: u32,
+    pub sub_batches: u32,
+    pub fallback: u32,
+}
+
 extern "C" {
     pub fn kmg_last_error() -> *const c_char;
     pub fn kmg_version() -> *const c_char;
@@ -298,6 +312,67 @@ extern "C" {
         out_index: *mut *const (),
         batch_report: *mut kmg_batch_report,
         apply_report: *mut kmg_batch_apply_report,
+    ) -> c_int;
+    // batched quality targets: a colour count per image (`ks`: `n_images` counts; `centroids4` / `palettes_rgba` concatenated in
+    // image order), the batched error record, and kmg_reduce_quality for many small images
+    pub fn kmg_dev_palette_batch_counts(
+        p: *mut kmg_processor,
+        n_images: u32,
+        d_rgba: *mut *const u8,
+        widths: *const u32,
+        heights: *const u32,
+        ks: *const u32,
+        centroids4: *mut f32,
+        iterations: *mut u32,
+        report: *mut kmg_batch_report,
+        stream: *mut (),
+    ) -> c_int;
+    pub fn kmg_dev_apply_batch_counts(
+        p: *mut kmg_processor,
+        n_images: u32,
+        d_rgba: *mut *const u8,
+        widths: *const u32,
+        heights: *const u32,
+        centroids4: *const f32,
+        ks: *const u32,
+        mode: c_int,
+        format: c_int,
+        d_out: *mut *const (),
+        report: *mut kmg_batch_apply_report,
+        stream: *mut (),
+    ) -> c_int;
+    pub fn kmg_dev_compare_batch(
+        p: *mut kmg_processor,
+        n_images: u32,
+        d_src_rgba: *mut *const u8,
+        d_out: *mut *const (),
+        n_pixels: *const u64,
+        format: c_int,
+        palettes_rgba: *const u8,
+        ks: *const u32,
+        alpha_cutoff: u32,
+        what: u32,
+        d_stats: *mut kmg_error_stats,
+        stream: *mut (),
+    ) -> c_int;
+    pub fn kmg_reduce_quality_batch(
+        p: *mut kmg_processor,
+        n_images: u32,
+        rgba: *mut *const u8,
+        widths: *const u32,
+        heights: *const u32,
+        k_min: u32,
+        k_max: u32,
+        target: u32,
+        mode: c_int,
+        format: c_int,
+        max_resident_bytes: u64,
+        out_palette_rgba: *mut *const u8,
+        out_counts: *mut u32,
+        out: *mut *const (),
+        achieved: *mut kmg_error_stats,
+        reached: *mut c_int,
+        report: *mut kmg_batch_quality_report,
     ) -> c_int;
     // error statistics of an output against its source (host buffers; `out` holds 4, 1 or 2 bytes per pixel for `format`) and the
     // colour count chosen by a quality target: no counterpart in the reference

@@ -18,7 +18,13 @@ dither, the same protocol (warm processor, result arrays allocated once, batch a
   pruned  : (dither, k = 256, the images a plan of their own sends to the candidate lists) kmg_dev_apply_batch with the strategy
             "scan" -- they join the launch -- against "table" -- they take their own pass inside the call
   ppt     : (tools build only: KMG_LIBRARY=lib/libkmeans_hip_tools.so) kmg_dev_apply_batch with 4 against 8 pixels per thread
-    python tools/batch_probe.py apply [largest N] > profiles/r10_batch_apply_time.txt"""
+    python tools/batch_probe.py apply [largest N] > profiles/r10_batch_apply_time.txt
+
+`quality`: kmg_reduce_quality_batch against kmg_reduce_quality image after image on the same processor, the same
+protocol; the first 2, 8 and 128 images of the 128-image set (N = 64), dither, INDEX8 / INDEX16 as reduce_quality chooses;
+(k_min, k_max, max dE) = (2, 16, 22.0), (2, 64, 13.0), (2, 256, 8.0) -- targets inside the range of E(k) of these images, so that
+the counts chosen spread over the range; the row gives their spread and how many images reached the target
+    python tools/batch_probe.py quality [most images] [runs] > profiles/r11_batch_quality_time.txt"""
 import os
 import sys
 import time
@@ -31,7 +37,8 @@ import kmeans_gpu_amd as kg
 from PIL import Image
 
 APPLY = len(sys.argv) > 1 and sys.argv[1] == "apply"
-args = sys.argv[2:] if APPLY else sys.argv[1:]
+QUALITY = len(sys.argv) > 1 and sys.argv[1] == "quality"
+args = sys.argv[2:] if APPLY or QUALITY else sys.argv[1:]
 largest = int(args[0]) if args else 256
 NS = [n for n in (1, 2, 4, 8, 16, 64, 256) if n <= largest]
 KS = (8, 64, 256)
@@ -149,8 +156,45 @@ def apply_probe():
     proc.close()
 
 
+def quality_probe():
+    global RUNS
+    most = int(args[0]) if args else 128
+    RUNS = int(args[1]) if len(args) > 1 else RUNS
+    proc = kg.ImageProcessor()
+    full = []
+    for i in range(64):                                              # the 128-image set, tokyo and synthetic images in turn
+        full += [tokyo, synthetic(i)]
+    rows = [f"tokyo.png {tokyo.shape[1]}x{tokyo.shape[0]} and synthetic images of {len(SIZES)} sizes in turn; wall ms, warm, minimum of {RUNS}",
+            "batch = kmg_reduce_quality_batch; sequential = kmg_reduce_quality image after image on the same processor (tools/batch_probe.py quality)",
+            f"{'':8} {'k_min':>5} {'k_max':>5} {'dE':>4} {'images':>6} {'batch':>10} {'sequential':>11} {'batch/seq':>10} {'rounds':>6} {'runs':>5} {'launches':>9} "
+            f"{'k* min/median/max':>18} {'reached':>7}"]
+    for k_min, k_max, de in ((2, 16, 22.0), (2, 64, 13.0), (2, 256, 8.0)):
+        for n in [n for n in (2, 8, 128) if n <= most]:
+            images = full[:n]
+            got, want = [], []
+
+            def batch():
+                got[:] = proc.reduce_quality_batch(images, de, k_min, k_max, kg.ReduceMode.Dither, indexed=True)
+
+            def sequential():
+                want[:] = [proc.reduce_quality(im, de, k_min, k_max, kg.ReduceMode.Dither, indexed=True) for im in images]
+
+            t_b, t_s = best(batch, sequential)
+            assert all(g[0] == w[0] and np.array_equal(g[1], w[1]) and np.array_equal(g[2], w[2]) and g[4] == w[4] for g, w in zip(got, want))
+            rep = proc.last_quality_report
+            stars = sorted(g[0] for g in got)
+            rows.append(f"{'quality':8} {k_min:5d} {k_max:5d} {de:4.1f} {n:6d} {t_b:10.3f} {t_s:11.3f} {t_b / t_s:10.3f} {rep.rounds:6d} {rep.palette_runs:5d} "
+                        f"{rep.launches:9d} {f'{stars[0]}/{stars[len(stars) // 2]}/{stars[-1]}':>18} {sum(1 for g in got if g[4]):7d}")
+            print(rows[-1], file=sys.stderr, flush=True)
+    print("\n".join(rows))
+    proc.close()
+
+
 if APPLY:
     apply_probe()
+    sys.exit(0)
+if QUALITY:
+    quality_probe()
     sys.exit(0)
 
 proc = kg.ImageProcessor()
