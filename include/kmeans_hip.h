@@ -892,6 +892,39 @@ KMG_API int kmg_dev_frame_delta_lossy(kmg_processor *p, const uint8_t *d_src_rgb
                                       uint8_t *d_held_rgba, uint32_t width, uint32_t rows, uint32_t row0, int format, uint32_t k,
                                       uint32_t tolerance, void *d_delta, kmg_frame_hold *d_info, void *stream);
 
+/* All frames of a clip through the delta pass in one launch chain.  The outputs, the records, the canvas and the held source are
+ * exactly what n_frames calls of kmg_dev_frame_delta (tolerances == NULL) or of kmg_dev_frame_delta_lossy (frame t at
+ * tolerances[t]) leave, in order, each on the whole frame with row0 = 0 -- but a lane keeps its pixels' canvas index and held
+ * source in registers across the frames, so that state crosses the memory bus once per KMG_CLIP_FRAMES frames instead of once
+ * per frame (a longer clip runs as several launches over the same pixels).
+ *   d_src_rgba, d_index, d_out: HOST arrays of n_frames DEVICE pointers: the frames' sources (NULL when tolerances == NULL), their
+ *   maps I_t, and where delta map t goes.  d_canvas, d_held_rgba: as for the two passes; d_held_rgba may be NULL when tolerances ==
+ *   NULL.  An exact clip writes only the first 32 bytes of each record and updates the held source only when d_held_rgba and the
+ *   sources are both given: it then is the last frame.  tolerances: HOST, n_frames words.  d_info: DEVICE, n_frames records of 48
+ *   bytes, combined into as they stand.  The table of pointers goes to the device in one stream-ordered copy; the arrays may change
+ *   as soon as the call returns.
+ *   KMG_CLIP_FULL_ON_CLEAR: a frame whose own record has cleared > 0 follows the rule of kmg_sequence_output_frame_lossy: d_out[t]
+ *   = I_t, d_full[t] = 1 (every other word of d_full: 0), and after it the canvas equals I_t and the held source the frame at every
+ *   pixel; the record stays as measured; every later frame sees that state.  Which frames those are follows from the maps alone:
+ *   after any frame the canvas shows slot k exactly where that frame's map does, so frame t >= 1 clears a pixel exactly when some
+ *   pixel has I_t == k and I_{t-1} != k (frame 0: the canvas in place of I_{t-1}).  d_full: DEVICE, n_frames words, 4-byte aligned;
+ *   may be NULL without the flag, and is not touched then.
+ * Pointer rules: those of the two passes, frame by frame, and across the frames: a lane has the next frame's source and map in
+ * flight while it stores this frame's delta map, so no buffer that is written (any d_out[t], the canvas, the held source, the
+ * records, d_full) may overlap any other buffer of any frame; the sources and maps, which are only read, may overlap each other
+ * (the same map may serve two frames).  As in the two passes, no overlap is checked.  No alignment beyond the element's (RGBA8: 4 bytes) is required -- each
+ * buffer whose pointer does not allow the vector access goes element by element.  Indices above k are compared like any other.
+ * Refusals, in this order: those of kmg_dev_frame_delta_lossy (RGBA8, format, k, a NULL pointer -- the arrays, the canvas, the
+ * records, and for a lossy clip the held source --, the size, a misaligned canvas, held source or record); n_frames == 0; a NULL
+ * or misaligned entry of an array; unknown flags; KMG_CLIP_FULL_ON_CLEAR without d_full.  Only enqueues work on `stream`.        */
+#define KMG_CLIP_FULL_ON_CLEAR 1u
+#define KMG_CLIP_FRAMES 32u            /* frames one launch of the walk takes */
+#define KMG_CLIP_MIN_FRAMES 8u         /* the shortest clip kmg_sequence_output_frames sends through the launch chain */
+KMG_API int kmg_dev_frame_delta_clip(kmg_processor *p, uint32_t n_frames, const uint8_t *const *d_src_rgba, const void *const *d_index,
+                                     void *d_canvas, uint8_t *d_held_rgba, uint32_t width, uint32_t height, int format, uint32_t k,
+                                     const uint32_t *tolerances, uint32_t flags, void *const *d_out, kmg_frame_hold *d_info,
+                                     uint32_t *d_full, void *stream);
+
 /* Frame output with the sequence's palette, on HOST buffers.
  *   _output_begin   the centroids of W at k (as _centroids); out_palette_rgba (k x 4 bytes) / *out_count: the palette in index
  *                   order, exactly as kmg_reduce_indexed returns it; one apply plan (kmg_apply_plan_create_format with
@@ -923,6 +956,33 @@ KMG_API int kmg_sequence_output_frame(kmg_sequence *s, const uint8_t *rgba, uint
 KMG_API int kmg_sequence_output_frame_lossy(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, uint32_t tolerance, void *out,
                                             kmg_frame_hold *info, int *is_full);
 KMG_API int kmg_sequence_output_end(kmg_sequence *s);
+
+/* A whole clip through the open output: out[t], info[t] and is_full[t] are exactly what frame t gets from _output_frame (tolerances
+ * == NULL) or _output_frame_lossy (at tolerances[t]) called one after another, and the output is left in the same state (canvas
+ * and held source), so clips and single frames alternate freely.  The frames are staged in one block, their maps come from the
+ * batched output launch where they can join it (kmg_dev_apply_batch's rule, with the plan's alpha cutoff) and from a pass of their
+ * own otherwise (every diffuse frame), the delta maps from kmg_dev_frame_delta_clip, the records come back in one copy.  Without
+ * KMG_FRAME_DELTA (every RGBA8 clip) the call writes the full maps; the canvas becomes the last map, the held source the last
+ * frame; info and is_full are optional.  info: n_frames records of kmg_frame_hold -- an exact clip leaves held = held_sse = 0.
+ * max_resident_bytes: the clip is cut (kmg_reduce_batch's rule) over the 4 + 2e bytes per pixel a frame keeps on the device, e the
+ * bytes of an index; 0 = no bound of the caller's.  A clip of fewer than KMG_CLIP_MIN_FRAMES frames -- where the chain was measured
+ * not to pay: profiles/r12_clip_time.txt, two frames of 256 x 256 take up to 1.63 of the per-frame calls, eight at most 0.80 -- is that
+ * many _output_frame calls: nothing is staged, max_resident_bytes has nothing to cut, and the report says launches = batched = 0,
+ * per_image = n_frames, sub_clips = 1.  report: optional.
+ * Refusals, in this order, for the whole clip before anything is uploaded: those of _output_frame / _output_frame_lossy (no
+ * sequence, a local output, no open output, a NULL rgba or out array, unknown flags, a lossy clip without KMG_FRAME_DELTA,
+ * KMG_FRAME_DELTA with RGBA8 or without info / is_full), n_frames == 0, a NULL entry.  A refused call leaves the output untouched.
+ * Any later failure, on the chain or in one of a short clip's frames, ENDS the open output, as a second _begin does: no half-updated
+ * canvas can be used.                          */
+typedef struct kmg_clip_report {   /* 16 bytes, no padding */
+    uint32_t launches;    /* launches of the batched output kernel and of the two clip kernels */
+    uint32_t batched;     /* frames whose map came from the batched output launch              */
+    uint32_t per_image;   /* frames whose map took its own output pass                         */
+    uint32_t sub_clips;   /* pieces max_resident_bytes cut the clip into                       */
+} kmg_clip_report;
+KMG_API int kmg_sequence_output_frames(kmg_sequence *s, uint32_t n_frames, const uint8_t *const *rgba, uint32_t flags,
+                                       const uint32_t *tolerances, uint64_t max_resident_bytes, void *const *out, kmg_frame_hold *info,
+                                       int *is_full, kmg_clip_report *report);
 
 /* ======================= per-frame palettes: colour-keyed delta frames =====================
  * One palette for all frames is what limits a 256-entry format on a clip whose content changes (a cut, a pan, a fade); GIF has

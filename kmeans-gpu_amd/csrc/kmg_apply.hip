@@ -370,6 +370,8 @@ void kmg::apply_plan_restart(kmg_apply_plan *pl)
     if (pl) pl->drows = 0;
 }
 
+uint32_t kmg::apply_plan_cutoff(const kmg_apply_plan *pl) { return pl->alpha_cutoff; }
+
 // kmg_dev_apply and kmg_apply_plan_status: did any diffusion run of the plan time out?  (Read after the last run has completed.)
 static int diffuse_status(kmg_apply_plan *pl)
 {

@@ -140,6 +140,13 @@ int check_index_band(const char *name, bool lossy, const kmg_processor *p, const
 int frame_hold_impl(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_index, void *d_canvas, uint8_t *d_held_rgba, uint32_t width,
                     uint32_t rows, uint32_t row0, int format, uint32_t k, uint32_t tolerance, void *d_delta, kmg_frame_hold *d_info,
                     hipStream_t st);
+// kmg_dev_frame_delta_clip on a hipStream_t (kmg_clip.hip): every frame of a clip through the delta passes in one launch chain.
+// launches (may be NULL): ADDS the launches of the two clip kernels.  Only enqueues.
+int frame_clip_impl(kmg_processor *p, uint32_t n_frames, const uint8_t *const *d_src_rgba, const void *const *d_index, void *d_canvas,
+                    uint8_t *d_held_rgba, uint32_t width, uint32_t height, int format, uint32_t k, const uint32_t *tolerances, uint32_t flags,
+                    void *const *d_out, kmg_frame_hold *d_info, uint32_t *d_full, uint32_t *launches, hipStream_t st);
+// the alpha cutoff a plan was made with (kmg_apply.hip)
+uint32_t apply_plan_cutoff(const kmg_apply_plan *plan);
 
 // kmg_dev_frame_delta_colour / _colour_lossy on a hipStream_t (kmg_local.hip): the frames of an output with per-frame palettes.
 // lossy: d_src_rgba, d_held_rgba and a hold record; exact: both NULL and a delta record

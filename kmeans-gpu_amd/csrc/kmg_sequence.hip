@@ -12,11 +12,13 @@
 //                    the tile's (columns, rows) step.  Six u32 fields are reduced as kmg_pass.h says.
 //   kmg_sequence     host object: the working sequence W (one device block, grown geometrically), the palette step on it, and
 //                    the frame output -- one apply plan, the frame buffers, the canvas and its held source (lossy frames:
-//                    kmg_hold.hip) in one block.
+//                    kmg_hold.hip) in one block.  kmg_sequence_output_frames takes a whole clip: the maps of its frames from the
+//                    batched output launch (kmg_batch_apply.hip), the delta maps from one launch chain (kmg_clip.hip).
 
 #include <initializer_list>
 #include <utility>
 
+#include "kmg_batch_layout.h"
 #include "kmg_pass.h"
 #include "kmg_state.h"
 
@@ -255,6 +257,7 @@ struct kmg_sequence {
     uint32_t local_flags = 0;
     uint8_t *d_shown = nullptr, *d_pal = nullptr;
     std::vector<float> prev_c4;      // C_{t-1}: where a warm frame's Lloyd loop starts
+    std::vector<float> c4;           // the open output's centroids (shared palette): what a clip's batched output launch takes
 };
 
 namespace {
@@ -511,6 +514,7 @@ try {
     if (format == KMG_FORMAT_INDEX8) e = hipMemsetD8Async((hipDeviceptr_t)s->d_canvas, (unsigned char)k, n, st);
     else if (format == KMG_FORMAT_INDEX16) e = hipMemsetD16Async((hipDeviceptr_t)s->d_canvas, (unsigned short)k, n, st);
     KMG_TRY(output_opened(s, e, k, mode, format, width, height));
+    s->c4.assign(c4.begin(), c4.begin() + 4 * (size_t)k);
     for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], out_palette_rgba + 4 * i);
     *out_count = k;
     return KMG_OK;
@@ -587,7 +591,122 @@ int output_frame(kmg_sequence *s, const uint8_t *rgba, bool delta, const uint32_
     return KMG_OK;
 }
 
+// The smallest clip that takes the launch chain: staging, the table and the extra synchronisation of the batched output cost about
+// three single-frame calls of 256 x 256 pixels; measured (profiles/r12_clip_time.txt), two frames are up to 1.63 of
+// the per-frame path, eight at most 0.80.  Shorter clips go frame by frame through output_frame.
+constexpr uint32_t kClipMinFrames = KMG_CLIP_MIN_FRAMES;
+
+// A clip of kClipMinFrames frames or more through the open output (the caller has checked its arguments and ends the output when this fails):
+// per sub-clip the frames in one stream-ordered block, their maps from apply_batch, the delta maps and records from
+// frame_clip_impl, one read-back of the records, the downloads.
+int output_clip(kmg_sequence *s, uint32_t n_frames, const uint8_t *const *rgba, bool delta, const uint32_t *tolerances, uint64_t max_resident_bytes,
+                void *const *out, kmg_frame_hold *info, int *is_full, kmg_clip_report *rep)
+{
+    kmg_processor *p = s->p;
+    hipStream_t st = s->sg.st;
+    const bool lossy = tolerances != nullptr;
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t n = (size_t)s->width * s->height, map_bytes = n * format_bytes(s->format);
+    const uint32_t cutoff = apply_plan_cutoff(s->plan);                // (the plan's, not the processor's current one)
+    // a frame keeps its source, its map and its delta map on the device
+    const std::vector<uint64_t> bytes(n_frames, (uint64_t)n * 4 + 2 * (uint64_t)map_bytes);
+    const std::vector<uint32_t> cuts = batch_cuts(bytes.data(), n_frames, max_resident_bytes);
+    rep->sub_clips = (uint32_t)cuts.size() - 1u;
+    const size_t fs = pad256(n * 4), ms = pad256(map_bytes);
+    for (size_t c = 0; c + 1 < cuts.size(); ++c) {
+        const uint32_t a = cuts[c], m = cuts[c + 1] - a;
+        // the block: m frames | m maps | m delta maps | m records | m words
+        const size_t rec_at = (size_t)m * (fs + 2 * ms), full_at = rec_at + pad256(sizeof(kmg_frame_hold) * (size_t)m);
+        StreamBuf blk;
+        HIP_TRY(blk.alloc(p, full_at + pad256(sizeof(uint32_t) * (size_t)m), st));
+        uint8_t *base = (uint8_t *)blk.ptr;
+        std::vector<const uint8_t *> src(m);
+        std::vector<void *> maps(m), outs(m);
+        const std::vector<uint32_t> widths(m, s->width), heights(m, s->height);
+        for (uint32_t t = 0; t < m; ++t) {
+            src[t] = base + (size_t)t * fs;
+            maps[t] = base + (size_t)m * fs + (size_t)t * ms;
+            outs[t] = base + (size_t)m * (fs + ms) + (size_t)t * ms;
+            HIP_TRY_DRAIN(st, copy_host_image(p, const_cast<uint8_t *>(src[t]), rgba[a + t], n * 4, hipMemcpyHostToDevice, st));
+        }
+        kmg_batch_apply_report arep = {0u, 0u, 0u, 0u};
+        KMG_TRY_DRAIN(st, apply_batch(p, m, src.data(), widths.data(), heights.data(), s->c4.data(), 1u, s->k, s->mode, s->format, cutoff,
+                                      maps.data(), &arep, st));
+        rep->launches += arep.launches;
+        rep->batched += arep.batched;
+        rep->per_image += arep.per_image;
+        if (!delta) {
+            for (uint32_t t = 0; t < m; ++t) {
+                HIP_TRY_DRAIN(st, copy_host_image(p, out[a + t], maps[t], map_bytes, hipMemcpyDeviceToHost, st));
+                if (info) info[a + t] = kmg_frame_hold{0, 0, kFresh, kFresh, 0, 0, 0, 0};
+                if (is_full) is_full[a + t] = 1;
+            }
+            // index formats: a later delta frame starts from the last map, with the last frame as every pixel's held source
+            if (s->d_canvas && a + m == n_frames) {
+                HIP_TRY_DRAIN(st, hipMemcpyAsync(s->d_canvas, maps[m - 1], map_bytes, hipMemcpyDeviceToDevice, st));
+                HIP_TRY_DRAIN(st, hipMemcpyAsync(s->d_held, src[m - 1], n * 4, hipMemcpyDeviceToDevice, st));
+            }
+            HIP_TRY(hipStreamSynchronize(st));
+            continue;
+        }
+        kmg_frame_hold *d_info = (kmg_frame_hold *)(base + rec_at);
+        uint32_t *d_full = (uint32_t *)(base + full_at);
+        // the fresh records: zero sums and maxima, all-ones minima
+        HIP_TRY_DRAIN(st, hipMemsetAsync(d_info, 0, sizeof(kmg_frame_hold) * (size_t)m, st));
+        HIP_TRY_DRAIN(st, hipMemset2DAsync(&d_info->x0, sizeof(kmg_frame_hold), 0xFF, 2 * sizeof(uint32_t), m, st));
+        // with cutoff 0 no map holds slot k: no frame is full.  An exact clip needs no flags either: its canvas is I_t in both cases.
+        const uint32_t clip_flags = lossy && cutoff ? KMG_CLIP_FULL_ON_CLEAR : 0u;
+        KMG_TRY_DRAIN(st, frame_clip_impl(p, m, src.data(), maps.data(), s->d_canvas, s->d_held, s->width, s->height, s->format, s->k,
+                                          lossy ? tolerances + a : nullptr, clip_flags, outs.data(), d_info, d_full, &rep->launches, st));
+        HIP_TRY_DRAIN(st, hipMemcpyAsync(info + a, d_info, sizeof(kmg_frame_hold) * (size_t)m, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t t = 0; t < m; ++t) {
+            const bool full = info[a + t].cleared > 0;                 // "over" cannot show a pixel that turns transparent
+            // (a lossy frame that is full has its map in the out block already)
+            HIP_TRY_DRAIN(st, copy_host_image(p, out[a + t], !lossy && full ? maps[t] : outs[t], map_bytes, hipMemcpyDeviceToHost, st));
+            is_full[a + t] = full ? 1 : 0;
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return KMG_OK;
+}
+
 }  // namespace
+
+extern "C" int kmg_sequence_output_frames(kmg_sequence *s, uint32_t n_frames, const uint8_t *const *rgba, uint32_t flags,
+                                          const uint32_t *tolerances, uint64_t max_resident_bytes, void *const *out, kmg_frame_hold *info,
+                                          int *is_full, kmg_clip_report *report)
+try {
+    const bool lossy = tolerances != nullptr, delta = (flags & KMG_FRAME_DELTA) != 0;
+    KMG_TRY(check_shared_frame(s, lossy, rgba, flags, out, info, is_full));
+    if (n_frames == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frames: the clip has no frames");
+    for (uint32_t t = 0; t < n_frames; ++t)
+        if (!rgba[t] || !out[t]) return fail(KMG_ERR_INVALID_ARGUMENT, "sequence_output_frames: a pointer of frame %u is NULL", t);
+    kmg_clip_report rep = {0u, 0u, 0u, 1u};
+    if (n_frames < kClipMinFrames) {                                   // a short clip: the single-frame call itself, frame by frame
+        for (uint32_t t = 0; t < n_frames; ++t) {
+            kmg_frame_hold rec;
+            bool full;
+            const int rc = output_frame(s, rgba[t], delta, lossy ? tolerances + t : nullptr, out[t], &rec, &full);
+            if (rc != KMG_OK) {
+                output_end(s);                                         // (as the chain below: no clip is left half done on an open output)
+                return rc;
+            }
+            if (info) info[t] = rec;
+            if (is_full) is_full[t] = full ? 1 : 0;
+        }
+        rep.per_image = n_frames;
+    } else {
+        const int rc = output_clip(s, n_frames, rgba, delta, tolerances, max_resident_bytes, out, info, is_full, &rep);
+        if (rc != KMG_OK) {
+            output_end(s);                                             // no half-updated canvas can be used
+            return rc;
+        }
+    }
+    if (report) *report = rep;
+    return KMG_OK;
+}
+KMG_ABI_CATCH
 
 extern "C" int kmg_sequence_output_frame(kmg_sequence *s, const uint8_t *rgba, uint32_t flags, void *out, kmg_frame_delta *info,
                                          int *is_full)

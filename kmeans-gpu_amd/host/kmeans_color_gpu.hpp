@@ -518,6 +518,38 @@ public:
         f.is_full = full != 0;
         return f;
     }
+    // A whole clip in one launch chain (kmg_sequence_output_frames): frame by frame what frame() (max_delta_e empty) or frame_lossy()
+    // (one tolerance for all frames, or one per frame) return for the images one after another, and the same state afterwards.
+    std::vector<Frame> frames(const std::vector<Image> &images, bool delta = true, const std::vector<double> &max_delta_e = {},
+                              uint64_t max_resident_bytes = 0, kmg_clip_report *report = nullptr)
+    {
+        const size_t n = images.size();
+        if (!max_delta_e.empty() && max_delta_e.size() != 1 && max_delta_e.size() != n)
+            throw Error(KMG_ERR_INVALID_ARGUMENT, "frames: one tolerance, or one per frame");
+        std::vector<uint32_t> tol;
+        for (size_t t = 0; !max_delta_e.empty() && t < n; ++t) {
+            const double e = max_delta_e[max_delta_e.size() == 1 ? 0 : t], q = std::nearbyint(4096.0 * e * e);
+            if (!(e >= 0.0) || q > 4294967295.0) throw Error(KMG_ERR_INVALID_ARGUMENT, "frames: the tolerance does not fit 32 bits");
+            tol.push_back((uint32_t)q);
+        }
+        std::vector<Frame> out;
+        std::vector<const uint8_t *> src;
+        std::vector<void *> dst;
+        for (const Image &image : images) {
+            out.push_back(start(image));
+            src.push_back(reinterpret_cast<const uint8_t *>(image.rgba.data()));
+        }
+        for (Frame &f : out) dst.push_back(f.map.data());
+        std::vector<kmg_frame_hold> info(n ? n : 1, kmg_frame_hold{0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0});
+        std::vector<int> full(n ? n : 1, 1);
+        check(kmg_sequence_output_frames(s_, (uint32_t)n, src.data(), delta ? KMG_FRAME_DELTA : 0u, max_delta_e.empty() ? nullptr : tol.data(),
+                                         max_resident_bytes, dst.data(), info.data(), full.data(), report));
+        for (size_t t = 0; t < n; ++t) {
+            out[t].info = info[t];
+            out[t].is_full = full[t] != 0;
+        }
+        return out;
+    }
     // Per-frame palettes (kmg_sequence_output_begin_local): no frame needs to be added.  warm: the k-means of every frame after the
     // first starts from the previous frame's centroids.  frame_local: the frame's own palette in index order and its map -- a delta
     // map against what is shown (exact, or lossy within max_delta_e when that is >= 0), or the full map.

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "BatchReport", "BatchApplyReport", "BatchQualityReport", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "BatchReport", "BatchApplyReport", "BatchQualityReport", "ClipReport", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "CLIP_FULL_ON_CLEAR", "CLIP_FRAMES", "CLIP_MIN_FRAMES", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -122,6 +122,9 @@ class ErrorStats(C.Structure):          # include/kmeans_hip.h kmg_error_stats: 
 
 FRAME_DELTA = 1                         # include/kmeans_hip.h KMG_FRAME_DELTA
 LOCAL_WARM = 1                          # include/kmeans_hip.h KMG_LOCAL_WARM
+CLIP_FULL_ON_CLEAR = 1                  # include/kmeans_hip.h KMG_CLIP_FULL_ON_CLEAR
+CLIP_FRAMES = 32                        # include/kmeans_hip.h KMG_CLIP_FRAMES: frames one launch of the clip walk takes
+CLIP_MIN_FRAMES = 8                     # include/kmeans_hip.h KMG_CLIP_MIN_FRAMES: the shortest clip Sequence.frames sends through the chain
 
 
 class FrameDelta(C.Structure):          # include/kmeans_hip.h kmg_frame_delta: 32 bytes
@@ -223,6 +226,17 @@ class BatchApplyReport(C.Structure):    # include/kmeans_hip.h kmg_batch_apply_r
     def __repr__(self):
         return (f"BatchApplyReport(launches={self.launches}, batched={self.batched}, per_image={self.per_image}, "
                 f"sub_batches={self.sub_batches})")
+
+
+class ClipReport(C.Structure):          # include/kmeans_hip.h kmg_clip_report: 16 bytes
+    _fields_ = [("launches", C.c_uint32), ("batched", C.c_uint32), ("per_image", C.c_uint32), ("sub_clips", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.launches, self.batched, self.per_image, self.sub_clips)
+
+    def __repr__(self):
+        return (f"ClipReport(launches={self.launches}, batched={self.batched}, per_image={self.per_image}, "
+                f"sub_clips={self.sub_clips})")
 
 
 class IndexPlanInfo(C.Structure):       # include/kmeans_hip.h kmg_index_plan_info: 16 bytes
@@ -384,6 +398,7 @@ SYMBOLS = [
     "kmg_sequence_create", "kmg_sequence_destroy", "kmg_sequence_add", "kmg_sequence_add_device", "kmg_sequence_clear",
     "kmg_sequence_info", "kmg_sequence_centroids", "kmg_sequence_palette", "kmg_dev_frame_delta", "kmg_dev_frame_delta_lossy",
     "kmg_sequence_output_begin", "kmg_sequence_output_frame", "kmg_sequence_output_frame_lossy", "kmg_sequence_output_end",
+    "kmg_dev_frame_delta_clip", "kmg_sequence_output_frames",
     "kmg_dev_frame_delta_colour", "kmg_dev_frame_delta_colour_lossy", "kmg_sequence_output_begin_local", "kmg_sequence_output_frame_local",
     "kmg_dev_index_usage", "kmg_index_plan", "kmg_dev_index_remap", "kmg_index_usage", "kmg_index_remap", "kmg_index_optimize",
     "kmg_default_group_options", "kmg_group_create", "kmg_group_unique_id", "kmg_group_create_rank", "kmg_group_destroy",
@@ -519,6 +534,10 @@ def lib():
     L.kmg_dev_frame_delta_lossy.argtypes = [vp, u8p, vp, vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.kmg_sequence_output_frame_lossy.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, vp, C.POINTER(FrameHold), C.POINTER(C.c_int)]
     L.kmg_sequence_output_end.argtypes = [vp]
+    L.kmg_dev_frame_delta_clip.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(vp), vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                           C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(vp), vp, vp, vp]
+    L.kmg_sequence_output_frames.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(vp),
+                                             C.POINTER(FrameHold), C.POINTER(C.c_int), C.POINTER(ClipReport)]
     L.kmg_dev_frame_delta_colour.argtypes = [vp, vp, u8p, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp]
     L.kmg_dev_frame_delta_colour_lossy.argtypes = [vp, u8p, vp, u8p, u8p, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
                                                    vp, vp, vp]
@@ -1233,6 +1252,19 @@ class ImageProcessor:
                                                C.c_void_p(d_held_rgba), int(width), int(rows), int(row0), int(format), int(k), int(tolerance),
                                                C.c_void_p(d_delta), C.c_void_p(d_info), C.c_void_p(stream)))
 
+    def frame_delta_clip(self, d_src_rgba, d_index, d_canvas, d_held_rgba, width, height, format, k, tolerances, d_out, d_info,
+                         d_full=0, flags=0, stream=0):
+        """kmg_dev_frame_delta_clip: every frame of a clip through the delta pass in one launch chain -- what len(d_index) calls of
+        frame_delta (tolerances=None) or frame_delta_lossy (frame t at tolerances[t]) leave.  d_src_rgba (None for an exact clip),
+        d_index, d_out: sequences of device pointers, one per frame; d_info: device, 48 bytes per frame, combined into; flags:
+        CLIP_FULL_ON_CLEAR with d_full (device, a word per frame).  Only enqueues."""
+        n = len(d_index)
+        ptrs = lambda a: None if a is None else (C.c_void_p * max(len(a), 1))(*[int(v) if v else None for v in a])
+        tol = None if tolerances is None else (C.c_uint32 * max(n, 1))(*[int(t) for t in tolerances])
+        _check(lib().kmg_dev_frame_delta_clip(self._h, n, ptrs(d_src_rgba), ptrs(d_index), C.c_void_p(d_canvas), C.c_void_p(d_held_rgba),
+                                              int(width), int(height), int(format), int(k), tol, int(flags), ptrs(d_out), C.c_void_p(d_info),
+                                              C.c_void_p(d_full), C.c_void_p(stream)))
+
     def frame_delta_colour(self, d_index, d_palette_rgba, d_shown_rgba, width, rows, row0, format, k, d_delta, d_info, stream=0):
         """kmg_dev_frame_delta_colour: the delta pass for frames with a palette of their own -- the canvas d_shown_rgba holds the RGBA8
         word each pixel shows (0: nothing), a pixel is sent when palette[index] differs from it.  COMBINES into the 32-byte record at
@@ -1299,6 +1331,7 @@ class Sequence:
         self._p = processor
         self._h = C.c_void_p()
         self._out = None                # (k, format, width, height) of the open output
+        self.last_clip_report = None    # ClipReport of the last frames() call
         _check(lib().kmg_sequence_create(processor.handle, C.byref(self._h)))
 
     def close(self):
@@ -1388,6 +1421,39 @@ class Sequence:
         _check(lib().kmg_sequence_output_frame(self._h, _np_ptr(img), FRAME_DELTA if delta else 0, out.ctypes.data_as(C.c_void_p),
                                                C.byref(info), C.byref(full)))
         return out, info, bool(full.value)
+
+    def frames(self, images, delta=True, tolerance=None, max_resident_bytes=0):
+        """kmg_sequence_output_frames: a whole clip through the open output in one launch chain -- a list of (map, FrameDelta |
+        FrameHold, is_full), frame by frame what frame() returns for the images one after another, and the same state afterwards.
+        tolerance: None (exact), one integer for every frame, or one per frame.  Sets last_clip_report."""
+        if self._out is None:
+            raise KmgError(-1, "no output is open (Sequence.output)")
+        k, fmt, w, h = self._out
+        imgs = [_image(im) for im in images]
+        for img in imgs:
+            if img.shape[:2] != (h, w):
+                raise KmgError(-1, f"a frame is {img.shape[1]} x {img.shape[0]}, the output was opened for {w} x {h}")
+        n = len(imgs)
+        if fmt == OutputFormat.RGBA8:
+            outs = [np.empty((h, w, 4), np.uint8) for _ in imgs]
+        else:
+            outs = [np.empty((h, w), np.uint8 if fmt == OutputFormat.Index8 else np.uint16) for _ in imgs]
+        tol = None
+        if tolerance is not None:
+            tols = [int(t) for t in tolerance] if hasattr(tolerance, "__len__") else [int(tolerance)] * n
+            if len(tols) != n or any(t < 0 or t > 0xFFFFFFFF for t in tols):
+                raise KmgError(-1, f"tolerance {tolerance!r}: one uint32, or one per frame")
+            tol = (C.c_uint32 * max(n, 1))(*tols)
+        src = (C.c_void_p * max(n, 1))(*[im.ctypes.data for im in imgs])
+        dst = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        info = (FrameHold * max(n, 1))(*[FrameHold(*FrameHold.FRESH) for _ in range(max(n, 1))])
+        full = (C.c_int * max(n, 1))(*([1] * max(n, 1)))
+        report = ClipReport()
+        _check(lib().kmg_sequence_output_frames(self._h, n, src, FRAME_DELTA if delta else 0, tol, int(max_resident_bytes), dst, info, full,
+                                                C.byref(report)))
+        self.last_clip_report = report
+        rec = (lambda r: FrameHold.from_buffer_copy(bytes(r))) if tol is not None else (lambda r: FrameDelta.from_buffer_copy(bytes(r)[:32]))
+        return [(outs[t], rec(info[t]), bool(full[t])) for t in range(n)]
 
     def output_local(self, k, mode=ReduceMode.Replace, format=OutputFormat.Index8, width=0, height=0, warm=False):
         """kmg_sequence_output_begin_local: opens a frame output in which every frame gets a palette of its own (no frame needs to

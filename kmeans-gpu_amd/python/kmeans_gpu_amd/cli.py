@@ -260,8 +260,8 @@ def run_sequence(args, ap):
             seq.add(f)
         colors = seq.output(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h)
         coded, n_full, n_changed, n_held, lines = [], 0, 0, 0, []
-        for i, f in enumerate(frames):
-            index, info, is_full = seq.frame(f, delta=not args.no_delta, tolerance=args.lossy)
+        # the whole clip in one launch chain (Sequence.frames): frame by frame what Sequence.frame returns
+        for i, (index, info, is_full) in enumerate(seq.frames(frames, delta=not args.no_delta, tolerance=args.lossy)):
             coded.append((index, info.rect, is_full))
             n_full += 1 if is_full else 0
             n_changed += int(info.changed)
