@@ -73,6 +73,36 @@ typedef enum kmg_reduce_mode {
     KMG_MODE_DIFFUSE = 3
 } kmg_reduce_mode;
 
+/* The filter of KMG_MODE_DIFFUSE (kmg_processor_set_diffusion; the other modes ignore it).  A filter is a divisor D and weights
+ * W[dy][dx]: W[dy][dx] / D is the share of pixel (x, y)'s error that goes to (x + dx, y + dy).  Row 0 has dx = +1, +2, rows 1 and
+ * 2 have dx = -2 .. +2; absent entries are 0.  The contract is the one above with its first two lines generalised:
+ *   S   = sum over dy, dx of W[dy][dx] e(x - dx, y - dy)                 (a neighbour outside the image contributes 0)
+ *   v   = 16 src(x, y) + floor((S + D/2) / D)                            (mathematical floor, S may be negative; every D is even)
+ *   t, c, lbl, o, out, e: as above                                       (|e| <= 4080, |S| <= 4080 D <= 195 840: int32)
+ * For D = 16 the v line is (S + 8) >> 4: filter 0 is the contract above word for word.  Alpha mode, the index formats, the bands
+ * of a plan and kmg_dev_apply on a band behave as for Floyd-Steinberg.
+ *                                    D    row 0 (dx +1, +2)   row 1 (dx -2 .. +2)   row 2 (dx -2 .. +2)
+ *   KMG_DIFFUSION_FLOYD_STEINBERG   16    7, 0                0, 3, 5, 1, 0         -
+ *   KMG_DIFFUSION_SIERRA_LITE        4    2, 0                0, 1, 1, 0, 0         -
+ *   KMG_DIFFUSION_ATKINSON           8    1, 1                0, 1, 1, 1, 0         0, 0, 1, 0, 0     (passes on 6/8 of the error)
+ *   KMG_DIFFUSION_BURKES            32    8, 4                2, 4, 8, 4, 2         -
+ *   KMG_DIFFUSION_SIERRA2           16    4, 3                1, 2, 3, 2, 1         -
+ *   KMG_DIFFUSION_SIERRA3           32    5, 3                2, 4, 5, 4, 2         0, 2, 3, 2, 0
+ *   KMG_DIFFUSION_JARVIS            48    7, 5                3, 5, 7, 5, 3         1, 3, 5, 3, 1
+ *   KMG_DIFFUSION_STUCKI            42    8, 4                2, 4, 8, 4, 2         1, 2, 4, 2, 1
+ * kmg_diffusion_weights returns this table. */
+typedef enum kmg_diffusion {
+    KMG_DIFFUSION_FLOYD_STEINBERG = 0,
+    KMG_DIFFUSION_SIERRA_LITE = 1,
+    KMG_DIFFUSION_ATKINSON = 2,
+    KMG_DIFFUSION_BURKES = 3,
+    KMG_DIFFUSION_SIERRA2 = 4,
+    KMG_DIFFUSION_SIERRA3 = 5,
+    KMG_DIFFUSION_JARVIS = 6,
+    KMG_DIFFUSION_STUCKI = 7,
+    KMG_DIFFUSION_COUNT = 8
+} kmg_diffusion;
+
 /* Output format of the output passes (kmg_apply_plan_create_format, kmg_dev_apply_format, kmg_find_indexed, kmg_reduce_indexed).
  * KMG_FORMAT_RGBA8 is the RGBA8 image every other call writes: the same bytes.  The index formats write one uint8_t / uint16_t
  * per pixel, tightly packed, row-major: the label i the mode picks for the pixel -- the very label whose palette bytes the RGBA8
@@ -227,6 +257,14 @@ KMG_API int kmg_processor_set_strategy(kmg_processor *p, int strategy);
 /* changes kmg_options.alpha_cutoff of a live processor (0 .. 255); calls that are already running keep the value they started
  * with                                                                                                                         */
 KMG_API int kmg_processor_set_alpha_cutoff(kmg_processor *p, uint32_t alpha_cutoff);
+/* kmg_diffusion of a live processor: the filter of the KMG_MODE_DIFFUSE output from now on.  It is read where alpha_cutoff is
+ * read, when an apply plan is made: a plan keeps its filter over all its bands, every call that diffuses (kmg_find, kmg_reduce,
+ * their _indexed and _batch forms, kmg_dev_apply[_format], kmg_reduce_quality) follows it, and kmg_sequence_output_begin[_local]
+ * fixes it for the open output.  NULL or a filter outside 0 .. KMG_DIFFUSION_COUNT - 1: KMG_ERR_INVALID_ARGUMENT, nothing changes */
+KMG_API int kmg_processor_set_diffusion(kmg_processor *p, int filter);
+/* the table at kmg_diffusion (no device needed): weights points to 12 values, [0..1] row 0 (dx = +1, +2), [2..6] row 1 and [7..11]
+ * row 2 (dx = -2 .. +2).  A NULL pointer or an unknown filter: KMG_ERR_INVALID_ARGUMENT, nothing written                          */
+KMG_API int kmg_diffusion_weights(int filter, int32_t *weights, int32_t *divisor);
 /* KMG_WEIGHT_*: whether the palette step weighs a pixel by its alpha byte, see above                                              */
 KMG_API int kmg_processor_set_weighting(kmg_processor *p, int weighting);
 /* sets (n > 0: copies n x 4 bytes) or clears (n = 0) the processor's fixed colours, see above                                     */

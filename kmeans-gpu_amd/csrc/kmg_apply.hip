@@ -138,6 +138,7 @@ struct kmg_apply_plan {
     int mode = 0;
     int format = KMG_FORMAT_RGBA8;      // kmg_output_format of what _run writes
     uint32_t alpha_cutoff = 0;          // kmg_options.alpha_cutoff when the plan was made (0: alpha ignored)
+    int filter = KMG_DIFFUSION_FLOYD_STEINBERG;   // kmg_processor_set_diffusion when the plan was made (KMG_MODE_DIFFUSE reads it)
     bool dither = false;
     float thr = 0.0f;
     Route route = Route::kScan;
@@ -151,7 +152,7 @@ struct kmg_apply_plan {
     hipEvent_t ready = nullptr;         // the tables are built (recorded on the creating stream)
     hipStream_t built_on = nullptr;
     // KMG_MODE_DIFFUSE: the diffusion continues across the bands of consecutive runs
-    // dstate: 2 x width packed error rows, the sticky timeout word (zeroed once), the per-call control block (kmg_diffuse.hip);
+    // dstate: 4 x width packed error rows (Floyd-Steinberg uses the first 2 x width), the sticky timeout word (zeroed once), the per-call control block (kmg_diffuse.hip);
     // stream-ordered from the processor's pool on the first run's stream, given back on `built_on` (every stream is idle by then)
     void *dstate = nullptr;
     uint32_t dwidth = 0, drows = 0, dparity = 0;
@@ -213,7 +214,7 @@ static RouteScratch route_scratch(Route route, uint32_t k, bool index_format)
 }
 
 static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, uint64_t n_pixels_hint, void *stream,
-                       uint32_t alpha_cutoff, kmg_apply_plan **out, int format = KMG_FORMAT_RGBA8)
+                       uint32_t alpha_cutoff, kmg_apply_plan **out, int format = KMG_FORMAT_RGBA8, int filter = -1)
 {
     if (!p || !c4 || !out || k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply_plan arguments");
     *out = nullptr;
@@ -226,6 +227,7 @@ static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, 
     if (!pl) return fail(KMG_ERR_OUT_OF_MEMORY, "host allocation failed");
     struct Undo { kmg_apply_plan *pl; ~Undo() { if (pl) { if (pl->ready) (void)hipEventDestroy(pl->ready); (void)hipStreamSynchronize(pl->built_on); delete pl; } } } undo{pl};
     pl->p = p; pl->k = k; pl->mode = mode; pl->format = format; pl->alpha_cutoff = alpha_cutoff; pl->built_on = st;
+    pl->filter = filter >= 0 ? filter : p->diffusion.load(std::memory_order_relaxed);
 
     // per-centroid work on the host: (L,a,b,C) table, RGBA8 palette (lab_to_rgb.wgsl) with the sentinel's entry behind it
     // (mix_colors.wgsl:73), threshold
@@ -342,7 +344,7 @@ static int check_diffuse_band(kmg_apply_plan *pl, uint32_t w, uint32_t row0)
 static hipError_t run_diffuse(kmg_apply_plan *pl, const uint32_t *src, uint32_t w, uint32_t rows, void *d_out, hipStream_t st)
 {
     kmg_processor *p = pl->p;
-    const size_t erow_bytes = sizeof(uint32_t) * 2 * 2 * (size_t)w;
+    const size_t erow_bytes = sizeof(uint32_t) * 2 * 4 * (size_t)w;   // two ring slots of two rows (kmg_diffuse_wide.hip)
     const size_t sticky_off = pad256(erow_bytes), ctl_off = sticky_off + 16;
     const size_t ctl_bytes = (diffuse_ctl_bytes() + 15) & ~(size_t)15;
     if (!pl->dstate) {
@@ -351,12 +353,20 @@ static hipError_t run_diffuse(kmg_apply_plan *pl, const uint32_t *src, uint32_t 
     }
     uint8_t *erow = (uint8_t *)pl->dstate, *ctl = erow + ctl_off;
     uint32_t *sticky = (uint32_t *)(erow + sticky_off);
+    const bool wide = pl->filter != KMG_DIFFUSION_FLOYD_STEINBERG;      // its own kernel, two pending rows per slot
     if (pl->drows) HIP_PASS(hipStreamWaitEvent(st, pl->ddone, 0));
-    else HIP_PASS(hipMemsetAsync(erow + (size_t)pl->dparity * 8u * w, 0, 8u * (size_t)w, st));    // no row above the image
+    else {                                                             // no row above the image (the other filters: no two rows)
+        const size_t slot = (wide ? 16u : 8u) * (size_t)w;
+        HIP_PASS(hipMemsetAsync(erow + (size_t)pl->dparity * slot, 0, slot, st));
+    }
     HIP_PASS(hipMemsetAsync(ctl, 0, ctl_bytes, st));
     const int kernel = pl->route != Route::kDiffuseTable ? kDiffuseScan : (pl->k <= 256 ? kDiffusePairs : kDiffuseCells);
-    HIP_PASS(launch_diffuse(kernel, src, w, rows, d_out, erow, pl->dparity, ctl, sticky, pl->d_cent, pl->k, p->d_lut, pl->d_pal, pl->aux,
-                            pl->sub, st, pl->alpha_cutoff, pl->format));
+    if (wide)
+        HIP_PASS(launch_diffuse_wide(kernel, diffuse_filter(pl->filter), src, w, rows, d_out, erow, pl->dparity, ctl, sticky, pl->d_cent,
+                                     pl->k, p->d_lut, pl->d_pal, pl->aux, pl->sub, st, pl->alpha_cutoff, pl->format));
+    else
+        HIP_PASS(launch_diffuse(kernel, src, w, rows, d_out, erow, pl->dparity, ctl, sticky, pl->d_cent, pl->k, p->d_lut, pl->d_pal, pl->aux,
+                                pl->sub, st, pl->alpha_cutoff, pl->format));
     HIP_PASS(hipMemcpyAsync((void *)pl->h_timeout, sticky, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_PASS(hipEventRecord(pl->ddone, st));
     pl->dwidth = w;
@@ -371,6 +381,8 @@ void kmg::apply_plan_restart(kmg_apply_plan *pl)
 }
 
 uint32_t kmg::apply_plan_cutoff(const kmg_apply_plan *pl) { return pl->alpha_cutoff; }
+
+int kmg::apply_plan_filter(const kmg_apply_plan *pl) { return pl->filter; }
 
 // kmg_dev_apply and kmg_apply_plan_status: did any diffusion run of the plan time out?  (Read after the last run has completed.)
 static int diffuse_status(kmg_apply_plan *pl)
@@ -481,13 +493,13 @@ try {
 KMG_ABI_CATCH_VOID
 
 int kmg::dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, const float *c4, uint32_t k, int mode,
-                   uint8_t *d_out, void *stream, uint32_t alpha_cutoff, int format)
+                   uint8_t *d_out, void *stream, uint32_t alpha_cutoff, int format, int filter)
 {
     if (!p || !d_rgba || !d_out || !c4 || !w || !rows || k == 0)
         return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply arguments");
     if ((uint64_t)w * rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
     kmg_apply_plan *pl = nullptr;
-    KMG_TRY(plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, alpha_cutoff, &pl, format));
+    KMG_TRY(plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, alpha_cutoff, &pl, format, filter));
     // (diffusion: the band is an image of its own -- the plan is new, so its first run starts from a zero error row)
     int rc = kmg_apply_plan_run(pl, d_rgba, w, rows, mode == KMG_MODE_DIFFUSE ? 0u : row0, d_out, stream);
     const hipError_t e2 = hipStreamSynchronize(S(stream));            // the call returns when the band is written; the block is idle again

@@ -152,6 +152,19 @@ hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t 
                           void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
                           const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff = 0,
                           int format = 0);
+// The other filters of kmg_diffusion (kmg_diffuse_wide.hip): launch_diffuse's arguments and meaning, except that erow holds
+// 4 x w packed error words -- slot `parity` (rows 2 parity, 2 parity + 1) = the errors of the row above the band and of the row
+// above that (zero for a first band); the band leaves its last two rows' errors in slot (parity + chunks) & 1.
+struct DiffuseFilter {
+    int32_t w[12];                 // kmg_diffusion_weights' order
+    uint32_t bias, magic;          // floor((S + D/2) / D) = umulhi(S + bias, magic) - 4096: bias = D/2 + 4096 D, magic = ceil(2^32 / D)
+    int skew;                      // columns a row lags the row above: 3 when the filter takes e(x + 2, .) of a row above, else 2
+};
+DiffuseFilter diffuse_filter(int filter);
+hipError_t launch_diffuse_wide(int route, const DiffuseFilter &f, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out,
+                               void *erow, uint32_t parity, void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k,
+                               const float *lut, const uint32_t *pal, const void *colour_labels, const uint16_t *sub_table,
+                               hipStream_t st, uint32_t alpha_cutoff, int format);
 
 // ---- index output (kmg_output_format INDEX8 / INDEX16): the label of every pixel as u8 (wide = false) or u16 (wide = true);
 // alpha_cutoff != 0: k where the pixel's alpha is below it.  The same decisions as the RGBA8 launchers above.

@@ -6,6 +6,7 @@
 #include <stddef.h>
 
 #include "kmg_state.h"
+#include "kmg_diffusion.h"
 
 // ---------------------------------------------------------------------------------------------
 // errors
@@ -311,6 +312,24 @@ try {
     if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
     if (alpha_cutoff > 255u) return fail(KMG_ERR_INVALID_ARGUMENT, "alpha_cutoff: %u is above 255", alpha_cutoff);
     p->alpha_cutoff.store(alpha_cutoff);
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_processor_set_diffusion(kmg_processor *p, int filter)
+try {
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
+    if (filter < 0 || filter >= KMG_DIFFUSION_COUNT) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown diffusion filter %d", filter);
+    p->diffusion.store(filter);
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_diffusion_weights(int filter, int32_t *weights, int32_t *divisor)
+try {
+    if (!weights || !divisor) return fail(KMG_ERR_INVALID_ARGUMENT, "bad diffusion_weights arguments");
+    if (filter < 0 || filter >= KMG_DIFFUSION_COUNT) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown diffusion filter %d", filter);
+    *divisor = diffusion_table(filter, weights);
     return KMG_OK;
 }
 KMG_ABI_CATCH

@@ -403,6 +403,15 @@ public:
         check(kmg_processor_set_alpha_cutoff(p_, alpha_cutoff));
     }
 
+    // kmg_processor_set_diffusion (include/kmeans_hip.h at kmg_diffusion): the error-diffusion filter of ReduceMode::Diffuse for the
+    // outputs made from now on (KMG_DIFFUSION_FLOYD_STEINBERG is the default); the other modes ignore it.  A processor over
+    // several devices has no such mode.
+    void set_diffusion(int filter) const
+    {
+        if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "a processor over several devices has no diffusion mode");
+        check(kmg_processor_set_diffusion(p_, filter));
+    }
+
     // kmg_processor_set_fixed_colors (include/kmeans_hip.h): colours every k-means palette of the calls that start from now on keeps
     // exactly (alpha ignored), as entries 0 .. colors.size() - 1 in index order; an empty list clears them.  A color_count below
     // their number and Algorithm::Octree are then errors.  A processor over several devices has no fixed colours.

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "ErrorStats", "BatchReport", "BatchApplyReport", "BatchQualityReport", "ClipReport", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "CLIP_FULL_ON_CLEAR", "CLIP_FRAMES", "CLIP_MIN_FRAMES", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "Diffusion", "DIFFUSION_NAMES", "diffusion_weights", "ErrorStats", "BatchReport", "BatchApplyReport", "BatchQualityReport", "ClipReport", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "CLIP_FULL_ON_CLEAR", "CLIP_FRAMES", "CLIP_MIN_FRAMES", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -60,6 +60,41 @@ class ReduceMode(enum.IntEnum):         # core/src/lib.rs:234-239, plus Diffuse 
     Dither = 1
     Meld = 2
     Diffuse = 3                         # Floyd-Steinberg error diffusion (not in the reference; no Group support)
+
+
+class Diffusion(enum.IntEnum):          # include/kmeans_hip.h kmg_diffusion: the filter of ReduceMode.Diffuse
+    FloydSteinberg = 0
+    SierraLite = 1
+    Atkinson = 2
+    Burkes = 3
+    Sierra2 = 4
+    Sierra3 = 5
+    Jarvis = 6
+    Stucki = 7
+
+
+# the CLI's names: the lower-case constant suffixes with - for _
+DIFFUSION_NAMES = {"floyd-steinberg": 0, "sierra-lite": 1, "atkinson": 2, "burkes": 3, "sierra2": 4, "sierra3": 5, "jarvis": 6,
+                   "stucki": 7}
+
+
+def _diffusion_value(f):
+    """a Diffusion, its number, or one of DIFFUSION_NAMES (case and - / _ do not matter); unknown numbers pass through to the library"""
+    if isinstance(f, str):
+        key = f.strip().lower().replace("_", "-")
+        if key not in DIFFUSION_NAMES:
+            raise ValueError(f"unknown diffusion filter {f!r}: one of {', '.join(DIFFUSION_NAMES)}")
+        return DIFFUSION_NAMES[key]
+    return int(f)
+
+
+def diffusion_weights(filter):
+    """kmg_diffusion_weights (no device needed): (weights, divisor) with weights[0..1] row 0 (dx = +1, +2), [2..6] row 1 and
+    [7..11] row 2 (dx = -2 .. +2) as an int32 array"""
+    w = (C.c_int32 * 12)()
+    d = C.c_int32()
+    _check(lib().kmg_diffusion_weights(_diffusion_value(filter), w, C.byref(d)))
+    return np.array(w[:], np.int32), int(d.value)
 
 
 class OutputFormat(enum.IntEnum):       # include/kmeans_hip.h kmg_output_format
@@ -379,7 +414,7 @@ _lib = None
 # every symbol include/kmeans_hip.h declares
 SYMBOLS = [
     "kmg_last_error", "kmg_version", "kmg_host_alloc", "kmg_host_free", "kmg_default_options", "kmg_processor_create",
-    "kmg_processor_create_ex", "kmg_processor_destroy", "kmg_processor_set_strategy", "kmg_processor_set_alpha_cutoff", "kmg_processor_set_weighting", "kmg_processor_set_fixed_colors", "kmg_palette", "kmg_find", "kmg_reduce",
+    "kmg_processor_create_ex", "kmg_processor_destroy", "kmg_processor_set_strategy", "kmg_processor_set_alpha_cutoff", "kmg_processor_set_weighting", "kmg_processor_set_diffusion", "kmg_diffusion_weights", "kmg_processor_set_fixed_colors", "kmg_palette", "kmg_find", "kmg_reduce",
     "kmg_palette_to_centroids", "kmg_centroids_to_palette", "kmg_octree_palette", "kmg_dev_rgb_to_lab",
     "kmg_resized_dims", "kmg_dev_alpha_compact",
     "kmg_dev_resize", "kmg_lloyd_create", "kmg_lloyd_destroy", "kmg_lloyd_set_centroids",
@@ -513,6 +548,9 @@ def lib():
     L.kmg_lloyd_init_centroids_seeded.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, f32p, C.c_uint32, vp]
     L.kmg_lloyd_set_fixed.argtypes = [vp, C.c_uint32]
     L.kmg_processor_set_weighting.argtypes = [vp, C.c_int]
+    if hasattr(L, "kmg_processor_set_diffusion"):        # (KMG_LIBRARY may name an older build: tools/diffusion_filters_time.py times one)
+        L.kmg_processor_set_diffusion.argtypes = [vp, C.c_int]
+        L.kmg_diffusion_weights.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.kmg_lloyd_set_weighting.argtypes = [vp, C.c_int]
     L.kmg_dev_alpha_compact.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, u8p, vp, vp]
     L.kmg_dev_compare.argtypes = [vp, u8p, vp, C.c_uint64, C.c_int, u8p, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
@@ -741,11 +779,12 @@ class ImageProcessor:
     """Mirror of `kmeans_color_gpu::ImageProcessor` (core/src/lib.rs:24-165)."""
 
     def __init__(self, device=-1, shrink_max_dim=256, max_iterations=128, check_period=8,
-                 convergence=1.0, strategy=None, alpha_cutoff=0, fixed_colors=None, alpha_weight=False):
+                 convergence=1.0, strategy=None, alpha_cutoff=0, fixed_colors=None, alpha_weight=False, diffusion=0):
         """alpha_cutoff: 0 = alpha ignored (the reference's behaviour); 1..255 = alpha mode (include/kmeans_hip.h at
         kmg_options): only pixels whose alpha is >= alpha_cutoff shape the palette, and the outputs keep the input's alpha.
         fixed_colors: colours every k-means palette of this processor keeps, as its first entries (set_fixed_colors)
-        alpha_weight: the k-means palettes weigh every pixel by its alpha byte (set_alpha_weight)"""
+        alpha_weight: the k-means palettes weigh every pixel by its alpha byte (set_alpha_weight)
+        diffusion: the filter of ReduceMode.Diffuse (set_diffusion)"""
         self._h = C.c_void_p()
         o = default_options()
         o.device = device
@@ -767,6 +806,16 @@ class ImageProcessor:
             self.set_fixed_colors(fixed_colors)
         if alpha_weight:
             self.set_alpha_weight(True)
+        self.diffusion = Diffusion.FloydSteinberg
+        if _diffusion_value(diffusion):
+            self.set_diffusion(diffusion)
+
+    def set_diffusion(self, filter):
+        """kmg_processor_set_diffusion: the filter (a Diffusion, its number or its CLI name) of the ReduceMode.Diffuse outputs made
+        from now on; an apply plan and an open sequence output keep the one they were made under"""
+        v = _diffusion_value(filter)
+        _check(lib().kmg_processor_set_diffusion(self._h, v))
+        self.diffusion = Diffusion(v)
 
     def set_alpha_weight(self, on):
         """kmg_processor_set_weighting: True = the k-means palette steps of the calls that start from now on weigh every pixel by

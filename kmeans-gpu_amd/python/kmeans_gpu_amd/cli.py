@@ -9,6 +9,9 @@
 Every sub-command also takes `--alpha-cutoff N` (0..255, default 0 = alpha ignored, as in the reference): with N >= 1 only the
 pixels whose alpha is at least N shape the palette, and the output keeps the input's alpha (include/kmeans_hip.h, kmg_options).
 
+`find`, `reduce`, `sequence` and `batch` take `--diffusion NAME` with `-m diffuse`: the error-diffusion filter (floyd-steinberg, the
+default; sierra-lite, atkinson, burkes, sierra2, sierra3, jarvis, stucki; include/kmeans_hip.h at kmg_diffusion).
+
 `reduce` and `find` also take `--indexed`: the output is a palette-mode PNG (one index per pixel, PLTE = the palette; at most 256
 colours) instead of RGBA.  In alpha mode the pixels below the cutoff take one more, fully transparent entry (tRNS 0), so
 255 colours at most.
@@ -66,7 +69,7 @@ import time
 
 import numpy as np
 
-from . import Algorithm, Group, ImageProcessor, ReduceMode
+from . import DIFFUSION_NAMES, Algorithm, Group, ImageProcessor, ReduceMode
 
 _PALETTE_RE = re.compile(r"^#[0-9a-fA-F]{6}(?:,#[0-9a-fA-F]{6})*$")     # args.rs:184
 _MODES = {"replace": ReduceMode.Replace, "dither": ReduceMode.Dither, "meld": ReduceMode.Meld, "diffuse": ReduceMode.Diffuse}
@@ -217,7 +220,8 @@ def run_sequence_local(args, frames, w, h, out_path):
     # frame that is not a delta frame holds nothing: --lossy then has no effect
     delta = not (args.no_delta or args.alpha_cutoff)
     lossy = args.lossy if delta else None
-    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed, alpha_weight=args.alpha_weight) as proc, proc.sequence() as seq:
+    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed, alpha_weight=args.alpha_weight,
+                        diffusion=args.diffusion or 0) as proc, proc.sequence() as seq:
         seq.output_local(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h, warm=args.warm)
         for i, f in enumerate(frames):
             index, colors, info, is_full = seq.frame_local(f, delta=delta, tolerance=lossy)
@@ -255,7 +259,8 @@ def run_sequence(args, ap):
         frames = [with_weights(f, weights) for f in frames]
     if args.local:
         return run_sequence_local(args, frames, w, h, out_path)
-    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed, alpha_weight=args.alpha_weight) as proc, proc.sequence() as seq:
+    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed, alpha_weight=args.alpha_weight,
+                        diffusion=args.diffusion or 0) as proc, proc.sequence() as seq:
         for f in frames:
             seq.add(f)
         colors = seq.output(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h)
@@ -405,6 +410,9 @@ def build_parser():
     for s in (p, f, r, q, b):
         s.add_argument("--alpha-cutoff", type=validate_alpha_cutoff, default=0,
                        help="1..255: pixels with a lower alpha do not shape the palette, the output keeps the input's alpha")
+    for s in (f, r, q, b):
+        s.add_argument("--diffusion", choices=list(DIFFUSION_NAMES), default=None, metavar="NAME",
+                       help="with -m diffuse: the error-diffusion filter, one of " + ", ".join(DIFFUSION_NAMES) + " (default floyd-steinberg)")
     for s in (p, r, q):
         s.add_argument("--fixed", type=validate_palette, default=None, metavar="COLORS",
                        help='"#RRGGBB,..." or a palette image: colours the k-means palette keeps exactly, as its first entries; -c counts them')
@@ -426,6 +434,12 @@ def build_parser():
                    help="choose the colour count: as few colours (at most -c) as keep the dE76 RMS of the shrunk image at or below DE; k-means only")
     r.add_argument("--min-colors", type=validate_k, default=None, metavar="A", help="lower bound of --max-error's search (default 2)")
     return ap
+
+
+def check_diffusion(args, ap):
+    """--diffusion names the filter of -m diffuse: an argument error with any other mode"""
+    if getattr(args, "diffusion", None) is not None and args.mode != "diffuse":
+        ap.error("--diffusion names the filter of -m diffuse: it needs -m diffuse")
 
 
 def run_batch(args, ap):
@@ -456,7 +470,7 @@ def run_batch(args, ap):
             ap.error(f"--indexed writes a palette PNG of at most {limit} colours{' (plus the transparent slot)' if args.alpha_cutoff else ''}; "
                      f"{args.colorcount} requested")
     images = [_load(path) for path in args.input]
-    with ImageProcessor(alpha_cutoff=args.alpha_cutoff) as proc:
+    with ImageProcessor(alpha_cutoff=args.alpha_cutoff, diffusion=args.diffusion or 0) as proc:
         if args.max_error is not None:                   # every image's colour count from the quality target; -c is the upper bound
             os.makedirs(args.output, exist_ok=True)
             results = proc.reduce_quality_batch(images, args.max_error, args.min_colors, args.colorcount, _MODES[args.mode], indexed=args.indexed)
@@ -505,6 +519,7 @@ def run_batch(args, ap):
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
+    check_diffusion(args, ap)
     if args.command == "batch":
         return run_batch(args, ap)
     if getattr(args, "weights", None) is not None:
@@ -596,6 +611,8 @@ def main(argv=None):
             options["fixed_colors"] = fixed
         if getattr(args, "alpha_weight", False):
             options["alpha_weight"] = True
+        if getattr(args, "diffusion", None) is not None:
+            options["diffusion"] = args.diffusion
         proc = ImageProcessor(**options)
     with proc:
         if args.command == "palette":                    # main.rs:46-72

@@ -58,6 +58,16 @@ pub const KMG_MODE_REPLACE: c_int = 0;
 pub const KMG_MODE_DITHER: c_int = 1;
 pub const KMG_MODE_MELD: c_int = 2;
 pub const KMG_MODE_DIFFUSE: c_int = 3;
+/// `kmg_diffusion`: the filter of KMG_MODE_DIFFUSE (kmg_processor_set_diffusion)
+pub const KMG_DIFFUSION_FLOYD_STEINBERG: c_int = 0;
+pub const KMG_DIFFUSION_SIERRA_LITE: c_int = 1;
+pub const KMG_DIFFUSION_ATKINSON: c_int = 2;
+pub const KMG_DIFFUSION_BURKES: c_int = 3;
+pub const KMG_DIFFUSION_SIERRA2: c_int = 4;
+pub const KMG_DIFFUSION_SIERRA3: c_int = 5;
+pub const KMG_DIFFUSION_JARVIS: c_int = 6;
+pub const KMG_DIFFUSION_STUCKI: c_int = 7;
+pub const KMG_DIFFUSION_COUNT: c_int = 8;
 /// `kmg_output_format`: RGBA8, or one u8 / u16 palette index per pixel (`kmg_find_indexed`, `kmg_reduce_indexed`).
 pub const KMG_FORMAT_RGBA8: c_int = 0;
 pub const KMG_FORMAT_INDEX8: c_int = 1;
@@ -165,6 +175,8 @@ extern "C" {
     pub fn kmg_processor_set_alpha_cutoff(p: *mut kmg_processor, alpha_cutoff: u32) -> c_int;
     pub fn kmg_processor_set_fixed_colors(p: *mut kmg_processor, rgba: *const u8, n: u32) -> c_int;
     pub fn kmg_processor_set_weighting(p: *mut kmg_processor, weighting: c_int) -> c_int;
+    pub fn kmg_processor_set_diffusion(p: *mut kmg_processor, filter: c_int) -> c_int;
+    pub fn kmg_diffusion_weights(filter: c_int, weights: *mut i32, divisor: *mut i32) -> c_int;
     // ImageProcessor::palette -- lib.rs:67-77
     pub fn kmg_palette(
         p: *mut kmg_processor,

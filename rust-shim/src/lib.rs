@@ -72,6 +72,16 @@ impl ImageProcessor {
         check(unsafe { ffi::kmg_processor_set_alpha_cutoff(self.raw, alpha_cutoff) })
     }
 
+    /// The error-diffusion filter of `ReduceMode::Diffuse` (`kmg_processor_set_diffusion`, include/kmeans_hip.h at
+    /// `kmg_diffusion`): one of `ffi::KMG_DIFFUSION_*`, 0 = Floyd-Steinberg, the default.  It holds for the outputs made from
+    /// now on; the other modes ignore it.  No counterpart in the reference.  A processor over several devices has no such mode.
+    pub fn set_diffusion(&self, filter: i32) -> Result<()> {
+        if !self.group.is_null() {
+            return Err(anyhow!("a processor over several devices has no diffusion mode"));
+        }
+        check(unsafe { ffi::kmg_processor_set_diffusion(self.raw, filter) })
+    }
+
     /// Alpha weighting (`kmg_processor_set_weighting`, include/kmeans_hip.h): `true` lets every k-means palette of the calls that
     /// start from now on weigh a pixel by its alpha byte (pixels of alpha 0 do not shape it at all); `Algorithm::Octree` is then
     /// an error.  `false`, the default, weighs every kept pixel 1.  No counterpart in the reference.  A processor over several
