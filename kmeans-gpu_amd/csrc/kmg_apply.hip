@@ -344,8 +344,7 @@ static int check_diffuse_band(kmg_apply_plan *pl, uint32_t w, uint32_t row0)
 static hipError_t run_diffuse(kmg_apply_plan *pl, const uint32_t *src, uint32_t w, uint32_t rows, void *d_out, hipStream_t st)
 {
     kmg_processor *p = pl->p;
-    const size_t erow_bytes = sizeof(uint32_t) * 2 * 4 * (size_t)w;   // two ring slots of two rows (kmg_diffuse_wide.hip)
-    const size_t sticky_off = pad256(erow_bytes), ctl_off = sticky_off + 16;
+    const size_t sticky_off = pad256(diffuse_erow_bytes(w)), ctl_off = sticky_off + 16;
     const size_t ctl_bytes = (diffuse_ctl_bytes() + 15) & ~(size_t)15;
     if (!pl->dstate) {
         HIP_PASS(pool_alloc(p, &pl->dstate, ctl_off + ctl_bytes, st));
@@ -353,20 +352,15 @@ static hipError_t run_diffuse(kmg_apply_plan *pl, const uint32_t *src, uint32_t 
     }
     uint8_t *erow = (uint8_t *)pl->dstate, *ctl = erow + ctl_off;
     uint32_t *sticky = (uint32_t *)(erow + sticky_off);
-    const bool wide = pl->filter != KMG_DIFFUSION_FLOYD_STEINBERG;      // its own kernel, two pending rows per slot
     if (pl->drows) HIP_PASS(hipStreamWaitEvent(st, pl->ddone, 0));
-    else {                                                             // no row above the image (the other filters: no two rows)
-        const size_t slot = (wide ? 16u : 8u) * (size_t)w;
+    else {                                                             // no row above the image
+        const size_t slot = diffuse_slot_bytes(pl->filter, w);
         HIP_PASS(hipMemsetAsync(erow + (size_t)pl->dparity * slot, 0, slot, st));
     }
     HIP_PASS(hipMemsetAsync(ctl, 0, ctl_bytes, st));
-    const int kernel = pl->route != Route::kDiffuseTable ? kDiffuseScan : (pl->k <= 256 ? kDiffusePairs : kDiffuseCells);
-    if (wide)
-        HIP_PASS(launch_diffuse_wide(kernel, diffuse_filter(pl->filter), src, w, rows, d_out, erow, pl->dparity, ctl, sticky, pl->d_cent,
-                                     pl->k, p->d_lut, pl->d_pal, pl->aux, pl->sub, st, pl->alpha_cutoff, pl->format));
-    else
-        HIP_PASS(launch_diffuse(kernel, src, w, rows, d_out, erow, pl->dparity, ctl, sticky, pl->d_cent, pl->k, p->d_lut, pl->d_pal, pl->aux,
-                                pl->sub, st, pl->alpha_cutoff, pl->format));
+    const int route = pl->route != Route::kDiffuseTable ? kDiffuseScan : (pl->k <= 256 ? kDiffusePairs : kDiffuseCells);
+    HIP_PASS(launch_diffuse(route, pl->filter, src, w, rows, d_out, pl->format, erow, pl->dparity, ctl, sticky, pl->d_cent, pl->k, p->d_lut,
+                            pl->d_pal, pl->aux, pl->sub, st, pl->alpha_cutoff));
     HIP_PASS(hipMemcpyAsync((void *)pl->h_timeout, sticky, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_PASS(hipEventRecord(pl->ddone, st));
     pl->dwidth = w;
@@ -416,7 +410,7 @@ static hipError_t run_dither_masks(kmg_apply_plan *pl, const uint32_t *src, uint
     StreamBuf lab;                                                    // (freed in stream order when this returns)
     HIP_PASS(lab.alloc(p, sizeof(uint32_t) * n_px, st));
     HIP_PASS(launch_dither_pruned(src, w, rows, row0, pl->d_cent, pl->k, p->d_lut, pl->d_ident, pl->thr, masks, (uint32_t *)lab.ptr, st));
-    return launch_narrow_index(src, (const uint32_t *)lab.ptr, n_px, pl->k, d_out, pl->format == KMG_FORMAT_INDEX16, st, pl->alpha_cutoff);
+    return launch_narrow_index(src, (const uint32_t *)lab.ptr, n_px, pl->k, d_out, pl->format, st, pl->alpha_cutoff);
 }
 
 // One band by the plan's route.  RGBA8 in alpha mode: the source's alpha byte over the output's -- inside the kernel (its ALPHA
@@ -428,22 +422,20 @@ static int run_band(kmg_apply_plan *pl, const uint32_t *src, uint32_t w, uint32_
     kmg_processor *p = pl->p;
     const uint64_t n_px = (uint64_t)w * rows;
     const uint32_t k = pl->k, cutoff = pl->alpha_cutoff;
-    const bool index = pl->format != KMG_FORMAT_RGBA8, wide = pl->format == KMG_FORMAT_INDEX16, alpha = cutoff != 0;
+    const bool index = pl->format != KMG_FORMAT_RGBA8, alpha = cutoff != 0;
     uint32_t *out = (uint32_t *)d_out;                                // (RGBA8)
     hipError_t e = hipSuccess;
     switch (pl->route) {
     case Route::kScan:
-        e = index ? launch_apply_index(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->dither, pl->thr, d_out, wide, st, cutoff)
-                  : launch_apply(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->dither, pl->thr, out, st, alpha);
+        e = launch_apply(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->dither, pl->thr, d_out, pl->format, st, cutoff);
         break;
     case Route::kReplaceTable:
-        if (index) e = launch_labels_index(src, n_px, pl->aux, pl->sub, k, d_out, wide, st, cutoff);
+        if (index) e = launch_labels_index(src, n_px, pl->aux, pl->sub, k, d_out, pl->format, st, cutoff);
         else if ((e = launch_labels(src, n_px, pl->aux, pl->sub, k, pl->d_pal, out, st)) == hipSuccess && alpha)
             e = launch_alpha_merge(src, out, n_px, st);
         break;
     case Route::kDitherLists:
-        e = index ? launch_dither_lists_index(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->thr, (const uint8_t *)pl->aux, d_out, wide, st, cutoff)
-                  : launch_dither_lists(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->thr, (const uint8_t *)pl->aux, out, st, alpha);
+        e = launch_dither_lists(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->thr, (const uint8_t *)pl->aux, d_out, pl->format, st, cutoff);
         break;
     case Route::kDitherMasks:
         e = run_dither_masks(pl, src, w, rows, row0, d_out, st);

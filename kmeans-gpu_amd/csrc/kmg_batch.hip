@@ -321,12 +321,9 @@ int batch_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uint8_t *
     const uint32_t kpad = (k + 3u) & ~3u;
     const size_t lds = sizeof(float4) * kpad + 256 * sizeof(float) + sizeof(unsigned long long) * 4ull * k;
     auto step = [&](uint32_t l) {
-#define KMG_BATCH_ASSIGN(SCAN) \
-    hipLaunchKernelGGL((k_batch_assign<SCAN>), dim3((uint32_t)grid), dim3(kBlock), lds, st, d_rec, m, d_stop, p->d_lut, l, o.convergence)
-        if (k_low >= 32u) KMG_BATCH_ASSIGN(kScanChunked);
-        else if (k < 32u) KMG_BATCH_ASSIGN(kScanPlain);
-        else KMG_BATCH_ASSIGN(kScanByImage);
-#undef KMG_BATCH_ASSIGN
+        with_value<kScanChunked, kScanPlain, kScanByImage>(k_low >= 32u ? kScanChunked : k < 32u ? kScanPlain : kScanByImage, [&](auto SCAN) {
+            hipLaunchKernelGGL((k_batch_assign<SCAN()>), dim3((uint32_t)grid), dim3(kBlock), lds, st, d_rec, m, d_stop, p->d_lut, l, o.convergence);
+        });
         ++n_launches;
         return hipGetLastError();
     };

@@ -80,46 +80,24 @@ int batch_apply_ppt()
 }
 
 // k: the largest count of the launch's images (all below 32, or all from 32 on); one: dither, and an image of the launch has k = 1
-template <int PPT, typename OutT>
-void launch_batch_apply_t(const BatchApplyImage *rec, uint32_t m, kmg::BatchLaunch cut, uint32_t k, const float *lut, bool dither, bool alpha,
-                          bool one, hipStream_t st)
-{
-    const uint32_t kpad = (k + 3u) & ~3u;
-    const bool chunked = k >= 32;
-    const size_t lds = sizeof(float4) * kpad + (256 + 16) * sizeof(float);
-    if (one) {
-        if (alpha) hipLaunchKernelGGL((k_batch_apply<PPT, true, false, true, OutT, true>), dim3(cut.count), dim3(kBlock), lds, st, rec, m, cut.first, lut);
-        else hipLaunchKernelGGL((k_batch_apply<PPT, true, false, false, OutT, true>), dim3(cut.count), dim3(kBlock), lds, st, rec, m, cut.first, lut);
-        return;
-    }
-#define KMG_BATCH_APPLY(D, C, A) \
-    hipLaunchKernelGGL((k_batch_apply<PPT, D, C, A, OutT>), dim3(cut.count), dim3(kBlock), lds, st, rec, m, cut.first, lut)
-    if (alpha) {
-        if (dither) { if (chunked) KMG_BATCH_APPLY(true, true, true); else KMG_BATCH_APPLY(true, false, true); }
-        else        { if (chunked) KMG_BATCH_APPLY(false, true, true); else KMG_BATCH_APPLY(false, false, true); }
-    } else {
-        if (dither) { if (chunked) KMG_BATCH_APPLY(true, true, false); else KMG_BATCH_APPLY(true, false, false); }
-        else        { if (chunked) KMG_BATCH_APPLY(false, true, false); else KMG_BATCH_APPLY(false, false, false); }
-    }
-#undef KMG_BATCH_APPLY
-}
-
 template <int PPT>
 hipError_t launch_batch_apply(const BatchApplyImage *rec, uint32_t m, kmg::BatchLaunch cut, uint32_t k, const float *lut, bool dither,
                               bool alpha, bool one, int format, hipStream_t st)
 {
-    if (format == KMG_FORMAT_INDEX8) launch_batch_apply_t<PPT, uint8_t>(rec, m, cut, k, lut, dither, alpha, one, st);
-    else if (format == KMG_FORMAT_INDEX16) launch_batch_apply_t<PPT, uint16_t>(rec, m, cut, k, lut, dither, alpha, one, st);
-    else launch_batch_apply_t<PPT, uint32_t>(rec, m, cut, k, lut, dither, alpha, one, st);
-    return hipGetLastError();
-}
-
-// what k_apply's launchers pass as `aligned` for (src, out) in `format` (kmg_kernels.hip launch_apply / launch_apply_index_t)
-uint32_t aligned_word(const void *src, const void *out, int format, uint32_t cutoff)
-{
-    if (format == KMG_FORMAT_INDEX8) return (uint32_t)output_aligned<uint8_t>(src, out) | ((cutoff & 255u) << 8);
-    if (format == KMG_FORMAT_INDEX16) return (uint32_t)output_aligned<uint16_t>(src, out) | ((cutoff & 255u) << 8);
-    return (uint32_t)output_aligned<uint32_t>(src, out);
+    const uint32_t kpad = (k + 3u) & ~3u;
+    const bool chunked = k >= 32;
+    const size_t lds = sizeof(float4) * kpad + (256 + 16) * sizeof(float);
+    const bool known = with_out_type(format, [&](auto t) { with_bool(alpha, [&](auto A) {
+        using OutT = typename decltype(t)::type;
+        if (one) {
+            hipLaunchKernelGGL((k_batch_apply<PPT, true, false, A(), OutT, true>), dim3(cut.count), dim3(kBlock), lds, st, rec, m, cut.first, lut);
+            return;
+        }
+        with_bool(dither, [&](auto D) { with_bool(chunked, [&](auto C) {
+            hipLaunchKernelGGL((k_batch_apply<PPT, D(), C(), A(), OutT>), dim3(cut.count), dim3(kBlock), lds, st, rec, m, cut.first, lut);
+        }); });
+    }); });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // Images idx[0 .. m) of the caller's arrays through ONE chain of the batched kernel (their counts all below 32, or all from 32
@@ -181,7 +159,7 @@ int batch_apply_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uin
         r.w = widths[idx[q]];
         r.first_wg = first_wg[q];
         r.threshold = thr[t];
-        r.aligned = aligned_word(r.rgba, r.out, format, cutoff);
+        with_out_type(format, [&](auto t) { r.aligned = (uint32_t)output_flags<typename decltype(t)::type>(r.rgba, r.out, cutoff); });
         r.k = ks[idx[q]];
         r.mode_format = (uint32_t)mode | ((uint32_t)format << 8);
         r.alpha_cutoff = cutoff;

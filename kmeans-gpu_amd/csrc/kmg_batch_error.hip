@@ -155,18 +155,19 @@ __global__ __launch_bounds__(kPassBlock) void k_batch_error_stats(const BatchErr
     }
 }
 
-template <int FORM>
-hipError_t batch_error_form(uint32_t what, const BatchErrorImage *rec, uint32_t m, BatchLaunch cut, uint32_t k_max, uint32_t cutoff,
-                            const float *lut, hipStream_t st)
+hipError_t launch_batch_error(int form, uint32_t what, const BatchErrorImage *rec, uint32_t m, BatchLaunch cut, uint32_t k_max, uint32_t cutoff,
+                              const float *lut, hipStream_t st)
 {
     const bool lab = (what & KMG_ERROR_LAB) != 0;
-    const size_t lds = FORM == kErrorRgba8 ? 0 : (size_t)k_max * (lab ? sizeof(int4) : sizeof(uint32_t));
-#define KMG_BES(W) hipLaunchKernelGGL((k_batch_error_stats<FORM, W>), dim3(cut.count), dim3(kPassBlock), lds, st, rec, m, cut.first, cutoff, lut)
-    if (what == KMG_ERROR_RGB) KMG_BES(KMG_ERROR_RGB);
-    else if (what == KMG_ERROR_LAB) KMG_BES(KMG_ERROR_LAB);
-    else KMG_BES(KMG_ERROR_RGB | KMG_ERROR_LAB);
-#undef KMG_BES
-    return hipGetLastError();
+    const size_t lds = form == kErrorRgba8 ? 0 : (size_t)k_max * (lab ? sizeof(int4) : sizeof(uint32_t));
+    bool launched = false;                                            // (stays false for a form or `what` that does not exist)
+    with_value<kErrorRgba8, kErrorIndex8, kErrorIndex16>(form, [&](auto F) {
+        with_value<KMG_ERROR_RGB, KMG_ERROR_LAB, KMG_ERROR_RGB | KMG_ERROR_LAB>((int)what, [&](auto W) {
+            hipLaunchKernelGGL((k_batch_error_stats<F(), W()>), dim3(cut.count), dim3(kPassBlock), lds, st, rec, m, cut.first, cutoff, lut);
+            launched = true;
+        });
+    });
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -217,9 +218,7 @@ int dev_compare_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const 
     }
     for (const BatchLaunch &cut : batch_launches(grid)) {
         const BatchErrorImage *d_rec = (const BatchErrorImage *)base;
-        if (form == kErrorRgba8) HIP_TRY(batch_error_form<kErrorRgba8>(what, d_rec, n_images, cut, k_max, cutoff, p->d_lut, st));
-        else if (form == kErrorIndex8) HIP_TRY(batch_error_form<kErrorIndex8>(what, d_rec, n_images, cut, k_max, cutoff, p->d_lut, st));
-        else HIP_TRY(batch_error_form<kErrorIndex16>(what, d_rec, n_images, cut, k_max, cutoff, p->d_lut, st));
+        HIP_TRY(launch_batch_error(form, what, d_rec, n_images, cut, k_max, cutoff, p->d_lut, st));
         if (launches) ++*launches;
     }
     return KMG_OK;

@@ -232,14 +232,11 @@ int clip_typed(kmg_processor *p, uint32_t n_frames, const uint8_t *const *d_src,
     unsigned long long *info = reinterpret_cast<unsigned long long *>(d_info);
     for (uint32_t f0 = 0; f0 < n_frames; f0 += kClipFrames) {
         const uint32_t nf = std::min(kClipFrames, n_frames - f0);
-        if (lossy)
-            hipLaunchKernelGGL((k_clip_hold<T, true>), dim3(grid), dim3(kPassBlock), 0, st, fr, f0, nf, static_cast<T *>(d_canvas),
-                               reinterpret_cast<uint32_t *>(d_held), n, width, k, p->d_lut, canvas_vec, held_vec, kPassTile % width,
-                               kPassTile / width, full_on_clear ? d_full : nullptr, info);
-        else
-            hipLaunchKernelGGL((k_clip_hold<T, false>), dim3(grid), dim3(kPassBlock), 0, st, fr, f0, nf, static_cast<T *>(d_canvas),
-                               static_cast<uint32_t *>(nullptr), n, width, k, p->d_lut, canvas_vec, 0u, kPassTile % width, kPassTile / width,
-                               full_on_clear ? d_full : nullptr, info);
+        with_bool(lossy, [&](auto L) {                                  // (an exact clip has no held source)
+            hipLaunchKernelGGL((k_clip_hold<T, L()>), dim3(grid), dim3(kPassBlock), 0, st, fr, f0, nf, static_cast<T *>(d_canvas),
+                               lossy ? reinterpret_cast<uint32_t *>(d_held) : nullptr, n, width, k, p->d_lut, canvas_vec, lossy ? held_vec : 0u,
+                               kPassTile % width, kPassTile / width, full_on_clear ? d_full : nullptr, info);
+        });
         HIP_TRY(hipGetLastError());
         ++*launches;
     }
@@ -278,11 +275,12 @@ int frame_clip_impl(kmg_processor *p, uint32_t n_frames, const uint8_t *const *d
     HIP_TRY(hipSetDevice(p->device));
     uint32_t none = 0;
     if (!launches) launches = &none;
-    if (format == KMG_FORMAT_INDEX8)
-        return clip_typed<uint8_t>(p, n_frames, d_src_rgba, d_index, d_canvas, d_held_rgba, n, width, k, tolerances, full_on_clear, d_out, d_info,
-                                   d_full, launches, st);
-    return clip_typed<uint16_t>(p, n_frames, d_src_rgba, d_index, d_canvas, d_held_rgba, n, width, k, tolerances, full_on_clear, d_out, d_info,
-                                d_full, launches, st);
+    int rc = KMG_OK;                                                  // (check_index_band has refused every other format)
+    with_index_type(format, [&](auto t) {
+        rc = clip_typed<typename decltype(t)::type>(p, n_frames, d_src_rgba, d_index, d_canvas, d_held_rgba, n, width, k, tolerances, full_on_clear, d_out,
+                                                    d_info, d_full, launches, st);
+    });
+    return rc;
 }
 
 }  // namespace kmg

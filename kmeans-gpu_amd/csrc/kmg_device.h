@@ -6,6 +6,7 @@
 
 #include <type_traits>
 
+#include "kmg_dispatch.h"
 #include "kmg_kernels.h"
 #include "kmg_math.h"
 
@@ -123,6 +124,14 @@ template <typename OutT>
 inline int output_aligned(const void *src, const void *out)
 {
     return ((reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & (4u * sizeof(OutT) - 1u)) == 0) ? 1 : 0;
+}
+
+// The last argument of the output kernels that have no cutoff argument of their own (k_apply, k_dither_lists, the batch records'
+// `aligned`): RGBA8 0 / 1; an index format bit 0 the same and the alpha cutoff in bits 8..15.  The one statement of this rule.
+template <typename OutT>
+inline int output_flags(const void *src, const void *out, uint32_t cutoff)
+{
+    return output_aligned<OutT>(src, out) | (kIndexOut<OutT> ? (int)((cutoff & 255u) << 8) : 0);
 }
 
 // Centroid table -> LDS as (L, a, b, C) float4, padded to a multiple of 4 with entries no pixel can

@@ -185,34 +185,30 @@ uint32_t diffuse_grid(int route, uint32_t rows)
     return g ? g : 1u;
 }
 
-template <typename OutT>
-static void launch_diffuse_t(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, OutT *out, void *erow, uint32_t parity,
-                             void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                             const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff)
-{
-    const uint32_t grid = diffuse_grid(route, rows);
-#define KMG_DIFFUSE_A(R, A)                                                                                                          \
-    hipLaunchKernelGGL((k_diffuse<R, A, OutT>), dim3(grid), dim3(64), 0, st, rgba, w, rows, out, (uint2 *)erow, parity, (DiffCtl *)ctl,  \
-                       sticky, cent, k, lut, pal, colour_labels, sub_table, alpha_cutoff)
-#define KMG_DIFFUSE(R) do { if (alpha_cutoff) KMG_DIFFUSE_A(R, true); else KMG_DIFFUSE_A(R, false); } while (0)
-    if (route == kDiffusePairs) KMG_DIFFUSE(kDiffusePairs);
-    else if (route == kDiffuseCells) KMG_DIFFUSE(kDiffuseCells);
-    else KMG_DIFFUSE(kDiffuseScan);
-#undef KMG_DIFFUSE
-#undef KMG_DIFFUSE_A
-}
+// The error rows in `erow`: two ring slots, each the rows a chunk hands to the next -- one row of w packed words (8 bytes a
+// column) for Floyd-Steinberg, two for the other filters (kmg_diffuse_wide.hip).  The buffer is sized for the larger.
+size_t diffuse_erow_bytes(uint32_t w) { return 2 * 16 * (size_t)w; }
 
-hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out, void *erow, uint32_t parity,
-                          void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff, int format)
+size_t diffuse_slot_bytes(int filter, uint32_t w) { return (filter == KMG_DIFFUSION_FLOYD_STEINBERG ? 8u : 16u) * (size_t)w; }
+
+hipError_t launch_diffuse(int route, int filter, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out, int format, void *erow,
+                          uint32_t parity, void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut,
+                          const uint32_t *pal, const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff)
 {
-    if (format == KMG_FORMAT_INDEX8)
-        launch_diffuse_t(route, rgba, w, rows, (uint8_t *)out, erow, parity, ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, st, alpha_cutoff);
-    else if (format == KMG_FORMAT_INDEX16)
-        launch_diffuse_t(route, rgba, w, rows, (uint16_t *)out, erow, parity, ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, st, alpha_cutoff);
-    else
-        launch_diffuse_t(route, rgba, w, rows, (uint32_t *)out, erow, parity, ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, st, alpha_cutoff);
-    return hipGetLastError();
+    if (filter != KMG_DIFFUSION_FLOYD_STEINBERG)
+        return launch_diffuse_wide(route, filter, rgba, w, rows, out, format, erow, parity, ctl, sticky, cent, k, lut, pal, colour_labels,
+                                   sub_table, st, alpha_cutoff);
+    const uint32_t grid = diffuse_grid(route, rows);
+    bool launched = false;                                            // (stays false for a route or format that does not exist)
+    with_value<kDiffuseScan, kDiffusePairs, kDiffuseCells>(route, [&](auto R) { with_bool(alpha_cutoff != 0, [&](auto A) {
+        with_out_type(format, [&](auto t) {
+            using OutT = typename decltype(t)::type;
+            hipLaunchKernelGGL((k_diffuse<R(), A(), OutT>), dim3(grid), dim3(64), 0, st, rgba, w, rows, static_cast<OutT *>(out), (uint2 *)erow,
+                               parity, (DiffCtl *)ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, alpha_cutoff);
+            launched = true;
+        });
+    }); });
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace kmg

@@ -10,6 +10,17 @@
 
 namespace kmg {
 
+// a filter of kmg_diffuse_wide.hip as its kernel takes it
+struct DiffuseFilter {
+    int32_t w[12];                 // kmg_diffusion_weights' order
+    uint32_t bias, magic;          // floor((S + D/2) / D) = umulhi(S + bias, magic) - 4096: bias = D/2 + 4096 D, magic = ceil(2^32 / D)
+    int skew;                      // columns a row lags the row above: 3 when the filter takes e(x + 2, .) of a row above, else 2
+};
+// launch_diffuse (kmg_kernels.h) for the filters other than Floyd-Steinberg; it calls this
+hipError_t launch_diffuse_wide(int route, int filter, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out, int format, void *erow,
+                               uint32_t parity, void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut,
+                               const uint32_t *pal, const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff);
+
 namespace {
 
 constexpr int kBody = 16;                          // columns per unrolled body: source block, output block, publish batch

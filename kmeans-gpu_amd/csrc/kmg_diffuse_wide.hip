@@ -218,27 +218,7 @@ __global__ __launch_bounds__(64) void k_diffuse_wide(const uint32_t *__restrict_
     }
 }
 
-template <typename OutT>
-void launch_wide_t(int route, int skew, const uint32_t *rgba, uint32_t w, uint32_t rows, OutT *out, void *erow, uint32_t parity,
-                   void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                   const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff, const DiffuseFilter &f)
-{
-    const uint32_t grid = diffuse_grid(route, rows);
-#define KMG_WIDE_S(R, A, S)                                                                                                          \
-    hipLaunchKernelGGL((k_diffuse_wide<R, A, OutT, S>), dim3(grid), dim3(64), 0, st, rgba, w, rows, out, (uint2 *)erow, parity,       \
-                       (DiffCtl *)ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, alpha_cutoff, f)
-#define KMG_WIDE_A(R, A) do { if (skew == 3) KMG_WIDE_S(R, A, 3); else KMG_WIDE_S(R, A, 2); } while (0)
-#define KMG_WIDE(R) do { if (alpha_cutoff) KMG_WIDE_A(R, true); else KMG_WIDE_A(R, false); } while (0)
-    if (route == kDiffusePairs) KMG_WIDE(kDiffusePairs);
-    else if (route == kDiffuseCells) KMG_WIDE(kDiffuseCells);
-    else KMG_WIDE(kDiffuseScan);
-#undef KMG_WIDE
-#undef KMG_WIDE_A
-#undef KMG_WIDE_S
-}
-
-}  // namespace
-
+// the kernel's arguments from kmg_diffusion.h's table
 DiffuseFilter diffuse_filter(int filter)
 {
     DiffuseFilter f{};
@@ -249,18 +229,24 @@ DiffuseFilter diffuse_filter(int filter)
     return f;
 }
 
-hipError_t launch_diffuse_wide(int route, const DiffuseFilter &f, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out,
-                               void *erow, uint32_t parity, void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k,
-                               const float *lut, const uint32_t *pal, const void *colour_labels, const uint16_t *sub_table,
-                               hipStream_t st, uint32_t alpha_cutoff, int format)
+}  // namespace
+
+hipError_t launch_diffuse_wide(int route, int filter, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out, int format, void *erow,
+                               uint32_t parity, void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut,
+                               const uint32_t *pal, const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff)
 {
-    if (format == KMG_FORMAT_INDEX8)
-        launch_wide_t(route, f.skew, rgba, w, rows, (uint8_t *)out, erow, parity, ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, st, alpha_cutoff, f);
-    else if (format == KMG_FORMAT_INDEX16)
-        launch_wide_t(route, f.skew, rgba, w, rows, (uint16_t *)out, erow, parity, ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, st, alpha_cutoff, f);
-    else
-        launch_wide_t(route, f.skew, rgba, w, rows, (uint32_t *)out, erow, parity, ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, st, alpha_cutoff, f);
-    return hipGetLastError();
+    const DiffuseFilter f = diffuse_filter(filter);
+    const uint32_t grid = diffuse_grid(route, rows);
+    bool launched = false;                                            // (stays false for a route or format that does not exist)
+    with_value<kDiffuseScan, kDiffusePairs, kDiffuseCells>(route, [&](auto R) { with_bool(alpha_cutoff != 0, [&](auto A) {
+        with_out_type(format, [&](auto t) { with_value<2, 3>(f.skew, [&](auto S) {
+            using OutT = typename decltype(t)::type;
+            hipLaunchKernelGGL((k_diffuse_wide<R(), A(), OutT, S()>), dim3(grid), dim3(64), 0, st, rgba, w, rows, static_cast<OutT *>(out),
+                               (uint2 *)erow, parity, (DiffCtl *)ctl, sticky, cent, k, lut, pal, colour_labels, sub_table, alpha_cutoff, f);
+            launched = true;
+        }); });
+    }); });
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace kmg

@@ -168,25 +168,6 @@ __global__ __launch_bounds__(kPassBlock) void k_error_stats(const uint32_t *__re
     }
 }
 
-template <int FORM>
-hipError_t error_stats_form(uint32_t what, const uint32_t *src, const void *out, uint64_t n, const uint32_t *pal, const void *entries,
-                            uint32_t k, uint32_t cutoff, const float *lut, unsigned long long *stats, hipStream_t st)
-{
-    const uint32_t grid = pass_grid((n + kPassTile - 1) / kPassTile);
-    // the vector loads: the source 16-byte aligned, the output for its own (RGBA8 words and u32 labels 16, u8 4, u16 8 bytes)
-    const uintptr_t out_mask = FORM == kErrorIndex8 ? 3u : (FORM == kErrorIndex16 ? 7u : 15u);
-    const int aligned = ((reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & out_mask) == 0) ? 1 : 0;
-    const bool lab = (what & KMG_ERROR_LAB) != 0;
-    const size_t lds = FORM == kErrorRgba8 ? 0 : (size_t)k * (lab ? sizeof(int4) : sizeof(uint32_t));
-#define KMG_ES(W) hipLaunchKernelGGL((k_error_stats<FORM, W>), dim3(grid), dim3(kPassBlock), lds, st, src, out, n, pal, \
-                                     static_cast<const int4 *>(entries), k, cutoff, lut, stats, aligned)
-    if (what == KMG_ERROR_RGB) KMG_ES(KMG_ERROR_RGB);
-    else if (what == KMG_ERROR_LAB) KMG_ES(KMG_ERROR_LAB);
-    else KMG_ES(KMG_ERROR_RGB | KMG_ERROR_LAB);
-#undef KMG_ES
-    return hipGetLastError();
-}
-
 }  // namespace
 
 size_t error_palette_bytes(uint32_t k) { return sizeof(int4) * (size_t)k; }
@@ -200,13 +181,21 @@ hipError_t launch_error_palette(const uint32_t *pal, uint32_t k, const float *lu
 hipError_t launch_error_stats(int form, uint32_t what, const uint32_t *src, const void *out, uint64_t n, const uint32_t *pal,
                               const void *entries, uint32_t k, uint32_t cutoff, const float *lut, unsigned long long *stats, hipStream_t st)
 {
-    switch (form) {
-    case kErrorRgba8: return error_stats_form<kErrorRgba8>(what, src, out, n, pal, entries, k, cutoff, lut, stats, st);
-    case kErrorIndex8: return error_stats_form<kErrorIndex8>(what, src, out, n, pal, entries, k, cutoff, lut, stats, st);
-    case kErrorIndex16: return error_stats_form<kErrorIndex16>(what, src, out, n, pal, entries, k, cutoff, lut, stats, st);
-    case kErrorLabel32: return error_stats_form<kErrorLabel32>(what, src, out, n, pal, entries, k, cutoff, lut, stats, st);
-    }
-    return hipErrorInvalidValue;
+    const uint32_t grid = pass_grid((n + kPassTile - 1) / kPassTile);
+    // the vector loads: the source 16-byte aligned, the output for its own (RGBA8 words and u32 labels 16, u8 4, u16 8 bytes)
+    const uintptr_t out_mask = form == kErrorIndex8 ? 3u : (form == kErrorIndex16 ? 7u : 15u);
+    const int aligned = ((reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & out_mask) == 0) ? 1 : 0;
+    const bool lab = (what & KMG_ERROR_LAB) != 0;
+    const size_t lds = form == kErrorRgba8 ? 0 : (size_t)k * (lab ? sizeof(int4) : sizeof(uint32_t));
+    bool launched = false;                                            // (stays false for a form or `what` that does not exist)
+    with_value<kErrorRgba8, kErrorIndex8, kErrorIndex16, kErrorLabel32>(form, [&](auto F) {
+        with_value<KMG_ERROR_RGB, KMG_ERROR_LAB, KMG_ERROR_RGB | KMG_ERROR_LAB>((int)what, [&](auto W) {
+            hipLaunchKernelGGL((k_error_stats<F(), W()>), dim3(grid), dim3(kPassBlock), lds, st, src, out, n, pal,
+                               static_cast<const int4 *>(entries), k, cutoff, lut, stats, aligned);
+            launched = true;
+        });
+    });
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace kmg

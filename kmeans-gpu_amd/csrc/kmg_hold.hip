@@ -178,10 +178,11 @@ int frame_hold_impl(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_i
     const uint64_t n = (uint64_t)width * rows;
     HIP_TRY(hipSetDevice(p->device));
     unsigned long long *info = reinterpret_cast<unsigned long long *>(d_info);
-    if (format == KMG_FORMAT_INDEX8)
-        HIP_TRY(frame_hold_typed<uint8_t>(d_src_rgba, d_index, d_canvas, d_held_rgba, d_delta, n, width, row0, k, tolerance, p->d_lut, info, st));
-    else
-        HIP_TRY(frame_hold_typed<uint16_t>(d_src_rgba, d_index, d_canvas, d_held_rgba, d_delta, n, width, row0, k, tolerance, p->d_lut, info, st));
+    hipError_t e = hipErrorInvalidValue;
+    with_index_type(format, [&](auto t) {
+        e = frame_hold_typed<typename decltype(t)::type>(d_src_rgba, d_index, d_canvas, d_held_rgba, d_delta, n, width, row0, k, tolerance, p->d_lut, info, st);
+    });
+    HIP_TRY(e);
     return KMG_OK;
 }
 

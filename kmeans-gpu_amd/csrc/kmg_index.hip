@@ -100,49 +100,36 @@ __global__ __launch_bounds__(kBlock) void k_narrow_index(const uint32_t *__restr
     }
 }
 
-template <typename OutT>
-void labels_index_t(const uint32_t *rgba, uint64_t n, const void *colour_labels, const uint16_t *sub_table, uint32_t k, OutT *out,
-                    hipStream_t st, uint32_t cutoff)
+}  // namespace
+
+hipError_t launch_labels_index(const uint32_t *rgba, uint64_t n, const void *colour_labels, const uint16_t *sub_table, uint32_t k,
+                               void *out, int format, hipStream_t st, uint32_t alpha_cutoff)
 {
     const uint64_t tiles = (n + kIndexBlock * 8 - 1) / (kIndexBlock * 8);
     // as launch_labels: one workgroup per CU with the 128 KiB pair table, two with the 64 KiB summaries
     const uint32_t cap = k <= 256 ? device_info().cus : 2u * device_info().cus;
     const uint32_t grid = (uint32_t)(tiles < cap ? (tiles ? tiles : 1) : cap);
-    const int aligned = output_aligned<OutT>(rgba, out);
-#define KMG_LI(A, P) hipLaunchKernelGGL((k_labels_index<OutT, A, P>), dim3(grid), dim3(kIndexBlock), 0, st, rgba, n, colour_labels, \
-                                        sub_table, k, out, aligned, cutoff)
-    if (k <= 256) { if (cutoff) KMG_LI(true, true); else KMG_LI(false, true); }
-    else { if (cutoff) KMG_LI(true, false); else KMG_LI(false, false); }
-#undef KMG_LI
+    const bool known = with_index_type(format, [&](auto t) { with_bool(alpha_cutoff != 0, [&](auto A) { with_bool(k <= 256, [&](auto P) {
+        using OutT = typename decltype(t)::type;
+        hipLaunchKernelGGL((k_labels_index<OutT, A(), P()>), dim3(grid), dim3(kIndexBlock), 0, st, rgba, n, colour_labels, sub_table, k,
+                           static_cast<OutT *>(out), output_aligned<OutT>(rgba, out), alpha_cutoff);
+    }); }); });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
-template <typename OutT>
-void narrow_index_t(const uint32_t *rgba, const uint32_t *labels, uint64_t n, uint32_t k, OutT *out, hipStream_t st, uint32_t cutoff)
+hipError_t launch_narrow_index(const uint32_t *rgba, const uint32_t *labels, uint64_t n, uint32_t k, void *out, int format, hipStream_t st,
+                               uint32_t alpha_cutoff)
 {
     const uint64_t blocks = ((n + 3) / 4 + kBlock - 1) / kBlock;
     const uint32_t grid = (uint32_t)(blocks < 4096 ? (blocks ? blocks : 1) : 4096);
-    // (labels: the plan's own scratch, 256-byte aligned; the source's alignment decides for both loads)
-    const int aligned = output_aligned<OutT>(rgba, out) & output_aligned<uint32_t>(labels, labels);
-    if (cutoff) hipLaunchKernelGGL((k_narrow_index<OutT, true>), dim3(grid), dim3(kBlock), 0, st, rgba, labels, n, k, out, aligned, cutoff);
-    else hipLaunchKernelGGL((k_narrow_index<OutT, false>), dim3(grid), dim3(kBlock), 0, st, rgba, labels, n, k, out, aligned, cutoff);
-}
-
-}  // namespace
-
-hipError_t launch_labels_index(const uint32_t *rgba, uint64_t n, const void *colour_labels, const uint16_t *sub_table, uint32_t k,
-                               void *out, bool wide, hipStream_t st, uint32_t alpha_cutoff)
-{
-    if (wide) labels_index_t(rgba, n, colour_labels, sub_table, k, (uint16_t *)out, st, alpha_cutoff);
-    else labels_index_t(rgba, n, colour_labels, sub_table, k, (uint8_t *)out, st, alpha_cutoff);
-    return hipGetLastError();
-}
-
-hipError_t launch_narrow_index(const uint32_t *rgba, const uint32_t *labels, uint64_t n, uint32_t k, void *out, bool wide, hipStream_t st,
-                               uint32_t alpha_cutoff)
-{
-    if (wide) narrow_index_t(rgba, labels, n, k, (uint16_t *)out, st, alpha_cutoff);
-    else narrow_index_t(rgba, labels, n, k, (uint8_t *)out, st, alpha_cutoff);
-    return hipGetLastError();
+    const bool known = with_index_type(format, [&](auto t) { with_bool(alpha_cutoff != 0, [&](auto A) {
+        using OutT = typename decltype(t)::type;
+        // (labels: the plan's own scratch, 256-byte aligned; the source's alignment decides for both loads)
+        const int aligned = output_aligned<OutT>(rgba, out) & output_aligned<uint32_t>(labels, labels);
+        hipLaunchKernelGGL((k_narrow_index<OutT, A()>), dim3(grid), dim3(kBlock), 0, st, rgba, labels, n, k, static_cast<OutT *>(out), aligned,
+                           alpha_cutoff);
+    }); });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace kmg

@@ -110,19 +110,23 @@ hipError_t launch_alpha_compact(const uint32_t *rgba, uint64_t n, uint32_t cutof
                                 unsigned long long *counts, hipStream_t st);
 // out[i] = (out[i] & 0x00FFFFFF) | (rgba[i] & 0xFF000000): alpha mode after an output kernel without the compile-time switch
 hipError_t launch_alpha_merge(const uint32_t *rgba, uint32_t *out, uint64_t n, hipStream_t st);
-// the list-based dither and meld passes (kmg_lists.hip) with the alpha switch; kmg_table.h declares them without it (= false)
+
+// ---- The output passes.  Where a family has index output (kmg_output_format) its launcher takes (void *out, int format,
+// alpha_cutoff): out holds RGBA8 words (format 0), or the label of every pixel as u8 (1) / u16 (2).  alpha_cutoff != 0 is alpha
+// mode, a separate instantiation of the kernel (alpha_cutoff = 0 runs the code of the passes without alpha mode): RGBA8 keeps the
+// pixel's own alpha byte over the output's, an index format writes k where the pixel's alpha is below the cutoff.  pal is read by
+// RGBA8 only.  A format (or route) that does not exist: hipErrorInvalidValue, nothing launched.
+
+// the list-based dither and meld passes (kmg_lists.hip); kmg_table.h declares them without alpha mode (RGBA8)
 hipError_t launch_meld_lists(const uint32_t *rgba, uint64_t n, const Centroid *cent, uint32_t k, const float *lut,
                              const uint8_t *lists, uint32_t *out, hipStream_t st, bool alpha);
 hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                               const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, uint32_t *out,
-                               hipStream_t st, bool alpha);
+                               const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, void *out, int format,
+                               hipStream_t st, uint32_t alpha_cutoff);
 
 // replace / dither output pass.  pal: k+1 RGBA8 words (entry k = the converted sentinel).
-// alpha (every output pass, kmg_options.alpha_cutoff != 0): the pixel's own alpha byte over the output's (a separate instantiation
-// of the kernel; alpha = false runs the code of the passes without alpha mode)
-hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0,
-                        const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                        bool dither, float threshold, uint32_t *out, hipStream_t st, bool alpha = false);
+hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k, const float *lut,
+                        const uint32_t *pal, bool dither, float threshold, void *out, int format, hipStream_t st, uint32_t alpha_cutoff = 0);
 
 // thr[256] (device): the linear-channel thresholds of the 256 sRGB8 output bytes (k_meld), made by the device's own encode
 hipError_t launch_encode_thresholds(float *thr, hipStream_t st);
@@ -138,8 +142,8 @@ hipError_t launch_meld(const uint32_t *rgba, uint64_t n, const Centroid *cent, u
 
 // error-diffusion output pass, KMG_MODE_DIFFUSE (kmg_diffuse.hip).  route: how a quantised colour finds its label --
 // kDiffuseScan: per-lane arg-min over cent (LDS); kDiffusePairs (k <= 256) / kDiffuseCells (k > 256): the replace pass's colour
-// table (colour_labels + sub_table of launch_cube without histogram).  erow: 2 x w packed error words, row `parity` = the error of
-// the row above the band (zero for a first band); the band leaves its last row's error in row (parity + chunks) & 1.
+// table (colour_labels + sub_table of launch_cube without histogram).  erow: two slots of packed error words, slot `parity` = the
+// error of the row above the band (zero for a first band); the band leaves its last row's error in slot (parity + chunks) & 1.
 // ctl: diffuse_ctl_bytes() of per-call control words, zero on entry; ctl word 1 != 0 afterwards = the pass timed out.
 // sticky: a word the caller zeroes once; a pass that times out also sets it (so a later pass does not hide the failure).
 // alpha_cutoff != 0: alpha mode -- pixels below the cutoff take no part in the diffusion, every output keeps its pixel's alpha.
@@ -147,39 +151,23 @@ enum { kDiffuseScan = 0, kDiffusePairs = 1, kDiffuseCells = 2 };
 constexpr uint32_t kDiffuseRing = 1024;
 size_t diffuse_ctl_bytes();
 uint32_t diffuse_grid(int route, uint32_t rows);
-// format (kmg_output_format): out holds RGBA8 words (0), or the labels as u8 (1) / u16 (2) -- k for a pixel alpha mode drops
-hipError_t launch_diffuse(int route, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out, void *erow, uint32_t parity,
-                          void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                          const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff = 0,
-                          int format = 0);
-// The other filters of kmg_diffusion (kmg_diffuse_wide.hip): launch_diffuse's arguments and meaning, except that erow holds
-// 4 x w packed error words -- slot `parity` (rows 2 parity, 2 parity + 1) = the errors of the row above the band and of the row
-// above that (zero for a first band); the band leaves its last two rows' errors in slot (parity + chunks) & 1.
-struct DiffuseFilter {
-    int32_t w[12];                 // kmg_diffusion_weights' order
-    uint32_t bias, magic;          // floor((S + D/2) / D) = umulhi(S + bias, magic) - 4096: bias = D/2 + 4096 D, magic = ceil(2^32 / D)
-    int skew;                      // columns a row lags the row above: 3 when the filter takes e(x + 2, .) of a row above, else 2
-};
-DiffuseFilter diffuse_filter(int filter);
-hipError_t launch_diffuse_wide(int route, const DiffuseFilter &f, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out,
-                               void *erow, uint32_t parity, void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k,
-                               const float *lut, const uint32_t *pal, const void *colour_labels, const uint16_t *sub_table,
-                               hipStream_t st, uint32_t alpha_cutoff, int format);
+// filter (kmg_diffusion): Floyd-Steinberg runs k_diffuse, the others k_diffuse_wide (kmg_diffuse_wide.hip), whose slots hold TWO
+// rows -- the errors of the row above the band and of the row above that -- and which leaves its last two rows' errors.
+// diffuse_erow_bytes(w): the size of erow for any filter; diffuse_slot_bytes(filter, w): the bytes of slot `parity` (at
+// erow + parity * that) which the caller zeroes before the first band of an image.
+size_t diffuse_erow_bytes(uint32_t w);
+size_t diffuse_slot_bytes(int filter, uint32_t w);
+hipError_t launch_diffuse(int route, int filter, const uint32_t *rgba, uint32_t w, uint32_t rows, void *out, int format, void *erow,
+                          uint32_t parity, void *ctl, uint32_t *sticky, const Centroid *cent, uint32_t k, const float *lut,
+                          const uint32_t *pal, const void *colour_labels, const uint16_t *sub_table, hipStream_t st, uint32_t alpha_cutoff);
 
-// ---- index output (kmg_output_format INDEX8 / INDEX16): the label of every pixel as u8 (wide = false) or u16 (wide = true);
-// alpha_cutoff != 0: k where the pixel's alpha is below it.  The same decisions as the RGBA8 launchers above.
-hipError_t launch_apply_index(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                              const float *lut, bool dither, float threshold, void *out, bool wide, hipStream_t st, uint32_t alpha_cutoff);
-hipError_t launch_dither_lists_index(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                                     const float *lut, float threshold, const uint8_t *lists, void *out, bool wide, hipStream_t st,
-                                     uint32_t alpha_cutoff);
-// kmg_index.hip: the replace pass through the colour cube's label tables (those launch_labels reads: the pair entries and u8
-// per-colour labels for k <= 256, the 8x8x8 / 4x4x4 summaries and u16 per-colour labels above)
+// kmg_index.hip, index formats only: the replace pass through the colour cube's label tables (those launch_labels reads: the pair
+// entries and u8 per-colour labels for k <= 256, the 8x8x8 / 4x4x4 summaries and u16 per-colour labels above)
 hipError_t launch_labels_index(const uint32_t *rgba, uint64_t n, const void *colour_labels, const uint16_t *sub_table, uint32_t k,
-                               void *out, bool wide, hipStream_t st, uint32_t alpha_cutoff);
-// kmg_index.hip: out[i] = labels[i] (u32 labels of a pass that ran with an identity palette) as u8 / u16, or k where alpha mode drops
-// the pixel
-hipError_t launch_narrow_index(const uint32_t *rgba, const uint32_t *labels, uint64_t n, uint32_t k, void *out, bool wide, hipStream_t st,
+                               void *out, int format, hipStream_t st, uint32_t alpha_cutoff);
+// kmg_index.hip, index formats only: out[i] = labels[i] (u32 labels of a pass that ran with an identity palette) as u8 / u16, or k
+// where alpha mode drops the pixel
+hipError_t launch_narrow_index(const uint32_t *rgba, const uint32_t *labels, uint64_t n, uint32_t k, void *out, int format, hipStream_t st,
                                uint32_t alpha_cutoff);
 
 // ---- error statistics (kmg_error.hip; kmg_error_stats of include/kmeans_hip.h): `stats` = 14 u64 the launch COMBINES into (sums

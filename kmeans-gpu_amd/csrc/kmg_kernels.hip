@@ -23,7 +23,8 @@
 
 namespace kmg {
 
-
+// kmg_dispatch.h includes nothing of the library and lists the output formats by value
+static_assert(KMG_FORMAT_RGBA8 == 0 && KMG_FORMAT_INDEX8 == 1 && KMG_FORMAT_INDEX16 == 2, "with_out_type / with_index_type");
 
 // ------------------------------------------------------------------------------------------
 // RGBA8 -> Lab  (rgb_to_lab.wgsl:66-80).  Only used by tests / callers that want Lab itself.
@@ -283,25 +284,14 @@ hipError_t launch_assign(const uint32_t *rgba, uint64_t n, const Centroid *cent,
     const bool chunked = k >= 32;   // the recovery step costs ~4 extra pairs per pixel
     size_t lds = sizeof(float4) * kpad + 256 * sizeof(float);
     if (partials) lds += sizeof(unsigned long long) * 4ull * k;
-#define KMG_ASSIGN(P, A, C)                                                                                    \
-    hipLaunchKernelGGL((k_assign<P, A, C>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, partials, aligned, AssignLoop())
-#define KMG_ASSIGN_W(P, C)                                                                                     \
-    hipLaunchKernelGGL((k_assign<P, true, C, false, true>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, partials, aligned, AssignLoop())
-#define KMG_ASSIGN_P(P)                                                                                        \
-    do {                                                                                                       \
-        if (partials && weighted) { if (chunked) KMG_ASSIGN_W(P, true); else KMG_ASSIGN_W(P, false); }         \
-        else if (partials) { if (chunked) KMG_ASSIGN(P, true, true); else KMG_ASSIGN(P, true, false); }        \
-        else          { if (chunked) KMG_ASSIGN(P, false, true); else KMG_ASSIGN(P, false, false); }           \
-    } while (0)
-    switch (assign_ppt(n)) {
-    case 1: KMG_ASSIGN_P(1); break;
-    case 2: KMG_ASSIGN_P(2); break;
-    case 4: KMG_ASSIGN_P(4); break;
-    default: KMG_ASSIGN_P(kAssignPPT); break;
-    }
-#undef KMG_ASSIGN_P
-#undef KMG_ASSIGN_W
-#undef KMG_ASSIGN
+    // weighted changes the sums only: without partials it selects nothing
+    with_value<1, 2, 4, kAssignPPT>(assign_ppt(n), [&](auto P) { with_bool(partials != nullptr, [&](auto A) { with_bool(chunked, [&](auto C) {
+        auto launch = [&](auto W) {
+            hipLaunchKernelGGL((k_assign<P(), A(), C(), false, W()>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, partials,
+                               aligned, AssignLoop());
+        };
+        if constexpr (A()) with_bool(weighted, launch); else launch(std::false_type{});
+    }); }); });
     return hipGetLastError();
 }
 
@@ -322,14 +312,9 @@ hipError_t launch_assign_loop(const uint32_t *rgba, uint64_t n, const Centroid *
     loop.acc_in = acc_in; loop.acc_out = acc_out; loop.acc_clear = acc_clear; loop.cent_out = cent_out;
     loop.n_converged = n_converged; loop.convergence = convergence; loop.do_update = do_update;
     int64_t *no_partials = nullptr;
-    if (weighted && k >= 32)
-        hipLaunchKernelGGL((k_assign<1, true, true, true, true>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, no_partials, aligned, loop);
-    else if (weighted)
-        hipLaunchKernelGGL((k_assign<1, true, false, true, true>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, no_partials, aligned, loop);
-    else if (k >= 32)
-        hipLaunchKernelGGL((k_assign<1, true, true, true>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, no_partials, aligned, loop);
-    else
-        hipLaunchKernelGGL((k_assign<1, true, false, true>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, no_partials, aligned, loop);
+    with_bool(k >= 32, [&](auto C) { with_bool(weighted, [&](auto W) {
+        hipLaunchKernelGGL((k_assign<1, true, C(), true, W()>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, labels, no_partials, aligned, loop);
+    }); });
     return hipGetLastError();
 }
 
@@ -860,8 +845,7 @@ hipError_t launch_init_pass(const uint32_t *rgba, uint64_t n, const float *lut, 
                             uint32_t j, float *dist, unsigned long long *key, uint64_t first_index, hipStream_t st, bool pick)
 {
     const uint32_t grid = init_pass_grid(n);
-    if (pick) hipLaunchKernelGGL(k_init_pass<true>, dim3(grid), dim3(kBlock), 0, st, rgba, n, lut, cent, j, dist, key, first_index);
-    else hipLaunchKernelGGL(k_init_pass<false>, dim3(grid), dim3(kBlock), 0, st, rgba, n, lut, cent, j, dist, key, first_index);
+    with_bool(pick, [&](auto P) { hipLaunchKernelGGL(k_init_pass<P()>, dim3(grid), dim3(kBlock), 0, st, rgba, n, lut, cent, j, dist, key, first_index); });
     return hipGetLastError();
 }
 
@@ -1079,62 +1063,24 @@ __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ r
     }
 }
 
-hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0,
-                        const Centroid *cent, uint32_t k, const float *lut, const uint32_t *pal,
-                        bool dither, float threshold, uint32_t *out, hipStream_t st, bool alpha)
+hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k, const float *lut,
+                        const uint32_t *pal, bool dither, float threshold, void *out, int format, hipStream_t st, uint32_t alpha_cutoff)
 {
     const uint64_t n = (uint64_t)w * rows;
     const uint64_t tiles = (n + (uint64_t)kBlock * kAssignPPT - 1) / ((uint64_t)kBlock * kAssignPPT);
     const uint32_t grid = (uint32_t)(tiles < 2048 ? (tiles ? tiles : 1) : 2048);
     const uint32_t kpad = (k + 3u) & ~3u;
-    const int aligned = ((reinterpret_cast<uintptr_t>(rgba) & 15u) == 0 &&
-                         (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
     const bool chunked = k >= 32;
     const size_t lds = sizeof(float4) * kpad + (256 + 16) * sizeof(float);
-#define KMG_APPLY(D, C, A)                                                                                      \
-    hipLaunchKernelGGL((k_apply<kAssignPPT, D, C, A, uint32_t>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, \
-                       row0, cent, k, lut, pal, threshold, out, aligned)
-    if (alpha) {
-        if (dither) { if (chunked) KMG_APPLY(true, true, true); else KMG_APPLY(true, false, true); }
-        else        { if (chunked) KMG_APPLY(false, true, true); else KMG_APPLY(false, false, true); }
-    } else {
-        if (dither) { if (chunked) KMG_APPLY(true, true, false); else KMG_APPLY(true, false, false); }
-        else        { if (chunked) KMG_APPLY(false, true, false); else KMG_APPLY(false, false, false); }
-    }
-#undef KMG_APPLY
-    return hipGetLastError();
-}
-
-template <typename OutT>
-static void launch_apply_index_t(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                                 const float *lut, bool dither, float threshold, OutT *out, hipStream_t st, uint32_t alpha_cutoff)
-{
-    const uint64_t n = (uint64_t)w * rows;
-    const uint64_t tiles = (n + (uint64_t)kBlock * kAssignPPT - 1) / ((uint64_t)kBlock * kAssignPPT);
-    const uint32_t grid = (uint32_t)(tiles < 2048 ? (tiles ? tiles : 1) : 2048);
-    const uint32_t kpad = (k + 3u) & ~3u;
-    const int flags = output_aligned<OutT>(rgba, out) | (int)((alpha_cutoff & 255u) << 8);
-    const bool chunked = k >= 32;
-    const size_t lds = sizeof(float4) * kpad + (256 + 16) * sizeof(float);
-#define KMG_APPLY(D, C, A)                                                                                  \
-    hipLaunchKernelGGL((k_apply<kAssignPPT, D, C, A, OutT>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, \
-                       row0, cent, k, lut, nullptr, threshold, out, flags)
-    if (alpha_cutoff) {
-        if (dither) { if (chunked) KMG_APPLY(true, true, true); else KMG_APPLY(true, false, true); }
-        else        { if (chunked) KMG_APPLY(false, true, true); else KMG_APPLY(false, false, true); }
-    } else {
-        if (dither) { if (chunked) KMG_APPLY(true, true, false); else KMG_APPLY(true, false, false); }
-        else        { if (chunked) KMG_APPLY(false, true, false); else KMG_APPLY(false, false, false); }
-    }
-#undef KMG_APPLY
-}
-
-hipError_t launch_apply_index(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                              const float *lut, bool dither, float threshold, void *out, bool wide, hipStream_t st, uint32_t alpha_cutoff)
-{
-    if (wide) launch_apply_index_t(rgba, w, rows, row0, cent, k, lut, dither, threshold, (uint16_t *)out, st, alpha_cutoff);
-    else launch_apply_index_t(rgba, w, rows, row0, cent, k, lut, dither, threshold, (uint8_t *)out, st, alpha_cutoff);
-    return hipGetLastError();
+    const bool known = with_out_type(format, [&](auto t) {
+        using OutT = typename decltype(t)::type;
+        const int flags = output_flags<OutT>(rgba, out, alpha_cutoff);
+        with_bool(dither, [&](auto D) { with_bool(chunked, [&](auto C) { with_bool(alpha_cutoff != 0, [&](auto A) {
+            hipLaunchKernelGGL((k_apply<kAssignPPT, D(), C(), A(), OutT>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut,
+                               kIndexOut<OutT> ? nullptr : pal, threshold, static_cast<OutT *>(out), flags);
+        }); }); });
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1300,8 +1246,7 @@ hipError_t launch_meld(const uint32_t *rgba, uint64_t n, const Centroid *cent, u
     const uint32_t grid = (uint32_t)(blocks < 8192 ? (blocks ? blocks : 1) : 8192);
     const uint32_t kpad = (k + 3u) & ~3u;
     const size_t lds = sizeof(float4) * kpad + (256 + 257) * sizeof(float);
-    if (alpha) hipLaunchKernelGGL(k_meld<true>, dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, masks, out);
-    else hipLaunchKernelGGL(k_meld<false>, dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, masks, out);
+    with_bool(alpha, [&](auto A) { hipLaunchKernelGGL(k_meld<A()>, dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, masks, out); });
     return hipGetLastError();
 }
 

@@ -202,10 +202,9 @@ hipError_t launch_lab_candidates(const Centroid *cent, uint32_t k, float thresho
     if (e != hipSuccess) return e;
     const uint32_t n_waves = ((reach.nL + kCellsPerWave - 1u) / kCellsPerWave) * reach.nA * reach.nB;
     const dim3 grid((n_waves + kBlock / 64 - 1) / (kBlock / 64));
-    if (two_closest && halves == 2u) hipLaunchKernelGGL((k_lab_candidates<true, 2>), grid, dim3(kBlock), 0, st, cent, k, reach, lists);
-    else if (two_closest) hipLaunchKernelGGL((k_lab_candidates<true, 1>), grid, dim3(kBlock), 0, st, cent, k, reach, lists);
-    else if (halves == 2u) hipLaunchKernelGGL((k_lab_candidates<false, 2>), grid, dim3(kBlock), 0, st, cent, k, reach, lists);
-    else hipLaunchKernelGGL((k_lab_candidates<false, 1>), grid, dim3(kBlock), 0, st, cent, k, reach, lists);
+    with_bool(two_closest, [&](auto T) { with_value<1, 2>((int)halves, [&](auto H) {
+        hipLaunchKernelGGL((k_lab_candidates<T(), H()>), grid, dim3(kBlock), 0, st, cent, k, reach, lists);
+    }); });
     return hipGetLastError();
 }
 
@@ -421,54 +420,28 @@ hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, 
                                const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, uint32_t *out,
                                hipStream_t st)
 {
-    return launch_dither_lists(rgba, w, rows, row0, cent, k, lut, pal, threshold, lists, out, st, false);
+    return launch_dither_lists(rgba, w, rows, row0, cent, k, lut, pal, threshold, lists, out, KMG_FORMAT_RGBA8, st, 0);
 }
 
 hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                               const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, uint32_t *out,
-                               hipStream_t st, bool alpha)
+                               const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, void *out, int format,
+                               hipStream_t st, uint32_t alpha_cutoff)
 {
     if (k > kLabListMaxK) return hipErrorInvalidValue;
     const uint64_t n = (uint64_t)w * rows;
     const uint64_t tiles = (n + kBlock * 4 - 1) / (kBlock * 4);
     const uint32_t grid = (uint32_t)(tiles < 8192 ? (tiles ? tiles : 1) : 8192);
-    const uint32_t halves = k > 256u ? 2u : 1u;
+    const int halves = k > 256u ? 2 : 1;
     const size_t lds = sizeof(float4) * 256 * halves + (256 + 16) * sizeof(float);
-    const int aligned = ((reinterpret_cast<uintptr_t>(rgba) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
-#define KMG_DL(H, A) hipLaunchKernelGGL((k_dither_lists<H, A, uint32_t>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut, \
-                                        pal, threshold, lists, out, aligned)
-    if (halves == 2u) { if (alpha) KMG_DL(2, true); else KMG_DL(2, false); }
-    else { if (alpha) KMG_DL(1, true); else KMG_DL(1, false); }
-#undef KMG_DL
-    return hipGetLastError();
-}
-
-template <typename OutT>
-static void launch_dither_lists_index_t(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                                        const float *lut, float threshold, const uint8_t *lists, OutT *out, hipStream_t st,
-                                        uint32_t alpha_cutoff)
-{
-    const uint64_t n = (uint64_t)w * rows;
-    const uint64_t tiles = (n + kBlock * 4 - 1) / (kBlock * 4);
-    const uint32_t grid = (uint32_t)(tiles < 8192 ? (tiles ? tiles : 1) : 8192);
-    const uint32_t halves = k > 256u ? 2u : 1u;
-    const size_t lds = sizeof(float4) * 256 * halves + (256 + 16) * sizeof(float);
-    const int flags = output_aligned<OutT>(rgba, out) | (int)((alpha_cutoff & 255u) << 8);
-#define KMG_DL(H, A) hipLaunchKernelGGL((k_dither_lists<H, A, OutT>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut, \
-                                        nullptr, threshold, lists, out, flags)
-    if (halves == 2u) { if (alpha_cutoff) KMG_DL(2, true); else KMG_DL(2, false); }
-    else { if (alpha_cutoff) KMG_DL(1, true); else KMG_DL(1, false); }
-#undef KMG_DL
-}
-
-hipError_t launch_dither_lists_index(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                                     const float *lut, float threshold, const uint8_t *lists, void *out, bool wide, hipStream_t st,
-                                     uint32_t alpha_cutoff)
-{
-    if (k > kLabListMaxK) return hipErrorInvalidValue;
-    if (wide) launch_dither_lists_index_t(rgba, w, rows, row0, cent, k, lut, threshold, lists, (uint16_t *)out, st, alpha_cutoff);
-    else launch_dither_lists_index_t(rgba, w, rows, row0, cent, k, lut, threshold, lists, (uint8_t *)out, st, alpha_cutoff);
-    return hipGetLastError();
+    const bool known = with_out_type(format, [&](auto t) {
+        using OutT = typename decltype(t)::type;
+        const int flags = output_flags<OutT>(rgba, out, alpha_cutoff);
+        with_value<1, 2>(halves, [&](auto H) { with_bool(alpha_cutoff != 0, [&](auto A) {
+            hipLaunchKernelGGL((k_dither_lists<H(), A(), OutT>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut,
+                               kIndexOut<OutT> ? nullptr : pal, threshold, lists, static_cast<OutT *>(out), flags);
+        }); });
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 #ifdef KMG_TOOLS
@@ -701,11 +674,10 @@ hipError_t launch_meld_lists(const uint32_t *rgba, uint64_t n, const Centroid *c
     const uint32_t grid = (uint32_t)(tiles < 8192 ? (tiles ? tiles : 1) : 8192);
     const uint32_t halves = k > 256u ? 2u : 1u;
     const size_t lds = sizeof(float4) * 256 * halves + (256 + 257) * sizeof(float);
-    const int aligned = ((reinterpret_cast<uintptr_t>(rgba) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
-#define KMG_ML(H, A) hipLaunchKernelGGL((k_meld_lists<H, A>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, lists, out, aligned)
-    if (halves == 2u) { if (alpha) KMG_ML(2, true); else KMG_ML(2, false); }
-    else { if (alpha) KMG_ML(1, true); else KMG_ML(1, false); }
-#undef KMG_ML
+    const int aligned = output_aligned<uint32_t>(rgba, out);
+    with_value<1, 2>((int)halves, [&](auto H) { with_bool(alpha, [&](auto A) {
+        hipLaunchKernelGGL((k_meld_lists<H(), A()>), dim3(grid), dim3(kBlock), lds, st, rgba, n, cent, k, lut, lists, out, aligned);
+    }); });
     return hipGetLastError();
 }
 

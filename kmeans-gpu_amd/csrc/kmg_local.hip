@@ -196,18 +196,12 @@ int frame_local_impl(kmg_processor *p, const uint8_t *d_src_rgba, const void *d_
     const uint64_t n = (uint64_t)width * rows;
     HIP_TRY(hipSetDevice(p->device));
     unsigned long long *info = reinterpret_cast<unsigned long long *>(d_info);
-    const bool u8 = format == KMG_FORMAT_INDEX8;
-    hipError_t e;
-    if (lossy)
-        e = u8 ? frame_local_typed<uint8_t, true>(d_src_rgba, d_index, d_palette_rgba, d_shown_rgba, d_held_rgba, d_delta, n, width, row0, k,
-                                                  tolerance, p->d_lut, info, st)
-               : frame_local_typed<uint16_t, true>(d_src_rgba, d_index, d_palette_rgba, d_shown_rgba, d_held_rgba, d_delta, n, width, row0, k,
-                                                   tolerance, p->d_lut, info, st);
-    else
-        e = u8 ? frame_local_typed<uint8_t, false>(nullptr, d_index, d_palette_rgba, d_shown_rgba, nullptr, d_delta, n, width, row0, k, 0u,
-                                                   p->d_lut, info, st)
-               : frame_local_typed<uint16_t, false>(nullptr, d_index, d_palette_rgba, d_shown_rgba, nullptr, d_delta, n, width, row0, k, 0u,
-                                                    p->d_lut, info, st);
+    hipError_t e = hipErrorInvalidValue;
+    if (!lossy) { d_src_rgba = nullptr; d_held_rgba = nullptr; tolerance = 0u; }                // (the exact rule reads none of them)
+    with_index_type(format, [&](auto t) { with_bool(lossy, [&](auto L) {
+        e = frame_local_typed<typename decltype(t)::type, L()>(d_src_rgba, d_index, d_palette_rgba, d_shown_rgba, d_held_rgba, d_delta, n, width,
+                                                               row0, k, tolerance, p->d_lut, info, st);
+    }); });
     HIP_TRY(e);
     return KMG_OK;
 }

@@ -189,8 +189,9 @@ int frame_delta_impl(kmg_processor *p, const void *d_index, void *d_canvas, uint
     const uint64_t n = (uint64_t)width * rows;
     HIP_TRY(hipSetDevice(p->device));
     unsigned long long *info = reinterpret_cast<unsigned long long *>(d_info);
-    if (format == KMG_FORMAT_INDEX8) HIP_TRY(frame_delta_typed<uint8_t>(d_index, d_canvas, d_delta, n, width, row0, k, info, st));
-    else HIP_TRY(frame_delta_typed<uint16_t>(d_index, d_canvas, d_delta, n, width, row0, k, info, st));
+    hipError_t e = hipErrorInvalidValue;
+    with_index_type(format, [&](auto t) { e = frame_delta_typed<typename decltype(t)::type>(d_index, d_canvas, d_delta, n, width, row0, k, info, st); });
+    HIP_TRY(e);
     return KMG_OK;
 }
 

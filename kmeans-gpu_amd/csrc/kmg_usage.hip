@@ -234,31 +234,23 @@ hipError_t remap_typed(const void *in, void *out, uint32_t width, uint32_t rows,
     return hipGetLastError();
 }
 
-template <typename TIn>
-hipError_t remap_bits(uint32_t bits, const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, const uint16_t *map,
-                      unsigned long long *bad, hipStream_t st)
-{
-    switch (bits) {
-    case 1: return remap_typed<TIn, 1u>(in, out, width, rows, k, map, bad, st);
-    case 2: return remap_typed<TIn, 2u>(in, out, width, rows, k, map, bad, st);
-    case 4: return remap_typed<TIn, 4u>(in, out, width, rows, k, map, bad, st);
-    case 8: return remap_typed<TIn, 8u>(in, out, width, rows, k, map, bad, st);
-    case 16: return remap_typed<TIn, 16u>(in, out, width, rows, k, map, bad, st);
-    }
-    return hipErrorInvalidValue;
-}
-
 }  // namespace
 
 hipError_t launch_index_usage(const void *index, bool wide, uint64_t n, uint32_t k, unsigned long long *usage, hipStream_t st)
 {
-    return wide ? usage_typed<uint16_t>(index, n, k, usage, st) : usage_typed<uint8_t>(index, n, k, usage, st);
+    hipError_t e = hipErrorInvalidValue;
+    with_index_type(wide, [&](auto t) { e = usage_typed<typename decltype(t)::type>(index, n, k, usage, st); });
+    return e;
 }
 
 hipError_t launch_index_remap(const void *in, bool wide, uint32_t width, uint32_t rows, uint32_t k, const uint16_t *map, uint32_t out_bits,
                               void *out, unsigned long long *bad, hipStream_t st)
 {
-    return wide ? remap_bits<uint16_t>(out_bits, in, out, width, rows, k, map, bad, st) : remap_bits<uint8_t>(out_bits, in, out, width, rows, k, map, bad, st);
+    hipError_t e = hipErrorInvalidValue;                              // (stays for out_bits outside 1 / 2 / 4 / 8 / 16)
+    with_index_type(wide, [&](auto t) { with_value<1, 2, 4, 8, 16>((int)out_bits, [&](auto B) {
+        e = remap_typed<typename decltype(t)::type, B()>(in, out, width, rows, k, map, bad, st);
+    }); });
+    return e;
 }
 
 namespace {

@@ -270,3 +270,95 @@ def test_dither_lists_with_equal_centroids_in_both_halves(oracle, procs):
     assert np.array_equal(got["scan"], want)
     bad = np.flatnonzero(got["table"].reshape(-1) != want.reshape(-1))
     assert bad.size == 0, (bad.size, bad[:4], got["table"].reshape(-1)[bad[:4]], want.reshape(-1)[bad[:4]])
+
+
+# ---- every instantiation and alignment branch of the launchers at a small size ------------------------------------------------
+# The route tests above leave gaps in the launchers' (format x alpha x route) products: their bands move the source and the output
+# off alignment TOGETHER, and the diffusion filters other than Floyd-Steinberg meet alpha mode in RGBA8 / INDEX8 at one k only
+# (tests/test_gpu_diffusion_filters.py).  Here: a 67 x 41 noise image with random alpha (2 747 pixels: no multiple of four, odd
+# width, three workgroups of k_apply's 1 024-pixel tiles), the source aligned and the output at its base AND one element in (bit 0
+# of the kernels' flag word 0 for the format's own vector store: 16 bytes RGBA8, 4 u8, 8 u16), k = 5 / 40 / 300 / 600 (unchunked,
+# chunked, two list halves and INDEX16 only, mask words), both forced strategies, cutoff 0 and 128, every format the k admits,
+# replace, dither, and diffusion under Floyd-Steinberg, Atkinson (skew 2) and Burkes (skew 3) -- against the oracle (replace,
+# dither) and the diffusion references.
+SW, SH = 67, 41
+ATKINSON, BURKES = 2, 3
+_small_want, _small_near = {}, {}
+
+
+def _small_image():
+    rng = np.random.default_rng(6741)
+    return rng.integers(0, 256, (SH, SW, 4), dtype=np.uint8)
+
+
+def _small_reference(oracle, img, cent, k, mode, f, cutoff):
+    """the RGBA8 bytes of (mode, filter, cutoff), alpha = the source's in alpha mode; computed once per k"""
+    import alpha_ref
+    import diffuse_ref
+    import diffusion_ref
+    import kmeans_gpu_amd as kg
+    key = (k, mode, f, cutoff)
+    if key not in _small_want:
+        keep = img[..., 3] >= cutoff
+        if mode != 3:
+            want = oracle.apply(img, cent, mode)
+        else:
+            if k not in _small_near:
+                _small_near[k] = diffuse_ref.Nearest(diffuse_ref.oracle_apply_replace(oracle, cent))
+            if f == 0:
+                want = alpha_ref.diffuse(img, None, cutoff, nearest=_small_near[k]) if cutoff else diffuse_ref.diffuse(img, None, nearest=_small_near[k])
+            else:
+                weights, divisor = kg.diffusion_weights(f)
+                want = diffusion_ref.diffuse(img, None, weights, divisor, keep=keep if cutoff else None, nearest=_small_near[k])
+        if cutoff:
+            want = alpha_ref.with_alpha(want, img)
+        _small_want[key] = want
+    return _small_want[key]
+
+
+def _small_run(torch, proc, d_in, cent, mode, fmt, offset):
+    """the call with the output `offset` elements into a buffer filled with 0x5A; nothing outside the image is written"""
+    n = SW * SH
+    if fmt is None:
+        buf = torch.full((n + 8, 4), 0x5A, dtype=torch.uint8, device="cuda")
+        size, view = 4, np.uint8
+    else:
+        buf = torch.full((n + 8,), 0x5A, dtype=torch.uint8 if fmt == FMT8 else torch.int16, device="cuda")
+        size, view = (1, np.uint8) if fmt == FMT8 else (2, np.uint16)
+    assert buf.data_ptr() % 16 == 0 and d_in.data_ptr() % 16 == 0
+    proc.apply(d_in.data_ptr(), SW, SH, 0, cent, mode, buf.data_ptr() + size * offset, torch.cuda.current_stream().cuda_stream, format=fmt)
+    torch.cuda.synchronize()
+    host = buf.cpu().numpy().view(view)
+    assert (host[:offset] == 0x5A).all() and (host[offset + n:] == 0x5A).all(), "written outside the image"
+    return host[offset:offset + n].reshape((SH, SW, 4) if fmt is None else (SH, SW))
+
+
+@pytest.mark.parametrize("strategy", ("scan", "table"))
+@pytest.mark.parametrize("k", (5, 40, 300, 600))
+def test_small_image_every_format_alpha_and_alignment(oracle, torch_cuda, procs, strategy, k):
+    torch = torch_cuda
+    set_strategy(strategy)
+    img = _small_image()
+    cent = _centroids(oracle, k)
+    P = oracle.lab_to_rgba8(cent[:, :3])
+    d_in = torch.from_numpy(img.reshape(-1, 4)).cuda()
+    try:
+        for mode, f in ((0, 0), (1, 0), (3, 0), (3, ATKINSON), (3, BURKES)):
+            for cutoff in (0, T):
+                proc = procs[cutoff]
+                proc.set_diffusion(f)
+                want = _small_reference(oracle, img, cent, k, mode, f, cutoff)
+                keep = img[..., 3] >= cutoff
+                for fmt in (None, FMT8, FMT16) if k <= 255 else (None, FMT16):
+                    for offset in (0, 1):
+                        got = _small_run(torch, proc, d_in, cent, mode, fmt, offset)
+                        where = f"mode {mode}, filter {f}, cutoff {cutoff}, format {fmt}, output offset {offset}"
+                        if fmt is None:
+                            assert np.array_equal(got, want), where
+                            continue
+                        assert np.array_equal(got == k, ~keep), where + ": index k exactly where alpha is below the cutoff"
+                        assert int(got[keep].max()) < k, where
+                        assert np.array_equal(P[got[keep]][:, :3], want[keep][:, :3]), where + ": P[index] is not the reference's RGB"
+    finally:
+        for proc in procs.values():
+            proc.set_diffusion(0)
