@@ -6,6 +6,7 @@ error_ref.q_of / q_table (the oracle's Lab on the grid q = rint(64 Lab)) and num
   combine           two records into one (sums added, minima minned, maxima maxed)
   replay            an encoder and a viewer at once: exact and lossy frames over one canvas, with -- per pixel -- the number of the
                     frame that wrote it (whose exact index it shows)
+  replay_from       the same from a caller's canvas and held source, with the full-on-clear rule as a switch
 
 A record is 8 exact integers: changed, cleared, x0, y0, x1, y1, held, held_sse."""
 import numpy as np
@@ -115,12 +116,21 @@ def replay(oracle, frames, maps, k, tolerances, use_table=None):
     Returns one dict per frame: map (what the call writes), record (6 or 8 integers), is_full, canvas (what a viewer shows after
     the frame), held (the held source), origin (per pixel: the number of the frame that wrote it -- whose exact index it shows
     and whose source is its held source; -1: none yet)"""
+    if not len(maps):
+        return []
+    return replay_from(oracle, np.full_like(np.asarray(maps[0]), k), np.zeros_like(np.asarray(frames[0], np.uint8)), frames, maps, k, tolerances,
+                       True, use_table)
+
+
+def replay_from(oracle, canvas, held, frames, maps, k, tolerances, full_on_clear=True, use_table=None):
+    """the same rule from a caller's canvas (h, w) and held source (h, w, 4), neither of which is modified; full_on_clear False: no
+    frame is sent in full, a frame that clears a pixel leaves what the pass itself leaves (kmg_dev_frame_delta_clip without
+    KMG_CLIP_FULL_ON_CLEAR)"""
     import sequence_ref
-    out, canvas, held, origin = [], None, None, None
+    canvas, held = np.array(canvas), np.array(held, np.uint8)
+    out, origin = [], np.full(canvas.shape, -1, np.int64)
     for t, (f, I, tol) in enumerate(zip(frames, maps, tolerances)):
         f, I = np.asarray(f, np.uint8), np.asarray(I)
-        if canvas is None:
-            canvas, held, origin = np.full_like(I, k), np.zeros_like(f), np.full(I.shape, -1, np.int64)
         if tol is None:
             d, _, rec = sequence_ref.delta(I, canvas, k)
             sent = np.ones(I.shape, bool)                            # an exact frame leaves the canvas equal to its map everywhere
@@ -128,7 +138,7 @@ def replay(oracle, frames, maps, k, tolerances, use_table=None):
         else:
             sent = ~held_mask(oracle, f, I, canvas, held, k, tol, use_table)[0]   # written now: the exact index, anchored at this frame
             d, canvas, held, rec = hold(oracle, f, I, canvas, held, k, tol, use_table=use_table)
-        full = rec[1] > 0
+        full = bool(full_on_clear) and rec[1] > 0
         if full:                                                     # "over" cannot show a pixel that turns transparent
             canvas, held, sent = I.copy(), f.copy(), np.ones(I.shape, bool)
         origin = np.where(sent, t, origin)

@@ -1,7 +1,11 @@
 """Lossy delta frames on the device (include/kmeans_hip.h at kmg_dev_frame_delta_lossy), against tests/hold_ref.py:
   1. k_frame_hold bit for bit -- delta map, canvas, held source and all eight record fields: shapes around the 4-pixel group, the
      1024-pixel tile and the grid cap, both index types, pointers that allow the 16-byte accesses and pointers that force the
-     per-pixel path, sentinels around every buffer, five patterns, and a frame in two bands on two streams in both orders;
+     per-pixel path, sentinels around every buffer, five patterns, and a frame in two bands on two streams in both orders; the
+     per-lane (x, y) cursor where a workgroup walks several tiles (tests/tile_walk.py, tests/probe_run.py): one-pixel frames, pairs,
+     a clear and planted held pixels whose record is known by construction, in bands of 4200, 4100, 2099, 4102, 4102 and 2049 tiles
+     of 1024 pixels of the widths 1000 (step_y = 1), 1024 (step_x = 0), 1023, 300 (step_y = 3), 3 and 1 (both formats, all six),
+     and as the second of two bands with an odd row0;
   2. refusals, after each of which the processor still works;
   3. the sequence layer: noise under the tolerance in three modes and both formats, exact and lossy frames alternating on one output
      (the held source and the frame buffer swap), a pixel that turns transparent, begin / end / begin at another size;
@@ -13,6 +17,8 @@ import numpy as np
 import pytest
 
 import alpha_ref
+import probe_run
+import tile_walk
 import hold_ref as H
 import sequence_ref
 from test_hold_contract import check_invariant
@@ -214,6 +220,16 @@ def test_hold_kernel_many_tiles_per_workgroup(torch_cuda, processor, oracle, fmt
         dev = _Dev(torch_cuda, fmt, width * rows, offs)
         _run(torch_cuda, processor, dev, case, k, width, rows, fmt)
         _check(dev, case, want, width, rows, fmt, f"{name}, offsets {offs}")
+
+
+PROBE_BANDS = [(name, 0) for name, _, _, _ in tile_walk.shapes(1024)] + [("below", tile_walk.BAND_ROW0)]
+
+
+@pytest.mark.parametrize("fmt", [FMT8, FMT16])
+@pytest.mark.parametrize("name,row0", PROBE_BANDS)
+def test_hold_box_of_single_pixels_over_several_tiles_per_workgroup(torch_cuda, processor, oracle, fmt, name, row0):
+    _, width, rows, per = next(s for s in tile_walk.shapes(1024) if s[0] == name)
+    probe_run.drive(probe_run.HoldState(torch_cuda, processor, oracle, fmt, width, rows), per, row0)
 
 
 def test_tolerance_zero_runs_the_kernel(torch_cuda, processor, oracle):

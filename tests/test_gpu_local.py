@@ -3,7 +3,11 @@
   1. k_frame_local bit for bit -- delta map, shown words, held source and every record field: widths and rows around the 4-pixel
      group and the 1024-pixel tile, both index types at their smallest and largest k, indices above k, a palette with duplicate
      entries and a zero word, every buffer on the vector route and at element offsets 1..3 (the per-pixel route), sentinels around
-     every buffer; three uneven bands in reverse order on two streams; a band with several tiles per workgroup;
+     every buffer; three uneven bands in reverse order on two streams; a band with several tiles per workgroup; the per-lane (x, y)
+     cursor where a workgroup walks several tiles (tests/tile_walk.py, tests/probe_run.py): one-pixel frames, pairs, a clear and
+     planted held pixels whose record is known by construction, exact and lossy, in bands of 4200, 4100, 2099, 4102, 4102 and 2049
+     tiles of 1024 pixels of the widths 1000 (step_y = 1), 1024 (step_x = 0), 1023, 300 (step_y = 3), 3 and 1 (both formats, all
+     six), and as the second of two bands with an odd row0;
   2. the same-palette equivalence with kmg_dev_frame_delta / _lossy on the device, at three tolerances;
   3. a ten-frame random walk, exact and lossy frames alternating, a new palette per frame;
   4. the sequence layer: cold frames against kmg_reduce_indexed, delta frames against the model and the replay, warm frames against
@@ -18,7 +22,9 @@ import pytest
 import fixed_ref
 import hold_ref
 import local_ref as R
+import probe_run
 import sequence_ref
+import tile_walk
 
 pytestmark = pytest.mark.gpu
 
@@ -223,6 +229,17 @@ def test_more_tiles_than_workgroups(torch_cuda, processor, oracle, fmt):
         _run(torch_cuda, processor, dev, case, k, width, rows, fmt, tol)
         _check(dev, case, want, k, width, rows, fmt, tol is not None, f"tolerance {tol}")
         assert want[3][0] > 0
+
+
+PROBE_BANDS = [(name, 0) for name, _, _, _ in tile_walk.shapes(1024)] + [("below", tile_walk.BAND_ROW0)]
+
+
+@pytest.mark.parametrize("lossy", [False, True])
+@pytest.mark.parametrize("fmt", [FMT8, FMT16])
+@pytest.mark.parametrize("name,row0", PROBE_BANDS)
+def test_local_box_of_single_pixels_over_several_tiles_per_workgroup(torch_cuda, processor, oracle, fmt, name, row0, lossy):
+    _, width, rows, per = next(s for s in tile_walk.shapes(1024) if s[0] == name)
+    probe_run.drive(probe_run.LocalState(torch_cuda, processor, oracle, fmt, width, rows, lossy), per, row0)
 
 
 @pytest.mark.parametrize("fmt", [FMT8, FMT16])

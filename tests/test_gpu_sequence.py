@@ -1,7 +1,11 @@
 """Frame sequences on the device (include/kmeans_hip.h at kmg_sequence), against tests/sequence_ref.py:
   1. k_frame_delta bit for bit: shapes around the 16-byte chunk, the 256-chunk tile and the grid cap, both index types, pointers
      1 - 3 elements into sentinel-filled buffers (apart: the element-wise path; together: the vector path with a partial first
-     chunk), four change patterns, and a frame in two bands combined in both orders;
+     chunk), four change patterns, and a frame in two bands combined in both orders; the per-lane (x, y) cursor where a workgroup
+     walks several tiles (tests/tile_walk.py, tests/probe_run.py): one-pixel frames whose record is known by construction, in bands
+     of 4200, 4100, 2101 (INDEX16: 2100), 4102, 4102 and 2049 tiles (tile = 4096 elements INDEX8, 2048 INDEX16) of the widths 1000 tile / 1024
+     (step_y = 1), tile (step_x = 0), tile - 1, 300 tile / 1024 (step_y = 3), 3 and 1 (both formats, all six), behind a partial
+     first chunk, and as the second of two bands with an odd row0;
   2. refusals, after each of which the processor still works;
   3. the shared palette: one frame = kmg_palette / kmg_reduce_indexed, frames of different sizes, alpha mode, the colour-table
      strategy on a large working sequence, many re-allocations of W -- float bit patterns, under both strategies;
@@ -14,6 +18,8 @@ import numpy as np
 import pytest
 
 import alpha_ref
+import probe_run
+import tile_walk
 import sequence_ref as R
 from conftest import set_strategy
 from test_sequence_contract import read_apng
@@ -136,6 +142,20 @@ def test_delta_kernel(torch_cuda, processor, fmt, width, rows):
 @pytest.mark.parametrize("fmt", [FMT8, FMT16])
 def test_delta_kernel_many_tiles_per_workgroup(torch_cuda, processor, fmt):
     _delta_cases(torch_cuda, processor, fmt, MANY_TILES[0], MANY_TILES[1], [(3, 3, 3)], ("corners", "random"))
+
+
+PROBE_BANDS = [(name, 0, 0) for name, _, _, _ in tile_walk.shapes(1024)] + [("below", 3, 0), ("below", 0, tile_walk.BAND_ROW0)]
+
+
+@pytest.mark.parametrize("fmt", [FMT8, FMT16])
+@pytest.mark.parametrize("name,offs,row0", PROBE_BANDS)
+def test_delta_box_of_single_pixels_over_several_tiles_per_workgroup(torch_cuda, processor, fmt, name, offs, row0):
+    """offs: elements the three pointers lie past a 16-byte boundary (3: a partial first chunk); row0: the band starts there"""
+    tile = tile_walk.tile_elems("delta", 1 if fmt == FMT8 else 2)
+    _, width, rows, per = next(s for s in tile_walk.shapes(tile) if s[0] == name)
+    state = probe_run.DeltaState(torch_cuda, processor, None, fmt, width, rows, offs)
+    assert state.shift(0) == offs
+    probe_run.drive(state, per, row0)
 
 
 def test_delta_refusals(torch_cuda, processor):
