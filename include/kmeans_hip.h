@@ -103,6 +103,37 @@ typedef enum kmg_diffusion {
     KMG_DIFFUSION_COUNT = 8
 } kmg_diffusion;
 
+/* The threshold map and the strength of KMG_MODE_DITHER (kmg_processor_set_dither[_custom]; the other modes ignore them).  A map is
+ * mw x mh levels l(x, y), each a uint16_t below n_levels; mw and mh are powers of two in 1 .. 64, independent of each other, and
+ * 1 <= n_levels <= 65536.  For the image pixel (x, y) -- y the image row, so a band starting at row0 reads row row0 + its own --
+ *   v   = (float)l(x mod mw, y mod mh) / (float)n_levels - 0.5f     (on the host, once per map, IEEE fp32: one correctly rounded
+ *                                                                     division, then one subtraction)
+ *   t   = threshold * strength                                       (threshold = palette diameter / sqrt(k) as before; fp32, one
+ *                                                                     rounding)
+ *   off = t * v                                                      (fp32, no contraction)
+ *   adjusted = (L + off, a + off, b + off)
+ * and then mix_colors.wgsl:73-80 as before: the scan starts at the sentinel (10000, 10000, 10000), whose index is k, and k = 1
+ * behaves as KMG_MODE_REPLACE.  With the reference's matrix, n_levels = 16 and strength 1.0f this is the reference's arithmetic
+ * operation for operation (threshold * 1.0f is exact, M / 16 - 0.5 is what it computes): KMG_DITHER_BAYER4 at strength 1, the
+ * default, writes the bytes this library wrote before it had maps.
+ *   KMG_DITHER_BAYER4    the reference's 4 x 4 matrix (mix_colors.wgsl:14-17), n_levels = 16
+ *   KMG_DITHER_BAYER2 / BAYER8 / BAYER16   the Bayer recursion M2 = [[0, 2], [3, 1]], M2n = [[4M, 4M + 2], [4M + 3, 4M + 1]]
+ *                        (which also gives the reference's matrix), n_levels = side^2
+ *   KMG_DITHER_BLUE64    a 64 x 64 void-and-cluster (blue-noise) map, a permutation of 0 .. 4095, n_levels = 4096
+ *   KMG_DITHER_CUSTOM    the caller's own map (kmg_processor_set_dither_custom)
+ * kmg_dither_map_values returns the table of a built-in map.  strength is finite and in [0, 4].
+ * The kmg_group_* calls in KMG_MODE_DITHER refuse a member processor whose choice is not the default (KMG_ERR_INVALID_ARGUMENT),
+ * as they refuse alpha weighting. */
+typedef enum kmg_dither_map {
+    KMG_DITHER_BAYER4 = 0,
+    KMG_DITHER_BAYER2 = 1,
+    KMG_DITHER_BAYER8 = 2,
+    KMG_DITHER_BAYER16 = 3,
+    KMG_DITHER_BLUE64 = 4,
+    KMG_DITHER_CUSTOM = 5,
+    KMG_DITHER_COUNT = 6
+} kmg_dither_map;
+
 /* Output format of the output passes (kmg_apply_plan_create_format, kmg_dev_apply_format, kmg_find_indexed, kmg_reduce_indexed).
  * KMG_FORMAT_RGBA8 is the RGBA8 image every other call writes: the same bytes.  The index formats write one uint8_t / uint16_t
  * per pixel, tightly packed, row-major: the label i the mode picks for the pixel -- the very label whose palette bytes the RGBA8
@@ -265,6 +296,23 @@ KMG_API int kmg_processor_set_diffusion(kmg_processor *p, int filter);
 /* the table at kmg_diffusion (no device needed): weights points to 12 values, [0..1] row 0 (dx = +1, +2), [2..6] row 1 and [7..11]
  * row 2 (dx = -2 .. +2).  A NULL pointer or an unknown filter: KMG_ERR_INVALID_ARGUMENT, nothing written                          */
 KMG_API int kmg_diffusion_weights(int filter, int32_t *weights, int32_t *divisor);
+/* kmg_dither_map of a live processor: a built-in threshold map and the strength of the KMG_MODE_DITHER output from now on.  It is
+ * read where the diffusion filter is read, when an apply plan is made: a plan keeps a copy of its map and strength for all its
+ * runs, every call that dithers (kmg_find, kmg_reduce, their _indexed and _batch forms, kmg_dev_apply[_format],
+ * kmg_reduce_quality[_batch], the sequence calls) follows it, and kmg_sequence_output_begin[_local] fixes it for the open output,
+ * single frames and clips alike.  A plan whose device cannot hold the centroid table and the map in one workgroup's LDS (k close
+ * to KMG_MAX_K with a 64 x 64 map on a device with 64 KiB) is KMG_ERR_UNSUPPORTED.
+ * NULL, an unknown map, KMG_DITHER_CUSTOM, or a strength that is not finite or outside [0, 4]: KMG_ERR_INVALID_ARGUMENT, nothing
+ * changes                                                                                                                        */
+KMG_API int kmg_processor_set_dither(kmg_processor *p, int map, float strength);
+/* the same with the caller's own map: levels points to width x height values, row-major, which are copied.  Also refused
+ * (KMG_ERR_INVALID_ARGUMENT, nothing changes): a side that is 0, above 64 or not a power of two, n_levels of 0 or above 65536, a
+ * level that is not below n_levels                                                                                                */
+KMG_API int kmg_processor_set_dither_custom(kmg_processor *p, const uint16_t *levels, uint32_t width, uint32_t height, uint32_t n_levels,
+                                            float strength);
+/* the table of a built-in map (no device needed): levels points to room for 4096 values and receives width x height of them,
+ * row-major.  A NULL pointer, an unknown map or KMG_DITHER_CUSTOM: KMG_ERR_INVALID_ARGUMENT, nothing written                       */
+KMG_API int kmg_dither_map_values(int map, uint32_t *width, uint32_t *height, uint32_t *n_levels, uint16_t *levels);
 /* KMG_WEIGHT_*: whether the palette step weighs a pixel by its alpha byte, see above                                              */
 KMG_API int kmg_processor_set_weighting(kmg_processor *p, int weighting);
 /* sets (n > 0: copies n x 4 bytes) or clears (n = 0) the processor's fixed colours, see above                                     */

@@ -141,6 +141,11 @@ struct kmg_apply_plan {
     int filter = KMG_DIFFUSION_FLOYD_STEINBERG;   // kmg_processor_set_diffusion when the plan was made (KMG_MODE_DIFFUSE reads it)
     bool dither = false;
     float thr = 0.0f;
+    // kmg_processor_set_dither[_custom] when the plan was made (KMG_MODE_DITHER reads it): null = the default, the kernels that carry
+    // the reference's matrix; else the plan's copy of the map, its v in the scratch block (d_v) and t = thr * strength
+    DitherPtr choice;
+    float *d_v = nullptr;
+    float t = 0.0f;
     Route route = Route::kScan;
     ArenaGuard arena;
     std::vector<uint8_t> staged;        // host copy of the tables: lives as long as the asynchronous upload may
@@ -214,7 +219,8 @@ static RouteScratch route_scratch(Route route, uint32_t k, bool index_format)
 }
 
 static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, uint64_t n_pixels_hint, void *stream,
-                       uint32_t alpha_cutoff, kmg_apply_plan **out, int format = KMG_FORMAT_RGBA8, int filter = -1)
+                       uint32_t alpha_cutoff, kmg_apply_plan **out, int format = KMG_FORMAT_RGBA8, int filter = -1,
+                       const DitherPtr *dither = nullptr)
 {
     if (!p || !c4 || !out || k == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply_plan arguments");
     *out = nullptr;
@@ -241,13 +247,24 @@ static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, 
     }
     pl->dither = (mode == KMG_MODE_DITHER) && k > 1;                   // mix_colors.wgsl:104-108
     pl->thr = pl->dither ? dither_threshold(c4, k) : 0.0f;
+    if (pl->dither) pl->choice = dither ? *dither : dither_snapshot(p);
+    const DitherChoice *map = pl->choice.get();
+    const size_t map_bytes = map ? sizeof(float) * map->v.size() : 0u;
+    if (map) {
+        volatile float t = pl->thr * map->strength;                   // fp32, one rounding
+        pl->t = t;
+        if (apply_map_lds_bytes(k, (uint32_t)map->v.size()) > device_info().lds_max)
+            return fail(KMG_ERR_UNSUPPORTED, "k = %u centroids and a %u x %u dither map need %zu bytes of LDS, the device gives a workgroup %zu", k,
+                        map->mw, map->mh, apply_map_lds_bytes(k, (uint32_t)map->v.size()), device_info().lds_max);
+    }
 
     // which route (by the number of pixels the plan is made for), and the scratch it needs: one block per plan
     const bool mask_words_only = (p->strategy.load(std::memory_order_relaxed) & KMG_STRATEGY_MASK_WORDS) != 0;
-    pl->route = apply_route(mode, k, n_pixels_hint, forced_strategy(p), mask_words_only);
+    pl->route = apply_route_mapped(map != nullptr, mode, k, n_pixels_hint, forced_strategy(p), mask_words_only);
     const RouteScratch scratch = route_scratch(pl->route, k, format != KMG_FORMAT_RGBA8);
     const size_t cent_bytes = sizeof(Centroid) * k, pal_bytes = sizeof(uint32_t) * (k + 1);
-    const size_t tables_bytes = cent_bytes + pal_bytes * (scratch.ident ? 2u : 1u);
+    const size_t ident_bytes = scratch.ident ? pal_bytes : 0u;
+    const size_t tables_bytes = cent_bytes + pal_bytes + ident_bytes + map_bytes;   // (the map's v last: 4-byte aligned like the palette)
     size_t need = ArenaGuard::padded(tables_bytes);
     for (const size_t bytes : scratch.parts) need += ArenaGuard::padded(bytes);
     ArenaGuard &arena = pl->arena;
@@ -263,6 +280,10 @@ static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, 
     Centroid *d_cent = pl->d_cent = (Centroid *)arena.take(tables_bytes);
     pl->d_pal = (uint32_t *)((uint8_t *)d_cent + cent_bytes);
     if (scratch.ident) pl->d_ident = pl->d_pal + (k + 1);
+    if (map) {
+        memcpy(pl->staged.data() + cent_bytes + pal_bytes + ident_bytes, map->v.data(), map_bytes);
+        pl->d_v = (float *)((uint8_t *)d_cent + cent_bytes + pal_bytes + ident_bytes);
+    }
     void *part[4] = {nullptr, nullptr, nullptr, nullptr};
     for (size_t i = 0; i < scratch.parts.size(); ++i) part[i] = arena.take(scratch.parts[i]);
     pl->aux = part[0];
@@ -277,7 +298,10 @@ static int plan_create(kmg_processor *p, const float *c4, uint32_t k, int mode, 
     case Route::kDitherLists:
         // candidate lists per cell of a grid over Lab, then a scan of the pixel's candidates only (meld: whatever can be one of the
         // two closest; its threshold is 0)
-        HIP_TRY(launch_lab_candidates(d_cent, k, pl->thr, mode == KMG_MODE_MELD, (uint8_t *)part[0], st));
+        // (a map: the reach of its own offsets t v, for speed only)
+        if (map) HIP_TRY(launch_lab_candidates_range(d_cent, k, fminf(pl->t * map->vmin, pl->t * map->vmax), fmaxf(pl->t * map->vmin, pl->t * map->vmax),
+                                                     false, (uint8_t *)part[0], st));
+        else HIP_TRY(launch_lab_candidates(d_cent, k, pl->thr, mode == KMG_MODE_MELD, (uint8_t *)part[0], st));
         break;
     case Route::kMeldMasks:
         // large image: per colour cell, the centroids that can be one of a pixel's two closest
@@ -378,6 +402,15 @@ uint32_t kmg::apply_plan_cutoff(const kmg_apply_plan *pl) { return pl->alpha_cut
 
 int kmg::apply_plan_filter(const kmg_apply_plan *pl) { return pl->filter; }
 
+const DitherPtr &kmg::apply_plan_dither(const kmg_apply_plan *pl) { return pl->choice; }
+
+// the plan's map as its kernels take it
+static DitherMapDev plan_map(const kmg_apply_plan *pl)
+{
+    const DitherChoice &c = *pl->choice;
+    return {pl->d_v, c.mw - 1u, c.mh - 1u, (uint32_t)__builtin_ctz(c.mw)};
+}
+
 // kmg_dev_apply and kmg_apply_plan_status: did any diffusion run of the plan time out?  (Read after the last run has completed.)
 static int diffuse_status(kmg_apply_plan *pl)
 {
@@ -427,7 +460,8 @@ static int run_band(kmg_apply_plan *pl, const uint32_t *src, uint32_t w, uint32_
     hipError_t e = hipSuccess;
     switch (pl->route) {
     case Route::kScan:
-        e = launch_apply(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->dither, pl->thr, d_out, pl->format, st, cutoff);
+        if (pl->choice) e = launch_apply_map(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->t, plan_map(pl), d_out, pl->format, st, cutoff);
+        else e = launch_apply(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->dither, pl->thr, d_out, pl->format, st, cutoff);
         break;
     case Route::kReplaceTable:
         if (index) e = launch_labels_index(src, n_px, pl->aux, pl->sub, k, d_out, pl->format, st, cutoff);
@@ -435,7 +469,9 @@ static int run_band(kmg_apply_plan *pl, const uint32_t *src, uint32_t w, uint32_
             e = launch_alpha_merge(src, out, n_px, st);
         break;
     case Route::kDitherLists:
-        e = launch_dither_lists(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->thr, (const uint8_t *)pl->aux, d_out, pl->format, st, cutoff);
+        if (pl->choice) e = launch_dither_lists_map(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->t, plan_map(pl), (const uint8_t *)pl->aux,
+                                                    d_out, pl->format, st, cutoff);
+        else e = launch_dither_lists(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->thr, (const uint8_t *)pl->aux, d_out, pl->format, st, cutoff);
         break;
     case Route::kDitherMasks:
         e = run_dither_masks(pl, src, w, rows, row0, d_out, st);
@@ -485,13 +521,13 @@ try {
 KMG_ABI_CATCH_VOID
 
 int kmg::dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, const float *c4, uint32_t k, int mode,
-                   uint8_t *d_out, void *stream, uint32_t alpha_cutoff, int format, int filter)
+                   uint8_t *d_out, void *stream, uint32_t alpha_cutoff, int format, int filter, const DitherPtr *dither)
 {
     if (!p || !d_rgba || !d_out || !c4 || !w || !rows || k == 0)
         return fail(KMG_ERR_INVALID_ARGUMENT, "bad apply arguments");
     if ((uint64_t)w * rows > 0xFFFFFFFFull) return fail(KMG_ERR_UNSUPPORTED, "band has more than 2^32-1 pixels");
     kmg_apply_plan *pl = nullptr;
-    KMG_TRY(plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, alpha_cutoff, &pl, format, filter));
+    KMG_TRY(plan_create(p, c4, k, mode, (uint64_t)w * rows, stream, alpha_cutoff, &pl, format, filter, dither));
     // (diffusion: the band is an image of its own -- the plan is new, so its first run starts from a zero error row)
     int rc = kmg_apply_plan_run(pl, d_rgba, w, rows, mode == KMG_MODE_DIFFUSE ? 0u : row0, d_out, stream);
     const hipError_t e2 = hipStreamSynchronize(S(stream));            // the call returns when the band is written; the block is idle again

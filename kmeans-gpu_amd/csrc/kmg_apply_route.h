@@ -85,6 +85,15 @@ inline Route apply_route(int mode, uint32_t k, uint64_t n_pixels_hint, int force
     return Route::kScan;
 }
 
+// A plan whose dither choice is not the default (kmg_processor_set_dither[_custom]) never takes the mask words --
+// their records are per (cell, index of the reference's 4 x 4 matrix) --: it scans instead, above k = 512 as under
+// KMG_STRATEGY_MASK_WORDS.  The candidate lists are over Lab itself and serve any map.
+inline Route apply_route_mapped(bool map_choice, int mode, uint32_t k, uint64_t n_pixels_hint, int forced, bool mask_words)
+{
+    const Route route = apply_route(mode, k, n_pixels_hint, forced, mask_words);
+    return map_choice && route == Route::kDitherMasks ? Route::kScan : route;
+}
+
 // Which images of a batch join the batched output launch (kmg_batch_apply.hip): replace or dither, and the image's
 // own plan would scan all centroids per pixel -- the batched launch then does the same work with one launch and no plan build.
 // Every other image (meld, diffusion, a table, lists or mask-word route, a forced KMG_STRATEGY_TABLE) keeps its per-image pass.

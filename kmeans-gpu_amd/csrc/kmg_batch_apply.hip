@@ -183,10 +183,14 @@ int batch_apply_run(kmg_processor *p, const uint32_t *idx, uint32_t m, const uin
 
 int kmg::apply_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
                             const float *c4, const size_t *at, const uint32_t *ks, bool shared, int mode, int format, uint32_t cutoff,
-                            void *const *d_out, kmg_batch_apply_report *report, hipStream_t st, int filter)
+                            void *const *d_out, kmg_batch_apply_report *report, hipStream_t st, int filter, const DitherPtr *dither)
 {
     // the diffusion filter: the processor's switch as it is when the call starts, for every per-image pass of the call
     if (filter < 0) filter = p->diffusion.load(std::memory_order_relaxed);
+    // the dither choice likewise.  The batched kernel carries the reference's matrix: with any other choice the dither images take
+    // their own pass, as meld and diffusion images do (a batched map kernel: DESIGN.md 7)
+    const DitherPtr choice = dither ? *dither : dither_snapshot(p);
+    const bool mapped = mode == KMG_MODE_DITHER && choice != nullptr;
     // which images join a launch (kmg_apply_route.h), each asked with its own k: the others take their own output pass, after the
     // launches are on their way.  The chunked scan is a launch's: the joined images below k = 32 go out as one chain, the others
     // as a second.
@@ -194,7 +198,7 @@ int kmg::apply_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *
     const bool mask_words_only = (p->strategy.load(std::memory_order_relaxed) & KMG_STRATEGY_MASK_WORDS) != 0;
     std::vector<uint32_t> joined[2], alone;
     for (uint32_t i = 0; i < n_images; ++i)
-        (batch_apply_joins(mode, ks[i], (uint64_t)widths[i] * heights[i], forced, mask_words_only, n_images) ? joined[ks[i] >= 32u ? 1 : 0] : alone)
+        (!mapped && batch_apply_joins(mode, ks[i], (uint64_t)widths[i] * heights[i], forced, mask_words_only, n_images) ? joined[ks[i] >= 32u ? 1 : 0] : alone)
             .push_back(i);
     ArenaGuard blk[2];
     uint32_t launches = 0;
@@ -203,7 +207,7 @@ int kmg::apply_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *
             KMG_TRY_DRAIN(st, batch_apply_run(p, joined[c].data(), (uint32_t)joined[c].size(), d_src, widths, heights, c4, at, ks, shared, mode,
                                               format, cutoff, d_out, &launches, &blk[c], st));
     for (const uint32_t i : alone)
-        KMG_TRY_DRAIN(st, dev_apply(p, d_src[i], widths[i], heights[i], 0, c4 + at[i], ks[i], mode, (uint8_t *)d_out[i], st, cutoff, format, filter));
+        KMG_TRY_DRAIN(st, dev_apply(p, d_src[i], widths[i], heights[i], 0, c4 + at[i], ks[i], mode, (uint8_t *)d_out[i], st, cutoff, format, filter, &choice));
     HIP_TRY(hipStreamSynchronize(st));                                 // (the blocks are idle again)
     if (report) {
         report->launches += launches;
@@ -216,12 +220,12 @@ int kmg::apply_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *
 // (the case where every table has k colours: n_tables = 1, one table for all images, or one per image)
 int kmg::apply_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
                      const float *c4, uint32_t n_tables, uint32_t k, int mode, int format, uint32_t cutoff, void *const *d_out,
-                     kmg_batch_apply_report *report, hipStream_t st, int filter)
+                     kmg_batch_apply_report *report, hipStream_t st, int filter, const DitherPtr *dither)
 {
     const std::vector<uint32_t> ks(n_images, k);
     std::vector<size_t> at(n_images, 0);
     for (uint32_t i = 0; n_tables != 1 && i < n_images; ++i) at[i] = 4ull * k * i;
-    return apply_batch_counts(p, n_images, d_src, widths, heights, c4, at.data(), ks.data(), n_tables == 1, mode, format, cutoff, d_out, report, st, filter);
+    return apply_batch_counts(p, n_images, d_src, widths, heights, c4, at.data(), ks.data(), n_tables == 1, mode, format, cutoff, d_out, report, st, filter, dither);
 }
 
 // The outputs of apply_batch / apply_batch_counts in one stream-ordered block, then to the host

@@ -1309,6 +1309,17 @@ static int refuse_fixed(kmg_group *g)
     return KMG_OK;
 }
 
+// (a threshold map is a feature of the single-device calls too: in KMG_MODE_DITHER a member processor whose dither choice is not
+// the default makes the group's output calls refuse)
+static int refuse_dither_choice(kmg_group *g, int mode)
+{
+    if (!g || mode != KMG_MODE_DITHER) return KMG_OK;
+    for (uint32_t i = 0; i < g->n_local; ++i)
+        if (g->ranks[i].p && dither_snapshot(g->ranks[i].p))
+            return fail(KMG_ERR_INVALID_ARGUMENT, "the processor of rank %u has a dither map or strength set: the kmg_group_* calls dither with the default", i);
+    return KMG_OK;
+}
+
 extern "C" int kmg_group_palette(kmg_group *g, const uint8_t *rgba, uint32_t width, uint32_t height, uint32_t color_count, int algo,
                                  uint8_t *out_rgba, uint32_t *out_count)
 try {
@@ -1337,6 +1348,7 @@ try {
     if (!palette_rgba || n_colors == 0) return fail(KMG_ERR_INVALID_ARGUMENT, "palette is empty");
     if (!out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
     KMG_TRY(check_mode(mode, KMG_MODE_MELD));
+    KMG_TRY(refuse_dither_choice(g, mode));
     KMG_TRY(check_k_limit(n_colors));
     HostCall c;
     c.rgba = rgba; c.w = width; c.h = height; c.k = n_colors; c.mode = mode; c.want_output = true; c.out = out_rgba;
@@ -1354,6 +1366,7 @@ try {
     if (!out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "output pointer is NULL");
     KMG_TRY(check_algo(algo));
     KMG_TRY(check_mode(mode, KMG_MODE_MELD));
+    KMG_TRY(refuse_dither_choice(g, mode));
     if (algo == KMG_ALGO_KMEANS) KMG_TRY(check_k_limit(color_count));
     HostCall c;
     c.rgba = rgba; c.w = width; c.h = height; c.k = color_count; c.algo = algo; c.mode = mode;
@@ -1368,6 +1381,7 @@ try {
     if (!g || !rgba || !widths || !heights || !out_rgba) return fail(KMG_ERR_INVALID_ARGUMENT, "bad group_reduce_batch arguments");
     KMG_TRY(refuse_fixed(g));
     KMG_TRY(check_mode(mode, KMG_MODE_MELD));                          // (no diffusion)
+    KMG_TRY(refuse_dither_choice(g, mode));
     if (g->world != g->n_local) return fail(KMG_ERR_UNSUPPORTED, "the host-buffer calls of a group need all its ranks in one process");
     std::lock_guard<std::mutex> lock(g->call_mu);
     // whole images per device, no exchange of any kind: a failure of one image must not leave the others' ranks waiting

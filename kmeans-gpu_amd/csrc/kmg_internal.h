@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/kmeans_hip.h"
+#include "kmg_dither_map.h"
 
 // Tuning switches and knock-outs (kernel variants that skip work and return WRONG results, for measurements) exist only in the
 // tools build (make tools: -DKMG_TOOLS, lib/libkmeans_hip_tools.so, loaded by tools/ through KMG_LIBRARY).  In the product
@@ -75,8 +76,12 @@ int octree_centroids(const std::vector<std::array<uint8_t, 4>> &colors, std::vec
 
 // kmg_dev_apply with the alpha cutoff given (kmg_apply.hip): the host-buffer calls read the processor's once per call
 // filter: the kmg_diffusion of KMG_MODE_DIFFUSE, or -1 = the processor's switch as it is now (an open sequence output hands on its own)
+// dither: the map and strength of KMG_MODE_DITHER (*dither null: the default), or NULL = the processor's choice as it is now
 int dev_apply(kmg_processor *p, const uint8_t *d_rgba, uint32_t w, uint32_t rows, uint32_t row0, const float *centroids4, uint32_t k,
-              int mode, uint8_t *d_out, void *stream, uint32_t alpha_cutoff, int format = KMG_FORMAT_RGBA8, int filter = -1);
+              int mode, uint8_t *d_out, void *stream, uint32_t alpha_cutoff, int format = KMG_FORMAT_RGBA8, int filter = -1,
+              const DitherPtr *dither = nullptr);
+// the dither choice set on a processor right now (kmg_processor.hip; kmg_processor_set_dither[_custom]), null = the default
+DitherPtr dither_snapshot(kmg_processor *p);
 // the box of the index formats (include/kmeans_hip.h at kmg_output_format)
 constexpr float kIndexBoxLmin = -100.0f, kIndexBoxLmax = 200.0f, kIndexBoxAB = 300.0f;
 // the rules of the index formats for a centroid table (kmg_apply.hip): the mode has an index, k fits the format, every centroid lies
@@ -88,7 +93,7 @@ int check_index_format(const float *centroids4, uint32_t k, int mode, int format
 // Synchronises `st`.
 int apply_batch(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
                 const float *centroids4, uint32_t n_tables, uint32_t k, int mode, int format, uint32_t alpha_cutoff, void *const *d_out,
-                kmg_batch_apply_report *report, hipStream_t st, int filter = -1);
+                kmg_batch_apply_report *report, hipStream_t st, int filter = -1, const DitherPtr *dither = nullptr);
 // apply_batch into one stream-ordered block (kmg_batch_layout.h: every image at a 16-byte aligned offset), then the images'
 // outputs to the host buffers out[i].  Synchronises `st`.
 int apply_batch_download(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
@@ -115,7 +120,7 @@ int dev_palette_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t 
 // of the first, all ks equal).  The joined images go out as at most two chains of launches, those below k = 32 and the others.
 int apply_batch_counts(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
                        const float *centroids4, const size_t *at, const uint32_t *ks, bool shared, int mode, int format, uint32_t alpha_cutoff,
-                       void *const *d_out, kmg_batch_apply_report *report, hipStream_t st, int filter = -1);
+                       void *const *d_out, kmg_batch_apply_report *report, hipStream_t st, int filter = -1, const DitherPtr *dither = nullptr);
 int apply_batch_counts_download(kmg_processor *p, uint32_t n_images, const uint8_t *const *d_src, const uint32_t *widths, const uint32_t *heights,
                                 const float *centroids4, const size_t *at, const uint32_t *ks, int mode, int format, uint32_t alpha_cutoff,
                                 uint8_t *const *out, kmg_batch_apply_report *report, hipStream_t st);
@@ -150,6 +155,8 @@ int frame_clip_impl(kmg_processor *p, uint32_t n_frames, const uint8_t *const *d
 uint32_t apply_plan_cutoff(const kmg_apply_plan *plan);
 // the diffusion filter a plan was made with (kmg_apply.hip)
 int apply_plan_filter(const kmg_apply_plan *plan);
+// the dither choice a plan was made with (kmg_apply.hip), null = the default
+const DitherPtr &apply_plan_dither(const kmg_apply_plan *plan);
 
 // kmg_dev_frame_delta_colour / _colour_lossy on a hipStream_t (kmg_local.hip): the frames of an output with per-frame palettes.
 // lossy: d_src_rgba, d_held_rgba and a hold record; exact: both NULL and a delta record

@@ -128,6 +128,25 @@ hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, 
 hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k, const float *lut,
                         const uint32_t *pal, bool dither, float threshold, void *out, int format, hipStream_t st, uint32_t alpha_cutoff = 0);
 
+// ---- KMG_MODE_DITHER with a threshold map (include/kmeans_hip.h at kmg_dither_map).  v: mw x mh values in device
+// memory, row-major; the sides are powers of two, so pixel (x, y) reads v[(x & xmask) + ((y & ymask) << xshift)].  t = threshold *
+// strength; a workgroup stages t * v into LDS.
+struct DitherMapDev { const float *v; uint32_t xmask, ymask, xshift; };
+static inline uint32_t dither_map_entries(const DitherMapDev &m) { return (m.xmask + 1u) * (m.ymask + 1u); }
+// the dither body of launch_apply with the map (kmg_dither_map.hip: k_apply_map).  apply_map_lds_bytes: its dynamic LDS, which the
+// caller compares with device_info().lds_max (the launcher refuses a request above it: hipErrorInvalidValue)
+size_t apply_map_lds_bytes(uint32_t k, uint32_t map_entries);
+hipError_t launch_apply_map(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k, const float *lut,
+                            const uint32_t *pal, float t, DitherMapDev map, void *out, int format, hipStream_t st, uint32_t alpha_cutoff);
+// launch_dither_lists with the map (kmg_lists.hip: k_dither_lists_map)
+hipError_t launch_dither_lists_map(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
+                                   const float *lut, const uint32_t *pal, float t, DitherMapDev map, const uint8_t *lists, void *out,
+                                   int format, hipStream_t st, uint32_t alpha_cutoff);
+// launch_lab_candidates (kmg_table.h) of the dither pass for offsets in [off_lo, off_hi] instead of the reference matrix's
+// threshold * [-0.5, 0.4375]: the box of cells that get a list (speed only; cells outside mean "scan everything")
+hipError_t launch_lab_candidates_range(const Centroid *cent, uint32_t k, float off_lo, float off_hi, bool two_closest, uint8_t *lists,
+                                       hipStream_t st);
+
 // thr[256] (device): the linear-channel thresholds of the 256 sRGB8 output bytes (k_meld), made by the device's own encode
 hipError_t launch_encode_thresholds(float *thr, hipStream_t st);
 // out[0..2] (device; the caller sets {0, ~0, 0}): mismatches of div_const(x, c) against x / c over every binary32 x, and the

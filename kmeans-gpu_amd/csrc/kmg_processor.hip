@@ -7,6 +7,7 @@
 
 #include "kmg_state.h"
 #include "kmg_diffusion.h"
+#include "kmg_blue_noise.h"
 
 // ---------------------------------------------------------------------------------------------
 // errors
@@ -330,6 +331,89 @@ try {
     if (!weights || !divisor) return fail(KMG_ERR_INVALID_ARGUMENT, "bad diffusion_weights arguments");
     if (filter < 0 || filter >= KMG_DIFFUSION_COUNT) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown diffusion filter %d", filter);
     *divisor = diffusion_table(filter, weights);
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+// Bayer recursion, M2 = [[0, 2], [3, 1]], M2n = [[4M, 4M + 2], [4M + 3, 4M + 1]]: the level of (x, y) in the side x side matrix
+static uint32_t bayer_level(uint32_t x, uint32_t y, uint32_t side)
+{
+    uint32_t v = 0;
+    // the quadrant at the coarsest scale adds the smallest term: (top-left, top-right, bottom-left, bottom-right) = (0, 2, 3, 1)
+    for (uint32_t half = side >> 1, scale = 1; half >= 1u; half >>= 1, scale *= 4u) {
+        const uint32_t qx = (x / half) & 1u, qy = (y / half) & 1u;
+        v += scale * (qy ? (qx ? 1u : 3u) : (qx ? 2u : 0u));
+    }
+    return v;
+}
+
+bool kmg::dither_builtin(int map, uint32_t *w, uint32_t *h, uint32_t *n_levels, uint16_t *levels)
+{
+    // mix_colors.wgsl:14-17
+    static const uint16_t bayer4[16] = {0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5};
+    uint32_t side = 0;
+    switch (map) {
+    case KMG_DITHER_BAYER4: side = 4; break;
+    case KMG_DITHER_BAYER2: side = 2; break;
+    case KMG_DITHER_BAYER8: side = 8; break;
+    case KMG_DITHER_BAYER16: side = 16; break;
+    case KMG_DITHER_BLUE64: side = 64; break;
+    default: return false;
+    }
+    *w = *h = side;
+    *n_levels = side * side;
+    for (uint32_t i = 0; i < side * side; ++i)
+        levels[i] = map == KMG_DITHER_BLUE64 ? kBlueNoise64[i] : map == KMG_DITHER_BAYER4 ? bayer4[i] : (uint16_t)bayer_level(i % side, i / side, side);
+    return true;
+}
+
+// the processor's choice as it is now (null: the default)
+DitherPtr kmg::dither_snapshot(kmg_processor *p)
+{
+    std::lock_guard<std::mutex> lock(p->mu);
+    return p->dither;
+}
+
+extern "C" int kmg_processor_set_dither(kmg_processor *p, int map, float strength)
+try {
+    if (!p) return fail(KMG_ERR_INVALID_ARGUMENT, "processor is NULL");
+    uint32_t w = 0, h = 0, n_levels = 0;
+    std::vector<uint16_t> levels(kDitherMapMaxSide * kDitherMapMaxSide);
+    if (!dither_builtin(map, &w, &h, &n_levels, levels.data())) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown built-in dither map %d", map);
+    if (!dither_strength_ok(strength)) return fail(KMG_ERR_INVALID_ARGUMENT, "dither strength %g is not in [0, 4]", (double)strength);
+    // (the reference's matrix at strength 1 is the default: the kernels that carry it in their code)
+    DitherPtr c = map == KMG_DITHER_BAYER4 && strength == 1.0f ? nullptr : dither_choice(map, levels.data(), w, h, n_levels, strength);
+    std::lock_guard<std::mutex> lock(p->mu);
+    p->dither = std::move(c);
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_processor_set_dither_custom(kmg_processor *p, const uint16_t *levels, uint32_t width, uint32_t height, uint32_t n_levels,
+                                               float strength)
+try {
+    if (!p || !levels) return fail(KMG_ERR_INVALID_ARGUMENT, "bad set_dither_custom arguments");
+    if (!dither_side_ok(width) || !dither_side_ok(height))
+        return fail(KMG_ERR_INVALID_ARGUMENT, "dither map of %u x %u: each side is a power of two in 1 .. %u", width, height, kDitherMapMaxSide);
+    if (n_levels == 0 || n_levels > kDitherMapMaxLevels) return fail(KMG_ERR_INVALID_ARGUMENT, "n_levels = %u is not in 1 .. %u", n_levels, kDitherMapMaxLevels);
+    for (uint32_t i = 0; i < width * height; ++i)
+        if (levels[i] >= n_levels) return fail(KMG_ERR_INVALID_ARGUMENT, "dither level %u at (%u, %u) is not below n_levels = %u", levels[i], i % width, i / width, n_levels);
+    if (!dither_strength_ok(strength)) return fail(KMG_ERR_INVALID_ARGUMENT, "dither strength %g is not in [0, 4]", (double)strength);
+    DitherPtr c = dither_choice(KMG_DITHER_CUSTOM, levels, width, height, n_levels, strength);
+    std::lock_guard<std::mutex> lock(p->mu);
+    p->dither = std::move(c);
+    return KMG_OK;
+}
+KMG_ABI_CATCH
+
+extern "C" int kmg_dither_map_values(int map, uint32_t *width, uint32_t *height, uint32_t *n_levels, uint16_t *levels)
+try {
+    if (!width || !height || !n_levels || !levels) return fail(KMG_ERR_INVALID_ARGUMENT, "bad dither_map_values arguments");
+    uint32_t w = 0, h = 0, n = 0;
+    std::vector<uint16_t> tmp(kDitherMapMaxSide * kDitherMapMaxSide);
+    if (!dither_builtin(map, &w, &h, &n, tmp.data())) return fail(KMG_ERR_INVALID_ARGUMENT, "unknown built-in dither map %d", map);
+    *width = w; *height = h; *n_levels = n;
+    memcpy(levels, tmp.data(), sizeof(uint16_t) * w * h);
     return KMG_OK;
 }
 KMG_ABI_CATCH

@@ -257,6 +257,7 @@ struct kmg_sequence {
     bool local = false, have_prev = false;
     uint32_t local_flags = 0;
     int local_filter = 0;               // kmg_processor_set_diffusion when the per-frame output was opened
+    DitherPtr local_dither;             // kmg_processor_set_dither[_custom] likewise (null: the default)
     uint8_t *d_shown = nullptr, *d_pal = nullptr;
     std::vector<float> prev_c4;      // C_{t-1}: where a warm frame's Lloyd loop starts
     std::vector<float> c4;           // the open output's centroids (shared palette): what a clip's batched output launch takes
@@ -633,7 +634,7 @@ int output_clip(kmg_sequence *s, uint32_t n_frames, const uint8_t *const *rgba, 
         }
         kmg_batch_apply_report arep = {0u, 0u, 0u, 0u};
         KMG_TRY_DRAIN(st, apply_batch(p, m, src.data(), widths.data(), heights.data(), s->c4.data(), 1u, s->k, s->mode, s->format, cutoff,
-                                      maps.data(), &arep, st, apply_plan_filter(s->plan)));
+                                      maps.data(), &arep, st, apply_plan_filter(s->plan), &apply_plan_dither(s->plan)));
         rep->launches += arep.launches;
         rep->batched += arep.batched;
         rep->per_image += arep.per_image;
@@ -765,6 +766,7 @@ try {
     KMG_TRY(output_opened(s, hipMemsetAsync(s->d_shown, 0, n * 4, s->sg.st), k, mode, format, width, height));
     s->local = true; s->have_prev = false; s->local_flags = flags;
     s->local_filter = s->p->diffusion.load(std::memory_order_relaxed);
+    s->local_dither = dither_snapshot(s->p);
     return KMG_OK;
 }
 KMG_ABI_CATCH
@@ -801,7 +803,7 @@ try {
     std::vector<float> c4(4 * (size_t)k);
     KMG_TRY_DRAIN(st, local_frame_centroids(p, s->d_frame, s->width, s->height, k, cutoff, st, c4.data(), f ? fixed->data() : nullptr, f,
                                             warm ? s->prev_c4.data() : nullptr, weighting));
-    KMG_TRY_DRAIN(st, dev_apply(p, s->d_frame, s->width, s->height, 0, c4.data(), k, s->mode, s->d_map, st, cutoff, s->format, s->local_filter));
+    KMG_TRY_DRAIN(st, dev_apply(p, s->d_frame, s->width, s->height, 0, c4.data(), k, s->mode, s->d_map, st, cutoff, s->format, s->local_filter, &s->local_dither));
     // P_t: the bytes the output pass writes for each centroid, to the caller and -- one small stream-ordered copy -- to the device
     std::vector<uint8_t> pal(4 * (size_t)k);
     for (uint32_t i = 0; i < k; ++i) shader_lab_to_rgba8(&c4[4 * i], &pal[4 * i]);

@@ -82,6 +82,7 @@ struct kmg_processor {
     std::atomic<int> strategy{0};   // KMG_STRATEGY_* (kmg_options.strategy, kmg_processor_set_strategy)
     std::atomic<uint32_t> alpha_cutoff{0};   // kmg_options.alpha_cutoff, kmg_processor_set_alpha_cutoff (0 = alpha ignored)
     std::atomic<int> diffusion{0};  // KMG_DIFFUSION_* (kmg_processor_set_diffusion): the filter of the KMG_MODE_DIFFUSE plans made from now on
+    DitherPtr dither;               // kmg_processor_set_dither[_custom] (mu): the map and strength of the KMG_MODE_DITHER plans made from now on; null = the default
     std::atomic<int> weighting{0};  // KMG_WEIGHT_* (kmg_processor_set_weighting): the palette step's sums weigh a pixel by its alpha
     // kmg_processor_set_fixed_colors (mu): the pinned palette entries as Lab (kmg_palette_to_centroids of the caller's list, 4 floats
     // each), or null = none.  A call takes the pointer once when it starts and keeps that list to its end.

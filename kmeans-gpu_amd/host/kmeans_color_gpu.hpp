@@ -412,6 +412,37 @@ public:
         check(kmg_processor_set_diffusion(p_, filter));
     }
 
+    // kmg_processor_set_dither (include/kmeans_hip.h at kmg_dither_map): a built-in threshold map (KMG_DITHER_*) and the strength
+    // (0 .. 4) of ReduceMode::Dither for the outputs made from now on; KMG_DITHER_BAYER4 at 1, the reference's dither, is the
+    // default, and the other modes ignore both.  A processor over several devices dithers with the default only.
+    void set_dither(int map, float strength = 1.0f) const
+    {
+        if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "a processor over several devices has no dither maps");
+        check(kmg_processor_set_dither(p_, map, strength));
+    }
+
+    // kmg_processor_set_dither_custom: the same with the caller's own map -- width x height levels below n_levels, row-major, each
+    // side a power of two up to 64
+    void set_dither(const std::vector<uint16_t> &levels, uint32_t width, uint32_t height, uint32_t n_levels, float strength = 1.0f) const
+    {
+        if (g_) throw Error(KMG_ERR_INVALID_ARGUMENT, "a processor over several devices has no dither maps");
+        if (levels.size() != (size_t)width * height) throw Error(KMG_ERR_INVALID_ARGUMENT, "the dither map's levels do not match its sides");
+        check(kmg_processor_set_dither_custom(p_, levels.data(), width, height, n_levels, strength));
+    }
+
+    // kmg_dither_map_values: the table of a built-in map (no device needed), row-major; the sides and n_levels through the pointers
+    static std::vector<uint16_t> dither_map_values(int map, uint32_t *width, uint32_t *height, uint32_t *n_levels)
+    {
+        std::vector<uint16_t> levels(4096);
+        uint32_t w = 0, h = 0, n = 0;
+        check(kmg_dither_map_values(map, &w, &h, &n, levels.data()));
+        levels.resize((size_t)w * h);
+        if (width) *width = w;
+        if (height) *height = h;
+        if (n_levels) *n_levels = n;
+        return levels;
+    }
+
     // kmg_processor_set_fixed_colors (include/kmeans_hip.h): colours every k-means palette of the calls that start from now on keeps
     // exactly (alpha ignored), as entries 0 .. colors.size() - 1 in index order; an empty list clears them.  A color_count below
     // their number and Algorithm::Octree are then errors.  A processor over several devices has no fixed colours.

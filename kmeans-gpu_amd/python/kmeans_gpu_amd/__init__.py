@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "Diffusion", "DIFFUSION_NAMES", "diffusion_weights", "ErrorStats", "BatchReport", "BatchApplyReport", "BatchQualityReport", "ClipReport", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "CLIP_FULL_ON_CLEAR", "CLIP_FRAMES", "CLIP_MIN_FRAMES", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
+__all__ = ["ImageProcessor", "Algorithm", "ReduceMode", "OutputFormat", "Diffusion", "DIFFUSION_NAMES", "diffusion_weights", "DitherMap", "DITHER_MAP_NAMES", "dither_map_values", "ErrorStats", "BatchReport", "BatchApplyReport", "BatchQualityReport", "ClipReport", "Sequence", "FrameDelta", "FrameHold", "FRAME_DELTA", "CLIP_FULL_ON_CLEAR", "CLIP_FRAMES", "CLIP_MIN_FRAMES", "LOCAL_WARM", "MAX_TOLERANCE", "tolerance_of", "ERROR_RGB", "ERROR_LAB", "Lloyd", "ApplyPlan", "Group", "GroupLloyd", "GroupOptions", "KmgError", "lib",
            "library_path", "GROUP_FORCE_COLLECTIVES", "GROUP_LOOPBACK", "GROUP_CELLS", "GROUP_OVERLAP", "GROUP_FUSED_UPDATE",
            "resized_dims", "palette_to_centroids", "centroids_to_palette", "dither_threshold",
            "default_options", "Options"]
@@ -95,6 +95,39 @@ def diffusion_weights(filter):
     d = C.c_int32()
     _check(lib().kmg_diffusion_weights(_diffusion_value(filter), w, C.byref(d)))
     return np.array(w[:], np.int32), int(d.value)
+
+
+class DitherMap(enum.IntEnum):          # include/kmeans_hip.h kmg_dither_map: the threshold map of ReduceMode.Dither
+    Bayer4 = 0                          # the reference's matrix, the default
+    Bayer2 = 1
+    Bayer8 = 2
+    Bayer16 = 3
+    Blue64 = 4                          # 64 x 64 void-and-cluster (blue noise)
+    Custom = 5                          # the caller's own map (set_dither with an array)
+
+
+# the CLI's names of the built-in maps
+DITHER_MAP_NAMES = {"bayer4": 0, "bayer2": 1, "bayer8": 2, "bayer16": 3, "blue": 4}
+
+
+def _dither_map_value(m):
+    """a DitherMap, its number, or one of DITHER_MAP_NAMES (case does not matter; blue64 = blue); unknown numbers pass through to
+    the library"""
+    if isinstance(m, str):
+        key = m.strip().lower()
+        key = "blue" if key == "blue64" else key
+        if key not in DITHER_MAP_NAMES:
+            raise ValueError(f"unknown dither map {m!r}: one of {', '.join(DITHER_MAP_NAMES)}")
+        return DITHER_MAP_NAMES[key]
+    return int(m)
+
+
+def dither_map_values(map):
+    """kmg_dither_map_values (no device needed): (levels, n_levels) of a built-in map, levels a (height, width) uint16 array"""
+    buf = (C.c_uint16 * 4096)()
+    w, h, n = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().kmg_dither_map_values(_dither_map_value(map), C.byref(w), C.byref(h), C.byref(n), buf))
+    return np.array(buf[:w.value * h.value], np.uint16).reshape(h.value, w.value), int(n.value)
 
 
 class OutputFormat(enum.IntEnum):       # include/kmeans_hip.h kmg_output_format
@@ -414,7 +447,7 @@ _lib = None
 # every symbol include/kmeans_hip.h declares
 SYMBOLS = [
     "kmg_last_error", "kmg_version", "kmg_host_alloc", "kmg_host_free", "kmg_default_options", "kmg_processor_create",
-    "kmg_processor_create_ex", "kmg_processor_destroy", "kmg_processor_set_strategy", "kmg_processor_set_alpha_cutoff", "kmg_processor_set_weighting", "kmg_processor_set_diffusion", "kmg_diffusion_weights", "kmg_processor_set_fixed_colors", "kmg_palette", "kmg_find", "kmg_reduce",
+    "kmg_processor_create_ex", "kmg_processor_destroy", "kmg_processor_set_strategy", "kmg_processor_set_alpha_cutoff", "kmg_processor_set_weighting", "kmg_processor_set_diffusion", "kmg_diffusion_weights", "kmg_processor_set_dither", "kmg_processor_set_dither_custom", "kmg_dither_map_values", "kmg_processor_set_fixed_colors", "kmg_palette", "kmg_find", "kmg_reduce",
     "kmg_palette_to_centroids", "kmg_centroids_to_palette", "kmg_octree_palette", "kmg_dev_rgb_to_lab",
     "kmg_resized_dims", "kmg_dev_alpha_compact",
     "kmg_dev_resize", "kmg_lloyd_create", "kmg_lloyd_destroy", "kmg_lloyd_set_centroids",
@@ -551,6 +584,10 @@ def lib():
     if hasattr(L, "kmg_processor_set_diffusion"):        # (KMG_LIBRARY may name an older build: tools/diffusion_filters_time.py times one)
         L.kmg_processor_set_diffusion.argtypes = [vp, C.c_int]
         L.kmg_diffusion_weights.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    if hasattr(L, "kmg_processor_set_dither"):           # (likewise: tools/dither_map_time.py times the build before the maps)
+        L.kmg_processor_set_dither.argtypes = [vp, C.c_int, C.c_float]
+        L.kmg_processor_set_dither_custom.argtypes = [vp, C.POINTER(C.c_uint16), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float]
+        L.kmg_dither_map_values.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint16)]
     L.kmg_lloyd_set_weighting.argtypes = [vp, C.c_int]
     L.kmg_dev_alpha_compact.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, u8p, vp, vp]
     L.kmg_dev_compare.argtypes = [vp, u8p, vp, C.c_uint64, C.c_int, u8p, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
@@ -779,12 +816,14 @@ class ImageProcessor:
     """Mirror of `kmeans_color_gpu::ImageProcessor` (core/src/lib.rs:24-165)."""
 
     def __init__(self, device=-1, shrink_max_dim=256, max_iterations=128, check_period=8,
-                 convergence=1.0, strategy=None, alpha_cutoff=0, fixed_colors=None, alpha_weight=False, diffusion=0):
+                 convergence=1.0, strategy=None, alpha_cutoff=0, fixed_colors=None, alpha_weight=False, diffusion=0,
+                 dither_map=0, dither_strength=1.0):
         """alpha_cutoff: 0 = alpha ignored (the reference's behaviour); 1..255 = alpha mode (include/kmeans_hip.h at
         kmg_options): only pixels whose alpha is >= alpha_cutoff shape the palette, and the outputs keep the input's alpha.
         fixed_colors: colours every k-means palette of this processor keeps, as its first entries (set_fixed_colors)
         alpha_weight: the k-means palettes weigh every pixel by its alpha byte (set_alpha_weight)
-        diffusion: the filter of ReduceMode.Diffuse (set_diffusion)"""
+        diffusion: the filter of ReduceMode.Diffuse (set_diffusion)
+        dither_map, dither_strength: the threshold map and strength of ReduceMode.Dither (set_dither)"""
         self._h = C.c_void_p()
         o = default_options()
         o.device = device
@@ -809,6 +848,35 @@ class ImageProcessor:
         self.diffusion = Diffusion.FloydSteinberg
         if _diffusion_value(diffusion):
             self.set_diffusion(diffusion)
+
+        self.dither_map, self.dither_strength = DitherMap.Bayer4, 1.0
+        if not (isinstance(dither_map, (int, DitherMap)) and int(dither_map) == 0 and float(dither_strength) == 1.0):
+            self.set_dither(dither_map, dither_strength)
+
+    def set_dither(self, map, strength=1.0, levels=None):
+        """kmg_processor_set_dither[_custom]: the threshold map and the strength (0 .. 4) of the ReduceMode.Dither outputs made from
+        now on; an apply plan and an open sequence output keep the ones they were made under.  map: a DitherMap, its number, its
+        CLI name, or a 2-D integer array (height, width) of levels for a custom map, whose sides are powers of two up to 64;
+        levels: the n_levels of a custom map (default: its largest level + 1).  DitherMap.Bayer4 at strength 1 is the default, the
+        reference's dither"""
+        if isinstance(map, (str, int, enum.IntEnum, np.integer)):
+            v = _dither_map_value(map)
+            _check(lib().kmg_processor_set_dither(self._h, v, float(strength)))
+            self.dither_map = DitherMap(v)
+        else:
+            a = np.asarray(map)
+            if a.ndim != 2 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("a custom dither map is a 2-D integer array (height, width)")
+            if a.min() < 0 or a.max() > 65535:
+                raise ValueError("the levels of a dither map are 0 .. 65535")
+            n_levels = int(a.max()) + 1 if levels is None else int(levels)
+            if not 0 <= n_levels <= 0xFFFFFFFF:
+                raise ValueError("levels does not fit the call")
+            a16 = np.ascontiguousarray(a, np.uint16)
+            _check(lib().kmg_processor_set_dither_custom(self._h, a16.ctypes.data_as(C.POINTER(C.c_uint16)), a.shape[1], a.shape[0], n_levels,
+                                                         float(strength)))
+            self.dither_map = DitherMap.Custom
+        self.dither_strength = float(strength)
 
     def set_diffusion(self, filter):
         """kmg_processor_set_diffusion: the filter (a Diffusion, its number or its CLI name) of the ReduceMode.Diffuse outputs made

@@ -12,6 +12,11 @@ pixels whose alpha is at least N shape the palette, and the output keeps the inp
 `find`, `reduce`, `sequence` and `batch` take `--diffusion NAME` with `-m diffuse`: the error-diffusion filter (floyd-steinberg, the
 default; sierra-lite, atkinson, burkes, sierra2, sierra3, jarvis, stucki; include/kmeans_hip.h at kmg_diffusion).
 
+`find`, `reduce`, `sequence` and `batch` take `--dither-map bayer2|bayer4|bayer8|bayer16|blue|FILE.png` and `--dither-strength S` with
+`-m dither`: the threshold map of the ordered dither (bayer4, the reference's matrix, is the default; blue is a 64 x 64 blue-noise
+map; a file is a grey 8-bit PNG whose sides are powers of two up to 64, its grey values the levels out of 256) and the factor
+0 .. 4 on the dither's amplitude (default 1; include/kmeans_hip.h at kmg_dither_map).  Not with --devices.
+
 `reduce` and `find` also take `--indexed`: the output is a palette-mode PNG (one index per pixel, PLTE = the palette; at most 256
 colours) instead of RGBA.  In alpha mode the pixels below the cutoff take one more, fully transparent entry (tRNS 0), so
 255 colours at most.
@@ -69,7 +74,7 @@ import time
 
 import numpy as np
 
-from . import DIFFUSION_NAMES, Algorithm, Group, ImageProcessor, ReduceMode
+from . import DIFFUSION_NAMES, DITHER_MAP_NAMES, Algorithm, Group, ImageProcessor, ReduceMode
 
 _PALETTE_RE = re.compile(r"^#[0-9a-fA-F]{6}(?:,#[0-9a-fA-F]{6})*$")     # args.rs:184
 _MODES = {"replace": ReduceMode.Replace, "dither": ReduceMode.Dither, "meld": ReduceMode.Meld, "diffuse": ReduceMode.Diffuse}
@@ -222,6 +227,7 @@ def run_sequence_local(args, frames, w, h, out_path):
     lossy = args.lossy if delta else None
     with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed, alpha_weight=args.alpha_weight,
                         diffusion=args.diffusion or 0) as proc, proc.sequence() as seq:
+        _set_dither(proc, args)
         seq.output_local(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h, warm=args.warm)
         for i, f in enumerate(frames):
             index, colors, info, is_full = seq.frame_local(f, delta=delta, tolerance=lossy)
@@ -261,6 +267,7 @@ def run_sequence(args, ap):
         return run_sequence_local(args, frames, w, h, out_path)
     with ImageProcessor(alpha_cutoff=args.alpha_cutoff, fixed_colors=args.fixed, alpha_weight=args.alpha_weight,
                         diffusion=args.diffusion or 0) as proc, proc.sequence() as seq:
+        _set_dither(proc, args)
         for f in frames:
             seq.add(f)
         colors = seq.output(args.colorcount, _MODES[args.mode], OutputFormat.Index8, w, h)
@@ -413,6 +420,12 @@ def build_parser():
     for s in (f, r, q, b):
         s.add_argument("--diffusion", choices=list(DIFFUSION_NAMES), default=None, metavar="NAME",
                        help="with -m diffuse: the error-diffusion filter, one of " + ", ".join(DIFFUSION_NAMES) + " (default floyd-steinberg)")
+    for s in (f, r, q, b):
+        s.add_argument("--dither-map", default=None, metavar="MAP",
+                       help="with -m dither: the threshold map, one of " + ", ".join(sorted(DITHER_MAP_NAMES)) + " (default bayer4, the "
+                            "reference's matrix) or a grey 8-bit PNG with sides that are powers of two up to 64")
+        s.add_argument("--dither-strength", type=validate_dither_strength, default=None, metavar="S",
+                       help="with -m dither: a factor 0 .. 4 on the dither's amplitude (default 1)")
     for s in (p, r, q):
         s.add_argument("--fixed", type=validate_palette, default=None, metavar="COLORS",
                        help='"#RRGGBB,..." or a palette image: colours the k-means palette keeps exactly, as its first entries; -c counts them')
@@ -440,6 +453,52 @@ def check_diffusion(args, ap):
     """--diffusion names the filter of -m diffuse: an argument error with any other mode"""
     if getattr(args, "diffusion", None) is not None and args.mode != "diffuse":
         ap.error("--diffusion names the filter of -m diffuse: it needs -m diffuse")
+
+
+def validate_dither_strength(s):
+    try:
+        v = float(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{s} is not a number")
+    if not (np.isfinite(v) and 0.0 <= v <= 4.0):
+        raise argparse.ArgumentTypeError(f"{s} is not in 0..=4")
+    return v
+
+
+def check_dither(args, ap):
+    """--dither-map and --dither-strength belong to -m dither: an argument error with any other mode.  Leaves args.dither = None
+    (the default) or (map, strength, levels) as ImageProcessor.set_dither takes them"""
+    name, strength = getattr(args, "dither_map", None), getattr(args, "dither_strength", None)
+    args.dither = None
+    if name is None and strength is None:
+        return
+    if args.mode != "dither":
+        ap.error("--dither-map and --dither-strength shape the ordered dither: they need -m dither")
+    if getattr(args, "devices", None):
+        ap.error("--dither-map and --dither-strength are not supported with --devices")
+    if name is None or name.lower() in DITHER_MAP_NAMES:
+        args.dither = ((name or "bayer4").lower(), 1.0 if strength is None else strength, None)
+        return
+    if not name.lower().endswith(".png"):
+        ap.error(f"--dither-map: {name} is neither one of {', '.join(sorted(DITHER_MAP_NAMES))} nor a PNG file")
+    from PIL import Image
+    try:
+        im = Image.open(name)
+        im.load()
+    except OSError as e:
+        ap.error(f"--dither-map: cannot read {name}: {e}")
+    if im.mode != "L":
+        ap.error(f"--dither-map: {name} is not a grey 8-bit PNG (mode {im.mode})")
+    w, h = im.size
+    if any(v < 1 or v > 64 or v & (v - 1) for v in (w, h)):
+        ap.error(f"--dither-map: {name} is {w}x{h}; each side must be a power of two up to 64")
+    args.dither = (np.asarray(im, np.uint8).astype(np.uint16), 1.0 if strength is None else strength, 256)
+
+
+def _set_dither(proc, args):
+    if args.dither is not None:
+        proc.set_dither(args.dither[0], args.dither[1], levels=args.dither[2])
+    return proc
 
 
 def run_batch(args, ap):
@@ -471,6 +530,7 @@ def run_batch(args, ap):
                      f"{args.colorcount} requested")
     images = [_load(path) for path in args.input]
     with ImageProcessor(alpha_cutoff=args.alpha_cutoff, diffusion=args.diffusion or 0) as proc:
+        _set_dither(proc, args)
         if args.max_error is not None:                   # every image's colour count from the quality target; -c is the upper bound
             os.makedirs(args.output, exist_ok=True)
             results = proc.reduce_quality_batch(images, args.max_error, args.min_colors, args.colorcount, _MODES[args.mode], indexed=args.indexed)
@@ -520,6 +580,7 @@ def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
     check_diffusion(args, ap)
+    check_dither(args, ap)
     if args.command == "batch":
         return run_batch(args, ap)
     if getattr(args, "weights", None) is not None:
@@ -613,7 +674,7 @@ def main(argv=None):
             options["alpha_weight"] = True
         if getattr(args, "diffusion", None) is not None:
             options["diffusion"] = args.diffusion
-        proc = ImageProcessor(**options)
+        proc = _set_dither(ImageProcessor(**options), args)
     with proc:
         if args.command == "palette":                    # main.rs:46-72
             colors = proc.palette(args.colorcount, image, _ALGOS[args.algo])

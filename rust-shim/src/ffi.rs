@@ -68,6 +68,16 @@ pub const KMG_DIFFUSION_SIERRA3: c_int = 5;
 pub const KMG_DIFFUSION_JARVIS: c_int = 6;
 pub const KMG_DIFFUSION_STUCKI: c_int = 7;
 pub const KMG_DIFFUSION_COUNT: c_int = 8;
+/// `kmg_dither_map`: the threshold map of KMG_MODE_DITHER (kmg_processor_set_dither)
+pub const KMG_DITHER_BAYER4: c_int = 0;
+pub const KMG_DITHER_BAYER2: c_int = 1;
+pub const KMG_DITHER_BAYER8: c_int = 2;
+pub const KMG_DITHER_BAYER16: c_int = 3;
+pub const KMG_DITHER_BLUE64: c_int = 4;
+pub const KMG_DITHER_CUSTOM: c_int = 5;
+pub const KMG_DITHER_COUNT: c_int = 6;
+/// the header's name of a map level (tests/test_rust_shim.py compares the declarations below with the header's by type name)
+pub type uint16_t = u16;
 /// `kmg_output_format`: RGBA8, or one u8 / u16 palette index per pixel (`kmg_find_indexed`, `kmg_reduce_indexed`).
 pub const KMG_FORMAT_RGBA8: c_int = 0;
 pub const KMG_FORMAT_INDEX8: c_int = 1;
@@ -177,6 +187,16 @@ extern "C" {
     pub fn kmg_processor_set_weighting(p: *mut kmg_processor, weighting: c_int) -> c_int;
     pub fn kmg_processor_set_diffusion(p: *mut kmg_processor, filter: c_int) -> c_int;
     pub fn kmg_diffusion_weights(filter: c_int, weights: *mut i32, divisor: *mut i32) -> c_int;
+    pub fn kmg_processor_set_dither(p: *mut kmg_processor, map: c_int, strength: f32) -> c_int;
+    pub fn kmg_processor_set_dither_custom(
+        p: *mut kmg_processor,
+        levels: *const uint16_t,
+        width: u32,
+        height: u32,
+        n_levels: u32,
+        strength: f32,
+    ) -> c_int;
+    pub fn kmg_dither_map_values(map: c_int, width: *mut u32, height: *mut u32, n_levels: *mut u32, levels: *mut uint16_t) -> c_int;
     // ImageProcessor::palette -- lib.rs:67-77
     pub fn kmg_palette(
         p: *mut kmg_processor,

@@ -82,6 +82,29 @@ impl ImageProcessor {
         check(unsafe { ffi::kmg_processor_set_diffusion(self.raw, filter) })
     }
 
+    /// The threshold map and the strength of `ReduceMode::Dither` (`kmg_processor_set_dither`, include/kmeans_hip.h at
+    /// `kmg_dither_map`): one of the built-in `ffi::KMG_DITHER_*` maps and a factor 0 ..= 4 on the dither's amplitude;
+    /// `KMG_DITHER_BAYER4` at 1.0, the reference's dither, is the default.  It holds for the outputs made from now on; the other
+    /// modes ignore it.  No counterpart in the reference.  A processor over several devices dithers with the default only.
+    pub fn set_dither(&self, map: i32, strength: f32) -> Result<()> {
+        if !self.group.is_null() {
+            return Err(anyhow!("a processor over several devices has no dither maps"));
+        }
+        check(unsafe { ffi::kmg_processor_set_dither(self.raw, map, strength) })
+    }
+
+    /// The same with the caller's own map (`kmg_processor_set_dither_custom`): `levels` holds `width * height` values below
+    /// `n_levels`, row-major; each side is a power of two up to 64.
+    pub fn set_dither_custom(&self, levels: &[u16], width: u32, height: u32, n_levels: u32, strength: f32) -> Result<()> {
+        if !self.group.is_null() {
+            return Err(anyhow!("a processor over several devices has no dither maps"));
+        }
+        if levels.len() as u64 != width as u64 * height as u64 {
+            return Err(anyhow!("a dither map of {}x{} has {} levels, {} given", width, height, width as u64 * height as u64, levels.len()));
+        }
+        check(unsafe { ffi::kmg_processor_set_dither_custom(self.raw, levels.as_ptr(), width, height, n_levels, strength) })
+    }
+
     /// Alpha weighting (`kmg_processor_set_weighting`, include/kmeans_hip.h): `true` lets every k-means palette of the calls that
     /// start from now on weigh a pixel by its alpha byte (pixels of alpha 0 do not shape it at all); `Algorithm::Octree` is then
     /// an error.  `false`, the default, weighs every kept pixel 1.  No counterpart in the reference.  A processor over several
