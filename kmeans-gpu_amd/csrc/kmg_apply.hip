@@ -404,11 +404,12 @@ int kmg::apply_plan_filter(const kmg_apply_plan *pl) { return pl->filter; }
 
 const DitherPtr &kmg::apply_plan_dither(const kmg_apply_plan *pl) { return pl->choice; }
 
-// the plan's map as its kernels take it
-static DitherMapDev plan_map(const kmg_apply_plan *pl)
+// the plan's dither offsets as the launchers take them: the default choice is the reference's matrix at the plan's threshold
+static MapOffsets plan_offsets(const kmg_apply_plan *pl)
 {
+    if (!pl->choice) return {pl->thr, {}};
     const DitherChoice &c = *pl->choice;
-    return {pl->d_v, c.mw - 1u, c.mh - 1u, (uint32_t)__builtin_ctz(c.mw)};
+    return {pl->t, {pl->d_v, c.mw - 1u, c.mh - 1u, (uint32_t)__builtin_ctz(c.mw)}};
 }
 
 // kmg_dev_apply and kmg_apply_plan_status: did any diffusion run of the plan time out?  (Read after the last run has completed.)
@@ -460,8 +461,7 @@ static int run_band(kmg_apply_plan *pl, const uint32_t *src, uint32_t w, uint32_
     hipError_t e = hipSuccess;
     switch (pl->route) {
     case Route::kScan:
-        if (pl->choice) e = launch_apply_map(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->t, plan_map(pl), d_out, pl->format, st, cutoff);
-        else e = launch_apply(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->dither, pl->thr, d_out, pl->format, st, cutoff);
+        e = launch_apply(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->dither, plan_offsets(pl), d_out, pl->format, st, cutoff);
         break;
     case Route::kReplaceTable:
         if (index) e = launch_labels_index(src, n_px, pl->aux, pl->sub, k, d_out, pl->format, st, cutoff);
@@ -469,9 +469,7 @@ static int run_band(kmg_apply_plan *pl, const uint32_t *src, uint32_t w, uint32_
             e = launch_alpha_merge(src, out, n_px, st);
         break;
     case Route::kDitherLists:
-        if (pl->choice) e = launch_dither_lists_map(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->t, plan_map(pl), (const uint8_t *)pl->aux,
-                                                    d_out, pl->format, st, cutoff);
-        else e = launch_dither_lists(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, pl->thr, (const uint8_t *)pl->aux, d_out, pl->format, st, cutoff);
+        e = launch_dither_lists(src, w, rows, row0, pl->d_cent, k, p->d_lut, pl->d_pal, plan_offsets(pl), (const uint8_t *)pl->aux, d_out, pl->format, st, cutoff);
         break;
     case Route::kDitherMasks:
         e = run_dither_masks(pl, src, w, rows, row0, d_out, st);

@@ -1,10 +1,14 @@
 // kmg_apply_dev.h -- the per-pixel output pass at full resolution as one __device__ function: find_centroid + swap + lab_to_rgb
 // (replace), or mix_colors.wgsl main_dither + lab_to_rgb (dither): the body of k_apply (kmg_kernels.hip), statement for statement,
 // with the tiles a workgroup takes as arguments -- a grid stride over the tiles of ONE image there, one tile of the image the
-// workgroup belongs to in k_batch_apply (kmg_batch_apply.hip).  k_apply itself keeps its own text: calling this
-// function from it changed the register allocation of its instantiations (llvm-objdump -d of the code object, compared kernel by
-// kernel), and the per-image kernels keep their code.  Only k (+1 sentinel) distinct output colours exist, so the Lab->sRGB8
-// conversion is done once per centroid on the host (pal[]).
+// workgroup belongs to in k_batch_apply (kmg_batch_apply.hip).  No threshold map here: a batch gives images with
+// a map their own per-image pass.  k_apply itself keeps its own text.  Calling this function from it (with the offsets type of
+// kmg_kernels.h as a last template parameter) was built and timed against the parent build (DESIGN.md 4.20,
+// profiles/r15_output_bodies_time.txt): all 36 instantiations came out 14 - 87 instructions shorter with 0 - 34 fewer VGPRs, the
+// 8192^2 passes 0 - 4 % faster, bytes identical -- and one of 17 rows, a 256 x 256 image at k = 256 with the blue-noise map,
+// 0.6 us (0.9 %) slower where the parent's own two turns differed by 0.1 us, which the acceptance rule set beforehand does not
+// allow.  Only k (+1 sentinel) distinct output colours exist, so the Lab->sRGB8 conversion is done once per centroid on the host
+// (pal[]).  c_bayer below is the one definition of the reference's matrix for the scan (k_apply reads it too).
 //
 // Compile with -ffp-contract=off: arithmetic must match kmg_math.h operation for operation.
 #pragma once

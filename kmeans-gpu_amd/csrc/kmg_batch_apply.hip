@@ -1,6 +1,6 @@
 // kmg_batch_apply.hip -- the output pass of many small images in one launch: the segmented version of the per-pixel output pass
-// k_apply<PPT, DITHER, CHUNKED, ALPHA, OutT> of kmg_kernels.hip (replace and dither; RGBA8, INDEX8, INDEX16; alpha mode on and off;
-// the chunked scan from k = 32) and kmg_dev_apply_batch on top of it (include/kmeans_hip.h at kmg_batch_apply_report).
+// k_apply<PPT, DITHER, CHUNKED, ALPHA, OutT, BayerOffsets> of kmg_kernels.hip (replace and dither with the reference's matrix; RGBA8,
+// INDEX8, INDEX16; alpha mode on and off; the chunked scan from k = 32) and kmg_dev_apply_batch on top of it (include/kmeans_hip.h at kmg_batch_apply_report).
 //
 // A launch reads a table of BatchApplyImage records in device memory, one per image.  Its grid is the sum of the images' tiles
 // (kBlock * PPT pixels each); a workgroup finds its image by the bounded binary search over the records' first-workgroup column

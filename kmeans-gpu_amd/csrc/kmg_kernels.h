@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace kmg {
 
 // Device centroid entry: (L, a, b, C = sqrt(a^2 + b^2)).  C is hoisted out of the per-pixel loop
@@ -117,31 +119,39 @@ hipError_t launch_alpha_merge(const uint32_t *rgba, uint32_t *out, uint64_t n, h
 // pixel's own alpha byte over the output's, an index format writes k where the pixel's alpha is below the cutoff.  pal is read by
 // RGBA8 only.  A format (or route) that does not exist: hipErrorInvalidValue, nothing launched.
 
+// ---- The offsets of KMG_MODE_DITHER, the last template parameter and a by-value argument of the kernels that dither per image
+// (k_apply, k_dither_lists): the reference's matrix, which the kernels carry in their code, or a threshold map
+// (include/kmeans_hip.h at kmg_dither_map).  A workgroup stages its offsets into LDS behind the sRGB table.
+// v: mw x mh values in device memory, row-major; the sides are powers of two, so pixel (x, y) reads
+// v[(x & xmask) + ((y & ymask) << xshift)].
+struct DitherMapDev { const float *v; uint32_t xmask, ymask, xshift; };
+static inline uint32_t dither_map_entries(const DitherMapDev &m) { return (m.xmask + 1u) * (m.ymask + 1u); }
+struct BayerOffsets { float threshold; };              // 16 offsets threshold * (M / 16 - 0.5): as a kernel argument, the float
+struct MapOffsets { float t; DitherMapDev map; };      // mw x mh offsets t * v, t = threshold * strength
+// (The two places where the forms differ -- staging the offsets, and which of them pixel (x, y) reads -- are `if constexpr (MAP)`
+// inside the two kernels, not helpers here: as inlined functions the 16-entry index came out with its operands in another order
+// and the staging loop four instructions longer (tools/compare_kernels.py), and the instantiations keep the code they had.)
+// The launchers take a MapOffsets: map.v == nullptr is the reference's matrix at threshold t (dither_offsets<BayerOffsets>).
+template <typename Off>
+inline Off dither_offsets(const MapOffsets &o)
+{
+    if constexpr (std::is_same<Off, MapOffsets>::value) return o; else return BayerOffsets{o.t};
+}
+
 // the list-based dither and meld passes (kmg_lists.hip); kmg_table.h declares them without alpha mode (RGBA8)
 hipError_t launch_meld_lists(const uint32_t *rgba, uint64_t n, const Centroid *cent, uint32_t k, const float *lut,
                              const uint8_t *lists, uint32_t *out, hipStream_t st, bool alpha);
 hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                               const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, void *out, int format,
+                               const float *lut, const uint32_t *pal, const MapOffsets &off, const uint8_t *lists, void *out, int format,
                                hipStream_t st, uint32_t alpha_cutoff);
 
-// replace / dither output pass.  pal: k+1 RGBA8 words (entry k = the converted sentinel).
-hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k, const float *lut,
-                        const uint32_t *pal, bool dither, float threshold, void *out, int format, hipStream_t st, uint32_t alpha_cutoff = 0);
-
-// ---- KMG_MODE_DITHER with a threshold map (include/kmeans_hip.h at kmg_dither_map).  v: mw x mh values in device
-// memory, row-major; the sides are powers of two, so pixel (x, y) reads v[(x & xmask) + ((y & ymask) << xshift)].  t = threshold *
-// strength; a workgroup stages t * v into LDS.
-struct DitherMapDev { const float *v; uint32_t xmask, ymask, xshift; };
-static inline uint32_t dither_map_entries(const DitherMapDev &m) { return (m.xmask + 1u) * (m.ymask + 1u); }
-// the dither body of launch_apply with the map (kmg_dither_map.hip: k_apply_map).  apply_map_lds_bytes: its dynamic LDS, which the
-// caller compares with device_info().lds_max (the launcher refuses a request above it: hipErrorInvalidValue)
+// replace / dither output pass.  pal: k+1 RGBA8 words (entry k = the converted sentinel).  off is read when `dither`.  With a map
+// the pass needs apply_map_lds_bytes of dynamic LDS, which the caller compares with device_info().lds_max (the launcher refuses a
+// request above it: hipErrorInvalidValue).
 size_t apply_map_lds_bytes(uint32_t k, uint32_t map_entries);
-hipError_t launch_apply_map(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k, const float *lut,
-                            const uint32_t *pal, float t, DitherMapDev map, void *out, int format, hipStream_t st, uint32_t alpha_cutoff);
-// launch_dither_lists with the map (kmg_lists.hip: k_dither_lists_map)
-hipError_t launch_dither_lists_map(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                                   const float *lut, const uint32_t *pal, float t, DitherMapDev map, const uint8_t *lists, void *out,
-                                   int format, hipStream_t st, uint32_t alpha_cutoff);
+hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k, const float *lut,
+                        const uint32_t *pal, bool dither, const MapOffsets &off, void *out, int format, hipStream_t st, uint32_t alpha_cutoff = 0);
+
 // launch_lab_candidates (kmg_table.h) of the dither pass for offsets in [off_lo, off_hi] instead of the reference matrix's
 // threshold * [-0.5, 0.4375]: the box of cells that get a list (speed only; cells outside mean "scan everything")
 hipError_t launch_lab_candidates_range(const Centroid *cent, uint32_t k, float off_lo, float off_hi, bool two_closest, uint8_t *lists,

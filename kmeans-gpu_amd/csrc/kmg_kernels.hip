@@ -20,6 +20,7 @@
 #include "kmg_device.h"
 #include "kmg_table_dev.h"       // lane_value, wave_min, wave_max_u32_dpp
 #include "kmg_lloyd_dev.h"       // argmin_scan, init_key_index, init_max_slot
+#include "kmg_apply_dev.h"       // c_bayer
 
 namespace kmg {
 
@@ -970,18 +971,24 @@ hipError_t launch_resize_band(const uint32_t *band, uint32_t w, uint32_t h, uint
 // mix_colors.wgsl main_dither + lab_to_rgb (dither).  Only k (+1 sentinel) distinct output colours
 // exist, so the Lab->sRGB8 conversion is done once per centroid on the host (pal[]).
 // ------------------------------------------------------------------------------------------
-__constant__ const float c_bayer[16] = {0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5};
-
 // OutT (kmg_device.h): uint32_t writes pal[label] (RGBA8), uint8_t / uint16_t the index (the alpha cutoff in bits 8..15 of
 // `aligned`)
-template <int PPT, bool DITHER, bool CHUNKED, bool ALPHA, typename OutT>
+// Off (kmg_kernels.h): the offsets of the dither pass -- BayerOffsets (also what the replace pass is instantiated with: it reads
+// none), or MapOffsets, DITHER only.
+// LDS (dynamic): [centroids kpad x 16 B][sRGB table 1 KiB][the offsets: 16, or mw x mh of a map]
+// A map's offsets lie row-major, so the four pixels of a lane read consecutive dwords and the lanes of a wave read at stride four:
+// four lanes per bank on a map 32 or 64 wide (MI355X: 32 banks per group of 32 lanes for a dword read), 8 LDS cycles instead of 2
+// for each of the 4 reads of a group of pixels -- against k x 4 centroid reads of the scan behind it.
+template <int PPT, bool DITHER, bool CHUNKED, bool ALPHA, typename OutT, typename Off>
 __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ rgba, uint32_t w,
                                                   uint64_t n, uint32_t row0,
                                                   const Centroid *__restrict__ cent, uint32_t k,
                                                   const float *__restrict__ lut,
-                                                  const uint32_t *__restrict__ pal, float threshold,
+                                                  const uint32_t *__restrict__ pal, Off off_arg,
                                                   OutT *__restrict__ out, int aligned)
 {
+    constexpr bool MAP = std::is_same<Off, MapOffsets>::value;
+    static_assert(DITHER || !MAP, "a map implies dither");
     extern __shared__ float4 smem4[];
     const uint32_t kpad = (k + 3u) & ~3u;
     float4 *s_cent = smem4;
@@ -990,10 +997,13 @@ __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ r
 
     s_lut[threadIdx.x] = lut[threadIdx.x];
     stage_centroids(s_cent, cent, k, kpad);
-    if (DITHER && threadIdx.x < 16) {
+    if constexpr (MAP) {
+        const uint32_t entries = (off_arg.map.xmask + 1u) * (off_arg.map.ymask + 1u);
+        for (uint32_t i = threadIdx.x; i < entries; i += kBlock) s_off[i] = off_arg.t * off_arg.map.v[i];    // off = t * v, one rounding
+    } else if (DITHER && threadIdx.x < 16) {
         // mix_colors.wgsl:21-27,70,72: threshold * (M[x%4 + 4*(y%4)] / 16 - 0.5)
         float iv = c_bayer[threadIdx.x] / 16.0f - 0.5f;
-        s_off[threadIdx.x] = threshold * iv;
+        s_off[threadIdx.x] = off_arg.threshold * iv;
     }
     __syncthreads();
 
@@ -1029,7 +1039,9 @@ __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ r
                 float L, a, b;
                 px_to_lab(s_lut, px[q], L, a, b);
                 if (DITHER) {
-                    const float off = s_off[(gx & 3u) + ((gy & 3u) << 2)];
+                    float off;
+                    if constexpr (MAP) off = s_off[(gx & off_arg.map.xmask) + ((gy & off_arg.map.ymask) << off_arg.map.xshift)];
+                    else off = s_off[(gx & 3u) + ((gy & 3u) << 2)];
                     L = L + off; a = a + off; b = b + off;         // :72
                     gx += 1;
                     if (gx == w) { gx = 0; gy += 1; }
@@ -1063,21 +1075,35 @@ __global__ __launch_bounds__(kBlock) void k_apply(const uint32_t *__restrict__ r
     }
 }
 
+size_t apply_map_lds_bytes(uint32_t k, uint32_t map_entries)
+{
+    return sizeof(float4) * ((k + 3u) & ~3u) + (256 + (size_t)map_entries) * sizeof(float);
+}
+
+// the grid is capped at kApplyGridCap workgroups of kBlock * kAssignPPT pixels: from kApplyGridCap * 2048 + 1 pixels on a workgroup
+// walks a second tile
+constexpr uint32_t kApplyGridCap = 2048;
+
 hipError_t launch_apply(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k, const float *lut,
-                        const uint32_t *pal, bool dither, float threshold, void *out, int format, hipStream_t st, uint32_t alpha_cutoff)
+                        const uint32_t *pal, bool dither, const MapOffsets &off, void *out, int format, hipStream_t st, uint32_t alpha_cutoff)
 {
     const uint64_t n = (uint64_t)w * rows;
     const uint64_t tiles = (n + (uint64_t)kBlock * kAssignPPT - 1) / ((uint64_t)kBlock * kAssignPPT);
-    const uint32_t grid = (uint32_t)(tiles < 2048 ? (tiles ? tiles : 1) : 2048);
-    const uint32_t kpad = (k + 3u) & ~3u;
+    const uint32_t grid = (uint32_t)(tiles < kApplyGridCap ? (tiles ? tiles : 1) : kApplyGridCap);
     const bool chunked = k >= 32;
-    const size_t lds = sizeof(float4) * kpad + (256 + 16) * sizeof(float);
+    const bool map = dither && off.map.v != nullptr;
+    // 48 KiB of centroids at KMG_MAX_K and 16 KiB of a 64 x 64 map are above the 64 KiB every device has: gfx950 gives a
+    // workgroup up to 160 KiB
+    const size_t lds = apply_map_lds_bytes(k, map ? dither_map_entries(off.map) : 16u);
+    if (map && lds > device_info().lds_max) return hipErrorInvalidValue;
     const bool known = with_out_type(format, [&](auto t) {
         using OutT = typename decltype(t)::type;
         const int flags = output_flags<OutT>(rgba, out, alpha_cutoff);
-        with_bool(dither, [&](auto D) { with_bool(chunked, [&](auto C) { with_bool(alpha_cutoff != 0, [&](auto A) {
-            hipLaunchKernelGGL((k_apply<kAssignPPT, D(), C(), A(), OutT>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut,
-                               kIndexOut<OutT> ? nullptr : pal, threshold, static_cast<OutT *>(out), flags);
+        // replace, dither, dither with a map
+        with_value<0, 1, 2>(map ? 2 : dither ? 1 : 0, [&](auto D) { with_bool(chunked, [&](auto C) { with_bool(alpha_cutoff != 0, [&](auto A) {
+            using Off = std::conditional_t<D() == 2, MapOffsets, BayerOffsets>;
+            hipLaunchKernelGGL((k_apply<kAssignPPT, D() != 0, C(), A(), OutT, Off>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k,
+                               lut, kIndexOut<OutT> ? nullptr : pal, dither_offsets<Off>(off), static_cast<OutT *>(out), flags);
         }); }); });
     });
     return known ? hipGetLastError() : hipErrorInvalidValue;

@@ -305,13 +305,17 @@ __device__ __forceinline__ void walk_list(const uint8_t *__restrict__ lists, uin
 
 // OutT (kmg_device.h): uint32_t writes pal[label] (RGBA8), uint8_t / uint16_t the index (the alpha cutoff in bits 8..15 of
 // `aligned`)
-template <int HALVES, bool ALPHA, typename OutT>
+// Off (kmg_kernels.h): BayerOffsets, the 16 offsets of the reference's matrix, or MapOffsets, the mw x mh offsets t * v of a
+// threshold map (include/kmeans_hip.h at kmg_dither_map); either way staged behind the sRGB table.  The lists are
+// over cells of Lab and serve any offset.
+template <int HALVES, bool ALPHA, typename OutT, typename Off>
 __global__ __launch_bounds__(kBlock) void k_dither_lists(const uint32_t *__restrict__ rgba, uint32_t w, uint64_t n,
                                                          uint32_t row0, const Centroid *__restrict__ cent, uint32_t k,
                                                          const float *__restrict__ lut, const uint32_t *__restrict__ pal,
-                                                         float threshold, const uint8_t *__restrict__ lists,
+                                                         Off off_arg, const uint8_t *__restrict__ lists,
                                                          OutT *__restrict__ out, int aligned)
 {
+    constexpr bool MAP = std::is_same<Off, MapOffsets>::value;
     extern __shared__ float4 smem4[];
     constexpr uint32_t kpad = 256u * HALVES;                       // every (half, byte) indexes the table: entries k .. are far away
     float4 *s_cent = smem4;
@@ -329,7 +333,12 @@ __global__ __launch_bounds__(kBlock) void k_dither_lists(const uint32_t *__restr
         if (j < k) { const Centroid ce = cent[j]; c = make_float4(ce.L, ce.a, ce.b, ce.C); }
         s_cent[j] = c;
     }
-    if (threadIdx.x < 16) s_off[threadIdx.x] = threshold * (bayer16(threadIdx.x) / 16.0f - 0.5f);
+    if constexpr (MAP) {
+        const uint32_t entries = (off_arg.map.xmask + 1u) * (off_arg.map.ymask + 1u);
+        for (uint32_t i = threadIdx.x; i < entries; i += kBlock) s_off[i] = off_arg.t * off_arg.map.v[i];    // off = t * v, one rounding
+    } else {
+        if (threadIdx.x < 16) s_off[threadIdx.x] = off_arg.threshold * (bayer16(threadIdx.x) / 16.0f - 0.5f);
+    }
     __syncthreads();
     constexpr uint64_t TILE = (uint64_t)kBlock * 4;
     const uint64_t tiles = (n + TILE - 1) / TILE;
@@ -345,7 +354,9 @@ __global__ __launch_bounds__(kBlock) void k_dither_lists(const uint32_t *__restr
         uint4 rec[4][2];                                            // the four pixels' lists (first half)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const uint32_t bi = (gx & 3u) + ((gy & 3u) << 2);
+            uint32_t bi;
+            if constexpr (MAP) bi = (gx & off_arg.map.xmask) + ((gy & off_arg.map.ymask) << off_arg.map.xshift);
+            else bi = (gx & 3u) + ((gy & 3u) << 2);
             px_to_lab(s_lut, px[q], pL[q], pa[q], pb[q]);
             const float off = s_off[bi];
             pL[q] = pL[q] + off; pa[q] = pa[q] + off; pb[q] = pb[q] + off;   // mix_colors.wgsl:72
@@ -427,167 +438,32 @@ hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, 
                                const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, uint32_t *out,
                                hipStream_t st)
 {
-    return launch_dither_lists(rgba, w, rows, row0, cent, k, lut, pal, threshold, lists, out, KMG_FORMAT_RGBA8, st, 0);
+    return launch_dither_lists(rgba, w, rows, row0, cent, k, lut, pal, MapOffsets{threshold, {}}, lists, out, KMG_FORMAT_RGBA8, st, 0);
 }
 
+// the grid is capped at kDitherListsGridCap workgroups of kBlock * 4 pixels: from kDitherListsGridCap * 1024 + 1 pixels on a
+// workgroup walks a second tile
+constexpr uint32_t kDitherListsGridCap = 8192;
+
 hipError_t launch_dither_lists(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                               const float *lut, const uint32_t *pal, float threshold, const uint8_t *lists, void *out, int format,
+                               const float *lut, const uint32_t *pal, const MapOffsets &off, const uint8_t *lists, void *out, int format,
                                hipStream_t st, uint32_t alpha_cutoff)
 {
     if (k > kLabListMaxK) return hipErrorInvalidValue;
     const uint64_t n = (uint64_t)w * rows;
     const uint64_t tiles = (n + kBlock * 4 - 1) / (kBlock * 4);
-    const uint32_t grid = (uint32_t)(tiles < 8192 ? (tiles ? tiles : 1) : 8192);
+    const uint32_t grid = (uint32_t)(tiles < kDitherListsGridCap ? (tiles ? tiles : 1) : kDitherListsGridCap);
     const int halves = k > 256u ? 2 : 1;
-    const size_t lds = sizeof(float4) * 256 * halves + (256 + 16) * sizeof(float);
+    const bool map = off.map.v != nullptr;
+    const size_t lds = sizeof(float4) * 256 * halves + (256 + (size_t)(map ? dither_map_entries(off.map) : 16u)) * sizeof(float);   // at most 25 KiB
     const bool known = with_out_type(format, [&](auto t) {
         using OutT = typename decltype(t)::type;
         const int flags = output_flags<OutT>(rgba, out, alpha_cutoff);
-        with_value<1, 2>(halves, [&](auto H) { with_bool(alpha_cutoff != 0, [&](auto A) {
-            hipLaunchKernelGGL((k_dither_lists<H(), A(), OutT>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut,
-                               kIndexOut<OutT> ? nullptr : pal, threshold, lists, static_cast<OutT *>(out), flags);
-        }); });
-    });
-    return known ? hipGetLastError() : hipErrorInvalidValue;
-}
-
-// k_dither_lists with a threshold map (include/kmeans_hip.h at kmg_dither_map): its text with the 16 offsets of the
-// reference's matrix replaced by the mw x mh offsets t * v (kmg_kernels.h DitherMapDev), staged behind the sRGB table.  A kernel of
-// its own, so that k_dither_lists keeps its code; the lists are over cells of Lab and serve any offset.
-template <int HALVES, bool ALPHA, typename OutT>
-__global__ __launch_bounds__(kBlock) void k_dither_lists_map(const uint32_t *__restrict__ rgba, uint32_t w, uint64_t n,
-                                                         uint32_t row0, const Centroid *__restrict__ cent, uint32_t k,
-                                                         const float *__restrict__ lut, const uint32_t *__restrict__ pal,
-                                                         float t, DitherMapDev map, const uint8_t *__restrict__ lists,
-                                                         OutT *__restrict__ out, int aligned)
-{
-    extern __shared__ float4 smem4[];
-    constexpr uint32_t kpad = 256u * HALVES;                       // every (half, byte) indexes the table: entries k .. are far away
-    float4 *s_cent = smem4;
-    // the kernel has no static LDS, so its dynamic LDS -- the centroid table first -- starts at LDS address 0 (entry_key)
-    if ((uint32_t)reinterpret_cast<uintptr_t>(s_cent) != 0u) __builtin_trap();
-    float *s_lut = reinterpret_cast<float *>(smem4 + kpad);
-    float *s_off = s_lut + 256;
-    const float sentinel_C = chroma(10000.0f, 10000.0f);
-    s_lut[threadIdx.x] = lut[threadIdx.x];
-    static_assert(kBlock == 256, "one table entry per thread and half");
-#pragma unroll
-    for (uint32_t h = 0; h < (uint32_t)HALVES; ++h) {
-        const uint32_t j = h * 256u + threadIdx.x;
-        float4 c = make_float4(1.0e18f, 0.0f, 0.0f, 0.0f);       // key ~ 1e36: far above the sentinel's
-        if (j < k) { const Centroid ce = cent[j]; c = make_float4(ce.L, ce.a, ce.b, ce.C); }
-        s_cent[j] = c;
-    }
-    const uint32_t entries = (map.xmask + 1u) * (map.ymask + 1u);
-    for (uint32_t i = threadIdx.x; i < entries; i += kBlock) s_off[i] = t * map.v[i];    // off = t * v, one rounding
-    __syncthreads();
-    constexpr uint64_t TILE = (uint64_t)kBlock * 4;
-    const uint64_t tiles = (n + TILE - 1) / TILE;
-    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const uint64_t i0 = tile * TILE + (uint64_t)threadIdx.x * 4;
-        uint32_t px[4];
-        load4_stream(rgba, i0, n, kIndexOut<OutT> ? (aligned & 1) != 0 : aligned != 0, px);
-        const uint32_t i32 = (uint32_t)i0;                          // n < 2^32
-        uint32_t gy = i32 / w, gx = i32 - gy * w;
-        gy += row0;
-        float pL[4], pa[4], pb[4];
-        uint32_t cell[4];
-        uint4 rec[4][2];                                            // the four pixels' lists (first half)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t bi = (gx & map.xmask) + ((gy & map.ymask) << map.xshift);
-            px_to_lab(s_lut, px[q], pL[q], pa[q], pb[q]);
-            const float off = s_off[bi];
-            pL[q] = pL[q] + off; pa[q] = pa[q] + off; pb[q] = pb[q] + off;   // mix_colors.wgsl:72
-            cell[q] = lab_cell_index(pL[q], pa[q], pb[q]);
-            const uint4 *r = reinterpret_cast<const uint4 *>(lists + list_record_offset(HALVES, 0u, 0u, cell[q]));
-            rec[q][0] = r[0]; rec[q][1] = r[1];
-            gx += 1;
-            if (gx == w) { gx = 0; gy += 1; }
-        }
-        uint32_t res[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const PixelTerms pt = pixel_terms_fast(pL[q], pa[q], pb[q], chroma(pa[q], pb[q]));
-            // mix_colors.wgsl:73-80 starts the scan at the sentinel (10000, 10000, 10000), index k.  Its key is not computed here: a
-            // pixel whose smallest key is not below kSentinelFloor -- (10000 - L)^2 alone is above that for every L < 9000, and no
-            // centroid of a palette in Lab is 1000 units from a pixel -- goes to the literal scan below, which starts at the
-            // sentinel and is exact for any input.
-            constexpr uint32_t kSentinelFloor = 0x49742400u;          // 1.0e6f
-            uint32_t best = 0x7F7FFF00u, second = 0x7F7FFFFFu;
-            uint4 next0 = make_uint4(0u, 0u, 0u, 0u), next1 = next0;
-            if (HALVES == 2) {                                       // the second half's record, in flight during the first walk
-                const uint4 *r = reinterpret_cast<const uint4 *>(lists + list_record_offset(HALVES, 1u, 0u, cell[q]));
-                next0 = r[0]; next1 = r[1];
-            }
-            walk_list<HALVES>(lists, cell[q], 0u, rec[q][0], rec[q][1], pt, k, best, second);
-            uint32_t idx = best & 255u;
-            if (HALVES == 2) {
-                // the halves apart, then merged; packed keys that differ in their low byte only are a near-tie (decided below)
-                uint32_t best1 = 0x7F7FFF00u, second1 = 0x7F7FFFFFu;
-                walk_list<HALVES>(lists, cell[q], 1u, next0, next1, pt, k, best1, second1);
-                const bool from1 = best1 < best;
-                idx = from1 ? 256u + (best1 & 255u) : idx;
-                second = min(max(best, best1), min(second, second1));
-                best = min(best, best1);
-            }
-            const float thr = tie_threshold(__uint_as_float(best));
-            // (two halves: the runner-up without its index byte.  At a key of exactly 0 -- the pixel lies on two equal centroids, one
-            // in each half -- the threshold is 0 too and the index bytes alone would order the pair, the second half's low byte first)
-            const bool near = __uint_as_float(HALVES == 2 ? second & ~255u : second) <= thr || best >= kSentinelFloor || !(pt.L < 9000.0f);
-            if (__ballot(near)) {
-                // near-tie (kmg_math.h): mix_colors.wgsl:73-80 with the literal distance, the sentinel first, same order.  Rare:
-                // the lists are read again, byte by byte
-                float lb = cie94_c(pt.L, pt.a, pt.b, pt.C, 10000.0f, 10000.0f, 10000.0f, sentinel_C);
-                uint32_t li = k;
-                if (near) {
-                    for (uint32_t h = 0; h < (uint32_t)HALVES; ++h) {
-                        const uint8_t *first = lists + list_record_offset(HALVES, h, 0u, cell[q]);
-                        const uint8_t *cont = lists + list_record_offset(HALVES, h, 1u, cell[q]);
-                        const uint32_t cnt = first[0];
-                        const uint32_t n_half = min(k - h * 256u, 256u);
-                        const uint32_t steps = cnt == 255u ? n_half : cnt;
-                        for (uint32_t i = 0; i < steps; ++i) {
-                            const uint32_t j = h * 256u + (cnt == 255u ? i : (uint32_t)(i < kListBytes - 1u ? first[1u + i] : cont[i - (kListBytes - 1u)]));
-                            const float4 c = s_cent[j];
-                            if (cie94_key(pt, c.x, c.y, c.z, c.w) <= thr) {
-                                const float d = cie94_c(pt.L, pt.a, pt.b, pt.C, c.x, c.y, c.z, c.w);
-                                if (d < lb) { lb = d; li = j; }
-                            }
-                        }
-                    }
-                    idx = li;
-                }
-            }
-            if constexpr (kIndexOut<OutT>) res[q] = index_of<ALPHA>(idx, px[q], ((uint32_t)aligned >> 8) & 255u, k);
-            else res[q] = with_alpha<ALPHA>(pal[idx], px[q]);
-        }
-        if constexpr (kIndexOut<OutT>) store4_index<OutT, true>(out, i0, n, (aligned & 1) != 0, res);
-        else store4_stream(out, i0, n, aligned != 0, res);
-    }
-}
-
-// the grid is capped at kListsMapGridCap workgroups of kBlock * 4 pixels: from kListsMapGridCap * 1024 + 1 pixels on a workgroup
-// walks a second tile
-constexpr uint32_t kListsMapGridCap = 8192;
-
-hipError_t launch_dither_lists_map(const uint32_t *rgba, uint32_t w, uint32_t rows, uint32_t row0, const Centroid *cent, uint32_t k,
-                                   const float *lut, const uint32_t *pal, float t, DitherMapDev map, const uint8_t *lists, void *out,
-                                   int format, hipStream_t st, uint32_t alpha_cutoff)
-{
-    if (k > kLabListMaxK) return hipErrorInvalidValue;
-    const uint64_t n = (uint64_t)w * rows;
-    const uint64_t tiles = (n + kBlock * 4 - 1) / (kBlock * 4);
-    const uint32_t grid = (uint32_t)(tiles < kListsMapGridCap ? (tiles ? tiles : 1) : kListsMapGridCap);
-    const int halves = k > 256u ? 2 : 1;
-    const size_t lds = sizeof(float4) * 256 * halves + (256 + (size_t)dither_map_entries(map)) * sizeof(float);   // at most 25 KiB
-    const bool known = with_out_type(format, [&](auto ot) {
-        using OutT = typename decltype(ot)::type;
-        const int flags = output_flags<OutT>(rgba, out, alpha_cutoff);
-        with_value<1, 2>(halves, [&](auto H) { with_bool(alpha_cutoff != 0, [&](auto A) {
-            hipLaunchKernelGGL((k_dither_lists_map<H(), A(), OutT>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut,
-                               kIndexOut<OutT> ? nullptr : pal, t, map, lists, static_cast<OutT *>(out), flags);
-        }); });
+        with_value<1, 2>(halves, [&](auto H) { with_bool(alpha_cutoff != 0, [&](auto A) { with_bool(map, [&](auto M) {
+            using Off = std::conditional_t<M(), MapOffsets, BayerOffsets>;
+            hipLaunchKernelGGL((k_dither_lists<H(), A(), OutT, Off>), dim3(grid), dim3(kBlock), lds, st, rgba, w, n, row0, cent, k, lut,
+                               kIndexOut<OutT> ? nullptr : pal, dither_offsets<Off>(off), lists, static_cast<OutT *>(out), flags);
+        }); }); });
     });
     return known ? hipGetLastError() : hipErrorInvalidValue;
 }

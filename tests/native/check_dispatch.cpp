@@ -3,8 +3,8 @@
 //   for an input it does not list it calls nothing and says so (false);
 //   the nests the launchers use map the full cross product of their runtime inputs onto as many DISTINCT template tuples, each
 //   equal to its inputs -- stand-in function templates with the kernels' parameter lists record the tuple they were instantiated
-//   with: k_apply (3 formats x alpha x dither x chunked = 24), k_dither_lists (3 formats x halves x alpha = 12), diffusion
-//   (route x alpha x format x skew = 36).
+//   with: k_apply (3 formats x alpha x chunked x {replace, dither, dither with a map} = 36), k_dither_lists (3 formats x halves x
+//   alpha x {the reference's matrix, a map} = 24), diffusion (route x alpha x format x skew = 36).
 #include <cstdint>
 #include <cstdio>
 #include <set>
@@ -23,9 +23,19 @@ template <typename T> constexpr int format_of() { return std::is_same<T, uint32_
 
 typedef std::tuple<int, int, int, int> Tuple;
 
+// the offsets types of the dither kernels (kmg_kernels.h), as the launchers choose between them
+struct BayerOffsets {};
+struct MapOffsets {};
+template <class Off> constexpr int map_of() { return std::is_same<Off, MapOffsets>::value ? 1 : std::is_same<Off, BayerOffsets>::value ? 0 : -1; }
+
 // stand-ins with the kernels' template parameter lists
-template <int PPT, bool D, bool C, bool A, class OutT> static Tuple apply_standin() { static_assert(PPT == 8, ""); return Tuple(D, C, A, format_of<OutT>()); }
-template <int H, bool A, class OutT> static Tuple lists_standin() { return Tuple(H, A, format_of<OutT>(), 0); }
+template <int PPT, bool D, bool C, bool A, class OutT, class Off> static Tuple apply_standin()
+{
+    static_assert(PPT == 8, "");
+    static_assert(D || map_of<Off>() == 0, "a map implies dither");
+    return Tuple(D + map_of<Off>(), C, A, format_of<OutT>());         // 0 replace, 1 dither, 2 dither with a map
+}
+template <int H, bool A, class OutT, class Off> static Tuple lists_standin() { return Tuple(H, A, format_of<OutT>(), map_of<Off>()); }
 template <int R, bool A, class OutT, int S> static Tuple diffuse_standin() { return Tuple(R, A, format_of<OutT>(), S); }
 
 static void helpers()
@@ -76,40 +86,44 @@ static void nests()
     int calls = 0;
     for (int format = 0; format < 3; ++format)
         for (int alpha = 0; alpha < 2; ++alpha)
-            for (int dither = 0; dither < 2; ++dither)
+            for (int pass = 0; pass < 3; ++pass)                       // replace, dither, dither with a map
                 for (int chunked = 0; chunked < 2; ++chunked) {
+                    const bool dither = pass != 0, map = pass == 2;
                     const bool known = with_out_type(format, [&](auto t) {
                         using OutT = typename decltype(t)::type;
-                        with_bool(dither != 0, [&](auto D) { with_bool(chunked != 0, [&](auto C) { with_bool(alpha != 0, [&](auto A) {
-                            const Tuple got = apply_standin<8, D(), C(), A(), OutT>();
+                        with_value<0, 1, 2>(map ? 2 : dither ? 1 : 0, [&](auto D) { with_bool(chunked != 0, [&](auto C) { with_bool(alpha != 0, [&](auto A) {
+                            using Off = std::conditional_t<D() == 2, MapOffsets, BayerOffsets>;
+                            const Tuple got = apply_standin<8, D() != 0, C(), A(), OutT, Off>();
                             ++calls;
-                            CHECK(got == Tuple(dither, chunked, alpha, format));
+                            CHECK(got == Tuple(pass, chunked, alpha, format));
                             seen.insert(got);
                         }); }); });
                     });
                     CHECK(known);
                 }
-    CHECK(calls == 24 && seen.size() == 24);
-    CHECK(!with_out_type(3, [&](auto) { ++calls; }) && calls == 24);
+    CHECK(calls == 36 && seen.size() == 36);
+    CHECK(!with_out_type(3, [&](auto) { ++calls; }) && calls == 36);
 
     // launch_dither_lists (kmg_lists.hip)
     seen.clear();
     calls = 0;
     for (int format = 0; format < 3; ++format)
         for (int halves = 1; halves <= 2; ++halves)
-            for (int alpha = 0; alpha < 2; ++alpha) {
-                const bool known = with_out_type(format, [&](auto t) {
-                    using OutT = typename decltype(t)::type;
-                    with_value<1, 2>(halves, [&](auto H) { with_bool(alpha != 0, [&](auto A) {
-                        const Tuple got = lists_standin<H(), A(), OutT>();
-                        ++calls;
-                        CHECK(got == Tuple(halves, alpha, format, 0));
-                        seen.insert(got);
-                    }); });
-                });
-                CHECK(known);
-            }
-    CHECK(calls == 12 && seen.size() == 12);
+            for (int alpha = 0; alpha < 2; ++alpha)
+                for (int map = 0; map < 2; ++map) {
+                    const bool known = with_out_type(format, [&](auto t) {
+                        using OutT = typename decltype(t)::type;
+                        with_value<1, 2>(halves, [&](auto H) { with_bool(alpha != 0, [&](auto A) { with_bool(map != 0, [&](auto M) {
+                            using Off = std::conditional_t<M(), MapOffsets, BayerOffsets>;
+                            const Tuple got = lists_standin<H(), A(), OutT, Off>();
+                            ++calls;
+                            CHECK(got == Tuple(halves, alpha, format, map));
+                            seen.insert(got);
+                        }); }); });
+                    });
+                    CHECK(known);
+                }
+    CHECK(calls == 24 && seen.size() == 24);
 
     // launch_diffuse_wide (kmg_diffuse_wide.hip); launch_diffuse is the same nest without the skew.  An input outside the sets
     // launches nothing.

@@ -13,7 +13,7 @@ NATIVE = os.path.join(ROOT, "tests", "native")
 @pytest.mark.parametrize("flags", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]], ids=["plain", "sanitized"])
 def test_every_helper_and_every_nest(tmp_path, flags):
     """every helper calls its lambda exactly once with the tag of a listed input and not at all for an unlisted one (and reports
-    which); the nests of launch_apply (24 tuples), launch_dither_lists (12) and the diffusion launchers (36) reach as many distinct
+    which); the nests of launch_apply (36 tuples), launch_dither_lists (24) and the diffusion launchers (36) reach as many distinct
     template tuples, each equal to its runtime inputs"""
     exe = str(tmp_path / "check_dispatch")
     subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", *flags, "-I", os.path.join(ROOT, "kmeans-gpu_amd", "csrc"),

@@ -1,4 +1,4 @@
-"""KMG_MODE_DITHER with a threshold map on the device (kmg_dither_map.hip: k_apply_map; kmg_lists.hip: k_dither_lists_map) against the
+"""KMG_MODE_DITHER with a threshold map on the device (the MapOffsets instantiations of k_apply and k_dither_lists) against the
 test-side reference of the contract (tests/dither_map_ref.py), byte for byte: every built-in map and three custom ones on both
 routes, in every format, with and without alpha mode; the LDS bound; bands; strengths; a workgroup that walks two tiles in each
 kernel; the custom copy of the reference's matrix against the kernels of the default; the sticky rules; the refusals.
@@ -192,7 +192,7 @@ def test_strengths_equal_the_reference(torch_cuda, dproc, oracle, strength):
         for strategy in ("scan", "table"):
             kg.set_strategy(strategy)
             assert np.array_equal(_apply(torch_cuda, dproc, host, cent, "index8"), lab.astype(np.uint8)), (name, strategy)
-    # the reference's matrix at another strength runs the map kernels too
+    # the reference's matrix at another strength runs the map instantiations too
     dproc.set_dither("bayer4", strength)
     lab4 = R.labels(oracle, host, cent, R.BAYER4, 16, strength)
     for strategy in ("scan", "table"):
@@ -203,27 +203,35 @@ def test_strengths_equal_the_reference(torch_cuda, dproc, oracle, strength):
 
 
 # ---- 6. a workgroup that walks two tiles ---------------------------------------------------------------------------------------------------
-# k_apply_map: the grid is capped at 2048 workgroups of 256 threads x 8 pixels (kApplyMapGridCap, kmg_dither_map.hip), so some
-# workgroup takes a second tile from 2048 * 2048 + 1 = 4 194 305 pixels on; 2049 x 2048 = 4 196 352 is the smallest image of odd
-# width 2049 above that (2049 tiles).  k_dither_lists_map: 8192 workgroups of 256 x 4 pixels (kListsMapGridCap, kmg_lists.hip), a
-# second tile from 8192 * 1024 + 1 = 8 388 609 pixels on; 2049 x 4095 = 8 390 655 is the smallest of that width (8194 tiles).
-@pytest.mark.parametrize("strategy,w,h", [("scan", 2049, 2048), ("table", 2049, 4095)])
-def test_a_workgroup_walks_two_tiles(torch_cuda, dproc, oracle, strategy, w, h):
+# k_apply: the grid is capped at 2048 workgroups of 256 threads x 8 pixels (kApplyGridCap, kmg_kernels.hip), so some workgroup
+# takes a second tile from 2048 * 2048 + 1 = 4 194 305 pixels on; 2049 x 2048 = 4 196 352 is the smallest image of odd width 2049
+# above that (2049 tiles).  k_dither_lists: 8192 workgroups of 256 x 4 pixels (kDitherListsGridCap, kmg_lists.hip), a second tile
+# from 8192 * 1024 + 1 = 8 388 609 pixels on; 2049 x 4095 = 8 390 655 is the smallest of that width (8194 tiles).  A map and the
+# default choice are instantiations of the same two kernels behind the same two launchers: both walk.
+@pytest.mark.parametrize("strategy,w,h,choice", [pytest.param("scan", 2049, 2048, "blue", id="scan-2049-2048"),
+                                                 pytest.param("table", 2049, 4095, "blue", id="table-2049-4095"),
+                                                 pytest.param("scan", 2049, 2048, "default", id="scan-2049-2048-default"),
+                                                 pytest.param("table", 2049, 4095, "default", id="table-2049-4095-default")])
+def test_a_workgroup_walks_two_tiles(torch_cuda, dproc, oracle, strategy, w, h, choice):
     import kmeans_gpu_amd as kg
     tile = 2048 if strategy == "scan" else 1024
     cap = 2048 if strategy == "scan" else 8192
     assert (w * h + tile - 1) // tile > cap >= ((w * (h - 1)) + tile - 1) // tile and w % 2 == 1
     kg.set_strategy(strategy)
-    entry = _maps()["blue"]
-    _set(dproc, entry)
     host = _noise(h, w, w + h)
     cent = kg.palette_to_centroids(_palette(8, 808))
+    if choice == "default":
+        dproc.set_dither(0, 1.0)
+        want = oracle.dither(oracle.rgb_to_lab(host), w, h, cent).reshape(h, w).astype(np.uint8)
+    else:
+        entry = _maps()[choice]
+        _set(dproc, entry)
+        want = R.labels(oracle, host, cent, entry[1], entry[2]).astype(np.uint8)
     got = _apply(torch_cuda, dproc, host, cent, "index8")
-    want = R.labels(oracle, host, cent, entry[1], entry[2]).astype(np.uint8)
     assert np.array_equal(got, want)
 
 
-# ---- 7. the custom copy of the reference's matrix through the new kernels = the default through the old ones ---------------------------
+# ---- 7. the custom copy of the reference's matrix through the map instantiations = the default through the Bayer ones ---------------------------
 @pytest.mark.parametrize("strategy", ["scan", "table"])
 def test_custom_copy_of_the_reference_matrix_equals_a_fresh_default_processor(torch_cuda, dproc, oracle, strategy):
     import kmeans_gpu_amd as kg
@@ -238,7 +246,7 @@ def test_custom_copy_of_the_reference_matrix_equals_a_fresh_default_processor(to
                 for fmt in ("rgba8", "index16"):
                     dproc.set_dither(0, 1.0)
                     old = _apply(torch_cuda, fresh, host, cent, fmt)
-                    assert np.array_equal(_apply(torch_cuda, dproc, host, cent, fmt), old)          # the default choice: the old kernels
+                    assert np.array_equal(_apply(torch_cuda, dproc, host, cent, fmt), old)          # the default choice: the Bayer instantiations
                     dproc.set_dither(R.BAYER4, 1.0, levels=16)
                     assert dproc.dither_map == kg.DitherMap.Custom
                     assert np.array_equal(_apply(torch_cuda, dproc, host, cent, fmt), old), (k, cutoff, fmt)
@@ -285,7 +293,7 @@ def test_the_other_modes_ignore_the_choice(dproc):
 def test_host_calls_follow_the_processor(torch_cuda, dproc, oracle):
     """find against the reference; reduce, reduce_indexed, reduce_quality and reduce_indexed_batch against each other, against the
     default (they must differ) and -- the palette step does not read the choice, so the centroids are the same -- under the custom
-    copy of the reference's matrix (the map kernels) against the default (the old kernels), which they must equal"""
+    copy of the reference's matrix (the map instantiations) against the default (the Bayer instantiations), which they must equal"""
     import kmeans_gpu_amd as kg
     D = kg.ReduceMode.Dither
     k = 6

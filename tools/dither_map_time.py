@@ -6,9 +6,11 @@ and blue-noise maps, on the scan route (KMG_STRATEGY_SCAN) and the list route (K
 repeat in one process, median and spread (min .. max) over the repeats, and the ratio of each map to the default of the same
 route.
 
-With --parent-lib PATH (a libkmeans_hip.so built from the parent commit) the default choice is also timed in fresh child
-processes, parent library and this one in turn (A B A B), and the SHA-256 of their outputs compared: its kernels are meant to be
-untouched.
+With --parent-lib PATH (a libkmeans_hip.so built from the parent commit) fresh child processes then time, parent library and this
+one in turn (A B A B): the default choice on both routes and, on the scan route, Bayer 8, the blue-noise map and the replace pass
+at the same k, and the dither pass of a 256 x 256 image at k = 256 (the reference's default call).  Per pass the medians of the
+four turns, B's excess over A beside the difference of A's own two medians, and whether the SHA-256 of the outputs agree.  "This
+one" is what KMG_LIBRARY names when the tool starts, else the tree's build.
     python tools/dither_map_time.py [repeats] [--parent-lib PATH]        (writes the table to stdout)"""
 import hashlib, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,8 +23,8 @@ args = [a for a in sys.argv[1:]]
 parent_lib = None
 if "--parent-lib" in args:
     i = args.index("--parent-lib"); parent_lib = args[i + 1]; del args[i:i + 2]
-default_only = "--default-only" in args                 # (the child processes: the default choice through whatever library KMG_LIBRARY names)
-args = [a for a in args if a != "--default-only"]
+child = "--child" in args                               # (the child processes: the passes below through whatever library KMG_LIBRARY names)
+args = [a for a in args if a != "--child"]
 reps = int(args[0]) if args else 7
 SIDE = 8192
 KS = [8, 64, 256]
@@ -42,33 +44,39 @@ def centroids(k):
     return kg.palette_to_centroids(pal)
 
 
-def one_pass(cent):
-    """(pass ms, build + pass ms)"""
+def one_pass(cent, mode=kg.ReduceMode.Dither, side=SIDE):
+    """(pass ms, build + pass ms) on the first side x side pixels"""
     e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
     torch.cuda.synchronize()
     e0.record()
-    plan = proc.apply_plan(cent, kg.ReduceMode.Dither, SIDE * SIDE, st)
+    plan = proc.apply_plan(cent, mode, side * side, st)
     e1.record()
-    plan.run(photo.data_ptr(), SIDE, SIDE, 0, out.data_ptr(), st)
+    plan.run(photo.data_ptr(), side, side, 0, out.data_ptr(), st)
     e2.record()
     torch.cuda.synchronize()
     plan.close()
     return e1.elapsed_time(e2), e0.elapsed_time(e2)
 
 
-def digest():
-    return hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()
+def digest(side=SIDE):
+    return hashlib.sha256(out[:side * side].cpu().numpy().tobytes()).hexdigest()
 
 
-if default_only:
+if child:
+    # (route, k, what, mode, map, side): the default choice on both routes; on the scan route, where one kernel body serves them
+    # all, also two maps, the replace pass, and the reference's default call (a 256 x 256 working image at k = 256)
+    D, R = kg.ReduceMode.Dither, kg.ReduceMode.Replace
+    cases = [(route, k, "", D, "bayer4", SIDE) for route in ROUTES for k in KS]
+    cases += [("scan", k, what, mode, m, SIDE) for k in KS for what, mode, m in ((" bayer8", D, "bayer8"), (" blue64", D, "blue"), (" replace", R, "bayer4"))]
+    cases += [("scan", 256, " 256^2", D, "bayer4", 256), ("scan", 256, " 256^2 blue64", D, "blue", 256)]
     res = {}
-    for route in ROUTES:
+    for route, k, what, mode, m, side in cases:
         kg.set_strategy(route)
-        for k in KS:
-            cent = centroids(k)
-            t = [one_pass(cent) for _ in range(reps + 1)][1:]
-            res[f"{route} {k}"] = {"ms": [a for a, _ in t], "total": [b for _, b in t], "sha256": digest()}
-    print("DEFAULT " + json.dumps(res), flush=True)
+        proc.set_dither(m, 1.0)
+        cent = centroids(k)
+        t = [one_pass(cent, mode, side) for _ in range(reps + 1)][1:]
+        res[f"{route} {k}{what}"] = {"ms": [a for a, _ in t], "total": [b for _, b in t], "sha256": digest(side)}
+    print("CHILD " + json.dumps(res), flush=True)
     sys.exit(0)
 
 # bayer16 as 16 x 16 and tiled to 64 x 64: the same offsets for every pixel, so the pair differs in the LDS table's width alone (the
@@ -99,24 +107,25 @@ for route in ROUTES:
 proc.set_dither(0, 1.0)
 
 if parent_lib:
-    print(f"# the default choice, fresh processes in turn: the parent commit's library (A) and this one (B), {reps} warm repeats each", flush=True)
+    print(f"# fresh processes in turn: the parent commit's library (A) and this one (B), {reps} warm repeats each; medians in ms", flush=True)
+    print("# excess: median of B's repeats over both turns - the same of A; A/A: |A's first median - A's second|; ok: excess <= A/A", flush=True)
     runs = []
     for tag, lib_path in (("A", parent_lib), ("B", None), ("A", parent_lib), ("B", None)):
         env = dict(os.environ)
         if lib_path:
             env["KMG_LIBRARY"] = os.path.abspath(lib_path)
-        else:
-            env.pop("KMG_LIBRARY", None)
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), str(reps), "--default-only"], env=env, capture_output=True, text=True,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), str(reps), "--child"], env=env, capture_output=True, text=True,
                            timeout=600)
-        line = [ln for ln in r.stdout.splitlines() if ln.startswith("DEFAULT ")]
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("CHILD ")]
         if r.returncode != 0 or not line:
             print(f"# child {tag} failed ({r.returncode}): {r.stderr[-400:]}", flush=True)
             sys.exit(1)
-        runs.append((tag, json.loads(line[0][8:])))
-    for key in runs[0][1]:
-        for tag, res in runs:
-            t = np.array(res[key]["ms"])
-            print(f"{key:>10s} {tag} pass median {np.median(t):9.3f} ms  min {t.min():9.3f}  max {t.max():9.3f}", flush=True)
-        same = len({res[key]["sha256"] for _, res in runs}) == 1
-        print(f"{key:>10s} outputs of A and B {'identical' if same else 'DIFFER'}", flush=True)
+        runs.append(json.loads(line[0][6:]))
+    print(f"{'route k pass':>24s} {'A':>9s} {'B':>9s} {'A':>9s} {'B':>9s} {'excess':>9s} {'A/A':>8s} {'ok':>4s}  outputs", flush=True)
+    for key in runs[0]:
+        med = [float(np.median(res[key]["ms"])) for res in runs]
+        excess = float(np.median(runs[1][key]["ms"] + runs[3][key]["ms"]) - np.median(runs[0][key]["ms"] + runs[2][key]["ms"]))
+        spread = abs(med[0] - med[2])
+        same = len({res[key]["sha256"] for res in runs}) == 1
+        print(f"{key:>24s} {med[0]:9.4f} {med[1]:9.4f} {med[2]:9.4f} {med[3]:9.4f} {excess:+9.4f} {spread:8.4f} {'yes' if excess <= spread else 'NO':>4s}  "
+              f"{'identical' if same else 'DIFFER'}", flush=True)
